@@ -1,10 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X-native CP-HNSW hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5|recall]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5|recall] [--full] [--dump-outputs DIR]
     (N > 1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
      ..., WORLD_SIZE must equal --gpus -- or on its own: bench.py then starts the N ranks itself, before it touches the
      GPU, and relays rank 0's line)
+
+A plain run does what the headline figure needs and nothing else: data and index, the batch-sets trial, W warm-up
+steps, the K timed steps, the outputs if --dump-outputs is given, and the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the workload).  --full adds every other measurement and check listed below.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy: `ids` (float64: the int64
+ids, exact below 2**53) and `dist` (float32) of the whole batch, a fixed seeded sample of its rows (`rows`) where that
+would exceed 64 MB; C5: the pass checksum and the estimates / lower bounds of its first 64 blocks.  The inputs are
+seeded, so two builds of the project can be compared output for output.  The search is deterministic on a given index,
+but the GPU builder is not (two fresh builds of the C2 index answer ~6 % of the queries differently).  So compare two
+builds on ONE index file: the same --workdir, where the first run caches the index under a key of data, size, bit
+width and BUILDER_VERSION.
 
 Default workload = BASELINE.json configs[1] (c2): SIFT1M-class synthetic data, 1M x 128 (D=128),
 4-bit RaBitQ codes, R=32, index built in-bench by this repo's GPU builder, k=10 (the reference's
@@ -24,7 +35,8 @@ Other configs (parity-backed lines for profiles/, not the driver's default):
   recall Gaussian 100k x 128, 2-bit, k=20: a workload where the reference algorithm meets recall@10 >= 0.95
   recall1m the same at SIFT1M scale (1M x 128): the gate leg of the default line
 
-The JSON line also carries
+With --full the JSON line also carries
+  * recall_at_10 / recall_target_met: the recall protocol, rank 0, before the timed region,
   * qps_at_recall_gate (c2, N = 1): the metric's gate, recall@10 >= 0.95, is not reachable for the reference algorithm
     on the SIFT-like data (our ids are the reference's bit for bit), so a short child run of the `recall1m` config --
     Gaussian data at the same scale, 1M x 128, 2-bit, k = 20, where it is -- is condensed into this object: QPS, recall,
@@ -135,16 +147,19 @@ def use_native_file(cfg, n):
     return int(os.environ.get("WORLD_SIZE", "1")) > 1 or n * (D * cfg["bits"] * 4 + 704) < 8e9
 
 
-def get_index_file(args, cfg, n, rank, local):
+def get_index_file(args, cfg, n, rank, local, need_base=True):
     """Rank 0 builds the index with this repo's builder (once per cache key) and writes it twice: as the reference's v2
     file (what the CPU baseline / parity check loads) and as the GPU-native file every rank loads -- mmap + two copies,
-    no per-vertex re-layout on eight ranks' host cores at once."""
+    no per-vertex re-layout on eight ranks' host cores at once.  The base vectors come back on rank 0 when `need_base`
+    or when they had to be generated for a build anyway, else None."""
     path = index_path(args, cfg, n)
     info = {"builder": "cphnsw_mi355x (this repo)", "build_s": None}
     X = None
     if rank == 0:
-        X = make_base(cfg, n)
-        if not (os.path.exists(path) and (os.path.exists(path + ".native") or not use_native_file(cfg, n))):
+        cached = os.path.exists(path) and (os.path.exists(path + ".native") or not use_native_file(cfg, n))
+        if need_base or not cached:
+            X = make_base(cfg, n)
+        if not cached:
             import cphnsw_mi355x
             t0 = time.time()
             idx = cphnsw_mi355x.CPIndex(cfg["dim"], cfg["bits"], device=local)
@@ -393,8 +408,10 @@ AFFINITY0 = None
 
 
 def child_line(args, extra, timeout):
-    """One more configuration in a fresh child process of this script; returns its JSON line (or raises)."""
+    """One more configuration in a fresh child process of this script, with its own --full measurements; returns its
+    JSON line (or raises)."""
     import subprocess
+    extra = ["--full"] + extra
     cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--workdir", args.workdir, "--no-extra-legs"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -487,7 +504,7 @@ def config_legs(args, t_start, failed):
             failed.append("c4")
     else:
         skipped.append({"leg": "c4", "elapsed_s": round(elapsed, 1), "deadline_s": args.c4_deadline,
-                        "run_it_with": "python bench.py --config c4"})
+                        "run_it_with": "python bench.py --full --config c4"})
     return out, skipped
 
 
@@ -569,6 +586,27 @@ def timed_region(step, steps, warmup, serial, use_dist, dist, sync, dev, marks_l
     return el, ids, d
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 or float64 only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def batch_outputs(ids, d):
+    """A batch's (ids, distances) as dump arrays: ids as float64 (exact: ids are far below 2**53, -1 = empty slot); where
+    the whole batch exceeds DUMP_BYTES, a fixed seeded sample of its rows, ascending, and the row numbers (`rows`)."""
+    rows, k = ids.shape
+    if rows * k * 12 <= DUMP_BYTES:
+        return {"ids": ids.astype(np.float64), "dist": d.astype(np.float32)}
+    sel = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // (k * 12 + 8), replace=False))
+    return {"ids": ids[sel].astype(np.float64), "dist": d[sel].astype(np.float32), "rows": sel.astype(np.float64)}
+
+
 def bench_stream_c5(args, local, world, rank, use_dist, dist, dev):
     """C5: streaming FastScan over the largest D=1024 / 2-bit block set that fits this GPU.
     Blocks only (random valid codes / aux), one encoded query, both N-bit stages per block."""
@@ -585,7 +623,7 @@ def bench_stream_c5(args, local, world, rank, use_dist, dist, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ms, _ = stream.run(args.steps)
+    ms, checksum = stream.run(args.steps)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -598,24 +636,9 @@ def bench_stream_c5(args, local, world, rank, use_dist, dist, dev):
         return
     dps = world * n_blocks * 32 * args.steps / elapsed
     gbs = n_blocks * 32 * bpd / (ms * 1e-3) / 1e9
-    # parity of this instantiation on a sample of its own blocks against the oracle
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from oracle_lib import Oracle
-    orc = Oracle()
-    L = orc.layout(D, bits)
-    nbb = L[0] - L[1]
-    first = max(0, n_blocks - 64)
-    blocks, lut, qp, dqp = stream.export(first, 64, nbb)
-    est, lower = stream.eval(first, 64)
-    ok = True
-    for b in range(64):
-        nb = blocks.reshape(64, nbb)[b]
-        planes = nb[L[2]:L[2] + bits * D * 4].reshape(bits, D // 8, 32)
-        s, m = orc.fastscan_nbit(D, bits, lut, planes)
-        e, lo = orc.convert_nbit(D, bits, qp, s, m, nb[L[3]:L[3] + 128].view(np.float32),
-                                 nb[L[4]:L[4] + 128].view(np.float32), nb[L[5]:L[5] + 128].view(np.float32),
-                                 nb[L[6]:L[6] + 64].view(np.uint16), nb[L[7]:L[7] + 64].view(np.uint16), dqp)
-        ok = ok and est[b].tobytes() == e.tobytes() and lower[b].tobytes() == lo.tobytes()
+    if args.dump_outputs:
+        est0, lower0 = stream.eval(0, min(64, n_blocks))
+        dump_outputs(args.dump_outputs, {"checksum": np.array([checksum], np.float64), "est": est0, "lower": lower0})
     out = {
         "metric": "fastscan_dist_per_s (streaming FastScan, both N-bit stages, vs HBM roofline)",
         "value": dps, "unit": "distances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -631,8 +654,27 @@ def bench_stream_c5(args, local, world, rank, use_dist, dist, dev):
                      "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "kernel_ms": ms,
                      "traffic": n_blocks * stride / (ms * 1e-3) / 1e9,
                      "traffic_note": "the kernel reads every block once: n_blocks x stride (PMC-calibrated, profiles/r1_pmc_summary.md)"},
-        "parity_vs_oracle": {"blocks": 64, "est_and_lower_bit_identical": bool(ok)},
     }
+    if args.full:
+        # parity of this instantiation on a sample of its own blocks against the oracle
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from oracle_lib import Oracle
+        orc = Oracle()
+        L = orc.layout(D, bits)
+        nbb = L[0] - L[1]
+        first = max(0, n_blocks - 64)
+        blocks, lut, qp, dqp = stream.export(first, 64, nbb)
+        est, lower = stream.eval(first, 64)
+        ok = True
+        for b in range(64):
+            nb = blocks.reshape(64, nbb)[b]
+            planes = nb[L[2]:L[2] + bits * D * 4].reshape(bits, D // 8, 32)
+            s, m = orc.fastscan_nbit(D, bits, lut, planes)
+            e, lo = orc.convert_nbit(D, bits, qp, s, m, nb[L[3]:L[3] + 128].view(np.float32),
+                                     nb[L[4]:L[4] + 128].view(np.float32), nb[L[5]:L[5] + 128].view(np.float32),
+                                     nb[L[6]:L[6] + 64].view(np.uint16), nb[L[7]:L[7] + 64].view(np.uint16), dqp)
+            ok = ok and est[b].tobytes() == e.tobytes() and lower[b].tobytes() == lo.tobytes()
+        out["parity_vs_oracle"] = {"blocks": 64, "est_and_lower_bit_identical": bool(ok)}
     print(json.dumps(out), flush=True)
 
 
@@ -754,6 +796,12 @@ def main():
                          "untimed trial of 2 and 4 picks the faster")
     ap.add_argument("--slots", type=int, default=int(os.environ.get("CPH_BENCH_SLOTS", 0)), help="resident query slots per batch (0 = automatic)")
     ap.add_argument("--workdir", default=os.environ.get("CPH_BENCH_DIR", "/tmp/cph_bench"))
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement and check beyond the headline figure: recall protocol, full queue, host API, kernel "
+                         "alone + roofline, serial rate, FastScan stream, CPU baseline + parity, gate and config legs (c2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB); "
+                         "compare builds of the project on one cached index (same --workdir)")
     ap.add_argument("--stub-search", action="store_true", help=argparse.SUPPRESS)   # test hook: stub_main
     args = ap.parse_args()
     spawn_ranks_if_asked(args)      # N > 1 without a launcher: start the ranks and relay (never returns then)
@@ -808,7 +856,7 @@ def main():
     # ---- data, index ----------------------------------------------------------------------
     nq_total = nq_gpu * world
     Q = make_queries(cfg, n, nq_total)
-    path, build_info, X = get_index_file(args, cfg, n, rank, local)
+    path, build_info, X = get_index_file(args, cfg, n, rank, local, need_base=args.full)
     if use_dist:
         dist.barrier()
     index = cphnsw_mi355x.CPIndex(dim, bits, device=local)
@@ -822,7 +870,7 @@ def main():
 
     # ---- recall protocol (rank 0, outside the timed region) --------------------------------
     recall = {}
-    if rank == 0 and X is not None:
+    if args.full and rank == 0 and X is not None:
         nrq = min(args.recall_queries, len(Q))
         gt_d = ground_truth(X, Q[:nrq], local)
         for kk in sorted({10, 20, 100, k_run}):
@@ -877,7 +925,59 @@ def main():
     qps = nq_total * args.steps / elapsed
     rank_rates = per_rank_qps(dist, use_dist, dev, nq_gpu, args.steps)
     log(f"[bench] rank {rank}: {qps:.0f} q/s")
+    if args.dump_outputs:
+        ids_out, d_out = ids, d
+        if use_dist:       # what the caller receives: the whole batch, every rank's block gathered inside the last step
+            pk = next(p for p in packs if p.ids.data_ptr() == ids.data_ptr())
+            nb = nq_gpu * k_run * 8
+            ids_out = pk.all[:, :nb].contiguous().view(torch.int64).view(world * nq_gpu, k_run)
+            d_out = pk.all[:, nb:].contiguous().view(torch.float32).view(world * nq_gpu, k_run)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, batch_outputs(ids_out.cpu().numpy(), d_out.cpu().numpy()))
 
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "qps (search_batch_device, layer-0 hot path end to end) + fastscan_dist_per_s",
+            "value": qps,
+            "unit": "queries/s",
+            "n_gpus": world,
+            "rccl_ranks": dist.get_world_size() if use_dist else 1,
+            "per_rank_qps": rank_rates,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32 popcount / f32",
+            "data": "synthetic",
+            "config": {"workload": f"{cfg['label']}: {n}x{dim} f32 (D={D}), {bits}-bit RaBitQ FastScan + exact-L2 "
+                                   f"rerank, R=32, k={k_run}, {nq_gpu} queries per GPU resident in HBM",
+                       "name": args.config, "n_index": n, "dim": dim, "bits": bits, "k": k_run,
+                       "nq_per_gpu": nq_gpu, "index_builder": build_info["builder"],
+                       "index_build_s": build_info["build_s"],
+                       "step": ("one stream, each step waits for the previous one" if args.serial else
+                                f"steps rotate over {n_streams} HIP streams (as many batch scratch sets" +
+                                (", half of the resident slots per batch: two batches run side by side, the next ones "
+                                 "fill their drain)" if n_streams > 2 else "): a step starts while the previous one drains")) +
+                               ("; ends with the RCCL all-gather" if use_dist else ""),
+                       "batch_sets": n_streams,
+                       "batch_sets_trial_ms_per_step": ({str(ns): round(1e3 * t, 4) for ns, t in tuning.items()} if tuning else None),
+                       "parallelism": f"query-sharded x{world}, index replicated"},
+        }
+    if not args.full:
+        if rank == 0:
+            out["timed_region_s"] = elapsed
+            out["index_load_s"] = load_s
+            out["run_s"] = round(time.time() - T_START, 1)
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below measures or checks more than the headline figure ----------------
     # ---- the same kernel with a full queue (rank 0, c2 / c4): one launch over ten batches' worth of DISTINCT queries.  The
     # config's own batch is as long as its longest query (a chain of dependent expansions); this launch shows the rate the
     # kernel sustains once that tail is amortised -- reported next to `roofline`, never instead of it.
@@ -945,34 +1045,7 @@ def main():
         ids_np = ids.cpu().numpy()
         kname = f"search_kernel<{bits},{D if D in (128, 1024) else 0}>"
         gate = bool(recall and recall.get(f"k{k_run}_dedup", 0.0) >= 0.95)
-        out = {
-            "metric": "qps (search_batch_device, layer-0 hot path end to end) + fastscan_dist_per_s",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "rccl_ranks": dist.get_world_size() if use_dist else 1,
-            "per_rank_qps": rank_rates,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32 popcount / f32",
-            "data": "synthetic",
-            "config": {"workload": f"{cfg['label']}: {n}x{dim} f32 (D={D}), {bits}-bit RaBitQ FastScan + exact-L2 "
-                                   f"rerank, R=32, k={k_run}, {nq_gpu} queries per GPU resident in HBM",
-                       "name": args.config, "n_index": n, "dim": dim, "bits": bits, "k": k_run,
-                       "nq_per_gpu": nq_gpu, "index_builder": build_info["builder"],
-                       "index_build_s": build_info["build_s"],
-                       "step": ("one stream, each step waits for the previous one" if args.serial else
-                                f"steps rotate over {n_streams} HIP streams (as many batch scratch sets" +
-                                (", half of the resident slots per batch: two batches run side by side, the next ones "
-                                 "fill their drain)" if n_streams > 2 else "): a step starts while the previous one drains")) +
-                               ("; ends with the RCCL all-gather" if use_dist else ""),
-                       "batch_sets": n_streams,
-                       "batch_sets_trial_ms_per_step": ({str(ns): round(1e3 * t, 4) for ns, t in tuning.items()} if tuning else None),
-                       "parallelism": f"query-sharded x{world}, index replicated"},
+        out.update({
             "recall_at_10": recall,
             "recall_target_met": gate,
             "recall_note": ("recall@10 >= 0.95 holds at this k" if gate else
@@ -1005,7 +1078,7 @@ def main():
             "search_stats": stats,
             "index_load_s": load_s,
             "dup_slots_per_query": float((ids_np[:, 1:] == ids_np[:, :-1]).sum(1).mean()),
-        }
+        })
         if not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args, cfg, path, Q, stream, k_run, index)
         failed, skipped = [], []

@@ -1,11 +1,11 @@
 #!/bin/bash
-# the driver's default command, as the driver runs it (fresh box: builds every index), with its wall time
+# the full benchmark (bench.py --full: every leg; a fresh box builds every index), with its wall time
 export TMPDIR=/tmp
 O=${1:-gpurun_out/fullbench}; mkdir -p $O
 ( while true; do sleep 60; echo "[keepalive] $(date +%T)" >> $O/progress.log; done ) &
 KA=$!
 t0=$(date +%s)
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; rc=$?
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; rc=$?
 kill $KA
 echo "rc=$rc wall=$(( $(date +%s) - t0 )) s"
 python3 - <<PY

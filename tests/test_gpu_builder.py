@@ -5,6 +5,8 @@ is (i) format/semantic: an index written by our builder loads in the compiled re
 reference's CPU search on it equals our GPU search bit for bit, and (ii) statistical: graph
 quality (recall of the same search protocol) is not worse than the reference-built index'.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -193,77 +195,77 @@ def test_built_index_is_valid_for_reference_and_search_matches(tmp_path, bits, n
     assert np.array_equal(ids1, ids2) and d1.tobytes() == d2.tobytes()
 
 
+def quality_data_20k():
+    """Clustered, integer-valued 20k x 128 with 200 queries near the cluster centres."""
+    rng = np.random.default_rng(5)
+    X, cent = sift_like(rng, 20000, 128, 20)
+    Q = (cent[rng.integers(0, 20, 200)] + rng.normal(0, 12, (200, 128))).astype(np.float32)
+    return X, Q
+
+
+def quality_data_100k():
+    """BASELINE.md 2.2's generator at 100k x 128 (1,000 clusters), 300 integer-valued queries."""
+    rng = np.random.default_rng(11)
+    n, dim, nq = 100_000, 128, 300
+    X, cent = sift_like(rng, n, dim, 1000)
+    Q = np.clip(np.round(cent[rng.integers(0, 1000, nq)] + rng.normal(0, 12, (nq, dim))), 0, 218).astype(np.float32)
+    return X, Q
+
+
+def input_rows(path, X):
+    """internal id -> input row of every vertex of an index over X (duplicates map to any equal row: distances equal)."""
+    n, dim = X.shape
+    raw = index_rows(path, n, dim, 128)
+    key = {X[i].tobytes(): i for i in range(n)}
+    return [key[raw[i].tobytes()] for i in range(n)]
+
+
+def reference_recall(name):
+    """What the compiled reference's own build + search reached on the same seeded data (tests/golden/make_golden_quality.py)."""
+    import json
+    from golden_util import GOLDEN_DIR
+    with open(os.path.join(GOLDEN_DIR, "ref_graph_quality.json")) as f:
+        return json.load(f)[name]
+
+
 def test_graph_quality_not_worse_than_reference(tmp_path):
     import cphnsw_mi355x
-    from oracle_lib import ref_available, ref_module
-    if not ref_available():
-        pytest.skip("oracle/_ref not present")
-    rng = np.random.default_rng(5)
-    n, dim, bits = 20000, 128, 4
-    X, cent = sift_like(rng, n, dim, 20)
-    Q = (cent[rng.integers(0, 20, 200)] + rng.normal(0, 12, (200, dim))).astype(np.float32)
+    X, Q = quality_data_20k()
+    dim, bits = X.shape[1], 4
     gt = brute_topk(X, Q, 10)
     mine = cphnsw_mi355x.CPIndex(dim, bits)
     mine.build(X)
     mine.finalize()
     pm = str(tmp_path / "mine.idx")
     mine.save(pm)
-    ref = ref_module().CPIndex(dim, bits)
-    ref.build(X)
-    ref.finalize()
-    pr = str(tmp_path / "ref.idx")
-    ref.save(pr)
-
-    def rows_of(path):
-        raw = index_rows(path, n, dim, 128)
-        # map stored vectors back to input rows (duplicates map to any equal row: distances equal)
-        key = {X[i].tobytes(): i for i in range(n)}
-        return [key[raw[i].tobytes()] for i in range(n)]
-
     ids_m, _ = mine.search_batch(Q, 20)
-    ids_r, _ = ref.search_batch(Q, 20)
-    rec_m = dedup_recall(ids_m, rows_of(pm), gt, X)
-    rec_r = dedup_recall(ids_r, rows_of(pr), gt, X)
+    rec_m = dedup_recall(ids_m, input_rows(pm, X), gt, X)
+    rec_r = reference_recall("q20k_b4")["k20"]
     print("recall@10 (dedup of k=20): ours", rec_m, "reference", rec_r)
     assert rec_m >= rec_r - 0.05
 
 
 def test_graph_quality_at_benchmark_scale_tracks_the_reference(tmp_path):
     """The gate that would catch a graph-quality regression at a size that is benchmarked: clustered, integer-valued
-    100k x 128 at 4 bits (BASELINE.md 2.2's generator: 1,000 clusters), built by this repo's GPU builder and by the
-    compiled reference (it can finalize up to ~230k vertices, finding F9); same search protocol on both; dedup
-    recall@10 of k = 20 and of k = 100 must be within 0.03 of the reference's."""
+    100k x 128 at 4 bits (BASELINE.md 2.2's generator: 1,000 clusters), built by this repo's GPU builder, against what
+    the compiled reference's build reached on the same data (it can finalize up to ~230k vertices, finding F9; stored
+    in tests/golden/ref_graph_quality.json); same search protocol on both; dedup recall@10 of k = 20 and of k = 100
+    must be within 0.03 of the reference's."""
     import cphnsw_mi355x
-    from oracle_lib import ref_available, ref_module
-    if not ref_available():
-        pytest.skip("oracle/_ref not present")
-    rng = np.random.default_rng(11)
-    n, dim, bits, nq = 100_000, 128, 4, 300
-    X, cent = sift_like(rng, n, dim, 1000)
-    Q = np.clip(np.round(cent[rng.integers(0, 1000, nq)] + rng.normal(0, 12, (nq, dim))), 0, 218).astype(np.float32)
+    X, Q = quality_data_100k()
+    dim, bits = X.shape[1], 4
     gt = brute_topk(X, Q, 10)
     mine = cphnsw_mi355x.CPIndex(dim, bits)
     mine.build(X)
     mine.finalize()
     pm = str(tmp_path / "mine.idx")
     mine.save(pm)
-    ref = ref_module().CPIndex(dim, bits)
-    ref.build(X)
-    ref.finalize()
-    pr = str(tmp_path / "ref.idx")
-    ref.save(pr)
-    key = {X[i].tobytes(): i for i in range(n)}
-
-    def rows_of(path):
-        raw = index_rows(path, n, dim, 128)
-        return [key[raw[i].tobytes()] for i in range(n)]
-
-    rm, rr = rows_of(pm), rows_of(pr)
+    rm = input_rows(pm, X)
+    ref = reference_recall("q100k_b4")
     for k in (20, 100):
         ids_m, _ = mine.search_batch(Q, k)
-        ids_r, _ = ref.search_batch(Q, k)
         rec_m = dedup_recall(ids_m, rm, gt, X)
-        rec_r = dedup_recall(ids_r, rr, gt, X)
+        rec_r = ref[f"k{k}"]
         print(f"100k clustered, 4-bit: dedup recall@10 of k={k}: ours {rec_m:.4f}, reference {rec_r:.4f}")
         assert rec_m >= rec_r - 0.03, (k, rec_m, rec_r)
     # an index of this size (n + 1 beyond the default per-slot capacity) is where the copy-free small-batch path runs:

@@ -252,16 +252,29 @@ def test_launch_order_and_per_query_work(cph, oracle, gold, name, bits):
 
 
 def test_large_index_against_oracle(cph, oracle, tmp_path):
-    """Bigger graph (many thousands of expansions per query): GPU vs the oracle on an index built
-    by the compiled reference when it is available on this box."""
+    """Bigger graph (many thousands of expansions per query): GPU vs the oracle on an index built by this
+    repo's builder, ids and distance bits; and vs the compiled reference's own search on an index the
+    reference built, when oracle/_ref is on this box."""
     from oracle_lib import ref_available, ref_module
-    if not ref_available():
-        pytest.skip("oracle/_ref not present on this box")
-    m = ref_module()
     rng = np.random.default_rng(77)
     n, dim = 20000, 128
     X = rng.standard_normal((n, dim)).astype(np.float32)
     Q = rng.standard_normal((64, dim)).astype(np.float32)
+    for bits in (1, 4):
+        ix = cph.CPIndex(dim, bits)
+        ix.build(X)
+        ix.finalize()
+        p = str(tmp_path / f"big_mine_{bits}.idx")
+        ix.save(p)
+        oi = oracle.load(p)
+        for k in (10, 100):
+            oids, od, _ = oi.search_batch(Q, k)
+            ids, d = ix.search_batch(Q, k)
+            assert np.array_equal(ids, oids), (bits, k)
+            assert _beq(d, od), (bits, k)
+    if not ref_available():
+        return
+    m = ref_module()
     for bits in (1, 4):
         ridx = m.CPIndex(dim, bits)
         ridx.build(X)

@@ -25,6 +25,20 @@ DATASETS = {
                 variants=("plain", "gamma_tight", "shortcount")),
     "g1024": dict(n=160, dim=960, D=1024, bits=(2,), kind="gauss", seed=104,
                   variants=("plain", "affine", "shortcount")),
+    # The padded dimensions the search kernel serves through its generic instantiation (runtime layout): D = 32 and 64
+    # take the dword ("small") block layout, D = 256, 512 and 2048 the wide one with runtime NH / CPL.  dim < D
+    # everywhere, so the query and vector padding is exercised too.  Their goldens live in golden_dims*.npz
+    # (make_golden_dims.py); n is capped so that every index file stays under 1 MiB.
+    "g32": dict(n=300, dim=24, D=32, bits=(1, 4), kind="gauss", seed=105,
+                variants=("plain", "gamma", "shortcount"), golden="golden_dims.npz"),
+    "g64": dict(n=300, dim=50, D=64, bits=(2, 4), kind="gauss", seed=106,
+                variants=("plain", "bignop", "shortcount"), golden="golden_dims.npz"),
+    "g256": dict(n=160, dim=200, D=256, bits=(1, 4), kind="gauss", seed=107,
+                 variants=("plain", "gamma", "bignop", "shortcount"), golden="golden_dims.npz"),
+    "g512": dict(n=160, dim=300, D=512, bits=(2,), kind="gauss", seed=108,
+                 variants=("plain", "gamma", "shortcount"), golden="golden_dims.npz"),
+    "g2048": dict(n=88, dim=1536, D=2048, bits=(1,), kind="sift", seed=109,
+                  variants=("plain", "gamma", "shortcount"), golden="golden_dims.npz"),
 }
 NQ = 24
 
@@ -138,11 +152,53 @@ def fixture_path(name, bits, variant="plain"):
     return p
 
 
+GOLDEN_FILES = ("golden.npz", "golden_dims.npz", "golden_dims_fastscan.npz")
+
+
+class MergedGolden:
+    """Read-only view over several .npz files as one key space; a key held by two files is an error."""
+
+    def __init__(self, paths):
+        self._npz = [np.load(p) for p in paths]
+        self._where = {}
+        for z in self._npz:
+            for k in z.files:
+                if k in self._where:
+                    raise ValueError(f"golden key {k!r} is in more than one file")
+                self._where[k] = z
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __iter__(self):
+        return iter(self.files)
+
+    def __len__(self):
+        return len(self.files)
+
+
 _G = None
+_GB = None
+
+
+def enc_golden(dim, D, bits):
+    """Edge-encoder goldens of one shape as per-case lists (parent, nbrs, values, aux, pops): golden_build.npz holds
+    ENC/<dim>/<D>/b<bits>/{parent,nbrs,...}; golden_dims.npz shares parent / nbrs between the bit widths."""
+    global _GB
+    if _GB is None:
+        _GB = np.load(os.path.join(GOLDEN_DIR, "golden_build.npz"))
+    k = f"ENC/{dim}/{D}/b{bits}"
+    src = _GB if f"{k}/values" in _GB.files else golden()
+    shared = f"ENC/{dim}/{D}" if f"ENC/{dim}/{D}/parent" in src else k
+    return src[f"{shared}/parent"], src[f"{shared}/nbrs"], src[f"{k}/values"], src[f"{k}/aux"], src[f"{k}/pops"]
 
 
 def golden():
     global _G
     if _G is None:
-        _G = np.load(os.path.join(GOLDEN_DIR, "golden.npz"))
+        _G = MergedGolden([os.path.join(GOLDEN_DIR, f) for f in GOLDEN_FILES])
     return _G

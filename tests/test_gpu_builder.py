@@ -53,23 +53,24 @@ def index_rows(path, n, dim, D):
     return raw
 
 
-ENC_SHAPES = ((10, 16), (50, 64), (96, 128), (128, 128), (300, 512), (960, 1024))
+ENC_SHAPES = ((10, 16), (50, 64), (96, 128), (128, 128), (300, 512), (960, 1024), (24, 32), (200, 256), (1536, 2048))
 
 
 @pytest.mark.parametrize("dim,D", ENC_SHAPES)
 @pytest.mark.parametrize("bits", [1, 2, 4])
-def test_gpu_edge_encoder_matches_reference(gold_build, oracle, dim, D, bits):
+def test_gpu_edge_encoder_matches_reference(oracle, dim, D, bits):
     """The kernel finalize() encodes every edge with (one lane per edge, sequential coordinate descent on
     LDS rows) against what the reference's encoder computed for the same parent / neighbours: code values,
     nop, ip_qo, ip_cp (float bits) and both popcounts -- including an exact-duplicate neighbour (nop = 0)."""
     import cphnsw_mi355x
-    k = f"ENC/{dim}/{D}/b{bits}"
-    for c in range(len(gold_build[f"{k}/parent"])):
-        p, nb = gold_build[f"{k}/parent"][c], gold_build[f"{k}/nbrs"][c]
+    from golden_util import enc_golden
+    P, N, V, A, S = enc_golden(dim, D, bits)
+    for c in range(len(P)):
+        p, nb = P[c], N[c]
         v, a, s = cphnsw_mi355x.encode_edges(p, nb, bits)
-        assert np.array_equal(v, gold_build[f"{k}/values"][c]), (dim, bits, c, int((v != gold_build[f"{k}/values"][c]).sum()))
-        assert a.tobytes() == gold_build[f"{k}/aux"][c].tobytes(), (dim, bits, c)
-        assert np.array_equal(s, gold_build[f"{k}/pops"][c])
+        assert np.array_equal(v, V[c]), (dim, bits, c, int((v != V[c]).sum()))
+        assert a.tobytes() == A[c].tobytes(), (dim, bits, c)
+        assert np.array_equal(s, S[c])
         # fewer than 32 edges, and the oracle on fresh inputs
         rng = np.random.default_rng(c + dim)
         m = int(rng.integers(1, 32))
@@ -162,7 +163,11 @@ def test_knn_symmetric_self_join_is_exact(n, dim, kind, tmp_path):
 
 
 @pytest.mark.parametrize("bits,n,dim", [(1, 6000, 128), (2, 6000, 128), (4, 6000, 128), (4, 2500, 960),
-                                        (2, 3000, 96), (4, 1200, 10)])
+                                        (2, 3000, 96), (4, 1200, 10),
+                                        # the generic search instantiation: D = 32, 256, 512 and 2048, with dims
+                                        # far below D and (500, 2000) within its last 128 padded dims
+                                        (4, 1500, 24), (1, 1200, 200), (2, 1000, 300), (2, 600, 1536), (4, 600, 1536),
+                                        (2, 800, 500), (1, 500, 2000)])
 def test_built_index_is_valid_for_reference_and_search_matches(tmp_path, bits, n, dim):
     import cphnsw_mi355x
     from oracle_lib import Oracle, ref_available, ref_module

@@ -168,10 +168,19 @@ def test_stream_blocks_match_oracle(cph, oracle, D, bits):
 
 
 @pytest.mark.parametrize("name,bits,D,dim", [("g128", 1, 128, 128), ("sift96", 4, 128, 96),
-                                             ("g16", 2, 16, 10), ("g1024", 2, 1024, 960)])
+                                             ("g16", 2, 16, 10), ("g1024", 2, 1024, 960),
+                                             ("g64", 2, 64, 50), ("g256", 1, 256, 200), ("g2048", 1, 2048, 1536),
+                                             (None, 1, 32, 32), (None, 2, 512, 512)])
 def test_device_query_encoder_matches_reference(cph, gold, name, bits, D, dim):
-    """The on-device rotation + LUT scalars + coefficients against the reference's vectors."""
-    ix = _load(cph, name, bits)
+    """The on-device rotation + LUT scalars + coefficients against the reference's vectors, at every E/ shape of the
+    goldens.  No fixture has dim 32 or 512: those two encode on a small index built here (the encoder depends on D only)."""
+    if name is None:
+        rng = np.random.default_rng(D)
+        ix = cph.CPIndex(dim, bits)
+        ix.build(rng.standard_normal((400, dim)).astype(np.float32))
+        ix.finalize()
+    else:
+        ix = _load(cph, name, bits)
     q = gold[f"E/{D}/{dim}/q"]
     for i in range(len(q)):
         lut, co = ix.encode_query(q[i])
@@ -230,7 +239,22 @@ def test_capacity_overflow_rerun_is_exact(cph, gold):
     assert np.array_equal(ids, gold["S/g128/b2/plain/k10/ids"]) and _beq(d, gold["S/g128/b2/plain/k10/d"])
 
 
-@pytest.mark.parametrize("name,bits", [("g128", 4), ("sift96", 4), ("g16", 1)])
+@pytest.mark.parametrize("name,bits", [("g256", 1), ("g512", 2)])
+def test_capacity_overflow_rerun_at_generic_wide_d(cph, gold, name, bits):
+    """The same overflow -> re-run path on the generic instantiation's wide layout (runtime NH / CPL).  A query
+    overflows when its beam has no room for an expansion's new ids; by the oracle's counters every g256 / 1-bit query
+    pushes 130 or more vertices into its beam at k = 10, g512 / 2-bit queries 58 to 86."""
+    ix = _load(cph, name, bits)
+    ix.set_search_params(slots=8, beam_capacity=64)
+    Q = gold[f"Q/{name}"]
+    for k in (10, 100):
+        ids, d = ix.search_batch(Q, k)
+        assert ix.last_search_stats()["rerun_queries"] > 0, (name, k)
+        assert np.array_equal(ids, gold[f"S/{name}/b{bits}/plain/k{k}/ids"]), (name, k)
+        assert _beq(d, gold[f"S/{name}/b{bits}/plain/k{k}/d"]), (name, k)
+
+
+@pytest.mark.parametrize("name,bits", [("g128", 4), ("sift96", 4), ("g16", 1), ("g64", 4), ("g256", 1)])
 def test_launch_order_and_per_query_work(cph, oracle, gold, name, bits):
     """More queries than resident slots: the closest-entry-first launch order changes nothing in
     the results, and the per-query expansion counts equal the oracle's counters."""
@@ -539,7 +563,7 @@ def test_device_batch_validates_out_buffers(cph, gold):
         ix.search_batch_device(Q.cpu(), 10)
 
 
-@pytest.mark.parametrize("name,bits", [("g128", 4), ("g16", 2), ("g1024", 2)])
+@pytest.mark.parametrize("name,bits", [("g128", 4), ("g16", 2), ("g1024", 2), ("g256", 4), ("g2048", 1)])
 def test_native_file_roundtrip(cph, gold, tmp_path, name, bits):
     """GPU-native index file: v2 -> native -> load_native gives the same search results and stored vectors,
     and a v2 file written from it is searched identically (by us; and it has the v2 file's size)."""

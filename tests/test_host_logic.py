@@ -13,7 +13,8 @@ def _lib():
     return _lib
 
 
-@pytest.mark.parametrize("name,bits", [("g128", 1), ("g128", 4), ("sift96", 4), ("g16", 2), ("g1024", 2)])
+@pytest.mark.parametrize("name,bits", [("g128", 1), ("g128", 4), ("sift96", 4), ("g16", 2), ("g1024", 2)]
+                         + [(n, b) for n, s in DATASETS.items() if s.get("golden") == "golden_dims.npz" for b in s["bits"]])
 def test_index_reader_writer_is_byte_identical(tmp_path, name, bits):
     L = _lib()
     src = fixture_path(name, bits)
@@ -120,7 +121,8 @@ def test_repacker_layout_and_roundtrip(oracle, D, bits):
     assert np.array_equal(back, expect)
 
 
-@pytest.mark.parametrize("D,dim", [(16, 10), (128, 128), (128, 96), (1024, 960), (2048, 1536)])
+@pytest.mark.parametrize("D,dim", [(16, 10), (128, 128), (128, 96), (1024, 960), (2048, 1536),
+                                   (32, 32), (64, 50), (256, 200), (512, 512)])
 def test_host_query_encoder_matches_reference(gold, D, dim):
     L = _lib()
     q = gold[f"E/{D}/{dim}/q"]

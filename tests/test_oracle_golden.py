@@ -6,7 +6,11 @@ encoder and the full search results (ids AND distances, duplicates and ties incl
 import numpy as np
 import pytest
 
-from golden_util import DATASETS, KS, SHORT_COUNTS, fixture_path
+from golden_util import DATASETS, KS, SHORT_COUNTS, enc_golden, fixture_path
+
+# D = 16, 128, 1024 are pinned by golden.npz, the padded dimensions of the generic search instantiation by
+# golden_dims*.npz (tests/golden/make_golden_dims.py)
+F_DIMS = [16, 128, 1024, 32, 64, 256, 512, 2048]
 
 
 def _beq(a, b):
@@ -24,7 +28,7 @@ def test_query_encoder(oracle, gold, D, dim):
         assert _beq(rot, gold[f"E/{D}/{dim}/rot"][i])
 
 
-@pytest.mark.parametrize("D", [16, 128, 1024])
+@pytest.mark.parametrize("D", F_DIMS)
 @pytest.mark.parametrize("bits", [1, 2, 4])
 def test_fastscan_block(oracle, gold, D, bits):
     k = f"F/{D}/b{bits}"
@@ -66,7 +70,7 @@ def test_fastscan_block(oracle, gold, D, bits):
                         assert _beq(got[:cnt], gold[f"{k}/c{cnt}/{name}"][a, c, i, :cnt]), (D, bits, cnt, name)
 
 
-@pytest.mark.parametrize("D", [16, 128, 1024])
+@pytest.mark.parametrize("D", F_DIMS)
 def test_exact_arithmetic(oracle, gold, D):
     a, b = gold[f"X/{D}/a"], gold[f"X/{D}/b"]
     for i in range(len(a)):
@@ -110,17 +114,17 @@ def test_load_errors(oracle, tmp_path):
         oracle.load(str(tmp_path / "missing.idx"))
 
 
-ENC_SHAPES = ((10, 16), (50, 64), (96, 128), (128, 128), (300, 512), (960, 1024))
+ENC_SHAPES = ((10, 16), (50, 64), (96, 128), (128, 128), (300, 512), (960, 1024), (24, 32), (200, 256), (1536, 2048))
 
 
 @pytest.mark.parametrize("dim,D", ENC_SHAPES)
 @pytest.mark.parametrize("bits", [1, 2, 4])
-def test_edge_encoder(oracle, gold_build, dim, D, bits):
+def test_edge_encoder(oracle, dim, D, bits):
     """Data-side encoder (per-edge RaBitQ / CAQ codes, nop, ip_qo, ip_cp, popcounts): the oracle's
     restatement against what the reference computed, code values and float bits."""
-    k = f"ENC/{dim}/{D}/b{bits}"
-    for c in range(len(gold_build[f"{k}/parent"])):
-        v, a, s = oracle.encode_edges(gold_build[f"{k}/parent"][c], gold_build[f"{k}/nbrs"][c], D, bits)
-        assert np.array_equal(v, gold_build[f"{k}/values"][c])
-        assert _beq(a, gold_build[f"{k}/aux"][c])
-        assert np.array_equal(s, gold_build[f"{k}/pops"][c])
+    P, N, V, A, S = enc_golden(dim, D, bits)
+    for c in range(len(P)):
+        v, a, s = oracle.encode_edges(P[c], N[c], D, bits)
+        assert np.array_equal(v, V[c])
+        assert _beq(a, A[c])
+        assert np.array_equal(s, S[c])

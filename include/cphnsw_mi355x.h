@@ -139,6 +139,29 @@ int cph_search_batch_device(cph_index* h, const float* d_queries, uint64_t n, ui
 /* Blocks the calling host thread until every batch enqueued on this handle has finished. */
 int cph_synchronize(cph_index* h);
 
+/* ---- filtered search ------------------------------------------------------------- */
+/* An allowed-id bitmap, uploaded once to the handle's device: bit (id & 31) of words[id >> 5] set = id may be
+ * returned.  Ids are the internal (post-reorder) ids the searches return.  n_bits must equal the size of the index
+ * the filter is used with (checked at every search); bits behind n_bits are ignored.  The filter records its
+ * popcount: a search with no id allowed returns padding without launching anything. */
+typedef struct cph_filter cph_filter;
+int cph_filter_create(cph_index* h, const uint32_t* words, uint64_t n_bits, cph_filter** out);
+/* Waits for the filter's device (batches enqueued with cph_search_batch_device_filtered may still read the
+ * bitmap), then frees it.  NULL is a no-op. */
+int cph_filter_destroy(cph_filter* f);
+/* cph_search_batch / cph_search_batch_device restricted to the allowed ids: the reference search in which only
+ * allowed ids may enter the result heap (its nn.push at the popped vertex, the warm-up and the reranked neighbours,
+ * gated); every other step is unchanged -- vertices outside the set are still estimated, reranked, pushed into the
+ * beam and expanded, and the warm-up, the lower-bound pruning, DABS and the gamma termination follow the result
+ * heap of allowed ids.  Rows with fewer than k allowed ids reached are padded with -1 / FLT_MAX.  f = NULL is the
+ * unfiltered call; a filter made for an index of another size or on another device fails with
+ * CPH_INVALID_ARGUMENT.  These batches never take the probe-first instantiation; cph_last_search_stats and
+ * cph_last_query_expansions report them as any other batch. */
+int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f,
+                              int64_t* ids, float* dist);
+int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
+                                     const cph_filter* f, int64_t* d_ids, float* d_dist, void* stream);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);

@@ -18,6 +18,42 @@ def _as_f32(a):
     return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
 
 
+def pack_allowed_bits(mask):
+    """Bool mask [n] -> uint32 words [ceil(n / 32)]: bit (i & 31) of word i >> 5 = mask[i] (the bitmap the filtered
+    search reads; the same bits as np.packbits(mask, bitorder="little") read as little-endian words)."""
+    m = np.asarray(mask, dtype=bool).ravel()
+    nw = (m.size + 31) // 32
+    padded = np.zeros(nw * 32, dtype=np.uint64)
+    padded[:m.size] = m
+    return (padded.reshape(nw, 32) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32)
+
+
+class IdFilter:
+    """An allowed-id set on the index' device (CPIndex.make_filter).  Ids are internal ids, the ones searches return
+    (internal_to_input_rows maps them to input rows).  Usable with any index of the same size on the same device;
+    freeing it waits for the batches that may still read it."""
+
+    def __init__(self, index, words, n_bits, count):
+        self._h = C.c_void_p()
+        self.size = int(n_bits)      # ids the filter covers (= the index size)
+        self.count = int(count)      # allowed ids
+        w = np.ascontiguousarray(words, np.uint32)
+        _lib.check(_lib.lib().cph_filter_create(index._h, w.ctypes.data if w.size else None, self.size,
+                                                C.byref(self._h)))
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._h = C.c_void_p()
+            _lib.check(_lib.lib().cph_filter_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CPIndex:
     def __init__(self, dim, bits=1, device=None):
         if dim < 0 or bits < 0:
@@ -49,12 +85,44 @@ class CPIndex:
     def finalize(self):
         _lib.check(_lib.lib().cph_finalize(self._h))
 
+    # -- filtered search (not in the reference) ------------------------------------------------
+    def make_filter(self, allowed):
+        """IdFilter from a bool mask of length `size` or an integer array of allowed internal ids."""
+        a = np.asarray(allowed)
+        n = self.size
+        if a.dtype == bool:
+            if a.ndim != 1 or a.shape[0] != n:
+                raise ValueError(f"filter mask must be a 1D bool array of length {n} (the index size)")
+            mask = a
+        elif a.size == 0 or np.issubdtype(a.dtype, np.integer):
+            ids = a.astype(np.int64).ravel()
+            if ids.size and (ids.min() < 0 or ids.max() >= n):
+                raise ValueError(f"filter ids must lie in [0, {n})")
+            mask = np.zeros(n, dtype=bool)
+            mask[ids] = True
+        else:
+            raise ValueError("filter must be a bool mask or an integer array of ids")
+        return IdFilter(self, pack_allowed_bits(mask), n, int(np.count_nonzero(mask)))
+
+    def _filter(self, f):
+        if isinstance(f, IdFilter):
+            if not f._h.value:
+                raise ValueError("filter was closed")
+            return f
+        return self.make_filter(f)
+
     # -- search -----------------------------------------------------------------------------
-    def search(self, query, k=DEFAULT_K):
+    def search(self, query, k=DEFAULT_K, filter=None):
+        """Single query, unpadded rows.  With `filter` (an IdFilter or anything make_filter accepts) only allowed ids
+        are returned; that query runs as a batch of one through the filtered batch path."""
         q = _as_f32(query)
         if q.ndim != 1 or q.shape[0] != self._dim:
             raise ValueError("query must be 1D and match index dimension")
         kk = max(int(k), 1)
+        if filter is not None:
+            ids, dist = self.search_batch(q[None, :], kk, filter=filter)
+            m = int(np.count_nonzero(ids[0] >= 0))
+            return ids[0, :m].copy(), dist[0, :m].copy()
         ids = np.empty(kk, np.int64)
         dist = np.empty(kk, np.float32)
         m = C.c_uint64(0)
@@ -62,22 +130,29 @@ class CPIndex:
                                          dist.ctypes.data, C.byref(m)))
         return ids[:m.value].copy(), dist[:m.value].copy()
 
-    def search_batch(self, queries, k=DEFAULT_K):
+    def search_batch(self, queries, k=DEFAULT_K, filter=None):
+        """Rows padded with -1 / FLT_MAX.  `filter`: restrict the results to allowed ids (see make_filter)."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
         n, k = q.shape[0], int(k)
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
-        _lib.check(_lib.lib().cph_search_batch(self._h, q.ctypes.data, n, k, ids.ctypes.data,
-                                               dist.ctypes.data))
+        if filter is None:
+            _lib.check(_lib.lib().cph_search_batch(self._h, q.ctypes.data, n, k, ids.ctypes.data,
+                                                   dist.ctypes.data))
+            return ids, dist
+        f = self._filter(filter)
+        _lib.check(_lib.lib().cph_search_batch_filtered(self._h, q.ctypes.data, n, k, f._h, ids.ctypes.data,
+                                                        dist.ctypes.data))
         return ids, dist
 
-    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None):
+    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None):
         """Device-resident variant: `queries` is a float32 CUDA/HIP torch tensor (n, dim) on this
         index' device; returns (ids int64, dist float32) torch tensors on the same device.  The work
         is enqueued on `stream` (default: torch's current stream) and the call does not wait for it:
-        the tensors are valid in stream order.  Two batches on two streams overlap."""
+        the tensors are valid in stream order.  Two batches on two streams overlap.  `filter`: as in
+        search_batch (an IdFilter made here from a mask or ids is freed on return, which waits for the batch)."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
@@ -110,8 +185,13 @@ class CPIndex:
                 ext.wait_stream(cur)
                 for t in fresh:
                     t.record_stream(ext)
-        _lib.check(_lib.lib().cph_search_batch_device(self._h, queries.data_ptr(), n, k, ids.data_ptr(),
-                                                      dist.data_ptr(), C.c_void_p(st)))
+        if filter is None:
+            _lib.check(_lib.lib().cph_search_batch_device(self._h, queries.data_ptr(), n, k, ids.data_ptr(),
+                                                          dist.data_ptr(), C.c_void_p(st)))
+            return ids, dist
+        f = self._filter(filter)
+        _lib.check(_lib.lib().cph_search_batch_device_filtered(self._h, queries.data_ptr(), n, k, f._h, ids.data_ptr(),
+                                                               dist.data_ptr(), C.c_void_p(st)))
         return ids, dist
 
     # -- persistence ------------------------------------------------------------------------

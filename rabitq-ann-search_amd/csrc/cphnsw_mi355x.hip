@@ -134,6 +134,14 @@ constexpr int kStatWords = 18;
 constexpr int kMaxBatchSets = 4;
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 
+// An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
+struct cph_filter {
+    int device = 0;
+    uint64_t n_bits = 0;
+    uint64_t popcount = 0;
+    DevBuf<uint32_t> words;
+};
+
 struct cph_index {
     uint64_t dim = 0;
     uint32_t bits = 0;
@@ -478,9 +486,22 @@ struct DoneFlags {          // per-query completion flags in pinned host memory 
     uint32_t seq = 0;
 };
 
+// The filtered instantiations: no probe first (D = 128 / 1024 with a compile-time D, the generic one elsewhere).
+template <int SD>
+void launch_filtered(uint32_t bits, uint32_t grid, size_t lds, hipStream_t st, const SearchArgs& a) {
+    if (bits == 1) hipLaunchKernelGGL((search_kernel<1, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
+    else if (bits == 2) hipLaunchKernelGGL((search_kernel<2, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((search_kernel<4, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
+    HIP_CHECK(hipGetLastError());
+}
+
+// d_allow: the allowed-id bitmap of a filtered batch (cph_filter::words), or null.  A filtered batch never probes first.
 void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist, uint32_t* d_count,
-                   const uint32_t* d_todo, int mode, hipStream_t st, DoneFlags done = DoneFlags()) {
+                   const uint32_t* d_todo, int mode, hipStream_t st, DoneFlags done = DoneFlags(),
+                   const uint32_t* d_allow = nullptr) {
     SearchArgs a{};
+    a.allow = d_allow;
+    const bool pf = d_allow == nullptr && probe_first(h);
     a.done_flags = done.flags;
     a.done_seq = done.seq;
     a.blocks = h->d_blocks.p;
@@ -511,7 +532,7 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
         a.beam_pages = s.d_beam.p;
         a.beam_tail = s.d_beam_tail.p;
         a.log_ids = s.d_logids.p;
-        a.redo = (s.cap < h->host.n + 1 || probe_first(h)) ? s.d_redo.p : nullptr;
+        a.redo = (s.cap < h->host.n + 1 || pf) ? s.d_redo.p : nullptr;
         a.redo_count = words + 1;
         grid = s.run_slots;
     } else {
@@ -528,14 +549,20 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     }
     const size_t lds = search_lds_bytes(h->L.D, h->L.PW, k);
     if (lds > 160 * 1024) throw InvalidArg("k too large for the on-chip result heap");
-    if ((mode != 0 || !probe_first(h)) && h->L.D == 1024) {
+    if (d_allow) {
+        if (h->L.D == 1024) launch_filtered<1024>(h->bits, grid, lds, st, a);
+        else if (h->L.D == 128) launch_filtered<128>(h->bits, grid, lds, st, a);
+        else launch_filtered<0>(h->bits, grid, lds, st, a);
+        return;
+    }
+    if ((mode != 0 || !pf) && h->L.D == 1024) {
         if (h->bits == 1) hipLaunchKernelGGL((search_kernel<1, 1024, false>), dim3(grid), dim3(64), lds, st, a);
         else if (h->bits == 2) hipLaunchKernelGGL((search_kernel<2, 1024, false>), dim3(grid), dim3(64), lds, st, a);
         else hipLaunchKernelGGL((search_kernel<4, 1024, false>), dim3(grid), dim3(64), lds, st, a);
         HIP_CHECK(hipGetLastError());
         return;
     }
-    if ((mode != 0 || !probe_first(h)) && h->L.D == 128) {
+    if ((mode != 0 || !pf) && h->L.D == 128) {
         // a handful of queries: latency, not traffic -- the order of loads without the third dependent round trip.  Also
         // the instantiation of the re-run launch (it takes the stage-2 decisions the probe-first one hands over), of an
         // index with short neighbour lists (flags bit 1: it evaluates their scalar tails) and of workloads on which
@@ -549,11 +576,26 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     CPH_LAUNCH(search_kernel, h->bits, h->L.D, dim3(grid), dim3(64), lds, st, a);
 }
 
+// Statistics block to pinned memory, completion event, bookkeeping: the tail of every enqueued batch.
+void finish_batch(cph_index* h, BatchSet& s, hipStream_t st) {
+    HIP_CHECK(hipEventRecord(s.ev1, st));
+    // the statistics block lands in pinned host memory; it is only read when somebody asks.  (The private sets of the
+    // cph_search leader slots leave it in HBM until then: their callers wait for the stream, and the copy command would
+    // sit on that path -- nothing of theirs can overflow, so nobody reads the block unasked.)
+    s.stats_in_hbm = (&s - h->sets) >= kMaxBatchSets;
+    if (!s.stats_in_hbm) HIP_CHECK(hipMemcpyAsync(s.pin_stats, s.d_stats.p, kStatWords * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(s.ev_done, st));
+    s.used = true;
+    h->last_search = (int)(&s - h->sets);
+}
+
 // Core: queries already staged in the set; results into device buffers.  Everything is enqueued on
 // `st` and nothing waits for the device: a query that outgrows its scratch is answered by the
 // full-capacity re-run launch that always follows the main one (it finds an empty list otherwise).
+// `filter` (null: unfiltered) restricts the result heap to its allowed ids; with no id allowed nothing is launched.
 void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist,
-                    hipStream_t st, uint32_t* d_count_out = nullptr, DoneFlags done = DoneFlags()) {
+                    hipStream_t st, uint32_t* d_count_out = nullptr, DoneFlags done = DoneFlags(),
+                    const cph_filter* filter = nullptr) {
     const uint64_t n = h->host.n;
     if (s.d_count.n < nq) {
         if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
@@ -563,6 +605,22 @@ void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t*
     }
     s.d_stats.alloc(kStatWords);
     HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
+    if (filter && filter->popcount == 0) {
+        // nothing can enter a result heap: every row is padding (-1 / FLT_MAX), no query expands anything -- the search
+        // would have walked each query's whole connected component to find that out
+        uint32_t* d_count = d_count_out ? d_count_out : s.d_count.p;
+        HIP_CHECK(hipEventRecord(s.ev0, st));
+        HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, (size_t)nq * k * 8, st));
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_dist), (int)0x7F7FFFFF, (size_t)nq * k, st));
+        HIP_CHECK(hipMemsetAsync(d_count, 0, (size_t)nq * 4, st));
+        HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));
+        s.run_slots = 0;
+        s.run_cap = 0;
+        s.nq = nq;
+        finish_batch(h, s, st);
+        return;
+    }
+    const uint32_t* d_allow = filter ? filter->words.p : nullptr;
     // resident query slots: one wave each
     uint32_t wpc = h->waves_per_cu;
     if (!h->waves_from_env) {
@@ -619,25 +677,18 @@ void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t*
     }
     uint32_t* d_count = d_count_out ? d_count_out : s.d_count.p;
     HIP_CHECK(hipEventRecord(s.ev0, st));
-    const bool rerun = s.cap < n + 1 || probe_first(h);
+    // (a filtered batch does not probe first: its re-run launch exists for capacity overflows only)
+    const bool rerun = s.cap < n + 1 || (d_allow == nullptr && probe_first(h));
     if (rerun && nq <= s.r_slots && !h->want_cap && !h->want_slots) {   // (explicit search params keep the general path)
         // a handful of queries: straight onto the full-capacity slots -- one launch, nothing can overflow
         s.run_slots = nq;
         s.run_cap = n + 1;
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 2, st, done);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 2, st, done, d_allow);
     } else {
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, 0, st, done);
-        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 1, st, done);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, 0, st, done, d_allow);
+        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 1, st, done, d_allow);
     }
-    HIP_CHECK(hipEventRecord(s.ev1, st));
-    // the statistics block lands in pinned host memory; it is only read when somebody asks.  (The private sets of the
-    // cph_search leader slots leave it in HBM until then: their callers wait for the stream, and the copy command would
-    // sit on that path -- nothing of theirs can overflow, so nobody reads the block unasked.)
-    s.stats_in_hbm = (&s - h->sets) >= kMaxBatchSets;
-    if (!s.stats_in_hbm) HIP_CHECK(hipMemcpyAsync(s.pin_stats, s.d_stats.p, kStatWords * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(s.ev_done, st));
-    s.used = true;
-    h->last_search = (int)(&s - h->sets);
+    finish_batch(h, s, st);
 }
 
 hipStream_t own_stream(cph_index* h) {
@@ -1254,6 +1305,102 @@ int cph_search_batch_device(cph_index* h, const float* d_queries, uint64_t n, ui
         BatchSet& s = next_set(h, st);
         stage_queries(h, s, d_queries, n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st);
+    });
+}
+
+// ---- filtered search --------------------------------------------------------------------
+int cph_filter_create(cph_index* h, const uint32_t* words, uint64_t n_bits, cph_filter** out) {
+    return guarded([&] {
+        if (!h || !out || (!words && n_bits != 0)) throw InvalidArg("null argument");
+        *out = nullptr;
+        if (n_bits > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+        const uint64_t nw = (n_bits + 31) / 32;
+        std::vector<uint32_t> w(words, words + nw);
+        if (n_bits & 31) w[nw - 1] &= (1u << (n_bits & 31)) - 1u;   // bits behind the last id are never set
+        uint64_t pc = 0;
+        for (uint32_t x : w) pc += (uint64_t)__builtin_popcount(x);
+        std::unique_ptr<cph_filter> f(new cph_filter());
+        f->device = h->device;
+        f->n_bits = n_bits;
+        f->popcount = pc;
+        h->use_device();
+        f->words.alloc(std::max<uint64_t>(nw, 1));
+        if (nw) HIP_CHECK(hipMemcpy(f->words.p, w.data(), nw * 4, hipMemcpyHostToDevice));
+        *out = f.release();
+    });
+}
+
+int cph_filter_destroy(cph_filter* f) {
+    return guarded([&] {
+        if (!f) return;
+        std::unique_ptr<cph_filter> own(f);
+        // batches enqueued with cph_search_batch_device_filtered may still read the bitmap
+        HIP_CHECK(hipSetDevice(f->device));
+        HIP_CHECK(hipDeviceSynchronize());
+    });
+}
+
+static void check_filter(const cph_index* h, const cph_filter* f) {
+    if (f->device != h->device) throw InvalidArg("filter belongs to another device");
+    if (f->n_bits != h->host.n)
+        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " ids, the index holds " + std::to_string(h->host.n));
+}
+
+int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f,
+                              int64_t* ids, float* dist) {
+    if (!f) return cph_search_batch(h, queries, n, k, ids, dist);
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        check_filter(h, f);
+        if (n == 0 || k == 0) return;
+        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+        if (!queries || !ids || !dist) throw InvalidArg("null argument");
+        h->use_device();
+        hipStream_t st = own_stream(h);
+        BatchSet& s = next_set(h, st);
+        if (f->popcount != 0 && n <= kSmallBatch && n * k <= (1u << 20)) {
+            // cph_search_batch's copy-free path (an empty filter writes its padding with copy commands: device buffers below)
+            SmallIo io = small_io(h, s, n, k);
+            std::memcpy(io.h_query, queries, n * h->dim * sizeof(float));
+            stage_queries(h, s, io.d_query, n, st);
+            enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.d_ids, io.d_dist, st, io.d_count, DoneFlags(), f);
+            HIP_CHECK(hipStreamSynchronize(st));
+            std::memcpy(ids, io.h_ids, n * k * 8);
+            std::memcpy(dist, io.h_dist, n * k * 4);
+            return;
+        }
+        if (f->popcount != 0) stage_queries(h, s, upload_queries(h, s, queries, n, st), n, st);
+        if (s.d_ids.n < n * k) {
+            if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
+            s.d_ids.alloc(n * k);
+            s.d_dist.alloc(n * k);
+        }
+        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f);
+        HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipEventRecord(s.ev_done, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
+                                     int64_t* d_ids, float* d_dist, void* stream) {
+    if (!f) return cph_search_batch_device(h, d_queries, n, k, d_ids, d_dist, stream);
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        check_filter(h, f);
+        if (n == 0 || k == 0) return;
+        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+        if (!d_queries || !d_ids || !d_dist) throw InvalidArg("null argument");
+        h->use_device();
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        BatchSet& s = next_set(h, st);
+        if (f->popcount != 0) stage_queries(h, s, d_queries, n, st);
+        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
     });
 }
 

@@ -76,6 +76,9 @@ struct SearchArgs {
     // the outputs then live in pinned, device-mapped memory and every caller waits for its own query only
     uint32_t* done_flags;
     uint32_t done_seq;
+    // filtered instantiations only (FILT): allowed-id bitmap, bit id & 31 of word id >> 5.  Last, so that no offset of the
+    // fields above moves
+    const uint32_t* allow;
 };
 
 // Kernel arguments that are touched once per query (work queue, encoded-query arrays, outputs, statistics) are read from
@@ -654,7 +657,10 @@ __host__ __device__ constexpr int search_waves_per_simd(int sd, int bw) {
 }
 // PF: the probe-first order of the loads (see the expansion loop).  The small-batch launch uses the instantiation without it:
 // a handful of queries is a matter of latency, and the third dependent round trip costs a single query 10 % (565 -> 624 us).
-template <int BW, int SD, bool PF = true>
+// FILT: filtered search -- only ids whose bit is set in SearchArgs::allow enter the result heap (the reference's nn.push at
+// its three call sites, gated; nothing else changes: every vertex is still estimated, reranked, pushed into the beam and
+// expanded as before).  Instantiated without probe first only: its stage-2 hand-over is never combined with a filter.
+template <int BW, int SD, bool PF = true, bool FILT = false>
 __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kernel(SearchArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -872,6 +878,9 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             }
             const float norm_ld = a.norm_sq[cur_id];
             const uint32_t nid_ld = reinterpret_cast<const uint32_t*>(blk + blk_ids_off)[li];
+            // filtered: the popped vertex's allowed bit travels with the norm (retired with the block's loads below)
+            uint32_t allow_cur = 0;
+            if constexpr (FILT) allow_cur = CPH_COLD(allow)[cur_id >> 5];
             // ---- everything else this expansion reads is issued before the probe ----------
             BlockLoads<BW, SD> bl;
             // PROBE FIRST (the static-D instantiations, D = 128 and D = 1024; 4-bit codes at D = 128 in round 3, every width and
@@ -979,7 +988,9 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             // beats the threshold: both are wave-uniform facts, so the three expansions out of four
             // that leave it alone skip the lane-0 section and the re-read of the threshold
             float worst0 = worst_pop;
-            const bool nn_changes = bcast_u32((nn_size < k || exact_dist < worst_pop) ? 1u : 0u) != 0u;   // provably uniform
+            // (filtered: a vertex outside the allowed set never enters the result heap -- cur_id is uniform, so is this)
+            const bool cur_allowed = !FILT || ((allow_cur >> (cur_id & 31u)) & 1u) != 0u;
+            const bool nn_changes = bcast_u32((cur_allowed && (nn_size < k || exact_dist < worst_pop)) ? 1u : 0u) != 0u;   // provably uniform
             if (nn_changes) {
                 nn_push_wave(nnw, nn, nn_size, k, cur_id, exact_dist, worst_pop, lane);
                 __builtin_amdgcn_wave_barrier();
@@ -1127,7 +1138,14 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             CPH_TICK(3);
 
             // ---- speculative exact L2 of the candidates, 8 per pass (rare: ~0.15 per expansion) --
+            // Filtered: the allowed bits of the new neighbours -- the only ones the serial replay below can push into the
+            // result heap -- as one lane-parallel load, issued ahead of the exact-L2 loads and turned into a mask behind
+            // them.  The replay is taken exactly when cand_mask != 0 (in the warm-up cand_mask == new_mask != 0), so the mask
+            // is ready wherever it is read; the lane-parallel path (no candidate) never touches the result heap.
+            uint32_t allow_mask = 0;
             if (cand_mask) {
+                uint32_t allow_w = 0;
+                if constexpr (FILT) allow_w = CPH_COLD(allow)[is_new ? nid >> 5 : 0u];
                 if (cand) s_list[__builtin_amdgcn_mbcnt_lo(cand_mask, 0u)] = (uint8_t)lane;
                 __syncthreads();
                 const uint32_t n_cand = __popc(cand_mask);
@@ -1145,6 +1163,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                 }
                 st_exact += n_cand;
                 __syncthreads();
+                if constexpr (FILT) allow_mask = (uint32_t)(__ballot(is_new && ((allow_w >> (nid & 31u)) & 1u) != 0u) & 0xFFFFFFFFull);
             }
             CPH_TICK(4);
             CPH_TICKF(6);
@@ -1235,7 +1254,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                     bool push = (act & 2u) != 0;
                     if (act & 1u) {
                         const float ex = bcast_f32(s_exact[i]);
-                        nn_push_wave(nnw, nn, nn_size, k, id_i, ex, worst, lane);
+                        if (!FILT || ((allow_mask >> i) & 1u) != 0u) nn_push_wave(nnw, nn, nn_size, k, id_i, ex, worst, lane);
                         if (ex < dabs) { push = true; key = ex; if (warmup) lo = ex; }
                         if ((act & 4u) && ex > kEpsSmall) {
                             // gamma adaptation (:255-267), fused as the reference compiles it; fp64 on one lane

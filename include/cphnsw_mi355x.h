@@ -250,6 +250,14 @@ int cph_host_rewrite_index(const char* path_in, const char* path_out);
  * layout (dev_block, *dev_bytes bytes) and back into `ref_roundtrip`. */
 int cph_host_repack_block(uint32_t D, uint32_t bits, const uint8_t* ref_block, uint8_t* dev_block,
                           uint64_t* dev_bytes, uint8_t* ref_roundtrip);
+/* Host restatement of the device re-layout: one device block in the storage layout (what cph_host_repack_block
+ * writes) -> the layout it is resident in on the GPU (4-bit codes at D >= 128: neighbour-major nibbles; every other
+ * format: unchanged), and back into `dev_roundtrip` (optional).  All three are dev_bytes long. */
+int cph_host_relayout_block(uint32_t D, uint32_t bits, const uint8_t* dev_block, uint8_t* resident_block,
+                            uint8_t* dev_roundtrip);
+/* Copies device blocks [first, first + count) of a finalized index to `out` (count x dev_bytes): as they are
+ * resident on the GPU (resident != 0), or converted back to the storage layout by the device (resident == 0). */
+int cph_export_blocks(cph_index* h, uint64_t first, uint64_t count, int resident, uint8_t* out);
 /* Host mirror of the query encoder (the device encoder is cph_encode_query): lut u8[D/4][16],
  * coeffs[3], masks u32[max(1,D/32)][4] (the bit-sliced form the kernels consume). */
 int cph_host_encode_query(uint64_t dim, const float* query, uint8_t* lut, float* coeffs, uint32_t* masks);

@@ -57,6 +57,8 @@ SYMBOLS = {
     "cph_exact_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cph_host_rewrite_index": (C.c_int, [C.c_char_p, C.c_char_p]),
     "cph_host_repack_block": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "cph_host_relayout_block": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_export_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     "cph_host_encode_query": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_fastscan_stream_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

@@ -291,6 +291,7 @@ inline void build_graph(HostIndex& hi, BuiltDevice& dev, const float* vecs, size
         a.nbr = nullptr;
         run_encode(bw, a, (n + 31) / 32, num_cus);
     }
+    relayout_blocks(dev.blocks.p, n, L, true);   // the encoder writes the storage layout; the index keeps the resident one
     tm.lap("gather + edge / own codes");
 
     // ---- upper layers: started before the kNN (above) --------------------------------------------------------------

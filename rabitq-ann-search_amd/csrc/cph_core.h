@@ -16,9 +16,22 @@
 //     aux     32 x {nop, ip_qo, ip_cp, popcount | weighted_popcount << 16}   (16 B each)
 //     ids     32 x u32
 //     count   u32
+//
+// 4-bit codes at D >= 128 are RESIDENT on the device in a second code layout (`nib`): neighbour i's D/2 bytes are
+// contiguous at byte i*D/2, and 32-bit word w of a neighbour holds dimensions 8w..8w+7, dimension 8w+j in bits
+// 4j..4j+3 as the 4-bit value c = sum_b 2^(3-b) bit_b (the operand order of v_dot8_u32_u4).  Two neighbours share
+// a 128-B line instead of eight, and one dot instruction sums eight dimensions of all four planes.  The plane-major
+// layout above stays the STORAGE layout (native file, repack_*): the device converts after every upload and back
+// before every download (relayout_kernel, device_relayout.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#if defined(__HIPCC__)
+#define CPH_HD __host__ __device__
+#else
+#define CPH_HD
+#endif
 
 namespace cph {
 
@@ -41,6 +54,7 @@ struct DevLayout {
     uint32_t ids_off;
     uint32_t count_off;
     uint32_t stride;   // block bytes (multiple of 64)
+    uint32_t nib;      // BW == 4 and wide: the resident codes are neighbour-major nibbles (see the top of this file)
 };
 
 #ifndef CPH_BLOCK_ALIGN
@@ -77,7 +91,52 @@ inline DevLayout make_dev_layout(uint32_t D, uint32_t BW) {
     L.ids_off = L.aux_off + 32 * 16;
     L.count_off = L.ids_off + 32 * 4;
     L.stride = (L.count_off + 4 + CPH_BLOCK_ALIGN - 1) / CPH_BLOCK_ALIGN * CPH_BLOCK_ALIGN;
+    L.nib = (BW == 4 && L.wide) ? 1 : 0;
     return L;
+}
+
+// Byte offset of plane-major code dword (plane, w) of neighbour i (the storage layout).
+CPH_HD inline uint32_t plane_dword_offset(const DevLayout& L, uint32_t plane, uint32_t w, uint32_t i) {
+    const uint32_t t = plane * L.PW + w;
+    if (L.wide) {
+        const uint32_t ck = t / 4, e = t % 4;
+        const uint32_t h = (L.NH == 2) ? ck / L.CPL : 0;
+        const uint32_t k = (L.NH == 2) ? ck % L.CPL : ck;
+        return (k * L.NH * 32 + h * 32 + i) * 16 + e * 4;
+    }
+    return (t * 32 + i) * 4;
+}
+
+// bit j of the low byte -> bit 4j, and back
+CPH_HD inline uint32_t nib_spread8(uint32_t x) {
+    x &= 0xFFu;
+    x = (x | (x << 12)) & 0x000F000Fu;
+    x = (x | (x << 6)) & 0x03030303u;
+    return (x | (x << 3)) & 0x11111111u;
+}
+CPH_HD inline uint32_t nib_compact8(uint32_t x) {
+    x &= 0x11111111u;
+    x = (x | (x >> 3)) & 0x03030303u;
+    x = (x | (x >> 6)) & 0x000F000Fu;
+    return (x | (x >> 12)) & 0xFFu;
+}
+// Nibble word w (dims 8w..8w+7) of one neighbour from its four plane dwords of 32-dim word w/4 (plane 0 = MSB).
+CPH_HD inline uint32_t nib_word_from_planes(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t w) {
+    const uint32_t sh = 8u * (w & 3u);
+    return (nib_spread8(p0 >> sh) << 3) | (nib_spread8(p1 >> sh) << 2) | (nib_spread8(p2 >> sh) << 1) |
+           nib_spread8(p3 >> sh);
+}
+// Plane dword (plane b, 32-dim word pw) of one neighbour from its nibble words 4pw..4pw+3.
+CPH_HD inline uint32_t plane_dword_from_nibs(uint32_t n0, uint32_t n1, uint32_t n2, uint32_t n3, uint32_t b) {
+    const uint32_t sh = 3u - b;
+    return nib_compact8(n0 >> sh) | (nib_compact8(n1 >> sh) << 8) | (nib_compact8(n2 >> sh) << 16) |
+           (nib_compact8(n3 >> sh) << 24);
+}
+// The query's 4-bit scalars of 32 dims, bit-sliced {Q0,Q1,Q2,Q3} (bit t of Q_j = bit j of q_u[32g+t]), as the four
+// nibble words of those dims (dims 32g+8s.. in word s).
+CPH_HD inline uint32_t qmask_nib_word(uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, uint32_t s) {
+    const uint32_t sh = 8u * s;
+    return nib_spread8(q0 >> sh) | (nib_spread8(q1 >> sh) << 1) | (nib_spread8(q2 >> sh) << 2) | (nib_spread8(q3 >> sh) << 3);
 }
 
 // Reference (file) layout of VertexSearchData<D,32,BW>; SURVEY.md §5.4.

@@ -28,6 +28,7 @@
 #include "device_search.h"
 #include "device_stream.h"
 #include "device_heap_test.h"
+#include "device_relayout.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -253,6 +254,7 @@ void upload_arrays(cph_index* h) {
         HIP_CHECK(hipMemcpy(h->d_blocks.p + base * stride, stage.data(), cnt * stride,
                             hipMemcpyHostToDevice));
     }
+    relayout_blocks(h->d_blocks.p, n, h->L, true);   // storage layout -> resident layout (cph_core.h, `nib`)
     HIP_CHECK(hipMemcpy(h->d_raw.p, hi.raw.data(), n * hi.D * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(h->d_norm.p, hi.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
 }
@@ -349,7 +351,7 @@ void materialize_search_data(cph_index* h) {
     std::vector<uint8_t> stage(chunk * stride);
     for (size_t base = 0; base < n; base += chunk) {
         const size_t c = std::min(chunk, n - base);
-        HIP_CHECK(hipMemcpy(stage.data(), h->d_blocks.p + base * stride, c * stride, hipMemcpyDeviceToHost));
+        download_blocks(h->d_blocks.p + base * stride, c, h->L, stage.data());
         parallel_for(c, 256, [&](size_t lo, size_t hi_) {
             for (size_t v = lo; v < hi_; ++v) {
                 uint8_t* dst = &hi.search_data[(base + v) * hi.RL.vertex_bytes];
@@ -858,7 +860,7 @@ int cph_save_native(cph_index* h, const char* path) {
         const HostIndex& hi = h->host;
         const size_t n = hi.n, stride = h->L.stride, own_stride = hi.RL.nb_off;
         std::vector<uint8_t> blocks(n * stride), own;
-        HIP_CHECK(hipMemcpy(blocks.data(), h->d_blocks.p, n * stride, hipMemcpyDeviceToHost));
+        download_blocks(h->d_blocks.p, n, h->L, blocks.data());   // the file keeps the storage layout
         const uint8_t* own_p = h->own_view;
         if (!own_p) {
             own.resize(n * own_stride);
@@ -891,6 +893,7 @@ int cph_load_native(cph_index* h, const char* path) {
         h->d_raw.alloc(n * h->host.D);
         h->d_norm.alloc(n);
         HIP_CHECK(hipMemcpy(h->d_blocks.p, base + nh.blocks_off, n * (size_t)nh.stride, hipMemcpyHostToDevice));
+        relayout_blocks(h->d_blocks.p, n, h->L, true);
         HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
         upload_feeders(h);
@@ -1654,6 +1657,32 @@ int cph_host_repack_block(uint32_t D, uint32_t bits, const uint8_t* ref_block, u
     });
 }
 
+int cph_host_relayout_block(uint32_t D, uint32_t bits, const uint8_t* dev_block, uint8_t* resident_block,
+                            uint8_t* dev_roundtrip) {
+    return guarded([&] {
+        if (bits != 1 && bits != 2 && bits != 4) throw InvalidArg("bits must be 1, 2 or 4");
+        if (D < 16 || D > 2048 || (D & (D - 1))) throw InvalidArg("D must be a power of two in 16..2048");
+        if (!dev_block || !resident_block) throw InvalidArg("null block");
+        const DevLayout L = make_dev_layout(D, bits);
+        block_plane_to_nib(dev_block, L, resident_block);
+        if (dev_roundtrip) block_nib_to_plane(resident_block, L, dev_roundtrip);
+    });
+}
+
+int cph_export_blocks(cph_index* h, uint64_t first, uint64_t count, int resident, uint8_t* out) {
+    return guarded([&] {
+        if (!h || !out) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->finalized) throw std::runtime_error("Index must be finalized.");
+        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("block range out of bounds");
+        h->use_device();
+        quiesce(h);
+        const uint8_t* src = h->d_blocks.p + first * h->L.stride;
+        if (resident) HIP_CHECK(hipMemcpy(out, src, count * h->L.stride, hipMemcpyDeviceToHost));
+        else download_blocks(src, count, h->L, out);
+    });
+}
+
 int cph_host_encode_query(uint64_t dim, const float* query, uint8_t* lut, float* coeffs, uint32_t* masks) {
     return guarded([&] {
         const size_t D = std::max<size_t>(16, next_pow2(dim));
@@ -1800,6 +1829,7 @@ int cph_fastscan_stream_create(int device, uint32_t D, uint32_t bits, uint64_t n
         hipLaunchKernelGGL(stream_fill_kernel, dim3(s->num_cus * 16), dim3(64), 0, nullptr,
                            s->d_blocks.p, n_blocks, s->L, seed);
         HIP_CHECK(hipGetLastError());
+        relayout_blocks(s->d_blocks.p, n_blocks, s->L, true);   // filled in the storage layout
         // one seeded query: random rotated vector -> 4-bit scalars -> masks / LUT / coefficients
         std::mt19937_64 rng(seed * 7919 + 13);
         std::normal_distribution<float> nd(0.0f, 1.0f);
@@ -1853,8 +1883,7 @@ int cph_fastscan_stream_export(cph_stream* s, uint64_t first, uint64_t count, ui
         if (first + count > s->n_blocks) throw InvalidArg("block range out of bounds");
         if (count && ref_blocks) {
             std::vector<uint8_t> dev(count * s->L.stride);
-            HIP_CHECK(hipMemcpy(dev.data(), s->d_blocks.p + first * s->L.stride, dev.size(),
-                                hipMemcpyDeviceToHost));
+            download_blocks(s->d_blocks.p + first * s->L.stride, count, s->L, dev.data());
             parallel_for(count, 1024, [&](size_t lo, size_t hi) {
                 for (size_t b = lo; b < hi; ++b)
                     repack_dev_to_ref(&dev[b * s->L.stride], s->L, s->RL, ref_blocks + b * s->RL.nb_bytes);

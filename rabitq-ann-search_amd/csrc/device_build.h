@@ -708,7 +708,7 @@ __global__ __launch_bounds__(64) void calib_kernel(CalibArgs a) {
     const int lane = threadIdx.x;
     for (uint32_t s = blockIdx.x; s < a.ns; s += gridDim.x) {
         __syncthreads();
-        for (uint32_t w = lane; w < PW; w += 64) qm[w] = a.qmasks[(size_t)s * PW + w];
+        for (uint32_t w = lane; w < PW; w += 64) qm[w] = qm_lds_word(a.qmasks[(size_t)s * PW + w], nib_codes<BW, 0>(a.L));
         for (uint32_t d = lane; d < D; d += 64) qv[d] = a.queries[(size_t)s * D + d];
         __syncthreads();
         uint32_t parent = a.start[s];

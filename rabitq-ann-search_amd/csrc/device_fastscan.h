@@ -18,6 +18,11 @@
 // wave-uniform broadcasts.  One wave handles one vertex' 32-neighbour block: lane
 // (h = lane>>5, i = lane&31) owns half of neighbour i's code dwords, so each load
 // instruction of the wave reads 1 KiB contiguous.
+//
+// 4-bit codes at D >= 128 are resident as neighbour-major nibbles (cph_core.h, `nib`), and the query's scalars sit in
+// LDS as nibble words of the same dims.  The code value c[d] = sum_b 2^(3-b) bit_b[d] and q_u[d] are both 4-bit, so
+//      nbit = sum_d q_u c,   8 S0 = sum_d q_u (c & 8),   4 (2 S0 + S1) = sum_d q_u (c & 12)
+// are three v_dot8_u32_u4 per 8 dims (plus two v_and) -- the identical integers, so every float behind them is too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,6 +73,55 @@ __device__ __forceinline__ void half_pair(uint32_t x, uint32_t& lo, uint32_t& hi
     hi = r[1];
 }
 
+// Whether a block's codes are in the nibble layout: 4-bit codes at D >= 128 (cph_core.h, make_dev_layout).
+template <int BW, int SD>
+__device__ __forceinline__ bool nib_codes(const DevLayout& L) {
+    if constexpr (BW != 4) return false;
+    else if constexpr (SD != 0) return SD >= 128;
+    else return L.nib != 0u;
+}
+
+// One 16-B word of the query in LDS: the bit-sliced masks {Q0,Q1,Q2,Q3} of 32 dims, or (nibble layout) the four nibble
+// words of the same 32 dims -- same size, same index.
+__device__ __forceinline__ uint4 qm_lds_word(uint4 m, bool nib) {
+    if (!nib) return m;
+    return make_uint4(qmask_nib_word(m.x, m.y, m.z, m.w, 0), qmask_nib_word(m.x, m.y, m.z, m.w, 1),
+                      qmask_nib_word(m.x, m.y, m.z, m.w, 2), qmask_nib_word(m.x, m.y, m.z, m.w, 3));
+}
+
+// The three 4-bit dot products of one code word (8 dims of one neighbour) against the query's nibble word q.
+__device__ __forceinline__ void dot3(uint32_t c, uint32_t q, uint32_t& s, uint32_t& s8, uint32_t& s12) {
+    s = __builtin_amdgcn_udot8(c, q, s, false);
+    s8 = __builtin_amdgcn_udot8(c & 0x88888888u, q, s8, false);
+    s12 = __builtin_amdgcn_udot8(c & 0xCCCCCCCCu, q, s12, false);
+}
+__device__ __forceinline__ void dot3(uint4 c, uint4 q, uint32_t& s, uint32_t& s8, uint32_t& s12) {
+    dot3(c.x, q.x, s, s8, s12);
+    dot3(c.y, q.y, s, s8, s12);
+    dot3(c.z, q.z, s, s8, s12);
+    dot3(c.w, q.w, s, s8, s12);
+}
+// Both lane halves' partial sums merged.  At D <= 256 the full sums of s and s8 fit 16 bits (225 D and 120 D), so
+// they travel packed through one swap.
+template <int SD>
+__device__ __forceinline__ void nib_merge(uint32_t s, uint32_t s8, uint32_t s12, uint32_t& nbit, uint32_t& msb,
+                                          uint32_t& msb2) {
+    uint32_t lo, hi;
+    if constexpr (SD != 0 && SD <= 256) {
+        half_pair(s | (s8 << 16), lo, hi);
+        const uint32_t t = lo + hi;
+        nbit = t & 0xFFFFu;
+        msb = t >> 19;
+    } else {
+        half_pair(s, lo, hi);
+        nbit = lo + hi;
+        half_pair(s8, lo, hi);
+        msb = (lo + hi) >> 3;
+    }
+    half_pair(s12, lo, hi);
+    msb2 = (lo + hi) >> 2;
+}
+
 template <int BW, int SD>
 __device__ __forceinline__ void block_sums(const uint8_t* __restrict__ blk, const DevLayout& L,
                                            const uint4* qm, int lane, uint32_t& nbit,
@@ -77,7 +131,15 @@ __device__ __forceinline__ void block_sums(const uint8_t* __restrict__ blk, cons
     const bool wide = SD ? (SD >= 128) : (L.wide != 0);
     if (wide) {
         const uint4* cp = reinterpret_cast<const uint4*>(blk) + lane;
-        if constexpr (BW >= 2) {
+        if constexpr (BW == 4) {
+            // nibble layout: lane (h, i) takes 16-B chunks h, h+2, h+4, .. of neighbour i's PW chunks
+            const uint4* cn = reinterpret_cast<const uint4*>(blk) + (uint32_t)(lane & 31) * PW + h;
+            const uint4* qn = qm + h;
+            uint32_t s = 0, s8 = 0, s12 = 0;
+#pragma unroll 2
+            for (uint32_t g = 0; g < PW / 2; ++g) dot3(cn[2 * g], qn[2 * g], s, s8, s12);
+            nib_merge<SD>(s, s8, s12, nbit, msb, msb2);
+        } else if constexpr (BW == 2) {
             constexpr int PPH = BW / 2;  // planes per lane half (NH == 2 always here)
             const uint32_t G = PW >> 2;  // 16-B chunks per plane
             uint32_t S[PPH];
@@ -102,15 +164,8 @@ __device__ __forceinline__ void block_sums(const uint8_t* __restrict__ blk, cons
             half_pair(part, plo, phi);
             nbit = plo + phi;
             half_pair(S[0], s0, s0hi);          // plane 0 lives in the h = 0 half
-            if constexpr (BW == 2) {
-                msb = s0;
-                msb2 = 2 * s0 + s0hi;           // plane 1 = S[0] of the h = 1 half
-            } else {
-                uint32_t s1, s1hi;
-                half_pair(S[1], s1, s1hi);      // planes 0,1 both in the h = 0 half
-                msb = s0;
-                msb2 = 2 * s0 + s1;
-            }
+            msb = s0;
+            msb2 = 2 * s0 + s0hi;               // plane 1 = S[0] of the h = 1 half
         } else {
             const uint32_t NH = SD ? ((SD / 32) / 4 >= 2 ? 2 : 1) : L.NH;
             const uint32_t CPL = SD ? ((SD / 32) / 4 / NH) : L.CPL;
@@ -161,24 +216,33 @@ struct BlockLoads {
     static constexpr int kT = kStatic ? BW * (SD / 32) : 4;          // dwords per neighbour
     static constexpr int kNH = (kT / 4 >= 2) ? 2 : 1;
     static constexpr int kCPL = kStatic ? kT / 4 / kNH : 1;          // 16-B chunks per lane
+    // 4-bit nibble layout (cph_core.h): lane (h, i) holds chunks h, h+2, .., of neighbour i's SD/32 contiguous chunks,
+    // i.e. one half-line of codes per neighbour at D = 128 (plane-major: four 16-B pieces in four lines)
+    static constexpr bool kNib = kStatic && BW == 4;
     uint4 c[kCPL];
     uint4 aux;
 
-    // aux offset known at compile time (see cph_core.h StaticLayout)
-    __device__ __forceinline__ void issue_static(const uint8_t* __restrict__ blk, int lane) {
-        static_assert(kStatic, "static D only");
-        const uint4* cp = reinterpret_cast<const uint4*>(blk) + (lane & (kNH * 32 - 1));
+    __device__ __forceinline__ void issue_codes(const uint8_t* __restrict__ blk, int lane) {
+        if constexpr (kNib) {
+            const uint4* cp = reinterpret_cast<const uint4*>(blk) + (lane & 31) * (SD / 32) + (lane >> 5);
 #pragma unroll
-        for (int k = 0; k < kCPL; ++k) c[k] = cp[k * kNH * 32];
-        aux = reinterpret_cast<const uint4*>(blk + StaticLayout<BW, SD>::kAuxOff)[lane & 31];
-    }
-
-    __device__ __forceinline__ void issue(const uint8_t* __restrict__ blk, const DevLayout& L, int lane) {
-        if constexpr (kStatic) {
+            for (int k = 0; k < kCPL; ++k) c[k] = cp[k * kNH];
+        } else {
             const uint4* cp = reinterpret_cast<const uint4*>(blk) + (lane & (kNH * 32 - 1));
 #pragma unroll
             for (int k = 0; k < kCPL; ++k) c[k] = cp[k * kNH * 32];
         }
+    }
+
+    // aux offset known at compile time (see cph_core.h StaticLayout)
+    __device__ __forceinline__ void issue_static(const uint8_t* __restrict__ blk, int lane) {
+        static_assert(kStatic, "static D only");
+        issue_codes(blk, lane);
+        aux = reinterpret_cast<const uint4*>(blk + StaticLayout<BW, SD>::kAuxOff)[lane & 31];
+    }
+
+    __device__ __forceinline__ void issue(const uint8_t* __restrict__ blk, const DevLayout& L, int lane) {
+        if constexpr (kStatic) issue_codes(blk, lane);
         aux = reinterpret_cast<const uint4*>(blk + L.aux_off)[lane & 31];
     }
 
@@ -194,7 +258,13 @@ struct BlockLoads {
 
     __device__ __forceinline__ void reduce(const uint8_t* __restrict__ blk, const DevLayout& L,
                                            const uint4* qm, int lane, LaneEst& o) {
-        if constexpr (kStatic) {
+        if constexpr (kNib) {
+            const uint4* qn = qm + (lane >> 5);
+            uint32_t s = 0, s8 = 0, s12 = 0;
+#pragma unroll
+            for (int k = 0; k < kCPL; ++k) dot3(c[k], qn[k * kNH], s, s8, s12);
+            nib_merge<SD>(s, s8, s12, o.nbit, o.msb, o.msb2);
+        } else if constexpr (kStatic) {
             const int h = lane >> 5;
             constexpr int PW = SD / 32;
             if constexpr (BW >= 2) {
@@ -221,15 +291,8 @@ struct BlockLoads {
                 half_pair(part, plo, phi);
                 o.nbit = plo + phi;
                 half_pair(S[0], s0, s0hi);      // plane 0 lives in the h = 0 half
-                if constexpr (BW == 2) {
-                    o.msb = s0;
-                    o.msb2 = 2 * s0 + s0hi;     // plane 1 = S[0] of the h = 1 half
-                } else {
-                    uint32_t s1, s1hi;
-                    half_pair(S[1], s1, s1hi);  // planes 0,1 both in the h = 0 half
-                    o.msb = s0;
-                    o.msb2 = 2 * s0 + s1;
-                }
+                o.msb = s0;
+                o.msb2 = 2 * s0 + s0hi;         // plane 1 = S[0] of the h = 1 half (BW == 2: 4-bit is kNib)
             } else {
                 uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
                 if (h < kNH) {

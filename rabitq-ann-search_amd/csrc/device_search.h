@@ -728,7 +728,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         {
             const uint4* qmasks = CPH_COLD(qmasks);
             const float* queries = CPH_COLD(queries);
-            for (uint32_t w = lane; w < PW; w += 64) qm[w] = qmasks[(size_t)qi * PW + w];
+            for (uint32_t w = lane; w < PW; w += 64) qm[w] = qm_lds_word(qmasks[(size_t)qi * PW + w], nib_codes<BW, SD>(a.L));
             for (uint32_t d = lane; d < D; d += 64) qv[d] = queries[(size_t)qi * D + d];
         }
         const QueryHeader hd = CPH_COLD(qhdr)[qi];

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void fastscan_stream_kernel(StreamArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     uint4* qm = reinterpret_cast<uint4*>(smem);
     const uint32_t PW = SD ? (SD >= 32 ? SD / 32 : 1) : a.L.PW;
-    for (uint32_t w = threadIdx.x; w < PW; w += blockDim.x) qm[w] = a.qmask[w];
+    for (uint32_t w = threadIdx.x; w < PW; w += blockDim.x) qm[w] = qm_lds_word(a.qmask[w], nib_codes<BW, SD>(a.L));
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void block_hook_kernel(BlockHookArgs a) {
     uint4* qm = reinterpret_cast<uint4*>(smem);
     const uint32_t PW = SD ? (SD >= 32 ? SD / 32 : 1) : a.L.PW;
     const int lane = threadIdx.x;
-    for (uint32_t w = lane; w < PW; w += 64) qm[w] = a.qmask[w];
+    for (uint32_t w = lane; w < PW; w += 64) qm[w] = qm_lds_word(a.qmask[w], nib_codes<BW, SD>(a.L));
     __syncthreads();
     LaneEst v;
     load_block<BW, SD>(a.blk, a.L, qm, lane, v);

@@ -340,14 +340,41 @@ struct HostIndex {
 
 // ---- reference neighbour block <-> device block -----------------------------------------
 inline size_t dev_dword_offset(const DevLayout& L, uint32_t plane, uint32_t w, uint32_t i) {
-    const uint32_t t = plane * L.PW + w;
-    if (L.wide) {
-        const uint32_t ck = t / 4, e = t % 4;
-        const uint32_t h = (L.NH == 2) ? ck / L.CPL : 0;
-        const uint32_t k = (L.NH == 2) ? ck % L.CPL : ck;
-        return ((size_t)(k * L.NH * 32 + h * 32 + i) * 16 + e * 4);
+    return plane_dword_offset(L, plane, w, i);
+}
+
+// Host restatement of the device re-layout of one block's codes (cph_core.h: `nib`; device_relayout.h).  The
+// repackers below read and write the plane-major storage layout; these convert its codes region to the resident
+// nibble layout and back.  Aux, ids and count are copied unchanged.  src and dst may be the same block.
+inline void block_plane_to_nib(const uint8_t* src, const DevLayout& L, uint8_t* dst) {
+    std::vector<uint8_t> out(src, src + L.stride);
+    if (L.nib) {
+        const uint32_t NW = L.D / 8;  // nibble words per neighbour
+        for (uint32_t i = 0; i < 32; ++i)
+            for (uint32_t w = 0; w < NW; ++w) {
+                uint32_t p[4];
+                for (uint32_t b = 0; b < 4; ++b) std::memcpy(&p[b], src + plane_dword_offset(L, b, w / 4, i), 4);
+                const uint32_t v = nib_word_from_planes(p[0], p[1], p[2], p[3], w);
+                std::memcpy(&out[((size_t)i * NW + w) * 4], &v, 4);
+            }
     }
-    return ((size_t)t * 32 + i) * 4;
+    std::memcpy(dst, out.data(), L.stride);
+}
+inline void block_nib_to_plane(const uint8_t* src, const DevLayout& L, uint8_t* dst) {
+    std::vector<uint8_t> out(src, src + L.stride);
+    if (L.nib) {
+        const uint32_t NW = L.D / 8;
+        for (uint32_t i = 0; i < 32; ++i)
+            for (uint32_t pw = 0; pw < L.PW; ++pw) {
+                uint32_t n[4];
+                std::memcpy(n, src + ((size_t)i * NW + 4 * pw) * 4, 16);
+                for (uint32_t b = 0; b < 4; ++b) {
+                    const uint32_t v = plane_dword_from_nibs(n[0], n[1], n[2], n[3], b);
+                    std::memcpy(&out[plane_dword_offset(L, b, pw, i)], &v, 4);
+                }
+            }
+    }
+    std::memcpy(dst, out.data(), L.stride);
 }
 
 inline void repack_ref_to_dev(const uint8_t* ref_nb, const RefLayout& RL, const DevLayout& L,

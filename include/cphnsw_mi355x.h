@@ -25,7 +25,7 @@
  * thrown.  CPH_INVALID_ARGUMENT maps to Python ValueError (std::invalid_argument),
  * CPH_RUNTIME_ERROR to RuntimeError (std::runtime_error), CPH_OUT_OF_MEMORY to MemoryError.
  * The caller owns all buffers; the library owns the handle.  A handle is bound to one HIP
- * device.  Threads: every entry point may be called from any thread.  Concurrent cph_search callers on one handle
+ * device (cph_multi_*: one index replicated on several devices, one call).  Threads: every entry point may be called from any thread.  Concurrent cph_search callers on one handle
  * are COALESCED into shared launches (the reference answers them in parallel under a shared lock,
  * src/bindings.cpp:146-175, api/hnsw_index.hpp:172): a caller that finds a free leader slot takes everybody queued
  * so far with the same k into one launch; each waits for its own query only and gets its own rows.  The other entry points serialise on the handle
@@ -196,6 +196,60 @@ int cph_last_query_expansions(cph_index* index, uint32_t* out, uint64_t n);
 /* Launch order of a batch (hook of the counting sort that hands queries out closest-entry-first):
  * order[n] = permutation of 0..n-1, ascending in the top 14 bits of the non-negative float keys. */
 int cph_order_queries(cph_index* index, const float* keys, uint64_t n, uint32_t* order);
+
+/* ---- one index on several devices (in-process replicas; csrc/multi_device.h) ----------------------------------- */
+/* The reference's search_batch uses every host core in one call; a cph_multi uses several GPUs (or several replicas
+ * on one GPU) in one call, with no launcher and no collective.  The index is replicated on every listed device,
+ * queries are split into contiguous shards, each shard runs the single-device cph_search_batch[_filtered] on its
+ * replica, and results land straight in the caller's rows: byte-identical to a single-device handle.
+ *
+ *   create   devices[n_dev]: HIP ordinals, 1 <= n_dev <= 16, duplicates allowed (several replicas on one GPU).
+ *   load / load_native / finalize
+ *            run once on replica 0 (the file is read and parsed, or mapped, once; the builder runs on replica 0);
+ *            replicas 1..N-1 then receive replica 0's resident device arrays by device-to-device copy.  Host memory
+ *            for the index is held once: only replica 0 keeps host arrays.  If a call fails after replica 0 gave up
+ *            its previous index, no replica is searchable until the next successful load / finalize.
+ *   save / save_native
+ *            from replica 0: the same bytes as cph_save / cph_save_native.
+ *   build    pending vectors on replica 0; the previous index leaves every replica.
+ *   search_batch[_filtered]
+ *            queries split into shards whose sizes differ by at most one, none smaller than min_shard
+ *            (cph_multi_set_min_shard; default 1024); fewer than 2 * min_shard queries go whole to one replica, round
+ *            robin.  Each shard runs on its replica's persistent worker thread; the call returns when every shard has
+ *            finished, also on error (no worker touches ids / dist afterwards).  On failure the status and
+ *            cph_last_error() text (on the calling thread) are those of the lowest-numbered failing replica.
+ *            f[n_dev]: one filter per replica, each made with cph_filter_create on that replica (NULL = unfiltered).
+ *   search   one single query, routed to one replica (round robin), whose coalescer gathers it with that replica's
+ *            other callers: the same answer as cph_search.
+ *   last_search_stats / last_query_expansions
+ *            over the replicas of the last search_batch[_filtered]: words 0-5, 7, 8, 10, 11 summed, 6 (kernel_us)
+ *            and 9 (capacity) the maximum; expansions concatenated in query order.
+ *   replica  borrowed handle of replica i (owned by m; never destroyed by the caller): cph_search_batch_device on that
+ *            device, cph_filter_create, cph_set_search_params / cph_set_batch_sets, the hooks.  cph_load,
+ *            cph_load_native, cph_build, cph_finalize and cph_destroy on it fail with CPH_INVALID_ARGUMENT; on
+ *            replicas other than 0 so do cph_save, cph_save_native and cph_get_vectors (no host arrays).
+ * Threads: search_batch[_filtered] and search may be called concurrently from any number of threads; load,
+ * load_native, build, finalize and destroy wait for the searches in flight on the multi handle. */
+typedef struct cph_multi cph_multi;
+int cph_multi_create(uint64_t dim, uint64_t bits, const int* devices, uint32_t n_dev, cph_multi** out);
+int cph_multi_destroy(cph_multi* m);
+int cph_multi_load(cph_multi* m, const char* path);
+int cph_multi_load_native(cph_multi* m, const char* path);
+int cph_multi_save(cph_multi* m, const char* path);
+int cph_multi_save_native(cph_multi* m, const char* path);
+int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n);
+int cph_multi_finalize(cph_multi* m);
+int cph_multi_size(cph_multi* m, uint64_t* n);
+int cph_multi_is_finalized(cph_multi* m, int* flag);
+int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist);
+int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
+                                    const cph_filter* const* f, int64_t* ids, float* dist);
+int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
+int cph_multi_set_min_shard(cph_multi* m, uint64_t q);
+int cph_multi_last_search_stats(cph_multi* m, uint64_t out[12]);
+int cph_multi_last_query_expansions(cph_multi* m, uint32_t* out, uint64_t n);
+int cph_multi_num_replicas(cph_multi* m, uint32_t* n);
+int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out);
 
 /* ---- kernel-level hooks ------------------------------------------------------------ */
 /* Query encoder (encoder/rabitq_encoder.hpp:73-79,98-136,197-209): lut = u8[D/4][16] in

@@ -50,6 +50,26 @@ SYMBOLS = {
     "cph_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_last_query_expansions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "cph_order_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cph_multi_create": (C.c_int, [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cph_multi_destroy": (C.c_int, [C.c_void_p]),
+    "cph_multi_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_multi_load_native": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_multi_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_multi_save_native": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_multi_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_multi_finalize": (C.c_int, [C.c_void_p]),
+    "cph_multi_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_multi_is_finalized": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_multi_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cph_multi_search_batch_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "cph_multi_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_uint64)]),
+    "cph_multi_set_min_shard": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_multi_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_multi_last_query_expansions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_multi_num_replicas": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "cph_multi_replica": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "cph_encode_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_entry_point": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "cph_fastscan_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float,

@@ -31,21 +31,28 @@ def pack_allowed_bits(mask):
 class IdFilter:
     """An allowed-id set on the index' device (CPIndex.make_filter).  Ids are internal ids, the ones searches return
     (internal_to_input_rows maps them to input rows).  Usable with any index of the same size on the same device;
-    freeing it waits for the batches that may still read it."""
+    freeing it waits for the batches that may still read it.  A multi-device index' filter holds one bitmap per
+    replica, each on that replica's device."""
 
     def __init__(self, index, words, n_bits, count):
         self._h = C.c_void_p()
+        self._hs = []                # one cph_filter per replica (a single-device index: one)
         self.size = int(n_bits)      # ids the filter covers (= the index size)
         self.count = int(count)      # allowed ids
         w = np.ascontiguousarray(words, np.uint32)
-        _lib.check(_lib.lib().cph_filter_create(index._h, w.ctypes.data if w.size else None, self.size,
-                                                C.byref(self._h)))
+        for rh in index._replicas():
+            h = C.c_void_p()
+            _lib.check(_lib.lib().cph_filter_create(rh, w.ctypes.data if w.size else None, self.size, C.byref(h)))
+            self._hs.append(h)
+        self._h = self._hs[0]
 
     def close(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._h = C.c_void_p()
-            _lib.check(_lib.lib().cph_filter_destroy(h))
+        hs = getattr(self, "_hs", [])
+        self._hs = []
+        self._h = C.c_void_p()
+        for h in hs:
+            if h.value:
+                _lib.check(_lib.lib().cph_filter_destroy(h))
 
     def __del__(self):
         try:
@@ -55,18 +62,53 @@ class IdFilter:
 
 
 class CPIndex:
-    def __init__(self, dim, bits=1, device=None):
+    """`devices=[...]` (instead of `device`): the index is replicated on every listed HIP device (duplicates allowed:
+    several replicas on one GPU) and search_batch splits its queries across the replicas in one call, with results
+    byte-identical to a single-device index.  Hooks, get_vectors and internal_to_input_rows are served by replica 0."""
+
+    def __init__(self, dim, bits=1, device=None, devices=None):
+        self._h = C.c_void_p()
+        self._m = None               # cph_multi handle of a multi-device index
         if dim < 0 or bits < 0:
             raise TypeError("CPIndex(): incompatible constructor arguments")  # size_t in pybind11
-        if device is None:
-            device = _default_device()
-        self._h = C.c_void_p()
         self._dim = int(dim)
         self._bits = int(bits)
+        if devices is not None:
+            if device is not None:
+                raise ValueError("pass either device or devices, not both")
+            devs = [int(d) for d in devices]
+            if not devs:
+                raise ValueError("devices must list at least one device")
+            m = C.c_void_p()
+            _lib.check(_lib.lib().cph_multi_create(int(dim), int(bits), (C.c_int * len(devs))(*devs), len(devs),
+                                                   C.byref(m)))
+            self._m = m
+            self._devices = devs
+            self._device = devs[0]
+            self._reps = []          # borrowed replica handles (owned by the multi handle)
+            for i in range(len(devs)):
+                h = C.c_void_p()
+                _lib.check(_lib.lib().cph_multi_replica(m, i, C.byref(h)))
+                self._reps.append(h)
+            self._h = self._reps[0]  # hooks, get_vectors, ...: replica 0
+            self._next_dev = 0       # search_batch_device: alternates between the replicas on the queries' device
+            return
+        if device is None:
+            device = _default_device()
         self._device = int(device)
+        self._devices = [self._device]
         _lib.check(_lib.lib().cph_create(int(dim), int(bits), int(device), C.byref(self._h)))
 
     def __del__(self):
+        m = getattr(self, "_m", None)
+        if m is not None:
+            self._m = None
+            self._h = C.c_void_p()
+            try:
+                _lib.lib().cph_multi_destroy(m)
+            except Exception:
+                pass
+            return
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             try:
@@ -75,14 +117,34 @@ class CPIndex:
                 pass
             self._h = C.c_void_p()
 
+    def _replicas(self):
+        return self._reps if self._m is not None else [self._h]
+
+    @property
+    def devices(self):
+        """HIP device of every replica (a single-device index: its one device)."""
+        return list(self._devices)
+
+    def set_min_shard(self, q):
+        """Smallest shard of a search_batch worth a replica (default 1024 queries; a batch of fewer than 2 * q
+        queries goes whole to one replica).  No effect on a single-device index."""
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_set_min_shard(self._m, int(q)))
+
     # -- construction (host side; SURVEY.md §8f N2) -------------------------------------------
     def build(self, vectors):
         v = _as_f32(vectors)
         if v.ndim != 2 or v.shape[1] != self._dim:
             raise ValueError("vectors must be a (n, dim) float32 array")
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_build(self._m, v.ctypes.data, v.shape[0]))
+            return
         _lib.check(_lib.lib().cph_build(self._h, v.ctypes.data, v.shape[0]))
 
     def finalize(self):
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_finalize(self._m))
+            return
         _lib.check(_lib.lib().cph_finalize(self._h))
 
     # -- filtered search (not in the reference) ------------------------------------------------
@@ -108,6 +170,8 @@ class CPIndex:
         if isinstance(f, IdFilter):
             if not f._h.value:
                 raise ValueError("filter was closed")
+            if len(f._hs) != len(self._replicas()):
+                raise ValueError("filter was made for an index with another number of replicas")
             return f
         return self.make_filter(f)
 
@@ -126,6 +190,10 @@ class CPIndex:
         ids = np.empty(kk, np.int64)
         dist = np.empty(kk, np.float32)
         m = C.c_uint64(0)
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_search(self._m, q.ctypes.data, int(k), ids.ctypes.data,
+                                                   dist.ctypes.data, C.byref(m)))
+            return ids[:m.value].copy(), dist[:m.value].copy()
         _lib.check(_lib.lib().cph_search(self._h, q.ctypes.data, int(k), ids.ctypes.data,
                                          dist.ctypes.data, C.byref(m)))
         return ids[:m.value].copy(), dist[:m.value].copy()
@@ -138,6 +206,17 @@ class CPIndex:
         n, k = q.shape[0], int(k)
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
+        if self._m is not None:
+            fs = None
+            if filter is not None:
+                f = self._filter(filter)
+                fs = (C.c_void_p * len(f._hs))(*[h.value for h in f._hs])
+                _lib.check(_lib.lib().cph_multi_search_batch_filtered(self._m, q.ctypes.data, n, k, fs, ids.ctypes.data,
+                                                                      dist.ctypes.data))
+            else:
+                _lib.check(_lib.lib().cph_multi_search_batch(self._m, q.ctypes.data, n, k, ids.ctypes.data,
+                                                             dist.ctypes.data))
+            return ids, dist
         if filter is None:
             _lib.check(_lib.lib().cph_search_batch(self._h, q.ctypes.data, n, k, ids.ctypes.data,
                                                    dist.ctypes.data))
@@ -152,13 +231,23 @@ class CPIndex:
         index' device; returns (ids int64, dist float32) torch tensors on the same device.  The work
         is enqueued on `stream` (default: torch's current stream) and the call does not wait for it:
         the tensors are valid in stream order.  Two batches on two streams overlap.  `filter`: as in
-        search_batch (an IdFilter made here from a mask or ids is freed on return, which waits for the batch)."""
+        search_batch (an IdFilter made here from a mask or ids is freed on return, which waits for the batch).
+        A multi-device index runs the whole batch on one replica that lives on the queries' device (alternating
+        between several there); the batch is not split."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
         n, k = queries.shape[0], int(k)
-        if not queries.is_cuda or queries.device.index != self._device:
+        rep = 0
+        if self._m is not None:
+            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
+            if not on:
+                raise ValueError("queries must live on one of this index' devices")
+            rep = on[self._next_dev % len(on)]
+            self._next_dev += 1
+        elif not queries.is_cuda or queries.device.index != self._device:
             raise ValueError("queries must live on this index' device")
+        h = self._replicas()[rep]
         fresh = []                       # tensors allocated here, on torch's current stream
         if not queries.is_contiguous():
             queries = queries.contiguous()
@@ -186,19 +275,25 @@ class CPIndex:
                 for t in fresh:
                     t.record_stream(ext)
         if filter is None:
-            _lib.check(_lib.lib().cph_search_batch_device(self._h, queries.data_ptr(), n, k, ids.data_ptr(),
+            _lib.check(_lib.lib().cph_search_batch_device(h, queries.data_ptr(), n, k, ids.data_ptr(),
                                                           dist.data_ptr(), C.c_void_p(st)))
             return ids, dist
         f = self._filter(filter)
-        _lib.check(_lib.lib().cph_search_batch_device_filtered(self._h, queries.data_ptr(), n, k, f._h, ids.data_ptr(),
+        _lib.check(_lib.lib().cph_search_batch_device_filtered(h, queries.data_ptr(), n, k, f._hs[rep], ids.data_ptr(),
                                                                dist.data_ptr(), C.c_void_p(st)))
         return ids, dist
 
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_save(self._m, str(path).encode()))
+            return
         _lib.check(_lib.lib().cph_save(self._h, str(path).encode()))
 
     def load(self, path):
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_load(self._m, str(path).encode()))
+            return
         _lib.check(_lib.lib().cph_load(self._h, str(path).encode()))
 
     def calib_samples_debug(self, queries, start):
@@ -215,16 +310,25 @@ class CPIndex:
 
     def save_native(self, path):
         """GPU-native file (device block layout; not readable by the reference): fast to load."""
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_save_native(self._m, str(path).encode()))
+            return
         _lib.check(_lib.lib().cph_save_native(self._h, str(path).encode()))
 
     def load_native(self, path):
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_load_native(self._m, str(path).encode()))
+            return
         _lib.check(_lib.lib().cph_load_native(self._h, str(path).encode()))
 
     # -- properties -------------------------------------------------------------------------
     @property
     def size(self):
         n = C.c_uint64(0)
-        _lib.check(_lib.lib().cph_size(self._h, C.byref(n)))
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_size(self._m, C.byref(n)))
+        else:
+            _lib.check(_lib.lib().cph_size(self._h, C.byref(n)))
         return n.value
 
     @property
@@ -234,20 +338,31 @@ class CPIndex:
     @property
     def is_finalized(self):
         f = C.c_int(0)
-        _lib.check(_lib.lib().cph_is_finalized(self._h, C.byref(f)))
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_is_finalized(self._m, C.byref(f)))
+        else:
+            _lib.check(_lib.lib().cph_is_finalized(self._h, C.byref(f)))
         return bool(f.value)
 
     # -- extras (not in the reference) ------------------------------------------------------
     def set_batch_sets(self, n_sets):
-        """Batch scratch sets in rotation (1..4, default 2): batches that can be in flight together on different streams."""
-        _lib.check(_lib.lib().cph_set_batch_sets(self._h, int(n_sets)))
+        """Batch scratch sets in rotation (1..4, default 2): batches that can be in flight together on different streams.
+        A multi-device index sets every replica."""
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_set_batch_sets(h, int(n_sets)))
 
     def set_search_params(self, slots=0, beam_capacity=0):
-        _lib.check(_lib.lib().cph_set_search_params(self._h, int(slots), int(beam_capacity)))
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_set_search_params(h, int(slots), int(beam_capacity)))
 
     def last_search_stats(self):
+        """Work counters of the last batch; a multi-device index' last search_batch: summed over the replicas that
+        took part, kernel_us and capacity their maximum."""
         out = (C.c_uint64 * 12)()
-        _lib.check(_lib.lib().cph_last_search_stats(self._h, out))
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_last_search_stats(self._m, out))
+        else:
+            _lib.check(_lib.lib().cph_last_search_stats(self._h, out))
         keys = ("expansions", "exact_l2", "new_neighbours", "beam_pushes", "stage2_skipped",
                 "rerun_queries", "kernel_us", "expansions_nothing_new", "slots", "capacity",
                 "stage2_reruns", "stage2_undecided")
@@ -255,12 +370,16 @@ class CPIndex:
 
     def synchronize(self):
         """Waits for every batch enqueued with search_batch_device."""
-        _lib.check(_lib.lib().cph_synchronize(self._h))
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_synchronize(h))
 
     def last_query_expansions(self, n):
         """Vertices expanded by each of the n queries of the last batch."""
         out = np.empty(int(n), np.uint32)
-        _lib.check(_lib.lib().cph_last_query_expansions(self._h, out.ctypes.data, int(n)))
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_last_query_expansions(self._m, out.ctypes.data, int(n)))
+        else:
+            _lib.check(_lib.lib().cph_last_query_expansions(self._h, out.ctypes.data, int(n)))
         return out
 
     def order_queries(self, keys):

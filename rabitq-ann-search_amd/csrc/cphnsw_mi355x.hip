@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -32,6 +33,7 @@
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
+#include "multi_device.h"
 #include "native_file.h"
 #include "builder_pipeline.h"
 
@@ -150,6 +152,11 @@ struct cph_index {
     int device = 0;
     bool finalized = false;
     bool needs_build = false;          // build() done, finalize() pending
+    // a replica of a cph_multi (cph_multi_replica hands it out): load, load_native, build, finalize and destroy refuse
+    // it; a replica other than the first holds the host-side scalars of the index but none of its arrays (save,
+    // save_native and get_vectors refuse it too)
+    bool borrowed = false;
+    bool host_less = false;
     std::vector<float> pending;        // vectors handed to build()
     uint64_t pending_n = 0;
     HostIndex host;
@@ -741,7 +748,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 100; }
+int cph_version(void) { return 101; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -783,29 +790,47 @@ int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     });
 }
 
-int cph_destroy(cph_index* h) {
+}  // extern "C"
+
+// Refuses the lifecycle calls of a replica that a cph_multi owns (cph_multi_replica).
+static void refuse_borrowed(const cph_index* h, const char* what) {
+    if (h->borrowed)
+        throw InvalidArg(std::string(what) + " on a replica of a multi-device index: call it on the multi-device handle");
+}
+// ... and the calls that need the host arrays on a replica that keeps none (every replica but the first).
+static void refuse_host_less(const cph_index* h, const char* what) {
+    if (h->host_less)
+        throw InvalidArg(std::string(what) + " on a replica that keeps no host arrays: use replica 0");
+}
+
+static void destroy_index(cph_index* h) {
+    (void)hipSetDevice(h->device);
+    for (auto& s : h->sets) {
+        if (s.used && s.ev_done) (void)hipEventSynchronize(s.ev_done);
+        if (s.ev0) (void)hipEventDestroy(s.ev0);
+        if (s.ev1) (void)hipEventDestroy(s.ev1);
+        if (s.ev_done) (void)hipEventDestroy(s.ev_done);
+        if (s.pin_stats) (void)hipHostFree(s.pin_stats);
+        if (s.pin_io) (void)hipHostFree(s.pin_io);
+    }
+#ifdef CPH_SEARCH_TRACE
+    if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
+                         (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
+    for (auto& x : g_tr) x = 0;
+#endif
+    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    for (auto& ls : h->leaders) {
+        if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
+        if (ls.pin) (void)hipHostFree(ls.pin);
+    }
+    delete h;
+}
+
+extern "C" int cph_destroy(cph_index* h) {
     return guarded([&] {
         if (!h) return;
-        (void)hipSetDevice(h->device);
-        for (auto& s : h->sets) {
-            if (s.used && s.ev_done) (void)hipEventSynchronize(s.ev_done);
-            if (s.ev0) (void)hipEventDestroy(s.ev0);
-            if (s.ev1) (void)hipEventDestroy(s.ev1);
-            if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-            if (s.pin_stats) (void)hipHostFree(s.pin_stats);
-            if (s.pin_io) (void)hipHostFree(s.pin_io);
-        }
-#ifdef CPH_SEARCH_TRACE
-        if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
-                             (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
-        for (auto& x : g_tr) x = 0;
-#endif
-        if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-        for (auto& ls : h->leaders) {
-            if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
-            if (ls.pin) (void)hipHostFree(ls.pin);
-        }
-        delete h;
+        refuse_borrowed(h, "cph_destroy");
+        destroy_index(h);
     });
 }
 
@@ -820,29 +845,37 @@ static void begin_device_swap(cph_index* h) {
     h->last_search = -1;
 }
 
+static void load_v2(cph_index* h, const char* path) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    HostIndex t;
+    t.load(path, h->D, h->bits, h->dim);        // a file that fails to parse leaves the handle as it was
+    begin_device_swap(h);
+    h->host = std::move(t);
+    h->needs_build = false;                       // api/hnsw_index.hpp:442
+    std::vector<float>().swap(h->pending);
+    h->pending_n = 0;
+    h->native_map.reset();
+    h->own_view = nullptr;
+    std::vector<uint8_t>().swap(h->own_store);
+    upload_arrays(h);
+    upload_feeders(h);
+    h->finalized = true;
+}
+
+extern "C" {
+
 int cph_load(cph_index* h, const char* path) {
     return guarded([&] {
         if (!h || !path) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        HostIndex t;
-        t.load(path, h->D, h->bits, h->dim);        // a file that fails to parse leaves the handle as it was
-        begin_device_swap(h);
-        h->host = std::move(t);
-        h->needs_build = false;                       // api/hnsw_index.hpp:442
-        std::vector<float>().swap(h->pending);
-        h->pending_n = 0;
-        h->native_map.reset();
-        h->own_view = nullptr;
-        std::vector<uint8_t>().swap(h->own_store);
-        upload_arrays(h);
-        upload_feeders(h);
-        h->finalized = true;
+        refuse_borrowed(h, "cph_load");
+        load_v2(h, path);
     });
 }
 
 int cph_save(cph_index* h, const char* path) {
     return guarded([&] {
         if (!h || !path) throw InvalidArg("null argument");
+        refuse_host_less(h, "cph_save");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized before saving.");
         materialize_search_data(h);
@@ -853,6 +886,7 @@ int cph_save(cph_index* h, const char* path) {
 int cph_save_native(cph_index* h, const char* path) {
     return guarded([&] {
         if (!h || !path) throw InvalidArg("null argument");
+        refuse_host_less(h, "cph_save_native");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized before saving.");
         h->use_device();
@@ -871,33 +905,42 @@ int cph_save_native(cph_index* h, const char* path) {
     });
 }
 
+}  // extern "C"
+
+static void load_native_file(cph_index* h, const char* path) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    HostIndex t;
+    NativeMapping map;
+    const NativeHeader nh = read_native(path, h->D, h->bits, h->dim, t, map);   // validates everything it maps
+    begin_device_swap(h);
+    h->host = std::move(t);
+    h->needs_build = false;
+    std::vector<float>().swap(h->pending);
+    h->pending_n = 0;
+    h->native_map = std::move(map);
+    const uint8_t* base = static_cast<const uint8_t*>(h->native_map.base);
+    std::vector<uint8_t>().swap(h->own_store);
+    h->own_view = base + nh.own_off;
+    h->L = make_dev_layout((uint32_t)h->host.D, (uint32_t)h->host.bw);
+    const size_t n = h->host.n;
+    h->d_blocks.alloc(n * nh.stride + 64);
+    h->d_raw.alloc(n * h->host.D);
+    h->d_norm.alloc(n);
+    HIP_CHECK(hipMemcpy(h->d_blocks.p, base + nh.blocks_off, n * (size_t)nh.stride, hipMemcpyHostToDevice));
+    relayout_blocks(h->d_blocks.p, n, h->L, true);
+    HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
+    upload_feeders(h);
+    h->finalized = true;
+}
+
+extern "C" {
+
 int cph_load_native(cph_index* h, const char* path) {
     return guarded([&] {
         if (!h || !path) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        HostIndex t;
-        NativeMapping map;
-        const NativeHeader nh = read_native(path, h->D, h->bits, h->dim, t, map);   // validates everything it maps
-        begin_device_swap(h);
-        h->host = std::move(t);
-        h->needs_build = false;
-        std::vector<float>().swap(h->pending);
-        h->pending_n = 0;
-        h->native_map = std::move(map);
-        const uint8_t* base = static_cast<const uint8_t*>(h->native_map.base);
-        std::vector<uint8_t>().swap(h->own_store);
-        h->own_view = base + nh.own_off;
-        h->L = make_dev_layout((uint32_t)h->host.D, (uint32_t)h->host.bw);
-        const size_t n = h->host.n;
-        h->d_blocks.alloc(n * nh.stride + 64);
-        h->d_raw.alloc(n * h->host.D);
-        h->d_norm.alloc(n);
-        HIP_CHECK(hipMemcpy(h->d_blocks.p, base + nh.blocks_off, n * (size_t)nh.stride, hipMemcpyHostToDevice));
-        relayout_blocks(h->d_blocks.p, n, h->L, true);
-        HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
-        upload_feeders(h);
-        h->finalized = true;
+        refuse_borrowed(h, "cph_load_native");
+        load_native_file(h, path);
     });
 }
 
@@ -911,60 +954,74 @@ int cph_is_finalized(cph_index* h, int* flag) {
     return guarded([&] { *flag = h->finalized ? 1 : 0; });
 }
 
+}  // extern "C"
+
+static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    // api/hnsw_index.hpp:93-120: build() replaces any previous state
+    if (n == 0) throw InvalidArg("build requires at least one vector.");
+    if (!vectors) throw InvalidArg("null vectors");
+    h->use_device();
+    quiesce(h);
+    h->host = HostIndex();
+    h->native_map.reset();
+    h->own_view = nullptr;
+    std::vector<uint8_t>().swap(h->own_store);
+    h->finalized = false;
+    h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
+    for (auto& s : h->sets) release_scratch(s);
+    h->pending.assign(vectors, vectors + n * h->dim);
+    h->pending_n = n;
+    h->needs_build = true;
+}
+
+static void finalize_build(cph_index* h) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    // api/hnsw_index.hpp:122-166
+    const uint64_t n = h->needs_build ? h->pending_n : h->host.n;
+    if (n == 0) throw std::runtime_error("Cannot finalize an empty index.");
+    if (!h->needs_build) throw std::runtime_error("Finalize called without a pending build.");
+    if (n < 50) throw std::runtime_error("Calibration requires at least 50 nodes.");
+    if (n >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
+    h->use_device();
+    const bool verbose = getenv("CPH_BUILD_VERBOSE") != nullptr;
+    quiesce(h);
+    h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
+    for (auto& s : h->sets) release_scratch(s);
+    build::BuiltDevice dev;
+    build::build_graph(h->host, dev, h->pending.data(), n, h->dim, h->D, h->bits, h->num_cus, verbose);
+    std::vector<float>().swap(h->pending);
+    h->pending_n = 0;
+    h->needs_build = false;
+    // the pipeline's device arrays are the searchable index: adopt them, no second upload
+    h->d_blocks = std::move(dev.blocks);
+    h->d_raw = std::move(dev.raw);
+    h->d_norm = std::move(dev.norm);
+    h->native_map.reset();
+    h->own_store = std::move(dev.own_host);
+    h->own_view = h->own_store.data();
+    upload_feeders(h);
+    build::DeviceIndexView view{h->d_blocks.p, h->d_raw.p, h->d_signs.p, h->L, h->norm_factor, h->inv_sqrt_d};
+    build::calibrate(h->host, view, h->num_cus, verbose);
+    h->sc = h->host.consts();
+    h->finalized = true;
+}
+
+extern "C" {
+
 int cph_build(cph_index* h, const float* vectors, uint64_t n) {
     return guarded([&] {
         if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        // api/hnsw_index.hpp:93-120: build() replaces any previous state
-        if (n == 0) throw InvalidArg("build requires at least one vector.");
-        if (!vectors) throw InvalidArg("null vectors");
-        h->use_device();
-        quiesce(h);
-        h->host = HostIndex();
-        h->native_map.reset();
-        h->own_view = nullptr;
-        std::vector<uint8_t>().swap(h->own_store);
-        h->finalized = false;
-        h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
-        for (auto& s : h->sets) release_scratch(s);
-        h->pending.assign(vectors, vectors + n * h->dim);
-        h->pending_n = n;
-        h->needs_build = true;
+        refuse_borrowed(h, "cph_build");
+        build_pending(h, vectors, n);
     });
 }
 
 int cph_finalize(cph_index* h) {
     return guarded([&] {
         if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        // api/hnsw_index.hpp:122-166
-        const uint64_t n = h->needs_build ? h->pending_n : h->host.n;
-        if (n == 0) throw std::runtime_error("Cannot finalize an empty index.");
-        if (!h->needs_build) throw std::runtime_error("Finalize called without a pending build.");
-        if (n < 50) throw std::runtime_error("Calibration requires at least 50 nodes.");
-        if (n >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
-        h->use_device();
-        const bool verbose = getenv("CPH_BUILD_VERBOSE") != nullptr;
-        quiesce(h);
-        h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
-        for (auto& s : h->sets) release_scratch(s);
-        build::BuiltDevice dev;
-        build::build_graph(h->host, dev, h->pending.data(), n, h->dim, h->D, h->bits, h->num_cus, verbose);
-        std::vector<float>().swap(h->pending);
-        h->pending_n = 0;
-        h->needs_build = false;
-        // the pipeline's device arrays are the searchable index: adopt them, no second upload
-        h->d_blocks = std::move(dev.blocks);
-        h->d_raw = std::move(dev.raw);
-        h->d_norm = std::move(dev.norm);
-        h->native_map.reset();
-        h->own_store = std::move(dev.own_host);
-        h->own_view = h->own_store.data();
-        upload_feeders(h);
-        build::DeviceIndexView view{h->d_blocks.p, h->d_raw.p, h->d_signs.p, h->L, h->norm_factor, h->inv_sqrt_d};
-        build::calibrate(h->host, view, h->num_cus, verbose);
-        h->sc = h->host.consts();
-        h->finalized = true;
+        refuse_borrowed(h, "cph_finalize");
+        finalize_build(h);
     });
 }
 
@@ -1147,6 +1204,7 @@ int cph_calib_hook(cph_index* h, const float* queries, const uint32_t* start, ui
 int cph_get_vectors(cph_index* h, uint64_t first, uint64_t count, float* out) {
     return guarded([&] {
         if (!h || !out) throw InvalidArg("null argument");
+        refuse_host_less(h, "cph_get_vectors");
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
         if (first + count > h->host.n) throw InvalidArg("vector range out of bounds");
@@ -1920,6 +1978,321 @@ int cph_fastscan_stream_destroy(cph_stream* s) {
         if (s->ev0) (void)hipEventDestroy(s->ev0);
         if (s->ev1) (void)hipEventDestroy(s->ev1);
         delete s;
+    });
+}
+
+}  // extern "C"
+
+// ---- one index on several devices: in-process replicas (cph_multi_*, multi_device.h) ------------------------------
+// Every replica is a complete cph_index on its device.  Lifecycle calls run on replica 0 (the only one with host
+// arrays), then replicas 1..N-1 receive replica 0's device arrays by device-to-device copy.  A batch is split into
+// contiguous shards, one per replica, each answered by the existing single-device cph_search_batch[_filtered] on that
+// replica's persistent worker thread, straight into the caller's rows.
+struct cph_multi {
+    std::vector<cph_index*> reps;             // reps[i] on devices[i]; owned (destroy_index)
+    std::unique_ptr<ReplicaPool> pool;        // one worker thread per replica
+    std::shared_mutex life;                   // searches hold it shared; load / build / finalize / destroy exclusively
+    std::atomic<uint64_t> rr{0};              // round robin: whole (small) batches and single queries
+    std::atomic<uint64_t> min_shard{kDefaultMinShard};
+    std::mutex last_mu;
+    std::vector<Shard> last_plan;             // the shards of the last successful cph_multi_search_batch[_filtered]
+    ~cph_multi() {
+        pool.reset();                         // joins the workers
+        for (cph_index* h : reps) destroy_index(h);
+    }
+};
+
+namespace {
+
+[[noreturn]] void raise_status(int rc, const std::string& msg) {
+    if (rc == CPH_INVALID_ARGUMENT) throw InvalidArg(msg);
+    if (rc == CPH_OUT_OF_MEMORY) throw std::bad_alloc();
+    throw std::runtime_error(msg);
+}
+void check_rc(int rc) {
+    if (rc != CPH_OK) raise_status(rc, g_err);
+}
+
+// The host-side scalars of an index (what the search path reads: sizes, entry point, calibration), none of its arrays.
+HostIndex host_scalars(const HostIndex& s) {
+    HostIndex t;
+    t.D = s.D; t.bw = s.bw; t.dim = s.dim; t.n = s.n;
+    t.max_level = s.max_level;
+    t.entry = s.entry;
+    t.upper_tau = s.upper_tau; t.upper_alpha = s.upper_alpha;
+    t.mL = s.mL;
+    t.seed = s.seed;
+    std::memcpy(t.calib, s.calib, sizeof(t.calib));
+    std::memcpy(t.profile, s.profile, sizeof(t.profile));
+    t.RL = s.RL;
+    t.has_dup_neighbors = s.has_dup_neighbors;
+    return t;
+}
+
+// dst becomes a searchable copy of the finalized src: src's resident device arrays (blocks in the resident layout,
+// vectors, norms, rotation signs, upper layers, row maps) copied device to device (no peer access needed), its search
+// scalars copied, the upper-layer pointers rebased onto dst's own buffers.  dst keeps no host arrays.
+void replicate(cph_index* src, cph_index* dst) {
+    std::lock_guard<std::mutex> ls(src->mu), ld(dst->mu);
+    if (!src->finalized) throw std::runtime_error("replicate: the first replica is not finalized");
+    src->use_device();
+    HIP_CHECK(hipDeviceSynchronize());          // whatever wrote the source arrays has landed
+    begin_device_swap(dst);
+    dst->host = host_scalars(src->host);
+    dst->needs_build = false;
+    std::vector<float>().swap(dst->pending);
+    dst->pending_n = 0;
+    dst->native_map.reset();
+    dst->own_view = nullptr;
+    std::vector<uint8_t>().swap(dst->own_store);
+    dst->L = src->L;
+    dst->sc = src->sc;
+    dst->flags = src->flags;
+    dst->dev_max_level = src->dev_max_level;
+    dst->norm_factor = src->norm_factor;
+    dst->inv_sqrt_d = src->inv_sqrt_d;
+    hipStream_t st = own_stream(dst);
+    auto copy = [&](auto& d, const auto& s) {
+        d.alloc(s.n);
+        if (s.n) HIP_CHECK(hipMemcpyPeerAsync(d.p, dst->device, s.p, src->device, s.n * sizeof(*s.p), st));
+    };
+    copy(dst->d_blocks, src->d_blocks);
+    copy(dst->d_raw, src->d_raw);
+    copy(dst->d_norm, src->d_norm);
+    copy(dst->d_signs, src->d_signs);
+    copy(dst->d_upper, src->d_upper);
+    copy(dst->d_row_of, src->d_row_of);
+    HIP_CHECK(hipStreamSynchronize(st));
+    auto rebase = [](const uint32_t* p, const DevBuf<uint32_t>& from, const DevBuf<uint32_t>& to) -> const uint32_t* {
+        return p ? to.p + (p - from.p) : nullptr;
+    };
+    for (int l = 0; l < kMaxUpperLayers; ++l) {
+        const UpperLayerDev& s = src->layers[l];
+        dst->layers[l] = UpperLayerDev{rebase(s.nodes, src->d_upper, dst->d_upper), rebase(s.offsets, src->d_upper, dst->d_upper),
+                                       rebase(s.nbrs, src->d_upper, dst->d_upper), rebase(s.row_of, src->d_row_of, dst->d_row_of),
+                                       s.n_nodes};
+    }
+    dst->auto_cap = 0;
+    dst->pf_off = false;
+    dst->pf_dense = false;
+    dst->last_search = -1;
+    dst->finalized = true;
+}
+
+// A lifecycle call: `first` on replica 0, then every other replica copies it.  If it fails after replica 0 gave up
+// its old index, no replica stays searchable (they would answer from different indexes).
+template <class F>
+void multi_lifecycle(cph_multi* m, F&& first) {
+    std::unique_lock<std::shared_mutex> lk(m->life);
+    cph_index* r0 = m->reps[0];
+    bool first_done = false;
+    try {
+        first(r0);
+        first_done = true;
+        for (size_t i = 1; i < m->reps.size(); ++i) replicate(r0, m->reps[i]);
+    } catch (...) {
+        if (first_done || !r0->finalized)
+            for (cph_index* h : m->reps) {
+                std::lock_guard<std::mutex> g(h->mu);
+                h->finalized = false;
+            }
+        throw;
+    }
+}
+
+// cph_multi_search_batch[_filtered]: f = one filter per replica, or null.
+void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
+                        int64_t* ids, float* dist) {
+    if (!m) throw InvalidArg("null handle");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    const uint32_t R = (uint32_t)m->reps.size();
+    if (f)
+        for (uint32_t r = 0; r < R; ++r) {
+            cph_index* h = m->reps[r];
+            std::lock_guard<std::mutex> g(h->mu);
+            require_finalized(h);
+            if (!f[r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
+            check_filter(h, f[r]);
+        }
+    const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
+    const uint64_t dim = m->reps[0]->dim;
+    std::string err;
+    const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
+        cph_index* h = m->reps[s.replica];
+        const float* q = queries ? queries + s.lo * dim : nullptr;
+        int64_t* oi = ids ? ids + s.lo * k : nullptr;
+        float* od = dist ? dist + s.lo * k : nullptr;
+        const int r = f ? cph_search_batch_filtered(h, q, s.hi - s.lo, k, f[s.replica], oi, od)
+                        : cph_search_batch(h, q, s.hi - s.lo, k, oi, od);
+        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
+        return r;
+    }, err);
+    if (rc != CPH_OK) raise_status(rc, err);
+    std::lock_guard<std::mutex> g(m->last_mu);
+    m->last_plan = plan;
+}
+
+template <class F>
+int multi_shared(cph_multi* m, F&& f) {
+    if (!m) return fail(CPH_INVALID_ARGUMENT, "null handle");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    return f();
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_multi_create(uint64_t dim, uint64_t bits, const int* devices, uint32_t n_dev, cph_multi** out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("out must not be null");
+        *out = nullptr;
+        if (!devices) throw InvalidArg("devices must not be null");
+        if (n_dev < 1 || n_dev > kMaxReplicas) throw InvalidArg("n_dev must be 1.." + std::to_string(kMaxReplicas));
+        std::unique_ptr<cph_multi> m(new cph_multi());
+        for (uint32_t i = 0; i < n_dev; ++i) {
+            cph_index* h = nullptr;
+            check_rc(cph_create(dim, bits, devices[i], &h));
+            h->borrowed = true;
+            h->host_less = i > 0;
+            m->reps.push_back(h);
+        }
+        cph_multi* raw = m.get();
+        m->pool.reset(new ReplicaPool(n_dev, [raw](uint32_t r) { (void)hipSetDevice(raw->reps[r]->device); }));
+        *out = m.release();
+    });
+}
+
+int cph_multi_destroy(cph_multi* m) {
+    return guarded([&] {
+        if (!m) return;
+        { std::unique_lock<std::shared_mutex> lk(m->life); }   // searches in flight finish first
+        delete m;
+    });
+}
+
+int cph_multi_load(cph_multi* m, const char* path) {
+    return guarded([&] {
+        if (!m || !path) throw InvalidArg("null argument");
+        multi_lifecycle(m, [&](cph_index* r0) { load_v2(r0, path); });
+    });
+}
+
+int cph_multi_load_native(cph_multi* m, const char* path) {
+    return guarded([&] {
+        if (!m || !path) throw InvalidArg("null argument");
+        multi_lifecycle(m, [&](cph_index* r0) { load_native_file(r0, path); });
+    });
+}
+
+int cph_multi_save(cph_multi* m, const char* path) {
+    return multi_shared(m, [&] { return cph_save(m->reps[0], path); });
+}
+
+int cph_multi_save_native(cph_multi* m, const char* path) {
+    return multi_shared(m, [&] { return cph_save_native(m->reps[0], path); });
+}
+
+int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        build_pending(m->reps[0], vectors, n);
+        for (size_t i = 1; i < m->reps.size(); ++i) {   // the old index goes from every replica (finalize copies the new one)
+            cph_index* h = m->reps[i];
+            std::lock_guard<std::mutex> g(h->mu);
+            begin_device_swap(h);
+            h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
+            h->host = HostIndex();
+        }
+    });
+}
+
+int cph_multi_finalize(cph_multi* m) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        multi_lifecycle(m, [&](cph_index* r0) { finalize_build(r0); });
+    });
+}
+
+int cph_multi_size(cph_multi* m, uint64_t* n) {
+    return multi_shared(m, [&] { return cph_size(m->reps[0], n); });
+}
+
+int cph_multi_is_finalized(cph_multi* m, int* flag) {
+    return multi_shared(m, [&] { return cph_is_finalized(m->reps[0], flag); });
+}
+
+int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist) {
+    return guarded([&] { multi_search_batch(m, queries, n, k, nullptr, ids, dist); });
+}
+
+int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
+                                    const cph_filter* const* f, int64_t* ids, float* dist) {
+    return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist); });
+}
+
+int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count) {
+    // one replica per caller, round robin: that replica's coalescer gathers its callers (its error text is ours:
+    // cph_search runs on this thread)
+    return multi_shared(m, [&] { return cph_search(m->reps[m->rr.fetch_add(1) % m->reps.size()], query, k, ids, dist, count); });
+}
+
+int cph_multi_set_min_shard(cph_multi* m, uint64_t q) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        if (q == 0) throw InvalidArg("min_shard must be >= 1");
+        m->min_shard.store(q);
+    });
+}
+
+int cph_multi_last_search_stats(cph_multi* m, uint64_t out[12]) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::vector<Shard> plan;
+        {
+            std::lock_guard<std::mutex> g(m->last_mu);
+            plan = m->last_plan;
+        }
+        uint64_t acc[12] = {};
+        for (const Shard& s : plan) {
+            uint64_t w[12];
+            check_rc(cph_last_search_stats(m->reps[s.replica], w));
+            for (int i = 0; i < 12; ++i)
+                acc[i] = (i == 6 || i == 9) ? std::max(acc[i], w[i]) : acc[i] + w[i];   // kernel_us, capacity: the max
+        }
+        std::memcpy(out, acc, sizeof(acc));
+    });
+}
+
+int cph_multi_last_query_expansions(cph_multi* m, uint32_t* out, uint64_t n) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::vector<Shard> plan;
+        {
+            std::lock_guard<std::mutex> g(m->last_mu);
+            plan = m->last_plan;
+        }
+        if (plan.empty() || plan.back().hi != n) throw InvalidArg("n must equal the size of the last batch");
+        for (const Shard& s : plan)
+            if (s.hi > s.lo) check_rc(cph_last_query_expansions(m->reps[s.replica], out + s.lo, s.hi - s.lo));
+    });
+}
+
+int cph_multi_num_replicas(cph_multi* m, uint32_t* n) {
+    return guarded([&] {
+        if (!m || !n) throw InvalidArg("null argument");
+        *n = (uint32_t)m->reps.size();
+    });
+}
+
+int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        if (i >= m->reps.size()) throw InvalidArg("replica index out of range");
+        *out = m->reps[i];
     });
 }
 

@@ -72,8 +72,8 @@ size_t next_pow2(size_t n) {
     return p;
 }
 
-// kernel dispatch over (bits, static D): D == 128 and D == 1024 (the BASELINE shapes) get instantiations with a
-// compile-time D -- every code load of a block in flight at once, the vertex vector through LDS-DMA
+// kernel dispatch over (bits, static D) of block_hook_kernel and fastscan_stream_kernel: D == 128 and D == 1024 (the
+// BASELINE shapes) get instantiations with a compile-time D.  (The search kernel has its own table: launch_search_kernel.)
 #define CPH_LAUNCH_BITS(KERNEL, bits, SDV, grid, block, lds, st, args)                            \
     do {                                                                                          \
         if ((bits) == 1) hipLaunchKernelGGL((KERNEL<1, SDV>), grid, block, lds, st, args);        \
@@ -108,9 +108,7 @@ struct BatchSet {
     DevBuf<QueryHeader> d_qhdr;
     DevBuf<int64_t> d_ids;
     DevBuf<uint32_t> d_count, d_status, d_order, d_redo;
-    // u64 words: [0..15] counters | [16] lo = work-queue counter, hi = length of the re-run list |
-    // [17] lo = work-queue counter of the re-run launch
-    DevBuf<unsigned long long> d_stats;
+    DevBuf<unsigned long long> d_stats;        // kStatWords u64 words: counters, then the work queues (device_search.h: StatWord)
     unsigned long long* pin_stats = nullptr;   // pinned host copy, written at the end of every batch
     // small batches (cph_search, cph_search_batch with a handful of queries): queries are read and results written by
     // the kernels straight from / to this pinned, device-mapped host buffer -- no copy commands at all
@@ -133,7 +131,6 @@ struct BatchSet {
     uint64_t run_cap = 0;     // per-slot capacity that launch ran with (n + 1 on the full-capacity slots of the small-batch path)
     bool stats_in_hbm = false; // the last batch's statistics were not copied to pin_stats yet
 };
-constexpr int kStatWords = 18;
 constexpr int kMaxBatchSets = 4;
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 
@@ -200,7 +197,7 @@ struct cph_index {
     // a leader slot's resources: a stream, a pinned device-mapped I/O buffer and a batch set (sets[kMaxBatchSets + i])
     struct LeaderSlot {
         hipStream_t stream = nullptr;
-        uint8_t* pin = nullptr;        // [flags kLeaderGroup x u32 | ids n*k*8 | dist n*k*4 | counts n*4 | queries n*dim*4]
+        uint8_t* pin = nullptr;        // [flags kLeaderGroup x u32 | PinnedIo]
         uint8_t* pin_dev = nullptr;
         size_t pin_bytes = 0;
         uint32_t seq = 0;              // launch counter: the value the kernels write into the flags of THIS launch
@@ -217,6 +214,36 @@ namespace {
 // bit 1: scalar tails), goes to the instantiation without it; so does a workload on which most neighbours are new (pf_dense).
 bool probe_first(const cph_index* h) {
     return (h->L.D == 128 || h->L.D == 1024) && !(h->flags & 2u) && !h->pf_off && !h->pf_dense;
+}
+
+// The two stage-2 counters of a finished batch (w = kStatStage2Reruns / kStatStage2Undecided).  The diagnostic builds
+// keep their cycle / traffic counters in those words and the kernel does not flush the two there: they read as 0.
+uint64_t stage2_stat(const BatchSet& s, StatWord w) {
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+    (void)s; (void)w;
+    return 0;
+#else
+    return s.pin_stats[w];
+#endif
+}
+
+// What earlier batches taught the handle about its index: void once the index changes.
+void reset_adaptation(cph_index* h) {
+    h->auto_cap = 0;
+    h->pf_off = false;
+    h->pf_dense = false;
+    h->last_search = -1;
+}
+
+// The host-side leftovers of the previous index: vectors waiting for finalize(), the native file's mapping, the own-code
+// headers of an index built here.
+void drop_host_state(cph_index* h) {
+    h->needs_build = false;                       // api/hnsw_index.hpp:442
+    std::vector<float>().swap(h->pending);
+    h->pending_n = 0;
+    h->native_map.reset();
+    h->own_view = nullptr;
+    std::vector<uint8_t>().swap(h->own_store);
 }
 
 void require_finalized(cph_index* h) {
@@ -339,10 +366,7 @@ void upload_feeders(cph_index* h) {
                                      h->d_upper.p + off_nbrs[l], dmap, (uint32_t)hi.upper[l].size()};
     }
     for (auto& s : h->sets) release_scratch(s);
-    h->auto_cap = 0;
-    h->pf_off = false;
-    h->pf_dense = false;
-    h->last_search = -1;
+    reset_adaptation(h);
 }
 
 // The reference-layout image of an index that came from a native file: own-code headers from the mapping,
@@ -387,18 +411,19 @@ BatchSet& next_set(cph_index* h, hipStream_t st) {
     // (either set's finished batch counts: the other set's is the more recent one)
     for (BatchSet& o : h->sets) {
         if (!(o.used && o.ev_done && !o.stats_in_hbm && hipEventQuery(o.ev_done) == hipSuccess)) continue;
-        // [5] = queries re-run, [8] = those of them that were re-run for a stage-2 decision (probe first), not for capacity
-        if (o.pin_stats[5] > o.pin_stats[8] && o.cap < h->host.n + 1)
+        // queries re-run, and those of them that were re-run for a stage-2 decision (probe first), not for capacity
+        const uint64_t reruns = o.pin_stats[kStatReruns], stage2_reruns = stage2_stat(o, kStatStage2Reruns);
+        if (reruns > stage2_reruns && o.cap < h->host.n + 1)
             h->auto_cap = std::max<uint64_t>(h->auto_cap, std::min<uint64_t>(h->host.n + 1, o.cap * 4));
-        if (o.pin_stats[8] * 50 > o.nq) h->pf_off = true;
+        if (stage2_reruns * 50 > o.nq) h->pf_off = true;
         // Probe first pays when few of a block's neighbours are new (C2: 3.3 of 32 -- 40 % of the code lines are never
         // fetched); on a workload where most expansions find new neighbours in every group of eight it only adds a
         // dependent round trip (Gaussian 1M at 4 bits: 9.7 new per expansion, 13 % slower with it).  Decided from the
         // finished batches' own counters, with hysteresis; results are the same either way.
         // Narrow codes have less to skip (512 B / 1 KB of codes against 2 KB) and lose the estimator's overlap with the
         // probe: their break-even is lower (2-bit: +12 % at 1.5 new per expansion, -3.5 % at 5.3; 1-bit: +8 % at 1.0).
-        if (o.pin_stats[0] >= 10000) {
-            const double new_per_exp = (double)o.pin_stats[2] / (double)o.pin_stats[0];
+        if (o.pin_stats[kStatExpansions] >= 10000) {
+            const double new_per_exp = (double)o.pin_stats[kStatNew] / (double)o.pin_stats[kStatExpansions];
             const double off = h->bits == 4 ? 6.0 : 2.8, on = h->bits == 4 ? 4.5 : 2.2;
             if (new_per_exp > off) h->pf_dense = true;
             else if (new_per_exp < on) h->pf_dense = false;
@@ -488,35 +513,62 @@ void ensure_scratch(cph_index* h, BatchSet& s, uint32_t slots, uint64_t cap, hip
     }
 }
 
-// mode 0: the batch on the set's slots (capacity s.cap); 1: the overflow re-run on the full-capacity slots (its list of
-// queries lives on the device); 2: a batch small enough for the full-capacity slots, run there directly (no re-run needed)
 struct DoneFlags {          // per-query completion flags in pinned host memory (coalesced cph_search), or none
     uint32_t* flags = nullptr;
     uint32_t seq = 0;
 };
 
-// The filtered instantiations: no probe first (D = 128 / 1024 with a compile-time D, the generic one elsewhere).
-template <int SD>
-void launch_filtered(uint32_t bits, uint32_t grid, size_t lds, hipStream_t st, const SearchArgs& a) {
-    if (bits == 1) hipLaunchKernelGGL((search_kernel<1, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
-    else if (bits == 2) hipLaunchKernelGGL((search_kernel<2, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((search_kernel<4, SD, false, true>), dim3(grid), dim3(64), lds, st, a);
+// The launches of a batch (launch_search).
+enum class Launch {
+    Main,     // the batch on the set's slots (capacity s.cap); the only launch that may probe first
+    Rerun,    // behind Main, on the full-capacity slots: the queries Main handed over (their list lives on the device)
+    Direct,   // a batch small enough for the full-capacity slots, run there at once: nothing can overflow, no re-run
+};
+
+// The one table of search_kernel instantiations (24) and the only place that names them.
+//   filtered (a filtered batch never probes first)          <BW, D or 0, false, true>
+//   unfiltered, static D (128, 1024), probe first           <BW, D, true, false>      Launch::Main while probe_first(h)
+//   unfiltered, static D, no probe first                    <BW, D, false, false>     re-run, direct, probe first off
+//   unfiltered, any other D                                 <BW, 0, true, false>
+// Without probe first the codes are fetched with the ids: no third dependent round trip for a handful of queries
+// (latency, not traffic); it takes the stage-2 decisions the probe-first launch hands over, evaluates the scalar tails
+// of short neighbour lists (flags bit 1) and serves the workloads on which probe first does not pay.
+// The last row has no <BW, 0, false, false> twin: probe first exists for SD >= 128 only (device_search.h: kProbeFirst,
+// kStaticLayout), so with SD = 0 the PF argument is inert and both values would be the same kernel compiled twice.
+void launch_search_kernel(uint32_t bits, uint32_t D, bool pf, bool filtered, uint32_t grid, size_t lds, hipStream_t st,
+                          const SearchArgs& a) {
+    using Kernel = void (*)(SearchArgs);
+    // [bits 1, 2, 4][D other, 128, 1024][no probe first, probe first, filtered]
+    static const Kernel table[3][3][3] = {
+        {{search_kernel<1, 0, true, false>, search_kernel<1, 0, true, false>, search_kernel<1, 0, false, true>},
+         {search_kernel<1, 128, false, false>, search_kernel<1, 128, true, false>, search_kernel<1, 128, false, true>},
+         {search_kernel<1, 1024, false, false>, search_kernel<1, 1024, true, false>, search_kernel<1, 1024, false, true>}},
+        {{search_kernel<2, 0, true, false>, search_kernel<2, 0, true, false>, search_kernel<2, 0, false, true>},
+         {search_kernel<2, 128, false, false>, search_kernel<2, 128, true, false>, search_kernel<2, 128, false, true>},
+         {search_kernel<2, 1024, false, false>, search_kernel<2, 1024, true, false>, search_kernel<2, 1024, false, true>}},
+        {{search_kernel<4, 0, true, false>, search_kernel<4, 0, true, false>, search_kernel<4, 0, false, true>},
+         {search_kernel<4, 128, false, false>, search_kernel<4, 128, true, false>, search_kernel<4, 128, false, true>},
+         {search_kernel<4, 1024, false, false>, search_kernel<4, 1024, true, false>, search_kernel<4, 1024, false, true>}},
+    };
+    const Kernel kernel = table[bits == 1 ? 0 : bits == 2 ? 1 : 2][D == 128 ? 1 : D == 1024 ? 2 : 0][filtered ? 2 : pf ? 1 : 0];
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, st, a);
     HIP_CHECK(hipGetLastError());
 }
 
-// d_allow: the allowed-id bitmap of a filtered batch (cph_filter::words), or null.  A filtered batch never probes first.
+// d_allow: the allowed-id bitmap of a filtered batch (cph_filter::words), or null.
 void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist, uint32_t* d_count,
-                   const uint32_t* d_todo, int mode, hipStream_t st, DoneFlags done = DoneFlags(),
+                   const uint32_t* d_todo, Launch mode, hipStream_t st, DoneFlags done = DoneFlags(),
                    const uint32_t* d_allow = nullptr) {
+    const uint64_t n = h->host.n;
+    const bool pf = mode == Launch::Main && d_allow == nullptr && probe_first(h);
     SearchArgs a{};
     a.allow = d_allow;
-    const bool pf = d_allow == nullptr && probe_first(h);
     a.done_flags = done.flags;
     a.done_seq = done.seq;
     a.blocks = h->d_blocks.p;
     a.raw = h->d_raw.p;
     a.norm_sq = h->d_norm.p;
-    a.n = h->host.n;
+    a.n = n;
     a.L = h->L;
     a.flags = h->flags;
     a.queries = s.d_queries.p;
@@ -524,65 +576,51 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     a.qhdr = s.d_qhdr.p;
     a.k = k;
     a.sc = h->sc;
-    a.bm_words = (h->host.n + 31) / 32;
+    a.bm_words = (n + 31) / 32;
     a.out_ids = d_ids;
     a.out_dist = d_dist;
     a.out_count = d_count;
     a.status = s.d_status.p;
     a.stats = s.d_stats.p;
-    uint32_t* words = reinterpret_cast<uint32_t*>(s.d_stats.p + 16);   // [0] queue, [1] re-run list length, [2] re-run queue
-    uint32_t grid;
-    if (mode == 0) {
-        a.todo = d_todo;
-        a.nq = nq;
-        a.counter = words;
+    if (mode == Launch::Main) {     // the set's own slots ...
         a.cap = s.cap;
         a.bitmaps = s.d_bitmaps.p;
         a.beam_pages = s.d_beam.p;
         a.beam_tail = s.d_beam_tail.p;
         a.log_ids = s.d_logids.p;
-        a.redo = (s.cap < h->host.n + 1 || pf) ? s.d_redo.p : nullptr;
-        a.redo_count = words + 1;
-        grid = s.run_slots;
-    } else {
-        a.todo = mode == 1 ? s.d_redo.p : nullptr;
-        a.nq = mode == 1 ? 0 : nq;
-        a.nq_dev = mode == 1 ? words + 1 : nullptr;
-        a.counter = mode == 1 ? words + 2 : words;
-        a.cap = h->host.n + 1;
+    } else {                        // ... or its full-capacity ones
+        a.cap = n + 1;
         a.bitmaps = s.r_bitmaps.p;
         a.beam_pages = s.r_beam.p;
         a.beam_tail = s.r_beam_tail.p;
         a.log_ids = s.r_logids.p;
-        grid = mode == 1 ? s.r_slots : nq;
+    }
+    uint32_t* queue = reinterpret_cast<uint32_t*>(s.d_stats.p + kStatQueues);   // StatQueueWord
+    uint32_t grid = 0;
+    switch (mode) {
+    case Launch::Main:
+        a.todo = d_todo;
+        a.nq = nq;
+        a.counter = queue + kQueueMain;
+        a.redo = (s.cap < n + 1 || pf) ? s.d_redo.p : nullptr;
+        a.redo_count = queue + kQueueRerunLen;
+        grid = s.run_slots;
+        break;
+    case Launch::Rerun:
+        a.todo = s.d_redo.p;
+        a.nq_dev = queue + kQueueRerunLen;
+        a.counter = queue + kQueueRerun;
+        grid = s.r_slots;
+        break;
+    case Launch::Direct:
+        a.nq = nq;
+        a.counter = queue + kQueueMain;
+        grid = nq;
+        break;
     }
     const size_t lds = search_lds_bytes(h->L.D, h->L.PW, k);
     if (lds > 160 * 1024) throw InvalidArg("k too large for the on-chip result heap");
-    if (d_allow) {
-        if (h->L.D == 1024) launch_filtered<1024>(h->bits, grid, lds, st, a);
-        else if (h->L.D == 128) launch_filtered<128>(h->bits, grid, lds, st, a);
-        else launch_filtered<0>(h->bits, grid, lds, st, a);
-        return;
-    }
-    if ((mode != 0 || !pf) && h->L.D == 1024) {
-        if (h->bits == 1) hipLaunchKernelGGL((search_kernel<1, 1024, false>), dim3(grid), dim3(64), lds, st, a);
-        else if (h->bits == 2) hipLaunchKernelGGL((search_kernel<2, 1024, false>), dim3(grid), dim3(64), lds, st, a);
-        else hipLaunchKernelGGL((search_kernel<4, 1024, false>), dim3(grid), dim3(64), lds, st, a);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if ((mode != 0 || !pf) && h->L.D == 128) {
-        // a handful of queries: latency, not traffic -- the order of loads without the third dependent round trip.  Also
-        // the instantiation of the re-run launch (it takes the stage-2 decisions the probe-first one hands over), of an
-        // index with short neighbour lists (flags bit 1: it evaluates their scalar tails) and of workloads on which
-        // probe first does not pay.
-        if (h->bits == 1) hipLaunchKernelGGL((search_kernel<1, 128, false>), dim3(grid), dim3(64), lds, st, a);
-        else if (h->bits == 2) hipLaunchKernelGGL((search_kernel<2, 128, false>), dim3(grid), dim3(64), lds, st, a);
-        else hipLaunchKernelGGL((search_kernel<4, 128, false>), dim3(grid), dim3(64), lds, st, a);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    CPH_LAUNCH(search_kernel, h->bits, h->L.D, dim3(grid), dim3(64), lds, st, a);
+    launch_search_kernel(h->bits, h->L.D, pf, d_allow != nullptr, grid, lds, st, a);
 }
 
 // Statistics block to pinned memory, completion event, bookkeeping: the tail of every enqueued batch.
@@ -692,10 +730,10 @@ void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t*
         // a handful of queries: straight onto the full-capacity slots -- one launch, nothing can overflow
         s.run_slots = nq;
         s.run_cap = n + 1;
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 2, st, done, d_allow);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Direct, st, done, d_allow);
     } else {
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, 0, st, done, d_allow);
-        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, 1, st, done, d_allow);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, Launch::Main, st, done, d_allow);
+        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Rerun, st, done, d_allow);
     }
     finish_batch(h, s, st);
 }
@@ -705,31 +743,106 @@ hipStream_t own_stream(cph_index* h) {
     return h->own_stream;
 }
 
-// Views into a set's pinned, device-mapped I/O buffer for a batch of `n` queries: [ids n*k*8 | dist n*k*4 | counts n*4 |
-// queries n*dim*4], host and device addresses of the same bytes.
-struct SmallIo {
-    int64_t* h_ids; float* h_dist; uint32_t* h_count; float* h_query;
-    int64_t* d_ids; float* d_dist; uint32_t* d_count; const float* d_query;
-};
-SmallIo small_io(cph_index* h, BatchSet& s, uint64_t n, uint64_t k) {
-    const size_t o_dist = n * k * 8, o_cnt = o_dist + n * k * 4, o_q = (o_cnt + n * 4 + 15) & ~(size_t)15;
-    const size_t need = o_q + n * h->dim * 4;
-    if (s.pin_io_bytes < need) {
-        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-        if (s.pin_io) HIP_CHECK(hipHostFree(s.pin_io));
-        s.pin_io = nullptr;
-        s.pin_io_bytes = 0;
-        const size_t bytes = std::max<size_t>(need * 2, 64 * 1024);
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.pin_io), bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.pin_io_dev), s.pin_io, 0));
-        s.pin_io_bytes = bytes;
+// A batch of `n` queries in a pinned, device-mapped host buffer, read and written by the kernels over PCIe:
+// [prefix | ids n*k*8 | dist n*k*4 | counts n*4 | pad to 16 | queries n*dim*4].  prefix: 0 for a batch set's buffer,
+// kFlagBytes (the per-query completion flags) for a leader slot's.  The accessors take the buffer's host or device address.
+constexpr size_t kFlagBytes = kLeaderGroup * 4;
+struct PinnedIo {
+    size_t o_ids, o_dist, o_cnt, o_q, need;
+    PinnedIo(uint64_t n, uint64_t k, uint64_t dim, size_t prefix) {
+        o_ids = prefix;
+        o_dist = o_ids + n * k * 8;
+        o_cnt = o_dist + n * k * 4;
+        o_q = (o_cnt + n * 4 + 15) & ~(size_t)15;
+        need = o_q + n * dim * 4;
     }
-    uint8_t* hb = s.pin_io;
-    uint8_t* db = s.pin_io_dev;
-    return SmallIo{reinterpret_cast<int64_t*>(hb), reinterpret_cast<float*>(hb + o_dist), reinterpret_cast<uint32_t*>(hb + o_cnt),
-                   reinterpret_cast<float*>(hb + o_q),
-                   reinterpret_cast<int64_t*>(db), reinterpret_cast<float*>(db + o_dist), reinterpret_cast<uint32_t*>(db + o_cnt),
-                   reinterpret_cast<const float*>(db + o_q)};
+    int64_t* ids(uint8_t* base) const { return reinterpret_cast<int64_t*>(base + o_ids); }
+    float* dist(uint8_t* base) const { return reinterpret_cast<float*>(base + o_dist); }
+    uint32_t* counts(uint8_t* base) const { return reinterpret_cast<uint32_t*>(base + o_cnt); }
+    float* queries(uint8_t* base) const { return reinterpret_cast<float*>(base + o_q); }
+};
+
+// Replaces a pinned, device-mapped buffer that is smaller than `need` (its contents are lost; the caller knows that
+// nothing in flight uses it) and says whether it did.
+bool grow_pinned(uint8_t*& host, uint8_t*& dev, size_t& bytes, size_t need) {
+    if (bytes >= need) return false;
+    if (host) HIP_CHECK(hipHostFree(host));
+    host = nullptr;
+    bytes = 0;
+    const size_t want = std::max<size_t>(need * 2, 64 * 1024);
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host), want, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0));
+    bytes = want;
+    return true;
+}
+
+void check_filter(const cph_index* h, const cph_filter* f) {
+    if (f->device != h->device) throw InvalidArg("filter belongs to another device");
+    if (f->n_bits != h->host.n)
+        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " ids, the index holds " + std::to_string(h->host.n));
+}
+
+// What every batch entry checks, under the handle mutex, before it touches the device; false: nothing to do ((n, 0)
+// outputs: nothing to write; the entry point has been validated like search()'s).
+bool batch_has_work(cph_index* h, const cph_filter* f, const float* queries, uint64_t n, uint64_t k, const int64_t* ids,
+                    const float* dist) {
+    require_finalized(h);
+    if (f) check_filter(h, f);
+    if (n == 0 || k == 0) return false;
+    if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+    if (!queries || !ids || !dist) throw InvalidArg("null argument");
+    return true;
+}
+
+// cph_search_batch[_filtered]: queries and results in host memory; f = null: unfiltered.  An empty filter launches
+// nothing (enqueue_search): no encoder, and its padding is written into device buffers by copy commands.
+void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* ids,
+                       float* dist) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!batch_has_work(h, f, queries, n, k, ids, dist)) return;
+    h->use_device();
+    hipStream_t st = own_stream(h);
+    BatchSet& s = next_set(h, st);
+    const bool empty = f && f->popcount == 0;
+    if (!empty && n <= kSmallBatch && n * k <= (1u << 20)) {
+        // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
+        const PinnedIo io(n, k, h->dim, 0);
+        if (s.pin_io_bytes < io.need && s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
+        grow_pinned(s.pin_io, s.pin_io_dev, s.pin_io_bytes, io.need);
+        std::memcpy(io.queries(s.pin_io), queries, n * h->dim * sizeof(float));
+        stage_queries(h, s, io.queries(s.pin_io_dev), n, st);
+        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
+                       DoneFlags(), f);
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::memcpy(ids, io.ids(s.pin_io), n * k * 8);
+        std::memcpy(dist, io.dist(s.pin_io), n * k * 4);
+        return;
+    }
+    if (!empty) stage_queries(h, s, upload_queries(h, s, queries, n, st), n, st);
+    if (s.d_ids.n < n * k) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
+        s.d_ids.alloc(n * k);
+        s.d_dist.alloc(n * k);
+    }
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f);
+    HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// cph_search_batch_device[_filtered]: queries and results in device memory, everything enqueued on the caller's stream.
+void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
+                         float* d_dist, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!batch_has_work(h, f, d_queries, n, k, d_ids, d_dist)) return;
+    h->use_device();
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    BatchSet& s = next_set(h, st);
+    if (!(f && f->popcount == 0)) stage_queries(h, s, d_queries, n, st);
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
 }
 
 }  // namespace
@@ -740,7 +853,7 @@ static std::atomic<uint64_t> g_tr[6];   // groups, callers, ns waiting for the h
 static inline uint64_t now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 #define CPH_TR(i, v) g_tr[i] += (v)
 #else
-#define CPH_TR(i, v) do {} while (0)
+#define CPH_TR(i, v) ((void)(v))
 static inline uint64_t now_ns() { return 0; }
 #endif
 
@@ -759,18 +872,10 @@ int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
             throw InvalidArg("Unsupported bits=" + std::to_string(bits) + ". Supported: 1, 2, 4.");
         const size_t pd = next_pow2(dim);
         if (dim == 0) throw InvalidArg("dim must be > 0");
-        if (pd < 16 || pd > 2048) {
-            if (pd < 16) {
-                // the reference pads only up to the next power of two; dims below 9 land on
-                // padded sizes it does not instantiate
-                throw InvalidArg("Unsupported dimension " + std::to_string(dim) + " (padded to " +
-                                 std::to_string(pd) +
-                                 "). Supported padded dims: 16, 32, 64, 128, 256, 512, 1024, 2048.");
-            }
-            throw InvalidArg("Unsupported dimension " + std::to_string(dim) + " (padded to " +
-                             std::to_string(pd) +
+        // (the reference pads only up to the next power of two; dims below 9 land on padded sizes it does not instantiate)
+        if (pd < 16 || pd > 2048)
+            throw InvalidArg("Unsupported dimension " + std::to_string(dim) + " (padded to " + std::to_string(pd) +
                              "). Supported padded dims: 16, 32, 64, 128, 256, 512, 1024, 2048.");
-        }
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
             throw std::runtime_error("No HIP device available: the MI355X path has no CPU fallback.");
@@ -851,12 +956,7 @@ static void load_v2(cph_index* h, const char* path) {
     t.load(path, h->D, h->bits, h->dim);        // a file that fails to parse leaves the handle as it was
     begin_device_swap(h);
     h->host = std::move(t);
-    h->needs_build = false;                       // api/hnsw_index.hpp:442
-    std::vector<float>().swap(h->pending);
-    h->pending_n = 0;
-    h->native_map.reset();
-    h->own_view = nullptr;
-    std::vector<uint8_t>().swap(h->own_store);
+    drop_host_state(h);
     upload_arrays(h);
     upload_feeders(h);
     h->finalized = true;
@@ -914,12 +1014,9 @@ static void load_native_file(cph_index* h, const char* path) {
     const NativeHeader nh = read_native(path, h->D, h->bits, h->dim, t, map);   // validates everything it maps
     begin_device_swap(h);
     h->host = std::move(t);
-    h->needs_build = false;
-    std::vector<float>().swap(h->pending);
-    h->pending_n = 0;
+    drop_host_state(h);
     h->native_map = std::move(map);
     const uint8_t* base = static_cast<const uint8_t*>(h->native_map.base);
-    std::vector<uint8_t>().swap(h->own_store);
     h->own_view = base + nh.own_off;
     h->L = make_dev_layout((uint32_t)h->host.D, (uint32_t)h->host.bw);
     const size_t n = h->host.n;
@@ -964,9 +1061,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     h->use_device();
     quiesce(h);
     h->host = HostIndex();
-    h->native_map.reset();
-    h->own_view = nullptr;
-    std::vector<uint8_t>().swap(h->own_store);
+    drop_host_state(h);
     h->finalized = false;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     for (auto& s : h->sets) release_scratch(s);
@@ -1249,25 +1344,26 @@ int cph_last_search_stats(cph_index* h, uint64_t out[12]) {
         }
         float ms = 0.0f;
         HIP_CHECK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        for (int i = 0; i < 6; ++i) out[i] = s.pin_stats[i];
-        out[6] = (uint64_t)(ms * 1000.0);
-        out[7] = s.pin_stats[7];
+        // out[0..7] are the block's words kStatExpansions..kStatAllSeen, with the device time in the word no kernel writes
+        for (int i = kStatExpansions; i <= kStatAllSeen; ++i) out[i] = s.pin_stats[i];
+        out[kStatNoCounter] = (uint64_t)(ms * 1000.0);
         out[8] = s.run_slots;
         out[9] = s.run_cap;
-#if !defined(CPH_PHASE_TIMERS) && !defined(CPH_TRAFFIC_STATS)
-        out[10] = s.pin_stats[8];
-        out[11] = s.pin_stats[9];
+        out[10] = stage2_stat(s, kStatStage2Reruns);
+        out[11] = stage2_stat(s, kStatStage2Undecided);
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+        const unsigned long long* diag = s.pin_stats + kStatDiag;
 #endif
 #if CPH_PHASE_TIMERS + 0 == 2
         fprintf(stderr, "[fine cycles] head+issue=%llu pop=%llu block_wait=%llu probe_issue+exact+nnpush=%llu estimator=%llu probe_wait=%llu mark+cand=%llu pushes+tail=%llu\n",
-                s.pin_stats[8], s.pin_stats[9], s.pin_stats[10], s.pin_stats[11], s.pin_stats[12], s.pin_stats[13], s.pin_stats[14], s.pin_stats[15]);
+                diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
 #elif defined(CPH_PHASE_TIMERS)
         fprintf(stderr, "[phase cycles] pop=%llu load+exact+nnpush=%llu sums+epi=%llu atomic+log+stage=%llu spec_exact=%llu replay=%llu tail=%llu other=%llu\n",
-                s.pin_stats[8], s.pin_stats[9], s.pin_stats[10], s.pin_stats[11], s.pin_stats[12], s.pin_stats[13], s.pin_stats[14], s.pin_stats[15]);
+                diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
 #endif
 #ifdef CPH_TRAFFIC_STATS
         fprintf(stderr, "[traffic] hybrid_pops=%llu windows=%llu hybrid_pushes=%llu hbm_appends=%llu probe_lines=%llu sum_beam_at_pop=%llu max_beam=%llu pops_beyond_8191=%llu\n",
-                s.pin_stats[8], s.pin_stats[9], s.pin_stats[10], s.pin_stats[11], s.pin_stats[12], s.pin_stats[13], s.pin_stats[14], s.pin_stats[15]);
+                diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
 #endif
     });
 }
@@ -1314,59 +1410,12 @@ int cph_order_queries(cph_index* h, const float* keys, uint64_t n, uint32_t* ord
 
 int cph_search_batch(cph_index* h, const float* queries, uint64_t n, uint64_t k, int64_t* ids,
                      float* dist) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        require_finalized(h);
-        if (n == 0 || k == 0) {
-            // (n, 0) outputs: nothing to write; still validates the entry point like search()
-            return;
-        }
-        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
-        if (!queries || !ids || !dist) throw InvalidArg("null argument");
-        h->use_device();
-        hipStream_t st = own_stream(h);
-        BatchSet& s = next_set(h, st);
-        if (n <= kSmallBatch && n * k <= (1u << 20)) {
-            // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
-            SmallIo io = small_io(h, s, n, k);
-            std::memcpy(io.h_query, queries, n * h->dim * sizeof(float));
-            stage_queries(h, s, io.d_query, n, st);
-            enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.d_ids, io.d_dist, st, io.d_count);
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memcpy(ids, io.h_ids, n * k * 8);
-            std::memcpy(dist, io.h_dist, n * k * 4);
-            return;
-        }
-        stage_queries(h, s, upload_queries(h, s, queries, n, st), n, st);
-        if (s.d_ids.n < n * k) {
-            if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-            s.d_ids.alloc(n * k);
-            s.d_dist.alloc(n * k);
-        }
-        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st);
-        HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(s.ev_done, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    });
+    return guarded([&] { search_batch_host(h, queries, n, k, nullptr, ids, dist); });
 }
 
 int cph_search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
                             int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        require_finalized(h);
-        if (n == 0 || k == 0) return;
-        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
-        if (!d_queries || !d_ids || !d_dist) throw InvalidArg("null argument");
-        h->use_device();
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        BatchSet& s = next_set(h, st);
-        stage_queries(h, s, d_queries, n, st);
-        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st);
-    });
+    return guarded([&] { search_batch_device(h, d_queries, n, k, nullptr, d_ids, d_dist, stream); });
 }
 
 // ---- filtered search --------------------------------------------------------------------
@@ -1401,68 +1450,14 @@ int cph_filter_destroy(cph_filter* f) {
     });
 }
 
-static void check_filter(const cph_index* h, const cph_filter* f) {
-    if (f->device != h->device) throw InvalidArg("filter belongs to another device");
-    if (f->n_bits != h->host.n)
-        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " ids, the index holds " + std::to_string(h->host.n));
-}
-
 int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f,
                               int64_t* ids, float* dist) {
-    if (!f) return cph_search_batch(h, queries, n, k, ids, dist);
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        require_finalized(h);
-        check_filter(h, f);
-        if (n == 0 || k == 0) return;
-        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
-        if (!queries || !ids || !dist) throw InvalidArg("null argument");
-        h->use_device();
-        hipStream_t st = own_stream(h);
-        BatchSet& s = next_set(h, st);
-        if (f->popcount != 0 && n <= kSmallBatch && n * k <= (1u << 20)) {
-            // cph_search_batch's copy-free path (an empty filter writes its padding with copy commands: device buffers below)
-            SmallIo io = small_io(h, s, n, k);
-            std::memcpy(io.h_query, queries, n * h->dim * sizeof(float));
-            stage_queries(h, s, io.d_query, n, st);
-            enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.d_ids, io.d_dist, st, io.d_count, DoneFlags(), f);
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memcpy(ids, io.h_ids, n * k * 8);
-            std::memcpy(dist, io.h_dist, n * k * 4);
-            return;
-        }
-        if (f->popcount != 0) stage_queries(h, s, upload_queries(h, s, queries, n, st), n, st);
-        if (s.d_ids.n < n * k) {
-            if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-            s.d_ids.alloc(n * k);
-            s.d_dist.alloc(n * k);
-        }
-        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f);
-        HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(s.ev_done, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    });
+    return guarded([&] { search_batch_host(h, queries, n, k, f, ids, dist); });
 }
 
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                      int64_t* d_ids, float* d_dist, void* stream) {
-    if (!f) return cph_search_batch_device(h, d_queries, n, k, d_ids, d_dist, stream);
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        require_finalized(h);
-        check_filter(h, f);
-        if (n == 0 || k == 0) return;
-        if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
-        if (!d_queries || !d_ids || !d_dist) throw InvalidArg("null argument");
-        h->use_device();
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        BatchSet& s = next_set(h, st);
-        if (f->popcount != 0) stage_queries(h, s, d_queries, n, st);
-        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
-    });
+    return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream); });
 }
 
 // One launch for up to kLeaderGroup single-query callers with the same k: queries gathered into the leader slot's
@@ -1470,18 +1465,6 @@ int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint6
 // the launch is ENQUEUED, not while it runs: the next leader's launch (other slot, other stream, its own batch set)
 // overlaps this one.  Nobody waits for the launch as a whole: the kernels raise a flag per query in the pinned buffer
 // once its results are visible to the host, and every caller waits for its own (wait_search_one).
-constexpr size_t kFlagBytes = kLeaderGroup * 4;
-struct GroupLayout {
-    size_t o_ids, o_dist, o_cnt, o_q, need;
-    GroupLayout(uint64_t n, uint64_t kk, uint64_t dim) {
-        o_ids = kFlagBytes;
-        o_dist = o_ids + n * kk * 8;
-        o_cnt = o_dist + n * kk * 4;
-        o_q = (o_cnt + n * 4 + 15) & ~(size_t)15;
-        need = o_q + n * dim * 4;
-    }
-};
-
 static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const std::vector<SearchReq*>& group) {
     const uint64_t n = group.size(), kk = group[0]->k;
     const uint64_t t0 = now_ns();
@@ -1490,28 +1473,19 @@ static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const s
     require_finalized(h);
     h->use_device();
     if (!ls.stream) HIP_CHECK(hipStreamCreateWithFlags(&ls.stream, hipStreamNonBlocking));
-    const GroupLayout g(n, kk, h->dim);
-    if (ls.pin_bytes < g.need) {          // (the slot is ours alone: nothing in flight reads the old buffer)
-        if (ls.pin) HIP_CHECK(hipHostFree(ls.pin));
-        ls.pin = nullptr; ls.pin_bytes = 0;
-        const size_t bytes = std::max<size_t>(g.need * 2, 64 * 1024);
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ls.pin), bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ls.pin_dev), ls.pin, 0));
-        std::memset(ls.pin, 0, kFlagBytes);
-        ls.pin_bytes = bytes;
-    }
-    float* h_query = reinterpret_cast<float*>(ls.pin + g.o_q);
-    for (uint64_t i = 0; i < n; ++i) std::memcpy(h_query + i * h->dim, group[i]->query, h->dim * sizeof(float));
+    const PinnedIo io(n, kk, h->dim, kFlagBytes);
+    // (no wait for the set's last batch: the slot is ours alone, nothing in flight reads the old buffer)
+    if (grow_pinned(ls.pin, ls.pin_dev, ls.pin_bytes, io.need)) std::memset(ls.pin, 0, kFlagBytes);
+    for (uint64_t i = 0; i < n; ++i) std::memcpy(io.queries(ls.pin) + i * h->dim, group[i]->query, h->dim * sizeof(float));
     if (++ls.seq == 0) ls.seq = 1;                                     // (a flag never holds a future launch's number)
     ls.cur_n = n; ls.cur_k = kk;
     BatchSet& s = h->sets[kMaxBatchSets + (&ls - h->leaders)];         // the slot's own set: its launches are ordered by its stream
     init_set(s);
-    stage_queries(h, s, reinterpret_cast<const float*>(ls.pin_dev + g.o_q), n, ls.stream);      // the encoder reads the queries over PCIe
+    stage_queries(h, s, io.queries(ls.pin_dev), n, ls.stream);                                 // the encoder reads the queries over PCIe
     DoneFlags done;
     done.flags = reinterpret_cast<uint32_t*>(ls.pin_dev);
     done.seq = ls.seq;
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, reinterpret_cast<int64_t*>(ls.pin_dev + g.o_ids), reinterpret_cast<float*>(ls.pin_dev + g.o_dist),
-                   ls.stream, reinterpret_cast<uint32_t*>(ls.pin_dev + g.o_cnt), done);           // ... the search writes the results back
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, io.ids(ls.pin_dev), io.dist(ls.pin_dev), ls.stream, io.counts(ls.pin_dev), done);   // ... the search writes the results back
     CPH_TR(0, 1); CPH_TR(1, n); CPH_TR(2, t1 - t0); CPH_TR(3, now_ns() - t1);
 }
 
@@ -1541,11 +1515,11 @@ static void wait_search_one(cph_index* h, cph_index::LeaderSlot& ls, uint32_t in
             __builtin_ia32_pause();
         }
     }
-    const GroupLayout g(n, kk, h->dim);
+    const PinnedIo io(n, kk, h->dim, kFlagBytes);
     // the reference returns every result it found (<= max(k,1)); the caller's buffers hold max(k,1) entries
-    const uint32_t cnt = reinterpret_cast<const uint32_t*>(ls.pin + g.o_cnt)[index];
-    std::memcpy(r.ids, reinterpret_cast<const int64_t*>(ls.pin + g.o_ids) + (size_t)index * kk, (size_t)cnt * 8);
-    std::memcpy(r.dist, reinterpret_cast<const float*>(ls.pin + g.o_dist) + (size_t)index * kk, (size_t)cnt * 4);
+    const uint32_t cnt = io.counts(ls.pin)[index];
+    std::memcpy(r.ids, io.ids(ls.pin) + (size_t)index * kk, (size_t)cnt * 8);
+    std::memcpy(r.dist, io.dist(ls.pin) + (size_t)index * kk, (size_t)cnt * 4);
     *r.m = cnt;
     CPH_TR(4, now_ns() - t0);
 }
@@ -2039,12 +2013,7 @@ void replicate(cph_index* src, cph_index* dst) {
     HIP_CHECK(hipDeviceSynchronize());          // whatever wrote the source arrays has landed
     begin_device_swap(dst);
     dst->host = host_scalars(src->host);
-    dst->needs_build = false;
-    std::vector<float>().swap(dst->pending);
-    dst->pending_n = 0;
-    dst->native_map.reset();
-    dst->own_view = nullptr;
-    std::vector<uint8_t>().swap(dst->own_store);
+    drop_host_state(dst);
     dst->L = src->L;
     dst->sc = src->sc;
     dst->flags = src->flags;
@@ -2072,10 +2041,7 @@ void replicate(cph_index* src, cph_index* dst) {
                                        rebase(s.nbrs, src->d_upper, dst->d_upper), rebase(s.row_of, src->d_row_of, dst->d_row_of),
                                        s.n_nodes};
     }
-    dst->auto_cap = 0;
-    dst->pf_off = false;
-    dst->pf_dense = false;
-    dst->last_search = -1;
+    reset_adaptation(dst);
     dst->finalized = true;
 }
 
@@ -2122,8 +2088,7 @@ void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t
         const float* q = queries ? queries + s.lo * dim : nullptr;
         int64_t* oi = ids ? ids + s.lo * k : nullptr;
         float* od = dist ? dist + s.lo * k : nullptr;
-        const int r = f ? cph_search_batch_filtered(h, q, s.hi - s.lo, k, f[s.replica], oi, od)
-                        : cph_search_batch(h, q, s.hi - s.lo, k, oi, od);
+        const int r = cph_search_batch_filtered(h, q, s.hi - s.lo, k, f ? f[s.replica] : nullptr, oi, od);
         if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
         return r;
     }, err);

@@ -37,6 +37,36 @@ struct Result {
     float dist;
 };
 
+// The statistics block of one batch (SearchArgs::stats): kStatWords u64 words.  Words [0, kStatFlushed) are counters summed
+// over the batch's queries: every wave adds them up in LDS (s_tot) and flushes them when it leaves.
+enum StatWord : int {
+    kStatExpansions = 0,        // FastScan blocks
+    kStatExact = 1,             // exact L2 evaluations
+    kStatNew = 2,               // new neighbours
+    kStatPushes = 3,            // beam pushes
+    kStatSkips = 4,             // stage-2 skipped batches
+    kStatReruns = 5,            // queries handed to the re-run launch (capacity overflow or stage-2 decision)
+    kStatNoCounter = 6,         // never written (cph_last_search_stats reports the launches' device time in its place)
+    kStatAllSeen = 7,           // expansions whose 32 neighbours were all estimated already
+    kStatStage2Reruns = 8,      // those of kStatReruns that were handed over for a stage-2 decision (probe first)
+    kStatStage2Undecided = 9,   // expansions whose stage-2 decision was left open (probe first)
+    // -DCPH_PHASE_TIMERS / -DCPH_TRAFFIC_STATS: eight cycle or traffic counters take words 8..15; the two stage-2 words
+    // are not flushed there (and read as 0 on the host)
+    kStatDiag = 8,
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+    kStatFlushed = 8,
+#else
+    kStatFlushed = 10,
+#endif
+    kStatQueues = 16,           // from here on u32 words, indexed by StatQueueWord
+    kStatWords = 18,
+};
+enum StatQueueWord : int {      // the u32 words at stats + kStatQueues
+    kQueueMain = 0,             // work-queue counter of the main (or direct) launch
+    kQueueRerunLen = 1,         // length of the re-run list
+    kQueueRerun = 2,            // work-queue counter of the re-run launch
+};
+
 struct SearchArgs {
     // index
     const uint8_t* blocks;
@@ -67,7 +97,7 @@ struct SearchArgs {
     float* out_dist;        // [nq][k]
     uint32_t* out_count;    // [nq]
     uint32_t* status;       // [nq]
-    unsigned long long* stats;  // [16]
+    unsigned long long* stats;  // [kStatWords], see StatWord
     // queries whose beam or id log outgrew `cap` are appended here and answered by the full-capacity
     // re-run launch that follows on the same stream (no host round trip)
     uint32_t* redo;         // [nq] or null
@@ -680,7 +710,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
     // The work counters of this wave's queries are summed here and reach the statistics line in HBM ONCE, when the wave
     // leaves: six atomics per query on one line from six thousand waves are a queue in the L2's atomic unit that every
     // query's first load has to wait behind (vmcnt counts them).
-    unsigned long long* s_tot = reinterpret_cast<unsigned long long*>(fixed + vsz + 336);   // [10], indexed like stats[]
+    unsigned long long* s_tot = reinterpret_cast<unsigned long long*>(fixed + vsz + 336);   // [10], indexed by StatWord
     if (lane < 10) s_tot[lane] = 0ull;
     Result* nn = reinterpret_cast<Result*>(fixed + vsz + kLdsTail);
     NnLds nnw;
@@ -1321,25 +1351,25 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             CPH_COLD(out_count)[qi] = nn_final;
             // bits 0..7: QueryStatus; bits 8..31: vertices expanded (per-query work, for load analysis)
             CPH_COLD(status)[qi] = (overflow ? kStatusOverflow : kStatusOk) | (st_exp << 8);
-            s_tot[0] += st_exp;
-            s_tot[1] += st_exact;
-            s_tot[2] += st_new;
-            s_tot[3] += st_push;
-            s_tot[4] += st_skip;
-            s_tot[7] += st_allseen;
-            if (stage2_redo) s_tot[8] += 1;                       // queries handed to the re-run launch for a stage-2 decision
-            s_tot[9] += st_undecided;
+            s_tot[kStatExpansions] += st_exp;
+            s_tot[kStatExact] += st_exact;
+            s_tot[kStatNew] += st_new;
+            s_tot[kStatPushes] += st_push;
+            s_tot[kStatSkips] += st_skip;
+            s_tot[kStatAllSeen] += st_allseen;
+            if (stage2_redo) s_tot[kStatStage2Reruns] += 1;
+            s_tot[kStatStage2Undecided] += st_undecided;
 #if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
             unsigned long long* stats = CPH_COLD(stats);
 #endif
 #ifdef CPH_PHASE_TIMERS
-            for (int i = 0; i < 8; ++i) atomicAdd(&stats[8 + i], tph[i]);
+            for (int i = 0; i < 8; ++i) atomicAdd(&stats[kStatDiag + i], tph[i]);
 #endif
 #ifdef CPH_TRAFFIC_STATS
-            for (int i = 0; i < 8; ++i) { if (i == 6) atomicMax(&stats[8 + i], trf[i]); else atomicAdd(&stats[8 + i], trf[i]); }
+            for (int i = 0; i < 8; ++i) { if (i == 6) atomicMax(&stats[kStatDiag + i], trf[i]); else atomicAdd(&stats[kStatDiag + i], trf[i]); }
 #endif
             if (overflow) {
-                s_tot[5] += 1;
+                s_tot[kStatReruns] += 1;
                 uint32_t* redo = CPH_COLD(redo);
                 if (redo) redo[atomicAdd(CPH_COLD(redo_count), 1u)] = qi;
             }
@@ -1359,15 +1389,11 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         __syncthreads();
     }
     // the wave leaves: its totals go to the statistics line
-#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
-    if (lane < 8) {            // (stats[8..15] carry the diagnostic counters in these builds)
-#else
-    if (lane < 10) {
-#endif
+    if (lane < kStatFlushed) {
         const unsigned long long v = s_tot[lane];
         // (an atomic add of a constant zero is turned into an atomic LOAD of the line by the compiler -- a synchronous
         // round trip; the values here are not constants, and zeros are skipped anyway)
-        if (v != 0ull && lane != 6) atomicAdd(&CPH_COLD(stats)[lane], v);
+        if (v != 0ull && lane != kStatNoCounter) atomicAdd(&CPH_COLD(stats)[lane], v);
     }
 }
 

@@ -290,7 +290,7 @@ def test_graph_quality_at_benchmark_scale_tracks_the_reference(tmp_path):
 @pytest.mark.parametrize("bits", [1, 2, 4])
 def test_small_batch_path_equals_the_batch_path(bits):
     """Batches of up to 32 queries on an index beyond the default slot capacity take the copy-free path: one launch on the
-    full-capacity slots, queries read and results written by the kernels over PCIe (cphnsw_mi355x.hip, launch mode 2).
+    full-capacity slots, queries read and results written by the kernels over PCIe (cphnsw_mi355x.hip, Launch::Direct).
     Ids and distance bits must equal what the same queries get inside a large batch (the path the oracle and the
     reference pin), for every code width and for `search`."""
     import cphnsw_mi355x

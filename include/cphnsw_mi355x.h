@@ -30,7 +30,12 @@
  * src/bindings.cpp:146-175, api/hnsw_index.hpp:172): a caller that finds a free leader slot takes everybody queued
  * so far with the same k into one launch; each waits for its own query only and gets its own rows.  The other entry points serialise on the handle
  * (cph_search_batch_device only while it enqueues).  Knobs: CPH_LEADER_SLOTS (default 3), CPH_GATHER_US (80).
- * Returned ids are the reference's internal (post-BFS-reorder) node ids.
+ * Ids: by default searches return, and filters speak of, the reference's internal (post-BFS-reorder) node ids.  An index
+ * built here keeps the builder's row map (internal id -> row of the array given to cph_build); with it a handle can
+ * return input rows instead (cph_set_result_ids) and take filters in input rows (cph_filter_create_rows).  The map is
+ * saved by cph_save_native; cph_save writes the reference's v2 format, which cannot carry it and silently drops it:
+ * an index loaded from a v2 file has no map until cph_set_row_map supplies one.  cph_get_vectors and the kernel-level
+ * hooks (cph_entry_point, cph_fastscan_block, cph_exact_l2, cph_export_blocks) always use internal ids.
  */
 #ifndef CPHNSW_MI355X_H
 #define CPHNSW_MI355X_H
@@ -162,13 +167,38 @@ int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, ui
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
                                      const cph_filter* f, int64_t* d_ids, float* d_dist, void* stream);
 
+/* The same bitmap contract as cph_filter_create, but bit r speaks of INPUT ROW r (the handle needs a row map, else
+ * CPH_INVALID_ARGUMENT; n_bits must equal the size of the index).  The device converts it once, through the row map,
+ * into an ordinary cph_filter (an internal-id bitmap), usable with every filtered entry point and with any result id
+ * space.  A later cph_set_row_map does not change filters made before it. */
+int cph_filter_create_rows(cph_index* h, const uint32_t* words, uint64_t n_bits, cph_filter** out);
+
+/* ---- ids in input rows ------------------------------------------------------------ */
+/* The row map: rows[i] = 0-based row, in the array given to cph_build, of internal id i; a permutation of 0..n-1.
+ * cph_finalize keeps it (host copy and device copy, 4 B per vertex), cph_save_native / cph_load_native carry it (native
+ * file format 2: format 1 plus a `rows` section, laid out so that a library that knows format 1 only still loads and
+ * searches the file; an index without a map is written as format 1), cph_load (v2 file) leaves the handle without one. */
+int cph_has_row_map(cph_index* h, int* flag);
+int cph_get_row_map(cph_index* h, uint64_t first, uint64_t count, uint32_t* out);
+/* For an index that came from a v2 file and whose owner has the map from elsewhere: n must equal the size of the index
+ * and rows must be a permutation of 0..n-1 (CPH_INVALID_ARGUMENT otherwise).  rows == NULL removes the map (and puts the
+ * handle back to CPH_IDS_INTERNAL).  Waits for everything enqueued on the handle. */
+int cph_set_row_map(cph_index* h, const uint32_t* rows, uint64_t n);
+/* The id space of the results of EVERY search entry point of this handle (a property of the handle, read when a search
+ * is enqueued; waits for everything enqueued before, like cph_set_batch_sets).  CPH_IDS_INPUT: ids leave the GPU as input
+ * rows (padding stays -1); distances, counts and statistics are those of CPH_IDS_INTERNAL.  CPH_IDS_INPUT on a handle
+ * without a row map fails with CPH_INVALID_ARGUMENT; losing the map (cph_load of a v2 file, cph_set_row_map(NULL),
+ * cph_build) puts the handle back to CPH_IDS_INTERNAL. */
+enum { CPH_IDS_INTERNAL = 0, CPH_IDS_INPUT = 1 };
+int cph_set_result_ids(cph_index* h, int space);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);
 
-/* Stored vectors of internal ids [first, first+count) (dim floats each, row-major).  The reference
- * never exposes its BFS permutation; a harness recovers internal -> input row numbers by
- * matching these rows against its own base vectors. */
+/* Stored vectors of internal ids [first, first+count) (dim floats each, row-major), whatever the result id space.
+ * The reference never exposes its BFS permutation: for an index without a row map a harness recovers
+ * internal -> input row numbers by matching these rows against its own base vectors. */
 int cph_get_vectors(cph_index* h, uint64_t first, uint64_t count, float* out);
 
 /* Batch scratch sets in rotation (default 2, at most 4): that many batches enqueued on different streams can be in
@@ -224,9 +254,13 @@ int cph_order_queries(cph_index* index, const float* keys, uint64_t n, uint32_t*
  *   last_search_stats / last_query_expansions
  *            over the replicas of the last search_batch[_filtered]: words 0-5, 7, 8, 10, 11 summed, 6 (kernel_us)
  *            and 9 (capacity) the maximum; expansions concatenated in query order.
+ *   has_row_map / set_row_map / set_result_ids
+ *            the row map lives on replica 0 (host copy) and, resident, on every replica: set_row_map validates once and
+ *            hands it to all of them, set_result_ids switches all of them; both wait for the searches in flight.
+ *            Filters in input rows: cph_filter_create_rows on each borrowed replica handle.
  *   replica  borrowed handle of replica i (owned by m; never destroyed by the caller): cph_search_batch_device on that
  *            device, cph_filter_create, cph_set_search_params / cph_set_batch_sets, the hooks.  cph_load,
- *            cph_load_native, cph_build, cph_finalize and cph_destroy on it fail with CPH_INVALID_ARGUMENT; on
+ *            cph_load_native, cph_build, cph_finalize, cph_set_row_map and cph_destroy on it fail with CPH_INVALID_ARGUMENT; on
  *            replicas other than 0 so do cph_save, cph_save_native and cph_get_vectors (no host arrays).
  * Threads: search_batch[_filtered] and search may be called concurrently from any number of threads; load,
  * load_native, build, finalize and destroy wait for the searches in flight on the multi handle. */
@@ -245,6 +279,9 @@ int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint6
 int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
                                     const cph_filter* const* f, int64_t* ids, float* dist);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
+int cph_multi_has_row_map(cph_multi* m, int* flag);
+int cph_multi_set_row_map(cph_multi* m, const uint32_t* rows, uint64_t n);
+int cph_multi_set_result_ids(cph_multi* m, int space);
 int cph_multi_set_min_shard(cph_multi* m, uint64_t q);
 int cph_multi_last_search_stats(cph_multi* m, uint64_t out[12]);
 int cph_multi_last_query_expansions(cph_multi* m, uint32_t* out, uint64_t n);
@@ -315,6 +352,10 @@ int cph_export_blocks(cph_index* h, uint64_t first, uint64_t count, int resident
 /* Host mirror of the query encoder (the device encoder is cph_encode_query): lut u8[D/4][16],
  * coeffs[3], masks u32[max(1,D/32)][4] (the bit-sliced form the kernels consume). */
 int cph_host_encode_query(uint64_t dim, const float* query, uint8_t* lut, float* coeffs, uint32_t* masks);
+/* Host statement of the conversion in cph_filter_create_rows: bit i of words_out = bit rows[i] of words_in for the n
+ * internal ids (both bitmaps (n + 31) / 32 words; bits of the last output word behind n are clear).  Every rows[i] must
+ * be < n. */
+int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_t n, uint32_t* words_out);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ import sys
 from . import build as _build
 
 OK, INVALID_ARGUMENT, RUNTIME_ERROR, OUT_OF_MEMORY, NOT_IMPLEMENTED = range(5)
+IDS_INTERNAL, IDS_INPUT = 0, 1      # cph_set_result_ids
 
 # name -> (restype, argtypes); the list is checked against the header by tests/test_abi.py
 SYMBOLS = {
@@ -41,6 +42,11 @@ SYMBOLS = {
                                             C.c_void_p]),
     "cph_search_batch_device_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "cph_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "cph_set_row_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_set_result_ids": (C.c_int, [C.c_void_p, C.c_int]),
     "cph_synchronize": (C.c_int, [C.c_void_p]),
     "cph_set_batch_sets": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -65,6 +71,9 @@ SYMBOLS = {
                                                   C.c_void_p, C.c_void_p]),
     "cph_multi_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_uint64)]),
+    "cph_multi_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_multi_set_row_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_multi_set_result_ids": (C.c_int, [C.c_void_p, C.c_int]),
     "cph_multi_set_min_shard": (C.c_int, [C.c_void_p, C.c_uint64]),
     "cph_multi_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_multi_last_query_expansions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -80,6 +89,7 @@ SYMBOLS = {
     "cph_host_relayout_block": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_export_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]),
     "cph_host_encode_query": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_rows_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cph_fastscan_stream_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "cph_fastscan_stream_run": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -90,7 +90,7 @@ def run_benchmark(dataset_name, base_dir, k, n_runs, output_dir, bit_widths=BIT_
             ids, _ = index.search_batch(queries, k)
             times.append(time.perf_counter() - t0)
         med = float(np.median(times))
-        rows = index.internal_to_input_rows(base)
+        rows = index.row_map() if index.has_row_map else index.internal_to_input_rows(base)
         mapped = np.where(ids >= 0, rows[np.maximum(ids, 0)], -1)
         res_d = ((base[np.maximum(mapped[:, :adr_k], 0)] - queries[:, None, :]) ** 2).sum(axis=2)
         results.append({

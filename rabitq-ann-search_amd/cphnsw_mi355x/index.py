@@ -2,7 +2,9 @@
 query path runs on an MI355X through the C-ABI in include/cphnsw_mi355x.h.
 
 Same constructor, methods, argument meaning, return shapes/dtypes and exception types as the
-pybind11 class.  Returned ids are the reference's internal (post-reorder) node ids.
+pybind11 class.  Returned ids are the reference's internal (post-reorder) node ids by default; an index that
+has a row map (built here, or loaded from a native file that holds one) returns rows of the array given to
+build() with `index.result_ids = "input"` (not in the reference).
 """
 import ctypes as C
 
@@ -29,12 +31,13 @@ def pack_allowed_bits(mask):
 
 
 class IdFilter:
-    """An allowed-id set on the index' device (CPIndex.make_filter).  Ids are internal ids, the ones searches return
-    (internal_to_input_rows maps them to input rows).  Usable with any index of the same size on the same device;
-    freeing it waits for the batches that may still read it.  A multi-device index' filter holds one bitmap per
-    replica, each on that replica's device."""
+    """An allowed-id set on the index' device (CPIndex.make_filter).  The bitmap speaks of internal ids, or, with
+    input_rows=True, of input rows: the device then converts it through the index' row map, once, into the internal-id
+    bitmap the searches read.  Usable with any index of the same size on the same device; freeing it waits for the
+    batches that may still read it.  A multi-device index' filter holds one bitmap per replica, each on that
+    replica's device."""
 
-    def __init__(self, index, words, n_bits, count):
+    def __init__(self, index, words, n_bits, count, input_rows=False):
         self._h = C.c_void_p()
         self._hs = []                # one cph_filter per replica (a single-device index: one)
         self.size = int(n_bits)      # ids the filter covers (= the index size)
@@ -42,7 +45,8 @@ class IdFilter:
         w = np.ascontiguousarray(words, np.uint32)
         for rh in index._replicas():
             h = C.c_void_p()
-            _lib.check(_lib.lib().cph_filter_create(rh, w.ctypes.data if w.size else None, self.size, C.byref(h)))
+            create = _lib.lib().cph_filter_create_rows if input_rows else _lib.lib().cph_filter_create
+            _lib.check(create(rh, w.ctypes.data if w.size else None, self.size, C.byref(h)))
             self._hs.append(h)
         self._h = self._hs[0]
 
@@ -73,6 +77,7 @@ class CPIndex:
             raise TypeError("CPIndex(): incompatible constructor arguments")  # size_t in pybind11
         self._dim = int(dim)
         self._bits = int(bits)
+        self._result_ids = "internal"
         if devices is not None:
             if device is not None:
                 raise ValueError("pass either device or devices, not both")
@@ -136,6 +141,7 @@ class CPIndex:
         v = _as_f32(vectors)
         if v.ndim != 2 or v.shape[1] != self._dim:
             raise ValueError("vectors must be a (n, dim) float32 array")
+        self._result_ids = "internal"    # the old index and its row map are gone
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_build(self._m, v.ctypes.data, v.shape[0]))
             return
@@ -148,8 +154,13 @@ class CPIndex:
         _lib.check(_lib.lib().cph_finalize(self._h))
 
     # -- filtered search (not in the reference) ------------------------------------------------
-    def make_filter(self, allowed):
-        """IdFilter from a bool mask of length `size` or an integer array of allowed internal ids."""
+    def make_filter(self, allowed, ids=None):
+        """IdFilter from a bool mask of length `size` or an integer array of allowed ids.  `ids`: the space `allowed`
+        speaks of, "internal" or "input" (rows of the array given to build(); needs a row map); default: the index'
+        result_ids, so that a filter and the results it restricts use the same numbers."""
+        space = self._result_ids if ids is None else ids
+        if space not in ("internal", "input"):
+            raise ValueError('ids must be "internal" or "input"')
         a = np.asarray(allowed)
         n = self.size
         if a.dtype == bool:
@@ -164,7 +175,7 @@ class CPIndex:
             mask[ids] = True
         else:
             raise ValueError("filter must be a bool mask or an integer array of ids")
-        return IdFilter(self, pack_allowed_bits(mask), n, int(np.count_nonzero(mask)))
+        return IdFilter(self, pack_allowed_bits(mask), n, int(np.count_nonzero(mask)), input_rows=space == "input")
 
     def _filter(self, f):
         if isinstance(f, IdFilter):
@@ -291,10 +302,14 @@ class CPIndex:
         _lib.check(_lib.lib().cph_save(self._h, str(path).encode()))
 
     def load(self, path):
-        if self._m is not None:
-            _lib.check(_lib.lib().cph_multi_load(self._m, str(path).encode()))
-            return
-        _lib.check(_lib.lib().cph_load(self._h, str(path).encode()))
+        """Reference-format (v2) file: it holds no row map, so the index comes back with result_ids "internal"."""
+        try:
+            if self._m is not None:
+                _lib.check(_lib.lib().cph_multi_load(self._m, str(path).encode()))
+                return
+            _lib.check(_lib.lib().cph_load(self._h, str(path).encode()))
+        finally:
+            self._after_index_change()
 
     def calib_samples_debug(self, queries, start):
         """Construction hook: the calibration sampler on given queries / start vertices: (rec [ns, 32, 6], cnt, dqp)."""
@@ -316,10 +331,77 @@ class CPIndex:
         _lib.check(_lib.lib().cph_save_native(self._h, str(path).encode()))
 
     def load_native(self, path):
+        try:
+            if self._m is not None:
+                _lib.check(_lib.lib().cph_multi_load_native(self._m, str(path).encode()))
+                return
+            _lib.check(_lib.lib().cph_load_native(self._h, str(path).encode()))
+        finally:
+            self._after_index_change()
+
+    # -- ids in input rows (not in the reference) ------------------------------------------------
+    def _after_index_change(self):
+        # the handle returns internal ids again once it has lost its row map
+        if self._result_ids == "input" and not self.has_row_map:
+            self.result_ids = "internal"
+
+    @property
+    def has_row_map(self):
+        """The index knows the input row of every internal id: it was built here, loaded from a native file saved
+        from such an index, or given a map with set_row_map.  A reference-format file (save / load) cannot carry it."""
+        f = C.c_int(0)
         if self._m is not None:
-            _lib.check(_lib.lib().cph_multi_load_native(self._m, str(path).encode()))
+            _lib.check(_lib.lib().cph_multi_has_row_map(self._m, C.byref(f)))
+        else:
+            _lib.check(_lib.lib().cph_has_row_map(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def row_map(self):
+        """int64[size] copy: row_map()[i] = row, in the array given to build(), of internal id i (a permutation; exact
+        also where rows repeat, which internal_to_input_rows is not)."""
+        out = np.empty(self.size, np.uint32)
+        _lib.check(_lib.lib().cph_get_row_map(self._h, 0, out.size, out.ctypes.data))
+        return out.astype(np.int64)
+
+    def set_row_map(self, rows):
+        """Gives an index that has none (loaded from a reference-format file) its row map: a permutation of 0..size-1,
+        else ValueError.  None removes the map and puts result_ids back to "internal"."""
+        if rows is None:
+            if self._m is not None:
+                _lib.check(_lib.lib().cph_multi_set_row_map(self._m, None, 0))
+            else:
+                _lib.check(_lib.lib().cph_set_row_map(self._h, None, 0))
+            self._result_ids = "internal"
             return
-        _lib.check(_lib.lib().cph_load_native(self._h, str(path).encode()))
+        r = np.asarray(rows)
+        if r.ndim != 1 or not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("row map must be a 1D integer array")
+        if r.size and (r.min() < 0 or r.max() > 0xFFFFFFFF):
+            raise ValueError("row map must be a permutation of 0..size-1")
+        r = np.ascontiguousarray(r, np.uint32)
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_set_row_map(self._m, r.ctypes.data, r.size))
+        else:
+            _lib.check(_lib.lib().cph_set_row_map(self._h, r.ctypes.data, r.size))
+
+    @property
+    def result_ids(self):
+        """"internal" (default: the reference's post-reorder ids) or "input": every search returns rows of the array
+        given to build(), translated on the GPU where the results are written (padding stays -1; distances are the
+        same bytes).  Also the default id space of make_filter and of the `filter=` arguments.  get_vectors, exact_l2,
+        fastscan_block and entry_point stay in internal ids."""
+        return self._result_ids
+
+    @result_ids.setter
+    def result_ids(self, space):
+        if space not in ("internal", "input"):
+            raise ValueError('result_ids must be "internal" or "input"')
+        code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_set_result_ids(self._m, code))
+        else:
+            _lib.check(_lib.lib().cph_set_result_ids(self._h, code))
+        self._result_ids = space
 
     # -- properties -------------------------------------------------------------------------
     @property
@@ -390,7 +472,8 @@ class CPIndex:
         return out
 
     def get_vectors(self, first=0, count=None):
-        """Stored vectors of internal ids [first, first+count) as float32 (count, dim)."""
+        """Stored vectors of internal ids [first, first+count) as float32 (count, dim) (internal ids also when
+        result_ids is "input")."""
         if count is None:
             count = self.size - first
         out = np.empty((count, self._dim), np.float32)
@@ -399,7 +482,8 @@ class CPIndex:
 
     def internal_to_input_rows(self, base, chunk=1 << 18):
         """int64[size]: input row number of every internal id, by exact row matching.
-        Rows that occur several times in `base` map to one of their equal copies."""
+        Rows that occur several times in `base` map to one of their equal copies.  (For an index without a row map;
+        with one, row_map() is exact and needs neither `base` nor the download.)"""
         base = _as_f32(base)
         key = {}
         for i in range(base.shape[0] - 1, -1, -1):

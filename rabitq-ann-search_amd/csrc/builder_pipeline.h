@@ -13,6 +13,7 @@ struct BuiltDevice {            // the searchable index as the pipeline leaves i
     DevBuf<uint8_t> blocks;     // [n][stride] device blocks
     DevBuf<float> raw;          // [n][D] vectors, final order
     DevBuf<float> norm;         // [n]
+    DevBuf<uint32_t> rows;      // [n] the row map: input row of every final (post-BFS) id (HostIndex::rows on the host)
     std::vector<uint8_t> own_host;   // [n][nb_off]: every vertex' own code header (reference layout), for save()
 };
 
@@ -269,6 +270,7 @@ inline void build_graph(HostIndex& hi, BuiltDevice& dev, const float* vecs, size
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     d_x.release(); d_norm.release(); d_nbr.release(); d_cnt.release();
+    dev.rows = std::move(d_n2o);     // the renumbering IS the row map: it stays resident next to the norms
 
     // ---- codes: every edge into the device blocks, every vertex' own code for the file ----------------------
     DevBuf<float> d_signs(3 * D);
@@ -308,6 +310,7 @@ inline void build_graph(HostIndex& hi, BuiltDevice& dev, const float* vecs, size
     HIP_CHECK(hipMemcpy(hi.raw.data(), dev.raw.p, n * D * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(hi.norm_sq.data(), dev.norm.p, n * 4, hipMemcpyDeviceToHost));
     hi.levels = std::move(levels_new);
+    hi.rows = std::move(new_to_old);
     // The reference-layout image of the neighbour blocks (hi.search_data, 2.9 KB per vertex at D = 128, 17.7 KB at
     // D = 1024) is only what save() writes: it is derived from the device blocks when a save asks for it
     // (materialize_search_data), not here.  The own-code headers are small and come down now.

@@ -30,6 +30,7 @@
 #include "device_stream.h"
 #include "device_heap_test.h"
 #include "device_relayout.h"
+#include "device_rows.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -166,6 +167,11 @@ struct cph_index {
     // device-resident index
     DevBuf<uint8_t> d_blocks;
     DevBuf<float> d_raw, d_norm;
+    // the row map (input row of every internal id; host copy: host.rows), resident next to the norms; has_rows: the
+    // index has one (a replica without host arrays holds the device copy only)
+    DevBuf<uint32_t> d_rows;
+    bool has_rows = false;
+    bool ids_input = false;            // cph_set_result_ids: searches return input rows (needs has_rows)
     // per-query feeders on the device: rotation signs + upper layers (CSR)
     DevBuf<float> d_signs;
     DevBuf<uint32_t> d_upper;          // all layers' nodes | offsets | nbrs, concatenated
@@ -244,6 +250,20 @@ void drop_host_state(cph_index* h) {
     h->native_map.reset();
     h->own_view = nullptr;
     std::vector<uint8_t>().swap(h->own_store);
+}
+
+// After the host index changed: the device copy of its row map, or none -- and without a map the handle returns
+// internal ids again.
+void sync_row_map(cph_index* h) {
+    const std::vector<uint32_t>& rows = h->host.rows;
+    h->has_rows = !rows.empty();
+    if (h->has_rows) {
+        h->d_rows.alloc(rows.size());
+        HIP_CHECK(hipMemcpy(h->d_rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    } else {
+        h->d_rows.release();
+        h->ids_input = false;
+    }
 }
 
 void require_finalized(cph_index* h) {
@@ -563,6 +583,7 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     const bool pf = mode == Launch::Main && d_allow == nullptr && probe_first(h);
     SearchArgs a{};
     a.allow = d_allow;
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
     a.done_flags = done.flags;
     a.done_seq = done.seq;
     a.blocks = h->d_blocks.p;
@@ -861,7 +882,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 101; }
+int cph_version(void) { return 102; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -958,6 +979,7 @@ static void load_v2(cph_index* h, const char* path) {
     h->host = std::move(t);
     drop_host_state(h);
     upload_arrays(h);
+    sync_row_map(h);                            // (a v2 file carries no row map)
     upload_feeders(h);
     h->finalized = true;
 }
@@ -1027,6 +1049,7 @@ static void load_native_file(cph_index* h, const char* path) {
     relayout_blocks(h->d_blocks.p, n, h->L, true);
     HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
+    sync_row_map(h);
     upload_feeders(h);
     h->finalized = true;
 }
@@ -1064,6 +1087,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     drop_host_state(h);
     h->finalized = false;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
+    sync_row_map(h);
     for (auto& s : h->sets) release_scratch(s);
     h->pending.assign(vectors, vectors + n * h->dim);
     h->pending_n = n;
@@ -1092,6 +1116,8 @@ static void finalize_build(cph_index* h) {
     h->d_blocks = std::move(dev.blocks);
     h->d_raw = std::move(dev.raw);
     h->d_norm = std::move(dev.norm);
+    h->d_rows = std::move(dev.rows);           // the BFS renumbering, kept: host.rows is its host copy
+    h->has_rows = true;
     h->native_map.reset();
     h->own_store = std::move(dev.own_host);
     h->own_view = h->own_store.data();
@@ -1458,6 +1484,116 @@ int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, ui
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                      int64_t* d_ids, float* d_dist, void* stream) {
     return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream); });
+}
+
+}  // extern "C"
+
+// ---- row map: ids in input rows ------------------------------------------------------------
+// Installs (rows != null: validated by the caller) or removes the row map of a finalized handle.  keep_host: also as
+// host.rows (what save_native writes); a replica without host arrays keeps the device copy only.
+static void install_row_map(cph_index* h, const uint32_t* rows, uint64_t n, bool keep_host) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (rows && n != h->host.n)
+        throw InvalidArg("row map has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->host.n));
+    h->use_device();
+    quiesce(h);                                  // a batch in flight may be reading the old map
+    if (!rows) {
+        std::vector<uint32_t>().swap(h->host.rows);
+        sync_row_map(h);
+        return;
+    }
+    h->d_rows.alloc(n);
+    HIP_CHECK(hipMemcpy(h->d_rows.p, rows, n * 4, hipMemcpyHostToDevice));
+    if (keep_host) h->host.rows.assign(rows, rows + n);
+    h->has_rows = true;
+}
+
+static void set_result_ids(cph_index* h, int space) {
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("result id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (space == CPH_IDS_INPUT && !h->has_rows)
+        throw InvalidArg("the index has no row map (it was loaded from a v2 file): results in input rows need cph_set_row_map");
+    h->use_device();
+    quiesce(h);
+    h->ids_input = space == CPH_IDS_INPUT;
+}
+
+extern "C" {
+
+int cph_has_row_map(cph_index* h, int* flag) {
+    return guarded([&] {
+        if (!h || !flag) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *flag = h->finalized && h->has_rows ? 1 : 0;
+    });
+}
+
+int cph_get_row_map(cph_index* h, uint64_t first, uint64_t count, uint32_t* out) {
+    return guarded([&] {
+        if (!h || (!out && count != 0)) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        if (!h->has_rows) throw InvalidArg("the index has no row map");
+        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("row map range out of bounds");
+        if (count == 0) return;
+        h->use_device();
+        HIP_CHECK(hipMemcpy(out, h->d_rows.p + first, count * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_set_row_map(cph_index* h, const uint32_t* rows, uint64_t n) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_row_map");
+        if (rows && !is_row_permutation(rows, n)) throw InvalidArg("row map must be a permutation of 0..n-1");
+        install_row_map(h, rows, n, true);
+    });
+}
+
+int cph_set_result_ids(cph_index* h, int space) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        set_result_ids(h, space);
+    });
+}
+
+int cph_filter_create_rows(cph_index* h, const uint32_t* words, uint64_t n_bits, cph_filter** out) {
+    return guarded([&] {
+        if (!h || !out || (!words && n_bits != 0)) throw InvalidArg("null argument");
+        *out = nullptr;
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        if (!h->has_rows) throw InvalidArg("the index has no row map: a filter in input rows needs one");
+        if (n_bits != h->host.n)
+            throw InvalidArg("filter covers " + std::to_string(n_bits) + " rows, the index holds " + std::to_string(h->host.n));
+        const uint64_t nw = (n_bits + 31) / 32;
+        std::vector<uint32_t> w(words, words + nw);
+        if (n_bits & 31) w[nw - 1] &= (1u << (n_bits & 31)) - 1u;
+        uint64_t pc = 0;                             // (a permutation of the bits: the id bitmap has the same popcount)
+        for (uint32_t x : w) pc += (uint64_t)__builtin_popcount(x);
+        std::unique_ptr<cph_filter> f(new cph_filter());
+        f->device = h->device;
+        f->n_bits = n_bits;
+        f->popcount = pc;
+        h->use_device();
+        f->words.alloc(std::max<uint64_t>(nw, 1));
+        DevBuf<uint32_t> d_in(std::max<uint64_t>(nw, 1));
+        hipStream_t st = own_stream(h);
+        HIP_CHECK(hipMemcpyAsync(d_in.p, w.data(), nw * 4, hipMemcpyHostToDevice, st));
+        rows_filter(d_in.p, h->d_rows.p, n_bits, f->words.p, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        *out = f.release();
+    });
+}
+
+int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_t n, uint32_t* words_out) {
+    return guarded([&] {
+        if (n != 0 && (!words_in || !rows || !words_out)) throw InvalidArg("null argument");
+        for (uint64_t i = 0; i < n; ++i)
+            if (rows[i] >= n) throw InvalidArg("row out of range");
+        rows_filter_host(words_in, rows, n, words_out);
+    });
 }
 
 // One launch for up to kLeaderGroup single-query callers with the same k: queries gathered into the leader slot's
@@ -2004,7 +2140,7 @@ HostIndex host_scalars(const HostIndex& s) {
 }
 
 // dst becomes a searchable copy of the finalized src: src's resident device arrays (blocks in the resident layout,
-// vectors, norms, rotation signs, upper layers, row maps) copied device to device (no peer access needed), its search
+// vectors, norms, the row map, rotation signs, upper layers and their vertex -> row tables) copied device to device (no peer access needed), its search
 // scalars copied, the upper-layer pointers rebased onto dst's own buffers.  dst keeps no host arrays.
 void replicate(cph_index* src, cph_index* dst) {
     std::lock_guard<std::mutex> ls(src->mu), ld(dst->mu);
@@ -2028,6 +2164,10 @@ void replicate(cph_index* src, cph_index* dst) {
     copy(dst->d_blocks, src->d_blocks);
     copy(dst->d_raw, src->d_raw);
     copy(dst->d_norm, src->d_norm);
+    if (src->has_rows) copy(dst->d_rows, src->d_rows);
+    else dst->d_rows.release();
+    dst->has_rows = src->has_rows;
+    dst->ids_input = dst->ids_input && dst->has_rows;
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
     copy(dst->d_row_of, src->d_row_of);
@@ -2169,6 +2309,7 @@ int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n) {
             begin_device_swap(h);
             h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
             h->host = HostIndex();
+            sync_row_map(h);
         }
     });
 }
@@ -2201,6 +2342,27 @@ int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids,
     // one replica per caller, round robin: that replica's coalescer gathers its callers (its error text is ours:
     // cph_search runs on this thread)
     return multi_shared(m, [&] { return cph_search(m->reps[m->rr.fetch_add(1) % m->reps.size()], query, k, ids, dist, count); });
+}
+
+int cph_multi_has_row_map(cph_multi* m, int* flag) {
+    return multi_shared(m, [&] { return cph_has_row_map(m->reps[0], flag); });
+}
+
+int cph_multi_set_row_map(cph_multi* m, const uint32_t* rows, uint64_t n) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        if (rows && !is_row_permutation(rows, n)) throw InvalidArg("row map must be a permutation of 0..n-1");
+        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
+        for (size_t i = 0; i < m->reps.size(); ++i) install_row_map(m->reps[i], rows, n, i == 0);
+    });
+}
+
+int cph_multi_set_result_ids(cph_multi* m, int space) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->reps) set_result_ids(h, space);
+    });
 }
 
 int cph_multi_set_min_shard(cph_multi* m, uint64_t q) {

@@ -106,9 +106,12 @@ struct SearchArgs {
     // the outputs then live in pinned, device-mapped memory and every caller waits for its own query only
     uint32_t* done_flags;
     uint32_t done_seq;
-    // filtered instantiations only (FILT): allowed-id bitmap, bit id & 31 of word id >> 5.  Last, so that no offset of the
-    // fields above moves
+    // filtered instantiations only (FILT): allowed-id bitmap, bit id & 31 of word id >> 5.  Behind everything older, so
+    // that no offset of the fields above moves
     const uint32_t* allow;
+    // optional: the row map, [n] (result ids in input rows, cph_set_result_ids): a result id i leaves as rows[i].  Null:
+    // internal ids.  Read once per query, where the rows are written; the search itself knows internal ids only.
+    const uint32_t* rows;
 };
 
 // Kernel arguments that are touched once per query (work queue, encoded-query arrays, outputs, statistics) are read from
@@ -1337,9 +1340,12 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         if (!overflow) {
             int64_t* out_ids = CPH_COLD(out_ids);
             float* out_dist = CPH_COLD(out_dist);
+            const uint32_t* rows = CPH_COLD(rows);
             for (uint32_t j = lane; j < k; j += 64) {
                 if (j < nn_final) {
-                    out_ids[(size_t)qi * k + j] = (int64_t)nn[j].id;
+                    // (translated here and not by a pass behind the kernel: the done flag below tells a cph_search
+                    // caller that its row is final)
+                    out_ids[(size_t)qi * k + j] = (int64_t)(rows ? rows[nn[j].id] : nn[j].id);
                     out_dist[(size_t)qi * k + j] = nn[j].dist;
                 } else {
                     out_ids[(size_t)qi * k + j] = -1;

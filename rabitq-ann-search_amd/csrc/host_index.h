@@ -158,6 +158,26 @@ struct AtomicFile {
     }
 };
 
+// rows[0..n) holds every value of 0..n-1 once (what a row map must be: HostIndex::rows).
+inline bool is_row_permutation(const uint32_t* rows, size_t n) {
+    std::vector<uint8_t> seen(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (rows[i] >= n || seen[rows[i]]) return false;
+        seen[rows[i]] = 1;
+    }
+    return true;
+}
+
+// The host statement of the row-space filter (cph_filter_create_rows; device_rows.h): bit i of `out` = bit rows[i] of
+// `in`, for the n internal ids; bits of the last word behind n are clear.  Both bitmaps are (n + 31) / 32 words.
+inline void rows_filter_host(const uint32_t* in, const uint32_t* rows, size_t n, uint32_t* out) {
+    for (size_t w = 0; w < (n + 31) / 32; ++w) out[w] = 0u;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t r = rows[i];
+        out[i >> 5] |= ((in[r >> 5] >> (r & 31)) & 1u) << (i & 31);
+    }
+}
+
 struct HostIndex {
     size_t D = 0, bw = 0, dim = 0, n = 0;
     int32_t max_level = 0;
@@ -174,6 +194,9 @@ struct HostIndex {
     const float* raw_view = nullptr;  // [n][D] inside a mapped native file (csrc/native_file.h), else null
     std::vector<uint8_t> search_data; // n * vertex_bytes, reference layout (kept for save; a native load rebuilds it on demand)
     std::vector<std::vector<UpperEdge>> upper;
+    // The row map: rows[i] = row of the array given to build() that internal id i holds (a permutation of 0..n-1).
+    // Empty = no map: the index came from a v2 file, which cannot carry one (save() drops it).
+    std::vector<uint32_t> rows;
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

@@ -5,9 +5,21 @@
 // (0.99 s).  The native file keeps what the GPU reads in the form the GPU reads it:
 //
 //   header | calibration, profile, centroid, levels, norms, upper layers      (the v2 file's small fields)
+//          [ NativeRowsExt ]  format 2 only: the last bytes of the small section
+//   rows   [n] u32           4096-aligned, format 2 only: the row map (HostIndex::rows), input row of every internal id
 //   own    [n][own_stride]   the vertices' own codes + {nop, ip_qo} (only needed to write a v2 file again)
 //   raw    [n][D] f32        4096-aligned
 //   blocks [n][stride]       4096-aligned, device block layout (cph_core.h)
+//
+// Format 1 has no row map; format 2 = format 1 plus the `rows` section and a NativeRowsExt record that names the
+// format and the section's offset.  An index without a map is written as format 1, byte for byte what earlier
+// releases wrote.  Format 2 is an EXTENSION a format-1 reader can still load: index caches are shared between builds
+// of the project (bench.py compares builds on one cached file), so a file written by this library must stay readable
+// by the previous one.  A format-1 reader refuses any NativeHeader::version but 1, reads the small section field by
+// field and ignores what follows the upper layers, and lets sections start later than the previous one ends.  So
+// NativeHeader::version stays 1 -- "what a reader must understand to search the file" -- the record sits at the END
+// of the small section (inside small_bytes), and the `rows` section sits in front of `own`, inside file_bytes.  This
+// reader returns the file's format (1 or 2) in the `version` field of the header it hands back.
 //
 // load = mmap + two host-to-device copies straight out of the mapping; the vectors stay mapped for
 // cph_get_vectors / save.  A v2 file can always be regenerated from a native one (cph_save after
@@ -32,7 +44,9 @@
 namespace cph {
 
 constexpr uint64_t kNativeMagic = 0x3535334948504300ULL;   // "\0CPHI355"
-constexpr uint32_t kNativeVersion = 1;
+constexpr uint32_t kNativeVersion = 1;        // NativeHeader::version of every file; the format of one without a row map
+constexpr uint32_t kNativeVersionRows = 2;    // NativeRowsExt::version: the format of a file with one
+constexpr uint64_t kNativeRowsMagic = 0x53574F5249485043ULL;   // "CPHIROWS"
 
 struct NativeHeader {
     uint64_t magic;
@@ -47,6 +61,13 @@ struct NativeHeader {
     uint32_t has_dup, n_layers;
     uint64_t small_bytes;     // bytes of the small section that follows the header
     uint64_t own_off, raw_off, blocks_off, file_bytes;
+};
+
+struct NativeRowsExt {        // format 2: the last sizeof(NativeRowsExt) bytes of the small section
+    uint64_t magic;           // kNativeRowsMagic
+    uint32_t version;         // kNativeVersionRows
+    uint32_t reserved;        // 0
+    uint64_t rows_off;        // n x u32, between the small section and `own`
 };
 
 struct NativeMapping {
@@ -90,13 +111,21 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
             put(e.nbrs.data(), (size_t)cnt * 4);
         }
     }
+    const bool with_rows = !hi.rows.empty();
+    if (with_rows && hi.rows.size() != hi.n) throw std::runtime_error("row map does not match the index size");
+    uint64_t rows_off = 0;
+    if (with_rows) {
+        rows_off = align_up(sizeof(NativeHeader) + small.size() + sizeof(NativeRowsExt), 4096);
+        const NativeRowsExt ext{kNativeRowsMagic, kNativeVersionRows, 0u, rows_off};
+        put(&ext, sizeof(ext));
+    }
     NativeHeader h{};
     h.magic = kNativeMagic; h.version = kNativeVersion; h.D = (uint32_t)hi.D; h.bw = (uint32_t)hi.bw; h.dim = (uint32_t)hi.dim;
     h.n = hi.n; h.stride = stride; h.own_stride = own_stride; h.max_level = hi.max_level; h.entry = hi.entry;
     h.upper_tau = hi.upper_tau; h.upper_alpha = hi.upper_alpha; h.mL = hi.mL; h.seed = hi.seed;
     h.has_dup = hi.has_dup_neighbors ? 1u : 0u; h.n_layers = (uint32_t)hi.upper.size();
     h.small_bytes = small.size();
-    h.own_off = align_up(sizeof(NativeHeader) + small.size(), 4096);
+    h.own_off = with_rows ? align_up(rows_off + hi.n * 4, 4096) : align_up(sizeof(NativeHeader) + small.size(), 4096);
     h.raw_off = align_up(h.own_off + hi.n * own_stride, 4096);
     h.blocks_off = align_up(h.raw_off + hi.n * hi.D * 4, 4096);
     h.file_bytes = h.blocks_off + hi.n * (uint64_t)stride;
@@ -109,6 +138,10 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
     };
     wr(&h, sizeof(h));
     wr(small.data(), small.size());
+    if (with_rows) {
+        pad_to(rows_off);
+        wr(hi.rows.data(), hi.n * 4);
+    }
     pad_to(h.own_off);
     wr(own, hi.n * own_stride);
     pad_to(h.raw_off);
@@ -118,7 +151,8 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
     out.commit();
 }
 
-// Maps the file and fills everything of `hi` except raw / search_data (raw_view points into the mapping).
+// Maps the file and fills everything of `hi` except raw / search_data (raw_view points into the mapping); hi.rows is
+// the file's row map (format 2) or empty (format 1); the returned header's `version` is that format.
 inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t expect_bw, size_t expect_dim, HostIndex& hi,
                                 NativeMapping& map) {
     const int fd = ::open(path.c_str(), O_RDONLY);
@@ -193,6 +227,22 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
                 if (x >= t.n) throw std::runtime_error("Corrupt index: upper-layer neighbour out of range");
         }
     }
+    // What follows the upper layers: nothing (format 1) or the row-map record (format 2); anything else is damage.
+    bool with_rows = false;
+    NativeRowsExt ext{};
+    if (p != end) {
+        typedef unsigned __int128 u128;
+        if ((size_t)(end - p) != sizeof(ext)) throw std::runtime_error("Corrupt index: unknown data behind the upper layers");
+        get(&ext, sizeof(ext));
+        if (ext.magic != kNativeRowsMagic) throw std::runtime_error("Corrupt index: unknown data behind the upper layers");
+        if (ext.version != kNativeVersionRows)
+            throw std::runtime_error("Unsupported native index file version: " + std::to_string(ext.version));
+        if (ext.rows_off % 4 != 0 || (u128)ext.rows_off < (u128)sizeof(NativeHeader) + h.small_bytes ||
+            (u128)ext.rows_off + (u128)h.n * 4 > h.own_off)
+            throw std::runtime_error("Corrupt index: row map section out of bounds");
+        with_rows = true;
+        h.version = kNativeVersionRows;      // the format, for the caller (the file's field stays 1, see the top)
+    }
     // The device blocks are handed to the GPU as they are: a neighbour id the search kernel would chase must be a
     // vertex (the v2 loader's validate() makes the same promise), unused slots must carry the invalid marker the
     // kernels rely on instead of `count`, and the repeated-id flag is recomputed rather than believed.
@@ -221,6 +271,11 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
         if (bad.load() == 1) throw std::runtime_error("Corrupt index: neighbour count > 32");
         if (bad.load()) throw std::runtime_error("Corrupt index: neighbour id out of range");
         t.has_dup_neighbors = dup.load() != 0;
+    }
+    if (with_rows) {
+        t.rows.resize(t.n);
+        std::memcpy(t.rows.data(), static_cast<const uint8_t*>(base) + ext.rows_off, t.n * 4);
+        if (!is_row_permutation(t.rows.data(), t.n)) throw std::runtime_error("Corrupt index: the row map is not a permutation");
     }
     t.raw_view = reinterpret_cast<const float*>(static_cast<const uint8_t*>(base) + h.raw_off);
     t.rot.init(t.D, t.seed);

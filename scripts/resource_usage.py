@@ -7,7 +7,7 @@ txt = open(sys.argv[1]).read()
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 cur = {}
 for line in txt.splitlines():
-    m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark:.*?\s(Function Name|TotalSGPRs|VGPRs|AGPRs|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         continue
     k, v = m.group(1), m.group(2)

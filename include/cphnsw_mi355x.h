@@ -167,6 +167,26 @@ int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, ui
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
                                      const cph_filter* f, int64_t* d_ids, float* d_dist, void* stream);
 
+/* ---- exact search ---------------------------------------------------------------------- */
+/* Brute force over the allowed ids (f = NULL: over every id) on the fp32 VALU, instead of the graph search: each row
+ * holds the k nearest allowed ids, exactly.  A distance has the bits cph_exact_l2 returns for the pair -- the bits the
+ * graph search returns for the same id.  Rows are in ascending distance, equal distance bits in ascending INTERNAL id
+ * (also under CPH_IDS_INPUT, where the ids are translated as the rows are written); an id appears at most once; rows with
+ * fewer than k allowed ids are padded with -1 / FLT_MAX.  k <= 1024 (CPH_INVALID_ARGUMENT above).  The filter checks are
+ * those of the filtered calls; an empty filter returns padding without a launch.  The _device form only enqueues, takes a
+ * batch set in rotation like cph_search_batch_device, and its filter must outlive it as there (cph_filter_destroy waits).
+ * The filter's ascending id list is made on the device at its first exact use and kept until the filter is destroyed.
+ * Afterwards cph_last_search_stats reports [0] = 0, [1] = n x candidates, [6] = device time, every other word 0;
+ * cph_last_query_expansions returns zeros. */
+int cph_search_batch_exact(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f,
+                           int64_t* ids, float* dist);
+int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
+                                  int64_t* d_ids, float* d_dist, void* stream);
+/* Cut-over of the filtered entry points (cph_search_batch_filtered, cph_search_batch_device_filtered and, through them,
+ * the multi form): a filter that allows at most max_allowed ids (and a k <= 1024) takes the exact path.  Default 0: never,
+ * every call does what it did before. */
+int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
+
 /* The same bitmap contract as cph_filter_create, but bit r speaks of INPUT ROW r (the handle needs a row map, else
  * CPH_INVALID_ARGUMENT; n_bits must equal the size of the index).  The device converts it once, through the row map,
  * into an ordinary cph_filter (an internal-id bitmap), usable with every filtered entry point and with any result id
@@ -278,6 +298,10 @@ int cph_multi_is_finalized(cph_multi* m, int* flag);
 int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist);
 int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
                                     const cph_filter* const* f, int64_t* ids, float* dist);
+/* cph_search_batch_exact sharded like cph_multi_search_batch_filtered; f = NULL, or one filter per replica. */
+int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
+                                 const cph_filter* const* f, int64_t* ids, float* dist);
+int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);
 int cph_multi_set_row_map(cph_multi* m, const uint32_t* rows, uint64_t n);
@@ -356,6 +380,15 @@ int cph_host_encode_query(uint64_t dim, const float* query, uint8_t* lut, float*
  * internal ids (both bitmaps (n + 31) / 32 words; bits of the last output word behind n are clear).  Every rows[i] must
  * be < n. */
 int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_t n, uint32_t* words_out);
+
+/* Host statement of the compaction the exact search runs on a filter: out_ids = the set bits of words (bit id & 31 of
+ * word id >> 5, bits behind n_bits ignored) in ascending order, *out_count = how many.  out_ids holds popcount entries. */
+int cph_host_filter_ids(const uint32_t* words, uint64_t n_bits, uint32_t* out_ids, uint64_t* out_count);
+/* How an exact batch of n_queries against `candidates` ids is cut on a device of num_cus compute units with at most
+ * scratch_bytes of pool scratch (the planner the exact entry points run; 1 <= k <= 1024): out[6] = parts, candidates per
+ * part, queries per group, queries per launch, keys per pool, pool bytes.  More than one part: the merge kernel folds the
+ * parts' lists; queries per launch < n_queries: the batch is tiled inside the call. */
+int cph_host_exact_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t* out);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,16 @@ SYMBOLS = {
                                             C.c_void_p]),
     "cph_search_batch_device_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_search_batch_exact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "cph_search_batch_exact_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_multi_search_batch_exact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "cph_multi_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_host_filter_ids": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_host_exact_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cph_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "cph_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

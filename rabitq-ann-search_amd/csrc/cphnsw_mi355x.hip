@@ -31,6 +31,7 @@
 #include "device_heap_test.h"
 #include "device_relayout.h"
 #include "device_rows.h"
+#include "device_exact.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -130,6 +131,10 @@ struct BatchSet {
     uint32_t nq = 0;          // size of that batch
     uint32_t run_slots = 0;   // slots its search launch used
     uint64_t run_cap = 0;     // per-slot capacity that launch ran with (n + 1 on the full-capacity slots of the small-batch path)
+    // exact batches (device_exact.h): padded queries and their norms, the (part, query) pools and their fill counts
+    DevBuf<float> x_qpad, x_qnorm;
+    DevBuf<unsigned long long> x_pools;
+    DevBuf<uint32_t> x_counts;
     bool stats_in_hbm = false; // the last batch's statistics were not copied to pin_stats yet
 };
 constexpr int kMaxBatchSets = 4;
@@ -141,6 +146,12 @@ struct cph_filter {
     uint64_t n_bits = 0;
     uint64_t popcount = 0;
     DevBuf<uint32_t> words;
+    // the same set as an ascending id list, for the exact scan: made on the first exact use (filter_id_list), reused after
+    // that by every stream (they wait for ids_ev), freed with the filter
+    mutable std::mutex ids_mu;
+    mutable DevBuf<uint32_t> ids, ids_scratch;
+    mutable hipEvent_t ids_ev = nullptr;
+    ~cph_filter() { if (ids_ev) (void)hipEventDestroy(ids_ev); }
 };
 
 struct cph_index {
@@ -172,6 +183,8 @@ struct cph_index {
     DevBuf<uint32_t> d_rows;
     bool has_rows = false;
     bool ids_input = false;            // cph_set_result_ids: searches return input rows (needs has_rows)
+    size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
+    uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // per-query feeders on the device: rotation signs + upper layers (CSR)
     DevBuf<float> d_signs;
     DevBuf<uint32_t> d_upper;          // all layers' nodes | offsets | nbrs, concatenated
@@ -275,6 +288,7 @@ void require_finalized(cph_index* h) {
 void release_scratch(BatchSet& s) {
     s.d_bitmaps.release(); s.d_logids.release(); s.d_beam.release(); s.d_beam_tail.release();
     s.r_bitmaps.release(); s.r_logids.release(); s.r_beam.release(); s.r_beam_tail.release();
+    s.x_qpad.release(); s.x_qnorm.release(); s.x_pools.release(); s.x_counts.release();
     s.slots = 0; s.cap = 0; s.r_slots = 0;
 }
 
@@ -815,16 +829,114 @@ bool batch_has_work(cph_index* h, const cph_filter* f, const float* queries, uin
     return true;
 }
 
-// cph_search_batch[_filtered]: queries and results in host memory; f = null: unfiltered.  An empty filter launches
+// The filter's allowed ids as an ascending list on its device.  The first caller enqueues the compaction on its stream;
+// every caller's stream waits for it.
+const uint32_t* filter_id_list(const cph_filter* f, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(f->ids_mu);
+    if (!f->ids_ev) {
+        f->ids.alloc(f->popcount);
+        f->ids_scratch.alloc((f->n_bits + kFilterSpan - 1) / kFilterSpan);
+        filter_ids(f->words.p, f->n_bits, f->ids_scratch.p, f->ids.p, st);
+        hipEvent_t ev = nullptr;
+        HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_CHECK(hipEventRecord(ev, st));
+        f->ids_ev = ev;
+    } else {
+        HIP_CHECK(hipStreamWaitEvent(st, f->ids_ev, 0));
+    }
+    return f->ids.p;
+}
+
+// An exact batch (device_exact.h) in the place of enqueue_search: d_raw_q = [nq][dim] raw queries in HBM, results into
+// device buffers, everything enqueued on `st`.  The candidates are the filter's ids (not empty), or every id.
+void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
+                   int64_t* d_ids, float* d_dist, hipStream_t st) {
+    const uint64_t n = h->host.n, m = filter ? filter->popcount : n;
+    const uint32_t D = h->L.D;
+    const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT;
+    const ExactPlan pl = plan_exact(m, nq, k, h->num_cus, h->exact_scratch_bytes);
+    if (s.x_qpad.n < (size_t)nq_pad * D || s.x_pools.n < pl.pool_keys || s.x_counts.n < (size_t)pl.P * pl.tile_q || s.d_status.n < nq) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
+        s.x_qpad.alloc((size_t)nq_pad * D);
+        s.x_qnorm.alloc(nq_pad);
+        s.x_pools.alloc(pl.pool_keys);
+        s.x_counts.alloc((size_t)pl.P * pl.tile_q);
+        s.d_count.alloc(nq);
+        s.d_status.alloc(nq);
+        s.d_redo.alloc(nq);
+    }
+    const uint32_t* d_list = filter ? filter_id_list(filter, st) : nullptr;
+    s.d_stats.alloc(kStatWords);
+    HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
+    HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));      // no query expands anything
+    HIP_CHECK(hipEventRecord(s.ev0, st));
+    hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q, nq,
+                       nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * m);
+    HIP_CHECK(hipGetLastError());
+    ExactArgs a{};
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.ids = d_list;
+    a.m = (uint32_t)m;
+    a.D = D;
+    a.qpad = s.x_qpad.p;
+    a.qnorm = s.x_qnorm.p;
+    a.gq = pl.gq;
+    a.part = pl.part;
+    a.k = k;
+    a.C = pl.C;
+    a.pools = s.x_pools.p;
+    a.counts = s.x_counts.p;
+    for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile_q) {
+        a.q_first = q0;
+        a.q_count = std::min(pl.tile_q, nq - q0);
+        const dim3 grid(pl.P, (a.q_count + pl.gq - 1) / pl.gq);
+        launch_exact_scan(D, grid, (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+        hipLaunchKernelGGL(exact_merge_kernel, dim3(a.q_count), dim3(64), (size_t)pl.C * 8, st, (const unsigned long long*)s.x_pools.p,
+                           (const uint32_t*)s.x_counts.p, pl.P, a.q_first, a.q_count, k, pl.C,
+                           (const uint32_t*)(h->ids_input ? h->d_rows.p : nullptr), d_ids, d_dist);
+        HIP_CHECK(hipGetLastError());
+    }
+    s.run_slots = 0;
+    s.run_cap = 0;
+    s.nq = nq;
+    finish_batch(h, s, st);
+}
+
+// Which path a batch takes.  Exact: asked for (cph_search_batch_exact*), or a filtered batch whose filter allows at most
+// exact_threshold ids (and whose k the scan supports).  The empty filter keeps its no-launch padding path either way.
+bool takes_exact(const cph_index* h, const cph_filter* f, uint64_t k, bool exact) {
+    if (exact && k > kExactMaxK)
+        throw InvalidArg("exact search supports k <= " + std::to_string(kExactMaxK) + ", got k = " + std::to_string(k));
+    if (f && f->popcount == 0) return false;
+    return exact || (f && h->exact_threshold > 0 && f->popcount <= h->exact_threshold && k <= kExactMaxK);
+}
+
+// cph_search_batch[_filtered | _exact]: queries and results in host memory; f = null: unfiltered.  An empty filter launches
 // nothing (enqueue_search): no encoder, and its padding is written into device buffers by copy commands.
 void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* ids,
-                       float* dist) {
+                       float* dist, bool exact = false) {
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!batch_has_work(h, f, queries, n, k, ids, dist)) return;
+    exact = takes_exact(h, f, k, exact);
     h->use_device();
     hipStream_t st = own_stream(h);
     BatchSet& s = next_set(h, st);
+    if (exact) {
+        const float* d_q = upload_queries(h, s, queries, n, st);
+        if (s.d_ids.n < n * k) {
+            if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
+            s.d_ids.alloc(n * k);
+            s.d_dist.alloc(n * k);
+        }
+        enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, s.d_ids.p, s.d_dist.p, st);
+        HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
+        HIP_CHECK(hipStreamSynchronize(st));
+        return;
+    }
     const bool empty = f && f->popcount == 0;
     if (!empty && n <= kSmallBatch && n * k <= (1u << 20)) {
         // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
@@ -855,13 +967,18 @@ void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t 
 
 // cph_search_batch_device[_filtered]: queries and results in device memory, everything enqueued on the caller's stream.
 void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
-                         float* d_dist, void* stream) {
+                         float* d_dist, void* stream, bool exact = false) {
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!batch_has_work(h, f, d_queries, n, k, d_ids, d_dist)) return;
+    exact = takes_exact(h, f, k, exact);
     h->use_device();
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchSet& s = next_set(h, st);
+    if (exact) {
+        enqueue_exact(h, s, d_queries, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
+        return;
+    }
     if (!(f && f->popcount == 0)) stage_queries(h, s, d_queries, n, st);
     enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
 }
@@ -882,7 +999,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 102; }
+int cph_version(void) { return 103; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -910,6 +1027,7 @@ int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->num_cus = prop.multiProcessorCount;
         if (const char* e = getenv("CPH_QUERY_ORDER")) h->order_queries = atoi(e) != 0;
         if (const char* e = getenv("CPH_LEADER_SLOTS")) h->coal.n_slots = std::max(1, std::min(kLeaderSlots, atoi(e)));
+        if (const char* e = getenv("CPH_EXACT_SCRATCH_MB")) h->exact_scratch_bytes = (size_t)std::max(1, atoi(e)) << 20;
         if (const char* e = getenv("CPH_GATHER_US")) h->coal.gather_us = std::max(0, atoi(e));
         if (const char* e = getenv("CPH_WAVES_PER_CU")) { h->waves_per_cu = (uint32_t)std::max(1, atoi(e)); h->waves_from_env = true; }
         *out = h;
@@ -1484,6 +1602,50 @@ int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, ui
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                      int64_t* d_ids, float* d_dist, void* stream) {
     return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream); });
+}
+
+// ---- exact search -----------------------------------------------------------------------
+int cph_search_batch_exact(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* ids,
+                           float* dist) {
+    return guarded([&] { search_batch_host(h, queries, n, k, f, ids, dist, true); });
+}
+
+int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
+                                  int64_t* d_ids, float* d_dist, void* stream) {
+    return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream, true); });
+}
+
+int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->exact_threshold = max_allowed;
+    });
+}
+
+int cph_host_filter_ids(const uint32_t* words, uint64_t n_bits, uint32_t* out_ids, uint64_t* out_count) {
+    return guarded([&] {
+        if (!out_count || (n_bits != 0 && !words)) throw InvalidArg("null argument");
+        if (n_bits > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+        uint64_t pc = 0;
+        for (uint64_t w = 0, nw = (n_bits + 31) / 32; w < nw; ++w) {
+            uint32_t x = words[w];
+            if (w == nw - 1 && (n_bits & 31)) x &= (1u << (n_bits & 31)) - 1u;
+            pc += (uint64_t)__builtin_popcount(x);
+        }
+        if (pc != 0 && !out_ids) throw InvalidArg("null argument");
+        *out_count = filter_ids_host(words, n_bits, out_ids);
+    });
+}
+
+int cph_host_exact_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        if (k == 0 || k > kExactMaxK || candidates == 0 || candidates > 0xFFFFFFFFull || n_queries == 0 || n_queries > 0xFFFFFFFFull)
+            throw InvalidArg("exact plan: sizes out of range");
+        const ExactPlan pl = plan_exact(candidates, (uint32_t)n_queries, (uint32_t)k, num_cus, (size_t)scratch_bytes);
+        out[0] = pl.P; out[1] = pl.part; out[2] = pl.gq; out[3] = pl.tile_q; out[4] = pl.C; out[5] = (uint64_t)pl.pool_keys * 8;
+    });
 }
 
 }  // extern "C"
@@ -2208,7 +2370,7 @@ void multi_lifecycle(cph_multi* m, F&& first) {
 
 // cph_multi_search_batch[_filtered]: f = one filter per replica, or null.
 void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
-                        int64_t* ids, float* dist) {
+                        int64_t* ids, float* dist, bool exact = false) {
     if (!m) throw InvalidArg("null handle");
     std::shared_lock<std::shared_mutex> lk(m->life);
     const uint32_t R = (uint32_t)m->reps.size();
@@ -2228,7 +2390,9 @@ void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t
         const float* q = queries ? queries + s.lo * dim : nullptr;
         int64_t* oi = ids ? ids + s.lo * k : nullptr;
         float* od = dist ? dist + s.lo * k : nullptr;
-        const int r = cph_search_batch_filtered(h, q, s.hi - s.lo, k, f ? f[s.replica] : nullptr, oi, od);
+        const cph_filter* fr = f ? f[s.replica] : nullptr;
+        const int r = exact ? cph_search_batch_exact(h, q, s.hi - s.lo, k, fr, oi, od)
+                            : cph_search_batch_filtered(h, q, s.hi - s.lo, k, fr, oi, od);
         if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
         return r;
     }, err);
@@ -2336,6 +2500,19 @@ int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint6
 int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
                                     const cph_filter* const* f, int64_t* ids, float* dist) {
     return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist); });
+}
+
+int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
+                                 int64_t* ids, float* dist) {
+    return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist, true); });
+}
+
+int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->reps) check_rc(cph_set_exact_threshold(h, max_allowed));
+    });
 }
 
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count) {

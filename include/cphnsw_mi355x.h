@@ -187,6 +187,26 @@ int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t
  * every call does what it did before. */
 int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
 
+/* ---- per-query filters ------------------------------------------------------------------ */
+/* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
+ * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
+ * one of cph_search_batch_filtered).  Row i holds the bytes the single-filter call returns for that query and that
+ * filter.  Routing is per query, by the rules of the single-filter entries: an empty filter gives a padded row; exact != 0
+ * sends every query to the exact scan (k <= 1024; -1 scans the whole index); otherwise a filter at or below the exact
+ * threshold (and a k <= 1024) is scanned, every other filter and -1 take the graph search.  All scanned queries of the
+ * call share one pad, one scan and one merge launch (per scratch budget), all graph-searched filtered queries one launch
+ * pair, the unfiltered ones another.  Statistics: the counters are the sums of what the separate single-filter calls
+ * report, cph_last_query_expansions is 0 for scanned and padded rows, kernel_us covers the whole call.
+ * filter_of is host memory in both forms (the routing needs every filter's size on the host).  The _device form only
+ * enqueues: the call's tables travel through a pinned buffer of the batch set; the filters must outlive the batch.  It
+ * waits for no kernel, but before it rewrites that buffer it waits on the host until the copy of the tables the same
+ * batch set carried the last time (as many batches back as there are sets) has read it. */
+int cph_search_batch_filters(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                             uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist);
+int cph_search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
+                                    const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
+                                    int64_t* d_ids, float* d_dist, void* stream);
+
 /* The same bitmap contract as cph_filter_create, but bit r speaks of INPUT ROW r (the handle needs a row map, else
  * CPH_INVALID_ARGUMENT; n_bits must equal the size of the index).  The device converts it once, through the row map,
  * into an ordinary cph_filter (an internal-id bitmap), usable with every filtered entry point and with any result id
@@ -301,6 +321,10 @@ int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t
 /* cph_search_batch_exact sharded like cph_multi_search_batch_filtered; f = NULL, or one filter per replica. */
 int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
                                  const cph_filter* const* f, int64_t* ids, float* dist);
+/* cph_search_batch_filters sharded like cph_multi_search_batch_filtered: filters[f * n_dev + r] = filter f on replica r;
+ * the shards are contiguous and filter_of is sliced with the queries. */
+int cph_multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                   uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);
@@ -389,6 +413,20 @@ int cph_host_filter_ids(const uint32_t* words, uint64_t n_bits, uint32_t* out_id
  * part, queries per group, queries per launch, keys per pool, pool bytes.  More than one part: the merge kernel folds the
  * parts' lists; queries per launch < n_queries: the batch is tiled inside the call. */
 int cph_host_exact_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t* out);
+/* The grouping of a batch with per-query filters (no HIP call).  popcounts[n_filters] = allowed ids of every filter.
+ * routes[n_filters + 1]: 0 padded row, 1 exact scan, 2 graph search, per filter and, last, for the queries with -1.
+ * perm[n]: the queries ordered by filter (those with -1 last), inside a filter in query order; seg[n_filters + 2]: the
+ * queries of filter f are perm[seg[f] .. seg[f + 1]), the unfiltered ones the last segment. */
+int cph_host_filter_groups(const int32_t* filter_of, uint64_t n, const uint64_t* popcounts, uint32_t n_filters, uint64_t k,
+                           int exact, uint64_t exact_threshold, uint8_t* routes, uint32_t* perm, uint32_t* seg);
+/* The work-item table of the grouped scan (no HIP call): segment s = seg_candidates[s] ids against seg_queries[s]
+ * queries; 1 <= k <= 1024.  out[6] = items, launches, queries per group, pool capacity C in keys, pool bytes of the
+ * largest launch, 0.  items (may be NULL with cap_items 0, to size the table): the first cap_items rows of 8 words --
+ * segment, part, first candidate, end candidate, first query of the segment, queries, pool index inside the launch of
+ * (part, first query), launch.  A segment has at most 256 parts; a launch's pools stay within scratch_bytes unless one
+ * query group of one part alone exceeds it. */
+int cph_host_exact_group_plan(const uint64_t* seg_candidates, const uint64_t* seg_queries, uint32_t n_segments, uint64_t k,
+                              int num_cus, uint64_t scratch_bytes, uint32_t* items, uint64_t cap_items, uint64_t* out);
 
 #ifdef __cplusplus
 }

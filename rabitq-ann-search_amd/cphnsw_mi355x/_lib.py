@@ -47,6 +47,16 @@ SYMBOLS = {
     "cph_search_batch_exact_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_search_batch_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cph_search_batch_filters_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_multi_search_batch_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cph_host_filter_groups": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_exact_group_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p,
+                                            C.c_uint64, C.c_void_p]),
     "cph_multi_search_batch_exact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "cph_multi_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),

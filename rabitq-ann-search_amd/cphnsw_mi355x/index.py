@@ -187,6 +187,37 @@ class CPIndex:
             return f
         return self.make_filter(f)
 
+    def _filter_list(self, filter, filter_of, n):
+        """The arguments of a batch with per-query filters -> ([IdFilter], filter_of as int32 [n])."""
+        if filter_of is None:
+            # (a flat list of ids or of bools stays what it always was: ONE filter, the argument of make_filter)
+            if isinstance(filter, (list, tuple)) and any(isinstance(f, (IdFilter, np.ndarray, list, tuple)) for f in filter):
+                raise ValueError("a sequence of filters needs filter_of (the filter of every query)")
+            return None, None
+        if not isinstance(filter, (list, tuple)):
+            raise ValueError("filter_of needs filter to be a sequence of filters")
+        fo = np.asarray(filter_of)
+        if fo.ndim != 1 or fo.shape[0] != n or not (fo.size == 0 or np.issubdtype(fo.dtype, np.integer)):
+            raise ValueError(f"filter_of must be a 1D integer array of length {n} (one entry per query)")
+        if fo.size and (fo.min() < -1 or fo.max() >= len(filter)):
+            raise ValueError(f"filter_of values must lie in [-1, {len(filter)})")
+        fs = []
+        try:
+            for f in filter:
+                fs.append(self._filter(f))
+        except Exception:
+            for made, given in zip(fs, filter):     # the filters this call made are freed now, not by the collector
+                if made is not given:
+                    made.close()
+            raise
+        return fs, np.ascontiguousarray(fo, np.int32)
+
+    @staticmethod
+    def _filter_handles(fs, rep=None):
+        """cph_filter* array of a filter list: [f] of replica `rep`, or (rep None) [f][replica]."""
+        hs = [h.value for f in fs for h in (f._hs if rep is None else [f._hs[rep]])]
+        return (C.c_void_p * len(hs))(*hs) if hs else None
+
     # -- search -----------------------------------------------------------------------------
     def search(self, query, k=DEFAULT_K, filter=None, exact=False):
         """Single query, unpadded rows.  With `filter` (an IdFilter or anything make_filter accepts) only allowed ids
@@ -211,17 +242,31 @@ class CPIndex:
                                          dist.ctypes.data, C.byref(m)))
         return ids[:m.value].copy(), dist[:m.value].copy()
 
-    def search_batch(self, queries, k=DEFAULT_K, filter=None, exact=False):
+    def search_batch(self, queries, k=DEFAULT_K, filter=None, exact=False, filter_of=None):
         """Rows padded with -1 / FLT_MAX.  `filter`: restrict the results to allowed ids (see make_filter).
         `exact=True`: brute force instead of the graph search -- every row holds the k nearest allowed ids (without a
         filter: of the whole index), ascending by distance, equal distances by ascending internal id, no id twice;
-        k <= 1024.  A distance has the same bytes the graph search returns for that id.  See also exact_threshold."""
+        k <= 1024.  A distance has the same bytes the graph search returns for that id.  See also exact_threshold.
+        Per-query filters: `filter` = a sequence of filters and `filter_of` = an integer array [n] (host data): query i
+        is searched under filter[filter_of[i]], unfiltered where filter_of[i] == -1, and row i holds the bytes of the
+        single-filter call for that query and that filter.  Every query is routed on its own (padding, exact scan or
+        graph search, by the rules above); one call serves them all."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
         n, k = q.shape[0], int(k)
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
+        fs, fo = self._filter_list(filter, filter_of, n)
+        if fs is not None:
+            if self._m is not None:
+                _lib.check(_lib.lib().cph_multi_search_batch_filters(self._m, q.ctypes.data, n, k, self._filter_handles(fs),
+                                                                     len(fs), fo.ctypes.data, int(bool(exact)), ids.ctypes.data,
+                                                                     dist.ctypes.data))
+            else:
+                _lib.check(_lib.lib().cph_search_batch_filters(self._h, q.ctypes.data, n, k, self._filter_handles(fs, 0), len(fs),
+                                                               fo.ctypes.data, int(bool(exact)), ids.ctypes.data, dist.ctypes.data))
+            return ids, dist
         if exact:
             f = None if filter is None else self._filter(filter)
             if self._m is not None:
@@ -252,14 +297,15 @@ class CPIndex:
                                                         dist.ctypes.data))
         return ids, dist
 
-    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None, exact=False):
+    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None, exact=False, filter_of=None):
         """Device-resident variant: `queries` is a float32 CUDA/HIP torch tensor (n, dim) on this
         index' device; returns (ids int64, dist float32) torch tensors on the same device.  The work
         is enqueued on `stream` (default: torch's current stream) and the call does not wait for it:
         the tensors are valid in stream order.  Two batches on two streams overlap.  `filter`: as in
         search_batch (an IdFilter made here from a mask or ids is freed on return, which waits for the batch).
         A multi-device index runs the whole batch on one replica that lives on the queries' device (alternating
-        between several there); the batch is not split.  `exact`: as in search_batch."""
+        between several there); the batch is not split.  `exact`: as in search_batch.  `filter_of` (with a sequence
+        of filters): per-query filters as in search_batch; it is host data here too, a numpy array or a list."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
@@ -300,6 +346,12 @@ class CPIndex:
                 ext.wait_stream(cur)
                 for t in fresh:
                     t.record_stream(ext)
+        fs, fo = self._filter_list(filter, filter_of, n)
+        if fs is not None:
+            _lib.check(_lib.lib().cph_search_batch_filters_device(h, queries.data_ptr(), n, k, self._filter_handles(fs, rep),
+                                                                  len(fs), fo.ctypes.data, int(bool(exact)), ids.data_ptr(),
+                                                                  dist.data_ptr(), C.c_void_p(st)))
+            return ids, dist
         if exact:
             f = None if filter is None else self._filter(filter)
             _lib.check(_lib.lib().cph_search_batch_exact_device(h, queries.data_ptr(), n, k, None if f is None else f._hs[rep],

@@ -136,6 +136,16 @@ struct BatchSet {
     DevBuf<unsigned long long> x_pools;
     DevBuf<uint32_t> x_counts;
     bool stats_in_hbm = false; // the last batch's statistics were not copied to pin_stats yet
+    // batches with per-query filters (enqueue_filters): the call's tables -- scan descriptors, permutation, work lists,
+    // filter_of, bitmap pointers -- are written into pin_tab and copied to d_tab by one command on the batch's stream;
+    // ev_tab: that copy has read pin_tab (the next such batch on this set waits for it before it writes).  d_redo2: the
+    // re-run list of the batch's second pair of graph launches
+    uint8_t* pin_tab = nullptr;
+    size_t pin_tab_bytes = 0;
+    DevBuf<uint8_t> d_tab;
+    DevBuf<uint32_t> d_redo2;
+    hipEvent_t ev_tab = nullptr;
+    bool tab_used = false;
 };
 constexpr int kMaxBatchSets = 4;
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
@@ -559,8 +569,9 @@ enum class Launch {
     Direct,   // a batch small enough for the full-capacity slots, run there at once: nothing can overflow, no re-run
 };
 
-// The one table of search_kernel instantiations (24) and the only place that names them.
+// The one table of search_kernel instantiations (33) and the only place that names them.
 //   filtered (a filtered batch never probes first)          <BW, D or 0, false, true>
+//   filtered, every query under its own filter              <BW, D or 0, false, true, true>
 //   unfiltered, static D (128, 1024), probe first           <BW, D, true, false>      Launch::Main while probe_first(h)
 //   unfiltered, static D, no probe first                    <BW, D, false, false>     re-run, direct, probe first off
 //   unfiltered, any other D                                 <BW, 0, true, false>
@@ -569,34 +580,56 @@ enum class Launch {
 // of short neighbour lists (flags bit 1) and serves the workloads on which probe first does not pay.
 // The last row has no <BW, 0, false, false> twin: probe first exists for SD >= 128 only (device_search.h: kProbeFirst,
 // kStaticLayout), so with SD = 0 the PF argument is inert and both values would be the same kernel compiled twice.
-void launch_search_kernel(uint32_t bits, uint32_t D, bool pf, bool filtered, uint32_t grid, size_t lds, hipStream_t st,
-                          const SearchArgs& a) {
+void launch_search_kernel(uint32_t bits, uint32_t D, bool pf, bool filtered, bool table_of_filters, uint32_t grid, size_t lds,
+                          hipStream_t st, const SearchArgs& a) {
     using Kernel = void (*)(SearchArgs);
-    // [bits 1, 2, 4][D other, 128, 1024][no probe first, probe first, filtered]
-    static const Kernel table[3][3][3] = {
-        {{search_kernel<1, 0, true, false>, search_kernel<1, 0, true, false>, search_kernel<1, 0, false, true>},
-         {search_kernel<1, 128, false, false>, search_kernel<1, 128, true, false>, search_kernel<1, 128, false, true>},
-         {search_kernel<1, 1024, false, false>, search_kernel<1, 1024, true, false>, search_kernel<1, 1024, false, true>}},
-        {{search_kernel<2, 0, true, false>, search_kernel<2, 0, true, false>, search_kernel<2, 0, false, true>},
-         {search_kernel<2, 128, false, false>, search_kernel<2, 128, true, false>, search_kernel<2, 128, false, true>},
-         {search_kernel<2, 1024, false, false>, search_kernel<2, 1024, true, false>, search_kernel<2, 1024, false, true>}},
-        {{search_kernel<4, 0, true, false>, search_kernel<4, 0, true, false>, search_kernel<4, 0, false, true>},
-         {search_kernel<4, 128, false, false>, search_kernel<4, 128, true, false>, search_kernel<4, 128, false, true>},
-         {search_kernel<4, 1024, false, false>, search_kernel<4, 1024, true, false>, search_kernel<4, 1024, false, true>}},
+    // [bits 1, 2, 4][D other, 128, 1024][no probe first, probe first, filtered, filter table]
+    static const Kernel table[3][3][4] = {
+        {{search_kernel<1, 0, true, false>, search_kernel<1, 0, true, false>, search_kernel<1, 0, false, true>,
+          search_kernel<1, 0, false, true, true>},
+         {search_kernel<1, 128, false, false>, search_kernel<1, 128, true, false>, search_kernel<1, 128, false, true>,
+          search_kernel<1, 128, false, true, true>},
+         {search_kernel<1, 1024, false, false>, search_kernel<1, 1024, true, false>, search_kernel<1, 1024, false, true>,
+          search_kernel<1, 1024, false, true, true>}},
+        {{search_kernel<2, 0, true, false>, search_kernel<2, 0, true, false>, search_kernel<2, 0, false, true>,
+          search_kernel<2, 0, false, true, true>},
+         {search_kernel<2, 128, false, false>, search_kernel<2, 128, true, false>, search_kernel<2, 128, false, true>,
+          search_kernel<2, 128, false, true, true>},
+         {search_kernel<2, 1024, false, false>, search_kernel<2, 1024, true, false>, search_kernel<2, 1024, false, true>,
+          search_kernel<2, 1024, false, true, true>}},
+        {{search_kernel<4, 0, true, false>, search_kernel<4, 0, true, false>, search_kernel<4, 0, false, true>,
+          search_kernel<4, 0, false, true, true>},
+         {search_kernel<4, 128, false, false>, search_kernel<4, 128, true, false>, search_kernel<4, 128, false, true>,
+          search_kernel<4, 128, false, true, true>},
+         {search_kernel<4, 1024, false, false>, search_kernel<4, 1024, true, false>, search_kernel<4, 1024, false, true>,
+          search_kernel<4, 1024, false, true, true>}},
     };
-    const Kernel kernel = table[bits == 1 ? 0 : bits == 2 ? 1 : 2][D == 128 ? 1 : D == 1024 ? 2 : 0][filtered ? 2 : pf ? 1 : 0];
+    const Kernel kernel = table[bits == 1 ? 0 : bits == 2 ? 1 : 2][D == 128 ? 1 : D == 1024 ? 2 : 0][table_of_filters ? 3 : filtered ? 2 : pf ? 1 : 0];
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, st, a);
     HIP_CHECK(hipGetLastError());
 }
 
-// d_allow: the allowed-id bitmap of a filtered batch (cph_filter::words), or null.
+// One of the two pairs of graph launches of a batch with per-query filters (enqueue_filters): its queries, its three
+// queue words and its re-run list; the filtered pair also names the tables of SearchArgs.
+struct SubBatch {
+    const uint32_t* todo = nullptr;                  // the pair's queries (null: all nq, in order)
+    int queue = 0;                                   // first of its StatQueueWords
+    uint32_t* redo = nullptr;
+    const uint32_t* const* allow_tab = nullptr;
+    const uint32_t* filter_of = nullptr;
+};
+
+// d_allow: the allowed-id bitmap of a filtered batch (cph_filter::words), or null.  sub: the launch belongs to a batch
+// with per-query filters -- nq counts sub->todo.
 void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist, uint32_t* d_count,
                    const uint32_t* d_todo, Launch mode, hipStream_t st, DoneFlags done = DoneFlags(),
-                   const uint32_t* d_allow = nullptr) {
+                   const uint32_t* d_allow = nullptr, const SubBatch* sub = nullptr) {
     const uint64_t n = h->host.n;
-    const bool pf = mode == Launch::Main && d_allow == nullptr && probe_first(h);
+    const bool tab = sub && sub->allow_tab;
+    const bool pf = mode == Launch::Main && d_allow == nullptr && !tab && probe_first(h);
     SearchArgs a{};
     a.allow = d_allow;
+    if (tab) { a.allow_tab = sub->allow_tab; a.filter_of = sub->filter_of; }
     a.rows = h->ids_input ? h->d_rows.p : nullptr;
     a.done_flags = done.flags;
     a.done_seq = done.seq;
@@ -630,24 +663,26 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
         a.beam_tail = s.r_beam_tail.p;
         a.log_ids = s.r_logids.p;
     }
-    uint32_t* queue = reinterpret_cast<uint32_t*>(s.d_stats.p + kStatQueues);   // StatQueueWord
+    uint32_t* queue = reinterpret_cast<uint32_t*>(s.d_stats.p + kStatQueues) + (sub ? sub->queue : 0);   // StatQueueWord
+    uint32_t* const d_redo = sub ? sub->redo : s.d_redo.p;
     uint32_t grid = 0;
     switch (mode) {
     case Launch::Main:
         a.todo = d_todo;
         a.nq = nq;
         a.counter = queue + kQueueMain;
-        a.redo = (s.cap < n + 1 || pf) ? s.d_redo.p : nullptr;
+        a.redo = (s.cap < n + 1 || pf) ? d_redo : nullptr;
         a.redo_count = queue + kQueueRerunLen;
-        grid = s.run_slots;
+        grid = std::min(s.run_slots, nq);
         break;
     case Launch::Rerun:
-        a.todo = s.d_redo.p;
+        a.todo = d_redo;
         a.nq_dev = queue + kQueueRerunLen;
         a.counter = queue + kQueueRerun;
         grid = s.r_slots;
         break;
     case Launch::Direct:
+        a.todo = d_todo;
         a.nq = nq;
         a.counter = queue + kQueueMain;
         grid = nq;
@@ -655,7 +690,7 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     }
     const size_t lds = search_lds_bytes(h->L.D, h->L.PW, k);
     if (lds > 160 * 1024) throw InvalidArg("k too large for the on-chip result heap");
-    launch_search_kernel(h->bits, h->L.D, pf, d_allow != nullptr, grid, lds, st, a);
+    launch_search_kernel(h->bits, h->L.D, pf, d_allow != nullptr, tab, grid, lds, st, a);
 }
 
 // Statistics block to pinned memory, completion event, bookkeeping: the tail of every enqueued batch.
@@ -671,38 +706,10 @@ void finish_batch(cph_index* h, BatchSet& s, hipStream_t st) {
     h->last_search = (int)(&s - h->sets);
 }
 
-// Core: queries already staged in the set; results into device buffers.  Everything is enqueued on
-// `st` and nothing waits for the device: a query that outgrows its scratch is answered by the
-// full-capacity re-run launch that always follows the main one (it finds an empty list otherwise).
-// `filter` (null: unfiltered) restricts the result heap to its allowed ids; with no id allowed nothing is launched.
-void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist,
-                    hipStream_t st, uint32_t* d_count_out = nullptr, DoneFlags done = DoneFlags(),
-                    const cph_filter* filter = nullptr) {
+// The slots and the per-slot capacity of a graph launch over nq queries (s.run_slots, s.run_cap; the set's scratch is
+// (re)allocated to match); returns whether the launch order is closest-entry-first.
+bool size_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, hipStream_t st) {
     const uint64_t n = h->host.n;
-    if (s.d_count.n < nq) {
-        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-        s.d_count.alloc(nq);
-        s.d_status.alloc(nq);
-        s.d_redo.alloc(nq);
-    }
-    s.d_stats.alloc(kStatWords);
-    HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
-    if (filter && filter->popcount == 0) {
-        // nothing can enter a result heap: every row is padding (-1 / FLT_MAX), no query expands anything -- the search
-        // would have walked each query's whole connected component to find that out
-        uint32_t* d_count = d_count_out ? d_count_out : s.d_count.p;
-        HIP_CHECK(hipEventRecord(s.ev0, st));
-        HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, (size_t)nq * k * 8, st));
-        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_dist), (int)0x7F7FFFFF, (size_t)nq * k, st));
-        HIP_CHECK(hipMemsetAsync(d_count, 0, (size_t)nq * 4, st));
-        HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));
-        s.run_slots = 0;
-        s.run_cap = 0;
-        s.nq = nq;
-        finish_batch(h, s, st);
-        return;
-    }
-    const uint32_t* d_allow = filter ? filter->words.p : nullptr;
     // resident query slots: one wave each
     uint32_t wpc = h->waves_per_cu;
     if (!h->waves_from_env) {
@@ -749,6 +756,43 @@ void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t*
     slots = std::min(slots, s.slots);
     s.run_slots = slots;
     s.run_cap = s.cap;
+    return ordered;
+}
+
+// Core: queries already staged in the set; results into device buffers.  Everything is enqueued on
+// `st` and nothing waits for the device: a query that outgrows its scratch is answered by the
+// full-capacity re-run launch that always follows the main one (it finds an empty list otherwise).
+// `filter` (null: unfiltered) restricts the result heap to its allowed ids; with no id allowed nothing is launched.
+void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist,
+                    hipStream_t st, uint32_t* d_count_out = nullptr, DoneFlags done = DoneFlags(),
+                    const cph_filter* filter = nullptr) {
+    const uint64_t n = h->host.n;
+    if (s.d_count.n < nq) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
+        s.d_count.alloc(nq);
+        s.d_status.alloc(nq);
+        s.d_redo.alloc(nq);
+    }
+    s.d_stats.alloc(kStatWords);
+    HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
+    if (filter && filter->popcount == 0) {
+        // nothing can enter a result heap: every row is padding (-1 / FLT_MAX), no query expands anything -- the search
+        // would have walked each query's whole connected component to find that out
+        uint32_t* d_count = d_count_out ? d_count_out : s.d_count.p;
+        HIP_CHECK(hipEventRecord(s.ev0, st));
+        HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, (size_t)nq * k * 8, st));
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_dist), (int)0x7F7FFFFF, (size_t)nq * k, st));
+        HIP_CHECK(hipMemsetAsync(d_count, 0, (size_t)nq * 4, st));
+        HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));
+        s.run_slots = 0;
+        s.run_cap = 0;
+        s.nq = nq;
+        finish_batch(h, s, st);
+        return;
+    }
+    const uint32_t* d_allow = filter ? filter->words.p : nullptr;
+    const bool ordered = size_search(h, s, nq, k, st);
+    const uint32_t slots = s.run_slots;
     s.nq = nq;
     // closest-entry-first launch order (device_encode.h) when the batch outnumbers the slots
     const uint32_t* d_order = nullptr;
@@ -983,6 +1027,266 @@ void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint6
     enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
 }
 
+// ---- per-query filters: row i of the batch under filter filter_of[i] ------------------------------------------------------
+// The grouping of such a batch (device_exact.h: filter_groups), made on the host before anything touches the device.
+struct FilterGroups {
+    std::vector<uint64_t> pop;         // [F] allowed ids of every filter
+    std::vector<uint8_t> route;        // [F + 1] ExactRoute of every filter and, last, of the unfiltered queries
+    std::vector<uint32_t> perm, seg;   // [n], [F + 2]
+};
+
+FilterGroups group_filters(const cph_index* h, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, uint64_t n,
+                           uint64_t k, bool exact) {
+    if (exact && k > kExactMaxK)
+        throw InvalidArg("exact search supports k <= " + std::to_string(kExactMaxK) + ", got k = " + std::to_string(k));
+    FilterGroups g;
+    g.pop.resize(F);
+    for (uint32_t f = 0; f < F; ++f) g.pop[f] = filters[f]->popcount;
+    g.route.resize(F + 1);
+    g.perm.resize(n);
+    g.seg.resize(F + 2);
+    filter_groups(filter_of, n, g.pop.data(), F, k, exact, h->exact_threshold, g.route.data(), g.perm.data(), g.seg.data());
+    return g;
+}
+
+// What every entry with per-query filters checks, under the handle mutex, before it touches the device (batch_has_work).
+bool filters_batch_has_work(cph_index* h, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, const float* queries,
+                            uint64_t n, uint64_t k, const int64_t* ids, const float* dist) {
+    require_finalized(h);
+    if (F && !filters) throw InvalidArg("null argument");
+    for (uint32_t f = 0; f < F; ++f) {
+        if (!filters[f]) throw InvalidArg("null filter in the filter list");
+        check_filter(h, filters[f]);
+    }
+    if (n == 0 || k == 0) return false;
+    if (n > 0xFFFFFFFFull || k > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+    if (!queries || !ids || !dist || !filter_of) throw InvalidArg("null argument");
+    return true;
+}
+
+// A batch with per-query filters in the place of enqueue_search / enqueue_exact: d_raw_q = [nq][dim] raw queries in HBM,
+// results into device buffers, everything enqueued on `st`.  Per route (FilterGroups): padded rows are filled, scanned
+// queries of ALL filters share one pad launch and one scan + merge launch pair per scratch budget (device_exact.h: the
+// grouped scan), graph-searched queries run as two launch pairs -- the filtered ones through the filter-table
+// instantiation, the unfiltered ones (-1) through the kernels of the plain call, so their rows and counters are those.
+// One host wait: the tables are written into the set's pinned buffer, so the call first waits (ev_tab) until the copy of
+// the tables this set carried the last time -- n_sets batches back -- has read it; nothing waits for a kernel.  As soon as
+// one query takes the graph route, stage_queries encodes and descends ALL nq queries (the graph kernels index the staged
+// queries by row), also the scanned and padded ones.
+void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* const* filters,
+                     uint32_t F, const int32_t* filter_of, const FilterGroups& g, int64_t* d_ids, float* d_dist, hipStream_t st) {
+    const uint64_t n = h->host.n;
+    const uint32_t D = h->L.D;
+    // the segments of the scan, the other routes' sizes
+    std::vector<uint64_t> seg_m, seg_q;
+    std::vector<uint32_t> seg_group, seg_first;
+    uint32_t nqs = 0, n_pad = 0, n_gf = 0, n_gp = 0;
+    unsigned long long n_exact = 0;
+    for (uint32_t f = 0; f <= F; ++f) {
+        const uint32_t cnt = g.seg[f + 1] - g.seg[f];
+        if (!cnt) continue;
+        if (g.route[f] == kRoutePad) n_pad += cnt;
+        else if (g.route[f] == kRouteGraph) (f < F ? n_gf : n_gp) += cnt;
+        else {
+            seg_group.push_back(f);
+            seg_m.push_back(f < F ? g.pop[f] : n);
+            seg_q.push_back(cnt);
+            seg_first.push_back(nqs);
+            nqs += cnt;
+            n_exact += (unsigned long long)cnt * seg_m.back();
+        }
+    }
+    const ExactGroupPlan pl = plan_exact_groups(seg_m.data(), seg_q.data(), (uint32_t)seg_m.size(), k, h->num_cus, h->exact_scratch_bytes);
+    const uint32_t nq_pad = nqs ? (nqs + kExactQT - 1) / kExactQT * kExactQT + kExactQT : 0;   // (a group's last tile reads up to 7 rows behind it)
+    // the call's tables, one blob
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t o = need; need = (need + bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_items = take(pl.items.size() * sizeof(ExactItem)), o_desc = take((size_t)nqs * 16), o_scanq = take((size_t)nqs * 4),
+                 o_pad = take((size_t)n_pad * 4), o_gf = take((size_t)n_gf * 4), o_gp = take((size_t)n_gp * 4),
+                 o_fof = take(n_gf ? (size_t)nq * 4 : 0), o_tab = take(n_gf ? (size_t)F * 8 : 0);
+    need = std::max<size_t>(need, 16);
+    if (s.tab_used) HIP_CHECK(hipEventSynchronize(s.ev_tab));     // the copy of the set's previous tables has read pin_tab
+    const size_t pools = (size_t)pl.max_pools;
+    if (s.pin_tab_bytes < need || s.d_tab.n < need || s.x_qpad.n < (size_t)nq_pad * D || s.x_pools.n < pools * pl.C ||
+        s.x_counts.n < pools || s.d_status.n < nq || s.d_redo2.n < nq) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
+        if (s.pin_tab_bytes < need) {
+            if (s.pin_tab) HIP_CHECK(hipHostFree(s.pin_tab));
+            s.pin_tab = nullptr;
+            s.pin_tab_bytes = 0;
+            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.pin_tab), need * 2, hipHostMallocDefault));
+            s.pin_tab_bytes = need * 2;
+        }
+        s.d_tab.alloc(need * 2);
+        s.x_qpad.alloc((size_t)nq_pad * D);
+        s.x_qnorm.alloc(nq_pad);
+        s.x_pools.alloc(pools * pl.C);
+        s.x_counts.alloc(pools);
+        s.d_count.alloc(nq);
+        s.d_status.alloc(nq);
+        s.d_redo.alloc(nq);
+        s.d_redo2.alloc(nq);
+    }
+    if (!s.ev_tab) HIP_CHECK(hipEventCreateWithFlags(&s.ev_tab, hipEventDisableTiming));
+    // every scanned filter's id list: made once (filter_id_list), the stream waits for it
+    std::vector<const uint32_t*> seg_ids(seg_m.size(), nullptr);
+    for (size_t i = 0; i < seg_m.size(); ++i)
+        if (seg_group[i] < F) seg_ids[i] = filter_id_list(filters[seg_group[i]], st);
+    uint8_t* const tb = s.pin_tab;
+    ExactItem* items = reinterpret_cast<ExactItem*>(tb + o_items);
+    uint4* desc = reinterpret_cast<uint4*>(tb + o_desc);
+    uint32_t* scanq = reinterpret_cast<uint32_t*>(tb + o_scanq);
+    uint32_t *pad_rows = reinterpret_cast<uint32_t*>(tb + o_pad), *gf = reinterpret_cast<uint32_t*>(tb + o_gf),
+             *gp = reinterpret_cast<uint32_t*>(tb + o_gp);
+    for (size_t i = 0; i < seg_m.size(); ++i)
+        std::memcpy(scanq + seg_first[i], g.perm.data() + g.seg[seg_group[i]], (size_t)seg_q[i] * 4);
+    const size_t n_launch = pl.launch_pools.size();
+    std::vector<uint32_t> l_qlo(n_launch, 0xFFFFFFFFu), l_qhi(n_launch, 0);       // scan positions every launch merges
+    for (size_t i = 0; i < pl.items.size(); ++i) {
+        const ExactGroupItem& it = pl.items[i];
+        const uint32_t row0 = seg_first[it.seg] + it.q_lo;
+        items[i] = ExactItem{seg_ids[it.seg], it.c_lo, it.c_hi, row0, it.q_cnt, it.pool, 0u};
+        if (it.part != 0) continue;
+        for (uint32_t j = 0; j < it.q_cnt; ++j) desc[row0 + j] = make_uint4(it.pool + j, it.q_cnt, pl.seg_parts[it.seg], scanq[row0 + j]);
+        l_qlo[it.launch] = std::min(l_qlo[it.launch], row0);
+        l_qhi[it.launch] = std::max(l_qhi[it.launch], row0 + it.q_cnt);
+    }
+    {
+        uint32_t a_pad = 0, a_gf = 0, a_gp = 0;
+        for (uint32_t i = 0; i < nq; ++i) {
+            const uint32_t f = filter_of[i] < 0 ? F : (uint32_t)filter_of[i];
+            if (g.route[f] == kRoutePad) pad_rows[a_pad++] = i;
+            else if (g.route[f] == kRouteGraph) (f < F ? gf[a_gf++] : gp[a_gp++]) = i;
+        }
+    }
+    if (n_gf) {
+        std::memcpy(tb + o_fof, filter_of, (size_t)nq * 4);
+        const uint32_t** tab = reinterpret_cast<const uint32_t**>(tb + o_tab);
+        for (uint32_t f = 0; f < F; ++f) tab[f] = filters[f]->words.p;
+    }
+    HIP_CHECK(hipMemcpyAsync(s.d_tab.p, tb, need, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(s.ev_tab, st));
+    s.tab_used = true;
+    const uint8_t* const dt = s.d_tab.p;
+
+    s.d_stats.alloc(kStatWords);
+    HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
+    HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));      // scanned and padded queries expand nothing
+    HIP_CHECK(hipMemsetAsync(s.d_count.p, 0, (size_t)nq * 4, st));
+    HIP_CHECK(hipEventRecord(s.ev0, st));
+    const uint32_t* d_rows = h->ids_input ? h->d_rows.p : nullptr;
+    if (nqs) {
+        hipLaunchKernelGGL(exact_pad_groups_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q,
+                           reinterpret_cast<const uint32_t*>(dt + o_scanq), nqs, nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p,
+                           s.d_stats.p, n_exact);
+        HIP_CHECK(hipGetLastError());
+        ExactGroupArgs a{};
+        a.raw = h->d_raw.p;
+        a.norm_sq = h->d_norm.p;
+        a.D = D;
+        a.qpad = s.x_qpad.p;
+        a.qnorm = s.x_qnorm.p;
+        a.gq = pl.gq;
+        a.k = k;
+        a.C = pl.C;
+        a.pools = s.x_pools.p;
+        a.counts = s.x_counts.p;
+        for (size_t l = 0; l < n_launch; ++l) {
+            a.items = reinterpret_cast<const ExactItem*>(dt + o_items) + pl.launch_items[l];
+            launch_exact_scan_groups(D, pl.launch_items[l + 1] - pl.launch_items[l], (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+            hipLaunchKernelGGL(exact_merge_groups_kernel, dim3(l_qhi[l] - l_qlo[l]), dim3(64), (size_t)pl.C * 8, st,
+                               (const unsigned long long*)s.x_pools.p, (const uint32_t*)s.x_counts.p,
+                               reinterpret_cast<const uint4*>(dt + o_desc) + l_qlo[l], k, pl.C, d_rows, d_ids, d_dist);
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+    if (n_pad) {
+        hipLaunchKernelGGL(exact_fill_rows_kernel, dim3(n_pad), dim3(64), 0, st, reinterpret_cast<const uint32_t*>(dt + o_pad), k, d_ids, d_dist);
+        HIP_CHECK(hipGetLastError());
+    }
+    s.run_slots = 0;
+    s.run_cap = 0;
+    if (n_gf + n_gp) {
+        stage_queries(h, s, d_raw_q, nq, st);
+        const bool ordered = size_search(h, s, std::max(n_gf, n_gp), k, st);
+        // a pair that holds the whole batch is launched closest entry first, like a plain batch; a part of it in query order
+        const uint32_t* d_order = nullptr;
+        if (std::max(n_gf, n_gp) == nq && nq > s.run_slots && ordered) {
+            hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, st, s.d_entry_dist.p, nq, s.d_order.p);
+            HIP_CHECK(hipGetLastError());
+            d_order = s.d_order.p;
+        }
+        bool any_main = false;
+        uint32_t direct_slots = 0;
+        auto run = [&](uint32_t cnt, const uint32_t* list, SubBatch sub) {
+            if (!cnt) return;
+            sub.todo = cnt == nq ? d_order : list;
+            // (as in enqueue_search: a filtered launch does not probe first, a handful of queries goes straight to the full-capacity slots)
+            const bool rerun = s.cap < n + 1 || (!sub.allow_tab && probe_first(h));
+            if (rerun && cnt <= s.r_slots && !h->want_cap && !h->want_slots) {
+                direct_slots = std::max(direct_slots, cnt);
+                launch_search(h, s, cnt, k, d_ids, d_dist, s.d_count.p, sub.todo, Launch::Direct, st, DoneFlags(), nullptr, &sub);
+            } else {
+                any_main = true;
+                launch_search(h, s, cnt, k, d_ids, d_dist, s.d_count.p, sub.todo, Launch::Main, st, DoneFlags(), nullptr, &sub);
+                if (rerun) launch_search(h, s, cnt, k, d_ids, d_dist, s.d_count.p, nullptr, Launch::Rerun, st, DoneFlags(), nullptr, &sub);
+            }
+        };
+        SubBatch filtered, plain;
+        filtered.queue = 0;
+        filtered.redo = s.d_redo.p;
+        filtered.allow_tab = reinterpret_cast<const uint32_t* const*>(dt + o_tab);
+        filtered.filter_of = reinterpret_cast<const uint32_t*>(dt + o_fof);
+        plain.queue = kQueueSecond;
+        plain.redo = s.d_redo2.p;
+        run(n_gf, reinterpret_cast<const uint32_t*>(dt + o_gf), filtered);
+        run(n_gp, reinterpret_cast<const uint32_t*>(dt + o_gp), plain);
+        if (!any_main) {      // only the full-capacity slots ran (enqueue_search's bookkeeping for that case): the larger of the two launches
+            s.run_slots = direct_slots;
+            s.run_cap = n + 1;
+        }
+    }
+    s.nq = nq;
+    finish_batch(h, s, st);
+}
+
+// cph_search_batch_filters: queries and results in host memory.
+void search_batch_filters_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters, uint32_t F,
+                               const int32_t* filter_of, bool exact, int64_t* ids, float* dist) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!filters_batch_has_work(h, filters, F, filter_of, queries, n, k, ids, dist)) return;
+    const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
+    h->use_device();
+    hipStream_t st = own_stream(h);
+    BatchSet& s = next_set(h, st);
+    const float* d_q = upload_queries(h, s, queries, n, st);
+    if (s.d_ids.n < n * k) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
+        s.d_ids.alloc(n * k);
+        s.d_dist.alloc(n * k);
+    }
+    enqueue_filters(h, s, d_q, (uint32_t)n, (uint32_t)k, filters, F, filter_of, g, s.d_ids.p, s.d_dist.p, st);
+    HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// cph_search_batch_filters_device: queries and results in device memory (filter_of on the host), everything enqueued on
+// the caller's stream.
+void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                 uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!filters_batch_has_work(h, filters, F, filter_of, d_queries, n, k, d_ids, d_dist)) return;
+    const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
+    h->use_device();
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    BatchSet& s = next_set(h, st);
+    enqueue_filters(h, s, d_queries, (uint32_t)n, (uint32_t)k, filters, F, filter_of, g, d_ids, d_dist, st);
+}
+
 }  // namespace
 
 // diagnostic build (-DCPH_SEARCH_TRACE): where a coalesced cph_search launch spends its host time
@@ -1056,6 +1360,8 @@ static void destroy_index(cph_index* h) {
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
         if (s.pin_stats) (void)hipHostFree(s.pin_stats);
         if (s.pin_io) (void)hipHostFree(s.pin_io);
+        if (s.pin_tab) (void)hipHostFree(s.pin_tab);
+        if (s.ev_tab) (void)hipEventDestroy(s.ev_tab);
     }
 #ifdef CPH_SEARCH_TRACE
     if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
@@ -1613,6 +1919,46 @@ int cph_search_batch_exact(cph_index* h, const float* queries, uint64_t n, uint6
 int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                   int64_t* d_ids, float* d_dist, void* stream) {
     return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream, true); });
+}
+
+int cph_search_batch_filters(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                             uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist) {
+    return guarded([&] { search_batch_filters_host(h, queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist); });
+}
+
+int cph_search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                    uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* d_ids, float* d_dist,
+                                    void* stream) {
+    return guarded([&] {
+        search_batch_filters_device(h, d_queries, n, k, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, stream);
+    });
+}
+
+int cph_host_filter_groups(const int32_t* filter_of, uint64_t n, const uint64_t* popcounts, uint32_t n_filters, uint64_t k, int exact,
+                           uint64_t exact_threshold, uint8_t* routes, uint32_t* perm, uint32_t* seg) {
+    return guarded([&] {
+        if (!routes || !seg || (n && (!filter_of || !perm)) || (n_filters && !popcounts)) throw InvalidArg("null argument");
+        if (n > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+        filter_groups(filter_of, n, popcounts, n_filters, k, exact != 0, exact_threshold, routes, perm, seg);
+    });
+}
+
+int cph_host_exact_group_plan(const uint64_t* seg_candidates, const uint64_t* seg_queries, uint32_t n_segments, uint64_t k, int num_cus,
+                              uint64_t scratch_bytes, uint32_t* items, uint64_t cap_items, uint64_t* out) {
+    return guarded([&] {
+        if (!out || (n_segments && (!seg_candidates || !seg_queries)) || (cap_items && !items)) throw InvalidArg("null argument");
+        if (k == 0 || k > kExactMaxK) throw InvalidArg("exact plan: sizes out of range");
+        for (uint32_t s = 0; s < n_segments; ++s)
+            if (seg_candidates[s] > 0xFFFFFFFFull || seg_queries[s] > 0xFFFFFFFFull) throw InvalidArg("exact plan: sizes out of range");
+        const ExactGroupPlan pl = plan_exact_groups(seg_candidates, seg_queries, n_segments, (uint32_t)k, num_cus, (size_t)scratch_bytes);
+        out[0] = pl.items.size(); out[1] = pl.launch_pools.size(); out[2] = pl.gq; out[3] = pl.C;
+        out[4] = (uint64_t)pl.max_pools * pl.C * 8; out[5] = 0;
+        for (size_t i = 0; i < pl.items.size() && i < cap_items; ++i) {
+            const ExactGroupItem& it = pl.items[i];
+            const uint32_t row[8] = {it.seg, it.part, it.c_lo, it.c_hi, it.q_lo, it.q_cnt, it.pool, it.launch};
+            std::memcpy(items + i * 8, row, sizeof(row));
+        }
+    });
 }
 
 int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed) {
@@ -2401,6 +2747,45 @@ void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t
     m->last_plan = plan;
 }
 
+// cph_multi_search_batch_filters: filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
+void multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist) {
+    if (!m) throw InvalidArg("null handle");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    const uint32_t R = (uint32_t)m->reps.size();
+    if (F && !filters) throw InvalidArg("null argument");
+    for (uint32_t r = 0; r < R; ++r) {
+        cph_index* h = m->reps[r];
+        std::lock_guard<std::mutex> g(h->mu);
+        require_finalized(h);
+        for (uint32_t f = 0; f < F; ++f) {
+            if (!filters[(size_t)f * R + r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
+            check_filter(h, filters[(size_t)f * R + r]);
+        }
+    }
+    if (n && k && !filter_of) throw InvalidArg("null argument");
+    for (uint64_t i = 0; i < n && k; ++i)         // (before any shard runs: a bad value must not leave half of the rows written)
+        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
+            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
+                             std::to_string(F) + ")");
+    const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
+    const uint64_t dim = m->reps[0]->dim;
+    std::string err;
+    const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
+        cph_index* h = m->reps[s.replica];
+        std::vector<const cph_filter*> fr(F);
+        for (uint32_t f = 0; f < F; ++f) fr[f] = filters[(size_t)f * R + s.replica];
+        const int r = cph_search_batch_filters(h, queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, fr.data(), F,
+                                               filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0, ids ? ids + s.lo * k : nullptr,
+                                               dist ? dist + s.lo * k : nullptr);
+        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
+        return r;
+    }, err);
+    if (rc != CPH_OK) raise_status(rc, err);
+    std::lock_guard<std::mutex> g(m->last_mu);
+    m->last_plan = plan;
+}
+
 template <class F>
 int multi_shared(cph_multi* m, F&& f) {
     if (!m) return fail(CPH_INVALID_ARGUMENT, "null handle");
@@ -2505,6 +2890,11 @@ int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t
 int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
                                  int64_t* ids, float* dist) {
     return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist, true); });
+}
+
+int cph_multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                   uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist) {
+    return guarded([&] { multi_search_batch_filters(m, queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist); });
 }
 
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed) {

@@ -31,6 +31,9 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "device_buf.h"
 #include "device_fastscan.h"
@@ -130,15 +133,18 @@ inline uint64_t filter_ids_host(const uint32_t* words, uint64_t n_bits, uint32_t
 // ---- queries: zero-padded rows and their norms ------------------------------------------------------------------------
 // qpad[nq_pad][D] (rows behind nq are zero: the last tile reads them), qnorm[nq_pad] = the search kernel's query_norm_sq
 // (the same chains, the same tree).  Also leaves the batch's one statistic, the number of exact evaluations.
-__global__ __launch_bounds__(64) void exact_pad_kernel(const float* __restrict__ q, uint32_t nq, uint32_t nq_pad, uint32_t dim,
-                                                       uint32_t D, float* __restrict__ qpad, float* __restrict__ qnorm,
-                                                       unsigned long long* stats, unsigned long long n_exact) {
+// perm (the grouped form): padded row j holds query perm[j] -- a batch with per-query filters lays the queries of one filter
+// next to each other (cphnsw_mi355x.hip: enqueue_filters); null: row j holds query j.
+__device__ __forceinline__ void exact_pad_rows(const float* __restrict__ q, const uint32_t* __restrict__ perm, uint32_t nq,
+                                               uint32_t nq_pad, uint32_t dim, uint32_t D, float* __restrict__ qpad,
+                                               float* __restrict__ qnorm, unsigned long long* stats, unsigned long long n_exact) {
     __shared__ float s_q[2048];
     const int lane = threadIdx.x;
     if (blockIdx.x == 0 && lane == 0) stats[kStatExact] = n_exact;
     for (uint32_t qi = blockIdx.x; qi < nq_pad; qi += gridDim.x) {
+        const size_t src = (perm && qi < nq) ? perm[qi] : qi;
         for (uint32_t d = lane; d < D; d += 64) {
-            const float x = (qi < nq && d < dim) ? q[(size_t)qi * dim + d] : 0.0f;
+            const float x = (qi < nq && d < dim) ? q[src * dim + d] : 0.0f;
             s_q[d] = x;
             qpad[(size_t)qi * D + d] = x;
         }
@@ -149,6 +155,19 @@ __global__ __launch_bounds__(64) void exact_pad_kernel(const float* __restrict__
         if (lane == 0) qnorm[qi] = c;
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(64) void exact_pad_kernel(const float* __restrict__ q, uint32_t nq, uint32_t nq_pad, uint32_t dim,
+                                                       uint32_t D, float* __restrict__ qpad, float* __restrict__ qnorm,
+                                                       unsigned long long* stats, unsigned long long n_exact) {
+    exact_pad_rows(q, nullptr, nq, nq_pad, dim, D, qpad, qnorm, stats, n_exact);
+}
+
+__global__ __launch_bounds__(64) void exact_pad_groups_kernel(const float* __restrict__ q, const uint32_t* __restrict__ perm,
+                                                              uint32_t nq, uint32_t nq_pad, uint32_t dim, uint32_t D,
+                                                              float* __restrict__ qpad, float* __restrict__ qnorm,
+                                                              unsigned long long* stats, unsigned long long n_exact) {
+    exact_pad_rows(q, perm, nq, nq_pad, dim, D, qpad, qnorm, stats, n_exact);
 }
 
 // ---- the scan ---------------------------------------------------------------------------------------------------------
@@ -253,35 +272,32 @@ __device__ __forceinline__ void exact_load_chunk(const float* __restrict__ row, 
 }
 
 // SD: compile-time padded dimension (0: a.D, any power of two 16..2048); CH: dimensions a lane holds at a time (CH == SD:
-// the whole vector, loaded once per 64 candidates).  Grid (P, G), one wave per workgroup; LDS: C keys + 2 gq words.
+// the whole vector, loaded once per 64 candidates).
+// exact_scan_work is one work item, the body both scan kernels share: candidates [c_lo, c_hi) of the list `ids` (null:
+// candidate c is id c) against the nqg <= gq queries whose padded rows start at qbase / qnorms; pools / counts point at
+// the pool and the fill count of the item's first query, the other queries' follow.
 template <int SD, int CH>
-__global__ __launch_bounds__(64) void exact_scan_kernel(ExactArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
+__device__ __forceinline__ void exact_scan_work(const float* __restrict__ raw, const float* __restrict__ norm_sq,
+                                                const uint32_t* __restrict__ ids, uint32_t D, uint32_t c_lo, uint32_t c_hi,
+                                                exact_uniform_ptr qbase, exact_uniform_ptr qnorms, uint32_t nqg, uint32_t gq,
+                                                unsigned long long* const pools, uint32_t* const counts, uint32_t k, uint32_t C,
+                                                unsigned char* smem) {
     unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
-    uint32_t* s_thr = reinterpret_cast<uint32_t*>(sm + a.C);
-    uint32_t* s_cnt = s_thr + a.gq;
+    uint32_t* s_thr = reinterpret_cast<uint32_t*>(sm + C);
+    uint32_t* s_cnt = s_thr + gq;
     const int lane = threadIdx.x;
-    const uint32_t D = SD ? (uint32_t)SD : a.D;
-    const uint32_t p = blockIdx.x;
-    const uint32_t c_lo = p * a.part, c_hi = min(a.m, c_lo + a.part);
-    const uint32_t ql_lo = blockIdx.y * a.gq, ql_hi = min(a.q_count, ql_lo + a.gq);   // relative to q_first
-    if (c_lo >= c_hi || ql_lo >= ql_hi) return;
-    for (uint32_t i = lane; i < a.gq; i += 64) { s_thr[i] = 0xFFFFFFFFu; s_cnt[i] = 0; }
+    for (uint32_t i = lane; i < gq; i += 64) { s_thr[i] = 0xFFFFFFFFu; s_cnt[i] = 0; }
     __syncthreads();
-    const exact_uniform_ptr qbase = (exact_uniform_ptr)(a.qpad + (size_t)(a.q_first + ql_lo) * D);
-    const exact_uniform_ptr qnorms = (exact_uniform_ptr)(a.qnorm + a.q_first + ql_lo);
-    unsigned long long* const pools = a.pools + ((size_t)p * a.q_count + ql_lo) * a.C;
-    const uint32_t k = a.k, C = a.C;
 
     for (uint32_t cb = c_lo; cb < c_hi; cb += 64) {
         const bool valid = cb + lane < c_hi;
         const uint32_t cc = valid ? cb + lane : c_hi - 1;
-        const uint32_t id = a.ids ? a.ids[cc] : cc;
-        const float* __restrict__ row = a.raw + (size_t)id * D;
-        const float nrm = a.norm_sq[id];
+        const uint32_t id = ids ? ids[cc] : cc;
+        const float* __restrict__ row = raw + (size_t)id * D;
+        const float nrm = norm_sq[id];
         float v[CH];
         if constexpr (SD == CH) exact_load_chunk<CH>(row, v);
-        for (uint32_t qt = 0; qt < ql_hi - ql_lo; qt += kExactQT) {
+        for (uint32_t qt = 0; qt < nqg; qt += kExactQT) {
             float acc[kExactQT][8];
 #pragma unroll
             for (int t = 0; t < kExactQT; ++t)
@@ -299,7 +315,7 @@ __global__ __launch_bounds__(64) void exact_scan_kernel(ExactArgs a) {
 #pragma unroll
             for (int t = 0; t < kExactQT; ++t) {
                 const uint32_t ql = qt + t;                        // index inside the group
-                if (ql >= ql_hi - ql_lo) break;                    // (wave-uniform: the zero rows of the last tile)
+                if (ql >= nqg) break;                              // (wave-uniform: the rows behind the group in its last tile)
                 const float dot = ((acc[t][0] + acc[t][4]) + (acc[t][1] + acc[t][5])) + ((acc[t][2] + acc[t][6]) + (acc[t][3] + acc[t][7]));
                 const uint32_t dbits = __float_as_uint(exact_from_dot(qnorms[ql], nrm, dot));
                 const bool pass = valid && dbits <= s_thr[ql];
@@ -319,40 +335,126 @@ __global__ __launch_bounds__(64) void exact_scan_kernel(ExactArgs a) {
         }
     }
     // every pool: sorted, cut to k
-    for (uint32_t ql = 0; ql < ql_hi - ql_lo; ++ql) {
+    for (uint32_t ql = 0; ql < nqg; ++ql) {
         uint32_t cnt = s_cnt[ql], thr;
         if (cnt) cnt = exact_compact(sm, pools + (size_t)ql * C, cnt, k, lane, thr);
-        if (lane == 0) a.counts[(size_t)p * a.q_count + ql_lo + ql] = cnt;
+        if (lane == 0) counts[ql] = cnt;
     }
+}
+
+// Grid (P, G), one wave per workgroup; LDS: C keys + 2 gq words.
+template <int SD, int CH>
+__global__ __launch_bounds__(64) void exact_scan_kernel(ExactArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t D = SD ? (uint32_t)SD : a.D;
+    const uint32_t p = blockIdx.x;
+    const uint32_t c_lo = p * a.part, c_hi = min(a.m, c_lo + a.part);
+    const uint32_t ql_lo = blockIdx.y * a.gq, ql_hi = min(a.q_count, ql_lo + a.gq);   // relative to q_first
+    if (c_lo >= c_hi || ql_lo >= ql_hi) return;
+    const size_t pool = (size_t)p * a.q_count + ql_lo;
+    exact_scan_work<SD, CH>(a.raw, a.norm_sq, a.ids, D, c_lo, c_hi, (exact_uniform_ptr)(a.qpad + (size_t)(a.q_first + ql_lo) * D),
+                            (exact_uniform_ptr)(a.qnorm + a.q_first + ql_lo), ql_hi - ql_lo, a.gq, a.pools + pool * a.C,
+                            a.counts + pool, a.k, a.C, smem);
+}
+
+// The grouped scan of a batch with per-query filters: ONE launch for every scanned (filter, query) pair.  A SEGMENT is a
+// filter's id list (or the whole index) together with the queries that name it, contiguous in the padded query array
+// (exact_pad_groups_kernel); the host planner (plan_exact_groups) cuts every segment into parts x query groups and
+// writes one descriptor per work item; workgroup b, one wave, runs item b.  Pool geometry, LDS and the arithmetic are
+// those of exact_scan_kernel -- the same body.
+struct ExactItem {                // 32 bytes
+    const uint32_t* ids;          // the segment's ascending id list, or null: candidate c is id c
+    uint32_t c_lo, c_hi;          // candidates of this part
+    uint32_t q_lo, q_cnt;         // padded query rows of this group, q_cnt <= gq
+    uint32_t pool;                // pool (and count) index of (this part, row q_lo); row q_lo + i: pool + i
+    uint32_t reserved;
+};
+
+struct ExactGroupArgs {
+    const float* raw;             // [n][D]
+    const float* norm_sq;         // [n]
+    uint32_t D;
+    const float* qpad;            // [nq_pad][D], permuted
+    const float* qnorm;           // [nq_pad]
+    uint32_t gq, k, C;
+    unsigned long long* pools;    // [pools of the launch][C]
+    uint32_t* counts;             // [pools of the launch]
+    const ExactItem* items;       // [gridDim.x]
+};
+
+template <int SD, int CH>
+__global__ __launch_bounds__(64) void exact_scan_groups_kernel(ExactGroupArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    typedef __attribute__((address_space(4))) const uint32_t* word_ptr;
+    const word_ptr w = (word_ptr)reinterpret_cast<const uint32_t*>(a.items + blockIdx.x);   // wave-uniform: scalar loads
+    ExactItem it;
+    it.ids = reinterpret_cast<const uint32_t*>((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+    it.c_lo = w[2]; it.c_hi = w[3]; it.q_lo = w[4]; it.q_cnt = w[5]; it.pool = w[6];
+    const uint32_t D = SD ? (uint32_t)SD : a.D;
+    if (it.c_lo >= it.c_hi || it.q_cnt == 0) return;
+    exact_scan_work<SD, CH>(a.raw, a.norm_sq, it.ids, D, it.c_lo, it.c_hi, (exact_uniform_ptr)(a.qpad + (size_t)it.q_lo * D),
+                            (exact_uniform_ptr)(a.qnorm + it.q_lo), it.q_cnt, a.gq, a.pools + (size_t)it.pool * a.C,
+                            a.counts + it.pool, a.k, a.C, smem);
 }
 
 // One wave per query of the launch: the P sorted part lists -> out rows [k], ascending, ids through `rows` if given,
 // padded with -1 / FLT_MAX.  LDS: C keys: the lower half holds the Kp smallest keys so far, ascending; a part's list is
 // laid behind it in descending order and one bitonic merge (log C stages, not a sort) leaves all C ascending again.
-__global__ __launch_bounds__(64) void exact_merge_kernel(const unsigned long long* __restrict__ pools, const uint32_t* __restrict__ counts,
-                                                         uint32_t P, uint32_t q_first, uint32_t q_count, uint32_t k, uint32_t C,
-                                                         const uint32_t* __restrict__ rows, int64_t* __restrict__ out_ids,
-                                                         float* __restrict__ out_dist) {
-    extern __shared__ __align__(16) unsigned char smem[];
+// exact_merge_query is one query's fold, shared by both merge kernels: its part p's pool is pool index first + p * stride;
+// the row goes to out row `out_row`.
+__device__ __forceinline__ void exact_merge_query(const unsigned long long* __restrict__ pools, const uint32_t* __restrict__ counts,
+                                                  size_t first, uint32_t stride, uint32_t P, uint32_t k, uint32_t C,
+                                                  const uint32_t* __restrict__ rows, int64_t* __restrict__ out_ids,
+                                                  float* __restrict__ out_dist, size_t out_row, unsigned char* smem) {
     unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
     const int lane = threadIdx.x;
-    const uint32_t q = blockIdx.x, Kp = C / 2;
+    const uint32_t Kp = C / 2;
     for (uint32_t i = lane; i < Kp; i += 64) sm[i] = kExactNoKey;
     for (uint32_t p = 0; p < P; ++p) {
-        const uint32_t cnt = counts[(size_t)p * q_count + q];       // <= k <= Kp
-        const unsigned long long* pool = pools + ((size_t)p * q_count + q) * C;
+        const uint32_t cnt = counts[first + (size_t)p * stride];    // <= k <= Kp
+        const unsigned long long* pool = pools + (first + (size_t)p * stride) * C;
         for (uint32_t i = lane; i < Kp; i += 64) sm[C - 1 - i] = i < cnt ? pool[i] : kExactNoKey;
         __syncthreads();
         exact_merge_keys(sm, C, lane);
     }
     __syncthreads();
-    const size_t o = (size_t)(q_first + q) * k;
+    const size_t o = out_row * k;
     for (uint32_t i = lane; i < k; i += 64) {
         const unsigned long long key = sm[i];
         const bool have = key != kExactNoKey;
         const uint32_t id = (uint32_t)key;
         out_ids[o + i] = have ? (int64_t)(rows ? rows[id] : id) : (int64_t)-1;
         out_dist[o + i] = have ? __uint_as_float((uint32_t)(key >> 32)) : FLT_MAX;
+    }
+}
+
+__global__ __launch_bounds__(64) void exact_merge_kernel(const unsigned long long* __restrict__ pools, const uint32_t* __restrict__ counts,
+                                                         uint32_t P, uint32_t q_first, uint32_t q_count, uint32_t k, uint32_t C,
+                                                         const uint32_t* __restrict__ rows, int64_t* __restrict__ out_ids,
+                                                         float* __restrict__ out_dist) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    exact_merge_query(pools, counts, blockIdx.x, q_count, P, k, C, rows, out_ids, out_dist, (size_t)q_first + blockIdx.x, smem);
+}
+
+// The grouped merge: one wave per scanned query of the launch.  desc[q] = (pool index of its part 0, pool index stride
+// between its parts, its segment's parts, its row in the batch): the query folds the parts of its OWN segment and writes
+// to its original row.
+__global__ __launch_bounds__(64) void exact_merge_groups_kernel(const unsigned long long* __restrict__ pools,
+                                                                const uint32_t* __restrict__ counts, const uint4* __restrict__ desc,
+                                                                uint32_t k, uint32_t C, const uint32_t* __restrict__ rows,
+                                                                int64_t* __restrict__ out_ids, float* __restrict__ out_dist) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint4 d = desc[blockIdx.x];
+    exact_merge_query(pools, counts, d.x, d.y, d.z, k, C, rows, out_ids, out_dist, d.w, smem);
+}
+
+// Rows of queries whose filter allows nothing: padding.  One wave per listed row.
+__global__ __launch_bounds__(64) void exact_fill_rows_kernel(const uint32_t* __restrict__ list, uint32_t k, int64_t* __restrict__ out_ids,
+                                                             float* __restrict__ out_dist) {
+    const size_t o = (size_t)list[blockIdx.x] * k;
+    for (uint32_t i = threadIdx.x; i < k; i += 64) {
+        out_ids[o + i] = -1;
+        out_dist[o + i] = FLT_MAX;
     }
 }
 
@@ -390,6 +492,114 @@ inline ExactPlan plan_exact(uint64_t m, uint32_t nq, uint32_t k, int num_cus, si
     }
     if (pl.pool_keys * 8 > budget) parts(budget / ((size_t)pl.tile_q * pl.C * 8));
     return pl;
+}
+
+// ---- per-query filters: grouping and the grouped plan (host only, no HIP call) -----------------------------------------
+// Where a query of such a batch goes (the rules of takes_exact, per filter).
+enum ExactRoute : uint8_t {
+    kRoutePad = 0,        // its filter allows nothing: a padded row, no work
+    kRouteScan = 1,       // the exact scan
+    kRouteGraph = 2,      // the graph search
+};
+
+// Groups the n queries of a batch by filter: group f < F holds the queries with filter_of == f, group F those with -1.
+// route[F + 1]; perm[n]: the queries ordered by group, inside a group in query order; seg[F + 2]: group g is
+// perm[seg[g] .. seg[g + 1]).  popcount[F]: allowed ids of every filter.  Throws std::invalid_argument on a value outside [-1, F).
+inline void filter_groups(const int32_t* filter_of, uint64_t n, const uint64_t* popcount, uint32_t F, uint64_t k, bool exact,
+                          uint64_t exact_threshold, uint8_t* route, uint32_t* perm, uint32_t* seg) {
+    for (uint32_t f = 0; f < F; ++f)
+        route[f] = popcount[f] == 0 ? kRoutePad
+                 : (exact || (exact_threshold > 0 && popcount[f] <= exact_threshold && k <= kExactMaxK)) ? kRouteScan : kRouteGraph;
+    route[F] = exact ? kRouteScan : kRouteGraph;
+    for (uint32_t g = 0; g < F + 2; ++g) seg[g] = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int32_t f = filter_of[i];
+        if (f < -1 || f >= (int64_t)F)
+            throw std::invalid_argument("filter_of[" + std::to_string(i) + "] = " + std::to_string(f) + " is outside [-1, " +
+                                        std::to_string(F) + ")");
+        ++seg[(f < 0 ? F : (uint32_t)f) + 1];
+    }
+    for (uint32_t g = 0; g < F + 1; ++g) seg[g + 1] += seg[g];
+    std::vector<uint32_t> at(seg, seg + F + 1);
+    for (uint64_t i = 0; i < n; ++i) perm[at[filter_of[i] < 0 ? F : (uint32_t)filter_of[i]]++] = (uint32_t)i;
+}
+
+// One work item of the grouped scan as the planner states it (ExactItem is the device form).
+struct ExactGroupItem {
+    uint32_t seg, part;           // segment, part of the segment
+    uint32_t c_lo, c_hi;          // candidates [c_lo, c_hi) of the segment
+    uint32_t q_lo, q_cnt;         // queries [q_lo, q_lo + q_cnt) of the segment
+    uint32_t pool;                // pool index inside the launch of (this part, query q_lo); query q_lo + i: pool + i
+    uint32_t launch;
+};
+struct ExactGroupPlan {
+    uint32_t Kp = 0, C = 0, gq = 0;
+    std::vector<ExactGroupItem> items;        // ordered by (launch, segment, query group, part)
+    std::vector<uint32_t> launch_items;       // [launches + 1]: launch l is items [launch_items[l], launch_items[l + 1])
+    std::vector<uint32_t> launch_pools;       // [launches]: pools (of C keys) launch l uses
+    std::vector<uint32_t> seg_parts;          // [segments]
+    uint32_t max_pools = 0;
+};
+
+// Segment s: seg_m[s] candidates against seg_q[s] queries (one with no candidate or no query gets no item).  Every
+// segment is cut into query groups of at most gq and into parts of whole 64-candidate blocks, at most kExactMaxParts.
+// The parts are sized over ALL segments: about `waves` = two per SIMD work items of equal candidate-block count, so a
+// small segment stays whole and a large one is cut as often as its share of the work says.  Pools: one per (part, query);
+// a launch takes (segment, group) units in order while its pools fit the budget -- a unit whose parts alone would not
+// fit gets fewer parts (one at least: like plan_exact, a budget below one group's pools is exceeded).
+inline ExactGroupPlan plan_exact_groups(const uint64_t* seg_m, const uint64_t* seg_q, uint32_t n_seg, uint32_t k, int num_cus,
+                                        size_t budget) {
+    ExactGroupPlan pl;
+    pl.Kp = 64;
+    while (pl.Kp < k) pl.Kp <<= 1;
+    pl.C = 2 * pl.Kp;
+    pl.gq = 128;
+    const uint64_t waves = (uint64_t)std::max(1, num_cus) * 8;
+    const uint64_t budget_pools = std::max<uint64_t>(1, (uint64_t)budget / ((uint64_t)pl.C * 8));
+    uint64_t total = 0;                       // candidate blocks x query groups
+    for (uint32_t s = 0; s < n_seg; ++s)
+        if (seg_m[s] && seg_q[s]) total += ((seg_m[s] + 63) / 64) * ((seg_q[s] + pl.gq - 1) / pl.gq);
+    const uint64_t per = std::max<uint64_t>(1, (total + waves - 1) / waves);    // blocks per item
+    pl.seg_parts.assign(n_seg, 0);
+    pl.launch_items.push_back(0);
+    uint64_t used = 0;
+    uint32_t launch = 0;
+    for (uint32_t s = 0; s < n_seg; ++s) {
+        if (!seg_m[s] || !seg_q[s]) continue;
+        const uint64_t m = seg_m[s], blocks = (m + 63) / 64, widest = std::min<uint64_t>(pl.gq, seg_q[s]);
+        uint64_t want = std::min<uint64_t>({(blocks + per - 1) / per, blocks, (uint64_t)kExactMaxParts});
+        want = std::max<uint64_t>(1, std::min<uint64_t>(want, budget_pools / widest));
+        const uint32_t part = (uint32_t)((blocks + want - 1) / want * 64);
+        const uint32_t P = (uint32_t)((m + part - 1) / part);
+        pl.seg_parts[s] = P;
+        for (uint64_t q0 = 0; q0 < seg_q[s]; q0 += pl.gq) {
+            const uint32_t qc = (uint32_t)std::min<uint64_t>(pl.gq, seg_q[s] - q0);
+            const uint64_t need = (uint64_t)P * qc;
+            if (used && used + need > budget_pools) {
+                pl.launch_items.push_back((uint32_t)pl.items.size());
+                pl.launch_pools.push_back((uint32_t)used);
+                used = 0;
+                ++launch;
+            }
+            for (uint32_t p = 0; p < P; ++p)
+                pl.items.push_back(ExactGroupItem{s, p, p * part, (uint32_t)std::min<uint64_t>(m, (uint64_t)(p + 1) * part), (uint32_t)q0, qc,
+                                                  (uint32_t)(used + (uint64_t)p * qc), launch});
+            used += need;
+        }
+    }
+    if (used) {
+        pl.launch_items.push_back((uint32_t)pl.items.size());
+        pl.launch_pools.push_back((uint32_t)used);
+    }
+    for (uint32_t x : pl.launch_pools) pl.max_pools = std::max(pl.max_pools, x);
+    return pl;
+}
+
+inline void launch_exact_scan_groups(uint32_t D, uint32_t items, size_t lds, hipStream_t st, const ExactGroupArgs& a) {
+    if (D == 128) hipLaunchKernelGGL((exact_scan_groups_kernel<128, 128>), dim3(items), dim3(64), lds, st, a);
+    else if (D == 1024) hipLaunchKernelGGL((exact_scan_groups_kernel<1024, 64>), dim3(items), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((exact_scan_groups_kernel<0, 16>), dim3(items), dim3(64), lds, st, a);
+    HIP_CHECK(hipGetLastError());
 }
 
 inline void launch_exact_scan(uint32_t D, dim3 grid, size_t lds, hipStream_t st, const ExactArgs& a) {

@@ -59,12 +59,15 @@ enum StatWord : int {
     kStatFlushed = 10,
 #endif
     kStatQueues = 16,           // from here on u32 words, indexed by StatQueueWord
-    kStatWords = 18,
+    kStatWords = 20,
 };
 enum StatQueueWord : int {      // the u32 words at stats + kStatQueues
     kQueueMain = 0,             // work-queue counter of the main (or direct) launch
     kQueueRerunLen = 1,         // length of the re-run list
     kQueueRerun = 2,            // work-queue counter of the re-run launch
+    // a batch with per-query filters runs two pairs of launches, one over the filtered queries, one over the unfiltered:
+    // the second pair's three words
+    kQueueSecond = 3,
 };
 
 struct SearchArgs {
@@ -112,6 +115,10 @@ struct SearchArgs {
     // optional: the row map, [n] (result ids in input rows, cph_set_result_ids): a result id i leaves as rows[i].  Null:
     // internal ids.  Read once per query, where the rows are written; the search itself knows internal ids only.
     const uint32_t* rows;
+    // filter-table instantiations only (FTAB): a batch whose queries carry their own filters.  allow_tab[f] = the bitmap
+    // of filter f, filter_of[qi] = the filter of query qi (every query such a launch runs has one); `allow` is unused.
+    const uint32_t* const* allow_tab;
+    const uint32_t* filter_of;
 };
 
 // Kernel arguments that are touched once per query (work queue, encoded-query arrays, outputs, statistics) are read from
@@ -693,7 +700,10 @@ __host__ __device__ constexpr int search_waves_per_simd(int sd, int bw) {
 // FILT: filtered search -- only ids whose bit is set in SearchArgs::allow enter the result heap (the reference's nn.push at
 // its three call sites, gated; nothing else changes: every vertex is still estimated, reranked, pushed into the beam and
 // expanded as before).  Instantiated without probe first only: its stage-2 hand-over is never combined with a filter.
-template <int BW, int SD, bool PF = true, bool FILT = false>
+// FTAB (with FILT): the bitmap is the query's own -- looked up in SearchArgs::allow_tab once, where the query is taken from
+// the work queue, and kept in scalar registers; the expansion loop is the FILT one.  A FILT instantiation without FTAB
+// reads SearchArgs::allow as ever.
+template <int BW, int SD, bool PF = true, bool FILT = false, bool FTAB = false>
 __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kernel(SearchArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -765,6 +775,8 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             for (uint32_t d = lane; d < D; d += 64) qv[d] = queries[(size_t)qi * D + d];
         }
         const QueryHeader hd = CPH_COLD(qhdr)[qi];
+        const uint32_t* allow_q = nullptr;
+        if constexpr (FTAB) allow_q = CPH_COLD(allow_tab)[CPH_COLD(filter_of)[qi]];
         __syncthreads();
 
         QP qp;
@@ -913,7 +925,8 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             const uint32_t nid_ld = reinterpret_cast<const uint32_t*>(blk + blk_ids_off)[li];
             // filtered: the popped vertex's allowed bit travels with the norm (retired with the block's loads below)
             uint32_t allow_cur = 0;
-            if constexpr (FILT) allow_cur = CPH_COLD(allow)[cur_id >> 5];
+            if constexpr (FTAB) allow_cur = allow_q[cur_id >> 5];
+            else if constexpr (FILT) allow_cur = CPH_COLD(allow)[cur_id >> 5];
             // ---- everything else this expansion reads is issued before the probe ----------
             BlockLoads<BW, SD> bl;
             // PROBE FIRST (the static-D instantiations, D = 128 and D = 1024; 4-bit codes at D = 128 in round 3, every width and
@@ -1178,7 +1191,8 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             uint32_t allow_mask = 0;
             if (cand_mask) {
                 uint32_t allow_w = 0;
-                if constexpr (FILT) allow_w = CPH_COLD(allow)[is_new ? nid >> 5 : 0u];
+                if constexpr (FTAB) allow_w = allow_q[is_new ? nid >> 5 : 0u];
+                else if constexpr (FILT) allow_w = CPH_COLD(allow)[is_new ? nid >> 5 : 0u];
                 if (cand) s_list[__builtin_amdgcn_mbcnt_lo(cand_mask, 0u)] = (uint8_t)lane;
                 __syncthreads();
                 const uint32_t n_cand = __popc(cand_mask);

@@ -5,6 +5,8 @@ import re
 import sys
 
 txt = open(sys.argv[1]).read()
+# .file <index> ["dir"] "name": the source file a .loc's first number speaks of
+files = {int(i): name.rsplit("/", 1)[-1] for i, name in re.findall(r'^\s*\.file\s+(\d+)\s+(?:"[^"]*"\s+)?"([^"]+)"', txt, re.M)}
 for kn in re.findall(r"^(_ZN3cph13search_kernelILi\dELi\d+E(?:Lb\dE)*EEvNS_10SearchArgsE):", txt, re.M):
     m = re.search(r"^%s:(.*?)^\s*\.end_amdhsa_kernel" % re.escape(kn), txt, re.S | re.M)
     lines = m.group(1).splitlines()
@@ -12,7 +14,7 @@ for kn in re.findall(r"^(_ZN3cph13search_kernelILi\dELi\d+E(?:Lb\dE)*EEvNS_10Sea
     for i, ln in enumerate(lines):
         mm = re.search(r"\.loc\s+(\d+)\s+(\d+)", ln)
         if mm:
-            cur = int(mm.group(2))
+            cur = "%s:%s" % (files.get(int(mm.group(1)), "file %s" % mm.group(1)), mm.group(2))
         lb = re.match(r"^\.LBB\S+:\s*;\s*(.*)", ln)
         if re.match(r"^\.LBB\S+:", ln):
             dm = re.search(r"Depth=(\d+)", ln)
@@ -24,4 +26,4 @@ for kn in re.findall(r"^(_ZN3cph13search_kernelILi\dELi\d+E(?:Lb\dE)*EEvNS_10Sea
             out.append((cur, depth, ln.strip().split(";")[0].strip()))
     print(kn[17:30], "in-loop scratch ops:", len(out))
     for o in out:
-        print("    line", o[0], "depth", o[1], o[2])
+        print("    at", o[0], "depth", o[1], o[2])

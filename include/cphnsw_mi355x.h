@@ -336,6 +336,91 @@ int cph_multi_last_query_expansions(cph_multi* m, uint32_t* out, uint64_t n);
 int cph_multi_num_replicas(cph_multi* m, uint32_t* n);
 int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out);
 
+/* ---- one index split across several devices (parts; csrc/partitioned.h, csrc/device_merge.h) ------------------- */
+/* A cph_multi replicates: more queries per second, the same capacity and the same build time.  A cph_parts PARTITIONS
+ * (what FAISS calls IndexShards): part p is an ordinary single-device index over the contiguous input rows
+ * [lo_p, hi_p) on devices[p] (ordinals may repeat), every query goes to all parts, and their rows are merged.
+ *
+ *   create   devices[n_dev]: HIP ordinals, 1 <= n_dev <= 16.  devices[0] is the home device: the merge runs there.
+ *   build    n rows: part p gets rows [n/P * p + min(p, n % P), ...): contiguous, sizes differ by at most one
+ *            (cph_host_part_bounds).  n < 64 * P is CPH_INVALID_ARGUMENT.
+ *   finalize every part's builder at once, each on its part's worker thread, with 1 / P of the host threads
+ *            (CPH_BUILD_THREADS or its default, divided by P).
+ *   ids      input rows only: every id is lo_p + (the part's input row).  There is no internal id space across parts.
+ *   search_batch[_filtered | _exact | _filters]
+ *            every part searches the whole batch with the caller's k (the existing cph_search_batch_device* of the part,
+ *            CPH_IDS_INPUT, on the part's worker thread); the P rows of a query travel to the home device (a peer copy
+ *            where hipDeviceCanAccessPeer allows it, else through pinned host memory) and row i of the answer is the
+ *            first k entries of their STABLE MERGE in part order: ascending distance compared as float values, equal
+ *            distances lower part first, inside a part the part's own order (numpy: argsort(concatenate(rows),
+ *            kind="stable")[:k]).  Padding (-1 / FLT_MAX) sorts last and stays padding; a part's duplicate slots pass
+ *            through; distance bytes are the part's.  _exact: the exact global top-k, equal distance bits ordered by part,
+ *            then by the part's internal id.  The exact threshold (set_exact_threshold) is compared with the PART's
+ *            allowed count; a part whose slice of a filter is empty returns padding without a launch.
+ *   search_batch_device (and the _filtered, _exact_device, _filters_device forms)
+ *            queries and results on the home device.  The call waits ON THE HOST for the searches of all parts, then
+ *            enqueues the merge on `stream` and returns: the results are complete in stream order.  filter_of is host
+ *            memory.
+ *   search   a batch of one through all parts (not the coalesced path of cph_search); *count results, unpadded.
+ *   filter_create_rows
+ *            words = allowed-row bitmap over ALL input rows (n_bits = size).  It is cut at the part bounds and every
+ *            part gets cph_filter_create_rows on its slice; the object holds the P filters.
+ *   last_search_stats
+ *            out[0..11] as cph_last_search_stats, summed over the parts, kernel_us ([6]) and capacity ([9]) the maximum;
+ *            out[12] = device time of the merge kernel in microseconds.  last_query_expansions: summed per query.
+ *   save_native / load_native
+ *            one ordinary format-2 native file per part, `path`.p<i>of<P>.  load_native validates all P files first: a
+ *            missing file (also: saved with another number of parts), a wrong dim or bits, or a part without a row map
+ *            is CPH_INVALID_ARGUMENT and leaves the handle as it was; the validated files are then installed as read.  A
+ *            device failure during that (out of memory) leaves no part searchable until the next successful load_native
+ *            or finalize.  There is no v2 form: that format holds one graph and no row map.
+ *   part     borrowed handle of part i (owned by m): searches, filters, hooks, cph_get_row_map, cph_get_vectors in the
+ *            part's own spaces.  cph_load*, cph_build, cph_finalize, cph_set_row_map and cph_destroy on it fail; switching
+ *            it to CPH_IDS_INTERNAL makes the searches of m fail until it is switched back.
+ *   bounds   out[P + 1]: part p holds input rows [out[p], out[p + 1]).
+ * Threads: searches on one handle run one after the other; build, finalize, load_native and destroy wait for them. */
+typedef struct cph_parts cph_parts;
+typedef struct cph_parts_filter cph_parts_filter;
+int cph_parts_create(uint64_t dim, uint64_t bits, const int* devices, uint32_t n_dev, cph_parts** out);
+int cph_parts_destroy(cph_parts* m);
+int cph_parts_build(cph_parts* m, const float* vectors, uint64_t n);
+int cph_parts_finalize(cph_parts* m);
+int cph_parts_size(cph_parts* m, uint64_t* n);
+int cph_parts_is_finalized(cph_parts* m, int* flag);
+int cph_parts_save_native(cph_parts* m, const char* path);
+int cph_parts_load_native(cph_parts* m, const char* path);
+int cph_parts_search_batch(cph_parts* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist);
+int cph_parts_search_batch_filtered(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                    int64_t* ids, float* dist);
+int cph_parts_search_batch_exact(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                 int64_t* ids, float* dist);
+int cph_parts_search_batch_filters(cph_parts* m, const float* queries, uint64_t n, uint64_t k,
+                                   const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
+                                   int64_t* ids, float* dist);
+int cph_parts_search_batch_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, int64_t* d_ids, float* d_dist,
+                                  void* stream);
+int cph_parts_search_batch_device_filtered(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                           int64_t* d_ids, float* d_dist, void* stream);
+int cph_parts_search_batch_exact_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                        int64_t* d_ids, float* d_dist, void* stream);
+int cph_parts_search_batch_filters_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k,
+                                          const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                                          int exact, int64_t* d_ids, float* d_dist, void* stream);
+int cph_parts_search(cph_parts* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
+int cph_parts_set_exact_threshold(cph_parts* m, uint64_t max_allowed);
+int cph_parts_filter_create_rows(cph_parts* m, const uint32_t* words, uint64_t n_bits, cph_parts_filter** out);
+int cph_parts_filter_destroy(cph_parts_filter* f);
+int cph_parts_last_search_stats(cph_parts* m, uint64_t out[13]);
+int cph_parts_last_query_expansions(cph_parts* m, uint32_t* out, uint64_t n);
+int cph_parts_num_parts(cph_parts* m, uint32_t* n);
+int cph_parts_part(cph_parts* m, uint32_t i, cph_index** out);
+int cph_parts_bounds(cph_parts* m, uint64_t* out);
+/* Test hook: merge_parts_kernel on given rows (host arrays): ids / dist [P][n][k], every row ascending in distance,
+ * lo[P]; out_ids / out_dist [n][k] are uploaded first, so a slot the kernel did not write keeps the caller's value.
+ * 1 <= P <= 16, n >= 1, k >= 1. */
+int cph_merge_rows_hook(int device, const int64_t* ids, const float* dist, uint32_t P, uint64_t n, uint64_t k, const int64_t* lo,
+                        int64_t* out_ids, float* out_dist);
+
 /* ---- kernel-level hooks ------------------------------------------------------------ */
 /* Query encoder (encoder/rabitq_encoder.hpp:73-79,98-136,197-209): lut = u8[D/4][16] in
  * the reference's LUT format, coeffs = {coeff_fastscan, coeff_popcount, coeff_constant}. */
@@ -427,6 +512,9 @@ int cph_host_filter_groups(const int32_t* filter_of, uint64_t n, const uint64_t*
  * query group of one part alone exceeds it. */
 int cph_host_exact_group_plan(const uint64_t* seg_candidates, const uint64_t* seg_queries, uint32_t n_segments, uint64_t k,
                               int num_cus, uint64_t scratch_bytes, uint32_t* items, uint64_t cap_items, uint64_t* out);
+/* The part bounds of a partitioned index (no HIP call): out[P + 1], part p of P over n rows holds the input rows
+ * [out[p], out[p + 1]); 1 <= P <= 16. */
+int cph_host_part_bounds(uint64_t n, uint32_t P, uint64_t* out);
 
 #ifdef __cplusplus
 }

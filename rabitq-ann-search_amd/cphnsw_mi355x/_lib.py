@@ -99,6 +99,41 @@ SYMBOLS = {
     "cph_multi_last_query_expansions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "cph_multi_num_replicas": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "cph_multi_replica": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cph_parts_create": (C.c_int, [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cph_parts_destroy": (C.c_int, [C.c_void_p]),
+    "cph_parts_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_parts_finalize": (C.c_int, [C.c_void_p]),
+    "cph_parts_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_parts_is_finalized": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_parts_save_native": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_parts_load_native": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "cph_parts_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cph_parts_search_batch_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "cph_parts_search_batch_exact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "cph_parts_search_batch_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cph_parts_search_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "cph_parts_search_batch_device_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_parts_search_batch_exact_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_parts_search_batch_filters_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_parts_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_parts_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_parts_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "cph_parts_filter_destroy": (C.c_int, [C.c_void_p]),
+    "cph_parts_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_parts_last_query_expansions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_parts_num_parts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "cph_parts_part": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "cph_parts_bounds": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_merge_rows_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "cph_host_part_bounds": (C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p]),
     "cph_encode_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_entry_point": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "cph_fastscan_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float,

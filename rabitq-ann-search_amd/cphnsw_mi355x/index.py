@@ -35,14 +35,23 @@ class IdFilter:
     input_rows=True, of input rows: the device then converts it through the index' row map, once, into the internal-id
     bitmap the searches read.  Usable with any index of the same size on the same device; freeing it waits for the
     batches that may still read it.  A multi-device index' filter holds one bitmap per replica, each on that
-    replica's device."""
+    replica's device.  A partitioned index' filter speaks of global input rows and holds one bitmap per part, each the
+    part's slice, behind one handle."""
 
     def __init__(self, index, words, n_bits, count, input_rows=False):
         self._h = C.c_void_p()
         self._hs = []                # one cph_filter per replica (a single-device index: one)
+        self._pf = None              # partitioned index: the cph_parts_filter that owns the per-part filters
         self.size = int(n_bits)      # ids the filter covers (= the index size)
         self.count = int(count)      # allowed ids
         w = np.ascontiguousarray(words, np.uint32)
+        if index._p is not None:
+            pf = C.c_void_p()
+            _lib.check(_lib.lib().cph_parts_filter_create_rows(index._p, w.ctypes.data if w.size else None, self.size,
+                                                               C.byref(pf)))
+            self._pf = pf
+            self._parts = len(index._devices)
+            return
         for rh in index._replicas():
             h = C.c_void_p()
             create = _lib.lib().cph_filter_create_rows if input_rows else _lib.lib().cph_filter_create
@@ -51,6 +60,10 @@ class IdFilter:
         self._h = self._hs[0]
 
     def close(self):
+        pf = getattr(self, "_pf", None)
+        if pf is not None:
+            self._pf = None
+            _lib.check(_lib.lib().cph_parts_filter_destroy(pf))
         hs = getattr(self, "_hs", [])
         self._hs = []
         self._h = C.c_void_p()
@@ -68,23 +81,49 @@ class IdFilter:
 class CPIndex:
     """`devices=[...]` (instead of `device`): the index is replicated on every listed HIP device (duplicates allowed:
     several replicas on one GPU) and search_batch splits its queries across the replicas in one call, with results
-    byte-identical to a single-device index.  Hooks, get_vectors and internal_to_input_rows are served by replica 0."""
+    byte-identical to a single-device index.  Hooks, get_vectors and internal_to_input_rows are served by replica 0.
 
-    def __init__(self, dim, bits=1, device=None, devices=None):
+    `devices=[...], partition=True`: the index is PARTITIONED instead (FAISS: IndexShards).  build() gives device p the
+    contiguous rows dist.shard_bounds(n, P, p) as an ordinary single-device index, finalize() builds all parts at once,
+    every search goes to all parts and row i of the answer is the first k entries of the stable merge of their rows
+    (ascending distance, equal distances lower part first), made on devices[0].  One handle holds P times as much and
+    the quadratic build does 1 / P of the work, on P devices; a query costs P searches.  Such an index speaks input
+    rows only (result_ids is "input"), is saved and loaded with save_native / load_native (one file per part), and has
+    no index-wide hooks: `parts` lists the (lo, hi) bounds and `part(i)` is part i as a single-device CPIndex."""
+
+    def __init__(self, dim, bits=1, device=None, devices=None, partition=False):
         self._h = C.c_void_p()
         self._m = None               # cph_multi handle of a multi-device index
+        self._p = None               # cph_parts handle of a partitioned index
+        self._owner = None           # a part(i) view: the partitioned index that owns the handle
         if dim < 0 or bits < 0:
             raise TypeError("CPIndex(): incompatible constructor arguments")  # size_t in pybind11
         self._dim = int(dim)
         self._bits = int(bits)
         self._result_ids = "internal"
         self._exact_threshold = 0
+        if partition and (devices is None or device is not None):
+            raise ValueError("partition=True needs devices=[...] (one part per listed device), not device")
         if devices is not None:
             if device is not None:
                 raise ValueError("pass either device or devices, not both")
             devs = [int(d) for d in devices]
             if not devs:
                 raise ValueError("devices must list at least one device")
+            if partition:
+                p = C.c_void_p()
+                _lib.check(_lib.lib().cph_parts_create(int(dim), int(bits), (C.c_int * len(devs))(*devs), len(devs),
+                                                       C.byref(p)))
+                self._p = p
+                self._devices = devs
+                self._device = devs[0]
+                self._result_ids = "input"
+                self._part_handles = []      # borrowed part handles (owned by the parts handle)
+                for i in range(len(devs)):
+                    h = C.c_void_p()
+                    _lib.check(_lib.lib().cph_parts_part(p, i, C.byref(h)))
+                    self._part_handles.append(h)
+                return
             m = C.c_void_p()
             _lib.check(_lib.lib().cph_multi_create(int(dim), int(bits), (C.c_int * len(devs))(*devs), len(devs),
                                                    C.byref(m)))
@@ -106,6 +145,18 @@ class CPIndex:
         _lib.check(_lib.lib().cph_create(int(dim), int(bits), int(device), C.byref(self._h)))
 
     def __del__(self):
+        if getattr(self, "_owner", None) is not None:      # a borrowed part: the partitioned index destroys it
+            self._owner = None
+            self._h = C.c_void_p()
+            return
+        p = getattr(self, "_p", None)
+        if p is not None:
+            self._p = None
+            try:
+                _lib.lib().cph_parts_destroy(p)
+            except Exception:
+                pass
+            return
         m = getattr(self, "_m", None)
         if m is not None:
             self._m = None
@@ -124,7 +175,51 @@ class CPIndex:
             self._h = C.c_void_p()
 
     def _replicas(self):
+        if self._p is not None:
+            return self._part_handles
         return self._reps if self._m is not None else [self._h]
+
+    # -- partitioned index (not in the reference) -----------------------------------------------
+    @property
+    def partitioned(self):
+        return self._p is not None
+
+    @property
+    def parts(self):
+        """[(lo, hi)] input rows of every part of a partitioned index (zeros before build())."""
+        self._need_parts("parts")
+        b = np.zeros(len(self._devices) + 1, np.uint64)
+        _lib.check(_lib.lib().cph_parts_bounds(self._p, b.ctypes.data))
+        return [(int(b[i]), int(b[i + 1])) for i in range(len(self._devices))]
+
+    def part(self, i):
+        """Part i of a partitioned index as a single-device CPIndex over its slice: a borrowed view (the partitioned
+        index owns it and must outlive it) that returns slice-local input rows; add parts[i][0] for global rows.  Its
+        hooks, row_map() and get_vectors work as on any index; load, build and finalize on it are refused."""
+        self._need_parts("part()")
+        i = int(i)
+        if not 0 <= i < len(self._devices):
+            raise ValueError(f"part index must lie in [0, {len(self._devices)})")
+        v = CPIndex.__new__(CPIndex)
+        v._h = self._part_handles[i]
+        v._m = None
+        v._p = None
+        v._owner = self
+        v._dim, v._bits = self._dim, self._bits
+        v._device = self._devices[i]
+        v._devices = [self._devices[i]]
+        v._result_ids = "input" if self.is_finalized else "internal"
+        v._exact_threshold = self._exact_threshold
+        return v
+
+    def _need_parts(self, what):
+        if self._p is None:
+            raise ValueError(f"{what} needs a partitioned index (CPIndex(..., devices=[...], partition=True))")
+
+    def _no_parts(self, what):
+        if self._p is not None:
+            raise ValueError(f"{what} is not defined on a partitioned index (every part has its own internal ids): "
+                             f"use part(i).{what}")
 
     @property
     def devices(self):
@@ -142,6 +237,9 @@ class CPIndex:
         v = _as_f32(vectors)
         if v.ndim != 2 or v.shape[1] != self._dim:
             raise ValueError("vectors must be a (n, dim) float32 array")
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_build(self._p, v.ctypes.data, v.shape[0]))
+            return
         self._result_ids = "internal"    # the old index and its row map are gone
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_build(self._m, v.ctypes.data, v.shape[0]))
@@ -149,6 +247,9 @@ class CPIndex:
         _lib.check(_lib.lib().cph_build(self._h, v.ctypes.data, v.shape[0]))
 
     def finalize(self):
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_finalize(self._p))
+            return
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_finalize(self._m))
             return
@@ -162,6 +263,8 @@ class CPIndex:
         space = self._result_ids if ids is None else ids
         if space not in ("internal", "input"):
             raise ValueError('ids must be "internal" or "input"')
+        if self._p is not None and space != "input":
+            raise ValueError('a partitioned index takes filters in input rows only (ids="input")')
         a = np.asarray(allowed)
         n = self.size
         if a.dtype == bool:
@@ -180,6 +283,12 @@ class CPIndex:
 
     def _filter(self, f):
         if isinstance(f, IdFilter):
+            if self._p is not None:
+                if f._pf is None:
+                    raise ValueError("filter was closed, or was not made by a partitioned index")
+                if f._parts != len(self._devices):
+                    raise ValueError("filter was made for an index with another number of parts")
+                return f
             if not f._h.value:
                 raise ValueError("filter was closed")
             if len(f._hs) != len(self._replicas()):
@@ -227,6 +336,13 @@ class CPIndex:
         if q.ndim != 1 or q.shape[0] != self._dim:
             raise ValueError("query must be 1D and match index dimension")
         kk = max(int(k), 1)
+        if self._p is not None and filter is None and not exact:
+            ids = np.empty(kk, np.int64)
+            dist = np.empty(kk, np.float32)
+            m = C.c_uint64(0)
+            _lib.check(_lib.lib().cph_parts_search(self._p, q.ctypes.data, int(k), ids.ctypes.data, dist.ctypes.data,
+                                                   C.byref(m)))
+            return ids[:m.value].copy(), dist[:m.value].copy()
         if filter is not None or exact:
             ids, dist = self.search_batch(q[None, :], kk, filter=filter, exact=exact)
             m = int(np.count_nonzero(ids[0] >= 0))
@@ -258,6 +374,20 @@ class CPIndex:
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
         fs, fo = self._filter_list(filter, filter_of, n)
+        if self._p is not None:
+            L, pa = _lib.lib(), (q.ctypes.data, n, k)
+            if fs is not None:
+                hs = [f._pf.value for f in fs]
+                _lib.check(L.cph_parts_search_batch_filters(self._p, *pa, (C.c_void_p * len(hs))(*hs) if hs else None, len(hs),
+                                                            fo.ctypes.data, int(bool(exact)), ids.ctypes.data, dist.ctypes.data))
+                return ids, dist
+            fl = None if filter is None else self._filter(filter)     # (held until the call returns: it may have been made here)
+            f = None if fl is None else fl._pf
+            if exact:
+                _lib.check(L.cph_parts_search_batch_exact(self._p, *pa, f, ids.ctypes.data, dist.ctypes.data))
+            else:
+                _lib.check(L.cph_parts_search_batch_filtered(self._p, *pa, f, ids.ctypes.data, dist.ctypes.data))
+            return ids, dist
         if fs is not None:
             if self._m is not None:
                 _lib.check(_lib.lib().cph_multi_search_batch_filters(self._m, q.ctypes.data, n, k, self._filter_handles(fs),
@@ -311,7 +441,10 @@ class CPIndex:
             raise ValueError("queries must be a (n, dim) array")
         n, k = queries.shape[0], int(k)
         rep = 0
-        if self._m is not None:
+        if self._p is not None:
+            if not queries.is_cuda or queries.device.index != self._device:
+                raise ValueError("queries must live on the first device of a partitioned index (the merge runs there)")
+        elif self._m is not None:
             on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
             if not on:
                 raise ValueError("queries must live on one of this index' devices")
@@ -347,6 +480,21 @@ class CPIndex:
                 for t in fresh:
                     t.record_stream(ext)
         fs, fo = self._filter_list(filter, filter_of, n)
+        if self._p is not None:
+            # (waits on the host for every part's search, then enqueues the merge on the stream)
+            L, pa, po = _lib.lib(), (queries.data_ptr(), n, k), (ids.data_ptr(), dist.data_ptr(), C.c_void_p(st))
+            if fs is not None:
+                hs = [f._pf.value for f in fs]
+                _lib.check(L.cph_parts_search_batch_filters_device(self._p, *pa, (C.c_void_p * len(hs))(*hs) if hs else None,
+                                                                   len(hs), fo.ctypes.data, int(bool(exact)), *po))
+                return ids, dist
+            fl = None if filter is None else self._filter(filter)     # (held until the call returns; freeing it waits for the batch)
+            f = None if fl is None else fl._pf
+            if exact:
+                _lib.check(L.cph_parts_search_batch_exact_device(self._p, *pa, f, *po))
+            else:
+                _lib.check(L.cph_parts_search_batch_device_filtered(self._p, *pa, f, *po))
+            return ids, dist
         if fs is not None:
             _lib.check(_lib.lib().cph_search_batch_filters_device(h, queries.data_ptr(), n, k, self._filter_handles(fs, rep),
                                                                   len(fs), fo.ctypes.data, int(bool(exact)), ids.data_ptr(),
@@ -368,6 +516,9 @@ class CPIndex:
 
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):
+        if self._p is not None:
+            raise RuntimeError("a partitioned index has no reference-format file (that format holds one graph and no row "
+                               "map): use save_native")
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_save(self._m, str(path).encode()))
             return
@@ -375,6 +526,9 @@ class CPIndex:
 
     def load(self, path):
         """Reference-format (v2) file: it holds no row map, so the index comes back with result_ids "internal"."""
+        if self._p is not None:
+            raise RuntimeError("a partitioned index cannot load a reference-format file (that format holds one graph and "
+                               "no row map): use load_native")
         try:
             if self._m is not None:
                 _lib.check(_lib.lib().cph_multi_load(self._m, str(path).encode()))
@@ -385,6 +539,7 @@ class CPIndex:
 
     def calib_samples_debug(self, queries, start):
         """Construction hook: the calibration sampler on given queries / start vertices: (rec [ns, 32, 6], cnt, dqp)."""
+        self._no_parts("calib_samples_debug")
         q = _as_f32(queries)
         st = np.ascontiguousarray(start, np.uint32)
         ns = q.shape[0]
@@ -397,12 +552,18 @@ class CPIndex:
 
     def save_native(self, path):
         """GPU-native file (device block layout; not readable by the reference): fast to load."""
+        if self._p is not None:       # one file per part: path.p<i>of<P>
+            _lib.check(_lib.lib().cph_parts_save_native(self._p, str(path).encode()))
+            return
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_save_native(self._m, str(path).encode()))
             return
         _lib.check(_lib.lib().cph_save_native(self._h, str(path).encode()))
 
     def load_native(self, path):
+        if self._p is not None:       # the files of save_native on a handle with as many parts; ValueError leaves it untouched
+            _lib.check(_lib.lib().cph_parts_load_native(self._p, str(path).encode()))
+            return
         try:
             if self._m is not None:
                 _lib.check(_lib.lib().cph_multi_load_native(self._m, str(path).encode()))
@@ -422,6 +583,8 @@ class CPIndex:
         """The index knows the input row of every internal id: it was built here, loaded from a native file saved
         from such an index, or given a map with set_row_map.  A reference-format file (save / load) cannot carry it."""
         f = C.c_int(0)
+        if self._p is not None:
+            return self.is_finalized        # (every part of a partitioned index keeps its row map)
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_has_row_map(self._m, C.byref(f)))
         else:
@@ -431,6 +594,7 @@ class CPIndex:
     def row_map(self):
         """int64[size] copy: row_map()[i] = row, in the array given to build(), of internal id i (a permutation; exact
         also where rows repeat, which internal_to_input_rows is not)."""
+        self._no_parts("row_map")
         out = np.empty(self.size, np.uint32)
         _lib.check(_lib.lib().cph_get_row_map(self._h, 0, out.size, out.ctypes.data))
         return out.astype(np.int64)
@@ -438,6 +602,7 @@ class CPIndex:
     def set_row_map(self, rows):
         """Gives an index that has none (loaded from a reference-format file) its row map: a permutation of 0..size-1,
         else ValueError.  None removes the map and puts result_ids back to "internal"."""
+        self._no_parts("set_row_map")
         if rows is None:
             if self._m is not None:
                 _lib.check(_lib.lib().cph_multi_set_row_map(self._m, None, 0))
@@ -468,6 +633,11 @@ class CPIndex:
     def result_ids(self, space):
         if space not in ("internal", "input"):
             raise ValueError('result_ids must be "internal" or "input"')
+        if self._p is not None:
+            if space != "input":
+                raise ValueError('a partitioned index speaks input rows only: result_ids stays "input" '
+                                 "(every part has its own internal ids: part(i))")
+            return
         code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
         if self._m is not None:
             _lib.check(_lib.lib().cph_multi_set_result_ids(self._m, code))
@@ -487,7 +657,9 @@ class CPIndex:
         v = int(max_allowed)
         if v < 0:
             raise ValueError("exact_threshold must be >= 0")
-        if self._m is not None:
+        if self._p is not None:       # compared with every PART's allowed count
+            _lib.check(_lib.lib().cph_parts_set_exact_threshold(self._p, v))
+        elif self._m is not None:
             _lib.check(_lib.lib().cph_multi_set_exact_threshold(self._m, v))
         else:
             _lib.check(_lib.lib().cph_set_exact_threshold(self._h, v))
@@ -497,7 +669,9 @@ class CPIndex:
     @property
     def size(self):
         n = C.c_uint64(0)
-        if self._m is not None:
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_size(self._p, C.byref(n)))
+        elif self._m is not None:
             _lib.check(_lib.lib().cph_multi_size(self._m, C.byref(n)))
         else:
             _lib.check(_lib.lib().cph_size(self._h, C.byref(n)))
@@ -510,7 +684,9 @@ class CPIndex:
     @property
     def is_finalized(self):
         f = C.c_int(0)
-        if self._m is not None:
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_is_finalized(self._p, C.byref(f)))
+        elif self._m is not None:
             _lib.check(_lib.lib().cph_multi_is_finalized(self._m, C.byref(f)))
         else:
             _lib.check(_lib.lib().cph_is_finalized(self._h, C.byref(f)))
@@ -529,15 +705,18 @@ class CPIndex:
 
     def last_search_stats(self):
         """Work counters of the last batch; a multi-device index' last search_batch: summed over the replicas that
-        took part, kernel_us and capacity their maximum."""
-        out = (C.c_uint64 * 12)()
-        if self._m is not None:
+        took part, kernel_us and capacity their maximum.  A partitioned index: summed over the parts, kernel_us and
+        capacity their maximum, plus merge_us, the device time of the merge kernel."""
+        out = (C.c_uint64 * 13)()
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_last_search_stats(self._p, out))
+        elif self._m is not None:
             _lib.check(_lib.lib().cph_multi_last_search_stats(self._m, out))
         else:
             _lib.check(_lib.lib().cph_last_search_stats(self._h, out))
         keys = ("expansions", "exact_l2", "new_neighbours", "beam_pushes", "stage2_skipped",
                 "rerun_queries", "kernel_us", "expansions_nothing_new", "slots", "capacity",
-                "stage2_reruns", "stage2_undecided")
+                "stage2_reruns", "stage2_undecided") + (("merge_us",) if self._p is not None else ())
         return dict(zip(keys, [int(x) for x in out]))
 
     def synchronize(self):
@@ -548,7 +727,9 @@ class CPIndex:
     def last_query_expansions(self, n):
         """Vertices expanded by each of the n queries of the last batch."""
         out = np.empty(int(n), np.uint32)
-        if self._m is not None:
+        if self._p is not None:       # summed over the parts
+            _lib.check(_lib.lib().cph_parts_last_query_expansions(self._p, out.ctypes.data, int(n)))
+        elif self._m is not None:
             _lib.check(_lib.lib().cph_multi_last_query_expansions(self._m, out.ctypes.data, int(n)))
         else:
             _lib.check(_lib.lib().cph_last_query_expansions(self._h, out.ctypes.data, int(n)))
@@ -556,6 +737,7 @@ class CPIndex:
 
     def order_queries(self, keys):
         """Launch order the search would use for these (non-negative) scheduling keys."""
+        self._no_parts("order_queries")
         keys = np.ascontiguousarray(keys, np.float32)
         out = np.empty(len(keys), np.uint32)
         _lib.check(_lib.lib().cph_order_queries(self._h, keys.ctypes.data, len(keys), out.ctypes.data))
@@ -564,6 +746,7 @@ class CPIndex:
     def get_vectors(self, first=0, count=None):
         """Stored vectors of internal ids [first, first+count) as float32 (count, dim) (internal ids also when
         result_ids is "input")."""
+        self._no_parts("get_vectors")
         if count is None:
             count = self.size - first
         out = np.empty((count, self._dim), np.float32)
@@ -587,6 +770,7 @@ class CPIndex:
 
     # kernel-level hooks (parity tests)
     def encode_query(self, query):
+        self._no_parts("encode_query")
         q = _as_f32(query)
         D = 1
         while D < self._dim:
@@ -597,12 +781,14 @@ class CPIndex:
         return lut, co
 
     def entry_point(self, query):
+        self._no_parts("entry_point")
         q = _as_f32(query)
         ep = C.c_uint32(0)
         _lib.check(_lib.lib().cph_entry_point(self._h, q.ctypes.data, C.byref(ep)))
         return ep.value
 
     def fastscan_block(self, lut, qparams, vertex, dist_qp_sq, worst=3.402823466e+38, nn_full=False):
+        self._no_parts("fastscan_block")
         lut = np.ascontiguousarray(lut, np.uint8)
         qp = np.ascontiguousarray(qparams, np.float32)
         sums = np.zeros(32, np.uint32)
@@ -617,6 +803,7 @@ class CPIndex:
         return sums, msb, est, lower, lower1
 
     def exact_l2(self, query, ids):
+        self._no_parts("exact_l2")
         q = _as_f32(query)
         ids = np.ascontiguousarray(ids, np.uint32)
         out = np.zeros(len(ids), np.float32)

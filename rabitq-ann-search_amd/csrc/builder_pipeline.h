@@ -123,8 +123,12 @@ inline void build_graph(HostIndex& hi, BuiltDevice& dev, const float* vecs, size
         ~Background() { if (th.joinable()) th.join(); }
         void wait() { if (th.joinable()) th.join(); if (err) std::rethrow_exception(err); }
     } upper_job;
-    upper_job.th = std::thread([&ul, &upper_job] {
-        try { ul.build(); } catch (...) { upper_job.err = std::current_exception(); }
+    const size_t share = host_threads_divisor();    // this builder's share of the host threads goes with the job
+    upper_job.th = std::thread([&ul, &upper_job, share] {
+        try {
+            HostThreadsShare inherited(share);
+            ul.build();
+        } catch (...) { upper_job.err = std::current_exception(); }
     });
 
     // ---- exact 32-NN lists on the matrix cores ----------------------------------------------------------

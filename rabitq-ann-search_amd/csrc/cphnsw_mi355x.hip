@@ -36,6 +36,8 @@
 #include "host_parallel.h"
 #include "search_coalescer.h"
 #include "multi_device.h"
+#include "partitioned.h"
+#include "device_merge.h"
 #include "native_file.h"
 #include "builder_pipeline.h"
 
@@ -1453,11 +1455,23 @@ int cph_save_native(cph_index* h, const char* path) {
 
 }  // extern "C"
 
-static void load_native_file(cph_index* h, const char* path) {
-    std::lock_guard<std::mutex> lk(h->mu);
+// A native file read and validated (read_native), not yet anybody's index.
+struct NativeLoaded {
     HostIndex t;
     NativeMapping map;
-    const NativeHeader nh = read_native(path, h->D, h->bits, h->dim, t, map);   // validates everything it maps
+    NativeHeader nh;
+};
+
+static void read_native_for(const cph_index* h, const char* path, NativeLoaded& out) {
+    out.nh = read_native(path, h->D, h->bits, h->dim, out.t, out.map);   // validates everything it maps
+}
+
+// The handle gives up its index for the one in `in` (which is consumed).
+static void install_native(cph_index* h, NativeLoaded& in) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    HostIndex& t = in.t;
+    NativeMapping& map = in.map;
+    const NativeHeader nh = in.nh;
     begin_device_swap(h);
     h->host = std::move(t);
     drop_host_state(h);
@@ -1476,6 +1490,12 @@ static void load_native_file(cph_index* h, const char* path) {
     sync_row_map(h);
     upload_feeders(h);
     h->finalized = true;
+}
+
+static void load_native_file(cph_index* h, const char* path) {
+    NativeLoaded in;
+    read_native_for(h, path, in);               // a file that fails to validate leaves the handle as it was
+    install_native(h, in);
 }
 
 extern "C" {
@@ -2987,6 +3007,639 @@ int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out) {
         if (!m || !out) throw InvalidArg("null argument");
         if (i >= m->reps.size()) throw InvalidArg("replica index out of range");
         *out = m->reps[i];
+    });
+}
+
+}  // extern "C"
+
+// ---- one index split across several devices: parts (cph_parts_*, partitioned.h, device_merge.h) ---------------------
+// Every part is a complete, ordinary cph_index over a contiguous slice of the input rows, on its own device, returning
+// slice-local input rows (CPH_IDS_INPUT).  A search sends the whole batch to every part at once, each on its part's
+// persistent worker thread through the existing cph_search_batch_device* entry points, gathers the P result rows on the
+// home device (devices[0]) and merges them there with merge_parts_kernel, which also adds every part's first row.
+struct cph_parts_filter {
+    std::vector<cph_filter*> f;               // f[p]: the slice of part p, made with cph_filter_create_rows on that part
+    uint64_t n_bits = 0;                      // rows of the whole index
+    ~cph_parts_filter() {
+        for (cph_filter* x : f) (void)cph_filter_destroy(x);
+    }
+};
+
+namespace {
+
+// One part's side of a search: a stream on the part's device and, for a part that does not live on the home device,
+// the queries and its rows there, plus the pinned bounce buffer of a pair of devices without peer access.
+struct PartScratch {
+    hipStream_t st = nullptr;
+    DevBuf<float> d_q, d_dist;
+    DevBuf<int64_t> d_ids;
+    uint8_t* pin = nullptr;
+    size_t pin_bytes = 0;
+    int peer = -1;                            // peer access between this part's device and the home device: -1 not asked yet
+};
+
+}  // namespace
+
+struct cph_parts {
+    std::vector<cph_index*> parts;            // parts[p] on devices[p]; owned (destroy_index)
+    std::vector<int> devices;
+    std::vector<uint64_t> bounds;             // [P + 1]: part p holds input rows [bounds[p], bounds[p + 1]); zeros before build
+    std::unique_ptr<ReplicaPool> pool;        // one worker thread per part
+    std::shared_mutex life;                   // searches hold it shared; build / finalize / load_native / destroy exclusively
+    std::mutex search_mu;                     // one search at a time: the buffers below belong to the handle
+    std::vector<PartScratch> scratch;
+    // on the home device
+    DevBuf<float> h_q, h_part_dist, h_out_dist;
+    DevBuf<int64_t> h_part_ids, h_out_ids, h_lo;
+    hipStream_t h_st = nullptr;
+    hipEvent_t ev_q = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;   // queries ready; around the merge kernel (ev_m1: merged)
+    bool merged = false;                      // ev_m0 / ev_m1 have been recorded
+    uint64_t last_n = 0;                      // size of the last batch
+    ~cph_parts() {
+        pool.reset();                         // joins the workers
+        for (size_t p = 0; p < scratch.size(); ++p) {
+            (void)hipSetDevice(devices[p]);
+            if (scratch[p].st) { (void)hipStreamSynchronize(scratch[p].st); (void)hipStreamDestroy(scratch[p].st); }
+            if (scratch[p].pin) (void)hipHostFree(scratch[p].pin);
+        }
+        if (!devices.empty()) (void)hipSetDevice(devices[0]);
+        if (ev_m1 && merged) (void)hipEventSynchronize(ev_m1);
+        if (h_st) (void)hipStreamDestroy(h_st);
+        for (hipEvent_t e : {ev_q, ev_m0, ev_m1})
+            if (e) (void)hipEventDestroy(e);
+        for (cph_index* h : parts) destroy_index(h);
+    }
+};
+
+namespace {
+
+std::string part_file(const char* path, uint32_t p, uint32_t P) {
+    return std::string(path) + ".p" + std::to_string(p) + "of" + std::to_string(P);
+}
+
+bool parts_finalized(cph_parts* m) {
+    for (cph_index* h : m->parts) {
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->finalized) return false;
+    }
+    return true;
+}
+
+// After a successful finalize / load_native: the bounds are the prefix sums of the part sizes; lo[P] goes to the home device.
+void parts_set_bounds(cph_parts* m) {
+    const uint32_t P = (uint32_t)m->parts.size();
+    std::vector<int64_t> lo(P);
+    m->bounds.assign(P + 1, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+        lo[p] = (int64_t)m->bounds[p];
+        m->bounds[p + 1] = m->bounds[p] + m->parts[p]->host.n;
+    }
+    HIP_CHECK(hipSetDevice(m->devices[0]));
+    if (m->merged) HIP_CHECK(hipEventSynchronize(m->ev_m1));
+    m->h_lo.alloc(P);
+    HIP_CHECK(hipMemcpy(m->h_lo.p, lo.data(), P * sizeof(int64_t), hipMemcpyHostToDevice));
+    m->last_n = 0;
+}
+
+// Peer access between a part's device and the home device, asked once per part (before its first search off the home
+// device, so that every later decision of that call sees the answer).
+void resolve_peer(PartScratch& s, int my_dev, int home_dev) {
+    if (s.peer >= 0) return;
+    int a = 0, b = 0;
+    HIP_CHECK(hipDeviceCanAccessPeer(&a, my_dev, home_dev));
+    HIP_CHECK(hipDeviceCanAccessPeer(&b, home_dev, my_dev));
+    s.peer = (a && b) ? 1 : 0;
+}
+
+// `bytes` from src on src_dev to dst on dst_dev, called on a part's worker whose stream `s.st` lives on one of the two.
+// With peer access: a peer copy enqueued on s.st.  Without: through pinned host memory, blocking, after s.st has been
+// synchronised (partitioned.h: cross_device_copy); a source that another device's stream wrote (the queries) the caller
+// has waited for.  Returns with the worker's device current.
+void copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, PartScratch& s, int my_dev, int home_dev) {
+    if (bytes == 0) return;
+    resolve_peer(s, my_dev, home_dev);
+    CrossDeviceCopy ops;
+    ops.peer_async = [&] { HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, s.st)); };
+    // the blocking copies below run on the null stream, which does not wait for s.st (non-blocking): whatever this
+    // worker enqueued there -- the search that writes the rows -- has to be complete before the source is read
+    ops.sync_source = [&] { HIP_CHECK(hipStreamSynchronize(s.st)); };
+    ops.to_host = [&] {
+        if (s.pin_bytes < bytes) {
+            if (s.pin) HIP_CHECK(hipHostFree(s.pin));
+            s.pin = nullptr;
+            s.pin_bytes = 0;
+            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.pin), bytes, hipHostMallocPortable));
+            s.pin_bytes = bytes;
+        }
+        HIP_CHECK(hipSetDevice(src_dev));
+        HIP_CHECK(hipMemcpy(s.pin, src, bytes, hipMemcpyDeviceToHost));
+    };
+    ops.from_host = [&] {
+        HIP_CHECK(hipSetDevice(dst_dev));
+        HIP_CHECK(hipMemcpy(dst, s.pin, bytes, hipMemcpyHostToDevice));
+        HIP_CHECK(hipSetDevice(my_dev));
+    };
+    cross_device_copy(s.peer == 1, ops);
+}
+
+// One search of a partitioned index, in every form the entry points offer.
+struct PartsCall {
+    const float* q = nullptr;                 // [n][dim]: host memory, or (on_device) on the home device
+    uint64_t n = 0, k = 0;
+    bool on_device = false;                   // queries and results on the home device, the merge enqueued on `stream`
+    hipStream_t stream = nullptr;
+    bool exact = false;
+    const cph_parts_filter* f = nullptr;      // one filter for the batch, or
+    const cph_parts_filter* const* filters = nullptr;   // per-query filters: filters[F], filter_of[n] (host)
+    uint32_t F = 0;
+    const int32_t* filter_of = nullptr;
+    bool per_query = false;
+    int64_t* ids = nullptr;                   // [n][k], where the queries are
+    float* dist = nullptr;
+};
+
+void check_parts_filter(cph_parts* m, const cph_parts_filter* f) {
+    if (!f) throw InvalidArg("null filter");
+    if (f->f.size() != m->parts.size()) throw InvalidArg("filter was made for an index with another number of parts");
+    if (f->n_bits != m->bounds.back())
+        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " rows, the index holds " + std::to_string(m->bounds.back()));
+}
+
+void parts_search(cph_parts* m, const PartsCall& c) {
+    if (!m) throw InvalidArg("null handle");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    std::lock_guard<std::mutex> one(m->search_mu);
+    const uint32_t P = (uint32_t)m->parts.size();
+    const uint64_t n = c.n, k = c.k, dim = m->parts[0]->dim;
+    for (uint32_t p = 0; p < P; ++p) {
+        cph_index* h = m->parts[p];
+        std::lock_guard<std::mutex> g(h->mu);
+        require_finalized(h);
+        if (!h->ids_input)
+            throw InvalidArg("part(" + std::to_string(p) + ") was switched to internal ids: a partitioned index needs its parts in input rows");
+    }
+    if (c.f) check_parts_filter(m, c.f);
+    if (c.per_query) {
+        if (c.F && !c.filters) throw InvalidArg("null argument");
+        for (uint32_t f = 0; f < c.F; ++f) check_parts_filter(m, c.filters[f]);
+        if (n && k && !c.filter_of) throw InvalidArg("null argument");
+        for (uint64_t i = 0; i < n && k; ++i)
+            if (c.filter_of[i] < -1 || c.filter_of[i] >= (int64_t)c.F)
+                throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(c.filter_of[i]) + " is outside [-1, " +
+                                 std::to_string(c.F) + ")");
+    }
+    if (c.exact && k > kExactMaxK)
+        throw InvalidArg("exact search supports k <= " + std::to_string(kExactMaxK) + ", got k = " + std::to_string(k));
+    if (n == 0 || k == 0) return;
+    if (n > 0xFFFFFFFFull || k >= (1ull << 27) || n * k > (1ull << 40)) throw InvalidArg("batch too large");
+    if (!c.q || !c.ids || !c.dist) throw InvalidArg("null argument");
+
+    const int home = m->devices[0];
+    HIP_CHECK(hipSetDevice(home));
+    if (m->merged) HIP_CHECK(hipEventSynchronize(m->ev_m1));     // the last merge has read the part rows
+    if (!m->h_st) {
+        HIP_CHECK(hipStreamCreateWithFlags(&m->h_st, hipStreamNonBlocking));
+        HIP_CHECK(hipEventCreateWithFlags(&m->ev_q, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreate(&m->ev_m0));
+        HIP_CHECK(hipEventCreate(&m->ev_m1));
+    }
+    m->h_part_ids.alloc((size_t)P * n * k);
+    m->h_part_dist.alloc((size_t)P * n * k);
+    const float* q_home = c.q;
+    hipStream_t mst = c.stream;
+    int64_t* out_ids = c.ids;
+    float* out_dist = c.dist;
+    if (c.on_device) {
+        HIP_CHECK(hipEventRecord(m->ev_q, c.stream));
+    } else {
+        m->h_q.alloc(n * dim);
+        m->h_out_ids.alloc(n * k);
+        m->h_out_dist.alloc(n * k);
+        mst = m->h_st;
+        HIP_CHECK(hipMemcpyAsync(m->h_q.p, c.q, n * dim * sizeof(float), hipMemcpyHostToDevice, mst));
+        HIP_CHECK(hipEventRecord(m->ev_q, mst));
+        q_home = m->h_q.p;
+        out_ids = m->h_out_ids.p;
+        out_dist = m->h_out_dist.p;
+    }
+
+    std::string err;
+    const int rc = run_on_parts(*m->pool, P, [&](uint32_t p, std::string& e) -> int {
+        cph_index* h = m->parts[p];
+        PartScratch& s = m->scratch[p];
+        const int dev = m->devices[p];
+        HIP_CHECK(hipSetDevice(dev));
+        if (!s.st) HIP_CHECK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+        // on every way out, an exception included: nothing this part enqueued may still write into the handle's buffers
+        // (or read the caller's queries) once the call has returned
+        struct Drain {
+            hipStream_t st;
+            ~Drain() { (void)hipStreamSynchronize(st); }
+        } drain{s.st};
+        if (dev != home) resolve_peer(s, dev, home);
+        int64_t* h_ids = m->h_part_ids.p + (size_t)p * n * k;
+        float* h_dist = m->h_part_dist.p + (size_t)p * n * k;
+        const float* dq = q_home;
+        int64_t* oi = h_ids;
+        float* od = h_dist;
+        if (dev == home) {
+            HIP_CHECK(hipStreamWaitEvent(s.st, m->ev_q, 0));
+        } else {
+            s.d_q.alloc(n * dim);
+            s.d_ids.alloc(n * k);
+            s.d_dist.alloc(n * k);
+            if (c.on_device) {
+                HIP_CHECK(hipEventSynchronize(m->ev_q));
+                copy_between(s.d_q.p, dev, q_home, home, n * dim * sizeof(float), s, dev, home);
+            } else {
+                HIP_CHECK(hipMemcpyAsync(s.d_q.p, c.q, n * dim * sizeof(float), hipMemcpyHostToDevice, s.st));
+            }
+            dq = s.d_q.p;
+            oi = s.d_ids.p;
+            od = s.d_dist.p;
+        }
+        int r;
+        if (c.per_query) {
+            std::vector<const cph_filter*> fr(c.F);
+            for (uint32_t f = 0; f < c.F; ++f) fr[f] = c.filters[f]->f[p];
+            r = cph_search_batch_filters_device(h, dq, n, k, fr.data(), c.F, c.filter_of, c.exact ? 1 : 0, oi, od, s.st);
+        } else if (c.exact) {
+            r = cph_search_batch_exact_device(h, dq, n, k, c.f ? c.f->f[p] : nullptr, oi, od, s.st);
+        } else {
+            r = cph_search_batch_device_filtered(h, dq, n, k, c.f ? c.f->f[p] : nullptr, oi, od, s.st);
+        }
+        if (r != CPH_OK) {
+            e = g_err;                            // (thread-local: this worker's message)
+            return r;
+        }
+        if (dev != home) {
+            copy_between(h_ids, home, oi, dev, n * k * sizeof(int64_t), s, dev, home);
+            copy_between(h_dist, home, od, dev, n * k * sizeof(float), s, dev, home);
+        }
+        HIP_CHECK(hipStreamSynchronize(s.st));
+        return CPH_OK;
+    }, err);
+    if (rc != CPH_OK) raise_status(rc, err);
+
+    // every part's rows are on the home device: the merge, then (host form) one copy of [n][k] out
+    HIP_CHECK(hipSetDevice(home));
+    HIP_CHECK(hipEventRecord(m->ev_m0, mst));
+    merge_parts(m->h_part_ids.p, m->h_part_dist.p, P, (uint32_t)n, (uint32_t)k, m->h_lo.p, out_ids, out_dist, mst);
+    HIP_CHECK(hipEventRecord(m->ev_m1, mst));
+    m->merged = true;
+    m->last_n = n;
+    if (!c.on_device) {
+        HIP_CHECK(hipMemcpyAsync(c.ids, out_ids, n * k * sizeof(int64_t), hipMemcpyDeviceToHost, mst));
+        HIP_CHECK(hipMemcpyAsync(c.dist, out_dist, n * k * sizeof(float), hipMemcpyDeviceToHost, mst));
+        HIP_CHECK(hipStreamSynchronize(mst));
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_parts_create(uint64_t dim, uint64_t bits, const int* devices, uint32_t n_dev, cph_parts** out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("out must not be null");
+        *out = nullptr;
+        if (!devices) throw InvalidArg("devices must not be null");
+        if (n_dev < 1 || n_dev > kMaxReplicas) throw InvalidArg("n_dev must be 1.." + std::to_string(kMaxReplicas));
+        std::unique_ptr<cph_parts> m(new cph_parts());
+        for (uint32_t i = 0; i < n_dev; ++i) {
+            cph_index* h = nullptr;
+            check_rc(cph_create(dim, bits, devices[i], &h));
+            h->borrowed = true;
+            m->parts.push_back(h);
+            m->devices.push_back(devices[i]);
+        }
+        m->bounds.assign(n_dev + 1, 0);
+        m->scratch.resize(n_dev);
+        cph_parts* raw = m.get();
+        m->pool.reset(new ReplicaPool(n_dev, [raw](uint32_t p) { (void)hipSetDevice(raw->devices[p]); }));
+        *out = m.release();
+    });
+}
+
+int cph_parts_destroy(cph_parts* m) {
+    return guarded([&] {
+        if (!m) return;
+        { std::unique_lock<std::shared_mutex> lk(m->life); }   // searches in flight finish first
+        delete m;
+    });
+}
+
+int cph_parts_build(cph_parts* m, const float* vectors, uint64_t n) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        const uint32_t P = (uint32_t)m->parts.size();
+        if (n < kMinPartRows * P)
+            throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
+                             std::to_string(n) + " rows for " + std::to_string(P) + " parts");
+        if (!vectors) throw InvalidArg("null vectors");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        const std::vector<uint64_t> b = all_part_bounds(n, P);
+        for (uint32_t p = 0; p < P; ++p) build_pending(m->parts[p], vectors + b[p] * m->parts[p]->dim, b[p + 1] - b[p]);
+        m->bounds = b;
+    });
+}
+
+int cph_parts_finalize(cph_parts* m) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        const uint32_t P = (uint32_t)m->parts.size();
+        std::string err;
+        const int rc = run_on_parts(*m->pool, P, [&](uint32_t p, std::string&) -> int {
+            HostThreadsShare share(P);            // P builders at once: each takes 1 / P of the host threads
+            finalize_build(m->parts[p]);
+            set_result_ids(m->parts[p], CPH_IDS_INPUT);
+            return CPH_OK;
+        }, err);
+        if (rc != CPH_OK) raise_status(rc, err);
+        parts_set_bounds(m);
+    });
+}
+
+int cph_parts_size(cph_parts* m, uint64_t* n) {
+    return guarded([&] {
+        if (!m || !n) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        *n = 0;
+        for (cph_index* h : m->parts) {
+            uint64_t x = 0;
+            check_rc(cph_size(h, &x));
+            *n += x;
+        }
+    });
+}
+
+int cph_parts_is_finalized(cph_parts* m, int* flag) {
+    return guarded([&] {
+        if (!m || !flag) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        *flag = parts_finalized(m) ? 1 : 0;
+    });
+}
+
+int cph_parts_num_parts(cph_parts* m, uint32_t* n) {
+    return guarded([&] {
+        if (!m || !n) throw InvalidArg("null argument");
+        *n = (uint32_t)m->parts.size();
+    });
+}
+
+int cph_parts_part(cph_parts* m, uint32_t i, cph_index** out) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        if (i >= m->parts.size()) throw InvalidArg("part index out of range");
+        *out = m->parts[i];
+    });
+}
+
+int cph_parts_bounds(cph_parts* m, uint64_t* out) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::copy(m->bounds.begin(), m->bounds.end(), out);
+    });
+}
+
+int cph_parts_save_native(cph_parts* m, const char* path) {
+    return guarded([&] {
+        if (!m || !path) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Index must be finalized before saving.");
+        const uint32_t P = (uint32_t)m->parts.size();
+        for (uint32_t p = 0; p < P; ++p) check_rc(cph_save_native(m->parts[p], part_file(path, p, P).c_str()));
+    });
+}
+
+int cph_parts_load_native(cph_parts* m, const char* path) {
+    return guarded([&] {
+        if (!m || !path) throw InvalidArg("null argument");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        const uint32_t P = (uint32_t)m->parts.size();
+        // every file is read and validated before any part gives up its index: a failure leaves the handle untouched
+        std::vector<NativeLoaded> loaded(P);
+        for (uint32_t p = 0; p < P; ++p) {
+            const std::string file = part_file(path, p, P);
+            try {
+                read_native_for(m->parts[p], file.c_str(), loaded[p]);
+                if (loaded[p].t.rows.size() != loaded[p].t.n || loaded[p].t.n == 0)
+                    throw std::runtime_error("the part holds no row map (a partitioned index speaks input rows only)");
+            } catch (const std::bad_alloc&) {
+                throw;
+            } catch (const std::exception& e) {
+                throw InvalidArg("part " + std::to_string(p) + " of " + std::to_string(P) + " (" + file + "): " + e.what() +
+                                 " -- a partitioned index loads the files of save_native on a handle with the same number of parts");
+            }
+        }
+        // the validated files are installed as they were read (no second read).  What can still fail here is the device
+        // (allocation, copies): then the parts already replaced stay replaced, every part is marked unfinalized and the
+        // handle is not searchable until the next successful load_native or finalize
+        try {
+            for (uint32_t p = 0; p < P; ++p) {
+                install_native(m->parts[p], loaded[p]);
+                set_result_ids(m->parts[p], CPH_IDS_INPUT);
+            }
+            parts_set_bounds(m);
+        } catch (...) {
+            for (cph_index* h : m->parts) {
+                std::lock_guard<std::mutex> g(h->mu);
+                h->finalized = false;
+            }
+            throw;
+        }
+    });
+}
+
+int cph_parts_set_exact_threshold(cph_parts* m, uint64_t max_allowed) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->parts) check_rc(cph_set_exact_threshold(h, max_allowed));
+    });
+}
+
+int cph_parts_filter_create_rows(cph_parts* m, const uint32_t* words, uint64_t n_bits, cph_parts_filter** out) {
+    return guarded([&] {
+        if (!m || !out || (!words && n_bits != 0)) throw InvalidArg("null argument");
+        *out = nullptr;
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        if (n_bits != m->bounds.back())
+            throw InvalidArg("filter covers " + std::to_string(n_bits) + " rows, the index holds " + std::to_string(m->bounds.back()));
+        std::unique_ptr<cph_parts_filter> f(new cph_parts_filter());
+        f->n_bits = n_bits;
+        for (size_t p = 0; p < m->parts.size(); ++p) {
+            const std::vector<uint32_t> w = cut_mask(words, m->bounds[p], m->bounds[p + 1]);
+            cph_filter* x = nullptr;
+            check_rc(cph_filter_create_rows(m->parts[p], w.data(), m->bounds[p + 1] - m->bounds[p], &x));
+            f->f.push_back(x);
+        }
+        *out = f.release();
+    });
+}
+
+int cph_parts_filter_destroy(cph_parts_filter* f) {
+    return guarded([&] { delete f; });
+}
+
+int cph_parts_search_batch(cph_parts* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist) {
+    return cph_parts_search_batch_filtered(m, queries, n, k, nullptr, ids, dist);
+}
+
+int cph_parts_search_batch_filtered(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                    int64_t* ids, float* dist) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = queries; c.n = n; c.k = k; c.f = f; c.ids = ids; c.dist = dist;
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search_batch_exact(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                 int64_t* ids, float* dist) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = queries; c.n = n; c.k = k; c.f = f; c.exact = true; c.ids = ids; c.dist = dist;
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search_batch_filters(cph_parts* m, const float* queries, uint64_t n, uint64_t k,
+                                   const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
+                                   int64_t* ids, float* dist) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = queries; c.n = n; c.k = k; c.per_query = true; c.filters = filters; c.F = n_filters; c.filter_of = filter_of;
+        c.exact = exact != 0; c.ids = ids; c.dist = dist;
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search_batch_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, int64_t* d_ids, float* d_dist,
+                                  void* stream) {
+    return cph_parts_search_batch_device_filtered(m, d_queries, n, k, nullptr, d_ids, d_dist, stream);
+}
+
+int cph_parts_search_batch_device_filtered(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                           int64_t* d_ids, float* d_dist, void* stream) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = d_queries; c.n = n; c.k = k; c.f = f; c.ids = d_ids; c.dist = d_dist;
+        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search_batch_exact_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
+                                        int64_t* d_ids, float* d_dist, void* stream) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = d_queries; c.n = n; c.k = k; c.f = f; c.exact = true; c.ids = d_ids; c.dist = d_dist;
+        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search_batch_filters_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k,
+                                          const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                                          int exact, int64_t* d_ids, float* d_dist, void* stream) {
+    return guarded([&] {
+        PartsCall c;
+        c.q = d_queries; c.n = n; c.k = k; c.per_query = true; c.filters = filters; c.F = n_filters; c.filter_of = filter_of;
+        c.exact = exact != 0; c.ids = d_ids; c.dist = d_dist;
+        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
+        parts_search(m, c);
+    });
+}
+
+int cph_parts_search(cph_parts* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count) {
+    return guarded([&] {
+        if (!m || !query || !ids || !dist || !count) throw InvalidArg("null argument");
+        const uint64_t kk = std::max<uint64_t>(k, 1);
+        std::vector<int64_t> ri(kk);
+        std::vector<float> rd(kk);
+        PartsCall c;
+        c.q = query; c.n = 1; c.k = kk; c.ids = ri.data(); c.dist = rd.data();
+        parts_search(m, c);
+        uint64_t cnt = 0;
+        while (cnt < kk && ri[cnt] >= 0) ++cnt;       // the merge keeps padding last
+        std::copy(ri.begin(), ri.begin() + cnt, ids);
+        std::copy(rd.begin(), rd.begin() + cnt, dist);
+        *count = cnt;
+    });
+}
+
+int cph_parts_last_search_stats(cph_parts* m, uint64_t out[13]) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::lock_guard<std::mutex> one(m->search_mu);
+        uint64_t acc[13] = {};
+        if (m->last_n) {
+            for (cph_index* h : m->parts) {
+                uint64_t w[12];
+                check_rc(cph_last_search_stats(h, w));
+                for (int i = 0; i < 12; ++i)
+                    acc[i] = (i == 6 || i == 9) ? std::max(acc[i], w[i]) : acc[i] + w[i];   // kernel_us, capacity: the max
+            }
+            HIP_CHECK(hipSetDevice(m->devices[0]));
+            HIP_CHECK(hipEventSynchronize(m->ev_m1));
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, m->ev_m0, m->ev_m1));
+            acc[12] = (uint64_t)(ms * 1000.0);
+        }
+        std::memcpy(out, acc, sizeof(acc));
+    });
+}
+
+int cph_parts_last_query_expansions(cph_parts* m, uint32_t* out, uint64_t n) {
+    return guarded([&] {
+        if (!m || !out) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::lock_guard<std::mutex> one(m->search_mu);
+        if (m->last_n == 0 || n != m->last_n) throw InvalidArg("n must equal the size of the last batch");
+        std::vector<uint32_t> w(n);
+        std::fill(out, out + n, 0u);
+        for (cph_index* h : m->parts) {
+            check_rc(cph_last_query_expansions(h, w.data(), n));
+            for (uint64_t i = 0; i < n; ++i) out[i] += w[i];
+        }
+    });
+}
+
+int cph_merge_rows_hook(int device, const int64_t* ids, const float* dist, uint32_t P, uint64_t n, uint64_t k, const int64_t* lo,
+                        int64_t* out_ids, float* out_dist) {
+    return guarded([&] {
+        if (!ids || !dist || !lo || !out_ids || !out_dist) throw InvalidArg("null argument");
+        if (P < 1 || P > kMaxReplicas) throw InvalidArg("P must be 1.." + std::to_string(kMaxReplicas));
+        if (n < 1 || n > 0xFFFFFFFFull || k < 1 || k >= (1ull << 27) || n * k > (1ull << 32)) throw InvalidArg("merge: sizes out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t rows = (size_t)n * k;
+        DevBuf<int64_t> d_ids(P * rows), d_out_ids(rows), d_lo(P);
+        DevBuf<float> d_dist(P * rows), d_out_dist(rows);
+        HIP_CHECK(hipMemcpy(d_ids.p, ids, P * rows * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dist.p, dist, P * rows * sizeof(float), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_lo.p, lo, P * sizeof(int64_t), hipMemcpyHostToDevice));
+        // (the caller's output arrives first: a slot the kernel left out would keep what the caller put there)
+        HIP_CHECK(hipMemcpy(d_out_ids.p, out_ids, rows * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_out_dist.p, out_dist, rows * sizeof(float), hipMemcpyHostToDevice));
+        merge_parts(d_ids.p, d_dist.p, P, (uint32_t)n, (uint32_t)k, d_lo.p, d_out_ids.p, d_out_dist.p, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_ids, d_out_ids.p, rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_dist, d_out_dist.p, rows * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_part_bounds(uint64_t n, uint32_t P, uint64_t* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        if (P < 1 || P > kMaxReplicas) throw InvalidArg("P must be 1.." + std::to_string(kMaxReplicas));
+        const std::vector<uint64_t> b = all_part_bounds(n, P);
+        std::copy(b.begin(), b.end(), out);
     });
 }
 

@@ -16,10 +16,31 @@
 
 namespace cph {
 
-inline size_t host_threads() {
+inline size_t host_threads_budget() {
     if (const char* e = getenv("CPH_BUILD_THREADS")) return (size_t)std::max(1, atoi(e));
     const unsigned hw = std::min(64u, std::thread::hardware_concurrency());
     return hw ? hw : 4;
+}
+
+// The calling thread's share of the budget: several builders running at once (the parts of a partitioned index, one per
+// worker thread) divide it between them so that together they do not oversubscribe the host.  1: the whole budget.
+// The share is per thread, and a thread that a sharer starts has to INHERIT it: run_threads hands it to its workers, and
+// a bare std::thread takes it over with HostThreadsShare(inherited), inherited = host_threads_divisor() read on the
+// starting thread (builder_pipeline.h: the upper-layer job).
+inline size_t& host_threads_divisor() {
+    thread_local size_t div = 1;
+    return div;
+}
+struct HostThreadsShare {
+    size_t before;
+    explicit HostThreadsShare(size_t sharers) : before(host_threads_divisor()) { host_threads_divisor() = std::max<size_t>(sharers, 1); }
+    HostThreadsShare(const HostThreadsShare&) = delete;
+    HostThreadsShare& operator=(const HostThreadsShare&) = delete;
+    ~HostThreadsShare() { host_threads_divisor() = before; }
+};
+
+inline size_t host_threads() {
+    return std::max<size_t>(1, host_threads_budget() / host_threads_divisor());
 }
 
 // Runs body(t) on `nt` threads (t = 0..nt-1; the caller's thread is one of them) and rethrows the first exception.
@@ -27,8 +48,10 @@ inline void run_threads(size_t nt, const std::function<void(size_t)>& body) {
     if (nt <= 1) { body(0); return; }
     std::exception_ptr first;
     std::mutex mu;
+    const size_t share = host_threads_divisor();      // the workers inherit the caller's share of the host threads
     auto guarded = [&](size_t t) {
         try {
+            HostThreadsShare inherited(share);
             body(t);
         } catch (...) {
             std::lock_guard<std::mutex> lk(mu);

@@ -232,6 +232,46 @@ int cph_set_row_map(cph_index* h, const uint32_t* rows, uint64_t n);
 enum { CPH_IDS_INTERNAL = 0, CPH_IDS_INPUT = 1 };
 int cph_set_result_ids(cph_index* h, int space);
 
+/* ---- removed rows: tombstones and compact() --------------------------------------------- */
+/* A finalized handle carries a set R of removed INTERNAL ids, empty by default.  A removed row is a tombstone: it stays
+ * in the graph and is still walked, but can never enter a result.  With R not empty EVERY search entry point returns the
+ * bytes (ids, distances, padding) the same call returns on the same index with R empty under the filter F & ~R, F being
+ * the caller's filter, or every id: cph_search_batch[_device] and their _filtered, _exact and _filters forms, the exact
+ * threshold (compared with the count of F & ~R), an empty F & ~R (padded rows, no launch), filter_of == -1 (~R); the
+ * counters of cph_last_search_stats other than kernel_us, and cph_last_query_expansions, are those of that filtered
+ * call.  cph_search on such a handle runs as a batch of one through the filtered path (not coalesced).  The search
+ * kernels are not involved: the price of the first removed row is that unfiltered batches leave the probe-first
+ * instantiation.  With R empty nothing changes: launches, results, statistics and the bytes of
+ * cph_save_native are those of a handle that never heard of cph_remove.  cph_size is unchanged by a remove (ids keep
+ * their meaning, a filter's n_bits is still the size); cph_live_count = size - |R|.
+ *
+ * cph_remove   ids[m]: host array, internal ids (space = CPH_IDS_INTERNAL) or input rows (CPH_IDS_INPUT; needs a row
+ *              map).  An id outside [0, size) is CPH_INVALID_ARGUMENT and changes nothing; duplicates and ids removed
+ *              before are fine.  *newly (may be NULL) = ids newly removed.  Waits for everything enqueued on the handle
+ *              (like cph_set_row_map), then updates the resident bitmap with the kernels of csrc/device_tombstone.h.
+ * filters      a cph_filter made before a remove observes it at its next use: it caches F & ~R with its count and its
+ *              exact-scan id list per state of R (the first use after a remove computes it on the handle's own stream
+ *              and waits for the count), so one filter may serve two handles of one size with different R.  A cached
+ *              bitmap is freed only after the device has drained: a filter keeps four, and the first use under a fifth
+ *              state of R waits for the whole device, also in the _device entry points that otherwise only enqueue.
+ * R ends       with cph_build, cph_load (v2) and cph_compact; cph_load_native takes the file's R; cph_set_row_map and
+ *              cph_set_result_ids do not touch it.
+ * files        cph_save_native writes R, when it is not empty, as native format 3 (format 1 or 2 plus a `removed`
+ *              section, csrc/native_file.h), which a library that knows formats 1 and 2 only REFUSES instead of loading
+ *              the file with the rows back.  cph_save (the reference's v2 format, which cannot carry R) fails with
+ *              CPH_RUNTIME_ERROR on a handle with removed rows: compact first, or save natively.
+ * cph_get_removed  words[(size + 31) / 32]: R as a bitmap over internal ids.
+ * cph_compact  rebuilds the index from the live rows with the builder of cph_build + cph_finalize: the live vectors in
+ *              input-row order (internal-id order without a row map).  old_to_new[old size]: the new input row of every
+ *              old id, in the handle's result id space (cph_set_result_ids), -1 for removed ids.  Afterwards size ==
+ *              live_count, R is empty, the handle has a fresh row map and keeps CPH_IDS_INPUT if it had it.  With R
+ *              empty it still rebuilds.  Fewer live rows than the builder takes is the builder's own error and leaves
+ *              the handle as it was. */
+int cph_remove(cph_index* h, const int64_t* ids, uint64_t m, int space, uint64_t* newly);
+int cph_live_count(cph_index* h, uint64_t* n);
+int cph_get_removed(cph_index* h, uint32_t* words);
+int cph_compact(cph_index* h, int64_t* old_to_new);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);
@@ -333,6 +373,13 @@ int cph_multi_set_result_ids(cph_multi* m, int space);
 int cph_multi_set_min_shard(cph_multi* m, uint64_t q);
 int cph_multi_last_search_stats(cph_multi* m, uint64_t out[12]);
 int cph_multi_last_query_expansions(cph_multi* m, uint32_t* out, uint64_t n);
+/* cph_remove on every replica before the call returns (it waits for the searches in flight); live_count / get_removed from
+ * replica 0; compact on replica 0, then copied to the others like finalize.  cph_remove / cph_compact on a borrowed replica
+ * handle fail with CPH_INVALID_ARGUMENT. */
+int cph_multi_remove(cph_multi* m, const int64_t* ids, uint64_t cnt, int space, uint64_t* newly);
+int cph_multi_live_count(cph_multi* m, uint64_t* n);
+int cph_multi_get_removed(cph_multi* m, uint32_t* words);
+int cph_multi_compact(cph_multi* m, int64_t* old_to_new);
 int cph_multi_num_replicas(cph_multi* m, uint32_t* n);
 int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out);
 
@@ -412,6 +459,15 @@ int cph_parts_filter_create_rows(cph_parts* m, const uint32_t* words, uint64_t n
 int cph_parts_filter_destroy(cph_parts_filter* f);
 int cph_parts_last_search_stats(cph_parts* m, uint64_t out[13]);
 int cph_parts_last_query_expansions(cph_parts* m, uint32_t* out, uint64_t n);
+/* Removed rows of a partitioned index: ids are GLOBAL input rows, cut at the part bounds; every part keeps its own R (a
+ * part whose rows are all removed returns padding without a launch).  get_removed: words[(size + 31) / 32] over global
+ * input rows.  compact: a full cph_parts_build + cph_parts_finalize of the live rows in row order, so the parts are cut
+ * again by cph_host_part_bounds; old_to_new[old size] in global rows; fewer live rows than cph_parts_build takes is its
+ * error and leaves the handle as it was. */
+int cph_parts_remove(cph_parts* m, const int64_t* ids, uint64_t cnt, uint64_t* newly);
+int cph_parts_live_count(cph_parts* m, uint64_t* n);
+int cph_parts_get_removed(cph_parts* m, uint32_t* words);
+int cph_parts_compact(cph_parts* m, int64_t* old_to_new);
 int cph_parts_num_parts(cph_parts* m, uint32_t* n);
 int cph_parts_part(cph_parts* m, uint32_t i, cph_index** out);
 int cph_parts_bounds(cph_parts* m, uint64_t* out);
@@ -489,6 +545,12 @@ int cph_host_encode_query(uint64_t dim, const float* query, uint8_t* lut, float*
  * internal ids (both bitmaps (n + 31) / 32 words; bits of the last output word behind n are clear).  Every rows[i] must
  * be < n. */
 int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_t n, uint32_t* words_out);
+
+/* Host statement of the effective filter of a handle with removed rows (csrc/device_tombstone.h: live_filter_kernel):
+ * words_out = words_f & ~words_removed over n ids (words_f NULL: every id), all bitmaps (n + 31) / 32 words; bits of the
+ * last word behind n are ignored in both inputs and clear in the output; *count_out (may be NULL) = ids left. */
+int cph_host_live_filter(const uint32_t* words_f, const uint32_t* words_removed, uint64_t n, uint32_t* words_out,
+                         uint64_t* count_out);
 
 /* Host statement of the compaction the exact search runs on a filter: out_ids = the set bits of words (bit id & 31 of
  * word id >> 5, bits behind n_bits ignored) in ascending order, *out_count = how many.  out_ids holds popcount entries. */

@@ -67,6 +67,19 @@ SYMBOLS = {
     "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "cph_set_row_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "cph_set_result_ids": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "cph_live_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_compact": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_host_live_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_multi_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "cph_multi_live_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_multi_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_multi_compact": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_parts_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cph_parts_live_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_parts_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_parts_compact": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cph_synchronize": (C.c_int, [C.c_void_p]),
     "cph_set_batch_sets": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,

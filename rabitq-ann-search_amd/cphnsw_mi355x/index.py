@@ -514,6 +514,84 @@ class CPIndex:
                                                                dist.data_ptr(), C.c_void_p(st)))
         return ids, dist
 
+    # -- removed rows (not in the reference) ---------------------------------------------------
+    def _id_space(self, ids):
+        space = self._result_ids if ids is None else ids
+        if space not in ("internal", "input"):
+            raise ValueError('ids must be "internal" or "input"')
+        if self._p is not None and space != "input":
+            raise ValueError('a partitioned index speaks input rows only (ids="input")')
+        return space
+
+    def remove(self, rows, ids=None):
+        """Removes rows from the finalized index; returns how many were newly removed.  `rows`: an integer array of ids,
+        in the space `ids` ("internal" or "input"; default: result_ids, as for make_filter).  An id outside [0, size)
+        raises ValueError and changes nothing; duplicates and ids removed before are fine.  A removed row is a tombstone:
+        it stays in the graph, `size` and every id keep their meaning, and every search from now on returns what the
+        same call would return under the filter "caller's filter AND not removed" -- also filters made before the
+        call.  Waits for the batches in flight.  The first removed row takes unfiltered batches off the probe-first
+        kernel (they run the filtered one); compact() rebuilds the index without the removed rows."""
+        space = self._id_space(ids)
+        a = np.asarray(rows)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("remove takes an integer array of ids")
+        r = np.ascontiguousarray(a.ravel(), np.int64)
+        newly = C.c_uint64(0)
+        ptr = r.ctypes.data if r.size else None
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_remove(self._p, ptr, r.size, C.byref(newly)))
+            return newly.value
+        code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
+        if self._m is not None:
+            _lib.check(_lib.lib().cph_multi_remove(self._m, ptr, r.size, code, C.byref(newly)))
+        else:
+            _lib.check(_lib.lib().cph_remove(self._h, ptr, r.size, code, C.byref(newly)))
+        return newly.value
+
+    @property
+    def live_count(self):
+        """Rows that can still be returned: size minus the removed rows."""
+        n = C.c_uint64(0)
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_live_count(self._p, C.byref(n)))
+        elif self._m is not None:
+            _lib.check(_lib.lib().cph_multi_live_count(self._m, C.byref(n)))
+        else:
+            _lib.check(_lib.lib().cph_live_count(self._h, C.byref(n)))
+        return n.value
+
+    def removed_mask(self, ids=None):
+        """bool[size]: True where the id (in the space `ids`; default: result_ids) has been removed."""
+        space = self._id_space(ids)
+        n = self.size
+        w = np.zeros((n + 31) // 32, np.uint32)
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_get_removed(self._p, w.ctypes.data))
+        elif self._m is not None:
+            _lib.check(_lib.lib().cph_multi_get_removed(self._m, w.ctypes.data))
+        else:
+            _lib.check(_lib.lib().cph_get_removed(self._h, w.ctypes.data))
+        mask = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+        if space == "input" and self._p is None:
+            by_row = np.zeros(n, bool)
+            by_row[self.row_map()] = mask
+            return by_row
+        return mask
+
+    def compact(self):
+        """Rebuilds the index from the rows that are left (build + finalize of the live vectors in input-row order;
+        internal-id order if the index has no row map).  Returns int64[old size]: the new input row of every old id, in
+        the space remove() defaults to (result_ids), -1 for removed ids.  Afterwards size == live_count, nothing is
+        removed, the index has a fresh row map and result_ids is kept.  A partitioned index is cut into parts again."""
+        out = np.empty(self.size, np.int64)
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_compact(self._p, out.ctypes.data))
+        elif self._m is not None:
+            _lib.check(_lib.lib().cph_multi_compact(self._m, out.ctypes.data))
+        else:
+            _lib.check(_lib.lib().cph_compact(self._h, out.ctypes.data))
+        return out
+
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):
         if self._p is not None:

@@ -31,6 +31,7 @@
 #include "device_heap_test.h"
 #include "device_relayout.h"
 #include "device_rows.h"
+#include "device_tombstone.h"
 #include "device_exact.h"
 #include "host_index.h"
 #include "host_parallel.h"
@@ -163,8 +164,22 @@ struct cph_filter {
     mutable std::mutex ids_mu;
     mutable DevBuf<uint32_t> ids, ids_scratch;
     mutable hipEvent_t ids_ev = nullptr;
+    // F & ~R for the handles with removed rows that used this filter (effective_filter): complete filters of their own
+    // (bitmap, count, id list), keyed by the epoch of the handle's R -- a value no other state of any handle's R ever
+    // has, so a remove makes the old entry unreachable and two handles with different R each find their own.  At most
+    // kEffCached entries; one is only freed after the device has drained (EffDeleter): a batch in flight may read it.
+    mutable std::mutex eff_mu;
+    mutable std::vector<std::pair<uint64_t, std::shared_ptr<cph_filter>>> eff;
     ~cph_filter() { if (ids_ev) (void)hipEventDestroy(ids_ev); }
 };
+constexpr size_t kEffCached = 4;
+struct EffDeleter {
+    void operator()(cph_filter* f) const {
+        if (hipSetDevice(f->device) == hipSuccess) (void)hipDeviceSynchronize();
+        delete f;
+    }
+};
+static std::atomic<uint64_t> g_removed_epoch{0};
 
 struct cph_index {
     uint64_t dim = 0;
@@ -197,6 +212,14 @@ struct cph_index {
     bool ids_input = false;            // cph_set_result_ids: searches return input rows (needs has_rows)
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
+    // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
+    // host.n_removed (what save_native writes).  rm_epoch names this state of R (g_removed_epoch); live = ~R as a filter,
+    // what an unfiltered call of a handle with tombstones runs under.  tombstones: n_removed != 0, readable without the mutex.
+    DevBuf<uint32_t> d_removed;
+    DevBuf<unsigned long long> d_rm_count;
+    uint64_t rm_epoch = 0;
+    std::shared_ptr<cph_filter> live;
+    std::atomic<bool> tombstones{false};
     // per-query feeders on the device: rotation signs + upper layers (CSR)
     DevBuf<float> d_signs;
     DevBuf<uint32_t> d_upper;          // all layers' nodes | offsets | nbrs, concatenated
@@ -289,6 +312,64 @@ void sync_row_map(cph_index* h) {
         h->d_rows.release();
         h->ids_input = false;
     }
+}
+
+hipStream_t own_stream(cph_index* h);
+
+// F & ~R (allow null: ~R) of this handle as a filter of its own, made on the handle's stream and complete on return: the
+// count is needed on the host, for the routing.
+std::shared_ptr<cph_filter> make_live_filter(cph_index* h, const uint32_t* d_allow) {
+    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    std::shared_ptr<cph_filter> e(new cph_filter(), EffDeleter());
+    e->device = h->device;
+    e->n_bits = n;
+    e->words.alloc(std::max<uint64_t>(nw, 1));
+    h->d_rm_count.alloc(1);
+    hipStream_t st = own_stream(h);
+    live_filter(d_allow, h->d_removed.p, n, e->words.p, h->d_rm_count.p, st);
+    unsigned long long c = 0;
+    HIP_CHECK(hipMemcpyAsync(&c, h->d_rm_count.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    e->popcount = c;
+    return e;
+}
+
+// After host.removed changed (a remove, a load, a build): the resident copy of R, a new epoch, the ~R filter.  The
+// caller holds the mutex and has waited for the batches in flight.
+void sync_removed(cph_index* h) {
+    HostIndex& hi = h->host;
+    h->rm_epoch = ++g_removed_epoch;            // (first: whatever fails below, no filter's cache of the old state is found again)
+    h->live.reset();
+    if (hi.n_removed == 0) {
+        std::vector<uint32_t>().swap(hi.removed);
+        h->d_removed.release();
+        h->tombstones.store(false);
+        return;
+    }
+    h->tombstones.store(true);                  // (before the device work: a failure must not bring the rows back;
+                                                //  effective_filter makes `live` when it is missing)
+    const uint64_t nw = (hi.n + 31) / 32;
+    h->d_removed.alloc(nw);
+    HIP_CHECK(hipMemcpy(h->d_removed.p, hi.removed.data(), nw * 4, hipMemcpyHostToDevice));
+    h->live = make_live_filter(h, nullptr);
+}
+
+// The filter a search of this handle runs under: the caller's (null: none) on a handle without removed rows, else
+// F & ~R -- for f == null the handle's ~R.  The caller holds the handle mutex and keeps the returned pointer until its
+// batch is enqueued.
+std::shared_ptr<const cph_filter> effective_filter(cph_index* h, const cph_filter* f) {
+    if (h->host.n_removed == 0) return std::shared_ptr<const cph_filter>(std::shared_ptr<const cph_filter>(), f);   // (aliasing: owns nothing)
+    if (!f) {
+        if (!h->live) h->live = make_live_filter(h, nullptr);       // (only after a failed sync_removed)
+        return h->live;
+    }
+    std::lock_guard<std::mutex> lk(f->eff_mu);
+    for (auto& e : f->eff)
+        if (e.first == h->rm_epoch) return e.second;
+    if (f->eff.size() >= kEffCached) f->eff.erase(f->eff.begin());
+    std::shared_ptr<cph_filter> e = make_live_filter(h, f->words.p);
+    f->eff.emplace_back(h->rm_epoch, e);
+    return e;
 }
 
 void require_finalized(cph_index* h) {
@@ -965,8 +1046,10 @@ void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t 
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!batch_has_work(h, f, queries, n, k, ids, dist)) return;
-    exact = takes_exact(h, f, k, exact);
     h->use_device();
+    const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
+    f = eff.get();
+    exact = takes_exact(h, f, k, exact);
     hipStream_t st = own_stream(h);
     BatchSet& s = next_set(h, st);
     if (exact) {
@@ -1017,8 +1100,10 @@ void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint6
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!batch_has_work(h, f, d_queries, n, k, d_ids, d_dist)) return;
-    exact = takes_exact(h, f, k, exact);
     h->use_device();
+    const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
+    f = eff.get();
+    exact = takes_exact(h, f, k, exact);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchSet& s = next_set(h, st);
     if (exact) {
@@ -1049,6 +1134,37 @@ FilterGroups group_filters(const cph_index* h, const cph_filter* const* filters,
     g.seg.resize(F + 2);
     filter_groups(filter_of, n, g.pop.data(), F, k, exact, h->exact_threshold, g.route.data(), g.perm.data(), g.seg.data());
     return g;
+}
+
+// The per-query arguments of a handle with removed rows: every filter becomes F & ~R, the handle's ~R is appended and the
+// queries with -1 are sent to it -- the call a caller without cph_remove would have had to make.  (Without removed rows:
+// the arguments as they came.)
+struct LiveFilters {
+    std::vector<std::shared_ptr<const cph_filter>> hold;
+    std::vector<const cph_filter*> list;
+    std::vector<int32_t> of;
+    const cph_filter* const* filters = nullptr;
+    uint32_t F = 0;
+    const int32_t* filter_of = nullptr;
+};
+
+void live_filters(cph_index* h, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, uint64_t n, LiveFilters& out) {
+    out.filters = filters; out.F = F; out.filter_of = filter_of;
+    if (h->host.n_removed == 0) return;
+    for (uint64_t i = 0; i < n; ++i)               // (before -1 is renumbered: F itself must stay an invalid value)
+        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
+            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
+                             std::to_string(F) + ")");
+    h->use_device();
+    for (uint32_t f = 0; f < F; ++f) {
+        out.hold.push_back(effective_filter(h, filters[f]));
+        out.list.push_back(out.hold.back().get());
+    }
+    out.list.push_back(h->live.get());
+    out.of.assign(filter_of, filter_of + n);
+    for (int32_t& x : out.of)
+        if (x < 0) x = (int32_t)F;
+    out.filters = out.list.data(); out.F = F + 1; out.filter_of = out.of.data();
 }
 
 // What every entry with per-query filters checks, under the handle mutex, before it touches the device (batch_has_work).
@@ -1258,6 +1374,9 @@ void search_batch_filters_host(cph_index* h, const float* queries, uint64_t n, u
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!filters_batch_has_work(h, filters, F, filter_of, queries, n, k, ids, dist)) return;
+    LiveFilters lf;
+    live_filters(h, filters, F, filter_of, n, lf);
+    filters = lf.filters; F = lf.F; filter_of = lf.filter_of;
     const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
     h->use_device();
     hipStream_t st = own_stream(h);
@@ -1282,6 +1401,9 @@ void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t 
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (!filters_batch_has_work(h, filters, F, filter_of, d_queries, n, k, d_ids, d_dist)) return;
+    LiveFilters lf;
+    live_filters(h, filters, F, filter_of, n, lf);
+    filters = lf.filters; F = lf.F; filter_of = lf.filter_of;
     const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
     h->use_device();
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1305,7 +1427,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 103; }
+int cph_version(void) { return 104; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1406,6 +1528,7 @@ static void load_v2(cph_index* h, const char* path) {
     drop_host_state(h);
     upload_arrays(h);
     sync_row_map(h);                            // (a v2 file carries no row map)
+    sync_removed(h);                            // (... and no removed rows)
     upload_feeders(h);
     h->finalized = true;
 }
@@ -1426,6 +1549,9 @@ int cph_save(cph_index* h, const char* path) {
         refuse_host_less(h, "cph_save");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized before saving.");
+        if (h->host.n_removed != 0)
+            throw std::runtime_error("The reference format cannot carry removed rows (" + std::to_string(h->host.n_removed) +
+                                     " here) and a file without them would bring them back: compact() the index first, or use save_native.");
         materialize_search_data(h);
         h->host.save(path);
     });
@@ -1488,6 +1614,7 @@ static void install_native(cph_index* h, NativeLoaded& in) {
     HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
     sync_row_map(h);
+    sync_removed(h);                            // the file's removed rows, or none
     upload_feeders(h);
     h->finalized = true;
 }
@@ -1520,10 +1647,21 @@ int cph_is_finalized(cph_index* h, int* flag) {
 
 }  // extern "C"
 
+// What build() and finalize() refuse about the number of rows -- one statement, also asked by compact() BEFORE the
+// handle gives up its index.
+static void require_buildable(uint64_t n) {
+    if (n == 0) throw InvalidArg("build requires at least one vector.");
+}
+static void require_finalizable(uint64_t n) {
+    if (n == 0) throw std::runtime_error("Cannot finalize an empty index.");
+    if (n < 50) throw std::runtime_error("Calibration requires at least 50 nodes.");
+    if (n >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
+}
+
 static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     std::lock_guard<std::mutex> lk(h->mu);
     // api/hnsw_index.hpp:93-120: build() replaces any previous state
-    if (n == 0) throw InvalidArg("build requires at least one vector.");
+    require_buildable(n);
     if (!vectors) throw InvalidArg("null vectors");
     h->use_device();
     quiesce(h);
@@ -1532,6 +1670,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     h->finalized = false;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     sync_row_map(h);
+    sync_removed(h);
     for (auto& s : h->sets) release_scratch(s);
     h->pending.assign(vectors, vectors + n * h->dim);
     h->pending_n = n;
@@ -1544,8 +1683,7 @@ static void finalize_build(cph_index* h) {
     const uint64_t n = h->needs_build ? h->pending_n : h->host.n;
     if (n == 0) throw std::runtime_error("Cannot finalize an empty index.");
     if (!h->needs_build) throw std::runtime_error("Finalize called without a pending build.");
-    if (n < 50) throw std::runtime_error("Calibration requires at least 50 nodes.");
-    if (n >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
+    require_finalizable(n);
     h->use_device();
     const bool verbose = getenv("CPH_BUILD_VERBOSE") != nullptr;
     quiesce(h);
@@ -2149,7 +2287,10 @@ static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const s
     DoneFlags done;
     done.flags = reinterpret_cast<uint32_t*>(ls.pin_dev);
     done.seq = ls.seq;
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, io.ids(ls.pin_dev), io.dist(ls.pin_dev), ls.stream, io.counts(ls.pin_dev), done);   // ... the search writes the results back
+    // (a handle with removed rows sends its single queries through the batch path, cph_search; a launch that was gathered
+    // while the first row was being removed still runs under ~R)
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, io.ids(ls.pin_dev), io.dist(ls.pin_dev), ls.stream, io.counts(ls.pin_dev), done,
+                   h->live.get());   // ... the search writes the results back
     CPH_TR(0, 1); CPH_TR(1, n); CPH_TR(2, t1 - t0); CPH_TR(3, now_ns() - t1);
 }
 
@@ -2196,6 +2337,18 @@ int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float
         if (!query || !ids || !dist || !m) throw InvalidArg("null argument");
         const uint64_t kk = std::max<uint64_t>(k, 1);  // api/hnsw_index.hpp:187
         if (kk > 0xFFFFFFFFull) throw InvalidArg("k too large");
+        if (h->tombstones.load(std::memory_order_acquire)) {
+            // removed rows: a batch of one through the filtered path under ~R (what a search with filter= does)
+            std::vector<int64_t> ri(kk);
+            std::vector<float> rd(kk);
+            search_batch_host(h, query, 1, kk, nullptr, ri.data(), rd.data());
+            uint64_t cnt = 0;
+            for (uint64_t i = 0; i < kk; ++i) cnt += ri[i] >= 0 ? 1 : 0;
+            for (uint64_t i = 0, o = 0; i < kk; ++i)
+                if (ri[i] >= 0) { ids[o] = ri[i]; dist[o] = rd[i]; ++o; }
+            *m = cnt;
+            return;
+        }
         r.query = query; r.k = kk; r.ids = ids; r.dist = dist; r.m = m;
         // concurrent callers are gathered into shared launches (search_coalescer.h); the status codes it records are cph_status
         h->coal.submit(r,
@@ -2677,6 +2830,8 @@ void replicate(cph_index* src, cph_index* dst) {
     HIP_CHECK(hipDeviceSynchronize());          // whatever wrote the source arrays has landed
     begin_device_swap(dst);
     dst->host = host_scalars(src->host);
+    dst->host.removed = src->host.removed;      // every replica answers without the removed rows
+    dst->host.n_removed = src->host.n_removed;
     drop_host_state(dst);
     dst->L = src->L;
     dst->sc = src->sc;
@@ -2700,6 +2855,7 @@ void replicate(cph_index* src, cph_index* dst) {
     copy(dst->d_upper, src->d_upper);
     copy(dst->d_row_of, src->d_row_of);
     HIP_CHECK(hipStreamSynchronize(st));
+    sync_removed(dst);
     auto rebase = [](const uint32_t* p, const DevBuf<uint32_t>& from, const DevBuf<uint32_t>& to) -> const uint32_t* {
         return p ? to.p + (p - from.p) : nullptr;
     };
@@ -2879,6 +3035,7 @@ int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n) {
             h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
             h->host = HostIndex();
             sync_row_map(h);
+            sync_removed(h);
         }
     });
 }
@@ -3640,6 +3797,270 @@ int cph_host_part_bounds(uint64_t n, uint32_t P, uint64_t* out) {
         if (P < 1 || P > kMaxReplicas) throw InvalidArg("P must be 1.." + std::to_string(kMaxReplicas));
         const std::vector<uint64_t> b = all_part_bounds(n, P);
         std::copy(b.begin(), b.end(), out);
+    });
+}
+
+}  // extern "C"
+
+// ---- removed rows: tombstones and compact() (cph_remove, cph_compact; device_tombstone.h) ---------------------------------
+// R lives on the handle as a resident bitmap over internal ids (host copy: host.removed).  The search kernels are not
+// told: every search entry substitutes the effective filter F & ~R (effective_filter) and runs the filtered, exact or
+// per-query path as it is.
+namespace {
+
+// cph_remove on one handle: ids in internal ids or (space == CPH_IDS_INPUT) input rows, validated before anything
+// changes; returns the number of ids newly removed.
+uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+    if (m && !ids) throw InvalidArg("null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (space == CPH_IDS_INPUT && !h->has_rows)
+        throw InvalidArg("the index has no row map (it was loaded from a v2 file): removing input rows needs cph_set_row_map");
+    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    std::vector<uint32_t> list(m);
+    for (uint64_t i = 0; i < m; ++i) {
+        if (ids[i] < 0 || (uint64_t)ids[i] >= n)
+            throw InvalidArg("remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n) + ")");
+        list[i] = (uint32_t)ids[i];
+    }
+    h->use_device();
+    quiesce(h);                                  // a batch in flight may be reading R, or a filter made from it
+    if (m == 0) return 0;
+    hipStream_t st = own_stream(h);
+    DevBuf<uint32_t> d_list(m), d_mark(nw), d_conv;
+    HIP_CHECK(hipMemcpyAsync(d_list.p, list.data(), m * 4, hipMemcpyHostToDevice, st));
+    mark_ids(d_list.p, m, n, d_mark.p, st);
+    const uint32_t* d_fresh = d_mark.p;
+    if (space == CPH_IDS_INPUT) {                // a row bitmap: through the row map, like a filter in input rows
+        d_conv.alloc(nw);
+        rows_filter(d_mark.p, h->d_rows.p, n, d_conv.p, st);
+        d_fresh = d_conv.p;
+    }
+    // the new R is folded in a scratch copy: until everything below has succeeded, the handle's R (resident bitmap, host
+    // copy, count, epoch, cached filters) is the old one, all of it
+    DevBuf<uint32_t> d_next(nw);
+    if (h->host.n_removed == 0) HIP_CHECK(hipMemsetAsync(d_next.p, 0, nw * 4, st));
+    else HIP_CHECK(hipMemcpyAsync(d_next.p, h->d_removed.p, nw * 4, hipMemcpyDeviceToDevice, st));
+    h->d_rm_count.alloc(1);
+    fold_removed(d_next.p, d_fresh, n, h->d_rm_count.p, st);
+    unsigned long long newly = 0;
+    std::vector<uint32_t> next(nw);
+    HIP_CHECK(hipMemcpyAsync(&newly, h->d_rm_count.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(next.data(), d_next.p, nw * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (newly == 0) return 0;
+    h->host.removed.swap(next);                  // (nothing below this line and above sync_removed throws)
+    h->host.n_removed += newly;
+    sync_removed(h);                             // uploads the host copy: the resident bitmap is made from what save_native writes
+    return newly;
+}
+
+// The live vectors of a finalized handle in input-row order (internal-id order without a row map), appended to `vecs`
+// (dim floats each); map[i] (the caller's, `n` entries from map_first on) = first_new + rank of the live row, -1 for a
+// removed one, indexed by input row (by_row) or by internal id.  Returns the number of live rows.
+uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new) {
+    const HostIndex& hi = h->host;
+    const uint64_t n = hi.n;
+    const bool rows = h->has_rows && hi.rows.size() == n;
+    if (by_row && !rows) throw InvalidArg("the index has no row map");
+    std::vector<uint32_t> id_of_row(n);
+    for (uint64_t i = 0; i < n; ++i) id_of_row[rows ? hi.rows[i] : i] = (uint32_t)i;
+    uint64_t live = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        const uint32_t id = id_of_row[r];
+        const bool gone = hi.n_removed != 0 && ((hi.removed[id >> 5] >> (id & 31)) & 1u);
+        map[by_row ? r : id] = gone ? -1 : first_new + (int64_t)live;
+        if (gone) continue;
+        vecs.insert(vecs.end(), hi.vec(id), hi.vec(id) + hi.dim);
+        ++live;
+    }
+    return live;
+}
+
+// cph_compact on one handle (a lifecycle call, like build + finalize).
+void compact_index(cph_index* h, int64_t* old_to_new) {
+    if (!old_to_new) throw InvalidArg("null argument");
+    refuse_host_less(h, "cph_compact");
+    std::vector<float> vecs;
+    uint64_t live = 0;
+    bool was_input = false;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        // the builder's own refusals, before the handle gives anything up
+        live = h->host.n - h->host.n_removed;
+        require_buildable(live);
+        require_finalizable(live);
+        was_input = h->ids_input;
+        vecs.reserve(live * h->dim);
+        std::vector<int64_t> map(h->host.n);
+        gather_live(h, vecs, map.data(), was_input, 0);
+        std::copy(map.begin(), map.end(), old_to_new);
+    }
+    build_pending(h, vecs.data(), live);
+    std::vector<float>().swap(vecs);
+    finalize_build(h);
+    if (was_input) set_result_ids(h, CPH_IDS_INPUT);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_remove(cph_index* h, const int64_t* ids, uint64_t m, int space, uint64_t* newly) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_remove");
+        const uint64_t c = remove_ids(h, ids, m, space);
+        if (newly) *newly = c;
+    });
+}
+
+int cph_live_count(cph_index* h, uint64_t* n) {
+    return guarded([&] {
+        if (!h || !n) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *n = h->needs_build ? h->pending_n : h->host.n - h->host.n_removed;
+    });
+}
+
+int cph_get_removed(cph_index* h, uint32_t* words) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        const uint64_t nw = (h->host.n + 31) / 32;
+        if (nw && !words) throw InvalidArg("null argument");
+        if (h->host.n_removed == 0) std::fill(words, words + nw, 0u);
+        else std::copy(h->host.removed.begin(), h->host.removed.end(), words);
+    });
+}
+
+int cph_compact(cph_index* h, int64_t* old_to_new) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_compact");
+        compact_index(h, old_to_new);
+    });
+}
+
+int cph_host_live_filter(const uint32_t* words_f, const uint32_t* words_removed, uint64_t n, uint32_t* words_out, uint64_t* count_out) {
+    return guarded([&] {
+        if (n != 0 && (!words_removed || !words_out)) throw InvalidArg("null argument");
+        if (n > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+        const uint64_t c = live_filter_host(words_f, words_removed, n, words_out);
+        if (count_out) *count_out = c;
+    });
+}
+
+int cph_multi_remove(cph_multi* m, const int64_t* ids, uint64_t cnt, int space, uint64_t* newly) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first; the next one sees R on every replica
+        uint64_t c = 0;
+        for (size_t i = 0; i < m->reps.size(); ++i) {        // (replica 0 validates: a bad id changes no replica)
+            const uint64_t ci = remove_ids(m->reps[i], ids, cnt, space);
+            if (i == 0) c = ci;
+        }
+        if (newly) *newly = c;
+    });
+}
+
+int cph_multi_live_count(cph_multi* m, uint64_t* n) {
+    return multi_shared(m, [&] { return cph_live_count(m->reps[0], n); });
+}
+
+int cph_multi_get_removed(cph_multi* m, uint32_t* words) {
+    return multi_shared(m, [&] { return cph_get_removed(m->reps[0], words); });
+}
+
+int cph_multi_compact(cph_multi* m, int64_t* old_to_new) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        multi_lifecycle(m, [&](cph_index* r0) { compact_index(r0, old_to_new); });
+    });
+}
+
+int cph_parts_remove(cph_parts* m, const int64_t* ids, uint64_t cnt, uint64_t* newly) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        if (cnt && !ids) throw InvalidArg("null argument");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        const uint32_t P = (uint32_t)m->parts.size();
+        const uint64_t total = m->bounds.back();
+        std::vector<std::vector<int64_t>> cut(P);            // global input rows, cut at the part bounds
+        for (uint64_t i = 0; i < cnt; ++i) {
+            if (ids[i] < 0 || (uint64_t)ids[i] >= total)
+                throw InvalidArg("remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(total) + ")");
+            const uint32_t p = (uint32_t)(std::upper_bound(m->bounds.begin(), m->bounds.end(), (uint64_t)ids[i]) - m->bounds.begin()) - 1;
+            cut[p].push_back(ids[i] - (int64_t)m->bounds[p]);
+        }
+        uint64_t c = 0;
+        for (uint32_t p = 0; p < P; ++p) c += remove_ids(m->parts[p], cut[p].data(), cut[p].size(), CPH_IDS_INPUT);
+        if (newly) *newly = c;
+    });
+}
+
+int cph_parts_live_count(cph_parts* m, uint64_t* n) {
+    return guarded([&] {
+        if (!m || !n) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        *n = 0;
+        for (cph_index* h : m->parts) {
+            uint64_t x = 0;
+            check_rc(cph_live_count(h, &x));
+            *n += x;
+        }
+    });
+}
+
+int cph_parts_get_removed(cph_parts* m, uint32_t* words) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        const uint64_t total = m->bounds.back();
+        if (total && !words) throw InvalidArg("null argument");
+        std::fill(words, words + (total + 31) / 32, 0u);
+        for (size_t p = 0; p < m->parts.size(); ++p) {
+            cph_index* h = m->parts[p];
+            std::lock_guard<std::mutex> g(h->mu);
+            const HostIndex& hi = h->host;
+            if (hi.n_removed == 0) continue;
+            for (uint64_t i = 0; i < hi.n; ++i)
+                if ((hi.removed[i >> 5] >> (i & 31)) & 1u) {
+                    const uint64_t r = m->bounds[p] + hi.rows[i];
+                    words[r >> 5] |= 1u << (r & 31);
+                }
+        }
+    });
+}
+
+int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
+    return guarded([&] {
+        if (!m || !old_to_new) throw InvalidArg("null argument");
+        std::vector<float> vecs;
+        uint64_t live = 0;
+        {
+            std::unique_lock<std::shared_mutex> lk(m->life);
+            if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+            const uint32_t P = (uint32_t)m->parts.size();
+            std::vector<int64_t> map(m->bounds.back());
+            for (uint32_t p = 0; p < P; ++p) {
+                cph_index* h = m->parts[p];
+                std::lock_guard<std::mutex> g(h->mu);
+                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live);
+            }
+            if (live < kMinPartRows * P)      // cph_parts_build's own refusal, before any part gives up its index
+                throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
+                                 std::to_string(live) + " rows for " + std::to_string(P) + " parts");
+            std::copy(map.begin(), map.end(), old_to_new);
+        }
+        check_rc(cph_parts_build(m, vecs.data(), live));      // the live rows, cut again by cph_host_part_bounds
+        std::vector<float>().swap(vecs);
+        check_rc(cph_parts_finalize(m));
     });
 }
 

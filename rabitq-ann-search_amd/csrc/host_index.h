@@ -178,6 +178,20 @@ inline void rows_filter_host(const uint32_t* in, const uint32_t* rows, size_t n,
     }
 }
 
+// The host statement of the effective filter of a handle with removed rows (device_tombstone.h: live_filter_kernel;
+// cph_host_live_filter): out = allow & ~removed (allow null: every id) over n ids, the bits of the last word behind n
+// clear whatever the inputs hold there; returns the number of ids left.  All bitmaps are (n + 31) / 32 words.
+inline uint64_t live_filter_host(const uint32_t* allow, const uint32_t* removed, size_t n, uint32_t* out) {
+    uint64_t c = 0;
+    for (size_t w = 0, nw = (n + 31) / 32; w < nw; ++w) {
+        uint32_t x = (allow ? allow[w] : 0xFFFFFFFFu) & ~removed[w];
+        if (w == nw - 1 && (n & 31)) x &= (1u << (n & 31)) - 1u;
+        out[w] = x;
+        c += (uint64_t)__builtin_popcount(x);
+    }
+    return c;
+}
+
 struct HostIndex {
     size_t D = 0, bw = 0, dim = 0, n = 0;
     int32_t max_level = 0;
@@ -197,6 +211,10 @@ struct HostIndex {
     // The row map: rows[i] = row of the array given to build() that internal id i holds (a permutation of 0..n-1).
     // Empty = no map: the index came from a v2 file, which cannot carry one (save() drops it).
     std::vector<uint32_t> rows;
+    // The removed rows (cph_remove): bit i & 31 of word i >> 5 = internal id i is a tombstone; (n + 31) / 32 words, or
+    // empty = none (n_removed = 0).  Only a native file carries them; save() refuses an index that has some.
+    std::vector<uint32_t> removed;
+    uint64_t n_removed = 0;
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

@@ -5,8 +5,10 @@
 // (0.99 s).  The native file keeps what the GPU reads in the form the GPU reads it:
 //
 //   header | calibration, profile, centroid, levels, norms, upper layers      (the v2 file's small fields)
-//          [ NativeRowsExt ]  format 2 only: the last bytes of the small section
+//          [ NativeRemovedExt ]  format 3 only: behind the upper layers, in front of the row-map record
+//          [ NativeRowsExt ]  format 2 (and a format 3 made from it): the last bytes of the small section
 //   rows   [n] u32           4096-aligned, format 2 only: the row map (HostIndex::rows), input row of every internal id
+//   removed [(n + 31) / 32] u32  4096-aligned, format 3 only: the removed rows (HostIndex::removed), one bit per internal id
 //   own    [n][own_stride]   the vertices' own codes + {nop, ip_qo} (only needed to write a v2 file again)
 //   raw    [n][D] f32        4096-aligned
 //   blocks [n][stride]       4096-aligned, device block layout (cph_core.h)
@@ -19,7 +21,16 @@
 // field and ignores what follows the upper layers, and lets sections start later than the previous one ends.  So
 // NativeHeader::version stays 1 -- "what a reader must understand to search the file" -- the record sits at the END
 // of the small section (inside small_bytes), and the `rows` section sits in front of `own`, inside file_bytes.  This
-// reader returns the file's format (1 or 2) in the `version` field of the header it hands back.
+// reader returns the file's format (1, 2 or 3) in the `version` field of the header it hands back.
+//
+// Format 3 = format 1 or 2 plus the `removed` section (cph_remove) and a NativeRemovedExt record; an index without
+// removed rows is written as format 1 or 2, byte for byte as before.  Format 3 is NOT an extension an older reader may
+// load: it would search the file with the removed rows back in every result.  So the record is laid out to be refused:
+// the format-2 reader accepts behind the upper layers nothing, or exactly sizeof(NativeRowsExt) = 24 bytes that start
+// with the rows magic, and calls anything else damage ("unknown data behind the upper layers").  NativeRemovedExt is 32
+// bytes, starts with its own magic and comes FIRST, so what such a reader finds there is 32 or 56 bytes, never 24 --
+// it refuses the file whether or not a row map follows.  (NativeHeader::version stays 1: the sections it names are
+// unchanged, and one way of refusing is enough.)  The section sits behind `rows`, in front of `own`.
 //
 // load = mmap + two host-to-device copies straight out of the mapping; the vectors stay mapped for
 // cph_get_vectors / save.  A v2 file can always be regenerated from a native one (cph_save after
@@ -47,6 +58,8 @@ constexpr uint64_t kNativeMagic = 0x3535334948504300ULL;   // "\0CPHI355"
 constexpr uint32_t kNativeVersion = 1;        // NativeHeader::version of every file; the format of one without a row map
 constexpr uint32_t kNativeVersionRows = 2;    // NativeRowsExt::version: the format of a file with one
 constexpr uint64_t kNativeRowsMagic = 0x53574F5249485043ULL;   // "CPHIROWS"
+constexpr uint32_t kNativeVersionRemoved = 3; // NativeRemovedExt::version: the format of a file with removed rows
+constexpr uint64_t kNativeRemovedMagic = 0x44564D5249485043ULL;   // "CPHIRMVD"
 
 struct NativeHeader {
     uint64_t magic;
@@ -69,6 +82,15 @@ struct NativeRowsExt {        // format 2: the last sizeof(NativeRowsExt) bytes 
     uint32_t reserved;        // 0
     uint64_t rows_off;        // n x u32, between the small section and `own`
 };
+
+struct NativeRemovedExt {     // format 3: behind the upper layers, in front of NativeRowsExt (if any)
+    uint64_t magic;           // kNativeRemovedMagic
+    uint32_t version;         // kNativeVersionRemoved
+    uint32_t reserved;        // 0
+    uint64_t removed_off;     // (n + 31) / 32 x u32, between the small section (and `rows`) and `own`
+    uint64_t removed_count;   // set bits of the section: 1..n, no bit at or behind n
+};
+static_assert(sizeof(NativeRemovedExt) != sizeof(NativeRowsExt) && sizeof(NativeRemovedExt) == 32, "a format-2 reader must refuse the record");
 
 struct NativeMapping {
     void* base = nullptr;
@@ -113,9 +135,29 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
     }
     const bool with_rows = !hi.rows.empty();
     if (with_rows && hi.rows.size() != hi.n) throw std::runtime_error("row map does not match the index size");
-    uint64_t rows_off = 0;
+    const bool with_removed = hi.n_removed != 0;
+    const uint64_t rm_words = (hi.n + 31) / 32;
+    if (with_removed) {
+        uint64_t pc = 0;
+        if (hi.removed.size() != rm_words) throw std::runtime_error("removed-row bitmap does not match the index size");
+        for (uint32_t x : hi.removed) pc += (uint64_t)__builtin_popcount(x);
+        if (pc != hi.n_removed || ((hi.n & 31) && (hi.removed.back() >> (hi.n & 31))))
+            throw std::runtime_error("removed-row bitmap does not match its count");
+    }
+    uint64_t rows_off = 0, removed_off = 0;
+    const uint64_t records = (with_rows ? sizeof(NativeRowsExt) : 0) + (with_removed ? sizeof(NativeRemovedExt) : 0);
+    uint64_t sections_end = sizeof(NativeHeader) + small.size() + records;
     if (with_rows) {
-        rows_off = align_up(sizeof(NativeHeader) + small.size() + sizeof(NativeRowsExt), 4096);
+        rows_off = align_up(sections_end, 4096);
+        sections_end = rows_off + hi.n * 4;
+    }
+    if (with_removed) {
+        removed_off = align_up(sections_end, 4096);
+        sections_end = removed_off + rm_words * 4;
+        const NativeRemovedExt ext{kNativeRemovedMagic, kNativeVersionRemoved, 0u, removed_off, hi.n_removed};
+        put(&ext, sizeof(ext));
+    }
+    if (with_rows) {
         const NativeRowsExt ext{kNativeRowsMagic, kNativeVersionRows, 0u, rows_off};
         put(&ext, sizeof(ext));
     }
@@ -125,7 +167,7 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
     h.upper_tau = hi.upper_tau; h.upper_alpha = hi.upper_alpha; h.mL = hi.mL; h.seed = hi.seed;
     h.has_dup = hi.has_dup_neighbors ? 1u : 0u; h.n_layers = (uint32_t)hi.upper.size();
     h.small_bytes = small.size();
-    h.own_off = with_rows ? align_up(rows_off + hi.n * 4, 4096) : align_up(sizeof(NativeHeader) + small.size(), 4096);
+    h.own_off = align_up(sections_end, 4096);
     h.raw_off = align_up(h.own_off + hi.n * own_stride, 4096);
     h.blocks_off = align_up(h.raw_off + hi.n * hi.D * 4, 4096);
     h.file_bytes = h.blocks_off + hi.n * (uint64_t)stride;
@@ -142,6 +184,10 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
         pad_to(rows_off);
         wr(hi.rows.data(), hi.n * 4);
     }
+    if (with_removed) {
+        pad_to(removed_off);
+        wr(hi.removed.data(), rm_words * 4);
+    }
     pad_to(h.own_off);
     wr(own, hi.n * own_stride);
     pad_to(h.raw_off);
@@ -152,7 +198,8 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
 }
 
 // Maps the file and fills everything of `hi` except raw / search_data (raw_view points into the mapping); hi.rows is
-// the file's row map (format 2) or empty (format 1); the returned header's `version` is that format.
+// the file's row map (format 2) or empty (format 1), hi.removed / hi.n_removed the file's removed rows (format 3) or
+// none; the returned header's `version` is that format.
 inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t expect_bw, size_t expect_dim, HostIndex& hi,
                                 NativeMapping& map) {
     const int fd = ::open(path.c_str(), O_RDONLY);
@@ -227,9 +274,24 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
                 if (x >= t.n) throw std::runtime_error("Corrupt index: upper-layer neighbour out of range");
         }
     }
-    // What follows the upper layers: nothing (format 1) or the row-map record (format 2); anything else is damage.
-    bool with_rows = false;
+    // What follows the upper layers: nothing (format 1), the row-map record (format 2), or the removed-rows record with
+    // or without the row-map record behind it (format 3); anything else is damage.
+    bool with_rows = false, with_removed = false;
     NativeRowsExt ext{};
+    NativeRemovedExt rext{};
+    const uint64_t rm_words = (h.n + 31) / 32;
+    if ((size_t)(end - p) == sizeof(rext) || (size_t)(end - p) == sizeof(rext) + sizeof(ext)) {
+        typedef unsigned __int128 u128;
+        get(&rext, sizeof(rext));
+        if (rext.magic != kNativeRemovedMagic) throw std::runtime_error("Corrupt index: unknown data behind the upper layers");
+        if (rext.version != kNativeVersionRemoved)
+            throw std::runtime_error("Unsupported native index file version: " + std::to_string(rext.version));
+        if (rext.reserved != 0 || rext.removed_off % 4 != 0 || (u128)rext.removed_off < (u128)sizeof(NativeHeader) + h.small_bytes ||
+            (u128)rext.removed_off + (u128)rm_words * 4 > h.own_off)
+            throw std::runtime_error("Corrupt index: removed-rows section out of bounds");
+        if (rext.removed_count == 0 || rext.removed_count > h.n) throw std::runtime_error("Corrupt index: removed-rows count out of range");
+        with_removed = true;
+    }
     if (p != end) {
         typedef unsigned __int128 u128;
         if ((size_t)(end - p) != sizeof(ext)) throw std::runtime_error("Corrupt index: unknown data behind the upper layers");
@@ -240,9 +302,13 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
         if (ext.rows_off % 4 != 0 || (u128)ext.rows_off < (u128)sizeof(NativeHeader) + h.small_bytes ||
             (u128)ext.rows_off + (u128)h.n * 4 > h.own_off)
             throw std::runtime_error("Corrupt index: row map section out of bounds");
+        // (sections in order, no overlap: the row map lies in front of the removed rows)
+        if (with_removed && (u128)ext.rows_off + (u128)h.n * 4 > rext.removed_off)
+            throw std::runtime_error("Corrupt index: row map section out of bounds");
         with_rows = true;
         h.version = kNativeVersionRows;      // the format, for the caller (the file's field stays 1, see the top)
     }
+    if (with_removed) h.version = kNativeVersionRemoved;
     // The device blocks are handed to the GPU as they are: a neighbour id the search kernel would chase must be a
     // vertex (the v2 loader's validate() makes the same promise), unused slots must carry the invalid marker the
     // kernels rely on instead of `count`, and the repeated-id flag is recomputed rather than believed.
@@ -276,6 +342,15 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
         t.rows.resize(t.n);
         std::memcpy(t.rows.data(), static_cast<const uint8_t*>(base) + ext.rows_off, t.n * 4);
         if (!is_row_permutation(t.rows.data(), t.n)) throw std::runtime_error("Corrupt index: the row map is not a permutation");
+    }
+    if (with_removed) {
+        t.removed.resize(rm_words);
+        std::memcpy(t.removed.data(), static_cast<const uint8_t*>(base) + rext.removed_off, rm_words * 4);
+        uint64_t pc = 0;
+        for (uint32_t x : t.removed) pc += (uint64_t)__builtin_popcount(x);
+        if ((h.n & 31) && (t.removed.back() >> (h.n & 31))) throw std::runtime_error("Corrupt index: removed row behind the last id");
+        if (pc != rext.removed_count) throw std::runtime_error("Corrupt index: removed-rows count does not match the bitmap");
+        t.n_removed = pc;
     }
     t.raw_view = reinterpret_cast<const float*>(static_cast<const uint8_t*>(base) + h.raw_off);
     t.rot.init(t.D, t.seed);

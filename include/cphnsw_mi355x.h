@@ -187,6 +187,53 @@ int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t
  * every call does what it did before. */
 int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
 
+/* ---- range search ----------------------------------------------------------------------- */
+/* Every allowed id closer than a radius, in CSR form: lims[n + 1] (lims[0] = 0), query i owns ids / dist
+ * [lims[i], lims[i + 1]).  An id is a hit iff dist < radius[i], compared as float32 against the squared-L2 values the
+ * searches return (strict: FAISS's rule for L2; distances are >= +0, so a radius <= 0 or NaN selects nothing and +inf
+ * every candidate).  Two steps, because the caller allocates the output:
+ *
+ * cph_range_search_begin   queries: [n][dim] in host memory, or (queries_on_device != 0) on the handle's device, then
+ *     `stream` is the caller's stream (the host form runs on the handle's own stream and ignores it).  radius_host[n] is
+ *     host memory in both forms.  exact != 0: the candidates are the filter's ids (NULL: every id) minus the removed rows,
+ *     as in cph_search_batch_exact, scanned with its arithmetic: every hit is returned (no cap), each segment ascends by
+ *     (distance bits, INTERNAL id), no id twice, distances are the bytes of the exact search.  exact == 0: the graph route,
+ *     needs max_results = K >= 1: segment i = the entries of row i of cph_search_batch_filtered(queries, K, filter) with
+ *     id >= 0 and dist < radius[i], in row order, the same bytes; that call, with all its routing, is enqueued into scratch
+ *     rows.  Runs the count pass (the search) and the offsets scan, WAITS for the sizes and returns *total = lims[n] and
+ *     the object.  The object owns its scratch (no batch set) and holds the effective filter: a cph_remove between the
+ *     two steps does not change the answer; a load, build or compact does (finish then fails with CPH_RUNTIME_ERROR).
+ *     n == 0 and a filter that allows nothing give *total = 0 without a scan launch.
+ * cph_range_search_finish  lims_host[n + 1]: host memory; ids[total], dist[total]: host memory, or device memory
+ *     (results_on_device != 0).  The queries are cut into consecutive tiles whose keys (twice when a segment is longer
+ *     than one LDS sort) fit the exact scratch budget (CPH_EXACT_SCRATCH_MB; a single query may exceed it); per tile the
+ *     fill pass, the segmented sort and the emit run on the stream of begin.  Under CPH_IDS_INPUT ids are translated as
+ *     they are written; the order stays the internal-id order.  WAITS for its kernels (and copies) before it returns.
+ *     Once per object.  With *total == 0 ids and dist may be NULL.
+ * cph_range_destroy        frees the object (NULL: no-op); nothing of it is in flight after begin / finish returned.
+ *     Its device buffers go back to the handle, which keeps those of two finished calls for the next ones (an index
+ *     swap frees them): in steady state a call makes no hipMalloc and no hipFree of its own.  The handle must outlive
+ *     the object (destroy it first); on a handle without removed rows the caller's filter must outlive finish.
+ *     Both steps hold the handle mutex, host waits included: other calls on the same handle queue behind them.
+ *
+ * cph_last_search_stats after an exact range search: [1] = 2 x n x candidates (two passes), every other word 0; after
+ * the graph route: those of the underlying search. */
+typedef struct cph_range cph_range;
+int cph_range_search_begin(cph_index* h, const void* queries, int queries_on_device, uint64_t n, const float* radius_host,
+                           const cph_filter* filter, int exact, uint64_t max_results, void* stream, cph_range** out,
+                           uint64_t* total);
+int cph_range_search_finish(cph_range* r, int64_t* lims_host, void* ids, void* dist, int results_on_device);
+int cph_range_destroy(cph_range* r);
+/* Host statements of the range search (no HIP call).  cph_host_range_plan: out[5] = parts, candidates per part (a
+ * multiple of 64), queries per group, keys of one LDS sort, rows of the padded query array (a fill launch starts at a
+ * tile's first query and reads whole tiles of 8 rows: every row it can touch lies below this count).  cph_host_range_tiles: the tiles finish cuts n queries with
+ * these lims into under budget_bytes: starts_out[*n_tiles_out + 1] (room for n + 1), tile t = queries [starts[t],
+ * starts[t + 1]).  cph_host_range_merge_pass: one merge pass of width `width` over a segment of `len` unique keys that
+ * is sorted in runs of `width`: out = the segment sorted in runs of 2 x width. */
+int cph_host_range_plan(uint64_t candidates, uint64_t n_queries, int num_cus, uint64_t* out);
+int cph_host_range_tiles(const int64_t* lims, uint64_t n, uint64_t budget_bytes, uint64_t* starts_out, uint64_t* n_tiles_out);
+int cph_host_range_merge_pass(const uint64_t* in, uint64_t* out, uint64_t len, uint64_t width);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -365,6 +412,16 @@ int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n,
  * the shards are contiguous and filter_of is sliced with the queries. */
 int cph_multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
                                    uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist);
+/* The range search (host form) over the same shards: every shard runs cph_range_search_begin / _finish on its replica's
+ * worker; begin sums the totals, finish writes every shard's segments behind those of the shards before it.  The bytes are
+ * those of one device.  f = NULL, or one filter per replica.  (The device form is the single-device call on a replica.)
+ * Destroy the object before the multi handle. */
+typedef struct cph_multi_range cph_multi_range;
+int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n, const float* radius_host,
+                                 const cph_filter* const* f, int exact, uint64_t max_results, cph_multi_range** out,
+                                 uint64_t* total);
+int cph_multi_range_search_finish(cph_multi_range* r, int64_t* lims_host, int64_t* ids, float* dist);
+int cph_multi_range_destroy(cph_multi_range* r);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

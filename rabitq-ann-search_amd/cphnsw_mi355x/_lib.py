@@ -62,6 +62,17 @@ SYMBOLS = {
     "cph_multi_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
     "cph_host_filter_ids": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_host_exact_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cph_range_search_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
+                                         C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "cph_range_search_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cph_range_destroy": (C.c_int, [C.c_void_p]),
+    "cph_multi_range_search_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "cph_multi_range_search_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_multi_range_destroy": (C.c_int, [C.c_void_p]),
+    "cph_host_range_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "cph_host_range_tiles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_host_range_merge_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "cph_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "cph_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

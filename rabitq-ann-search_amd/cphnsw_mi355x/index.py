@@ -514,6 +514,126 @@ class CPIndex:
                                                                dist.data_ptr(), C.c_void_p(st)))
         return ids, dist
 
+    # -- range search (not in the reference) ---------------------------------------------------
+    def _range_args(self, n, radius, filter, exact, max_results, filter_of):
+        """Validation shared by both range entry points -> (radius float32 [n] on the host, IdFilter or None, K)."""
+        if self._p is not None:
+            raise ValueError("range_search is not defined on a partitioned index (every part has its own internal ids "
+                             "and its own segments): use part(i).range_search")
+        if filter_of is not None or (isinstance(filter, (list, tuple))
+                                     and any(isinstance(f, (IdFilter, np.ndarray, list, tuple)) for f in filter)):
+            raise ValueError("range_search takes one filter for the whole batch (per-query filters, filter_of, are not "
+                             "supported)")
+        if hasattr(radius, "detach"):                     # a torch tensor (copied to the host: the C-ABI takes host radii)
+            radius = radius.detach().cpu().numpy()
+        r = np.asarray(radius)
+        if r.dtype == bool or not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
+            raise ValueError("radius must be a number or a float array with one entry per query")
+        if r.ndim == 0:
+            r = np.full(n, r, np.float32)
+        elif r.ndim != 1 or r.shape[0] != n:
+            raise ValueError(f"radius must be a scalar or a 1D array of length {n} (one entry per query)")
+        r = np.ascontiguousarray(r, np.float32)
+        K = 0
+        if not exact:
+            if max_results is None:
+                raise ValueError("range_search(exact=False) needs max_results (the k of the underlying search)")
+            K = int(max_results)
+            if K < 1:
+                raise ValueError("max_results must be >= 1")
+        return r, (None if filter is None else self._filter(filter)), K
+
+    def range_search(self, queries, radius, filter=None, exact=True, max_results=None, filter_of=None):
+        """Every allowed id closer than `radius`: (lims int64 [n + 1], ids int64 [lims[n]], dist float32 [lims[n]]);
+        query i owns ids[lims[i]:lims[i + 1]] and dist[...] (the FAISS layout, ids first as everywhere here).  `radius`: a
+        scalar or a float array [n], compared as float32 against the squared-L2 values the searches return; an id is a
+        hit iff dist < radius (strict), so a radius <= 0 or NaN selects nothing and +inf every allowed id.
+        exact=True (default): the candidates are the filter's ids, or the whole index, minus removed rows; EVERY hit is
+        returned, each segment ascends by (distance, internal id), no id twice, and a distance has the bytes
+        search_batch(..., exact=True) returns for the pair.  With result_ids = "input" the ids are input rows, in the
+        same (internal-id) order.  exact=False needs max_results=K: segment i is row i of search_batch(queries, K,
+        filter=filter) cut at the radius -- its entries with id >= 0 and dist < radius[i], in row order.
+        A multi-device index shards the queries like search_batch(exact=True); the bytes are those of one device.
+        Per-query filters (filter_of) and a partitioned index are refused (use part(i).range_search)."""
+        q = _as_f32(queries)
+        if q.ndim != 2 or q.shape[1] != self._dim:
+            raise ValueError("queries must be a (n, dim) array")
+        n = q.shape[0]
+        r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
+        L = _lib.lib()
+        obj, total = C.c_void_p(), C.c_uint64(0)
+        lims = np.zeros(n + 1, np.int64)
+        qp, rp = (q.ctypes.data if n else None), (r.ctypes.data if n else None)
+        if self._m is not None:
+            fs = None if f is None else (C.c_void_p * len(f._hs))(*[h.value for h in f._hs])
+            _lib.check(L.cph_multi_range_search_begin(self._m, qp, n, rp, fs, int(bool(exact)), K, C.byref(obj), C.byref(total)))
+            finish, destroy = L.cph_multi_range_search_finish, L.cph_multi_range_destroy
+            tail = ()
+        else:
+            _lib.check(L.cph_range_search_begin(self._h, qp, 0, n, rp, None if f is None else f._h, int(bool(exact)), K, None,
+                                                C.byref(obj), C.byref(total)))
+            finish, destroy = L.cph_range_search_finish, L.cph_range_destroy
+            tail = (0,)
+        try:
+            ids = np.empty(total.value, np.int64)
+            dist = np.empty(total.value, np.float32)
+            _lib.check(finish(obj, lims.ctypes.data, ids.ctypes.data if total.value else None,
+                              dist.ctypes.data if total.value else None, *tail))
+        finally:
+            destroy(obj)
+        return lims, ids, dist
+
+    def range_search_device(self, queries, radius, filter=None, exact=True, max_results=None, stream=None, filter_of=None):
+        """range_search on a float32 torch tensor (n, dim) on this index' device; returns (lims, ids, dist) with `lims`
+        a CPU int64 tensor and ids / dist on the queries' device.  The kernels run on `stream` (default: torch's current
+        stream), but unlike search_batch_device this call is NOT enqueue-only: the size of the output is data, so it
+        waits once for the counts, allocates ids / dist, and waits for its own kernels before it returns -- the tensors
+        are complete on return, and a filter may be closed right after the call.  `radius`: a scalar, an array, or a
+        tensor (copied to the host).  A multi-device index runs the whole batch on one replica on the queries' device,
+        alternating like search_batch_device."""
+        import torch
+        if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, dim) array")
+        n = queries.shape[0]
+        r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
+        rep = 0
+        if self._m is not None:
+            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
+            if not on:
+                raise ValueError("queries must live on one of this index' devices")
+            rep = on[self._next_dev % len(on)]
+            self._next_dev += 1
+        elif not queries.is_cuda or queries.device.index != self._device:
+            raise ValueError("queries must live on this index' device")
+        h = self._replicas()[rep]
+        cur = torch.cuda.current_stream(queries.device)
+        st = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        ext = None
+        if st != cur.cuda_stream:
+            ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
+        if not queries.is_contiguous():
+            queries = queries.contiguous()
+            if ext is not None:                  # (the copy belongs to the current stream)
+                ext.wait_stream(cur)
+        L = _lib.lib()
+        obj, total = C.c_void_p(), C.c_uint64(0)
+        _lib.check(L.cph_range_search_begin(h, queries.data_ptr() if n else None, 1, n, r.ctypes.data if n else None,
+                                            None if f is None else f._hs[rep], int(bool(exact)), K, C.c_void_p(st), C.byref(obj),
+                                            C.byref(total)))
+        try:
+            lims = torch.zeros(n + 1, dtype=torch.int64)
+            ids = torch.empty(total.value, dtype=torch.int64, device=queries.device)
+            dist = torch.empty(total.value, dtype=torch.float32, device=queries.device)
+            if ext is not None:
+                # The blocks belong to the current stream, whose earlier work may still use them: the fill runs after it.
+                # (finish waits for its writes, so nothing has to be recorded for the allocator.)
+                ext.wait_stream(cur)
+            _lib.check(L.cph_range_search_finish(obj, lims.data_ptr(), ids.data_ptr() if total.value else None,
+                                                 dist.data_ptr() if total.value else None, 1))
+        finally:
+            L.cph_range_destroy(obj)
+        return lims, ids, dist
+
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):
         space = self._result_ids if ids is None else ids

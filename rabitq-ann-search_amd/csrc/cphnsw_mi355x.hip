@@ -33,6 +33,7 @@
 #include "device_rows.h"
 #include "device_tombstone.h"
 #include "device_exact.h"
+#include "device_range.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -151,6 +152,16 @@ struct BatchSet {
     bool tab_used = false;
 };
 constexpr int kMaxBatchSets = 4;
+
+// The device buffers of one range search (cph_range).  A handle keeps up to kRangeScratchKept idle ones for the next call.
+struct RangeScratch {
+    DevBuf<float> d_q, qpad, qnorm, d_rad, g_dist, o_dist;
+    DevBuf<int64_t> g_ids, o_ids;
+    DevBuf<uint32_t> counts;
+    DevBuf<unsigned long long> offs, sums, d_lims, d_stats, arena, arena2;
+    DevBuf<uint8_t> d_tab;
+};
+constexpr size_t kRangeScratchKept = 2;
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
@@ -236,6 +247,10 @@ struct cph_index {
     int n_sets = 2;                    // sets in rotation (cph_set_batch_sets): batches that may be in flight together
     int last_set = kMaxBatchSets - 1;  // the set handed out last (they take turns)
     int last_search = -1;              // the set the most recent search went to
+    bool last_range = false;           // ... unless an exact range search came later: it uses no set, its one counter is
+    uint64_t range_exact = 0;          //     kept here (cph_last_search_stats)
+    std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
+    uint64_t index_epoch = 0;          // counts the index swaps (begin_device_swap): a cph_range of an older index refuses to finish
     hipStream_t own_stream = nullptr;  // host-API calls (cph_search_batch, cph_search, hooks)
     bool order_queries = true;         // CPH_QUERY_ORDER=0 disables the closest-entry-first launch order
     // knobs
@@ -287,6 +302,7 @@ void reset_adaptation(cph_index* h) {
     h->pf_off = false;
     h->pf_dense = false;
     h->last_search = -1;
+    h->last_range = false;
 }
 
 // The host-side leftovers of the previous index: vectors waiting for finalize(), the native file's mapping, the own-code
@@ -787,6 +803,7 @@ void finish_batch(cph_index* h, BatchSet& s, hipStream_t st) {
     HIP_CHECK(hipEventRecord(s.ev_done, st));
     s.used = true;
     h->last_search = (int)(&s - h->sets);
+    h->last_range = false;
 }
 
 // The slots and the per-slot capacity of a graph launch over nq queries (s.run_slots, s.run_cap; the set's scratch is
@@ -1095,10 +1112,9 @@ void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t 
 }
 
 // cph_search_batch_device[_filtered]: queries and results in device memory, everything enqueued on the caller's stream.
-void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
-                         float* d_dist, void* stream, bool exact = false) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
+// search_batch_device_locked: the caller holds the handle mutex.
+void search_batch_device_locked(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
+                                float* d_dist, void* stream, bool exact = false) {
     if (!batch_has_work(h, f, d_queries, n, k, d_ids, d_dist)) return;
     h->use_device();
     const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
@@ -1112,6 +1128,13 @@ void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint6
     }
     if (!(f && f->popcount == 0)) stage_queries(h, s, d_queries, n, st);
     enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
+}
+
+void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
+                         float* d_dist, void* stream, bool exact = false) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    search_batch_device_locked(h, d_queries, n, k, f, d_ids, d_dist, stream, exact);
 }
 
 // ---- per-query filters: row i of the batch under filter filter_of[i] ------------------------------------------------------
@@ -1517,6 +1540,9 @@ static void begin_device_swap(cph_index* h) {
     h->finalized = false;
     for (auto& s : h->sets) release_scratch(s);
     h->last_search = -1;
+    h->last_range = false;
+    h->range_scratch.clear();
+    ++h->index_epoch;
 }
 
 static void load_v2(cph_index* h, const char* path) {
@@ -1668,6 +1694,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     h->host = HostIndex();
     drop_host_state(h);
     h->finalized = false;
+    ++h->index_epoch;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     sync_row_map(h);
     sync_removed(h);
@@ -1687,6 +1714,7 @@ static void finalize_build(cph_index* h) {
     h->use_device();
     const bool verbose = getenv("CPH_BUILD_VERBOSE") != nullptr;
     quiesce(h);
+    ++h->index_epoch;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     for (auto& s : h->sets) release_scratch(s);
     build::BuiltDevice dev;
@@ -1942,6 +1970,10 @@ int cph_last_search_stats(cph_index* h, uint64_t out[12]) {
         if (!h || !out) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
         for (int i = 0; i < 12; ++i) out[i] = 0;
+        if (h->last_range) {                     // an exact range search: two passes over the candidates, nothing else
+            out[kStatExact] = h->range_exact;
+            return;
+        }
         if (h->last_search < 0) return;
         BatchSet& s = h->sets[h->last_search];
         h->use_device();
@@ -2149,6 +2181,353 @@ int cph_host_exact_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int
             throw InvalidArg("exact plan: sizes out of range");
         const ExactPlan pl = plan_exact(candidates, (uint32_t)n_queries, (uint32_t)k, num_cus, (size_t)scratch_bytes);
         out[0] = pl.P; out[1] = pl.part; out[2] = pl.gq; out[3] = pl.tile_q; out[4] = pl.C; out[5] = (uint64_t)pl.pool_keys * 8;
+    });
+}
+
+}  // extern "C"
+
+// ---- range search: every allowed id closer than a radius, in CSR form (device_range.h) ----------------------------------
+// Two steps, because the caller allocates the output: cph_range_search_begin counts (exact: the count pass and the offsets
+// scan; graph route: an ordinary search into scratch rows, cut at the radius) and returns the total, cph_range_search_finish
+// writes the segments.  The object owns its scratch (it takes no batch set; the buffers come from, and go back to, the
+// handle's short free list, so that a call in steady state makes no hipMalloc and no hipFree -- a hipFree waits for the
+// whole device) and holds the effective filter it began under: a cph_remove between the two steps does not change the
+// answer.
+struct cph_range {
+    cph_index* h = nullptr;
+    int device = 0;
+    uint64_t epoch = 0;                        // h->index_epoch at begin
+    uint64_t n = 0;                            // queries
+    bool exact = true;
+    uint32_t K = 0;                            // graph route: entries per scratch row
+    hipStream_t st = nullptr;                  // the caller's (device form) or the handle's own
+    bool in_flight = false;                    // something enqueued has not been waited for (a failure in between)
+    bool finished = false;
+    std::shared_ptr<const cph_filter> filt;    // the snapshot F & ~R (aliasing the caller's F on a handle without removed rows)
+    uint64_t m = 0;                            // candidates
+    const uint32_t* d_list = nullptr;          // their ascending ids, or null: every id
+    RangePlan pl{};
+    std::vector<int64_t> lims;                 // [n + 1]
+    uint64_t total = 0;
+    std::unique_ptr<RangeScratch> s;           // its device buffers: taken from the handle at begin, handed back by destroy
+};
+
+namespace {
+
+void range_sync(cph_range* r) {
+    HIP_CHECK(hipStreamSynchronize(r->st));
+    r->in_flight = false;
+}
+
+// The scan launches of one pass over the queries [q_first, q_first + q_count): grid.y holds at most 65,535 groups.
+template <bool kFill>
+void range_scan_pass(cph_range* r, RangeArgs a, uint32_t q_first, uint32_t q_count) {
+    const uint32_t per = 65535u * r->pl.gq;
+    for (uint64_t q0 = q_first; q0 < (uint64_t)q_first + q_count; q0 += per) {
+        a.q_first = (uint32_t)q0;
+        a.q_count = (uint32_t)std::min<uint64_t>(per, (uint64_t)q_first + q_count - q0);
+        // (the fill's arena index is relative to the TILE's first query, whichever launch writes it)
+        launch_range_scan<kFill>(r->h->L.D, dim3(r->pl.P, (a.q_count + r->pl.gq - 1) / r->pl.gq), (size_t)r->pl.gq * 12, r->st, a);
+    }
+}
+
+RangeArgs range_args(const cph_range* r) {
+    const cph_index* h = r->h;
+    RangeArgs a{};
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.ids = r->d_list;
+    a.m = (uint32_t)r->m;
+    a.D = h->L.D;
+    a.qpad = r->s->qpad.p;
+    a.qnorm = r->s->qnorm.p;
+    a.radius = r->s->d_rad.p;
+    a.gq = r->pl.gq;
+    a.part = r->pl.part;
+    a.P = r->pl.P;
+    a.counts = r->s->counts.p;
+    a.offs = r->s->offs.p;
+    a.arena = r->s->arena.p;
+    return a;
+}
+
+void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, const float* radius, const cph_filter* f, bool exact,
+                 uint64_t K, void* stream, cph_range** out, uint64_t* total) {
+    if (!h) throw InvalidArg("null handle");
+    if (!out || !total) throw InvalidArg("null argument");
+    *out = nullptr;
+    *total = 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (f) check_filter(h, f);
+    if (n > 0xFFFFFFFFull) throw InvalidArg("batch too large");
+    if (n && (!queries || !radius)) throw InvalidArg("null argument");
+    if (!exact && (K == 0 || K > 0xFFFFFFFFull)) throw InvalidArg("the graph route of a range search needs max_results >= 1");
+    h->use_device();
+    std::unique_ptr<cph_range> r(new cph_range());
+    r->h = h;
+    r->device = h->device;
+    r->epoch = h->index_epoch;
+    r->n = n;
+    r->exact = exact;
+    r->K = (uint32_t)K;
+    r->lims.assign(n + 1, 0);
+    if (!h->range_scratch.empty()) {
+        r->s = std::move(h->range_scratch.back());
+        h->range_scratch.pop_back();
+    } else {
+        r->s.reset(new RangeScratch());
+    }
+    hipStream_t st = q_dev ? reinterpret_cast<hipStream_t>(stream) : own_stream(h);
+    r->st = st;
+    if (exact) {
+        r->filt = effective_filter(h, f);                  // removed rows: F & ~R
+        r->m = r->filt ? r->filt->popcount : h->host.n;
+    }
+    if (n == 0 || (exact && r->m == 0)) {                  // nothing to scan: every segment is empty
+        if (exact) { h->last_range = true; h->range_exact = 0; }
+        *out = r.release();
+        return;
+    }
+    try {
+        r->in_flight = true;
+        r->s->d_rad.alloc(n);
+        HIP_CHECK(hipMemcpyAsync(r->s->d_rad.p, radius, n * 4, hipMemcpyHostToDevice, st));
+        const float* d_q = queries;
+        if (!q_dev) {
+            r->s->d_q.alloc(n * h->dim);
+            HIP_CHECK(hipMemcpyAsync(r->s->d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
+            d_q = r->s->d_q.p;
+        }
+        uint64_t n_cnt = n;
+        uint32_t P = 1;
+        if (!exact) {
+            // the search itself, with all its routing, into scratch rows; then the cut
+            r->s->g_ids.alloc(n * K);
+            r->s->g_dist.alloc(n * K);
+            r->s->counts.alloc(n);
+            search_batch_device_locked(h, d_q, n, K, f, r->s->g_ids.p, r->s->g_dist.p, st);
+            hipLaunchKernelGGL(range_cut_count_kernel, dim3((uint32_t)n), dim3(64), 0, st, (const int64_t*)r->s->g_ids.p, (const float*)r->s->g_dist.p,
+                               (uint32_t)K, (const float*)r->s->d_rad.p, r->s->counts.p);
+            HIP_CHECK(hipGetLastError());
+        } else {
+            const cph_filter* ef = r->filt.get();
+            r->pl = plan_range(r->m, n, h->num_cus);
+            P = r->pl.P;
+            n_cnt = n * P;
+            const uint32_t D = h->L.D;
+            // Padded query rows.  exact_fma_chunk loads all kExactQT rows of a query tile, whatever the group holds, and a
+            // fill launch starts its groups at a scratch tile's first query (range_tiles), which need not be a multiple of
+            // kExactQT: the rows read end below q0 + roundup(n - q0) <= n + kExactQT - 1.  range_query_rows(n) holds them
+            // all, zero behind n (cph_host_range_plan states it, the CPU tests check it against the tiles).
+            const uint32_t nq_pad = (uint32_t)range_query_rows(n);
+            r->s->qpad.alloc((size_t)nq_pad * D);
+            r->s->qnorm.alloc(nq_pad);
+            r->s->counts.alloc(n_cnt);
+            r->s->d_stats.alloc(kStatWords);
+            r->d_list = ef ? filter_id_list(ef, st) : nullptr;
+            hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_q, (uint32_t)n,
+                               nq_pad, (uint32_t)h->dim, D, r->s->qpad.p, r->s->qnorm.p, r->s->d_stats.p, (unsigned long long)(2 * n * r->m));
+            HIP_CHECK(hipGetLastError());
+            range_scan_pass<false>(r.get(), range_args(r.get()), 0, (uint32_t)n);
+        }
+        r->s->offs.alloc(n_cnt + 1);
+        r->s->sums.alloc(n_cnt / kRangeScanSpan + 2);
+        r->s->d_lims.alloc(n + 1);
+        range_offsets(r->s->counts.p, n_cnt, P, r->s->sums.p, r->s->offs.p, r->s->d_lims.p, st);
+        HIP_CHECK(hipMemcpyAsync(r->lims.data(), r->s->d_lims.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        range_sync(r.get());                               // the output size is data
+    } catch (...) {
+        if (r->in_flight) (void)hipStreamSynchronize(st);  // nothing may still read the buffers that go with r
+        throw;
+    }
+    r->total = (uint64_t)r->lims[n];
+    if (exact) { h->last_range = true; h->range_exact = 2 * n * r->m; }
+    *total = r->total;
+    *out = r.release();
+}
+
+// The sort tables of one tile, appended to `tab`: RangeRun[n_runs] | RangeLong[n_long]; returns the longest run / segment.
+struct RangeTileTab {
+    size_t o_runs = 0, o_long = 0;
+    uint32_t n_runs = 0, n_long = 0, max_run = 0;
+    uint64_t max_long = 0;
+};
+
+RangeTileTab range_tile_tables(const std::vector<int64_t>& lims, uint64_t lo, uint64_t hi, std::vector<uint8_t>& tab) {
+    RangeTileTab t;
+    std::vector<RangeRun> runs;
+    std::vector<RangeLong> longs;
+    const uint64_t base = (uint64_t)lims[lo];
+    for (uint64_t q = lo; q < hi; ++q) {
+        const uint64_t start = (uint64_t)lims[q] - base, len = (uint64_t)(lims[q + 1] - lims[q]);
+        if (len > kRangeRun) {
+            longs.push_back(RangeLong{start, len});
+            t.max_long = std::max(t.max_long, len);
+        }
+        for (uint64_t o = 0; o < len; o += kRangeRun) {
+            const uint32_t rl = (uint32_t)std::min<uint64_t>(kRangeRun, len - o);
+            if (rl < 2) continue;
+            runs.push_back(RangeRun{start + o, rl, 0});
+            t.max_run = std::max(t.max_run, rl);
+        }
+    }
+    t.n_runs = (uint32_t)runs.size();
+    t.n_long = (uint32_t)longs.size();
+    t.o_runs = tab.size();
+    tab.insert(tab.end(), reinterpret_cast<const uint8_t*>(runs.data()), reinterpret_cast<const uint8_t*>(runs.data() + runs.size()));
+    t.o_long = tab.size();
+    tab.insert(tab.end(), reinterpret_cast<const uint8_t*>(longs.data()), reinterpret_cast<const uint8_t*>(longs.data() + longs.size()));
+    return t;
+}
+
+void range_finish(cph_range* r, int64_t* lims_host, int64_t* ids, float* dist, bool on_dev) {
+    if (!r || !lims_host) throw InvalidArg("null argument");
+    cph_index* h = r->h;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (r->finished) throw InvalidArg("cph_range_search_finish was called on this object before");
+    if (!h->finalized || h->index_epoch != r->epoch)
+        throw std::runtime_error("The index changed between cph_range_search_begin and cph_range_search_finish.");
+    std::memcpy(lims_host, r->lims.data(), (r->n + 1) * 8);
+    if (r->total == 0) {
+        r->finished = true;
+        return;
+    }
+    if (!ids || !dist) throw InvalidArg("null argument");
+    h->use_device();
+    hipStream_t st = r->st;
+    const uint64_t n = r->n;
+    std::vector<uint8_t> tab;                              // (lives until the wait at the end: the copy may read it late)
+    try {
+        r->in_flight = true;
+        int64_t* d_ids = ids;
+        float* d_dist = dist;
+        if (!on_dev) {
+            r->s->o_ids.alloc(r->total);
+            r->s->o_dist.alloc(r->total);
+            d_ids = r->s->o_ids.p;
+            d_dist = r->s->o_dist.p;
+        }
+        if (!r->exact) {
+            hipLaunchKernelGGL(range_cut_emit_kernel, dim3((uint32_t)n), dim3(64), 0, st, (const int64_t*)r->s->g_ids.p, (const float*)r->s->g_dist.p,
+                               r->K, (const float*)r->s->d_rad.p, (const unsigned long long*)r->s->d_lims.p, d_ids, d_dist);
+            HIP_CHECK(hipGetLastError());
+        } else {
+            const std::vector<uint64_t> starts = range_tiles(r->lims.data(), n, h->exact_scratch_bytes);
+            std::vector<RangeTileTab> tt;
+            uint64_t max_keys = 0, max_keys_long = 0;
+            for (size_t t = 0; t + 1 < starts.size(); ++t) {
+                tt.push_back(range_tile_tables(r->lims, starts[t], starts[t + 1], tab));
+                const uint64_t keys = (uint64_t)(r->lims[starts[t + 1]] - r->lims[starts[t]]);
+                max_keys = std::max(max_keys, keys);
+                if (tt.back().n_long) max_keys_long = std::max(max_keys_long, keys);
+            }
+            r->s->arena.alloc(max_keys);
+            if (max_keys_long) r->s->arena2.alloc(max_keys_long);
+            if (!tab.empty()) {
+                r->s->d_tab.alloc(tab.size());
+                HIP_CHECK(hipMemcpyAsync(r->s->d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+            }
+            const uint32_t* rows = h->ids_input ? h->d_rows.p : nullptr;
+            for (size_t t = 0; t + 1 < starts.size(); ++t) {
+                const uint64_t lo = starts[t], hi = starts[t + 1];
+                const unsigned long long base = (unsigned long long)r->lims[lo];
+                if ((uint64_t)r->lims[hi] == base) continue;           // no hit in the whole tile
+                RangeArgs a = range_args(r);
+                a.tile_base = base;
+                range_scan_pass<true>(r, a, (uint32_t)lo, (uint32_t)(hi - lo));
+                const RangeTileTab& x = tt[t];
+                if (x.n_runs) {
+                    uint32_t N = 64;
+                    while (N < x.max_run) N <<= 1;
+                    hipLaunchKernelGGL(range_sort_runs_kernel, dim3(x.n_runs), dim3(64), (size_t)N * 8, st,
+                                       reinterpret_cast<const RangeRun*>(r->s->d_tab.p + x.o_runs), r->s->arena.p);
+                    HIP_CHECK(hipGetLastError());
+                }
+                unsigned long long* src = r->s->arena.p;
+                unsigned long long* dst = r->s->arena2.p;
+                for (unsigned long long w = kRangeRun; x.n_long && w < x.max_long; w <<= 1) {
+                    for (uint32_t s0 = 0; s0 < x.n_long; s0 += 65535u) {
+                        const dim3 grid((uint32_t)((x.max_long + 255) / 256), std::min<uint32_t>(65535u, x.n_long - s0));
+                        hipLaunchKernelGGL(range_merge_pass_kernel, grid, dim3(256), 0, st,
+                                           reinterpret_cast<const RangeLong*>(r->s->d_tab.p + x.o_long) + s0, (const unsigned long long*)src, dst, w);
+                        HIP_CHECK(hipGetLastError());
+                    }
+                    std::swap(src, dst);
+                }
+                hipLaunchKernelGGL(range_emit_kernel, dim3((uint32_t)(hi - lo)), dim3(256), 0, st, (const unsigned long long*)r->s->arena.p,
+                                   (const unsigned long long*)src, (const unsigned long long*)r->s->d_lims.p, (uint32_t)lo, base, rows, d_ids, d_dist);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (!on_dev) {
+            HIP_CHECK(hipMemcpyAsync(ids, d_ids, r->total * 8, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(dist, d_dist, r->total * 4, hipMemcpyDeviceToHost, st));
+        }
+        range_sync(r);
+    } catch (...) {
+        if (r->in_flight) (void)hipStreamSynchronize(st);
+        throw;
+    }
+    r->finished = true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_range_search_begin(cph_index* h, const void* queries, int queries_on_device, uint64_t n, const float* radius_host,
+                           const cph_filter* filter, int exact, uint64_t max_results, void* stream, cph_range** out, uint64_t* total) {
+    return guarded([&] {
+        range_begin(h, static_cast<const float*>(queries), queries_on_device != 0, n, radius_host, filter, exact != 0, max_results, stream, out,
+                    total);
+    });
+}
+
+int cph_range_search_finish(cph_range* r, int64_t* lims_host, void* ids, void* dist, int results_on_device) {
+    return guarded([&] { range_finish(r, lims_host, static_cast<int64_t*>(ids), static_cast<float*>(dist), results_on_device != 0); });
+}
+
+int cph_range_destroy(cph_range* r) {
+    return guarded([&] {
+        if (!r) return;
+        std::unique_ptr<cph_range> own(r);
+        if (r->in_flight) {                                // (only after a failure whose own wait failed too)
+            HIP_CHECK(hipSetDevice(r->device));
+            HIP_CHECK(hipDeviceSynchronize());
+        }
+        std::lock_guard<std::mutex> lk(r->h->mu);
+        if (r->s && r->h->range_scratch.size() < kRangeScratchKept) r->h->range_scratch.push_back(std::move(r->s));
+    });
+}
+
+int cph_host_range_plan(uint64_t candidates, uint64_t n_queries, int num_cus, uint64_t* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        if (candidates == 0 || candidates > 0xFFFFFFFFull || n_queries == 0 || n_queries > 0xFFFFFFFFull)
+            throw InvalidArg("range plan: sizes out of range");
+        const RangePlan pl = plan_range(candidates, n_queries, num_cus);
+        out[0] = pl.P; out[1] = pl.part; out[2] = pl.gq; out[3] = pl.run; out[4] = range_query_rows(n_queries);
+    });
+}
+
+int cph_host_range_tiles(const int64_t* lims, uint64_t n, uint64_t budget_bytes, uint64_t* starts_out, uint64_t* n_tiles_out) {
+    return guarded([&] {
+        if (!lims || !n_tiles_out || (n && !starts_out)) throw InvalidArg("null argument");
+        for (uint64_t i = 0; i < n; ++i)
+            if (lims[i + 1] < lims[i]) throw InvalidArg("lims must not descend");
+        const std::vector<uint64_t> starts = range_tiles(lims, n, budget_bytes);
+        for (size_t i = 0; i < starts.size(); ++i) starts_out[i] = starts[i];
+        *n_tiles_out = starts.empty() ? 0 : starts.size() - 1;
+    });
+}
+
+int cph_host_range_merge_pass(const uint64_t* in, uint64_t* out, uint64_t len, uint64_t width) {
+    return guarded([&] {
+        if (len && (!in || !out)) throw InvalidArg("null argument");
+        if (width == 0) throw InvalidArg("width must be >= 1");
+        for (uint64_t i = 0; i < len; ++i)
+            out[range_merge_dest(reinterpret_cast<const unsigned long long*>(in), len, width, i)] = in[i];
     });
 }
 
@@ -3165,6 +3544,107 @@ int cph_multi_replica(cph_multi* m, uint32_t i, cph_index** out) {
         if (i >= m->reps.size()) throw InvalidArg("replica index out of range");
         *out = m->reps[i];
     });
+}
+
+}  // extern "C"
+
+// ---- range search on replicas ---------------------------------------------------------------------------------------------
+// The host form over plan_shards: every shard runs the single-device two-step protocol on its replica's worker, begin
+// sums the totals, finish lets every shard write behind the hits of the shards before it.
+struct cph_multi_range {
+    cph_multi* m = nullptr;
+    uint64_t n = 0, total = 0;
+    std::vector<Shard> plan;
+    std::vector<cph_range*> parts;             // one per shard
+    std::vector<uint64_t> first;               // hits before shard i
+    ~cph_multi_range() {
+        for (cph_range* r : parts) (void)cph_range_destroy(r);
+    }
+};
+
+namespace {
+
+size_t shard_index(const std::vector<Shard>& plan, const Shard& s) {
+    for (size_t i = 0; i < plan.size(); ++i)
+        if (plan[i].replica == s.replica && plan[i].lo == s.lo && plan[i].hi == s.hi) return i;
+    throw std::runtime_error("shard not in the plan");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n, const float* radius_host, const cph_filter* const* f,
+                                 int exact, uint64_t max_results, cph_multi_range** out, uint64_t* total) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        if (!out || !total) throw InvalidArg("null argument");
+        *out = nullptr;
+        *total = 0;
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        const uint32_t R = (uint32_t)m->reps.size();
+        for (uint32_t r = 0; r < R; ++r) {
+            cph_index* h = m->reps[r];
+            std::lock_guard<std::mutex> g(h->mu);
+            require_finalized(h);
+            if (f) {
+                if (!f[r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
+                check_filter(h, f[r]);
+            }
+        }
+        if (n && (!queries || !radius_host)) throw InvalidArg("null argument");
+        std::unique_ptr<cph_multi_range> mr(new cph_multi_range());
+        mr->m = m;
+        mr->n = n;
+        mr->plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
+        mr->parts.assign(mr->plan.size(), nullptr);
+        mr->first.assign(mr->plan.size() + 1, 0);
+        std::vector<uint64_t> totals(mr->plan.size(), 0);
+        const uint64_t dim = m->reps[0]->dim;
+        std::string err;
+        const int rc = m->pool->run(mr->plan, [&](const Shard& s, std::string& e) {
+            const size_t i = shard_index(mr->plan, s);
+            const int r = cph_range_search_begin(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, 0, s.hi - s.lo,
+                                                 radius_host ? radius_host + s.lo : nullptr, f ? f[s.replica] : nullptr, exact, max_results,
+                                                 nullptr, &mr->parts[i], &totals[i]);
+            if (r != CPH_OK) e = g_err;           // (thread-local: this worker's message)
+            return r;
+        }, err);
+        if (rc != CPH_OK) raise_status(rc, err);
+        for (size_t i = 0; i < totals.size(); ++i) mr->first[i + 1] = mr->first[i] + totals[i];
+        mr->total = mr->first.back();
+        {
+            std::lock_guard<std::mutex> g(m->last_mu);
+            m->last_plan = mr->plan;
+        }
+        *total = mr->total;
+        *out = mr.release();
+    });
+}
+
+int cph_multi_range_search_finish(cph_multi_range* mr, int64_t* lims_host, int64_t* ids, float* dist) {
+    return guarded([&] {
+        if (!mr || !lims_host) throw InvalidArg("null argument");
+        if (mr->total && (!ids || !dist)) throw InvalidArg("null argument");
+        cph_multi* m = mr->m;
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        std::string err;
+        const int rc = m->pool->run(mr->plan, [&](const Shard& s, std::string& e) {
+            const size_t i = shard_index(mr->plan, s);
+            std::vector<int64_t> local(s.hi - s.lo + 1);
+            const uint64_t at = mr->first[i];
+            const int r = cph_range_search_finish(mr->parts[i], local.data(), ids ? ids + at : nullptr, dist ? dist + at : nullptr, 0);
+            if (r != CPH_OK) { e = g_err; return r; }
+            for (uint64_t j = 0; j < s.hi - s.lo; ++j) lims_host[s.lo + j] = (int64_t)at + local[j];
+            return r;
+        }, err);
+        if (rc != CPH_OK) raise_status(rc, err);
+        lims_host[mr->n] = (int64_t)mr->total;
+    });
+}
+
+int cph_multi_range_destroy(cph_multi_range* mr) {
+    return guarded([&] { delete mr; });
 }
 
 }  // extern "C"

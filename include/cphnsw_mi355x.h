@@ -319,6 +319,44 @@ int cph_live_count(cph_index* h, uint64_t* n);
 int cph_get_removed(cph_index* h, uint32_t* words);
 int cph_compact(cph_index* h, int64_t* old_to_new);
 
+/* ---- label column and label filters ------------------------------------------------------- */
+/* A finalized handle may carry one int32 label per row (a tenant, a category, a day), resident on its device in
+ * internal-id order (4 B per vertex, next to the row map), so that "rows whose label is t" becomes a filter without a
+ * host-built bitmap: cph_filters_from_labels makes many filters in one device pass (csrc/device_labels.h).
+ *
+ * cph_set_labels   labels[n]: one int32 per row, n == size (else CPH_INVALID_ARGUMENT), in internal ids
+ *                  (CPH_IDS_INTERNAL) or input rows (CPH_IDS_INPUT; needs a row map, else CPH_INVALID_ARGUMENT; moved to
+ *                  internal order once, on the host).  NULL (n ignored) removes the column.  A handle that is not
+ *                  finalized is CPH_INVALID_ARGUMENT; a borrowed replica or part handle is refused like cph_set_row_map.
+ *                  Holds the handle mutex; filters made before keep their bits.
+ * lifetime         the column ends with cph_build, cph_load and cph_load_native (no file carries it: cph_save_native
+ *                  writes the bytes it writes without one; the caller keeps the array and sets it again after a load);
+ *                  it survives cph_remove, cph_set_row_map and cph_set_result_ids; cph_compact carries it over: new input
+ *                  row j has the label of the live row it came from.
+ * cph_get_labels   labels of internal ids [first, first + count), like cph_get_row_map. */
+int cph_set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space);
+int cph_has_labels(cph_index* h, int* flag);
+int cph_get_labels(cph_index* h, uint64_t first, uint64_t count, int32_t* out);
+/* m filters at once: filter j allows the ids whose label x satisfies lo[j] <= x <= hi[j] (signed, both ends inclusive;
+ * lo[j] > hi[j]: the empty filter).  out[m] receives ordinary cph_filter objects (bitmap on the handle's device, bits
+ * behind size clear, popcount counted on the device), usable with every filtered entry point and destroyed one by one
+ * with cph_filter_destroy; their bitmaps share one device allocation, which goes with the last of them.  The call waits
+ * once, for the m counts.  All or nothing: on failure nothing is left allocated and out[] is all NULL.  m == 0 is a
+ * no-op.  Needs a label column (CPH_INVALID_ARGUMENT without; also for m above 65,535 x 64).  Allowed on a borrowed replica or part handle. */
+int cph_filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out);
+/* Debug hooks of the measurement script (scripts/label_filter_sweep.py), not for production use: while switched on,
+ * every cph_filters_from_labels pass of this handle is bracketed by two HIP events on the handle's (private) stream;
+ * _us returns the device time of the last such pass (the memset of the counts and the kernel) in microseconds, or
+ * CPH_INVALID_ARGUMENT when none ran.  Off by default: the call then records no event. */
+int cph_debug_time_label_filters(cph_index* h, int on);
+int cph_debug_last_label_filters_us(cph_index* h, double* us);
+/* The bitmap and count of any cph_filter, back on the host: words[(n_bits + 31) / 32].  Either of words and count
+ * may be NULL (the count alone makes no device call). */
+int cph_filter_export(const cph_filter* f, uint32_t* words, uint64_t* count);
+/* Host statement of cph_filters_from_labels (no HIP call): words_out[m][(n + 31) / 32], counts_out[m]. */
+int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo, const int32_t* hi, uint32_t m,
+                           uint32_t* words_out, uint64_t* counts_out);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);
@@ -525,6 +563,17 @@ int cph_parts_remove(cph_parts* m, const int64_t* ids, uint64_t cnt, uint64_t* n
 int cph_parts_live_count(cph_parts* m, uint64_t* n);
 int cph_parts_get_removed(cph_parts* m, uint32_t* words);
 int cph_parts_compact(cph_parts* m, int64_t* old_to_new);
+/* The label column (cph_set_labels) of replicas and parts.  Replicas: the column on every replica (waits for the
+ * searches in flight); the per-replica filters are made with cph_filters_from_labels on each borrowed replica handle.
+ * Both set calls ask every replica / part first and change none when one refuses (a part without a row map).  Parts: labels[n] over GLOBAL input rows, cut at the part
+ * bounds; cph_parts_filters_from_labels lets every part evaluate its own slice (a part in which no row matches holds an
+ * empty filter and returns padding without a launch); cph_parts_filter_count: allowed rows over all parts.  finalize,
+ * load* and build drop the column on every replica and part; cph_multi_compact and cph_parts_compact carry it (parts cut
+ * it again at the new bounds). */
+int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int space);
+int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n);
+int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out);
+int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count);
 int cph_parts_num_parts(cph_parts* m, uint32_t* n);
 int cph_parts_part(cph_parts* m, uint32_t i, cph_index** out);
 int cph_parts_bounds(cph_parts* m, uint64_t* out);

@@ -91,6 +91,18 @@ SYMBOLS = {
     "cph_parts_live_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_parts_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cph_parts_compact": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cph_set_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_has_labels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_get_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "cph_filters_from_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_debug_time_label_filters": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_label_filters_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_filter_export": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_host_label_filters": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cph_multi_set_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_parts_set_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_parts_filters_from_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_parts_filter_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_synchronize": (C.c_int, [C.c_void_p]),
     "cph_set_batch_sets": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,

@@ -59,6 +59,31 @@ class IdFilter:
             self._hs.append(h)
         self._h = self._hs[0]
 
+    @classmethod
+    def _adopt(cls, size, count, hs=(), pf=None, parts=None):
+        """An IdFilter around filters the library made itself (CPIndex.label_filters): one cph_filter per replica, or
+        the cph_parts_filter of a partitioned index."""
+        f = cls.__new__(cls)
+        f._hs = list(hs)
+        f._h = f._hs[0] if f._hs else C.c_void_p()
+        f._pf = pf
+        f._parts = parts
+        f.size = int(size)
+        f.count = int(count)
+        return f
+
+    def words(self):
+        """The bitmap as it is resident on the device (replica 0's copy): uint32 [ceil(size / 32)], internal ids --
+        what pack_allowed_bits gives for the allowed-id mask."""
+        if getattr(self, "_pf", None) is not None:
+            raise ValueError("words() is not defined for a partitioned index' filter (one bitmap per part, each in the "
+                             "part's own internal ids)")
+        if not self._h.value:
+            raise ValueError("filter was closed")
+        w = np.empty((self.size + 31) // 32, np.uint32)
+        _lib.check(_lib.lib().cph_filter_export(self._h, w.ctypes.data if w.size else None, None))
+        return w
+
     def close(self):
         pf = getattr(self, "_pf", None)
         if pf is not None:
@@ -327,14 +352,174 @@ class CPIndex:
         hs = [h.value for f in fs for h in (f._hs if rep is None else [f._hs[rep]])]
         return (C.c_void_p * len(hs))(*hs) if hs else None
 
+    # -- labels (not in the reference) -----------------------------------------------------------
+    @staticmethod
+    def _as_labels(a, what):
+        a = np.asarray(a)
+        if a.dtype == bool or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{what} must be integers")
+        if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1):
+            raise ValueError(f"{what} must fit int32")
+        return a.astype(np.int32, order="C")     # (a scalar stays 0-d)
+
+    def set_labels(self, labels, ids=None):
+        """One integer label per row (a tenant, a category, a day), kept on the device (4 B per row): an integer array
+        [size] of any width whose values fit int32, indexed in the space `ids` ("internal" or "input"; default:
+        result_ids, as for make_filter).  None removes the column.  label_filter / label_filters and the `label=`
+        argument of the searches read it.  build(), load() and load_native() drop it (no file carries it: keep the array
+        and call set_labels again after loading); remove() and set_row_map() leave it; compact() carries it over."""
+        L = _lib.lib()
+        if labels is None:
+            if self._p is not None:
+                _lib.check(L.cph_parts_set_labels(self._p, None, 0))
+            elif self._m is not None:
+                _lib.check(L.cph_multi_set_labels(self._m, None, 0, _lib.IDS_INTERNAL))
+            else:
+                _lib.check(L.cph_set_labels(self._h, None, 0, _lib.IDS_INTERNAL))
+            return
+        space = self._id_space(ids)
+        a = self._as_labels(labels, "labels")
+        if a.ndim != 1 or a.shape[0] != self.size:
+            raise ValueError(f"labels must be a 1D integer array of length {self.size} (the index size)")
+        code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
+        if self._p is not None:
+            _lib.check(L.cph_parts_set_labels(self._p, a.ctypes.data, a.size))
+        elif self._m is not None:
+            _lib.check(L.cph_multi_set_labels(self._m, a.ctypes.data, a.size, code))
+        else:
+            _lib.check(L.cph_set_labels(self._h, a.ctypes.data, a.size, code))
+
+    @property
+    def has_labels(self):
+        """The index holds a label column (set_labels)."""
+        def has(h):
+            f = C.c_int(0)
+            _lib.check(_lib.lib().cph_has_labels(h, C.byref(f)))
+            return bool(f.value)
+        if self._p is not None:
+            return all(has(h) for h in self._part_handles)
+        return has(self._h)
+
+    @staticmethod
+    def _labels_of(h, n, by_row):
+        out = np.empty(n, np.int32)
+        if n:
+            _lib.check(_lib.lib().cph_get_labels(h, 0, n, out.ctypes.data))
+        if not by_row:
+            return out
+        rows = np.empty(n, np.uint32)
+        if n:
+            _lib.check(_lib.lib().cph_get_row_map(h, 0, n, rows.ctypes.data))
+        r = np.empty(n, np.int32)
+        r[rows] = out
+        return r
+
+    def labels(self, ids=None):
+        """int32[size] copy of the label column, indexed in the space `ids` (default: result_ids)."""
+        by_row = self._id_space(ids) == "input"          # (a partitioned index: always; _id_space refuses "internal")
+        if self._p is not None:
+            return np.concatenate([self._labels_of(h, hi - lo, by_row) for h, (lo, hi) in zip(self._part_handles, self.parts)])
+        return self._labels_of(self._h, self.size, by_row)
+
+    def label_filters(self, lo, hi=None):
+        """[IdFilter]: filter j allows the rows whose label x satisfies lo[j] <= x <= hi[j] (hi=None: x == lo[j];
+        lo[j] > hi[j]: nothing).  All of them are made in ONE pass over the label column on the device, which also
+        counts them (`count`); nothing is packed on the host.  They are ordinary filters: usable wherever filter=
+        is, with removed rows, replicas and parts.  Their bitmaps share one device allocation, freed with the last."""
+        lo = self._as_labels(lo, "label bounds").ravel()
+        hi = lo if hi is None else self._as_labels(hi, "label bounds").ravel()
+        if hi.shape != lo.shape:
+            raise ValueError("lo and hi must have the same length")
+        m, L, n = lo.size, _lib.lib(), self.size
+        if m == 0:
+            return []
+        if self._p is not None:
+            out = (C.c_void_p * m)()
+            _lib.check(L.cph_parts_filters_from_labels(self._p, lo.ctypes.data, hi.ctypes.data, m, out))
+            fs = [IdFilter._adopt(n, 0, pf=C.c_void_p(out[j]), parts=len(self._devices)) for j in range(m)]
+            return self._with_counts(fs, lambda f, c: L.cph_parts_filter_count(f._pf, c))
+        per_rep = []
+        try:
+            for rh in self._replicas():
+                out = (C.c_void_p * m)()
+                _lib.check(L.cph_filters_from_labels(rh, lo.ctypes.data, hi.ctypes.data, m, out))
+                per_rep.append(out)
+        except Exception:
+            for out in per_rep:
+                for j in range(m):
+                    L.cph_filter_destroy(C.c_void_p(out[j]))
+            raise
+        fs = [IdFilter._adopt(n, 0, hs=[C.c_void_p(out[j]) for out in per_rep]) for j in range(m)]
+        return self._with_counts(fs, lambda f, c: L.cph_filter_export(f._h, None, c))
+
+    @staticmethod
+    def _with_counts(fs, ask):
+        """Fills in `count` of filters the library just made; if that fails they are closed here, not by the collector."""
+        try:
+            for f in fs:
+                c = C.c_uint64(0)
+                _lib.check(ask(f, C.byref(c)))
+                f.count = c.value
+        except Exception:
+            for f in fs:
+                f.close()
+            raise
+        return fs
+
+    def time_label_filters(self, on=True):
+        """Debug hook of the measurement script: while on, every label pass is bracketed by HIP events
+        (last_label_filters_us).  Off by default."""
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_debug_time_label_filters(h, int(bool(on))))
+
+    def last_label_filters_us(self):
+        """Device time (HIP events, microseconds) of the last label_filters pass made under time_label_filters(): a
+        multi-device or partitioned index reports the longest of its replicas' / parts' passes."""
+        out = []
+        for h in self._replicas():
+            us = C.c_double(0)
+            _lib.check(_lib.lib().cph_debug_last_label_filters_us(h, C.byref(us)))
+            out.append(us.value)
+        return max(out)
+
+    def label_filter(self, lo, hi=None):
+        """IdFilter of the rows whose label is `lo`, or lies in [lo, hi] (both ends inclusive)."""
+        return self.label_filters([lo], None if hi is None else [hi])[0]
+
+    def _from_label(self, label, filter, filter_of, n):
+        """The `label=` argument of a search -> (filter, filter_of, [filters made here, closed by that call]).  A scalar:
+        one filter for the batch; an integer array [n] (n None: not allowed here): one label per query -- a filter per
+        distinct value, all made in one device pass, and the filter_of path."""
+        if filter is not None or filter_of is not None:
+            raise ValueError("label= and filter= exclude each other")
+        if not self.has_labels:
+            raise ValueError("label= needs a label column: call set_labels first")
+        a = self._as_labels(label, "label")
+        if a.ndim == 0:
+            f = self.label_filter(int(a))
+            return f, None, [f]
+        if n is None:
+            raise ValueError("this call takes one label (a label per query needs search_batch / search_batch_device)")
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"label must be one integer or a 1D integer array of length {n} (one entry per query)")
+        vals, inv = np.unique(a, return_inverse=True)
+        fs = self.label_filters(vals)
+        return fs, np.ascontiguousarray(inv.ravel(), np.int32), fs
+
     # -- search -----------------------------------------------------------------------------
-    def search(self, query, k=DEFAULT_K, filter=None, exact=False):
+    def search(self, query, k=DEFAULT_K, filter=None, exact=False, label=None):
         """Single query, unpadded rows.  With `filter` (an IdFilter or anything make_filter accepts) only allowed ids
         are returned; that query runs as a batch of one through the filtered batch path.  `exact`: as in search_batch
-        (a batch of one as well)."""
+        (a batch of one as well).  `label`: one label value, instead of filter=label_filter(label)."""
         q = _as_f32(query)
         if q.ndim != 1 or q.shape[0] != self._dim:
             raise ValueError("query must be 1D and match index dimension")
+        if label is not None:
+            filter, _, made = self._from_label(label, filter, None, None)
+            try:
+                return self.search(q, k, filter=filter, exact=exact)
+            finally:
+                made[0].close()
         kk = max(int(k), 1)
         if self._p is not None and filter is None and not exact:
             ids = np.empty(kk, np.int64)
@@ -358,7 +543,7 @@ class CPIndex:
                                          dist.ctypes.data, C.byref(m)))
         return ids[:m.value].copy(), dist[:m.value].copy()
 
-    def search_batch(self, queries, k=DEFAULT_K, filter=None, exact=False, filter_of=None):
+    def search_batch(self, queries, k=DEFAULT_K, filter=None, exact=False, filter_of=None, label=None):
         """Rows padded with -1 / FLT_MAX.  `filter`: restrict the results to allowed ids (see make_filter).
         `exact=True`: brute force instead of the graph search -- every row holds the k nearest allowed ids (without a
         filter: of the whole index), ascending by distance, equal distances by ascending internal id, no id twice;
@@ -366,10 +551,20 @@ class CPIndex:
         Per-query filters: `filter` = a sequence of filters and `filter_of` = an integer array [n] (host data): query i
         is searched under filter[filter_of[i]], unfiltered where filter_of[i] == -1, and row i holds the bytes of the
         single-filter call for that query and that filter.  Every query is routed on its own (padding, exact scan or
-        graph search, by the rules above); one call serves them all."""
+        graph search, by the rules above); one call serves them all.
+        `label` (needs set_labels; instead of filter=): one value = filter=label_filter(value); an integer array [n] =
+        one label per query -- the filters of the distinct values are made in one device pass and the batch runs as
+        with filter_of.  The filters live for this call only."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, filter_of, made = self._from_label(label, filter, filter_of, q.shape[0])
+            try:
+                return self.search_batch(q, k, filter=filter, exact=exact, filter_of=filter_of)
+            finally:
+                for f in made:
+                    f.close()
         n, k = q.shape[0], int(k)
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
@@ -427,7 +622,8 @@ class CPIndex:
                                                         dist.ctypes.data))
         return ids, dist
 
-    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None, exact=False, filter_of=None):
+    def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None, exact=False, filter_of=None,
+                            label=None):
         """Device-resident variant: `queries` is a float32 CUDA/HIP torch tensor (n, dim) on this
         index' device; returns (ids int64, dist float32) torch tensors on the same device.  The work
         is enqueued on `stream` (default: torch's current stream) and the call does not wait for it:
@@ -435,10 +631,19 @@ class CPIndex:
         search_batch (an IdFilter made here from a mask or ids is freed on return, which waits for the batch).
         A multi-device index runs the whole batch on one replica that lives on the queries' device (alternating
         between several there); the batch is not split.  `exact`: as in search_batch.  `filter_of` (with a sequence
-        of filters): per-query filters as in search_batch; it is host data here too, a numpy array or a list."""
+        of filters): per-query filters as in search_batch; it is host data here too, a numpy array or a list.
+        `label`: as in search_batch (host data; its filters are freed on return, which waits for the batch)."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, filter_of, made = self._from_label(label, filter, filter_of, queries.shape[0])
+            try:
+                return self.search_batch_device(queries, k, out=out, stream=stream, filter=filter, exact=exact,
+                                                filter_of=filter_of)
+            finally:
+                for f in made:
+                    f.close()
         n, k = queries.shape[0], int(k)
         rep = 0
         if self._p is not None:
@@ -543,7 +748,7 @@ class CPIndex:
                 raise ValueError("max_results must be >= 1")
         return r, (None if filter is None else self._filter(filter)), K
 
-    def range_search(self, queries, radius, filter=None, exact=True, max_results=None, filter_of=None):
+    def range_search(self, queries, radius, filter=None, exact=True, max_results=None, filter_of=None, label=None):
         """Every allowed id closer than `radius`: (lims int64 [n + 1], ids int64 [lims[n]], dist float32 [lims[n]]);
         query i owns ids[lims[i]:lims[i + 1]] and dist[...] (the FAISS layout, ids first as everywhere here).  `radius`: a
         scalar or a float array [n], compared as float32 against the squared-L2 values the searches return; an id is a
@@ -554,10 +759,17 @@ class CPIndex:
         same (internal-id) order.  exact=False needs max_results=K: segment i is row i of search_batch(queries, K,
         filter=filter) cut at the radius -- its entries with id >= 0 and dist < radius[i], in row order.
         A multi-device index shards the queries like search_batch(exact=True); the bytes are those of one device.
-        Per-query filters (filter_of) and a partitioned index are refused (use part(i).range_search)."""
+        Per-query filters (filter_of) and a partitioned index are refused (use part(i).range_search).
+        `label`: one label value, instead of filter=label_filter(label)."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, _, made = self._from_label(label, filter, filter_of, None)
+            try:
+                return self.range_search(q, radius, filter=filter, exact=exact, max_results=max_results)
+            finally:
+                made[0].close()
         n = q.shape[0]
         r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
         L = _lib.lib()
@@ -583,17 +795,25 @@ class CPIndex:
             destroy(obj)
         return lims, ids, dist
 
-    def range_search_device(self, queries, radius, filter=None, exact=True, max_results=None, stream=None, filter_of=None):
+    def range_search_device(self, queries, radius, filter=None, exact=True, max_results=None, stream=None, filter_of=None,
+                            label=None):
         """range_search on a float32 torch tensor (n, dim) on this index' device; returns (lims, ids, dist) with `lims`
         a CPU int64 tensor and ids / dist on the queries' device.  The kernels run on `stream` (default: torch's current
         stream), but unlike search_batch_device this call is NOT enqueue-only: the size of the output is data, so it
         waits once for the counts, allocates ids / dist, and waits for its own kernels before it returns -- the tensors
         are complete on return, and a filter may be closed right after the call.  `radius`: a scalar, an array, or a
         tensor (copied to the host).  A multi-device index runs the whole batch on one replica on the queries' device,
-        alternating like search_batch_device."""
+        alternating like search_batch_device.  `label`: as in range_search."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, _, made = self._from_label(label, filter, filter_of, None)
+            try:
+                return self.range_search_device(queries, radius, filter=filter, exact=exact, max_results=max_results,
+                                                stream=stream)
+            finally:
+                made[0].close()
         n = queries.shape[0]
         r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
         rep = 0

@@ -32,6 +32,7 @@
 #include "device_relayout.h"
 #include "device_rows.h"
 #include "device_tombstone.h"
+#include "device_labels.h"
 #include "device_exact.h"
 #include "device_range.h"
 #include "host_index.h"
@@ -181,7 +182,13 @@ struct cph_filter {
     // kEffCached entries; one is only freed after the device has drained (EffDeleter): a batch in flight may read it.
     mutable std::mutex eff_mu;
     mutable std::vector<std::pair<uint64_t, std::shared_ptr<cph_filter>>> eff;
-    ~cph_filter() { if (ids_ev) (void)hipEventDestroy(ids_ev); }
+    // a filter of cph_filters_from_labels: `words` is a view into the one allocation that holds the bitmaps of all the
+    // filters of that call, freed with the last of them
+    std::shared_ptr<DevBuf<uint32_t>> slab;
+    ~cph_filter() {
+        if (ids_ev) (void)hipEventDestroy(ids_ev);
+        if (slab) { words.p = nullptr; words.n = 0; }      // (not this filter's to free)
+    }
 };
 constexpr size_t kEffCached = 4;
 struct EffDeleter {
@@ -221,6 +228,15 @@ struct cph_index {
     DevBuf<uint32_t> d_rows;
     bool has_rows = false;
     bool ids_input = false;            // cph_set_result_ids: searches return input rows (needs has_rows)
+    // the label column (cph_set_labels): one int32 per internal id, resident next to the row map (host copy:
+    // host.labels; a replica without host arrays holds the device copy only), and the call buffers of
+    // cph_filters_from_labels ([lo | hi] and the counts), which only grow
+    DevBuf<int32_t> d_labels, d_label_bounds;
+    DevBuf<unsigned long long> d_label_counts;
+    bool has_labels = false;
+    // debug hook cph_debug_time_label_filters: only while label_timing is on is a label pass bracketed by the two events
+    hipEvent_t ev_label0 = nullptr, ev_label1 = nullptr;
+    bool label_timing = false, label_timed = false;
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
@@ -327,6 +343,18 @@ void sync_row_map(cph_index* h) {
     } else {
         h->d_rows.release();
         h->ids_input = false;
+    }
+}
+
+// After the host index changed: the device copy of its label column, or none (a load or a build leaves none).
+void sync_labels(cph_index* h) {
+    const std::vector<int32_t>& labels = h->host.labels;
+    h->has_labels = !labels.empty();
+    if (h->has_labels) {
+        h->d_labels.alloc(labels.size());
+        HIP_CHECK(hipMemcpy(h->d_labels.p, labels.data(), labels.size() * 4, hipMemcpyHostToDevice));
+    } else {
+        h->d_labels.release();
     }
 }
 
@@ -1450,7 +1478,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 104; }
+int cph_version(void) { return 105; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1516,6 +1544,8 @@ static void destroy_index(cph_index* h) {
     for (auto& x : g_tr) x = 0;
 #endif
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    if (h->ev_label0) (void)hipEventDestroy(h->ev_label0);
+    if (h->ev_label1) (void)hipEventDestroy(h->ev_label1);
     for (auto& ls : h->leaders) {
         if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
         if (ls.pin) (void)hipHostFree(ls.pin);
@@ -1554,6 +1584,7 @@ static void load_v2(cph_index* h, const char* path) {
     drop_host_state(h);
     upload_arrays(h);
     sync_row_map(h);                            // (a v2 file carries no row map)
+    sync_labels(h);                             // (no file carries labels)
     sync_removed(h);                            // (... and no removed rows)
     upload_feeders(h);
     h->finalized = true;
@@ -1640,6 +1671,7 @@ static void install_native(cph_index* h, NativeLoaded& in) {
     HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
     sync_row_map(h);
+    sync_labels(h);
     sync_removed(h);                            // the file's removed rows, or none
     upload_feeders(h);
     h->finalized = true;
@@ -1697,6 +1729,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     ++h->index_epoch;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     sync_row_map(h);
+    sync_labels(h);
     sync_removed(h);
     for (auto& s : h->sets) release_scratch(s);
     h->pending.assign(vectors, vectors + n * h->dim);
@@ -2641,6 +2674,176 @@ int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_
     });
 }
 
+}  // extern "C"
+
+// ---- label column and label filters ----------------------------------------------------------
+// One int32 per row on the handle (internal-id order, resident); cph_filters_from_labels turns it into ordinary
+// cph_filter objects, many per device pass (device_labels.h), so no search path learns anything new.
+namespace {
+
+// The caller holds the handle mutex.  labels: n == size entries in internal-id order, or null: the column goes.
+// keep_host: also as host.labels (what compact gathers from); a replica without host arrays keeps the device copy only.
+void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool keep_host) {
+    h->use_device();
+    if (!labels) {
+        std::vector<int32_t>().swap(h->host.labels);
+        sync_labels(h);
+        return;
+    }
+    h->d_labels.alloc(n);
+    HIP_CHECK(hipMemcpy(h->d_labels.p, labels, n * 4, hipMemcpyHostToDevice));
+    if (keep_host) h->host.labels.assign(labels, labels + n);
+    h->has_labels = true;
+}
+
+void require_labels_target(const cph_index* h, const int32_t* labels, uint64_t n) {
+    if (!h->finalized) throw InvalidArg("labels belong to a finalized index: finalize or load it first");
+    if (labels && n != h->host.n)
+        throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->host.n));
+}
+
+// cph_set_labels on a handle that keeps its host arrays: labels in internal ids, or in input rows (moved to internal
+// order on the host, through host.rows: labels_to_internal_host).
+void set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space) {
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_labels_target(h, labels, n);
+    if (!labels || space == CPH_IDS_INTERNAL) {
+        install_labels_locked(h, labels, n, true);
+        return;
+    }
+    if (!h->has_rows || h->host.rows.size() != n)
+        throw InvalidArg("the index has no row map (it was loaded from a v2 file): labels in input rows need cph_set_row_map");
+    std::vector<int32_t> internal(n);
+    labels_to_internal_host(labels, h->host.rows.data(), n, internal.data());
+    install_labels_locked(h, internal.data(), n, true);
+}
+
+// cph_filters_from_labels: out[m] all made, or none.
+void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (!h->has_labels) throw InvalidArg("the index has no label column: call cph_set_labels first");
+    if (m > kLabelMaxFilters) throw InvalidArg("at most " + std::to_string(kLabelMaxFilters) + " label filters per call");
+    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
+    h->use_device();
+    std::vector<std::unique_ptr<cph_filter>> made(m);
+    for (auto& f : made) f.reset(new cph_filter());
+    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
+    h->d_label_bounds.alloc((size_t)2 * m);
+    h->d_label_counts.alloc(m);
+    hipStream_t st = own_stream(h);
+    HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p, lo, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p + m, hi, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    h->label_timed = false;
+    if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label0, st));
+    label_filters(h->d_labels.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
+    if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label1, st));
+    std::vector<unsigned long long> counts(m);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_label_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
+    h->label_timed = h->label_timing;
+    for (uint32_t j = 0; j < m; ++j) {
+        cph_filter* f = made[j].get();
+        f->device = h->device;
+        f->n_bits = n;
+        f->popcount = counts[j];
+        f->slab = slab;
+        f->words.p = slab->p + (size_t)j * stride;
+        f->words.n = std::max<uint64_t>(nw, 1);
+    }
+    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_labels");
+        set_labels(h, labels, n, space);
+    });
+}
+
+int cph_has_labels(cph_index* h, int* flag) {
+    return guarded([&] {
+        if (!h || !flag) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *flag = h->finalized && h->has_labels ? 1 : 0;
+    });
+}
+
+int cph_get_labels(cph_index* h, uint64_t first, uint64_t count, int32_t* out) {
+    return guarded([&] {
+        if (!h || (!out && count != 0)) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        if (!h->has_labels) throw InvalidArg("the index has no label column");
+        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("label range out of bounds");
+        if (count == 0) return;
+        h->use_device();
+        HIP_CHECK(hipMemcpy(out, h->d_labels.p + first, count * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + m, nullptr);
+        if (!h || !lo || !hi) throw InvalidArg("null argument");
+        filters_from_labels(h, lo, hi, m, out);
+    });
+}
+
+int cph_debug_time_label_filters(cph_index* h, int on) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->use_device();
+        if (on && !h->ev_label0) HIP_CHECK(hipEventCreate(&h->ev_label0));
+        if (on && !h->ev_label1) HIP_CHECK(hipEventCreate(&h->ev_label1));
+        h->label_timing = on != 0;
+        h->label_timed = false;
+    });
+}
+
+int cph_debug_last_label_filters_us(cph_index* h, double* us) {
+    return guarded([&] {
+        if (!h || !us) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->label_timed) throw InvalidArg("no timed label pass has run on this handle (cph_debug_time_label_filters)");
+        h->use_device();
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, h->ev_label0, h->ev_label1));
+        *us = (double)ms * 1e3;
+    });
+}
+
+int cph_filter_export(const cph_filter* f, uint32_t* words, uint64_t* count) {
+    return guarded([&] {
+        if (!f) throw InvalidArg("null filter");
+        const uint64_t nw = (f->n_bits + 31) / 32;
+        if (count) *count = f->popcount;
+        if (!words || nw == 0) return;               // (the count alone: no device call)
+        HIP_CHECK(hipSetDevice(f->device));
+        HIP_CHECK(hipMemcpy(words, f->words.p, nw * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo, const int32_t* hi, uint32_t m, uint32_t* words_out,
+                           uint64_t* counts_out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if ((n != 0 && (!labels || !words_out)) || !lo || !hi || !counts_out) throw InvalidArg("null argument");
+        if (n > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+        label_filters_host(labels, n, lo, hi, m, words_out, counts_out);
+    });
+}
+
 // One launch for up to kLeaderGroup single-query callers with the same k: queries gathered into the leader slot's
 // pinned, device-mapped buffer, the copy-free small-batch path on the slot's own stream.  The handle mutex is held while
 // the launch is ENQUEUED, not while it runs: the next leader's launch (other slot, other stream, its own batch set)
@@ -3230,6 +3433,9 @@ void replicate(cph_index* src, cph_index* dst) {
     else dst->d_rows.release();
     dst->has_rows = src->has_rows;
     dst->ids_input = dst->ids_input && dst->has_rows;
+    if (src->has_labels) copy(dst->d_labels, src->d_labels);     // (compact carries the column; a load or finalize has none)
+    else dst->d_labels.release();
+    dst->has_labels = src->has_labels;
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
     copy(dst->d_row_of, src->d_row_of);
@@ -3414,6 +3620,7 @@ int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n) {
             h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
             h->host = HostIndex();
             sync_row_map(h);
+            sync_labels(h);
             sync_removed(h);
         }
     });
@@ -4338,8 +4545,10 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
 
 // The live vectors of a finalized handle in input-row order (internal-id order without a row map), appended to `vecs`
 // (dim floats each); map[i] (the caller's, `n` entries from map_first on) = first_new + rank of the live row, -1 for a
-// removed one, indexed by input row (by_row) or by internal id.  Returns the number of live rows.
-uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new) {
+// removed one, indexed by input row (by_row) or by internal id.  labs (may be null): the live rows' labels, appended in
+// the same order, when the handle has a label column.  Returns the number of live rows.
+uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new,
+                     std::vector<int32_t>* labs = nullptr) {
     const HostIndex& hi = h->host;
     const uint64_t n = hi.n;
     const bool rows = h->has_rows && hi.rows.size() == n;
@@ -4353,6 +4562,7 @@ uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool 
         map[by_row ? r : id] = gone ? -1 : first_new + (int64_t)live;
         if (gone) continue;
         vecs.insert(vecs.end(), hi.vec(id), hi.vec(id) + hi.dim);
+        if (labs && hi.labels.size() == n) labs->push_back(hi.labels[id]);
         ++live;
     }
     return live;
@@ -4363,6 +4573,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     if (!old_to_new) throw InvalidArg("null argument");
     refuse_host_less(h, "cph_compact");
     std::vector<float> vecs;
+    std::vector<int32_t> labs;                   // the live rows' labels, in the order of the new input rows
     uint64_t live = 0;
     bool was_input = false;
     {
@@ -4375,13 +4586,14 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
         was_input = h->ids_input;
         vecs.reserve(live * h->dim);
         std::vector<int64_t> map(h->host.n);
-        gather_live(h, vecs, map.data(), was_input, 0);
+        gather_live(h, vecs, map.data(), was_input, 0, &labs);
         std::copy(map.begin(), map.end(), old_to_new);
     }
     build_pending(h, vecs.data(), live);
     std::vector<float>().swap(vecs);
     finalize_build(h);
     if (was_input) set_result_ids(h, CPH_IDS_INPUT);
+    if (labs.size() == live) set_labels(h, labs.data(), live, CPH_IDS_INPUT);     // new input row j: the label of the live row it came from
 }
 
 }  // namespace
@@ -4522,6 +4734,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
     return guarded([&] {
         if (!m || !old_to_new) throw InvalidArg("null argument");
         std::vector<float> vecs;
+        std::vector<int32_t> labs;                // the live rows' labels in global row order (every part has a column, or none)
         uint64_t live = 0;
         {
             std::unique_lock<std::shared_mutex> lk(m->life);
@@ -4531,7 +4744,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
             for (uint32_t p = 0; p < P; ++p) {
                 cph_index* h = m->parts[p];
                 std::lock_guard<std::mutex> g(h->mu);
-                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live);
+                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live, &labs);
             }
             if (live < kMinPartRows * P)      // cph_parts_build's own refusal, before any part gives up its index
                 throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
@@ -4541,6 +4754,90 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
         check_rc(cph_parts_build(m, vecs.data(), live));      // the live rows, cut again by cph_host_part_bounds
         std::vector<float>().swap(vecs);
         check_rc(cph_parts_finalize(m));
+        if (labs.size() == live) check_rc(cph_parts_set_labels(m, labs.data(), live));     // cut again at the new bounds
+    });
+}
+
+// ---- label column of replicas and parts ----
+int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int space) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
+        cph_index* r0 = m->reps[0];
+        for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
+            std::lock_guard<std::mutex> g(h->mu);
+            require_labels_target(h, labels, n);
+        }
+        set_labels(r0, labels, n, space);                    // validates the rest, and moves input rows to internal order once
+        try {
+            for (size_t i = 1; i < m->reps.size(); ++i) {
+                cph_index* h = m->reps[i];
+                std::lock_guard<std::mutex> g(h->mu);
+                install_labels_locked(h, labels ? r0->host.labels.data() : nullptr, n, false);
+            }
+        } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
+            for (cph_index* h : m->reps) {
+                std::lock_guard<std::mutex> g(h->mu);
+                try { install_labels_locked(h, nullptr, 0, false); } catch (...) {}
+            }
+            throw;
+        }
+    });
+}
+
+int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw InvalidArg("labels belong to a finalized index: finalize or load it first");
+        if (labels && n != m->bounds.back())
+            throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(m->bounds.back()));
+        for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
+            std::lock_guard<std::mutex> g(h->mu);
+            if (labels && (!h->has_rows || h->host.rows.size() != h->host.n))
+                throw InvalidArg("a part has no row map: labels of a partitioned index are given in input rows");
+        }
+        try {
+            for (size_t p = 0; p < m->parts.size(); ++p)     // global input rows, cut at the part bounds
+                set_labels(m->parts[p], labels ? labels + m->bounds[p] : nullptr, m->bounds[p + 1] - m->bounds[p], CPH_IDS_INPUT);
+        } catch (...) {                                      // (a device failure: no part keeps a column the others lack)
+            for (cph_index* h : m->parts) {
+                std::lock_guard<std::mutex> g(h->mu);
+                try { install_labels_locked(h, nullptr, 0, true); } catch (...) {}
+            }
+            throw;
+        }
+    });
+}
+
+int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] {
+        if (cnt == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + cnt, nullptr);
+        if (!m || !lo || !hi) throw InvalidArg("null argument");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
+        for (auto& f : made) {
+            f.reset(new cph_parts_filter());
+            f->n_bits = m->bounds.back();
+            f->f.reserve(m->parts.size());
+        }
+        std::vector<cph_filter*> slice(cnt);
+        for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
+            filters_from_labels(m->parts[p], lo, hi, cnt, slice.data());
+            for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
+        }
+        for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
+    });
+}
+
+int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
+    return guarded([&] {
+        if (!f || !count) throw InvalidArg("null argument");
+        *count = 0;
+        for (const cph_filter* x : f->f) *count += x->popcount;
     });
 }
 

@@ -192,6 +192,32 @@ inline uint64_t live_filter_host(const uint32_t* allow, const uint32_t* removed,
     return c;
 }
 
+// The host statement of the label filters (cph_filters_from_labels; device_labels.h): bit i of filter j = lo[j] <=
+// labels[i] <= hi[j] (signed, both ends inclusive; lo[j] > hi[j]: the empty filter).  out: m bitmaps of (n + 31) / 32
+// words each, one behind the other, every word written and the bits of the last word behind n clear; counts[j] = ids
+// allowed by filter j.
+inline void label_filters_host(const int32_t* labels, size_t n, const int32_t* lo, const int32_t* hi, size_t m, uint32_t* out,
+                               uint64_t* counts) {
+    const size_t nw = (n + 31) / 32;
+    for (size_t j = 0; j < m; ++j) {
+        uint32_t* w = out + j * nw;
+        uint64_t c = 0;
+        for (size_t k = 0; k < nw; ++k) w[k] = 0u;
+        for (size_t i = 0; i < n; ++i)
+            if (labels[i] >= lo[j] && labels[i] <= hi[j]) {
+                w[i >> 5] |= 1u << (i & 31);
+                ++c;
+            }
+        counts[j] = c;
+    }
+}
+
+// Labels given per input row -> the label column in internal-id order (cph_set_labels with CPH_IDS_INPUT): out[i] =
+// by_row[rows[i]] for the n internal ids; rows is a row map (every entry < n).
+inline void labels_to_internal_host(const int32_t* by_row, const uint32_t* rows, size_t n, int32_t* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = by_row[rows[i]];
+}
+
 struct HostIndex {
     size_t D = 0, bw = 0, dim = 0, n = 0;
     int32_t max_level = 0;
@@ -215,6 +241,8 @@ struct HostIndex {
     // empty = none (n_removed = 0).  Only a native file carries them; save() refuses an index that has some.
     std::vector<uint32_t> removed;
     uint64_t n_removed = 0;
+    // The label column (cph_set_labels): labels[i] = label of internal id i; empty = none.  No file carries it.
+    std::vector<int32_t> labels;
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

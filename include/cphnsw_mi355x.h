@@ -319,6 +319,64 @@ int cph_live_count(cph_index* h, uint64_t* n);
 int cph_get_removed(cph_index* h, uint32_t* words);
 int cph_compact(cph_index* h, int64_t* old_to_new);
 
+/* ---- added rows: the tail ---------------------------------------------------------------- */
+/* A finalized handle holds n_b BASE rows, the rows of its graph, and behind them t >= 0 TAIL rows (cph_add): a flat
+ * segment of fp32 rows that no graph, block or code knows of.  size = n_b + t; tail row j has id n_b + j in internal ids
+ * AND in input rows (it is its own input row: the row map is extended by the identity).  With t == 0 nothing changes:
+ * launches, results, statistics and the bytes of cph_save_native are those of a handle that never heard of cph_add.
+ *
+ * cph_add      vectors[m][dim]: host array; labels[m]: required iff the handle has a label column, else NULL.
+ *              *first_id (may be NULL) = id of the first new row = size before the call; the rows get consecutive ids.
+ *              Holds the handle mutex, waits for everything enqueued on the handle (like cph_remove), uploads the rows
+ *              and runs one device pass (csrc/device_tail.h: tail_append_kernel) that zero-pads each row, writes its
+ *              norm with the builder's arithmetic (the same floats get the norm bits cph_build gives them), extends the
+ *              row map, the label column and the removed bitmap (clear bits).  The resident arrays grow amortised (half
+ *              as much again, a device-to-device copy).  With removed rows present the handle takes a new state of R:
+ *              filters cached F & ~R again at their next use.  m == 0 is a no-op.  CPH_INVALID_ARGUMENT: not finalized,
+ *              NULL vectors, labels given without a column or missing with one, size + m >= 2^32 - 1, a borrowed
+ *              replica or part handle (like cph_set_row_map).  cph_multi_* and cph_parts_* have no add.
+ * cph_tail_count  *t; cph_size returns n_b + t.
+ * ids          every call that names ids ranges over size: cph_remove, cph_get_removed, cph_live_count, cph_get_row_map,
+ *              cph_get_labels, cph_set_labels, cph_get_vectors, cph_exact_l2, cph_filters_from_labels.  A filter's n_bits
+ *              must equal the size, so a filter made before an add is refused afterwards; bit n_b + j speaks of tail row
+ *              j in cph_filter_create and in cph_filter_create_rows.  cph_fastscan_block and cph_export_blocks name
+ *              vertices of the graph: ids < n_b only.
+ * exact routes cph_search_batch_exact*, the exact threshold (compared with the allowed count over ALL ids), the exact
+ *              cph_range_search_* and the scanned queries of cph_search_batch_filters*: the tail rows are more
+ *              candidates, nothing else changes; the order is (distance bits, internal id), tail ids are the largest.
+ * graph route  cph_search_batch[_device][_filtered], cph_search and the exact == 0 range search through them: row i is
+ *              the first k entries of the stable merge of G_i then T_i.  G_i: the row the same call returns on the same
+ *              handle before any add, under the effective filter restricted to the base rows (bytes, duplicates and
+ *              padding included; already in input rows under CPH_IDS_INPUT).  T_i: the exact top-k of the allowed tail
+ *              rows, ascending by (distance bits, id), distances with the bits of cph_exact_l2.  Entries are compared as
+ *              float values, the graph entry first where they are equal, padding last -- numpy:
+ *              argsort(concatenate([G_i, T_i]), kind="stable")[:k].  The graph launch is the one a handle without a tail
+ *              makes (same instantiation, probe first included; same counters; same cph_last_query_expansions);
+ *              cph_last_search_stats [1] grows by n x t (the scan evaluates every tail row and masks by the filter) and
+ *              [6] covers all launches.  Tail rows are found exactly: recall does not fall as the tail grows, time does.
+ *              A filter that allows nothing launches nothing, tail included.  cph_search runs as a batch of one (not
+ *              coalesced), as on a handle with removed rows.  The _device forms still only enqueue.
+ * refused      while t > 0, each message naming cph_compact: cph_save and cph_save_native (CPH_RUNTIME_ERROR: no file
+ *              format carries a tail), cph_set_row_map (CPH_INVALID_ARGUMENT), graph-routed calls with k > 1024
+ *              (CPH_INVALID_ARGUMENT: the scan's limit), cph_search_batch_filters[_device] when a query would take the
+ *              graph route (CPH_NOT_IMPLEMENTED; fine when every query is scanned or padded).
+ * the tail ends  with cph_build, cph_load, cph_load_native and cph_compact.  cph_compact rebuilds from the live rows, the
+ *              tail included: base rows in input-row order, then tail rows in id order; old_to_new[old size]; labels
+ *              carried over; afterwards t == 0. */
+int cph_add(cph_index* h, const float* vectors, uint64_t m, const int32_t* labels, int64_t* first_id);
+int cph_tail_count(cph_index* h, uint64_t* t);
+/* Test hook: tail_fold_kernel on given rows (host arrays).  g_ids / g_dist [n][k]: graph rows, ascending in distance,
+ * padding (-1 / FLT_MAX) last; pools[P][n][C]: keys (distance bits << 32 | id), each list ascending; counts[P][n], each
+ * <= k: the lists as the tail scan leaves them.  C: a power of two, 128 <= C, 2 k <= C; k <= 1024; P <= 256.  The rows are
+ * uploaded and folded in place, as the library does, then copied to out_ids / out_dist [n][k].  cph_host_tail_fold is
+ * the host statement (no HIP call); cph_host_tail_capacity: *out = rows the resident arrays hold room for once `need`
+ * rows no longer fit into `capacity` (csrc/host_tail.h). */
+int cph_tail_fold_hook(int device, const int64_t* g_ids, const float* g_dist, uint64_t n, uint64_t k, const uint64_t* pools,
+                       const uint32_t* counts, uint32_t P, uint32_t C, int64_t* out_ids, float* out_dist);
+int cph_host_tail_fold(const int64_t* g_ids, const float* g_dist, uint64_t n, uint64_t k, const uint64_t* pools,
+                       const uint32_t* counts, uint32_t P, uint32_t C, int64_t* out_ids, float* out_dist);
+int cph_host_tail_capacity(uint64_t capacity, uint64_t need, uint64_t* out);
+
 /* ---- label column and label filters ------------------------------------------------------- */
 /* A finalized handle may carry one int32 label per row (a tenant, a category, a day), resident on its device in
  * internal-id order (4 B per vertex, next to the row map), so that "rows whose label is t" becomes a filter without a

@@ -83,6 +83,13 @@ SYMBOLS = {
     "cph_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cph_compact": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cph_host_live_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "cph_tail_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_tail_fold_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cph_host_tail_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p]),
+    "cph_host_tail_capacity": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cph_multi_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "cph_multi_live_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_multi_get_removed": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -922,7 +922,9 @@ class CPIndex:
         """Rebuilds the index from the rows that are left (build + finalize of the live vectors in input-row order;
         internal-id order if the index has no row map).  Returns int64[old size]: the new input row of every old id, in
         the space remove() defaults to (result_ids), -1 for removed ids.  Afterwards size == live_count, nothing is
-        removed, the index has a fresh row map and result_ids is kept.  A partitioned index is cut into parts again."""
+        removed, the index has a fresh row map and result_ids is kept.  A partitioned index is cut into parts again.
+        Rows added with add() are folded into the new graph: they follow the base rows, in id order, and tail_size is 0
+        afterwards."""
         out = np.empty(self.size, np.int64)
         if self._p is not None:
             _lib.check(_lib.lib().cph_parts_compact(self._p, out.ctypes.data))
@@ -931,6 +933,41 @@ class CPIndex:
         else:
             _lib.check(_lib.lib().cph_compact(self._h, out.ctypes.data))
         return out
+
+    # -- added rows (not in the reference) -----------------------------------------------------
+    def add(self, vectors, labels=None):
+        """Appends rows to the finalized index without a rebuild; returns their ids as int64, arange(size before, size
+        after): the same numbers in internal ids and in input rows.  `labels`: one int per row, required exactly when
+        the index has a label column.  The rows form a tail behind the graph: every exact path sees them as more
+        candidates, a graph-routed search scans them exactly and folds them into the graph's rows (ascending distance,
+        the graph's entry first where two are equal), so they are always found and a search slows down as the tail
+        grows -- compact() folds the tail into a new graph.  Filters made before the call no longer fit (size changed).
+        While tail_size > 0: save, save_native and set_row_map raise (compact() first), graph-routed searches take
+        k <= 1024, and per-query filters serve scanned queries only (NotImplementedError otherwise).  Waits for the
+        batches in flight.  Not available on devices=[...] indexes, their replicas or parts."""
+        if self._m is not None or self._p is not None or self._owner is not None:
+            raise NotImplementedError("add is not available on a multi-device or partitioned index, its replicas or parts")
+        v = _as_f32(vectors)
+        if v.ndim != 2 or v.shape[1] != self._dim:
+            raise ValueError("vectors must be a (m, dim) float32 array")
+        lab = None
+        if labels is not None:
+            lab = self._as_labels(labels, "labels")
+            if lab.ndim != 1 or lab.shape[0] != v.shape[0]:
+                raise ValueError(f"labels must hold one entry per added row ({v.shape[0]})")
+        first = C.c_int64(0)
+        _lib.check(_lib.lib().cph_add(self._h, v.ctypes.data if v.size else None, v.shape[0],
+                                      lab.ctypes.data if lab is not None and lab.size else None, C.byref(first)))
+        return np.arange(first.value, first.value + v.shape[0], dtype=np.int64)
+
+    @property
+    def tail_size(self):
+        """Rows added since the index was built, loaded or compacted (size counts them)."""
+        if self._m is not None or self._p is not None:
+            return 0
+        t = C.c_uint64(0)
+        _lib.check(_lib.lib().cph_tail_count(self._h, C.byref(t)))
+        return t.value
 
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):

@@ -35,6 +35,7 @@
 #include "device_labels.h"
 #include "device_exact.h"
 #include "device_range.h"
+#include "device_tail.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -58,6 +59,9 @@ int fail(int code, const std::string& msg) {
 struct InvalidArg : std::invalid_argument {
     using std::invalid_argument::invalid_argument;
 };
+struct NotImplemented : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
 
 template <class F>
 int guarded(F&& f) {
@@ -68,6 +72,8 @@ int guarded(F&& f) {
         return fail(CPH_INVALID_ARGUMENT, e.what());
     } catch (const std::bad_alloc&) {
         return fail(CPH_OUT_OF_MEMORY, "out of memory");
+    } catch (const NotImplemented& e) {
+        return fail(CPH_NOT_IMPLEMENTED, e.what());
     } catch (const std::exception& e) {
         return fail(CPH_RUNTIME_ERROR, e.what());
     }
@@ -247,6 +253,14 @@ struct cph_index {
     uint64_t rm_epoch = 0;
     std::shared_ptr<cph_filter> live;
     std::atomic<bool> tombstones{false};
+    // the tail (cph_add; device_tail.h): host.n / L stay the rows of the graph, `tail` rows live behind them at index
+    // host.n + j of d_raw, d_norm, d_rows, d_labels and d_removed, which then hold room for more rows than they carry
+    // (tail_capacity).  tail_vecs: their host copy ([tail][dim], what cph_get_vectors and cph_compact read); host.labels
+    // and host.removed cover the tail too, host.rows does not (a tail row is its own input row).  has_tail: tail != 0,
+    // readable without the mutex.
+    uint64_t tail = 0;
+    std::vector<float> tail_vecs;
+    std::atomic<bool> has_tail{false};
     // per-query feeders on the device: rotation signs + upper layers (CSR)
     DevBuf<float> d_signs;
     DevBuf<uint32_t> d_upper;          // all layers' nodes | offsets | nbrs, concatenated
@@ -290,6 +304,7 @@ struct cph_index {
     } leaders[kLeaderSlots];
 
     void use_device() const { HIP_CHECK(hipSetDevice(device)); }
+    uint64_t size() const { return host.n + tail; }         // ids a result, a filter or a label may name
 };
 
 namespace {
@@ -330,6 +345,9 @@ void drop_host_state(cph_index* h) {
     h->native_map.reset();
     h->own_view = nullptr;
     std::vector<uint8_t>().swap(h->own_store);
+    h->tail = 0;                                  // a load or a build ends the tail
+    std::vector<float>().swap(h->tail_vecs);
+    h->has_tail.store(false);
 }
 
 // After the host index changed: the device copy of its row map, or none -- and without a map the handle returns
@@ -363,7 +381,7 @@ hipStream_t own_stream(cph_index* h);
 // F & ~R (allow null: ~R) of this handle as a filter of its own, made on the handle's stream and complete on return: the
 // count is needed on the host, for the routing.
 std::shared_ptr<cph_filter> make_live_filter(cph_index* h, const uint32_t* d_allow) {
-    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    const uint64_t n = h->size(), nw = (n + 31) / 32;
     std::shared_ptr<cph_filter> e(new cph_filter(), EffDeleter());
     e->device = h->device;
     e->n_bits = n;
@@ -392,7 +410,7 @@ void sync_removed(cph_index* h) {
     }
     h->tombstones.store(true);                  // (before the device work: a failure must not bring the rows back;
                                                 //  effective_filter makes `live` when it is missing)
-    const uint64_t nw = (hi.n + 31) / 32;
+    const uint64_t nw = (h->size() + 31) / 32;
     h->d_removed.alloc(nw);
     HIP_CHECK(hipMemcpy(h->d_removed.p, hi.removed.data(), nw * 4, hipMemcpyHostToDevice));
     h->live = make_live_filter(h, nullptr);
@@ -414,6 +432,11 @@ std::shared_ptr<const cph_filter> effective_filter(cph_index* h, const cph_filte
     std::shared_ptr<cph_filter> e = make_live_filter(h, f->words.p);
     f->eff.emplace_back(h->rm_epoch, e);
     return e;
+}
+
+// The stored vector (dim floats) of internal id `id` < size: a base row from the host index, a tail row from its host copy.
+const float* row_vec(const cph_index* h, uint64_t id) {
+    return id < h->host.n ? h->host.vec(id) : h->tail_vecs.data() + (id - h->host.n) * h->dim;
 }
 
 void require_finalized(cph_index* h) {
@@ -887,13 +910,81 @@ bool size_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, hipStream_t
     return ordered;
 }
 
+// ---- the tail of a graph-routed batch (device_tail.h) ---------------------------------------------------------------------
+// What every graph-routed entry refuses on a handle with a tail, before it touches the device.
+void require_tail_k(const cph_index* h, uint64_t k) {
+    if (h->tail && k > kExactMaxK)
+        throw InvalidArg("the index holds " + std::to_string(h->tail) + " added rows, which a search scans exactly: k <= " +
+                         std::to_string(kExactMaxK) + " (got k = " + std::to_string(k) + "); compact() the index first");
+}
+
+// First half, enqueued BEFORE the graph launch: the batch's padded queries and their norms (d_raw_q: [nq][dim] raw
+// queries the device can read).  exact_pad_kernel STORES the scan's evaluation count -- every tail row against every
+// query -- into the statistics word the graph launch then ADDS its own to.
+ExactPlan tail_begin(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, hipStream_t st) {
+    const uint32_t D = h->L.D;
+    const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT;
+    const ExactPlan pl = plan_exact(h->tail, nq, k, h->num_cus, h->exact_scratch_bytes);
+    if (s.x_qpad.n < (size_t)nq_pad * D || s.x_qnorm.n < nq_pad || s.x_pools.n < pl.pool_keys || s.x_counts.n < (size_t)pl.P * pl.tile_q) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
+        s.x_qpad.alloc((size_t)nq_pad * D);
+        s.x_qnorm.alloc(nq_pad);
+        s.x_pools.alloc(pl.pool_keys);
+        s.x_counts.alloc((size_t)pl.P * pl.tile_q);
+    }
+    hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q, nq,
+                       nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * h->tail);
+    HIP_CHECK(hipGetLastError());
+    return pl;
+}
+
+// Second half, behind the graph launches: scan the tail under the batch's effective filter (d_allow null: every id) and
+// fold the lists into the graph's rows, in place.  Nothing waits for the device.
+void tail_finish(cph_index* h, BatchSet& s, const ExactPlan& pl, uint32_t nq, uint32_t k, const uint32_t* d_allow, int64_t* d_ids,
+                 float* d_dist, uint32_t* d_count, DoneFlags done, hipStream_t st) {
+    TailScanArgs a{};
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.allow = d_allow;
+    a.base = (uint32_t)h->host.n;
+    a.t = (uint32_t)h->tail;
+    a.D = h->L.D;
+    a.qpad = s.x_qpad.p;
+    a.qnorm = s.x_qnorm.p;
+    a.gq = pl.gq;
+    a.part = pl.part;
+    a.k = k;
+    a.C = pl.C;
+    a.pools = s.x_pools.p;
+    a.counts = s.x_counts.p;
+    TailFoldArgs f{};
+    f.pools = s.x_pools.p;
+    f.counts = s.x_counts.p;
+    f.P = pl.P;
+    f.k = k;
+    f.C = pl.C;
+    f.ids = d_ids;
+    f.dist = d_dist;
+    f.out_count = d_count;
+    f.done_flags = done.flags;
+    f.done_seq = done.seq;
+    for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile_q) {
+        a.q_first = f.q_first = q0;
+        a.q_count = f.q_count = std::min(pl.tile_q, nq - q0);
+        launch_tail_scan(a.D, dim3(pl.P, (a.q_count + pl.gq - 1) / pl.gq), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+        tail_fold(f, st);
+    }
+}
+
 // Core: queries already staged in the set; results into device buffers.  Everything is enqueued on
 // `st` and nothing waits for the device: a query that outgrows its scratch is answered by the
 // full-capacity re-run launch that always follows the main one (it finds an empty list otherwise).
 // `filter` (null: unfiltered) restricts the result heap to its allowed ids; with no id allowed nothing is launched.
+// On a handle with a tail the graph launches are the ones a handle without it makes; around them the tail's scan and
+// fold (tail_begin / tail_finish), which need d_raw_q, the batch's raw queries.
 void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* d_ids, float* d_dist,
                     hipStream_t st, uint32_t* d_count_out = nullptr, DoneFlags done = DoneFlags(),
-                    const cph_filter* filter = nullptr) {
+                    const cph_filter* filter = nullptr, const float* d_raw_q = nullptr) {
     const uint64_t n = h->host.n;
     if (s.d_count.n < nq) {
         if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
@@ -931,17 +1022,25 @@ void enqueue_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t*
     }
     uint32_t* d_count = d_count_out ? d_count_out : s.d_count.p;
     HIP_CHECK(hipEventRecord(s.ev0, st));
+    const bool tail = h->tail != 0;
+    ExactPlan tail_plan{};
+    if (tail) {
+        if (!d_raw_q) throw std::runtime_error("a search of an index with added rows needs the raw queries");
+        tail_plan = tail_begin(h, s, d_raw_q, nq, k, st);
+    }
+    const DoneFlags graph_done = tail ? DoneFlags() : done;      // (with a tail a row is final only after the fold)
     // (a filtered batch does not probe first: its re-run launch exists for capacity overflows only)
     const bool rerun = s.cap < n + 1 || (d_allow == nullptr && probe_first(h));
     if (rerun && nq <= s.r_slots && !h->want_cap && !h->want_slots) {   // (explicit search params keep the general path)
         // a handful of queries: straight onto the full-capacity slots -- one launch, nothing can overflow
         s.run_slots = nq;
         s.run_cap = n + 1;
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Direct, st, done, d_allow);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Direct, st, graph_done, d_allow);
     } else {
-        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, Launch::Main, st, done, d_allow);
-        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Rerun, st, done, d_allow);
+        launch_search(h, s, nq, k, d_ids, d_dist, d_count, d_order, Launch::Main, st, graph_done, d_allow);
+        if (rerun) launch_search(h, s, nq, k, d_ids, d_dist, d_count, nullptr, Launch::Rerun, st, graph_done, d_allow);
     }
+    if (tail) tail_finish(h, s, tail_plan, nq, k, d_allow, d_ids, d_dist, d_count, done, st);
     finish_batch(h, s, st);
 }
 
@@ -985,8 +1084,8 @@ bool grow_pinned(uint8_t*& host, uint8_t*& dev, size_t& bytes, size_t need) {
 
 void check_filter(const cph_index* h, const cph_filter* f) {
     if (f->device != h->device) throw InvalidArg("filter belongs to another device");
-    if (f->n_bits != h->host.n)
-        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " ids, the index holds " + std::to_string(h->host.n));
+    if (f->n_bits != h->size())
+        throw InvalidArg("filter covers " + std::to_string(f->n_bits) + " ids, the index holds " + std::to_string(h->size()));
 }
 
 // What every batch entry checks, under the handle mutex, before it touches the device; false: nothing to do ((n, 0)
@@ -1023,7 +1122,7 @@ const uint32_t* filter_id_list(const cph_filter* f, hipStream_t st) {
 // device buffers, everything enqueued on `st`.  The candidates are the filter's ids (not empty), or every id.
 void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
                    int64_t* d_ids, float* d_dist, hipStream_t st) {
-    const uint64_t n = h->host.n, m = filter ? filter->popcount : n;
+    const uint64_t n = h->size(), m = filter ? filter->popcount : n;     // (the tail rows: more candidates)
     const uint32_t D = h->L.D;
     const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT;
     const ExactPlan pl = plan_exact(m, nq, k, h->num_cus, h->exact_scratch_bytes);
@@ -1095,6 +1194,7 @@ void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t 
     const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
     f = eff.get();
     exact = takes_exact(h, f, k, exact);
+    if (!exact) require_tail_k(h, k);
     hipStream_t st = own_stream(h);
     BatchSet& s = next_set(h, st);
     if (exact) {
@@ -1120,19 +1220,20 @@ void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t 
         std::memcpy(io.queries(s.pin_io), queries, n * h->dim * sizeof(float));
         stage_queries(h, s, io.queries(s.pin_io_dev), n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
-                       DoneFlags(), f);
+                       DoneFlags(), f, io.queries(s.pin_io_dev));
         HIP_CHECK(hipStreamSynchronize(st));
         std::memcpy(ids, io.ids(s.pin_io), n * k * 8);
         std::memcpy(dist, io.dist(s.pin_io), n * k * 4);
         return;
     }
-    if (!empty) stage_queries(h, s, upload_queries(h, s, queries, n, st), n, st);
+    const float* d_q = empty ? nullptr : upload_queries(h, s, queries, n, st);
+    if (!empty) stage_queries(h, s, d_q, n, st);
     if (s.d_ids.n < n * k) {
         if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
         s.d_ids.alloc(n * k);
         s.d_dist.alloc(n * k);
     }
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f);
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f, d_q);
     HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
@@ -1148,6 +1249,7 @@ void search_batch_device_locked(cph_index* h, const float* d_queries, uint64_t n
     const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
     f = eff.get();
     exact = takes_exact(h, f, k, exact);
+    if (!exact) require_tail_k(h, k);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchSet& s = next_set(h, st);
     if (exact) {
@@ -1155,7 +1257,7 @@ void search_batch_device_locked(cph_index* h, const float* d_queries, uint64_t n
         return;
     }
     if (!(f && f->popcount == 0)) stage_queries(h, s, d_queries, n, st);
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f);
+    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f, d_queries);
 }
 
 void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
@@ -1184,6 +1286,12 @@ FilterGroups group_filters(const cph_index* h, const cph_filter* const* filters,
     g.perm.resize(n);
     g.seg.resize(F + 2);
     filter_groups(filter_of, n, g.pop.data(), F, k, exact, h->exact_threshold, g.route.data(), g.perm.data(), g.seg.data());
+    if (h->tail)
+        for (uint32_t f = 0; f <= F; ++f)
+            if (g.route[f] == kRouteGraph && g.seg[f + 1] != g.seg[f])
+                throw NotImplemented("per-query filters on an index with added rows serve the scanned queries only (exact, or every "
+                                     "filter at or below the exact threshold): a query of this batch would walk the graph; "
+                                     "compact() the index first");
     return g;
 }
 
@@ -1258,7 +1366,7 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
         else if (g.route[f] == kRouteGraph) (f < F ? n_gf : n_gp) += cnt;
         else {
             seg_group.push_back(f);
-            seg_m.push_back(f < F ? g.pop[f] : n);
+            seg_m.push_back(f < F ? g.pop[f] : h->size());
             seg_q.push_back(cnt);
             seg_first.push_back(nqs);
             nqs += cnt;
@@ -1478,7 +1586,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 105; }
+int cph_version(void) { return 106; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1575,6 +1683,13 @@ static void begin_device_swap(cph_index* h) {
     ++h->index_epoch;
 }
 
+// No file format carries a tail: a file written now would lose the added rows.
+static void refuse_tail_file(const cph_index* h) {
+    if (h->tail)
+        throw std::runtime_error("No file format carries added rows (" + std::to_string(h->tail) +
+                                 " here) and a file without them would lose them: compact() the index first.");
+}
+
 static void load_v2(cph_index* h, const char* path) {
     std::lock_guard<std::mutex> lk(h->mu);
     HostIndex t;
@@ -1609,6 +1724,7 @@ int cph_save(cph_index* h, const char* path) {
         if (h->host.n_removed != 0)
             throw std::runtime_error("The reference format cannot carry removed rows (" + std::to_string(h->host.n_removed) +
                                      " here) and a file without them would bring them back: compact() the index first, or use save_native.");
+        refuse_tail_file(h);
         materialize_search_data(h);
         h->host.save(path);
     });
@@ -1620,6 +1736,7 @@ int cph_save_native(cph_index* h, const char* path) {
         refuse_host_less(h, "cph_save_native");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized before saving.");
+        refuse_tail_file(h);
         h->use_device();
         quiesce(h);
         const HostIndex& hi = h->host;
@@ -1694,7 +1811,7 @@ int cph_load_native(cph_index* h, const char* path) {
 }
 
 int cph_size(cph_index* h, uint64_t* n) {
-    return guarded([&] { *n = h->needs_build ? h->pending_n : h->host.n; });
+    return guarded([&] { *n = h->needs_build ? h->pending_n : h->size(); });
 }
 int cph_dim(cph_index* h, uint64_t* dim) {
     return guarded([&] { *dim = h->dim; });
@@ -1971,9 +2088,9 @@ int cph_get_vectors(cph_index* h, uint64_t first, uint64_t count, float* out) {
         refuse_host_less(h, "cph_get_vectors");
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
-        if (first + count > h->host.n) throw InvalidArg("vector range out of bounds");
+        if (first > h->size() || count > h->size() - first) throw InvalidArg("vector range out of bounds");
         for (uint64_t i = 0; i < count; ++i)
-            std::memcpy(out + i * h->dim, h->host.vec(first + i), h->dim * sizeof(float));
+            std::memcpy(out + i * h->dim, row_vec(h, first + i), h->dim * sizeof(float));
     });
 }
 
@@ -2315,7 +2432,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
     r->st = st;
     if (exact) {
         r->filt = effective_filter(h, f);                  // removed rows: F & ~R
-        r->m = r->filt ? r->filt->popcount : h->host.n;
+        r->m = r->filt ? r->filt->popcount : h->size();
     }
     if (n == 0 || (exact && r->m == 0)) {                  // nothing to scan: every segment is empty
         if (exact) { h->last_range = true; h->range_exact = 0; }
@@ -2572,6 +2689,9 @@ int cph_host_range_merge_pass(const uint64_t* in, uint64_t* out, uint64_t len, u
 static void install_row_map(cph_index* h, const uint32_t* rows, uint64_t n, bool keep_host) {
     std::lock_guard<std::mutex> lk(h->mu);
     require_finalized(h);
+    if (h->tail)
+        throw InvalidArg("the index holds " + std::to_string(h->tail) + " added rows, whose input rows are their ids: compact() the "
+                         "index before it gets another row map");
     if (rows && n != h->host.n)
         throw InvalidArg("row map has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->host.n));
     h->use_device();
@@ -2613,7 +2733,7 @@ int cph_get_row_map(cph_index* h, uint64_t first, uint64_t count, uint32_t* out)
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
         if (!h->has_rows) throw InvalidArg("the index has no row map");
-        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("row map range out of bounds");
+        if (first > h->size() || count > h->size() - first) throw InvalidArg("row map range out of bounds");
         if (count == 0) return;
         h->use_device();
         HIP_CHECK(hipMemcpy(out, h->d_rows.p + first, count * 4, hipMemcpyDeviceToHost));
@@ -2643,8 +2763,8 @@ int cph_filter_create_rows(cph_index* h, const uint32_t* words, uint64_t n_bits,
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
         if (!h->has_rows) throw InvalidArg("the index has no row map: a filter in input rows needs one");
-        if (n_bits != h->host.n)
-            throw InvalidArg("filter covers " + std::to_string(n_bits) + " rows, the index holds " + std::to_string(h->host.n));
+        if (n_bits != h->size())
+            throw InvalidArg("filter covers " + std::to_string(n_bits) + " rows, the index holds " + std::to_string(h->size()));
         const uint64_t nw = (n_bits + 31) / 32;
         std::vector<uint32_t> w(words, words + nw);
         if (n_bits & 31) w[nw - 1] &= (1u << (n_bits & 31)) - 1u;
@@ -2698,8 +2818,8 @@ void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool
 
 void require_labels_target(const cph_index* h, const int32_t* labels, uint64_t n) {
     if (!h->finalized) throw InvalidArg("labels belong to a finalized index: finalize or load it first");
-    if (labels && n != h->host.n)
-        throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->host.n));
+    if (labels && n != h->size())
+        throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->size()));
 }
 
 // cph_set_labels on a handle that keeps its host arrays: labels in internal ids, or in input rows (moved to internal
@@ -2712,10 +2832,12 @@ void set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space) {
         install_labels_locked(h, labels, n, true);
         return;
     }
-    if (!h->has_rows || h->host.rows.size() != n)
+    const uint64_t nb = h->host.n;
+    if (!h->has_rows || h->host.rows.size() != nb)
         throw InvalidArg("the index has no row map (it was loaded from a v2 file): labels in input rows need cph_set_row_map");
     std::vector<int32_t> internal(n);
-    labels_to_internal_host(labels, h->host.rows.data(), n, internal.data());
+    labels_to_internal_host(labels, h->host.rows.data(), nb, internal.data());
+    std::copy(labels + nb, labels + n, internal.begin() + nb);      // (a tail row is its own input row)
     install_labels_locked(h, internal.data(), n, true);
 }
 
@@ -2725,7 +2847,7 @@ void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uin
     require_finalized(h);
     if (!h->has_labels) throw InvalidArg("the index has no label column: call cph_set_labels first");
     if (m > kLabelMaxFilters) throw InvalidArg("at most " + std::to_string(kLabelMaxFilters) + " label filters per call");
-    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    const uint64_t n = h->size(), nw = (n + 31) / 32;
     const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
     h->use_device();
     std::vector<std::unique_ptr<cph_filter>> made(m);
@@ -2782,7 +2904,7 @@ int cph_get_labels(cph_index* h, uint64_t first, uint64_t count, int32_t* out) {
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
         if (!h->has_labels) throw InvalidArg("the index has no label column");
-        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("label range out of bounds");
+        if (first > h->size() || count > h->size() - first) throw InvalidArg("label range out of bounds");
         if (count == 0) return;
         h->use_device();
         HIP_CHECK(hipMemcpy(out, h->d_labels.p + first, count * 4, hipMemcpyDeviceToHost));
@@ -2871,8 +2993,10 @@ static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const s
     done.seq = ls.seq;
     // (a handle with removed rows sends its single queries through the batch path, cph_search; a launch that was gathered
     // while the first row was being removed still runs under ~R)
+    // (... and so does a handle with added rows; a launch gathered during the first cph_add scans and folds the tail)
+    require_tail_k(h, kk);
     enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, io.ids(ls.pin_dev), io.dist(ls.pin_dev), ls.stream, io.counts(ls.pin_dev), done,
-                   h->live.get());   // ... the search writes the results back
+                   h->live.get(), io.queries(ls.pin_dev));   // ... the search writes the results back
     CPH_TR(0, 1); CPH_TR(1, n); CPH_TR(2, t1 - t0); CPH_TR(3, now_ns() - t1);
 }
 
@@ -2919,8 +3043,9 @@ int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float
         if (!query || !ids || !dist || !m) throw InvalidArg("null argument");
         const uint64_t kk = std::max<uint64_t>(k, 1);  // api/hnsw_index.hpp:187
         if (kk > 0xFFFFFFFFull) throw InvalidArg("k too large");
-        if (h->tombstones.load(std::memory_order_acquire)) {
-            // removed rows: a batch of one through the filtered path under ~R (what a search with filter= does)
+        if (h->tombstones.load(std::memory_order_acquire) || h->has_tail.load(std::memory_order_acquire)) {
+            // removed rows: a batch of one through the filtered path under ~R (what a search with filter= does); added
+            // rows: a batch of one, so that the tail's scan and fold follow the graph launch
             std::vector<int64_t> ri(kk);
             std::vector<float> rd(kk);
             search_batch_host(h, query, 1, kk, nullptr, ri.data(), rd.data());
@@ -2992,7 +3117,7 @@ int cph_fastscan_block(cph_index* h, const uint8_t* lut, const float* qparams, u
     return guarded([&] {
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
-        if (vertex >= h->host.n) throw InvalidArg("vertex out of range");
+        if (vertex >= h->host.n) throw InvalidArg("vertex out of range");      // (a vertex of the graph: an added row has no block)
         h->use_device();
         const uint32_t D = h->D, PW = h->L.PW;
         std::vector<uint8_t> qu(D);
@@ -3034,7 +3159,7 @@ int cph_exact_l2(cph_index* h, const float* query, const uint32_t* ids, uint64_t
         require_finalized(h);
         if (n == 0) return;
         for (uint64_t i = 0; i < n; ++i)
-            if (ids[i] >= h->host.n) throw InvalidArg("id out of range");
+            if (ids[i] >= h->size()) throw InvalidArg("id out of range");
         h->use_device();
         const uint32_t D = h->D;
         std::vector<float> buf(D, 0.0f);
@@ -3105,7 +3230,7 @@ int cph_export_blocks(cph_index* h, uint64_t first, uint64_t count, int resident
         if (!h || !out) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized.");
-        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("block range out of bounds");
+        if (first > h->host.n || count > h->host.n - first) throw InvalidArg("block range out of bounds");      // (blocks of the graph: added rows have none)
         h->use_device();
         quiesce(h);
         const uint8_t* src = h->d_blocks.p + first * h->L.stride;
@@ -4504,7 +4629,7 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
     require_finalized(h);
     if (space == CPH_IDS_INPUT && !h->has_rows)
         throw InvalidArg("the index has no row map (it was loaded from a v2 file): removing input rows needs cph_set_row_map");
-    const uint64_t n = h->host.n, nw = (n + 31) / 32;
+    const uint64_t n = h->size(), nw = (n + 31) / 32;
     std::vector<uint32_t> list(m);
     for (uint64_t i = 0; i < m; ++i) {
         if (ids[i] < 0 || (uint64_t)ids[i] >= n)
@@ -4550,19 +4675,19 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
 uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new,
                      std::vector<int32_t>* labs = nullptr) {
     const HostIndex& hi = h->host;
-    const uint64_t n = hi.n;
+    const uint64_t n = hi.n, size = h->size();
     const bool rows = h->has_rows && hi.rows.size() == n;
     if (by_row && !rows) throw InvalidArg("the index has no row map");
     std::vector<uint32_t> id_of_row(n);
     for (uint64_t i = 0; i < n; ++i) id_of_row[rows ? hi.rows[i] : i] = (uint32_t)i;
     uint64_t live = 0;
-    for (uint64_t r = 0; r < n; ++r) {
-        const uint32_t id = id_of_row[r];
+    for (uint64_t r = 0; r < size; ++r) {        // the base rows, then the added rows in id order (each its own input row)
+        const uint32_t id = r < n ? id_of_row[r] : (uint32_t)r;
         const bool gone = hi.n_removed != 0 && ((hi.removed[id >> 5] >> (id & 31)) & 1u);
         map[by_row ? r : id] = gone ? -1 : first_new + (int64_t)live;
         if (gone) continue;
-        vecs.insert(vecs.end(), hi.vec(id), hi.vec(id) + hi.dim);
-        if (labs && hi.labels.size() == n) labs->push_back(hi.labels[id]);
+        vecs.insert(vecs.end(), row_vec(h, id), row_vec(h, id) + hi.dim);
+        if (labs && hi.labels.size() == size) labs->push_back(hi.labels[id]);
         ++live;
     }
     return live;
@@ -4580,12 +4705,12 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
         // the builder's own refusals, before the handle gives anything up
-        live = h->host.n - h->host.n_removed;
+        live = h->size() - h->host.n_removed;
         require_buildable(live);
         require_finalizable(live);
         was_input = h->ids_input;
         vecs.reserve(live * h->dim);
-        std::vector<int64_t> map(h->host.n);
+        std::vector<int64_t> map(h->size());
         gather_live(h, vecs, map.data(), was_input, 0, &labs);
         std::copy(map.begin(), map.end(), old_to_new);
     }
@@ -4613,7 +4738,7 @@ int cph_live_count(cph_index* h, uint64_t* n) {
     return guarded([&] {
         if (!h || !n) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
-        *n = h->needs_build ? h->pending_n : h->host.n - h->host.n_removed;
+        *n = h->needs_build ? h->pending_n : h->size() - h->host.n_removed;
     });
 }
 
@@ -4622,7 +4747,7 @@ int cph_get_removed(cph_index* h, uint32_t* words) {
         if (!h) throw InvalidArg("null handle");
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
-        const uint64_t nw = (h->host.n + 31) / 32;
+        const uint64_t nw = (h->size() + 31) / 32;
         if (nw && !words) throw InvalidArg("null argument");
         if (h->host.n_removed == 0) std::fill(words, words + nw, 0u);
         else std::copy(h->host.removed.begin(), h->host.removed.end(), words);
@@ -4634,6 +4759,165 @@ int cph_compact(cph_index* h, int64_t* old_to_new) {
         if (!h) throw InvalidArg("null handle");
         refuse_borrowed(h, "cph_compact");
         compact_index(h, old_to_new);
+    });
+}
+
+}  // extern "C"
+
+// ---- added rows: the tail (cph_add; device_tail.h) -------------------------------------------------------------------------
+namespace {
+
+// Makes `b` hold `want` elements, keeping its first `keep`; the copy runs on `st`, which has drained before the old
+// buffer is freed.
+template <class T>
+void grow_keep(DevBuf<T>& b, size_t keep, size_t want, hipStream_t st) {
+    if (b.p && b.n >= want) return;
+    DevBuf<T> nb(want);
+    if (keep) HIP_CHECK(hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    b = std::move(nb);
+}
+
+// cph_add on one handle; returns the id of the first new row.
+uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t* labels) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->finalized) throw InvalidArg("rows are added to a finalized index: finalize or load it first");
+    const uint64_t size = h->size(), need = size + m;
+    if (m == 0) return size;
+    if (!vectors) throw InvalidArg("null vectors");
+    if ((labels != nullptr) != h->has_labels)
+        throw InvalidArg(h->has_labels ? "the index has a label column: the added rows need labels"
+                                       : "the index has no label column: labels for the added rows have nowhere to go");
+    if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
+    h->use_device();
+    quiesce(h);                                  // a batch in flight reads the arrays that may move
+    HostIndex& hi = h->host;
+    const uint64_t D = h->L.D, dim = h->dim, nw = (need + 31) / 32;
+    const bool removed = hi.n_removed != 0;
+    // everything that can fail comes first: host room, device room, the device pass; the handle changes after that
+    h->tail_vecs.reserve((h->tail + m) * dim);
+    if (h->has_labels) hi.labels.reserve(need);
+    if (removed) hi.removed.reserve(nw);
+    hipStream_t st = own_stream(h);
+    const uint64_t cap = tail_capacity(std::min<uint64_t>(h->d_raw.n / D, h->d_norm.n), need);
+    grow_keep(h->d_raw, size * D, cap * D, st);
+    grow_keep(h->d_norm, size, cap, st);
+    if (h->has_rows) grow_keep(h->d_rows, size, cap, st);
+    if (h->has_labels) grow_keep(h->d_labels, size, cap, st);
+    if (removed) grow_keep(h->d_removed, (size + 31) / 32, (cap + 31) / 32, st);
+    DevBuf<float> d_src(m * dim);
+    DevBuf<int32_t> d_lab(labels ? m : 0);
+    HIP_CHECK(hipMemcpyAsync(d_src.p, vectors, m * dim * 4, hipMemcpyHostToDevice, st));
+    if (labels) HIP_CHECK(hipMemcpyAsync(d_lab.p, labels, m * 4, hipMemcpyHostToDevice, st));
+    if (removed) {                               // whole words behind the old last one: clear, whatever the buffer held
+        const uint64_t w0 = (size + 31) / 32;
+        if (nw > w0) HIP_CHECK(hipMemsetAsync(h->d_removed.p + w0, 0, (nw - w0) * 4, st));
+    }
+    TailAppendArgs a{};
+    a.src = d_src.p;
+    a.src_labels = labels ? d_lab.p : nullptr;
+    a.first = size;
+    a.m = m;
+    a.dim = (uint32_t)dim;
+    a.D = (uint32_t)D;
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.rows = h->has_rows ? h->d_rows.p : nullptr;
+    a.labels = labels ? h->d_labels.p : nullptr;
+    a.removed = removed ? h->d_removed.p : nullptr;
+    tail_append(a, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    // (nothing below throws before the handle is consistent again: the room was reserved above)
+    h->tail_vecs.insert(h->tail_vecs.end(), vectors, vectors + m * dim);
+    if (h->has_labels && hi.labels.size() == size) hi.labels.insert(hi.labels.end(), labels, labels + m);
+    if (removed) {
+        if (size & 31) hi.removed[(size - 1) >> 5] &= (1u << (size & 31)) - 1u;
+        hi.removed.resize(nw, 0u);
+    }
+    h->tail += m;
+    h->has_tail.store(true);
+    if (removed) {                               // R has another size: a new state, so no cached F & ~R of the old size is found again
+        h->rm_epoch = ++g_removed_epoch;
+        h->live.reset();
+        h->live = make_live_filter(h, nullptr);
+    }
+    return size;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_add(cph_index* h, const float* vectors, uint64_t m, const int32_t* labels, int64_t* first_id) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_add");
+        const uint64_t first = add_rows(h, vectors, m, labels);
+        if (first_id) *first_id = (int64_t)first;
+    });
+}
+
+int cph_tail_count(cph_index* h, uint64_t* t) {
+    return guarded([&] {
+        if (!h || !t) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *t = h->tail;
+    });
+}
+
+static void check_tail_fold_args(const int64_t* g_ids, const float* g_dist, uint64_t n, uint64_t k, const uint64_t* pools,
+                                 const uint32_t* counts, uint32_t P, uint32_t C, const int64_t* out_ids, const float* out_dist) {
+    if (!g_ids || !g_dist || !pools || !counts || !out_ids || !out_dist) throw InvalidArg("null argument");
+    if (P < 1 || P > kExactMaxParts) throw InvalidArg("P must be 1.." + std::to_string(kExactMaxParts));
+    if (n < 1 || n > 0xFFFFFFFFull || k < 1 || k > kExactMaxK) throw InvalidArg("fold: sizes out of range");
+    if (C < 128 || C > 4 * kExactMaxK || (C & (C - 1)) || k > C / 2) throw InvalidArg("C must be a power of two, 128 <= C and 2 k <= C");
+    for (uint64_t i = 0; i < (uint64_t)P * n; ++i)
+        if (counts[i] > k) throw InvalidArg("a tail list holds more than k keys");
+}
+
+int cph_tail_fold_hook(int device, const int64_t* g_ids, const float* g_dist, uint64_t n, uint64_t k, const uint64_t* pools,
+                       const uint32_t* counts, uint32_t P, uint32_t C, int64_t* out_ids, float* out_dist) {
+    return guarded([&] {
+        check_tail_fold_args(g_ids, g_dist, n, k, pools, counts, P, C, out_ids, out_dist);
+        HIP_CHECK(hipSetDevice(device));
+        const size_t rows = (size_t)n * k, lists = (size_t)P * n;
+        DevBuf<int64_t> d_ids(rows);
+        DevBuf<float> d_dist(rows);
+        DevBuf<unsigned long long> d_pools(lists * C);
+        DevBuf<uint32_t> d_counts(lists);
+        HIP_CHECK(hipMemcpy(d_ids.p, g_ids, rows * 8, hipMemcpyHostToDevice));      // the graph's rows: folded in place, as the library does
+        HIP_CHECK(hipMemcpy(d_dist.p, g_dist, rows * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_pools.p, pools, lists * C * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_counts.p, counts, lists * 4, hipMemcpyHostToDevice));
+        TailFoldArgs f{};
+        f.pools = d_pools.p;
+        f.counts = d_counts.p;
+        f.P = P;
+        f.q_first = 0;
+        f.q_count = (uint32_t)n;
+        f.k = (uint32_t)k;
+        f.C = C;
+        f.ids = d_ids.p;
+        f.dist = d_dist.p;
+        tail_fold(f, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_ids, d_ids.p, rows * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_dist, d_dist.p, rows * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_tail_fold(const int64_t* g_ids, const float* g_dist, uint64_t n, uint64_t k, const uint64_t* pools, const uint32_t* counts,
+                       uint32_t P, uint32_t C, int64_t* out_ids, float* out_dist) {
+    return guarded([&] {
+        check_tail_fold_args(g_ids, g_dist, n, k, pools, counts, P, C, out_ids, out_dist);
+        tail_fold_host(g_ids, g_dist, n, k, pools, counts, P, C, out_ids, out_dist);
+    });
+}
+
+int cph_host_tail_capacity(uint64_t capacity, uint64_t need, uint64_t* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = tail_capacity(capacity, need);
     });
 }
 

@@ -234,6 +234,77 @@ int cph_host_range_plan(uint64_t candidates, uint64_t n_queries, int num_cus, ui
 int cph_host_range_tiles(const int64_t* lims, uint64_t n, uint64_t budget_bytes, uint64_t* starts_out, uint64_t* n_tiles_out);
 int cph_host_range_merge_pass(const uint64_t* in, uint64_t* out, uint64_t len, uint64_t width);
 
+/* ---- grouped search --------------------------------------------------------------------- */
+/* The k best key groups of every query, up to group_size rows of each (group-by / collapse): rows that share a key -- the
+ * chunks of a document, the products of a seller -- answer as one group.  key_of[id] is an int32 per INTERNAL id: the
+ * handle's label column (cph_set_labels), or a cph_group_keys object when the labels mean something else.
+ *
+ * A query's candidate row is what the ordinary search returns for it at k = candidates (C): C entries ascending by
+ * (distance, id), padded with -1 / FLT_MAX -- cph_search_batch_filtered / _exact / _filters with the same filters, exact
+ * flag, exact threshold, removed rows and tail, with all their routing and all their refusals (per-query filters that
+ * would walk the graph of an index with a tail are CPH_NOT_IMPLEMENTED here too).  The row is walked front to back:
+ *   - padding is skipped;
+ *   - an id that occurred earlier in the row is skipped (a graph row can hold an id twice, a grouped answer cannot);
+ *   - an entry whose key has no group opens one at the next group index while fewer than k groups exist;
+ *   - an entry whose key has a group with fewer than group_size members is appended to it;
+ *   - every other entry is dropped.
+ * So groups are ordered by their best member, members ascend, ties keep the order of the underlying search.  Keys are
+ * compared as values over the whole int32 range: INT32_MIN, INT32_MAX, 0 and -1 are ordinary keys, none is a sentinel.
+ *
+ * Outputs per query (g = group_size): ids [k][g] int64, padded with -1 (internal ids; under CPH_IDS_INPUT input rows,
+ * translated where a member is written); dist [k][g] float32, padded with FLT_MAX, else the bytes of the candidate row;
+ * group_keys [k] int32 and counts [k] int32 (members per group), both 0 where there is no group; complete uint8 =
+ * (k groups exist and each has g members) or (the row holds fewer than C entries that are not padding: the underlying
+ * search ran dry and a longer row would add nothing).  complete is a function of the row alone; with exact != 0 and
+ * complete == 1 the answer is the exact grouped top-k over the allowed ids.  complete == 0 at C = 1024 means that the
+ * 1,024 nearest candidates did not fill the groups (a few keys own most near rows): the groups returned are still the
+ * best of those candidates.
+ *
+ * Limits: 1 <= k, 1 <= group_size, k * group_size <= candidates <= 1024 (the longest row of the exact route and of a
+ * tail's graph route).  filters / n_filters / filter_of: filter_of == NULL takes n_filters 0 (unfiltered) or 1 (one filter
+ * for the batch); else per-query filters as in cph_search_batch_filters.  CPH_INVALID_ARGUMENT: NULL pointers, a shape
+ * outside the limits, no label column and no keys object, a keys object of another size, device or index.
+ *
+ * The work: under the handle mutex the search runs at k = C into scratch rows the handle owns (four sets in rotation,
+ * only ever grown: a call in steady state makes no hipMalloc and no hipFree), written in internal ids whatever the
+ * handle's result id space is (nothing of the handle is changed once the call returns); then ONE launch of
+ * group_rows_kernel (csrc/device_group.h) on the same stream writes all five outputs, padding included.
+ * cph_search_grouped takes and returns host arrays; cph_search_grouped_device takes device pointers and a stream and
+ * waits for nothing (filters and the keys object must outlive the batch; their destroy calls wait).
+ * cph_last_search_stats afterwards: those of the underlying search.
+ *
+ * cph_group_keys_create  keys[size]: one int32 per row, size == cph_size (else CPH_INVALID_ARGUMENT), in internal ids or in
+ *     input rows (space = CPH_IDS_INPUT: needs a row map; moved to internal order once, on the host).  The object is
+ *     resident on the handle's device and serves that handle only.  It covers `size` ids: after a cph_add it is refused
+ *     with the size message a filter gets; a load, build or compact invalidates it (refused as made for another index).
+ * cph_group_keys_destroy waits for the device, then frees; NULL is a no-op.
+ * Partitioned indexes have no grouped search: every part has its own internal ids and its own slice of the labels. */
+typedef struct cph_group_keys cph_group_keys;
+int cph_group_keys_create(cph_index* h, const int32_t* keys, uint64_t size, int space, cph_group_keys** out);
+int cph_group_keys_destroy(cph_group_keys* keys);
+int cph_search_grouped(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                       const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                       int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts, uint8_t* complete);
+int cph_search_grouped_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                              const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                              int exact, int64_t* d_ids, float* d_dist, int32_t* d_group_keys, int32_t* d_counts, uint8_t* d_complete,
+                              void* stream);
+/* Debug hooks of the measurement script (scripts/grouped_sweep.py), not for production use: while switched on, the
+ * group_rows_kernel launch of every grouped search of this handle is bracketed by two HIP events on the call's stream;
+ * _us waits for the second event and returns the device time of the last such launch in microseconds, or
+ * CPH_INVALID_ARGUMENT when none ran.  Off by default: the call then records no event of this kind. */
+int cph_debug_time_grouped(cph_index* h, int on);
+int cph_debug_last_group_rows_us(cph_index* h, double* us);
+/* Test hook: group_rows_kernel on given rows (host arrays).  ids / dist [n][candidates]; key_of [n_keys]; rows [n_keys] or
+ * NULL; every id >= 0 must be < n_keys (CPH_INVALID_ARGUMENT).  The device outputs start as 0xA5 bytes, so a slot the
+ * kernel left alone shows.  cph_host_group_rows is the host statement (csrc/host_group.h, no HIP call). */
+int cph_group_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const int32_t* key_of,
+                        uint64_t n_keys, const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist,
+                        int32_t* out_keys, int32_t* out_counts, uint8_t* out_complete);
+int cph_host_group_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const int32_t* key_of, uint64_t n_keys,
+                        const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist, int32_t* out_keys,
+                        int32_t* out_counts, uint8_t* out_complete);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -518,6 +589,14 @@ int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n,
                                  uint64_t* total);
 int cph_multi_range_search_finish(cph_multi_range* r, int64_t* lims_host, int64_t* ids, float* dist);
 int cph_multi_range_destroy(cph_multi_range* r);
+/* cph_search_grouped over the same shards, every shard on its replica's worker; the bytes are those of one device.
+ * keys: NULL (every replica's label column) or one cph_group_keys per replica, keys[r] made with cph_multi_replica(m, r);
+ * filters[f * R + r] = filter f on replica r (R replicas), as in cph_multi_search_batch_filters; filter_of == NULL takes
+ * n_filters 0 or 1.  Every replica is asked before any shard runs: a refusal leaves no row written. */
+int cph_multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                             const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                             const int32_t* filter_of, int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts,
+                             uint8_t* complete);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

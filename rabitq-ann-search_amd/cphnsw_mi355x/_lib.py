@@ -73,6 +73,20 @@ SYMBOLS = {
     "cph_host_range_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "cph_host_range_tiles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cph_host_range_merge_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "cph_group_keys_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
+    "cph_group_keys_destroy": (C.c_int, [C.c_void_p]),
+    "cph_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_search_grouped_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_multi_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_debug_time_grouped": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_group_rows_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_group_rows_hook": (C.c_int, [C.c_int] + [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_group_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
+        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "cph_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -103,6 +103,41 @@ class IdFilter:
             pass
 
 
+class GroupKeys:
+    """A key column for grouped search on the index' device (CPIndex.make_group_keys): one int32 per row, for callers whose
+    labels mean something else than their groups (labels = tenants, keys = documents).  It serves the index it was made
+    for and covers `size` ids: after an add() it is refused with the size error a filter gets; load(), build() and
+    compact() invalidate it.  A multi-device index' object holds one copy per replica.  close() waits for the batches
+    that may still read it."""
+
+    def __init__(self, index, keys, input_rows=False):
+        self._hs = []                # one cph_group_keys per replica (a single-device index: one)
+        self.size = int(keys.size)
+        code = _lib.IDS_INPUT if input_rows else _lib.IDS_INTERNAL
+        try:
+            for rh in index._replicas():
+                h = C.c_void_p()
+                _lib.check(_lib.lib().cph_group_keys_create(rh, keys.ctypes.data if keys.size else None, self.size, code,
+                                                            C.byref(h)))
+                self._hs.append(h)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        hs = getattr(self, "_hs", [])
+        self._hs = []
+        for h in hs:
+            if h.value:
+                _lib.check(_lib.lib().cph_group_keys_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CPIndex:
     """`devices=[...]` (instead of `device`): the index is replicated on every listed HIP device (duplicates allowed:
     several replicas on one GPU) and search_batch splits its queries across the replicas in one call, with results
@@ -853,6 +888,214 @@ class CPIndex:
         finally:
             L.cph_range_destroy(obj)
         return lims, ids, dist
+
+    # -- grouped search (not in the reference) --------------------------------------------------
+    GROUP_MAX_CANDIDATES = 1024
+
+    def make_group_keys(self, keys, ids=None):
+        """GroupKeys from an integer array [size] whose values fit int32, indexed in the space `ids` ("internal" or
+        "input"; default: result_ids, as for set_labels): the `keys=` argument of search_grouped, for grouping by
+        something else than the label column."""
+        self._no_parts("make_group_keys")
+        space = self._id_space(ids)
+        a = self._as_labels(keys, "keys")
+        if a.ndim != 1 or a.shape[0] != self.size:
+            raise ValueError(f"keys must be a 1D integer array of length {self.size} (the index size)")
+        return GroupKeys(self, a, input_rows=space == "input")
+
+    def _grouped_args(self, n, k, group_size, keys, candidates, filter, filter_of):
+        """Validation shared by both grouped entry points -> (k, g, C or None, GroupKeys or None, [IdFilter] or None,
+        filter_of or None, IdFilter or None)."""
+        if self._p is not None:
+            raise ValueError("search_grouped is not defined on a partitioned index (every part has its own internal ids and "
+                             "its own slice of the labels): use part(i).search_grouped")
+        k, g = int(k), int(group_size)
+        cap = self.GROUP_MAX_CANDIDATES
+        if k < 1 or g < 1:
+            raise ValueError("search_grouped needs k >= 1 and group_size >= 1")
+        if k * g > cap:
+            raise ValueError(f"search_grouped needs k * group_size <= {cap} (the longest candidate row)")
+        if candidates is not None:
+            candidates = int(candidates)
+            if not k * g <= candidates <= cap:
+                raise ValueError(f"candidates must lie in [k * group_size, {cap}]")
+        if keys is not None:
+            if not isinstance(keys, GroupKeys):
+                raise ValueError("keys must be a GroupKeys object (make_group_keys)")
+            if not keys._hs:
+                raise ValueError("group keys were closed")
+            if len(keys._hs) != len(self._replicas()):
+                raise ValueError("group keys were made for an index with another number of replicas")
+        elif not self.has_labels:
+            raise ValueError("search_grouped needs keys: call set_labels first, or pass keys=make_group_keys(...)")
+        fs, fo = self._filter_list(filter, filter_of, n)
+        f = None if (fs is not None or filter is None) else self._filter(filter)
+        return k, g, candidates, keys, fs, fo, f
+
+    def _grouped_pass(self, q, k, g, C_, keys, fs, fo, f, exact):
+        """One pass of the host form at C_ candidates over the float32 array q [n, dim] -> the five arrays."""
+        n, L = q.shape[0], _lib.lib()
+        out = (np.empty((n, k, g), np.int64), np.empty((n, k, g), np.float32), np.empty((n, k), np.int32),
+               np.empty((n, k), np.int32), np.empty(n, np.uint8))
+        multi = self._m is not None
+        if fs is not None:
+            fh, nf, fop = self._filter_handles(fs, None if multi else 0), len(fs), fo.ctypes.data
+        elif f is not None:
+            hs = [h.value for h in (f._hs if multi else f._hs[:1])]
+            fh, nf, fop = (C.c_void_p * len(hs))(*hs), 1, None
+        else:
+            fh, nf, fop = None, 0, None
+        po = [o.ctypes.data if n else None for o in out]
+        qp = q.ctypes.data if n else None
+        if multi:
+            kh = None if keys is None else (C.c_void_p * len(keys._hs))(*[h.value for h in keys._hs])
+            _lib.check(L.cph_multi_search_grouped(self._m, qp, n, k, g, C_, kh, fh, nf, fop, int(bool(exact)), *po))
+        else:
+            _lib.check(L.cph_search_grouped(self._h, qp, n, k, g, C_, None if keys is None else keys._hs[0], fh, nf, fop,
+                                            int(bool(exact)), *po))
+        return out
+
+    def search_grouped(self, queries, k=DEFAULT_K, group_size=1, keys=None, candidates=None, filter=None, exact=False,
+                       filter_of=None, label=None):
+        """The k best key groups of every query, up to group_size rows of each (group-by / collapse):
+        (ids int64 [n, k, g], dist float32 [n, k, g], keys int32 [n, k], counts int32 [n, k], complete bool [n]).
+        Rows that share a key answer as one group; the key of a row is its label (set_labels), or its entry in
+        `keys` (make_group_keys).  A query's candidate row is row i of search_batch(queries, C, filter=..., exact=...,
+        filter_of=...) -- same routing, removed rows, tail and refusals -- walked front to back: padding and repeated ids
+        are skipped, a new key opens a group while fewer than k exist, an entry joins its key's group while that has fewer
+        than g members, everything else is dropped.  Groups are ordered by their best member, members ascend, ties keep
+        the order of the search; every int32 value is an ordinary key.  ids are padded with -1 (input rows under
+        result_ids = "input"), dist with FLT_MAX, keys and counts with 0; counts[i, j] == 0 means no group j.
+        complete[i]: k groups with g members each were found, or the candidate row held fewer than C ids (the search ran
+        dry: a longer row would add nothing).  With exact=True and complete[i] the answer is the exact grouped top-k
+        over the allowed ids.
+        `candidates=C` (k * g <= C <= 1024) runs one pass at that C.  candidates=None is a policy, not a measured
+        optimum: one pass at C0 = min(1024, max(64, 4 * k * g)), then the queries that came back incomplete are run
+        again at min(4 * C, 1024) until they are complete or C is 1024; a query's answer is that of the last pass it
+        took part in.  complete[i] can still be False at C = 1024: the 1,024 nearest candidates did not fill the groups
+        (a few keys own most near rows); the groups returned are the best of those candidates.
+        `label`: as in search_batch (it restricts the rows; the groups still come from the label column or `keys`).
+        A multi-device index shards the queries like search_batch; the bytes are those of one device.  A partitioned
+        index is refused (use part(i).search_grouped)."""
+        q = _as_f32(queries)
+        if q.ndim != 2 or q.shape[1] != self._dim:
+            raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, filter_of, made = self._from_label(label, filter, filter_of, q.shape[0])
+            try:
+                return self.search_grouped(q, k, group_size, keys=keys, candidates=candidates, filter=filter, exact=exact,
+                                           filter_of=filter_of)
+            finally:
+                for f in made:
+                    f.close()
+        n = q.shape[0]
+        k, g, C_, keys, fs, fo, f = self._grouped_args(n, k, group_size, keys, candidates, filter, filter_of)
+        if C_ is not None:
+            out = self._grouped_pass(q, k, g, C_, keys, fs, fo, f, exact)
+            return out[:4] + (out[4].astype(bool),)
+        cap = self.GROUP_MAX_CANDIDATES
+        C_ = min(cap, max(64, 4 * k * g))
+        out = self._grouped_pass(q, k, g, C_, keys, fs, fo, f, exact)
+        todo = np.flatnonzero(out[4] == 0)
+        while todo.size and C_ < cap:
+            C_ = min(4 * C_, cap)
+            sub = self._grouped_pass(np.ascontiguousarray(q[todo]), k, g, C_, keys, fs,
+                                     None if fo is None else np.ascontiguousarray(fo[todo]), f, exact)
+            for o, s_ in zip(out, sub):
+                o[todo] = s_
+            todo = todo[sub[4] == 0]
+        return out[:4] + (out[4].astype(bool),)
+
+    def search_grouped_device(self, queries, k=DEFAULT_K, group_size=1, keys=None, candidates=None, out=None, stream=None,
+                              filter=None, exact=False, filter_of=None, label=None):
+        """search_grouped on a float32 torch tensor (n, dim) on this index' device; returns the five outputs as torch
+        tensors on the same device (complete: bool).  Like search_batch_device it only enqueues, on `stream` (default:
+        torch's current stream), and never waits: the tensors are valid in stream order, two batches on two streams
+        overlap.  ONE pass: at `candidates`, or (None) at the C0 of search_grouped -- re-running incomplete queries
+        would need `complete` on the host.  `out`: the five tensors to write (contiguous, on the queries' device;
+        complete as uint8 or bool).  filter / filter_of / label are host data as in search_batch_device; a filter or
+        GroupKeys closed after the call waits for the batch.  A multi-device index runs the whole batch on one replica
+        on the queries' device."""
+        import torch
+        if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            filter, filter_of, made = self._from_label(label, filter, filter_of, queries.shape[0])
+            try:
+                return self.search_grouped_device(queries, k, group_size, keys=keys, candidates=candidates, out=out,
+                                                  stream=stream, filter=filter, exact=exact, filter_of=filter_of)
+            finally:
+                for f in made:
+                    f.close()
+        n = queries.shape[0]
+        k, g, C_, keys, fs, fo, f = self._grouped_args(n, k, group_size, keys, candidates, filter, filter_of)
+        if C_ is None:
+            C_ = min(self.GROUP_MAX_CANDIDATES, max(64, 4 * k * g))
+        rep = 0
+        if self._m is not None:
+            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
+            if not on:
+                raise ValueError("queries must live on one of this index' devices")
+            rep = on[self._next_dev % len(on)]
+            self._next_dev += 1
+        elif not queries.is_cuda or queries.device.index != self._device:
+            raise ValueError("queries must live on this index' device")
+        h = self._replicas()[rep]
+        fresh = []                       # tensors allocated here, on torch's current stream
+        if not queries.is_contiguous():
+            queries = queries.contiguous()
+            fresh.append(queries)
+        shapes = (((n, k, g), torch.int64), ((n, k, g), torch.float32), ((n, k), torch.int32), ((n, k), torch.int32),
+                  ((n,), torch.uint8))
+        if out is None:
+            res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in shapes]
+            fresh += res
+        else:
+            res = list(out)
+            if len(res) != 5:
+                raise ValueError("out must be the five tensors (ids, dist, keys, counts, complete)")
+            for i, (t, (sh, dt)) in enumerate(zip(res, shapes)):
+                ok_dt = t.dtype == dt or (i == 4 and t.dtype == torch.bool)
+                if tuple(t.shape) != sh or not ok_dt or t.device != queries.device or not t.is_contiguous():
+                    raise ValueError("out must be contiguous (n, k, g) int64 / float32, (n, k) int32 / int32 and (n,) uint8 "
+                                     "tensors on the queries' device")
+        cur = torch.cuda.current_stream(queries.device)
+        if stream is None:
+            st = cur.cuda_stream
+        else:
+            st = getattr(stream, "cuda_stream", stream)
+            if fresh and st != cur.cuda_stream:
+                # (as in search_batch_device: the search stream runs after the allocations' stream, and the caching
+                #  allocator must not hand the blocks out again while the search still uses them)
+                ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
+                ext.wait_stream(cur)
+                for t in fresh:
+                    t.record_stream(ext)
+        if fs is not None:
+            fh, nf, fop = self._filter_handles(fs, rep), len(fs), fo.ctypes.data
+        elif f is not None:
+            fh, nf, fop = (C.c_void_p * 1)(f._hs[rep].value), 1, None
+        else:
+            fh, nf, fop = None, 0, None
+        _lib.check(_lib.lib().cph_search_grouped_device(h, queries.data_ptr() if n else None, n, k, g, C_,
+                                                        None if keys is None else keys._hs[rep], fh, nf, fop, int(bool(exact)),
+                                                        *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))
+        if res[4].dtype != torch.bool:
+            res[4] = res[4].view(torch.bool)
+        return tuple(res)
+
+    def time_grouped(self, on=True):
+        """Debug hook of the measurement script: while on, the group kernel of every grouped search is bracketed by HIP
+        events (last_group_rows_us).  Off by default."""
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_debug_time_grouped(h, int(bool(on))))
+
+    def last_group_rows_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the group kernel of the last grouped search made under
+        time_grouped() on the given replica; waits for that launch."""
+        us = C.c_double(0)
+        _lib.check(_lib.lib().cph_debug_last_group_rows_us(self._replicas()[replica], C.byref(us)))
+        return us.value
 
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):

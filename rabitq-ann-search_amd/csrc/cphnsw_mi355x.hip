@@ -36,6 +36,7 @@
 #include "device_exact.h"
 #include "device_range.h"
 #include "device_tail.h"
+#include "device_group.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -169,6 +170,18 @@ struct RangeScratch {
     DevBuf<uint8_t> d_tab;
 };
 constexpr size_t kRangeScratchKept = 2;
+
+// The device buffers of one grouped search (cph_search_grouped*): the [n][C] candidate rows of the underlying search and,
+// for the host form, the queries and the five outputs.  A handle owns kMaxBatchSets of them, used in turn and only ever
+// grown; `ev` follows the last kernel that touched the rows, the next call on these buffers makes its stream wait for it.
+struct GroupScratch {
+    DevBuf<int64_t> r_ids, o_ids;
+    DevBuf<float> r_dist, o_dist, d_q;
+    DevBuf<int32_t> o_keys, o_counts;
+    DevBuf<uint8_t> o_complete;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+};
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
@@ -280,6 +293,11 @@ struct cph_index {
     bool last_range = false;           // ... unless an exact range search came later: it uses no set, its one counter is
     uint64_t range_exact = 0;          //     kept here (cph_last_search_stats)
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
+    GroupScratch group_scratch[kMaxBatchSets];                  // buffers of grouped searches, in rotation (under mu)
+    int last_group = kMaxBatchSets - 1;
+    // debug hook cph_debug_time_grouped: only while group_timing is on is a group pass bracketed by the two events
+    hipEvent_t ev_group0 = nullptr, ev_group1 = nullptr;
+    bool group_timing = false, group_timed = false;
     uint64_t index_epoch = 0;          // counts the index swaps (begin_device_swap): a cph_range of an older index refuses to finish
     hipStream_t own_stream = nullptr;  // host-API calls (cph_search_batch, cph_search, hooks)
     bool order_queries = true;         // CPH_QUERY_ORDER=0 disables the closest-entry-first launch order
@@ -456,6 +474,8 @@ void release_scratch(BatchSet& s) {
 void quiesce(cph_index* h) {
     for (auto& s : h->sets)
         if (s.used && s.ev_done) HIP_CHECK(hipEventSynchronize(s.ev_done));
+    for (auto& gs : h->group_scratch)            // (the group pass runs behind its batch's ev_done)
+        if (gs.used && gs.ev) HIP_CHECK(hipEventSynchronize(gs.ev));
 }
 
 // The big arrays of a loaded index: blocks repacked into the device layout, vectors, norms.  (An index
@@ -1555,10 +1575,9 @@ void search_batch_filters_host(cph_index* h, const float* queries, uint64_t n, u
 
 // cph_search_batch_filters_device: queries and results in device memory (filter_of on the host), everything enqueued on
 // the caller's stream.
-void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
-                                 uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
+// search_batch_filters_device_locked: the caller holds the handle mutex.
+void search_batch_filters_device_locked(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                        uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
     if (!filters_batch_has_work(h, filters, F, filter_of, d_queries, n, k, d_ids, d_dist)) return;
     LiveFilters lf;
     live_filters(h, filters, F, filter_of, n, lf);
@@ -1568,6 +1587,13 @@ void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchSet& s = next_set(h, st);
     enqueue_filters(h, s, d_queries, (uint32_t)n, (uint32_t)k, filters, F, filter_of, g, d_ids, d_dist, st);
+}
+
+void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
+                                 uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    search_batch_filters_device_locked(h, d_queries, n, k, filters, F, filter_of, exact, d_ids, d_dist, stream);
 }
 
 }  // namespace
@@ -1586,7 +1612,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 106; }
+int cph_version(void) { return 107; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1651,9 +1677,15 @@ static void destroy_index(cph_index* h) {
                          (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
     for (auto& x : g_tr) x = 0;
 #endif
+    for (auto& gs : h->group_scratch) {
+        if (gs.used && gs.ev) (void)hipEventSynchronize(gs.ev);
+        if (gs.ev) (void)hipEventDestroy(gs.ev);
+    }
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->ev_label0) (void)hipEventDestroy(h->ev_label0);
     if (h->ev_label1) (void)hipEventDestroy(h->ev_label1);
+    if (h->ev_group0) (void)hipEventDestroy(h->ev_group0);
+    if (h->ev_group1) (void)hipEventDestroy(h->ev_group1);
     for (auto& ls : h->leaders) {
         if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
         if (ls.pin) (void)hipHostFree(ls.pin);
@@ -2805,6 +2837,7 @@ namespace {
 // keep_host: also as host.labels (what compact gathers from); a replica without host arrays keeps the device copy only.
 void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool keep_host) {
     h->use_device();
+    quiesce(h);                                  // a grouped batch in flight may be reading the old column
     if (!labels) {
         std::vector<int32_t>().swap(h->host.labels);
         sync_labels(h);
@@ -5122,6 +5155,381 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
         if (!f || !count) throw InvalidArg("null argument");
         *count = 0;
         for (const cph_filter* x : f->f) *count += x->popcount;
+    });
+}
+
+}  // extern "C"
+
+// ---- grouped search: the k best key groups, up to g rows of each (device_group.h, host_group.h) ---------------------------
+// An ordinary search at k = C into scratch rows the handle owns, then group_rows_kernel on the same stream.  The rows
+// hold INTERNAL ids whatever the handle returns (the keys are looked up by internal id); the row map is applied where a
+// member is written.  Nothing here waits for the device in the _device form.
+struct cph_group_keys {
+    cph_index* h = nullptr;                    // the handle it was made for ...
+    uint64_t epoch = 0;                        // ... and the index that handle held then (index_epoch)
+    int device = 0;
+    uint64_t size = 0;                         // ids it covers
+    DevBuf<int32_t> keys;                      // [size], internal-id order
+};
+
+namespace {
+
+// While it lives, searches of the handle write internal ids.  The caller holds the handle mutex from before its
+// construction until after its destruction, so no other call observes the change.
+struct InternalIdsScope {
+    cph_index* h;
+    bool was;
+    explicit InternalIdsScope(cph_index* h_) : h(h_), was(h_->ids_input) { h->ids_input = false; }
+    ~InternalIdsScope() { h->ids_input = was; }
+};
+
+void check_group_shape(uint64_t k, uint64_t g, uint64_t C) {
+    if (k < 1 || g < 1) throw InvalidArg("grouped search needs k >= 1 and group_size >= 1");
+    if (C > kGroupMaxCandidates)
+        throw InvalidArg("grouped search supports candidates <= " + std::to_string(kGroupMaxCandidates) + ", got " + std::to_string(C));
+    if (k > C || g > C || k * g > C)
+        throw InvalidArg("grouped search needs k * group_size <= candidates (got " + std::to_string(k) + " * " + std::to_string(g) +
+                         " > " + std::to_string(C) + ")");
+}
+
+void check_group_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, const int32_t* key_of, uint64_t n_keys,
+                           uint64_t k, uint64_t g, const int64_t* out_ids, const float* out_dist, const int32_t* out_keys,
+                           const int32_t* out_counts, const uint8_t* out_complete) {
+    if (!ids || !dist || !key_of || !out_ids || !out_dist || !out_keys || !out_counts || !out_complete) throw InvalidArg("null argument");
+    if (C < 1) throw InvalidArg("group rows: candidates must be >= 1");
+    check_group_shape(k, g, C);
+    if (n < 1 || n > 0x7FFFFFFFull || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("group rows: sizes out of range");
+    for (uint64_t i = 0; i < n * C; ++i)
+        if (ids[i] >= 0 && (uint64_t)ids[i] >= n_keys) throw InvalidArg("group rows: id out of range");
+}
+
+// The key column of a grouped call: the keys object (checked against the handle), else the label column.
+const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) {
+    if (!keys) {
+        if (!h->has_labels) throw InvalidArg("grouped search needs keys: the index has no label column (cph_set_labels) and no keys object was given");
+        return h->d_labels.p;
+    }
+    if (keys->device != h->device) throw InvalidArg("group keys belong to another device");
+    if (keys->size != h->size())
+        throw InvalidArg("group keys cover " + std::to_string(keys->size) + " ids, the index holds " + std::to_string(h->size()));
+    if (keys->h != h || keys->epoch != h->index_epoch)
+        throw InvalidArg("group keys were made for another index (a load, build or compact invalidates them)");
+    return keys->keys.p;
+}
+
+// The body of both forms: d_queries and the five outputs in device memory, everything enqueued on `st`.  The caller
+// holds the handle mutex, has set the device and has checked the shape and the output pointers.
+void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
+                           const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
+                           int64_t* d_ids, float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, hipStream_t st) {
+    if (!gs.ev) HIP_CHECK(hipEventCreateWithFlags(&gs.ev, hipEventDisableTiming));
+    if (gs.r_ids.n < n * C) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));      // growing: the old rows must be idle
+        gs.r_ids.alloc(n * C);
+        gs.r_dist.alloc(n * C);
+    }
+    if (gs.used) HIP_CHECK(hipStreamWaitEvent(st, gs.ev, 0));    // the rows' previous batch, maybe on another stream
+    try {
+        {
+            InternalIdsScope internal(h);
+            if (filter_of)
+                search_batch_filters_device_locked(h, d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, st);
+            else
+                search_batch_device_locked(h, d_queries, n, C, F ? filters[0] : nullptr, gs.r_ids.p, gs.r_dist.p, st, exact);
+        }
+        GroupArgs a{};
+        a.ids = gs.r_ids.p;
+        a.dist = gs.r_dist.p;
+        a.C = (uint32_t)C;
+        a.k = (uint32_t)k;
+        a.g = (uint32_t)g;
+        a.key_of = d_key_of;
+        a.n_ids = (uint32_t)h->size();
+        a.rows = h->ids_input ? h->d_rows.p : nullptr;
+        a.out_ids = d_ids;
+        a.out_dist = d_dist;
+        a.out_keys = d_keys;
+        a.out_counts = d_counts;
+        a.out_complete = d_complete;
+        h->group_timed = false;
+        if (h->group_timing) HIP_CHECK(hipEventRecord(h->ev_group0, st));
+        group_rows(a, (uint32_t)n, st);
+        if (h->group_timing) HIP_CHECK(hipEventRecord(h->ev_group1, st));
+        h->group_timed = h->group_timing;
+    } catch (...) {
+        (void)hipEventRecord(gs.ev, st);                          // whatever was enqueued may still write the rows
+        gs.used = true;
+        throw;
+    }
+    HIP_CHECK(hipEventRecord(gs.ev, st));
+    gs.used = true;
+}
+
+// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
+bool grouped_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_filter* const* filters,
+                      uint32_t F, const int32_t* filter_of, const void* ids, const void* dist, const void* keys_out, const void* counts,
+                      const void* complete) {
+    require_finalized(h);
+    if (C < 1) throw InvalidArg("grouped search needs candidates >= 1");
+    check_group_shape(k, g, C);
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    if (n > 0x7FFFFFFFull) throw InvalidArg("batch too large");
+    if (n == 0) return false;
+    if (!queries || !ids || !dist || !keys_out || !counts || !complete) throw InvalidArg("null argument");
+    return true;
+}
+
+GroupScratch& next_group_scratch(cph_index* h) {
+    h->last_group = (h->last_group + 1) % kMaxBatchSets;
+    return h->group_scratch[h->last_group];
+}
+
+void search_grouped_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_group_keys* keys,
+                         const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist,
+                         int32_t* keys_out, int32_t* counts, uint8_t* complete) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!grouped_has_work(h, queries, n, k, g, C, filters, F, filter_of, ids, dist, keys_out, counts, complete)) return;
+    const int32_t* d_key_of = group_key_column(h, keys);
+    h->use_device();
+    hipStream_t st = own_stream(h);
+    GroupScratch& gs = next_group_scratch(h);
+    const size_t slots = (size_t)n * k * g;
+    if (gs.d_q.n < n * h->dim || gs.o_ids.n < slots || gs.o_keys.n < n * k || gs.o_complete.n < n) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        gs.d_q.alloc(n * h->dim);
+        gs.o_ids.alloc(slots);
+        gs.o_dist.alloc(slots);
+        gs.o_keys.alloc(n * k);
+        gs.o_counts.alloc(n * k);
+        gs.o_complete.alloc(n);
+    }
+    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
+    search_grouped_locked(h, gs, gs.d_q.p, n, k, g, C, d_key_of, filters, F, filter_of, exact, gs.o_ids.p, gs.o_dist.p, gs.o_keys.p,
+                          gs.o_counts.p, gs.o_complete.p, st);
+    HIP_CHECK(hipMemcpyAsync(ids, gs.o_ids.p, slots * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(dist, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(keys_out, gs.o_keys.p, n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(counts, gs.o_counts.p, n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(complete, gs.o_complete.p, n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void search_grouped_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_group_keys* keys,
+                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
+                           float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!grouped_has_work(h, d_queries, n, k, g, C, filters, F, filter_of, d_ids, d_dist, d_keys, d_counts, d_complete)) return;
+    const int32_t* d_key_of = group_key_column(h, keys);
+    h->use_device();
+    search_grouped_locked(h, next_group_scratch(h), d_queries, n, k, g, C, d_key_of, filters, F, filter_of, exact, d_ids, d_dist, d_keys,
+                          d_counts, d_complete, reinterpret_cast<hipStream_t>(stream));
+}
+
+// cph_multi_search_grouped: keys[r] = the keys object of replica r (or keys == null: every replica's label column),
+// filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
+void multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
+                          const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
+                          bool exact, int64_t* ids, float* dist, int32_t* keys_out, int32_t* counts, uint8_t* complete) {
+    if (!m) throw InvalidArg("null handle");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    const uint32_t R = (uint32_t)m->reps.size();
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    for (uint32_t r = 0; r < R; ++r) {              // (before any shard runs: a refusal must not leave half of the rows written)
+        cph_index* h = m->reps[r];
+        std::lock_guard<std::mutex> lg(h->mu);
+        grouped_has_work(h, queries, n, k, g, C, filters, F, filter_of, ids, dist, keys_out, counts, complete);
+        if (keys && !keys[r]) throw InvalidArg("a grouped multi-device search needs one keys object per replica");
+        (void)group_key_column(h, keys ? keys[r] : nullptr);
+        for (uint32_t f = 0; f < F; ++f) {
+            if (!filters[(size_t)f * R + r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
+            check_filter(h, filters[(size_t)f * R + r]);
+        }
+    }
+    if (n == 0) return;
+    for (uint64_t i = 0; i < n && filter_of; ++i)
+        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
+            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
+                             std::to_string(F) + ")");
+    const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
+    const uint64_t dim = m->reps[0]->dim;
+    std::string err;
+    const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
+        cph_index* h = m->reps[s.replica];
+        std::vector<const cph_filter*> fr(F);
+        for (uint32_t f = 0; f < F; ++f) fr[f] = filters[(size_t)f * R + s.replica];
+        const int r = cph_search_grouped(h, queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, g, C, keys ? keys[s.replica] : nullptr,
+                                         F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0,
+                                         ids ? ids + s.lo * k * g : nullptr, dist ? dist + s.lo * k * g : nullptr,
+                                         keys_out ? keys_out + s.lo * k : nullptr, counts ? counts + s.lo * k : nullptr,
+                                         complete ? complete + s.lo : nullptr);
+        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
+        return r;
+    }, err);
+    if (rc != CPH_OK) raise_status(rc, err);
+    std::lock_guard<std::mutex> lg(m->last_mu);
+    m->last_plan = plan;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_group_keys_create(cph_index* h, const int32_t* keys, uint64_t size, int space, cph_group_keys** out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = nullptr;
+        if (!h || (!keys && size != 0)) throw InvalidArg("null argument");
+        if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->finalized) throw InvalidArg("group keys belong to a finalized index: finalize or load it first");
+        if (size != h->size())
+            throw InvalidArg("group keys have " + std::to_string(size) + " entries, the index holds " + std::to_string(h->size()));
+        h->use_device();
+        std::vector<int32_t> internal;
+        const int32_t* src = keys;
+        if (space == CPH_IDS_INPUT) {
+            const uint64_t nb = h->host.n;
+            if (!h->has_rows) throw InvalidArg("the index has no row map (it was loaded from a v2 file): keys in input rows need cph_set_row_map");
+            std::vector<uint32_t> rows(h->host.rows);
+            if (rows.size() != nb) {                       // a replica without host arrays: its device copy
+                rows.resize(nb);
+                if (nb) HIP_CHECK(hipMemcpy(rows.data(), h->d_rows.p, nb * 4, hipMemcpyDeviceToHost));
+            }
+            internal.resize(size);
+            labels_to_internal_host(keys, rows.data(), nb, internal.data());
+            std::copy(keys + nb, keys + size, internal.begin() + nb);      // (a tail row is its own input row)
+            src = internal.data();
+        }
+        std::unique_ptr<cph_group_keys> gk(new cph_group_keys());
+        gk->h = h;
+        gk->epoch = h->index_epoch;
+        gk->device = h->device;
+        gk->size = size;
+        gk->keys.alloc(std::max<uint64_t>(size, 1));
+        if (size) HIP_CHECK(hipMemcpy(gk->keys.p, src, size * 4, hipMemcpyHostToDevice));
+        *out = gk.release();
+    });
+}
+
+int cph_group_keys_destroy(cph_group_keys* keys) {
+    return guarded([&] {
+        if (!keys) return;
+        std::unique_ptr<cph_group_keys> own(keys);
+        if (hipSetDevice(keys->device) == hipSuccess) (void)hipDeviceSynchronize();     // a batch in flight may read the column
+    });
+}
+
+int cph_search_grouped(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                       const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                       int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts, uint8_t* complete) {
+    return guarded([&] {
+        search_grouped_host(h, queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, ids, dist, group_keys,
+                            counts, complete);
+    });
+}
+
+int cph_search_grouped_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                              const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                              int exact, int64_t* d_ids, float* d_dist, int32_t* d_group_keys, int32_t* d_counts, uint8_t* d_complete,
+                              void* stream) {
+    return guarded([&] {
+        search_grouped_device(h, d_queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, d_ids, d_dist,
+                              d_group_keys, d_counts, d_complete, stream);
+    });
+}
+
+int cph_multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
+                             const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                             const int32_t* filter_of, int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts,
+                             uint8_t* complete) {
+    return guarded([&] {
+        multi_search_grouped(m, queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, ids, dist, group_keys,
+                             counts, complete);
+    });
+}
+
+int cph_debug_time_grouped(cph_index* h, int on) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->use_device();
+        if (on && !h->ev_group0) HIP_CHECK(hipEventCreate(&h->ev_group0));
+        if (on && !h->ev_group1) HIP_CHECK(hipEventCreate(&h->ev_group1));
+        h->group_timing = on != 0;
+        h->group_timed = false;
+    });
+}
+
+int cph_debug_last_group_rows_us(cph_index* h, double* us) {
+    return guarded([&] {
+        if (!h || !us) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->group_timed) throw InvalidArg("no timed grouped search has run on this handle (cph_debug_time_grouped)");
+        h->use_device();
+        HIP_CHECK(hipEventSynchronize(h->ev_group1));
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, h->ev_group0, h->ev_group1));
+        *us = (double)ms * 1e3;
+    });
+}
+
+int cph_group_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const int32_t* key_of,
+                        uint64_t n_keys, const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist,
+                        int32_t* out_keys, int32_t* out_counts, uint8_t* out_complete) {
+    return guarded([&] {
+        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, out_ids, out_dist, out_keys, out_counts, out_complete);
+        HIP_CHECK(hipSetDevice(device));
+        const size_t cells = (size_t)n * candidates, slots = (size_t)n * k * group_size;
+        DevBuf<int64_t> d_ids(cells), o_ids(slots);
+        DevBuf<float> d_dist(cells), o_dist(slots);
+        DevBuf<int32_t> d_key_of(n_keys), o_keys(n * k), o_counts(n * k);
+        DevBuf<uint32_t> d_rows(rows ? n_keys : 1);
+        DevBuf<uint8_t> o_complete(n);
+        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_key_of.p, key_of, n_keys * 4, hipMemcpyHostToDevice));
+        if (rows) HIP_CHECK(hipMemcpy(d_rows.p, rows, n_keys * 4, hipMemcpyHostToDevice));
+        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
+        HIP_CHECK(hipMemset(o_ids.p, 0xA5, slots * 8));
+        HIP_CHECK(hipMemset(o_dist.p, 0xA5, slots * 4));
+        HIP_CHECK(hipMemset(o_keys.p, 0xA5, n * k * 4));
+        HIP_CHECK(hipMemset(o_counts.p, 0xA5, n * k * 4));
+        HIP_CHECK(hipMemset(o_complete.p, 0xA5, n));
+        GroupArgs a{};
+        a.ids = d_ids.p;
+        a.dist = d_dist.p;
+        a.C = (uint32_t)candidates;
+        a.k = (uint32_t)k;
+        a.g = (uint32_t)group_size;
+        a.key_of = d_key_of.p;
+        a.n_ids = (uint32_t)n_keys;
+        a.rows = rows ? d_rows.p : nullptr;
+        a.out_ids = o_ids.p;
+        a.out_dist = o_dist.p;
+        a.out_keys = o_keys.p;
+        a.out_counts = o_counts.p;
+        a.out_complete = o_complete.p;
+        group_rows(a, (uint32_t)n, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_ids, o_ids.p, slots * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_dist, o_dist.p, slots * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_keys, o_keys.p, n * k * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_counts, o_counts.p, n * k * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_complete, o_complete.p, n, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_group_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const int32_t* key_of, uint64_t n_keys,
+                        const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist, int32_t* out_keys,
+                        int32_t* out_counts, uint8_t* out_complete) {
+    return guarded([&] {
+        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, out_ids, out_dist, out_keys, out_counts, out_complete);
+        group_rows_host(ids, dist, n, (uint32_t)candidates, key_of, rows, (uint32_t)k, (uint32_t)group_size, out_ids, out_dist, out_keys,
+                        out_counts, out_complete);
     });
 }
 

@@ -930,6 +930,31 @@ bool size_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, hipStream_t
     return ordered;
 }
 
+// ---- what the scans share on the host (device_exact.h) ----------------------------------------------------------------------
+// Enqueues the pad pass of a scan: qpad[nq_pad][D] and qnorm[nq_pad] from the nq raw queries at d_q (d_perm, or null:
+// exact_pad_rows), and n_exact, the batch's evaluation count, STORED into the statistics.
+void pad_queries(const cph_index* h, const float* d_q, const uint32_t* d_perm, uint32_t nq, uint32_t nq_pad, float* qpad, float* qnorm,
+                 unsigned long long* d_stats, unsigned long long n_exact, hipStream_t st) {
+    const dim3 grid(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16));
+    if (d_perm) hipLaunchKernelGGL(exact_pad_groups_kernel, grid, dim3(64), 0, st, d_q, d_perm, nq, nq_pad, (uint32_t)h->dim, h->L.D, qpad, qnorm, d_stats, n_exact);
+    else hipLaunchKernelGGL(exact_pad_kernel, grid, dim3(64), 0, st, d_q, nq, nq_pad, (uint32_t)h->dim, h->L.D, qpad, qnorm, d_stats, n_exact);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The fields every scan kernel's arguments share; q_first / q_count are set per launch.  part: 0 where the kernel's work
+// items state the cut (the grouped scan).
+ScanCommon scan_common(const cph_index* h, const float* qpad, const float* qnorm, uint32_t gq, uint32_t part) {
+    ScanCommon s{};
+    s.raw = h->d_raw.p;
+    s.norm_sq = h->d_norm.p;
+    s.qpad = qpad;
+    s.qnorm = qnorm;
+    s.D = h->L.D;
+    s.gq = gq;
+    s.part = part;
+    return s;
+}
+
 // ---- the tail of a graph-routed batch (device_tail.h) ---------------------------------------------------------------------
 // What every graph-routed entry refuses on a handle with a tail, before it touches the device.
 void require_tail_k(const cph_index* h, uint64_t k) {
@@ -952,9 +977,7 @@ ExactPlan tail_begin(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
         s.x_pools.alloc(pl.pool_keys);
         s.x_counts.alloc((size_t)pl.P * pl.tile_q);
     }
-    hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q, nq,
-                       nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * h->tail);
-    HIP_CHECK(hipGetLastError());
+    pad_queries(h, d_raw_q, nullptr, nq, nq_pad, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * h->tail, st);
     return pl;
 }
 
@@ -963,16 +986,10 @@ ExactPlan tail_begin(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
 void tail_finish(cph_index* h, BatchSet& s, const ExactPlan& pl, uint32_t nq, uint32_t k, const uint32_t* d_allow, int64_t* d_ids,
                  float* d_dist, uint32_t* d_count, DoneFlags done, hipStream_t st) {
     TailScanArgs a{};
-    a.raw = h->d_raw.p;
-    a.norm_sq = h->d_norm.p;
+    a.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, pl.gq, pl.part);
     a.allow = d_allow;
     a.base = (uint32_t)h->host.n;
     a.t = (uint32_t)h->tail;
-    a.D = h->L.D;
-    a.qpad = s.x_qpad.p;
-    a.qnorm = s.x_qnorm.p;
-    a.gq = pl.gq;
-    a.part = pl.part;
     a.k = k;
     a.C = pl.C;
     a.pools = s.x_pools.p;
@@ -989,9 +1006,9 @@ void tail_finish(cph_index* h, BatchSet& s, const ExactPlan& pl, uint32_t nq, ui
     f.done_flags = done.flags;
     f.done_seq = done.seq;
     for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile_q) {
-        a.q_first = f.q_first = q0;
-        a.q_count = f.q_count = std::min(pl.tile_q, nq - q0);
-        launch_tail_scan(a.D, dim3(pl.P, (a.q_count + pl.gq - 1) / pl.gq), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+        a.s.q_first = f.q_first = q0;
+        a.s.q_count = f.q_count = std::min(pl.tile_q, nq - q0);
+        CPH_LAUNCH_SCAN(tail_scan_kernel, a.s.D, dim3(pl.P, (f.q_count + pl.gq - 1) / pl.gq), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
         tail_fold(f, st);
     }
 }
@@ -1161,30 +1178,22 @@ void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq,
     HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
     HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));      // no query expands anything
     HIP_CHECK(hipEventRecord(s.ev0, st));
-    hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q, nq,
-                       nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * m);
-    HIP_CHECK(hipGetLastError());
+    pad_queries(h, d_raw_q, nullptr, nq, nq_pad, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * m, st);
     ExactArgs a{};
-    a.raw = h->d_raw.p;
-    a.norm_sq = h->d_norm.p;
+    a.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, pl.gq, pl.part);
     a.ids = d_list;
     a.m = (uint32_t)m;
-    a.D = D;
-    a.qpad = s.x_qpad.p;
-    a.qnorm = s.x_qnorm.p;
-    a.gq = pl.gq;
-    a.part = pl.part;
     a.k = k;
     a.C = pl.C;
     a.pools = s.x_pools.p;
     a.counts = s.x_counts.p;
     for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile_q) {
-        a.q_first = q0;
-        a.q_count = std::min(pl.tile_q, nq - q0);
-        const dim3 grid(pl.P, (a.q_count + pl.gq - 1) / pl.gq);
-        launch_exact_scan(D, grid, (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
-        hipLaunchKernelGGL(exact_merge_kernel, dim3(a.q_count), dim3(64), (size_t)pl.C * 8, st, (const unsigned long long*)s.x_pools.p,
-                           (const uint32_t*)s.x_counts.p, pl.P, a.q_first, a.q_count, k, pl.C,
+        const uint32_t q_count = std::min(pl.tile_q, nq - q0);
+        a.s.q_first = q0;
+        a.s.q_count = q_count;
+        CPH_LAUNCH_SCAN(exact_scan_kernel, D, dim3(pl.P, (q_count + pl.gq - 1) / pl.gq), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+        hipLaunchKernelGGL(exact_merge_kernel, dim3(q_count), dim3(64), (size_t)pl.C * 8, st, (const unsigned long long*)s.x_pools.p,
+                           (const uint32_t*)s.x_counts.p, pl.P, q0, q_count, k, pl.C,
                            (const uint32_t*)(h->ids_input ? h->d_rows.p : nullptr), d_ids, d_dist);
         HIP_CHECK(hipGetLastError());
     }
@@ -1473,24 +1482,16 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
     HIP_CHECK(hipEventRecord(s.ev0, st));
     const uint32_t* d_rows = h->ids_input ? h->d_rows.p : nullptr;
     if (nqs) {
-        hipLaunchKernelGGL(exact_pad_groups_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_raw_q,
-                           reinterpret_cast<const uint32_t*>(dt + o_scanq), nqs, nq_pad, (uint32_t)h->dim, D, s.x_qpad.p, s.x_qnorm.p,
-                           s.d_stats.p, n_exact);
-        HIP_CHECK(hipGetLastError());
+        pad_queries(h, d_raw_q, reinterpret_cast<const uint32_t*>(dt + o_scanq), nqs, nq_pad, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, n_exact, st);
         ExactGroupArgs a{};
-        a.raw = h->d_raw.p;
-        a.norm_sq = h->d_norm.p;
-        a.D = D;
-        a.qpad = s.x_qpad.p;
-        a.qnorm = s.x_qnorm.p;
-        a.gq = pl.gq;
+        a.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, pl.gq, 0);
         a.k = k;
         a.C = pl.C;
         a.pools = s.x_pools.p;
         a.counts = s.x_counts.p;
         for (size_t l = 0; l < n_launch; ++l) {
             a.items = reinterpret_cast<const ExactItem*>(dt + o_items) + pl.launch_items[l];
-            launch_exact_scan_groups(D, pl.launch_items[l + 1] - pl.launch_items[l], (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
+            CPH_LAUNCH_SCAN(exact_scan_groups_kernel, D, dim3(pl.launch_items[l + 1] - pl.launch_items[l]), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
             hipLaunchKernelGGL(exact_merge_groups_kernel, dim3(l_qhi[l] - l_qlo[l]), dim3(64), (size_t)pl.C * 8, st,
                                (const unsigned long long*)s.x_pools.p, (const uint32_t*)s.x_counts.p,
                                reinterpret_cast<const uint4*>(dt + o_desc) + l_qlo[l], k, pl.C, d_rows, d_ids, d_dist);
@@ -2406,26 +2407,19 @@ template <bool kFill>
 void range_scan_pass(cph_range* r, RangeArgs a, uint32_t q_first, uint32_t q_count) {
     const uint32_t per = 65535u * r->pl.gq;
     for (uint64_t q0 = q_first; q0 < (uint64_t)q_first + q_count; q0 += per) {
-        a.q_first = (uint32_t)q0;
-        a.q_count = (uint32_t)std::min<uint64_t>(per, (uint64_t)q_first + q_count - q0);
+        a.s.q_first = (uint32_t)q0;
+        a.s.q_count = (uint32_t)std::min<uint64_t>(per, (uint64_t)q_first + q_count - q0);
         // (the fill's arena index is relative to the TILE's first query, whichever launch writes it)
-        launch_range_scan<kFill>(r->h->L.D, dim3(r->pl.P, (a.q_count + r->pl.gq - 1) / r->pl.gq), (size_t)r->pl.gq * 12, r->st, a);
+        CPH_LAUNCH_SCAN(range_scan_kernel, a.s.D, dim3(r->pl.P, (a.s.q_count + r->pl.gq - 1) / r->pl.gq), (size_t)r->pl.gq * 12, r->st, a, kFill);
     }
 }
 
 RangeArgs range_args(const cph_range* r) {
-    const cph_index* h = r->h;
     RangeArgs a{};
-    a.raw = h->d_raw.p;
-    a.norm_sq = h->d_norm.p;
+    a.s = scan_common(r->h, r->s->qpad.p, r->s->qnorm.p, r->pl.gq, r->pl.part);
     a.ids = r->d_list;
     a.m = (uint32_t)r->m;
-    a.D = h->L.D;
-    a.qpad = r->s->qpad.p;
-    a.qnorm = r->s->qnorm.p;
     a.radius = r->s->d_rad.p;
-    a.gq = r->pl.gq;
-    a.part = r->pl.part;
     a.P = r->pl.P;
     a.counts = r->s->counts.p;
     a.offs = r->s->offs.p;
@@ -2508,9 +2502,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
             r->s->counts.alloc(n_cnt);
             r->s->d_stats.alloc(kStatWords);
             r->d_list = ef ? filter_id_list(ef, st) : nullptr;
-            hipLaunchKernelGGL(exact_pad_kernel, dim3(std::min<uint32_t>(nq_pad, (uint32_t)h->num_cus * 16)), dim3(64), 0, st, d_q, (uint32_t)n,
-                               nq_pad, (uint32_t)h->dim, D, r->s->qpad.p, r->s->qnorm.p, r->s->d_stats.p, (unsigned long long)(2 * n * r->m));
-            HIP_CHECK(hipGetLastError());
+            pad_queries(h, d_q, nullptr, (uint32_t)n, nq_pad, r->s->qpad.p, r->s->qnorm.p, r->s->d_stats.p, (unsigned long long)(2 * n * r->m), st);
             range_scan_pass<false>(r.get(), range_args(r.get()), 0, (uint32_t)n);
         }
         r->s->offs.alloc(n_cnt + 1);

@@ -171,17 +171,23 @@ __global__ __launch_bounds__(64) void exact_pad_groups_kernel(const float* __res
 }
 
 // ---- the scan ---------------------------------------------------------------------------------------------------------
-struct ExactArgs {
+// What every scan kernel is told about the rows, the padded queries and the cut of a launch (scan_common in
+// cphnsw_mi355x.hip fills it); the kernels' own argument structs embed it.
+struct ScanCommon {
     const float* raw;             // [n][D]
     const float* norm_sq;         // [n]
-    const uint32_t* ids;          // [m] ascending internal ids, or null: candidate c is id c
-    uint32_t m;                   // candidates
-    uint32_t D;
     const float* qpad;            // [nq_pad][D]
     const float* qnorm;           // [nq_pad]
-    uint32_t q_first, q_count;    // the queries of this launch
+    uint32_t D;
     uint32_t gq;                  // queries per group (a multiple of kExactQT)
+    uint32_t q_first, q_count;    // the queries of this launch   (the grouped scan: unused, its items state the cut)
     uint32_t part;                // candidates per part (a multiple of 64)
+};
+
+struct ExactArgs {
+    ScanCommon s;
+    const uint32_t* ids;          // [m] ascending internal ids, or null: candidate c is id c
+    uint32_t m;                   // candidates
     uint32_t k, C;                // pool capacity C = 2 Kp >= k + 64, a power of two
     unsigned long long* pools;    // [P][q_count][C]
     uint32_t* counts;             // [P][q_count]
@@ -271,28 +277,34 @@ __device__ __forceinline__ void exact_load_chunk(const float* __restrict__ row, 
     }
 }
 
-// SD: compile-time padded dimension (0: a.D, any power of two 16..2048); CH: dimensions a lane holds at a time (CH == SD:
-// the whole vector, loaded once per 64 candidates).
-// exact_scan_work is one work item, the body both scan kernels share: candidates [c_lo, c_hi) of the list `ids` (null:
-// candidate c is id c) against the nqg <= gq queries whose padded rows start at qbase / qnorms; pools / counts point at
-// the pool and the fill count of the item's first query, the other queries' follow.
-template <int SD, int CH>
-__device__ __forceinline__ void exact_scan_work(const float* __restrict__ raw, const float* __restrict__ norm_sq,
-                                                const uint32_t* __restrict__ ids, uint32_t D, uint32_t c_lo, uint32_t c_hi,
-                                                exact_uniform_ptr qbase, exact_uniform_ptr qnorms, uint32_t nqg, uint32_t gq,
-                                                unsigned long long* const pools, uint32_t* const counts, uint32_t k, uint32_t C,
-                                                unsigned char* smem) {
-    unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
-    uint32_t* s_thr = reinterpret_cast<uint32_t*>(sm + C);
-    uint32_t* s_cnt = s_thr + gq;
-    const int lane = threadIdx.x;
-    for (uint32_t i = lane; i < gq; i += 64) { s_thr[i] = 0xFFFFFFFFu; s_cnt[i] = 0; }
-    __syncthreads();
+// The candidate source of the exact, grouped and range scans: candidate c is ids[c] (null: c), and every id may be
+// selected -- the list is the filter.  (The tail's source, which tests a bitmap, is in device_tail.h.)
+struct ExactListSource {
+    const uint32_t* ids;
+    __device__ __forceinline__ uint32_t id(uint32_t c) const { return ids ? ids[c] : c; }
+    __device__ __forceinline__ bool allowed(uint32_t) const { return true; }
+};
 
+// THE candidate loop, the one place that forms a distance: every scan kernel (exact, grouped, tail, range) is this
+// function with a source and a sink of its own.  Candidates [c_lo, c_hi) of `src` against the nqg queries whose padded
+// rows start at qbase / qnorms; the workgroup is one wave.
+//   Source  id(c): candidate c's internal id;  allowed(id): whether it may be selected -- asked once per 64 candidates,
+//           before the query tiles.
+//   Sink    take(ql, d, id, live, lane): called by the whole wave once per (query ql of the group, 64 candidates) with
+//           each lane's distance; live is false in lanes behind c_hi or not allowed (their d and id are a neighbour's and
+//           must not be selected).  finish(nqg, lane): after the last candidate.  A sink sets its LDS up, and lets a barrier
+//           follow, where it is constructed.
+// SD: compile-time padded dimension (0: D, any power of two 16..2048); CH: dimensions a lane holds at a time (CH == SD:
+// the whole vector, loaded once per 64 candidates).
+template <int SD, int CH, class Source, class Sink>
+__device__ __forceinline__ void exact_scan_candidates(const float* __restrict__ raw, const float* __restrict__ norm_sq, uint32_t D,
+                                                      const Source src, uint32_t c_lo, uint32_t c_hi, exact_uniform_ptr qbase,
+                                                      exact_uniform_ptr qnorms, uint32_t nqg, const Sink sink) {
+    const int lane = threadIdx.x;
     for (uint32_t cb = c_lo; cb < c_hi; cb += 64) {
         const bool valid = cb + lane < c_hi;
-        const uint32_t cc = valid ? cb + lane : c_hi - 1;
-        const uint32_t id = ids ? ids[cc] : cc;
+        const uint32_t id = src.id(valid ? cb + lane : c_hi - 1);
+        const bool live = valid && src.allowed(id);
         const float* __restrict__ row = raw + (size_t)id * D;
         const float nrm = norm_sq[id];
         float v[CH];
@@ -317,51 +329,95 @@ __device__ __forceinline__ void exact_scan_work(const float* __restrict__ raw, c
                 const uint32_t ql = qt + t;                        // index inside the group
                 if (ql >= nqg) break;                              // (wave-uniform: the rows behind the group in its last tile)
                 const float dot = ((acc[t][0] + acc[t][4]) + (acc[t][1] + acc[t][5])) + ((acc[t][2] + acc[t][6]) + (acc[t][3] + acc[t][7]));
-                const uint32_t dbits = __float_as_uint(exact_from_dot(qnorms[ql], nrm, dot));
-                const bool pass = valid && dbits <= s_thr[ql];
-                const unsigned long long mask = __ballot(pass);
-                if (mask == 0) continue;
-                unsigned long long* pool = pools + (size_t)ql * C;
-                uint32_t cnt = s_cnt[ql];
-                const uint32_t add = (uint32_t)__popcll(mask);
-                if (cnt + add > C) {                               // (afterwards cnt <= k <= C - 64)
-                    uint32_t thr;
-                    cnt = exact_compact(sm, pool, cnt, k, lane, thr);
-                    if (lane == 0) s_thr[ql] = thr;
-                }
-                if (pass) pool[cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)dbits << 32) | id;
-                if (lane == 0) s_cnt[ql] = cnt + add;
+                sink.take(ql, exact_from_dot(qnorms[ql], nrm, dot), id, live, lane);
             }
         }
     }
-    // every pool: sorted, cut to k
-    for (uint32_t ql = 0; ql < nqg; ++ql) {
-        uint32_t cnt = s_cnt[ql], thr;
-        if (cnt) cnt = exact_compact(sm, pools + (size_t)ql * C, cnt, k, lane, thr);
-        if (lane == 0) counts[ql] = cnt;
+    sink.finish(nqg, lane);
+}
+
+// The top-k sink of the exact, grouped and tail scans: the pools and fill counts of the work item's queries (query ql's at
+// pools + ql * C, counts + ql).  LDS: C keys | gq thresholds | gq fill counts.  No barrier between lane 0's store of a
+// count or threshold and the wave's next load of it: the workgroup is ONE wave, whose LDS operations complete in program
+// order, and the store and the load are ordinary accesses of one address the compiler keeps in order.
+struct ExactPoolSink {
+    unsigned long long* sm;
+    uint32_t* s_thr;
+    uint32_t* s_cnt;
+    unsigned long long* pools;
+    uint32_t* counts;
+    uint32_t k, C;
+
+    __device__ __forceinline__ ExactPoolSink(unsigned char* smem, uint32_t gq, unsigned long long* pools_, uint32_t* counts_,
+                                             uint32_t k_, uint32_t C_)
+        : sm(reinterpret_cast<unsigned long long*>(smem)), s_thr(reinterpret_cast<uint32_t*>(sm + C_)), s_cnt(s_thr + gq),
+          pools(pools_), counts(counts_), k(k_), C(C_) {
+        for (uint32_t i = threadIdx.x; i < gq; i += 64) { s_thr[i] = 0xFFFFFFFFu; s_cnt[i] = 0; }
+        __syncthreads();
     }
+
+    __device__ __forceinline__ void take(uint32_t ql, float d, uint32_t id, bool live, int lane) const {
+        const uint32_t dbits = __float_as_uint(d);
+        const bool pass = live && dbits <= s_thr[ql];
+        const unsigned long long mask = __ballot(pass);
+        if (mask == 0) return;
+        unsigned long long* pool = pools + (size_t)ql * C;
+        uint32_t cnt = s_cnt[ql];
+        const uint32_t add = (uint32_t)__popcll(mask);
+        if (cnt + add > C) {                               // (afterwards cnt <= k <= C - 64)
+            uint32_t thr;
+            cnt = exact_compact(sm, pool, cnt, k, lane, thr);
+            if (lane == 0) s_thr[ql] = thr;
+        }
+        if (pass) pool[cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)dbits << 32) | id;
+        if (lane == 0) s_cnt[ql] = cnt + add;
+    }
+
+    // every pool: sorted, cut to k
+    __device__ __forceinline__ void finish(uint32_t nqg, int lane) const {
+        for (uint32_t ql = 0; ql < nqg; ++ql) {
+            uint32_t cnt = s_cnt[ql], thr;
+            if (cnt) cnt = exact_compact(sm, pools + (size_t)ql * C, cnt, k, lane, thr);
+            if (lane == 0) counts[ql] = cnt;
+        }
+    }
+};
+
+// The cut of a (parts, query groups) grid: workgroup (p, g) takes candidates [c_lo, c_hi) of m and the launch's queries
+// [ql_lo, ql_hi) (relative to q_first); q_rows / q_norms: where the padded rows and the norms of those queries start.
+struct ScanCut {
+    uint32_t c_lo, c_hi, ql_lo, ql_hi;
+    exact_uniform_ptr q_rows, q_norms;
+};
+
+__device__ __forceinline__ ScanCut scan_cut(const ScanCommon& s, uint32_t m, uint32_t D) {
+    ScanCut c;
+    c.c_lo = blockIdx.x * s.part;
+    c.c_hi = min(m, c.c_lo + s.part);
+    c.ql_lo = blockIdx.y * s.gq;
+    c.ql_hi = min(s.q_count, c.ql_lo + s.gq);
+    c.q_rows = (exact_uniform_ptr)(s.qpad + (size_t)(s.q_first + c.ql_lo) * D);
+    c.q_norms = (exact_uniform_ptr)(s.qnorm + s.q_first + c.ql_lo);
+    return c;
 }
 
 // Grid (P, G), one wave per workgroup; LDS: C keys + 2 gq words.
 template <int SD, int CH>
 __global__ __launch_bounds__(64) void exact_scan_kernel(ExactArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint32_t D = SD ? (uint32_t)SD : a.D;
-    const uint32_t p = blockIdx.x;
-    const uint32_t c_lo = p * a.part, c_hi = min(a.m, c_lo + a.part);
-    const uint32_t ql_lo = blockIdx.y * a.gq, ql_hi = min(a.q_count, ql_lo + a.gq);   // relative to q_first
-    if (c_lo >= c_hi || ql_lo >= ql_hi) return;
-    const size_t pool = (size_t)p * a.q_count + ql_lo;
-    exact_scan_work<SD, CH>(a.raw, a.norm_sq, a.ids, D, c_lo, c_hi, (exact_uniform_ptr)(a.qpad + (size_t)(a.q_first + ql_lo) * D),
-                            (exact_uniform_ptr)(a.qnorm + a.q_first + ql_lo), ql_hi - ql_lo, a.gq, a.pools + pool * a.C,
-                            a.counts + pool, a.k, a.C, smem);
+    const uint32_t D = SD ? (uint32_t)SD : a.s.D;
+    const ScanCut c = scan_cut(a.s, a.m, D);
+    if (c.c_lo >= c.c_hi || c.ql_lo >= c.ql_hi) return;
+    const size_t pool = (size_t)blockIdx.x * a.s.q_count + c.ql_lo;
+    exact_scan_candidates<SD, CH>(a.s.raw, a.s.norm_sq, D, ExactListSource{a.ids}, c.c_lo, c.c_hi, c.q_rows, c.q_norms, c.ql_hi - c.ql_lo,
+                                  ExactPoolSink(smem, a.s.gq, a.pools + pool * a.C, a.counts + pool, a.k, a.C));
 }
 
 // The grouped scan of a batch with per-query filters: ONE launch for every scanned (filter, query) pair.  A SEGMENT is a
 // filter's id list (or the whole index) together with the queries that name it, contiguous in the padded query array
 // (exact_pad_groups_kernel); the host planner (plan_exact_groups) cuts every segment into parts x query groups and
 // writes one descriptor per work item; workgroup b, one wave, runs item b.  Pool geometry, LDS and the arithmetic are
-// those of exact_scan_kernel -- the same body.
+// those of exact_scan_kernel -- the same source and sink.
 struct ExactItem {                // 32 bytes
     const uint32_t* ids;          // the segment's ascending id list, or null: candidate c is id c
     uint32_t c_lo, c_hi;          // candidates of this part
@@ -371,12 +427,8 @@ struct ExactItem {                // 32 bytes
 };
 
 struct ExactGroupArgs {
-    const float* raw;             // [n][D]
-    const float* norm_sq;         // [n]
-    uint32_t D;
-    const float* qpad;            // [nq_pad][D], permuted
-    const float* qnorm;           // [nq_pad]
-    uint32_t gq, k, C;
+    ScanCommon s;                 // (qpad: permuted)
+    uint32_t k, C;
     unsigned long long* pools;    // [pools of the launch][C]
     uint32_t* counts;             // [pools of the launch]
     const ExactItem* items;       // [gridDim.x]
@@ -390,25 +442,22 @@ __global__ __launch_bounds__(64) void exact_scan_groups_kernel(ExactGroupArgs a)
     ExactItem it;
     it.ids = reinterpret_cast<const uint32_t*>((uint64_t)w[0] | ((uint64_t)w[1] << 32));
     it.c_lo = w[2]; it.c_hi = w[3]; it.q_lo = w[4]; it.q_cnt = w[5]; it.pool = w[6];
-    const uint32_t D = SD ? (uint32_t)SD : a.D;
+    const uint32_t D = SD ? (uint32_t)SD : a.s.D;
     if (it.c_lo >= it.c_hi || it.q_cnt == 0) return;
-    exact_scan_work<SD, CH>(a.raw, a.norm_sq, it.ids, D, it.c_lo, it.c_hi, (exact_uniform_ptr)(a.qpad + (size_t)it.q_lo * D),
-                            (exact_uniform_ptr)(a.qnorm + it.q_lo), it.q_cnt, a.gq, a.pools + (size_t)it.pool * a.C,
-                            a.counts + it.pool, a.k, a.C, smem);
+    exact_scan_candidates<SD, CH>(a.s.raw, a.s.norm_sq, D, ExactListSource{it.ids}, it.c_lo, it.c_hi,
+                                  (exact_uniform_ptr)(a.s.qpad + (size_t)it.q_lo * D), (exact_uniform_ptr)(a.s.qnorm + it.q_lo), it.q_cnt,
+                                  ExactPoolSink(smem, a.s.gq, a.pools + (size_t)it.pool * a.C, a.counts + it.pool, a.k, a.C));
 }
 
-// One wave per query of the launch: the P sorted part lists -> out rows [k], ascending, ids through `rows` if given,
-// padded with -1 / FLT_MAX.  LDS: C keys: the lower half holds the Kp smallest keys so far, ascending; a part's list is
-// laid behind it in descending order and one bitonic merge (log C stages, not a sort) leaves all C ascending again.
-// exact_merge_query is one query's fold, shared by both merge kernels: its part p's pool is pool index first + p * stride;
-// the row goes to out row `out_row`.
-__device__ __forceinline__ void exact_merge_query(const unsigned long long* __restrict__ pools, const uint32_t* __restrict__ counts,
-                                                  size_t first, uint32_t stride, uint32_t P, uint32_t k, uint32_t C,
-                                                  const uint32_t* __restrict__ rows, int64_t* __restrict__ out_ids,
-                                                  float* __restrict__ out_dist, size_t out_row, unsigned char* smem) {
-    unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
-    const int lane = threadIdx.x;
+// One query's P sorted part lists (part p's pool is pool index first + p * stride) -> sm[0 .. Kp), Kp = C / 2, ascending,
+// padded with kExactNoKey; returns the lists' total length.  sm: C keys: the lower half holds the Kp smallest keys so far,
+// ascending; a part's list is laid behind it in descending order and one bitonic merge (log C stages, not a sort) leaves
+// all C ascending again.  One wave.
+__device__ __forceinline__ uint32_t exact_fold_parts(unsigned long long* sm, const unsigned long long* __restrict__ pools,
+                                                     const uint32_t* __restrict__ counts, size_t first, uint32_t stride, uint32_t P,
+                                                     uint32_t C, int lane) {
     const uint32_t Kp = C / 2;
+    uint32_t total = 0;
     for (uint32_t i = lane; i < Kp; i += 64) sm[i] = kExactNoKey;
     for (uint32_t p = 0; p < P; ++p) {
         const uint32_t cnt = counts[first + (size_t)p * stride];    // <= k <= Kp
@@ -416,7 +465,21 @@ __device__ __forceinline__ void exact_merge_query(const unsigned long long* __re
         for (uint32_t i = lane; i < Kp; i += 64) sm[C - 1 - i] = i < cnt ? pool[i] : kExactNoKey;
         __syncthreads();
         exact_merge_keys(sm, C, lane);
+        total += cnt;
     }
+    return total;
+}
+
+// One wave per query of the launch: the P sorted part lists -> out rows [k], ascending, ids through `rows` if given,
+// padded with -1 / FLT_MAX.  LDS: C keys.  exact_merge_query is one query's fold, shared by both merge kernels; the row
+// goes to out row `out_row`.
+__device__ __forceinline__ void exact_merge_query(const unsigned long long* __restrict__ pools, const uint32_t* __restrict__ counts,
+                                                  size_t first, uint32_t stride, uint32_t P, uint32_t k, uint32_t C,
+                                                  const uint32_t* __restrict__ rows, int64_t* __restrict__ out_ids,
+                                                  float* __restrict__ out_dist, size_t out_row, unsigned char* smem) {
+    unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
+    const int lane = threadIdx.x;
+    (void)exact_fold_parts(sm, pools, counts, first, stride, P, C, lane);
     __syncthreads();
     const size_t o = out_row * k;
     for (uint32_t i = lane; i < k; i += 64) {
@@ -595,18 +658,15 @@ inline ExactGroupPlan plan_exact_groups(const uint64_t* seg_m, const uint64_t* s
     return pl;
 }
 
-inline void launch_exact_scan_groups(uint32_t D, uint32_t items, size_t lds, hipStream_t st, const ExactGroupArgs& a) {
-    if (D == 128) hipLaunchKernelGGL((exact_scan_groups_kernel<128, 128>), dim3(items), dim3(64), lds, st, a);
-    else if (D == 1024) hipLaunchKernelGGL((exact_scan_groups_kernel<1024, 64>), dim3(items), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((exact_scan_groups_kernel<0, 16>), dim3(items), dim3(64), lds, st, a);
-    HIP_CHECK(hipGetLastError());
-}
-
-inline void launch_exact_scan(uint32_t D, dim3 grid, size_t lds, hipStream_t st, const ExactArgs& a) {
-    if (D == 128) hipLaunchKernelGGL((exact_scan_kernel<128, 128>), grid, dim3(64), lds, st, a);
-    else if (D == 1024) hipLaunchKernelGGL((exact_scan_kernel<1024, 64>), grid, dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((exact_scan_kernel<0, 16>), grid, dim3(64), lds, st, a);
-    HIP_CHECK(hipGetLastError());
-}
+// Launches the <SD, CH> instantiation of a scan kernel (one wave per workgroup) that serves padded dimension D: the whole
+// vector in registers at 128, 64 dimensions at a time at 1024, the generic 16 at any other.  Template arguments of the
+// kernel behind <SD, CH> follow `args`.
+#define CPH_LAUNCH_SCAN(KERNEL, D, grid, lds, st, args, ...)                                                           \
+    do {                                                                                                               \
+        if ((D) == 128) hipLaunchKernelGGL((KERNEL<128, 128, ##__VA_ARGS__>), grid, dim3(64), lds, st, args);          \
+        else if ((D) == 1024) hipLaunchKernelGGL((KERNEL<1024, 64, ##__VA_ARGS__>), grid, dim3(64), lds, st, args);    \
+        else hipLaunchKernelGGL((KERNEL<0, 16, ##__VA_ARGS__>), grid, dim3(64), lds, st, args);                        \
+        HIP_CHECK(hipGetLastError());                                                                                  \
+    } while (0)
 
 }  // namespace cph

@@ -1,8 +1,8 @@
 // device_range.h — range search (cph_range_search_*): every allowed id closer than a per-query radius, in CSR form.
 //
-// The distance of a (query, id) pair is the one of device_exact.h -- the same loads, the same eight FMA chains, the same
-// reduction tree, exact_from_dot on top -- so its bits are those the exact search and the graph search report.  What is
-// new is everything behind the distance: the selection is a threshold, not a top-k, and the output has no fixed shape.
+// The distance of a (query, id) pair is the one of device_exact.h, formed by the same function (exact_scan_candidates),
+// so its bits are those the exact search and the graph search report.  What is new is everything behind the distance
+// (RangeSink): the selection is a threshold, not a top-k, and the output has no fixed shape.
 //
 // Two passes over the candidates, one kernel body (range_scan_kernel<SD, CH, kFill>), the work split of exact_scan_kernel
 // (P contiguous parts x G query groups, one wave per workgroup, a lane owns a candidate):
@@ -39,105 +39,74 @@ constexpr uint32_t kRangeScanSpan = 2048;     // counters per block of the offse
 
 // ---- the scan: count and fill -------------------------------------------------------------------------------------------
 struct RangeArgs {
-    const float* raw;                     // [n][D]
-    const float* norm_sq;                 // [n]
+    ScanCommon s;
     const uint32_t* ids;                  // [m] ascending internal ids, or null: candidate c is id c
     uint32_t m;                           // candidates
-    uint32_t D;
-    const float* qpad;                    // [nq_pad][D]
-    const float* qnorm;                   // [nq_pad]
+    uint32_t P;                           // parts
     const float* radius;                  // [nq]
-    uint32_t q_first, q_count;            // the queries of this launch
-    uint32_t gq;                          // queries per group (a multiple of kExactQT)
-    uint32_t part, P;                     // candidates per part (a multiple of 64), parts
     uint32_t* counts;                     // [nq][P]: written by the count pass
     const unsigned long long* offs;       // [nq * P + 1]: read by the fill pass
     unsigned long long tile_base;         // offs[q_first * P]: the arena starts there
     unsigned long long* arena;
 };
 
-// Grid (P, G), one wave per workgroup; LDS: gq radii + gq counters (count) or gq 64-bit write positions (fill).
+// The sink of exact_scan_candidates for a part's hits of the queries q0 .. q0 + nqg - 1: counted (count pass) or written
+// to the arena behind the part's offset (fill pass).  LDS: gq counters (count) or gq 64-bit write positions (fill), then
+// gq radii.
+template <bool kFill>
+struct RangeSink {
+    unsigned long long* s_pos;            // fill: next free arena index
+    uint32_t* s_cnt;                      // count: hits so far
+    float* s_rad;
+    unsigned long long* arena;
+    uint32_t* counts;                     // the counter of (query q0, this part); query q0 + i: counts[i * P]
+    uint32_t P;
+
+    __device__ __forceinline__ RangeSink(unsigned char* smem, const RangeArgs& a, uint32_t q0, uint32_t nqg)
+        : s_pos(reinterpret_cast<unsigned long long*>(smem)), s_cnt(reinterpret_cast<uint32_t*>(smem)),
+          s_rad(reinterpret_cast<float*>(smem + (size_t)a.s.gq * 8)), arena(a.arena), counts(a.counts + (size_t)q0 * a.P + blockIdx.x),
+          P(a.P) {
+        for (uint32_t i = threadIdx.x; i < nqg; i += 64) {
+            s_rad[i] = a.radius[q0 + i];
+            if constexpr (kFill) s_pos[i] = a.offs[(size_t)(q0 + i) * a.P + blockIdx.x] - a.tile_base;
+            else s_cnt[i] = 0;
+        }
+        __syncthreads();
+    }
+
+    __device__ __forceinline__ void take(uint32_t ql, float d, uint32_t id, bool live, int lane) const {
+        const bool hit = live && d < s_rad[ql];            // strict; a NaN radius selects nothing
+        const unsigned long long mask = __ballot(hit);
+        if (mask == 0) return;
+        const uint32_t add = (uint32_t)__popcll(mask);
+        if constexpr (kFill) {
+            // (every lane reads the position lane 0 stored after the query's previous hits: no barrier in between, for
+            //  ExactPoolSink's reason -- one wave, LDS in program order)
+            const unsigned long long at = s_pos[ql];
+            if (hit) arena[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)__float_as_uint(d) << 32) | id;
+            if (lane == 0) s_pos[ql] = at + add;
+        } else {
+            if (lane == 0) s_cnt[ql] += add;
+        }
+    }
+
+    __device__ __forceinline__ void finish(uint32_t nqg, int lane) const {
+        if constexpr (!kFill) {
+            __syncthreads();
+            for (uint32_t i = lane; i < nqg; i += 64) counts[(size_t)i * P] = s_cnt[i];
+        }
+    }
+};
+
+// Grid (P, G), one wave per workgroup; LDS: 12 gq bytes (RangeSink).  A part behind the candidates still writes its zeros.
 template <int SD, int CH, bool kFill>
 __global__ __launch_bounds__(64) void range_scan_kernel(RangeArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    unsigned long long* s_pos = reinterpret_cast<unsigned long long*>(smem);          // fill: next free arena index
-    uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem);                              // count: hits so far
-    float* s_rad = reinterpret_cast<float*>(smem + (size_t)a.gq * 8);
-    const uint32_t D = SD ? (uint32_t)SD : a.D;
-    const int lane = threadIdx.x;
-    const uint32_t p = blockIdx.x;
-    const uint32_t c_lo = p * a.part, c_hi = min(a.m, c_lo + a.part);
-    const uint32_t ql_lo = blockIdx.y * a.gq, ql_hi = min(a.q_count, ql_lo + a.gq);     // relative to q_first
-    if (ql_lo >= ql_hi) return;
-    const uint32_t nqg = ql_hi - ql_lo, q0 = a.q_first + ql_lo;
-    const exact_uniform_ptr qbase = (exact_uniform_ptr)(a.qpad + (size_t)q0 * D);
-    const exact_uniform_ptr qnorms = (exact_uniform_ptr)(a.qnorm + q0);
-    for (uint32_t i = lane; i < nqg; i += 64) {
-        s_rad[i] = a.radius[q0 + i];
-        if constexpr (kFill) s_pos[i] = a.offs[(size_t)(q0 + i) * a.P + p] - a.tile_base;
-        else s_cnt[i] = 0;
-    }
-    __syncthreads();
-
-    for (uint32_t cb = c_lo; cb < c_hi; cb += 64) {
-        const bool valid = cb + lane < c_hi;
-        const uint32_t cc = valid ? cb + lane : c_hi - 1;
-        const uint32_t id = a.ids ? a.ids[cc] : cc;
-        const float* __restrict__ row = a.raw + (size_t)id * D;
-        const float nrm = a.norm_sq[id];
-        float v[CH];
-        if constexpr (SD == CH) exact_load_chunk<CH>(row, v);
-        for (uint32_t qt = 0; qt < nqg; qt += kExactQT) {
-            float acc[kExactQT][8];
-#pragma unroll
-            for (int t = 0; t < kExactQT; ++t)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[t][j] = 0.0f;
-            if constexpr (SD == CH) {
-                exact_fma_chunk<CH>(v, qbase + (size_t)qt * D, D, acc);
-            } else {
-#pragma unroll 2
-                for (uint32_t base = 0; base < D; base += CH) {
-                    exact_load_chunk<CH>(row + base, v);
-                    exact_fma_chunk<CH>(v, qbase + (size_t)qt * D + base, D, acc);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < kExactQT; ++t) {
-                const uint32_t ql = qt + t;                        // index inside the group
-                if (ql >= nqg) break;                              // (wave-uniform: the rows behind the group in its last tile)
-                const float dot = ((acc[t][0] + acc[t][4]) + (acc[t][1] + acc[t][5])) + ((acc[t][2] + acc[t][6]) + (acc[t][3] + acc[t][7]));
-                const float d = exact_from_dot(qnorms[ql], nrm, dot);
-                const bool hit = valid && d < s_rad[ql];           // strict; a NaN radius selects nothing
-                const unsigned long long mask = __ballot(hit);
-                if (mask == 0) continue;
-                const uint32_t add = (uint32_t)__popcll(mask);
-                if constexpr (kFill) {
-                    // (every lane reads the position lane 0 stored after the query's previous hits: no barrier in between,
-                    //  as with s_cnt in exact_scan_work -- the workgroup is ONE wave, whose LDS operations complete in
-                    //  program order, and the store and the load are ordinary accesses of one address the compiler keeps
-                    //  in order)
-                    const unsigned long long at = s_pos[ql];
-                    if (hit) a.arena[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)__float_as_uint(d) << 32) | id;
-                    if (lane == 0) s_pos[ql] = at + add;
-                } else {
-                    if (lane == 0) s_cnt[ql] += add;
-                }
-            }
-        }
-    }
-    if constexpr (!kFill) {
-        __syncthreads();
-        for (uint32_t i = lane; i < nqg; i += 64) a.counts[(size_t)(q0 + i) * a.P + p] = s_cnt[i];
-    }
-}
-
-template <bool kFill>
-inline void launch_range_scan(uint32_t D, dim3 grid, size_t lds, hipStream_t st, const RangeArgs& a) {
-    if (D == 128) hipLaunchKernelGGL((range_scan_kernel<128, 128, kFill>), grid, dim3(64), lds, st, a);
-    else if (D == 1024) hipLaunchKernelGGL((range_scan_kernel<1024, 64, kFill>), grid, dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((range_scan_kernel<0, 16, kFill>), grid, dim3(64), lds, st, a);
-    HIP_CHECK(hipGetLastError());
+    const uint32_t D = SD ? (uint32_t)SD : a.s.D;
+    const ScanCut c = scan_cut(a.s, a.m, D);
+    if (c.ql_lo >= c.ql_hi) return;
+    exact_scan_candidates<SD, CH>(a.s.raw, a.s.norm_sq, D, ExactListSource{a.ids}, c.c_lo, c.c_hi, c.q_rows, c.q_norms, c.ql_hi - c.ql_lo,
+                                  RangeSink<kFill>(smem, a, a.s.q_first + c.ql_lo, c.ql_hi - c.ql_lo));
 }
 
 // ---- offsets: exclusive uint64 scan of counts[n_cnt] -------------------------------------------------------------------

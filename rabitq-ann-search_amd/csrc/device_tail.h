@@ -10,14 +10,12 @@
 //                       arithmetic of the builder's row_norms_kernel (ONE fmaf chain over the first dim elements, so a
 //                       tail row has the norm bits the same floats would get from a build), extends the row map by the
 //                       identity, the label column by the given labels and the removed bitmap by clear bits.
-//   tail_scan_kernel    the scan of device_exact.h (its chains, its tree, exact_from_dot, query values through scalar
-//                       loads, the pool / threshold / compaction selection) over the candidates n_b .. n_b + t - 1, with
-//                       the allowed bit of the effective filter tested where `pass` is formed: no id list per filter is
-//                       made and no count comes to the host.  A body of its own next to exact_scan_work, so that the
-//                       exact instantiations keep the code they had; the helpers are shared.  Parts over t come from
-//                       plan_exact.
-//   tail_fold_kernel    one wave per query: folds the query's P sorted tail lists in LDS (exact_merge_query's bitonic
-//                       merges), stages the graph's row, places every entry at its rank in the stable merge (graph
+//   tail_scan_kernel    the scan of device_exact.h (exact_scan_candidates into the top-k pools of ExactPoolSink) over the
+//                       candidates n_b .. n_b + t - 1.  Only the candidate source is the tail's own: it tests the allowed
+//                       bit of the effective filter, once per 64 candidates, so no id list per filter is made and no
+//                       count comes to the host.  Parts over t come from plan_exact.
+//   tail_fold_kernel    one wave per query: folds the query's P sorted tail lists in LDS (exact_fold_parts, the fold of
+//                       exact_merge_query), stages the graph's row, places every entry at its rank in the stable merge (graph
 //                       entry first where the float values are equal -- merge_parts_kernel's rule) and writes the
 //                       first k over the graph's row.  The whole row is in LDS before the first store, so it folds in
 //                       place, also rows that live in pinned host memory (small batches).
@@ -74,100 +72,32 @@ inline void tail_append(const TailAppendArgs& a, hipStream_t st) {
 
 // ---- the scan -------------------------------------------------------------------------------------------------------------
 struct TailScanArgs {
-    const float* raw;             // [n_b + t][D]
-    const float* norm_sq;         // [n_b + t]
+    ScanCommon s;                 // (raw, norm_sq: [n_b + t] rows)
     const uint32_t* allow;        // the effective filter's bitmap over all ids, or null: every id
     uint32_t base, t;             // tail candidate c is id base + c
-    uint32_t D;
-    const float* qpad;            // [nq_pad][D]
-    const float* qnorm;           // [nq_pad]
-    uint32_t q_first, q_count;    // the queries of this launch
-    uint32_t gq, part, k, C;      // as in ExactArgs
+    uint32_t k, C;                // as in ExactArgs
     unsigned long long* pools;    // [P][q_count][C]
     uint32_t* counts;             // [P][q_count]
+};
+
+// The tail's candidate source: candidate c is id base + c, allowed where the effective filter's bit is set.
+struct TailSource {
+    const uint32_t* allow;
+    uint32_t base;
+    __device__ __forceinline__ uint32_t id(uint32_t c) const { return base + c; }
+    __device__ __forceinline__ bool allowed(uint32_t id) const { return allow == nullptr || ((allow[id >> 5] >> (id & 31)) & 1u); }
 };
 
 // Grid (P, G), one wave per workgroup; LDS: C keys + 2 gq words -- the geometry of exact_scan_kernel.
 template <int SD, int CH>
 __global__ __launch_bounds__(64) void tail_scan_kernel(TailScanArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint32_t D = SD ? (uint32_t)SD : a.D;
-    const uint32_t p = blockIdx.x;
-    const uint32_t c_lo = p * a.part, c_hi = min(a.t, c_lo + a.part);
-    const uint32_t ql_lo = blockIdx.y * a.gq, ql_hi = min(a.q_count, ql_lo + a.gq);   // relative to q_first
-    if (c_lo >= c_hi || ql_lo >= ql_hi) return;
-    const uint32_t nqg = ql_hi - ql_lo, gq = a.gq, k = a.k, C = a.C;
-    const size_t pool0 = (size_t)p * a.q_count + ql_lo;
-    unsigned long long* const pools = a.pools + pool0 * C;
-    uint32_t* const counts = a.counts + pool0;
-    const exact_uniform_ptr qbase = (exact_uniform_ptr)(a.qpad + (size_t)(a.q_first + ql_lo) * D);
-    const exact_uniform_ptr qnorms = (exact_uniform_ptr)(a.qnorm + a.q_first + ql_lo);
-
-    unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
-    uint32_t* s_thr = reinterpret_cast<uint32_t*>(sm + C);
-    uint32_t* s_cnt = s_thr + gq;
-    const int lane = threadIdx.x;
-    for (uint32_t i = lane; i < gq; i += 64) { s_thr[i] = 0xFFFFFFFFu; s_cnt[i] = 0; }
-    __syncthreads();
-
-    for (uint32_t cb = c_lo; cb < c_hi; cb += 64) {
-        const bool valid = cb + lane < c_hi;
-        const uint32_t id = a.base + (valid ? cb + lane : c_hi - 1);
-        const bool allowed = valid && (a.allow == nullptr || ((a.allow[id >> 5] >> (id & 31)) & 1u));
-        const float* __restrict__ row = a.raw + (size_t)id * D;
-        const float nrm = a.norm_sq[id];
-        float v[CH];
-        if constexpr (SD == CH) exact_load_chunk<CH>(row, v);
-        for (uint32_t qt = 0; qt < nqg; qt += kExactQT) {
-            float acc[kExactQT][8];
-#pragma unroll
-            for (int t = 0; t < kExactQT; ++t)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[t][j] = 0.0f;
-            if constexpr (SD == CH) {
-                exact_fma_chunk<CH>(v, qbase + (size_t)qt * D, D, acc);
-            } else {
-#pragma unroll 2
-                for (uint32_t b = 0; b < D; b += CH) {
-                    exact_load_chunk<CH>(row + b, v);
-                    exact_fma_chunk<CH>(v, qbase + (size_t)qt * D + b, D, acc);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < kExactQT; ++t) {
-                const uint32_t ql = qt + t;                        // index inside the group
-                if (ql >= nqg) break;                              // (wave-uniform)
-                const float dot = ((acc[t][0] + acc[t][4]) + (acc[t][1] + acc[t][5])) + ((acc[t][2] + acc[t][6]) + (acc[t][3] + acc[t][7]));
-                const uint32_t dbits = __float_as_uint(exact_from_dot(qnorms[ql], nrm, dot));
-                const bool pass = allowed && dbits <= s_thr[ql];
-                const unsigned long long mask = __ballot(pass);
-                if (mask == 0) continue;
-                unsigned long long* pool = pools + (size_t)ql * C;
-                uint32_t cnt = s_cnt[ql];
-                const uint32_t add = (uint32_t)__popcll(mask);
-                if (cnt + add > C) {                               // (afterwards cnt <= k <= C - 64)
-                    uint32_t thr;
-                    cnt = exact_compact(sm, pool, cnt, k, lane, thr);
-                    if (lane == 0) s_thr[ql] = thr;
-                }
-                if (pass) pool[cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)dbits << 32) | id;
-                if (lane == 0) s_cnt[ql] = cnt + add;
-            }
-        }
-    }
-    // every pool: sorted, cut to k
-    for (uint32_t ql = 0; ql < nqg; ++ql) {
-        uint32_t cnt = s_cnt[ql], thr;
-        if (cnt) cnt = exact_compact(sm, pools + (size_t)ql * C, cnt, k, lane, thr);
-        if (lane == 0) counts[ql] = cnt;
-    }
-}
-
-inline void launch_tail_scan(uint32_t D, dim3 grid, size_t lds, hipStream_t st, const TailScanArgs& a) {
-    if (D == 128) hipLaunchKernelGGL((tail_scan_kernel<128, 128>), grid, dim3(64), lds, st, a);
-    else if (D == 1024) hipLaunchKernelGGL((tail_scan_kernel<1024, 64>), grid, dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((tail_scan_kernel<0, 16>), grid, dim3(64), lds, st, a);
-    HIP_CHECK(hipGetLastError());
+    const uint32_t D = SD ? (uint32_t)SD : a.s.D;
+    const ScanCut c = scan_cut(a.s, a.t, D);
+    if (c.c_lo >= c.c_hi || c.ql_lo >= c.ql_hi) return;
+    const size_t pool = (size_t)blockIdx.x * a.s.q_count + c.ql_lo;
+    exact_scan_candidates<SD, CH>(a.s.raw, a.s.norm_sq, D, TailSource{a.allow, a.base}, c.c_lo, c.c_hi, c.q_rows, c.q_norms,
+                                  c.ql_hi - c.ql_lo, ExactPoolSink(smem, a.s.gq, a.pools + pool * a.C, a.counts + pool, a.k, a.C));
 }
 
 // ---- the fold -------------------------------------------------------------------------------------------------------------
@@ -191,20 +121,10 @@ __global__ __launch_bounds__(64) void tail_fold_kernel(TailFoldArgs a) {
     int64_t* g_id = reinterpret_cast<int64_t*>(sm + a.C);
     float* g_d = reinterpret_cast<float*>(g_id + a.k);
     const int lane = threadIdx.x;
-    const uint32_t k = a.k, C = a.C, Kp = C / 2;
+    const uint32_t k = a.k;
     const size_t qi = (size_t)a.q_first + blockIdx.x, o = qi * k;
-    // the tail's top-k: sm[0 .. Kp) ascending, behind the keys kExactNoKey
-    for (uint32_t i = lane; i < Kp; i += 64) sm[i] = kExactNoKey;
-    uint32_t tn = 0;
-    for (uint32_t p = 0; p < a.P; ++p) {
-        const size_t pi = (size_t)p * a.q_count + blockIdx.x;
-        const uint32_t cnt = a.counts[pi];                          // <= k <= Kp
-        const unsigned long long* pool = a.pools + pi * C;
-        for (uint32_t i = lane; i < Kp; i += 64) sm[C - 1 - i] = i < cnt ? pool[i] : kExactNoKey;
-        __syncthreads();
-        exact_merge_keys(sm, C, lane);
-        tn += cnt;
-    }
+    // the tail's top-k: sm[0 .. tn) ascending
+    uint32_t tn = exact_fold_parts(sm, a.pools, a.counts, blockIdx.x, a.q_count, a.P, a.C, lane);
     tn = tn < k ? tn : k;
     // the graph's row, all of it, before anything is stored
     uint32_t gn = 0;

@@ -199,8 +199,8 @@ def main():
         fh.write(("```\n" + json.dumps(kern, indent=1) + "\n```\n\n") if kern else NM + "\n\n")
         fh.write("## add() and compact()\n\n")
         fh.write(("```\n" + "\n".join(json.dumps(r) for r in life) + "\n```\n\n") if life else NM + "\n\n")
-        fh.write("## Resource usage of the exact instantiations\n\nThe shared scan body (`exact_scan_work`) is not edited: the tail scan is "
-                 "a body of its own in `device_tail.h`, so the exact instantiations compile from the text they had "
+        fh.write("## Resource usage of the scan instantiations\n\nThe tail scan is the candidate loop of the exact scan "
+                 "(`exact_scan_candidates`, `device_exact.h`) with a candidate source of its own "
                  "(`hipcc -Rpass-analysis=kernel-resource-usage`, `scripts/resource_usage.py`).\n\n")
         if args.resource_usage and os.path.exists(args.resource_usage):
             fh.write("```\n" + open(args.resource_usage).read().rstrip() + "\n```\n\n")

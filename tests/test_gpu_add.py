@@ -136,6 +136,36 @@ def test_every_fixture_graph_route_equals_model(cph, oracle, gold, tmp_path, cas
         A_ix.search_batch(Q, 1025)
 
 
+@pytest.mark.parametrize("name", ("g16", "g1024"))
+def test_filtered_tail_scan_generic_and_1024(cph, oracle, gold, tmp_path, name):
+    """The tail scan's candidate source (the allowed bit of the effective filter) in the instantiations the `built` index
+    (D = 128) does not reach: the generic one (g16) and <1024, 64> (g1024).  65 tail rows: one past the 64-lane block."""
+    bits, t = max(DATASETS[name]["bits"]), 65
+    A_ix, B_ix = _load(cph, name, bits), _load(cph, name, bits)          # B: the untouched twin
+    nb = A_ix.size
+    rng = np.random.default_rng(zlib.crc32(name.encode()) + 1)
+    A = _rows_like(name, rng, t)
+    Q = gold[f"Q/{name}"]
+    new = A_ix.add(A)
+    assert np.array_equal(new, np.arange(nb, nb + t))
+    T = oracle_tail_dist(cph, oracle, DATASETS[name]["dim"], bits, A, Q, tmp_path)
+    M = rng.random(nb + t) < 0.5                                         # internal ids
+    no_tail = M.copy()
+    no_tail[nb:] = False
+    assert M[nb:].any() and not M[nb:].all() and M[:nb].any()
+    for where, mask in (("mask", M), ("no tail row allowed", no_tail)):
+        fa, fb = A_ix.make_filter(mask), B_ix.make_filter(mask[:nb])
+        for k in (1, 100):
+            g_ids, g_d = B_ix.search_batch(Q, k, filter=fb)
+            wi, wd = fold(g_ids, g_d, T, new, mask[nb:], k)
+            ids, d = A_ix.search_batch(Q, k, filter=fa)
+            assert A_ix.last_search_stats()["expansions"] > 0            # the graph route: the tail is scanned by its own kernel
+            assert np.array_equal(ids, wi), (name, where, k)
+            assert _beq(d, wd), (name, where, k)
+            if not mask[nb:].any():                                      # the twin's rows
+                assert np.array_equal(ids, g_ids) and _beq(d, g_d), (name, where, k)
+
+
 # ---- 3. growth -------------------------------------------------------------------------------------------------------------
 def test_growth_in_five_calls_equals_one_call(cph, gold):
     name, bits = "g16", 4

@@ -383,9 +383,57 @@ class CPIndex:
 
     @staticmethod
     def _filter_handles(fs, rep=None):
-        """cph_filter* array of a filter list: [f] of replica `rep`, or (rep None) [f][replica]."""
-        hs = [h.value for f in fs for h in (f._hs if rep is None else [f._hs[rep]])]
+        """cph_filter* array of a filter list: [f] of replica `rep`, or (rep None) [f][replica]; of filters of a
+        partitioned index: their cph_parts_filter*."""
+        hs = [h.value for f in fs for h in ([f._pf] if f._pf is not None else f._hs if rep is None else [f._hs[rep]])]
         return (C.c_void_p * len(hs))(*hs) if hs else None
+
+    def _filter_args(self, fs, fo, f, rep):
+        """(filters, n_filters, filter_of) of a C entry that takes all three: the list `fs` with `fo`, or the one filter
+        `f` (filter_of NULL), or none.  rep: as in _filter_handles."""
+        if fs is not None:
+            return self._filter_handles(fs, rep), len(fs), fo.ctypes.data
+        if f is not None:
+            return self._filter_handles([f], rep), 1, None
+        return None, 0, None
+
+    # (handle kind, call form) -> the C entry of a batch in host memory, in device memory (replicas: the replica's own)
+    _BATCH_ENTRY = {
+        ("single", "filtered"): ("cph_search_batch_filtered", "cph_search_batch_device_filtered"),
+        ("single", "exact"): ("cph_search_batch_exact", "cph_search_batch_exact_device"),
+        ("single", "filters"): ("cph_search_batch_filters", "cph_search_batch_filters_device"),
+        ("multi", "filtered"): ("cph_multi_search_batch_filtered", "cph_search_batch_device_filtered"),
+        ("multi", "exact"): ("cph_multi_search_batch_exact", "cph_search_batch_exact_device"),
+        ("multi", "filters"): ("cph_multi_search_batch_filters", "cph_search_batch_filters_device"),
+        ("parts", "filtered"): ("cph_parts_search_batch_filtered", "cph_parts_search_batch_device_filtered"),
+        ("parts", "exact"): ("cph_parts_search_batch_exact", "cph_parts_search_batch_exact_device"),
+        ("parts", "filters"): ("cph_parts_search_batch_filters", "cph_parts_search_batch_filters_device"),
+    }
+
+    def _batch_call(self, qp, n, k, filter, exact, filter_of, out, rep=None, stream=None):
+        """One batch through its C entry.  qp, out = (ids, dist): addresses; rep None: the host form on the whole index,
+        else the device form on replica `rep` (a partitioned index: 0), enqueued on `stream`."""
+        fs, fo = self._filter_list(filter, filter_of, n)
+        kind, whole = (("parts", self._p) if self._p is not None else ("multi", self._m) if self._m is not None
+                       else ("single", self._h))
+        if fs is not None:
+            form, fa = "filters", self._filter_args(fs, fo, None, rep) + (int(bool(exact)),)
+        else:
+            # (f is held until the call returns: it may have been made here, and freeing it waits for the batch)
+            f = None if filter is None else self._filter(filter)
+            if f is None:
+                fa = (None,)
+            elif kind == "multi" and rep is None:               # one filter per replica
+                fa = (self._filter_handles([f]),)
+            else:
+                fa = (f._pf if kind == "parts" else f._hs[rep or 0],)
+            form = "exact" if exact else "filtered"
+        host, dev = self._BATCH_ENTRY[kind, form]
+        if rep is None:
+            fn, h, tail = host, whole, ()
+        else:
+            fn, h, tail = dev, (whole if kind == "parts" else self._replicas()[rep]), (C.c_void_p(stream),)
+        _lib.check(getattr(_lib.lib(), fn)(h, qp, n, k, *fa, *out, *tail))
 
     # -- labels (not in the reference) -----------------------------------------------------------
     @staticmethod
@@ -541,6 +589,50 @@ class CPIndex:
         fs = self.label_filters(vals)
         return fs, np.ascontiguousarray(inv.ravel(), np.int32), fs
 
+    def _with_label(self, label, filter, filter_of, n, call):
+        """The `label=` prologue of every search entry: call(filter, filter_of) under the filters of `label`
+        (_from_label), which live for that call only."""
+        filter, filter_of, made = self._from_label(label, filter, filter_of, n)
+        try:
+            return call(filter, filter_of)
+        finally:
+            for f in made:
+                f.close()
+
+    def _device_replica(self, queries):
+        """The replica that serves a batch in the device tensor `queries`: one on the tensor's device, alternating
+        between several there.  A single-device index: 0; a partitioned one (in the calls that take one): 0, and the
+        tensor lives on its first device."""
+        dev = queries.device.index if queries.is_cuda else None
+        if self._m is None:
+            if dev != self._device:
+                raise ValueError("queries must live on the first device of a partitioned index (the merge runs there)"
+                                 if self._p is not None else "queries must live on this index' device")
+            return 0
+        on = [i for i, d in enumerate(self._devices) if d == dev]
+        if not on:
+            raise ValueError("queries must live on one of this index' devices")
+        self._next_dev += 1
+        return on[(self._next_dev - 1) % len(on)]
+
+    @staticmethod
+    def _search_stream(stream, queries, fresh):
+        """The stream of a device-form call -> (its handle, its torch stream, or None where it is torch's current stream:
+        the caller's allocations are in order already).  `fresh`: tensors the call has just allocated, on the current
+        stream; another search stream has to run after them, and the caching allocator must not hand the blocks out
+        again while the search still uses them."""
+        import torch
+        cur = torch.cuda.current_stream(queries.device)
+        st = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        if st == cur.cuda_stream:
+            return st, None
+        ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
+        if fresh:
+            ext.wait_stream(cur)
+            for t in fresh:
+                t.record_stream(ext)
+        return st, ext
+
     # -- search -----------------------------------------------------------------------------
     def search(self, query, k=DEFAULT_K, filter=None, exact=False, label=None):
         """Single query, unpadded rows.  With `filter` (an IdFilter or anything make_filter accepts) only allowed ids
@@ -550,11 +642,7 @@ class CPIndex:
         if q.ndim != 1 or q.shape[0] != self._dim:
             raise ValueError("query must be 1D and match index dimension")
         if label is not None:
-            filter, _, made = self._from_label(label, filter, None, None)
-            try:
-                return self.search(q, k, filter=filter, exact=exact)
-            finally:
-                made[0].close()
+            return self._with_label(label, filter, None, None, lambda f, _: self.search(q, k, filter=f, exact=exact))
         kk = max(int(k), 1)
         if self._p is not None and filter is None and not exact:
             ids = np.empty(kk, np.int64)
@@ -594,67 +682,12 @@ class CPIndex:
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, filter_of, made = self._from_label(label, filter, filter_of, q.shape[0])
-            try:
-                return self.search_batch(q, k, filter=filter, exact=exact, filter_of=filter_of)
-            finally:
-                for f in made:
-                    f.close()
+            return self._with_label(label, filter, filter_of, q.shape[0],
+                                    lambda f, fo: self.search_batch(q, k, filter=f, exact=exact, filter_of=fo))
         n, k = q.shape[0], int(k)
         ids = np.empty((n, k), np.int64)
         dist = np.empty((n, k), np.float32)
-        fs, fo = self._filter_list(filter, filter_of, n)
-        if self._p is not None:
-            L, pa = _lib.lib(), (q.ctypes.data, n, k)
-            if fs is not None:
-                hs = [f._pf.value for f in fs]
-                _lib.check(L.cph_parts_search_batch_filters(self._p, *pa, (C.c_void_p * len(hs))(*hs) if hs else None, len(hs),
-                                                            fo.ctypes.data, int(bool(exact)), ids.ctypes.data, dist.ctypes.data))
-                return ids, dist
-            fl = None if filter is None else self._filter(filter)     # (held until the call returns: it may have been made here)
-            f = None if fl is None else fl._pf
-            if exact:
-                _lib.check(L.cph_parts_search_batch_exact(self._p, *pa, f, ids.ctypes.data, dist.ctypes.data))
-            else:
-                _lib.check(L.cph_parts_search_batch_filtered(self._p, *pa, f, ids.ctypes.data, dist.ctypes.data))
-            return ids, dist
-        if fs is not None:
-            if self._m is not None:
-                _lib.check(_lib.lib().cph_multi_search_batch_filters(self._m, q.ctypes.data, n, k, self._filter_handles(fs),
-                                                                     len(fs), fo.ctypes.data, int(bool(exact)), ids.ctypes.data,
-                                                                     dist.ctypes.data))
-            else:
-                _lib.check(_lib.lib().cph_search_batch_filters(self._h, q.ctypes.data, n, k, self._filter_handles(fs, 0), len(fs),
-                                                               fo.ctypes.data, int(bool(exact)), ids.ctypes.data, dist.ctypes.data))
-            return ids, dist
-        if exact:
-            f = None if filter is None else self._filter(filter)
-            if self._m is not None:
-                fs = None if f is None else (C.c_void_p * len(f._hs))(*[h.value for h in f._hs])
-                _lib.check(_lib.lib().cph_multi_search_batch_exact(self._m, q.ctypes.data, n, k, fs, ids.ctypes.data,
-                                                                   dist.ctypes.data))
-            else:
-                _lib.check(_lib.lib().cph_search_batch_exact(self._h, q.ctypes.data, n, k, None if f is None else f._h,
-                                                             ids.ctypes.data, dist.ctypes.data))
-            return ids, dist
-        if self._m is not None:
-            fs = None
-            if filter is not None:
-                f = self._filter(filter)
-                fs = (C.c_void_p * len(f._hs))(*[h.value for h in f._hs])
-                _lib.check(_lib.lib().cph_multi_search_batch_filtered(self._m, q.ctypes.data, n, k, fs, ids.ctypes.data,
-                                                                      dist.ctypes.data))
-            else:
-                _lib.check(_lib.lib().cph_multi_search_batch(self._m, q.ctypes.data, n, k, ids.ctypes.data,
-                                                             dist.ctypes.data))
-            return ids, dist
-        if filter is None:
-            _lib.check(_lib.lib().cph_search_batch(self._h, q.ctypes.data, n, k, ids.ctypes.data,
-                                                   dist.ctypes.data))
-            return ids, dist
-        f = self._filter(filter)
-        _lib.check(_lib.lib().cph_search_batch_filtered(self._h, q.ctypes.data, n, k, f._h, ids.ctypes.data,
-                                                        dist.ctypes.data))
+        self._batch_call(q.ctypes.data, n, k, filter, exact, filter_of, (ids.ctypes.data, dist.ctypes.data))
         return ids, dist
 
     def search_batch_device(self, queries, k=DEFAULT_K, out=None, stream=None, filter=None, exact=False, filter_of=None,
@@ -672,27 +705,11 @@ class CPIndex:
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, filter_of, made = self._from_label(label, filter, filter_of, queries.shape[0])
-            try:
-                return self.search_batch_device(queries, k, out=out, stream=stream, filter=filter, exact=exact,
-                                                filter_of=filter_of)
-            finally:
-                for f in made:
-                    f.close()
+            return self._with_label(label, filter, filter_of, queries.shape[0],
+                                    lambda f, fo: self.search_batch_device(queries, k, out=out, stream=stream, filter=f,
+                                                                           exact=exact, filter_of=fo))
         n, k = queries.shape[0], int(k)
-        rep = 0
-        if self._p is not None:
-            if not queries.is_cuda or queries.device.index != self._device:
-                raise ValueError("queries must live on the first device of a partitioned index (the merge runs there)")
-        elif self._m is not None:
-            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
-            if not on:
-                raise ValueError("queries must live on one of this index' devices")
-            rep = on[self._next_dev % len(on)]
-            self._next_dev += 1
-        elif not queries.is_cuda or queries.device.index != self._device:
-            raise ValueError("queries must live on this index' device")
-        h = self._replicas()[rep]
+        rep = self._device_replica(queries)
         fresh = []                       # tensors allocated here, on torch's current stream
         if not queries.is_contiguous():
             queries = queries.contiguous()
@@ -707,51 +724,9 @@ class CPIndex:
                 if (tuple(t.shape) != (n, k) or t.dtype != dt or t.device != queries.device
                         or not t.is_contiguous()):
                     raise ValueError("out must be contiguous (n, k) int64 / float32 tensors on the queries' device")
-        cur = torch.cuda.current_stream(queries.device)
-        if stream is None:
-            st = cur.cuda_stream
-        else:
-            st = getattr(stream, "cuda_stream", stream)
-            if fresh and st != cur.cuda_stream:
-                # The copy / the allocations above belong to the current stream: the search stream has to run after
-                # them, and the caching allocator must not hand the blocks out again while the search still uses them.
-                ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
-                ext.wait_stream(cur)
-                for t in fresh:
-                    t.record_stream(ext)
-        fs, fo = self._filter_list(filter, filter_of, n)
-        if self._p is not None:
-            # (waits on the host for every part's search, then enqueues the merge on the stream)
-            L, pa, po = _lib.lib(), (queries.data_ptr(), n, k), (ids.data_ptr(), dist.data_ptr(), C.c_void_p(st))
-            if fs is not None:
-                hs = [f._pf.value for f in fs]
-                _lib.check(L.cph_parts_search_batch_filters_device(self._p, *pa, (C.c_void_p * len(hs))(*hs) if hs else None,
-                                                                   len(hs), fo.ctypes.data, int(bool(exact)), *po))
-                return ids, dist
-            fl = None if filter is None else self._filter(filter)     # (held until the call returns; freeing it waits for the batch)
-            f = None if fl is None else fl._pf
-            if exact:
-                _lib.check(L.cph_parts_search_batch_exact_device(self._p, *pa, f, *po))
-            else:
-                _lib.check(L.cph_parts_search_batch_device_filtered(self._p, *pa, f, *po))
-            return ids, dist
-        if fs is not None:
-            _lib.check(_lib.lib().cph_search_batch_filters_device(h, queries.data_ptr(), n, k, self._filter_handles(fs, rep),
-                                                                  len(fs), fo.ctypes.data, int(bool(exact)), ids.data_ptr(),
-                                                                  dist.data_ptr(), C.c_void_p(st)))
-            return ids, dist
-        if exact:
-            f = None if filter is None else self._filter(filter)
-            _lib.check(_lib.lib().cph_search_batch_exact_device(h, queries.data_ptr(), n, k, None if f is None else f._hs[rep],
-                                                                ids.data_ptr(), dist.data_ptr(), C.c_void_p(st)))
-            return ids, dist
-        if filter is None:
-            _lib.check(_lib.lib().cph_search_batch_device(h, queries.data_ptr(), n, k, ids.data_ptr(),
-                                                          dist.data_ptr(), C.c_void_p(st)))
-            return ids, dist
-        f = self._filter(filter)
-        _lib.check(_lib.lib().cph_search_batch_device_filtered(h, queries.data_ptr(), n, k, f._hs[rep], ids.data_ptr(),
-                                                               dist.data_ptr(), C.c_void_p(st)))
+        st, _ = self._search_stream(stream, queries, fresh)
+        # (a partitioned index waits on the host for every part's search, then enqueues the merge on the stream)
+        self._batch_call(queries.data_ptr(), n, k, filter, exact, filter_of, (ids.data_ptr(), dist.data_ptr()), rep, st)
         return ids, dist
 
     # -- range search (not in the reference) ---------------------------------------------------
@@ -800,11 +775,8 @@ class CPIndex:
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, _, made = self._from_label(label, filter, filter_of, None)
-            try:
-                return self.range_search(q, radius, filter=filter, exact=exact, max_results=max_results)
-            finally:
-                made[0].close()
+            return self._with_label(label, filter, filter_of, None, lambda f, _: self.range_search(
+                q, radius, filter=f, exact=exact, max_results=max_results))
         n = q.shape[0]
         r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
         L = _lib.lib()
@@ -843,33 +815,17 @@ class CPIndex:
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, _, made = self._from_label(label, filter, filter_of, None)
-            try:
-                return self.range_search_device(queries, radius, filter=filter, exact=exact, max_results=max_results,
-                                                stream=stream)
-            finally:
-                made[0].close()
+            return self._with_label(label, filter, filter_of, None, lambda f, _: self.range_search_device(
+                queries, radius, filter=f, exact=exact, max_results=max_results, stream=stream))
         n = queries.shape[0]
         r, f, K = self._range_args(n, radius, filter, exact, max_results, filter_of)
-        rep = 0
-        if self._m is not None:
-            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
-            if not on:
-                raise ValueError("queries must live on one of this index' devices")
-            rep = on[self._next_dev % len(on)]
-            self._next_dev += 1
-        elif not queries.is_cuda or queries.device.index != self._device:
-            raise ValueError("queries must live on this index' device")
+        rep = self._device_replica(queries)
         h = self._replicas()[rep]
-        cur = torch.cuda.current_stream(queries.device)
-        st = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
-        ext = None
-        if st != cur.cuda_stream:
-            ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
+        fresh = []
         if not queries.is_contiguous():
             queries = queries.contiguous()
-            if ext is not None:                  # (the copy belongs to the current stream)
-                ext.wait_stream(cur)
+            fresh.append(queries)                # (the copy belongs to the current stream)
+        st, ext = self._search_stream(stream, queries, fresh)
         L = _lib.lib()
         obj, total = C.c_void_p(), C.c_uint64(0)
         _lib.check(L.cph_range_search_begin(h, queries.data_ptr() if n else None, 1, n, r.ctypes.data if n else None,
@@ -882,7 +838,7 @@ class CPIndex:
             if ext is not None:
                 # The blocks belong to the current stream, whose earlier work may still use them: the fill runs after it.
                 # (finish waits for its writes, so nothing has to be recorded for the allocator.)
-                ext.wait_stream(cur)
+                ext.wait_stream(torch.cuda.current_stream(queries.device))
             _lib.check(L.cph_range_search_finish(obj, lims.data_ptr(), ids.data_ptr() if total.value else None,
                                                  dist.data_ptr() if total.value else None, 1))
         finally:
@@ -938,13 +894,7 @@ class CPIndex:
         out = (np.empty((n, k, g), np.int64), np.empty((n, k, g), np.float32), np.empty((n, k), np.int32),
                np.empty((n, k), np.int32), np.empty(n, np.uint8))
         multi = self._m is not None
-        if fs is not None:
-            fh, nf, fop = self._filter_handles(fs, None if multi else 0), len(fs), fo.ctypes.data
-        elif f is not None:
-            hs = [h.value for h in (f._hs if multi else f._hs[:1])]
-            fh, nf, fop = (C.c_void_p * len(hs))(*hs), 1, None
-        else:
-            fh, nf, fop = None, 0, None
+        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
         po = [o.ctypes.data if n else None for o in out]
         qp = q.ctypes.data if n else None
         if multi:
@@ -981,13 +931,8 @@ class CPIndex:
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, filter_of, made = self._from_label(label, filter, filter_of, q.shape[0])
-            try:
-                return self.search_grouped(q, k, group_size, keys=keys, candidates=candidates, filter=filter, exact=exact,
-                                           filter_of=filter_of)
-            finally:
-                for f in made:
-                    f.close()
+            return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_grouped(
+                q, k, group_size, keys=keys, candidates=candidates, filter=f, exact=exact, filter_of=fo))
         n = q.shape[0]
         k, g, C_, keys, fs, fo, f = self._grouped_args(n, k, group_size, keys, candidates, filter, filter_of)
         if C_ is not None:
@@ -1020,32 +965,20 @@ class CPIndex:
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
         if label is not None:
-            filter, filter_of, made = self._from_label(label, filter, filter_of, queries.shape[0])
-            try:
-                return self.search_grouped_device(queries, k, group_size, keys=keys, candidates=candidates, out=out,
-                                                  stream=stream, filter=filter, exact=exact, filter_of=filter_of)
-            finally:
-                for f in made:
-                    f.close()
+            return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_grouped_device(
+                queries, k, group_size, keys=keys, candidates=candidates, out=out, stream=stream, filter=f, exact=exact,
+                filter_of=fo))
         n = queries.shape[0]
         k, g, C_, keys, fs, fo, f = self._grouped_args(n, k, group_size, keys, candidates, filter, filter_of)
         if C_ is None:
             C_ = min(self.GROUP_MAX_CANDIDATES, max(64, 4 * k * g))
-        rep = 0
-        if self._m is not None:
-            on = [i for i, d in enumerate(self._devices) if queries.is_cuda and d == queries.device.index]
-            if not on:
-                raise ValueError("queries must live on one of this index' devices")
-            rep = on[self._next_dev % len(on)]
-            self._next_dev += 1
-        elif not queries.is_cuda or queries.device.index != self._device:
-            raise ValueError("queries must live on this index' device")
+        rep = self._device_replica(queries)
         h = self._replicas()[rep]
         fresh = []                       # tensors allocated here, on torch's current stream
         if not queries.is_contiguous():
             queries = queries.contiguous()
             fresh.append(queries)
-        shapes = (((n, k, g), torch.int64), ((n, k, g), torch.float32), ((n, k), torch.int32), ((n, k), torch.int32),
+        shapes =(((n, k, g), torch.int64), ((n, k, g), torch.float32), ((n, k), torch.int32), ((n, k), torch.int32),
                   ((n,), torch.uint8))
         if out is None:
             res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in shapes]
@@ -1059,24 +992,8 @@ class CPIndex:
                 if tuple(t.shape) != sh or not ok_dt or t.device != queries.device or not t.is_contiguous():
                     raise ValueError("out must be contiguous (n, k, g) int64 / float32, (n, k) int32 / int32 and (n,) uint8 "
                                      "tensors on the queries' device")
-        cur = torch.cuda.current_stream(queries.device)
-        if stream is None:
-            st = cur.cuda_stream
-        else:
-            st = getattr(stream, "cuda_stream", stream)
-            if fresh and st != cur.cuda_stream:
-                # (as in search_batch_device: the search stream runs after the allocations' stream, and the caching
-                #  allocator must not hand the blocks out again while the search still uses them)
-                ext = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(st, device=queries.device)
-                ext.wait_stream(cur)
-                for t in fresh:
-                    t.record_stream(ext)
-        if fs is not None:
-            fh, nf, fop = self._filter_handles(fs, rep), len(fs), fo.ctypes.data
-        elif f is not None:
-            fh, nf, fop = (C.c_void_p * 1)(f._hs[rep].value), 1, None
-        else:
-            fh, nf, fop = None, 0, None
+        st, _ = self._search_stream(stream, queries, fresh)
+        fh, nf, fop = self._filter_args(fs, fo, f, rep)
         _lib.check(_lib.lib().cph_search_grouped_device(h, queries.data_ptr() if n else None, n, k, g, C_,
                                                         None if keys is None else keys._hs[rep], fh, nf, fop, int(bool(exact)),
                                                         *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))

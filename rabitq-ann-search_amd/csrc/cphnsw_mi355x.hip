@@ -1212,88 +1212,36 @@ bool takes_exact(const cph_index* h, const cph_filter* f, uint64_t k, bool exact
     return exact || (f && h->exact_threshold > 0 && f->popcount <= h->exact_threshold && k <= kExactMaxK);
 }
 
-// cph_search_batch[_filtered | _exact]: queries and results in host memory; f = null: unfiltered.  An empty filter launches
-// nothing (enqueue_search): no encoder, and its padding is written into device buffers by copy commands.
-void search_batch_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* ids,
-                       float* dist, bool exact = false) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!batch_has_work(h, f, queries, n, k, ids, dist)) return;
-    h->use_device();
-    const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
-    f = eff.get();
-    exact = takes_exact(h, f, k, exact);
-    if (!exact) require_tail_k(h, k);
-    hipStream_t st = own_stream(h);
-    BatchSet& s = next_set(h, st);
-    if (exact) {
-        const float* d_q = upload_queries(h, s, queries, n, st);
-        if (s.d_ids.n < n * k) {
-            if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-            s.d_ids.alloc(n * k);
-            s.d_dist.alloc(n * k);
-        }
-        enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, s.d_ids.p, s.d_dist.p, st);
-        HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
-        HIP_CHECK(hipStreamSynchronize(st));
-        return;
-    }
-    const bool empty = f && f->popcount == 0;
-    if (!empty && n <= kSmallBatch && n * k <= (1u << 20)) {
-        // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
-        const PinnedIo io(n, k, h->dim, 0);
-        if (s.pin_io_bytes < io.need && s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
-        grow_pinned(s.pin_io, s.pin_io_dev, s.pin_io_bytes, io.need);
-        std::memcpy(io.queries(s.pin_io), queries, n * h->dim * sizeof(float));
-        stage_queries(h, s, io.queries(s.pin_io_dev), n, st);
-        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
-                       DoneFlags(), f, io.queries(s.pin_io_dev));
-        HIP_CHECK(hipStreamSynchronize(st));
-        std::memcpy(ids, io.ids(s.pin_io), n * k * 8);
-        std::memcpy(dist, io.dist(s.pin_io), n * k * 4);
-        return;
-    }
-    const float* d_q = empty ? nullptr : upload_queries(h, s, queries, n, st);
-    if (!empty) stage_queries(h, s, d_q, n, st);
-    if (s.d_ids.n < n * k) {
-        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-        s.d_ids.alloc(n * k);
-        s.d_dist.alloc(n * k);
-    }
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, s.d_ids.p, s.d_dist.p, st, nullptr, DoneFlags(), f, d_q);
-    HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
-    HIP_CHECK(hipStreamSynchronize(st));
+// One batch search, in every form the entry points offer.  Filter: cph_filter (on replicas filters[f * R + r] is filter f on
+// replica r) or cph_parts_filter.  filter_of == null: F <= 1, one filter (filters[0]) or none for the whole batch;
+// filter_of != null: per-query filters, filter_of[n] in host memory.
+template <class Filter>
+struct BatchCallT {
+    const float* q = nullptr;                 // [n][dim]: host memory, or (on_device) device memory
+    uint64_t n = 0, k = 0;
+    const Filter* const* filters = nullptr;
+    uint32_t F = 0;
+    const int32_t* filter_of = nullptr;
+    bool exact = false;
+    int64_t* ids = nullptr;                   // [n][k], where the queries are
+    float* dist = nullptr;
+    bool on_device = false;                   // everything is enqueued on `stream`, nothing waits for the device
+    hipStream_t stream = nullptr;
+};
+using BatchCall = BatchCallT<cph_filter>;
+
+template <class Filter>
+BatchCallT<Filter> batch_call(const float* q, uint64_t n, uint64_t k, const Filter* const* filters, uint32_t F, const int32_t* filter_of,
+                              bool exact, int64_t* ids, float* dist, bool on_device = false, void* stream = nullptr) {
+    return BatchCallT<Filter>{q, n, k, filters, F, filter_of, exact, ids, dist, on_device, reinterpret_cast<hipStream_t>(stream)};
 }
 
-// cph_search_batch_device[_filtered]: queries and results in device memory, everything enqueued on the caller's stream.
-// search_batch_device_locked: the caller holds the handle mutex.
-void search_batch_device_locked(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
-                                float* d_dist, void* stream, bool exact = false) {
-    if (!batch_has_work(h, f, d_queries, n, k, d_ids, d_dist)) return;
-    h->use_device();
-    const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
-    f = eff.get();
-    exact = takes_exact(h, f, k, exact);
-    if (!exact) require_tail_k(h, k);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    BatchSet& s = next_set(h, st);
-    if (exact) {
-        enqueue_exact(h, s, d_queries, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
-        return;
-    }
-    if (!(f && f->popcount == 0)) stage_queries(h, s, d_queries, n, st);
-    enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f, d_queries);
-}
-
-void search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* d_ids,
-                         float* d_dist, void* stream, bool exact = false) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    search_batch_device_locked(h, d_queries, n, k, f, d_ids, d_dist, stream, exact);
+// Every filter_of value is -1 or the number of a filter (F itself must stay an invalid value).
+void check_filter_of(const int32_t* filter_of, uint64_t n, uint32_t F) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
+            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
+                             std::to_string(F) + ")");
 }
 
 // ---- per-query filters: row i of the batch under filter filter_of[i] ------------------------------------------------------
@@ -1339,10 +1287,7 @@ struct LiveFilters {
 void live_filters(cph_index* h, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, uint64_t n, LiveFilters& out) {
     out.filters = filters; out.F = F; out.filter_of = filter_of;
     if (h->host.n_removed == 0) return;
-    for (uint64_t i = 0; i < n; ++i)               // (before -1 is renumbered: F itself must stay an invalid value)
-        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
-            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
-                             std::to_string(F) + ")");
+    check_filter_of(filter_of, n, F);              // (before -1 is renumbered)
     h->use_device();
     for (uint32_t f = 0; f < F; ++f) {
         out.hold.push_back(effective_filter(h, filters[f]));
@@ -1548,54 +1493,86 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
     finish_batch(h, s, st);
 }
 
-// cph_search_batch_filters: queries and results in host memory.
-void search_batch_filters_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters, uint32_t F,
-                               const int32_t* filter_of, bool exact, int64_t* ids, float* dist) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!filters_batch_has_work(h, filters, F, filter_of, queries, n, k, ids, dist)) return;
-    LiveFilters lf;
-    live_filters(h, filters, F, filter_of, n, lf);
-    filters = lf.filters; F = lf.F; filter_of = lf.filter_of;
-    const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
-    h->use_device();
-    hipStream_t st = own_stream(h);
-    BatchSet& s = next_set(h, st);
-    const float* d_q = upload_queries(h, s, queries, n, st);
+// The host form's I/O around `enqueue(d_q, d_ids, d_dist)`: the queries up (unless nothing will read them), result rows in
+// the set's buffers, both copied back; the set is busy until the copies have landed, and the call waits for them.
+template <class Enqueue>
+void with_host_io(cph_index* h, BatchSet& s, const BatchCall& c, bool upload, hipStream_t st, Enqueue&& enqueue) {
+    const uint64_t n = c.n, k = c.k;
+    const float* d_q = upload ? upload_queries(h, s, c.q, n, st) : nullptr;
     if (s.d_ids.n < n * k) {
         if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
         s.d_ids.alloc(n * k);
         s.d_dist.alloc(n * k);
     }
-    enqueue_filters(h, s, d_q, (uint32_t)n, (uint32_t)k, filters, F, filter_of, g, s.d_ids.p, s.d_dist.p, st);
-    HIP_CHECK(hipMemcpyAsync(ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(s.ev_done, st));     // the set is busy until the copies have landed
+    enqueue(d_q, s.d_ids.p, s.d_dist.p);
+    HIP_CHECK(hipMemcpyAsync(c.ids, s.d_ids.p, n * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(c.dist, s.d_dist.p, n * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(s.ev_done, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
-// cph_search_batch_filters_device: queries and results in device memory (filter_of on the host), everything enqueued on
-// the caller's stream.
-// search_batch_filters_device_locked: the caller holds the handle mutex.
-void search_batch_filters_device_locked(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
-                                        uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
-    if (!filters_batch_has_work(h, filters, F, filter_of, d_queries, n, k, d_ids, d_dist)) return;
-    LiveFilters lf;
-    live_filters(h, filters, F, filter_of, n, lf);
-    filters = lf.filters; F = lf.F; filter_of = lf.filter_of;
-    const FilterGroups g = group_filters(h, filters, F, filter_of, n, k, exact);
+// Every cph_search_batch* entry of one index; the caller holds the handle mutex.  The device form enqueues everything on the
+// caller's stream.  Two routes, by the call's form and not by what it holds:
+// * one filter or none (filter_of == null) -> enqueue_search, or enqueue_exact (takes_exact).  An empty filter launches
+//   nothing (enqueue_search): no encoder, and its padding is written into device buffers by copy commands;
+// * per-query filters -> enqueue_filters, over the handle's live filters and their grouping.
+void search_batch_locked(cph_index* h, const BatchCall& c) {
+    const uint64_t n = c.n, k = c.k;
+    if (c.filter_of || c.F > 1) {                 // (F > 1 without filter_of: checked like a per-query call, refused if there is work)
+        if (!filters_batch_has_work(h, c.filters, c.F, c.filter_of, c.q, n, k, c.ids, c.dist)) return;
+        LiveFilters lf;
+        live_filters(h, c.filters, c.F, c.filter_of, n, lf);
+        const FilterGroups g = group_filters(h, lf.filters, lf.F, lf.filter_of, n, k, c.exact);
+        h->use_device();
+        hipStream_t st = c.on_device ? c.stream : own_stream(h);
+        BatchSet& s = next_set(h, st);
+        auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
+            enqueue_filters(h, s, d_q, (uint32_t)n, (uint32_t)k, lf.filters, lf.F, lf.filter_of, g, d_ids, d_dist, st);
+        };
+        if (c.on_device) enqueue(c.q, c.ids, c.dist);
+        else with_host_io(h, s, c, true, st, enqueue);
+        return;
+    }
+    if (c.F && !c.filters) throw InvalidArg("null argument");
+    const cph_filter* f = c.F ? c.filters[0] : nullptr;
+    if (!batch_has_work(h, f, c.q, n, k, c.ids, c.dist)) return;
     h->use_device();
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const std::shared_ptr<const cph_filter> eff = effective_filter(h, f);     // removed rows: F & ~R
+    f = eff.get();
+    const bool exact = takes_exact(h, f, k, c.exact);
+    if (!exact) require_tail_k(h, k);
+    hipStream_t st = c.on_device ? c.stream : own_stream(h);
     BatchSet& s = next_set(h, st);
-    enqueue_filters(h, s, d_queries, (uint32_t)n, (uint32_t)k, filters, F, filter_of, g, d_ids, d_dist, st);
+    const bool empty = f && f->popcount == 0;     // (never exact: takes_exact)
+    auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
+        if (exact) return enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
+        if (!empty) stage_queries(h, s, d_q, n, st);
+        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f, d_q);
+    };
+    if (c.on_device) return enqueue(c.q, c.ids, c.dist);
+    if (!exact && !empty && n <= kSmallBatch && n * k <= (1u << 20)) {
+        // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
+        const PinnedIo io(n, k, h->dim, 0);
+        if (s.pin_io_bytes < io.need && s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
+        grow_pinned(s.pin_io, s.pin_io_dev, s.pin_io_bytes, io.need);
+        std::memcpy(io.queries(s.pin_io), c.q, n * h->dim * sizeof(float));
+        stage_queries(h, s, io.queries(s.pin_io_dev), n, st);
+        enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
+                       DoneFlags(), f, io.queries(s.pin_io_dev));
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::memcpy(c.ids, io.ids(s.pin_io), n * k * 8);
+        std::memcpy(c.dist, io.dist(s.pin_io), n * k * 4);
+        return;
+    }
+    with_host_io(h, s, c, !empty, st, enqueue);
 }
 
-void search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
-                                 uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids, float* d_dist, void* stream) {
+void search_batch(cph_index* h, const BatchCall& c) {
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    search_batch_filters_device_locked(h, d_queries, n, k, filters, F, filter_of, exact, d_ids, d_dist, stream);
+    search_batch_locked(h, c);
 }
+
 
 }  // namespace
 
@@ -2233,12 +2210,12 @@ int cph_order_queries(cph_index* h, const float* keys, uint64_t n, uint32_t* ord
 
 int cph_search_batch(cph_index* h, const float* queries, uint64_t n, uint64_t k, int64_t* ids,
                      float* dist) {
-    return guarded([&] { search_batch_host(h, queries, n, k, nullptr, ids, dist); });
+    return cph_search_batch_filtered(h, queries, n, k, nullptr, ids, dist);
 }
 
 int cph_search_batch_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k,
                             int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] { search_batch_device(h, d_queries, n, k, nullptr, d_ids, d_dist, stream); });
+    return cph_search_batch_device_filtered(h, d_queries, n, k, nullptr, d_ids, d_dist, stream);
 }
 
 // ---- filtered search --------------------------------------------------------------------
@@ -2275,36 +2252,34 @@ int cph_filter_destroy(cph_filter* f) {
 
 int cph_search_batch_filtered(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f,
                               int64_t* ids, float* dist) {
-    return guarded([&] { search_batch_host(h, queries, n, k, f, ids, dist); });
+    return guarded([&] { search_batch(h, batch_call(queries, n, k, &f, f ? 1u : 0u, nullptr, false, ids, dist)); });
 }
 
 int cph_search_batch_device_filtered(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                      int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream); });
+    return guarded([&] { search_batch(h, batch_call(d_queries, n, k, &f, f ? 1u : 0u, nullptr, false, d_ids, d_dist, true, stream)); });
 }
 
 // ---- exact search -----------------------------------------------------------------------
 int cph_search_batch_exact(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* f, int64_t* ids,
                            float* dist) {
-    return guarded([&] { search_batch_host(h, queries, n, k, f, ids, dist, true); });
+    return guarded([&] { search_batch(h, batch_call(queries, n, k, &f, f ? 1u : 0u, nullptr, true, ids, dist)); });
 }
 
 int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* f,
                                   int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] { search_batch_device(h, d_queries, n, k, f, d_ids, d_dist, stream, true); });
+    return guarded([&] { search_batch(h, batch_call(d_queries, n, k, &f, f ? 1u : 0u, nullptr, true, d_ids, d_dist, true, stream)); });
 }
 
 int cph_search_batch_filters(cph_index* h, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
                              uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist) {
-    return guarded([&] { search_batch_filters_host(h, queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist); });
+    return guarded([&] { search_batch(h, batch_call(queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist)); });
 }
 
 int cph_search_batch_filters_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
                                     uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* d_ids, float* d_dist,
                                     void* stream) {
-    return guarded([&] {
-        search_batch_filters_device(h, d_queries, n, k, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, stream);
-    });
+    return guarded([&] { search_batch(h, batch_call(d_queries, n, k, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, true, stream)); });
 }
 
 int cph_host_filter_groups(const int32_t* filter_of, uint64_t n, const uint64_t* popcounts, uint32_t n_filters, uint64_t k, int exact,
@@ -2482,7 +2457,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
             r->s->g_ids.alloc(n * K);
             r->s->g_dist.alloc(n * K);
             r->s->counts.alloc(n);
-            search_batch_device_locked(h, d_q, n, K, f, r->s->g_ids.p, r->s->g_dist.p, st);
+            search_batch_locked(h, batch_call(d_q, n, K, &f, f ? 1u : 0u, nullptr, false, r->s->g_ids.p, r->s->g_dist.p, true, st));
             hipLaunchKernelGGL(range_cut_count_kernel, dim3((uint32_t)n), dim3(64), 0, st, (const int64_t*)r->s->g_ids.p, (const float*)r->s->g_dist.p,
                                (uint32_t)K, (const float*)r->s->d_rad.p, r->s->counts.p);
             HIP_CHECK(hipGetLastError());
@@ -3073,7 +3048,7 @@ int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float
             // rows: a batch of one, so that the tail's scan and fold follow the graph launch
             std::vector<int64_t> ri(kk);
             std::vector<float> rd(kk);
-            search_batch_host(h, query, 1, kk, nullptr, ri.data(), rd.data());
+            search_batch(h, batch_call<cph_filter>(query, 1, kk, nullptr, 0, nullptr, false, ri.data(), rd.data()));
             uint64_t cnt = 0;
             for (uint64_t i = 0; i < kk; ++i) cnt += ri[i] >= 0 ? 1 : 0;
             for (uint64_t i = 0, o = 0; i < kk; ++i)
@@ -3625,76 +3600,86 @@ void multi_lifecycle(cph_multi* m, F&& first) {
     }
 }
 
-// cph_multi_search_batch[_filtered]: f = one filter per replica, or null.
-void multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
-                        int64_t* ids, float* dist, bool exact = false) {
-    if (!m) throw InvalidArg("null handle");
-    std::shared_lock<std::shared_mutex> lk(m->life);
-    const uint32_t R = (uint32_t)m->reps.size();
-    if (f)
-        for (uint32_t r = 0; r < R; ++r) {
-            cph_index* h = m->reps[r];
-            std::lock_guard<std::mutex> g(h->mu);
-            require_finalized(h);
-            if (!f[r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
-            check_filter(h, f[r]);
-        }
-    const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
-    const uint64_t dim = m->reps[0]->dim;
+size_t shard_index(const std::vector<Shard>& plan, const Shard& s) {
+    for (size_t i = 0; i < plan.size(); ++i)
+        if (plan[i].replica == s.replica && plan[i].lo == s.lo && plan[i].hi == s.hi) return i;
+    throw std::runtime_error("shard not in the plan");
+}
+
+// Runs call(shard, its index in the plan) -> cph_status on every shard's worker; a failing shard's status and message
+// (thread-local on the worker: `call` has just made the failing cph_* call there) are raised on this thread.
+template <class Call>
+void run_shards(cph_multi* m, const std::vector<Shard>& plan, Call&& call) {
     std::string err;
     const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
-        cph_index* h = m->reps[s.replica];
-        const float* q = queries ? queries + s.lo * dim : nullptr;
-        int64_t* oi = ids ? ids + s.lo * k : nullptr;
-        float* od = dist ? dist + s.lo * k : nullptr;
-        const cph_filter* fr = f ? f[s.replica] : nullptr;
-        const int r = exact ? cph_search_batch_exact(h, q, s.hi - s.lo, k, fr, oi, od)
-                            : cph_search_batch_filtered(h, q, s.hi - s.lo, k, fr, oi, od);
-        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
+        const int r = call(s, shard_index(plan, s));
+        if (r != CPH_OK) e = g_err;
         return r;
     }, err);
     if (rc != CPH_OK) raise_status(rc, err);
-    std::lock_guard<std::mutex> g(m->last_mu);
-    m->last_plan = plan;
 }
 
-// cph_multi_search_batch_filters: filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
-void multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
-                                uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist) {
+// The replica fan-out of every batch entry of a cph_multi, all of it before any shard runs (a refusal must not leave half of
+// the rows written): under the shared lock, per_replica_check(h, r) on every finalized replica under its mutex (null: no
+// replica is visited, every shard's own entry checks its handle), then has_work() -- the checks that need no replica;
+// false: nothing to do, and the round robin does not advance.  Then the shards (run_shards); the plan is returned and,
+// on success only, becomes the handle's last plan.
+using ReplicaCheck = std::function<void(cph_index*, uint32_t)>;
+template <class HasWork, class Call>
+std::vector<Shard> multi_fan_out(cph_multi* m, uint64_t n, const ReplicaCheck& per_replica_check, HasWork&& has_work, Call&& per_shard_call) {
     if (!m) throw InvalidArg("null handle");
     std::shared_lock<std::shared_mutex> lk(m->life);
     const uint32_t R = (uint32_t)m->reps.size();
-    if (F && !filters) throw InvalidArg("null argument");
-    for (uint32_t r = 0; r < R; ++r) {
+    for (uint32_t r = 0; r < R && per_replica_check; ++r) {
         cph_index* h = m->reps[r];
         std::lock_guard<std::mutex> g(h->mu);
         require_finalized(h);
-        for (uint32_t f = 0; f < F; ++f) {
-            if (!filters[(size_t)f * R + r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
-            check_filter(h, filters[(size_t)f * R + r]);
-        }
+        per_replica_check(h, r);
     }
-    if (n && k && !filter_of) throw InvalidArg("null argument");
-    for (uint64_t i = 0; i < n && k; ++i)         // (before any shard runs: a bad value must not leave half of the rows written)
-        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
-            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
-                             std::to_string(F) + ")");
+    if (!has_work()) return {};
     const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
-    const uint64_t dim = m->reps[0]->dim;
-    std::string err;
-    const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
-        cph_index* h = m->reps[s.replica];
-        std::vector<const cph_filter*> fr(F);
-        for (uint32_t f = 0; f < F; ++f) fr[f] = filters[(size_t)f * R + s.replica];
-        const int r = cph_search_batch_filters(h, queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, fr.data(), F,
-                                               filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0, ids ? ids + s.lo * k : nullptr,
-                                               dist ? dist + s.lo * k : nullptr);
-        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
-        return r;
-    }, err);
-    if (rc != CPH_OK) raise_status(rc, err);
+    run_shards(m, plan, per_shard_call);
     std::lock_guard<std::mutex> g(m->last_mu);
     m->last_plan = plan;
+    return plan;
+}
+
+// The F filters of replica r in a cph_multi filter list (filters[f * R + r]), as the single-index entries take them.
+std::vector<const cph_filter*> replica_filters(const cph_filter* const* filters, uint32_t F, uint32_t R, uint32_t r) {
+    std::vector<const cph_filter*> fr(F);
+    for (uint32_t f = 0; f < F; ++f) fr[f] = filters[(size_t)f * R + r];
+    return fr;
+}
+void check_replica_filters(cph_index* h, const cph_filter* const* filters, uint32_t F, uint32_t R, uint32_t r) {
+    for (const cph_filter* f : replica_filters(filters, F, R, r)) {
+        if (!f) throw InvalidArg("a filtered multi-device search needs one filter per replica");
+        check_filter(h, f);
+    }
+}
+
+// cph_multi_search_batch[_filtered | _exact | _filters]: filter_of is sliced with the queries.  The unfiltered call visits
+// no replica beforehand.
+void multi_search_batch(cph_multi* m, const BatchCall& c) {
+    if (!m) throw InvalidArg("null handle");
+    const uint64_t n = c.n, k = c.k;
+    const uint32_t R = (uint32_t)m->reps.size();
+    if (c.F && !c.filters) throw InvalidArg("null argument");
+    ReplicaCheck check;
+    if (c.F || c.filter_of) check = [&](cph_index* h, uint32_t r) { check_replica_filters(h, c.filters, c.F, R, r); };
+    multi_fan_out(m, n, check, [&] {
+        if (n && k && !c.filter_of && c.F > 1) throw InvalidArg("null argument");
+        if (n && k && c.filter_of) check_filter_of(c.filter_of, n, c.F);
+        return true;
+    }, [&](const Shard& s, size_t) {
+        const std::vector<const cph_filter*> fr = replica_filters(c.filters, c.F, R, s.replica);
+        const float* q = c.q ? c.q + s.lo * m->reps[0]->dim : nullptr;
+        int64_t* oi = c.ids ? c.ids + s.lo * k : nullptr;
+        float* od = c.dist ? c.dist + s.lo * k : nullptr;
+        cph_index* h = m->reps[s.replica];
+        if (c.filter_of) return cph_search_batch_filters(h, q, s.hi - s.lo, k, fr.data(), c.F, c.filter_of + s.lo, c.exact ? 1 : 0, oi, od);
+        const cph_filter* f = c.F ? fr[0] : nullptr;
+        return c.exact ? cph_search_batch_exact(h, q, s.hi - s.lo, k, f, oi, od) : cph_search_batch_filtered(h, q, s.hi - s.lo, k, f, oi, od);
+    });
 }
 
 template <class F>
@@ -3792,22 +3777,23 @@ int cph_multi_is_finalized(cph_multi* m, int* flag) {
 }
 
 int cph_multi_search_batch(cph_multi* m, const float* queries, uint64_t n, uint64_t k, int64_t* ids, float* dist) {
-    return guarded([&] { multi_search_batch(m, queries, n, k, nullptr, ids, dist); });
+    return cph_multi_search_batch_filtered(m, queries, n, k, nullptr, ids, dist);
 }
 
+// (f: one filter per replica, the layout of a list of one filter)
 int cph_multi_search_batch_filtered(cph_multi* m, const float* queries, uint64_t n, uint64_t k,
                                     const cph_filter* const* f, int64_t* ids, float* dist) {
-    return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist); });
+    return guarded([&] { multi_search_batch(m, batch_call(queries, n, k, f, f ? 1u : 0u, nullptr, false, ids, dist)); });
 }
 
 int cph_multi_search_batch_exact(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* f,
                                  int64_t* ids, float* dist) {
-    return guarded([&] { multi_search_batch(m, queries, n, k, f, ids, dist, true); });
+    return guarded([&] { multi_search_batch(m, batch_call(queries, n, k, f, f ? 1u : 0u, nullptr, true, ids, dist)); });
 }
 
 int cph_multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t n, uint64_t k, const cph_filter* const* filters,
                                    uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist) {
-    return guarded([&] { multi_search_batch_filters(m, queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist); });
+    return guarded([&] { multi_search_batch(m, batch_call(queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist)); });
 }
 
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed) {
@@ -3919,16 +3905,6 @@ struct cph_multi_range {
     }
 };
 
-namespace {
-
-size_t shard_index(const std::vector<Shard>& plan, const Shard& s) {
-    for (size_t i = 0; i < plan.size(); ++i)
-        if (plan[i].replica == s.replica && plan[i].lo == s.lo && plan[i].hi == s.hi) return i;
-    throw std::runtime_error("shard not in the plan");
-}
-
-}  // namespace
-
 extern "C" {
 
 int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n, const float* radius_host, const cph_filter* const* f,
@@ -3938,42 +3914,25 @@ int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n,
         if (!out || !total) throw InvalidArg("null argument");
         *out = nullptr;
         *total = 0;
-        std::shared_lock<std::shared_mutex> lk(m->life);
         const uint32_t R = (uint32_t)m->reps.size();
-        for (uint32_t r = 0; r < R; ++r) {
-            cph_index* h = m->reps[r];
-            std::lock_guard<std::mutex> g(h->mu);
-            require_finalized(h);
-            if (f) {
-                if (!f[r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
-                check_filter(h, f[r]);
-            }
-        }
-        if (n && (!queries || !radius_host)) throw InvalidArg("null argument");
+        const uint64_t dim = m->reps[0]->dim;
         std::unique_ptr<cph_multi_range> mr(new cph_multi_range());
         mr->m = m;
         mr->n = n;
-        mr->plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
-        mr->parts.assign(mr->plan.size(), nullptr);
+        mr->parts.assign(R, nullptr);             // (a plan has at most R shards)
+        std::vector<uint64_t> totals(R, 0);
+        mr->plan = multi_fan_out(m, n, [&](cph_index* h, uint32_t r) { check_replica_filters(h, f, f ? 1 : 0, R, r); }, [&] {
+            if (n && (!queries || !radius_host)) throw InvalidArg("null argument");
+            return true;
+        }, [&](const Shard& s, size_t i) {
+            return cph_range_search_begin(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, 0, s.hi - s.lo,
+                                          radius_host ? radius_host + s.lo : nullptr, f ? f[s.replica] : nullptr, exact, max_results,
+                                          nullptr, &mr->parts[i], &totals[i]);
+        });
+        mr->parts.resize(mr->plan.size());
         mr->first.assign(mr->plan.size() + 1, 0);
-        std::vector<uint64_t> totals(mr->plan.size(), 0);
-        const uint64_t dim = m->reps[0]->dim;
-        std::string err;
-        const int rc = m->pool->run(mr->plan, [&](const Shard& s, std::string& e) {
-            const size_t i = shard_index(mr->plan, s);
-            const int r = cph_range_search_begin(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, 0, s.hi - s.lo,
-                                                 radius_host ? radius_host + s.lo : nullptr, f ? f[s.replica] : nullptr, exact, max_results,
-                                                 nullptr, &mr->parts[i], &totals[i]);
-            if (r != CPH_OK) e = g_err;           // (thread-local: this worker's message)
-            return r;
-        }, err);
-        if (rc != CPH_OK) raise_status(rc, err);
-        for (size_t i = 0; i < totals.size(); ++i) mr->first[i + 1] = mr->first[i] + totals[i];
+        for (size_t i = 0; i < mr->plan.size(); ++i) mr->first[i + 1] = mr->first[i] + totals[i];
         mr->total = mr->first.back();
-        {
-            std::lock_guard<std::mutex> g(m->last_mu);
-            m->last_plan = mr->plan;
-        }
         *total = mr->total;
         *out = mr.release();
     });
@@ -3985,17 +3944,13 @@ int cph_multi_range_search_finish(cph_multi_range* mr, int64_t* lims_host, int64
         if (mr->total && (!ids || !dist)) throw InvalidArg("null argument");
         cph_multi* m = mr->m;
         std::shared_lock<std::shared_mutex> lk(m->life);
-        std::string err;
-        const int rc = m->pool->run(mr->plan, [&](const Shard& s, std::string& e) {
-            const size_t i = shard_index(mr->plan, s);
+        run_shards(m, mr->plan, [&](const Shard& s, size_t i) {
             std::vector<int64_t> local(s.hi - s.lo + 1);
             const uint64_t at = mr->first[i];
             const int r = cph_range_search_finish(mr->parts[i], local.data(), ids ? ids + at : nullptr, dist ? dist + at : nullptr, 0);
-            if (r != CPH_OK) { e = g_err; return r; }
-            for (uint64_t j = 0; j < s.hi - s.lo; ++j) lims_host[s.lo + j] = (int64_t)at + local[j];
+            for (uint64_t j = 0; r == CPH_OK && j < s.hi - s.lo; ++j) lims_host[s.lo + j] = (int64_t)at + local[j];
             return r;
-        }, err);
-        if (rc != CPH_OK) raise_status(rc, err);
+        });
         lims_host[mr->n] = (int64_t)mr->total;
     });
 }
@@ -4136,21 +4091,9 @@ void copy_between(void* dst, int dst_dev, const void* src, int src_dev, size_t b
     cross_device_copy(s.peer == 1, ops);
 }
 
-// One search of a partitioned index, in every form the entry points offer.
-struct PartsCall {
-    const float* q = nullptr;                 // [n][dim]: host memory, or (on_device) on the home device
-    uint64_t n = 0, k = 0;
-    bool on_device = false;                   // queries and results on the home device, the merge enqueued on `stream`
-    hipStream_t stream = nullptr;
-    bool exact = false;
-    const cph_parts_filter* f = nullptr;      // one filter for the batch, or
-    const cph_parts_filter* const* filters = nullptr;   // per-query filters: filters[F], filter_of[n] (host)
-    uint32_t F = 0;
-    const int32_t* filter_of = nullptr;
-    bool per_query = false;
-    int64_t* ids = nullptr;                   // [n][k], where the queries are
-    float* dist = nullptr;
-};
+// One search of a partitioned index, in every form the entry points offer (on_device: queries and results on the home
+// device, the merge enqueued on `stream`).
+using PartsCall = BatchCallT<cph_parts_filter>;
 
 void check_parts_filter(cph_parts* m, const cph_parts_filter* f) {
     if (!f) throw InvalidArg("null filter");
@@ -4172,16 +4115,10 @@ void parts_search(cph_parts* m, const PartsCall& c) {
         if (!h->ids_input)
             throw InvalidArg("part(" + std::to_string(p) + ") was switched to internal ids: a partitioned index needs its parts in input rows");
     }
-    if (c.f) check_parts_filter(m, c.f);
-    if (c.per_query) {
-        if (c.F && !c.filters) throw InvalidArg("null argument");
-        for (uint32_t f = 0; f < c.F; ++f) check_parts_filter(m, c.filters[f]);
-        if (n && k && !c.filter_of) throw InvalidArg("null argument");
-        for (uint64_t i = 0; i < n && k; ++i)
-            if (c.filter_of[i] < -1 || c.filter_of[i] >= (int64_t)c.F)
-                throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(c.filter_of[i]) + " is outside [-1, " +
-                                 std::to_string(c.F) + ")");
-    }
+    if (c.F && !c.filters) throw InvalidArg("null argument");
+    for (uint32_t f = 0; f < c.F; ++f) check_parts_filter(m, c.filters[f]);
+    if (n && k && !c.filter_of && c.F > 1) throw InvalidArg("null argument");
+    if (n && k && c.filter_of) check_filter_of(c.filter_of, n, c.F);
     if (c.exact && k > kExactMaxK)
         throw InvalidArg("exact search supports k <= " + std::to_string(kExactMaxK) + ", got k = " + std::to_string(k));
     if (n == 0 || k == 0) return;
@@ -4252,16 +4189,12 @@ void parts_search(cph_parts* m, const PartsCall& c) {
             oi = s.d_ids.p;
             od = s.d_dist.p;
         }
-        int r;
-        if (c.per_query) {
-            std::vector<const cph_filter*> fr(c.F);
-            for (uint32_t f = 0; f < c.F; ++f) fr[f] = c.filters[f]->f[p];
-            r = cph_search_batch_filters_device(h, dq, n, k, fr.data(), c.F, c.filter_of, c.exact ? 1 : 0, oi, od, s.st);
-        } else if (c.exact) {
-            r = cph_search_batch_exact_device(h, dq, n, k, c.f ? c.f->f[p] : nullptr, oi, od, s.st);
-        } else {
-            r = cph_search_batch_device_filtered(h, dq, n, k, c.f ? c.f->f[p] : nullptr, oi, od, s.st);
-        }
+        std::vector<const cph_filter*> fr(c.F);
+        for (uint32_t f = 0; f < c.F; ++f) fr[f] = c.filters[f]->f[p];
+        const cph_filter* one = c.F ? fr[0] : nullptr;
+        const int r = c.filter_of ? cph_search_batch_filters_device(h, dq, n, k, fr.data(), c.F, c.filter_of, c.exact ? 1 : 0, oi, od, s.st)
+                      : c.exact   ? cph_search_batch_exact_device(h, dq, n, k, one, oi, od, s.st)
+                                  : cph_search_batch_device_filtered(h, dq, n, k, one, oi, od, s.st);
         if (r != CPH_OK) {
             e = g_err;                            // (thread-local: this worker's message)
             return r;
@@ -4486,31 +4419,18 @@ int cph_parts_search_batch(cph_parts* m, const float* queries, uint64_t n, uint6
 
 int cph_parts_search_batch_filtered(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
                                     int64_t* ids, float* dist) {
-    return guarded([&] {
-        PartsCall c;
-        c.q = queries; c.n = n; c.k = k; c.f = f; c.ids = ids; c.dist = dist;
-        parts_search(m, c);
-    });
+    return guarded([&] { parts_search(m, batch_call(queries, n, k, &f, f ? 1u : 0u, nullptr, false, ids, dist)); });
 }
 
 int cph_parts_search_batch_exact(cph_parts* m, const float* queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
                                  int64_t* ids, float* dist) {
-    return guarded([&] {
-        PartsCall c;
-        c.q = queries; c.n = n; c.k = k; c.f = f; c.exact = true; c.ids = ids; c.dist = dist;
-        parts_search(m, c);
-    });
+    return guarded([&] { parts_search(m, batch_call(queries, n, k, &f, f ? 1u : 0u, nullptr, true, ids, dist)); });
 }
 
 int cph_parts_search_batch_filters(cph_parts* m, const float* queries, uint64_t n, uint64_t k,
                                    const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
                                    int64_t* ids, float* dist) {
-    return guarded([&] {
-        PartsCall c;
-        c.q = queries; c.n = n; c.k = k; c.per_query = true; c.filters = filters; c.F = n_filters; c.filter_of = filter_of;
-        c.exact = exact != 0; c.ids = ids; c.dist = dist;
-        parts_search(m, c);
-    });
+    return guarded([&] { parts_search(m, batch_call(queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist)); });
 }
 
 int cph_parts_search_batch_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, int64_t* d_ids, float* d_dist,
@@ -4520,33 +4440,19 @@ int cph_parts_search_batch_device(cph_parts* m, const float* d_queries, uint64_t
 
 int cph_parts_search_batch_device_filtered(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
                                            int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] {
-        PartsCall c;
-        c.q = d_queries; c.n = n; c.k = k; c.f = f; c.ids = d_ids; c.dist = d_dist;
-        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
-        parts_search(m, c);
-    });
+    return guarded([&] { parts_search(m, batch_call(d_queries, n, k, &f, f ? 1u : 0u, nullptr, false, d_ids, d_dist, true, stream)); });
 }
 
 int cph_parts_search_batch_exact_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k, const cph_parts_filter* f,
                                         int64_t* d_ids, float* d_dist, void* stream) {
-    return guarded([&] {
-        PartsCall c;
-        c.q = d_queries; c.n = n; c.k = k; c.f = f; c.exact = true; c.ids = d_ids; c.dist = d_dist;
-        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
-        parts_search(m, c);
-    });
+    return guarded([&] { parts_search(m, batch_call(d_queries, n, k, &f, f ? 1u : 0u, nullptr, true, d_ids, d_dist, true, stream)); });
 }
 
 int cph_parts_search_batch_filters_device(cph_parts* m, const float* d_queries, uint64_t n, uint64_t k,
                                           const cph_parts_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
                                           int exact, int64_t* d_ids, float* d_dist, void* stream) {
     return guarded([&] {
-        PartsCall c;
-        c.q = d_queries; c.n = n; c.k = k; c.per_query = true; c.filters = filters; c.F = n_filters; c.filter_of = filter_of;
-        c.exact = exact != 0; c.ids = d_ids; c.dist = d_dist;
-        c.on_device = true; c.stream = reinterpret_cast<hipStream_t>(stream);
-        parts_search(m, c);
+        parts_search(m, batch_call(d_queries, n, k, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, true, stream));
     });
 }
 
@@ -4556,9 +4462,7 @@ int cph_parts_search(cph_parts* m, const float* query, uint64_t k, int64_t* ids,
         const uint64_t kk = std::max<uint64_t>(k, 1);
         std::vector<int64_t> ri(kk);
         std::vector<float> rd(kk);
-        PartsCall c;
-        c.q = query; c.n = 1; c.k = kk; c.ids = ri.data(); c.dist = rd.data();
-        parts_search(m, c);
+        parts_search(m, batch_call<cph_parts_filter>(query, 1, kk, nullptr, 0, nullptr, false, ri.data(), rd.data()));
         uint64_t cnt = 0;
         while (cnt < kk && ri[cnt] >= 0) ++cnt;       // the merge keeps padding last
         std::copy(ri.begin(), ri.begin() + cnt, ids);
@@ -5224,10 +5128,7 @@ void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_querie
     try {
         {
             InternalIdsScope internal(h);
-            if (filter_of)
-                search_batch_filters_device_locked(h, d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, st);
-            else
-                search_batch_device_locked(h, d_queries, n, C, F ? filters[0] : nullptr, gs.r_ids.p, gs.r_dist.p, st, exact);
+            search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, true, st));
         }
         GroupArgs a{};
         a.ids = gs.r_ids.p;
@@ -5326,44 +5227,26 @@ void multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uint64
                           const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
                           bool exact, int64_t* ids, float* dist, int32_t* keys_out, int32_t* counts, uint8_t* complete) {
     if (!m) throw InvalidArg("null handle");
-    std::shared_lock<std::shared_mutex> lk(m->life);
     const uint32_t R = (uint32_t)m->reps.size();
+    const uint64_t dim = m->reps[0]->dim;
     if (F && !filters) throw InvalidArg("null argument");
     if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    for (uint32_t r = 0; r < R; ++r) {              // (before any shard runs: a refusal must not leave half of the rows written)
-        cph_index* h = m->reps[r];
-        std::lock_guard<std::mutex> lg(h->mu);
+    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
         grouped_has_work(h, queries, n, k, g, C, filters, F, filter_of, ids, dist, keys_out, counts, complete);
         if (keys && !keys[r]) throw InvalidArg("a grouped multi-device search needs one keys object per replica");
         (void)group_key_column(h, keys ? keys[r] : nullptr);
-        for (uint32_t f = 0; f < F; ++f) {
-            if (!filters[(size_t)f * R + r]) throw InvalidArg("a filtered multi-device search needs one filter per replica");
-            check_filter(h, filters[(size_t)f * R + r]);
-        }
-    }
-    if (n == 0) return;
-    for (uint64_t i = 0; i < n && filter_of; ++i)
-        if (filter_of[i] < -1 || filter_of[i] >= (int64_t)F)
-            throw InvalidArg("filter_of[" + std::to_string(i) + "] = " + std::to_string(filter_of[i]) + " is outside [-1, " +
-                             std::to_string(F) + ")");
-    const std::vector<Shard> plan = plan_shards(n, R, m->min_shard.load(), (uint32_t)(m->rr.fetch_add(1) % R));
-    const uint64_t dim = m->reps[0]->dim;
-    std::string err;
-    const int rc = m->pool->run(plan, [&](const Shard& s, std::string& e) {
-        cph_index* h = m->reps[s.replica];
-        std::vector<const cph_filter*> fr(F);
-        for (uint32_t f = 0; f < F; ++f) fr[f] = filters[(size_t)f * R + s.replica];
-        const int r = cph_search_grouped(h, queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, g, C, keys ? keys[s.replica] : nullptr,
-                                         F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0,
-                                         ids ? ids + s.lo * k * g : nullptr, dist ? dist + s.lo * k * g : nullptr,
-                                         keys_out ? keys_out + s.lo * k : nullptr, counts ? counts + s.lo * k : nullptr,
-                                         complete ? complete + s.lo : nullptr);
-        if (r != CPH_OK) e = g_err;               // (thread-local: this worker's message)
-        return r;
-    }, err);
-    if (rc != CPH_OK) raise_status(rc, err);
-    std::lock_guard<std::mutex> lg(m->last_mu);
-    m->last_plan = plan;
+        check_replica_filters(h, filters, F, R, r);
+    }, [&] {
+        if (n && filter_of) check_filter_of(filter_of, n, F);
+        return n != 0;
+    }, [&](const Shard& s, size_t) {
+        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
+        return cph_search_grouped(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, g, C,
+                                  keys ? keys[s.replica] : nullptr, F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr,
+                                  exact ? 1 : 0, ids ? ids + s.lo * k * g : nullptr, dist ? dist + s.lo * k * g : nullptr,
+                                  keys_out ? keys_out + s.lo * k : nullptr, counts ? counts + s.lo * k : nullptr,
+                                  complete ? complete + s.lo : nullptr);
+    });
 }
 
 }  // namespace

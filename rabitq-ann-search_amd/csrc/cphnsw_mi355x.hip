@@ -278,6 +278,7 @@ struct cph_index {
     DevBuf<float> d_signs;
     DevBuf<uint32_t> d_upper;          // all layers' nodes | offsets | nbrs, concatenated
     DevBuf<uint32_t> d_row_of;
+    DevBuf<uint32_t> d_nbr_info;       // the mapped layers' row_of[nbrs[e]], layer after layer
     UpperLayerDev layers[kMaxUpperLayers];
     int32_t dev_max_level = 0;
     float norm_factor = 0.0f, inv_sqrt_d = 0.0f;
@@ -551,15 +552,24 @@ void upload_feeders(cph_index* h) {
     h->d_upper.alloc(flat.size() + 1);
     if (!flat.empty())
         HIP_CHECK(hipMemcpy(h->d_upper.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
-    for (int l = 0; l < kMaxUpperLayers; ++l) h->layers[l] = UpperLayerDev{nullptr, nullptr, nullptr, nullptr, 0};
+    for (int l = 0; l < kMaxUpperLayers; ++l) h->layers[l] = UpperLayerDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     // dense vertex -> row maps for the layers where a binary search would be a long chain of
-    // dependent loads (4 B x n each)
+    // dependent loads (4 B x n each), and next to each mapped layer's edges the map entry of every
+    // neighbour (4 B per edge): a hop's edges then bring the next hop's row with them
     int mapped = 0;
-    for (int l = 0; l < nl; ++l) mapped += hi.upper[l].size() > 16 ? 1 : 0;
+    size_t mapped_edges = 0;
+    for (int l = 0; l < nl; ++l) {
+        if (hi.upper[l].size() <= 16) continue;
+        ++mapped;
+        for (const auto& e : hi.upper[l]) mapped_edges += e.nbrs.size();
+    }
     h->d_row_of.alloc((size_t)mapped * n + 1);
-    std::vector<uint32_t> row_of;
+    h->d_nbr_info.alloc(mapped_edges + 1);
+    std::vector<uint32_t> row_of, nbr_info;
+    size_t info_off = 0;
     for (int l = 0, m = 0; l < nl; ++l) {
         const uint32_t* dmap = nullptr;
+        const uint32_t* dinfo = nullptr;
         if (hi.upper[l].size() > 16) {
             // vertex -> first edge | degree << 26 (the encoder then needs neither `nodes` nor `offsets`)
             row_of.assign(n, kInvalidNode);
@@ -571,13 +581,22 @@ void upload_feeders(cph_index* h) {
                 row_of[hi.upper[l][r].node] = (uint32_t)first | ((uint32_t)deg << 26);
                 first += deg;
             }
-            if (!fits) { h->layers[l] = UpperLayerDev{h->d_upper.p + off_nodes[l], h->d_upper.p + off_offs[l], h->d_upper.p + off_nbrs[l], nullptr, (uint32_t)hi.upper[l].size()}; ++m; continue; }
+            if (!fits) { h->layers[l] = UpperLayerDev{h->d_upper.p + off_nodes[l], h->d_upper.p + off_offs[l], h->d_upper.p + off_nbrs[l], nullptr, nullptr, (uint32_t)hi.upper[l].size()}; ++m; continue; }
             HIP_CHECK(hipMemcpy(h->d_row_of.p + (size_t)m * n, row_of.data(), n * 4, hipMemcpyHostToDevice));
             dmap = h->d_row_of.p + (size_t)m * n;
             ++m;
+            // (a neighbour outside the index or the layer ends the descent there, as its missing row_of entry did)
+            nbr_info.clear();
+            for (const auto& e : hi.upper[l])
+                for (const uint32_t nb : e.nbrs) nbr_info.push_back(nb < n ? row_of[nb] : kInvalidNode);
+            if (info_off + nbr_info.size() > mapped_edges) throw std::runtime_error("upper layers: edge count changed during upload");
+            if (!nbr_info.empty())
+                HIP_CHECK(hipMemcpy(h->d_nbr_info.p + info_off, nbr_info.data(), nbr_info.size() * 4, hipMemcpyHostToDevice));
+            dinfo = h->d_nbr_info.p + info_off;
+            info_off += nbr_info.size();
         }
         h->layers[l] = UpperLayerDev{h->d_upper.p + off_nodes[l], h->d_upper.p + off_offs[l],
-                                     h->d_upper.p + off_nbrs[l], dmap, (uint32_t)hi.upper[l].size()};
+                                     h->d_upper.p + off_nbrs[l], dmap, dinfo, (uint32_t)hi.upper[l].size()};
     }
     for (auto& s : h->sets) release_scratch(s);
     reset_adaptation(h);
@@ -3528,7 +3547,7 @@ HostIndex host_scalars(const HostIndex& s) {
 }
 
 // dst becomes a searchable copy of the finalized src: src's resident device arrays (blocks in the resident layout,
-// vectors, norms, the row map, rotation signs, upper layers and their vertex -> row tables) copied device to device (no peer access needed), its search
+// vectors, norms, the row map, rotation signs, upper layers, their vertex -> row tables and per-edge rows) copied device to device (no peer access needed), its search
 // scalars copied, the upper-layer pointers rebased onto dst's own buffers.  dst keeps no host arrays.
 void replicate(cph_index* src, cph_index* dst) {
     std::lock_guard<std::mutex> ls(src->mu), ld(dst->mu);
@@ -3564,6 +3583,7 @@ void replicate(cph_index* src, cph_index* dst) {
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
     copy(dst->d_row_of, src->d_row_of);
+    copy(dst->d_nbr_info, src->d_nbr_info);
     HIP_CHECK(hipStreamSynchronize(st));
     sync_removed(dst);
     auto rebase = [](const uint32_t* p, const DevBuf<uint32_t>& from, const DevBuf<uint32_t>& to) -> const uint32_t* {
@@ -3573,7 +3593,7 @@ void replicate(cph_index* src, cph_index* dst) {
         const UpperLayerDev& s = src->layers[l];
         dst->layers[l] = UpperLayerDev{rebase(s.nodes, src->d_upper, dst->d_upper), rebase(s.offsets, src->d_upper, dst->d_upper),
                                        rebase(s.nbrs, src->d_upper, dst->d_upper), rebase(s.row_of, src->d_row_of, dst->d_row_of),
-                                       s.n_nodes};
+                                       rebase(s.nbr_info, src->d_nbr_info, dst->d_nbr_info), s.n_nodes};
     }
     reset_adaptation(dst);
     dst->finalized = true;

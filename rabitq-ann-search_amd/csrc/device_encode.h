@@ -11,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "cph_core.h"
 #include "device_fastscan.h"
 
@@ -22,6 +24,8 @@ struct UpperLayerDev {       // CSR of one upper layer, nodes sorted ascending (
     const uint32_t* nbrs;
     const uint32_t* row_of;  // [n] vertex -> first edge | degree << 26 (kInvalidNode if absent), or null:
                              // binary search over `nodes` + `offsets`
+    const uint32_t* nbr_info;// [n_edges] row_of[nbrs[e]]: a hop's edges bring the next hop's (first edge, degree)
+                             // with them; present exactly where row_of is
     uint32_t n_nodes;
 };
 
@@ -57,6 +61,90 @@ __device__ __forceinline__ void wave_fht(float* x, uint32_t D, int lane) {
     }
 }
 
+// 8 N elements of sum (q - v)^2 on a lane PAIR: half h = lane & 1 runs chains 4h .. 4h+3 of the eight group_l2sq8
+// chains (chain c = elements c, c + 8, ... ascending, the order of chain_l2<16>).  `q` and `v` already point at
+// element 4h of the part: one 64-bit base per lane, N dwordx4 loads at immediate offsets, all in flight together.
+// The query comes from LDS through a ring of QR float4 (left to itself the compiler reads all N up front: 4 N
+// more registers next to the 4 N of the loads).
+template <int N, int QR>
+__device__ __forceinline__ void pair_l2_part(const float* q_lds, const float* __restrict__ v, float (&c)[4]) {
+    float4 r[N], q[QR];
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = *reinterpret_cast<const float4*>(v + 8 * j);
+#pragma unroll
+    for (int j = 0; j < QR; ++j) q[j] = *reinterpret_cast<const float4*>(q_lds + 8 * j);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const float4 qq = q[j % QR];
+        const float d0 = qq.x - r[j].x, d1 = qq.y - r[j].y, d2 = qq.z - r[j].z, d3 = qq.w - r[j].w;
+        c[0] = __fmaf_rn(d0, d0, c[0]);
+        c[1] = __fmaf_rn(d1, d1, c[1]);
+        c[2] = __fmaf_rn(d2, d2, c[2]);
+        c[3] = __fmaf_rn(d3, d3, c[3]);
+        if (j + QR < N) q[j % QR] = *reinterpret_cast<const float4*>(q_lds + 8 * (j + QR));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// The pair's reduction: s_i = c_i + c_{i+4} (the partner holds the other four chains), then (s0 + s1) + (s2 + s3) --
+// the tree ((c0+c4)+(c1+c5))+((c2+c6)+(c3+c7)) of group_reduce8; fp add is commutative, so both lanes of the pair
+// end with the bits group_l2sq8 gives.
+__device__ __forceinline__ float pair_reduce(const float (&c)[4]) {
+    const float s0 = c[0] + dpp_mov<0xB1>(c[0]), s1 = c[1] + dpp_mov<0xB1>(c[1]);   // quad_perm [1,0,3,2]: lane ^ 1
+    const float s2 = c[2] + dpp_mov<0xB1>(c[2]), s3 = c[3] + dpp_mov<0xB1>(c[3]);
+    return (s0 + s1) + (s2 + s3);
+}
+
+// (distance, position) minimum of the descent: smallest distance, first stored position on a tie.
+__device__ __forceinline__ void min_step(float& cand, uint32_t& pos, float od, uint32_t op) {
+    if (od < cand || (od == cand && op < pos)) { cand = od; pos = op; }
+}
+template <int CTRL>
+__device__ __forceinline__ void min_step_dpp(float& cand, uint32_t& pos) {
+    min_step(cand, pos, dpp_mov<CTRL>(cand), (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pos, CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float uniform_f32(float v) {   // a value every lane holds, moved to a scalar register
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// the minimum over the four rows of 16 lanes, each row already holding one value: scalar from here on
+__device__ __forceinline__ void min_rows(float& cand, uint32_t& pos) {
+    float bc = uniform_f32(cand);
+    uint32_t bp = uniform_u32(pos);
+#pragma unroll
+    for (int r = 16; r < 64; r += 16)
+        min_step(bc, bp, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cand), r)),
+                 (uint32_t)__builtin_amdgcn_readlane((int)pos, r));
+    cand = bc;
+    pos = bp;
+}
+// The lane index as a value the optimiser cannot see through (device_search.h's opaque_lane, which comes after this
+// header): what a path derives from it (LDS and row offsets, group indices) is computed inside that path, not hoisted
+// out of the enclosing loops and kept live across the load registers of the paired pass.
+__device__ __forceinline__ int fresh_lane(int lane) {
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
+// One layer's descriptor, read from the kernel-argument segment with scalar loads at a run-time index (indexing the
+// by-value array instead makes the compiler keep all 24 descriptors in SGPRs and spill them).  EncodeArgs is
+// encode_kernel's only argument, so it starts the segment.
+__device__ __forceinline__ UpperLayerDev load_layer(int idx) {
+    static_assert(sizeof(UpperLayerDev) == 48 && offsetof(UpperLayerDev, n_nodes) == 40, "six qwords per descriptor");
+    using kbyte = const __attribute__((address_space(4))) unsigned char;
+    using kqword = const __attribute__((address_space(4))) uint64_t;
+    kbyte* seg = (kbyte*)__builtin_amdgcn_kernarg_segment_ptr();
+    kqword* w = reinterpret_cast<kqword*>(seg + offsetof(EncodeArgs, layers) + (size_t)idx * sizeof(UpperLayerDev));
+    UpperLayerDev L;
+    L.nodes = reinterpret_cast<const uint32_t*>(w[0]);
+    L.offsets = reinterpret_cast<const uint32_t*>(w[1]);
+    L.nbrs = reinterpret_cast<const uint32_t*>(w[2]);
+    L.row_of = reinterpret_cast<const uint32_t*>(w[3]);
+    L.nbr_info = reinterpret_cast<const uint32_t*>(w[4]);
+    L.n_nodes = (uint32_t)w[5];
+    return L;
+}
+
 // LDS: raw padded query [D] | work buffer [D]
 __host__ __device__ inline size_t encode_lds_bytes(uint32_t D) { return (size_t)D * 8; }
 
@@ -64,9 +152,9 @@ __global__ __launch_bounds__(64) void encode_kernel(EncodeArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     float* qv = reinterpret_cast<float*>(smem);
     float* x = qv + a.D;
-    const int lane = threadIdx.x;
     const uint32_t D = a.D;
     for (uint32_t qi = blockIdx.x; qi < a.nq; qi += gridDim.x) {
+        const int lane = fresh_lane(threadIdx.x);   // per query: nothing lane-derived stays live from one to the next
         for (uint32_t d = lane; d < D; d += 64) {
             float v = d < a.dim ? a.queries_raw[(size_t)qi * a.dim + d] : 0.0f;
             qv[d] = v;
@@ -128,46 +216,99 @@ __global__ __launch_bounds__(64) void encode_kernel(EncodeArgs a) {
         const float sum_qu = (float)usum;  // integer-valued partial sums: exact in any order
         const float df = (float)D;
         QueryHeader hd;
-        hd.A = (2.0f * delta) * a.inv_sqrt_d;
-        hd.B = (2.0f * vl) * a.inv_sqrt_d;
-        hd.C = -__fmaf_rn(df, vl, delta * sum_qu) * a.inv_sqrt_d;
+        // (every lane computed the same three: scalar registers carry them across the descent)
+        hd.A = uniform_f32((2.0f * delta) * a.inv_sqrt_d);
+        hd.B = uniform_f32((2.0f * vl) * a.inv_sqrt_d);
+        hd.C = uniform_f32(-__fmaf_rn(df, vl, delta * sum_qu) * a.inv_sqrt_d);
 
         // ---- upper-layer greedy descent (api/hnsw_index.hpp:196-202,617-638) ---------------
         uint32_t ep = a.entry;
         float ep_dist = 0.0f;
         if (a.max_level > 0 && ep < a.n) {
+            const bool paired = (D % 128u) == 0;
             for (int level = a.max_level; level >= 1; --level) {
-                const UpperLayerDev& Ly = a.layers[level - 1];
+                const UpperLayerDev Ly = load_layer(level - 1);
                 // distance to the layer's entry: the previous layer's winner, whose distance is already
-                // known (same query, same vector, same arithmetic => same float as recomputing it)
-                float best = (level == a.max_level) ? group_l2sq8(qv, a.raw + (size_t)ep * D, D, lane & 7) : ep_dist;
+                // known (same query, same vector, same arithmetic => same float as recomputing it).
+                // (Requesting the entry's vector ahead of the three rotation passes was tried: its 16 registers stay
+                // live across the rotation's unrolled loops, 101 VGPRs and 4 waves per SIMD.  It is loaded here.)
+                float best = (level == a.max_level)
+                                 ? uniform_f32(group_l2sq8(qv, a.raw + (size_t)ep * D, D, fresh_lane(lane) & 7))
+                                 : ep_dist;
                 uint32_t best_id = ep;
-                bool improved = true;
-                while (improved) {
-                    improved = false;
-                    float cand = 3.402823466e+38f;
-                    uint32_t cand_id = kInvalidNode;
-                    uint32_t cand_pos = 0xFFFFFFFFu;
-                    if (Ly.row_of) {
-                        // dense vertex -> (first edge, degree) map, then the whole neighbour list in one
-                        // load: two dependent round trips per hop ahead of the vectors instead of
-                        // log2(n_nodes) + 1 + one per pass
-                        const uint32_t info = Ly.row_of[best_id];
-                        if (info == kInvalidNode) break;
+                if (Ly.row_of) {
+                    // dense vertex -> (first edge, degree) map: read once, for the vertex the layer is entered at.
+                    // Every later hop gets its own from nbr_info, in the round trip that fetches the edges, so a
+                    // hop is two dependent round trips: edges, then vectors.
+                    uint32_t info = Ly.row_of[best_id];
+                    while (info != kInvalidNode) {
                         const uint32_t beg = info & 0x03FFFFFFu, cnt = info >> 26;
-                        const uint32_t mine = (uint32_t)lane < cnt ? Ly.nbrs[beg + lane] : best_id;
-                        // (issuing the loads of all passes together was tried: 150 VGPRs, 3 waves per
-                        // SIMD, and the kernel got slower -- occupancy x latency stays the same product)
-                        for (uint32_t base = 0; base < cnt; base += 8) {
-                            const uint32_t pos = base + (lane >> 3);
-                            const bool have = pos < cnt;
-                            const uint32_t nb = (uint32_t)__shfl((int)mine, (int)(have ? pos : 0));
-                            const float d = group_l2sq8(qv, a.raw + (size_t)(have ? nb : best_id) * D, D, lane & 7);
-                            if (have && (d < cand || (d == cand && pos < cand_pos))) {
-                                cand = d; cand_id = nb; cand_pos = pos;
+                        float cand = 3.402823466e+38f;
+                        uint32_t cand_pos = 0xFFFFFFFFu;
+                        uint32_t mine = best_id, mine_info = kInvalidNode, src;
+                        if (paired && cnt <= 32) {
+                            // lanes 2p, 2p+1 own neighbour p and four of its eight chains each: the whole list in
+                            // one pass.  Per 64 elements a lane has 8 dwordx4 loads (32 registers) in flight: two
+                            // round trips per 128-element chunk, 79 VGPRs.  All 16 loads of a chunk together need
+                            // 64 registers next to the ~34 that are live across the pass: 98 and up, 4-5 waves per
+                            // SIMD, where an encoder wave no longer fits the 80 registers a search wave frees.
+                            // (Eight lanes and 16 dword loads per neighbour, all passes together: 150 VGPRs.)
+                            const int pl = fresh_lane(lane);
+                            const uint32_t p = (uint32_t)pl >> 1;
+                            const int half = pl & 1;
+                            const bool have = p < cnt;
+                            float c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                            if (have) {
+                                mine = Ly.nbrs[beg + p];
+                                mine_info = Ly.nbr_info[beg + p];
+                                const float* v = a.raw + (size_t)mine * D + 4 * half;
+                                for (uint32_t base = 0; base < D; base += 64) pair_l2_part<8, 3>(qv + base + 4 * half, v + base, c);
                             }
+                            const float d = pair_reduce(c);
+                            if (have && d < cand) { cand = d; cand_pos = p; }
+                            // both lanes of a pair agree; quads, rows of 16, then the four rows
+                            min_step_dpp<0x4E>(cand, cand_pos);    // quad_perm [2,3,0,1]
+                            min_step_dpp<0x124>(cand, cand_pos);   // row_ror:4
+                            min_step_dpp<0x128>(cand, cand_pos);   // row_ror:8
+                            min_rows(cand, cand_pos);
+                            src = cand_pos * 2;
+                        } else {
+                            // more than 32 neighbours (row_of allows 62) or D not a multiple of 128: eight lanes per
+                            // neighbour, eight neighbours per pass
+                            const int sl = fresh_lane(lane);
+                            if ((uint32_t)sl < cnt) {
+                                mine = Ly.nbrs[beg + sl];
+                                mine_info = Ly.nbr_info[beg + sl];
+                            }
+                            for (uint32_t base = 0; base < cnt; base += 8) {
+                                const uint32_t pos = base + (sl >> 3);
+                                const bool have = pos < cnt;
+                                const uint32_t nb = (uint32_t)__shfl((int)mine, (int)(have ? pos : 0));
+                                const float d = group_l2sq8(qv, a.raw + (size_t)(have ? nb : best_id) * D, D, sl & 7);
+                                if (have && (d < cand || (d == cand && pos < cand_pos))) { cand = d; cand_pos = pos; }
+                            }
+                            for (int o = 8; o < 64; o <<= 1) {
+                                const float od = __shfl_xor(cand, o);
+                                const uint32_t op = __shfl_xor(cand_pos, o);
+                                if (od < cand || (od == cand && op < cand_pos)) { cand = od; cand_pos = op; }
+                            }
+                            cand = uniform_f32(cand);
+                            src = cand_pos = uniform_u32(cand_pos);
                         }
-                    } else {
+                        // every lane holds the same (cand, cand_pos) now; the winner's id and its (first edge,
+                        // degree) come from the lane that loaded them
+                        if (cand_pos == 0xFFFFFFFFu || !(cand < best)) break;
+                        best = cand;
+                        best_id = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)src);
+                        info = (uint32_t)__builtin_amdgcn_readlane((int)mine_info, (int)src);
+                    }
+                } else {
+                    bool improved = true;
+                    while (improved) {
+                        improved = false;
+                        float cand = 3.402823466e+38f;
+                        uint32_t cand_id = kInvalidNode;
+                        uint32_t cand_pos = 0xFFFFFFFFu;
                         // find_edge: lower_bound over the sorted node list (uniform across lanes)
                         uint32_t lo = 0, hi = Ly.n_nodes;
                         while (lo < hi) {
@@ -177,26 +318,29 @@ __global__ __launch_bounds__(64) void encode_kernel(EncodeArgs a) {
                         if (lo >= Ly.n_nodes || Ly.nodes[lo] != best_id) break;
                         const uint32_t beg = Ly.offsets[lo], end = Ly.offsets[lo + 1];
                         // neighbours in stored order; strict improvement => the first minimum wins
+                        const int sl = fresh_lane(lane);
                         for (uint32_t base = beg; base < end; base += 8) {
-                            const uint32_t pos = base + (lane >> 3);
+                            const uint32_t pos = base + (sl >> 3);
                             const bool have = pos < end;
                             const uint32_t nb = have ? Ly.nbrs[pos] : best_id;
-                            const float d = group_l2sq8(qv, a.raw + (size_t)nb * D, D, lane & 7);
+                            const float d = group_l2sq8(qv, a.raw + (size_t)nb * D, D, sl & 7);
                             if (have && (d < cand || (d == cand && pos < cand_pos))) {
                                 cand = d; cand_id = nb; cand_pos = pos;
                             }
                         }
-                    }
-                    for (int o = 8; o < 64; o <<= 1) {
-                        const float od = __shfl_xor(cand, o);
-                        const uint32_t oi = __shfl_xor(cand_id, o);
-                        const uint32_t op = __shfl_xor(cand_pos, o);
-                        if (od < cand || (od == cand && op < cand_pos)) { cand = od; cand_id = oi; cand_pos = op; }
-                    }
-                    if (cand_id != kInvalidNode && cand < best) {
-                        best = cand;
-                        best_id = cand_id;
-                        improved = true;
+                        for (int o = 8; o < 64; o <<= 1) {
+                            const float od = __shfl_xor(cand, o);
+                            const uint32_t oi = __shfl_xor(cand_id, o);
+                            const uint32_t op = __shfl_xor(cand_pos, o);
+                            if (od < cand || (od == cand && op < cand_pos)) { cand = od; cand_id = oi; cand_pos = op; }
+                        }
+                        cand = uniform_f32(cand);          // (the same in every lane)
+                        cand_id = uniform_u32(cand_id);
+                        if (cand_id != kInvalidNode && cand < best) {
+                            best = cand;
+                            best_id = cand_id;
+                            improved = true;
+                        }
                     }
                 }
                 ep = best_id;

@@ -104,11 +104,22 @@ int cph_encode_edges(int device, uint64_t dim, uint64_t bits, const float* paren
 
 /* Construction hook: the neighbour-selection kernel on ONE vertex with a given candidate list -- the rule of
  * graph/neighbor_selection.hpp:21-88 (select_neighbors_alpha_cng), deterministic on a fixed list.  x = [n][D] padded
- * vectors, fwd = 32 forward candidates (0xFFFFFFFF = none), rev = up to 96 further candidates (the reverse edges),
- * err = per-vertex margin terms or null.  out_ids = 32 selected ids (0xFFFFFFFF padded), *out_cnt = how many. */
+ * vectors, fwd = 32 forward candidates (0xFFFFFFFF = none), rev = up to 65,536 further candidates (the reverse edges),
+ * err = per-vertex margin terms or null.  out_ids = 32 selected ids (0xFFFFFFFF padded), *out_cnt = how many.
+ * Up to 96 reverse edges all candidates are considered; beyond that the vertex is a hub and the kernel keeps the
+ * nearest 64 unique candidates (ties by id) of fwd and rev together, whatever the order of rev. */
 int cph_select_hook(int device, const float* x, uint64_t n, uint64_t D, uint32_t vertex, const uint32_t* fwd,
                     const uint32_t* rev, uint64_t n_rev, uint32_t R, float alpha, float tau, float alpha_max,
                     const float* err, uint32_t* out_ids, uint32_t* out_cnt);
+
+/* Construction hook: layer-0 selection of a WHOLE table as finalize() launches it -- the reverse CSR built from
+ * knn[n][32] (0xFFFFFFFF = none; every other id < n), then the selection kernel over all n rows on the production
+ * grid (grid_cap = 0) or on at most grid_cap workgroups, so that one workgroup walks many rows.  out_ids[n][32]
+ * (0xFFFFFFFF padded), out_cnt[n]; rev_off[n + 1] / rev[n * 32] (either may be null) receive the reverse CSR the
+ * kernel read: rev_off[n] entries of rev are written, each segment in the order the fill's atomics produced. */
+int cph_select_layer_hook(int device, const float* x, uint64_t n, uint64_t D, const uint32_t* knn, uint32_t R, float alpha,
+                          float tau, float alpha_max, const float* err, uint32_t grid_cap, uint32_t* out_ids,
+                          uint32_t* out_cnt, uint64_t* rev_off, uint32_t* rev);
 
 /* Construction hook: the calibration sampler (api/hnsw_index.hpp:770-1040 gathers the same quantities) on given sample
  * queries [ns][dim] and start vertices: per sample one greedy hop, then per edge of the vertex arrived at

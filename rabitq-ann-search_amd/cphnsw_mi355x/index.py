@@ -1465,7 +1465,8 @@ def encode_edges(parent, nbrs, bits, device=None):
 
 def select_neighbors_debug(x, vertex, fwd, rev, R, alpha, tau, alpha_max=0.0, err=None, device=None):
     """Construction hook: the GPU selection kernel on one vertex (x = [n, D] padded vectors, fwd = 32 candidate ids with
-    0xFFFFFFFF for none, rev = up to 96 more).  Returns the selected ids."""
+    0xFFFFFFFF for none, rev = up to 65,536 more: the reverse edges).  Beyond 96 reverse edges the vertex is a hub and the
+    kernel keeps the nearest 64 unique candidates of both lists, whatever the order of rev.  Returns the selected ids."""
     x = _as_f32(x)
     n, D = x.shape
     fwd = np.ascontiguousarray(fwd, np.uint32)
@@ -1479,6 +1480,28 @@ def select_neighbors_debug(x, vertex, fwd, rev, R, alpha, tau, alpha_max=0.0, er
                                           len(rev), int(R), float(alpha), float(tau), float(alpha_max),
                                           None if e is None else e.ctypes.data, out.ctypes.data, cnt.ctypes.data))
     return out[:cnt[0]].copy()
+
+
+def select_layer_debug(x, knn, R, alpha, tau, alpha_max=0.0, err=None, grid_cap=0, device=None):
+    """Construction hook: layer-0 selection of a whole table as finalize() launches it (x = [n, D] padded vectors, knn =
+    [n, 32] ids with 0xFFFFFFFF for none): the reverse CSR built from the table, then the selection kernel over all rows,
+    on the production grid or on at most grid_cap workgroups.  Returns (ids u32[n, 32] padded with 0xFFFFFFFF, counts
+    u32[n], rev_off u64[n + 1], rev u32[rev_off[n]]): the selected lists and the reverse CSR the kernel read."""
+    x = _as_f32(x)
+    n, D = x.shape
+    knn = np.ascontiguousarray(knn, np.uint32)
+    if knn.shape != (n, 32):
+        raise ValueError("knn must be a (n, 32) array")
+    ids = np.zeros((n, 32), np.uint32)
+    cnt = np.zeros(n, np.uint32)
+    off = np.zeros(n + 1, np.uint64)
+    rev = np.zeros(n * 32, np.uint32)
+    e = None if err is None else _as_f32(err)
+    dev = _default_device() if device is None else int(device)
+    _lib.check(_lib.lib().cph_select_layer_hook(dev, x.ctypes.data, n, D, knn.ctypes.data, int(R), float(alpha), float(tau),
+                                                float(alpha_max), None if e is None else e.ctypes.data, int(grid_cap),
+                                                ids.ctypes.data, cnt.ctypes.data, off.ctypes.data, rev.ctypes.data))
+    return ids, cnt, off, rev[:int(off[n])].copy()
 
 
 def heap_ops_debug(ops, keys, ids, device=None):

@@ -217,11 +217,20 @@ inline void reverse_csr(const uint32_t* d_knn, size_t rows, DevBuf<uint64_t>& d_
     HIP_CHECK(hipGetLastError());
 }
 
+// The reverse CSR a layer was selected from, for a caller that wants to look at it (the whole-layer test hook).
+struct LayerCsr {
+    DevBuf<uint64_t> off;    // [rows + 1]
+    DevBuf<uint32_t> rev;    // [off[rows] + 1] row indices, in the order the fill kernel's atomics gave them
+};
+
+// grid_cap (tests only): 0 = the production grid, else at most that many workgroups, so that one workgroup walks
+// many rows.  csr: where to leave the reverse CSR, or null.
 inline void select_layer(const float* d_x, size_t D, uint32_t* d_knn /* row indices; translated in place */,
                          size_t rows, const uint32_t* d_row_ids, const LayerParams& lp, int num_cus,
-                         uint32_t* d_out, uint32_t* d_out_cnt) {
-    DevBuf<uint64_t> d_off;
-    DevBuf<uint32_t> d_rev;
+                         uint32_t* d_out, uint32_t* d_out_cnt, LayerCsr* csr = nullptr, uint32_t grid_cap = 0) {
+    LayerCsr local;
+    DevBuf<uint64_t>& d_off = csr ? csr->off : local.off;
+    DevBuf<uint32_t>& d_rev = csr ? csr->rev : local.rev;
     reverse_csr(d_knn, rows, d_off, d_rev);
     if (d_row_ids) {
         hipLaunchKernelGGL(remap_ids_kernel, dim3(grid_for(rows * kKnnK, 256)), dim3(256), 0, nullptr, d_knn,
@@ -232,7 +241,8 @@ inline void select_layer(const float* d_x, size_t D, uint32_t* d_knn /* row indi
     a.x = d_x; a.fwd = d_knn; a.rev_off = d_off.p; a.rev = d_rev.p; a.row_ids = d_row_ids; a.err = lp.d_err;
     a.rows = rows; a.D = (uint32_t)D; a.R = lp.R; a.alpha = lp.alpha; a.tau = lp.tau; a.alpha_max = lp.alpha_max;
     a.out = d_out; a.out_cnt = d_out_cnt;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(rows, (uint64_t)num_cus * 32);
+    uint32_t grid = (uint32_t)std::min<uint64_t>(rows, (uint64_t)num_cus * 32);
+    if (grid_cap && grid_cap < grid) grid = grid_cap;
     hipLaunchKernelGGL(select_kernel, dim3(grid), dim3(64), select_lds(a.D), nullptr, a);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());

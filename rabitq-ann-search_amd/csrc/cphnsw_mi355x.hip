@@ -2042,7 +2042,8 @@ int cph_select_hook(int device, const float* x, uint64_t n, uint64_t D, uint32_t
     return guarded([&] {
         if (!x || !fwd || !out_ids || !out_cnt || n == 0 || vertex >= n) throw InvalidArg("bad arguments");
         if (D < 16 || D > 2048 || (D & (D - 1))) throw InvalidArg("D must be a power of two in 16..2048");
-        if (R == 0 || R > 32 || n_rev > 96) throw InvalidArg("R must be 1..32 and n_rev <= 96 (the hub path is not a unit case)");
+        if (R == 0 || R > 32 || n_rev > 65536) throw InvalidArg("R must be 1..32 and n_rev <= 65536");
+        if (n_rev && !rev) throw InvalidArg("bad arguments");
         for (int i = 0; i < 32; ++i)
             if (fwd[i] != kInvalidNode && fwd[i] >= n) throw InvalidArg("candidate out of range");
         for (uint64_t i = 0; i < n_rev; ++i)
@@ -2073,6 +2074,41 @@ int cph_select_hook(int device, const float* x, uint64_t n, uint64_t D, uint32_t
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out_ids, d_out.p, 128, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(out_cnt, d_cnt.p, 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_select_layer_hook(int device, const float* x, uint64_t n, uint64_t D, const uint32_t* knn, uint32_t R, float alpha,
+                          float tau, float alpha_max, const float* err, uint32_t grid_cap, uint32_t* out_ids,
+                          uint32_t* out_cnt, uint64_t* rev_off, uint32_t* rev) {
+    return guarded([&] {
+        if (!x || !knn || !out_ids || !out_cnt || n == 0 || n >= kInvalidNode) throw InvalidArg("bad arguments");
+        if (D < 16 || D > 2048 || (D & (D - 1))) throw InvalidArg("D must be a power of two in 16..2048");
+        if (R == 0 || R > 32) throw InvalidArg("R must be 1..32");
+        for (uint64_t i = 0; i < n * 32; ++i)
+            if (knn[i] != kInvalidNode && knn[i] >= n) throw InvalidArg("candidate out of range");
+        HIP_CHECK(hipSetDevice(device));
+        int cus = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
+        DevBuf<float> d_x(n * D), d_err(n);
+        DevBuf<uint32_t> d_knn(n * 32), d_out(n * 32), d_cnt(n);
+        HIP_CHECK(hipMemcpy(d_x.p, x, n * D * 4, hipMemcpyHostToDevice));
+        if (err) HIP_CHECK(hipMemcpy(d_err.p, err, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_knn.p, knn, n * 32 * 4, hipMemcpyHostToDevice));
+        // the layer-0 call of build_graph: every vertex a row (row_ids null), the CSR built from the table
+        const build::LayerParams lp{R, alpha, tau, alpha_max, err ? d_err.p : nullptr};
+        build::LayerCsr csr;
+        build::select_layer(d_x.p, D, d_knn.p, n, nullptr, lp, cus, d_out.p, d_cnt.p, &csr, grid_cap);
+        HIP_CHECK(hipMemcpy(out_ids, d_out.p, n * 32 * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_cnt, d_cnt.p, n * 4, hipMemcpyDeviceToHost));
+        if (rev_off) HIP_CHECK(hipMemcpy(rev_off, csr.off.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        if (rev) {
+            // at most n * 32 entries: one per valid entry of the table
+            uint64_t total = 0;
+            HIP_CHECK(hipMemcpy(&total, csr.off.p + n, 8, hipMemcpyDeviceToHost));
+            if (total > n * 32) throw std::runtime_error("reverse CSR larger than the table");
+            if (total) HIP_CHECK(hipMemcpy(rev, csr.rev.p, total * 4, hipMemcpyDeviceToHost));
+        }
     });
 }
 

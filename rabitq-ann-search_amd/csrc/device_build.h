@@ -610,7 +610,8 @@ __global__ __launch_bounds__(64) void select_kernel(SelectArgs a) {
             rank_sort();
         } else {
             // a hub: stream all reverse edges through the upper 64 slots, keeping the nearest 64 candidates
-            // seen so far in the lower ones -- the result does not depend on the order of the reverse list
+            // seen so far in the lower ones -- the result, the 64 nearest unique candidates by (distance, id), does not
+            // depend on the order of the reverse list (tests/test_gpu_layer.py: against the oracle, and under permutations)
             while (rb < re) {
                 const uint64_t take = re - rb < 64 ? re - rb : 64;
                 id1 = kInvalidNode;

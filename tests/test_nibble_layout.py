@@ -6,46 +6,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from block_layout import _codes_from_planes, _layout, _plane_dword_offset  # noqa: F401
+
 
 @pytest.fixture(scope="module")
 def L():
     from cphnsw_mi355x import _lib
     return _lib
-
-
-def _layout(D, bits):
-    PW = max(1, D // 32)
-    T = bits * PW
-    wide = D >= 128
-    NH = 2 if (wide and T // 4 >= 2) else 1
-    CPL = (T // 4 // NH) if wide else 0
-    stride = (32 * T * 4 + 512 + 128 + 4 + 63) // 64 * 64
-    return PW, T, wide, NH, CPL, stride
-
-
-def _plane_dword_offset(D, bits, b, w, i):
-    PW, T, wide, NH, CPL, _ = _layout(D, bits)
-    t = b * PW + w
-    if wide:
-        ck, e = t // 4, t % 4
-        h = ck // CPL if NH == 2 else 0
-        k = ck % CPL if NH == 2 else ck
-        return (k * NH * 32 + h * 32 + i) * 16 + e * 4
-    return (t * 32 + i) * 4
-
-
-def _codes_from_planes(dev, D, bits):
-    """c[i, d] = sum_b 2^(bits-1-b) bit_b[d] of neighbour i, read from a plane-major block."""
-    PW = max(1, D // 32)
-    c = np.zeros((32, D), np.int64)
-    for b in range(bits):
-        for w in range(PW):
-            for i in range(32):
-                o = _plane_dword_offset(D, bits, b, w, i)
-                v = int(dev[o:o + 4].view(np.uint32)[0])
-                for t in range(min(32, D)):
-                    c[i, 32 * w + t] += ((v >> t) & 1) << (bits - 1 - b)
-    return c
 
 
 def _relayout(L, D, bits, dev):

@@ -497,6 +497,53 @@ int cph_filter_export(const cph_filter* f, uint32_t* words, uint64_t* count);
 int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo, const int32_t* hi, uint32_t m,
                            uint32_t* words_out, uint64_t* counts_out);
 
+/* ---- filter algebra: AND / OR / ANDNOT / XOR / NOT of filters, on the device ------------------- */
+/* out[j] = a[j] OP b[j] for m filters in one device pass (csrc/device_filter_ops.h): the bitmap holds exactly the bits of
+ * the word-wise operation with the bits at or above n_bits clear, and popcount is counted on the device, as
+ * cph_filter_create counts a host bitmap.  b: n_b = m filters, or n_b = 1 filter that every j is combined with
+ * (broadcast: m tenant bitmaps AND one common mask), or b NULL and n_b = 0 for CPH_FILTER_NOT (~a[j]).  ANDNOT is
+ * a & ~b.  Removed rows are not special: NOT sets their bits, and every search still runs under "filter AND not
+ * removed" like under any other filter.
+ *
+ * No handle: a filter knows its device and n_bits, and its bitmap is complete when the call that made it returns.  The
+ * call runs on a stream of its own on the filters' device, copies the m counts back and waits once.  out[m] receives
+ * ordinary, immutable cph_filter objects (usable with every filtered entry point and as operands of further combines,
+ * destroyed one by one with cph_filter_destroy; their bitmaps share one device allocation, which goes with the last of
+ * them).  The operands are never modified (id lists and cached effective filters hang off them) and must stay alive
+ * for the duration of the call only.  All or nothing: on failure out[] is all NULL.  m == 0 returns CPH_OK and touches
+ * nothing; n_bits == 0 yields empty filters without a launch.
+ * CPH_INVALID_ARGUMENT: a NULL entry, operands of different n_bits or on different devices (parts: with different part
+ * counts), n_b outside {m, 1} (NOT: {0}, with b NULL), an unknown op.
+ * The parts form combines part p of every operand on part p's device. */
+enum { CPH_FILTER_AND = 0, CPH_FILTER_OR = 1, CPH_FILTER_ANDNOT = 2, CPH_FILTER_XOR = 3, CPH_FILTER_NOT = 4 };
+int cph_filters_combine(int op, const cph_filter* const* a, uint32_t m, const cph_filter* const* b, uint32_t n_b, cph_filter** out);
+/* Host statement of the combine pass (plain C++, no HIP call): a_words[m][nw], b_words[m][nw] or, with b_broadcast,
+ * [1][nw] (NULL for NOT), nw = (n_bits + 31) / 32; words_out[m][nw], counts_out[m].  Dirty bits behind n_bits in the
+ * inputs reach neither. */
+int cph_host_filter_combine(int op, const uint32_t* a_words, const uint32_t* b_words, int b_broadcast, uint64_t n_bits, uint32_t m,
+                            uint32_t* words_out, uint64_t* counts_out);
+/* Test hook: the production launcher on host arrays (same layout as cph_host_filter_combine): uploads every operand into
+ * a slab at a 256 B stride, launches between two HIP events into an output slab pre-filled with 0xA5 bytes, downloads.
+ * kernel_us (may be NULL): device time of the memset of the counts and the kernel. */
+int cph_filter_combine_hook(int device, int op, const uint32_t* a_words, const uint32_t* b_words, int b_broadcast, uint64_t n_bits,
+                            uint32_t m, uint32_t* words_out, uint64_t* counts_out, double* kernel_us);
+
+/* ---- attribute columns ------------------------------------------------------------------- */
+/* Up to CPH_MAX_COLUMNS more int32 columns next to the label column, addressed by slot: resident in internal-id order,
+ * 4 B per row each.  cph_set_column / cph_has_column / cph_get_column are cph_set_labels / cph_has_labels /
+ * cph_get_labels for the slot (values NULL drops it), and cph_filters_from_column is cph_filters_from_labels reading the
+ * slot: the same kernel, range semantics, slab and single wait.  Lifecycle as for labels: build, load and load_native
+ * drop every column (no file carries them); remove, set_row_map and set_result_ids leave them; compact carries them
+ * (parts cut them again at the new bounds); replicas copy them.  cph_add on a handle that holds columns is
+ * CPH_INVALID_ARGUMENT (the new rows would have no values: drop the columns, add, set them again at the new size);
+ * cph_set_column on an index that already has a tail works, with n == size.  A slot >= CPH_MAX_COLUMNS is
+ * CPH_INVALID_ARGUMENT. */
+enum { CPH_MAX_COLUMNS = 8 };
+int cph_set_column(cph_index* h, uint32_t slot, const int32_t* values, uint64_t n, int space);
+int cph_has_column(cph_index* h, uint32_t slot, int* flag);
+int cph_get_column(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, int32_t* out);
+int cph_filters_from_column(cph_index* h, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);
@@ -722,6 +769,15 @@ int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int sp
 int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n);
 int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out);
 int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count);
+/* The attribute columns (cph_set_column) and the filter algebra (cph_filters_combine) of replicas and parts, exactly as
+ * the label calls above: one slot on every replica; values[n] over GLOBAL input rows cut at the part bounds; every part
+ * evaluates its own slice; part p of every operand is combined on part p's device.  The per-replica forms of
+ * cph_filters_from_column and cph_filters_combine are the single-handle calls on each replica's handle and filters. */
+int cph_multi_set_column(cph_multi* m, uint32_t slot, const int32_t* values, uint64_t n, int space);
+int cph_parts_set_column(cph_parts* m, uint32_t slot, const int32_t* values, uint64_t n);
+int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out);
+int cph_parts_filters_combine(int op, const cph_parts_filter* const* a, uint32_t m, const cph_parts_filter* const* b, uint32_t n_b,
+                              cph_parts_filter** out);
 int cph_parts_num_parts(cph_parts* m, uint32_t* n);
 int cph_parts_part(cph_parts* m, uint32_t i, cph_index** out);
 int cph_parts_bounds(cph_parts* m, uint64_t* out);

@@ -126,6 +126,18 @@ SYMBOLS = {
     "cph_parts_set_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "cph_parts_filters_from_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cph_parts_filter_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_filters_combine": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_parts_filters_combine": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_host_filter_combine": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cph_filter_combine_hook": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_set_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_has_column": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    "cph_get_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "cph_filters_from_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_multi_set_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_parts_set_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "cph_parts_filters_from_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cph_synchronize": (C.c_int, [C.c_void_p]),
     "cph_set_batch_sets": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,

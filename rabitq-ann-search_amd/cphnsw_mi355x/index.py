@@ -102,6 +102,97 @@ class IdFilter:
         except Exception:
             pass
 
+    # -- filter algebra: a new IdFilter, made and counted on the device; the operands stay as they are.  Replica i is
+    # combined with replica i, part p with part p.  A result is closed by its owner like any filter (the temporaries of
+    # a chain such as (f & g) | h are freed when the expression drops them).
+    def _binary(self, op, other):
+        if not isinstance(other, IdFilter):
+            return NotImplemented
+        return combine_filters(op, [self], other)[0]
+
+    def __and__(self, other):
+        return self._binary("and", other)
+
+    def __or__(self, other):
+        return self._binary("or", other)
+
+    def __sub__(self, other):
+        """f - g: the ids of f that g does not allow (f AND NOT g)."""
+        return self._binary("andnot", other)
+
+    def __xor__(self, other):
+        return self._binary("xor", other)
+
+    def __invert__(self):
+        """~f: every id below `size` that f does not allow (removed rows included: searches drop them anyway)."""
+        return combine_filters("not", [self])[0]
+
+
+FILTER_OPS = {"and": 0, "or": 1, "andnot": 2, "xor": 3, "not": 4}      # CPH_FILTER_*
+
+
+def combine_filters(op, filters, other=None):
+    """[IdFilter]: filters[j] OP other for every j, in one device pass per replica / part (cph_filters_combine).  op:
+    "and", "or", "andnot" (a & ~b), "xor", or "not" (no `other`).  other: one IdFilter, combined with every filters[j], or
+    a sequence of len(filters).  ValueError: a closed operand, operands of different size, device, replica count or part
+    count, a partitioned filter mixed with a plain one, `other` of the wrong length."""
+    if op not in FILTER_OPS:
+        raise ValueError(f"op must be one of {sorted(FILTER_OPS)}")
+    fs = list(filters)
+    if op == "not":
+        if other is not None:
+            raise ValueError('"not" takes no second operand')
+        gs = []
+    elif isinstance(other, IdFilter):
+        gs = [other]
+    elif isinstance(other, (list, tuple)):
+        gs = list(other)
+        if len(gs) != len(fs):
+            raise ValueError(f"the second operand must be one filter or a sequence of {len(fs)} filters (got {len(gs)})")
+    else:
+        raise ValueError(f'"{op}" needs a second operand: an IdFilter or a sequence of them')
+    if not fs:
+        return []
+    for f in fs + gs:
+        if not isinstance(f, IdFilter):
+            raise ValueError("operands must be IdFilter objects")
+        if getattr(f, "_pf", None) is None and not getattr(f, "_hs", []):
+            raise ValueError("filter was closed")
+    first = fs[0]
+    parts = first._pf is not None
+    for f in fs + gs:
+        if (f._pf is not None) != parts:
+            raise ValueError("a partitioned index' filter cannot be combined with a plain one")
+        if f.size != first.size:
+            raise ValueError(f"filters of different sizes cannot be combined ({f.size} and {first.size} ids)")
+        if parts and f._parts != first._parts:
+            raise ValueError("filters with different part counts cannot be combined")
+        if not parts and len(f._hs) != len(first._hs):
+            raise ValueError("filters with different replica counts cannot be combined")
+    L, m, code = _lib.lib(), len(fs), FILTER_OPS[op]
+
+    def table(xs):
+        return (C.c_void_p * len(xs))(*[x.value for x in xs]) if xs else None
+
+    if parts:
+        out = (C.c_void_p * m)()
+        _lib.check(L.cph_parts_filters_combine(code, table([f._pf for f in fs]), m, table([g._pf for g in gs]), len(gs), out))
+        made = [IdFilter._adopt(first.size, 0, pf=C.c_void_p(out[j]), parts=first._parts) for j in range(m)]
+        return CPIndex._with_counts(made, lambda f, c: L.cph_parts_filter_count(f._pf, c))
+    per_rep = []
+    try:
+        for r in range(len(first._hs)):
+            out = (C.c_void_p * m)()
+            _lib.check(L.cph_filters_combine(code, table([f._hs[r] for f in fs]), m, table([g._hs[r] for g in gs]), len(gs), out))
+            per_rep.append(out)
+    except Exception:
+        for out in per_rep:
+            for j in range(m):
+                L.cph_filter_destroy(C.c_void_p(out[j]))
+        raise
+    made = [IdFilter._adopt(first.size, 0, hs=[C.c_void_p(out[j]) for out in per_rep]) for j in range(m)]
+    return CPIndex._with_counts(made, lambda f, c: L.cph_filter_export(f._h, None, c))
+
 
 class GroupKeys:
     """A key column for grouped search on the index' device (CPIndex.make_group_keys): one int32 per row, for callers whose
@@ -162,6 +253,7 @@ class CPIndex:
         self._bits = int(bits)
         self._result_ids = "internal"
         self._exact_threshold = 0
+        self._columns = {}           # attribute columns (set_column): name -> slot on the handle
         if partition and (devices is None or device is not None):
             raise ValueError("partition=True needs devices=[...] (one part per listed device), not device")
         if devices is not None:
@@ -270,6 +362,7 @@ class CPIndex:
         v._devices = [self._devices[i]]
         v._result_ids = "input" if self.is_finalized else "internal"
         v._exact_threshold = self._exact_threshold
+        v._columns = {}
         return v
 
     def _need_parts(self, what):
@@ -484,10 +577,13 @@ class CPIndex:
         return has(self._h)
 
     @staticmethod
-    def _labels_of(h, n, by_row):
+    def _labels_of(h, n, by_row, slot=None):
+        """The label column (slot None) or attribute column `slot` of handle h."""
         out = np.empty(n, np.int32)
-        if n:
+        if n and slot is None:
             _lib.check(_lib.lib().cph_get_labels(h, 0, n, out.ctypes.data))
+        elif n:
+            _lib.check(_lib.lib().cph_get_column(h, slot, 0, n, out.ctypes.data))
         if not by_row:
             return out
         rows = np.empty(n, np.uint32)
@@ -499,33 +595,43 @@ class CPIndex:
 
     def labels(self, ids=None):
         """int32[size] copy of the label column, indexed in the space `ids` (default: result_ids)."""
+        return self._column_values(None, ids)
+
+    def _column_values(self, slot, ids):
         by_row = self._id_space(ids) == "input"          # (a partitioned index: always; _id_space refuses "internal")
         if self._p is not None:
-            return np.concatenate([self._labels_of(h, hi - lo, by_row) for h, (lo, hi) in zip(self._part_handles, self.parts)])
-        return self._labels_of(self._h, self.size, by_row)
+            return np.concatenate([self._labels_of(h, hi - lo, by_row, slot) for h, (lo, hi) in zip(self._part_handles, self.parts)])
+        return self._labels_of(self._h, self.size, by_row, slot)
 
     def label_filters(self, lo, hi=None):
         """[IdFilter]: filter j allows the rows whose label x satisfies lo[j] <= x <= hi[j] (hi=None: x == lo[j];
         lo[j] > hi[j]: nothing).  All of them are made in ONE pass over the label column on the device, which also
         counts them (`count`); nothing is packed on the host.  They are ordinary filters: usable wherever filter=
         is, with removed rows, replicas and parts.  Their bitmaps share one device allocation, freed with the last."""
-        lo = self._as_labels(lo, "label bounds").ravel()
-        hi = lo if hi is None else self._as_labels(hi, "label bounds").ravel()
+        return self._range_filters(None, lo, hi, "label bounds")
+
+    def _range_filters(self, slot, lo, hi, what):
+        """label_filters on the label column (slot None) or on attribute column `slot`."""
+        lo = self._as_labels(lo, what).ravel()
+        hi = lo if hi is None else self._as_labels(hi, what).ravel()
         if hi.shape != lo.shape:
             raise ValueError("lo and hi must have the same length")
         m, L, n = lo.size, _lib.lib(), self.size
         if m == 0:
             return []
+        col = () if slot is None else (slot,)
         if self._p is not None:
             out = (C.c_void_p * m)()
-            _lib.check(L.cph_parts_filters_from_labels(self._p, lo.ctypes.data, hi.ctypes.data, m, out))
+            make = L.cph_parts_filters_from_labels if slot is None else L.cph_parts_filters_from_column
+            _lib.check(make(self._p, *col, lo.ctypes.data, hi.ctypes.data, m, out))
             fs = [IdFilter._adopt(n, 0, pf=C.c_void_p(out[j]), parts=len(self._devices)) for j in range(m)]
             return self._with_counts(fs, lambda f, c: L.cph_parts_filter_count(f._pf, c))
         per_rep = []
+        make = L.cph_filters_from_labels if slot is None else L.cph_filters_from_column
         try:
             for rh in self._replicas():
                 out = (C.c_void_p * m)()
-                _lib.check(L.cph_filters_from_labels(rh, lo.ctypes.data, hi.ctypes.data, m, out))
+                _lib.check(make(rh, *col, lo.ctypes.data, hi.ctypes.data, m, out))
                 per_rep.append(out)
         except Exception:
             for out in per_rep:
@@ -568,6 +674,120 @@ class CPIndex:
     def label_filter(self, lo, hi=None):
         """IdFilter of the rows whose label is `lo`, or lies in [lo, hi] (both ends inclusive)."""
         return self.label_filters([lo], None if hi is None else [hi])[0]
+
+    # -- attribute columns and filter algebra (not in the reference) ----------------------------
+    MAX_COLUMNS = 8                  # CPH_MAX_COLUMNS
+
+    def _column_slots(self):
+        """name -> slot of the columns the handle still holds: build(), load() and load_native() drop every column with
+        the label column, and their names go with them here."""
+        def has(h, slot):
+            f = C.c_int(0)
+            _lib.check(_lib.lib().cph_has_column(h, slot, C.byref(f)))
+            return bool(f.value)
+        hs = self._part_handles if self._p is not None else [self._h]
+        for name, slot in list(self._columns.items()):
+            if not all(has(h, slot) for h in hs):
+                del self._columns[name]
+        return self._columns
+
+    def _slot(self, name):
+        if name == "label":
+            if not self.has_labels:
+                raise ValueError('the index has no label column: call set_labels first')
+            return None
+        slots = self._column_slots()
+        if name not in slots:
+            raise ValueError(f"the index has no column {name!r}: call set_column first")
+        return slots[name]
+
+    def _set_slot(self, slot, a, code):
+        L, n = _lib.lib(), 0 if a is None else a.size
+        p = None if a is None else a.ctypes.data
+        if self._p is not None:
+            _lib.check(L.cph_parts_set_column(self._p, slot, p, n))
+        elif self._m is not None:
+            _lib.check(L.cph_multi_set_column(self._m, slot, p, n, code))
+        else:
+            _lib.check(L.cph_set_column(self._h, slot, p, n, code))
+
+    def set_column(self, name, values, ids=None):
+        """A named int32 attribute column next to the label column (a year, a price band, a stock flag): an integer array
+        [size] whose values fit int32, indexed in the space `ids` (default: result_ids), kept on the device (4 B per
+        row).  None drops the column and frees its name.  At most MAX_COLUMNS names; "label" is the label column's
+        (set_labels).  column_filter(s) and where() read it.  Lifecycle as for labels: build(), load() and
+        load_native() drop every column, remove() and set_row_map() leave them, compact() carries them; add() on an
+        index that holds columns raises (drop them, add, set them again at the new size)."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a column name must be a non-empty string")
+        if name == "label":
+            raise ValueError('"label" names the label column: use set_labels')
+        slots = self._column_slots()
+        if values is None:
+            if name in slots:
+                self._set_slot(slots[name], None, _lib.IDS_INTERNAL)
+                del slots[name]
+            return
+        space = self._id_space(ids)
+        a = self._as_labels(values, "column values")
+        if a.ndim != 1 or a.shape[0] != self.size:
+            raise ValueError(f"column values must be a 1D integer array of length {self.size} (the index size)")
+        slot = slots.get(name)
+        if slot is None:
+            free = [s for s in range(self.MAX_COLUMNS) if s not in slots.values()]
+            if not free:
+                raise ValueError(f"an index holds at most {self.MAX_COLUMNS} columns: drop one first (set_column(name, None))")
+            slot = free[0]
+        self._set_slot(slot, a, _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL)
+        slots[name] = slot
+
+    @property
+    def columns(self):
+        """Names of the attribute columns the index holds (set_column)."""
+        return list(self._column_slots())
+
+    def column(self, name, ids=None):
+        """int32[size] copy of column `name` ("label": the label column), indexed in the space `ids` (default: result_ids)."""
+        return self._column_values(self._slot(name), ids)
+
+    def column_filters(self, name, lo, hi=None):
+        """label_filters on column `name`: filter j allows the rows whose value x satisfies lo[j] <= x <= hi[j]
+        (hi=None: x == lo[j]); one device pass, the same kernel."""
+        return self._range_filters(self._slot(name), lo, hi, "column bounds")
+
+    def column_filter(self, name, lo, hi=None):
+        """IdFilter of the rows whose value in column `name` is `lo`, or lies in [lo, hi] (both ends inclusive)."""
+        return self.column_filters(name, [lo], None if hi is None else [hi])[0]
+
+    def combine_filters(self, op, filters, other=None):
+        """[IdFilter]: filters[j] OP other, made and counted on the device in one pass (module function
+        combine_filters): op "and" / "or" / "andnot" / "xor" with `other` one filter (combined with every filters[j]) or
+        a sequence of len(filters); "not" without `other`.  The per-tenant case: combine_filters("and",
+        label_filters(vals), in_stock) and search_batch(..., filter=that list, filter_of=...)."""
+        return combine_filters(op, filters, other)
+
+    def where(self, **tests):
+        """IdFilter of the rows that pass every test: name=value (equality) or name=(lo, hi) (inclusive range) on the
+        column `name`; "label" names the label column.  Each test is one column pass, the AND runs on the device; the
+        intermediate filters are closed here."""
+        if not tests:
+            raise ValueError("where() needs at least one column test")
+        made = []
+        try:
+            for name, t in tests.items():
+                lo, hi = t if isinstance(t, (tuple, list)) and len(t) == 2 else (t, None)
+                if isinstance(t, (tuple, list)) and len(t) != 2:
+                    raise ValueError(f"a test is a value or a (lo, hi) pair, got {t!r} for {name!r}")
+                made.append(self.column_filter(name, lo, hi))
+            acc = made[0]
+            for f in made[1:]:
+                acc = acc & f
+                made.append(acc)
+            made.remove(acc)
+            return acc
+        finally:
+            for f in made:
+                f.close()
 
     def _from_label(self, label, filter, filter_of, n):
         """The `label=` argument of a search -> (filter, filter_of, [filters made here, closed by that call]).  A scalar:

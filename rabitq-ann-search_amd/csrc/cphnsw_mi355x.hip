@@ -33,6 +33,7 @@
 #include "device_rows.h"
 #include "device_tombstone.h"
 #include "device_labels.h"
+#include "device_filter_ops.h"
 #include "device_exact.h"
 #include "device_range.h"
 #include "device_tail.h"
@@ -253,6 +254,11 @@ struct cph_index {
     DevBuf<int32_t> d_labels, d_label_bounds;
     DevBuf<unsigned long long> d_label_counts;
     bool has_labels = false;
+    // the attribute columns (cph_set_column): up to kMaxColumns more int32 columns, each held like the label column
+    // (host copies: host.columns); every walk over "the label column" -- sync_labels, replicate, the compact gather,
+    // the parts cut -- walks these slots too (column_of)
+    DevBuf<int32_t> d_columns[kMaxColumns];
+    bool has_column[kMaxColumns] = {};
     // debug hook cph_debug_time_label_filters: only while label_timing is on is a label pass bracketed by the two events
     hipEvent_t ev_label0 = nullptr, ev_label1 = nullptr;
     bool label_timing = false, label_timed = false;
@@ -383,15 +389,33 @@ void sync_row_map(cph_index* h) {
     }
 }
 
-// After the host index changed: the device copy of its label column, or none (a load or a build leaves none).
+// One int32 column of a handle: the label column (slot kLabelSlot) or attribute column `slot` < kMaxColumns.
+constexpr int kLabelSlot = -1;
+struct ColumnRef {
+    DevBuf<int32_t>& dev;
+    bool& has;
+    std::vector<int32_t>& host;
+};
+ColumnRef column_of(cph_index* h, int slot) {
+    if (slot == kLabelSlot) return ColumnRef{h->d_labels, h->has_labels, h->host.labels};
+    return ColumnRef{h->d_columns[slot], h->has_column[slot], h->host.columns[slot]};
+}
+bool has_extra_columns(const cph_index* h) {
+    return std::any_of(h->has_column, h->has_column + kMaxColumns, [](bool b) { return b; });
+}
+
+// After the host index changed: the device copy of its label column and of every attribute column, or none (a load or
+// a build leaves none).
 void sync_labels(cph_index* h) {
-    const std::vector<int32_t>& labels = h->host.labels;
-    h->has_labels = !labels.empty();
-    if (h->has_labels) {
-        h->d_labels.alloc(labels.size());
-        HIP_CHECK(hipMemcpy(h->d_labels.p, labels.data(), labels.size() * 4, hipMemcpyHostToDevice));
-    } else {
-        h->d_labels.release();
+    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
+        const ColumnRef c = column_of(h, slot);
+        c.has = !c.host.empty();
+        if (c.has) {
+            c.dev.alloc(c.host.size());
+            HIP_CHECK(hipMemcpy(c.dev.p, c.host.data(), c.host.size() * 4, hipMemcpyHostToDevice));
+        } else {
+            c.dev.release();
+        }
     }
 }
 
@@ -1609,7 +1633,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 107; }
+int cph_version(void) { return 108; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -2857,50 +2881,66 @@ namespace {
 
 // The caller holds the handle mutex.  labels: n == size entries in internal-id order, or null: the column goes.
 // keep_host: also as host.labels (what compact gathers from); a replica without host arrays keeps the device copy only.
-void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool keep_host) {
+// slot: kLabelSlot, or an attribute column (cph_set_column): the same lifecycle, one code path.
+void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool keep_host, int slot = kLabelSlot) {
     h->use_device();
     quiesce(h);                                  // a grouped batch in flight may be reading the old column
+    const ColumnRef c = column_of(h, slot);
     if (!labels) {
-        std::vector<int32_t>().swap(h->host.labels);
-        sync_labels(h);
+        std::vector<int32_t>().swap(c.host);
+        c.has = false;
+        c.dev.release();
         return;
     }
-    h->d_labels.alloc(n);
-    HIP_CHECK(hipMemcpy(h->d_labels.p, labels, n * 4, hipMemcpyHostToDevice));
-    if (keep_host) h->host.labels.assign(labels, labels + n);
-    h->has_labels = true;
+    c.dev.alloc(n);
+    HIP_CHECK(hipMemcpy(c.dev.p, labels, n * 4, hipMemcpyHostToDevice));
+    if (keep_host) c.host.assign(labels, labels + n);
+    c.has = true;
 }
 
-void require_labels_target(const cph_index* h, const int32_t* labels, uint64_t n) {
-    if (!h->finalized) throw InvalidArg("labels belong to a finalized index: finalize or load it first");
+void require_slot(uint32_t slot) {
+    if (slot >= kMaxColumns) throw InvalidArg("column slot must be below " + std::to_string(kMaxColumns) + " (CPH_MAX_COLUMNS)");
+}
+
+void require_labels_target(const cph_index* h, const int32_t* labels, uint64_t n, int slot = kLabelSlot) {
+    const bool lab = slot == kLabelSlot;
+    if (!h->finalized)
+        throw InvalidArg(lab ? "labels belong to a finalized index: finalize or load it first"
+                             : "columns belong to a finalized index: finalize or load it first");
     if (labels && n != h->size())
-        throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(h->size()));
+        throw InvalidArg(std::string(lab ? "label column has " : "column has ") + std::to_string(n) + " entries, the index holds " +
+                         std::to_string(h->size()));
 }
 
-// cph_set_labels on a handle that keeps its host arrays: labels in internal ids, or in input rows (moved to internal
-// order on the host, through host.rows: labels_to_internal_host).
-void set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space) {
+// cph_set_labels / cph_set_column on a handle that keeps its host arrays: values in internal ids, or in input rows
+// (moved to internal order on the host, through host.rows: labels_to_internal_host).
+void set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space, int slot = kLabelSlot) {
     if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
     std::lock_guard<std::mutex> lk(h->mu);
-    require_labels_target(h, labels, n);
+    require_labels_target(h, labels, n, slot);
     if (!labels || space == CPH_IDS_INTERNAL) {
-        install_labels_locked(h, labels, n, true);
+        install_labels_locked(h, labels, n, true, slot);
         return;
     }
     const uint64_t nb = h->host.n;
     if (!h->has_rows || h->host.rows.size() != nb)
-        throw InvalidArg("the index has no row map (it was loaded from a v2 file): labels in input rows need cph_set_row_map");
+        throw InvalidArg(slot == kLabelSlot
+                             ? "the index has no row map (it was loaded from a v2 file): labels in input rows need cph_set_row_map"
+                             : "the index has no row map (it was loaded from a v2 file): a column in input rows needs cph_set_row_map");
     std::vector<int32_t> internal(n);
     labels_to_internal_host(labels, h->host.rows.data(), nb, internal.data());
     std::copy(labels + nb, labels + n, internal.begin() + nb);      // (a tail row is its own input row)
-    install_labels_locked(h, internal.data(), n, true);
+    install_labels_locked(h, internal.data(), n, true, slot);
 }
 
-// cph_filters_from_labels: out[m] all made, or none.
-void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
+// cph_filters_from_labels / cph_filters_from_column: out[m] all made, or none.
+void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out, int slot = kLabelSlot) {
     std::lock_guard<std::mutex> lk(h->mu);
     require_finalized(h);
-    if (!h->has_labels) throw InvalidArg("the index has no label column: call cph_set_labels first");
+    const ColumnRef col = column_of(h, slot);
+    if (!col.has)
+        throw InvalidArg(slot == kLabelSlot ? "the index has no label column: call cph_set_labels first"
+                                            : "the index has no column in slot " + std::to_string(slot) + ": call cph_set_column first");
     if (m > kLabelMaxFilters) throw InvalidArg("at most " + std::to_string(kLabelMaxFilters) + " label filters per call");
     const uint64_t n = h->size(), nw = (n + 31) / 32;
     const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
@@ -2915,7 +2955,7 @@ void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uin
     HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p + m, hi, (size_t)m * 4, hipMemcpyHostToDevice, st));
     h->label_timed = false;
     if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label0, st));
-    label_filters(h->d_labels.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
+    label_filters(col.dev.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
     if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label1, st));
     std::vector<unsigned long long> counts(m);
     HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_label_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
@@ -2953,16 +2993,56 @@ int cph_has_labels(cph_index* h, int* flag) {
     });
 }
 
+// cph_get_labels / cph_get_column.
+static void get_column(cph_index* h, int slot, uint64_t first, uint64_t count, int32_t* out) {
+    if (!h || (!out && count != 0)) throw InvalidArg("null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    const ColumnRef c = column_of(h, slot);
+    if (!c.has) throw InvalidArg(slot == kLabelSlot ? "the index has no label column" : "the index has no column in slot " + std::to_string(slot));
+    if (first > h->size() || count > h->size() - first) throw InvalidArg(slot == kLabelSlot ? "label range out of bounds" : "column range out of bounds");
+    if (count == 0) return;
+    h->use_device();
+    HIP_CHECK(hipMemcpy(out, c.dev.p + first, count * 4, hipMemcpyDeviceToHost));
+}
+
 int cph_get_labels(cph_index* h, uint64_t first, uint64_t count, int32_t* out) {
+    return guarded([&] { get_column(h, kLabelSlot, first, count, out); });
+}
+
+int cph_set_column(cph_index* h, uint32_t slot, const int32_t* values, uint64_t n, int space) {
     return guarded([&] {
-        if (!h || (!out && count != 0)) throw InvalidArg("null argument");
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_column");
+        require_slot(slot);
+        set_labels(h, values, n, space, (int)slot);
+    });
+}
+
+int cph_has_column(cph_index* h, uint32_t slot, int* flag) {
+    return guarded([&] {
+        if (!h || !flag) throw InvalidArg("null argument");
+        require_slot(slot);
         std::lock_guard<std::mutex> lk(h->mu);
-        require_finalized(h);
-        if (!h->has_labels) throw InvalidArg("the index has no label column");
-        if (first > h->size() || count > h->size() - first) throw InvalidArg("label range out of bounds");
-        if (count == 0) return;
-        h->use_device();
-        HIP_CHECK(hipMemcpy(out, h->d_labels.p + first, count * 4, hipMemcpyDeviceToHost));
+        *flag = h->finalized && h->has_column[slot] ? 1 : 0;
+    });
+}
+
+int cph_get_column(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, int32_t* out) {
+    return guarded([&] {
+        require_slot(slot);
+        get_column(h, (int)slot, first, count, out);
+    });
+}
+
+int cph_filters_from_column(cph_index* h, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + m, nullptr);
+        if (!h || !lo || !hi) throw InvalidArg("null argument");
+        require_slot(slot);
+        filters_from_labels(h, lo, hi, m, out, (int)slot);
     });
 }
 
@@ -3018,6 +3098,164 @@ int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo,
         if ((n != 0 && (!labels || !words_out)) || !lo || !hi || !counts_out) throw InvalidArg("null argument");
         if (n > 0xFFFFFFFFull) throw InvalidArg("filter too large");
         label_filters_host(labels, n, lo, hi, m, words_out, counts_out);
+    });
+}
+
+// ---- filter algebra (cph_filters_combine; device_filter_ops.h) ----
+// What a combine call needs on its device and keeps for the next one: a stream of its own (no handle is involved), the
+// operand tables and the counts, which only grow.  One call per device at a time (mu).  Never freed: the HIP runtime
+// may be gone before a static destructor runs.
+struct CombineCtx {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    DevBuf<const uint32_t*> tab;
+    DevBuf<unsigned long long> counts;
+};
+static CombineCtx* combine_ctx(int device) {
+    static std::mutex mu;
+    static std::vector<std::pair<int, CombineCtx*>> all;
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& e : all)
+        if (e.first == device) return e.second;
+    all.emplace_back(device, new CombineCtx());
+    return all.back().second;
+}
+
+static void check_combine_shape(int op, uint32_t m, const void* b, uint32_t n_b) {
+    if (op < 0 || op >= kFilterOps) throw InvalidArg("unknown filter op " + std::to_string(op));
+    if (op == kFilterNot) {
+        if (n_b != 0 || b) throw InvalidArg("NOT takes one operand list: b must be NULL and n_b 0");
+    } else if (!b || (n_b != m && n_b != 1)) {
+        throw InvalidArg("the second operand list holds one filter per first operand or exactly one (got " + std::to_string(n_b) +
+                         " for " + std::to_string(m) + ")");
+    }
+}
+
+// cph_filters_combine on one device: out[m] all made, or none.  The operands are complete bitmaps (every call that makes
+// a filter waits for it), so nothing is waited for before the launch.
+static void filters_combine(int op, const cph_filter* const* a, uint32_t m, const cph_filter* const* b, uint32_t n_b,
+                            cph_filter** out) {
+    check_combine_shape(op, m, b, n_b);
+    for (uint32_t j = 0; j < m; ++j)
+        if (!a[j]) throw InvalidArg("null filter");
+    for (uint32_t j = 0; j < n_b; ++j)
+        if (!b[j]) throw InvalidArg("null filter");
+    const int device = a[0]->device;
+    const uint64_t n = a[0]->n_bits, nw = (n + 31) / 32;
+    auto same = [&](const cph_filter* f) {
+        if (f->n_bits != n)
+            throw InvalidArg("filters of different sizes cannot be combined (" + std::to_string(f->n_bits) + " and " + std::to_string(n) + " ids)");
+        if (f->device != device) throw InvalidArg("filters on different devices cannot be combined");
+    };
+    for (uint32_t j = 0; j < m; ++j) same(a[j]);
+    for (uint32_t j = 0; j < n_b; ++j) same(b[j]);
+    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
+    HIP_CHECK(hipSetDevice(device));
+    std::vector<std::unique_ptr<cph_filter>> made(m);
+    for (auto& f : made) f.reset(new cph_filter());
+    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
+    std::vector<unsigned long long> counts(m, 0);
+    if (n != 0) {
+        CombineCtx* cx = combine_ctx(device);
+        std::lock_guard<std::mutex> lk(cx->mu);
+        if (!cx->stream) HIP_CHECK(hipStreamCreateWithFlags(&cx->stream, hipStreamNonBlocking));
+        std::vector<const uint32_t*> pa(m), pb(n_b);
+        for (uint32_t j = 0; j < m; ++j) pa[j] = a[j]->words.p;
+        for (uint32_t j = 0; j < n_b; ++j) pb[j] = b[j]->words.p;
+        combine_tables(pa.data(), m, pb.data(), n_b, cx->tab, cx->stream);
+        cx->counts.alloc(m);
+        filter_combine(op, cx->tab.p, n_b ? cx->tab.p + m : nullptr, n_b == 1, n, m, slab->p, stride, cx->counts.p, cx->stream);
+        HIP_CHECK(hipMemcpyAsync(counts.data(), cx->counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, cx->stream));
+        HIP_CHECK(hipStreamSynchronize(cx->stream));     // the one wait of the call: the routing needs every count on the host
+    }
+    for (uint32_t j = 0; j < m; ++j) {
+        cph_filter* f = made[j].get();
+        f->device = device;
+        f->n_bits = n;
+        f->popcount = counts[j];
+        f->slab = slab;
+        f->words.p = slab->p + (size_t)j * stride;
+        f->words.n = std::max<uint64_t>(nw, 1);
+    }
+    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
+}
+
+int cph_filters_combine(int op, const cph_filter* const* a, uint32_t m, const cph_filter* const* b, uint32_t n_b, cph_filter** out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + m, nullptr);
+        if (!a) throw InvalidArg("null argument");
+        filters_combine(op, a, m, b, n_b, out);
+    });
+}
+
+static void check_combine_host_args(int op, const uint32_t* a_words, const uint32_t* b_words, uint64_t n_bits, const uint32_t* words_out,
+                                    const uint64_t* counts_out) {
+    if (op < 0 || op >= kFilterOps) throw InvalidArg("unknown filter op " + std::to_string(op));
+    if (n_bits > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+    if (!counts_out || (n_bits != 0 && (!a_words || !words_out))) throw InvalidArg("null argument");
+    if (op == kFilterNot ? b_words != nullptr : (n_bits != 0 && !b_words))
+        throw InvalidArg(op == kFilterNot ? "NOT takes one operand: b_words must be NULL" : "null argument");
+}
+
+int cph_host_filter_combine(int op, const uint32_t* a_words, const uint32_t* b_words, int b_broadcast, uint64_t n_bits, uint32_t m,
+                            uint32_t* words_out, uint64_t* counts_out) {
+    return guarded([&] {
+        if (m == 0) return;
+        check_combine_host_args(op, a_words, b_words, n_bits, words_out, counts_out);
+        filter_combine_host(op, a_words, b_words, b_broadcast != 0, n_bits, m, words_out, counts_out);
+    });
+}
+
+int cph_filter_combine_hook(int device, int op, const uint32_t* a_words, const uint32_t* b_words, int b_broadcast, uint64_t n_bits,
+                            uint32_t m, uint32_t* words_out, uint64_t* counts_out, double* kernel_us) {
+    return guarded([&] {
+        if (m == 0) return;
+        check_combine_host_args(op, a_words, b_words, n_bits, words_out, counts_out);
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t nw = (n_bits + 31) / 32, stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;
+        const uint32_t n_b = op == kFilterNot ? 0u : b_broadcast ? 1u : m;
+        // every operand in a slab of its own stride, like a label-filter view; the outputs start as 0xA5 bytes, so
+        // every word the kernel leaves alone shows
+        DevBuf<uint32_t> d_a((size_t)m * stride), d_b((size_t)std::max(n_b, 1u) * stride), d_out((size_t)m * stride);
+        DevBuf<unsigned long long> d_counts(m);
+        DevBuf<const uint32_t*> tab;
+        HIP_CHECK(hipMemset(d_out.p, 0xA5, (size_t)m * stride * 4));
+        HIP_CHECK(hipMemset(d_counts.p, 0xA5, (size_t)m * 8));
+        std::vector<const uint32_t*> pa(m), pb(n_b);
+        for (uint32_t j = 0; j < m; ++j) {
+            pa[j] = d_a.p + (size_t)j * stride;
+            if (nw) HIP_CHECK(hipMemcpy(d_a.p + (size_t)j * stride, a_words + (size_t)j * nw, nw * 4, hipMemcpyHostToDevice));
+        }
+        for (uint32_t j = 0; j < n_b; ++j) {
+            pb[j] = d_b.p + (size_t)j * stride;
+            if (nw) HIP_CHECK(hipMemcpy(d_b.p + (size_t)j * stride, b_words + (size_t)j * nw, nw * 4, hipMemcpyHostToDevice));
+        }
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_CHECK(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw std::runtime_error("hipEventCreate failed"); }
+        try {
+            combine_tables(pa.data(), m, pb.data(), n_b, tab, nullptr);
+            HIP_CHECK(hipEventRecord(e0, nullptr));
+            filter_combine(op, tab.p, n_b ? tab.p + m : nullptr, n_b == 1, n_bits, m, d_out.p, stride, d_counts.p, nullptr);
+            HIP_CHECK(hipEventRecord(e1, nullptr));
+            HIP_CHECK(hipDeviceSynchronize());
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            if (kernel_us) *kernel_us = (double)ms * 1e3;
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            throw;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        for (uint32_t j = 0; j < m && nw; ++j)
+            HIP_CHECK(hipMemcpy(words_out + (size_t)j * nw, d_out.p + (size_t)j * stride, nw * 4, hipMemcpyDeviceToHost));
+        std::vector<unsigned long long> counts(m);
+        HIP_CHECK(hipMemcpy(counts.data(), d_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost));
+        std::copy(counts.begin(), counts.end(), counts_out);
     });
 }
 
@@ -3613,9 +3851,12 @@ void replicate(cph_index* src, cph_index* dst) {
     else dst->d_rows.release();
     dst->has_rows = src->has_rows;
     dst->ids_input = dst->ids_input && dst->has_rows;
-    if (src->has_labels) copy(dst->d_labels, src->d_labels);     // (compact carries the column; a load or finalize has none)
-    else dst->d_labels.release();
-    dst->has_labels = src->has_labels;
+    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {      // (compact carries the columns; a load or finalize has none)
+        const ColumnRef from = column_of(src, slot), to = column_of(dst, slot);
+        if (from.has) copy(to.dev, from.dev);
+        else to.dev.release();
+        to.has = from.has;
+    }
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
     copy(dst->d_row_of, src->d_row_of);
@@ -4655,10 +4896,12 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
 
 // The live vectors of a finalized handle in input-row order (internal-id order without a row map), appended to `vecs`
 // (dim floats each); map[i] (the caller's, `n` entries from map_first on) = first_new + rank of the live row, -1 for a
-// removed one, indexed by input row (by_row) or by internal id.  labs (may be null): the live rows' labels, appended in
-// the same order, when the handle has a label column.  Returns the number of live rows.
+// removed one, indexed by input row (by_row) or by internal id.  labs (may be null): the live rows' labels and column
+// values, appended in the same order -- (*labs)[1 + slot] for every column the handle has, the label column at
+// kLabelSlot.  Returns the number of live rows.
+using LiveColumns = std::vector<int32_t>[1 + kMaxColumns];
 uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new,
-                     std::vector<int32_t>* labs = nullptr) {
+                     LiveColumns* labs = nullptr) {
     const HostIndex& hi = h->host;
     const uint64_t n = hi.n, size = h->size();
     const bool rows = h->has_rows && hi.rows.size() == n;
@@ -4672,7 +4915,11 @@ uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool 
         map[by_row ? r : id] = gone ? -1 : first_new + (int64_t)live;
         if (gone) continue;
         vecs.insert(vecs.end(), row_vec(h, id), row_vec(h, id) + hi.dim);
-        if (labs && hi.labels.size() == size) labs->push_back(hi.labels[id]);
+        if (labs)
+            for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
+                const std::vector<int32_t>& col = column_of(h, slot).host;
+                if (col.size() == size) (*labs)[1 + slot].push_back(col[id]);
+            }
         ++live;
     }
     return live;
@@ -4683,7 +4930,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     if (!old_to_new) throw InvalidArg("null argument");
     refuse_host_less(h, "cph_compact");
     std::vector<float> vecs;
-    std::vector<int32_t> labs;                   // the live rows' labels, in the order of the new input rows
+    LiveColumns labs;                            // the live rows' labels and column values, in the order of the new input rows
     uint64_t live = 0;
     bool was_input = false;
     {
@@ -4703,7 +4950,8 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     std::vector<float>().swap(vecs);
     finalize_build(h);
     if (was_input) set_result_ids(h, CPH_IDS_INPUT);
-    if (labs.size() == live) set_labels(h, labs.data(), live, CPH_IDS_INPUT);     // new input row j: the label of the live row it came from
+    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot)      // new input row j: the values of the live row it came from
+        if (labs[1 + slot].size() == live) set_labels(h, labs[1 + slot].data(), live, CPH_IDS_INPUT, slot);
 }
 
 }  // namespace
@@ -4773,6 +5021,9 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     if ((labels != nullptr) != h->has_labels)
         throw InvalidArg(h->has_labels ? "the index has a label column: the added rows need labels"
                                        : "the index has no label column: labels for the added rows have nowhere to go");
+    if (has_extra_columns(h))
+        throw InvalidArg("the index holds attribute columns and the added rows would have no values in them: drop the columns "
+                         "(cph_set_column with NULL), add, then set them again at the new size");
     if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
     h->use_device();
     quiesce(h);                                  // a batch in flight reads the arrays that may move
@@ -5003,7 +5254,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
     return guarded([&] {
         if (!m || !old_to_new) throw InvalidArg("null argument");
         std::vector<float> vecs;
-        std::vector<int32_t> labs;                // the live rows' labels in global row order (every part has a column, or none)
+        LiveColumns labs;                         // the live rows' labels and column values in global row order (every part has a column, or none)
         uint64_t live = 0;
         {
             std::unique_lock<std::shared_mutex> lk(m->life);
@@ -5023,79 +5274,155 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
         check_rc(cph_parts_build(m, vecs.data(), live));      // the live rows, cut again by cph_host_part_bounds
         std::vector<float>().swap(vecs);
         check_rc(cph_parts_finalize(m));
-        if (labs.size() == live) check_rc(cph_parts_set_labels(m, labs.data(), live));     // cut again at the new bounds
+        if (labs[0].size() == live) check_rc(cph_parts_set_labels(m, labs[0].data(), live));     // cut again at the new bounds
+        for (uint32_t slot = 0; slot < kMaxColumns; ++slot)
+            if (labs[1 + slot].size() == live) check_rc(cph_parts_set_column(m, slot, labs[1 + slot].data(), live));
     });
 }
 
 // ---- label column of replicas and parts ----
-int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int space) {
-    return guarded([&] {
-        if (!m) throw InvalidArg("null handle");
-        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
-        cph_index* r0 = m->reps[0];
-        for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
+// cph_multi_set_labels / cph_multi_set_column.
+static void multi_set_column(cph_multi* m, const int32_t* labels, uint64_t n, int space, int slot) {
+    if (!m) throw InvalidArg("null handle");
+    std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
+    cph_index* r0 = m->reps[0];
+    for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
+        std::lock_guard<std::mutex> g(h->mu);
+        require_labels_target(h, labels, n, slot);
+    }
+    set_labels(r0, labels, n, space, slot);              // validates the rest, and moves input rows to internal order once
+    try {
+        for (size_t i = 1; i < m->reps.size(); ++i) {
+            cph_index* h = m->reps[i];
             std::lock_guard<std::mutex> g(h->mu);
-            require_labels_target(h, labels, n);
+            install_labels_locked(h, labels ? column_of(r0, slot).host.data() : nullptr, n, false, slot);
         }
-        set_labels(r0, labels, n, space);                    // validates the rest, and moves input rows to internal order once
-        try {
-            for (size_t i = 1; i < m->reps.size(); ++i) {
-                cph_index* h = m->reps[i];
-                std::lock_guard<std::mutex> g(h->mu);
-                install_labels_locked(h, labels ? r0->host.labels.data() : nullptr, n, false);
-            }
-        } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
-            for (cph_index* h : m->reps) {
-                std::lock_guard<std::mutex> g(h->mu);
-                try { install_labels_locked(h, nullptr, 0, false); } catch (...) {}
-            }
-            throw;
+    } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
+        for (cph_index* h : m->reps) {
+            std::lock_guard<std::mutex> g(h->mu);
+            try { install_labels_locked(h, nullptr, 0, false, slot); } catch (...) {}
         }
+        throw;
+    }
+}
+
+int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int space) {
+    return guarded([&] { multi_set_column(m, labels, n, space, kLabelSlot); });
+}
+
+int cph_multi_set_column(cph_multi* m, uint32_t slot, const int32_t* values, uint64_t n, int space) {
+    return guarded([&] {
+        require_slot(slot);
+        multi_set_column(m, values, n, space, (int)slot);
     });
+}
+
+// cph_parts_set_labels / cph_parts_set_column.
+static void parts_set_column(cph_parts* m, const int32_t* labels, uint64_t n, int slot) {
+    const bool lab = slot == kLabelSlot;
+    if (!m) throw InvalidArg("null handle");
+    std::unique_lock<std::shared_mutex> lk(m->life);
+    if (!parts_finalized(m))
+        throw InvalidArg(lab ? "labels belong to a finalized index: finalize or load it first"
+                             : "columns belong to a finalized index: finalize or load it first");
+    if (labels && n != m->bounds.back())
+        throw InvalidArg(std::string(lab ? "label column has " : "column has ") + std::to_string(n) + " entries, the index holds " +
+                         std::to_string(m->bounds.back()));
+    for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
+        std::lock_guard<std::mutex> g(h->mu);
+        if (labels && (!h->has_rows || h->host.rows.size() != h->host.n))
+            throw InvalidArg(lab ? "a part has no row map: labels of a partitioned index are given in input rows"
+                                 : "a part has no row map: columns of a partitioned index are given in input rows");
+    }
+    try {
+        for (size_t p = 0; p < m->parts.size(); ++p)     // global input rows, cut at the part bounds
+            set_labels(m->parts[p], labels ? labels + m->bounds[p] : nullptr, m->bounds[p + 1] - m->bounds[p], CPH_IDS_INPUT, slot);
+    } catch (...) {                                      // (a device failure: no part keeps a column the others lack)
+        for (cph_index* h : m->parts) {
+            std::lock_guard<std::mutex> g(h->mu);
+            try { install_labels_locked(h, nullptr, 0, true, slot); } catch (...) {}
+        }
+        throw;
+    }
 }
 
 int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n) {
+    return guarded([&] { parts_set_column(m, labels, n, kLabelSlot); });
+}
+
+int cph_parts_set_column(cph_parts* m, uint32_t slot, const int32_t* values, uint64_t n) {
     return guarded([&] {
-        if (!m) throw InvalidArg("null handle");
-        std::unique_lock<std::shared_mutex> lk(m->life);
-        if (!parts_finalized(m)) throw InvalidArg("labels belong to a finalized index: finalize or load it first");
-        if (labels && n != m->bounds.back())
-            throw InvalidArg("label column has " + std::to_string(n) + " entries, the index holds " + std::to_string(m->bounds.back()));
-        for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
-            std::lock_guard<std::mutex> g(h->mu);
-            if (labels && (!h->has_rows || h->host.rows.size() != h->host.n))
-                throw InvalidArg("a part has no row map: labels of a partitioned index are given in input rows");
-        }
-        try {
-            for (size_t p = 0; p < m->parts.size(); ++p)     // global input rows, cut at the part bounds
-                set_labels(m->parts[p], labels ? labels + m->bounds[p] : nullptr, m->bounds[p + 1] - m->bounds[p], CPH_IDS_INPUT);
-        } catch (...) {                                      // (a device failure: no part keeps a column the others lack)
-            for (cph_index* h : m->parts) {
-                std::lock_guard<std::mutex> g(h->mu);
-                try { install_labels_locked(h, nullptr, 0, true); } catch (...) {}
-            }
-            throw;
-        }
+        require_slot(slot);
+        parts_set_column(m, values, n, (int)slot);
     });
 }
 
+// cph_parts_filters_from_labels / cph_parts_filters_from_column.
+static void parts_filters_from_column(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out, int slot) {
+    if (cnt == 0) return;
+    if (!out) throw InvalidArg("null argument");
+    std::fill(out, out + cnt, nullptr);
+    if (!m || !lo || !hi) throw InvalidArg("null argument");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+    std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
+    for (auto& f : made) {
+        f.reset(new cph_parts_filter());
+        f->n_bits = m->bounds.back();
+        f->f.reserve(m->parts.size());
+    }
+    std::vector<cph_filter*> slice(cnt);
+    for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
+        filters_from_labels(m->parts[p], lo, hi, cnt, slice.data(), slot);
+        for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
+    }
+    for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
+}
+
 int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] { parts_filters_from_column(m, lo, hi, cnt, out, kLabelSlot); });
+}
+
+int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] {
+        require_slot(slot);
+        parts_filters_from_column(m, lo, hi, cnt, out, (int)slot);
+    });
+}
+
+// Part p of every operand, combined on part p's device (filters_combine).  All made, or none.
+int cph_parts_filters_combine(int op, const cph_parts_filter* const* a, uint32_t cnt, const cph_parts_filter* const* b, uint32_t n_b,
+                              cph_parts_filter** out) {
     return guarded([&] {
         if (cnt == 0) return;
         if (!out) throw InvalidArg("null argument");
         std::fill(out, out + cnt, nullptr);
-        if (!m || !lo || !hi) throw InvalidArg("null argument");
-        std::shared_lock<std::shared_mutex> lk(m->life);
-        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        if (!a) throw InvalidArg("null argument");
+        check_combine_shape(op, cnt, b, n_b);
+        for (uint32_t j = 0; j < cnt; ++j)
+            if (!a[j]) throw InvalidArg("null filter");
+        for (uint32_t j = 0; j < n_b; ++j)
+            if (!b[j]) throw InvalidArg("null filter");
+        const size_t P = a[0]->f.size();
+        const uint64_t n_bits = a[0]->n_bits;
+        auto same = [&](const cph_parts_filter* f) {
+            if (f->f.size() != P) throw InvalidArg("filters with different part counts cannot be combined");
+            if (f->n_bits != n_bits) throw InvalidArg("filters of different sizes cannot be combined");
+        };
+        for (uint32_t j = 0; j < cnt; ++j) same(a[j]);
+        for (uint32_t j = 0; j < n_b; ++j) same(b[j]);
         std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
         for (auto& f : made) {
             f.reset(new cph_parts_filter());
-            f->n_bits = m->bounds.back();
-            f->f.reserve(m->parts.size());
+            f->n_bits = n_bits;
+            f->f.reserve(P);
         }
+        std::vector<const cph_filter*> ap(cnt), bp(n_b);
         std::vector<cph_filter*> slice(cnt);
-        for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
-            filters_from_labels(m->parts[p], lo, hi, cnt, slice.data());
+        for (size_t p = 0; p < P; ++p) {
+            for (uint32_t j = 0; j < cnt; ++j) ap[j] = a[j]->f[p];
+            for (uint32_t j = 0; j < n_b; ++j) bp[j] = b[j]->f[p];
+            filters_combine(op, ap.data(), cnt, n_b ? bp.data() : nullptr, n_b, slice.data());
             for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
         }
         for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();

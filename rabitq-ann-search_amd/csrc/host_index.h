@@ -218,6 +218,43 @@ inline void labels_to_internal_host(const int32_t* by_row, const uint32_t* rows,
     for (size_t i = 0; i < n; ++i) out[i] = by_row[rows[i]];
 }
 
+// The host statement of the filter algebra (cph_filters_combine; device_filter_ops.h): out[j] = a[j] OP b[j] word by
+// word for m bitmaps of (n_bits + 31) / 32 words each, one behind the other; b holds m bitmaps, or ONE that every j
+// reads (b_broadcast), and is not read for kFilterNot.  Every word of `out` is written; the bits of the last word at
+// or above n_bits are clear whatever the inputs hold there (NOT would set them); counts[j] = popcount(out[j]).
+enum FilterOp : int { kFilterAnd = 0, kFilterOr = 1, kFilterAndNot = 2, kFilterXor = 3, kFilterNot = 4 };
+constexpr int kFilterOps = 5;
+
+inline uint32_t filter_op_word(int op, uint32_t a, uint32_t b) {
+    switch (op) {
+        case kFilterAnd: return a & b;
+        case kFilterOr: return a | b;
+        case kFilterAndNot: return a & ~b;
+        case kFilterXor: return a ^ b;
+        default: return ~a;
+    }
+}
+
+inline void filter_combine_host(int op, const uint32_t* a, const uint32_t* b, bool b_broadcast, size_t n_bits, size_t m,
+                                uint32_t* out, uint64_t* counts) {
+    const size_t nw = (n_bits + 31) / 32;
+    const uint32_t last = (n_bits & 31) ? (1u << (n_bits & 31)) - 1u : 0xFFFFFFFFu;
+    for (size_t j = 0; j < m; ++j) {
+        const uint32_t* aj = a + j * nw;
+        const uint32_t* bj = op == kFilterNot ? nullptr : b + (b_broadcast ? 0 : j * nw);
+        uint64_t c = 0;
+        for (size_t w = 0; w < nw; ++w) {
+            uint32_t x = filter_op_word(op, aj[w], bj ? bj[w] : 0u);
+            if (w == nw - 1) x &= last;
+            out[j * nw + w] = x;
+            c += (uint64_t)__builtin_popcount(x);
+        }
+        counts[j] = c;
+    }
+}
+
+constexpr uint32_t kMaxColumns = 8;   // extra attribute columns of a handle (cph_set_column), next to the label column
+
 struct HostIndex {
     size_t D = 0, bw = 0, dim = 0, n = 0;
     int32_t max_level = 0;
@@ -243,6 +280,9 @@ struct HostIndex {
     uint64_t n_removed = 0;
     // The label column (cph_set_labels): labels[i] = label of internal id i; empty = none.  No file carries it.
     std::vector<int32_t> labels;
+    // The attribute columns (cph_set_column): columns[s][i] = value of internal id i in slot s; empty = none.  They
+    // live and die with the label column: no file carries them.
+    std::vector<int32_t> columns[kMaxColumns];
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

@@ -316,6 +316,56 @@ int cph_host_group_rows(const int64_t* ids, const float* dist, uint64_t n, uint6
                         const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist, int32_t* out_keys,
                         int32_t* out_counts, uint8_t* out_complete);
 
+/* ---- diversified search ------------------------------------------------------------------ */
+/* k results per query that are close to the query AND not copies of each other: maximal marginal relevance (MMR) over a
+ * candidate row, on the device.  A query's candidate row is what the ordinary search returns for it at k = candidates
+ * (C), exactly as for grouped search above: same filters, exact flag, exact threshold, removed rows, tail, routing and
+ * refusals.  The statement (csrc/host_diverse.h is its host form, tests/diverse_model.py its numpy form):
+ *   - walk the row front to back, skip padding and ids that occurred earlier in the row; the survivors are the
+ *     candidates, each with its position j in the row and its relevance r_j = dist[j] (bits kept);
+ *   - a = lam, b = 1.0f - a (float32, rounded once);
+ *   - d(s, j) has the bits cph_exact_l2 returns for query = the stored row of internal id s and id = j: eight FMA chains
+ *     over the zero-padded rows reduced ((c0+c4)+(c1+c5))+((c2+c6)+(c3+c7)), qnorm = the same chains over s * s, norm =
+ *     the stored norm of j.  It is not symmetric in its bits; the order of the arguments is as written;
+ *   - pick 0 is the first candidate; for pick t >= 1 every unpicked candidate has m_j = min over picked s of d(s, j) and
+ *     score_j = (a * r_j) - (b * m_j), three separately rounded float32 operations; the smallest score is picked, equal
+ *     scores (+0 == -0) go to the lower row position; k picks, or until the candidates run out.
+ * Outputs per query, in pick order (NOT ascending): ids [k] int64, padded with -1 (internal ids; under CPH_IDS_INPUT input
+ * rows, translated where a pick is written); dist [k] = r of the pick; gap [k] = m of the pick when it was taken, FLT_MAX
+ * for pick 0; dist and gap are padded with FLT_MAX.  lam = 1 gives the first k non-repeated entries of the row, lam = 0 a
+ * farthest-point walk over the candidates.
+ *
+ * Limits: 1 <= k <= candidates <= 1024, 0 <= lam <= 1 (NaN is refused).  CPH_INVALID_ARGUMENT: NULL pointers, a shape or
+ * lam outside the limits, every refusal of the underlying search; nothing is written then.
+ *
+ * The work: as for grouped search -- under the handle mutex the search runs at k = C into the same scratch rows (four
+ * sets in rotation, only ever grown; no hipMalloc and no hipFree in steady state), in internal ids; then ONE launch of
+ * diverse_rows_kernel (csrc/device_diverse.h) on the same stream reads the handle's resident vectors and norms and writes
+ * all three outputs, padding included.  cph_search_diverse takes and returns host arrays; cph_search_diverse_device takes
+ * device pointers and a stream and waits for nothing.  cph_last_search_stats afterwards: those of the underlying search
+ * ONLY; the kernel's pair distances are not counted as exact distances.
+ * Partitioned indexes have no diverse search: every part has its own internal ids. */
+int cph_search_diverse(cph_index* h, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                       const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist,
+                       float* gap);
+int cph_search_diverse_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                              const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* d_ids,
+                              float* d_dist, float* d_gap, void* stream);
+/* Debug hooks of the measurement script (scripts/diverse_sweep.py), as cph_debug_time_grouped / _last_group_rows_us: the
+ * diverse_rows_kernel launch of every diverse search of this handle between two HIP events while switched on. */
+int cph_debug_time_diverse(cph_index* h, int on);
+int cph_debug_last_diverse_rows_us(cph_index* h, double* us);
+/* Test hook: diverse_rows_kernel on given rows (host arrays ids / dist [n][candidates], internal ids; an id at or above
+ * cph_size counts as padding) against the vectors and norms of the handle; ids are written through the row map under
+ * CPH_IDS_INPUT.  The device outputs start as 0xA5 bytes, so a slot the kernel left alone shows.
+ * cph_host_diverse_rows is the host statement (csrc/host_diverse.h, no HIP call) over raw [n_ids][D] (zero-padded rows, D a
+ * multiple of 8) and norm_sq [n_ids]; rows [n_ids] or NULL. */
+int cph_diverse_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, uint64_t k, float lam,
+                          int64_t* out_ids, float* out_dist, float* out_gap);
+int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* raw, const float* norm_sq,
+                          uint64_t n_ids, uint64_t D, const uint32_t* rows, uint64_t k, float lam, int64_t* out_ids, float* out_dist,
+                          float* out_gap);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -655,6 +705,11 @@ int cph_multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uin
                              const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
                              const int32_t* filter_of, int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts,
                              uint8_t* complete);
+/* cph_search_diverse over the same shards (plan_shards), every shard on its replica's worker; the bytes are those of one
+ * device.  filters[f * R + r] = filter f on replica r; every replica is asked before any shard runs. */
+int cph_multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                             const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids,
+                             float* dist, float* gap);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

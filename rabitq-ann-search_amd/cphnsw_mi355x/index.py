@@ -1234,6 +1234,117 @@ class CPIndex:
         _lib.check(_lib.lib().cph_debug_last_group_rows_us(self._replicas()[replica], C.byref(us)))
         return us.value
 
+    # -- diversified search (not in the reference) ----------------------------------------------
+    DIVERSE_MAX_CANDIDATES = 1024
+
+    def _diverse_args(self, n, k, lam, candidates, filter, filter_of):
+        """Validation shared by both diverse entry points -> (k, lam, C, [IdFilter] or None, filter_of or None, IdFilter
+        or None)."""
+        if self._p is not None:
+            raise ValueError("search_diverse is not defined on a partitioned index (every part has its own internal ids): "
+                             "use part(i).search_diverse")
+        k, lam = int(k), float(lam)
+        cap = self.DIVERSE_MAX_CANDIDATES
+        if k < 1:
+            raise ValueError("search_diverse needs k >= 1")
+        if not 0.0 <= lam <= 1.0:                    # (NaN fails both comparisons)
+            raise ValueError("search_diverse needs lam in [0, 1]")
+        if candidates is None:
+            if k > cap:
+                raise ValueError(f"search_diverse needs k <= {cap} (the longest candidate row)")
+            candidates = min(cap, max(64, 4 * k))    # a policy, not a measured optimum
+        candidates = int(candidates)
+        if not k <= candidates <= cap:
+            raise ValueError(f"candidates must lie in [k, {cap}]")
+        fs, fo = self._filter_list(filter, filter_of, n)
+        f = None if (fs is not None or filter is None) else self._filter(filter)
+        return k, lam, candidates, fs, fo, f
+
+    def search_diverse(self, queries, k=DEFAULT_K, lam=0.5, candidates=None, filter=None, exact=False, filter_of=None,
+                       label=None):
+        """k results per query that are close to the query and not copies of each other (maximal marginal relevance),
+        re-ranked on the device: (ids int64 [n, k], dist float32 [n, k], gap float32 [n, k]), in PICK order, not ascending.
+        A query's candidate row is row i of search_batch(queries, C, filter=..., exact=..., filter_of=...) -- same
+        routing, removed rows, tail and refusals -- with padding and repeated ids skipped.  Pick 0 is the nearest
+        candidate.  Every later pick minimises lam * dist_j - (1 - lam) * m_j over the unpicked candidates, m_j = the
+        smallest distance from j to a row picked so far (float32, the arithmetic of exact_l2; equal scores go to the
+        earlier candidate).  dist[i, t] is the pick's distance to the query, gap[i, t] its m when it was taken (FLT_MAX
+        for pick 0).  Fewer than k candidates: ids padded with -1 (input rows under result_ids = "input"), dist and gap
+        with FLT_MAX.  lam = 1 is the plain search with repeats dropped, lam = 0 a farthest-point walk.
+        `candidates=C` (k <= C <= 1024) is the length of the candidate row; candidates=None takes
+        C = min(1024, max(64, 4 * k)): a policy, not a measured optimum, in ONE pass (nothing is re-run at a larger C).
+        last_search_stats() afterwards reports the underlying search only: the pair distances of the re-ranking are not
+        added to exact_l2.  A multi-device index shards the queries like search_batch; the bytes are those of one
+        device.  A partitioned index is refused (use part(i).search_diverse)."""
+        q = _as_f32(queries)
+        if q.ndim != 2 or q.shape[1] != self._dim:
+            raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_diverse(
+                q, k, lam, candidates=candidates, filter=f, exact=exact, filter_of=fo))
+        n, L = q.shape[0], _lib.lib()
+        k, lam, C_, fs, fo, f = self._diverse_args(n, k, lam, candidates, filter, filter_of)
+        out = (np.empty((n, k), np.int64), np.empty((n, k), np.float32), np.empty((n, k), np.float32))
+        multi = self._m is not None
+        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
+        po = [o.ctypes.data if n else None for o in out]
+        fn, h = (L.cph_multi_search_diverse, self._m) if multi else (L.cph_search_diverse, self._h)
+        _lib.check(fn(h, q.ctypes.data if n else None, n, k, lam, C_, fh, nf, fop, int(bool(exact)), *po))
+        return out
+
+    def search_diverse_device(self, queries, k=DEFAULT_K, lam=0.5, candidates=None, out=None, stream=None, filter=None,
+                              exact=False, filter_of=None, label=None):
+        """search_diverse on a float32 torch tensor (n, dim) on this index' device; returns (ids, dist, gap) as torch
+        tensors on the same device.  Like search_batch_device it only enqueues, on `stream` (default: torch's current
+        stream), and never waits: the tensors are valid in stream order, two batches on two streams overlap.  `out`: the
+        three tensors to write (contiguous, on the queries' device).  filter / filter_of / label are host data as in
+        search_batch_device; a filter closed after the call waits for the batch.  A multi-device index runs the whole
+        batch on one replica on the queries' device."""
+        import torch
+        if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_diverse_device(
+                queries, k, lam, candidates=candidates, out=out, stream=stream, filter=f, exact=exact, filter_of=fo))
+        n = queries.shape[0]
+        k, lam, C_, fs, fo, f = self._diverse_args(n, k, lam, candidates, filter, filter_of)
+        rep = self._device_replica(queries)
+        h = self._replicas()[rep]
+        fresh = []                       # tensors allocated here, on torch's current stream
+        if not queries.is_contiguous():
+            queries = queries.contiguous()
+            fresh.append(queries)
+        dtypes = (torch.int64, torch.float32, torch.float32)
+        if out is None:
+            res = [torch.empty((n, k), dtype=dt, device=queries.device) for dt in dtypes]
+            fresh += res
+        else:
+            res = list(out)
+            if len(res) != 3:
+                raise ValueError("out must be the three tensors (ids, dist, gap)")
+            for t, dt in zip(res, dtypes):
+                if tuple(t.shape) != (n, k) or t.dtype != dt or t.device != queries.device or not t.is_contiguous():
+                    raise ValueError("out must be contiguous (n, k) int64 / float32 / float32 tensors on the queries' device")
+        st, _ = self._search_stream(stream, queries, fresh)
+        fh, nf, fop = self._filter_args(fs, fo, f, rep)
+        _lib.check(_lib.lib().cph_search_diverse_device(h, queries.data_ptr() if n else None, n, k, lam, C_, fh, nf, fop,
+                                                        int(bool(exact)), *[t.data_ptr() if n else None for t in res],
+                                                        C.c_void_p(st)))
+        return tuple(res)
+
+    def time_diverse(self, on=True):
+        """Debug hook of the measurement script: while on, the re-ranking kernel of every diverse search is bracketed by
+        HIP events (last_diverse_rows_us).  Off by default."""
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_debug_time_diverse(h, int(bool(on))))
+
+    def last_diverse_rows_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the re-ranking kernel of the last diverse search made under
+        time_diverse() on the given replica; waits for that launch."""
+        us = C.c_double(0)
+        _lib.check(_lib.lib().cph_debug_last_diverse_rows_us(self._replicas()[replica], C.byref(us)))
+        return us.value
+
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):
         space = self._result_ids if ids is None else ids

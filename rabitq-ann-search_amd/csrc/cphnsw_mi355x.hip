@@ -37,6 +37,7 @@
 #include "device_exact.h"
 #include "device_range.h"
 #include "device_tail.h"
+#include "device_diverse.h"
 #include "device_group.h"
 #include "host_index.h"
 #include "host_parallel.h"
@@ -172,12 +173,13 @@ struct RangeScratch {
 };
 constexpr size_t kRangeScratchKept = 2;
 
-// The device buffers of one grouped search (cph_search_grouped*): the [n][C] candidate rows of the underlying search and,
-// for the host form, the queries and the five outputs.  A handle owns kMaxBatchSets of them, used in turn and only ever
-// grown; `ev` follows the last kernel that touched the rows, the next call on these buffers makes its stream wait for it.
+// The device buffers of one search that re-ranks candidate rows (cph_search_grouped*, cph_search_diverse*): the [n][C]
+// candidate rows of the underlying search and, for the host form, the queries and the outputs (grouped: five, diverse:
+// ids, dist and gap).  A handle owns kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel
+// that touched the rows, the next call on these buffers makes its stream wait for it.
 struct GroupScratch {
     DevBuf<int64_t> r_ids, o_ids;
-    DevBuf<float> r_dist, o_dist, d_q;
+    DevBuf<float> r_dist, o_dist, o_gap, d_q;
     DevBuf<int32_t> o_keys, o_counts;
     DevBuf<uint8_t> o_complete;
     hipEvent_t ev = nullptr;
@@ -302,9 +304,12 @@ struct cph_index {
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
     GroupScratch group_scratch[kMaxBatchSets];                  // buffers of grouped searches, in rotation (under mu)
     int last_group = kMaxBatchSets - 1;
-    // debug hook cph_debug_time_grouped: only while group_timing is on is a group pass bracketed by the two events
-    hipEvent_t ev_group0 = nullptr, ev_group1 = nullptr;
-    bool group_timing = false, group_timed = false;
+    // debug hooks cph_debug_time_grouped / cph_debug_time_diverse: only while its timer is on is a pass over the
+    // candidate rows bracketed by the two events
+    struct PassTimer {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        bool on = false, timed = false;
+    } group_timer, diverse_timer;
     uint64_t index_epoch = 0;          // counts the index swaps (begin_device_swap): a cph_range of an older index refuses to finish
     hipStream_t own_stream = nullptr;  // host-API calls (cph_search_batch, cph_search, hooks)
     bool order_queries = true;         // CPH_QUERY_ORDER=0 disables the closest-entry-first launch order
@@ -1633,7 +1638,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 108; }
+int cph_version(void) { return 109; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1705,8 +1710,10 @@ static void destroy_index(cph_index* h) {
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->ev_label0) (void)hipEventDestroy(h->ev_label0);
     if (h->ev_label1) (void)hipEventDestroy(h->ev_label1);
-    if (h->ev_group0) (void)hipEventDestroy(h->ev_group0);
-    if (h->ev_group1) (void)hipEventDestroy(h->ev_group1);
+    for (cph_index::PassTimer* pt : {&h->group_timer, &h->diverse_timer}) {
+        if (pt->ev0) (void)hipEventDestroy(pt->ev0);
+        if (pt->ev1) (void)hipEventDestroy(pt->ev1);
+    }
     for (auto& ls : h->leaders) {
         if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
         if (ls.pin) (void)hipHostFree(ls.pin);
@@ -5496,11 +5503,12 @@ const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) 
     return keys->keys.p;
 }
 
-// The body of both forms: d_queries and the five outputs in device memory, everything enqueued on `st`.  The caller
-// holds the handle mutex, has set the device and has checked the shape and the output pointers.
-void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
-                           const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
-                           int64_t* d_ids, float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, hipStream_t st) {
+// The body of both forms of a search that re-ranks candidate rows (grouped, diverse): the ordinary search at k = C into
+// the rows of `gs`, in internal ids, then pass(), which enqueues one kernel over those rows, bracketed by the timer's
+// events while it is on; everything on `st`.  The caller holds the handle mutex and has set the device.
+template <class Pass>
+void search_rows_then_pass(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
+                           uint32_t F, const int32_t* filter_of, bool exact, cph_index::PassTimer& timer, hipStream_t st, Pass pass) {
     if (!gs.ev) HIP_CHECK(hipEventCreateWithFlags(&gs.ev, hipEventDisableTiming));
     if (gs.r_ids.n < n * C) {
         if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));      // growing: the old rows must be idle
@@ -5513,6 +5521,26 @@ void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_querie
             InternalIdsScope internal(h);
             search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, true, st));
         }
+        timer.timed = false;
+        if (timer.on) HIP_CHECK(hipEventRecord(timer.ev0, st));
+        pass();
+        if (timer.on) HIP_CHECK(hipEventRecord(timer.ev1, st));
+        timer.timed = timer.on;
+    } catch (...) {
+        (void)hipEventRecord(gs.ev, st);                          // whatever was enqueued may still write the rows
+        gs.used = true;
+        throw;
+    }
+    HIP_CHECK(hipEventRecord(gs.ev, st));
+    gs.used = true;
+}
+
+// Grouped search: d_queries and the five outputs in device memory.  The caller has checked the shape and the output
+// pointers.
+void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
+                           const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
+                           int64_t* d_ids, float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, hipStream_t st) {
+    search_rows_then_pass(h, gs, d_queries, n, C, filters, F, filter_of, exact, h->group_timer, st, [&] {
         GroupArgs a{};
         a.ids = gs.r_ids.p;
         a.dist = gs.r_dist.p;
@@ -5527,18 +5555,8 @@ void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_querie
         a.out_keys = d_keys;
         a.out_counts = d_counts;
         a.out_complete = d_complete;
-        h->group_timed = false;
-        if (h->group_timing) HIP_CHECK(hipEventRecord(h->ev_group0, st));
         group_rows(a, (uint32_t)n, st);
-        if (h->group_timing) HIP_CHECK(hipEventRecord(h->ev_group1, st));
-        h->group_timed = h->group_timing;
-    } catch (...) {
-        (void)hipEventRecord(gs.ev, st);                          // whatever was enqueued may still write the rows
-        gs.used = true;
-        throw;
-    }
-    HIP_CHECK(hipEventRecord(gs.ev, st));
-    gs.used = true;
+    });
 }
 
 // What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
@@ -5559,6 +5577,21 @@ bool grouped_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t k,
 GroupScratch& next_group_scratch(cph_index* h) {
     h->last_group = (h->last_group + 1) % kMaxBatchSets;
     return h->group_scratch[h->last_group];
+}
+
+void pass_timer_switch(cph_index::PassTimer& t, bool on) {
+    if (on && !t.ev0) HIP_CHECK(hipEventCreate(&t.ev0));
+    if (on && !t.ev1) HIP_CHECK(hipEventCreate(&t.ev1));
+    t.on = on;
+    t.timed = false;
+}
+
+// Device time of the last timed pass in microseconds; waits for it.
+double pass_timer_us(cph_index::PassTimer& t) {
+    HIP_CHECK(hipEventSynchronize(t.ev1));
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t.ev0, t.ev1));
+    return (double)ms * 1e3;
 }
 
 void search_grouped_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_group_keys* keys,
@@ -5715,10 +5748,7 @@ int cph_debug_time_grouped(cph_index* h, int on) {
         if (!h) throw InvalidArg("null handle");
         std::lock_guard<std::mutex> lk(h->mu);
         h->use_device();
-        if (on && !h->ev_group0) HIP_CHECK(hipEventCreate(&h->ev_group0));
-        if (on && !h->ev_group1) HIP_CHECK(hipEventCreate(&h->ev_group1));
-        h->group_timing = on != 0;
-        h->group_timed = false;
+        pass_timer_switch(h->group_timer, on != 0);
     });
 }
 
@@ -5726,12 +5756,9 @@ int cph_debug_last_group_rows_us(cph_index* h, double* us) {
     return guarded([&] {
         if (!h || !us) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->group_timed) throw InvalidArg("no timed grouped search has run on this handle (cph_debug_time_grouped)");
+        if (!h->group_timer.timed) throw InvalidArg("no timed grouped search has run on this handle (cph_debug_time_grouped)");
         h->use_device();
-        HIP_CHECK(hipEventSynchronize(h->ev_group1));
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, h->ev_group0, h->ev_group1));
-        *us = (double)ms * 1e3;
+        *us = pass_timer_us(h->group_timer);
     });
 }
 
@@ -5788,6 +5815,207 @@ int cph_host_group_rows(const int64_t* ids, const float* dist, uint64_t n, uint6
         check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, out_ids, out_dist, out_keys, out_counts, out_complete);
         group_rows_host(ids, dist, n, (uint32_t)candidates, key_of, rows, (uint32_t)k, (uint32_t)group_size, out_ids, out_dist, out_keys,
                         out_counts, out_complete);
+    });
+}
+
+}  // extern "C"
+
+// ---- diversified search: MMR re-ranking of a candidate row (device_diverse.h, host_diverse.h) -----------------------------
+// The grouped entries line for line: an ordinary search at k = C into the scratch rows, in internal ids, then
+// diverse_rows_kernel on the same stream against the handle's resident vectors and norms.
+namespace {
+
+// (An id at or above n_ids in given rows is no error: the statement counts it as padding.)
+void check_diverse_shape(uint64_t k, uint64_t C, float lam) {
+    if (k < 1) throw InvalidArg("diverse search needs k >= 1");
+    if (C > kDiverseMaxCandidates)
+        throw InvalidArg("diverse search supports candidates <= " + std::to_string(kDiverseMaxCandidates) + ", got " + std::to_string(C));
+    if (C < k) throw InvalidArg("diverse search needs k <= candidates (got " + std::to_string(k) + " > " + std::to_string(C) + ")");
+    if (!(lam >= 0.0f && lam <= 1.0f)) throw InvalidArg("diverse search needs lam in [0, 1]");
+}
+
+void check_diverse_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, uint64_t n_ids, uint64_t k, float lam,
+                             const int64_t* out_ids, const float* out_dist, const float* out_gap) {
+    if (!ids || !dist || !out_ids || !out_dist || !out_gap) throw InvalidArg("null argument");
+    check_diverse_shape(k, C, lam);
+    if (n < 1 || n > 0x7FFFFFFFull || n_ids < 1 || n_ids > 0xFFFFFFFFull) throw InvalidArg("diverse rows: sizes out of range");
+}
+
+DiverseArgs diverse_args(const cph_index* h, const int64_t* r_ids, const float* r_dist, uint64_t C, uint64_t k, float lam, int64_t* d_ids,
+                         float* d_dist, float* d_gap) {
+    DiverseArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.a = lam;
+    a.b = 1.0f - lam;
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.n_ids = (uint32_t)h->size();
+    a.D = h->D;
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
+    a.out_ids = d_ids;
+    a.out_dist = d_dist;
+    a.out_gap = d_gap;
+    return a;
+}
+
+void search_diverse_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t C,
+                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
+                           float* d_dist, float* d_gap, hipStream_t st) {
+    search_rows_then_pass(h, gs, d_queries, n, C, filters, F, filter_of, exact, h->diverse_timer, st, [&] {
+        diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, d_ids, d_dist, d_gap), (uint32_t)n, st);
+    });
+}
+
+// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
+bool diverse_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
+                      uint32_t F, const int32_t* filter_of, const void* ids, const void* dist, const void* gap) {
+    require_finalized(h);
+    check_diverse_shape(k, C, lam);
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    if (n > 0x7FFFFFFFull) throw InvalidArg("batch too large");
+    if (n == 0) return false;
+    if (!queries || !ids || !dist || !gap) throw InvalidArg("null argument");
+    return true;
+}
+
+void search_diverse_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
+                         uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist, float* gap) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!diverse_has_work(h, queries, n, k, lam, C, filters, F, filter_of, ids, dist, gap)) return;
+    h->use_device();
+    hipStream_t st = own_stream(h);
+    GroupScratch& gs = next_group_scratch(h);
+    const size_t slots = (size_t)n * k;
+    if (gs.d_q.n < n * h->dim || gs.o_ids.n < slots || gs.o_dist.n < slots || gs.o_gap.n < slots) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.d_q.n < n * h->dim) gs.d_q.alloc(n * h->dim);
+        if (gs.o_ids.n < slots) gs.o_ids.alloc(slots);
+        if (gs.o_dist.n < slots) gs.o_dist.alloc(slots);
+        if (gs.o_gap.n < slots) gs.o_gap.alloc(slots);
+    }
+    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
+    search_diverse_locked(h, gs, gs.d_q.p, n, k, lam, C, filters, F, filter_of, exact, gs.o_ids.p, gs.o_dist.p, gs.o_gap.p, st);
+    HIP_CHECK(hipMemcpyAsync(ids, gs.o_ids.p, slots * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(dist, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(gap, gs.o_gap.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void search_diverse_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t C,
+                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
+                           float* d_dist, float* d_gap, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!diverse_has_work(h, d_queries, n, k, lam, C, filters, F, filter_of, d_ids, d_dist, d_gap)) return;
+    h->use_device();
+    search_diverse_locked(h, next_group_scratch(h), d_queries, n, k, lam, C, filters, F, filter_of, exact, d_ids, d_dist, d_gap,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+// cph_multi_search_diverse: filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
+void multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
+                          uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist, float* gap) {
+    if (!m) throw InvalidArg("null handle");
+    const uint32_t R = (uint32_t)m->reps.size();
+    const uint64_t dim = m->reps[0]->dim;
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
+        diverse_has_work(h, queries, n, k, lam, C, filters, F, filter_of, ids, dist, gap);
+        check_replica_filters(h, filters, F, R, r);
+    }, [&] {
+        if (n && filter_of) check_filter_of(filter_of, n, F);
+        return n != 0;
+    }, [&](const Shard& s, size_t) {
+        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
+        return cph_search_diverse(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, lam, C,
+                                  F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0,
+                                  ids ? ids + s.lo * k : nullptr, dist ? dist + s.lo * k : nullptr, gap ? gap + s.lo * k : nullptr);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_search_diverse(cph_index* h, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                       const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist,
+                       float* gap) {
+    return guarded([&] { search_diverse_host(h, queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, ids, dist, gap); });
+}
+
+int cph_search_diverse_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                              const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* d_ids,
+                              float* d_dist, float* d_gap, void* stream) {
+    return guarded([&] {
+        search_diverse_device(h, d_queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, d_gap, stream);
+    });
+}
+
+int cph_multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
+                             const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids,
+                             float* dist, float* gap) {
+    return guarded([&] { multi_search_diverse(m, queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, ids, dist, gap); });
+}
+
+int cph_debug_time_diverse(cph_index* h, int on) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->use_device();
+        pass_timer_switch(h->diverse_timer, on != 0);
+    });
+}
+
+int cph_debug_last_diverse_rows_us(cph_index* h, double* us) {
+    return guarded([&] {
+        if (!h || !us) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->diverse_timer.timed) throw InvalidArg("no timed diverse search has run on this handle (cph_debug_time_diverse)");
+        h->use_device();
+        *us = pass_timer_us(h->diverse_timer);
+    });
+}
+
+int cph_diverse_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, uint64_t k, float lam,
+                          int64_t* out_ids, float* out_dist, float* out_gap) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        check_diverse_rows_args(ids, dist, n, candidates, h->size(), k, lam, out_ids, out_dist, out_gap);
+        h->use_device();
+        const size_t cells = (size_t)n * candidates, slots = (size_t)n * k;
+        DevBuf<int64_t> d_ids(cells), o_ids(slots);
+        DevBuf<float> d_dist(cells), o_dist(slots), o_gap(slots);
+        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
+        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
+        HIP_CHECK(hipMemset(o_ids.p, 0xA5, slots * 8));
+        HIP_CHECK(hipMemset(o_dist.p, 0xA5, slots * 4));
+        HIP_CHECK(hipMemset(o_gap.p, 0xA5, slots * 4));
+        diverse_rows(diverse_args(h, d_ids.p, d_dist.p, candidates, k, lam, o_ids.p, o_dist.p, o_gap.p), (uint32_t)n, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_ids, o_ids.p, slots * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_dist, o_dist.p, slots * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_gap, o_gap.p, slots * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* raw, const float* norm_sq,
+                          uint64_t n_ids, uint64_t D, const uint32_t* rows, uint64_t k, float lam, int64_t* out_ids, float* out_dist,
+                          float* out_gap) {
+    return guarded([&] {
+        if (!raw || !norm_sq) throw InvalidArg("null argument");
+        if (D < 8 || D > 0xFFFFFFFFull || (D & 7)) throw InvalidArg("diverse rows: D must be a multiple of 8");
+        check_diverse_rows_args(ids, dist, n, candidates, n_ids, k, lam, out_ids, out_dist, out_gap);
+        diverse_rows_host(ids, dist, n, (uint32_t)candidates, raw, norm_sq, n_ids, (uint32_t)D, rows, (uint32_t)k, lam, out_ids, out_dist,
+                          out_gap);
     });
 }
 

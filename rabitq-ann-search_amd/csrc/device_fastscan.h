@@ -246,6 +246,15 @@ struct BlockLoads {
         aux = reinterpret_cast<const uint4*>(blk + L.aux_off)[lane & 31];
     }
 
+    // Gives every register of c[] and aux a definition that costs no instruction and whose value is whatever the
+    // register held: for callers that issue the loads under a lane predicate and never look at the other lanes'
+    // values (the probe-first expansion of device_search.h, which lists the readers and their masks).
+    __device__ __forceinline__ void leave_undefined() {
+#pragma unroll
+        for (int k = 0; k < kCPL; ++k) asm volatile("" : "=v"(c[k].x), "=v"(c[k].y), "=v"(c[k].z), "=v"(c[k].w));
+        asm volatile("" : "=v"(aux.x), "=v"(aux.y), "=v"(aux.z), "=v"(aux.w));
+    }
+
     // Makes the compiler retire (wait for) the loads of issue() at this point of the program.
     __device__ __forceinline__ void retire() {
         if constexpr (kStatic) {

@@ -22,7 +22,11 @@
 //    longest query and the steady state shares the CU's one scalar unit between 24 waves; on the recall-gate workloads
 //    (beams of thousands of entries, no id locality) it is HBM-bound on the bytes it actually moves.  Hence: no
 //    software prefetch, the probe is a load (atomics only for new ids), shuffles are DPP / v_permlane32_swap, and
-//    everything a lane can do without an exec-mask round trip on the scalar unit is done that way.
+//    everything a lane can do without an exec-mask round trip on the scalar unit is done that way;
+//  * on that steady state an issued instruction costs about what it is of the 520 per expansion, so the usual expansion
+//    carries none it does not need (profiles/issue_diet.md): the LDS pop's path walk is straight-line, wave votes are
+//    taken on bools (ballot64 / any64 / all64), the termination tests at the loop head are two votes with a branch each
+//    instead of a verdict word, and under probe first the code registers of lanes that fetch nothing stay undefined.
 #pragma once
 #include <cstddef>
 #include <hip/hip_runtime.h>
@@ -232,6 +236,13 @@ __device__ __forceinline__ int opaque_lane(int lane) {
     return lane;
 }
 
+// Wave votes on a bool.  HIP's __ballot / __any / __all take an int: a condition that already sits in an SGPR pair is
+// turned into 0 / 1 in a VGPR (v_cndmask) and compared again (v_cmp_ne), and __any / __all go through a library call that
+// ends in a v_readfirstlane.  These read the mask where it is.
+__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool any64(bool p) { return ballot64(p) != 0ull; }
+__device__ __forceinline__ bool all64(bool p) { return ballot64(!p) == 0ull; }
+
 // The LDS part is addressed through address-space-3 pointers so that every access is a ds_*
 // instruction (a generic pointer would make them flat_* accesses, which also wait on vmcnt).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -357,11 +368,11 @@ __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lan
     // this kernel runs out of.)
     const bool b0 = H::before(h.lds_key(2 * lane + 2), h.lds_key(2 * lane + 1)) && (uint32_t)lane < nint;
     bool b1 = false;
-    const unsigned long long m0 = __ballot(b0);
+    const unsigned long long m0 = ballot64(b0);
     unsigned long long m1 = 0;
     if (nint > 64) {
         if ((uint32_t)lane + 64 < nint) b1 = H::before(h.lds_key(2 * lane + 130), h.lds_key(2 * lane + 129));
-        m1 = __ballot(b1);
+        m1 = ballot64(b1);
     }
     // Walk on hp = hole + 1: taking the left child doubles it, the right child doubles it and adds 1,
     // so after d steps hp is the binary string "1 r0 r1 .. r(d-1)" of the choices and every node on
@@ -369,32 +380,47 @@ __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lan
     // then derives its own pair of path positions with two shifts.
     uint32_t hp = 1, d = 0;
     if (nint >= 1) {
-        // Scalar walk, four instructions per level: with the mask shifted up by one, node hp - 1's bit sits at position
-        // hp; s_bitcmp0 puts "the right child moves up" into SCC and s_addc turns hp into 2 hp + SCC.  Nodes 63..126
-        // (hp = 64..127: at most the last step of a heap of up to 255 entries) take their bit from a second mask at
-        // position hp - 64, which is hp's low six bits -- all the instruction looks at.  The depth is recovered from
-        // hp's leading one afterwards.
+        // Scalar walk, two instructions per level and no branch: with the mask shifted up by one, node hp - 1's bit sits
+        // at position hp; s_bitcmp0 puts "the right child moves up" into SCC and s_addc turns hp into 2 hp + SCC.
+        // The walk proper goes on while hp <= nint.  With L = floor(log2(nint)) its first L steps are certain (after t
+        // steps hp < 2^(t+1) <= nint), step L + 1 is taken when the hp of step L is still <= nint, and there is no
+        // further one.  So six steps are made whatever the heap holds -- nodes >= nint answer "right" (their bit is masked
+        // to 0 above) and only lengthen the string behind the path, which stays its prefix -- and the depth
+        // d = L + (hp_L <= nint) cuts the string back.  (Until now: a rolled loop with a compare and a taken branch per
+        // level.)  Nodes 63..126 (hp = 64..127: d = 7, the last step of a heap of 131 to 255 entries) take their bit from
+        // a second mask at position hp - 64, which is hp's low six bits -- all the instruction looks at.
         const unsigned long long ms0 = m0 << 1;
-        const uint32_t lim = nint < 63u ? nint : 63u;
         asm volatile(
-            "1:\n\t"
-            "s_bitcmp0_b64 %[m], %[hp]\n\t"
-            "s_addc_u32 %[hp], %[hp], %[hp]\n\t"
-            "s_cmp_le_u32 %[hp], %[n]\n\t"
-            "s_cbranch_scc1 1b"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]\n\t"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]\n\t"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]\n\t"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]\n\t"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]\n\t"
+            "s_bitcmp0_b64 %[m], %[hp]\n\ts_addc_u32 %[hp], %[hp], %[hp]"
             : [hp] "+s"(hp)
-            : [m] "s"(ms0), [n] "s"(lim)
+            : [m] "s"(ms0)
             : "scc");
-        if (hp <= nint) {                          // 64 <= hp <= 126
-            const unsigned long long ms1 = (m1 << 1) | (m0 >> 63);
-            asm volatile(
-                "s_bitcmp0_b64 %[m], %[hp]\n\t"
-                "s_addc_u32 %[hp], %[hp], %[hp]"
-                : [hp] "+s"(hp)
-                : [m] "s"(ms1)
+        if (__builtin_expect(nint < 64u, 1)) {
+            const uint32_t L = 31u - (uint32_t)__builtin_clz(nint);
+            const uint32_t hl = hp >> (6u - L);
+            asm("s_cmp_le_u32 %[h], %[n]\n\ts_addc_u32 %[d], %[l], 0"      // d = L + (hp_L <= nint)
+                : [d] "=s"(d)
+                : [h] "s"(hl), [n] "s"(nint), [l] "s"(L)
                 : "scc");
+            hp >>= 6u - d;
+        } else {                                   // L = 6
+            d = 6;
+            if (hp <= nint) {                      // 64 <= hp <= 126
+                const unsigned long long ms1 = (m1 << 1) | (m0 >> 63);
+                asm volatile(
+                    "s_bitcmp0_b64 %[m], %[hp]\n\t"
+                    "s_addc_u32 %[hp], %[hp], %[hp]"
+                    : [hp] "+s"(hp)
+                    : [m] "s"(ms1)
+                    : "scc");
+                d = 7;
+            }
         }
-        d = 31u - (uint32_t)__builtin_clz(hp);
     }
     if (2 * hp == len) {                           // a last node with a left child only: len even, hole == (len - 2) / 2
         hp = 2 * hp;
@@ -407,7 +433,7 @@ __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lan
     // __push_heap: parent (now e_t) > v -> parent moves down.  Lanes >= d read p_1 (t = 0) and are masked out below.
     const typename H::E e = h.lds(my_src);
     const bool c = H::before(H::key_of(e), H::key_of(v));
-    const unsigned long long stay = ~__ballot(c) & ((1ull << d) - 1ull);
+    const unsigned long long stay = ~ballot64(c) & ((1ull << d) - 1ull);
     const uint32_t fin = stay ? 64u - (uint32_t)__builtin_clzll(stay) : 0u;   // v ends at p_fin
     if ((uint32_t)lane < fin) h.lds_put(my_dst, e);
     // p_fin = (hp >> (d - fin)) - 1 for every fin (= the hole when fin == d): one writer, one wave-uniform address, behind
@@ -436,7 +462,7 @@ __device__ __forceinline__ void heap_push_wave(const H& h, uint32_t hole, typena
     const uint32_t pt = on ? (hp >> t) - 1 : 0u;
     const typename H::E e = h.lds(pt);                                 // (lanes past the root read it again and are masked)
     const bool down = on && H::before(H::key_of(e), H::key_of(v));
-    const unsigned long long stop = ~__ballot(down);                   // first ancestor that stays (bits >= depth are set)
+    const unsigned long long stop = ~ballot64(down);                   // first ancestor that stays (bits >= depth are set)
     const uint32_t m = (uint32_t)__builtin_ctzll(stop);                 // ancestors p_1..p_m move down
     if (t <= m) h.lds_put((hp >> (t - 1)) - 1, e);                      // p_t's entry to p_(t-1), p_0 = the leaf
     if ((uint32_t)lane == m) h.lds_put((hp >> m) - 1, v);              // (m <= depth <= 8 < 64: that lane exists)
@@ -460,10 +486,10 @@ __device__ __forceinline__ void beam_pop_hybrid(const Beam& h, uint32_t size, in
     const uint4 v = Beam::load3(h.spill_ptr(len));       // the value __adjust_heap re-inserts (same address in every lane)
     // LDS levels 0..6: nodes 0..126, both children always inside the LDS part
     const bool b0 = Beam::before(h.lds_key(2 * lane + 2), h.lds_key(2 * lane + 1));
-    const unsigned long long m0 = __ballot(b0);
+    const unsigned long long m0 = ballot64(b0);
     bool b1 = false;
     if (lane < 63) b1 = Beam::before(h.lds_key(2 * lane + 130), h.lds_key(2 * lane + 129));
-    const unsigned long long m1 = __ballot(b1);
+    const unsigned long long m1 = ballot64(b1);
     uint32_t hp = 1, d = 7;                        // hp = hole + 1, the path as a bit string (see heap_pop_wave)
     {
         // seven steps, two scalar instructions each (heap_pop_wave's walk, unrolled: every node of levels 0..6 has both
@@ -490,8 +516,8 @@ __device__ __forceinline__ void beam_pop_hybrid(const Beam& h, uint32_t size, in
     auto walk = [&](float key, uint32_t idx) {
         const float key_r = __shfl_down(key, 1);   // even lanes hold left children, their right siblings sit one lane up
         const bool both = (lane & 1) == 0 && lane < 62 && idx + 1 < len;
-        const unsigned long long E2 = __ballot(both) << 2;
-        const unsigned long long M = __ballot(both && Beam::before(key_r, key)) << 2;
+        const unsigned long long E2 = ballot64(both) << 2;
+        const unsigned long long M = ballot64(both && Beam::before(key_r, key)) << 2;
         uint32_t P = 1, tmp;
         asm volatile(
             "1:\n\t"
@@ -559,7 +585,7 @@ __device__ __forceinline__ void beam_pop_hybrid(const Beam& h, uint32_t size, in
         else e = h.tload(beam_tail_off(src_hp - 1));
         c = Beam::before(Beam::key_of(e), Beam::key_of(v));
     }
-    const unsigned long long stay = ~__ballot(c) & ((1ull << d) - 1ull);
+    const unsigned long long stay = ~ballot64(c) & ((1ull << d) - 1ull);
     const uint32_t fin = stay ? 64u - (uint32_t)__builtin_clzll(stay) : 0u;
     if ((uint32_t)lane < fin) put_level(t, dst_hp, e);
     if (fin == d) { if (lane == 0) put_level(d, hp, v); }
@@ -586,7 +612,7 @@ __device__ __forceinline__ void beam_push_hybrid(const Beam& h, uint32_t hole, u
             if (t < lvl) e = h.pload(pbase + 3u * (rl >> t)); else e = h.lds((hp >> t) - 1);
             down = Beam::before(Beam::key_of(e), Beam::key_of(v));
         }
-        const unsigned long long stop = ~__ballot(down);
+        const unsigned long long stop = ~ballot64(down);
         const uint32_t m = (uint32_t)__builtin_ctzll(stop);
         auto put_anc = [&](uint32_t s, uint4 val) {                            // ancestor p_s (s = 0: the leaf)
             if (s < lvl) h.pstore(pbase + 3u * (rl >> s), val); else h.lds_put((hp >> s) - 1, val);
@@ -600,7 +626,7 @@ __device__ __forceinline__ void beam_push_hybrid(const Beam& h, uint32_t hole, u
         e = h.raw(pt);
         down = Beam::before(Beam::key_of(e), Beam::key_of(v));
     }
-    const unsigned long long stop = ~__ballot(down);
+    const unsigned long long stop = ~ballot64(down);
     const uint32_t m = (uint32_t)__builtin_ctzll(stop);
     if (t <= m) h.put((hp >> (t - 1)) - 1, e);
     if ((uint32_t)lane == m) h.put((hp >> m) - 1, v);
@@ -789,6 +815,9 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             asm volatile("" : "+s"(af_a), "+s"(af_b), "+s"(fl));
             qp.affine_a = af_a; qp.affine_b = af_b; qp.floor = fl;
         }
+        // (Not the blocks' base: the <4,128,true> instantiation used to re-read a.blocks at the head of every expansion,
+        // and carrying it per query the same way cost four more SGPR spills inside the loop -- 1.6 % slower on C2.  With
+        // the loop head below the allocator keeps it resident by itself; profiles/issue_diet.md.)
         qp.slack = s_slack[0];
         const float gamma = a.sc.gamma;
 
@@ -879,12 +908,13 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                 cur_id = bcast_u32(topv.z);
                 const float cur_est = __uint_as_float(topv.x);
                 const float cur_lower = __uint_as_float(topv.y);
-                uint32_t verdict = 2;  // 0 = done, 1 = skip (lower-bound pruned), 2 = expand
-                if (nn_size >= k && cur_est >= gamma_q * worst) verdict = 0;
-                else if (nn_size >= k && cur_lower > worst) verdict = 1;
-                verdict = bcast_u32(verdict);   // every lane read the same words: make it provably uniform
-                if (verdict == 0) break;
-                if (verdict == 1) {             // pruned: the entry leaves the beam, nothing is loaded
+                // Every lane read the same words: the votes make the two decisions provably uniform.  (They were one
+                // integer verdict -- 0 done, 1 pruned, 2 expand -- broadcast and tested twice; the compiler merged that
+                // with the loop's other exits into a state word that the usual expansion tested again between the
+                // verdict and its first load, and once more on the back edge.)
+                const bool full = nn_size >= k;
+                if (any64(full && cur_est >= gamma_q * worst)) break;          // done
+                if (any64(full && cur_lower > worst)) {                          // pruned: the entry leaves the beam, nothing is loaded
                     pop_beam(beam_size);
                     --beam_size;
                     continue;
@@ -946,13 +976,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
 #else
             constexpr bool kProbeFirst = PF && SD >= 128;
 #endif
-            if constexpr (kProbeFirst) {
-#pragma unroll
-                for (int kk = 0; kk < BlockLoads<BW, SD>::kCPL; ++kk) bl.c[kk] = make_uint4(0u, 0u, 0u, 0u);
-                bl.aux = make_uint4(0u, 0u, 0u, 0u);
-            } else {
-                bl.issue(blk, a.L, lane);
-            }
+            if constexpr (!kProbeFirst) bl.issue(blk, a.L, lane);
             __builtin_amdgcn_sched_barrier(0);
             CPH_TICKF(0);
             // ---- the pop, while those loads are in flight.  It needs only the id of the top, which the loads
@@ -1016,7 +1040,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                     const bool aj = __shfl((int)active, j) != 0;
                     if (aj && lane > j && oj == line) first = false;
                 }
-                trf[4] += __popcll(__ballot(first));
+                trf[4] += __popcll(ballot64(first));
             }
 #endif
 
@@ -1036,7 +1060,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             float worst0 = worst_pop;
             // (filtered: a vertex outside the allowed set never enters the result heap -- cur_id is uniform, so is this)
             const bool cur_allowed = !FILT || ((allow_cur >> (cur_id & 31u)) & 1u) != 0u;
-            const bool nn_changes = bcast_u32((cur_allowed && (nn_size < k || exact_dist < worst_pop)) ? 1u : 0u) != 0u;   // provably uniform
+            const bool nn_changes = any64(cur_allowed && (nn_size < k || exact_dist < worst_pop));   // every lane agrees: provably uniform
             if (nn_changes) {
                 nn_push_wave(nnw, nn, nn_size, k, cur_id, exact_dist, worst_pop, lane);
                 __builtin_amdgcn_wave_barrier();
@@ -1045,7 +1069,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             const uint32_t nn_sz = nn_size;
             CPH_TICK(1);
             CPH_TICKF(3);
-            if (!__any(active)) {  // n_neighbors == 0 (:137)
+            if (!any64(active)) {  // n_neighbors == 0 (:137)
                 // (retire the probe's destination register on this path too: a load left pending
                 // across the back edge costs every expansion a wait where that register is reused)
                 asm volatile("" ::"v"(old_bits));
@@ -1082,7 +1106,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                     const bool tiny = bcast_f32(dqp) < kEpsSmall;
                     if (!tiny) lower_bounds_split<BW>(qp, v, dqp, sq, lane, lo1, lo2, tl);
                     // any_survivor (:178-187) ranges over ALL the list's neighbours, estimated before or not
-                    if (__builtin_expect(nn_sz < k || __any(fetched && valid && lo1 < worst0), 1)) {
+                    if (__builtin_expect(nn_sz < k || any64(fetched && valid && lo1 < worst0), 1)) {
                         est = stage2_est_only<BW>(qp, v, dqp, tl, tiny);
                         lower = lo2;
                     } else if constexpr (!kProbeFirst) {            // the reference's skipped batch (:201-205)
@@ -1111,7 +1135,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                         est = stage2_est_only<BW>(qp, w, dqp, tl, tiny);
                         lower = lo2;
                         const bool acts = fetched && !(lo2 >= worst0) && (est < worst0 || est < gamma_q * worst0);
-                        if (__any(acts)) return false;
+                        if (any64(acts)) return false;
                         undecided2 = true;
                     }
                 }
@@ -1132,7 +1156,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             // ---- estimated set: result of the probe issued above --------------------------------
             bool is_new = active && (old_bits & my_bit) == 0;
             // a vertex whose neighbour list repeats an id: only the first copy is new
-            if ((a.flags & 1u) && __any(is_new)) {
+            if ((a.flags & 1u) && any64(is_new)) {
                 // (graphs written by the reference never repeat an id; the loader sets the
                 // flag when one does, and only then is this screen paid for)
 #pragma unroll 1   // cold path: rolled, or its 31 lane masks are hoisted and spilled for everyone
@@ -1142,7 +1166,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                     if (nj && lane > j && lane < 32 && oj == nid) is_new = false;
                 }
             }
-            const uint32_t new_mask = (uint32_t)(__ballot(is_new) & 0xFFFFFFFFull);
+            const uint32_t new_mask = (uint32_t)(ballot64(is_new) & 0xFFFFFFFFull);
             // mark the new ids (two may share a word) and log them for the un-marking at query end (discovery order =
             // neighbour order) under ONE predicate; a log that would overflow ends the attempt before anything is marked
             const uint32_t n_new = __popc(new_mask);
@@ -1167,6 +1191,20 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             }
             if constexpr (kProbeFirst) {
                 const bool fetch = ((new_mask >> (lane & 31)) & 1u) != 0u;       // both lane halves of a new neighbour
+                // The codes and aux values are loaded behind the probe by the lanes of the new neighbours only (`fetch`
+                // below).  The other lanes' registers are left UNDEFINED -- whatever the previous expansion left there --
+                // instead of being zeroed (4 kCPL + 4 v_mov per expansion with a new neighbour).  Such a lane computes
+                // est / lower from garbage (there are no floating-point traps on this path, and no address is formed
+                // from these values), and none of it is observable: every reader is masked by a set of lanes that
+                // `fetch` contains -- fetch = new_mask's bit of (lane & 31), is_new = that bit in the lower lane half:
+                //   estimate(): any64(fetched && valid && lo1 < worst0)              -> fetched (= fetch)
+                //   estimate(): acts = fetched && ...                                -> fetched
+                //   cand = is_new && ...  (cand_mask, s_list, the speculative exact L2) -> is_new
+                //   lane-parallel pushes: p = is_new && ...  (pm, the parent check under chk = p && .., the append) -> p
+                //   serial replay: m = new_mask [& ballot(!(lower >= worst0))], v_readlane of est / lower at the set
+                //   bits of m only                                                   -> new_mask
+                //   replay of the lane-parallel pushes: v_readlane at the set bits of pm -> p
+                bl.leave_undefined();
                 if (fetch) bl.issue_static(blk, lane);
                 if (__builtin_expect(!estimate(fetch), 0)) { overflow = true; stage2_redo = true; break; }
             } else if constexpr (!kSpeculate) {
@@ -1178,7 +1216,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             CPH_TICK(2);
             const bool warmup = nn_sz < k;  // (:210)
             bool cand = is_new && (warmup || (!(lower >= worst0) && est < worst0));
-            const uint32_t cand_mask = (uint32_t)(__ballot(cand) & 0xFFFFFFFFull);
+            const uint32_t cand_mask = (uint32_t)(ballot64(cand) & 0xFFFFFFFFull);
 
             st_new += n_new;
             CPH_TICK(3);
@@ -1210,7 +1248,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                 }
                 st_exact += n_cand;
                 __syncthreads();
-                if constexpr (FILT) allow_mask = (uint32_t)(__ballot(is_new && ((allow_w >> (nid & 31u)) & 1u) != 0u) & 0xFFFFFFFFull);
+                if constexpr (FILT) allow_mask = (uint32_t)(ballot64(is_new && ((allow_w >> (nid & 31u)) & 1u) != 0u) & 0xFFFFFFFFull);
             }
             CPH_TICK(4);
             CPH_TICKF(6);
@@ -1225,7 +1263,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                 // only the beam pushes themselves keep neighbour order.
                 const float dabs0 = gamma_q * worst0;
                 const bool p = is_new && !(lower >= worst0) && est < dabs0;
-                uint32_t pm = (uint32_t)(__ballot(p) & 0xFFFFFFFFull);
+                uint32_t pm = (uint32_t)(ballot64(p) & 0xFFFFFFFFull);
                 // std::push_heap of each in neighbour order.  Usual case: every new entry is no
                 // better than the parent of the leaf it lands on, so nothing moves and the pushes
                 // are independent appends -- each lane checks its own parent and writes its own leaf.
@@ -1248,7 +1286,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                     } else if (p && pos > 0) {
                         stay = !(heap.raw_key((pos - 1) >> 1) > est);
                     }
-                    if (__all(stay)) {
+                    if (all64(stay)) {
 #ifdef CPH_TRAFFIC_STATS
                         if (!in_lds) trf[3]++;
 #endif
@@ -1279,7 +1317,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                 // past the warm-up the threshold only falls: a lower bound that fails it at loop
                 // entry fails it at its turn too (:241), so those neighbours are dropped here
                 uint32_t m = warmup ? new_mask
-                                    : new_mask & (uint32_t)(__ballot(!(lower >= worst0)) & 0xFFFFFFFFull);
+                                    : new_mask & (uint32_t)(ballot64(!(lower >= worst0)) & 0xFFFFFFFFull);
                 // Every quantity of the reference's loop body is wave-uniform here (neighbour i's values come out
                 // of lane i with v_readlane, the heaps live in LDS), so the whole wave walks the loop together and
                 // the heap operations are the wave-parallel ones: a rerank costs two LDS round trips per heap
@@ -1325,7 +1363,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
                             gamma_q = bcast_f32(gamma_q);
                         }
                     }
-                    if (bcast_u32(push ? 1u : 0u)) {
+                    if (any64(push)) {             // (every lane agrees)
                         const uint4 ent = beam_pack(BeamEntry{key, lo, id_i});
 #ifdef CPH_TRAFFIC_STATS
                         if (beam_size >= kBeamLds) trf[2]++;

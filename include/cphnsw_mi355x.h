@@ -943,6 +943,49 @@ int cph_host_exact_group_plan(const uint64_t* seg_candidates, const uint64_t* se
  * [out[p], out[p + 1]); 1 <= P <= 16. */
 int cph_host_part_bounds(uint64_t n, uint32_t P, uint64_t* out);
 
+/* ---- the metric -------------------------------------------------------------------------- */
+/* CPH_METRIC_L2 (the default): distances are squared L2.  CPH_METRIC_COSINE: distances are 1 - cos(q, x).
+ *
+ * A cosine index stores x~ = x / sqrt(2 |x|^2), so |x~|^2 = 1/2, and gives queries the same treatment; then
+ * || q~ - x~ ||^2 = 1/2 + 1/2 - (q.x) / (|q||x|) = 1 - cos(q, x), and every search of the library -- graph, exact, tail,
+ * range, grouped, diverse, replicas, parts, single query -- reports the cosine distance with the kernels of the L2
+ * metric: smaller is better, radii of cph_range are in 1 - cos, ties and padding mean what they meant.  One kernel
+ * (csrc/device_normalize.h) normalises rows on the way in and queries on the way into every search, one launch per
+ * batch on the batch's stream; an L2 handle launches and allocates nothing for it.  Its arithmetic is fixed (fp32): lane
+ * l of 64 sums x[j] * x[j] over j = l, l + 64, ... (product and sum rounded separately), a xor butterfly (32, 16, 8, 4,
+ * 2, 1) gives s, t = sqrt(s + s), out[j] = x[j] / t, both correctly rounded.  Scaling a row by a power of two changes no
+ * output bit.
+ *
+ * cph_set_metric / cph_multi_set_metric / cph_parts_set_metric: on an empty handle only (nothing built, pending or
+ *     loaded); later calls are CPH_INVALID_ARGUMENT.  The multi and parts forms set every replica / part.
+ * rows in: cph_build, cph_multi_build, cph_parts_build and cph_add normalise the rows; what the index stores, returns
+ *     from cph_get_vectors, writes to files and replicates are the normalised rows.  A row without a direction -- all
+ *     zero, a NaN or Inf in it, a squared norm that overflows fp32 -- refuses the call with CPH_INVALID_ARGUMENT; the
+ *     message names the first such row (of the call's array; a partitioned index: the global row) and their count, and
+ *     the handle is as it was.  cph_compact passes its live rows through as they are.
+ * queries in: a query without a direction is searched as the zero vector -- every distance is then the stored squared
+ *     norm of the row, about 0.5 -- and no call refuses it: the device forms only enqueue and cannot.
+ * hooks: cph_encode_query, cph_entry_point, cph_exact_l2, cph_fastscan_block and the calibration hooks act on the
+ *     vector as given; they do not normalise.
+ * files: cph_save_native writes the metric as a trailing record (format 4, csrc/native_file.h) that older readers
+ *     refuse; an L2 index is written byte for byte as before and a file without the record is L2.  cph_load_native
+ *     refuses a file whose metric is not the handle's.  cph_save / cph_load (the reference's format, which has no place
+ *     for a metric) are refused on a cosine handle. */
+enum { CPH_METRIC_L2 = 0, CPH_METRIC_COSINE = 1 };
+int cph_set_metric(cph_index* h, int metric);
+int cph_get_metric(cph_index* h, int* metric);
+int cph_multi_set_metric(cph_multi* m, int metric);
+int cph_parts_set_metric(cph_parts* m, int metric);
+/* out[0] = launches of the normalisation kernel this handle has made (rows and queries), out[1] = bytes of normalised-
+ * query buffers its batch sets hold.  Both stay 0 on an L2 handle.  Counted on the host, not timed. */
+int cph_metric_stats(cph_index* h, uint64_t out[2]);
+/* Test hook: the kernel on host arrays x, out [n][dim] (out == x: in place; otherwise the device output starts as 0xA5
+ * bytes, so a slot the kernel left alone shows).  bad_count: rows without a direction (written as +0.0f); first_bad: the
+ * lowest such row, UINT64_MAX when there is none.  cph_host_normalize_rows is the host statement
+ * (csrc/host_normalize.h, no HIP call). */
+int cph_normalize_rows_hook(int device, const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad);
+int cph_host_normalize_rows(const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ from . import build as _build
 
 OK, INVALID_ARGUMENT, RUNTIME_ERROR, OUT_OF_MEMORY, NOT_IMPLEMENTED = range(5)
 IDS_INTERNAL, IDS_INPUT = 0, 1      # cph_set_result_ids
+METRIC_L2, METRIC_COSINE = 0, 1     # cph_set_metric
 
 # name -> (restype, argtypes); the list is checked against the header by tests/test_abi.py
 SYMBOLS = {
@@ -234,6 +235,15 @@ SYMBOLS = {
                                              C.c_void_p, C.POINTER(C.c_float)]),
     "cph_fastscan_stream_eval": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "cph_fastscan_stream_destroy": (C.c_int, [C.c_void_p]),
+    "cph_set_metric": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_get_metric": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "cph_multi_set_metric": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_parts_set_metric": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_metric_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_normalize_rows_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]),
+    "cph_host_normalize_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]),
 }
 
 _LIB = None

@@ -240,9 +240,19 @@ class CPIndex:
     (ascending distance, equal distances lower part first), made on devices[0].  One handle holds P times as much and
     the quadratic build does 1 / P of the work, on P devices; a query costs P searches.  Such an index speaks input
     rows only (result_ids is "input"), is saved and loaded with save_native / load_native (one file per part), and has
-    no index-wide hooks: `parts` lists the (lo, hi) bounds and `part(i)` is part i as a single-device CPIndex."""
+    no index-wide hooks: `parts` lists the (lo, hi) bounds and `part(i)` is part i as a single-device CPIndex.
 
-    def __init__(self, dim, bits=1, device=None, devices=None, partition=False):
+    `metric="cosine"` (default "l2"): distances are 1 - cos(q, x) instead of squared L2.  build() and add() store every
+    row as x / (sqrt(2) |x|), normalised on the device, and refuse (ValueError naming the first such row) a row without
+    a direction: all zero, NaN or Inf in it, or a norm that overflows float32.  Every search normalises its queries the
+    same way with one more kernel launch per batch, so the squared-L2 kernels report 1 - cos; a query without a
+    direction is searched as the zero vector (every distance about 0.5) and is not refused.  The hooks (encode_query,
+    entry_point, exact_l2, fastscan_block, calib_samples_debug) act on the vector as given.  The metric is fixed at
+    construction; save_native / load_native carry it, save / load (the reference's format) do not and are refused."""
+
+    _METRICS = {"l2": _lib.METRIC_L2, "cosine": _lib.METRIC_COSINE}
+
+    def __init__(self, dim, bits=1, device=None, devices=None, partition=False, metric="l2"):
         self._h = C.c_void_p()
         self._m = None               # cph_multi handle of a multi-device index
         self._p = None               # cph_parts handle of a partitioned index
@@ -254,6 +264,9 @@ class CPIndex:
         self._result_ids = "internal"
         self._exact_threshold = 0
         self._columns = {}           # attribute columns (set_column): name -> slot on the handle
+        if metric not in self._METRICS:
+            raise ValueError(f'metric must be "l2" or "cosine", not {metric!r}')
+        self._metric = metric
         if partition and (devices is None or device is not None):
             raise ValueError("partition=True needs devices=[...] (one part per listed device), not device")
         if devices is not None:
@@ -275,6 +288,8 @@ class CPIndex:
                     h = C.c_void_p()
                     _lib.check(_lib.lib().cph_parts_part(p, i, C.byref(h)))
                     self._part_handles.append(h)
+                if metric != "l2":
+                    _lib.check(_lib.lib().cph_parts_set_metric(p, self._METRICS[metric]))
                 return
             m = C.c_void_p()
             _lib.check(_lib.lib().cph_multi_create(int(dim), int(bits), (C.c_int * len(devs))(*devs), len(devs),
@@ -289,12 +304,31 @@ class CPIndex:
                 self._reps.append(h)
             self._h = self._reps[0]  # hooks, get_vectors, ...: replica 0
             self._next_dev = 0       # search_batch_device: alternates between the replicas on the queries' device
+            if metric != "l2":
+                _lib.check(_lib.lib().cph_multi_set_metric(m, self._METRICS[metric]))
             return
         if device is None:
             device = _default_device()
         self._device = int(device)
         self._devices = [self._device]
         _lib.check(_lib.lib().cph_create(int(dim), int(bits), int(device), C.byref(self._h)))
+        if metric != "l2":
+            _lib.check(_lib.lib().cph_set_metric(self._h, self._METRICS[metric]))
+
+    @property
+    def metric(self):
+        """"l2" or "cosine": fixed at construction."""
+        return self._metric
+
+    def metric_stats(self):
+        """(launches of the normalisation kernel, bytes of normalised-query buffers), summed over the replicas / parts:
+        both 0 on an "l2" index, which launches and allocates nothing for the metric.  Counted on the host."""
+        tot = [0, 0]
+        for h in self._replicas():
+            out = (C.c_uint64 * 2)()
+            _lib.check(_lib.lib().cph_metric_stats(h, out))
+            tot = [tot[0] + int(out[0]), tot[1] + int(out[1])]
+        return tuple(tot)
 
     def __del__(self):
         if getattr(self, "_owner", None) is not None:      # a borrowed part: the partitioned index destroys it
@@ -358,6 +392,7 @@ class CPIndex:
         v._p = None
         v._owner = self
         v._dim, v._bits = self._dim, self._bits
+        v._metric = self._metric
         v._device = self._devices[i]
         v._devices = [self._devices[i]]
         v._result_ids = "input" if self.is_finalized else "internal"
@@ -857,7 +892,8 @@ class CPIndex:
     def search(self, query, k=DEFAULT_K, filter=None, exact=False, label=None):
         """Single query, unpadded rows.  With `filter` (an IdFilter or anything make_filter accepts) only allowed ids
         are returned; that query runs as a batch of one through the filtered batch path.  `exact`: as in search_batch
-        (a batch of one as well).  `label`: one label value, instead of filter=label_filter(label)."""
+        (a batch of one as well).  `label`: one label value, instead of filter=label_filter(label).
+        metric="cosine": distances are 1 - cos(query, row)."""
         q = _as_f32(query)
         if q.ndim != 1 or q.shape[0] != self._dim:
             raise ValueError("query must be 1D and match index dimension")
@@ -897,7 +933,8 @@ class CPIndex:
         graph search, by the rules above); one call serves them all.
         `label` (needs set_labels; instead of filter=): one value = filter=label_filter(value); an integer array [n] =
         one label per query -- the filters of the distinct values are made in one device pass and the batch runs as
-        with filter_of.  The filters live for this call only."""
+        with filter_of.  The filters live for this call only.
+        metric="cosine": distances are 1 - cos(query, row); the queries are normalised on the device first."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
@@ -920,7 +957,8 @@ class CPIndex:
         A multi-device index runs the whole batch on one replica that lives on the queries' device (alternating
         between several there); the batch is not split.  `exact`: as in search_batch.  `filter_of` (with a sequence
         of filters): per-query filters as in search_batch; it is host data here too, a numpy array or a list.
-        `label`: as in search_batch (host data; its filters are freed on return, which waits for the batch)."""
+        `label`: as in search_batch (host data; its filters are freed on return, which waits for the batch).
+        metric="cosine": distances are 1 - cos; the normalisation is one more launch on `stream`, still enqueue-only."""
         import torch
         if queries.dim() != 2 or queries.shape[1] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, dim) array")
@@ -990,7 +1028,8 @@ class CPIndex:
         filter=filter) cut at the radius -- its entries with id >= 0 and dist < radius[i], in row order.
         A multi-device index shards the queries like search_batch(exact=True); the bytes are those of one device.
         Per-query filters (filter_of) and a partitioned index are refused (use part(i).range_search).
-        `label`: one label value, instead of filter=label_filter(label)."""
+        `label`: one label value, instead of filter=label_filter(label).
+        metric="cosine": `radius` and the distances are in 1 - cos (0 = same direction, 1 = orthogonal, 2 = opposite)."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
@@ -1146,7 +1185,8 @@ class CPIndex:
         (a few keys own most near rows); the groups returned are the best of those candidates.
         `label`: as in search_batch (it restricts the rows; the groups still come from the label column or `keys`).
         A multi-device index shards the queries like search_batch; the bytes are those of one device.  A partitioned
-        index is refused (use part(i).search_grouped)."""
+        index is refused (use part(i).search_grouped).
+        metric="cosine": distances are 1 - cos(query, row)."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
@@ -1275,7 +1315,8 @@ class CPIndex:
         C = min(1024, max(64, 4 * k)): a policy, not a measured optimum, in ONE pass (nothing is re-run at a larger C).
         last_search_stats() afterwards reports the underlying search only: the pair distances of the re-ranking are not
         added to exact_l2.  A multi-device index shards the queries like search_batch; the bytes are those of one
-        device.  A partitioned index is refused (use part(i).search_diverse)."""
+        device.  A partitioned index is refused (use part(i).search_diverse).
+        metric="cosine": dist and gap are 1 - cos (to the query, and between stored rows); the formula is unchanged."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
             raise ValueError("queries must be a (n, dim) array")
@@ -1435,7 +1476,9 @@ class CPIndex:
         grows -- compact() folds the tail into a new graph.  Filters made before the call no longer fit (size changed).
         While tail_size > 0: save, save_native and set_row_map raise (compact() first), graph-routed searches take
         k <= 1024, and per-query filters serve scanned queries only (NotImplementedError otherwise).  Waits for the
-        batches in flight.  Not available on devices=[...] indexes, their replicas or parts."""
+        batches in flight.  Not available on devices=[...] indexes, their replicas or parts.
+        metric="cosine": the rows are normalised like those of build(); a row without a direction (zero, NaN, Inf)
+        raises ValueError naming it and adds nothing."""
         if self._m is not None or self._p is not None or self._owner is not None:
             raise NotImplementedError("add is not available on a multi-device or partitioned index, its replicas or parts")
         v = _as_f32(vectors)
@@ -1462,6 +1505,8 @@ class CPIndex:
 
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):
+        """Reference-format (v2) file.  metric="cosine": refused (ValueError) -- the format cannot carry the metric and a
+        reader would search the rows as squared-L2 data; use save_native."""
         if self._p is not None:
             raise RuntimeError("a partitioned index has no reference-format file (that format holds one graph and no row "
                                "map): use save_native")
@@ -1471,7 +1516,8 @@ class CPIndex:
         _lib.check(_lib.lib().cph_save(self._h, str(path).encode()))
 
     def load(self, path):
-        """Reference-format (v2) file: it holds no row map, so the index comes back with result_ids "internal"."""
+        """Reference-format (v2) file: it holds no row map, so the index comes back with result_ids "internal".
+        metric="cosine": refused (ValueError) -- nobody normalised the file's rows; use load_native."""
         if self._p is not None:
             raise RuntimeError("a partitioned index cannot load a reference-format file (that format holds one graph and "
                                "no row map): use load_native")
@@ -1691,7 +1737,7 @@ class CPIndex:
 
     def get_vectors(self, first=0, count=None):
         """Stored vectors of internal ids [first, first+count) as float32 (count, dim) (internal ids also when
-        result_ids is "input")."""
+        result_ids is "input").  metric="cosine": the rows as stored, x / (sqrt(2) |x|), not the rows given to build()."""
         self._no_parts("get_vectors")
         if count is None:
             count = self.size - first

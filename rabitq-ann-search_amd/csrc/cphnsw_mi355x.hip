@@ -39,6 +39,7 @@
 #include "device_tail.h"
 #include "device_diverse.h"
 #include "device_group.h"
+#include "device_normalize.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -160,6 +161,8 @@ struct BatchSet {
     DevBuf<uint32_t> d_redo2;
     hipEvent_t ev_tab = nullptr;
     bool tab_used = false;
+    // cosine metric (metric_queries): the batch's normalised queries; an L2 handle never allocates it
+    DevBuf<float> m_queries;
 };
 constexpr int kMaxBatchSets = 4;
 
@@ -233,6 +236,11 @@ struct cph_index {
     // save_native and get_vectors refuse it too)
     bool borrowed = false;
     bool host_less = false;
+    // the metric (cph_set_metric, on an empty handle only).  Cosine: rows are normalised to squared norm 1/2 on the way in
+    // (build, add) and queries on the way into every search (metric_queries), so the L2 kernels report 1 - cos.
+    // metric_launches counts the launches of the normalisation kernel this handle made (cph_metric_stats): 0 under L2.
+    uint32_t metric = CPH_METRIC_L2;
+    uint64_t metric_launches = 0;
     std::vector<float> pending;        // vectors handed to build()
     uint64_t pending_n = 0;
     HostIndex host;
@@ -497,6 +505,7 @@ void release_scratch(BatchSet& s) {
     s.d_bitmaps.release(); s.d_logids.release(); s.d_beam.release(); s.d_beam_tail.release();
     s.r_bitmaps.release(); s.r_logids.release(); s.r_beam.release(); s.r_beam_tail.release();
     s.x_qpad.release(); s.x_qnorm.release(); s.x_pools.release(); s.x_counts.release();
+    s.m_queries.release();
     s.slots = 0; s.cap = 0; s.r_slots = 0;
 }
 
@@ -741,6 +750,50 @@ const float* upload_queries(cph_index* h, BatchSet& s, const float* queries, uin
     }
     HIP_CHECK(hipMemcpyAsync(s.d_queries_raw.p, queries, nq * h->dim * 4, hipMemcpyHostToDevice, st));
     return s.d_queries_raw.p;
+}
+
+// The queries a batch's kernels read: d_raw_q itself under L2 (no launch, no allocation, no event); under cosine the
+// rows normalised to squared norm 1/2 (device_normalize.h) into the set's buffer, on the batch's stream.  Called once per
+// batch, before the first reader of the raw queries; d_raw_q may be pinned host memory (the copy-free routes).  A bad
+// query (zero, NaN, Inf) searches as the zero vector: the enqueue-only device form cannot refuse, so no form does.
+const float* metric_queries(cph_index* h, BatchSet& s, const float* d_raw_q, uint64_t nq, hipStream_t st) {
+    if (h->metric == CPH_METRIC_L2 || !d_raw_q || nq == 0) return d_raw_q;
+    if (s.m_queries.n < nq * h->dim) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
+        s.m_queries.alloc(nq * h->dim);
+    }
+    normalize_rows(d_raw_q, s.m_queries.p, nq, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
+    ++h->metric_launches;
+    return s.m_queries.p;
+}
+
+// Rows on their way into a cosine index (cph_build, cph_add): normalised on the device, in chunks, into `out` ([n][dim],
+// host).  A bad row refuses the call -- nothing of the handle has changed by then; row_base: the number of vectors[0] in
+// the caller's numbering (a partitioned index reports global rows).
+void normalize_rows_in(cph_index* h, const float* vectors, uint64_t n, uint64_t row_base, std::vector<float>& out) {
+    h->use_device();
+    const uint64_t dim = h->dim, chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, ((uint64_t)256 << 20) / (dim * 4)));
+    out.resize(n * dim);
+    DevBuf<float> d_x(chunk * dim);
+    DevBuf<unsigned long long> d_bad(2);
+    const unsigned long long init[2] = {0ull, kNoBadRow};
+    unsigned long long bad[2] = {0ull, kNoBadRow}, total = 0, first = kNoBadRow;
+    hipStream_t st = own_stream(h);
+    for (uint64_t base = 0; base < n; base += chunk) {
+        const uint64_t c = std::min(chunk, n - base);
+        HIP_CHECK(hipMemcpyAsync(d_bad.p, init, 16, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_x.p, vectors + base * dim, c * dim * 4, hipMemcpyHostToDevice, st));
+        normalize_rows(d_x.p, d_x.p, c, (uint32_t)dim, (uint32_t)dim, (uint32_t)dim, d_bad.p, d_bad.p + 1, st);
+        ++h->metric_launches;
+        HIP_CHECK(hipMemcpyAsync(out.data() + base * dim, d_x.p, c * dim * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(bad, d_bad.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (bad[0] && first == kNoBadRow) first = row_base + base + bad[1];
+        total += bad[0];
+    }
+    if (total)
+        throw InvalidArg("cosine metric: row " + std::to_string(first) + " has no direction (a zero row, NaN, Inf or an overflowing norm; " +
+                         std::to_string(total) + " such row" + (total == 1 ? "" : "s") + " in this call): nothing was changed");
 }
 
 // (Re)allocates the per-slot scratch of a set; the set must be idle.
@@ -1575,6 +1628,7 @@ void search_batch_locked(cph_index* h, const BatchCall& c) {
         hipStream_t st = c.on_device ? c.stream : own_stream(h);
         BatchSet& s = next_set(h, st);
         auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
+            d_q = metric_queries(h, s, d_q, n, st);
             enqueue_filters(h, s, d_q, (uint32_t)n, (uint32_t)k, lf.filters, lf.F, lf.filter_of, g, d_ids, d_dist, st);
         };
         if (c.on_device) enqueue(c.q, c.ids, c.dist);
@@ -1593,6 +1647,7 @@ void search_batch_locked(cph_index* h, const BatchCall& c) {
     BatchSet& s = next_set(h, st);
     const bool empty = f && f->popcount == 0;     // (never exact: takes_exact)
     auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
+        if (!empty) d_q = metric_queries(h, s, d_q, n, st);
         if (exact) return enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
         if (!empty) stage_queries(h, s, d_q, n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f, d_q);
@@ -1604,9 +1659,10 @@ void search_batch_locked(cph_index* h, const BatchCall& c) {
         if (s.pin_io_bytes < io.need && s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
         grow_pinned(s.pin_io, s.pin_io_dev, s.pin_io_bytes, io.need);
         std::memcpy(io.queries(s.pin_io), c.q, n * h->dim * sizeof(float));
-        stage_queries(h, s, io.queries(s.pin_io_dev), n, st);
+        const float* d_q = metric_queries(h, s, io.queries(s.pin_io_dev), n, st);    // (cosine: pinned rows in, HBM rows out)
+        stage_queries(h, s, d_q, n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
-                       DoneFlags(), f, io.queries(s.pin_io_dev));
+                       DoneFlags(), f, d_q);
         HIP_CHECK(hipStreamSynchronize(st));
         std::memcpy(c.ids, io.ids(s.pin_io), n * k * 8);
         std::memcpy(c.dist, io.dist(s.pin_io), n * k * 4);
@@ -1638,7 +1694,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 109; }
+int cph_version(void) { return 110; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1750,8 +1806,16 @@ static void refuse_tail_file(const cph_index* h) {
                                  " here) and a file without them would lose them: compact() the index first.");
 }
 
+// The reference's file format has no place for the metric: a file written from a cosine handle would be searched as L2
+// by whoever loads it, and a file loaded into one holds rows nobody normalised.
+static void refuse_metric_file(const cph_index* h, const char* what) {
+    if (h->metric != CPH_METRIC_L2)
+        throw InvalidArg(std::string(what) + ": the reference's file format cannot carry the cosine metric: use save_native / load_native");
+}
+
 static void load_v2(cph_index* h, const char* path) {
     std::lock_guard<std::mutex> lk(h->mu);
+    refuse_metric_file(h, "load");
     HostIndex t;
     t.load(path, h->D, h->bits, h->dim);        // a file that fails to parse leaves the handle as it was
     begin_device_swap(h);
@@ -1781,6 +1845,7 @@ int cph_save(cph_index* h, const char* path) {
         refuse_host_less(h, "cph_save");
         std::lock_guard<std::mutex> lk(h->mu);
         if (!h->finalized) throw std::runtime_error("Index must be finalized before saving.");
+        refuse_metric_file(h, "save");
         if (h->host.n_removed != 0)
             throw std::runtime_error("The reference format cannot carry removed rows (" + std::to_string(h->host.n_removed) +
                                      " here) and a file without them would bring them back: compact() the index first, or use save_native.");
@@ -1809,7 +1874,7 @@ int cph_save_native(cph_index* h, const char* path) {
             for (size_t v = 0; v < n; ++v) std::memcpy(&own[v * own_stride], &hi.search_data[v * hi.RL.vertex_bytes], own_stride);
             own_p = own.data();
         }
-        write_native(path, hi, (uint32_t)stride, own_p, (uint32_t)own_stride, blocks.data());
+        write_native(path, hi, (uint32_t)stride, own_p, (uint32_t)own_stride, blocks.data(), h->metric);
     });
 }
 
@@ -1823,7 +1888,11 @@ struct NativeLoaded {
 };
 
 static void read_native_for(const cph_index* h, const char* path, NativeLoaded& out) {
-    out.nh = read_native(path, h->D, h->bits, h->dim, out.t, out.map);   // validates everything it maps
+    uint32_t metric = CPH_METRIC_L2;
+    out.nh = read_native(path, h->D, h->bits, h->dim, out.t, out.map, &metric);   // validates everything it maps
+    if (metric != h->metric)
+        throw InvalidArg(std::string("the file holds ") + (metric == CPH_METRIC_COSINE ? "cosine" : "l2") + " rows and this handle's metric is " +
+                         (h->metric == CPH_METRIC_COSINE ? "cosine" : "l2") + ": load it into an index created with the file's metric");
 }
 
 // The handle gives up its index for the one in `in` (which is consumed).
@@ -1893,11 +1962,17 @@ static void require_finalizable(uint64_t n) {
     if (n >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
 }
 
-static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
+// The one funnel behind cph_build, cph_multi_build, cph_parts_build and cph_compact.  as_given: the rows are stored as
+// they are -- an L2 handle's, and under cosine the rows that are normalised already (compact's live rows: a second pass
+// over a nearly-unit row changes bits; a partitioned build's, normalised in one go for the global row numbers).
+// Otherwise a cosine handle normalises them first, and a bad row refuses the call with the handle as it was.
+static void build_pending(cph_index* h, const float* vectors, uint64_t n, bool as_given = false) {
     std::lock_guard<std::mutex> lk(h->mu);
     // api/hnsw_index.hpp:93-120: build() replaces any previous state
     require_buildable(n);
     if (!vectors) throw InvalidArg("null vectors");
+    std::vector<float> unit;
+    if (h->metric != CPH_METRIC_L2 && !as_given) normalize_rows_in(h, vectors, n, 0, unit);
     h->use_device();
     quiesce(h);
     h->host = HostIndex();
@@ -1909,7 +1984,8 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n) {
     sync_labels(h);
     sync_removed(h);
     for (auto& s : h->sets) release_scratch(s);
-    h->pending.assign(vectors, vectors + n * h->dim);
+    if (!unit.empty()) h->pending = std::move(unit);
+    else h->pending.assign(vectors, vectors + n * h->dim);
     h->pending_n = n;
     h->needs_build = true;
 }
@@ -2534,6 +2610,14 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
         if (!q_dev) {
             r->s->d_q.alloc(n * h->dim);
             HIP_CHECK(hipMemcpyAsync(r->s->d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
+            d_q = r->s->d_q.p;
+        }
+        if (exact && h->metric != CPH_METRIC_L2) {
+            // cosine: the scan reads normalised queries (the graph route's are normalised by its own search_batch_locked);
+            // into the call's own buffer -- in place when the queries were uploaded there
+            r->s->d_q.alloc(n * h->dim);
+            normalize_rows(d_q, r->s->d_q.p, n, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
+            ++h->metric_launches;
             d_q = r->s->d_q.p;
         }
         uint64_t n_cnt = n;
@@ -3287,7 +3371,8 @@ static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const s
     ls.cur_n = n; ls.cur_k = kk;
     BatchSet& s = h->sets[kMaxBatchSets + (&ls - h->leaders)];         // the slot's own set: its launches are ordered by its stream
     init_set(s);
-    stage_queries(h, s, io.queries(ls.pin_dev), n, ls.stream);                                 // the encoder reads the queries over PCIe
+    const float* d_q = metric_queries(h, s, io.queries(ls.pin_dev), n, ls.stream);             // (cosine: normalised into the slot's set)
+    stage_queries(h, s, d_q, n, ls.stream);                                                    // the encoder reads the queries over PCIe
     DoneFlags done;
     done.flags = reinterpret_cast<uint32_t*>(ls.pin_dev);
     done.seq = ls.seq;
@@ -3296,7 +3381,7 @@ static void launch_search_group(cph_index* h, cph_index::LeaderSlot& ls, const s
     // (... and so does a handle with added rows; a launch gathered during the first cph_add scans and folds the tail)
     require_tail_k(h, kk);
     enqueue_search(h, s, (uint32_t)n, (uint32_t)kk, io.ids(ls.pin_dev), io.dist(ls.pin_dev), ls.stream, io.counts(ls.pin_dev), done,
-                   h->live.get(), io.queries(ls.pin_dev));   // ... the search writes the results back
+                   h->live.get(), d_q);   // ... the search writes the results back
     CPH_TR(0, 1); CPH_TR(1, n); CPH_TR(2, t1 - t0); CPH_TR(3, now_ns() - t1);
 }
 
@@ -4560,19 +4645,34 @@ int cph_parts_destroy(cph_parts* m) {
     });
 }
 
+}  // extern "C"
+
+// cph_parts_build; as_given: the rows are stored as they are (cph_parts_compact's live rows under cosine, build_pending).
+static void parts_build(cph_parts* m, const float* vectors, uint64_t n, bool as_given) {
+    if (!m) throw InvalidArg("null handle");
+    const uint32_t P = (uint32_t)m->parts.size();
+    if (n < kMinPartRows * P)
+        throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
+                         std::to_string(n) + " rows for " + std::to_string(P) + " parts");
+    if (!vectors) throw InvalidArg("null vectors");
+    std::unique_lock<std::shared_mutex> lk(m->life);
+    const std::vector<uint64_t> b = all_part_bounds(n, P);
+    // cosine: every row is normalised before any part gives up its index -- a bad row refuses the whole call, by its
+    // global number
+    std::vector<float> unit;
+    if (m->parts[0]->metric != CPH_METRIC_L2 && !as_given) {
+        std::lock_guard<std::mutex> g(m->parts[0]->mu);
+        normalize_rows_in(m->parts[0], vectors, n, 0, unit);
+        vectors = unit.data();
+    }
+    for (uint32_t p = 0; p < P; ++p) build_pending(m->parts[p], vectors + b[p] * m->parts[p]->dim, b[p + 1] - b[p], true);
+    m->bounds = b;
+}
+
+extern "C" {
+
 int cph_parts_build(cph_parts* m, const float* vectors, uint64_t n) {
-    return guarded([&] {
-        if (!m) throw InvalidArg("null handle");
-        const uint32_t P = (uint32_t)m->parts.size();
-        if (n < kMinPartRows * P)
-            throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
-                             std::to_string(n) + " rows for " + std::to_string(P) + " parts");
-        if (!vectors) throw InvalidArg("null vectors");
-        std::unique_lock<std::shared_mutex> lk(m->life);
-        const std::vector<uint64_t> b = all_part_bounds(n, P);
-        for (uint32_t p = 0; p < P; ++p) build_pending(m->parts[p], vectors + b[p] * m->parts[p]->dim, b[p + 1] - b[p]);
-        m->bounds = b;
-    });
+    return guarded([&] { parts_build(m, vectors, n, false); });
 }
 
 int cph_parts_finalize(cph_parts* m) {
@@ -4953,7 +5053,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
         gather_live(h, vecs, map.data(), was_input, 0, &labs);
         std::copy(map.begin(), map.end(), old_to_new);
     }
-    build_pending(h, vecs.data(), live);
+    build_pending(h, vecs.data(), live, true);   // (cosine: the live rows are unit-half rows already)
     std::vector<float>().swap(vecs);
     finalize_build(h);
     if (was_input) set_result_ids(h, CPH_IDS_INPUT);
@@ -5032,6 +5132,11 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
         throw InvalidArg("the index holds attribute columns and the added rows would have no values in them: drop the columns "
                          "(cph_set_column with NULL), add, then set them again at the new size");
     if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
+    std::vector<float> unit;                     // cosine: the rows as the index stores them (a bad row refuses the call here)
+    if (h->metric != CPH_METRIC_L2) {
+        normalize_rows_in(h, vectors, m, 0, unit);
+        vectors = unit.data();
+    }
     h->use_device();
     quiesce(h);                                  // a batch in flight reads the arrays that may move
     HostIndex& hi = h->host;
@@ -5278,7 +5383,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
                                  std::to_string(live) + " rows for " + std::to_string(P) + " parts");
             std::copy(map.begin(), map.end(), old_to_new);
         }
-        check_rc(cph_parts_build(m, vecs.data(), live));      // the live rows, cut again by cph_host_part_bounds
+        parts_build(m, vecs.data(), live, true);              // the live rows, cut again by cph_host_part_bounds
         std::vector<float>().swap(vecs);
         check_rc(cph_parts_finalize(m));
         if (labs[0].size() == live) check_rc(cph_parts_set_labels(m, labs[0].data(), live));     // cut again at the new bounds
@@ -6016,6 +6121,115 @@ int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uin
         check_diverse_rows_args(ids, dist, n, candidates, n_ids, k, lam, out_ids, out_dist, out_gap);
         diverse_rows_host(ids, dist, n, (uint32_t)candidates, raw, norm_sq, n_ids, (uint32_t)D, rows, (uint32_t)k, lam, out_ids, out_dist,
                           out_gap);
+    });
+}
+
+}  // extern "C"
+
+// ---- the metric (cph_set_metric; device_normalize.h) -------------------------------------------------------------------
+static const char* metric_name(uint32_t metric) { return metric == CPH_METRIC_COSINE ? "cosine" : "l2"; }
+
+// Settable on an empty handle only: nothing built, pending or loaded -- the rows of an index are stored for one metric.
+static void set_metric(cph_index* h, int metric) {
+    if (metric != CPH_METRIC_L2 && metric != CPH_METRIC_COSINE)
+        throw InvalidArg("unknown metric " + std::to_string(metric) + " (CPH_METRIC_L2 = 0, CPH_METRIC_COSINE = 1)");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->finalized || h->needs_build || h->host.n != 0)
+        throw InvalidArg(std::string("the metric is set on an empty handle, before build or load: this one holds ") + metric_name(h->metric) +
+                         " rows");
+    h->metric = (uint32_t)metric;
+}
+
+static void check_normalize_args(const float* x, uint64_t n, uint64_t dim, const float* out) {
+    if (n && (!x || !out)) throw InvalidArg("null argument");
+    if (dim < 1 || dim > 0xFFFFFFFFull) throw InvalidArg("normalize rows: dim out of range");
+}
+
+extern "C" {
+
+int cph_set_metric(cph_index* h, int metric) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_metric");
+        set_metric(h, metric);
+    });
+}
+
+int cph_get_metric(cph_index* h, int* metric) {
+    return guarded([&] {
+        if (!h || !metric) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *metric = (int)h->metric;
+    });
+}
+
+int cph_multi_set_metric(cph_multi* m, int metric) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        set_metric(m->reps[0], metric);                      // (replica 0 holds the state that decides; the others follow it)
+        for (size_t i = 1; i < m->reps.size(); ++i) {
+            std::lock_guard<std::mutex> g(m->reps[i]->mu);
+            m->reps[i]->metric = (uint32_t)metric;
+        }
+    });
+}
+
+int cph_parts_set_metric(cph_parts* m, int metric) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
+            std::lock_guard<std::mutex> g(h->mu);
+            if (h->finalized || h->needs_build || h->host.n != 0)
+                throw InvalidArg("the metric is set on an empty handle, before build or load");
+        }
+        for (cph_index* h : m->parts) set_metric(h, metric);
+    });
+}
+
+int cph_metric_stats(cph_index* h, uint64_t out[2]) {
+    return guarded([&] {
+        if (!h || !out) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        out[0] = h->metric_launches;
+        out[1] = 0;
+        for (const BatchSet& s : h->sets) out[1] += s.m_queries.n * sizeof(float);
+    });
+}
+
+int cph_normalize_rows_hook(int device, const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad) {
+    return guarded([&] {
+        check_normalize_args(x, n, dim, out);
+        if (bad_count) *bad_count = 0;
+        if (first_bad) *first_bad = kNoBadRow;
+        if (n == 0) return;
+        if (n > 0xFFFFFFFFull / dim) throw InvalidArg("normalize rows: too many elements for the hook");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t cells = (size_t)n * dim;
+        const bool in_place = out == x;
+        DevBuf<float> d_in(cells), d_out(in_place ? 0 : cells);
+        DevBuf<unsigned long long> d_bad(2);
+        const unsigned long long init[2] = {0ull, kNoBadRow};
+        unsigned long long bad[2] = {0ull, kNoBadRow};
+        HIP_CHECK(hipMemcpy(d_in.p, x, cells * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_bad.p, init, 16, hipMemcpyHostToDevice));
+        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
+        if (!in_place) HIP_CHECK(hipMemset(d_out.p, 0xA5, cells * 4));
+        float* d_o = in_place ? d_in.p : d_out.p;
+        normalize_rows(d_in.p, d_o, n, (uint32_t)dim, (uint32_t)dim, (uint32_t)dim, d_bad.p, d_bad.p + 1, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_o, cells * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(bad, d_bad.p, 16, hipMemcpyDeviceToHost));
+        if (bad_count) *bad_count = bad[0];
+        if (first_bad) *first_bad = bad[1];
+    });
+}
+
+int cph_host_normalize_rows(const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad) {
+    return guarded([&] {
+        check_normalize_args(x, n, dim, out);
+        normalize_rows_host(x, n, (uint32_t)dim, out, bad_count, first_bad);
     });
 }
 

@@ -32,6 +32,13 @@
 // it refuses the file whether or not a row map follows.  (NativeHeader::version stays 1: the sections it names are
 // unchanged, and one way of refusing is enough.)  The section sits behind `rows`, in front of `own`.
 //
+// Format 4 = any of the above plus a NativeMetricExt record: the rows were stored for a metric other than squared L2
+// (cosine: every row scaled to squared norm 1/2).  An L2 index is written without the record, byte for byte as before,
+// and a file without it is L2.  Like format 3 it must be refused by older readers, which would search cosine rows as L2
+// data: the record is 16 bytes, starts with its own magic and comes FIRST behind the upper layers, so an older reader
+// finds there 16, 40, 48 or 72 bytes that do not start with a magic it knows -- never nothing, and never 24 bytes that
+// start with the rows magic or 32 / 56 that start with the removed-rows magic.  It names no section.
+//
 // load = mmap + two host-to-device copies straight out of the mapping; the vectors stay mapped for
 // cph_get_vectors / save.  A v2 file can always be regenerated from a native one (cph_save after
 // cph_load_native): the reference-layout blocks are re-derived from the device blocks.
@@ -60,6 +67,9 @@ constexpr uint32_t kNativeVersionRows = 2;    // NativeRowsExt::version: the for
 constexpr uint64_t kNativeRowsMagic = 0x53574F5249485043ULL;   // "CPHIROWS"
 constexpr uint32_t kNativeVersionRemoved = 3; // NativeRemovedExt::version: the format of a file with removed rows
 constexpr uint64_t kNativeRemovedMagic = 0x44564D5249485043ULL;   // "CPHIRMVD"
+constexpr uint32_t kNativeVersionMetric = 4;  // NativeMetricExt::version: the format of a file whose rows are not squared-L2 rows
+constexpr uint64_t kNativeMetricMagic = 0x5254454D49485043ULL;    // "CPHIMETR"
+constexpr uint32_t kNativeMetricL2 = 0, kNativeMetricCosine = 1;  // (CPH_METRIC_L2, CPH_METRIC_COSINE)
 
 struct NativeHeader {
     uint64_t magic;
@@ -92,6 +102,13 @@ struct NativeRemovedExt {     // format 3: behind the upper layers, in front of 
 };
 static_assert(sizeof(NativeRemovedExt) != sizeof(NativeRowsExt) && sizeof(NativeRemovedExt) == 32, "a format-2 reader must refuse the record");
 
+struct NativeMetricExt {      // format 4: behind the upper layers, in front of every other record
+    uint64_t magic;           // kNativeMetricMagic
+    uint32_t version;         // kNativeVersionMetric
+    uint32_t metric;          // kNativeMetricCosine (0, squared L2, is never written: such a file has no record)
+};
+static_assert(sizeof(NativeMetricExt) == 16, "older readers must refuse the record by its size");
+
 struct NativeMapping {
     void* base = nullptr;
     size_t bytes = 0;
@@ -115,7 +132,7 @@ inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // `own` = [n][own_stride] vertex headers, `blocks` = [n][stride] device blocks (both host pointers).
 inline void write_native(const std::string& path, const HostIndex& hi, uint32_t stride, const uint8_t* own,
-                         uint32_t own_stride, const uint8_t* blocks) {
+                         uint32_t own_stride, const uint8_t* blocks, uint32_t metric = kNativeMetricL2) {
     std::vector<uint8_t> small;
     auto put = [&](const void* p, size_t b) { const uint8_t* q = static_cast<const uint8_t*>(p); small.insert(small.end(), q, q + b); };
     put(hi.calib, 248);
@@ -144,9 +161,16 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
         if (pc != hi.n_removed || ((hi.n & 31) && (hi.removed.back() >> (hi.n & 31))))
             throw std::runtime_error("removed-row bitmap does not match its count");
     }
+    if (metric != kNativeMetricL2 && metric != kNativeMetricCosine) throw std::runtime_error("unknown metric");
+    const bool with_metric = metric != kNativeMetricL2;
     uint64_t rows_off = 0, removed_off = 0;
-    const uint64_t records = (with_rows ? sizeof(NativeRowsExt) : 0) + (with_removed ? sizeof(NativeRemovedExt) : 0);
+    const uint64_t records = (with_rows ? sizeof(NativeRowsExt) : 0) + (with_removed ? sizeof(NativeRemovedExt) : 0) +
+                             (with_metric ? sizeof(NativeMetricExt) : 0);
     uint64_t sections_end = sizeof(NativeHeader) + small.size() + records;
+    if (with_metric) {
+        const NativeMetricExt ext{kNativeMetricMagic, kNativeVersionMetric, metric};
+        put(&ext, sizeof(ext));
+    }
     if (with_rows) {
         rows_off = align_up(sections_end, 4096);
         sections_end = rows_off + hi.n * 4;
@@ -199,9 +223,10 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
 
 // Maps the file and fills everything of `hi` except raw / search_data (raw_view points into the mapping); hi.rows is
 // the file's row map (format 2) or empty (format 1), hi.removed / hi.n_removed the file's removed rows (format 3) or
-// none; the returned header's `version` is that format.
+// none; the returned header's `version` is that format.  *metric: the file's metric (format 4; L2 without the record) --
+// a caller that does not ask cannot hold anything but L2 rows, and is refused a file of another metric.
 inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t expect_bw, size_t expect_dim, HostIndex& hi,
-                                NativeMapping& map) {
+                                NativeMapping& map, uint32_t* metric = nullptr) {
     const int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw std::runtime_error("Cannot open file for reading: " + path);
     struct stat st{};
@@ -276,10 +301,26 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
     }
     // What follows the upper layers: nothing (format 1), the row-map record (format 2), or the removed-rows record with
     // or without the row-map record behind it (format 3); anything else is damage.
-    bool with_rows = false, with_removed = false;
+    // In front of them the metric record (format 4), told by its magic.
+    bool with_rows = false, with_removed = false, with_metric = false;
     NativeRowsExt ext{};
     NativeRemovedExt rext{};
+    NativeMetricExt mext{};
     const uint64_t rm_words = (h.n + 31) / 32;
+    if ((size_t)(end - p) >= sizeof(mext)) {
+        uint64_t magic = 0;
+        std::memcpy(&magic, p, 8);
+        if (magic == kNativeMetricMagic) {
+            get(&mext, sizeof(mext));
+            if (mext.version != kNativeVersionMetric)
+                throw std::runtime_error("Unsupported native index file version: " + std::to_string(mext.version));
+            if (mext.metric != kNativeMetricCosine) throw std::runtime_error("Corrupt index: unknown metric " + std::to_string(mext.metric));
+            with_metric = true;
+        }
+    }
+    if (with_metric && !metric)
+        throw std::runtime_error("The file holds cosine rows: it loads into an index created with the cosine metric only.");
+    if (metric) *metric = with_metric ? mext.metric : kNativeMetricL2;
     if ((size_t)(end - p) == sizeof(rext) || (size_t)(end - p) == sizeof(rext) + sizeof(ext)) {
         typedef unsigned __int128 u128;
         get(&rext, sizeof(rext));
@@ -309,6 +350,7 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
         h.version = kNativeVersionRows;      // the format, for the caller (the file's field stays 1, see the top)
     }
     if (with_removed) h.version = kNativeVersionRemoved;
+    if (with_metric) h.version = kNativeVersionMetric;
     // The device blocks are handed to the GPU as they are: a neighbour id the search kernel would chase must be a
     // vertex (the v2 loader's validate() makes the same promise), unused slots must carry the invalid marker the
     // kernels rely on instead of `count`, and the repeated-id flag is recomputed rather than believed.

@@ -366,6 +366,72 @@ int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uin
                           uint64_t n_ids, uint64_t D, const uint32_t* rows, uint64_t k, float lam, int64_t* out_ids, float* out_dist,
                           float* out_gap);
 
+/* ---- multi-vector search (late interaction, MaxSim) ---------------------------------------- */
+/* A query is `tokens` (T) vectors, of which the first n_tokens[i] (L, 1 <= L <= T; n_tokens == NULL: all T) are live:
+ * the token embeddings of a ColBERT- or ColPali-style retriever.  The answer is the k keys (documents; key_of as for
+ * grouped search: the label column, or a cph_group_keys object) that minimise the sum, over the live tokens, of the
+ * token's best row of the key.  Under CPH_METRIC_COSINE a distance is 1 - cos, so the MaxSim similarity of a returned key
+ * is n_tokens - score.
+ *
+ * queries is [n][T][dim]: the n * T token rows are ONE ordinary batch, searched at k = candidates (C) exactly as the rows
+ * of a grouped search are -- same filters, exact flag, exact threshold, removed rows, tail, metric, routing and refusals;
+ * filter_of[i] serves all T tokens of query i (the entry expands it).  The tokens t >= L are searched with the batch and
+ * then ignored entirely.  The statement over the T candidate rows of one query (csrc/host_maxsim.h is its host form,
+ * tests/maxsim_model.py its numpy form); an entry is valid when 0 <= id < cph_size, and everything but the sum and the
+ * final order is defined by position, so that no float comparison is ambiguous:
+ *   - floor_t = the distance of the last valid entry of row t, +0.0f when the row has none;
+ *   - for a key that occurs in a valid entry of a live row, pos_t(key) = the lowest position of row t whose entry has the
+ *     key, if any; term_t(key) = the distance there, else floor_t; hits(key) = the live t that have a pos_t(key);
+ *   - score(key): s = +0.0f; for t = 0 .. L-1: s = s + term_t(key) -- float32, in that order;
+ *   - the min(k, distinct keys) keys with the smallest (score as a float value, key as a signed int32), in that order.
+ * Outputs per query: out_keys [k] int32, out_score [k] float32, out_hits [k] int32, out_rows [k][T] int64 = the id at
+ * pos_t(key) (internal ids; under CPH_IDS_INPUT input rows, translated where it is written), -1 where token t has no row
+ * of the key or t >= L; out_found int32 = the keys returned.  Padding: key 0, score FLT_MAX, hits 0, rows -1.  Every int32
+ * value is an ordinary key.
+ *
+ * What the score means: floor_t is the C-th distance of token t, and a row of the key that the search did not return for
+ * t is no closer than that.  With exact != 0, score(key) is therefore a LOWER BOUND of the true
+ * sum_t min_{row of key, allowed} dist(q_t, row) (in float32 too: float addition is monotone), and EQUAL to it where
+ * hits == L: hits is this call's counterpart of `complete` in cph_search_grouped.  With exact != 0 and C at least the
+ * number of allowed rows the answer is the exact MaxSim top-k.  Nothing is re-run at a larger C, and missing (key, token)
+ * pairs are not re-scored against the stored vectors.
+ *
+ * Limits: 1 <= T <= 64, 1 <= C <= 1024, T * C <= 8192, 1 <= k <= 1024, n * T <= 2^31 - 1, 1 <= n_tokens[i] <= T (host
+ * array in both forms); anything else is CPH_INVALID_ARGUMENT with a message that names the limit, as are NULL pointers,
+ * no label column and no keys object, a keys object of another size, device or index.
+ *
+ * The work: as for grouped search -- under the handle mutex the search runs at k = C into the same scratch rows (n * T of
+ * them; four sets in rotation, only ever grown), in internal ids; then ONE launch of maxsim_rows_kernel
+ * (csrc/device_maxsim.h), one workgroup per query, on the same stream writes all five outputs, padding included.
+ * cph_search_maxsim takes and returns host arrays; cph_search_maxsim_device takes device pointers (queries and outputs)
+ * and a stream and waits for no kernel (n_tokens travels through a pinned buffer of the scratch set: the one host wait is
+ * for the COPY of the lengths that set carried four calls earlier).  An index that never calls these entries launches and
+ * allocates what it did before.  cph_last_search_stats afterwards: those of the underlying search.
+ * Partitioned indexes have no maxsim search: every part has its own internal ids and its own slice of the labels. */
+int cph_search_maxsim(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                      uint64_t candidates, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                      const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                      int32_t* out_found);
+int cph_search_maxsim_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                             uint64_t candidates, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                             const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score, int32_t* d_hits, int64_t* d_rows,
+                             int32_t* d_found, void* stream);
+/* Debug hooks of the measurement script (scripts/maxsim_sweep.py), as cph_debug_time_grouped / _last_group_rows_us: the
+ * maxsim_rows_kernel launch of every maxsim search of this handle (with the copy of n_tokens, when one is given) between
+ * two HIP events while switched on. */
+int cph_debug_time_maxsim(cph_index* h, int on);
+int cph_debug_last_maxsim_rows_us(cph_index* h, double* us);
+/* Test hook: maxsim_rows_kernel on given rows (host arrays).  ids / dist [n][tokens][candidates]; n_tokens [n] or NULL;
+ * key_of [n_keys]; rows [n_keys] or NULL; an id outside [0, n_keys) counts as padding.  The device outputs start as 0xA5
+ * bytes, so a slot the kernel left alone shows.  cph_host_maxsim_rows is the host statement (csrc/host_maxsim.h, no HIP
+ * call). */
+int cph_maxsim_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t tokens, const int32_t* n_tokens,
+                         uint64_t candidates, const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys,
+                         float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found);
+int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t candidates,
+                         const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score,
+                         int32_t* out_hits, int64_t* out_rows, int32_t* out_found);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -710,6 +776,13 @@ int cph_multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uin
 int cph_multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
                              const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids,
                              float* dist, float* gap);
+/* cph_search_maxsim over the same shards: the QUERIES are sharded (plan_shards over n), never the tokens of one query;
+ * n_tokens and filter_of are sliced with them, every shard runs on its replica's worker, the bytes are those of one
+ * device.  keys and filters as in cph_multi_search_grouped; every replica is asked before any shard runs. */
+int cph_multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                            uint64_t candidates, const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

@@ -1386,6 +1386,162 @@ class CPIndex:
         _lib.check(_lib.lib().cph_debug_last_diverse_rows_us(self._replicas()[replica], C.byref(us)))
         return us.value
 
+    # -- multi-vector search (not in the reference) ----------------------------------------------
+    MAXSIM_MAX_TOKENS = 64
+    MAXSIM_MAX_CANDIDATES = 1024
+    MAXSIM_MAX_ENTRIES = 8192          # tokens * candidates: what the kernel sorts in LDS
+    MAXSIM_MAX_K = 1024
+
+    def _maxsim_args(self, n, T, k, n_tokens, candidates, keys, filter, filter_of):
+        """Validation shared by both maxsim entry points -> (k, C, n_tokens as int32 [n] or None, GroupKeys or None,
+        [IdFilter] or None, filter_of or None, IdFilter or None)."""
+        if self._p is not None:
+            raise ValueError("search_maxsim is not defined on a partitioned index (every part has its own internal ids and "
+                             "its own slice of the labels): use part(i).search_maxsim")
+        k = int(k)
+        if not 1 <= T <= self.MAXSIM_MAX_TOKENS:
+            raise ValueError(f"search_maxsim needs 1 <= tokens <= {self.MAXSIM_MAX_TOKENS} (queries is [n, tokens, dim]), got {T}")
+        if not 1 <= k <= self.MAXSIM_MAX_K:
+            raise ValueError(f"search_maxsim needs 1 <= k <= {self.MAXSIM_MAX_K}")
+        if candidates is None:                       # a policy, not a measured optimum
+            candidates = min(self.MAXSIM_MAX_CANDIDATES, self.MAXSIM_MAX_ENTRIES // T, max(32, 4 * k))
+        candidates = int(candidates)
+        if not 1 <= candidates <= self.MAXSIM_MAX_CANDIDATES:
+            raise ValueError(f"candidates must lie in [1, {self.MAXSIM_MAX_CANDIDATES}]")
+        if T * candidates > self.MAXSIM_MAX_ENTRIES:
+            raise ValueError(f"search_maxsim needs tokens * candidates <= {self.MAXSIM_MAX_ENTRIES} (got {T} * {candidates})")
+        if n * T > 0x7FFFFFFF:
+            raise ValueError("search_maxsim needs n * tokens <= 2147483647")
+        if n_tokens is not None:
+            nt = np.asarray(n_tokens)
+            if nt.ndim != 1 or nt.shape[0] != n or not (nt.size == 0 or np.issubdtype(nt.dtype, np.integer)):
+                raise ValueError(f"n_tokens must be a 1D integer array of length {n} (one entry per query)")
+            if nt.size and (nt.min() < 1 or nt.max() > T):
+                raise ValueError(f"n_tokens values must lie in [1, {T}]")
+            n_tokens = np.ascontiguousarray(nt, np.int32)
+        if keys is not None:
+            if not isinstance(keys, GroupKeys):
+                raise ValueError("keys must be a GroupKeys object (make_group_keys)")
+            if not keys._hs:
+                raise ValueError("group keys were closed")
+            if len(keys._hs) != len(self._replicas()):
+                raise ValueError("group keys were made for an index with another number of replicas")
+        elif not self.has_labels:
+            raise ValueError("search_maxsim needs keys: call set_labels first, or pass keys=make_group_keys(...)")
+        fs, fo = self._filter_list(filter, filter_of, n)
+        f = None if (fs is not None or filter is None) else self._filter(filter)
+        return k, candidates, n_tokens, keys, fs, fo, f
+
+    def search_maxsim(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, filter=None, exact=False,
+                      filter_of=None, label=None):
+        """Multi-vector (late-interaction, ColBERT / ColPali style) search: `queries` is float32 [n, T, dim], T token vectors
+        per query of which the first n_tokens[i] (default: all T) are live; returns the k keys (documents) that minimise
+        the sum, over the live tokens, of the token's best row of the key:
+        (keys int32 [n, k], score float32 [n, k], hits int32 [n, k], rows int64 [n, k, T], found int32 [n]).
+        The key of a row is its label (set_labels) or its entry in `keys` (make_group_keys); every int32 value is an
+        ordinary key.  The statement, over the T candidate rows search_batch(queries.reshape(n * T, dim), C, filter=...,
+        exact=..., ...) returns for a query -- same routing, removed rows, tail and refusals; `filter_of[i]` and `label[i]`
+        serve all T tokens of query i -- in internal ids, an entry being valid when it is not padding:
+          floor_t = the distance of the last valid entry of row t (+0.0 when there is none);
+          pos_t(key) = the lowest position of row t whose entry has the key; term_t(key) = the distance there, else floor_t;
+          score(key) = ((+0.0 + term_0) + term_1) + ... over t < n_tokens, in float32, in that order;
+          hits(key) = the live tokens that have a pos_t(key);
+        the min(k, distinct keys) keys with the smallest (score, key) are returned in that order, found[i] of them;
+        rows[i, j, t] is the id at pos_t (input rows under result_ids = "input"), -1 where token t has no row of the key or
+        t >= n_tokens[i].  Padding: key 0, score FLT_MAX, hits 0, rows -1.  The tokens t >= n_tokens[i] are searched with
+        the batch and then ignored entirely.
+        Lower bound: floor_t is the C-th distance of token t, and a row of the key that the search did not return for t is
+        no closer.  With exact=True score is therefore a lower bound of the true sum_t min over the key's allowed rows of
+        dist(q_t, row) -- in float32 too -- and equal to it where hits == n_tokens; with exact=True and C at least the
+        number of allowed rows the answer is the exact MaxSim top-k.  hits is this call's counterpart of `complete` in
+        search_grouped; nothing is re-run on low hits.
+        cosine: MaxSim similarity = n_tokens - score.
+        `candidates=C` (1 <= C <= 1024, T * C <= 8192) is the length of every token's candidate row; candidates=None takes
+        C0 = min(1024, 8192 // T, max(32, 4 * k)): a policy, not a measured optimum, in ONE pass.  Limits: 1 <= T <= 64,
+        1 <= k <= 1024, n * T <= 2^31 - 1.  A multi-device index shards the QUERIES like search_batch, never the tokens of
+        one query; the bytes are those of one device.  A partitioned index is refused (use part(i).search_maxsim)."""
+        q = _as_f32(queries)
+        if q.ndim != 3 or q.shape[2] != self._dim:
+            raise ValueError("queries must be a (n, tokens, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_maxsim(
+                q, k, n_tokens=n_tokens, candidates=candidates, keys=keys, filter=f, exact=exact, filter_of=fo))
+        n, T, L = q.shape[0], q.shape[1], _lib.lib()
+        k, C_, nt, keys, fs, fo, f = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        out = (np.empty((n, k), np.int32), np.empty((n, k), np.float32), np.empty((n, k), np.int32),
+               np.empty((n, k, T), np.int64), np.empty(n, np.int32))
+        multi = self._m is not None
+        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
+        po = [o.ctypes.data if n else None for o in out]
+        qp = q.ctypes.data if n else None
+        ntp = None if (nt is None or n == 0) else nt.ctypes.data
+        if multi:
+            kh = None if keys is None else (C.c_void_p * len(keys._hs))(*[h.value for h in keys._hs])
+            _lib.check(L.cph_multi_search_maxsim(self._m, qp, n, T, ntp, k, C_, kh, fh, nf, fop, int(bool(exact)), *po))
+        else:
+            _lib.check(L.cph_search_maxsim(self._h, qp, n, T, ntp, k, C_, None if keys is None else keys._hs[0], fh, nf, fop,
+                                           int(bool(exact)), *po))
+        return out
+
+    def search_maxsim_device(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, out=None, stream=None,
+                             filter=None, exact=False, filter_of=None, label=None):
+        """search_maxsim on a float32 torch tensor (n, T, dim) on this index' device; returns the five outputs as torch
+        tensors on the same device.  Like search_batch_device it only enqueues, on `stream` (default: torch's current
+        stream), and waits for no kernel: the tensors are valid in stream order, two batches on two streams overlap.
+        ONE pass at `candidates`, or (None) at the C0 of search_maxsim.  `out`: the five tensors to write (contiguous, on
+        the queries' device).  n_tokens / filter / filter_of / label are host data as in search_batch_device (n_tokens is
+        copied to the device through a pinned buffer by a command on `stream`); a filter or GroupKeys closed after the
+        call waits for the batch.  A multi-device index runs the whole batch on one replica on the queries' device.
+        cosine: MaxSim similarity = n_tokens - score."""
+        import torch
+        if queries.dim() != 3 or queries.shape[2] != self._dim or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, tokens, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_maxsim_device(
+                queries, k, n_tokens=n_tokens, candidates=candidates, keys=keys, out=out, stream=stream, filter=f, exact=exact,
+                filter_of=fo))
+        n, T = queries.shape[0], queries.shape[1]
+        k, C_, nt, keys, fs, fo, f = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        rep = self._device_replica(queries)
+        h = self._replicas()[rep]
+        fresh = []                       # tensors allocated here, on torch's current stream
+        if not queries.is_contiguous():
+            queries = queries.contiguous()
+            fresh.append(queries)
+        shapes = (((n, k), torch.int32), ((n, k), torch.float32), ((n, k), torch.int32), ((n, k, T), torch.int64),
+                  ((n,), torch.int32))
+        if out is None:
+            res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in shapes]
+            fresh += res
+        else:
+            res = list(out)
+            if len(res) != 5:
+                raise ValueError("out must be the five tensors (keys, score, hits, rows, found)")
+            for t, (sh, dt) in zip(res, shapes):
+                if tuple(t.shape) != sh or t.dtype != dt or t.device != queries.device or not t.is_contiguous():
+                    raise ValueError("out must be contiguous (n, k) int32 / float32 / int32, (n, k, tokens) int64 and (n,) int32 "
+                                     "tensors on the queries' device")
+        st, _ = self._search_stream(stream, queries, fresh)
+        fh, nf, fop = self._filter_args(fs, fo, f, rep)
+        _lib.check(_lib.lib().cph_search_maxsim_device(h, queries.data_ptr() if n else None, n, T,
+                                                       None if (nt is None or n == 0) else nt.ctypes.data, k, C_,
+                                                       None if keys is None else keys._hs[rep], fh, nf, fop, int(bool(exact)),
+                                                       *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))
+        return tuple(res)
+
+    def time_maxsim(self, on=True):
+        """Debug hook of the measurement script: while on, the maxsim kernel of every maxsim search is bracketed by HIP
+        events (last_maxsim_rows_us).  Off by default."""
+        for h in self._replicas():
+            _lib.check(_lib.lib().cph_debug_time_maxsim(h, int(bool(on))))
+
+    def last_maxsim_rows_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the maxsim kernel of the last maxsim search made under time_maxsim()
+        on the given replica; waits for that launch."""
+        us = C.c_double(0)
+        _lib.check(_lib.lib().cph_debug_last_maxsim_rows_us(self._replicas()[replica], C.byref(us)))
+        return us.value
+
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):
         space = self._result_ids if ids is None else ids

@@ -39,6 +39,7 @@
 #include "device_tail.h"
 #include "device_diverse.h"
 #include "device_group.h"
+#include "device_maxsim.h"
 #include "device_normalize.h"
 #include "host_index.h"
 #include "host_parallel.h"
@@ -176,17 +177,24 @@ struct RangeScratch {
 };
 constexpr size_t kRangeScratchKept = 2;
 
-// The device buffers of one search that re-ranks candidate rows (cph_search_grouped*, cph_search_diverse*): the [n][C]
-// candidate rows of the underlying search and, for the host form, the queries and the outputs (grouped: five, diverse:
-// ids, dist and gap).  A handle owns kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel
-// that touched the rows, the next call on these buffers makes its stream wait for it.
+// The device buffers of one search that re-ranks candidate rows (cph_search_grouped*, cph_search_diverse*,
+// cph_search_maxsim*): the [n][C] candidate rows of the underlying search and, for the host form, the queries and the
+// outputs (grouped: five, diverse: ids, dist and gap, maxsim: keys, score in o_dist, hits in o_counts, rows in o_ids and
+// found).  A handle owns kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel that touched
+// the rows, the next call on these buffers makes its stream wait for it.  maxsim with n_tokens: the lengths are written
+// into pin_tok and copied to d_tok by one command on the call's stream; ev_tok: that copy has read pin_tok (the next such
+// call on this set waits for it before it writes).  A handle that never calls maxsim allocates none of the three.
 struct GroupScratch {
     DevBuf<int64_t> r_ids, o_ids;
     DevBuf<float> r_dist, o_dist, o_gap, d_q;
-    DevBuf<int32_t> o_keys, o_counts;
+    DevBuf<int32_t> o_keys, o_counts, o_found, d_tok;
     DevBuf<uint8_t> o_complete;
     hipEvent_t ev = nullptr;
     bool used = false;
+    int32_t* pin_tok = nullptr;
+    size_t pin_tok_n = 0;
+    hipEvent_t ev_tok = nullptr;
+    bool tok_used = false;
 };
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 
@@ -312,12 +320,12 @@ struct cph_index {
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
     GroupScratch group_scratch[kMaxBatchSets];                  // buffers of grouped searches, in rotation (under mu)
     int last_group = kMaxBatchSets - 1;
-    // debug hooks cph_debug_time_grouped / cph_debug_time_diverse: only while its timer is on is a pass over the
-    // candidate rows bracketed by the two events
+    // debug hooks cph_debug_time_grouped / cph_debug_time_diverse / cph_debug_time_maxsim: only while its timer is on is a
+    // pass over the candidate rows bracketed by the two events
     struct PassTimer {
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool on = false, timed = false;
-    } group_timer, diverse_timer;
+    } group_timer, diverse_timer, maxsim_timer;
     uint64_t index_epoch = 0;          // counts the index swaps (begin_device_swap): a cph_range of an older index refuses to finish
     hipStream_t own_stream = nullptr;  // host-API calls (cph_search_batch, cph_search, hooks)
     bool order_queries = true;         // CPH_QUERY_ORDER=0 disables the closest-entry-first launch order
@@ -1694,7 +1702,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 110; }
+int cph_version(void) { return 111; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1762,11 +1770,13 @@ static void destroy_index(cph_index* h) {
     for (auto& gs : h->group_scratch) {
         if (gs.used && gs.ev) (void)hipEventSynchronize(gs.ev);
         if (gs.ev) (void)hipEventDestroy(gs.ev);
+        if (gs.ev_tok) (void)hipEventDestroy(gs.ev_tok);
+        if (gs.pin_tok) (void)hipHostFree(gs.pin_tok);
     }
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->ev_label0) (void)hipEventDestroy(h->ev_label0);
     if (h->ev_label1) (void)hipEventDestroy(h->ev_label1);
-    for (cph_index::PassTimer* pt : {&h->group_timer, &h->diverse_timer}) {
+    for (cph_index::PassTimer* pt : {&h->group_timer, &h->diverse_timer, &h->maxsim_timer}) {
         if (pt->ev0) (void)hipEventDestroy(pt->ev0);
         if (pt->ev1) (void)hipEventDestroy(pt->ev1);
     }
@@ -6121,6 +6131,299 @@ int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uin
         check_diverse_rows_args(ids, dist, n, candidates, n_ids, k, lam, out_ids, out_dist, out_gap);
         diverse_rows_host(ids, dist, n, (uint32_t)candidates, raw, norm_sq, n_ids, (uint32_t)D, rows, (uint32_t)k, lam, out_ids, out_dist,
                           out_gap);
+    });
+}
+
+}  // extern "C"
+
+// ---- multi-vector search: MaxSim over key groups (device_maxsim.h, host_maxsim.h) ------------------------------------------
+// The grouped entries once more: the n * T token rows are an ordinary batch searched at k = C into the scratch rows, in
+// internal ids, then maxsim_rows_kernel on the same stream joins the T rows of every query by key.
+namespace {
+
+void check_maxsim_shape(uint64_t T, uint64_t C, uint64_t k) {
+    if (T < 1 || T > kMaxsimMaxTokens)
+        throw InvalidArg("maxsim search supports 1 <= tokens <= " + std::to_string(kMaxsimMaxTokens) + ", got " + std::to_string(T));
+    if (C < 1 || C > kMaxsimMaxCandidates)
+        throw InvalidArg("maxsim search supports 1 <= candidates <= " + std::to_string(kMaxsimMaxCandidates) + ", got " + std::to_string(C));
+    if (T * C > kMaxsimMaxEntries)
+        throw InvalidArg("maxsim search needs tokens * candidates <= " + std::to_string(kMaxsimMaxEntries) + " (got " + std::to_string(T) +
+                         " * " + std::to_string(C) + ")");
+    if (k < 1 || k > kMaxsimMaxK) throw InvalidArg("maxsim search supports 1 <= k <= " + std::to_string(kMaxsimMaxK) + ", got " + std::to_string(k));
+}
+
+void check_maxsim_tokens(const int32_t* n_tokens, uint64_t n, uint64_t T) {
+    for (uint64_t i = 0; n_tokens && i < n; ++i)
+        if (n_tokens[i] < 1 || (uint64_t)n_tokens[i] > T)
+            throw InvalidArg("n_tokens[" + std::to_string(i) + "] = " + std::to_string(n_tokens[i]) + " is outside [1, " + std::to_string(T) + "]");
+}
+
+void check_maxsim_batch(uint64_t n, uint64_t T) {
+    if (n > 0x7FFFFFFFull || n * T > 0x7FFFFFFFull)
+        throw InvalidArg("batch too large: maxsim search needs n * tokens <= 2147483647 (got " + std::to_string(n) + " * " + std::to_string(T) + ")");
+}
+
+void check_maxsim_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t C,
+                            const int32_t* key_of, uint64_t n_keys, uint64_t k, const void* o_keys, const void* o_score, const void* o_hits,
+                            const void* o_rows, const void* o_found) {
+    if (!ids || !dist || !key_of || !o_keys || !o_score || !o_hits || !o_rows || !o_found) throw InvalidArg("null argument");
+    check_maxsim_shape(T, C, k);
+    check_maxsim_batch(n, T);
+    if (n < 1 || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("maxsim rows: sizes out of range");
+    check_maxsim_tokens(n_tokens, n, T);
+}
+
+struct MaxsimOut {
+    int32_t* keys;
+    float* score;
+    int32_t* hits;
+    int64_t* rows;
+    int32_t* found;
+    bool all() const { return keys && score && hits && rows && found; }
+};
+
+MaxsimArgs maxsim_args(const int64_t* r_ids, const float* r_dist, const int32_t* d_tokens, uint64_t T, uint64_t C, uint64_t k,
+                       const int32_t* d_key_of, uint64_t n_ids, const uint32_t* d_rows, const MaxsimOut& o) {
+    MaxsimArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.n_tokens = d_tokens;
+    a.T = (uint32_t)T;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.key_of = d_key_of;
+    a.n_ids = (uint32_t)n_ids;
+    a.rows = d_rows;
+    a.out_keys = o.keys;
+    a.out_score = o.score;
+    a.out_hits = o.hits;
+    a.out_rows = o.rows;
+    a.out_found = o.found;
+    return a;
+}
+
+// n_tokens (host) -> the set's device copy, enqueued on `st`; null stays null.  One host wait: for the copy of the lengths
+// this set carried the last time (ev_tok), never for a kernel -- unless the buffers have to grow.  Called from the pass,
+// that is after `st` has been made to wait for the set's previous batch, whose kernel read d_tok.
+const int32_t* upload_maxsim_tokens(GroupScratch& gs, const int32_t* n_tokens, uint64_t n, hipStream_t st) {
+    if (!n_tokens) return nullptr;
+    if (gs.tok_used) HIP_CHECK(hipEventSynchronize(gs.ev_tok));
+    if (gs.pin_tok_n < n || gs.d_tok.n < n) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.pin_tok) HIP_CHECK(hipHostFree(gs.pin_tok));
+        gs.pin_tok = nullptr;
+        gs.pin_tok_n = 0;
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_tok), n * 2 * sizeof(int32_t), hipHostMallocDefault));
+        gs.pin_tok_n = n * 2;
+        gs.d_tok.alloc(n * 2);
+    }
+    if (!gs.ev_tok) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_tok, hipEventDisableTiming));
+    std::memcpy(gs.pin_tok, n_tokens, n * sizeof(int32_t));
+    HIP_CHECK(hipMemcpyAsync(gs.d_tok.p, gs.pin_tok, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(gs.ev_tok, st));
+    gs.tok_used = true;
+    return gs.d_tok.p;
+}
+
+// MaxSim search: d_queries [n][T][dim] and the five outputs in device memory, n_tokens and filter_of on the host.  A
+// query's filter serves its T tokens.  The caller has checked the shape, n_tokens and the output pointers.
+void search_maxsim_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k,
+                          uint64_t C, const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
+                          bool exact, const MaxsimOut& o, hipStream_t st) {
+    std::vector<int32_t> token_filter;
+    if (filter_of) {
+        token_filter.resize(n * T);
+        for (uint64_t i = 0; i < n; ++i) std::fill_n(token_filter.begin() + i * T, T, filter_of[i]);
+    }
+    search_rows_then_pass(h, gs, d_queries, n * T, C, filters, F, filter_of ? token_filter.data() : nullptr, exact, h->maxsim_timer, st, [&] {
+        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
+        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
+                    (uint32_t)n, h->device, st);
+    });
+}
+
+// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
+bool maxsim_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
+                     const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, const MaxsimOut& o) {
+    require_finalized(h);
+    check_maxsim_shape(T, C, k);
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    check_maxsim_batch(n, T);
+    if (n == 0) return false;
+    if (!queries || !o.all()) throw InvalidArg("null argument");
+    check_maxsim_tokens(n_tokens, n, T);
+    return true;
+}
+
+void search_maxsim_host(cph_index* h, const float* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
+                        const cph_group_keys* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
+                        const MaxsimOut& o) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!maxsim_has_work(h, queries, n, T, n_tokens, k, C, filters, F, filter_of, o)) return;
+    const int32_t* d_key_of = group_key_column(h, keys);
+    h->use_device();
+    hipStream_t st = own_stream(h);
+    GroupScratch& gs = next_group_scratch(h);
+    const size_t slots = (size_t)n * k, floats = (size_t)n * T * h->dim;
+    if (gs.d_q.n < floats || gs.o_ids.n < slots * T || gs.o_dist.n < slots || gs.o_keys.n < slots || gs.o_counts.n < slots || gs.o_found.n < n) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.d_q.n < floats) gs.d_q.alloc(floats);
+        if (gs.o_ids.n < slots * T) gs.o_ids.alloc(slots * T);
+        if (gs.o_dist.n < slots) gs.o_dist.alloc(slots);
+        if (gs.o_keys.n < slots) gs.o_keys.alloc(slots);
+        if (gs.o_counts.n < slots) gs.o_counts.alloc(slots);
+        if (gs.o_found.n < n) gs.o_found.alloc(n);
+    }
+    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, floats * 4, hipMemcpyHostToDevice, st));
+    search_maxsim_locked(h, gs, gs.d_q.p, n, T, n_tokens, k, C, d_key_of, filters, F, filter_of, exact,
+                         MaxsimOut{gs.o_keys.p, gs.o_dist.p, gs.o_counts.p, gs.o_ids.p, gs.o_found.p}, st);
+    HIP_CHECK(hipMemcpyAsync(o.keys, gs.o_keys.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.score, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.hits, gs.o_counts.p, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.rows, gs.o_ids.p, slots * T * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.found, gs.o_found.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void search_maxsim_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
+                          const cph_group_keys* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
+                          const MaxsimOut& o, void* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!maxsim_has_work(h, d_queries, n, T, n_tokens, k, C, filters, F, filter_of, o)) return;
+    const int32_t* d_key_of = group_key_column(h, keys);
+    h->use_device();
+    search_maxsim_locked(h, next_group_scratch(h), d_queries, n, T, n_tokens, k, C, d_key_of, filters, F, filter_of, exact, o,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
+// cph_multi_search_maxsim: sharded by query, never inside one; keys[r] = the keys object of replica r (or keys == null:
+// every replica's label column), filters[f * R + r] = filter f on replica r; n_tokens and filter_of are sliced with the
+// queries.
+void multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
+                         const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
+                         bool exact, const MaxsimOut& o) {
+    if (!m) throw InvalidArg("null handle");
+    const uint32_t R = (uint32_t)m->reps.size();
+    const uint64_t dim = m->reps[0]->dim;
+    if (F && !filters) throw InvalidArg("null argument");
+    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
+    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
+        maxsim_has_work(h, queries, n, T, n_tokens, k, C, filters, F, filter_of, o);
+        if (keys && !keys[r]) throw InvalidArg("a maxsim multi-device search needs one keys object per replica");
+        (void)group_key_column(h, keys ? keys[r] : nullptr);
+        check_replica_filters(h, filters, F, R, r);
+    }, [&] {
+        if (n && filter_of) check_filter_of(filter_of, n, F);
+        return n != 0;
+    }, [&](const Shard& s, size_t) {
+        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
+        return cph_search_maxsim(m->reps[s.replica], queries ? queries + s.lo * T * dim : nullptr, s.hi - s.lo, T,
+                                 n_tokens ? n_tokens + s.lo : nullptr, k, C, keys ? keys[s.replica] : nullptr, F ? fr.data() : nullptr, F,
+                                 filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0, o.keys ? o.keys + s.lo * k : nullptr,
+                                 o.score ? o.score + s.lo * k : nullptr, o.hits ? o.hits + s.lo * k : nullptr,
+                                 o.rows ? o.rows + s.lo * k * T : nullptr, o.found ? o.found + s.lo : nullptr);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_search_maxsim(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                      uint64_t candidates, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                      const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                      int32_t* out_found) {
+    return guarded([&] {
+        search_maxsim_host(h, queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
+                           MaxsimOut{out_keys, out_score, out_hits, out_rows, out_found});
+    });
+}
+
+int cph_search_maxsim_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                             uint64_t candidates, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                             const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score, int32_t* d_hits, int64_t* d_rows,
+                             int32_t* d_found, void* stream) {
+    return guarded([&] {
+        search_maxsim_device(h, d_queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
+                             MaxsimOut{d_keys, d_score, d_hits, d_rows, d_found}, stream);
+    });
+}
+
+int cph_multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                            uint64_t candidates, const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found) {
+    return guarded([&] {
+        multi_search_maxsim(m, queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
+                            MaxsimOut{out_keys, out_score, out_hits, out_rows, out_found});
+    });
+}
+
+int cph_debug_time_maxsim(cph_index* h, int on) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->use_device();
+        pass_timer_switch(h->maxsim_timer, on != 0);
+    });
+}
+
+int cph_debug_last_maxsim_rows_us(cph_index* h, double* us) {
+    return guarded([&] {
+        if (!h || !us) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->maxsim_timer.timed) throw InvalidArg("no timed maxsim search has run on this handle (cph_debug_time_maxsim)");
+        h->use_device();
+        *us = pass_timer_us(h->maxsim_timer);
+    });
+}
+
+int cph_maxsim_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t tokens, const int32_t* n_tokens,
+                         uint64_t candidates, const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys,
+                         float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found) {
+    return guarded([&] {
+        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k, out_keys, out_score, out_hits, out_rows,
+                               out_found);
+        HIP_CHECK(hipSetDevice(device));
+        const size_t cells = (size_t)n * tokens * candidates, slots = (size_t)n * k;
+        DevBuf<int64_t> d_ids(cells), o_rows(slots * tokens);
+        DevBuf<float> d_dist(cells), o_score(slots);
+        DevBuf<int32_t> d_key_of(n_keys), d_tok(n), o_keys(slots), o_hits(slots), o_found(n);
+        DevBuf<uint32_t> d_rows(rows ? n_keys : 1);
+        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_key_of.p, key_of, n_keys * 4, hipMemcpyHostToDevice));
+        if (n_tokens) HIP_CHECK(hipMemcpy(d_tok.p, n_tokens, n * 4, hipMemcpyHostToDevice));
+        if (rows) HIP_CHECK(hipMemcpy(d_rows.p, rows, n_keys * 4, hipMemcpyHostToDevice));
+        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
+        HIP_CHECK(hipMemset(o_keys.p, 0xA5, slots * 4));
+        HIP_CHECK(hipMemset(o_score.p, 0xA5, slots * 4));
+        HIP_CHECK(hipMemset(o_hits.p, 0xA5, slots * 4));
+        HIP_CHECK(hipMemset(o_rows.p, 0xA5, slots * tokens * 8));
+        HIP_CHECK(hipMemset(o_found.p, 0xA5, n * 4));
+        maxsim_rows(maxsim_args(d_ids.p, d_dist.p, n_tokens ? d_tok.p : nullptr, tokens, candidates, k, d_key_of.p, n_keys,
+                                rows ? d_rows.p : nullptr, MaxsimOut{o_keys.p, o_score.p, o_hits.p, o_rows.p, o_found.p}),
+                    (uint32_t)n, device, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_keys, o_keys.p, slots * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_score, o_score.p, slots * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_hits, o_hits.p, slots * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_rows, o_rows.p, slots * tokens * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_found, o_found.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t candidates,
+                         const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score,
+                         int32_t* out_hits, int64_t* out_rows, int32_t* out_found) {
+    return guarded([&] {
+        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k, out_keys, out_score, out_hits, out_rows,
+                               out_found);
+        maxsim_rows_host(ids, dist, n, (uint32_t)tokens, n_tokens, (uint32_t)candidates, key_of, n_keys, rows, (uint32_t)k, out_keys,
+                         out_score, out_hits, out_rows, out_found);
     });
 }
 

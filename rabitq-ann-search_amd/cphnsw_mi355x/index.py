@@ -693,18 +693,23 @@ class CPIndex:
     def time_label_filters(self, on=True):
         """Debug hook of the measurement script: while on, every label pass is bracketed by HIP events
         (last_label_filters_us).  Off by default."""
-        for h in self._replicas():
-            _lib.check(_lib.lib().cph_debug_time_label_filters(h, int(bool(on))))
+        self._time_pass("cph_debug_time_label_filters", on)
 
     def last_label_filters_us(self):
         """Device time (HIP events, microseconds) of the last label_filters pass made under time_label_filters(): a
         multi-device or partitioned index reports the longest of its replicas' / parts' passes."""
-        out = []
+        return max(self._last_pass_us("cph_debug_last_label_filters_us", r) for r in range(len(self._replicas())))
+
+    def _time_pass(self, entry, on):
+        """time_*: the debug hook `entry` (cph_debug_time_*) on every replica."""
         for h in self._replicas():
-            us = C.c_double(0)
-            _lib.check(_lib.lib().cph_debug_last_label_filters_us(h, C.byref(us)))
-            out.append(us.value)
-        return max(out)
+            _lib.check(getattr(_lib.lib(), entry)(h, int(bool(on))))
+
+    def _last_pass_us(self, entry, replica):
+        """last_*_us: what `entry` (cph_debug_last_*_us) reports on one replica."""
+        us = C.c_double(0)
+        _lib.check(getattr(_lib.lib(), entry)(self._replicas()[replica], C.byref(us)))
+        return us.value
 
     def label_filter(self, lo, hi=None):
         """IdFilter of the rows whose label is `lo`, or lies in [lo, hi] (both ends inclusive)."""
@@ -1118,6 +1123,79 @@ class CPIndex:
             raise ValueError(f"keys must be a 1D integer array of length {self.size} (the index size)")
         return GroupKeys(self, a, input_rows=space == "input")
 
+    # -- what grouped, diverse and maxsim search share: one validation tail, one host call, one device call ----------
+    def _group_keys_arg(self, keys, what):
+        """The `keys=` of search_grouped / search_maxsim (`what`): an open GroupKeys of this index, or None and a label
+        column."""
+        if keys is not None:
+            if not isinstance(keys, GroupKeys):
+                raise ValueError("keys must be a GroupKeys object (make_group_keys)")
+            if not keys._hs:
+                raise ValueError("group keys were closed")
+            if len(keys._hs) != len(self._replicas()):
+                raise ValueError("group keys were made for an index with another number of replicas")
+        elif not self.has_labels:
+            raise ValueError(f"{what} needs keys: call set_labels first, or pass keys=make_group_keys(...)")
+        return keys
+
+    def _filters_arg(self, filter, filter_of, n):
+        """-> ([IdFilter] or None, filter_of or None, IdFilter or None), as _filter_args takes them."""
+        fs, fo = self._filter_list(filter, filter_of, n)
+        return fs, fo, None if (fs is not None or filter is None) else self._filter(filter)
+
+    def _rerank_host(self, name, q, lead, keys, filters, exact, table):
+        """cph_search_<name>, or cph_multi_search_<name> on a multi-device index, over the float32 array q [n, ...] ->
+        the outputs, allocated from `table` = ((shape, dtype name), ...).  `lead`: the scalars between n and the keys;
+        `keys`: a GroupKeys, None (the label column), or False where the entry takes none; `filters`: _filters_arg."""
+        n, multi = q.shape[0], self._m is not None
+        out = tuple(np.empty(sh, dt) for sh, dt in table)
+        fh, nf, fop = self._filter_args(*filters, None if multi else 0)
+        if keys is False:
+            kh = ()
+        elif keys is None or not multi:
+            kh = (None if keys is None else keys._hs[0],)
+        else:
+            kh = ((C.c_void_p * len(keys._hs))(*[h.value for h in keys._hs]),)
+        fn = getattr(_lib.lib(), ("cph_multi_search_" if multi else "cph_search_") + name)
+        _lib.check(fn(self._m if multi else self._h, q.ctypes.data if n else None, n, *lead, *kh, fh, nf, fop, int(bool(exact)),
+                      *[o.ctypes.data if n else None for o in out]))
+        return out
+
+    def _rerank_device(self, name, queries, lead, keys, filters, exact, table, out, stream, out_what):
+        """cph_search_<name>_device over the float32 torch tensor `queries` on the stream of _search_stream -> the list of
+        outputs: `out` checked against `table` (a uint8 output may be bool; out_what = the two refusals), or allocated
+        from it.  The other arguments are those of _rerank_host."""
+        import torch
+        n = queries.shape[0]
+        rep = self._device_replica(queries)
+        fresh = []                       # tensors allocated here, on torch's current stream
+        if not queries.is_contiguous():
+            queries = queries.contiguous()
+            fresh.append(queries)
+        table = [(sh, getattr(torch, dt)) for sh, dt in table]
+        if out is None:
+            res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in table]
+            fresh += res
+        else:
+            res = list(out)
+            if len(res) != len(table):
+                raise ValueError(out_what[0])
+            for t, (sh, dt) in zip(res, table):
+                ok_dt = t.dtype == dt or (dt == torch.uint8 and t.dtype == torch.bool)
+                if tuple(t.shape) != sh or not ok_dt or t.device != queries.device or not t.is_contiguous():
+                    raise ValueError(out_what[1])
+        st, _ = self._search_stream(stream, queries, fresh)
+        fh, nf, fop = self._filter_args(*filters, rep)
+        kh = () if keys is False else (None if keys is None else keys._hs[rep],)
+        fn = getattr(_lib.lib(), f"cph_search_{name}_device")
+        _lib.check(fn(self._replicas()[rep], queries.data_ptr() if n else None, n, *lead, *kh, fh, nf, fop, int(bool(exact)),
+                      *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))
+        return res
+
+    @staticmethod
+    def _grouped_table(n, k, g):
+        return (((n, k, g), "int64"), ((n, k, g), "float32"), ((n, k), "int32"), ((n, k), "int32"), ((n,), "uint8"))
+
     def _grouped_args(self, n, k, group_size, keys, candidates, filter, filter_of):
         """Validation shared by both grouped entry points -> (k, g, C or None, GroupKeys or None, [IdFilter] or None,
         filter_of or None, IdFilter or None)."""
@@ -1134,35 +1212,11 @@ class CPIndex:
             candidates = int(candidates)
             if not k * g <= candidates <= cap:
                 raise ValueError(f"candidates must lie in [k * group_size, {cap}]")
-        if keys is not None:
-            if not isinstance(keys, GroupKeys):
-                raise ValueError("keys must be a GroupKeys object (make_group_keys)")
-            if not keys._hs:
-                raise ValueError("group keys were closed")
-            if len(keys._hs) != len(self._replicas()):
-                raise ValueError("group keys were made for an index with another number of replicas")
-        elif not self.has_labels:
-            raise ValueError("search_grouped needs keys: call set_labels first, or pass keys=make_group_keys(...)")
-        fs, fo = self._filter_list(filter, filter_of, n)
-        f = None if (fs is not None or filter is None) else self._filter(filter)
-        return k, g, candidates, keys, fs, fo, f
+        return (k, g, candidates, self._group_keys_arg(keys, "search_grouped")) + self._filters_arg(filter, filter_of, n)
 
     def _grouped_pass(self, q, k, g, C_, keys, fs, fo, f, exact):
         """One pass of the host form at C_ candidates over the float32 array q [n, dim] -> the five arrays."""
-        n, L = q.shape[0], _lib.lib()
-        out = (np.empty((n, k, g), np.int64), np.empty((n, k, g), np.float32), np.empty((n, k), np.int32),
-               np.empty((n, k), np.int32), np.empty(n, np.uint8))
-        multi = self._m is not None
-        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
-        po = [o.ctypes.data if n else None for o in out]
-        qp = q.ctypes.data if n else None
-        if multi:
-            kh = None if keys is None else (C.c_void_p * len(keys._hs))(*[h.value for h in keys._hs])
-            _lib.check(L.cph_multi_search_grouped(self._m, qp, n, k, g, C_, kh, fh, nf, fop, int(bool(exact)), *po))
-        else:
-            _lib.check(L.cph_search_grouped(self._h, qp, n, k, g, C_, None if keys is None else keys._hs[0], fh, nf, fop,
-                                            int(bool(exact)), *po))
-        return out
+        return self._rerank_host("grouped", q, (k, g, C_), keys, (fs, fo, f), exact, self._grouped_table(q.shape[0], k, g))
 
     def search_grouped(self, queries, k=DEFAULT_K, group_size=1, keys=None, candidates=None, filter=None, exact=False,
                        filter_of=None, label=None):
@@ -1232,31 +1286,10 @@ class CPIndex:
         k, g, C_, keys, fs, fo, f = self._grouped_args(n, k, group_size, keys, candidates, filter, filter_of)
         if C_ is None:
             C_ = min(self.GROUP_MAX_CANDIDATES, max(64, 4 * k * g))
-        rep = self._device_replica(queries)
-        h = self._replicas()[rep]
-        fresh = []                       # tensors allocated here, on torch's current stream
-        if not queries.is_contiguous():
-            queries = queries.contiguous()
-            fresh.append(queries)
-        shapes =(((n, k, g), torch.int64), ((n, k, g), torch.float32), ((n, k), torch.int32), ((n, k), torch.int32),
-                  ((n,), torch.uint8))
-        if out is None:
-            res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in shapes]
-            fresh += res
-        else:
-            res = list(out)
-            if len(res) != 5:
-                raise ValueError("out must be the five tensors (ids, dist, keys, counts, complete)")
-            for i, (t, (sh, dt)) in enumerate(zip(res, shapes)):
-                ok_dt = t.dtype == dt or (i == 4 and t.dtype == torch.bool)
-                if tuple(t.shape) != sh or not ok_dt or t.device != queries.device or not t.is_contiguous():
-                    raise ValueError("out must be contiguous (n, k, g) int64 / float32, (n, k) int32 / int32 and (n,) uint8 "
-                                     "tensors on the queries' device")
-        st, _ = self._search_stream(stream, queries, fresh)
-        fh, nf, fop = self._filter_args(fs, fo, f, rep)
-        _lib.check(_lib.lib().cph_search_grouped_device(h, queries.data_ptr() if n else None, n, k, g, C_,
-                                                        None if keys is None else keys._hs[rep], fh, nf, fop, int(bool(exact)),
-                                                        *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))
+        res = self._rerank_device("grouped", queries, (k, g, C_), keys, (fs, fo, f), exact, self._grouped_table(n, k, g), out, stream,
+                                  ("out must be the five tensors (ids, dist, keys, counts, complete)",
+                                   "out must be contiguous (n, k, g) int64 / float32, (n, k) int32 / int32 and (n,) uint8 tensors on the "
+                                   "queries' device"))
         if res[4].dtype != torch.bool:
             res[4] = res[4].view(torch.bool)
         return tuple(res)
@@ -1264,22 +1297,18 @@ class CPIndex:
     def time_grouped(self, on=True):
         """Debug hook of the measurement script: while on, the group kernel of every grouped search is bracketed by HIP
         events (last_group_rows_us).  Off by default."""
-        for h in self._replicas():
-            _lib.check(_lib.lib().cph_debug_time_grouped(h, int(bool(on))))
+        self._time_pass("cph_debug_time_grouped", on)
 
     def last_group_rows_us(self, replica=0):
         """Device time (HIP events, microseconds) of the group kernel of the last grouped search made under
         time_grouped() on the given replica; waits for that launch."""
-        us = C.c_double(0)
-        _lib.check(_lib.lib().cph_debug_last_group_rows_us(self._replicas()[replica], C.byref(us)))
-        return us.value
+        return self._last_pass_us("cph_debug_last_group_rows_us", replica)
 
     # -- diversified search (not in the reference) ----------------------------------------------
     DIVERSE_MAX_CANDIDATES = 1024
 
     def _diverse_args(self, n, k, lam, candidates, filter, filter_of):
-        """Validation shared by both diverse entry points -> (k, lam, C, [IdFilter] or None, filter_of or None, IdFilter
-        or None)."""
+        """Validation shared by both diverse entry points -> (k, lam, C, the filters as of _filters_arg)."""
         if self._p is not None:
             raise ValueError("search_diverse is not defined on a partitioned index (every part has its own internal ids): "
                              "use part(i).search_diverse")
@@ -1296,9 +1325,11 @@ class CPIndex:
         candidates = int(candidates)
         if not k <= candidates <= cap:
             raise ValueError(f"candidates must lie in [k, {cap}]")
-        fs, fo = self._filter_list(filter, filter_of, n)
-        f = None if (fs is not None or filter is None) else self._filter(filter)
-        return k, lam, candidates, fs, fo, f
+        return k, lam, candidates, self._filters_arg(filter, filter_of, n)
+
+    @staticmethod
+    def _diverse_table(n, k):
+        return (((n, k), "int64"), ((n, k), "float32"), ((n, k), "float32"))
 
     def search_diverse(self, queries, k=DEFAULT_K, lam=0.5, candidates=None, filter=None, exact=False, filter_of=None,
                        label=None):
@@ -1323,15 +1354,8 @@ class CPIndex:
         if label is not None:
             return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_diverse(
                 q, k, lam, candidates=candidates, filter=f, exact=exact, filter_of=fo))
-        n, L = q.shape[0], _lib.lib()
-        k, lam, C_, fs, fo, f = self._diverse_args(n, k, lam, candidates, filter, filter_of)
-        out = (np.empty((n, k), np.int64), np.empty((n, k), np.float32), np.empty((n, k), np.float32))
-        multi = self._m is not None
-        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
-        po = [o.ctypes.data if n else None for o in out]
-        fn, h = (L.cph_multi_search_diverse, self._m) if multi else (L.cph_search_diverse, self._h)
-        _lib.check(fn(h, q.ctypes.data if n else None, n, k, lam, C_, fh, nf, fop, int(bool(exact)), *po))
-        return out
+        k, lam, C_, filters = self._diverse_args(q.shape[0], k, lam, candidates, filter, filter_of)
+        return self._rerank_host("diverse", q, (k, lam, C_), False, filters, exact, self._diverse_table(q.shape[0], k))
 
     def search_diverse_device(self, queries, k=DEFAULT_K, lam=0.5, candidates=None, out=None, stream=None, filter=None,
                               exact=False, filter_of=None, label=None):
@@ -1348,43 +1372,20 @@ class CPIndex:
             return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_diverse_device(
                 queries, k, lam, candidates=candidates, out=out, stream=stream, filter=f, exact=exact, filter_of=fo))
         n = queries.shape[0]
-        k, lam, C_, fs, fo, f = self._diverse_args(n, k, lam, candidates, filter, filter_of)
-        rep = self._device_replica(queries)
-        h = self._replicas()[rep]
-        fresh = []                       # tensors allocated here, on torch's current stream
-        if not queries.is_contiguous():
-            queries = queries.contiguous()
-            fresh.append(queries)
-        dtypes = (torch.int64, torch.float32, torch.float32)
-        if out is None:
-            res = [torch.empty((n, k), dtype=dt, device=queries.device) for dt in dtypes]
-            fresh += res
-        else:
-            res = list(out)
-            if len(res) != 3:
-                raise ValueError("out must be the three tensors (ids, dist, gap)")
-            for t, dt in zip(res, dtypes):
-                if tuple(t.shape) != (n, k) or t.dtype != dt or t.device != queries.device or not t.is_contiguous():
-                    raise ValueError("out must be contiguous (n, k) int64 / float32 / float32 tensors on the queries' device")
-        st, _ = self._search_stream(stream, queries, fresh)
-        fh, nf, fop = self._filter_args(fs, fo, f, rep)
-        _lib.check(_lib.lib().cph_search_diverse_device(h, queries.data_ptr() if n else None, n, k, lam, C_, fh, nf, fop,
-                                                        int(bool(exact)), *[t.data_ptr() if n else None for t in res],
-                                                        C.c_void_p(st)))
-        return tuple(res)
+        k, lam, C_, filters = self._diverse_args(n, k, lam, candidates, filter, filter_of)
+        return tuple(self._rerank_device("diverse", queries, (k, lam, C_), False, filters, exact, self._diverse_table(n, k), out, stream,
+                                         ("out must be the three tensors (ids, dist, gap)",
+                                          "out must be contiguous (n, k) int64 / float32 / float32 tensors on the queries' device")))
 
     def time_diverse(self, on=True):
         """Debug hook of the measurement script: while on, the re-ranking kernel of every diverse search is bracketed by
         HIP events (last_diverse_rows_us).  Off by default."""
-        for h in self._replicas():
-            _lib.check(_lib.lib().cph_debug_time_diverse(h, int(bool(on))))
+        self._time_pass("cph_debug_time_diverse", on)
 
     def last_diverse_rows_us(self, replica=0):
         """Device time (HIP events, microseconds) of the re-ranking kernel of the last diverse search made under
         time_diverse() on the given replica; waits for that launch."""
-        us = C.c_double(0)
-        _lib.check(_lib.lib().cph_debug_last_diverse_rows_us(self._replicas()[replica], C.byref(us)))
-        return us.value
+        return self._last_pass_us("cph_debug_last_diverse_rows_us", replica)
 
     # -- multi-vector search (not in the reference) ----------------------------------------------
     MAXSIM_MAX_TOKENS = 64
@@ -1393,8 +1394,8 @@ class CPIndex:
     MAXSIM_MAX_K = 1024
 
     def _maxsim_args(self, n, T, k, n_tokens, candidates, keys, filter, filter_of):
-        """Validation shared by both maxsim entry points -> (k, C, n_tokens as int32 [n] or None, GroupKeys or None,
-        [IdFilter] or None, filter_of or None, IdFilter or None)."""
+        """Validation shared by both maxsim entry points -> (k, C, n_tokens as int32 [n] or None, GroupKeys or None, the
+        filters as of _filters_arg)."""
         if self._p is not None:
             raise ValueError("search_maxsim is not defined on a partitioned index (every part has its own internal ids and "
                              "its own slice of the labels): use part(i).search_maxsim")
@@ -1419,18 +1420,13 @@ class CPIndex:
             if nt.size and (nt.min() < 1 or nt.max() > T):
                 raise ValueError(f"n_tokens values must lie in [1, {T}]")
             n_tokens = np.ascontiguousarray(nt, np.int32)
-        if keys is not None:
-            if not isinstance(keys, GroupKeys):
-                raise ValueError("keys must be a GroupKeys object (make_group_keys)")
-            if not keys._hs:
-                raise ValueError("group keys were closed")
-            if len(keys._hs) != len(self._replicas()):
-                raise ValueError("group keys were made for an index with another number of replicas")
-        elif not self.has_labels:
-            raise ValueError("search_maxsim needs keys: call set_labels first, or pass keys=make_group_keys(...)")
-        fs, fo = self._filter_list(filter, filter_of, n)
-        f = None if (fs is not None or filter is None) else self._filter(filter)
-        return k, candidates, n_tokens, keys, fs, fo, f
+        return k, candidates, n_tokens, self._group_keys_arg(keys, "search_maxsim"), self._filters_arg(filter, filter_of, n)
+
+    @staticmethod
+    def _maxsim_call(n, T, k, C_, nt):
+        """-> (the scalars between n and the keys, the output table)."""
+        return ((T, None if (nt is None or n == 0) else nt.ctypes.data, k, C_),
+                (((n, k), "int32"), ((n, k), "float32"), ((n, k), "int32"), ((n, k, T), "int64"), ((n,), "int32")))
 
     def search_maxsim(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, filter=None, exact=False,
                       filter_of=None, label=None):
@@ -1466,22 +1462,10 @@ class CPIndex:
         if label is not None:
             return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_maxsim(
                 q, k, n_tokens=n_tokens, candidates=candidates, keys=keys, filter=f, exact=exact, filter_of=fo))
-        n, T, L = q.shape[0], q.shape[1], _lib.lib()
-        k, C_, nt, keys, fs, fo, f = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
-        out = (np.empty((n, k), np.int32), np.empty((n, k), np.float32), np.empty((n, k), np.int32),
-               np.empty((n, k, T), np.int64), np.empty(n, np.int32))
-        multi = self._m is not None
-        fh, nf, fop = self._filter_args(fs, fo, f, None if multi else 0)
-        po = [o.ctypes.data if n else None for o in out]
-        qp = q.ctypes.data if n else None
-        ntp = None if (nt is None or n == 0) else nt.ctypes.data
-        if multi:
-            kh = None if keys is None else (C.c_void_p * len(keys._hs))(*[h.value for h in keys._hs])
-            _lib.check(L.cph_multi_search_maxsim(self._m, qp, n, T, ntp, k, C_, kh, fh, nf, fop, int(bool(exact)), *po))
-        else:
-            _lib.check(L.cph_search_maxsim(self._h, qp, n, T, ntp, k, C_, None if keys is None else keys._hs[0], fh, nf, fop,
-                                           int(bool(exact)), *po))
-        return out
+        n, T = q.shape[0], q.shape[1]
+        k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        lead, table = self._maxsim_call(n, T, k, C_, nt)
+        return self._rerank_host("maxsim", q, lead, keys, filters, exact, table)
 
     def search_maxsim_device(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, out=None, stream=None,
                              filter=None, exact=False, filter_of=None, label=None):
@@ -1501,46 +1485,22 @@ class CPIndex:
                 queries, k, n_tokens=n_tokens, candidates=candidates, keys=keys, out=out, stream=stream, filter=f, exact=exact,
                 filter_of=fo))
         n, T = queries.shape[0], queries.shape[1]
-        k, C_, nt, keys, fs, fo, f = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
-        rep = self._device_replica(queries)
-        h = self._replicas()[rep]
-        fresh = []                       # tensors allocated here, on torch's current stream
-        if not queries.is_contiguous():
-            queries = queries.contiguous()
-            fresh.append(queries)
-        shapes = (((n, k), torch.int32), ((n, k), torch.float32), ((n, k), torch.int32), ((n, k, T), torch.int64),
-                  ((n,), torch.int32))
-        if out is None:
-            res = [torch.empty(sh, dtype=dt, device=queries.device) for sh, dt in shapes]
-            fresh += res
-        else:
-            res = list(out)
-            if len(res) != 5:
-                raise ValueError("out must be the five tensors (keys, score, hits, rows, found)")
-            for t, (sh, dt) in zip(res, shapes):
-                if tuple(t.shape) != sh or t.dtype != dt or t.device != queries.device or not t.is_contiguous():
-                    raise ValueError("out must be contiguous (n, k) int32 / float32 / int32, (n, k, tokens) int64 and (n,) int32 "
-                                     "tensors on the queries' device")
-        st, _ = self._search_stream(stream, queries, fresh)
-        fh, nf, fop = self._filter_args(fs, fo, f, rep)
-        _lib.check(_lib.lib().cph_search_maxsim_device(h, queries.data_ptr() if n else None, n, T,
-                                                       None if (nt is None or n == 0) else nt.ctypes.data, k, C_,
-                                                       None if keys is None else keys._hs[rep], fh, nf, fop, int(bool(exact)),
-                                                       *[t.data_ptr() if n else None for t in res], C.c_void_p(st)))
-        return tuple(res)
+        k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        lead, table = self._maxsim_call(n, T, k, C_, nt)
+        return tuple(self._rerank_device("maxsim", queries, lead, keys, filters, exact, table, out, stream,
+                                         ("out must be the five tensors (keys, score, hits, rows, found)",
+                                          "out must be contiguous (n, k) int32 / float32 / int32, (n, k, tokens) int64 and (n,) int32 "
+                                          "tensors on the queries' device")))
 
     def time_maxsim(self, on=True):
         """Debug hook of the measurement script: while on, the maxsim kernel of every maxsim search is bracketed by HIP
         events (last_maxsim_rows_us).  Off by default."""
-        for h in self._replicas():
-            _lib.check(_lib.lib().cph_debug_time_maxsim(h, int(bool(on))))
+        self._time_pass("cph_debug_time_maxsim", on)
 
     def last_maxsim_rows_us(self, replica=0):
         """Device time (HIP events, microseconds) of the maxsim kernel of the last maxsim search made under time_maxsim()
         on the given replica; waits for that launch."""
-        us = C.c_double(0)
-        _lib.check(_lib.lib().cph_debug_last_maxsim_rows_us(self._replicas()[replica], C.byref(us)))
-        return us.value
+        return self._last_pass_us("cph_debug_last_maxsim_rows_us", replica)
 
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):

@@ -178,17 +178,18 @@ struct RangeScratch {
 constexpr size_t kRangeScratchKept = 2;
 
 // The device buffers of one search that re-ranks candidate rows (cph_search_grouped*, cph_search_diverse*,
-// cph_search_maxsim*): the [n][C] candidate rows of the underlying search and, for the host form, the queries and the
-// outputs (grouped: five, diverse: ids, dist and gap, maxsim: keys, score in o_dist, hits in o_counts, rows in o_ids and
-// found).  A handle owns kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel that touched
-// the rows, the next call on these buffers makes its stream wait for it.  maxsim with n_tokens: the lengths are written
-// into pin_tok and copied to d_tok by one command on the call's stream; ev_tok: that copy has read pin_tok (the next such
-// call on this set waits for it before it writes).  A handle that never calls maxsim allocates none of the three.
+// cph_search_maxsim*): the [n][C] candidate rows of the underlying search and, for the host form, the queries and one
+// byte buffer per slot of the call's output table (RerankOuts), sized by reserve_group_scratch alone.  A handle owns
+// kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel that touched the rows, the next
+// call on these buffers makes its stream wait for it.  maxsim with n_tokens: the lengths are written into pin_tok and
+// copied to d_tok by one command on the call's stream; ev_tok: that copy has read pin_tok (the next such call on this
+// set waits for it before it writes).  A handle that never calls maxsim allocates none of the three.
+constexpr int kMaxRerankOuts = 5;
 struct GroupScratch {
-    DevBuf<int64_t> r_ids, o_ids;
-    DevBuf<float> r_dist, o_dist, o_gap, d_q;
-    DevBuf<int32_t> o_keys, o_counts, o_found, d_tok;
-    DevBuf<uint8_t> o_complete;
+    DevBuf<int64_t> r_ids;
+    DevBuf<float> r_dist, d_q;
+    DevBuf<uint8_t> out[kMaxRerankOuts];
+    DevBuf<int32_t> d_tok;
     hipEvent_t ev = nullptr;
     bool used = false;
     int32_t* pin_tok = nullptr;
@@ -197,6 +198,7 @@ struct GroupScratch {
     bool tok_used = false;
 };
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassKinds };     // the passes a handle can time (PassTimer)
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -277,9 +279,6 @@ struct cph_index {
     // the parts cut -- walks these slots too (column_of)
     DevBuf<int32_t> d_columns[kMaxColumns];
     bool has_column[kMaxColumns] = {};
-    // debug hook cph_debug_time_label_filters: only while label_timing is on is a label pass bracketed by the two events
-    hipEvent_t ev_label0 = nullptr, ev_label1 = nullptr;
-    bool label_timing = false, label_timed = false;
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
@@ -320,12 +319,12 @@ struct cph_index {
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
     GroupScratch group_scratch[kMaxBatchSets];                  // buffers of grouped searches, in rotation (under mu)
     int last_group = kMaxBatchSets - 1;
-    // debug hooks cph_debug_time_grouped / cph_debug_time_diverse / cph_debug_time_maxsim: only while its timer is on is a
-    // pass over the candidate rows bracketed by the two events
+    // debug hooks cph_debug_time_grouped / _diverse / _maxsim / _label_filters: only while its timer is on is that pass
+    // (over the candidate rows; over the label column) bracketed by the two events
     struct PassTimer {
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         bool on = false, timed = false;
-    } group_timer, diverse_timer, maxsim_timer;
+    } pass_timer[kPassKinds];
     uint64_t index_epoch = 0;          // counts the index swaps (begin_device_swap): a cph_range of an older index refuses to finish
     hipStream_t own_stream = nullptr;  // host-API calls (cph_search_batch, cph_search, hooks)
     bool order_queries = true;         // CPH_QUERY_ORDER=0 disables the closest-entry-first launch order
@@ -523,6 +522,49 @@ void quiesce(cph_index* h) {
         if (s.used && s.ev_done) HIP_CHECK(hipEventSynchronize(s.ev_done));
     for (auto& gs : h->group_scratch)            // (the group pass runs behind its batch's ev_done)
         if (gs.used && gs.ev) HIP_CHECK(hipEventSynchronize(gs.ev));
+}
+
+// ---- pass timers (cph_debug_time_*, cph_debug_last_*_us) --------------------------------------------------------------------
+constexpr const char* kNoTimedPass[kPassKinds] = {
+    "no timed grouped search has run on this handle (cph_debug_time_grouped)",
+    "no timed diverse search has run on this handle (cph_debug_time_diverse)",
+    "no timed maxsim search has run on this handle (cph_debug_time_maxsim)",
+    "no timed label pass has run on this handle (cph_debug_time_label_filters)",
+};
+
+// pass(), which enqueues on `st`, between the timer's two events while it is on.
+template <class Pass>
+void timed_pass(cph_index::PassTimer& t, hipStream_t st, Pass pass) {
+    t.timed = false;
+    if (t.on) HIP_CHECK(hipEventRecord(t.ev0, st));
+    pass();
+    if (t.on) HIP_CHECK(hipEventRecord(t.ev1, st));
+    t.timed = t.on;
+}
+
+// cph_debug_time_*.
+void pass_timer_switch(cph_index* h, PassKind kind, bool on) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->use_device();
+    cph_index::PassTimer& t = h->pass_timer[kind];
+    if (on && !t.ev0) HIP_CHECK(hipEventCreate(&t.ev0));
+    if (on && !t.ev1) HIP_CHECK(hipEventCreate(&t.ev1));
+    t.on = on;
+    t.timed = false;
+}
+
+// cph_debug_last_*_us: device time of the last timed pass in microseconds; waits for it.
+void pass_timer_us(cph_index* h, PassKind kind, double* us) {
+    if (!h || !us) throw InvalidArg("null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    cph_index::PassTimer& t = h->pass_timer[kind];
+    if (!t.timed) throw InvalidArg(kNoTimedPass[kind]);
+    h->use_device();
+    HIP_CHECK(hipEventSynchronize(t.ev1));
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t.ev0, t.ev1));
+    *us = (double)ms * 1e3;
 }
 
 // The big arrays of a loaded index: blocks repacked into the device layout, vectors, norms.  (An index
@@ -1774,11 +1816,9 @@ static void destroy_index(cph_index* h) {
         if (gs.pin_tok) (void)hipHostFree(gs.pin_tok);
     }
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (h->ev_label0) (void)hipEventDestroy(h->ev_label0);
-    if (h->ev_label1) (void)hipEventDestroy(h->ev_label1);
-    for (cph_index::PassTimer* pt : {&h->group_timer, &h->diverse_timer, &h->maxsim_timer}) {
-        if (pt->ev0) (void)hipEventDestroy(pt->ev0);
-        if (pt->ev1) (void)hipEventDestroy(pt->ev1);
+    for (auto& pt : h->pass_timer) {
+        if (pt.ev0) (void)hipEventDestroy(pt.ev0);
+        if (pt.ev1) (void)hipEventDestroy(pt.ev1);
     }
     for (auto& ls : h->leaders) {
         if (ls.stream) { (void)hipStreamSynchronize(ls.stream); (void)hipStreamDestroy(ls.stream); }
@@ -3054,14 +3094,12 @@ void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uin
     hipStream_t st = own_stream(h);
     HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p, lo, (size_t)m * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p + m, hi, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    h->label_timed = false;
-    if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label0, st));
-    label_filters(col.dev.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
-    if (h->label_timing) HIP_CHECK(hipEventRecord(h->ev_label1, st));
+    timed_pass(h->pass_timer[kPassLabels], st, [&] {
+        label_filters(col.dev.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
+    });
     std::vector<unsigned long long> counts(m);
     HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_label_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
-    h->label_timed = h->label_timing;
     for (uint32_t j = 0; j < m; ++j) {
         cph_filter* f = made[j].get();
         f->device = h->device;
@@ -3158,27 +3196,11 @@ int cph_filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, 
 }
 
 int cph_debug_time_label_filters(cph_index* h, int on) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->use_device();
-        if (on && !h->ev_label0) HIP_CHECK(hipEventCreate(&h->ev_label0));
-        if (on && !h->ev_label1) HIP_CHECK(hipEventCreate(&h->ev_label1));
-        h->label_timing = on != 0;
-        h->label_timed = false;
-    });
+    return guarded([&] { pass_timer_switch(h, kPassLabels, on != 0); });
 }
 
 int cph_debug_last_label_filters_us(cph_index* h, double* us) {
-    return guarded([&] {
-        if (!h || !us) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->label_timed) throw InvalidArg("no timed label pass has run on this handle (cph_debug_time_label_filters)");
-        h->use_device();
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, h->ev_label0, h->ev_label1));
-        *us = (double)ms * 1e3;
-    });
+    return guarded([&] { pass_timer_us(h, kPassLabels, us); });
 }
 
 int cph_filter_export(const cph_filter* f, uint32_t* words, uint64_t* count) {
@@ -5561,10 +5583,12 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
 
 }  // extern "C"
 
-// ---- grouped search: the k best key groups, up to g rows of each (device_group.h, host_group.h) ---------------------------
-// An ordinary search at k = C into scratch rows the handle owns, then group_rows_kernel on the same stream.  The rows
-// hold INTERNAL ids whatever the handle returns (the keys are looked up by internal id); the row map is applied where a
-// member is written.  Nothing here waits for the device in the _device form.
+// ---- searches that re-rank candidate rows: grouped, diverse, maxsim (device_group.h, device_diverse.h, device_maxsim.h) ----
+// One entry path for the three: an ordinary search at k = C into scratch rows the handle owns, then one kernel over those
+// rows on the same stream.  The rows hold INTERNAL ids whatever the handle returns (the keys are looked up by internal
+// id); the row map is applied where an id is written.  Nothing here waits for the device in the _device form.  A
+// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch): its scalars, its checks, its output table
+// and its pass; the entries, the scratch, the replica fan-out and the hooks below are written once over that.
 struct cph_group_keys {
     cph_index* h = nullptr;                    // the handle it was made for ...
     uint64_t epoch = 0;                        // ... and the index that handle held then (index_epoch)
@@ -5584,27 +5608,41 @@ struct InternalIdsScope {
     ~InternalIdsScope() { h->ids_input = was; }
 };
 
-void check_group_shape(uint64_t k, uint64_t g, uint64_t C) {
-    if (k < 1 || g < 1) throw InvalidArg("grouped search needs k >= 1 and group_size >= 1");
-    if (C > kGroupMaxCandidates)
-        throw InvalidArg("grouped search supports candidates <= " + std::to_string(kGroupMaxCandidates) + ", got " + std::to_string(C));
-    if (k > C || g > C || k * g > C)
-        throw InvalidArg("grouped search needs k * group_size <= candidates (got " + std::to_string(k) + " * " + std::to_string(g) +
-                         " > " + std::to_string(C) + ")");
+// The outputs of one re-ranker call, in the order of its C signature: where each goes and how many bytes of it a query
+// has.  Every walk over "the outputs" -- the null check, the scratch reservation, the copy-back of the host form, the
+// per-shard offsets of the replica form, the hooks' poison fill and download -- walks this table.
+struct RerankOuts {
+    struct Out { void* p; size_t stride; } o[kMaxRerankOuts];
+    int count;
+    bool all() const {
+        for (int i = 0; i < count; ++i)
+            if (!o[i].p) return false;
+        return true;
+    }
+    template <class T> T* at(int i) const { return static_cast<T*>(o[i].p); }
+};
+
+// What a re-ranker call carries besides the re-ranker's own scalars.
+struct RerankCall {
+    const float* q;
+    uint64_t n;
+    const cph_filter* const* filters;
+    uint32_t F;
+    const int32_t* filter_of;
+    bool exact;
+    RerankOuts out;
+};
+
+void check_filter_args(const RerankCall& c) {
+    if (c.F && !c.filters) throw InvalidArg("null argument");
+    if (!c.filter_of && c.F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
 }
 
-void check_group_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, const int32_t* key_of, uint64_t n_keys,
-                           uint64_t k, uint64_t g, const int64_t* out_ids, const float* out_dist, const int32_t* out_keys,
-                           const int32_t* out_counts, const uint8_t* out_complete) {
-    if (!ids || !dist || !key_of || !out_ids || !out_dist || !out_keys || !out_counts || !out_complete) throw InvalidArg("null argument");
-    if (C < 1) throw InvalidArg("group rows: candidates must be >= 1");
-    check_group_shape(k, g, C);
-    if (n < 1 || n > 0x7FFFFFFFull || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("group rows: sizes out of range");
-    for (uint64_t i = 0; i < n * C; ++i)
-        if (ids[i] >= 0 && (uint64_t)ids[i] >= n_keys) throw InvalidArg("group rows: id out of range");
+void check_batch_size(uint64_t n) {
+    if (n > 0x7FFFFFFFull) throw InvalidArg("batch too large");
 }
 
-// The key column of a grouped call: the keys object (checked against the handle), else the label column.
+// The key column of a grouped or maxsim call: the keys object (checked against the handle), else the label column.
 const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) {
     if (!keys) {
         if (!h->has_labels) throw InvalidArg("grouped search needs keys: the index has no label column (cph_set_labels) and no keys object was given");
@@ -5618,9 +5656,9 @@ const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) 
     return keys->keys.p;
 }
 
-// The body of both forms of a search that re-ranks candidate rows (grouped, diverse): the ordinary search at k = C into
-// the rows of `gs`, in internal ids, then pass(), which enqueues one kernel over those rows, bracketed by the timer's
-// events while it is on; everything on `st`.  The caller holds the handle mutex and has set the device.
+// The ordinary search at k = C into the rows of `gs`, in internal ids, then pass(), which enqueues one kernel over those
+// rows, bracketed by the timer's events while it is on; everything on `st`.  The caller holds the handle mutex and has set
+// the device.
 template <class Pass>
 void search_rows_then_pass(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
                            uint32_t F, const int32_t* filter_of, bool exact, cph_index::PassTimer& timer, hipStream_t st, Pass pass) {
@@ -5636,11 +5674,7 @@ void search_rows_then_pass(cph_index* h, GroupScratch& gs, const float* d_querie
             InternalIdsScope internal(h);
             search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, true, st));
         }
-        timer.timed = false;
-        if (timer.on) HIP_CHECK(hipEventRecord(timer.ev0, st));
-        pass();
-        if (timer.on) HIP_CHECK(hipEventRecord(timer.ev1, st));
-        timer.timed = timer.on;
+        timed_pass(timer, st, pass);
     } catch (...) {
         (void)hipEventRecord(gs.ev, st);                          // whatever was enqueued may still write the rows
         gs.used = true;
@@ -5650,135 +5684,346 @@ void search_rows_then_pass(cph_index* h, GroupScratch& gs, const float* d_querie
     gs.used = true;
 }
 
-// Grouped search: d_queries and the five outputs in device memory.  The caller has checked the shape and the output
-// pointers.
-void search_grouped_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
-                           const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
-                           int64_t* d_ids, float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, hipStream_t st) {
-    search_rows_then_pass(h, gs, d_queries, n, C, filters, F, filter_of, exact, h->group_timer, st, [&] {
-        GroupArgs a{};
-        a.ids = gs.r_ids.p;
-        a.dist = gs.r_dist.p;
-        a.C = (uint32_t)C;
-        a.k = (uint32_t)k;
-        a.g = (uint32_t)g;
-        a.key_of = d_key_of;
-        a.n_ids = (uint32_t)h->size();
-        a.rows = h->ids_input ? h->d_rows.p : nullptr;
-        a.out_ids = d_ids;
-        a.out_dist = d_dist;
-        a.out_keys = d_keys;
-        a.out_counts = d_counts;
-        a.out_complete = d_complete;
-        group_rows(a, (uint32_t)n, st);
-    });
-}
-
-// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
-bool grouped_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_filter* const* filters,
-                      uint32_t F, const int32_t* filter_of, const void* ids, const void* dist, const void* keys_out, const void* counts,
-                      const void* complete) {
-    require_finalized(h);
-    if (C < 1) throw InvalidArg("grouped search needs candidates >= 1");
-    check_group_shape(k, g, C);
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    if (n > 0x7FFFFFFFull) throw InvalidArg("batch too large");
-    if (n == 0) return false;
-    if (!queries || !ids || !dist || !keys_out || !counts || !complete) throw InvalidArg("null argument");
-    return true;
-}
-
 GroupScratch& next_group_scratch(cph_index* h) {
     h->last_group = (h->last_group + 1) % kMaxBatchSets;
     return h->group_scratch[h->last_group];
 }
 
-void pass_timer_switch(cph_index::PassTimer& t, bool on) {
-    if (on && !t.ev0) HIP_CHECK(hipEventCreate(&t.ev0));
-    if (on && !t.ev1) HIP_CHECK(hipEventCreate(&t.ev1));
-    t.on = on;
-    t.timed = false;
+// The one place the host-form buffers of a set grow: the staged queries and one buffer per slot of the table, each on its
+// own (DevBuf::alloc keeps a buffer that is long enough), after one wait for the set's previous batch if any has to.
+// -> the table at the set's device addresses.
+RerankOuts reserve_group_scratch(GroupScratch& gs, size_t q_floats, uint64_t n, const RerankOuts& host) {
+    bool grow = gs.d_q.n < q_floats;
+    for (int i = 0; i < host.count; ++i) grow |= gs.out[i].n < n * host.o[i].stride;
+    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+    gs.d_q.alloc(q_floats);
+    RerankOuts dev = host;
+    for (int i = 0; i < host.count; ++i) {
+        gs.out[i].alloc(n * host.o[i].stride);
+        dev.o[i].p = gs.out[i].p;
+    }
+    return dev;
 }
 
-// Device time of the last timed pass in microseconds; waits for it.
-double pass_timer_us(cph_index::PassTimer& t) {
-    HIP_CHECK(hipEventSynchronize(t.ev1));
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t.ev0, t.ev1));
-    return (double)ms * 1e3;
+// ---- the three re-rankers ----
+void check_group_shape(uint64_t k, uint64_t g, uint64_t C) {
+    if (k < 1 || g < 1) throw InvalidArg("grouped search needs k >= 1 and group_size >= 1");
+    if (C > kGroupMaxCandidates)
+        throw InvalidArg("grouped search supports candidates <= " + std::to_string(kGroupMaxCandidates) + ", got " + std::to_string(C));
+    if (k > C || g > C || k * g > C)
+        throw InvalidArg("grouped search needs k * group_size <= candidates (got " + std::to_string(k) + " * " + std::to_string(g) +
+                         " > " + std::to_string(C) + ")");
 }
 
-void search_grouped_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_group_keys* keys,
-                         const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist,
-                         int32_t* keys_out, int32_t* counts, uint8_t* complete) {
+void check_group_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, const int32_t* key_of, uint64_t n_keys,
+                           uint64_t k, uint64_t g, const RerankOuts& o) {
+    if (!ids || !dist || !key_of || !o.all()) throw InvalidArg("null argument");
+    if (C < 1) throw InvalidArg("group rows: candidates must be >= 1");
+    check_group_shape(k, g, C);
+    if (n < 1 || n > 0x7FFFFFFFull || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("group rows: sizes out of range");
+    for (uint64_t i = 0; i < n * C; ++i)
+        if (ids[i] >= 0 && (uint64_t)ids[i] >= n_keys) throw InvalidArg("group rows: id out of range");
+}
+
+GroupArgs group_args(const int64_t* r_ids, const float* r_dist, uint64_t C, uint64_t k, uint64_t g, const int32_t* d_key_of, uint64_t n_ids,
+                     const uint32_t* d_rows, const RerankOuts& o) {
+    GroupArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.g = (uint32_t)g;
+    a.key_of = d_key_of;
+    a.n_ids = (uint32_t)n_ids;
+    a.rows = d_rows;
+    a.out_ids = o.at<int64_t>(0);
+    a.out_dist = o.at<float>(1);
+    a.out_keys = o.at<int32_t>(2);
+    a.out_counts = o.at<int32_t>(3);
+    a.out_complete = o.at<uint8_t>(4);
+    return a;
+}
+
+struct GroupedSearch {
+    uint64_t k, g, C;
+    static constexpr PassKind kind = kPassGrouped;
+    static constexpr bool keyed = true;
+    static constexpr const char* name = "grouped";
+    uint64_t tokens() const { return 1; }
+    void check_shape() const {
+        if (C < 1) throw InvalidArg("grouped search needs candidates >= 1");
+        check_group_shape(k, g, C);
+    }
+    void check_batch(uint64_t n) const { check_batch_size(n); }
+    void check_inputs(uint64_t) const {}
+    RerankOuts outs(int64_t* ids, float* dist, int32_t* keys, int32_t* counts, uint8_t* complete) const {
+        return {{{ids, 8 * k * g}, {dist, 4 * k * g}, {keys, 4 * k}, {counts, 4 * k}, {complete, 1}}, 5};
+    }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const RerankOuts& o, hipStream_t st) const {
+        group_rows(group_args(gs.r_ids.p, gs.r_dist.p, C, k, g, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o), (uint32_t)n, st);
+    }
+};
+
+// (An id at or above n_ids in given rows is no error: the statement counts it as padding.)
+void check_diverse_shape(uint64_t k, uint64_t C, float lam) {
+    if (k < 1) throw InvalidArg("diverse search needs k >= 1");
+    if (C > kDiverseMaxCandidates)
+        throw InvalidArg("diverse search supports candidates <= " + std::to_string(kDiverseMaxCandidates) + ", got " + std::to_string(C));
+    if (C < k) throw InvalidArg("diverse search needs k <= candidates (got " + std::to_string(k) + " > " + std::to_string(C) + ")");
+    if (!(lam >= 0.0f && lam <= 1.0f)) throw InvalidArg("diverse search needs lam in [0, 1]");
+}
+
+void check_diverse_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, uint64_t n_ids, uint64_t k, float lam,
+                             const RerankOuts& o) {
+    if (!ids || !dist || !o.all()) throw InvalidArg("null argument");
+    check_diverse_shape(k, C, lam);
+    if (n < 1 || n > 0x7FFFFFFFull || n_ids < 1 || n_ids > 0xFFFFFFFFull) throw InvalidArg("diverse rows: sizes out of range");
+}
+
+DiverseArgs diverse_args(const cph_index* h, const int64_t* r_ids, const float* r_dist, uint64_t C, uint64_t k, float lam, const RerankOuts& o) {
+    DiverseArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.a = lam;
+    a.b = 1.0f - lam;
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.n_ids = (uint32_t)h->size();
+    a.D = h->D;
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
+    a.out_ids = o.at<int64_t>(0);
+    a.out_dist = o.at<float>(1);
+    a.out_gap = o.at<float>(2);
+    return a;
+}
+
+// The pass runs against the handle's resident vectors and norms.
+struct DiverseSearch {
+    uint64_t k;
+    float lam;
+    uint64_t C;
+    static constexpr PassKind kind = kPassDiverse;
+    static constexpr bool keyed = false;
+    static constexpr const char* name = "diverse";
+    uint64_t tokens() const { return 1; }
+    void check_shape() const { check_diverse_shape(k, C, lam); }
+    void check_batch(uint64_t n) const { check_batch_size(n); }
+    void check_inputs(uint64_t) const {}
+    RerankOuts outs(int64_t* ids, float* dist, float* gap) const { return {{{ids, 8 * k}, {dist, 4 * k}, {gap, 4 * k}}, 3}; }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const RerankOuts& o, hipStream_t st) const {
+        diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, o), (uint32_t)n, st);
+    }
+};
+
+void check_maxsim_shape(uint64_t T, uint64_t C, uint64_t k) {
+    if (T < 1 || T > kMaxsimMaxTokens)
+        throw InvalidArg("maxsim search supports 1 <= tokens <= " + std::to_string(kMaxsimMaxTokens) + ", got " + std::to_string(T));
+    if (C < 1 || C > kMaxsimMaxCandidates)
+        throw InvalidArg("maxsim search supports 1 <= candidates <= " + std::to_string(kMaxsimMaxCandidates) + ", got " + std::to_string(C));
+    if (T * C > kMaxsimMaxEntries)
+        throw InvalidArg("maxsim search needs tokens * candidates <= " + std::to_string(kMaxsimMaxEntries) + " (got " + std::to_string(T) +
+                         " * " + std::to_string(C) + ")");
+    if (k < 1 || k > kMaxsimMaxK) throw InvalidArg("maxsim search supports 1 <= k <= " + std::to_string(kMaxsimMaxK) + ", got " + std::to_string(k));
+}
+
+void check_maxsim_tokens(const int32_t* n_tokens, uint64_t n, uint64_t T) {
+    for (uint64_t i = 0; n_tokens && i < n; ++i)
+        if (n_tokens[i] < 1 || (uint64_t)n_tokens[i] > T)
+            throw InvalidArg("n_tokens[" + std::to_string(i) + "] = " + std::to_string(n_tokens[i]) + " is outside [1, " + std::to_string(T) + "]");
+}
+
+void check_maxsim_batch(uint64_t n, uint64_t T) {
+    if (n > 0x7FFFFFFFull || n * T > 0x7FFFFFFFull)
+        throw InvalidArg("batch too large: maxsim search needs n * tokens <= 2147483647 (got " + std::to_string(n) + " * " + std::to_string(T) + ")");
+}
+
+void check_maxsim_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t C,
+                            const int32_t* key_of, uint64_t n_keys, uint64_t k, const RerankOuts& o) {
+    if (!ids || !dist || !key_of || !o.all()) throw InvalidArg("null argument");
+    check_maxsim_shape(T, C, k);
+    check_maxsim_batch(n, T);
+    if (n < 1 || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("maxsim rows: sizes out of range");
+    check_maxsim_tokens(n_tokens, n, T);
+}
+
+MaxsimArgs maxsim_args(const int64_t* r_ids, const float* r_dist, const int32_t* d_tokens, uint64_t T, uint64_t C, uint64_t k,
+                       const int32_t* d_key_of, uint64_t n_ids, const uint32_t* d_rows, const RerankOuts& o) {
+    MaxsimArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.n_tokens = d_tokens;
+    a.T = (uint32_t)T;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.key_of = d_key_of;
+    a.n_ids = (uint32_t)n_ids;
+    a.rows = d_rows;
+    a.out_keys = o.at<int32_t>(0);
+    a.out_score = o.at<float>(1);
+    a.out_hits = o.at<int32_t>(2);
+    a.out_rows = o.at<int64_t>(3);
+    a.out_found = o.at<int32_t>(4);
+    return a;
+}
+
+// n_tokens (host) -> the set's device copy, enqueued on `st`; null stays null.  One host wait: for the copy of the lengths
+// this set carried the last time (ev_tok), never for a kernel -- unless the buffers have to grow.  Called from the pass,
+// that is after `st` has been made to wait for the set's previous batch, whose kernel read d_tok.
+const int32_t* upload_maxsim_tokens(GroupScratch& gs, const int32_t* n_tokens, uint64_t n, hipStream_t st) {
+    if (!n_tokens) return nullptr;
+    if (gs.tok_used) HIP_CHECK(hipEventSynchronize(gs.ev_tok));
+    if (gs.pin_tok_n < n || gs.d_tok.n < n) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.pin_tok) HIP_CHECK(hipHostFree(gs.pin_tok));
+        gs.pin_tok = nullptr;
+        gs.pin_tok_n = 0;
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_tok), n * 2 * sizeof(int32_t), hipHostMallocDefault));
+        gs.pin_tok_n = n * 2;
+        gs.d_tok.alloc(n * 2);
+    }
+    if (!gs.ev_tok) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_tok, hipEventDisableTiming));
+    std::memcpy(gs.pin_tok, n_tokens, n * sizeof(int32_t));
+    HIP_CHECK(hipMemcpyAsync(gs.d_tok.p, gs.pin_tok, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(gs.ev_tok, st));
+    gs.tok_used = true;
+    return gs.d_tok.p;
+}
+
+// The queries are [n][T][dim]: the n * T token rows are one ordinary batch, and the pass joins the T rows of every query
+// by key.  n_tokens is on the host (null: every token is live).
+struct MaxsimSearch {
+    uint64_t T;
+    const int32_t* n_tokens;
+    uint64_t k, C;
+    static constexpr PassKind kind = kPassMaxsim;
+    static constexpr bool keyed = true;
+    static constexpr const char* name = "maxsim";
+    uint64_t tokens() const { return T; }
+    void check_shape() const { check_maxsim_shape(T, C, k); }
+    void check_batch(uint64_t n) const { check_maxsim_batch(n, T); }
+    void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
+    RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found) const {
+        return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}}, 5};
+    }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const RerankOuts& o, hipStream_t st) const {
+        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
+        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
+                    (uint32_t)n, h->device, st);
+    }
+};
+
+// ---- the entries, once ----
+// What every form checks under the mutex before it touches the device; false: n == 0, nothing to do.
+template <class Rerank>
+bool rerank_has_work(cph_index* h, const Rerank& f, const RerankCall& c) {
+    require_finalized(h);
+    f.check_shape();
+    check_filter_args(c);
+    f.check_batch(c.n);
+    if (c.n == 0) return false;
+    if (!c.q || !c.out.all()) throw InvalidArg("null argument");
+    f.check_inputs(c.n);
+    return true;
+}
+
+// The body of both single-handle forms: d_queries and the outputs `o` in device memory, filter_of on the host (a query's
+// filter serves its T tokens).
+template <class Rerank>
+void rerank_locked(cph_index* h, GroupScratch& gs, const Rerank& f, const RerankCall& c, const float* d_queries, const int32_t* d_key_of,
+                   const RerankOuts& o, hipStream_t st) {
+    const uint64_t T = f.tokens();
+    std::vector<int32_t> token_filter;
+    if (c.filter_of && T > 1) {
+        token_filter.resize(c.n * T);
+        for (uint64_t i = 0; i < c.n; ++i) std::fill_n(token_filter.begin() + i * T, T, c.filter_of[i]);
+    }
+    search_rows_then_pass(h, gs, d_queries, c.n * T, f.C, c.filters, c.F, token_filter.empty() ? c.filter_of : token_filter.data(), c.exact,
+                          h->pass_timer[Rerank::kind], st, [&] { f.pass(h, gs, c.n, d_key_of, o, st); });
+}
+
+// cph_search_X (stream == null: queries and outputs on the host, staged through the scratch set, and the call waits) and
+// cph_search_X_device (*stream: everything in device memory, enqueued only).
+template <class Rerank>
+void rerank_search(cph_index* h, const Rerank& f, const RerankCall& c, const cph_group_keys* keys, void* const* stream = nullptr) {
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!grouped_has_work(h, queries, n, k, g, C, filters, F, filter_of, ids, dist, keys_out, counts, complete)) return;
-    const int32_t* d_key_of = group_key_column(h, keys);
+    if (!rerank_has_work(h, f, c)) return;
+    const int32_t* d_key_of = Rerank::keyed ? group_key_column(h, keys) : nullptr;
     h->use_device();
+    if (stream) return rerank_locked(h, next_group_scratch(h), f, c, c.q, d_key_of, c.out, reinterpret_cast<hipStream_t>(*stream));
     hipStream_t st = own_stream(h);
     GroupScratch& gs = next_group_scratch(h);
-    const size_t slots = (size_t)n * k * g;
-    if (gs.d_q.n < n * h->dim || gs.o_ids.n < slots || gs.o_keys.n < n * k || gs.o_complete.n < n) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        gs.d_q.alloc(n * h->dim);
-        gs.o_ids.alloc(slots);
-        gs.o_dist.alloc(slots);
-        gs.o_keys.alloc(n * k);
-        gs.o_counts.alloc(n * k);
-        gs.o_complete.alloc(n);
-    }
-    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
-    search_grouped_locked(h, gs, gs.d_q.p, n, k, g, C, d_key_of, filters, F, filter_of, exact, gs.o_ids.p, gs.o_dist.p, gs.o_keys.p,
-                          gs.o_counts.p, gs.o_complete.p, st);
-    HIP_CHECK(hipMemcpyAsync(ids, gs.o_ids.p, slots * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(keys_out, gs.o_keys.p, n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(counts, gs.o_counts.p, n * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(complete, gs.o_complete.p, n, hipMemcpyDeviceToHost, st));
+    const size_t q_floats = (size_t)c.n * f.tokens() * h->dim;
+    const RerankOuts dev = reserve_group_scratch(gs, q_floats, c.n, c.out);
+    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, c.q, q_floats * 4, hipMemcpyHostToDevice, st));
+    rerank_locked(h, gs, f, c, gs.d_q.p, d_key_of, dev, st);
+    for (int i = 0; i < dev.count; ++i) HIP_CHECK(hipMemcpyAsync(c.out.o[i].p, dev.o[i].p, c.n * dev.o[i].stride, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
-void search_grouped_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C, const cph_group_keys* keys,
-                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
-                           float* d_dist, int32_t* d_keys, int32_t* d_counts, uint8_t* d_complete, void* stream) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!grouped_has_work(h, d_queries, n, k, g, C, filters, F, filter_of, d_ids, d_dist, d_keys, d_counts, d_complete)) return;
-    const int32_t* d_key_of = group_key_column(h, keys);
-    h->use_device();
-    search_grouped_locked(h, next_group_scratch(h), d_queries, n, k, g, C, d_key_of, filters, F, filter_of, exact, d_ids, d_dist, d_keys,
-                          d_counts, d_complete, reinterpret_cast<hipStream_t>(stream));
-}
-
-// cph_multi_search_grouped: keys[r] = the keys object of replica r (or keys == null: every replica's label column),
-// filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
-void multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uint64_t k, uint64_t g, uint64_t C,
-                          const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
-                          bool exact, int64_t* ids, float* dist, int32_t* keys_out, int32_t* counts, uint8_t* complete) {
+// cph_multi_search_X: sharded by query, never inside one.  keys[r] = the keys object of replica r (or keys == null: every
+// replica's label column), filters[f * R + r] = filter f on replica r; the queries, filter_of and the outputs are sliced
+// by shard, and shard_call(replica, the shard's call, its keys object, its first query) makes the re-ranker's own
+// cph_search_X call on it.
+template <class Rerank, class ShardCall>
+void rerank_multi(cph_multi* m, const Rerank& f, const RerankCall& c, const cph_group_keys* const* keys, ShardCall shard_call) {
     if (!m) throw InvalidArg("null handle");
     const uint32_t R = (uint32_t)m->reps.size();
-    const uint64_t dim = m->reps[0]->dim;
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
-        grouped_has_work(h, queries, n, k, g, C, filters, F, filter_of, ids, dist, keys_out, counts, complete);
-        if (keys && !keys[r]) throw InvalidArg("a grouped multi-device search needs one keys object per replica");
-        (void)group_key_column(h, keys ? keys[r] : nullptr);
-        check_replica_filters(h, filters, F, R, r);
+    const uint64_t q_floats = f.tokens() * m->reps[0]->dim;
+    check_filter_args(c);
+    multi_fan_out(m, c.n, [&](cph_index* h, uint32_t r) {
+        rerank_has_work(h, f, c);
+        if (Rerank::keyed) {
+            if (keys && !keys[r]) throw InvalidArg(std::string("a ") + Rerank::name + " multi-device search needs one keys object per replica");
+            (void)group_key_column(h, keys ? keys[r] : nullptr);
+        }
+        check_replica_filters(h, c.filters, c.F, R, r);
     }, [&] {
-        if (n && filter_of) check_filter_of(filter_of, n, F);
-        return n != 0;
+        if (c.n && c.filter_of) check_filter_of(c.filter_of, c.n, c.F);
+        return c.n != 0;
     }, [&](const Shard& s, size_t) {
-        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
-        return cph_search_grouped(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, g, C,
-                                  keys ? keys[s.replica] : nullptr, F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr,
-                                  exact ? 1 : 0, ids ? ids + s.lo * k * g : nullptr, dist ? dist + s.lo * k * g : nullptr,
-                                  keys_out ? keys_out + s.lo * k : nullptr, counts ? counts + s.lo * k : nullptr,
-                                  complete ? complete + s.lo : nullptr);
+        const std::vector<const cph_filter*> fr = replica_filters(c.filters, c.F, R, s.replica);
+        RerankCall sub = c;
+        sub.q = c.q ? c.q + s.lo * q_floats : nullptr;
+        sub.n = s.hi - s.lo;
+        sub.filters = c.F ? fr.data() : nullptr;
+        sub.filter_of = c.filter_of ? c.filter_of + s.lo : nullptr;
+        for (int i = 0; i < c.out.count; ++i)
+            sub.out.o[i].p = c.out.o[i].p ? static_cast<char*>(c.out.o[i].p) + s.lo * c.out.o[i].stride : nullptr;
+        return shard_call(m->reps[s.replica], sub, keys ? keys[s.replica] : nullptr, s.lo);
     });
 }
+
+// ---- what the kernel hooks share ----
+// A host array on the device (null: one element nobody reads).
+template <class T>
+DevBuf<T> uploaded(const T* src, size_t n) {
+    DevBuf<T> d(src ? n : 1);
+    if (src) HIP_CHECK(hipMemcpy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+}
+
+// Device twins of a hook's outputs that start as 0xA5 bytes (every slot the kernel leaves alone shows): `dev` is the table
+// the kernel writes, download() waits for the device and fills the host arrays.
+struct PoisonedOuts {
+    const RerankOuts host;
+    const uint64_t n;
+    DevBuf<uint8_t> buf[kMaxRerankOuts];
+    RerankOuts dev;
+    PoisonedOuts(const RerankOuts& host_, uint64_t n_) : host(host_), n(n_), dev(host_) {
+        for (int i = 0; i < host.count; ++i) {
+            buf[i].alloc(n * host.o[i].stride);
+            HIP_CHECK(hipMemset(buf[i].p, 0xA5, n * host.o[i].stride));
+            dev.o[i].p = buf[i].p;
+        }
+    }
+    void download() {
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int i = 0; i < host.count; ++i) HIP_CHECK(hipMemcpy(host.o[i].p, buf[i].p, n * host.o[i].stride, hipMemcpyDeviceToHost));
+    }
+};
 
 }  // namespace
 
@@ -5829,12 +6074,13 @@ int cph_group_keys_destroy(cph_group_keys* keys) {
     });
 }
 
+// ---- grouped search: the k best key groups, up to g rows of each (host_group.h) ----
 int cph_search_grouped(cph_index* h, const float* queries, uint64_t n, uint64_t k, uint64_t group_size, uint64_t candidates,
                        const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
                        int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts, uint8_t* complete) {
     return guarded([&] {
-        search_grouped_host(h, queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, ids, dist, group_keys,
-                            counts, complete);
+        const GroupedSearch f{k, group_size, candidates};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, dist, group_keys, counts, complete)}, keys);
     });
 }
 
@@ -5843,8 +6089,9 @@ int cph_search_grouped_device(cph_index* h, const float* d_queries, uint64_t n, 
                               int exact, int64_t* d_ids, float* d_dist, int32_t* d_group_keys, int32_t* d_counts, uint8_t* d_complete,
                               void* stream) {
     return guarded([&] {
-        search_grouped_device(h, d_queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, d_ids, d_dist,
-                              d_group_keys, d_counts, d_complete, stream);
+        const GroupedSearch f{k, group_size, candidates};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_ids, d_dist, d_group_keys, d_counts, d_complete)},
+                      keys, &stream);
     });
 }
 
@@ -5853,73 +6100,39 @@ int cph_multi_search_grouped(cph_multi* m, const float* queries, uint64_t n, uin
                              const int32_t* filter_of, int exact, int64_t* ids, float* dist, int32_t* group_keys, int32_t* counts,
                              uint8_t* complete) {
     return guarded([&] {
-        multi_search_grouped(m, queries, n, k, group_size, candidates, keys, filters, n_filters, filter_of, exact != 0, ids, dist, group_keys,
-                             counts, complete);
+        const GroupedSearch f{k, group_size, candidates};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, dist, group_keys, counts, complete)}, keys,
+                     [&](cph_index* h, const RerankCall& s, const cph_group_keys* key, uint64_t) {
+            return cph_search_grouped(h, s.q, s.n, k, group_size, candidates, key, s.filters, s.F, s.filter_of, s.exact ? 1 : 0,
+                                      s.out.at<int64_t>(0), s.out.at<float>(1), s.out.at<int32_t>(2), s.out.at<int32_t>(3),
+                                      s.out.at<uint8_t>(4));
+        });
     });
 }
 
 int cph_debug_time_grouped(cph_index* h, int on) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->use_device();
-        pass_timer_switch(h->group_timer, on != 0);
-    });
+    return guarded([&] { pass_timer_switch(h, kPassGrouped, on != 0); });
 }
 
 int cph_debug_last_group_rows_us(cph_index* h, double* us) {
-    return guarded([&] {
-        if (!h || !us) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->group_timer.timed) throw InvalidArg("no timed grouped search has run on this handle (cph_debug_time_grouped)");
-        h->use_device();
-        *us = pass_timer_us(h->group_timer);
-    });
+    return guarded([&] { pass_timer_us(h, kPassGrouped, us); });
 }
 
 int cph_group_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const int32_t* key_of,
                         uint64_t n_keys, const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist,
                         int32_t* out_keys, int32_t* out_counts, uint8_t* out_complete) {
     return guarded([&] {
-        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, out_ids, out_dist, out_keys, out_counts, out_complete);
+        const RerankOuts o = GroupedSearch{k, group_size, candidates}.outs(out_ids, out_dist, out_keys, out_counts, out_complete);
+        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, o);
         HIP_CHECK(hipSetDevice(device));
-        const size_t cells = (size_t)n * candidates, slots = (size_t)n * k * group_size;
-        DevBuf<int64_t> d_ids(cells), o_ids(slots);
-        DevBuf<float> d_dist(cells), o_dist(slots);
-        DevBuf<int32_t> d_key_of(n_keys), o_keys(n * k), o_counts(n * k);
-        DevBuf<uint32_t> d_rows(rows ? n_keys : 1);
-        DevBuf<uint8_t> o_complete(n);
-        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_key_of.p, key_of, n_keys * 4, hipMemcpyHostToDevice));
-        if (rows) HIP_CHECK(hipMemcpy(d_rows.p, rows, n_keys * 4, hipMemcpyHostToDevice));
-        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
-        HIP_CHECK(hipMemset(o_ids.p, 0xA5, slots * 8));
-        HIP_CHECK(hipMemset(o_dist.p, 0xA5, slots * 4));
-        HIP_CHECK(hipMemset(o_keys.p, 0xA5, n * k * 4));
-        HIP_CHECK(hipMemset(o_counts.p, 0xA5, n * k * 4));
-        HIP_CHECK(hipMemset(o_complete.p, 0xA5, n));
-        GroupArgs a{};
-        a.ids = d_ids.p;
-        a.dist = d_dist.p;
-        a.C = (uint32_t)candidates;
-        a.k = (uint32_t)k;
-        a.g = (uint32_t)group_size;
-        a.key_of = d_key_of.p;
-        a.n_ids = (uint32_t)n_keys;
-        a.rows = rows ? d_rows.p : nullptr;
-        a.out_ids = o_ids.p;
-        a.out_dist = o_dist.p;
-        a.out_keys = o_keys.p;
-        a.out_counts = o_counts.p;
-        a.out_complete = o_complete.p;
-        group_rows(a, (uint32_t)n, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out_ids, o_ids.p, slots * 8, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_dist, o_dist.p, slots * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_keys, o_keys.p, n * k * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_counts, o_counts.p, n * k * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_complete, o_complete.p, n, hipMemcpyDeviceToHost));
+        const DevBuf<int64_t> d_ids = uploaded(ids, n * candidates);
+        const DevBuf<float> d_dist = uploaded(dist, n * candidates);
+        const DevBuf<int32_t> d_key_of = uploaded(key_of, n_keys);
+        const DevBuf<uint32_t> d_rows = uploaded(rows, n_keys);
+        PoisonedOuts po(o, n);
+        group_rows(group_args(d_ids.p, d_dist.p, candidates, k, group_size, d_key_of.p, n_keys, rows ? d_rows.p : nullptr, po.dev), (uint32_t)n,
+                   nullptr);
+        po.download();
     });
 }
 
@@ -5927,174 +6140,51 @@ int cph_host_group_rows(const int64_t* ids, const float* dist, uint64_t n, uint6
                         const uint32_t* rows, uint64_t k, uint64_t group_size, int64_t* out_ids, float* out_dist, int32_t* out_keys,
                         int32_t* out_counts, uint8_t* out_complete) {
     return guarded([&] {
-        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size, out_ids, out_dist, out_keys, out_counts, out_complete);
+        check_group_rows_args(ids, dist, n, candidates, key_of, n_keys, k, group_size,
+                              GroupedSearch{k, group_size, candidates}.outs(out_ids, out_dist, out_keys, out_counts, out_complete));
         group_rows_host(ids, dist, n, (uint32_t)candidates, key_of, rows, (uint32_t)k, (uint32_t)group_size, out_ids, out_dist, out_keys,
                         out_counts, out_complete);
     });
 }
 
-}  // extern "C"
-
-// ---- diversified search: MMR re-ranking of a candidate row (device_diverse.h, host_diverse.h) -----------------------------
-// The grouped entries line for line: an ordinary search at k = C into the scratch rows, in internal ids, then
-// diverse_rows_kernel on the same stream against the handle's resident vectors and norms.
-namespace {
-
-// (An id at or above n_ids in given rows is no error: the statement counts it as padding.)
-void check_diverse_shape(uint64_t k, uint64_t C, float lam) {
-    if (k < 1) throw InvalidArg("diverse search needs k >= 1");
-    if (C > kDiverseMaxCandidates)
-        throw InvalidArg("diverse search supports candidates <= " + std::to_string(kDiverseMaxCandidates) + ", got " + std::to_string(C));
-    if (C < k) throw InvalidArg("diverse search needs k <= candidates (got " + std::to_string(k) + " > " + std::to_string(C) + ")");
-    if (!(lam >= 0.0f && lam <= 1.0f)) throw InvalidArg("diverse search needs lam in [0, 1]");
-}
-
-void check_diverse_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, uint64_t n_ids, uint64_t k, float lam,
-                             const int64_t* out_ids, const float* out_dist, const float* out_gap) {
-    if (!ids || !dist || !out_ids || !out_dist || !out_gap) throw InvalidArg("null argument");
-    check_diverse_shape(k, C, lam);
-    if (n < 1 || n > 0x7FFFFFFFull || n_ids < 1 || n_ids > 0xFFFFFFFFull) throw InvalidArg("diverse rows: sizes out of range");
-}
-
-DiverseArgs diverse_args(const cph_index* h, const int64_t* r_ids, const float* r_dist, uint64_t C, uint64_t k, float lam, int64_t* d_ids,
-                         float* d_dist, float* d_gap) {
-    DiverseArgs a{};
-    a.ids = r_ids;
-    a.dist = r_dist;
-    a.C = (uint32_t)C;
-    a.k = (uint32_t)k;
-    a.a = lam;
-    a.b = 1.0f - lam;
-    a.raw = h->d_raw.p;
-    a.norm_sq = h->d_norm.p;
-    a.n_ids = (uint32_t)h->size();
-    a.D = h->D;
-    a.rows = h->ids_input ? h->d_rows.p : nullptr;
-    a.out_ids = d_ids;
-    a.out_dist = d_dist;
-    a.out_gap = d_gap;
-    return a;
-}
-
-void search_diverse_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t C,
-                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
-                           float* d_dist, float* d_gap, hipStream_t st) {
-    search_rows_then_pass(h, gs, d_queries, n, C, filters, F, filter_of, exact, h->diverse_timer, st, [&] {
-        diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, d_ids, d_dist, d_gap), (uint32_t)n, st);
-    });
-}
-
-// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
-bool diverse_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
-                      uint32_t F, const int32_t* filter_of, const void* ids, const void* dist, const void* gap) {
-    require_finalized(h);
-    check_diverse_shape(k, C, lam);
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    if (n > 0x7FFFFFFFull) throw InvalidArg("batch too large");
-    if (n == 0) return false;
-    if (!queries || !ids || !dist || !gap) throw InvalidArg("null argument");
-    return true;
-}
-
-void search_diverse_host(cph_index* h, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
-                         uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist, float* gap) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!diverse_has_work(h, queries, n, k, lam, C, filters, F, filter_of, ids, dist, gap)) return;
-    h->use_device();
-    hipStream_t st = own_stream(h);
-    GroupScratch& gs = next_group_scratch(h);
-    const size_t slots = (size_t)n * k;
-    if (gs.d_q.n < n * h->dim || gs.o_ids.n < slots || gs.o_dist.n < slots || gs.o_gap.n < slots) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.d_q.n < n * h->dim) gs.d_q.alloc(n * h->dim);
-        if (gs.o_ids.n < slots) gs.o_ids.alloc(slots);
-        if (gs.o_dist.n < slots) gs.o_dist.alloc(slots);
-        if (gs.o_gap.n < slots) gs.o_gap.alloc(slots);
-    }
-    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, n * h->dim * 4, hipMemcpyHostToDevice, st));
-    search_diverse_locked(h, gs, gs.d_q.p, n, k, lam, C, filters, F, filter_of, exact, gs.o_ids.p, gs.o_dist.p, gs.o_gap.p, st);
-    HIP_CHECK(hipMemcpyAsync(ids, gs.o_ids.p, slots * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(gap, gs.o_gap.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-void search_diverse_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t C,
-                           const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact, int64_t* d_ids,
-                           float* d_dist, float* d_gap, void* stream) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!diverse_has_work(h, d_queries, n, k, lam, C, filters, F, filter_of, d_ids, d_dist, d_gap)) return;
-    h->use_device();
-    search_diverse_locked(h, next_group_scratch(h), d_queries, n, k, lam, C, filters, F, filter_of, exact, d_ids, d_dist, d_gap,
-                          reinterpret_cast<hipStream_t>(stream));
-}
-
-// cph_multi_search_diverse: filters[f * R + r] = filter f on replica r; filter_of is sliced with the queries.
-void multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t C, const cph_filter* const* filters,
-                          uint32_t F, const int32_t* filter_of, bool exact, int64_t* ids, float* dist, float* gap) {
-    if (!m) throw InvalidArg("null handle");
-    const uint32_t R = (uint32_t)m->reps.size();
-    const uint64_t dim = m->reps[0]->dim;
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
-        diverse_has_work(h, queries, n, k, lam, C, filters, F, filter_of, ids, dist, gap);
-        check_replica_filters(h, filters, F, R, r);
-    }, [&] {
-        if (n && filter_of) check_filter_of(filter_of, n, F);
-        return n != 0;
-    }, [&](const Shard& s, size_t) {
-        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
-        return cph_search_diverse(m->reps[s.replica], queries ? queries + s.lo * dim : nullptr, s.hi - s.lo, k, lam, C,
-                                  F ? fr.data() : nullptr, F, filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0,
-                                  ids ? ids + s.lo * k : nullptr, dist ? dist + s.lo * k : nullptr, gap ? gap + s.lo * k : nullptr);
-    });
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- diversified search: MMR re-ranking of a candidate row (host_diverse.h) ----
 int cph_search_diverse(cph_index* h, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
                        const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* dist,
                        float* gap) {
-    return guarded([&] { search_diverse_host(h, queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, ids, dist, gap); });
+    return guarded([&] {
+        const DiverseSearch f{k, lam, candidates};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, dist, gap)}, nullptr);
+    });
 }
 
 int cph_search_diverse_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
                               const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* d_ids,
                               float* d_dist, float* d_gap, void* stream) {
     return guarded([&] {
-        search_diverse_device(h, d_queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, d_ids, d_dist, d_gap, stream);
+        const DiverseSearch f{k, lam, candidates};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_ids, d_dist, d_gap)}, nullptr, &stream);
     });
 }
 
 int cph_multi_search_diverse(cph_multi* m, const float* queries, uint64_t n, uint64_t k, float lam, uint64_t candidates,
                              const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids,
                              float* dist, float* gap) {
-    return guarded([&] { multi_search_diverse(m, queries, n, k, lam, candidates, filters, n_filters, filter_of, exact != 0, ids, dist, gap); });
+    return guarded([&] {
+        const DiverseSearch f{k, lam, candidates};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, dist, gap)}, nullptr,
+                     [&](cph_index* h, const RerankCall& s, const cph_group_keys*, uint64_t) {
+            return cph_search_diverse(h, s.q, s.n, k, lam, candidates, s.filters, s.F, s.filter_of, s.exact ? 1 : 0, s.out.at<int64_t>(0),
+                                      s.out.at<float>(1), s.out.at<float>(2));
+        });
+    });
 }
 
 int cph_debug_time_diverse(cph_index* h, int on) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->use_device();
-        pass_timer_switch(h->diverse_timer, on != 0);
-    });
+    return guarded([&] { pass_timer_switch(h, kPassDiverse, on != 0); });
 }
 
 int cph_debug_last_diverse_rows_us(cph_index* h, double* us) {
-    return guarded([&] {
-        if (!h || !us) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->diverse_timer.timed) throw InvalidArg("no timed diverse search has run on this handle (cph_debug_time_diverse)");
-        h->use_device();
-        *us = pass_timer_us(h->diverse_timer);
-    });
+    return guarded([&] { pass_timer_us(h, kPassDiverse, us); });
 }
 
 int cph_diverse_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, uint64_t k, float lam,
@@ -6103,22 +6193,14 @@ int cph_diverse_rows_hook(cph_index* h, const int64_t* ids, const float* dist, u
         if (!h) throw InvalidArg("null handle");
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
-        check_diverse_rows_args(ids, dist, n, candidates, h->size(), k, lam, out_ids, out_dist, out_gap);
+        const RerankOuts o = DiverseSearch{k, lam, candidates}.outs(out_ids, out_dist, out_gap);
+        check_diverse_rows_args(ids, dist, n, candidates, h->size(), k, lam, o);
         h->use_device();
-        const size_t cells = (size_t)n * candidates, slots = (size_t)n * k;
-        DevBuf<int64_t> d_ids(cells), o_ids(slots);
-        DevBuf<float> d_dist(cells), o_dist(slots), o_gap(slots);
-        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
-        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
-        HIP_CHECK(hipMemset(o_ids.p, 0xA5, slots * 8));
-        HIP_CHECK(hipMemset(o_dist.p, 0xA5, slots * 4));
-        HIP_CHECK(hipMemset(o_gap.p, 0xA5, slots * 4));
-        diverse_rows(diverse_args(h, d_ids.p, d_dist.p, candidates, k, lam, o_ids.p, o_dist.p, o_gap.p), (uint32_t)n, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out_ids, o_ids.p, slots * 8, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_dist, o_dist.p, slots * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_gap, o_gap.p, slots * 4, hipMemcpyDeviceToHost));
+        const DevBuf<int64_t> d_ids = uploaded(ids, n * candidates);
+        const DevBuf<float> d_dist = uploaded(dist, n * candidates);
+        PoisonedOuts po(o, n);
+        diverse_rows(diverse_args(h, d_ids.p, d_dist.p, candidates, k, lam, po.dev), (uint32_t)n, nullptr);
+        po.download();
     });
 }
 
@@ -6128,217 +6210,21 @@ int cph_host_diverse_rows(const int64_t* ids, const float* dist, uint64_t n, uin
     return guarded([&] {
         if (!raw || !norm_sq) throw InvalidArg("null argument");
         if (D < 8 || D > 0xFFFFFFFFull || (D & 7)) throw InvalidArg("diverse rows: D must be a multiple of 8");
-        check_diverse_rows_args(ids, dist, n, candidates, n_ids, k, lam, out_ids, out_dist, out_gap);
+        check_diverse_rows_args(ids, dist, n, candidates, n_ids, k, lam, DiverseSearch{k, lam, candidates}.outs(out_ids, out_dist, out_gap));
         diverse_rows_host(ids, dist, n, (uint32_t)candidates, raw, norm_sq, n_ids, (uint32_t)D, rows, (uint32_t)k, lam, out_ids, out_dist,
                           out_gap);
     });
 }
 
-}  // extern "C"
-
-// ---- multi-vector search: MaxSim over key groups (device_maxsim.h, host_maxsim.h) ------------------------------------------
-// The grouped entries once more: the n * T token rows are an ordinary batch searched at k = C into the scratch rows, in
-// internal ids, then maxsim_rows_kernel on the same stream joins the T rows of every query by key.
-namespace {
-
-void check_maxsim_shape(uint64_t T, uint64_t C, uint64_t k) {
-    if (T < 1 || T > kMaxsimMaxTokens)
-        throw InvalidArg("maxsim search supports 1 <= tokens <= " + std::to_string(kMaxsimMaxTokens) + ", got " + std::to_string(T));
-    if (C < 1 || C > kMaxsimMaxCandidates)
-        throw InvalidArg("maxsim search supports 1 <= candidates <= " + std::to_string(kMaxsimMaxCandidates) + ", got " + std::to_string(C));
-    if (T * C > kMaxsimMaxEntries)
-        throw InvalidArg("maxsim search needs tokens * candidates <= " + std::to_string(kMaxsimMaxEntries) + " (got " + std::to_string(T) +
-                         " * " + std::to_string(C) + ")");
-    if (k < 1 || k > kMaxsimMaxK) throw InvalidArg("maxsim search supports 1 <= k <= " + std::to_string(kMaxsimMaxK) + ", got " + std::to_string(k));
-}
-
-void check_maxsim_tokens(const int32_t* n_tokens, uint64_t n, uint64_t T) {
-    for (uint64_t i = 0; n_tokens && i < n; ++i)
-        if (n_tokens[i] < 1 || (uint64_t)n_tokens[i] > T)
-            throw InvalidArg("n_tokens[" + std::to_string(i) + "] = " + std::to_string(n_tokens[i]) + " is outside [1, " + std::to_string(T) + "]");
-}
-
-void check_maxsim_batch(uint64_t n, uint64_t T) {
-    if (n > 0x7FFFFFFFull || n * T > 0x7FFFFFFFull)
-        throw InvalidArg("batch too large: maxsim search needs n * tokens <= 2147483647 (got " + std::to_string(n) + " * " + std::to_string(T) + ")");
-}
-
-void check_maxsim_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t C,
-                            const int32_t* key_of, uint64_t n_keys, uint64_t k, const void* o_keys, const void* o_score, const void* o_hits,
-                            const void* o_rows, const void* o_found) {
-    if (!ids || !dist || !key_of || !o_keys || !o_score || !o_hits || !o_rows || !o_found) throw InvalidArg("null argument");
-    check_maxsim_shape(T, C, k);
-    check_maxsim_batch(n, T);
-    if (n < 1 || n_keys < 1 || n_keys > 0xFFFFFFFFull) throw InvalidArg("maxsim rows: sizes out of range");
-    check_maxsim_tokens(n_tokens, n, T);
-}
-
-struct MaxsimOut {
-    int32_t* keys;
-    float* score;
-    int32_t* hits;
-    int64_t* rows;
-    int32_t* found;
-    bool all() const { return keys && score && hits && rows && found; }
-};
-
-MaxsimArgs maxsim_args(const int64_t* r_ids, const float* r_dist, const int32_t* d_tokens, uint64_t T, uint64_t C, uint64_t k,
-                       const int32_t* d_key_of, uint64_t n_ids, const uint32_t* d_rows, const MaxsimOut& o) {
-    MaxsimArgs a{};
-    a.ids = r_ids;
-    a.dist = r_dist;
-    a.n_tokens = d_tokens;
-    a.T = (uint32_t)T;
-    a.C = (uint32_t)C;
-    a.k = (uint32_t)k;
-    a.key_of = d_key_of;
-    a.n_ids = (uint32_t)n_ids;
-    a.rows = d_rows;
-    a.out_keys = o.keys;
-    a.out_score = o.score;
-    a.out_hits = o.hits;
-    a.out_rows = o.rows;
-    a.out_found = o.found;
-    return a;
-}
-
-// n_tokens (host) -> the set's device copy, enqueued on `st`; null stays null.  One host wait: for the copy of the lengths
-// this set carried the last time (ev_tok), never for a kernel -- unless the buffers have to grow.  Called from the pass,
-// that is after `st` has been made to wait for the set's previous batch, whose kernel read d_tok.
-const int32_t* upload_maxsim_tokens(GroupScratch& gs, const int32_t* n_tokens, uint64_t n, hipStream_t st) {
-    if (!n_tokens) return nullptr;
-    if (gs.tok_used) HIP_CHECK(hipEventSynchronize(gs.ev_tok));
-    if (gs.pin_tok_n < n || gs.d_tok.n < n) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.pin_tok) HIP_CHECK(hipHostFree(gs.pin_tok));
-        gs.pin_tok = nullptr;
-        gs.pin_tok_n = 0;
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_tok), n * 2 * sizeof(int32_t), hipHostMallocDefault));
-        gs.pin_tok_n = n * 2;
-        gs.d_tok.alloc(n * 2);
-    }
-    if (!gs.ev_tok) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_tok, hipEventDisableTiming));
-    std::memcpy(gs.pin_tok, n_tokens, n * sizeof(int32_t));
-    HIP_CHECK(hipMemcpyAsync(gs.d_tok.p, gs.pin_tok, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(gs.ev_tok, st));
-    gs.tok_used = true;
-    return gs.d_tok.p;
-}
-
-// MaxSim search: d_queries [n][T][dim] and the five outputs in device memory, n_tokens and filter_of on the host.  A
-// query's filter serves its T tokens.  The caller has checked the shape, n_tokens and the output pointers.
-void search_maxsim_locked(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k,
-                          uint64_t C, const int32_t* d_key_of, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
-                          bool exact, const MaxsimOut& o, hipStream_t st) {
-    std::vector<int32_t> token_filter;
-    if (filter_of) {
-        token_filter.resize(n * T);
-        for (uint64_t i = 0; i < n; ++i) std::fill_n(token_filter.begin() + i * T, T, filter_of[i]);
-    }
-    search_rows_then_pass(h, gs, d_queries, n * T, C, filters, F, filter_of ? token_filter.data() : nullptr, exact, h->maxsim_timer, st, [&] {
-        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
-        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
-                    (uint32_t)n, h->device, st);
-    });
-}
-
-// What both forms check under the mutex before they touch the device; false: n == 0, nothing to do.
-bool maxsim_has_work(cph_index* h, const void* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
-                     const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, const MaxsimOut& o) {
-    require_finalized(h);
-    check_maxsim_shape(T, C, k);
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    check_maxsim_batch(n, T);
-    if (n == 0) return false;
-    if (!queries || !o.all()) throw InvalidArg("null argument");
-    check_maxsim_tokens(n_tokens, n, T);
-    return true;
-}
-
-void search_maxsim_host(cph_index* h, const float* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
-                        const cph_group_keys* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
-                        const MaxsimOut& o) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!maxsim_has_work(h, queries, n, T, n_tokens, k, C, filters, F, filter_of, o)) return;
-    const int32_t* d_key_of = group_key_column(h, keys);
-    h->use_device();
-    hipStream_t st = own_stream(h);
-    GroupScratch& gs = next_group_scratch(h);
-    const size_t slots = (size_t)n * k, floats = (size_t)n * T * h->dim;
-    if (gs.d_q.n < floats || gs.o_ids.n < slots * T || gs.o_dist.n < slots || gs.o_keys.n < slots || gs.o_counts.n < slots || gs.o_found.n < n) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.d_q.n < floats) gs.d_q.alloc(floats);
-        if (gs.o_ids.n < slots * T) gs.o_ids.alloc(slots * T);
-        if (gs.o_dist.n < slots) gs.o_dist.alloc(slots);
-        if (gs.o_keys.n < slots) gs.o_keys.alloc(slots);
-        if (gs.o_counts.n < slots) gs.o_counts.alloc(slots);
-        if (gs.o_found.n < n) gs.o_found.alloc(n);
-    }
-    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, queries, floats * 4, hipMemcpyHostToDevice, st));
-    search_maxsim_locked(h, gs, gs.d_q.p, n, T, n_tokens, k, C, d_key_of, filters, F, filter_of, exact,
-                         MaxsimOut{gs.o_keys.p, gs.o_dist.p, gs.o_counts.p, gs.o_ids.p, gs.o_found.p}, st);
-    HIP_CHECK(hipMemcpyAsync(o.keys, gs.o_keys.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(o.score, gs.o_dist.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(o.hits, gs.o_counts.p, slots * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(o.rows, gs.o_ids.p, slots * T * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(o.found, gs.o_found.p, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-void search_maxsim_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
-                          const cph_group_keys* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of, bool exact,
-                          const MaxsimOut& o, void* stream) {
-    if (!h) throw InvalidArg("null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!maxsim_has_work(h, d_queries, n, T, n_tokens, k, C, filters, F, filter_of, o)) return;
-    const int32_t* d_key_of = group_key_column(h, keys);
-    h->use_device();
-    search_maxsim_locked(h, next_group_scratch(h), d_queries, n, T, n_tokens, k, C, d_key_of, filters, F, filter_of, exact, o,
-                         reinterpret_cast<hipStream_t>(stream));
-}
-
-// cph_multi_search_maxsim: sharded by query, never inside one; keys[r] = the keys object of replica r (or keys == null:
-// every replica's label column), filters[f * R + r] = filter f on replica r; n_tokens and filter_of are sliced with the
-// queries.
-void multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint64_t T, const int32_t* n_tokens, uint64_t k, uint64_t C,
-                         const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
-                         bool exact, const MaxsimOut& o) {
-    if (!m) throw InvalidArg("null handle");
-    const uint32_t R = (uint32_t)m->reps.size();
-    const uint64_t dim = m->reps[0]->dim;
-    if (F && !filters) throw InvalidArg("null argument");
-    if (!filter_of && F > 1) throw InvalidArg("several filters need filter_of (the filter of every query)");
-    multi_fan_out(m, n, [&](cph_index* h, uint32_t r) {
-        maxsim_has_work(h, queries, n, T, n_tokens, k, C, filters, F, filter_of, o);
-        if (keys && !keys[r]) throw InvalidArg("a maxsim multi-device search needs one keys object per replica");
-        (void)group_key_column(h, keys ? keys[r] : nullptr);
-        check_replica_filters(h, filters, F, R, r);
-    }, [&] {
-        if (n && filter_of) check_filter_of(filter_of, n, F);
-        return n != 0;
-    }, [&](const Shard& s, size_t) {
-        const std::vector<const cph_filter*> fr = replica_filters(filters, F, R, s.replica);
-        return cph_search_maxsim(m->reps[s.replica], queries ? queries + s.lo * T * dim : nullptr, s.hi - s.lo, T,
-                                 n_tokens ? n_tokens + s.lo : nullptr, k, C, keys ? keys[s.replica] : nullptr, F ? fr.data() : nullptr, F,
-                                 filter_of ? filter_of + s.lo : nullptr, exact ? 1 : 0, o.keys ? o.keys + s.lo * k : nullptr,
-                                 o.score ? o.score + s.lo * k : nullptr, o.hits ? o.hits + s.lo * k : nullptr,
-                                 o.rows ? o.rows + s.lo * k * T : nullptr, o.found ? o.found + s.lo : nullptr);
-    });
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- multi-vector search: MaxSim over key groups (host_maxsim.h) ----
 int cph_search_maxsim(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
                       uint64_t candidates, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
                       const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
                       int32_t* out_found) {
     return guarded([&] {
-        search_maxsim_host(h, queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
-                           MaxsimOut{out_keys, out_score, out_hits, out_rows, out_found});
+        const MaxsimSearch f{tokens, n_tokens, k, candidates};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(out_keys, out_score, out_hits, out_rows, out_found)},
+                      keys);
     });
 }
 
@@ -6347,8 +6233,9 @@ int cph_search_maxsim_device(cph_index* h, const float* d_queries, uint64_t n, u
                              const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score, int32_t* d_hits, int64_t* d_rows,
                              int32_t* d_found, void* stream) {
     return guarded([&] {
-        search_maxsim_device(h, d_queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
-                             MaxsimOut{d_keys, d_score, d_hits, d_rows, d_found}, stream);
+        const MaxsimSearch f{tokens, n_tokens, k, candidates};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_keys, d_score, d_hits, d_rows, d_found)}, keys,
+                      &stream);
     });
 }
 
@@ -6357,62 +6244,40 @@ int cph_multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint
                             const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
                             int32_t* out_found) {
     return guarded([&] {
-        multi_search_maxsim(m, queries, n, tokens, n_tokens, k, candidates, keys, filters, n_filters, filter_of, exact != 0,
-                            MaxsimOut{out_keys, out_score, out_hits, out_rows, out_found});
+        const MaxsimSearch f{tokens, n_tokens, k, candidates};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(out_keys, out_score, out_hits, out_rows, out_found)},
+                     keys, [&](cph_index* h, const RerankCall& s, const cph_group_keys* key, uint64_t lo) {
+            return cph_search_maxsim(h, s.q, s.n, tokens, n_tokens ? n_tokens + lo : nullptr, k, candidates, key, s.filters, s.F, s.filter_of,
+                                     s.exact ? 1 : 0, s.out.at<int32_t>(0), s.out.at<float>(1), s.out.at<int32_t>(2), s.out.at<int64_t>(3),
+                                     s.out.at<int32_t>(4));
+        });
     });
 }
 
 int cph_debug_time_maxsim(cph_index* h, int on) {
-    return guarded([&] {
-        if (!h) throw InvalidArg("null handle");
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->use_device();
-        pass_timer_switch(h->maxsim_timer, on != 0);
-    });
+    return guarded([&] { pass_timer_switch(h, kPassMaxsim, on != 0); });
 }
 
 int cph_debug_last_maxsim_rows_us(cph_index* h, double* us) {
-    return guarded([&] {
-        if (!h || !us) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->maxsim_timer.timed) throw InvalidArg("no timed maxsim search has run on this handle (cph_debug_time_maxsim)");
-        h->use_device();
-        *us = pass_timer_us(h->maxsim_timer);
-    });
+    return guarded([&] { pass_timer_us(h, kPassMaxsim, us); });
 }
 
 int cph_maxsim_rows_hook(int device, const int64_t* ids, const float* dist, uint64_t n, uint64_t tokens, const int32_t* n_tokens,
                          uint64_t candidates, const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys,
                          float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found) {
     return guarded([&] {
-        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k, out_keys, out_score, out_hits, out_rows,
-                               out_found);
+        const RerankOuts o = MaxsimSearch{tokens, n_tokens, k, candidates}.outs(out_keys, out_score, out_hits, out_rows, out_found);
+        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k, o);
         HIP_CHECK(hipSetDevice(device));
-        const size_t cells = (size_t)n * tokens * candidates, slots = (size_t)n * k;
-        DevBuf<int64_t> d_ids(cells), o_rows(slots * tokens);
-        DevBuf<float> d_dist(cells), o_score(slots);
-        DevBuf<int32_t> d_key_of(n_keys), d_tok(n), o_keys(slots), o_hits(slots), o_found(n);
-        DevBuf<uint32_t> d_rows(rows ? n_keys : 1);
-        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_key_of.p, key_of, n_keys * 4, hipMemcpyHostToDevice));
-        if (n_tokens) HIP_CHECK(hipMemcpy(d_tok.p, n_tokens, n * 4, hipMemcpyHostToDevice));
-        if (rows) HIP_CHECK(hipMemcpy(d_rows.p, rows, n_keys * 4, hipMemcpyHostToDevice));
-        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
-        HIP_CHECK(hipMemset(o_keys.p, 0xA5, slots * 4));
-        HIP_CHECK(hipMemset(o_score.p, 0xA5, slots * 4));
-        HIP_CHECK(hipMemset(o_hits.p, 0xA5, slots * 4));
-        HIP_CHECK(hipMemset(o_rows.p, 0xA5, slots * tokens * 8));
-        HIP_CHECK(hipMemset(o_found.p, 0xA5, n * 4));
+        const DevBuf<int64_t> d_ids = uploaded(ids, n * tokens * candidates);
+        const DevBuf<float> d_dist = uploaded(dist, n * tokens * candidates);
+        const DevBuf<int32_t> d_key_of = uploaded(key_of, n_keys), d_tok = uploaded(n_tokens, n);
+        const DevBuf<uint32_t> d_rows = uploaded(rows, n_keys);
+        PoisonedOuts po(o, n);
         maxsim_rows(maxsim_args(d_ids.p, d_dist.p, n_tokens ? d_tok.p : nullptr, tokens, candidates, k, d_key_of.p, n_keys,
-                                rows ? d_rows.p : nullptr, MaxsimOut{o_keys.p, o_score.p, o_hits.p, o_rows.p, o_found.p}),
+                                rows ? d_rows.p : nullptr, po.dev),
                     (uint32_t)n, device, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out_keys, o_keys.p, slots * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_score, o_score.p, slots * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_hits, o_hits.p, slots * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_rows, o_rows.p, slots * tokens * 8, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_found, o_found.p, n * 4, hipMemcpyDeviceToHost));
+        po.download();
     });
 }
 
@@ -6420,14 +6285,15 @@ int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint
                          const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score,
                          int32_t* out_hits, int64_t* out_rows, int32_t* out_found) {
     return guarded([&] {
-        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k, out_keys, out_score, out_hits, out_rows,
-                               out_found);
+        check_maxsim_rows_args(ids, dist, n, tokens, n_tokens, candidates, key_of, n_keys, k,
+                               MaxsimSearch{tokens, n_tokens, k, candidates}.outs(out_keys, out_score, out_hits, out_rows, out_found));
         maxsim_rows_host(ids, dist, n, (uint32_t)tokens, n_tokens, (uint32_t)candidates, key_of, n_keys, rows, (uint32_t)k, out_keys,
                          out_score, out_hits, out_rows, out_found);
     });
 }
 
 }  // extern "C"
+
 
 // ---- the metric (cph_set_metric; device_normalize.h) -------------------------------------------------------------------
 static const char* metric_name(uint32_t metric) { return metric == CPH_METRIC_COSINE ? "cosine" : "l2"; }

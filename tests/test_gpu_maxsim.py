@@ -459,3 +459,48 @@ def test_other_searches_are_untouched(cph, gold):
         assert same_bytes(ix.search_batch(Q, 10), before)
     ix.result_ids = "internal"
     assert np.array_equal(ix.search_batch(Q, 10)[0], gold["S/g16/b1/plain/k10/ids"][:len(Q)])       # (Q: the first 12 queries)
+
+
+def test_rerankers_share_scratch_at_growing_shapes(cph, gold):
+    """Grouped, maxsim and diverse calls take turns on the scratch sets of ONE handle, four calls each (one per set), at shapes
+    chosen so that a later call needs a longer buffer in one output slot while every other size a call could compare is
+    already long enough: with n = 4, grouped (k=2, g=1) leaves 8 slots per output, maxsim (T=8, k=8) 256 rows but 32 scores,
+    grouped (k=8, g=8) then needs 256 distances with n * k = 32 and n = 4 unchanged.  Every answer is the model's, byte for
+    byte; then the same sequence in the _device forms into preallocated outputs on one stream."""
+    import torch
+    from diverse_model import diverse_model_batch
+    from group_model import group_model_batch
+    ix, _ = _open(cph, gold, None, "g16", 1)
+    Q = gold["Q/g16"][:4]
+    key_of = _keys_for(ix.size, 2).astype(np.int32)
+    ix.set_labels(key_of, ids="internal")
+    tok, _ = _tokens(Q, 4, 8, 5)
+    tok[-1, 1:] = tok[0, :7]                                # (every token is live: no n_tokens)
+    C_ = 64
+    was, ix.result_ids = ix.result_ids, "internal"
+    rows, rows_tok = ix.search_batch(Q, C_), ix.search_batch(tok.reshape(32, -1), C_)
+    ix.result_ids = was
+
+    def pair(s, js):
+        return ix.exact_l2(ix.get_vectors(s, 1)[0], np.asarray(js, np.int64))
+    want = {("grouped", 2, 1): group_model_batch(*rows, key_of, 2, 1), ("grouped", 8, 8): group_model_batch(*rows, key_of, 8, 8),
+            ("maxsim", 8): maxsim_model_batch(rows_tok[0].reshape(4, 8, C_), rows_tok[1].reshape(4, 8, C_), None, key_of, ix.size, 8),
+            ("diverse", 16): diverse_model_batch(*rows, 16, 0.5, pair, ix.size)}
+    sequence = [("grouped", 2, 1), ("maxsim", 8), ("grouped", 8, 8), ("diverse", 16), ("grouped", 8, 8)]
+    dev = torch.device("cuda", 0)
+    Qd, Td, st = torch.from_numpy(Q).to(dev), torch.from_numpy(tok).to(dev), torch.cuda.Stream(dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    for device_form in (False, True):
+        for step, call in enumerate(sequence):
+            for rep in range(4):
+                if device_form:
+                    out = [torch.full(w.shape, 9, dtype=getattr(torch, w.dtype.name), device=dev) for w in want[call]]
+                    st.wait_stream(torch.cuda.current_stream(dev))
+                    fn = getattr(ix, f"search_{call[0]}_device")
+                    got = fn(Td if call[0] == "maxsim" else Qd, *call[1:], candidates=C_, out=out, stream=st)
+                    st.synchronize()
+                    got = [t.cpu().numpy().view(w.dtype) for t, w in zip(got, want[call])]
+                else:
+                    got = getattr(ix, f"search_{call[0]}")(tok if call[0] == "maxsim" else Q, *call[1:], candidates=C_)
+                    got = [np.asarray(g).view(w.dtype) for g, w in zip(got, want[call])]
+                assert same_bytes(got, want[call]), (device_form, step, call, rep)

@@ -1059,6 +1059,61 @@ int cph_metric_stats(cph_index* h, uint64_t out[2]);
 int cph_normalize_rows_hook(int device, const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad);
 int cph_host_normalize_rows(const float* x, uint64_t n, uint64_t dim, float* out, uint64_t* bad_count, uint64_t* first_bad);
 
+/* ---- the inner-product metric ---------------------------------------------------------------- */
+/* CPH_METRIC_IP: maximum inner product search.  Every search returns score = -(q.x): smaller is better and rows ascend,
+ * as with the other metrics; ties and padding (-1 / FLT_MAX) mean what they meant.
+ *
+ * With M2 >= max |x|^2 the index stores x~ = [x, sqrt(M2 - |x|^2)], dim + 1 coordinates, and searches q~ = [q, 0]:
+ * |q~ - x~|^2 = |q|^2 + M2 - 2 q.x falls as q.x grows, so the graph, exact, tail and filter kernels of the L2 metric rank
+ * by inner product as they stand.  One kernel in front of them (csrc/device_ip.h) augments rows on the way in and queries
+ * on the way into every batch, where it also writes c = |q|^2 + M2 per query; one kernel behind them turns every
+ * distance whose id is not padding into 0.5 * (d - c), one subtraction and one multiplication, each rounded once.  Both
+ * run on the batch's stream, once per batch; cph_search_batch_device stays enqueue-only.  |x|^2 is the cosine metric's
+ * sum (64 lane sums, xor butterfly), the root is correctly rounded, and the first dim stored coordinates are the
+ * caller's bits.
+ *
+ * widths: cph_set_metric_ip / cph_multi_set_metric_ip, on an empty handle only, make the metric CPH_METRIC_IP (what
+ *     cph_get_metric reports and files carry), the stored width dim + 1 and the padded width next_pow2(dim + 1); they
+ *     refuse when that exceeds 2048, so dim is 8..2047.  (cph_set_metric itself keeps taking L2 and cosine only and
+ *     refuses 2 like every other value, as it did before this metric existed: callers and tests rely on that.)  The extra coordinate is free wherever
+ *     dim is not a power of two and doubles the padded width at dim = 16, 32, ..., 1024.  cph_dim keeps reporting the
+ *     caller's dim; rows and queries come in at that width.
+ * bound: cph_set_ip_bound(h, M2) on an empty IP handle; 0 (the default) takes the largest |x|^2 of the rows of the
+ *     cph_build call, found on the device.  cph_get_ip_bound: the M2 of the rows the handle holds (before a build: the
+ *     bound set).  Every replica holds it; cph_compact keeps it and does not augment again.
+ * rows in: cph_build, cph_multi_build and cph_add refuse (CPH_INVALID_ARGUMENT, naming the first such row and the count,
+ *     the handle as it was) a row with a NaN, an Inf or an overflowing |x|^2, and a row with |x|^2 > M2; cph_add checks
+ *     against the M2 of the index, which only a rebuild with a larger bound raises.  A zero row is a good row.  What the
+ *     index stores, replicates, writes to files and returns from cph_get_vectors are the stored rows, dim + 1 wide.
+ * queries in: a query with a NaN, an Inf or an overflowing norm searches as the zero vector with c = M2 (every score is
+ *     then 0 up to rounding); no call refuses it.
+ * single queries: cph_search runs as a batch of one (the coalesced path hands a row to its caller from inside the search
+ *     kernel, before an epilogue could run).
+ * hooks: cph_encode_query, cph_entry_point, cph_exact_l2, cph_fastscan_block and the calibration hooks act on vectors of
+ *     the stored width as given.
+ * not served yet, refused with CPH_INVALID_ARGUMENT before any output is written: cph_range_*, cph_search_grouped*,
+ *     cph_search_diverse*, cph_search_maxsim* (and their multi forms), cph_parts_set_metric(CPH_METRIC_IP), cph_save and
+ *     cph_load.
+ * files: cph_save_native writes format 5 (csrc/native_file.h): format 4's record with version 5, metric 2, M2 and a zero
+ *     word, which every older reader refuses; cph_load_native restores M2 and refuses a file of another metric.
+ * cph_metric_stats counts the launches of both kernels and the bytes of the augmented-query and c buffers. */
+enum { CPH_METRIC_IP = 2 };
+int cph_set_metric_ip(cph_index* h);
+int cph_multi_set_metric_ip(cph_multi* m);
+int cph_set_ip_bound(cph_index* h, float max_sq_norm);
+int cph_get_ip_bound(cph_index* h, float* m2);
+int cph_multi_set_ip_bound(cph_multi* m, float max_sq_norm);
+int cph_multi_get_ip_bound(cph_multi* m, float* m2);
+/* Test hooks: the kernels on host arrays.  x [n][dim] -> out [n][dim + 1]; mode 0: rows against max_sq_norm, 1: rows
+ * against the largest |x|^2 of the good rows of x (found by the max pass), 2: queries, which also write c [n] (c may be
+ * null otherwise).  The device outputs start as 0xA5 bytes.  *m2: the bound used; counters = {bad rows, rows over the
+ * bound, the lowest row of either kind or UINT64_MAX}.  The epilogue hook rewrites dist [n][k] in place; pinned != 0
+ * runs it on pinned, device-mapped host memory.  cph_host_ip_* are the host statement (csrc/host_ip.h, no HIP call). */
+int cph_ip_augment_hook(int device, const float* x, uint64_t n, uint64_t dim, int mode, float max_sq_norm, float* out, float* c, float* m2, uint64_t counters[3]);
+int cph_ip_epilogue_hook(int device, const int64_t* ids, float* dist, uint64_t n, uint64_t k, const float* c, int pinned);
+int cph_host_ip_augment(const float* x, uint64_t n, uint64_t dim, int mode, float max_sq_norm, float* out, float* c, float* m2, uint64_t counters[3]);
+int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k, const float* c);
+
 #ifdef __cplusplus
 }
 #endif

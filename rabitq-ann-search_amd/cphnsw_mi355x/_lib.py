@@ -9,6 +9,7 @@ from . import build as _build
 OK, INVALID_ARGUMENT, RUNTIME_ERROR, OUT_OF_MEMORY, NOT_IMPLEMENTED = range(5)
 IDS_INTERNAL, IDS_INPUT = 0, 1      # cph_set_result_ids
 METRIC_L2, METRIC_COSINE = 0, 1     # cph_set_metric
+METRIC_IP = 2
 
 # name -> (restype, argtypes); the list is checked against the header by tests/test_abi.py
 SYMBOLS = {
@@ -256,6 +257,18 @@ SYMBOLS = {
                                           C.POINTER(C.c_uint64)]),
     "cph_host_normalize_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]),
+    "cph_set_metric_ip": (C.c_int, [C.c_void_p]),
+    "cph_multi_set_metric_ip": (C.c_int, [C.c_void_p]),
+    "cph_set_ip_bound": (C.c_int, [C.c_void_p, C.c_float]),
+    "cph_get_ip_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cph_multi_set_ip_bound": (C.c_int, [C.c_void_p, C.c_float]),
+    "cph_multi_get_ip_bound": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cph_ip_augment_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+    "cph_ip_epilogue_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]),
+    "cph_host_ip_augment": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+    "cph_host_ip_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
 _LIB = None

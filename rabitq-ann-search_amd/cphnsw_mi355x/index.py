@@ -248,11 +248,22 @@ class CPIndex:
     same way with one more kernel launch per batch, so the squared-L2 kernels report 1 - cos; a query without a
     direction is searched as the zero vector (every distance about 0.5) and is not refused.  The hooks (encode_query,
     entry_point, exact_l2, fastscan_block, calib_samples_debug) act on the vector as given.  The metric is fixed at
-    construction; save_native / load_native carry it, save / load (the reference's format) do not and are refused."""
+    construction; save_native / load_native carry it, save / load (the reference's format) do not and are refused.
 
-    _METRICS = {"l2": _lib.METRIC_L2, "cosine": _lib.METRIC_COSINE}
+    `metric="ip"`: maximum inner product search; every search returns score = -(q . x), ascending, so the best row has the
+    most negative score.  The index stores [x, sqrt(M2 - |x|^2)], dim + 1 coordinates, for a bound M2 >= max |x|^2 and
+    searches [q, 0]: the squared-L2 kernels then rank by inner product, one kernel in front of a batch augments its
+    queries and one behind it turns distances into scores (two more launches per batch).  `max_norm` is sqrt(M2), a bound
+    on the length of every row ever stored, add() included; None takes the longest row of the build() call.  build() and
+    add() refuse (ValueError naming the first such row) a row with NaN or Inf, an overflowing norm, or a length above
+    the bound; a query with NaN or Inf searches as the zero vector.  `dim` stays the caller's; the padded width is
+    next_pow2(dim + 1), so dim = 128 pads to 256 (dim <= 2047).  get_vectors(stored=True) returns the stored rows,
+    `ip_bound` is M2.  search() runs as a batch of one.  range_search, search_grouped, search_diverse, search_maxsim,
+    partition=True and save / load are not available yet and raise; save_native / load_native carry the metric and M2."""
 
-    def __init__(self, dim, bits=1, device=None, devices=None, partition=False, metric="l2"):
+    _METRICS = {"l2": _lib.METRIC_L2, "cosine": _lib.METRIC_COSINE, "ip": _lib.METRIC_IP}
+
+    def __init__(self, dim, bits=1, device=None, devices=None, partition=False, metric="l2", max_norm=None):
         self._h = C.c_void_p()
         self._m = None               # cph_multi handle of a multi-device index
         self._p = None               # cph_parts handle of a partitioned index
@@ -265,8 +276,19 @@ class CPIndex:
         self._exact_threshold = 0
         self._columns = {}           # attribute columns (set_column): name -> slot on the handle
         if metric not in self._METRICS:
-            raise ValueError(f'metric must be "l2" or "cosine", not {metric!r}')
+            raise ValueError(f'metric must be "l2", "cosine" or "ip", not {metric!r}')
         self._metric = metric
+        self._sdim = self._dim + (1 if metric == "ip" else 0)      # the width of the stored rows
+        if metric == "ip" and partition:
+            raise ValueError('partition=True does not take metric="ip" yet: the parts would need one global bound')
+        if max_norm is not None and metric != "ip":
+            raise ValueError('max_norm belongs to metric="ip"')
+        if max_norm is not None and not (0 < float(max_norm) < float("inf")):
+            raise ValueError("max_norm must be a positive finite length (None: the longest row of build())")
+        # M2 as the float32 square of the float32 length (what the kernels compare squared norms with)
+        bound = None if max_norm is None else float(np.float32(max_norm) * np.float32(max_norm))
+        if bound is not None and not (0 < bound < float("inf")):
+            raise ValueError("max_norm squared must be a positive finite float32")
         if partition and (devices is None or device is not None):
             raise ValueError("partition=True needs devices=[...] (one part per listed device), not device")
         if devices is not None:
@@ -304,25 +326,44 @@ class CPIndex:
                 self._reps.append(h)
             self._h = self._reps[0]  # hooks, get_vectors, ...: replica 0
             self._next_dev = 0       # search_batch_device: alternates between the replicas on the queries' device
-            if metric != "l2":
+            if metric == "ip":
+                _lib.check(_lib.lib().cph_multi_set_metric_ip(m))
+            elif metric != "l2":
                 _lib.check(_lib.lib().cph_multi_set_metric(m, self._METRICS[metric]))
+            if bound is not None:
+                _lib.check(_lib.lib().cph_multi_set_ip_bound(m, bound))
             return
         if device is None:
             device = _default_device()
         self._device = int(device)
         self._devices = [self._device]
         _lib.check(_lib.lib().cph_create(int(dim), int(bits), int(device), C.byref(self._h)))
-        if metric != "l2":
+        if metric == "ip":
+            _lib.check(_lib.lib().cph_set_metric_ip(self._h))
+        elif metric != "l2":
             _lib.check(_lib.lib().cph_set_metric(self._h, self._METRICS[metric]))
+        if bound is not None:
+            _lib.check(_lib.lib().cph_set_ip_bound(self._h, bound))
 
     @property
     def metric(self):
-        """"l2" or "cosine": fixed at construction."""
+        """"l2", "cosine" or "ip": fixed at construction."""
         return self._metric
 
+    @property
+    def ip_bound(self):
+        """metric="ip": M2, the squared-length bound of the rows the index holds (before build(): max_norm squared, 0.0
+        when it comes from the data)."""
+        if self._metric != "ip":
+            raise ValueError('ip_bound belongs to metric="ip"')
+        m2 = C.c_float(0.0)
+        _lib.check(_lib.lib().cph_get_ip_bound(self._h, C.byref(m2)))
+        return float(m2.value)
+
     def metric_stats(self):
-        """(launches of the normalisation kernel, bytes of normalised-query buffers), summed over the replicas / parts:
-        both 0 on an "l2" index, which launches and allocates nothing for the metric.  Counted on the host."""
+        """(launches of the metric's kernels, bytes of the metric's query buffers), summed over the replicas / parts:
+        both 0 on an "l2" index, which launches and allocates nothing for the metric.  "cosine": the normalisation
+        kernel; "ip": the augmenting kernel, the max pass of build() and the score epilogue.  Counted on the host."""
         tot = [0, 0]
         for h in self._replicas():
             out = (C.c_uint64 * 2)()
@@ -393,6 +434,7 @@ class CPIndex:
         v._owner = self
         v._dim, v._bits = self._dim, self._bits
         v._metric = self._metric
+        v._sdim = self._sdim
         v._device = self._devices[i]
         v._devices = [self._devices[i]]
         v._result_ids = "input" if self.is_finalized else "internal"
@@ -1851,15 +1893,17 @@ class CPIndex:
         _lib.check(_lib.lib().cph_order_queries(self._h, keys.ctypes.data, len(keys), out.ctypes.data))
         return out
 
-    def get_vectors(self, first=0, count=None):
+    def get_vectors(self, first=0, count=None, stored=False):
         """Stored vectors of internal ids [first, first+count) as float32 (count, dim) (internal ids also when
-        result_ids is "input").  metric="cosine": the rows as stored, x / (sqrt(2) |x|), not the rows given to build()."""
+        result_ids is "input").  metric="cosine": the rows as stored, x / (sqrt(2) |x|), not the rows given to build().
+        metric="ip": the first dim columns of the stored rows, which are the rows given to build() bit for bit;
+        stored=True returns all dim + 1 columns, the last one sqrt(M2 - |x|^2)."""
         self._no_parts("get_vectors")
         if count is None:
             count = self.size - first
-        out = np.empty((count, self._dim), np.float32)
+        out = np.empty((count, self._sdim), np.float32)
         _lib.check(_lib.lib().cph_get_vectors(self._h, int(first), int(count), out.ctypes.data))
-        return out
+        return out if stored or self._sdim == self._dim else np.ascontiguousarray(out[:, :self._dim])
 
     def internal_to_input_rows(self, base, chunk=1 << 18):
         """int64[size]: input row number of every internal id, by exact row matching.
@@ -1881,7 +1925,7 @@ class CPIndex:
         self._no_parts("encode_query")
         q = _as_f32(query)
         D = 1
-        while D < self._dim:
+        while D < self._sdim:
             D *= 2
         lut = np.zeros((D // 4, 16), np.uint8)
         co = np.zeros(3, np.float32)

@@ -41,6 +41,7 @@
 #include "device_group.h"
 #include "device_maxsim.h"
 #include "device_normalize.h"
+#include "device_ip.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "search_coalescer.h"
@@ -163,7 +164,8 @@ struct BatchSet {
     hipEvent_t ev_tab = nullptr;
     bool tab_used = false;
     // cosine metric (metric_queries): the batch's normalised queries; an L2 handle never allocates it
-    DevBuf<float> m_queries;
+    // (inner product: the augmented queries [nq][dim + 1], and m_c [nq] = |q|^2 + M2, what the epilogue subtracts)
+    DevBuf<float> m_queries, m_c;
 };
 constexpr int kMaxBatchSets = 4;
 
@@ -235,7 +237,9 @@ struct EffDeleter {
 static std::atomic<uint64_t> g_removed_epoch{0};
 
 struct cph_index {
-    uint64_t dim = 0;
+    // dim: the width of the rows the index stores and every kernel reads; dim_in: the width of the caller's rows and
+    // queries (cph_dim).  They differ under the inner-product metric only (dim = dim_in + 1); D = next_pow2(dim).
+    uint64_t dim = 0, dim_in = 0;
     uint32_t bits = 0;
     uint32_t D = 0;
     int device = 0;
@@ -251,6 +255,10 @@ struct cph_index {
     // metric_launches counts the launches of the normalisation kernel this handle made (cph_metric_stats): 0 under L2.
     uint32_t metric = CPH_METRIC_L2;
     uint64_t metric_launches = 0;
+    // inner product (device_ip.h): rows are stored as [x, sqrt(M2 - |x|^2)], queries searched as [q, 0], and an epilogue
+    // behind every batch turns the distances into -(q.x).  ip_bound: the caller's M2 (cph_set_ip_bound; 0: the largest
+    // squared norm of the rows of the build call); ip_m2: the M2 of the rows the handle holds.
+    float ip_bound = 0.0f, ip_m2 = 0.0f;
     std::vector<float> pending;        // vectors handed to build()
     uint64_t pending_n = 0;
     HostIndex host;
@@ -512,7 +520,7 @@ void release_scratch(BatchSet& s) {
     s.d_bitmaps.release(); s.d_logids.release(); s.d_beam.release(); s.d_beam_tail.release();
     s.r_bitmaps.release(); s.r_logids.release(); s.r_beam.release(); s.r_beam_tail.release();
     s.x_qpad.release(); s.x_qnorm.release(); s.x_pools.release(); s.x_counts.release();
-    s.m_queries.release();
+    s.m_queries.release(); s.m_c.release();
     s.slots = 0; s.cap = 0; s.r_slots = 0;
 }
 
@@ -792,13 +800,15 @@ void stage_queries(cph_index* h, BatchSet& s, const float* d_raw_q, uint64_t nq,
     HIP_CHECK(hipGetLastError());
 }
 
-// host queries -> the set's staging buffer
-const float* upload_queries(cph_index* h, BatchSet& s, const float* queries, uint64_t nq, hipStream_t st) {
-    if (s.d_queries_raw.n < nq * h->dim) {
+// host queries -> the set's staging buffer.  A batch's queries have the caller's width; the hooks, which hand their
+// vector straight to the encoder, give one of the stored width (stored: the two differ under the inner product only).
+const float* upload_queries(cph_index* h, BatchSet& s, const float* queries, uint64_t nq, hipStream_t st, bool stored = false) {
+    const uint64_t width = stored ? h->dim : h->dim_in;
+    if (s.d_queries_raw.n < nq * width) {
         if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));
-        s.d_queries_raw.alloc(nq * h->dim);
+        s.d_queries_raw.alloc(nq * width);
     }
-    HIP_CHECK(hipMemcpyAsync(s.d_queries_raw.p, queries, nq * h->dim * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(s.d_queries_raw.p, queries, nq * width * 4, hipMemcpyHostToDevice, st));
     return s.d_queries_raw.p;
 }
 
@@ -808,13 +818,89 @@ const float* upload_queries(cph_index* h, BatchSet& s, const float* queries, uin
 // query (zero, NaN, Inf) searches as the zero vector: the enqueue-only device form cannot refuse, so no form does.
 const float* metric_queries(cph_index* h, BatchSet& s, const float* d_raw_q, uint64_t nq, hipStream_t st) {
     if (h->metric == CPH_METRIC_L2 || !d_raw_q || nq == 0) return d_raw_q;
-    if (s.m_queries.n < nq * h->dim) {
-        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
+    if (s.m_queries.n < nq * h->dim || (h->metric == CPH_METRIC_IP && s.m_c.n < nq)) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
         s.m_queries.alloc(nq * h->dim);
+        if (h->metric == CPH_METRIC_IP) s.m_c.alloc(nq);
+    }
+    if (h->metric == CPH_METRIC_IP) {
+        // [q, 0] at the stored width, and c = |q|^2 + M2 for the batch's epilogue (metric_scores)
+        ip_augment(d_raw_q, s.m_queries.p, nq, (uint32_t)h->dim_in, h->ip_m2, 0, s.m_c.p, nullptr, st);
+        ++h->metric_launches;
+        return s.m_queries.p;
     }
     normalize_rows(d_raw_q, s.m_queries.p, nq, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
     ++h->metric_launches;
     return s.m_queries.p;
+}
+
+// The scores of an inner-product batch: dist = 0.5 * (dist - c) wherever the id is not padding (device_ip.h), enqueued on
+// the batch's stream behind the last kernel that writes the result rows -- once per batch, on every route of
+// search_batch_locked; the tables may be device memory or the pinned buffer of the copy-free route.  The set's
+// completion event moves behind it: the next batch on this set may grow m_c.  Nothing under L2 and cosine.
+void metric_scores(cph_index* h, BatchSet& s, int64_t* d_ids, float* d_dist, uint64_t nq, uint64_t k, hipStream_t st) {
+    if (h->metric != CPH_METRIC_IP || nq == 0 || k == 0) return;
+    ip_epilogue(d_ids, d_dist, nq, (uint32_t)k, s.m_c.p, st);
+    ++h->metric_launches;
+    HIP_CHECK(hipEventRecord(s.ev_done, st));
+}
+
+// Rows on their way into an inner-product index, on the device, in chunks: `out` ([n][dim_in + 1], host) holds
+// [x, sqrt(M2 - |x|^2)].  bound == null: M2 is the largest squared norm of these rows, found by a pass over all of them
+// (which also rejects bad rows) before the pass that writes; otherwise M2 = *bound and a row above it is refused.
+// Returns M2.  A refusal leaves the handle as it was.  against_index: the bound is the M2 of the index the rows are
+// added to (cph_add), which changes what the caller is told.
+float ip_rows_in(cph_index* h, const float* vectors, uint64_t n, const float* bound, bool against_index, std::vector<float>& out) {
+    h->use_device();
+    const uint64_t dim = h->dim_in, sd = dim + 1;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, ((uint64_t)256 << 20) / (sd * 4)));
+    out.resize(n * sd);
+    DevBuf<float> d_x(chunk * dim), d_o(chunk * sd);
+    DevBuf<unsigned long long> d_cnt(3);
+    DevBuf<unsigned int> d_m2(1);
+    const unsigned long long init[3] = {0ull, 0ull, kIpNoRow};
+    unsigned long long cnt[3] = {0ull, 0ull, kIpNoRow};
+    hipStream_t st = own_stream(h);
+    auto refuse = [&](const char* why) {
+        const unsigned long long total = cnt[0] + cnt[1];
+        throw InvalidArg("inner-product metric: row " + std::to_string(cnt[2]) + " " + why + " (" + std::to_string(total) + " such row" +
+                         (total == 1 ? "" : "s") + " in this call): nothing was changed");
+    };
+    HIP_CHECK(hipMemcpyAsync(d_cnt.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+    float m2 = bound ? *bound : 0.0f;
+    const bool one_chunk = chunk >= n;
+    if (!bound) {
+        HIP_CHECK(hipMemsetAsync(d_m2.p, 0, 4, st));
+        for (uint64_t base = 0; base < n; base += chunk) {
+            const uint64_t c = std::min(chunk, n - base);
+            HIP_CHECK(hipMemcpyAsync(d_x.p, vectors + base * dim, c * dim * 4, hipMemcpyHostToDevice, st));
+            ip_max(d_x.p, c, (uint32_t)dim, base, d_m2.p, d_cnt.p, st);
+            ++h->metric_launches;
+            HIP_CHECK(hipStreamSynchronize(st));     // (the next chunk's upload overwrites d_x from pageable memory)
+        }
+        HIP_CHECK(hipMemcpyAsync(&m2, d_m2.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (cnt[0]) refuse("holds a NaN or an Inf, or its squared norm overflows");
+    }
+    for (uint64_t base = 0; base < n; base += chunk) {
+        const uint64_t c = std::min(chunk, n - base);
+        if (bound || !one_chunk) HIP_CHECK(hipMemcpyAsync(d_x.p, vectors + base * dim, c * dim * 4, hipMemcpyHostToDevice, st));
+        ip_augment(d_x.p, d_o.p, c, (uint32_t)dim, m2, base, nullptr, d_cnt.p, st);
+        ++h->metric_launches;
+        HIP_CHECK(hipMemcpyAsync(out.data() + base * sd, d_o.p, c * sd * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (cnt[0] + cnt[1]) {
+        const std::string b = std::to_string(m2);
+        if (cnt[0] && cnt[1]) refuse(("holds a NaN or an Inf, has an overflowing squared norm, or one above the bound " + b).c_str());
+        if (cnt[0]) refuse("holds a NaN or an Inf, or its squared norm overflows");
+        refuse(against_index ? ("has a squared norm above the bound " + b + " the index was built with: rebuild the index with a larger bound (max_norm)").c_str()
+                             : ("has a squared norm above the bound " + b + " given for this index").c_str());
+    }
+    return m2;
 }
 
 // Rows on their way into a cosine index (cph_build, cph_add): normalised on the device, in chunks, into `out` ([n][dim],
@@ -1680,6 +1766,7 @@ void search_batch_locked(cph_index* h, const BatchCall& c) {
         auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
             d_q = metric_queries(h, s, d_q, n, st);
             enqueue_filters(h, s, d_q, (uint32_t)n, (uint32_t)k, lf.filters, lf.F, lf.filter_of, g, d_ids, d_dist, st);
+            metric_scores(h, s, d_ids, d_dist, n, k, st);
         };
         if (c.on_device) enqueue(c.q, c.ids, c.dist);
         else with_host_io(h, s, c, true, st, enqueue);
@@ -1698,21 +1785,26 @@ void search_batch_locked(cph_index* h, const BatchCall& c) {
     const bool empty = f && f->popcount == 0;     // (never exact: takes_exact)
     auto enqueue = [&](const float* d_q, int64_t* d_ids, float* d_dist) {
         if (!empty) d_q = metric_queries(h, s, d_q, n, st);
-        if (exact) return enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
+        if (exact) {
+            enqueue_exact(h, s, d_q, (uint32_t)n, (uint32_t)k, f, d_ids, d_dist, st);
+            return metric_scores(h, s, d_ids, d_dist, n, k, st);
+        }
         if (!empty) stage_queries(h, s, d_q, n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, d_ids, d_dist, st, nullptr, DoneFlags(), f, d_q);
+        if (!empty) metric_scores(h, s, d_ids, d_dist, n, k, st);      // (an empty filter's rows are padding, and no c was made)
     };
     if (c.on_device) return enqueue(c.q, c.ids, c.dist);
     if (!exact && !empty && n <= kSmallBatch && n * k <= (1u << 20)) {
         // a handful of queries: no copy commands, the kernels read the queries and write the results over PCIe
-        const PinnedIo io(n, k, h->dim, 0);
+        const PinnedIo io(n, k, h->dim_in, 0);
         if (s.pin_io_bytes < io.need && s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffer must be idle
         grow_pinned(s.pin_io, s.pin_io_dev, s.pin_io_bytes, io.need);
-        std::memcpy(io.queries(s.pin_io), c.q, n * h->dim * sizeof(float));
+        std::memcpy(io.queries(s.pin_io), c.q, n * h->dim_in * sizeof(float));
         const float* d_q = metric_queries(h, s, io.queries(s.pin_io_dev), n, st);    // (cosine: pinned rows in, HBM rows out)
         stage_queries(h, s, d_q, n, st);
         enqueue_search(h, s, (uint32_t)n, (uint32_t)k, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), st, io.counts(s.pin_io_dev),
                        DoneFlags(), f, d_q);
+        metric_scores(h, s, io.ids(s.pin_io_dev), io.dist(s.pin_io_dev), n, k, st);      // (inner product: on the pinned rows)
         HIP_CHECK(hipStreamSynchronize(st));
         std::memcpy(c.ids, io.ids(s.pin_io), n * k * 8);
         std::memcpy(c.dist, io.dist(s.pin_io), n * k * 4);
@@ -1744,7 +1836,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 111; }
+int cph_version(void) { return 112; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1765,6 +1857,7 @@ int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
         if (device < 0 || device >= ndev) throw InvalidArg("invalid device ordinal");
         auto* h = new cph_index();
         h->dim = dim;
+        h->dim_in = dim;
         h->bits = (uint32_t)bits;
         h->D = (uint32_t)pd;
         h->device = device;
@@ -1858,9 +1951,18 @@ static void refuse_tail_file(const cph_index* h) {
 
 // The reference's file format has no place for the metric: a file written from a cosine handle would be searched as L2
 // by whoever loads it, and a file loaded into one holds rows nobody normalised.
+static const char* metric_name(uint32_t metric) { return metric == CPH_METRIC_IP ? "ip" : metric == CPH_METRIC_COSINE ? "cosine" : "l2"; }
 static void refuse_metric_file(const cph_index* h, const char* what) {
     if (h->metric != CPH_METRIC_L2)
-        throw InvalidArg(std::string(what) + ": the reference's file format cannot carry the cosine metric: use save_native / load_native");
+        throw InvalidArg(std::string(what) + ": the reference's file format cannot carry the " + (h->metric == CPH_METRIC_IP ? "inner-product (ip)" : "cosine") +
+                         " metric: use save_native / load_native");
+}
+// The searches an inner-product handle does not serve yet: their results need an epilogue of their own shape (grouped,
+// diverse, MaxSim), or a per-query radius map whose boundary rounding is not decided (range).  Refused before any output
+// row is written.
+static void refuse_ip(const cph_index* h, const char* what) {
+    if (h->metric == CPH_METRIC_IP)
+        throw InvalidArg(std::string(what) + " is not available under the inner-product (ip) metric");
 }
 
 static void load_v2(cph_index* h, const char* path) {
@@ -1924,7 +2026,7 @@ int cph_save_native(cph_index* h, const char* path) {
             for (size_t v = 0; v < n; ++v) std::memcpy(&own[v * own_stride], &hi.search_data[v * hi.RL.vertex_bytes], own_stride);
             own_p = own.data();
         }
-        write_native(path, hi, (uint32_t)stride, own_p, (uint32_t)own_stride, blocks.data(), h->metric);
+        write_native(path, hi, (uint32_t)stride, own_p, (uint32_t)own_stride, blocks.data(), h->metric, h->metric == CPH_METRIC_IP ? &h->ip_m2 : nullptr);
     });
 }
 
@@ -1935,14 +2037,15 @@ struct NativeLoaded {
     HostIndex t;
     NativeMapping map;
     NativeHeader nh;
+    float ip_m2 = 0.0f;       // an inner-product file's bound
 };
 
 static void read_native_for(const cph_index* h, const char* path, NativeLoaded& out) {
     uint32_t metric = CPH_METRIC_L2;
-    out.nh = read_native(path, h->D, h->bits, h->dim, out.t, out.map, &metric);   // validates everything it maps
+    out.nh = read_native(path, h->D, h->bits, h->dim, out.t, out.map, &metric, &out.ip_m2);   // validates everything it maps
     if (metric != h->metric)
-        throw InvalidArg(std::string("the file holds ") + (metric == CPH_METRIC_COSINE ? "cosine" : "l2") + " rows and this handle's metric is " +
-                         (h->metric == CPH_METRIC_COSINE ? "cosine" : "l2") + ": load it into an index created with the file's metric");
+        throw InvalidArg(std::string("the file holds ") + metric_name(metric) + " rows and this handle's metric is " +
+                         metric_name(h->metric) + ": load it into an index created with the file's metric");
 }
 
 // The handle gives up its index for the one in `in` (which is consumed).
@@ -1954,6 +2057,7 @@ static void install_native(cph_index* h, NativeLoaded& in) {
     begin_device_swap(h);
     h->host = std::move(t);
     drop_host_state(h);
+    if (h->metric == CPH_METRIC_IP) h->ip_m2 = in.ip_m2;
     h->native_map = std::move(map);
     const uint8_t* base = static_cast<const uint8_t*>(h->native_map.base);
     h->own_view = base + nh.own_off;
@@ -1993,7 +2097,7 @@ int cph_size(cph_index* h, uint64_t* n) {
     return guarded([&] { *n = h->needs_build ? h->pending_n : h->size(); });
 }
 int cph_dim(cph_index* h, uint64_t* dim) {
-    return guarded([&] { *dim = h->dim; });
+    return guarded([&] { *dim = h->dim_in; });
 }
 int cph_is_finalized(cph_index* h, int* flag) {
     return guarded([&] { *flag = h->finalized ? 1 : 0; });
@@ -2015,16 +2119,20 @@ static void require_finalizable(uint64_t n) {
 // The one funnel behind cph_build, cph_multi_build, cph_parts_build and cph_compact.  as_given: the rows are stored as
 // they are -- an L2 handle's, and under cosine the rows that are normalised already (compact's live rows: a second pass
 // over a nearly-unit row changes bits; a partitioned build's, normalised in one go for the global row numbers).
-// Otherwise a cosine handle normalises them first, and a bad row refuses the call with the handle as it was.
+// Otherwise a cosine handle normalises them first, and a bad row refuses the call with the handle as it was; an
+// inner-product handle takes rows of dim_in coordinates, augments them (ip_rows_in) and refuses likewise.
 static void build_pending(cph_index* h, const float* vectors, uint64_t n, bool as_given = false) {
     std::lock_guard<std::mutex> lk(h->mu);
     // api/hnsw_index.hpp:93-120: build() replaces any previous state
     require_buildable(n);
     if (!vectors) throw InvalidArg("null vectors");
     std::vector<float> unit;
-    if (h->metric != CPH_METRIC_L2 && !as_given) normalize_rows_in(h, vectors, n, 0, unit);
+    float m2 = h->ip_m2;                                  // (inner product, as_given: the rows keep the bound they were stored against)
+    if (h->metric == CPH_METRIC_IP && !as_given) m2 = ip_rows_in(h, vectors, n, h->ip_bound != 0.0f ? &h->ip_bound : nullptr, false, unit);
+    else if (h->metric != CPH_METRIC_L2 && !as_given) normalize_rows_in(h, vectors, n, 0, unit);
     h->use_device();
     quiesce(h);
+    h->ip_m2 = m2;
     h->host = HostIndex();
     drop_host_state(h);
     h->finalized = false;
@@ -2280,7 +2388,7 @@ int cph_calib_hook(cph_index* h, const float* queries, const uint32_t* start, ui
         h->use_device();
         hipStream_t st = own_stream(h);
         BatchSet& s = next_set(h, st);
-        stage_queries(h, s, upload_queries(h, s, queries, ns, st), ns, st);     // the search's own encoder
+        stage_queries(h, s, upload_queries(h, s, queries, ns, st, true), ns, st);     // the search's own encoder
         HIP_CHECK(hipEventRecord(s.ev_done, st));
         s.used = true;
         DevBuf<uint32_t> d_start(ns), d_rc(ns);
@@ -2621,6 +2729,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
     *out = nullptr;
     *total = 0;
     std::lock_guard<std::mutex> lk(h->mu);
+    refuse_ip(h, "range search");
     require_finalized(h);
     if (f) check_filter(h, f);
     if (n > 0xFFFFFFFFull) throw InvalidArg("batch too large");
@@ -3460,7 +3569,9 @@ int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float
         if (!query || !ids || !dist || !m) throw InvalidArg("null argument");
         const uint64_t kk = std::max<uint64_t>(k, 1);  // api/hnsw_index.hpp:187
         if (kk > 0xFFFFFFFFull) throw InvalidArg("k too large");
-        if (h->tombstones.load(std::memory_order_acquire) || h->has_tail.load(std::memory_order_acquire)) {
+        if (h->tombstones.load(std::memory_order_acquire) || h->has_tail.load(std::memory_order_acquire) || h->metric == CPH_METRIC_IP) {
+            // inner product: the coalesced path raises a query's completion flag from inside the search kernel, before an
+            // epilogue could have run: a batch of one instead (the metric is fixed before the handle holds rows);
             // removed rows: a batch of one through the filtered path under ~R (what a search with filter= does); added
             // rows: a batch of one, so that the tail's scan and fold follow the graph launch
             std::vector<int64_t> ri(kk);
@@ -3491,7 +3602,7 @@ int cph_encode_query(cph_index* h, const float* query, uint8_t* lut, float* coef
         h->use_device();
         hipStream_t st = own_stream(h);
         BatchSet& s = next_set(h, st);
-        stage_queries(h, s, upload_queries(h, s, query, 1, st), 1, st);
+        stage_queries(h, s, upload_queries(h, s, query, 1, st, true), 1, st);
         HIP_CHECK(hipEventRecord(s.ev_done, st));
         s.used = true;
         HIP_CHECK(hipStreamSynchronize(st));
@@ -3518,7 +3629,7 @@ int cph_entry_point(cph_index* h, const float* query, uint32_t* entry) {
         h->use_device();
         hipStream_t st = own_stream(h);
         BatchSet& s = next_set(h, st);
-        stage_queries(h, s, upload_queries(h, s, query, 1, st), 1, st);
+        stage_queries(h, s, upload_queries(h, s, query, 1, st, true), 1, st);
         HIP_CHECK(hipEventRecord(s.ev_done, st));
         s.used = true;
         HIP_CHECK(hipStreamSynchronize(st));
@@ -3963,6 +4074,7 @@ void replicate(cph_index* src, cph_index* dst) {
     dst->dev_max_level = src->dev_max_level;
     dst->norm_factor = src->norm_factor;
     dst->inv_sqrt_d = src->inv_sqrt_d;
+    dst->ip_m2 = src->ip_m2;                    // every replica holds M2: its queries and scores are made against it
     hipStream_t st = own_stream(dst);
     auto copy = [&](auto& d, const auto& s) {
         d.alloc(s.n);
@@ -4093,7 +4205,7 @@ void multi_search_batch(cph_multi* m, const BatchCall& c) {
         return true;
     }, [&](const Shard& s, size_t) {
         const std::vector<const cph_filter*> fr = replica_filters(c.filters, c.F, R, s.replica);
-        const float* q = c.q ? c.q + s.lo * m->reps[0]->dim : nullptr;
+        const float* q = c.q ? c.q + s.lo * m->reps[0]->dim_in : nullptr;
         int64_t* oi = c.ids ? c.ids + s.lo * k : nullptr;
         float* od = c.dist ? c.dist + s.lo * k : nullptr;
         cph_index* h = m->reps[s.replica];
@@ -4335,6 +4447,7 @@ int cph_multi_range_search_begin(cph_multi* m, const float* queries, uint64_t n,
         if (!out || !total) throw InvalidArg("null argument");
         *out = nullptr;
         *total = 0;
+        refuse_ip(m->reps[0], "range search");
         const uint32_t R = (uint32_t)m->reps.size();
         const uint64_t dim = m->reps[0]->dim;
         std::unique_ptr<cph_multi_range> mr(new cph_multi_range());
@@ -5165,7 +5278,10 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
                          "(cph_set_column with NULL), add, then set them again at the new size");
     if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
     std::vector<float> unit;                     // cosine: the rows as the index stores them (a bad row refuses the call here)
-    if (h->metric != CPH_METRIC_L2) {
+    if (h->metric == CPH_METRIC_IP) {            // (inner product: against the M2 of the index)
+        ip_rows_in(h, vectors, m, &h->ip_m2, true, unit);
+        vectors = unit.data();
+    } else if (h->metric != CPH_METRIC_L2) {
         normalize_rows_in(h, vectors, m, 0, unit);
         vectors = unit.data();
     }
@@ -5949,6 +6065,7 @@ template <class Rerank>
 void rerank_search(cph_index* h, const Rerank& f, const RerankCall& c, const cph_group_keys* keys, void* const* stream = nullptr) {
     if (!h) throw InvalidArg("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
+    refuse_ip(h, (std::string(Rerank::name) + " search").c_str());
     if (!rerank_has_work(h, f, c)) return;
     const int32_t* d_key_of = Rerank::keyed ? group_key_column(h, keys) : nullptr;
     h->use_device();
@@ -5971,6 +6088,7 @@ template <class Rerank, class ShardCall>
 void rerank_multi(cph_multi* m, const Rerank& f, const RerankCall& c, const cph_group_keys* const* keys, ShardCall shard_call) {
     if (!m) throw InvalidArg("null handle");
     const uint32_t R = (uint32_t)m->reps.size();
+    refuse_ip(m->reps[0], (std::string(Rerank::name) + " search").c_str());
     const uint64_t q_floats = f.tokens() * m->reps[0]->dim;
     check_filter_args(c);
     multi_fan_out(m, c.n, [&](cph_index* h, uint32_t r) {
@@ -6296,17 +6414,49 @@ int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint
 
 
 // ---- the metric (cph_set_metric; device_normalize.h) -------------------------------------------------------------------
-static const char* metric_name(uint32_t metric) { return metric == CPH_METRIC_COSINE ? "cosine" : "l2"; }
 
 // Settable on an empty handle only: nothing built, pending or loaded -- the rows of an index are stored for one metric.
-static void set_metric(cph_index* h, int metric) {
-    if (metric != CPH_METRIC_L2 && metric != CPH_METRIC_COSINE)
+// The inner product stores one coordinate more than the caller gives: dim = dim_in + 1, and D follows it.
+// cph_set_metric keeps the contract it had before the inner product existed -- it takes L2 and cosine and refuses every
+// other value, 2 included -- so CPH_METRIC_IP comes in through its own entry, cph_set_metric_ip (with_ip).
+static void set_metric(cph_index* h, int metric, bool with_ip = false) {
+    if (metric == CPH_METRIC_IP && !with_ip)
+        throw InvalidArg("metric 2 (CPH_METRIC_IP, the inner product) changes the widths of the handle and is set with cph_set_metric_ip / "
+                         "cph_multi_set_metric_ip; cph_set_metric takes CPH_METRIC_L2 = 0 and CPH_METRIC_COSINE = 1");
+    if (metric != CPH_METRIC_L2 && metric != CPH_METRIC_COSINE && metric != CPH_METRIC_IP)
         throw InvalidArg("unknown metric " + std::to_string(metric) + " (CPH_METRIC_L2 = 0, CPH_METRIC_COSINE = 1)");
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->finalized || h->needs_build || h->host.n != 0)
         throw InvalidArg(std::string("the metric is set on an empty handle, before build or load: this one holds ") + metric_name(h->metric) +
                          " rows");
+    const uint64_t stored = h->dim_in + (metric == CPH_METRIC_IP ? 1 : 0);
+    const size_t pd = next_pow2(stored);
+    if (pd > 2048)
+        throw InvalidArg("inner-product (ip) metric: the index stores dim + 1 = " + std::to_string(stored) + " coordinates, padded to " +
+                         std::to_string(pd) + "; supported padded dims end at 2048 (dim <= 2047)");
     h->metric = (uint32_t)metric;
+    h->dim = stored;
+    h->D = (uint32_t)pd;
+    if (metric != CPH_METRIC_IP) h->ip_bound = 0.0f;
+    h->ip_m2 = 0.0f;
+}
+
+static void set_ip_bound(cph_index* h, float max_sq_norm) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->metric != CPH_METRIC_IP) throw InvalidArg(std::string("the bound belongs to the inner-product (ip) metric: this handle's metric is ") + metric_name(h->metric));
+    if (h->finalized || h->needs_build || h->host.n != 0) throw InvalidArg("the inner-product bound is set on an empty handle, before build or load");
+    if (!(max_sq_norm >= 0.0f && max_sq_norm < std::numeric_limits<float>::infinity()))
+        throw InvalidArg("the inner-product bound is a finite squared norm >= 0 (0: from the rows of the build call)");
+    h->ip_bound = max_sq_norm;
+}
+
+static void check_ip_args(const float* x, uint64_t n, uint64_t dim, const float* out, int mode, const float* c, float max_sq_norm) {
+    if (n && (!x || !out)) throw InvalidArg("null argument");
+    if (dim < 1 || dim >= 0xFFFFFFFFull) throw InvalidArg("ip augment: dim out of range");
+    if (mode < 0 || mode > 2) throw InvalidArg("ip augment: mode is 0 (rows, given bound), 1 (rows, bound from the data) or 2 (queries)");
+    if (mode == 2 && n && !c) throw InvalidArg("null argument");
+    if (mode != 1 && !(max_sq_norm >= 0.0f && max_sq_norm < std::numeric_limits<float>::infinity())) throw InvalidArg("ip augment: the bound is a finite squared norm >= 0");
+    if (n > 0x7FFFFFFFull / (dim + 1)) throw InvalidArg("ip augment: too many elements for the hook");
 }
 
 static void check_normalize_args(const float* x, uint64_t n, uint64_t dim, const float* out) {
@@ -6337,11 +6487,53 @@ int cph_multi_set_metric(cph_multi* m, int metric) {
         if (!m) throw InvalidArg("null handle");
         std::unique_lock<std::shared_mutex> lk(m->life);
         set_metric(m->reps[0], metric);                      // (replica 0 holds the state that decides; the others follow it)
-        for (size_t i = 1; i < m->reps.size(); ++i) {
-            std::lock_guard<std::mutex> g(m->reps[i]->mu);
-            m->reps[i]->metric = (uint32_t)metric;
-        }
+        for (size_t i = 1; i < m->reps.size(); ++i) set_metric(m->reps[i], metric);      // (the widths follow the metric on every replica)
     });
+}
+
+int cph_set_metric_ip(cph_index* h) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_metric_ip");
+        set_metric(h, CPH_METRIC_IP, true);
+    });
+}
+
+int cph_multi_set_metric_ip(cph_multi* m) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->reps) set_metric(h, CPH_METRIC_IP, true);     // (replica 0 first: it holds the state that decides)
+    });
+}
+
+int cph_set_ip_bound(cph_index* h, float max_sq_norm) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_ip_bound");
+        set_ip_bound(h, max_sq_norm);
+    });
+}
+
+int cph_get_ip_bound(cph_index* h, float* m2) {
+    return guarded([&] {
+        if (!h || !m2) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (h->metric != CPH_METRIC_IP) throw InvalidArg(std::string("the bound belongs to the inner-product (ip) metric: this handle's metric is ") + metric_name(h->metric));
+        *m2 = h->finalized || h->needs_build ? h->ip_m2 : h->ip_bound;
+    });
+}
+
+int cph_multi_set_ip_bound(cph_multi* m, float max_sq_norm) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->reps) set_ip_bound(h, max_sq_norm);
+    });
+}
+
+int cph_multi_get_ip_bound(cph_multi* m, float* m2) {
+    return multi_shared(m, [&] { return cph_get_ip_bound(m->reps[0], m2); });
 }
 
 int cph_parts_set_metric(cph_parts* m, int metric) {
@@ -6353,6 +6545,8 @@ int cph_parts_set_metric(cph_parts* m, int metric) {
             if (h->finalized || h->needs_build || h->host.n != 0)
                 throw InvalidArg("the metric is set on an empty handle, before build or load");
         }
+        // (the parts would each find an M2 of their own, and the merged scores would not compare: a follow-up)
+        if (metric == CPH_METRIC_IP) throw InvalidArg("a partitioned index does not take the inner-product (ip) metric: its parts need one global bound");
         for (cph_index* h : m->parts) set_metric(h, metric);
     });
 }
@@ -6363,7 +6557,7 @@ int cph_metric_stats(cph_index* h, uint64_t out[2]) {
         std::lock_guard<std::mutex> lk(h->mu);
         out[0] = h->metric_launches;
         out[1] = 0;
-        for (const BatchSet& s : h->sets) out[1] += s.m_queries.n * sizeof(float);
+        for (const BatchSet& s : h->sets) out[1] += (s.m_queries.n + s.m_c.n) * sizeof(float);
     });
 }
 
@@ -6399,6 +6593,104 @@ int cph_host_normalize_rows(const float* x, uint64_t n, uint64_t dim, float* out
     return guarded([&] {
         check_normalize_args(x, n, dim, out);
         normalize_rows_host(x, n, (uint32_t)dim, out, bad_count, first_bad);
+    });
+}
+
+// Test hooks of the inner-product kernels (device_ip.h) on host arrays; cph_host_ip_* are the host statement (host_ip.h).
+int cph_ip_augment_hook(int device, const float* x, uint64_t n, uint64_t dim, int mode, float max_sq_norm, float* out, float* c, float* m2,
+                        uint64_t counters[3]) {
+    return guarded([&] {
+        check_ip_args(x, n, dim, out, mode, c, max_sq_norm);
+        if (counters) { counters[0] = 0; counters[1] = 0; counters[2] = kIpNoRow; }
+        if (m2) *m2 = mode == 1 ? 0.0f : max_sq_norm;
+        if (n == 0) return;
+        HIP_CHECK(hipSetDevice(device));
+        const size_t cells = (size_t)n * dim, ocells = (size_t)n * (dim + 1);
+        DevBuf<float> d_in(cells), d_out(ocells), d_c(n);
+        DevBuf<unsigned long long> d_cnt(3);
+        DevBuf<unsigned int> d_m2(1);
+        const unsigned long long init[3] = {0ull, 0ull, kIpNoRow};
+        unsigned long long cnt[3] = {0ull, 0ull, kIpNoRow};
+        HIP_CHECK(hipMemcpy(d_in.p, x, cells * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_cnt.p, init, sizeof(init), hipMemcpyHostToDevice));
+        // (the outputs start as 0xA5 bytes: every slot the kernel leaves alone shows)
+        HIP_CHECK(hipMemset(d_out.p, 0xA5, ocells * 4));
+        HIP_CHECK(hipMemset(d_c.p, 0xA5, n * 4));
+        float bound = max_sq_norm;
+        if (mode == 1) {
+            HIP_CHECK(hipMemset(d_m2.p, 0, 4));
+            ip_max(d_in.p, n, (uint32_t)dim, 0, d_m2.p, nullptr, nullptr);       // (the second pass counts the bad rows)
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&bound, d_m2.p, 4, hipMemcpyDeviceToHost));
+        }
+        ip_augment(d_in.p, d_out.p, n, (uint32_t)dim, bound, 0, mode == 2 ? d_c.p : nullptr, d_cnt.p, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_out.p, ocells * 4, hipMemcpyDeviceToHost));
+        if (c) HIP_CHECK(hipMemcpy(c, d_c.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
+        if (m2) *m2 = bound;
+        if (counters) { counters[0] = cnt[0]; counters[1] = cnt[1]; counters[2] = cnt[2]; }
+    });
+}
+
+static void check_ip_epilogue_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t k, const float* c) {
+    if (n && k && (!ids || !dist || !c)) throw InvalidArg("null argument");
+    if (k > 0xFFFFFFFFull || (k && n > 0x7FFFFFFFull / k)) throw InvalidArg("ip epilogue: table too large for the hook");
+}
+
+// pinned != 0: the tables live in pinned, device-mapped host memory (what the small-batch route hands the kernel).
+int cph_ip_epilogue_hook(int device, const int64_t* ids, float* dist, uint64_t n, uint64_t k, const float* c, int pinned) {
+    return guarded([&] {
+        check_ip_epilogue_args(ids, dist, n, k, c);
+        if (n == 0 || k == 0) return;
+        HIP_CHECK(hipSetDevice(device));
+        const size_t cells = (size_t)n * k;
+        DevBuf<float> d_c(n);
+        HIP_CHECK(hipMemcpy(d_c.p, c, n * 4, hipMemcpyHostToDevice));
+        if (pinned) {
+            uint8_t* pin = nullptr;
+            uint8_t* pin_dev = nullptr;
+            size_t bytes = 0;
+            grow_pinned(pin, pin_dev, bytes, cells * 12);
+            std::memcpy(pin, ids, cells * 8);
+            std::memcpy(pin + cells * 8, dist, cells * 4);
+            hipError_t e = hipSuccess;
+            try {
+                ip_epilogue(reinterpret_cast<const int64_t*>(pin_dev), reinterpret_cast<float*>(pin_dev + cells * 8), n, (uint32_t)k, d_c.p, nullptr);
+                e = hipDeviceSynchronize();
+            } catch (...) {
+                (void)hipHostFree(pin);
+                throw;
+            }
+            if (e == hipSuccess) std::memcpy(dist, pin + cells * 8, cells * 4);
+            (void)hipHostFree(pin);
+            HIP_CHECK(e);
+            return;
+        }
+        DevBuf<int64_t> d_ids(cells);
+        DevBuf<float> d_dist(cells);
+        HIP_CHECK(hipMemcpy(d_ids.p, ids, cells * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dist.p, dist, cells * 4, hipMemcpyHostToDevice));
+        ip_epilogue(d_ids.p, d_dist.p, n, (uint32_t)k, d_c.p, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(dist, d_dist.p, cells * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_host_ip_augment(const float* x, uint64_t n, uint64_t dim, int mode, float max_sq_norm, float* out, float* c, float* m2, uint64_t counters[3]) {
+    return guarded([&] {
+        check_ip_args(x, n, dim, out, mode, c, max_sq_norm);
+        if (counters) { counters[0] = 0; counters[1] = 0; counters[2] = kIpNoRow; }
+        const float bound = mode == 1 ? ip_max_sq_norm_host(x, n, (uint32_t)dim, nullptr) : max_sq_norm;
+        ip_augment_host(x, n, (uint32_t)dim, bound, out, mode == 2 ? c : nullptr, counters);
+        if (m2) *m2 = bound;
+    });
+}
+
+int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k, const float* c) {
+    return guarded([&] {
+        check_ip_epilogue_args(ids, dist, n, k, c);
+        ip_epilogue_host(ids, dist, n, k, c);
     });
 }
 

@@ -39,6 +39,13 @@
 // finds there 16, 40, 48 or 72 bytes that do not start with a magic it knows -- never nothing, and never 24 bytes that
 // start with the rows magic or 32 / 56 that start with the removed-rows magic.  It names no section.
 //
+// Format 5 = format 4's record with version = 5, metric = 2 (inner product) and two more words: the float M2 the rows
+// were augmented against and a zero reserved word -- 24 bytes in the place of 16 (NativeMetricIpExt).  A format-4
+// reader refuses it: it finds the metric magic, reads the 16 bytes it knows and rejects version 5 ("Unsupported native
+// index file version: 5") before it looks at anything behind them (read_metric_record with newest = 4 is that reader's
+// check, and tests/ip_host/ip_host.cpp pins it).  Older readers refuse it like format 4: the 24 bytes do not start
+// with the rows magic.  Cosine files stay format 4 and L2 files carry no record: both keep their bytes.
+//
 // load = mmap + two host-to-device copies straight out of the mapping; the vectors stay mapped for
 // cph_get_vectors / save.  A v2 file can always be regenerated from a native one (cph_save after
 // cph_load_native): the reference-layout blocks are re-derived from the device blocks.
@@ -48,8 +55,10 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -70,6 +79,8 @@ constexpr uint64_t kNativeRemovedMagic = 0x44564D5249485043ULL;   // "CPHIRMVD"
 constexpr uint32_t kNativeVersionMetric = 4;  // NativeMetricExt::version: the format of a file whose rows are not squared-L2 rows
 constexpr uint64_t kNativeMetricMagic = 0x5254454D49485043ULL;    // "CPHIMETR"
 constexpr uint32_t kNativeMetricL2 = 0, kNativeMetricCosine = 1;  // (CPH_METRIC_L2, CPH_METRIC_COSINE)
+constexpr uint32_t kNativeVersionIp = 5;      // NativeMetricIpExt::version: the format of a file of inner-product rows
+constexpr uint32_t kNativeMetricIp = 2;       // (CPH_METRIC_IP)
 
 struct NativeHeader {
     uint64_t magic;
@@ -109,6 +120,44 @@ struct NativeMetricExt {      // format 4: behind the upper layers, in front of 
 };
 static_assert(sizeof(NativeMetricExt) == 16, "older readers must refuse the record by its size");
 
+struct NativeMetricIpExt {    // format 5: in the place of NativeMetricExt
+    uint64_t magic;           // kNativeMetricMagic
+    uint32_t version;         // kNativeVersionIp
+    uint32_t metric;          // kNativeMetricIp
+    float m2;                 // the bound the rows were augmented against: finite, >= 0
+    uint32_t reserved;        // 0
+};
+static_assert(sizeof(NativeMetricIpExt) == 24 && offsetof(NativeMetricIpExt, version) == offsetof(NativeMetricExt, version),
+              "a format-4 reader must find the version where it looks for it");
+
+// The metric record at p (avail bytes are readable), as a reader that knows formats up to `newest` (4 or 5) takes it:
+// returns the bytes the record occupies, 0 when p does not start with the metric magic.  A version above `newest` is
+// refused before any byte behind the first 16 is read.
+inline size_t read_metric_record(const uint8_t* p, size_t avail, uint32_t newest, uint32_t* metric, float* m2) {
+    NativeMetricExt e{};
+    if (avail < sizeof(e)) return 0;
+    std::memcpy(&e, p, sizeof(e));
+    if (e.magic != kNativeMetricMagic) return 0;
+    if (e.version != kNativeVersionMetric && !(e.version == kNativeVersionIp && newest >= kNativeVersionIp))
+        throw std::runtime_error("Unsupported native index file version: " + std::to_string(e.version));
+    if (e.version == kNativeVersionMetric) {
+        if (e.metric != kNativeMetricCosine) throw std::runtime_error("Corrupt index: unknown metric " + std::to_string(e.metric));
+        *metric = e.metric;
+        *m2 = 0.0f;
+        return sizeof(e);
+    }
+    NativeMetricIpExt x{};
+    if (e.metric != kNativeMetricIp || avail < sizeof(x))
+        throw std::runtime_error("Corrupt index: a version-5 metric record holds the inner-product metric and its bound, not metric " +
+                                 std::to_string(e.metric));
+    std::memcpy(&x, p, sizeof(x));
+    if (!(x.m2 >= 0.0f && x.m2 < std::numeric_limits<float>::infinity()) || x.reserved != 0)
+        throw std::runtime_error("Corrupt index: bad inner-product bound");
+    *metric = x.metric;
+    *m2 = x.m2;
+    return sizeof(x);
+}
+
 struct NativeMapping {
     void* base = nullptr;
     size_t bytes = 0;
@@ -132,7 +181,7 @@ inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // `own` = [n][own_stride] vertex headers, `blocks` = [n][stride] device blocks (both host pointers).
 inline void write_native(const std::string& path, const HostIndex& hi, uint32_t stride, const uint8_t* own,
-                         uint32_t own_stride, const uint8_t* blocks, uint32_t metric = kNativeMetricL2) {
+                         uint32_t own_stride, const uint8_t* blocks, uint32_t metric = kNativeMetricL2, const float* ip_m2 = nullptr) {
     std::vector<uint8_t> small;
     auto put = [&](const void* p, size_t b) { const uint8_t* q = static_cast<const uint8_t*>(p); small.insert(small.end(), q, q + b); };
     put(hi.calib, 248);
@@ -161,13 +210,19 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
         if (pc != hi.n_removed || ((hi.n & 31) && (hi.removed.back() >> (hi.n & 31))))
             throw std::runtime_error("removed-row bitmap does not match its count");
     }
-    if (metric != kNativeMetricL2 && metric != kNativeMetricCosine) throw std::runtime_error("unknown metric");
+    if (metric != kNativeMetricL2 && metric != kNativeMetricCosine && metric != kNativeMetricIp) throw std::runtime_error("unknown metric");
+    // (inner-product rows mean nothing without the bound they were augmented against)
+    if (metric == kNativeMetricIp && !(ip_m2 && *ip_m2 >= 0.0f && *ip_m2 < std::numeric_limits<float>::infinity()))
+        throw std::runtime_error("the inner-product metric is written with its bound");
     const bool with_metric = metric != kNativeMetricL2;
     uint64_t rows_off = 0, removed_off = 0;
     const uint64_t records = (with_rows ? sizeof(NativeRowsExt) : 0) + (with_removed ? sizeof(NativeRemovedExt) : 0) +
-                             (with_metric ? sizeof(NativeMetricExt) : 0);
+                             (!with_metric ? 0 : metric == kNativeMetricIp ? sizeof(NativeMetricIpExt) : sizeof(NativeMetricExt));
     uint64_t sections_end = sizeof(NativeHeader) + small.size() + records;
-    if (with_metric) {
+    if (metric == kNativeMetricIp) {
+        const NativeMetricIpExt ext{kNativeMetricMagic, kNativeVersionIp, metric, *ip_m2, 0u};
+        put(&ext, sizeof(ext));
+    } else if (with_metric) {
         const NativeMetricExt ext{kNativeMetricMagic, kNativeVersionMetric, metric};
         put(&ext, sizeof(ext));
     }
@@ -223,10 +278,11 @@ inline void write_native(const std::string& path, const HostIndex& hi, uint32_t 
 
 // Maps the file and fills everything of `hi` except raw / search_data (raw_view points into the mapping); hi.rows is
 // the file's row map (format 2) or empty (format 1), hi.removed / hi.n_removed the file's removed rows (format 3) or
-// none; the returned header's `version` is that format.  *metric: the file's metric (format 4; L2 without the record) --
-// a caller that does not ask cannot hold anything but L2 rows, and is refused a file of another metric.
+// none; the returned header's `version` is that format.  *metric: the file's metric (formats 4 and 5; L2 without the
+// record) -- a caller that does not ask cannot hold anything but L2 rows, and is refused a file of another metric.
+// *ip_m2: the bound of an inner-product file (format 5); a caller that does not ask is refused such a file.
 inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t expect_bw, size_t expect_dim, HostIndex& hi,
-                                NativeMapping& map, uint32_t* metric = nullptr) {
+                                NativeMapping& map, uint32_t* metric = nullptr, float* ip_m2 = nullptr) {
     const int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw std::runtime_error("Cannot open file for reading: " + path);
     struct stat st{};
@@ -301,26 +357,25 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
     }
     // What follows the upper layers: nothing (format 1), the row-map record (format 2), or the removed-rows record with
     // or without the row-map record behind it (format 3); anything else is damage.
-    // In front of them the metric record (format 4), told by its magic.
+    // In front of them the metric record (formats 4 and 5), told by its magic.
     bool with_rows = false, with_removed = false, with_metric = false;
     NativeRowsExt ext{};
     NativeRemovedExt rext{};
-    NativeMetricExt mext{};
+    uint32_t file_metric = kNativeMetricL2;
+    float file_m2 = 0.0f;
     const uint64_t rm_words = (h.n + 31) / 32;
-    if ((size_t)(end - p) >= sizeof(mext)) {
-        uint64_t magic = 0;
-        std::memcpy(&magic, p, 8);
-        if (magic == kNativeMetricMagic) {
-            get(&mext, sizeof(mext));
-            if (mext.version != kNativeVersionMetric)
-                throw std::runtime_error("Unsupported native index file version: " + std::to_string(mext.version));
-            if (mext.metric != kNativeMetricCosine) throw std::runtime_error("Corrupt index: unknown metric " + std::to_string(mext.metric));
-            with_metric = true;
-        }
+    if (const size_t b = read_metric_record(p, (size_t)(end - p), kNativeVersionIp, &file_metric, &file_m2)) {
+        p += b;
+        with_metric = true;
     }
     if (with_metric && !metric)
-        throw std::runtime_error("The file holds cosine rows: it loads into an index created with the cosine metric only.");
-    if (metric) *metric = with_metric ? mext.metric : kNativeMetricL2;
+        throw std::runtime_error(file_metric == kNativeMetricIp
+                                     ? "The file holds inner-product rows: it loads into an index created with the inner-product metric only."
+                                     : "The file holds cosine rows: it loads into an index created with the cosine metric only.");
+    if (file_metric == kNativeMetricIp && !ip_m2)
+        throw std::runtime_error("The file holds inner-product rows: it loads into an index created with the inner-product metric only.");
+    if (metric) *metric = file_metric;
+    if (ip_m2) *ip_m2 = file_m2;
     if ((size_t)(end - p) == sizeof(rext) || (size_t)(end - p) == sizeof(rext) + sizeof(ext)) {
         typedef unsigned __int128 u128;
         get(&rext, sizeof(rext));
@@ -350,7 +405,7 @@ inline NativeHeader read_native(const std::string& path, size_t expect_D, size_t
         h.version = kNativeVersionRows;      // the format, for the caller (the file's field stays 1, see the top)
     }
     if (with_removed) h.version = kNativeVersionRemoved;
-    if (with_metric) h.version = kNativeVersionMetric;
+    if (with_metric) h.version = file_metric == kNativeMetricIp ? kNativeVersionIp : kNativeVersionMetric;
     // The device blocks are handed to the GPU as they are: a neighbour id the search kernel would chase must be a
     // vertex (the v2 loader's validate() makes the same promise), unused slots must carry the invalid marker the
     // kernels rely on instead of `count`, and the repeated-id flag is recomputed rather than believed.

@@ -372,7 +372,7 @@ bool probe_first(const cph_index* h) {
 // The two stage-2 counters of a finished batch (w = kStatStage2Reruns / kStatStage2Undecided).  The diagnostic builds
 // keep their cycle / traffic counters in those words and the kernel does not flush the two there: they read as 0.
 uint64_t stage2_stat(const BatchSet& s, StatWord w) {
-#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS) || defined(CPH_TAIL_CENSUS)
     (void)s; (void)w;
     return 0;
 #else
@@ -2471,7 +2471,7 @@ int cph_last_search_stats(cph_index* h, uint64_t out[12]) {
         out[9] = s.run_cap;
         out[10] = stage2_stat(s, kStatStage2Reruns);
         out[11] = stage2_stat(s, kStatStage2Undecided);
-#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS) || defined(CPH_TAIL_CENSUS)
         const unsigned long long* diag = s.pin_stats + kStatDiag;
 #endif
 #if CPH_PHASE_TIMERS + 0 == 2
@@ -2479,6 +2479,10 @@ int cph_last_search_stats(cph_index* h, uint64_t out[12]) {
                 diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
 #elif defined(CPH_PHASE_TIMERS)
         fprintf(stderr, "[phase cycles] pop=%llu load+exact+nnpush=%llu sums+epi=%llu atomic+log+stage=%llu spec_exact=%llu replay=%llu tail=%llu other=%llu\n",
+                diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
+#endif
+#ifdef CPH_TAIL_CENSUS
+        fprintf(stderr, "[tail census] lds_append=%llu spilled_append=%llu single_push_skips_append=%llu push_beats_parent=%llu nothing_to_push=%llu more_pushes_than_entries=%llu replay=%llu lane_parallel=%llu\n",
                 diag[0], diag[1], diag[2], diag[3], diag[4], diag[5], diag[6], diag[7]);
 #endif
 #ifdef CPH_TRAFFIC_STATS

@@ -62,10 +62,10 @@ enum StatWord : int {
     kStatAllSeen = 7,           // expansions whose 32 neighbours were all estimated already
     kStatStage2Reruns = 8,      // those of kStatReruns that were handed over for a stage-2 decision (probe first)
     kStatStage2Undecided = 9,   // expansions whose stage-2 decision was left open (probe first)
-    // -DCPH_PHASE_TIMERS / -DCPH_TRAFFIC_STATS: eight cycle or traffic counters take words 8..15; the two stage-2 words
-    // are not flushed there (and read as 0 on the host)
+    // -DCPH_PHASE_TIMERS / -DCPH_TRAFFIC_STATS / -DCPH_TAIL_CENSUS: eight cycle, traffic or arm counters take words
+    // 8..15; the two stage-2 words are not flushed there (and read as 0 on the host)
     kStatDiag = 8,
-#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS) || defined(CPH_TAIL_CENSUS)
     kStatFlushed = 8,
 #else
     kStatFlushed = 10,
@@ -835,7 +835,9 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         // and carrying it per query the same way cost four more SGPR spills inside the loop -- 1.6 % slower on C2.  With
         // the loop head below the allocator keeps it resident by itself; profiles/issue_diet.md.  With the expansion loop
         // compiled twice the re-read is back in both copies of <4,128,true>, and carrying the base per query still loses:
-        // 15 -> 29 SGPR spills, 13.51 -> 13.69 ms per 100,000 queries; profiles/steady_loop.md.)
+        // 15 -> 29 SGPR spills, 13.51 -> 13.69 ms per 100,000 queries; profiles/steady_loop.md.  With the steady copy's
+        // push tail reshaped and two values fewer carried through the loop the allocator keeps the base resident
+        // again: no s_load on the usual steady expansion, 15 -> 12 SGPR spills; profiles/steady_tail.md.)
         qp.slack = s_slack[0];
         const float gamma = a.sc.gamma;
 
@@ -871,6 +873,11 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         // expansion evaluate one distance each, so st_exact counts the speculative reranks only -- touched in the rare
         // expansion that has candidates --, and every new neighbour is logged, so the id log's length knows their number.
         constexpr bool kDerivedCounters = kTwoLoops;
+        // ... and state that only a rare arm changes is not carried through the loop at all: the speculative reranks are
+        // added to the wave's total in LDS where they happen, and `wipe` is what the id log's length says (it only grows,
+        // and goes on counting once the log is full).  Every value the loop carries is copied on its latch and on the
+        // exits that leave it unchanged; these two were among them (profiles/steady_tail.md).
+        constexpr bool kRareOffLoop = kTwoLoops;
         uint32_t st_exp = 0, st_exact = 0, st_new = 0, st_push = 0, st_skip = 0, st_allseen = 0;
         // probe first only: expansions where the reference's stage-2 decision is unobservable and was left open (the reference
         // may have skipped stage 2 there or not -- st_skip counts the skips that were decided)
@@ -878,6 +885,16 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
 #ifdef CPH_TRAFFIC_STATS
         // diagnostic build only: what the spilled beam and the estimated-set probe touch (stats[8..15])
         unsigned long long trf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+#ifdef CPH_TAIL_CENSUS
+        // diagnostic build only: which arm of the push tail the STEADY copy's expansions take (stats[8..15]; scripts/tail_census.py):
+        // 0 append in LDS | 1 append onto a spilled beam | 2 single push onto a spilled beam, append skipped | 3 a push beats
+        // its parent, serial pushes | 4 new neighbours, nothing to push | 5 more pushes than the beam can check, serial |
+        // 6 candidates: the serial replay | 7 expansions that reach the lane-parallel arm
+        unsigned long long tcs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#define CPH_CENSUS(i) do { if constexpr (ST) tcs[i]++; } while (0)
+#else
+#define CPH_CENSUS(i) do {} while (0)
 #endif
 #ifdef CPH_PHASE_TIMERS
         unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -950,6 +967,8 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
 #undef CPH_GO_STEADY
         }
 
+        // (an attempt that ends between the test and the addition has overflowed: it wipes in any case)
+        if constexpr (kRareOffLoop) wipe = log_count > a.cap;
         // ---- results (:276; src/bindings.cpp:202-210) ----------------------------------
         if (lane == 0 && !overflow) nn_sort(nn, nn_size);
         const uint32_t nn_final = bcast_u32(nn_size);
@@ -984,8 +1003,11 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
             s_tot[kStatAllSeen] += st_allseen;
             if (stage2_redo) s_tot[kStatStage2Reruns] += 1;
             s_tot[kStatStage2Undecided] += st_undecided;
-#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS)
+#if defined(CPH_PHASE_TIMERS) || defined(CPH_TRAFFIC_STATS) || defined(CPH_TAIL_CENSUS)
             unsigned long long* stats = CPH_COLD(stats);
+#endif
+#ifdef CPH_TAIL_CENSUS
+            for (int i = 0; i < 8; ++i) atomicAdd(&stats[kStatDiag + i], tcs[i]);
 #endif
 #ifdef CPH_PHASE_TIMERS
             for (int i = 0; i < 8; ++i) atomicAdd(&stats[kStatDiag + i], tph[i]);

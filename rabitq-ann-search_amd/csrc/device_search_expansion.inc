@@ -301,10 +301,18 @@
             // is full the query simply stops logging and wipes its whole bitmap at the end (n / 8 bytes -- less than the
             // log it would have needed: a query that discovers more than `cap` ids has touched a good part of the graph).
             if (beam_size + n_new > a.cap) { overflow = true; break; }
-            if (!wipe && log_count + n_new > a.cap) wipe = true;
+            // (two loops: no `wipe` flag is carried from expansion to expansion.  The log's length only grows, and it goes on
+            // counting after the log is full, so "full" is a comparison of the length -- here and at query end.)
+            bool nolog;
+            if constexpr (kRareOffLoop) {
+                nolog = log_count + n_new > a.cap;
+            } else {
+                if (!wipe && log_count + n_new > a.cap) wipe = true;
+                nolog = wipe;
+            }
             if (is_new) {
                 atomicOr(&bm[nid >> 5], my_bit);
-                if (!wipe) logi[log_count + my_rank] = nid;
+                if (!nolog) logi[log_count + my_rank] = nid;
             }
             // Every neighbour already estimated (a quarter to a third of the expansions, most of
             // them late in the search): the reference evaluates the block and then skips all 32
@@ -329,7 +337,8 @@
                 //   serial replay: m = new_mask [& ballot(!(lower >= worst0))], v_readlane of est / lower at the set
                 //   bits of m only                                                   -> new_mask
                 //   replay of the lane-parallel pushes: v_readlane at the set bits of pm -> p
-                // (the same readers in both copies of the loop: the steady one only drops the warm-up arms of cand and m)
+                // (the same readers in both copies of the loop: the steady one only drops the warm-up arms of cand and m;
+                // its own lane-parallel arm builds the entry in every lane and reads it, like the general one, under p)
                 bl.leave_undefined();
                 if (fetch) bl.issue_static(blk, lane);
                 if (__builtin_expect(!estimate(fetch), 0)) { overflow = true; stage2_redo = true; break; }
@@ -372,7 +381,9 @@
                     asm volatile("" ::"v"(ex));   // keeps the norm load out of the branch below
                     if (have && (lane & 7) == 0) s_exact[idx] = ex;
                 }
-                st_exact += n_cand;
+                // (two loops: added to the wave's total in LDS where it happens, not carried in a register)
+                if constexpr (kRareOffLoop) { if (lane == 0) s_tot[kStatExact] += n_cand; }
+                else st_exact += n_cand;
                 __syncthreads();
                 if constexpr (FILT) allow_mask = (uint32_t)(ballot64(is_new && ((allow_w >> (nid & 31u)) & 1u) != 0u) & 0xFFFFFFFFull);
             }
@@ -394,7 +405,68 @@
                 // better than the parent of the leaf it lands on, so nothing moves and the pushes
                 // are independent appends -- each lane checks its own parent and writes its own leaf.
                 const uint32_t np = __popc(pm);
-                bool appended = false;
+                bool appended = false;      // (general copy only: the steady arm clears `pm` instead)
+                if constexpr (ST) {
+                    // Steady copy: the same decisions as the general arm below (keep the two in step), shaped for the
+                    // compiler's control-flow pass (the loop holds divergent branches, so its uniform branches are rebuilt
+                    // with it: a bool that is live across a join -- `appended`, `in_lds` -- and every && of two uniform
+                    // tests comes back as a lane mask, s_cselect_b64 -1,0 / s_and_b64 vcc,exec / s_cbranch_vcc, plus
+                    // copies on the latch).  Here every uniform test is ONE scalar compare with its own branch, no flag
+                    // crosses a join -- the appended pushes leave the mask, and the serial loop below runs on what is
+                    // left of it --, and the beam in LDS, the usual case, has an arm of its own.
+                    // profiles/steady_tail.md: 43 scalar instructions fewer on the usual expansion.
+                    CPH_CENSUS(7);
+                    const uint4 ent = make_uint4(__float_as_uint(est), __float_as_uint(lower), nid, 0u);
+                    if (np - 1u <= beam_size) {               // np != 0 && np <= beam_size + 1, as one unsigned compare
+                        __builtin_amdgcn_wave_barrier();      // (no instruction: keeps the two compares two branches)
+                        if (beam_size + np <= kBeamLds) {     // in LDS (implies !(np == 1 && beam_size >= kBeamLds))
+                            const uint32_t pos = beam_size + __builtin_amdgcn_mbcnt_lo(pm, 0u);
+                            // every lane reads a parent (lanes without a push: the root) and is masked afterwards
+                            const bool chk = p && pos > 0;
+                            const bool stay = !(heap.lds_key(chk ? (pos - 1) >> 1 : 0u) > est) || !chk;
+                            if (all64(stay)) {
+                                CPH_CENSUS(0);
+                                if (p) heap.lds_put(pos, ent);
+                                beam_size += np;
+                                st_push += np;
+                                pm = 0;
+                            } else {
+                                CPH_CENSUS(3);
+                            }
+                        // (a single push onto a spilled beam goes straight to the push routine: the parent check of the
+                        // append path would be a dependent round trip of its own in front of the one the routine makes anyway)
+#ifdef CPH_NO_SKIP_APPEND
+                        } else {
+#else
+                        } else if (np != 1) {
+#endif
+                            const uint32_t pos = beam_size + __builtin_amdgcn_mbcnt_lo(pm, 0u);
+                            bool stay = true;
+                            if (p && pos > 0) stay = !(heap.raw_key((pos - 1) >> 1) > est);
+                            if (all64(stay)) {
+                                CPH_CENSUS(1);
+#ifdef CPH_TRAFFIC_STATS
+                                trf[3]++;
+#endif
+                                if (p) heap.put(pos, ent);
+                                beam_size += np;
+                                st_push += np;
+                                pm = 0;
+                            } else {
+                                CPH_CENSUS(3);
+                            }
+#ifndef CPH_NO_SKIP_APPEND
+                        } else {
+                            CPH_CENSUS(2);
+#endif
+                        }
+                    } else if (np == 0) {
+                        CPH_CENSUS(4);
+                    } else {
+                        CPH_CENSUS(5);
+                    }
+                } else
+                // General copy and every one-loop instantiation (the steady arm above takes the same decisions).
                 // (a single push onto a spilled beam goes straight to the push routine: the parent check of the append path
                 // would be a dependent round trip of its own in front of the one the routine makes anyway)
 #ifdef CPH_NO_SKIP_APPEND
@@ -423,7 +495,7 @@
                         appended = true;
                     }
                 }
-                if (!appended) {
+                if (ST || !appended) {
                     while (pm) {
                         const int i = __ffs((int)pm) - 1;
                         pm &= pm - 1;
@@ -440,6 +512,7 @@
                     }
                 }
             } else {
+                CPH_CENSUS(6);
                 // past the warm-up the threshold only falls: a lower bound that fails it at loop
                 // entry fails it at its turn too (:241), so those neighbours are dropped here
                 uint32_t m = warmup ? new_mask

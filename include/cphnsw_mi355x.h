@@ -432,6 +432,64 @@ int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint
                          const int32_t* key_of, uint64_t n_keys, const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score,
                          int32_t* out_hits, int64_t* out_rows, int32_t* out_found);
 
+/* ---- multi-vector search with exact rescoring (not in the reference) ---------------------- */
+/* cph_search_maxsim followed by the second stage of a late-interaction retriever: the best `rescore` = R keys of the
+ * lower-bound statement (k <= R <= 1024; the other limits are those of cph_search_maxsim) are scored against ALL their
+ * allowed rows, and the k best of those are returned.  csrc/host_maxsim_rescore.h is the host form of the statement,
+ * tests/maxsim_rescore_model.py its numpy form:
+ *   candidates  the cph_search_maxsim statement at k = R over the same token rows, C, filters, exact flag, routing, removed
+ *               rows and tail: f = found <= R keys with their lower bounds lb_j, in (lb, key) order; they stay in scratch;
+ *   A_i(key)    the ids < cph_size with that key whose bit is set in query i's effective filter (the caller's filter for
+ *               that query AND not removed, tail rows included; every id when there is neither);
+ *   best_t      per candidate and live token t: min over id in A_i(key) of (bits(d(q_t, id)), id) as an unsigned pair; d has
+ *               the bytes cph_exact_l2 returns for the pair, the token vector being the one the search saw (cosine: after
+ *               the normalise kernel); d >= +0, so equal distances go to the lowest internal id;
+ *   score       ((+0.0f + d_0) + d_1) + ... over t < n_tokens[i], float32, in that order;
+ *   answer      the min(k, f) candidates with the smallest (score, key), in that order: keys, score, hits (= n_tokens[i] in
+ *               every real slot), rows[t] = the argmin id (input rows under CPH_IDS_INPUT; -1 for t >= n_tokens[i]), found;
+ *               padding as in cph_search_maxsim;
+ *   certified   [n] int32: the number of leading answer slots whose score is strictly below lb_{R-1}, or found[i] when
+ *               f < R.  Every key outside the candidates has a lower bound >= lb_{R-1}, so with exact != 0 those leading
+ *               slots are the true MaxSim top slots over the allowed rows, in the true order.  With a graph-routed search
+ *               the bound is relative to the candidate rows the search returned, not to the whole index.
+ * The work, on the call's stream: maxsim_rows_kernel at k = R into scratch, exact_pad_kernel over the token rows, then
+ * maxsim_rescore_scan_kernel (one wave per (query, candidate)) and maxsim_rescore_select_kernel (one workgroup per query),
+ * csrc/device_maxsim_rescore.h.  The scan walks an INVERTED KEY COLUMN (ids by (key, id), distinct keys, offsets), built on
+ * the host -- a download of the column, a sort, an upload -- once per column and cached where the column lives: in the
+ * cph_group_keys object, or on the handle for the label column, where cph_set_labels, cph_add, cph_compact, a load and a
+ * build drop it.  Building it WAITS for the device: the one exception to "the _device form only enqueues";
+ * cph_prepare_maxsim_rescore(h, keys) (keys == NULL: the label column) builds it ahead of time.  A handle that never
+ * rescored allocates nothing for it.  The inner-product metric and partitioned indexes are refused as for cph_search_maxsim. */
+int cph_search_maxsim_rescored(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                               uint64_t candidates, uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters,
+                               uint32_t n_filters, const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score,
+                               int32_t* out_hits, int64_t* out_rows, int32_t* out_found, int32_t* out_certified);
+int cph_search_maxsim_rescored_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                      uint64_t candidates, uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters,
+                                      uint32_t n_filters, const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score,
+                                      int32_t* d_hits, int64_t* d_rows, int32_t* d_found, int32_t* d_certified, void* stream);
+int cph_prepare_maxsim_rescore(cph_index* h, const cph_group_keys* keys);
+/* Debug hooks of the measurement script (scripts/maxsim_rescore_sweep.py): the launch of maxsim_rescore_scan_kernel alone
+ * between two HIP events while switched on. */
+int cph_debug_time_maxsim_rescore(cph_index* h, int on);
+int cph_debug_last_maxsim_rescore_us(cph_index* h, double* us);
+/* Test hook: the pad, scan and select kernels on given candidates (host arrays) against the vectors of h.  cand_keys /
+ * cand_lb [n][rescore], cand_found [n] in [0, rescore]; tokens [n][n_tok][dim]; n_tokens [n] or NULL; keys: a keys object of
+ * h or NULL (the label column); allow: [n][(cph_size + 31) / 32] bitmap words, one bitmap per query, or NULL (every id).
+ * The device outputs start as 0xA5 bytes.  cph_host_maxsim_rescore is the host statement (no HIP call) over raw
+ * [n_ids][D] zero-padded rows and their norms; cph_host_key_rows the host routine that inverts a key column: out_ids [n],
+ * out_keys [n] (the first *out_n_keys are written), out_offsets [n + 1] (the first *out_n_keys + 1). */
+int cph_maxsim_rescore_hook(cph_index* h, const int32_t* cand_keys, const float* cand_lb, const int32_t* cand_found, uint64_t n,
+                            uint64_t rescore, const float* tokens, uint64_t n_tok, const int32_t* n_tokens, const cph_group_keys* keys,
+                            const uint32_t* allow, uint64_t k, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found, int32_t* out_certified);
+int cph_host_maxsim_rescore(const int32_t* cand_keys, const float* cand_lb, const int32_t* cand_found, uint64_t n, uint64_t rescore,
+                            const float* tokens, uint64_t n_tok, uint64_t dim, const int32_t* n_tokens, const float* raw,
+                            const float* norm_sq, uint64_t n_ids, uint64_t D, const int32_t* key_of, const uint32_t* allow,
+                            const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found, int32_t* out_certified);
+int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_t* out_keys, uint32_t* out_offsets, uint64_t* out_n_keys);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -783,6 +841,12 @@ int cph_multi_search_maxsim(cph_multi* m, const float* queries, uint64_t n, uint
                             uint64_t candidates, const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
                             const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
                             int32_t* out_found);
+/* cph_search_maxsim_rescored over the same shards; every replica keeps an inverted key column of its own. */
+int cph_multi_search_maxsim_rescored(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                     uint64_t candidates, uint64_t rescore, const cph_group_keys* const* keys,
+                                     const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
+                                     int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found,
+                                     int32_t* out_certified);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

@@ -1470,8 +1470,36 @@ class CPIndex:
         return ((T, None if (nt is None or n == 0) else nt.ctypes.data, k, C_),
                 (((n, k), "int32"), ((n, k), "float32"), ((n, k), "int32"), ((n, k, T), "int64"), ((n,), "int32")))
 
+    MAXSIM_MAX_RESCORE = 1024
+
+    def _maxsim_rescore_arg(self, rescore, k):
+        """rescore=R of search_maxsim / search_maxsim_device -> R, checked against k <= R <= 1024."""
+        if isinstance(rescore, bool) or not isinstance(rescore, (int, np.integer)):
+            raise ValueError("rescore must be an integer (the number of keys to rescore) or None")
+        R = int(rescore)
+        if not int(k) <= R <= self.MAXSIM_MAX_RESCORE:
+            raise ValueError(f"search_maxsim needs k <= rescore <= {self.MAXSIM_MAX_RESCORE} (got rescore={R} at k={int(k)})")
+        return R
+
+    @staticmethod
+    def _maxsim_rescored_call(n, T, k, C_, nt, R):
+        """-> (the scalars between n and the keys, the output table) of the rescored entries."""
+        lead, table = CPIndex._maxsim_call(n, T, k, C_, nt)
+        return lead + (R,), table + (((n,), "int32"),)
+
+    def prepare_maxsim_rescore(self, keys=None):
+        """Builds the inverted key column search_maxsim(..., rescore=R) walks -- of `keys` (a GroupKeys), or of the label
+        column -- ahead of the first rescored call, which would otherwise build it and wait for the device.  It is made
+        once per column: set_labels, add, compact, load and build drop the label column's; a GroupKeys keeps its own."""
+        if self._p is not None:
+            raise ValueError("search_maxsim is not defined on a partitioned index (every part has its own internal ids and "
+                             "its own slice of the labels): use part(i).prepare_maxsim_rescore")
+        keys = self._group_keys_arg(keys, "prepare_maxsim_rescore")
+        for r, rh in enumerate(self._replicas()):
+            _lib.check(_lib.lib().cph_prepare_maxsim_rescore(rh, None if keys is None else keys._hs[r]))
+
     def search_maxsim(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, filter=None, exact=False,
-                      filter_of=None, label=None):
+                      filter_of=None, label=None, rescore=None):
         """Multi-vector (late-interaction, ColBERT / ColPali style) search: `queries` is float32 [n, T, dim], T token vectors
         per query of which the first n_tokens[i] (default: all T) are live; returns the k keys (documents) that minimise
         the sum, over the live tokens, of the token's best row of the key:
@@ -1497,20 +1525,36 @@ class CPIndex:
         `candidates=C` (1 <= C <= 1024, T * C <= 8192) is the length of every token's candidate row; candidates=None takes
         C0 = min(1024, 8192 // T, max(32, 4 * k)): a policy, not a measured optimum, in ONE pass.  Limits: 1 <= T <= 64,
         1 <= k <= 1024, n * T <= 2^31 - 1.  A multi-device index shards the QUERIES like search_batch, never the tokens of
-        one query; the bytes are those of one device.  A partitioned index is refused (use part(i).search_maxsim)."""
+        one query; the bytes are those of one device.  A partitioned index is refused (use part(i).search_maxsim).
+        `rescore=R` (k <= R <= 1024; None: everything above, five outputs) adds the second stage of a late-interaction
+        retriever and returns SIX outputs, (keys, score, hits, rows, found, certified int32 [n]): the statement above at
+        k = R gives the candidate keys and their lower bounds lb_j in (lb, key) order; every candidate is then scored against
+        ALL its allowed rows -- the ids with that key in the query's effective filter (the caller's filter AND not removed,
+        tail rows included) -- per live token the row with the smallest (distance, internal id), the distance having the
+        bytes of exact_l2 for the token vector the search saw (cosine: normalised); score is the same sequential float32 sum
+        over those distances, hits == n_tokens in every real slot, rows holds the argmin ids, and the min(k, found at R)
+        candidates with the smallest (score, key) are returned.  certified[i] is the number of leading slots whose score is
+        strictly below lb_{R-1} (found[i] when fewer than R keys were found): every key outside the candidates has a lower
+        bound of at least lb_{R-1}, so with exact=True those leading slots are the true MaxSim top slots over the allowed
+        rows, in the true order; with a graph-routed search the bound is relative to the candidate rows the search returned,
+        not to the index.  The first rescored call on a key column builds its inverted form on the host and waits for the
+        device (prepare_maxsim_rescore does it ahead of time)."""
         q = _as_f32(queries)
         if q.ndim != 3 or q.shape[2] != self._dim:
             raise ValueError("queries must be a (n, tokens, dim) array")
         if label is not None:
             return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_maxsim(
-                q, k, n_tokens=n_tokens, candidates=candidates, keys=keys, filter=f, exact=exact, filter_of=fo))
+                q, k, n_tokens=n_tokens, candidates=candidates, keys=keys, filter=f, exact=exact, filter_of=fo, rescore=rescore))
         n, T = q.shape[0], q.shape[1]
         k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        if rescore is not None:
+            lead, table = self._maxsim_rescored_call(n, T, k, C_, nt, self._maxsim_rescore_arg(rescore, k))
+            return self._rerank_host("maxsim_rescored", q, lead, keys, filters, exact, table)
         lead, table = self._maxsim_call(n, T, k, C_, nt)
         return self._rerank_host("maxsim", q, lead, keys, filters, exact, table)
 
     def search_maxsim_device(self, queries, k=DEFAULT_K, n_tokens=None, candidates=None, keys=None, out=None, stream=None,
-                             filter=None, exact=False, filter_of=None, label=None):
+                             filter=None, exact=False, filter_of=None, label=None, rescore=None):
         """search_maxsim on a float32 torch tensor (n, T, dim) on this index' device; returns the five outputs as torch
         tensors on the same device.  Like search_batch_device it only enqueues, on `stream` (default: torch's current
         stream), and waits for no kernel: the tensors are valid in stream order, two batches on two streams overlap.
@@ -1518,16 +1562,25 @@ class CPIndex:
         the queries' device).  n_tokens / filter / filter_of / label are host data as in search_batch_device (n_tokens is
         copied to the device through a pinned buffer by a command on `stream`); a filter or GroupKeys closed after the
         call waits for the batch.  A multi-device index runs the whole batch on one replica on the queries' device.
-        cosine: MaxSim similarity = n_tokens - score."""
+        cosine: MaxSim similarity = n_tokens - score.
+        `rescore=R`: the six outputs of search_maxsim(..., rescore=R) (`out`: six tensors, the last (n,) int32).  The first
+        rescored call on a key column builds its inverted form and waits for the device -- the one exception to "only
+        enqueues"; prepare_maxsim_rescore builds it ahead of time."""
         import torch
         if queries.dim() != 3 or queries.shape[2] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, tokens, dim) array")
         if label is not None:
             return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_maxsim_device(
                 queries, k, n_tokens=n_tokens, candidates=candidates, keys=keys, out=out, stream=stream, filter=f, exact=exact,
-                filter_of=fo))
+                filter_of=fo, rescore=rescore))
         n, T = queries.shape[0], queries.shape[1]
         k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        if rescore is not None:
+            lead, table = self._maxsim_rescored_call(n, T, k, C_, nt, self._maxsim_rescore_arg(rescore, k))
+            return tuple(self._rerank_device("maxsim_rescored", queries, lead, keys, filters, exact, table, out, stream,
+                                             ("out must be the six tensors (keys, score, hits, rows, found, certified)",
+                                              "out must be contiguous (n, k) int32 / float32 / int32, (n, k, tokens) int64, (n,) int32 "
+                                              "and (n,) int32 tensors on the queries' device")))
         lead, table = self._maxsim_call(n, T, k, C_, nt)
         return tuple(self._rerank_device("maxsim", queries, lead, keys, filters, exact, table, out, stream,
                                          ("out must be the five tensors (keys, score, hits, rows, found)",
@@ -1543,6 +1596,16 @@ class CPIndex:
         """Device time (HIP events, microseconds) of the maxsim kernel of the last maxsim search made under time_maxsim()
         on the given replica; waits for that launch."""
         return self._last_pass_us("cph_debug_last_maxsim_rows_us", replica)
+
+    def time_maxsim_rescore(self, on=True):
+        """Debug hook of the measurement script: while on, the scan kernel of every rescored maxsim search (the exact terms;
+        not the lower-bound kernel, the pad or the select) is bracketed by HIP events (last_maxsim_rescore_us)."""
+        self._time_pass("cph_debug_time_maxsim_rescore", on)
+
+    def last_maxsim_rescore_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the scan kernel of the last rescored maxsim search made under
+        time_maxsim_rescore() on the given replica; waits for it."""
+        return self._last_pass_us("cph_debug_last_maxsim_rescore_us", replica)
 
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):

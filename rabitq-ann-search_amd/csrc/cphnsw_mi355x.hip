@@ -40,6 +40,7 @@
 #include "device_diverse.h"
 #include "device_group.h"
 #include "device_maxsim.h"
+#include "device_maxsim_rescore.h"
 #include "device_normalize.h"
 #include "device_ip.h"
 #include "host_index.h"
@@ -186,7 +187,12 @@ constexpr size_t kRangeScratchKept = 2;
 // call on these buffers makes its stream wait for it.  maxsim with n_tokens: the lengths are written into pin_tok and
 // copied to d_tok by one command on the call's stream; ev_tok: that copy has read pin_tok (the next such call on this
 // set waits for it before it writes).  A handle that never calls maxsim allocates none of the three.
-constexpr int kMaxRerankOuts = 5;
+// The rescored maxsim search (device_maxsim_rescore.h) adds its own: the candidates of the lower-bound pass (c_*), the token
+// rows as the search saw them (rs_q: cosine only), padded (rs_qpad, rs_qnorm), the exact scores and argmin ids of every
+// candidate slot, and the call's host tables -- filter_of and the bitmap pointers -- which travel like n_tokens: written into
+// pin_rs, copied to d_rs by one command on the call's stream, ev_rs behind that copy.  A handle that never rescored
+// allocates none of them.
+constexpr int kMaxRerankOuts = 6;
 struct GroupScratch {
     DevBuf<int64_t> r_ids;
     DevBuf<float> r_dist, d_q;
@@ -198,9 +204,31 @@ struct GroupScratch {
     size_t pin_tok_n = 0;
     hipEvent_t ev_tok = nullptr;
     bool tok_used = false;
+    DevBuf<int32_t> c_keys, c_hits, c_found;
+    DevBuf<float> c_lb, rs_q, rs_qpad, rs_qnorm, rs_score;
+    DevBuf<uint32_t> rs_rows;
+    DevBuf<unsigned long long> rs_stats;
+    uint8_t* pin_rs = nullptr;
+    size_t pin_rs_bytes = 0;
+    DevBuf<uint8_t> d_rs;
+    hipEvent_t ev_rs = nullptr;
+    bool rs_used = false;
+};
+
+// The inverted key column of one int32 column (host_maxsim_rescore.h: key_rows_host), resident: what the rescored maxsim
+// search walks.  Made on the host on first use (or by cph_prepare_maxsim_rescore) and kept where its column lives: in the
+// cph_group_keys object, or on the handle for the label column, where whatever changes the column drops it.
+struct KeyRows {
+    DevBuf<uint32_t> ids, offsets;
+    DevBuf<int32_t> keys;
+    uint32_t n_keys = 0;
+    uint64_t size = 0;                         // ids it covers
+    const int32_t* column = nullptr;           // the device column it was made from
 };
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassKinds };     // the passes a handle can time (PassTimer)
+// The passes a handle can time (PassTimer).  kPassMaxsimRescore is the scan kernel of the rescored maxsim search alone, bracketed
+// inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassUntimed, kPassKinds };
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -282,6 +310,7 @@ struct cph_index {
     DevBuf<int32_t> d_labels, d_label_bounds;
     DevBuf<unsigned long long> d_label_counts;
     bool has_labels = false;
+    std::unique_ptr<KeyRows> label_rows;      // the label column inverted (rescored maxsim search), or none: made on first use
     // the attribute columns (cph_set_column): up to kMaxColumns more int32 columns, each held like the label column
     // (host copies: host.columns); every walk over "the label column" -- sync_labels, replicate, the compact gather,
     // the parts cut -- walks these slots too (column_of)
@@ -435,6 +464,7 @@ bool has_extra_columns(const cph_index* h) {
 // After the host index changed: the device copy of its label column and of every attribute column, or none (a load or
 // a build leaves none).
 void sync_labels(cph_index* h) {
+    h->label_rows.reset();
     for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
         const ColumnRef c = column_of(h, slot);
         c.has = !c.host.empty();
@@ -538,6 +568,8 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed diverse search has run on this handle (cph_debug_time_diverse)",
     "no timed maxsim search has run on this handle (cph_debug_time_maxsim)",
     "no timed label pass has run on this handle (cph_debug_time_label_filters)",
+    "no timed rescored maxsim search has run on this handle (cph_debug_time_maxsim_rescore)",
+    "this pass is not timed",
 };
 
 // pass(), which enqueues on `st`, between the timer's two events while it is on.
@@ -1836,7 +1868,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 112; }
+int cph_version(void) { return 113; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1907,6 +1939,8 @@ static void destroy_index(cph_index* h) {
         if (gs.ev) (void)hipEventDestroy(gs.ev);
         if (gs.ev_tok) (void)hipEventDestroy(gs.ev_tok);
         if (gs.pin_tok) (void)hipHostFree(gs.pin_tok);
+        if (gs.ev_rs) (void)hipEventDestroy(gs.ev_rs);
+        if (gs.pin_rs) (void)hipHostFree(gs.pin_rs);
     }
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     for (auto& pt : h->pass_timer) {
@@ -1939,6 +1973,7 @@ static void begin_device_swap(cph_index* h) {
     h->last_search = -1;
     h->last_range = false;
     h->range_scratch.clear();
+    h->label_rows.reset();
     ++h->index_epoch;
 }
 
@@ -3140,6 +3175,7 @@ void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool
     h->use_device();
     quiesce(h);                                  // a grouped batch in flight may be reading the old column
     const ColumnRef c = column_of(h, slot);
+    if (slot == kLabelSlot) h->label_rows.reset();      // (idle: quiesce above)
     if (!labels) {
         std::vector<int32_t>().swap(c.host);
         c.has = false;
@@ -5291,6 +5327,7 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     }
     h->use_device();
     quiesce(h);                                  // a batch in flight reads the arrays that may move
+    h->label_rows.reset();                       // the inverted label column covers `size` ids: the next rescored call rebuilds it
     HostIndex& hi = h->host;
     const uint64_t D = h->L.D, dim = h->dim, nw = (need + 31) / 32;
     const bool removed = hi.n_removed != 0;
@@ -5707,14 +5744,16 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
 // One entry path for the three: an ordinary search at k = C into scratch rows the handle owns, then one kernel over those
 // rows on the same stream.  The rows hold INTERNAL ids whatever the handle returns (the keys are looked up by internal
 // id); the row map is applied where an id is written.  Nothing here waits for the device in the _device form.  A
-// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch): its scalars, its checks, its output table
-// and its pass; the entries, the scratch, the replica fan-out and the hooks below are written once over that.
+// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch, MaxsimRescoredSearch): its scalars, its checks,
+// its output table and its pass; the entries, the scratch, the replica fan-out and the hooks below are written once over
+// that.  (MaxsimRescoredSearch's pass is four launches, and the first one on a key column waits for the device: key_rows.)
 struct cph_group_keys {
     cph_index* h = nullptr;                    // the handle it was made for ...
     uint64_t epoch = 0;                        // ... and the index that handle held then (index_epoch)
     int device = 0;
     uint64_t size = 0;                         // ids it covers
     DevBuf<int32_t> keys;                      // [size], internal-id order
+    mutable std::unique_ptr<KeyRows> rows;     // the column inverted (rescored maxsim search): made on first use under the handle mutex
 };
 
 namespace {
@@ -5879,7 +5918,7 @@ struct GroupedSearch {
     RerankOuts outs(int64_t* ids, float* dist, int32_t* keys, int32_t* counts, uint8_t* complete) const {
         return {{{ids, 8 * k * g}, {dist, 4 * k * g}, {keys, 4 * k}, {counts, 4 * k}, {complete, 1}}, 5};
     }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const RerankOuts& o, hipStream_t st) const {
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
         group_rows(group_args(gs.r_ids.p, gs.r_dist.p, C, k, g, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o), (uint32_t)n, st);
     }
 };
@@ -5932,7 +5971,7 @@ struct DiverseSearch {
     void check_batch(uint64_t n) const { check_batch_size(n); }
     void check_inputs(uint64_t) const {}
     RerankOuts outs(int64_t* ids, float* dist, float* gap) const { return {{{ids, 8 * k}, {dist, 4 * k}, {gap, 4 * k}}, 3}; }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const RerankOuts& o, hipStream_t st) const {
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
         diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, o), (uint32_t)n, st);
     }
 };
@@ -6027,10 +6066,198 @@ struct MaxsimSearch {
     RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found) const {
         return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}}, 5};
     }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const RerankOuts& o, hipStream_t st) const {
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
         const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
         maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
                     (uint32_t)n, h->device, st);
+    }
+};
+
+// ---- maxsim with exact rescoring (device_maxsim_rescore.h, host_maxsim_rescore.h) ----
+void check_maxsim_rescore_shape(uint64_t T, uint64_t C, uint64_t k, uint64_t R) {
+    check_maxsim_shape(T, C, k);
+    if (R < k || R > kMaxsimRescoreMax)
+        throw InvalidArg("maxsim search supports k <= rescore <= " + std::to_string(kMaxsimRescoreMax) + ", got rescore = " + std::to_string(R) +
+                         " at k = " + std::to_string(k));
+}
+
+void check_maxsim_rescore_batch(uint64_t n, uint64_t T, uint64_t R) {
+    check_maxsim_batch(n, T);
+    if (n * R > 0x7FFFFFFFull)
+        throw InvalidArg("batch too large: rescored maxsim search needs n * rescore <= 2147483647 (got " + std::to_string(n) + " * " +
+                         std::to_string(R) + ")");
+}
+
+// The inverted column of a rescored call's keys: the cached one, or made now -- a download of the column, a host sort and an
+// upload, which WAIT for the device (the one exception to enqueue-only; cph_prepare_maxsim_rescore makes it ahead of time).
+// The caller holds the handle mutex and has set the device.
+const KeyRows& key_rows(cph_index* h, const cph_group_keys* keys, const int32_t* d_key_of) {
+    std::unique_ptr<KeyRows>& slot = keys ? keys->rows : h->label_rows;
+    const uint64_t size = h->size();
+    if (slot && slot->size == size && slot->column == d_key_of) return *slot;
+    if (slot) quiesce(h);                                 // (a batch in flight may read the one that goes)
+    slot.reset();
+    std::vector<int32_t> col(size), ukeys(size);
+    std::vector<uint32_t> ids(size), offs(size + 1);
+    if (size) HIP_CHECK(hipMemcpy(col.data(), d_key_of, size * 4, hipMemcpyDeviceToHost));
+    const uint64_t nk = key_rows_host(col.data(), size, ids.data(), ukeys.data(), offs.data());
+    std::unique_ptr<KeyRows> kr(new KeyRows());
+    kr->ids.alloc(std::max<uint64_t>(size, 1));
+    kr->keys.alloc(std::max<uint64_t>(nk, 1));
+    kr->offsets.alloc(nk + 1);
+    if (size) HIP_CHECK(hipMemcpy(kr->ids.p, ids.data(), size * 4, hipMemcpyHostToDevice));
+    if (nk) HIP_CHECK(hipMemcpy(kr->keys.p, ukeys.data(), nk * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(kr->offsets.p, offs.data(), (nk + 1) * 4, hipMemcpyHostToDevice));
+    kr->n_keys = (uint32_t)nk;
+    kr->size = size;
+    kr->column = d_key_of;
+    slot = std::move(kr);
+    return *slot;
+}
+
+// The rescore buffers of a set for n queries; one wait for the set's previous batch if one of them has to grow.
+void reserve_rescore_scratch(GroupScratch& gs, uint64_t n, uint64_t T, uint64_t R, uint64_t dim, uint64_t D, bool metric_rows) {
+    const size_t nr = n * R, rows = n * T + kExactQT;
+    const bool grow = gs.c_keys.n < nr || gs.c_found.n < n || gs.rs_rows.n < nr * T || gs.rs_qpad.n < rows * D || gs.rs_qnorm.n < rows ||
+                      (metric_rows && gs.rs_q.n < n * T * dim);
+    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+    gs.c_keys.alloc(nr);
+    gs.c_lb.alloc(nr);
+    gs.c_hits.alloc(nr);
+    gs.c_found.alloc(n);
+    gs.rs_score.alloc(nr);
+    gs.rs_rows.alloc(nr * T);
+    gs.rs_qpad.alloc(rows * D);
+    gs.rs_qnorm.alloc(rows);
+    gs.rs_stats.alloc(kStatWords);
+    if (metric_rows) gs.rs_q.alloc(n * T * dim);
+}
+
+// The filter a rescored query runs under, per query: filter_of and the table of bitmap pointers are host data and travel
+// the way n_tokens does -- written into the set's pinned buffer ([F pointers | n x int32]) and copied by one command on `st`;
+// the one host wait is for the copy this set carried the last time (ev_rs).  `hold` keeps the effective filters (F & ~R)
+// until the call is enqueued.  Called from the pass: `st` already waits for the set's previous batch.
+struct RescoreFilters {
+    const int32_t* d_filter_of = nullptr;
+    const uint32_t* const* d_bitmaps = nullptr;
+    const uint32_t* unfiltered = nullptr;
+    std::vector<std::shared_ptr<const cph_filter>> hold;
+};
+
+void upload_rescore_filters(cph_index* h, GroupScratch& gs, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
+                            uint64_t n, hipStream_t st, RescoreFilters& out) {
+    auto words = [&](const cph_filter* f) -> const uint32_t* {
+        out.hold.push_back(effective_filter(h, f));
+        return out.hold.back() ? out.hold.back()->words.p : nullptr;
+    };
+    if (!filter_of) {
+        out.unfiltered = words(F ? filters[0] : nullptr);
+        return;
+    }
+    out.unfiltered = words(nullptr);
+    const size_t need = (size_t)F * 8 + n * 4;
+    if (gs.rs_used) HIP_CHECK(hipEventSynchronize(gs.ev_rs));
+    if (gs.pin_rs_bytes < need || gs.d_rs.n < need) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.pin_rs) HIP_CHECK(hipHostFree(gs.pin_rs));
+        gs.pin_rs = nullptr;
+        gs.pin_rs_bytes = 0;
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_rs), need * 2, hipHostMallocDefault));
+        gs.pin_rs_bytes = need * 2;
+        gs.d_rs.alloc(need * 2);
+    }
+    if (!gs.ev_rs) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_rs, hipEventDisableTiming));
+    for (uint32_t f = 0; f < F; ++f) {
+        const uint64_t p = reinterpret_cast<uint64_t>(words(filters[f]));
+        std::memcpy(gs.pin_rs + (size_t)f * 8, &p, 8);
+    }
+    std::memcpy(gs.pin_rs + (size_t)F * 8, filter_of, n * 4);
+    HIP_CHECK(hipMemcpyAsync(gs.d_rs.p, gs.pin_rs, need, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(gs.ev_rs, st));
+    gs.rs_used = true;
+    out.d_bitmaps = reinterpret_cast<const uint32_t* const*>(gs.d_rs.p);
+    out.d_filter_of = reinterpret_cast<const int32_t*>(gs.d_rs.p + (size_t)F * 8);
+}
+
+MaxsimRescoreArgs maxsim_rescore_args(const cph_index* h, const KeyRows& kr, const float* qpad, const float* qnorm, const int32_t* cand_keys,
+                                      const float* cand_lb, const int32_t* cand_found, const int32_t* d_tokens, const int32_t* d_filter_of,
+                                      const uint32_t* const* d_bitmaps, const uint32_t* unfiltered, uint64_t T, uint64_t R, uint64_t k,
+                                      float* sc_score, uint32_t* sc_rows, const RerankOuts& o) {
+    MaxsimRescoreArgs a{};
+    a.s.raw = h->d_raw.p;
+    a.s.norm_sq = h->d_norm.p;
+    a.s.qpad = qpad;
+    a.s.qnorm = qnorm;
+    a.s.D = h->L.D;
+    a.csr = KeyRowsDev{kr.ids.p, kr.keys.p, kr.offsets.p, kr.n_keys};
+    a.cand_keys = cand_keys;
+    a.cand_lb = cand_lb;
+    a.cand_found = cand_found;
+    a.n_tokens = d_tokens;
+    a.filter_of = d_filter_of;
+    a.bitmaps = d_bitmaps;
+    a.unfiltered = unfiltered;
+    a.T = (uint32_t)T;
+    a.R = (uint32_t)R;
+    a.k = (uint32_t)k;
+    a.n_ids = (uint32_t)h->size();
+    a.sc_score = sc_score;
+    a.sc_rows = sc_rows;
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
+    a.out_keys = o.at<int32_t>(0);
+    a.out_score = o.at<float>(1);
+    a.out_hits = o.at<int32_t>(2);
+    a.out_rows = o.at<int64_t>(3);
+    a.out_found = o.at<int32_t>(4);
+    a.out_certified = o.at<int32_t>(5);
+    return a;
+}
+
+// The token rows as the search saw them (cosine: normalised into `metric_rows`), padded with their norms, on `st`.
+void pad_rescore_tokens(cph_index* h, const float* d_tokens_raw, uint64_t rows, float* metric_rows, float* qpad, float* qnorm,
+                        unsigned long long* d_stats, hipStream_t st) {
+    const float* src = d_tokens_raw;
+    if (h->metric == CPH_METRIC_COSINE) {
+        normalize_rows(d_tokens_raw, metric_rows, rows, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
+        src = metric_rows;
+    }
+    pad_queries(h, src, nullptr, (uint32_t)rows, (uint32_t)rows + kExactQT, qpad, qnorm, d_stats, 0, st);
+}
+
+// The lower-bound pass at k = R into the set's scratch, then the pad, the scan and the select.  The call's filters and keys
+// object ride along: the exact terms run under the same effective filters as the search.
+struct MaxsimRescoredSearch {
+    uint64_t T;
+    const int32_t* n_tokens;
+    uint64_t k, C, R;
+    const cph_group_keys* keys_obj;
+    const cph_filter* const* filters;
+    uint32_t F;
+    const int32_t* filter_of;
+    static constexpr PassKind kind = kPassUntimed;       // (the scan kernel alone is timed, inside the pass)
+    static constexpr bool keyed = true;
+    static constexpr const char* name = "maxsim";
+    uint64_t tokens() const { return T; }
+    void check_shape() const { check_maxsim_rescore_shape(T, C, k, R); }
+    void check_batch(uint64_t n) const { check_maxsim_rescore_batch(n, T, R); }
+    void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
+    RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found, int32_t* certified) const {
+        return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}, {certified, 4}}, 6};
+    }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float* d_queries, const RerankOuts& o,
+              hipStream_t st) const {
+        const KeyRows& kr = key_rows(h, keys_obj, d_key_of);
+        reserve_rescore_scratch(gs, n, T, R, h->dim, h->L.D, h->metric == CPH_METRIC_COSINE);
+        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
+        RescoreFilters rf;
+        upload_rescore_filters(h, gs, filters, F, filter_of, n, st, rf);
+        const RerankOuts cand = {{{gs.c_keys.p, 4 * R}, {gs.c_lb.p, 4 * R}, {gs.c_hits.p, 4 * R}, {nullptr, 0}, {gs.c_found.p, 4}}, 5};
+        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, R, d_key_of, h->size(), nullptr, cand), (uint32_t)n, h->device, st);
+        pad_rescore_tokens(h, d_queries, n * T, gs.rs_q.p, gs.rs_qpad.p, gs.rs_qnorm.p, gs.rs_stats.p, st);
+        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, gs.rs_qpad.p, gs.rs_qnorm.p, gs.c_keys.p, gs.c_lb.p, gs.c_found.p, d_tokens,
+                                                        rf.d_filter_of, rf.d_bitmaps, rf.unfiltered, T, R, k, gs.rs_score.p, gs.rs_rows.p, o);
+        timed_pass(h->pass_timer[kPassMaxsimRescore], st, [&] { maxsim_rescore_scan(a, (uint32_t)n, st); });
+        maxsim_rescore_select(a, (uint32_t)n, st);
     }
 };
 
@@ -6060,7 +6287,7 @@ void rerank_locked(cph_index* h, GroupScratch& gs, const Rerank& f, const Rerank
         for (uint64_t i = 0; i < c.n; ++i) std::fill_n(token_filter.begin() + i * T, T, c.filter_of[i]);
     }
     search_rows_then_pass(h, gs, d_queries, c.n * T, f.C, c.filters, c.F, token_filter.empty() ? c.filter_of : token_filter.data(), c.exact,
-                          h->pass_timer[Rerank::kind], st, [&] { f.pass(h, gs, c.n, d_key_of, o, st); });
+                          h->pass_timer[Rerank::kind], st, [&] { f.pass(h, gs, c.n, d_key_of, d_queries, o, st); });
 }
 
 // cph_search_X (stream == null: queries and outputs on the host, staged through the scratch set, and the call waits) and
@@ -6411,6 +6638,146 @@ int cph_host_maxsim_rows(const int64_t* ids, const float* dist, uint64_t n, uint
                                MaxsimSearch{tokens, n_tokens, k, candidates}.outs(out_keys, out_score, out_hits, out_rows, out_found));
         maxsim_rows_host(ids, dist, n, (uint32_t)tokens, n_tokens, (uint32_t)candidates, key_of, n_keys, rows, (uint32_t)k, out_keys,
                          out_score, out_hits, out_rows, out_found);
+    });
+}
+
+// ---- multi-vector search with exact rescoring of the best R keys (host_maxsim_rescore.h) ----
+int cph_search_maxsim_rescored(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                               uint64_t candidates, uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters,
+                               uint32_t n_filters, const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score,
+                               int32_t* out_hits, int64_t* out_rows, int32_t* out_found, int32_t* out_certified) {
+    return guarded([&] {
+        const MaxsimRescoredSearch f{tokens, n_tokens, k, candidates, rescore, keys, filters, n_filters, filter_of};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0,
+                             f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified)}, keys);
+    });
+}
+
+int cph_search_maxsim_rescored_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                      uint64_t candidates, uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters,
+                                      uint32_t n_filters, const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score,
+                                      int32_t* d_hits, int64_t* d_rows, int32_t* d_found, int32_t* d_certified, void* stream) {
+    return guarded([&] {
+        const MaxsimRescoredSearch f{tokens, n_tokens, k, candidates, rescore, keys, filters, n_filters, filter_of};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_keys, d_score, d_hits, d_rows, d_found, d_certified)},
+                      keys, &stream);
+    });
+}
+
+int cph_multi_search_maxsim_rescored(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                     uint64_t candidates, uint64_t rescore, const cph_group_keys* const* keys,
+                                     const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
+                                     int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found,
+                                     int32_t* out_certified) {
+    return guarded([&] {
+        const MaxsimRescoredSearch f{tokens, n_tokens, k, candidates, rescore, nullptr, filters, n_filters, filter_of};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0,
+                            f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified)},
+                     keys, [&](cph_index* h, const RerankCall& s, const cph_group_keys* key, uint64_t lo) {
+            return cph_search_maxsim_rescored(h, s.q, s.n, tokens, n_tokens ? n_tokens + lo : nullptr, k, candidates, rescore, key, s.filters, s.F,
+                                              s.filter_of, s.exact ? 1 : 0, s.out.at<int32_t>(0), s.out.at<float>(1), s.out.at<int32_t>(2),
+                                              s.out.at<int64_t>(3), s.out.at<int32_t>(4), s.out.at<int32_t>(5));
+        });
+    });
+}
+
+int cph_prepare_maxsim_rescore(cph_index* h, const cph_group_keys* keys) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        refuse_ip(h, "maxsim search");
+        require_finalized(h);
+        const int32_t* d_key_of = group_key_column(h, keys);
+        h->use_device();
+        (void)key_rows(h, keys, d_key_of);
+    });
+}
+
+int cph_debug_time_maxsim_rescore(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassMaxsimRescore, on != 0); });
+}
+
+int cph_debug_last_maxsim_rescore_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassMaxsimRescore, us); });
+}
+
+static void check_maxsim_rescore_args(const int32_t* cand_keys, const float* cand_lb, const int32_t* cand_found, uint64_t n, uint64_t R,
+                                      const float* tokens, uint64_t T, const int32_t* n_tokens, uint64_t k, const RerankOuts& o) {
+    if (!cand_keys || !cand_lb || !cand_found || !tokens || !o.all()) throw InvalidArg("null argument");
+    check_maxsim_rescore_shape(T, 1, k, R);
+    if (n < 1) throw InvalidArg("maxsim rescore: sizes out of range");
+    check_maxsim_rescore_batch(n, T, R);
+    check_maxsim_tokens(n_tokens, n, T);
+    for (uint64_t i = 0; i < n; ++i)
+        if (cand_found[i] < 0 || (uint64_t)cand_found[i] > R)
+            throw InvalidArg("cand_found[" + std::to_string(i) + "] = " + std::to_string(cand_found[i]) + " is outside [0, " + std::to_string(R) + "]");
+}
+
+int cph_maxsim_rescore_hook(cph_index* h, const int32_t* cand_keys, const float* cand_lb, const int32_t* cand_found, uint64_t n,
+                            uint64_t rescore, const float* tokens, uint64_t n_tok, const int32_t* n_tokens, const cph_group_keys* keys,
+                            const uint32_t* allow, uint64_t k, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found, int32_t* out_certified) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        refuse_ip(h, "maxsim search");
+        require_finalized(h);
+        const MaxsimRescoredSearch f{n_tok, n_tokens, k, 1, rescore, keys, nullptr, 0, nullptr};
+        const RerankOuts o = f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified);
+        check_maxsim_rescore_args(cand_keys, cand_lb, cand_found, n, rescore, tokens, n_tok, n_tokens, k, o);
+        const int32_t* d_key_of = group_key_column(h, keys);
+        h->use_device();
+        const KeyRows& kr = key_rows(h, keys, d_key_of);
+        const uint64_t T = n_tok, R = rescore, rows = n * T, nw = (h->size() + 31) / 32;
+        const DevBuf<int32_t> d_ck = uploaded(cand_keys, n * R), d_cf = uploaded(cand_found, n), d_tok = uploaded(n_tokens, n);
+        const DevBuf<float> d_lb = uploaded(cand_lb, n * R), d_q = uploaded(tokens, rows * h->dim);
+        const DevBuf<uint32_t> d_allow = uploaded(allow, n * nw);
+        std::vector<uint64_t> ptrs(n);
+        std::vector<int32_t> of(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            ptrs[i] = reinterpret_cast<uint64_t>(d_allow.p + i * nw);
+            of[i] = (int32_t)i;
+        }
+        const DevBuf<uint64_t> d_ptrs = uploaded(allow ? ptrs.data() : nullptr, n);
+        const DevBuf<int32_t> d_of = uploaded(allow ? of.data() : nullptr, n);
+        DevBuf<float> d_metric(rows * h->dim), d_qpad((rows + kExactQT) * h->L.D), d_qnorm(rows + kExactQT), d_score(n * R);
+        DevBuf<uint32_t> d_rows(n * R * T);
+        DevBuf<unsigned long long> d_stats(kStatWords);
+        PoisonedOuts po(o, n);
+        pad_rescore_tokens(h, d_q.p, rows, d_metric.p, d_qpad.p, d_qnorm.p, d_stats.p, nullptr);
+        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, d_qpad.p, d_qnorm.p, d_ck.p, d_lb.p, d_cf.p, n_tokens ? d_tok.p : nullptr,
+                                                        allow ? d_of.p : nullptr,
+                                                        allow ? reinterpret_cast<const uint32_t* const*>(d_ptrs.p) : nullptr, nullptr, T, R, k,
+                                                        d_score.p, d_rows.p, po.dev);
+        maxsim_rescore_scan(a, (uint32_t)n, nullptr);
+        maxsim_rescore_select(a, (uint32_t)n, nullptr);
+        po.download();
+    });
+}
+
+int cph_host_maxsim_rescore(const int32_t* cand_keys, const float* cand_lb, const int32_t* cand_found, uint64_t n, uint64_t rescore,
+                            const float* tokens, uint64_t n_tok, uint64_t dim, const int32_t* n_tokens, const float* raw,
+                            const float* norm_sq, uint64_t n_ids, uint64_t D, const int32_t* key_of, const uint32_t* allow,
+                            const uint32_t* rows, uint64_t k, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                            int32_t* out_found, int32_t* out_certified) {
+    return guarded([&] {
+        if (!raw || !norm_sq || !key_of) throw InvalidArg("null argument");
+        if (D < 8 || D > 0xFFFFFFFFull || (D & 7) || dim < 1 || dim > D) throw InvalidArg("maxsim rescore: D must be a multiple of 8 and dim <= D");
+        if (n_ids < 1 || n_ids > 0xFFFFFFFFull) throw InvalidArg("maxsim rescore: sizes out of range");
+        const MaxsimRescoredSearch f{n_tok, n_tokens, k, 1, rescore, nullptr, nullptr, 0, nullptr};
+        check_maxsim_rescore_args(cand_keys, cand_lb, cand_found, n, rescore, tokens, n_tok, n_tokens, k,
+                                  f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified));
+        maxsim_rescore_host(cand_keys, cand_lb, cand_found, n, (uint32_t)rescore, tokens, (uint32_t)n_tok, (uint32_t)dim, n_tokens, raw, norm_sq,
+                            n_ids, (uint32_t)D, key_of, allow, rows, (uint32_t)k, out_keys, out_score, out_hits, out_rows, out_found,
+                            out_certified);
+    });
+}
+
+int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_t* out_keys, uint32_t* out_offsets, uint64_t* out_n_keys) {
+    return guarded([&] {
+        if (!out_offsets || !out_n_keys || (n != 0 && (!keys || !out_ids || !out_keys))) throw InvalidArg("null argument");
+        if (n > 0xFFFFFFFEull) throw InvalidArg("key rows: too many ids");
+        *out_n_keys = key_rows_host(keys, n, out_ids, out_keys, out_offsets);
     });
 }
 

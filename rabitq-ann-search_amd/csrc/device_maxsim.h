@@ -49,7 +49,7 @@ struct MaxsimArgs {
     int32_t* out_keys;                    // [n][k]
     float* out_score;                     // [n][k]
     int32_t* out_hits;                    // [n][k]
-    int64_t* out_rows;                    // [n][k][T]
+    int64_t* out_rows;                    // [n][k][T], or null: not written
     int32_t* out_found;                   // [n]
 };
 
@@ -259,6 +259,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
         reinterpret_cast<uint32_t*>(a.out_score)[q * k + o] = score;
         a.out_hits[q * k + o] = hits;
     }
+    if (!a.out_rows) return;                              // (the rescored search keeps keys and scores only)
     int64_t* __restrict__ out_rows = a.out_rows + q * k * T;
     for (uint32_t idx = tid; idx < k * T; idx += kMaxsimThreads) {
         const uint32_t o = idx / T, t = idx - o * T;

@@ -1178,6 +1178,81 @@ int cph_ip_epilogue_hook(int device, const int64_t* ids, float* dist, uint64_t n
 int cph_host_ip_augment(const float* x, uint64_t n, uint64_t dim, int mode, float max_sq_norm, float* out, float* c, float* m2, uint64_t counters[3]);
 int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k, const float* c);
 
+/* ---- two-stage search: rescoring candidates against resident full-size rows (not in the reference) ----
+ * For embeddings whose prefix is itself a usable embedding: the index holds the first cph_dim coordinates, a
+ * cph_rescore_vectors object the full dim_full coordinates of the same rows, and one call runs the ordinary search at
+ * k = candidates and rescores those candidates against the full rows on the device, on the same stream.  Filters,
+ * exact, per-query filters, removed rows, the tail, both id spaces, the cosine metric and the refusals are those of the
+ * search underneath.  The statement is csrc/host_rescore.h (host form) and tests/rescore_model.py (numpy form).
+ *
+ * cph_rescore_vectors_create  rows [size][dim_full] float32 (host), size == cph_size, 1 <= dim_full <= 8192, indexed by
+ *     internal ids or by input rows (space = CPH_IDS_INPUT: needs a row map; the inverse of the map is made once on the
+ *     host and rescore_rows_in_kernel writes every row at its internal position).  dtype: how the rows are stored,
+ *     CPH_RESCORE_FLOAT16 (round to nearest even) or CPH_RESCORE_FLOAT32; the row stride is padded with zeros to a
+ *     multiple of 16 bytes, and one float32 squared norm per row is summed from the stored values.  metric:
+ *     CPH_RESCORE_L2 or CPH_RESCORE_IP -- it belongs to the object, not to the index (cosine: normalise rows and full
+ *     queries and use CPH_RESCORE_IP).  The rows are uploaded in chunks of at most 256 MB.  A row that holds a NaN or an
+ *     Inf, a value that overflows float16, or whose squared norm overflows refuses the call (CPH_INVALID_ARGUMENT: the
+ *     lowest such row and their number); no object exists then and nothing stays allocated.
+ *     The object is resident on the handle's device and follows the rules of cph_group_keys: it serves the handle and
+ *     the index it was made for (a load, build or compact invalidates it: "made for another index"; after cph_add it is
+ *     refused with the size message), another device refuses it, cph_save_native does not carry it.
+ * cph_rescore_vectors_destroy waits for the device, then frees; NULL is a no-op.
+ * cph_rescore_vectors_info    size, dim_full, dtype, metric, the stored bytes of a row and the device bytes of the object.
+ * cph_rescore_vectors_get     the stored bytes of rows [first, first + count): rows_out [count][row bytes], norms_out
+ *     [count]; waits for the device.
+ *
+ * cph_search_rescored  queries [n][cph_dim] go to the graph, full_queries [n][dim_full] to the rescoring (dim_full must
+ *     be the object's); both pointers are always given (a Matryoshka caller passes the prefixes as `queries`).
+ *     k <= candidates <= 1024.  Per query, over its candidate row (internal ids, -1 / FLT_MAX padding): padding, ids at
+ *     or above cph_size and every occurrence of an id after its first are dropped; each survivor is scored in float32,
+ *     every product and sum rounded on its own, in the sum shape csrc/host_rescore.h states (a pure function of dim_full
+ *     and dtype) -- L2: max(0, (|q|^2 + |x|^2) - 2 q.x), IP: -(q.x); a NaN score is dropped; the k best by (score,
+ *     internal id) ascending are returned: ids [k] int64 (input rows under CPH_IDS_INPUT), score [k], first [k] = the
+ *     candidate's first-stage distance bytes; unused slots are -1 / FLT_MAX / FLT_MAX.  A query whose |q|^2 is not < inf
+ *     gets a row of padding.  rescore_rows_kernel (csrc/device_rescore.h), one workgroup per query, writes every slot.
+ *     cph_search_rescored takes and returns host arrays and waits; cph_search_rescored_device takes device pointers
+ *     and only enqueues on `stream`.  Refused before any output is written: an inner-product index, a stale, foreign or
+ *     wrong-size object, k > candidates, candidates > 1024, a dim_full that is not the object's.  Partitioned indexes
+ *     have no rescored search: every part has its own internal ids.
+ * cph_multi_search_rescored  the same over the shards of a replicated index; vectors[r] = the object made on
+ *     cph_multi_replica(m, r); the bytes are those of one device.
+ * cph_debug_time_rescored / cph_debug_last_rescored_us  as cph_debug_time_diverse: the rescore_rows_kernel launch of every
+ *     rescored search of this handle between two HIP events while switched on.
+ * Test hooks: cph_rescore_rows_hook runs the kernel on given host candidate rows (ids / dist [n][candidates]) and full
+ *     queries [n][dim_full of the object]; the device outputs start as 0xA5 bytes.  cph_host_rescore_rows is the host
+ *     statement over stored rows and norms as cph_rescore_vectors_get returns them; cph_host_rescore_rows_in the host
+ *     statement of the conversion, the scatter and the norms (row_map [n_map]: rows arrive in input order and row
+ *     row_map[i] goes to position i, rows at or above n_map stay where they are; NULL: internal order); *bad = the
+ *     number of refused rows, *first_bad the lowest (UINT64_MAX: none).  Neither makes a HIP call. */
+enum { CPH_RESCORE_FLOAT16 = 0, CPH_RESCORE_FLOAT32 = 1 };
+enum { CPH_RESCORE_L2 = 0, CPH_RESCORE_IP = 1 };
+typedef struct cph_rescore_vectors cph_rescore_vectors;
+int cph_rescore_vectors_create(cph_index* h, const float* rows, uint64_t size, uint64_t dim_full, int space, int dtype, int metric,
+                               cph_rescore_vectors** out);
+int cph_rescore_vectors_destroy(cph_rescore_vectors* rv);
+int cph_rescore_vectors_info(const cph_rescore_vectors* rv, uint64_t* size, uint64_t* dim_full, int* dtype, int* metric, uint64_t* row_bytes,
+                             uint64_t* nbytes);
+int cph_rescore_vectors_get(const cph_rescore_vectors* rv, uint64_t first, uint64_t count, void* rows_out, float* norms_out);
+int cph_search_rescored(cph_index* h, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                        uint64_t candidates, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                        const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first);
+int cph_search_rescored_device(cph_index* h, const float* d_queries, uint64_t n, const float* d_full_queries, uint64_t dim_full, uint64_t k,
+                               uint64_t candidates, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                               const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, float* d_first, void* stream);
+int cph_multi_search_rescored(cph_multi* m, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                              uint64_t candidates, const cph_rescore_vectors* const* vectors, const cph_filter* const* filters,
+                              uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first);
+int cph_debug_time_rescored(cph_index* h, int on);
+int cph_debug_last_rescored_us(cph_index* h, double* us);
+int cph_rescore_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* full_queries,
+                          const cph_rescore_vectors* vectors, uint64_t k, int64_t* out_ids, float* out_score, float* out_first);
+int cph_host_rescore_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* full_queries,
+                          uint64_t dim_full, const void* stored, const float* norms, uint64_t n_ids, int dtype, int metric,
+                          const uint32_t* rows, uint64_t k, int64_t* out_ids, float* out_score, float* out_first);
+int cph_host_rescore_rows_in(const float* rows_in, uint64_t n, uint64_t dim_full, int dtype, const uint32_t* row_map, uint64_t n_map,
+                             void* stored, float* norms, uint64_t* bad, uint64_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,7 +284,28 @@ SYMBOLS = {
     "cph_host_ip_augment": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "cph_host_ip_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "cph_rescore_vectors_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cph_rescore_vectors_destroy": (C.c_int, [C.c_void_p]),
+    "cph_rescore_vectors_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cph_rescore_vectors_get": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cph_search_rescored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_search_rescored_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_multi_search_rescored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_debug_time_rescored": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_rescored_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_rescore_rows_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_rescore_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_rescore_rows_in": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
+RESCORE_FLOAT16, RESCORE_FLOAT32 = 0, 1      # cph_rescore_vectors_create: dtype
+RESCORE_L2, RESCORE_IP = 0, 1                # ... and metric
 
 _LIB = None
 

@@ -229,6 +229,74 @@ class GroupKeys:
             pass
 
 
+class RescoreVectors:
+    """Full-size rows for two-stage search on the index' device (CPIndex.make_rescore_vectors): one row of `dim`
+    coordinates per id of the index, stored as `dtype` ("float16" or "float32") with one float32 squared norm per row, and
+    the `metric` ("l2" or "ip") search_rescored scores them by.  It follows the rules of GroupKeys: it serves the index
+    it was made for and covers `size` ids -- after an add() it is refused with the size error; load(), build() and
+    compact() invalidate it; save_native does not carry it.  A multi-device index' object holds one copy per replica.
+    close() waits for the batches that may still read it."""
+
+    def __init__(self, index, rows, input_rows, dtype, metric):
+        self._hs = []                # one cph_rescore_vectors per replica (a single-device index: one)
+        self.size, self.dim = int(rows.shape[0]), int(rows.shape[1])
+        self.dtype, self.metric = dtype, metric
+        code = _lib.IDS_INPUT if input_rows else _lib.IDS_INTERNAL
+        dt = _lib.RESCORE_FLOAT32 if dtype == "float32" else _lib.RESCORE_FLOAT16
+        mt = _lib.RESCORE_IP if metric == "ip" else _lib.RESCORE_L2
+        try:
+            for rh in index._replicas():
+                h = C.c_void_p()
+                _lib.check(_lib.lib().cph_rescore_vectors_create(rh, rows.ctypes.data if rows.size else None, self.size, self.dim, code,
+                                                                 dt, mt, C.byref(h)))
+                self._hs.append(h)
+        except Exception:
+            self.close()
+            raise
+
+    def _info(self):
+        if not self._hs:
+            raise ValueError("rescore vectors were closed")
+        size, dim, row_bytes, nbytes = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        dt, mt = C.c_int(), C.c_int()
+        _lib.check(_lib.lib().cph_rescore_vectors_info(self._hs[0], C.byref(size), C.byref(dim), C.byref(dt), C.byref(mt),
+                                                       C.byref(row_bytes), C.byref(nbytes)))
+        return size.value, dim.value, dt.value, mt.value, row_bytes.value, nbytes.value
+
+    @property
+    def row_bytes(self):
+        """Stored bytes of one row: dim coordinates of the dtype, padded to a multiple of 16."""
+        return self._info()[4]
+
+    @property
+    def nbytes(self):
+        """Device bytes of the rows and norms, summed over the replicas."""
+        return self._info()[5] * len(self._hs)
+
+    def stored(self, first=0, count=None, replica=0):
+        """(rows uint8 [count, row_bytes], norms float32 [count]): the stored bytes in internal id order; waits for the
+        device."""
+        size, _, _, _, rb, _ = self._info()
+        count = size - first if count is None else int(count)
+        rows, norms = np.empty((count, rb), np.uint8), np.empty(count, np.float32)
+        _lib.check(_lib.lib().cph_rescore_vectors_get(self._hs[replica], int(first), count, rows.ctypes.data if count else None,
+                                                      norms.ctypes.data if count else None))
+        return rows, norms
+
+    def close(self):
+        hs = getattr(self, "_hs", [])
+        self._hs = []
+        for h in hs:
+            if h.value:
+                _lib.check(_lib.lib().cph_rescore_vectors_destroy(h))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CPIndex:
     """`devices=[...]` (instead of `device`): the index is replicated on every listed HIP device (duplicates allowed:
     several replicas on one GPU) and search_batch splits its queries across the replicas in one call, with results
@@ -1606,6 +1674,145 @@ class CPIndex:
         """Device time (HIP events, microseconds) of the scan kernel of the last rescored maxsim search made under
         time_maxsim_rescore() on the given replica; waits for it."""
         return self._last_pass_us("cph_debug_last_maxsim_rescore_us", replica)
+
+    # -- two-stage search: rescoring against full-size rows (not in the reference) -------------------
+    RESCORE_MAX_CANDIDATES = 1024
+    RESCORE_MAX_DIM = 8192
+
+    def make_rescore_vectors(self, rows, ids=None, dtype="float16", metric="l2"):
+        """RescoreVectors from a float32 or float16 array [size, dim_full] (1 <= dim_full <= 8192), one row per id of the
+        index, indexed in the space `ids` ("internal" or "input"; default: result_ids, as for make_group_keys; the input
+        form needs the row map): the `vectors` argument of search_rescored.  `dtype`: how the rows are stored on the
+        device, "float16" (default; float32 input is rounded to nearest even) or "float32".  `metric`: "l2" or "ip"; it
+        belongs to the object, not to the index -- for cosine, normalise the rows and the full queries yourself and use
+        "ip".  ValueError names the lowest row that holds a NaN or an Inf, a value that overflows float16, or whose
+        squared norm overflows, and how many there are; no object exists then."""
+        self._no_parts("make_rescore_vectors")
+        space = self._id_space(ids)
+        if dtype not in ("float16", "float32"):
+            raise ValueError('dtype must be "float16" or "float32"')
+        if metric not in ("l2", "ip"):
+            raise ValueError('metric must be "l2" or "ip" (cosine: normalise rows and full queries and use "ip")')
+        a = np.asarray(rows)
+        if a.dtype not in (np.float32, np.float16):
+            raise ValueError("rows must be a float32 or float16 array")
+        if a.ndim != 2 or a.shape[0] != self.size or not 1 <= a.shape[1] <= self.RESCORE_MAX_DIM:
+            raise ValueError(f"rows must be a ({self.size}, dim_full) array (the index size), 1 <= dim_full <= {self.RESCORE_MAX_DIM}")
+        return RescoreVectors(self, _as_f32(a), space == "input", dtype, metric)       # (float16 -> float32 is exact)
+
+    def _rescored_args(self, n, k, vectors, candidates, filter, filter_of):
+        """Validation shared by both rescored entry points -> (k, C, the filters as of _filters_arg)."""
+        if self._p is not None:
+            raise ValueError("search_rescored is not defined on a partitioned index (every part has its own internal ids): "
+                             "use part(i).search_rescored")
+        if not isinstance(vectors, RescoreVectors):
+            raise ValueError("vectors must be a RescoreVectors object (make_rescore_vectors)")
+        if not vectors._hs:
+            raise ValueError("rescore vectors were closed")
+        if len(vectors._hs) != len(self._replicas()):
+            raise ValueError("rescore vectors were made for an index with another number of replicas")
+        k = int(k)
+        cap = self.RESCORE_MAX_CANDIDATES
+        if k < 1:
+            raise ValueError("search_rescored needs k >= 1")
+        if candidates is None:
+            if k > cap:
+                raise ValueError(f"search_rescored needs k <= {cap} (the longest candidate row)")
+            candidates = min(cap, max(64, 4 * k))    # a policy, not a measured optimum
+        candidates = int(candidates)
+        if not k <= candidates <= cap:
+            raise ValueError(f"candidates must lie in [k, {cap}]")
+        return k, candidates, self._filters_arg(filter, filter_of, n)
+
+    @staticmethod
+    def _rescored_table(n, k):
+        return (((n, k), "int64"), ((n, k), "float32"), ((n, k), "float32"))
+
+    def search_rescored(self, queries, k=DEFAULT_K, vectors=None, full_queries=None, candidates=None, filter=None, exact=False,
+                        filter_of=None, label=None):
+        """Two-stage search: (ids int64 [n, k], score float32 [n, k], first float32 [n, k]).  The index finds C candidates
+        per query among its (narrow) rows, and the device rescores them against the full-size rows in `vectors`
+        (make_rescore_vectors) with the full query; nothing but the k answers leaves the device.
+        `queries` [n, dim] go to the graph and `full_queries` [n, dim_full] to the rescoring; with full_queries=None,
+        `queries` is [n, dim_full] with dim_full >= dim and the graph searches its first dim coordinates (embeddings
+        whose prefix is itself an embedding).  A query's candidate row is row i of search_batch(queries, C, filter=...,
+        exact=..., filter_of=...) -- same routing, removed rows, tail and refusals -- with padding and repeated ids
+        dropped.  Each candidate is scored in float32: "l2" max(0, (|q|^2 + |x|^2) - 2 q.x), "ip" -(q.x), x the STORED row
+        (rounded to float16 under dtype="float16"); the k best by (score, internal id) ascending are returned, `first` is
+        the candidate's first-stage distance; fewer than k candidates: ids padded with -1 (input rows under result_ids =
+        "input"), score and first with FLT_MAX.  A query whose full vector has no finite squared norm gets padding.
+        `candidates=C` (k <= C <= 1024); None takes C = min(1024, max(64, 4 * k)): a policy, not a measured optimum, in
+        ONE pass.  A multi-device index shards the queries like search_batch; the bytes are those of one device.  A
+        partitioned index is refused (use part(i).search_rescored), an inner-product index too: search a cosine or L2
+        index and give the object metric="ip"."""
+        q = _as_f32(queries)
+        if full_queries is None:
+            fq = q
+            if q.ndim != 2 or q.shape[1] < self._dim:
+                raise ValueError("queries must be a (n, dim_full) array with dim_full >= dim when full_queries is None")
+            q = np.ascontiguousarray(q[:, :self._dim])
+        else:
+            fq = _as_f32(full_queries)
+        if q.ndim != 2 or q.shape[1] != self._dim:
+            raise ValueError("queries must be a (n, dim) array")
+        if fq.ndim != 2 or fq.shape[0] != q.shape[0]:
+            raise ValueError("full_queries must be a (n, dim_full) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_rescored(
+                q, k, vectors, full_queries=fq, candidates=candidates, filter=f, exact=exact, filter_of=fo))
+        n = q.shape[0]
+        k, C_, filters = self._rescored_args(n, k, vectors, candidates, filter, filter_of)
+        return self._rerank_host("rescored", q, (fq.ctypes.data if n else None, fq.shape[1], k, C_), vectors, filters, exact,
+                                 self._rescored_table(n, k))
+
+    def search_rescored_device(self, queries, k=DEFAULT_K, vectors=None, full_queries=None, candidates=None, out=None, stream=None,
+                               filter=None, exact=False, filter_of=None, label=None):
+        """search_rescored on float32 torch tensors on this index' device; returns (ids, score, first) as torch tensors on
+        the same device.  Like search_batch_device it only enqueues, on `stream` (default: torch's current stream), and
+        never waits.  With full_queries=None the contiguous prefix of `queries` is made on that stream.  `out`: the three
+        tensors to write (contiguous, on the queries' device).  filter / filter_of / label are host data as in
+        search_batch_device; a filter or RescoreVectors closed after the call waits for the batch.  A multi-device index
+        runs the whole batch on one replica on the queries' device."""
+        import torch
+        if queries.dim() != 2 or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, dim) array")
+        if full_queries is None:
+            fq = queries
+            if queries.shape[1] < self._dim:
+                raise ValueError("queries must be a (n, dim_full) array with dim_full >= dim when full_queries is None")
+            cur = torch.cuda.current_stream(queries.device)
+            st = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+            on = cur if st == cur.cuda_stream else (stream if isinstance(stream, torch.cuda.Stream)
+                                                    else torch.cuda.ExternalStream(st, device=queries.device))
+            with torch.cuda.stream(on):
+                queries = queries[:, :self._dim].contiguous()
+        else:
+            fq = full_queries
+        if queries.shape[1] != self._dim:
+            raise ValueError("queries must be a (n, dim) array")
+        if (fq.dim() != 2 or fq.shape[0] != queries.shape[0] or fq.dtype != torch.float32 or fq.device != queries.device
+                or not fq.is_contiguous()):
+            raise ValueError("the full queries must be a contiguous float32 (n, dim_full) tensor on the queries' device")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_rescored_device(
+                queries, k, vectors, full_queries=fq, candidates=candidates, out=out, stream=stream, filter=f, exact=exact,
+                filter_of=fo))
+        n = queries.shape[0]
+        k, C_, filters = self._rescored_args(n, k, vectors, candidates, filter, filter_of)
+        return tuple(self._rerank_device("rescored", queries, (fq.data_ptr() if n else None, fq.shape[1], k, C_), vectors, filters, exact,
+                                         self._rescored_table(n, k), out, stream,
+                                         ("out must be the three tensors (ids, score, first)",
+                                          "out must be contiguous (n, k) int64 / float32 / float32 tensors on the queries' device")))
+
+    def time_rescored(self, on=True):
+        """Debug hook of the measurement script: while on, the rescoring kernel of every rescored search is bracketed by
+        HIP events (last_rescored_us).  Off by default."""
+        self._time_pass("cph_debug_time_rescored", on)
+
+    def last_rescored_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the rescoring kernel of the last rescored search made under
+        time_rescored() on the given replica; waits for that launch."""
+        return self._last_pass_us("cph_debug_last_rescored_us", replica)
 
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):

@@ -41,6 +41,7 @@
 #include "device_group.h"
 #include "device_maxsim.h"
 #include "device_maxsim_rescore.h"
+#include "device_rescore.h"
 #include "device_normalize.h"
 #include "device_ip.h"
 #include "host_index.h"
@@ -191,11 +192,13 @@ constexpr size_t kRangeScratchKept = 2;
 // rows as the search saw them (rs_q: cosine only), padded (rs_qpad, rs_qnorm), the exact scores and argmin ids of every
 // candidate slot, and the call's host tables -- filter_of and the bitmap pointers -- which travel like n_tokens: written into
 // pin_rs, copied to d_rs by one command on the call's stream, ev_rs behind that copy.  A handle that never rescored
-// allocates none of them.
+// allocates none of them.  The rescored search (device_rescore.h) adds d_fq, the staged full queries of its host form; a
+// handle that never calls it allocates nothing for it.
 constexpr int kMaxRerankOuts = 6;
 struct GroupScratch {
     DevBuf<int64_t> r_ids;
     DevBuf<float> r_dist, d_q;
+    DevBuf<float> d_fq;
     DevBuf<uint8_t> out[kMaxRerankOuts];
     DevBuf<int32_t> d_tok;
     hipEvent_t ev = nullptr;
@@ -227,8 +230,9 @@ struct KeyRows {
 };
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 // The passes a handle can time (PassTimer).  kPassMaxsimRescore is the scan kernel of the rescored maxsim search alone, bracketed
-// inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassUntimed, kPassKinds };
+// inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
+// rescoring kernel of cph_search_rescored* (device_rescore.h).
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassUntimed, kPassKinds };
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -569,6 +573,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed maxsim search has run on this handle (cph_debug_time_maxsim)",
     "no timed label pass has run on this handle (cph_debug_time_label_filters)",
     "no timed rescored maxsim search has run on this handle (cph_debug_time_maxsim_rescore)",
+    "no timed rescored search has run on this handle (cph_debug_time_rescored)",
     "this pass is not timed",
 };
 
@@ -1868,7 +1873,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 113; }
+int cph_version(void) { return 114; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -5744,9 +5749,11 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
 // One entry path for the three: an ordinary search at k = C into scratch rows the handle owns, then one kernel over those
 // rows on the same stream.  The rows hold INTERNAL ids whatever the handle returns (the keys are looked up by internal
 // id); the row map is applied where an id is written.  Nothing here waits for the device in the _device form.  A
-// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch, MaxsimRescoredSearch): its scalars, its checks,
-// its output table and its pass; the entries, the scratch, the replica fan-out and the hooks below are written once over
-// that.  (MaxsimRescoredSearch's pass is four launches, and the first one on a key column waits for the device: key_rows.)
+// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch, MaxsimRescoredSearch, RescoredSearch): its
+// scalars, its checks (check_on: those that need the handle a call runs on), its output table, what the host form stages
+// besides the queries (stage) and its pass; the entries, the scratch, the replica fan-out and the hooks below are written
+// once over that.  (MaxsimRescoredSearch's pass is four launches, and the first one on a key column waits for the device:
+// key_rows.)
 struct cph_group_keys {
     cph_index* h = nullptr;                    // the handle it was made for ...
     uint64_t epoch = 0;                        // ... and the index that handle held then (index_epoch)
@@ -5915,6 +5922,8 @@ struct GroupedSearch {
     }
     void check_batch(uint64_t n) const { check_batch_size(n); }
     void check_inputs(uint64_t) const {}
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int64_t* ids, float* dist, int32_t* keys, int32_t* counts, uint8_t* complete) const {
         return {{{ids, 8 * k * g}, {dist, 4 * k * g}, {keys, 4 * k}, {counts, 4 * k}, {complete, 1}}, 5};
     }
@@ -5970,6 +5979,8 @@ struct DiverseSearch {
     void check_shape() const { check_diverse_shape(k, C, lam); }
     void check_batch(uint64_t n) const { check_batch_size(n); }
     void check_inputs(uint64_t) const {}
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int64_t* ids, float* dist, float* gap) const { return {{{ids, 8 * k}, {dist, 4 * k}, {gap, 4 * k}}, 3}; }
     void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
         diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, o), (uint32_t)n, st);
@@ -6063,6 +6074,8 @@ struct MaxsimSearch {
     void check_shape() const { check_maxsim_shape(T, C, k); }
     void check_batch(uint64_t n) const { check_maxsim_batch(n, T); }
     void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found) const {
         return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}}, 5};
     }
@@ -6241,6 +6254,8 @@ struct MaxsimRescoredSearch {
     void check_shape() const { check_maxsim_rescore_shape(T, C, k, R); }
     void check_batch(uint64_t n) const { check_maxsim_rescore_batch(n, T, R); }
     void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found, int32_t* certified) const {
         return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}, {certified, 4}}, 6};
     }
@@ -6298,6 +6313,7 @@ void rerank_search(cph_index* h, const Rerank& f, const RerankCall& c, const cph
     std::lock_guard<std::mutex> lk(h->mu);
     refuse_ip(h, (std::string(Rerank::name) + " search").c_str());
     if (!rerank_has_work(h, f, c)) return;
+    f.check_on(h, 0);
     const int32_t* d_key_of = Rerank::keyed ? group_key_column(h, keys) : nullptr;
     h->use_device();
     if (stream) return rerank_locked(h, next_group_scratch(h), f, c, c.q, d_key_of, c.out, reinterpret_cast<hipStream_t>(*stream));
@@ -6306,6 +6322,7 @@ void rerank_search(cph_index* h, const Rerank& f, const RerankCall& c, const cph
     const size_t q_floats = (size_t)c.n * f.tokens() * h->dim;
     const RerankOuts dev = reserve_group_scratch(gs, q_floats, c.n, c.out);
     HIP_CHECK(hipMemcpyAsync(gs.d_q.p, c.q, q_floats * 4, hipMemcpyHostToDevice, st));
+    f.stage(gs, c.n, st);
     rerank_locked(h, gs, f, c, gs.d_q.p, d_key_of, dev, st);
     for (int i = 0; i < dev.count; ++i) HIP_CHECK(hipMemcpyAsync(c.out.o[i].p, dev.o[i].p, c.n * dev.o[i].stride, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -6323,7 +6340,7 @@ void rerank_multi(cph_multi* m, const Rerank& f, const RerankCall& c, const cph_
     const uint64_t q_floats = f.tokens() * m->reps[0]->dim;
     check_filter_args(c);
     multi_fan_out(m, c.n, [&](cph_index* h, uint32_t r) {
-        rerank_has_work(h, f, c);
+        if (rerank_has_work(h, f, c)) f.check_on(h, r);
         if (Rerank::keyed) {
             if (keys && !keys[r]) throw InvalidArg(std::string("a ") + Rerank::name + " multi-device search needs one keys object per replica");
             (void)group_key_column(h, keys ? keys[r] : nullptr);
@@ -6778,6 +6795,313 @@ int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_
         if (!out_offsets || !out_n_keys || (n != 0 && (!keys || !out_ids || !out_keys))) throw InvalidArg("null argument");
         if (n > 0xFFFFFFFEull) throw InvalidArg("key rows: too many ids");
         *out_n_keys = key_rows_host(keys, n, out_ids, out_keys, out_offsets);
+    });
+}
+
+}  // extern "C"
+
+// ---- two-stage search: rescoring against resident full-size rows (device_rescore.h, host_rescore.h) --------------------
+// A fourth re-ranker on the entry path above.  What is new is its second resident matrix, a cph_rescore_vectors object
+// with the lifetime rules of cph_group_keys: one handle, one index_epoch, one device.
+struct cph_rescore_vectors {
+    cph_index* h = nullptr;
+    uint64_t epoch = 0;
+    int device = 0;
+    uint64_t size = 0;                         // ids it covers
+    uint32_t dim = 0;                          // dim_full
+    bool f32 = false, ip = false;
+    RescoreLayout L{};
+    DevBuf<uint8_t> rows;                      // [size][L.stride], internal-id order
+    DevBuf<float> norms;                       // [size]
+};
+
+namespace {
+
+RescoreStore rescore_store(const cph_rescore_vectors* rv) {
+    return RescoreStore{rv->rows.p, rv->norms.p, (uint32_t)rv->size, rv->dim, rv->L.stride, rv->L.pieces, rv->L.padded, rv->L.G, rv->L.log2G};
+}
+
+void check_rescore_layout_args(uint64_t dim_full, int dtype, int metric) {
+    if (dim_full < 1 || dim_full > kRescoreMaxDim)
+        throw InvalidArg("rescore vectors support 1 <= dim_full <= " + std::to_string(kRescoreMaxDim) + ", got " + std::to_string(dim_full));
+    if (dtype != CPH_RESCORE_FLOAT16 && dtype != CPH_RESCORE_FLOAT32)
+        throw InvalidArg("rescore vectors are stored as CPH_RESCORE_FLOAT16 = 0 or CPH_RESCORE_FLOAT32 = 1");
+    if (metric != CPH_RESCORE_L2 && metric != CPH_RESCORE_IP) throw InvalidArg("the metric of rescore vectors is CPH_RESCORE_L2 = 0 or CPH_RESCORE_IP = 1");
+}
+
+void refuse_bad_rescore_rows(uint64_t bad, unsigned long long first) {
+    if (!bad) return;
+    throw InvalidArg("rescore vectors: row " + std::to_string(first) + " holds a NaN or an Inf, a value that overflows float16, or its squared "
+                     "norm overflows (" + std::to_string(bad) + " such row" + (bad == 1 ? "" : "s") + " in this call): no object was made");
+}
+
+// The object of a rescored call against the handle it runs on.
+void check_rescore_vectors(const cph_index* h, const cph_rescore_vectors* rv) {
+    if (!rv) throw InvalidArg("rescored search needs a rescore vectors object (cph_rescore_vectors_create)");
+    if (rv->device != h->device) throw InvalidArg("rescore vectors belong to another device");
+    if (rv->size != h->size())
+        throw InvalidArg("rescore vectors cover " + std::to_string(rv->size) + " ids, the index holds " + std::to_string(h->size()));
+    if (rv->h != h || rv->epoch != h->index_epoch)
+        throw InvalidArg("rescore vectors were made for another index (a load, build or compact invalidates them)");
+}
+
+void check_rescore_shape(uint64_t k, uint64_t C) {
+    if (k < 1) throw InvalidArg("rescored search needs k >= 1");
+    if (C > kRescoreMaxCandidates)
+        throw InvalidArg("rescored search supports candidates <= " + std::to_string(kRescoreMaxCandidates) + ", got " + std::to_string(C));
+    if (C < k) throw InvalidArg("rescored search needs k <= candidates (got " + std::to_string(k) + " > " + std::to_string(C) + ")");
+}
+
+RescoreArgs rescore_args(const RescoreStore& s, bool ip, const int64_t* r_ids, const float* r_dist, const float* d_fq, uint64_t C, uint64_t k,
+                         const uint32_t* d_rows, const RerankOuts& o) {
+    RescoreArgs a{};
+    a.ids = r_ids;
+    a.dist = r_dist;
+    a.fq = d_fq;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.s = s;
+    a.ip = ip ? 1 : 0;
+    a.rows = d_rows;
+    a.out_ids = o.at<int64_t>(0);
+    a.out_score = o.at<float>(1);
+    a.out_first = o.at<float>(2);
+    return a;
+}
+
+// vectors[r]: the object of replica r (one handle: r = 0).  full_q: [n][dim_full], on the host (host form: staged into
+// the scratch set before the search is enqueued, so that the timed pass is the kernel alone) or on the device.
+struct RescoredSearch {
+    uint64_t k, C;
+    const cph_rescore_vectors* const* vectors;
+    const float* full_q;
+    uint64_t dim_full;
+    bool host_form;
+    static constexpr PassKind kind = kPassRescored;
+    static constexpr bool keyed = false;
+    static constexpr const char* name = "rescored";
+    uint64_t tokens() const { return 1; }
+    void check_shape() const { check_rescore_shape(k, C); }
+    void check_batch(uint64_t n) const { check_batch_size(n); }
+    void check_inputs(uint64_t) const {
+        if (!full_q) throw InvalidArg("null argument");
+    }
+    void check_on(const cph_index* h, uint32_t r) const {
+        if (!vectors) throw InvalidArg("rescored search needs a rescore vectors object (cph_rescore_vectors_create)");
+        check_rescore_vectors(h, vectors[r]);
+        if (dim_full != vectors[r]->dim)
+            throw InvalidArg("full queries have " + std::to_string(dim_full) + " coordinates, the rescore vectors " + std::to_string(vectors[r]->dim));
+    }
+    void stage(GroupScratch& gs, uint64_t n, hipStream_t st) const {
+        const size_t floats = (size_t)n * dim_full;
+        if (gs.d_fq.n < floats) {
+            if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));      // growing: the old buffer must be idle
+            gs.d_fq.alloc(floats);
+        }
+        HIP_CHECK(hipMemcpyAsync(gs.d_fq.p, full_q, floats * 4, hipMemcpyHostToDevice, st));
+    }
+    RerankOuts outs(int64_t* ids, float* score, float* first) const { return {{{ids, 8 * k}, {score, 4 * k}, {first, 4 * k}}, 3}; }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
+        const cph_rescore_vectors* rv = vectors[0];
+        rescore_rows(rescore_args(rescore_store(rv), rv->ip, gs.r_ids.p, gs.r_dist.p, host_form ? gs.d_fq.p : full_q, C, k,
+                                  h->ids_input ? h->d_rows.p : nullptr, o),
+                     rv->f32, (uint32_t)n, st);
+    }
+};
+
+void check_rescore_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, const float* fq, uint64_t k, const RerankOuts& o) {
+    if (!ids || !dist || !fq || !o.all()) throw InvalidArg("null argument");
+    check_rescore_shape(k, C);
+    if (n < 1 || n > 0x7FFFFFFFull) throw InvalidArg("rescore rows: sizes out of range");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_rescore_vectors_create(cph_index* h, const float* rows, uint64_t size, uint64_t dim_full, int space, int dtype, int metric,
+                               cph_rescore_vectors** out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = nullptr;
+        if (!h || (!rows && size != 0)) throw InvalidArg("null argument");
+        if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+        check_rescore_layout_args(dim_full, dtype, metric);
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->finalized) throw InvalidArg("rescore vectors belong to a finalized index: finalize or load it first");
+        if (size != h->size())
+            throw InvalidArg("rescore vectors have " + std::to_string(size) + " rows, the index holds " + std::to_string(h->size()));
+        if (size > 0xFFFFFFFEull) throw InvalidArg("rescore vectors: too many rows");
+        h->use_device();
+        DevBuf<uint32_t> d_inv;
+        if (space == CPH_IDS_INPUT) {
+            const uint64_t nb = h->host.n;
+            if (!h->has_rows) throw InvalidArg("the index has no row map (it was loaded from a v2 file): rows in input order need cph_set_row_map");
+            std::vector<uint32_t> map(h->host.rows);
+            if (map.size() != nb) {                       // a replica without host arrays: its device copy
+                map.resize(nb);
+                if (nb) HIP_CHECK(hipMemcpy(map.data(), h->d_rows.p, nb * 4, hipMemcpyDeviceToHost));
+            }
+            const std::vector<uint32_t> inv = rescore_inverse_rows(map.data(), nb, size);
+            d_inv.alloc(std::max<uint64_t>(size, 1));
+            if (size) HIP_CHECK(hipMemcpy(d_inv.p, inv.data(), size * 4, hipMemcpyHostToDevice));
+        }
+        std::unique_ptr<cph_rescore_vectors> rv(new cph_rescore_vectors());
+        rv->h = h;
+        rv->epoch = h->index_epoch;
+        rv->device = h->device;
+        rv->size = size;
+        rv->dim = (uint32_t)dim_full;
+        rv->f32 = dtype == CPH_RESCORE_FLOAT32;
+        rv->ip = metric == CPH_RESCORE_IP;
+        rv->L = rescore_layout(rv->dim, rv->f32);
+        rv->rows.alloc(std::max<uint64_t>(size, 1) * rv->L.stride);
+        rv->norms.alloc(std::max<uint64_t>(size, 1));
+        const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(size, ((uint64_t)256 << 20) / (dim_full * 4)));
+        DevBuf<float> d_x(chunk * dim_full);
+        DevBuf<unsigned long long> d_cnt(2);
+        const unsigned long long init[2] = {0ull, kRescoreNoRow};
+        unsigned long long cnt[2] = {0ull, kRescoreNoRow};
+        hipStream_t st = own_stream(h);
+        HIP_CHECK(hipMemcpyAsync(d_cnt.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+        const RescoreStore s = rescore_store(rv.get());
+        for (uint64_t base = 0; base < size; base += chunk) {
+            const uint64_t c = std::min(chunk, size - base);
+            HIP_CHECK(hipMemcpyAsync(d_x.p, rows + base * dim_full, c * dim_full * 4, hipMemcpyHostToDevice, st));
+            rescore_rows_in(d_x.p, c, base, space == CPH_IDS_INPUT ? d_inv.p : nullptr, s, rv->f32, rv->rows.p, rv->norms.p, d_cnt.p, st);
+            HIP_CHECK(hipStreamSynchronize(st));          // (the next chunk's upload overwrites d_x from pageable memory)
+        }
+        HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        refuse_bad_rescore_rows(cnt[0], cnt[1]);
+        *out = rv.release();
+    });
+}
+
+int cph_rescore_vectors_destroy(cph_rescore_vectors* rv) {
+    return guarded([&] {
+        if (!rv) return;
+        std::unique_ptr<cph_rescore_vectors> own(rv);
+        if (hipSetDevice(rv->device) == hipSuccess) (void)hipDeviceSynchronize();       // a batch in flight may read the rows
+    });
+}
+
+int cph_rescore_vectors_info(const cph_rescore_vectors* rv, uint64_t* size, uint64_t* dim_full, int* dtype, int* metric, uint64_t* row_bytes,
+                             uint64_t* nbytes) {
+    return guarded([&] {
+        if (!rv || !size || !dim_full || !dtype || !metric || !row_bytes || !nbytes) throw InvalidArg("null argument");
+        *size = rv->size;
+        *dim_full = rv->dim;
+        *dtype = rv->f32 ? CPH_RESCORE_FLOAT32 : CPH_RESCORE_FLOAT16;
+        *metric = rv->ip ? CPH_RESCORE_IP : CPH_RESCORE_L2;
+        *row_bytes = rv->L.stride;
+        *nbytes = rv->size * ((uint64_t)rv->L.stride + 4);
+    });
+}
+
+int cph_rescore_vectors_get(const cph_rescore_vectors* rv, uint64_t first, uint64_t count, void* rows_out, float* norms_out) {
+    return guarded([&] {
+        if (!rv || (count != 0 && (!rows_out || !norms_out))) throw InvalidArg("null argument");
+        if (first > rv->size || count > rv->size - first) throw InvalidArg("rescore vectors: rows out of range");
+        if (count == 0) return;
+        HIP_CHECK(hipSetDevice(rv->device));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(rows_out, rv->rows.p + first * rv->L.stride, count * rv->L.stride, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(norms_out, rv->norms.p + first, count * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_search_rescored(cph_index* h, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                        uint64_t candidates, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                        const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first) {
+    return guarded([&] {
+        const RescoredSearch f{k, candidates, vectors ? &vectors : nullptr, full_queries, dim_full, true};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, first)}, nullptr);
+    });
+}
+
+int cph_search_rescored_device(cph_index* h, const float* d_queries, uint64_t n, const float* d_full_queries, uint64_t dim_full, uint64_t k,
+                               uint64_t candidates, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                               const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, float* d_first, void* stream) {
+    return guarded([&] {
+        const RescoredSearch f{k, candidates, vectors ? &vectors : nullptr, d_full_queries, dim_full, false};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_ids, d_score, d_first)}, nullptr, &stream);
+    });
+}
+
+int cph_multi_search_rescored(cph_multi* m, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                              uint64_t candidates, const cph_rescore_vectors* const* vectors, const cph_filter* const* filters,
+                              uint32_t n_filters, const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first) {
+    return guarded([&] {
+        if (m && vectors)
+            for (size_t r = 0; r < m->reps.size(); ++r)
+                if (!vectors[r]) throw InvalidArg("a rescored multi-device search needs one rescore vectors object per replica");
+        const RescoredSearch f{k, candidates, vectors, full_queries, dim_full, true};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, first)}, nullptr,
+                     [&](cph_index* h, const RerankCall& s, const cph_group_keys*, uint64_t lo) {
+            uint32_t r = 0;
+            while (m->reps[r] != h) ++r;
+            return cph_search_rescored(h, s.q, s.n, full_queries + lo * dim_full, dim_full, k, candidates, vectors[r], s.filters, s.F,
+                                       s.filter_of, s.exact ? 1 : 0, s.out.at<int64_t>(0), s.out.at<float>(1), s.out.at<float>(2));
+        });
+    });
+}
+
+int cph_debug_time_rescored(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassRescored, on != 0); });
+}
+
+int cph_debug_last_rescored_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassRescored, us); });
+}
+
+int cph_rescore_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* full_queries,
+                          const cph_rescore_vectors* vectors, uint64_t k, int64_t* out_ids, float* out_score, float* out_first) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        check_rescore_vectors(h, vectors);
+        const RerankOuts o = RescoredSearch{k, candidates, &vectors, full_queries, vectors->dim, true}.outs(out_ids, out_score, out_first);
+        check_rescore_rows_args(ids, dist, n, candidates, full_queries, k, o);
+        h->use_device();
+        const DevBuf<int64_t> d_ids = uploaded(ids, n * candidates);
+        const DevBuf<float> d_dist = uploaded(dist, n * candidates);
+        const DevBuf<float> d_fq = uploaded(full_queries, n * vectors->dim);
+        PoisonedOuts po(o, n);
+        rescore_rows(rescore_args(rescore_store(vectors), vectors->ip, d_ids.p, d_dist.p, d_fq.p, candidates, k,
+                                  h->ids_input ? h->d_rows.p : nullptr, po.dev),
+                     vectors->f32, (uint32_t)n, nullptr);
+        po.download();
+    });
+}
+
+int cph_host_rescore_rows(const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* full_queries,
+                          uint64_t dim_full, const void* stored, const float* norms, uint64_t n_ids, int dtype, int metric,
+                          const uint32_t* rows, uint64_t k, int64_t* out_ids, float* out_score, float* out_first) {
+    return guarded([&] {
+        if (!stored || !norms) throw InvalidArg("null argument");
+        check_rescore_layout_args(dim_full, dtype, metric);
+        if (n_ids < 1 || n_ids > 0xFFFFFFFEull) throw InvalidArg("rescore rows: sizes out of range");
+        const RescoredSearch f{k, candidates, nullptr, full_queries, dim_full, true};
+        check_rescore_rows_args(ids, dist, n, candidates, full_queries, k, f.outs(out_ids, out_score, out_first));
+        rescore_rows_host(ids, dist, n, (uint32_t)candidates, full_queries, (uint32_t)dim_full, static_cast<const uint8_t*>(stored), norms,
+                          n_ids, dtype == CPH_RESCORE_FLOAT32, metric == CPH_RESCORE_IP, rows, (uint32_t)k, out_ids, out_score, out_first);
+    });
+}
+
+int cph_host_rescore_rows_in(const float* rows_in, uint64_t n, uint64_t dim_full, int dtype, const uint32_t* row_map, uint64_t n_map,
+                             void* stored, float* norms, uint64_t* bad, uint64_t* first_bad) {
+    return guarded([&] {
+        if (!rows_in || !stored || !norms || !bad || !first_bad) throw InvalidArg("null argument");
+        check_rescore_layout_args(dim_full, dtype, CPH_RESCORE_L2);
+        if (n < 1 || n > 0xFFFFFFFEull || n_map > n) throw InvalidArg("rescore rows in: sizes out of range");
+        std::vector<uint32_t> inv;
+        if (row_map) inv = rescore_inverse_rows(row_map, n_map, n);
+        unsigned long long fb = kRescoreNoRow;
+        *bad = rescore_rows_in_host(rows_in, n, (uint32_t)dim_full, dtype == CPH_RESCORE_FLOAT32, row_map ? inv.data() : nullptr,
+                                    static_cast<uint8_t*>(stored), norms, &fb);
+        *first_bad = fb;
     });
 }
 

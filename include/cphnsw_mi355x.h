@@ -490,6 +490,50 @@ int cph_host_maxsim_rescore(const int32_t* cand_keys, const float* cand_lb, cons
                             int32_t* out_found, int32_t* out_certified);
 int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_t* out_keys, uint32_t* out_offsets, uint64_t* out_n_keys);
 
+/* ---- fused search: several query vectors per query, exact weighted-sum top-k (ABI 115) ----- */
+/* queries is [n][vectors][dim]: T = vectors query vectors per query (rewrites of one question, liked and disliked examples, an
+ * image and a text vector) of which the first L = n_vectors[i] are live (1 <= L <= T; NULL: all T), with weights [n][T],
+ * float32, finite, any sign (NULL: every weight 1).  One ranked list of ROWS per query comes back.  csrc/host_fused.h is the
+ * host form of the statement, tests/fused_model.py its numpy form:
+ *   candidates  the n * T vectors run as ONE ordinary search at k = C = candidates -- same routing, filters, exact flag,
+ *               per-query filters (filter_of[i] serves all T vectors of query i), removed and added rows, cosine
+ *               normalisation.  The candidates of query i are the DISTINCT ids that occur in the rows of its live vectors;
+ *               hits(x) = the live vectors whose row holds x.  The distances of that search are used for nothing else;
+ *   score       d_t(x) has the bytes cph_exact_l2 returns for vector t as the search saw it and id x, for EVERY live t;
+ *               s = +0.0f; for t = 0 .. L-1: s = fadd(s, fmul(w[i][t], d_t(x))), each rounded once, no contraction.  A
+ *               candidate whose s is a NaN (overflow under weights of both signs) is dropped;
+ *   answer      the k best by (s, internal id) ascending: ids [n][k] int64 (input rows under CPH_IDS_INPUT), score [n][k],
+ *               hits [n][k] int32; unused slots are -1 / FLT_MAX / 0.  Every slot is written by the pass.
+ * Limits (those of cph_search_maxsim): 1 <= T <= 64, 1 <= C <= 1024, T * C <= 8192, 1 <= k <= min(1024, T * C),
+ * n * T <= 2^31 - 1 (and n * ceil(T * C / 64) <= 2^31 - 1, the scan's grid).  With T = 1 and weight 1 the answer is the first
+ * k distinct ids of cph_search_batch at k = C wherever that search's distance bytes are cph_exact_l2's.
+ * The work, on the call's stream behind the search: exact_pad_kernel over the vectors, fused_union_kernel (one workgroup per
+ * query: sort and collapse the candidate rows), fused_scan_kernel (one wave per (query, 64 candidates): the exact sums) and
+ * fused_select_kernel (one workgroup per query), csrc/device_fused.h.  n_vectors and weights are host memory in both forms;
+ * the _device form only enqueues: they travel through a pinned buffer of the scratch set, and the call waits on the host only
+ * for the copy that set carried the last time.  The inner-product metric is refused; a partitioned index has no such entry
+ * (use the parts).  Every refusal happens before an output is written.  A handle that never calls it allocates nothing. */
+int cph_search_fused(cph_index* h, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                     uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                     int exact, int64_t* ids, float* score, int32_t* hits);
+int cph_search_fused_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors,
+                            const float* weights, uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, int32_t* d_hits, void* stream);
+/* Debug hooks of the measurement script (scripts/fused_sweep.py): the launch of fused_scan_kernel alone between two HIP events
+ * while switched on. */
+int cph_debug_time_fused(cph_index* h, int on);
+int cph_debug_last_fused_us(cph_index* h, double* us);
+/* Test hook: the pad, union, scan and select kernels on given candidate rows (host arrays, cand_ids [n * vectors][candidates],
+ * internal ids, -1 padding) and queries [n][vectors][dim] against the vectors of h; ids go through the row map under
+ * CPH_IDS_INPUT.  The device outputs start as 0xA5 bytes.  cph_host_fused_rows is the host statement (no HIP call) over
+ * queries_padded [n][vectors][D] (the vectors as the search saw them, zero-padded), raw [n_ids][D] zero-padded rows, their norms
+ * and an optional row map. */
+int cph_fused_rows_hook(cph_index* h, const int64_t* cand_ids, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors,
+                        const float* weights, uint64_t candidates, uint64_t k, int64_t* out_ids, float* out_score, int32_t* out_hits);
+int cph_host_fused_rows(const int64_t* cand_ids, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                        uint64_t candidates, const float* queries_padded, const float* raw, const float* norm_sq, uint64_t n_ids, uint64_t D,
+                        const uint32_t* rows, uint64_t k, int64_t* out_ids, float* out_score, int32_t* out_hits);
+
 /* ---- per-query filters ------------------------------------------------------------------ */
 /* One batch, a different allowed set per query: query i is searched under filters[filter_of[i]], or unfiltered where
  * filter_of[i] == -1 (any other value outside [0, n_filters) is CPH_INVALID_ARGUMENT; every filter is checked like the
@@ -847,6 +891,11 @@ int cph_multi_search_maxsim_rescored(cph_multi* m, const float* queries, uint64_
                                      const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
                                      int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found,
                                      int32_t* out_certified);
+/* cph_search_fused, sharded by query (never inside one query's vectors): n_vectors, weights, filter_of and the outputs are
+ * sliced by shard; filters[f * R + r] as in cph_multi_search_grouped.  The bytes are those of one device. */
+int cph_multi_search_fused(cph_multi* m, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                           uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                           int exact, int64_t* ids, float* score, int32_t* hits);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);

@@ -129,6 +129,18 @@ SYMBOLS = {
         C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
         C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_host_key_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_search_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_search_fused_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+        C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_multi_search_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+        C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_debug_time_fused": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_fused_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_fused_rows_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_host_fused_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_filter_create_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "cph_has_row_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "cph_get_row_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -1675,6 +1675,126 @@ class CPIndex:
         time_maxsim_rescore() on the given replica; waits for it."""
         return self._last_pass_us("cph_debug_last_maxsim_rescore_us", replica)
 
+    # -- fused search: several query vectors per query (not in the reference) -------------------------
+    FUSED_MAX_VECTORS = MAXSIM_MAX_TOKENS
+    FUSED_MAX_CANDIDATES = MAXSIM_MAX_CANDIDATES
+    FUSED_MAX_ENTRIES = MAXSIM_MAX_ENTRIES          # vectors * candidates: what the union kernel sorts in LDS
+    FUSED_MAX_K = MAXSIM_MAX_K
+
+    def _fused_args(self, n, T, k, weights, n_vectors, candidates, filter, filter_of):
+        """Validation shared by both fused entry points -> (k, C, weights as float32 [n, T], n_vectors as int32 [n] or None,
+        the filters as of _filters_arg)."""
+        if self._p is not None:
+            raise ValueError("search_fused is not defined on a partitioned index (every part has its own internal ids): "
+                             "use part(i).search_fused")
+        k = int(k)
+        if not 1 <= T <= self.FUSED_MAX_VECTORS:
+            raise ValueError(f"search_fused needs 1 <= vectors <= {self.FUSED_MAX_VECTORS} (queries is [n, vectors, dim]), got {T}")
+        if not 1 <= k <= self.FUSED_MAX_K:
+            raise ValueError(f"search_fused needs 1 <= k <= {self.FUSED_MAX_K}")
+        if candidates is None:                       # a policy, not a measured optimum
+            candidates = min(self.FUSED_MAX_CANDIDATES, self.FUSED_MAX_ENTRIES // T, max(32, 4 * k))
+        candidates = int(candidates)
+        if not 1 <= candidates <= self.FUSED_MAX_CANDIDATES:
+            raise ValueError(f"search_fused needs candidates in [1, {self.FUSED_MAX_CANDIDATES}]")
+        if T * candidates > self.FUSED_MAX_ENTRIES:
+            raise ValueError(f"search_fused needs vectors * candidates <= {self.FUSED_MAX_ENTRIES} (got {T} * {candidates})")
+        if k > T * candidates:
+            raise ValueError(f"search_fused needs k <= vectors * candidates (got {k} > {T} * {candidates})")
+        if n * T > 0x7FFFFFFF:
+            raise ValueError("search_fused needs n * vectors <= 2147483647")
+        if weights is None:
+            w = np.ones((n, T), np.float32)
+        else:
+            w = np.asarray(weights, np.float32)
+            if w.shape not in ((T,), (n, T)):
+                raise ValueError(f"search_fused needs weights of shape ({T},) or ({n}, {T}) (one weight per query vector)")
+            if not np.isfinite(w).all():
+                raise ValueError("search_fused needs finite weights")
+            w = np.ascontiguousarray(np.broadcast_to(w, (n, T)), np.float32)
+        if n_vectors is not None:
+            nv = np.asarray(n_vectors)
+            if nv.ndim != 1 or nv.shape[0] != n or not (nv.size == 0 or np.issubdtype(nv.dtype, np.integer)):
+                raise ValueError(f"search_fused needs n_vectors as a 1D integer array of length {n} (one entry per query)")
+            if nv.size and (nv.min() < 1 or nv.max() > T):
+                raise ValueError(f"search_fused needs n_vectors in [1, {T}]")
+            n_vectors = np.ascontiguousarray(nv, np.int32)
+        return k, candidates, w, n_vectors, self._filters_arg(filter, filter_of, n)
+
+    @staticmethod
+    def _fused_call(n, T, k, C_, w, nv):
+        """-> (the scalars between n and the filters, the output table)."""
+        return ((T, None if (nv is None or n == 0) else nv.ctypes.data, w.ctypes.data if n else None, k, C_),
+                (((n, k), "int64"), ((n, k), "float32"), ((n, k), "int32")))
+
+    def search_fused(self, queries, k=DEFAULT_K, weights=None, n_vectors=None, candidates=None, filter=None, exact=False,
+                     filter_of=None, label=None):
+        """Several query vectors per query, one ranked list of rows: `queries` is float32 [n, T, dim] -- rewrites of one
+        question (query expansion), liked (weight > 0) and disliked (weight < 0) examples, an image and a text vector -- of
+        which the first n_vectors[i] (default: all T) are live; `weights` is [T] (every query) or [n, T], float32, finite,
+        any sign, default all ones.  Returns (ids int64 [n, k], score float32 [n, k], hits int32 [n, k]).
+        The statement, over the T candidate rows search_batch(queries.reshape(n * T, dim), C, filter=..., exact=..., ...)
+        returns for a query in internal ids -- same routing, removed and added rows and refusals; `filter_of[i]` and
+        `label[i]` serve all T vectors of query i; the distances of that search are used for nothing else:
+          the candidates are the DISTINCT ids in the rows of the live vectors; hits(x) = the live vectors whose row holds x;
+          d_t(x) = exact_l2 of vector t (cosine: normalised, as the search saw it) and id x, for EVERY live t;
+          score(x) = s = +0.0; for t < n_vectors: s = s + (w[t] * d_t(x)), float32, product and sum each rounded once;
+          a candidate whose score is NaN (overflow under weights of both signs) is dropped;
+        the k candidates with the smallest (score, internal id) are returned in that order, ids as input rows under
+        result_ids = "input"; unused slots are -1 / FLT_MAX / 0.  No candidate has a missing term: a row that only one
+        vector found is still scored against all of them.  With T = 1 and weight 1 the answer is the first k distinct ids of
+        search_batch at k = C wherever that search's distance bytes are exact_l2's; scaling a query's weights by a power of
+        two changes no id.  The tokens t >= n_vectors[i] are searched with the batch and then ignored entirely.
+        `candidates=C` (1 <= C <= 1024, T * C <= 8192) is the length of every vector's candidate row; candidates=None takes
+        min(1024, 8192 // T, max(32, 4 * k)): a policy, not a measured optimum, in ONE pass.  Limits: 1 <= T <= 64,
+        1 <= k <= min(1024, T * C), n * T <= 2^31 - 1.  A multi-device index shards the QUERIES like search_batch, never the
+        vectors of one query; the bytes are those of one device.  A partitioned index (use part(i).search_fused) and the
+        inner-product metric are refused."""
+        q = _as_f32(queries)
+        if q.ndim != 3 or q.shape[2] != self._dim:
+            raise ValueError("queries must be a (n, vectors, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, q.shape[0], lambda f, fo: self.search_fused(
+                q, k, weights=weights, n_vectors=n_vectors, candidates=candidates, filter=f, exact=exact, filter_of=fo))
+        n, T = q.shape[0], q.shape[1]
+        k, C_, w, nv, filters = self._fused_args(n, T, k, weights, n_vectors, candidates, filter, filter_of)
+        lead, table = self._fused_call(n, T, k, C_, w, nv)
+        return self._rerank_host("fused", q, lead, False, filters, exact, table)
+
+    def search_fused_device(self, queries, k=DEFAULT_K, weights=None, n_vectors=None, candidates=None, out=None, stream=None,
+                            filter=None, exact=False, filter_of=None, label=None):
+        """search_fused on a float32 torch tensor (n, T, dim) on this index' device; returns (ids, score, hits) as torch
+        tensors on the same device.  Like search_batch_device it only enqueues, on `stream` (default: torch's current
+        stream), and waits for no kernel: the tensors are valid in stream order, two batches on two streams overlap.  ONE
+        pass at `candidates`, or (None) at the default of search_fused.  `out`: the three tensors to write (contiguous, on
+        the queries' device).  weights / n_vectors / filter / filter_of / label are host data as in search_batch_device
+        (weights and n_vectors are copied to the device through a pinned buffer by a command on `stream`); a filter closed
+        after the call waits for the batch.  A multi-device index runs the whole batch on one replica on the queries'
+        device."""
+        import torch
+        if queries.dim() != 3 or queries.shape[2] != self._dim or queries.dtype != torch.float32:
+            raise ValueError("queries must be a (n, vectors, dim) array")
+        if label is not None:
+            return self._with_label(label, filter, filter_of, queries.shape[0], lambda f, fo: self.search_fused_device(
+                queries, k, weights=weights, n_vectors=n_vectors, candidates=candidates, out=out, stream=stream, filter=f,
+                exact=exact, filter_of=fo))
+        n, T = queries.shape[0], queries.shape[1]
+        k, C_, w, nv, filters = self._fused_args(n, T, k, weights, n_vectors, candidates, filter, filter_of)
+        lead, table = self._fused_call(n, T, k, C_, w, nv)
+        return tuple(self._rerank_device("fused", queries, lead, False, filters, exact, table, out, stream,
+                                         ("out must be the three tensors (ids, score, hits)",
+                                          "out must be contiguous (n, k) int64 / float32 / int32 tensors on the queries' device")))
+
+    def time_fused(self, on=True):
+        """Debug hook of the measurement script: while on, the scan kernel of every fused search (the exact weighted sums;
+        not the pad, the union or the select) is bracketed by HIP events (last_fused_us)."""
+        self._time_pass("cph_debug_time_fused", on)
+
+    def last_fused_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the scan kernel of the last fused search made under time_fused() on
+        the given replica; waits for it."""
+        return self._last_pass_us("cph_debug_last_fused_us", replica)
+
     # -- two-stage search: rescoring against full-size rows (not in the reference) -------------------
     RESCORE_MAX_CANDIDATES = 1024
     RESCORE_MAX_DIM = 8192

@@ -41,6 +41,7 @@
 #include "device_group.h"
 #include "device_maxsim.h"
 #include "device_maxsim_rescore.h"
+#include "device_fused.h"
 #include "device_rescore.h"
 #include "device_normalize.h"
 #include "device_ip.h"
@@ -193,7 +194,9 @@ constexpr size_t kRangeScratchKept = 2;
 // candidate slot, and the call's host tables -- filter_of and the bitmap pointers -- which travel like n_tokens: written into
 // pin_rs, copied to d_rs by one command on the call's stream, ev_rs behind that copy.  A handle that never rescored
 // allocates none of them.  The rescored search (device_rescore.h) adds d_fq, the staged full queries of its host form; a
-// handle that never calls it allocates nothing for it.
+// handle that never calls it allocates nothing for it.  Fused search (device_fused.h) adds the union of every query's candidate
+// rows (fu_ids, fu_hits, fu_count) and the exact weighted sums (fu_score); it pads its vectors into rs_q / rs_qpad / rs_qnorm and
+// sends n_vectors and the weights through pin_rs / d_rs / ev_rs.
 constexpr int kMaxRerankOuts = 6;
 struct GroupScratch {
     DevBuf<int64_t> r_ids;
@@ -216,6 +219,8 @@ struct GroupScratch {
     DevBuf<uint8_t> d_rs;
     hipEvent_t ev_rs = nullptr;
     bool rs_used = false;
+    DevBuf<uint32_t> fu_ids, fu_hits, fu_count;
+    DevBuf<float> fu_score;
 };
 
 // The inverted key column of one int32 column (host_maxsim_rescore.h: key_rows_host), resident: what the rescored maxsim
@@ -231,8 +236,9 @@ struct KeyRows {
 constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the copy-free path of cph_search / cph_search_batch
 // The passes a handle can time (PassTimer).  kPassMaxsimRescore is the scan kernel of the rescored maxsim search alone, bracketed
 // inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
-// rescoring kernel of cph_search_rescored* (device_rescore.h).
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassUntimed, kPassKinds };
+// rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
+// same way.
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassUntimed, kPassKinds };
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -574,6 +580,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed label pass has run on this handle (cph_debug_time_label_filters)",
     "no timed rescored maxsim search has run on this handle (cph_debug_time_maxsim_rescore)",
     "no timed rescored search has run on this handle (cph_debug_time_rescored)",
+    "no timed fused search has run on this handle (cph_debug_time_fused)",
     "this pass is not timed",
 };
 
@@ -1873,7 +1880,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 114; }
+int cph_version(void) { return 115; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -5749,7 +5756,7 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count) {
 // One entry path for the three: an ordinary search at k = C into scratch rows the handle owns, then one kernel over those
 // rows on the same stream.  The rows hold INTERNAL ids whatever the handle returns (the keys are looked up by internal
 // id); the row map is applied where an id is written.  Nothing here waits for the device in the _device form.  A
-// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch, MaxsimRescoredSearch, RescoredSearch): its
+// re-ranker is a small struct (GroupedSearch, DiverseSearch, MaxsimSearch, MaxsimRescoredSearch, FusedSearch, RescoredSearch): its
 // scalars, its checks (check_on: those that need the handle a call runs on), its output table, what the host form stages
 // besides the queries (stage) and its pass; the entries, the scratch, the replica fan-out and the hooks below are written
 // once over that.  (MaxsimRescoredSearch's pass is four launches, and the first one on a key column waits for the device:
@@ -6276,6 +6283,142 @@ struct MaxsimRescoredSearch {
     }
 };
 
+// ---- fused search: several vectors per query, exact weighted-sum top-k (device_fused.h, host_fused.h) ----
+void check_fused_shape(uint64_t T, uint64_t C, uint64_t k) {
+    if (T < 1 || T > kFusedMaxVectors)
+        throw InvalidArg("fused search supports 1 <= vectors <= " + std::to_string(kFusedMaxVectors) + ", got " + std::to_string(T));
+    if (C < 1 || C > kFusedMaxCandidates)
+        throw InvalidArg("fused search supports 1 <= candidates <= " + std::to_string(kFusedMaxCandidates) + ", got " + std::to_string(C));
+    if (T * C > kFusedMaxEntries)
+        throw InvalidArg("fused search needs vectors * candidates <= " + std::to_string(kFusedMaxEntries) + " (got " + std::to_string(T) +
+                         " * " + std::to_string(C) + ")");
+    if (k < 1 || k > kFusedMaxK || k > T * C)
+        throw InvalidArg("fused search supports 1 <= k <= min(" + std::to_string(kFusedMaxK) + ", vectors * candidates), got " +
+                         std::to_string(k));
+}
+
+// n * vectors is the batch of the underlying search; the scan's grid is one workgroup per block of union slots.
+void check_fused_batch(uint64_t n, uint64_t T, uint64_t C) {
+    if (n > 0x7FFFFFFFull || n * T > 0x7FFFFFFFull)
+        throw InvalidArg("batch too large: fused search needs n * vectors <= 2147483647 (got " + std::to_string(n) + " * " + std::to_string(T) + ")");
+    if (n * ((T * C + kFusedItemSlots - 1) / kFusedItemSlots) > 0x7FFFFFFFull)
+        throw InvalidArg("batch too large: fused search needs n * ceil(vectors * candidates / 64) <= 2147483647");
+}
+
+void check_fused_inputs(const int32_t* n_vectors, const float* weights, uint64_t n, uint64_t T) {
+    for (uint64_t i = 0; n_vectors && i < n; ++i)
+        if (n_vectors[i] < 1 || (uint64_t)n_vectors[i] > T)
+            throw InvalidArg("n_vectors[" + std::to_string(i) + "] = " + std::to_string(n_vectors[i]) + " is outside [1, " + std::to_string(T) + "]");
+    for (uint64_t i = 0; weights && i < n * T; ++i)
+        if (!std::isfinite(weights[i]))
+            throw InvalidArg("weights[" + std::to_string(i / T) + "][" + std::to_string(i % T) + "] is not finite");
+}
+
+// The fused buffers of a set for n queries; one wait for the set's previous batch if one of them has to grow.
+void reserve_fused_scratch(GroupScratch& gs, uint64_t n, uint64_t T, uint64_t C, uint64_t dim, uint64_t D, bool metric_rows) {
+    const size_t slots = n * T * C, rows = n * T + kExactQT;
+    const bool grow = gs.fu_ids.n < slots || gs.fu_count.n < n || gs.rs_qpad.n < rows * D || gs.rs_qnorm.n < rows ||
+                      gs.rs_stats.n < kStatWords || (metric_rows && gs.rs_q.n < n * T * dim);
+    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+    gs.fu_ids.alloc(slots);
+    gs.fu_hits.alloc(slots);
+    gs.fu_score.alloc(slots);
+    gs.fu_count.alloc(n);
+    gs.rs_qpad.alloc(rows * D);
+    gs.rs_qnorm.alloc(rows);
+    gs.rs_stats.alloc(kStatWords);
+    if (metric_rows) gs.rs_q.alloc(n * T * dim);
+}
+
+// n_vectors and the weights are host data and travel the way n_tokens does: written into the set's pinned buffer
+// ([n * T floats | n x int32]; null weights: ones) and copied by one command on `st`; the one host wait is for the copy this set
+// carried the last time (ev_rs).  Called from the pass: `st` already waits for the set's previous batch.
+struct FusedHostData {
+    const float* d_weights = nullptr;
+    const int32_t* d_n_vectors = nullptr;
+};
+
+FusedHostData upload_fused_host_data(GroupScratch& gs, const int32_t* n_vectors, const float* weights, uint64_t n, uint64_t T, hipStream_t st) {
+    const size_t wb = n * T * 4, need = wb + (n_vectors ? n * 4 : 0);
+    if (gs.rs_used) HIP_CHECK(hipEventSynchronize(gs.ev_rs));
+    if (gs.pin_rs_bytes < need || gs.d_rs.n < need) {
+        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
+        if (gs.pin_rs) HIP_CHECK(hipHostFree(gs.pin_rs));
+        gs.pin_rs = nullptr;
+        gs.pin_rs_bytes = 0;
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_rs), need * 2, hipHostMallocDefault));
+        gs.pin_rs_bytes = need * 2;
+        gs.d_rs.alloc(need * 2);
+    }
+    if (!gs.ev_rs) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_rs, hipEventDisableTiming));
+    if (weights) std::memcpy(gs.pin_rs, weights, wb);
+    else std::fill_n(reinterpret_cast<float*>(gs.pin_rs), n * T, 1.0f);
+    if (n_vectors) std::memcpy(gs.pin_rs + wb, n_vectors, n * 4);
+    HIP_CHECK(hipMemcpyAsync(gs.d_rs.p, gs.pin_rs, need, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(gs.ev_rs, st));
+    gs.rs_used = true;
+    FusedHostData out;
+    out.d_weights = reinterpret_cast<const float*>(gs.d_rs.p);
+    if (n_vectors) out.d_n_vectors = reinterpret_cast<const int32_t*>(gs.d_rs.p + wb);
+    return out;
+}
+
+FusedArgs fused_args(const cph_index* h, const int64_t* cand, const float* qpad, const float* qnorm, const int32_t* d_n_vectors,
+                     const float* d_weights, uint64_t T, uint64_t C, uint64_t k, uint32_t* u_ids, uint32_t* u_hits, uint32_t* u_count,
+                     float* u_score, const RerankOuts& o) {
+    FusedArgs a{};
+    a.s.raw = h->d_raw.p;
+    a.s.norm_sq = h->d_norm.p;
+    a.s.qpad = qpad;
+    a.s.qnorm = qnorm;
+    a.s.D = h->L.D;
+    a.cand = cand;
+    a.n_vectors = d_n_vectors;
+    a.weights = d_weights;
+    a.T = (uint32_t)T;
+    a.C = (uint32_t)C;
+    a.k = (uint32_t)k;
+    a.n_ids = (uint32_t)h->size();
+    a.u_ids = u_ids;
+    a.u_hits = u_hits;
+    a.u_count = u_count;
+    a.u_score = u_score;
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
+    a.out_ids = o.at<int64_t>(0);
+    a.out_score = o.at<float>(1);
+    a.out_hits = o.at<int32_t>(2);
+    return a;
+}
+
+// The queries are [n][T][dim]: the n * T vectors are one ordinary batch at k = C; the pass forms every query's union, scores it
+// exactly against all live vectors and selects.  n_vectors and weights are on the host (null: all T live; every weight 1).
+struct FusedSearch {
+    uint64_t T;
+    const int32_t* n_vectors;
+    const float* weights;
+    uint64_t k, C;
+    static constexpr PassKind kind = kPassUntimed;       // (the scan kernel alone is timed, inside the pass)
+    static constexpr bool keyed = false;
+    static constexpr const char* name = "fused";
+    uint64_t tokens() const { return T; }
+    void check_shape() const { check_fused_shape(T, C, k); }
+    void check_batch(uint64_t n) const { check_fused_batch(n, T, C); }
+    void check_inputs(uint64_t n) const { check_fused_inputs(n_vectors, weights, n, T); }
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    RerankOuts outs(int64_t* ids, float* score, int32_t* hits) const { return {{{ids, 8 * k}, {score, 4 * k}, {hits, 4 * k}}, 3}; }
+    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float* d_queries, const RerankOuts& o, hipStream_t st) const {
+        reserve_fused_scratch(gs, n, T, C, h->dim, h->L.D, h->metric == CPH_METRIC_COSINE);
+        const FusedHostData hd = upload_fused_host_data(gs, n_vectors, weights, n, T, st);
+        pad_rescore_tokens(h, d_queries, n * T, gs.rs_q.p, gs.rs_qpad.p, gs.rs_qnorm.p, gs.rs_stats.p, st);
+        const FusedArgs a = fused_args(h, gs.r_ids.p, gs.rs_qpad.p, gs.rs_qnorm.p, hd.d_n_vectors, hd.d_weights, T, C, k, gs.fu_ids.p,
+                                       gs.fu_hits.p, gs.fu_count.p, gs.fu_score.p, o);
+        fused_union(a, (uint32_t)n, h->device, st);
+        timed_pass(h->pass_timer[kPassFused], st, [&] { fused_scan(a, (uint32_t)n, st); });
+        fused_select(a, (uint32_t)n, h->device, st);
+    }
+};
+
 // ---- the entries, once ----
 // What every form checks under the mutex before it touches the device; false: n == 0, nothing to do.
 template <class Rerank>
@@ -6795,6 +6938,101 @@ int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_
         if (!out_offsets || !out_n_keys || (n != 0 && (!keys || !out_ids || !out_keys))) throw InvalidArg("null argument");
         if (n > 0xFFFFFFFEull) throw InvalidArg("key rows: too many ids");
         *out_n_keys = key_rows_host(keys, n, out_ids, out_keys, out_offsets);
+    });
+}
+
+// ---- fused search: several query vectors per query, exact weighted-sum top-k (host_fused.h) ----
+int cph_search_fused(cph_index* h, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                     uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                     int exact, int64_t* ids, float* score, int32_t* hits) {
+    return guarded([&] {
+        const FusedSearch f{vectors, n_vectors, weights, k, candidates};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, hits)}, nullptr);
+    });
+}
+
+int cph_search_fused_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors,
+                            const float* weights, uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, int32_t* d_hits, void* stream) {
+    return guarded([&] {
+        const FusedSearch f{vectors, n_vectors, weights, k, candidates};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_ids, d_score, d_hits)}, nullptr, &stream);
+    });
+}
+
+int cph_multi_search_fused(cph_multi* m, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                           uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
+                           int exact, int64_t* ids, float* score, int32_t* hits) {
+    return guarded([&] {
+        const FusedSearch f{vectors, n_vectors, weights, k, candidates};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, hits)}, nullptr,
+                     [&](cph_index* h, const RerankCall& s, const cph_group_keys*, uint64_t lo) {
+            return cph_search_fused(h, s.q, s.n, vectors, n_vectors ? n_vectors + lo : nullptr, weights ? weights + lo * vectors : nullptr, k,
+                                    candidates, s.filters, s.F, s.filter_of, s.exact ? 1 : 0, s.out.at<int64_t>(0), s.out.at<float>(1),
+                                    s.out.at<int32_t>(2));
+        });
+    });
+}
+
+int cph_debug_time_fused(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassFused, on != 0); });
+}
+
+int cph_debug_last_fused_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassFused, us); });
+}
+
+static void check_fused_rows_args(const int64_t* cand_ids, const float* queries, uint64_t n, uint64_t T, const int32_t* n_vectors,
+                                  const float* weights, uint64_t C, uint64_t k, const RerankOuts& o) {
+    if (!cand_ids || !queries || !o.all()) throw InvalidArg("null argument");
+    check_fused_shape(T, C, k);
+    if (n < 1) throw InvalidArg("fused rows: sizes out of range");
+    check_fused_batch(n, T, C);
+    check_fused_inputs(n_vectors, weights, n, T);
+}
+
+int cph_fused_rows_hook(cph_index* h, const int64_t* cand_ids, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors,
+                        const float* weights, uint64_t candidates, uint64_t k, int64_t* out_ids, float* out_score, int32_t* out_hits) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        refuse_ip(h, "fused search");
+        require_finalized(h);
+        const uint64_t T = vectors, C = candidates, rows = n * T;
+        const FusedSearch f{T, n_vectors, weights, k, C};
+        const RerankOuts o = f.outs(out_ids, out_score, out_hits);
+        check_fused_rows_args(cand_ids, queries, n, T, n_vectors, weights, C, k, o);
+        h->use_device();
+        std::vector<float> ones;
+        if (!weights) ones.assign(rows, 1.0f);
+        const DevBuf<int64_t> d_cand = uploaded(cand_ids, rows * C);
+        const DevBuf<float> d_q = uploaded(queries, rows * h->dim), d_w = uploaded(weights ? weights : ones.data(), rows);
+        const DevBuf<int32_t> d_nv = uploaded(n_vectors, n);
+        DevBuf<float> d_metric(rows * h->dim), d_qpad((rows + kExactQT) * h->L.D), d_qnorm(rows + kExactQT), d_score(rows * C);
+        DevBuf<uint32_t> d_uids(rows * C), d_uhits(rows * C), d_ucount(n);
+        DevBuf<unsigned long long> d_stats(kStatWords);
+        PoisonedOuts po(o, n);
+        pad_rescore_tokens(h, d_q.p, rows, d_metric.p, d_qpad.p, d_qnorm.p, d_stats.p, nullptr);
+        const FusedArgs a = fused_args(h, d_cand.p, d_qpad.p, d_qnorm.p, n_vectors ? d_nv.p : nullptr, d_w.p, T, C, k, d_uids.p, d_uhits.p,
+                                       d_ucount.p, d_score.p, po.dev);
+        fused_union(a, (uint32_t)n, h->device, nullptr);
+        fused_scan(a, (uint32_t)n, nullptr);
+        fused_select(a, (uint32_t)n, h->device, nullptr);
+        po.download();
+    });
+}
+
+int cph_host_fused_rows(const int64_t* cand_ids, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
+                        uint64_t candidates, const float* queries_padded, const float* raw, const float* norm_sq, uint64_t n_ids, uint64_t D,
+                        const uint32_t* rows, uint64_t k, int64_t* out_ids, float* out_score, int32_t* out_hits) {
+    return guarded([&] {
+        if (!raw || !norm_sq) throw InvalidArg("null argument");
+        if (D < 8 || D > 0xFFFFFFFFull || (D & 7)) throw InvalidArg("fused rows: D must be a multiple of 8");
+        if (n_ids < 1 || n_ids > 0xFFFFFFFFull) throw InvalidArg("fused rows: sizes out of range");
+        const FusedSearch f{vectors, n_vectors, weights, k, candidates};
+        check_fused_rows_args(cand_ids, queries_padded, n, vectors, n_vectors, weights, candidates, k, f.outs(out_ids, out_score, out_hits));
+        fused_rows_host(cand_ids, n, (uint32_t)vectors, n_vectors, weights, (uint32_t)candidates, queries_padded, raw, norm_sq, n_ids,
+                        (uint32_t)D, rows, (uint32_t)k, out_ids, out_score, out_hits);
     });
 }
 

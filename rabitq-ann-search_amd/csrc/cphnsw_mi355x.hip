@@ -157,15 +157,10 @@ struct BatchSet {
     DevBuf<uint32_t> x_counts;
     bool stats_in_hbm = false; // the last batch's statistics were not copied to pin_stats yet
     // batches with per-query filters (enqueue_filters): the call's tables -- scan descriptors, permutation, work lists,
-    // filter_of, bitmap pointers -- are written into pin_tab and copied to d_tab by one command on the batch's stream;
-    // ev_tab: that copy has read pin_tab (the next such batch on this set waits for it before it writes).  d_redo2: the
-    // re-run list of the batch's second pair of graph launches
-    uint8_t* pin_tab = nullptr;
-    size_t pin_tab_bytes = 0;
-    DevBuf<uint8_t> d_tab;
+    // filter_of, bitmap pointers -- travel as one staged table on the batch's stream.  d_redo2: the re-run list of the
+    // batch's second pair of graph launches
+    StagedTable tab;
     DevBuf<uint32_t> d_redo2;
-    hipEvent_t ev_tab = nullptr;
-    bool tab_used = false;
     // cosine metric (metric_queries): the batch's normalised queries; an L2 handle never allocates it
     // (inner product: the augmented queries [nq][dim + 1], and m_c [nq] = |q|^2 + M2, what the epilogue subtracts)
     DevBuf<float> m_queries, m_c;
@@ -182,45 +177,45 @@ struct RangeScratch {
 };
 constexpr size_t kRangeScratchKept = 2;
 
-// The device buffers of one search that re-ranks candidate rows (cph_search_grouped*, cph_search_diverse*,
-// cph_search_maxsim*): the [n][C] candidate rows of the underlying search and, for the host form, the queries and one
-// byte buffer per slot of the call's output table (RerankOuts), sized by reserve_group_scratch alone.  A handle owns
-// kMaxBatchSets of them, used in turn and only ever grown; `ev` follows the last kernel that touched the rows, the next
-// call on these buffers makes its stream wait for it.  maxsim with n_tokens: the lengths are written into pin_tok and
-// copied to d_tok by one command on the call's stream; ev_tok: that copy has read pin_tok (the next such call on this
-// set waits for it before it writes).  A handle that never calls maxsim allocates none of the three.
-// The rescored maxsim search (device_maxsim_rescore.h) adds its own: the candidates of the lower-bound pass (c_*), the token
-// rows as the search saw them (rs_q: cosine only), padded (rs_qpad, rs_qnorm), the exact scores and argmin ids of every
-// candidate slot, and the call's host tables -- filter_of and the bitmap pointers -- which travel like n_tokens: written into
-// pin_rs, copied to d_rs by one command on the call's stream, ev_rs behind that copy.  A handle that never rescored
-// allocates none of them.  The rescored search (device_rescore.h) adds d_fq, the staged full queries of its host form; a
-// handle that never calls it allocates nothing for it.  Fused search (device_fused.h) adds the union of every query's candidate
-// rows (fu_ids, fu_hits, fu_count) and the exact weighted sums (fu_score); it pads its vectors into rs_q / rs_qpad / rs_qnorm and
-// sends n_vectors and the weights through pin_rs / d_rs / ev_rs.
+// The device buffers of one search that re-ranks candidate rows (the re-rankers below), grouped by what owns them.  A handle
+// owns kMaxBatchSets of these sets, used in turn and only ever grown (Reserve); a handle that never calls a feature
+// allocates nothing for it.
 constexpr int kMaxRerankOuts = 6;
-struct GroupScratch {
-    DevBuf<int64_t> r_ids;
-    DevBuf<float> r_dist, d_q;
-    DevBuf<float> d_fq;
-    DevBuf<uint8_t> out[kMaxRerankOuts];
-    DevBuf<int32_t> d_tok;
-    hipEvent_t ev = nullptr;
-    bool used = false;
-    int32_t* pin_tok = nullptr;
-    size_t pin_tok_n = 0;
-    hipEvent_t ev_tok = nullptr;
-    bool tok_used = false;
-    DevBuf<int32_t> c_keys, c_hits, c_found;
-    DevBuf<float> c_lb, rs_q, rs_qpad, rs_qnorm, rs_score;
-    DevBuf<uint32_t> rs_rows;
-    DevBuf<unsigned long long> rs_stats;
-    uint8_t* pin_rs = nullptr;
-    size_t pin_rs_bytes = 0;
-    DevBuf<uint8_t> d_rs;
-    hipEvent_t ev_rs = nullptr;
-    bool rs_used = false;
-    DevBuf<uint32_t> fu_ids, fu_hits, fu_count;
-    DevBuf<float> fu_score;
+struct RerankScratch {
+    // the [n][C] candidate rows of the underlying search; `ev` follows the last kernel that touched the set, the next call
+    // on it makes its stream wait for that
+    struct Rows {
+        DevBuf<int64_t> ids;
+        DevBuf<float> dist;
+        hipEvent_t ev = nullptr;
+        bool used = false;
+        ~Rows() { if (ev) (void)hipEventDestroy(ev); }
+    } rows;
+    // host form: the staged queries, the staged full queries of the rescored search, one byte buffer per output slot (RerankOuts)
+    struct HostForm {
+        DevBuf<float> q, fq;
+        DevBuf<uint8_t> out[kMaxRerankOuts];
+    } host;
+    // the call's host tables (n_tokens; filter_of and bitmap pointers; weights and n_vectors): one copy command per call
+    StagedTable tab;
+    // rescored maxsim and fused: the token rows as the search saw them (q: cosine only), padded, with their norms
+    struct Padded {
+        DevBuf<float> q, qpad, qnorm;
+        DevBuf<unsigned long long> stats;
+    } pad;
+    // rescored maxsim: the candidates of the lower-bound pass, the exact scores and argmin ids of every candidate slot
+    struct Cand {
+        DevBuf<int32_t> keys, hits, found;
+        DevBuf<float> lb, score;
+        DevBuf<uint32_t> rows;
+    } cand;
+    // fused: the union of every query's candidate rows and its exact weighted sums
+    struct Union {
+        DevBuf<uint32_t> ids, hits, count;
+        DevBuf<float> score;
+        void reserve(Reserve& r, size_t n, size_t slots) { r(ids, slots), r(hits, slots), r(score, slots), r(count, n); }
+    } un;
+    Reserve reserve() const { return Reserve{rows.ev, rows.used}; }      // growing: the set's previous batch must be done
 };
 
 // The inverted key column of one int32 column (host_maxsim_rescore.h: key_rows_host), resident: what the rescored maxsim
@@ -364,8 +359,8 @@ struct cph_index {
     bool last_range = false;           // ... unless an exact range search came later: it uses no set, its one counter is
     uint64_t range_exact = 0;          //     kept here (cph_last_search_stats)
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
-    GroupScratch group_scratch[kMaxBatchSets];                  // buffers of grouped searches, in rotation (under mu)
-    int last_group = kMaxBatchSets - 1;
+    RerankScratch rerank_scratch[kMaxBatchSets];                // buffers of the re-rankers, in rotation (under mu)
+    int last_rerank = kMaxBatchSets - 1;
     // debug hooks cph_debug_time_grouped / _diverse / _maxsim / _label_filters: only while its timer is on is that pass
     // (over the candidate rows; over the label column) bracketed by the two events
     struct PassTimer {
@@ -568,8 +563,8 @@ void release_scratch(BatchSet& s) {
 void quiesce(cph_index* h) {
     for (auto& s : h->sets)
         if (s.used && s.ev_done) HIP_CHECK(hipEventSynchronize(s.ev_done));
-    for (auto& gs : h->group_scratch)            // (the group pass runs behind its batch's ev_done)
-        if (gs.used && gs.ev) HIP_CHECK(hipEventSynchronize(gs.ev));
+    for (auto& gs : h->rerank_scratch)           // (the re-rank pass runs behind its batch's ev_done)
+        if (gs.rows.used) HIP_CHECK(hipEventSynchronize(gs.rows.ev));
 }
 
 // ---- pass timers (cph_debug_time_*, cph_debug_last_*_us) --------------------------------------------------------------------
@@ -1601,7 +1596,7 @@ bool filters_batch_has_work(cph_index* h, const cph_filter* const* filters, uint
 // queries of ALL filters share one pad launch and one scan + merge launch pair per scratch budget (device_exact.h: the
 // grouped scan), graph-searched queries run as two launch pairs -- the filtered ones through the filter-table
 // instantiation, the unfiltered ones (-1) through the kernels of the plain call, so their rows and counters are those.
-// One host wait: the tables are written into the set's pinned buffer, so the call first waits (ev_tab) until the copy of
+// One host wait: the tables are written into the set's pinned buffer, so the call first waits (StagedTable) until the copy of
 // the tables this set carried the last time -- n_sets batches back -- has read it; nothing waits for a kernel.  As soon as
 // one query takes the graph route, stage_queries encodes and descends ALL nq queries (the graph kernels index the staged
 // queries by row), also the scanned and padded ones.
@@ -1632,39 +1627,26 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
     const uint32_t nq_pad = nqs ? (nqs + kExactQT - 1) / kExactQT * kExactQT + kExactQT : 0;   // (a group's last tile reads up to 7 rows behind it)
     // the call's tables, one blob
     size_t need = 0;
-    auto take = [&](size_t bytes) { const size_t o = need; need = (need + bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_items = take(pl.items.size() * sizeof(ExactItem)), o_desc = take((size_t)nqs * 16), o_scanq = take((size_t)nqs * 4),
-                 o_pad = take((size_t)n_pad * 4), o_gf = take((size_t)n_gf * 4), o_gp = take((size_t)n_gp * 4),
-                 o_fof = take(n_gf ? (size_t)nq * 4 : 0), o_tab = take(n_gf ? (size_t)F * 8 : 0);
+    const size_t o_items = table_take(need, pl.items.size() * sizeof(ExactItem)), o_desc = table_take(need, (size_t)nqs * 16),
+                 o_scanq = table_take(need, (size_t)nqs * 4), o_pad = table_take(need, (size_t)n_pad * 4),
+                 o_gf = table_take(need, (size_t)n_gf * 4), o_gp = table_take(need, (size_t)n_gp * 4),
+                 o_fof = table_take(need, n_gf ? (size_t)nq * 4 : 0), o_tab = table_take(need, n_gf ? (size_t)F * 8 : 0);
     need = std::max<size_t>(need, 16);
-    if (s.tab_used) HIP_CHECK(hipEventSynchronize(s.ev_tab));     // the copy of the set's previous tables has read pin_tab
+    Reserve r{s.ev_done, s.used};                                 // growing: the old buffers must be idle (one wait)
+    uint8_t* const tb = s.tab.begin(need, r);
     const size_t pools = (size_t)pl.max_pools;
-    if (s.pin_tab_bytes < need || s.d_tab.n < need || s.x_qpad.n < (size_t)nq_pad * D || s.x_pools.n < pools * pl.C ||
-        s.x_counts.n < pools || s.d_status.n < nq || s.d_redo2.n < nq) {
-        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
-        if (s.pin_tab_bytes < need) {
-            if (s.pin_tab) HIP_CHECK(hipHostFree(s.pin_tab));
-            s.pin_tab = nullptr;
-            s.pin_tab_bytes = 0;
-            HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.pin_tab), need * 2, hipHostMallocDefault));
-            s.pin_tab_bytes = need * 2;
-        }
-        s.d_tab.alloc(need * 2);
-        s.x_qpad.alloc((size_t)nq_pad * D);
-        s.x_qnorm.alloc(nq_pad);
-        s.x_pools.alloc(pools * pl.C);
-        s.x_counts.alloc(pools);
-        s.d_count.alloc(nq);
-        s.d_status.alloc(nq);
-        s.d_redo.alloc(nq);
-        s.d_redo2.alloc(nq);
-    }
-    if (!s.ev_tab) HIP_CHECK(hipEventCreateWithFlags(&s.ev_tab, hipEventDisableTiming));
+    r(s.x_qpad, (size_t)nq_pad * D);
+    r(s.x_qnorm, nq_pad);
+    r(s.x_pools, pools * pl.C);
+    r(s.x_counts, pools);
+    r(s.d_count, nq);
+    r(s.d_status, nq);
+    r(s.d_redo, nq);
+    r(s.d_redo2, nq);
     // every scanned filter's id list: made once (filter_id_list), the stream waits for it
     std::vector<const uint32_t*> seg_ids(seg_m.size(), nullptr);
     for (size_t i = 0; i < seg_m.size(); ++i)
         if (seg_group[i] < F) seg_ids[i] = filter_id_list(filters[seg_group[i]], st);
-    uint8_t* const tb = s.pin_tab;
     ExactItem* items = reinterpret_cast<ExactItem*>(tb + o_items);
     uint4* desc = reinterpret_cast<uint4*>(tb + o_desc);
     uint32_t* scanq = reinterpret_cast<uint32_t*>(tb + o_scanq);
@@ -1696,10 +1678,7 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
         const uint32_t** tab = reinterpret_cast<const uint32_t**>(tb + o_tab);
         for (uint32_t f = 0; f < F; ++f) tab[f] = filters[f]->words.p;
     }
-    HIP_CHECK(hipMemcpyAsync(s.d_tab.p, tb, need, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(s.ev_tab, st));
-    s.tab_used = true;
-    const uint8_t* const dt = s.d_tab.p;
+    const uint8_t* const dt = s.tab.send(need, st);
 
     s.d_stats.alloc(kStatWords);
     HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
@@ -1938,22 +1917,14 @@ static void destroy_index(cph_index* h) {
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
         if (s.pin_stats) (void)hipHostFree(s.pin_stats);
         if (s.pin_io) (void)hipHostFree(s.pin_io);
-        if (s.pin_tab) (void)hipHostFree(s.pin_tab);
-        if (s.ev_tab) (void)hipEventDestroy(s.ev_tab);
     }
 #ifdef CPH_SEARCH_TRACE
     if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
                          (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
     for (auto& x : g_tr) x = 0;
 #endif
-    for (auto& gs : h->group_scratch) {
-        if (gs.used && gs.ev) (void)hipEventSynchronize(gs.ev);
-        if (gs.ev) (void)hipEventDestroy(gs.ev);
-        if (gs.ev_tok) (void)hipEventDestroy(gs.ev_tok);
-        if (gs.pin_tok) (void)hipHostFree(gs.pin_tok);
-        if (gs.ev_rs) (void)hipEventDestroy(gs.ev_rs);
-        if (gs.pin_rs) (void)hipHostFree(gs.pin_rs);
-    }
+    for (auto& gs : h->rerank_scratch)
+        if (gs.rows.used) (void)hipEventSynchronize(gs.rows.ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     for (auto& pt : h->pass_timer) {
         if (pt.ev0) (void)hipEventDestroy(pt.ev0);
@@ -5833,48 +5804,41 @@ const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) 
 // rows, bracketed by the timer's events while it is on; everything on `st`.  The caller holds the handle mutex and has set
 // the device.
 template <class Pass>
-void search_rows_then_pass(cph_index* h, GroupScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
+void search_rows_then_pass(cph_index* h, RerankScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
                            uint32_t F, const int32_t* filter_of, bool exact, cph_index::PassTimer& timer, hipStream_t st, Pass pass) {
-    if (!gs.ev) HIP_CHECK(hipEventCreateWithFlags(&gs.ev, hipEventDisableTiming));
-    if (gs.r_ids.n < n * C) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));      // growing: the old rows must be idle
-        gs.r_ids.alloc(n * C);
-        gs.r_dist.alloc(n * C);
-    }
-    if (gs.used) HIP_CHECK(hipStreamWaitEvent(st, gs.ev, 0));    // the rows' previous batch, maybe on another stream
+    RerankScratch::Rows& rows = gs.rows;
+    if (!rows.ev) HIP_CHECK(hipEventCreateWithFlags(&rows.ev, hipEventDisableTiming));
+    Reserve r = gs.reserve();
+    r(rows.ids, n * C);
+    r(rows.dist, n * C);
+    if (rows.used) HIP_CHECK(hipStreamWaitEvent(st, rows.ev, 0));    // the rows' previous batch, maybe on another stream
     try {
         {
             InternalIdsScope internal(h);
-            search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, gs.r_ids.p, gs.r_dist.p, true, st));
+            search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, rows.ids.p, rows.dist.p, true, st));
         }
         timed_pass(timer, st, pass);
     } catch (...) {
-        (void)hipEventRecord(gs.ev, st);                          // whatever was enqueued may still write the rows
-        gs.used = true;
+        (void)hipEventRecord(rows.ev, st);                        // whatever was enqueued may still write the rows
+        rows.used = true;
         throw;
     }
-    HIP_CHECK(hipEventRecord(gs.ev, st));
-    gs.used = true;
+    HIP_CHECK(hipEventRecord(rows.ev, st));
+    rows.used = true;
 }
 
-GroupScratch& next_group_scratch(cph_index* h) {
-    h->last_group = (h->last_group + 1) % kMaxBatchSets;
-    return h->group_scratch[h->last_group];
+RerankScratch& next_rerank_scratch(cph_index* h) {
+    h->last_rerank = (h->last_rerank + 1) % kMaxBatchSets;
+    return h->rerank_scratch[h->last_rerank];
 }
 
 // The one place the host-form buffers of a set grow: the staged queries and one buffer per slot of the table, each on its
-// own (DevBuf::alloc keeps a buffer that is long enough), after one wait for the set's previous batch if any has to.
-// -> the table at the set's device addresses.
-RerankOuts reserve_group_scratch(GroupScratch& gs, size_t q_floats, uint64_t n, const RerankOuts& host) {
-    bool grow = gs.d_q.n < q_floats;
-    for (int i = 0; i < host.count; ++i) grow |= gs.out[i].n < n * host.o[i].stride;
-    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-    gs.d_q.alloc(q_floats);
+// own.  -> the table at the set's device addresses.
+RerankOuts reserve_rerank_scratch(RerankScratch& gs, size_t q_floats, uint64_t n, const RerankOuts& host) {
+    Reserve r = gs.reserve();
+    r(gs.host.q, q_floats);
     RerankOuts dev = host;
-    for (int i = 0; i < host.count; ++i) {
-        gs.out[i].alloc(n * host.o[i].stride);
-        dev.o[i].p = gs.out[i].p;
-    }
+    for (int i = 0; i < host.count; ++i) dev.o[i].p = r(gs.host.out[i], n * host.o[i].stride);
     return dev;
 }
 
@@ -5930,12 +5894,12 @@ struct GroupedSearch {
     void check_batch(uint64_t n) const { check_batch_size(n); }
     void check_inputs(uint64_t) const {}
     void check_on(const cph_index*, uint32_t) const {}
-    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int64_t* ids, float* dist, int32_t* keys, int32_t* counts, uint8_t* complete) const {
         return {{{ids, 8 * k * g}, {dist, 4 * k * g}, {keys, 4 * k}, {counts, 4 * k}, {complete, 1}}, 5};
     }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
-        group_rows(group_args(gs.r_ids.p, gs.r_dist.p, C, k, g, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o), (uint32_t)n, st);
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
+        group_rows(group_args(gs.rows.ids.p, gs.rows.dist.p, C, k, g, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o), (uint32_t)n, st);
     }
 };
 
@@ -5987,10 +5951,10 @@ struct DiverseSearch {
     void check_batch(uint64_t n) const { check_batch_size(n); }
     void check_inputs(uint64_t) const {}
     void check_on(const cph_index*, uint32_t) const {}
-    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int64_t* ids, float* dist, float* gap) const { return {{{ids, 8 * k}, {dist, 4 * k}, {gap, 4 * k}}, 3}; }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
-        diverse_rows(diverse_args(h, gs.r_ids.p, gs.r_dist.p, C, k, lam, o), (uint32_t)n, st);
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
+        diverse_rows(diverse_args(h, gs.rows.ids.p, gs.rows.dist.p, C, k, lam, o), (uint32_t)n, st);
     }
 };
 
@@ -6045,31 +6009,10 @@ MaxsimArgs maxsim_args(const int64_t* r_ids, const float* r_dist, const int32_t*
     return a;
 }
 
-// n_tokens (host) -> the set's device copy, enqueued on `st`; null stays null.  One host wait: for the copy of the lengths
-// this set carried the last time (ev_tok), never for a kernel -- unless the buffers have to grow.  Called from the pass,
-// that is after `st` has been made to wait for the set's previous batch, whose kernel read d_tok.
-const int32_t* upload_maxsim_tokens(GroupScratch& gs, const int32_t* n_tokens, uint64_t n, hipStream_t st) {
-    if (!n_tokens) return nullptr;
-    if (gs.tok_used) HIP_CHECK(hipEventSynchronize(gs.ev_tok));
-    if (gs.pin_tok_n < n || gs.d_tok.n < n) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.pin_tok) HIP_CHECK(hipHostFree(gs.pin_tok));
-        gs.pin_tok = nullptr;
-        gs.pin_tok_n = 0;
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_tok), n * 2 * sizeof(int32_t), hipHostMallocDefault));
-        gs.pin_tok_n = n * 2;
-        gs.d_tok.alloc(n * 2);
-    }
-    if (!gs.ev_tok) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_tok, hipEventDisableTiming));
-    std::memcpy(gs.pin_tok, n_tokens, n * sizeof(int32_t));
-    HIP_CHECK(hipMemcpyAsync(gs.d_tok.p, gs.pin_tok, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(gs.ev_tok, st));
-    gs.tok_used = true;
-    return gs.d_tok.p;
-}
-
 // The queries are [n][T][dim]: the n * T token rows are one ordinary batch, and the pass joins the T rows of every query
-// by key.  n_tokens is on the host (null: every token is live).
+// by key.  n_tokens is on the host (null: every token is live) and travels as the set's staged table: one host wait, for the
+// copy of the table this set carried the last time, never for a kernel -- unless the buffers have to grow.  (The pass runs
+// after `st` has been made to wait for the set's previous batch, whose kernels read the table.)
 struct MaxsimSearch {
     uint64_t T;
     const int32_t* n_tokens;
@@ -6082,13 +6025,18 @@ struct MaxsimSearch {
     void check_batch(uint64_t n) const { check_maxsim_batch(n, T); }
     void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
     void check_on(const cph_index*, uint32_t) const {}
-    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found) const {
         return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}}, 5};
     }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
-        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
-        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t* d_key_of, const float*, const RerankOuts& o, hipStream_t st) const {
+        const int32_t* d_tokens = nullptr;
+        if (n_tokens) {
+            Reserve r = gs.reserve();
+            std::memcpy(gs.tab.begin(n * 4, r), n_tokens, n * 4);
+            d_tokens = reinterpret_cast<const int32_t*>(gs.tab.send(n * 4, st));
+        }
+        maxsim_rows(maxsim_args(gs.rows.ids.p, gs.rows.dist.p, d_tokens, T, C, k, d_key_of, h->size(), h->ids_input ? h->d_rows.p : nullptr, o),
                     (uint32_t)n, h->device, st);
     }
 };
@@ -6135,94 +6083,68 @@ const KeyRows& key_rows(cph_index* h, const cph_group_keys* keys, const int32_t*
     return *slot;
 }
 
-// The rescore buffers of a set for n queries; one wait for the set's previous batch if one of them has to grow.
-void reserve_rescore_scratch(GroupScratch& gs, uint64_t n, uint64_t T, uint64_t R, uint64_t dim, uint64_t D, bool metric_rows) {
-    const size_t nr = n * R, rows = n * T + kExactQT;
-    const bool grow = gs.c_keys.n < nr || gs.c_found.n < n || gs.rs_rows.n < nr * T || gs.rs_qpad.n < rows * D || gs.rs_qnorm.n < rows ||
-                      (metric_rows && gs.rs_q.n < n * T * dim);
-    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-    gs.c_keys.alloc(nr);
-    gs.c_lb.alloc(nr);
-    gs.c_hits.alloc(nr);
-    gs.c_found.alloc(n);
-    gs.rs_score.alloc(nr);
-    gs.rs_rows.alloc(nr * T);
-    gs.rs_qpad.alloc(rows * D);
-    gs.rs_qnorm.alloc(rows);
-    gs.rs_stats.alloc(kStatWords);
-    if (metric_rows) gs.rs_q.alloc(n * T * dim);
-}
-
-// The filter a rescored query runs under, per query: filter_of and the table of bitmap pointers are host data and travel
-// the way n_tokens does -- written into the set's pinned buffer ([F pointers | n x int32]) and copied by one command on `st`;
-// the one host wait is for the copy this set carried the last time (ev_rs).  `hold` keeps the effective filters (F & ~R)
-// until the call is enqueued.  Called from the pass: `st` already waits for the set's previous batch.
-struct RescoreFilters {
+// What a rescored maxsim call sends from the host: n_tokens, and the filter a query runs under -- filter_of and the table of
+// bitmap pointers -- as one staged table ([F pointers | n x int32 | n x int32], every piece only if the call has it) on `st`;
+// the one host wait is for the copy this set carried the last time.  `hold` keeps the effective filters (F & ~R) until the
+// call is enqueued.  Called from the pass: `st` already waits for the set's previous batch.
+struct RescoreTables {
+    const int32_t* d_tokens = nullptr;
     const int32_t* d_filter_of = nullptr;
     const uint32_t* const* d_bitmaps = nullptr;
     const uint32_t* unfiltered = nullptr;
     std::vector<std::shared_ptr<const cph_filter>> hold;
 };
 
-void upload_rescore_filters(cph_index* h, GroupScratch& gs, const cph_filter* const* filters, uint32_t F, const int32_t* filter_of,
-                            uint64_t n, hipStream_t st, RescoreFilters& out) {
+void send_rescore_tables(cph_index* h, RerankScratch& gs, Reserve& r, const int32_t* n_tokens, const cph_filter* const* filters, uint32_t F,
+                         const int32_t* filter_of, uint64_t n, hipStream_t st, RescoreTables& out) {
     auto words = [&](const cph_filter* f) -> const uint32_t* {
         out.hold.push_back(effective_filter(h, f));
         return out.hold.back() ? out.hold.back()->words.p : nullptr;
     };
-    if (!filter_of) {
-        out.unfiltered = words(F ? filters[0] : nullptr);
-        return;
+    out.unfiltered = words(!filter_of && F ? filters[0] : nullptr);
+    size_t need = 0;
+    const size_t o_ptr = table_take(need, filter_of ? (size_t)F * 8 : 0), o_fof = table_take(need, filter_of ? n * 4 : 0),
+                 o_tok = table_take(need, n_tokens ? n * 4 : 0);
+    if (!need) return;
+    uint8_t* const tb = gs.tab.begin(need, r);
+    if (filter_of) {
+        for (uint32_t f = 0; f < F; ++f) {
+            const uint64_t p = reinterpret_cast<uint64_t>(words(filters[f]));
+            std::memcpy(tb + o_ptr + (size_t)f * 8, &p, 8);
+        }
+        std::memcpy(tb + o_fof, filter_of, n * 4);
     }
-    out.unfiltered = words(nullptr);
-    const size_t need = (size_t)F * 8 + n * 4;
-    if (gs.rs_used) HIP_CHECK(hipEventSynchronize(gs.ev_rs));
-    if (gs.pin_rs_bytes < need || gs.d_rs.n < need) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.pin_rs) HIP_CHECK(hipHostFree(gs.pin_rs));
-        gs.pin_rs = nullptr;
-        gs.pin_rs_bytes = 0;
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_rs), need * 2, hipHostMallocDefault));
-        gs.pin_rs_bytes = need * 2;
-        gs.d_rs.alloc(need * 2);
+    if (n_tokens) std::memcpy(tb + o_tok, n_tokens, n * 4);
+    const uint8_t* const dt = gs.tab.send(need, st);
+    if (filter_of) {
+        out.d_bitmaps = reinterpret_cast<const uint32_t* const*>(dt + o_ptr);
+        out.d_filter_of = reinterpret_cast<const int32_t*>(dt + o_fof);
     }
-    if (!gs.ev_rs) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_rs, hipEventDisableTiming));
-    for (uint32_t f = 0; f < F; ++f) {
-        const uint64_t p = reinterpret_cast<uint64_t>(words(filters[f]));
-        std::memcpy(gs.pin_rs + (size_t)f * 8, &p, 8);
-    }
-    std::memcpy(gs.pin_rs + (size_t)F * 8, filter_of, n * 4);
-    HIP_CHECK(hipMemcpyAsync(gs.d_rs.p, gs.pin_rs, need, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(gs.ev_rs, st));
-    gs.rs_used = true;
-    out.d_bitmaps = reinterpret_cast<const uint32_t* const*>(gs.d_rs.p);
-    out.d_filter_of = reinterpret_cast<const int32_t*>(gs.d_rs.p + (size_t)F * 8);
+    if (n_tokens) out.d_tokens = reinterpret_cast<const int32_t*>(dt + o_tok);
 }
 
-MaxsimRescoreArgs maxsim_rescore_args(const cph_index* h, const KeyRows& kr, const float* qpad, const float* qnorm, const int32_t* cand_keys,
-                                      const float* cand_lb, const int32_t* cand_found, const int32_t* d_tokens, const int32_t* d_filter_of,
-                                      const uint32_t* const* d_bitmaps, const uint32_t* unfiltered, uint64_t T, uint64_t R, uint64_t k,
-                                      float* sc_score, uint32_t* sc_rows, const RerankOuts& o) {
+MaxsimRescoreArgs maxsim_rescore_args(const cph_index* h, const KeyRows& kr, const RerankScratch::Padded& p, const RerankScratch::Cand& c,
+                                      const RescoreTables& t, uint64_t T, uint64_t R, uint64_t k, const RerankOuts& o) {
     MaxsimRescoreArgs a{};
     a.s.raw = h->d_raw.p;
     a.s.norm_sq = h->d_norm.p;
-    a.s.qpad = qpad;
-    a.s.qnorm = qnorm;
+    a.s.qpad = p.qpad.p;
+    a.s.qnorm = p.qnorm.p;
     a.s.D = h->L.D;
     a.csr = KeyRowsDev{kr.ids.p, kr.keys.p, kr.offsets.p, kr.n_keys};
-    a.cand_keys = cand_keys;
-    a.cand_lb = cand_lb;
-    a.cand_found = cand_found;
-    a.n_tokens = d_tokens;
-    a.filter_of = d_filter_of;
-    a.bitmaps = d_bitmaps;
-    a.unfiltered = unfiltered;
+    a.cand_keys = c.keys.p;
+    a.cand_lb = c.lb.p;
+    a.cand_found = c.found.p;
+    a.n_tokens = t.d_tokens;
+    a.filter_of = t.d_filter_of;
+    a.bitmaps = t.d_bitmaps;
+    a.unfiltered = t.unfiltered;
     a.T = (uint32_t)T;
     a.R = (uint32_t)R;
     a.k = (uint32_t)k;
     a.n_ids = (uint32_t)h->size();
-    a.sc_score = sc_score;
-    a.sc_rows = sc_rows;
+    a.sc_score = c.score.p;
+    a.sc_rows = c.rows.p;
     a.rows = h->ids_input ? h->d_rows.p : nullptr;
     a.out_keys = o.at<int32_t>(0);
     a.out_score = o.at<float>(1);
@@ -6233,15 +6155,17 @@ MaxsimRescoreArgs maxsim_rescore_args(const cph_index* h, const KeyRows& kr, con
     return a;
 }
 
-// The token rows as the search saw them (cosine: normalised into `metric_rows`), padded with their norms, on `st`.
-void pad_rescore_tokens(cph_index* h, const float* d_tokens_raw, uint64_t rows, float* metric_rows, float* qpad, float* qnorm,
-                        unsigned long long* d_stats, hipStream_t st) {
+// `rows` token rows as the search saw them (cosine: normalised into p.q), padded with their norms into the buffers of `p`,
+// which grow as they must; on `st` (rescored maxsim and fused search).
+void pad_rescore_tokens(cph_index* h, Reserve& r, RerankScratch::Padded& p, const float* d_tokens_raw, uint64_t rows, hipStream_t st) {
     const float* src = d_tokens_raw;
     if (h->metric == CPH_METRIC_COSINE) {
-        normalize_rows(d_tokens_raw, metric_rows, rows, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
-        src = metric_rows;
+        normalize_rows(d_tokens_raw, r(p.q, rows * h->dim), rows, (uint32_t)h->dim, (uint32_t)h->dim, (uint32_t)h->dim, nullptr, nullptr, st);
+        src = p.q.p;
     }
-    pad_queries(h, src, nullptr, (uint32_t)rows, (uint32_t)rows + kExactQT, qpad, qnorm, d_stats, 0, st);
+    r(p.qpad, (rows + kExactQT) * h->L.D);
+    r(p.qnorm, rows + kExactQT);
+    pad_queries(h, src, nullptr, (uint32_t)rows, (uint32_t)rows + kExactQT, p.qpad.p, p.qnorm.p, r(p.stats, kStatWords), 0, st);
 }
 
 // The lower-bound pass at k = R into the set's scratch, then the pad, the scan and the select.  The call's filters and keys
@@ -6262,22 +6186,24 @@ struct MaxsimRescoredSearch {
     void check_batch(uint64_t n) const { check_maxsim_rescore_batch(n, T, R); }
     void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
     void check_on(const cph_index*, uint32_t) const {}
-    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found, int32_t* certified) const {
         return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}, {certified, 4}}, 6};
     }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t* d_key_of, const float* d_queries, const RerankOuts& o,
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t* d_key_of, const float* d_queries, const RerankOuts& o,
               hipStream_t st) const {
         const KeyRows& kr = key_rows(h, keys_obj, d_key_of);
-        reserve_rescore_scratch(gs, n, T, R, h->dim, h->L.D, h->metric == CPH_METRIC_COSINE);
-        const int32_t* d_tokens = upload_maxsim_tokens(gs, n_tokens, n, st);
-        RescoreFilters rf;
-        upload_rescore_filters(h, gs, filters, F, filter_of, n, st, rf);
-        const RerankOuts cand = {{{gs.c_keys.p, 4 * R}, {gs.c_lb.p, 4 * R}, {gs.c_hits.p, 4 * R}, {nullptr, 0}, {gs.c_found.p, 4}}, 5};
-        maxsim_rows(maxsim_args(gs.r_ids.p, gs.r_dist.p, d_tokens, T, C, R, d_key_of, h->size(), nullptr, cand), (uint32_t)n, h->device, st);
-        pad_rescore_tokens(h, d_queries, n * T, gs.rs_q.p, gs.rs_qpad.p, gs.rs_qnorm.p, gs.rs_stats.p, st);
-        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, gs.rs_qpad.p, gs.rs_qnorm.p, gs.c_keys.p, gs.c_lb.p, gs.c_found.p, d_tokens,
-                                                        rf.d_filter_of, rf.d_bitmaps, rf.unfiltered, T, R, k, gs.rs_score.p, gs.rs_rows.p, o);
+        Reserve r = gs.reserve();
+        RerankScratch::Cand& c = gs.cand;
+        const size_t nr = n * R;
+        const RerankOuts cand = {{{r(c.keys, nr), 4 * R}, {r(c.lb, nr), 4 * R}, {r(c.hits, nr), 4 * R}, {nullptr, 0}, {r(c.found, n), 4}}, 5};
+        r(c.score, nr);
+        r(c.rows, nr * T);
+        RescoreTables rt;
+        send_rescore_tables(h, gs, r, n_tokens, filters, F, filter_of, n, st, rt);
+        maxsim_rows(maxsim_args(gs.rows.ids.p, gs.rows.dist.p, rt.d_tokens, T, C, R, d_key_of, h->size(), nullptr, cand), (uint32_t)n, h->device, st);
+        pad_rescore_tokens(h, r, gs.pad, d_queries, n * T, st);
+        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, gs.pad, c, rt, T, R, k, o);
         timed_pass(h->pass_timer[kPassMaxsimRescore], st, [&] { maxsim_rescore_scan(a, (uint32_t)n, st); });
         maxsim_rescore_select(a, (uint32_t)n, st);
     }
@@ -6314,75 +6240,45 @@ void check_fused_inputs(const int32_t* n_vectors, const float* weights, uint64_t
             throw InvalidArg("weights[" + std::to_string(i / T) + "][" + std::to_string(i % T) + "] is not finite");
 }
 
-// The fused buffers of a set for n queries; one wait for the set's previous batch if one of them has to grow.
-void reserve_fused_scratch(GroupScratch& gs, uint64_t n, uint64_t T, uint64_t C, uint64_t dim, uint64_t D, bool metric_rows) {
-    const size_t slots = n * T * C, rows = n * T + kExactQT;
-    const bool grow = gs.fu_ids.n < slots || gs.fu_count.n < n || gs.rs_qpad.n < rows * D || gs.rs_qnorm.n < rows ||
-                      gs.rs_stats.n < kStatWords || (metric_rows && gs.rs_q.n < n * T * dim);
-    if (grow && gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-    gs.fu_ids.alloc(slots);
-    gs.fu_hits.alloc(slots);
-    gs.fu_score.alloc(slots);
-    gs.fu_count.alloc(n);
-    gs.rs_qpad.alloc(rows * D);
-    gs.rs_qnorm.alloc(rows);
-    gs.rs_stats.alloc(kStatWords);
-    if (metric_rows) gs.rs_q.alloc(n * T * dim);
-}
-
-// n_vectors and the weights are host data and travel the way n_tokens does: written into the set's pinned buffer
-// ([n * T floats | n x int32]; null weights: ones) and copied by one command on `st`; the one host wait is for the copy this set
-// carried the last time (ev_rs).  Called from the pass: `st` already waits for the set's previous batch.
+// n_vectors and the weights are host data and travel as the set's staged table ([n * T floats | n x int32]; null weights:
+// ones) on `st`; the one host wait is for the copy this set carried the last time.  Called from the pass: `st` already waits
+// for the set's previous batch.
 struct FusedHostData {
     const float* d_weights = nullptr;
     const int32_t* d_n_vectors = nullptr;
 };
 
-FusedHostData upload_fused_host_data(GroupScratch& gs, const int32_t* n_vectors, const float* weights, uint64_t n, uint64_t T, hipStream_t st) {
-    const size_t wb = n * T * 4, need = wb + (n_vectors ? n * 4 : 0);
-    if (gs.rs_used) HIP_CHECK(hipEventSynchronize(gs.ev_rs));
-    if (gs.pin_rs_bytes < need || gs.d_rs.n < need) {
-        if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));
-        if (gs.pin_rs) HIP_CHECK(hipHostFree(gs.pin_rs));
-        gs.pin_rs = nullptr;
-        gs.pin_rs_bytes = 0;
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&gs.pin_rs), need * 2, hipHostMallocDefault));
-        gs.pin_rs_bytes = need * 2;
-        gs.d_rs.alloc(need * 2);
-    }
-    if (!gs.ev_rs) HIP_CHECK(hipEventCreateWithFlags(&gs.ev_rs, hipEventDisableTiming));
-    if (weights) std::memcpy(gs.pin_rs, weights, wb);
-    else std::fill_n(reinterpret_cast<float*>(gs.pin_rs), n * T, 1.0f);
-    if (n_vectors) std::memcpy(gs.pin_rs + wb, n_vectors, n * 4);
-    HIP_CHECK(hipMemcpyAsync(gs.d_rs.p, gs.pin_rs, need, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipEventRecord(gs.ev_rs, st));
-    gs.rs_used = true;
-    FusedHostData out;
-    out.d_weights = reinterpret_cast<const float*>(gs.d_rs.p);
-    if (n_vectors) out.d_n_vectors = reinterpret_cast<const int32_t*>(gs.d_rs.p + wb);
-    return out;
+FusedHostData send_fused_host_data(RerankScratch& gs, Reserve& r, const int32_t* n_vectors, const float* weights, uint64_t n, uint64_t T,
+                                   hipStream_t st) {
+    size_t need = 0;
+    const size_t o_w = table_take(need, n * T * 4), o_nv = table_take(need, n_vectors ? n * 4 : 0);
+    uint8_t* const tb = gs.tab.begin(need, r);
+    if (weights) std::memcpy(tb + o_w, weights, n * T * 4);
+    else std::fill_n(reinterpret_cast<float*>(tb + o_w), n * T, 1.0f);
+    if (n_vectors) std::memcpy(tb + o_nv, n_vectors, n * 4);
+    const uint8_t* const dt = gs.tab.send(need, st);
+    return {reinterpret_cast<const float*>(dt + o_w), n_vectors ? reinterpret_cast<const int32_t*>(dt + o_nv) : nullptr};
 }
 
-FusedArgs fused_args(const cph_index* h, const int64_t* cand, const float* qpad, const float* qnorm, const int32_t* d_n_vectors,
-                     const float* d_weights, uint64_t T, uint64_t C, uint64_t k, uint32_t* u_ids, uint32_t* u_hits, uint32_t* u_count,
-                     float* u_score, const RerankOuts& o) {
+FusedArgs fused_args(const cph_index* h, const int64_t* cand, const RerankScratch::Padded& p, const FusedHostData& hd, uint64_t T, uint64_t C,
+                     uint64_t k, const RerankScratch::Union& u, const RerankOuts& o) {
     FusedArgs a{};
     a.s.raw = h->d_raw.p;
     a.s.norm_sq = h->d_norm.p;
-    a.s.qpad = qpad;
-    a.s.qnorm = qnorm;
+    a.s.qpad = p.qpad.p;
+    a.s.qnorm = p.qnorm.p;
     a.s.D = h->L.D;
     a.cand = cand;
-    a.n_vectors = d_n_vectors;
-    a.weights = d_weights;
+    a.n_vectors = hd.d_n_vectors;
+    a.weights = hd.d_weights;
     a.T = (uint32_t)T;
     a.C = (uint32_t)C;
     a.k = (uint32_t)k;
     a.n_ids = (uint32_t)h->size();
-    a.u_ids = u_ids;
-    a.u_hits = u_hits;
-    a.u_count = u_count;
-    a.u_score = u_score;
+    a.u_ids = u.ids.p;
+    a.u_hits = u.hits.p;
+    a.u_count = u.count.p;
+    a.u_score = u.score.p;
     a.rows = h->ids_input ? h->d_rows.p : nullptr;
     a.out_ids = o.at<int64_t>(0);
     a.out_score = o.at<float>(1);
@@ -6405,14 +6301,14 @@ struct FusedSearch {
     void check_batch(uint64_t n) const { check_fused_batch(n, T, C); }
     void check_inputs(uint64_t n) const { check_fused_inputs(n_vectors, weights, n, T); }
     void check_on(const cph_index*, uint32_t) const {}
-    void stage(GroupScratch&, uint64_t, hipStream_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
     RerankOuts outs(int64_t* ids, float* score, int32_t* hits) const { return {{{ids, 8 * k}, {score, 4 * k}, {hits, 4 * k}}, 3}; }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float* d_queries, const RerankOuts& o, hipStream_t st) const {
-        reserve_fused_scratch(gs, n, T, C, h->dim, h->L.D, h->metric == CPH_METRIC_COSINE);
-        const FusedHostData hd = upload_fused_host_data(gs, n_vectors, weights, n, T, st);
-        pad_rescore_tokens(h, d_queries, n * T, gs.rs_q.p, gs.rs_qpad.p, gs.rs_qnorm.p, gs.rs_stats.p, st);
-        const FusedArgs a = fused_args(h, gs.r_ids.p, gs.rs_qpad.p, gs.rs_qnorm.p, hd.d_n_vectors, hd.d_weights, T, C, k, gs.fu_ids.p,
-                                       gs.fu_hits.p, gs.fu_count.p, gs.fu_score.p, o);
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t*, const float* d_queries, const RerankOuts& o, hipStream_t st) const {
+        Reserve r = gs.reserve();
+        gs.un.reserve(r, n, n * T * C);
+        const FusedHostData hd = send_fused_host_data(gs, r, n_vectors, weights, n, T, st);
+        pad_rescore_tokens(h, r, gs.pad, d_queries, n * T, st);
+        const FusedArgs a = fused_args(h, gs.rows.ids.p, gs.pad, hd, T, C, k, gs.un, o);
         fused_union(a, (uint32_t)n, h->device, st);
         timed_pass(h->pass_timer[kPassFused], st, [&] { fused_scan(a, (uint32_t)n, st); });
         fused_select(a, (uint32_t)n, h->device, st);
@@ -6436,7 +6332,7 @@ bool rerank_has_work(cph_index* h, const Rerank& f, const RerankCall& c) {
 // The body of both single-handle forms: d_queries and the outputs `o` in device memory, filter_of on the host (a query's
 // filter serves its T tokens).
 template <class Rerank>
-void rerank_locked(cph_index* h, GroupScratch& gs, const Rerank& f, const RerankCall& c, const float* d_queries, const int32_t* d_key_of,
+void rerank_locked(cph_index* h, RerankScratch& gs, const Rerank& f, const RerankCall& c, const float* d_queries, const int32_t* d_key_of,
                    const RerankOuts& o, hipStream_t st) {
     const uint64_t T = f.tokens();
     std::vector<int32_t> token_filter;
@@ -6459,14 +6355,14 @@ void rerank_search(cph_index* h, const Rerank& f, const RerankCall& c, const cph
     f.check_on(h, 0);
     const int32_t* d_key_of = Rerank::keyed ? group_key_column(h, keys) : nullptr;
     h->use_device();
-    if (stream) return rerank_locked(h, next_group_scratch(h), f, c, c.q, d_key_of, c.out, reinterpret_cast<hipStream_t>(*stream));
+    if (stream) return rerank_locked(h, next_rerank_scratch(h), f, c, c.q, d_key_of, c.out, reinterpret_cast<hipStream_t>(*stream));
     hipStream_t st = own_stream(h);
-    GroupScratch& gs = next_group_scratch(h);
+    RerankScratch& gs = next_rerank_scratch(h);
     const size_t q_floats = (size_t)c.n * f.tokens() * h->dim;
-    const RerankOuts dev = reserve_group_scratch(gs, q_floats, c.n, c.out);
-    HIP_CHECK(hipMemcpyAsync(gs.d_q.p, c.q, q_floats * 4, hipMemcpyHostToDevice, st));
+    const RerankOuts dev = reserve_rerank_scratch(gs, q_floats, c.n, c.out);
+    HIP_CHECK(hipMemcpyAsync(gs.host.q.p, c.q, q_floats * 4, hipMemcpyHostToDevice, st));
     f.stage(gs, c.n, st);
-    rerank_locked(h, gs, f, c, gs.d_q.p, d_key_of, dev, st);
+    rerank_locked(h, gs, f, c, gs.host.q.p, d_key_of, dev, st);
     for (int i = 0; i < dev.count; ++i) HIP_CHECK(hipMemcpyAsync(c.out.o[i].p, dev.o[i].p, c.n * dev.o[i].stride, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -6889,8 +6785,15 @@ int cph_maxsim_rescore_hook(cph_index* h, const int32_t* cand_keys, const float*
         h->use_device();
         const KeyRows& kr = key_rows(h, keys, d_key_of);
         const uint64_t T = n_tok, R = rescore, rows = n * T, nw = (h->size() + 31) / 32;
-        const DevBuf<int32_t> d_ck = uploaded(cand_keys, n * R), d_cf = uploaded(cand_found, n), d_tok = uploaded(n_tokens, n);
-        const DevBuf<float> d_lb = uploaded(cand_lb, n * R), d_q = uploaded(tokens, rows * h->dim);
+        RerankScratch::Padded pad;
+        RerankScratch::Cand c;
+        c.keys = uploaded(cand_keys, n * R);
+        c.found = uploaded(cand_found, n);
+        c.lb = uploaded(cand_lb, n * R);
+        c.score.alloc(n * R);
+        c.rows.alloc(n * R * T);
+        const DevBuf<int32_t> d_tok = uploaded(n_tokens, n);
+        const DevBuf<float> d_q = uploaded(tokens, rows * h->dim);
         const DevBuf<uint32_t> d_allow = uploaded(allow, n * nw);
         std::vector<uint64_t> ptrs(n);
         std::vector<int32_t> of(n);
@@ -6900,15 +6803,14 @@ int cph_maxsim_rescore_hook(cph_index* h, const int32_t* cand_keys, const float*
         }
         const DevBuf<uint64_t> d_ptrs = uploaded(allow ? ptrs.data() : nullptr, n);
         const DevBuf<int32_t> d_of = uploaded(allow ? of.data() : nullptr, n);
-        DevBuf<float> d_metric(rows * h->dim), d_qpad((rows + kExactQT) * h->L.D), d_qnorm(rows + kExactQT), d_score(n * R);
-        DevBuf<uint32_t> d_rows(n * R * T);
-        DevBuf<unsigned long long> d_stats(kStatWords);
+        RescoreTables rt;
+        if (n_tokens) rt.d_tokens = d_tok.p;
+        if (allow) rt.d_filter_of = d_of.p;
+        if (allow) rt.d_bitmaps = reinterpret_cast<const uint32_t* const*>(d_ptrs.p);
         PoisonedOuts po(o, n);
-        pad_rescore_tokens(h, d_q.p, rows, d_metric.p, d_qpad.p, d_qnorm.p, d_stats.p, nullptr);
-        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, d_qpad.p, d_qnorm.p, d_ck.p, d_lb.p, d_cf.p, n_tokens ? d_tok.p : nullptr,
-                                                        allow ? d_of.p : nullptr,
-                                                        allow ? reinterpret_cast<const uint32_t* const*>(d_ptrs.p) : nullptr, nullptr, T, R, k,
-                                                        d_score.p, d_rows.p, po.dev);
+        Reserve fresh{nullptr, false};
+        pad_rescore_tokens(h, fresh, pad, d_q.p, rows, nullptr);
+        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, pad, c, rt, T, R, k, po.dev);
         maxsim_rescore_scan(a, (uint32_t)n, nullptr);
         maxsim_rescore_select(a, (uint32_t)n, nullptr);
         po.download();
@@ -7008,13 +6910,13 @@ int cph_fused_rows_hook(cph_index* h, const int64_t* cand_ids, const float* quer
         const DevBuf<int64_t> d_cand = uploaded(cand_ids, rows * C);
         const DevBuf<float> d_q = uploaded(queries, rows * h->dim), d_w = uploaded(weights ? weights : ones.data(), rows);
         const DevBuf<int32_t> d_nv = uploaded(n_vectors, n);
-        DevBuf<float> d_metric(rows * h->dim), d_qpad((rows + kExactQT) * h->L.D), d_qnorm(rows + kExactQT), d_score(rows * C);
-        DevBuf<uint32_t> d_uids(rows * C), d_uhits(rows * C), d_ucount(n);
-        DevBuf<unsigned long long> d_stats(kStatWords);
+        RerankScratch::Padded pad;
+        RerankScratch::Union u;
         PoisonedOuts po(o, n);
-        pad_rescore_tokens(h, d_q.p, rows, d_metric.p, d_qpad.p, d_qnorm.p, d_stats.p, nullptr);
-        const FusedArgs a = fused_args(h, d_cand.p, d_qpad.p, d_qnorm.p, n_vectors ? d_nv.p : nullptr, d_w.p, T, C, k, d_uids.p, d_uhits.p,
-                                       d_ucount.p, d_score.p, po.dev);
+        Reserve fresh{nullptr, false};
+        u.reserve(fresh, n, rows * C);
+        pad_rescore_tokens(h, fresh, pad, d_q.p, rows, nullptr);
+        const FusedArgs a = fused_args(h, d_cand.p, pad, {d_w.p, n_vectors ? d_nv.p : nullptr}, T, C, k, u, po.dev);
         fused_union(a, (uint32_t)n, h->device, nullptr);
         fused_scan(a, (uint32_t)n, nullptr);
         fused_select(a, (uint32_t)n, h->device, nullptr);
@@ -7130,18 +7032,14 @@ struct RescoredSearch {
         if (dim_full != vectors[r]->dim)
             throw InvalidArg("full queries have " + std::to_string(dim_full) + " coordinates, the rescore vectors " + std::to_string(vectors[r]->dim));
     }
-    void stage(GroupScratch& gs, uint64_t n, hipStream_t st) const {
+    void stage(RerankScratch& gs, uint64_t n, hipStream_t st) const {
         const size_t floats = (size_t)n * dim_full;
-        if (gs.d_fq.n < floats) {
-            if (gs.used) HIP_CHECK(hipEventSynchronize(gs.ev));      // growing: the old buffer must be idle
-            gs.d_fq.alloc(floats);
-        }
-        HIP_CHECK(hipMemcpyAsync(gs.d_fq.p, full_q, floats * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(gs.reserve()(gs.host.fq, floats), full_q, floats * 4, hipMemcpyHostToDevice, st));
     }
     RerankOuts outs(int64_t* ids, float* score, float* first) const { return {{{ids, 8 * k}, {score, 4 * k}, {first, 4 * k}}, 3}; }
-    void pass(cph_index* h, GroupScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
         const cph_rescore_vectors* rv = vectors[0];
-        rescore_rows(rescore_args(rescore_store(rv), rv->ip, gs.r_ids.p, gs.r_dist.p, host_form ? gs.d_fq.p : full_q, C, k,
+        rescore_rows(rescore_args(rescore_store(rv), rv->ip, gs.rows.ids.p, gs.rows.dist.p, host_form ? gs.host.fq.p : full_q, C, k,
                                   h->ids_input ? h->d_rows.p : nullptr, o),
                      rv->f32, (uint32_t)n, st);
     }

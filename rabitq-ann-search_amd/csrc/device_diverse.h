@@ -3,7 +3,7 @@
 // The statement is host_diverse.h's.  diverse_rows_kernel runs one 256-thread workgroup per query:
 //     c_id[C], c_r[C], c_m[C]   per row position: the internal id (kNoId: padding, a repeat, or picked already), the
 //                               relevance bits, the smallest pair distance to a pick so far
-//     tab_id[H], tab_pos[H]     a hash table over the row's ids (H = the power of two >= 2 C): an id's slot keeps the lowest
+//     tab_id[H], tab_pos[H]     the first-position id table (device_wg_primitives.h): an id's slot keeps the lowest
 //                               position it occurs at, so the candidates are the entries that sit at their id's position
 //     qv[D]                     the stored row of the last pick
 // A pick loads its row into qv; every 8-lane group computes qnorm with the chains of the search kernel's query_norm_sq and
@@ -23,6 +23,7 @@
 
 #include "device_buf.h"
 #include "device_fastscan.h"
+#include "device_wg_primitives.h"
 #include "host_diverse.h"
 
 namespace cph {
@@ -42,13 +43,6 @@ struct DiverseArgs {
 };
 
 constexpr uint32_t kDiverseThreads = 256;
-constexpr uint32_t kNoId = 0xFFFFFFFFu;   // (n_ids <= 0xFFFFFFFF: no id has this value)
-
-__host__ __device__ inline uint32_t diverse_table_slots(uint32_t C) {
-    uint32_t h = 2;
-    while (h < 2 * C) h *= 2;
-    return h;
-}
 inline size_t diverse_lds_bytes(uint32_t C, uint32_t D) {
     return ((size_t)D + 3 * (size_t)C + 2 * (size_t)diverse_table_slots(C) + 2 * (kDiverseThreads / 64)) * 4;   // at most 37 KiB
 }
@@ -80,7 +74,8 @@ __global__ __launch_bounds__(kDiverseThreads) void diverse_rows_kernel(DiverseAr
     uint32_t* __restrict__ out_dist = reinterpret_cast<uint32_t*>(a.out_dist) + q * k;
     uint32_t* __restrict__ out_gap = reinterpret_cast<uint32_t*>(a.out_gap) + q * k;
 
-    // the candidates: an id's first position in the row
+    // the candidates: an id's first position in the row.  (device_wg_primitives.h's table, written out: with its functions
+    // inlined here the compiler swaps two instructions of the pick loop, and this kernel's instruction stream is pinned.)
     for (uint32_t s = tid; s < H; s += kDiverseThreads) {
         tab_id[s] = kNoId;
         tab_pos[s] = kNoId;

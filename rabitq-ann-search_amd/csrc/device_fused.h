@@ -4,7 +4,7 @@
 // The statement is host_fused.h's.  Three kernels behind the ordinary search at k = C and exact_pad_kernel, on one stream:
 //   union    fused_union_kernel: one 256-thread workgroup per query, over the E = L * C entries of the query's live rows and
 //            P = the power of two >= max(E, 64).  A valid entry (0 <= id < n_ids) becomes the 64-bit word  id << 32 | t ,
-//            everything else the all-ones word, which no entry has.  The bitonic sort of device_maxsim.h orders them by
+//            everything else the all-ones word, which no entry has.  The bitonic sort of device_wg_primitives.h orders them by
 //            (id, vector); a segment of equal high halves is one candidate, the distinct low halves inside it are its hits.
 //            Segment heads and (id, vector) run heads by neighbour compares; every wave counts the heads of its quarter with
 //            ballots, the four totals give the offsets, a second walk writes u_ids[segment] (ascending) and the index of every
@@ -36,7 +36,7 @@
 #include <cstdint>
 
 #include "device_exact.h"
-#include "device_maxsim.h"
+#include "device_wg_primitives.h"
 #include "host_fused.h"
 
 namespace cph {
@@ -70,14 +70,14 @@ __device__ __forceinline__ uint32_t fused_live(const FusedArgs& a, size_t q) {
 
 // words u64 [P] | segment's first run u16 [P + 2] | counters u32 [8]
 inline size_t fused_union_lds(uint32_t T, uint32_t C) {
-    const size_t P = maxsim_sort_len(T * C);
+    const size_t P = wg_sort_len(T * C);
     return P * 8 + (P + 2) * 2 + 8 * 4;
 }
 
-// Grid n, kMaxsimThreads threads; LDS: fused_union_lds(T, C).
-__global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a) {
+// Grid n, kWgSortThreads threads; LDS: fused_union_lds(T, C).
+__global__ __launch_bounds__(kWgSortThreads) void fused_union_kernel(FusedArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint32_t T = a.T, C = a.C, Pmax = maxsim_sort_len(T * C);
+    const uint32_t T = a.T, C = a.C, Pmax = wg_sort_len(T * C);
     unsigned long long* w = reinterpret_cast<unsigned long long*>(smem);
     uint16_t* sf = reinterpret_cast<uint16_t*>(w + Pmax);
     uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + (size_t)Pmax * 8 + (((size_t)Pmax + 2) * 2 + 3) / 4 * 4);
@@ -85,10 +85,10 @@ __global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a
     const size_t q = blockIdx.x;
     const int64_t* __restrict__ qi = a.cand + q * T * C;
     const uint32_t L = fused_live(a, q);
-    const uint32_t E = L * C, P = maxsim_sort_len(E);
+    const uint32_t E = L * C, P = wg_sort_len(E);
 
-    for (uint32_t e = tid; e < P; e += kMaxsimThreads) {
-        unsigned long long word = kMaxsimNone;
+    for (uint32_t e = tid; e < P; e += kWgSortThreads) {
+        unsigned long long word = kSortNone;
         if (e < E) {
             const int64_t id = qi[e];
             if (id >= 0 && (unsigned long long)id < a.n_ids) word = ((unsigned long long)id << 32) | (e / C);
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a
         w[e] = word;
     }
     __syncthreads();
-    maxsim_sort(w, P, tid);
+    wg_sort(w, P, tid);
 
     // wave v owns [v * span, (v + 1) * span) of the sorted words
     const uint32_t span = P / 4 < 64 ? 64 : P / 4;
@@ -105,8 +105,8 @@ __global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a
     uint32_t runs = 0, segs = 0;
     for (uint32_t base = w_lo; base < w_hi; base += 64) {
         const uint32_t i = base + lane;
-        const unsigned long long x = w[i], pv = i ? w[i - 1] : kMaxsimNone;
-        const bool valid = x != kMaxsimNone;
+        const unsigned long long x = w[i], pv = i ? w[i - 1] : kSortNone;
+        const bool valid = x != kSortNone;
         const bool seg = valid && (i == 0 || (uint32_t)(pv >> 32) != (uint32_t)(x >> 32));
         const bool run = valid && (seg || pv != x);
         runs += (uint32_t)__popcll(__ballot(run));
@@ -127,8 +127,8 @@ __global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a
     uint32_t* __restrict__ u_hits = a.u_hits + q * T * C;
     for (uint32_t base = w_lo; base < w_hi; base += 64) {
         const uint32_t i = base + lane;
-        const unsigned long long x = w[i], pv = i ? w[i - 1] : kMaxsimNone;
-        const bool valid = x != kMaxsimNone;
+        const unsigned long long x = w[i], pv = i ? w[i - 1] : kSortNone;
+        const bool valid = x != kSortNone;
         const bool seg = valid && (i == 0 || (uint32_t)(pv >> 32) != (uint32_t)(x >> 32));
         const bool run = valid && (seg || pv != x);
         const unsigned long long run_m = __ballot(run), seg_m = __ballot(seg);
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void fused_union_kernel(FusedArgs a
         a.u_count[q] = n_segs;
     }
     __syncthreads();
-    for (uint32_t s = tid; s < n_segs; s += kMaxsimThreads) u_hits[s] = (uint32_t)sf[s + 1] - (uint32_t)sf[s];
+    for (uint32_t s = tid; s < n_segs; s += kWgSortThreads) u_hits[s] = (uint32_t)sf[s + 1] - (uint32_t)sf[s];
 }
 
 // The weighted sum of one block of 64 candidates: sm[lane] the lane's running sum, sw[t] the query's weights.  The workgroup
@@ -207,42 +207,42 @@ __global__ __launch_bounds__(64) void fused_scan_kernel(FusedArgs a) {
     }
 }
 
-inline size_t fused_select_lds(uint32_t T, uint32_t C) { return (size_t)maxsim_sort_len(T * C) * 8; }
+inline size_t fused_select_lds(uint32_t T, uint32_t C) { return (size_t)wg_sort_len(T * C) * 8; }
 
-// Grid n, kMaxsimThreads threads; LDS: fused_select_lds(T, C).
-__global__ __launch_bounds__(kMaxsimThreads) void fused_select_kernel(FusedArgs a) {
+// Grid n, kWgSortThreads threads; LDS: fused_select_lds(T, C).
+__global__ __launch_bounds__(kWgSortThreads) void fused_select_kernel(FusedArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned long long* w = reinterpret_cast<unsigned long long*>(smem);
     const uint32_t TC = a.T * a.C, k = a.k, tid = threadIdx.x;
     const size_t q = blockIdx.x;
     uint32_t U = a.u_count[q];
     if (U > TC) U = TC;
-    const uint32_t P = maxsim_sort_len(U);
+    const uint32_t P = wg_sort_len(U);
     const uint32_t* __restrict__ u_ids = a.u_ids + q * TC;
     const uint32_t* __restrict__ u_hits = a.u_hits + q * TC;
     const float* __restrict__ u_score = a.u_score + q * TC;
 
-    for (uint32_t s = tid; s < P; s += kMaxsimThreads) {
-        unsigned long long word = kMaxsimNone;
+    for (uint32_t s = tid; s < P; s += kWgSortThreads) {
+        unsigned long long word = kSortNone;
         if (s < U) {
             const float sc = u_score[s];
-            if (sc == sc) word = ((unsigned long long)maxsim_orderable(sc) << 32) | s;
+            if (sc == sc) word = ((unsigned long long)orderable(sc) << 32) | s;
         }
         w[s] = word;
     }
     __syncthreads();
-    maxsim_sort(w, P, tid);
+    wg_sort(w, P, tid);
 
-    for (uint32_t o = tid; o < k; o += kMaxsimThreads) {
+    for (uint32_t o = tid; o < k; o += kWgSortThreads) {
         int64_t id = -1;
         int32_t hits = 0;
         uint32_t score = 0x7F7FFFFFu;                     // FLT_MAX
-        const unsigned long long x = o < P ? w[o] : kMaxsimNone;
-        if (x != kMaxsimNone) {
+        const unsigned long long x = o < P ? w[o] : kSortNone;
+        if (x != kSortNone) {
             const uint32_t s = (uint32_t)x, i = u_ids[s];
             id = a.rows ? (int64_t)a.rows[i] : (int64_t)i;
             hits = (int32_t)u_hits[s];
-            score = __float_as_uint(maxsim_from_orderable((uint32_t)(x >> 32)));
+            score = __float_as_uint(from_orderable((uint32_t)(x >> 32)));
         }
         a.out_ids[q * k + o] = id;
         reinterpret_cast<uint32_t*>(a.out_score)[q * k + o] = score;
@@ -267,7 +267,7 @@ inline void fused_raise_lds(uint32_t T, uint32_t C, int device) {
 // are in place.  scan() alone is what the pass timer brackets.
 inline void fused_union(const FusedArgs& a, uint32_t n, int device, hipStream_t st) {
     fused_raise_lds(a.T, a.C, device);
-    hipLaunchKernelGGL(fused_union_kernel, dim3(n), dim3(kMaxsimThreads), fused_union_lds(a.T, a.C), st, a);
+    hipLaunchKernelGGL(fused_union_kernel, dim3(n), dim3(kWgSortThreads), fused_union_lds(a.T, a.C), st, a);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -280,7 +280,7 @@ inline void fused_scan(const FusedArgs& a, uint32_t n, hipStream_t st) {
 
 inline void fused_select(const FusedArgs& a, uint32_t n, int device, hipStream_t st) {
     fused_raise_lds(a.T, a.C, device);
-    hipLaunchKernelGGL(fused_select_kernel, dim3(n), dim3(kMaxsimThreads), fused_select_lds(a.T, a.C), st, a);
+    hipLaunchKernelGGL(fused_select_kernel, dim3(n), dim3(kWgSortThreads), fused_select_lds(a.T, a.C), st, a);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -20,11 +20,6 @@
 //   write    the first min(k, segments) words are the answer: key, score, hits per slot, and rows [k][T] with one
 //            thread per (slot, token), which finds its run head by bisection over the segment's tokens.  Every output
 //            slot is written here, padding included; nothing depends on a memset.
-// Bank conflicts of the sort (cdna_hip_programming.md, LDS): a compare-exchange at distance j >= 64 reads and writes 64-bit
-// words at consecutive addresses across each half wave (32 x 8 B = the 256-B bank row), conflict-free.  At j < 64 the same
-// mapping would put the lanes l and l + 16 of a half wave on one bank (2-way), so those steps never touch LDS: every lane
-// holds one element of a 64-element tile and exchanges it with lane ^ j by shuffle.  All lengths up to 64 are one such
-// pass, and every longer length ends in one; a wave works on four tiles at a time, four independent shuffle chains.
 // LDS (maxsim_lds_bytes, sized by the actual power of two): 17 bytes per element of P plus 580: 1.6 KiB at P = 64,
 // 35 KiB at P = 2,048 (T = 32, C = 64), 137 KiB at P = 8,192, which leaves one workgroup per CU.
 #pragma once
@@ -34,6 +29,7 @@
 #include <cstdint>
 
 #include "device_buf.h"
+#include "device_wg_primitives.h"
 #include "host_maxsim.h"
 
 namespace cph {
@@ -53,82 +49,19 @@ struct MaxsimArgs {
     int32_t* out_found;                   // [n]
 };
 
-constexpr uint32_t kMaxsimThreads = 256;
-constexpr unsigned long long kMaxsimNone = ~0ull;
+constexpr uint32_t kMaxsimThreads = kWgSortThreads;
 
-__host__ __device__ inline uint32_t maxsim_sort_len(uint32_t entries) {
-    uint32_t p = 64;
-    while (p < entries) p *= 2;
-    return p;
-}
 // words u64 [P] | run distance f32 [P] | run position u16 [P] | segment's first run u16 [P + 2] | run token u8 [P] |
 // floors f32 [64] | last valid position i32 [64] | counters u32 [16]
 inline size_t maxsim_lds_bytes(uint32_t T, uint32_t C) {
-    const size_t P = maxsim_sort_len(T * C);
+    const size_t P = wg_sort_len(T * C);
     return P * 8 + P * 4 + P * 2 + (P + 2) * 2 + P + 64 * 4 + 64 * 4 + 16 * 4;
-}
-
-__device__ __forceinline__ uint32_t maxsim_orderable(float s) {
-    const uint32_t u = __float_as_uint(s);
-    return u ^ ((u & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float maxsim_from_orderable(uint32_t v) {
-    return __uint_as_float((v & 0x80000000u) ? (v ^ 0x80000000u) : ~v);
-}
-
-// One compare-exchange step at distance j < 64 of the element at index i, held by this lane (lane = i & 63).
-__device__ __forceinline__ unsigned long long maxsim_lane_step(unsigned long long a, uint32_t i, uint32_t j, uint32_t len) {
-    const unsigned long long b = __shfl_xor(a, (int)j);
-    const bool keep_min = ((i & j) == 0) == ((i & len) == 0);
-    return keep_min ? (a < b ? a : b) : (a < b ? b : a);
-}
-
-// The steps at distances first_j, first_j / 2, ... 1 of the merges of length len_lo, 2 len_lo, ... len_hi (each merge starts
-// at min(first_j, its length / 2)) on every 64-element tile of w[0, P).  A wave holds four tiles at a time, one element per
-// lane each: the four shuffle chains are independent, which hides the latency of one behind the others.
-__device__ __forceinline__ void maxsim_lane_pass(unsigned long long* w, uint32_t P, uint32_t tid, uint32_t len_lo, uint32_t len_hi,
-                                                 uint32_t first_j) {
-    constexpr uint32_t kTiles = 4;
-    for (uint32_t base = tid; base < P; base += kTiles * kMaxsimThreads) {      // (base & ~63 is the same in a whole wave)
-        unsigned long long a[kTiles];
-#pragma unroll
-        for (uint32_t u = 0; u < kTiles; ++u) a[u] = base + u * kMaxsimThreads < P ? w[base + u * kMaxsimThreads] : kMaxsimNone;
-        for (uint32_t len = len_lo; len <= len_hi; len <<= 1)
-            for (uint32_t j = (len >> 1) < first_j ? (len >> 1) : first_j; j; j >>= 1) {
-#pragma unroll
-                for (uint32_t u = 0; u < kTiles; ++u) a[u] = maxsim_lane_step(a[u], base + u * kMaxsimThreads, j, len);
-            }
-#pragma unroll
-        for (uint32_t u = 0; u < kTiles; ++u)
-            if (base + u * kMaxsimThreads < P) w[base + u * kMaxsimThreads] = a[u];
-    }
-}
-
-// Ascending bitonic sort of w[0, P), P a power of two >= 64, by the whole workgroup; ends with a barrier.
-__device__ inline void maxsim_sort(unsigned long long* w, uint32_t P, uint32_t tid) {
-    maxsim_lane_pass(w, P, tid, 2, 64, 32);
-    __syncthreads();
-    for (uint32_t len = 128; len <= P; len <<= 1) {
-        for (uint32_t j = len >> 1; j >= 64; j >>= 1) {
-            for (uint32_t p = tid; p < P / 2; p += kMaxsimThreads) {
-                const uint32_t lo = 2 * p - (p & (j - 1)), hi = lo + j;
-                const unsigned long long a = w[lo], b = w[hi];
-                if ((a > b) == ((lo & len) == 0)) {
-                    w[lo] = b;
-                    w[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-        maxsim_lane_pass(w, P, tid, len, len, 32);
-        __syncthreads();
-    }
 }
 
 // Grid n, kMaxsimThreads threads; LDS: maxsim_lds_bytes(T, C).
 __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const uint32_t T = a.T, C = a.C, k = a.k, Pmax = maxsim_sort_len(T * C);
+    const uint32_t T = a.T, C = a.C, k = a.k, Pmax = wg_sort_len(T * C);
     unsigned long long* w = reinterpret_cast<unsigned long long*>(smem);
     float* rd = reinterpret_cast<float*>(w + Pmax);
     uint16_t* rh = reinterpret_cast<uint16_t*>(rd + Pmax);
@@ -146,13 +79,13 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
         const int32_t l = a.n_tokens[q];
         L = l < 1 ? 1u : ((uint32_t)l > T ? T : (uint32_t)l);
     }
-    const uint32_t E = L * C, P = maxsim_sort_len(E);
+    const uint32_t E = L * C, P = wg_sort_len(E);
 
     // load
     if (tid < 64) last[tid] = -1;
     __syncthreads();
     for (uint32_t e = tid; e < P; e += kMaxsimThreads) {
-        unsigned long long word = kMaxsimNone;
+        unsigned long long word = kSortNone;
         if (e < E) {
             const int64_t id = qi[e];
             if (id >= 0 && (unsigned long long)id < a.n_ids) {
@@ -172,7 +105,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
     __syncthreads();
     if (tid < L) fl[tid] = last[tid] >= 0 ? qd[tid * C + (uint32_t)last[tid]] : 0.0f;
 
-    maxsim_sort(w, P, tid);
+    wg_sort(w, P, tid);
 
     // compact: wave v owns [v * span, (v + 1) * span) of the sorted words
     const uint32_t span = P / 4 < 64 ? 64 : P / 4;
@@ -181,8 +114,8 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
     uint32_t runs = 0, segs = 0;
     for (uint32_t base = w_lo; base < w_hi; base += 64) {
         const uint32_t i = base + lane;
-        const unsigned long long x = w[i], pv = i ? w[i - 1] : kMaxsimNone;
-        const bool valid = x != kMaxsimNone;
+        const unsigned long long x = w[i], pv = i ? w[i - 1] : kSortNone;
+        const bool valid = x != kSortNone;
         const bool seg = valid && (i == 0 || (uint32_t)(pv >> 32) != (uint32_t)(x >> 32));
         const bool run = valid && (seg || ((uint32_t)pv >> 16) != ((uint32_t)x >> 16));
         runs += (uint32_t)__popcll(__ballot(run));
@@ -201,8 +134,8 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
     const uint32_t n_runs = cnt[0] + cnt[1] + cnt[2] + cnt[3], n_segs = cnt[4] + cnt[5] + cnt[6] + cnt[7];
     for (uint32_t base = w_lo; base < w_hi; base += 64) {
         const uint32_t i = base + lane;
-        const unsigned long long x = w[i], pv = i ? w[i - 1] : kMaxsimNone;
-        const bool valid = x != kMaxsimNone;
+        const unsigned long long x = w[i], pv = i ? w[i - 1] : kSortNone;
+        const bool valid = x != kSortNone;
         const bool seg = valid && (i == 0 || (uint32_t)(pv >> 32) != (uint32_t)(x >> 32));
         const bool run = valid && (seg || ((uint32_t)pv >> 16) != ((uint32_t)x >> 16));
         const unsigned long long run_m = __ballot(run), seg_m = __ballot(seg);
@@ -221,9 +154,9 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
     __syncthreads();                                      // (also: nobody reads the sorted words any more)
 
     // score
-    const uint32_t P2 = maxsim_sort_len(n_segs);
+    const uint32_t P2 = wg_sort_len(n_segs);
     for (uint32_t s = tid; s < P2; s += kMaxsimThreads) {
-        unsigned long long word = kMaxsimNone;
+        unsigned long long word = kSortNone;
         if (s < n_segs) {
             uint32_t r = sf[s];
             const uint32_t r_end = sf[s + 1];
@@ -233,14 +166,14 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
                 if (r < r_end && rt[r] == t) term = rd[r++];
                 sum = __fadd_rn(sum, term);
             }
-            word = ((unsigned long long)maxsim_orderable(sum) << 32) | s;
+            word = ((unsigned long long)orderable(sum) << 32) | s;
         }
         w[s] = word;
     }
     __syncthreads();
 
     // select
-    maxsim_sort(w, P2, tid);
+    wg_sort(w, P2, tid);
 
     // write
     const uint32_t found = k < n_segs ? k : n_segs;
@@ -253,7 +186,7 @@ __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rows_kernel(MaxsimArgs 
             const uint32_t s = (uint32_t)x, r = sf[s];
             key = a.key_of[qi[rh[r]]];
             hits = (int32_t)(sf[s + 1] - r);
-            score = __float_as_uint(maxsim_from_orderable((uint32_t)(x >> 32)));
+            score = __float_as_uint(from_orderable((uint32_t)(x >> 32)));
         }
         a.out_keys[q * k + o] = key;
         reinterpret_cast<uint32_t*>(a.out_score)[q * k + o] = score;

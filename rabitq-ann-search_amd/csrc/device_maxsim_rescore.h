@@ -13,7 +13,7 @@
 //            per token in finish(), which also forms the sequential float32 sum.  LDS: 512 bytes per token, 32 KiB at T = 64.
 //            (A wave reduction per take would cost six 64-bit exchange steps per token and 64 candidates, about a quarter of
 //            the 128 FMAs a D = 128 pair costs; the LDS words cost three instructions.)
-//   select   maxsim_rescore_select_kernel: one 256-thread workgroup per query.  Two bitonic sorts in LDS (maxsim_sort) over
+//   select   maxsim_rescore_select_kernel: one 256-thread workgroup per query.  Two bitonic sorts in LDS (wg_sort) over
 //            the power of two >= max(found, 64): by (key ^ 0x80000000, slot), which ranks the keys, then by
 //            (score bits, key rank, slot).  It writes all six outputs, padding included, rows through the row map if asked,
 //            and certified from lb_{R-1}.  LDS: 10 bytes per sorted element, 10 KiB at R = 1,024.
@@ -25,6 +25,7 @@
 
 #include "device_exact.h"
 #include "device_maxsim.h"
+#include "device_wg_primitives.h"
 #include "host_maxsim_rescore.h"
 
 namespace cph {
@@ -146,31 +147,31 @@ __global__ __launch_bounds__(64) void maxsim_rescore_scan_kernel(MaxsimRescoreAr
 }
 
 // words u64 [P] | key rank u16 [P]
-inline size_t maxsim_rescore_select_lds(uint32_t R) { return (size_t)maxsim_sort_len(R) * 10; }
+inline size_t maxsim_rescore_select_lds(uint32_t R) { return (size_t)wg_sort_len(R) * 10; }
 
 // Grid n, kMaxsimThreads threads; LDS: maxsim_rescore_select_lds(R).
 __global__ __launch_bounds__(kMaxsimThreads) void maxsim_rescore_select_kernel(MaxsimRescoreArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t T = a.T, R = a.R, k = a.k, tid = threadIdx.x;
     unsigned long long* w = reinterpret_cast<unsigned long long*>(smem);
-    uint16_t* rank = reinterpret_cast<uint16_t*>(w + maxsim_sort_len(R));
+    uint16_t* rank = reinterpret_cast<uint16_t*>(w + wg_sort_len(R));
     const size_t q = blockIdx.x;
     const int32_t fr = a.cand_found[q];
     const uint32_t f = fr < 0 ? 0u : ((uint32_t)fr > R ? R : (uint32_t)fr);
-    const uint32_t L = maxsim_rescore_live(a, q), P = maxsim_sort_len(f);
+    const uint32_t L = maxsim_rescore_live(a, q), P = wg_sort_len(f);
     const int32_t* __restrict__ ck = a.cand_keys + q * R;
     const uint32_t* __restrict__ sc = reinterpret_cast<const uint32_t*>(a.sc_score) + q * R;
 
     for (uint32_t s = tid; s < P; s += kMaxsimThreads)
-        w[s] = s < f ? ((unsigned long long)((uint32_t)ck[s] ^ 0x80000000u) << 32) | s : kMaxsimNone;
+        w[s] = s < f ? ((unsigned long long)((uint32_t)ck[s] ^ 0x80000000u) << 32) | s : kSortNone;
     __syncthreads();
-    maxsim_sort(w, P, tid);
+    wg_sort(w, P, tid);
     for (uint32_t p = tid; p < f; p += kMaxsimThreads) rank[(uint32_t)w[p]] = (uint16_t)p;
     __syncthreads();
     for (uint32_t s = tid; s < P; s += kMaxsimThreads)
-        w[s] = s < f ? ((unsigned long long)sc[s] << 32) | ((uint32_t)rank[s] << 16) | s : kMaxsimNone;
+        w[s] = s < f ? ((unsigned long long)sc[s] << 32) | ((uint32_t)rank[s] << 16) | s : kSortNone;
     __syncthreads();
-    maxsim_sort(w, P, tid);
+    wg_sort(w, P, tid);
 
     const uint32_t found = k < f ? k : f;
     if (tid == 0) {

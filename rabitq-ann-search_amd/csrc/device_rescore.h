@@ -16,12 +16,12 @@
 //     w[P2]                 the sort words, P2 = the power of two >= max(C, 64): (sign-folded score << 32) | id
 //     qv[padded]            the full query as float32, zeros behind dim_full: read from global memory once
 //     c_id[C]               per row position: the internal id, kNoId for padding, an id beyond the object, or a repeat
-//     tab_id[H], tab_pos[H] device_diverse.h's hash table over the row's ids: an id's slot keeps its lowest position
+//     tab_id[H], tab_pos[H] the first-position id table (device_wg_primitives.h): an id's slot keeps its lowest position
 // The 256 / G groups take candidates group, group + 256 / G, ...; a group works on kRescoreUnroll candidates at a time
 // with one accumulator each, so a lane has that many independent 16-byte row loads in flight per step (G = 64 at 2 KiB
 // rows: 4 x 1 KiB per wave-instruction, 16 KiB per workgroup).  A lane whose candidate is no candidate loads nothing and
 // adds zeros: the butterflies run in uniform control flow.  Lane 0 of the group turns the dot into the score and writes
-// the sort word; maxsim_sort (device_maxsim.h) sorts them; thread t < k writes output slot t -- every slot is written.
+// the sort word; wg_sort (device_wg_primitives.h) sorts them; thread t < k writes output slot t -- every slot is written.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -30,12 +30,12 @@
 
 #include "device_buf.h"
 #include "device_diverse.h"
-#include "device_maxsim.h"
+#include "device_wg_primitives.h"
 #include "host_rescore.h"
 
 namespace cph {
 
-constexpr uint32_t kRescoreThreads = kMaxsimThreads;      // (maxsim_sort is written for this workgroup)
+constexpr uint32_t kRescoreThreads = kWgSortThreads;
 constexpr uint32_t kRescoreUnroll = 4;
 
 struct RescoreStore {
@@ -59,7 +59,7 @@ struct RescoreArgs {
 };
 
 inline size_t rescore_lds_bytes(uint32_t C, uint32_t padded) {
-    return (size_t)maxsim_sort_len(C) * 8 + (size_t)padded * 4 + ((size_t)C + 2 * (size_t)diverse_table_slots(C)) * 4;   // at most 60 KiB
+    return (size_t)wg_sort_len(C) * 8 + (size_t)padded * 4 + ((size_t)C + 2 * (size_t)diverse_table_slots(C)) * 4;   // at most 60 KiB
 }
 
 __device__ __forceinline__ float rescore_fold(float p, uint32_t G) {
@@ -98,7 +98,7 @@ template <bool kF32>
 __global__ __launch_bounds__(kRescoreThreads) void rescore_rows_kernel(RescoreArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr uint32_t E = kF32 ? 4u : 8u;
-    const uint32_t C = a.C, k = a.k, P2 = maxsim_sort_len(C), H = diverse_table_slots(C);
+    const uint32_t C = a.C, k = a.k, P2 = wg_sort_len(C), H = diverse_table_slots(C);
     const uint32_t G = a.s.G, pieces = a.s.pieces, padded = a.s.padded;
     unsigned long long* w = reinterpret_cast<unsigned long long*>(smem);
     float* qv = reinterpret_cast<float*>(w + P2);
@@ -112,35 +112,22 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_rows_kernel(RescoreAr
     const float* __restrict__ fq = a.fq + q * a.s.dim;
 
     for (uint32_t i = tid; i < padded; i += kRescoreThreads) qv[i] = i < a.s.dim ? fq[i] : 0.0f;
-    for (uint32_t s = tid; s < H; s += kRescoreThreads) {
-        tab_id[s] = kNoId;
-        tab_pos[s] = kNoId;
-    }
-    for (uint32_t j = tid; j < P2; j += kRescoreThreads) w[j] = kMaxsimNone;
+    for (uint32_t s = tid; s < H; s += kRescoreThreads) id_table_clear(tab_id, tab_pos, s);
+    for (uint32_t j = tid; j < P2; j += kRescoreThreads) w[j] = kSortNone;
     __syncthreads();
-    // the candidates: an id's first position in the row (device_diverse.h)
+    // the candidates: an id's first position in the row
     for (uint32_t j = tid; j < C; j += kRescoreThreads) {
         const int64_t id64 = row_ids[j];
         const bool valid = id64 >= 0 && (unsigned long long)id64 < a.s.n_ids;
         const uint32_t id = valid ? (uint32_t)id64 : kNoId;
         c_id[j] = id;
-        if (valid) {
-            uint32_t s = (id * 2654435761u) & (H - 1);
-            for (;;) {                                    // (the table has at least C free slots: the probe ends)
-                const uint32_t old = atomicCAS(&tab_id[s], kNoId, id);
-                if (old == kNoId || old == id) break;
-                s = (s + 1) & (H - 1);
-            }
-            atomicMin(&tab_pos[s], j);
-        }
+        if (valid) id_table_insert(tab_id, tab_pos, H, id, j);
     }
     __syncthreads();
     for (uint32_t j = tid; j < C; j += kRescoreThreads) {
         const uint32_t id = c_id[j];
         if (id == kNoId) continue;
-        uint32_t s = (id * 2654435761u) & (H - 1);
-        while (tab_id[s] != id) s = (s + 1) & (H - 1);
-        if (tab_pos[s] != j) c_id[j] = kNoId;             // a repeat
+        if (tab_pos[id_table_find(tab_id, H, id)] != j) c_id[j] = kNoId;      // a repeat
     }
     __syncthreads();
 
@@ -184,28 +171,27 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_rows_kernel(RescoreAr
                 const float v = __fsub_rn(__fadd_rn(qn, a.s.norms[id[u]]), __fmul_rn(2.0f, dot));
                 score = (v < 0.0f) ? 0.0f : v;
             }
-            if (score == score) w[base + u * groups + grp] = ((unsigned long long)maxsim_orderable(score) << 32) | id[u];
+            if (score == score) w[base + u * groups + grp] = ((unsigned long long)orderable(score) << 32) | id[u];
         }
     }
     __syncthreads();
-    maxsim_sort(w, P2, tid);
+    wg_sort(w, P2, tid);
 
     int64_t* __restrict__ out_ids = a.out_ids + q * k;
     uint32_t* __restrict__ out_score = reinterpret_cast<uint32_t*>(a.out_score) + q * k;
     uint32_t* __restrict__ out_first = reinterpret_cast<uint32_t*>(a.out_first) + q * k;
     for (uint32_t t = tid; t < k; t += kRescoreThreads) {
         const unsigned long long word = w[t];             // (k <= C <= P2)
-        if (word == kMaxsimNone) {
+        if (word == kSortNone) {
             out_ids[t] = -1;
             out_score[t] = 0x7F7FFFFFu;                   // FLT_MAX
             out_first[t] = 0x7F7FFFFFu;
             continue;
         }
         const uint32_t id = (uint32_t)word;
-        uint32_t s = (id * 2654435761u) & (H - 1);
-        while (tab_id[s] != id) s = (s + 1) & (H - 1);
+        const uint32_t s = id_table_find(tab_id, H, id);
         out_ids[t] = (int64_t)(a.rows ? a.rows[id] : id);
-        out_score[t] = __float_as_uint(maxsim_from_orderable((uint32_t)(word >> 32)));
+        out_score[t] = __float_as_uint(from_orderable((uint32_t)(word >> 32)));
         out_first[t] = row_dist[tab_pos[s]];
     }
 }

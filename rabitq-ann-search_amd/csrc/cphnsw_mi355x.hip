@@ -1983,11 +1983,22 @@ static void refuse_ip(const cph_index* h, const char* what) {
         throw InvalidArg(std::string(what) + " is not available under the inner-product (ip) metric");
 }
 
+// The encoder carries kMaxUpperLayers layer descriptors.  A file that uses more would be descended from layer
+// kMaxUpperLayers starting at the file's entry vertex, where the reference starts at max_level: another walk, with no
+// error.  Refused before the handle gives up its index.
+static void refuse_deep_layers(const HostIndex& t) {
+    const long long usable = std::min<long long>((long long)t.upper.size(), t.max_level);
+    if (usable > kMaxUpperLayers)
+        throw std::runtime_error("Index file uses " + std::to_string(usable) + " upper layers; the descent supports at most " +
+                                 std::to_string(kMaxUpperLayers) + " (kMaxUpperLayers).");
+}
+
 static void load_v2(cph_index* h, const char* path) {
     std::lock_guard<std::mutex> lk(h->mu);
     refuse_metric_file(h, "load");
     HostIndex t;
     t.load(path, h->D, h->bits, h->dim);        // a file that fails to parse leaves the handle as it was
+    refuse_deep_layers(t);                      // (... and so does one with more layers than the descent has)
     begin_device_swap(h);
     h->host = std::move(t);
     drop_host_state(h);
@@ -2064,6 +2075,7 @@ static void read_native_for(const cph_index* h, const char* path, NativeLoaded& 
     if (metric != h->metric)
         throw InvalidArg(std::string("the file holds ") + metric_name(metric) + " rows and this handle's metric is " +
                          metric_name(h->metric) + ": load it into an index created with the file's metric");
+    refuse_deep_layers(out.t);
 }
 
 // The handle gives up its index for the one in `in` (which is consumed).

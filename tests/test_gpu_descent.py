@@ -13,8 +13,8 @@ What the cases reach in the kernel (asserted from the saved file, `upper_layers`
   * d960b4      D = 1024: the paired hop's loop over 64-element parts with carried accumulators.
   * d48b4       D = 64: not a multiple of 128, so mapped layers take the eight-lanes-per-neighbour loop.
 The builder's upper layers never hold more than 32 neighbours per vertex (asserted below for every case).  The hop for
-33..62 neighbours of a mapped layer is therefore not reached by any index built here; it is the loop the D = 64 case
-runs, entered on a wave-uniform branch, and no file is hand-made to reach it.
+33..62 neighbours of a mapped layer, the unmapped fallback and the other dimensions are reached on hand-made layers:
+tests/test_gpu_descent_shapes.py.
 """
 import ctypes as C
 import os

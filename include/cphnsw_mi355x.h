@@ -762,6 +762,54 @@ int cph_has_column(cph_index* h, uint32_t slot, int* flag);
 int cph_get_column(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, int32_t* out);
 int cph_filters_from_column(cph_index* h, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out);
 
+/* ---- tag columns -------------------------------------------------------------------------- */
+/* Set-valued attributes (the groups allowed to read a document, the topics of a chunk, the languages of a page): up to
+ * CPH_MAX_TAG_COLUMNS columns, addressed by slot, each giving every row a SET of int32 tags (possibly empty).  A column is
+ * resident on the device in internal-id order as a CSR: lims[n + 1] (uint32, lims[0] = 0) and tags[lims[n]], ascending
+ * and distinct inside a row (4 (n + 1) + 4 nnz bytes).  A tag test is a set V of int32 values and a mode; with c(row)
+ * the number of the row's tags that are in V it allows the row when
+ *   CPH_TAGS_ANY   c > 0          CPH_TAGS_ALL   c == |V|          CPH_TAGS_NONE   c == 0
+ * (both sides are distinct, so `all` by count is exact).  An empty V: nothing for any, every row for all and none; a
+ * row without tags passes none, and all only for an empty V.  Tags compare as int32: INT32_MIN and INT32_MAX are
+ * ordinary tags.
+ *
+ * cph_set_tags     lims[n + 1]: a non-decreasing CSR from 0 (64-bit on this side), n == size; tags[lims[n]] (may be
+ *                  NULL when lims[n] == 0).  Rows in internal ids or input rows (`space`, as in cph_set_labels; the
+ *                  host gathers input rows to internal order through the row map).  The rows may hold duplicates and
+ *                  be unsorted: the host sorts and dedups every row before the upload.  lims == NULL drops the slot.
+ *                  CPH_INVALID_ARGUMENT: slot >= CPH_MAX_TAG_COLUMNS, n != size, a lims that does not start at 0 or
+ *                  decreases, more than CPH_MAX_TAGS_PER_ROW distinct tags in a row, 2^32 tags or more after dedup,
+ *                  a handle that is not finalized, a borrowed replica or part handle.
+ * cph_get_tags     the canonical rows of internal ids [first, first + count): lims_out[count + 1] rebased to 0 and
+ *                  tags_out[lims_out[count]]; tags_out == NULL asks for the limits only.
+ * cph_filters_from_tags   m tests at once, test j = values test_vals[test_lims[j] .. test_lims[j + 1]) (any order,
+ *                  duplicates allowed: canonicalised on the host) under modes[j].  One upload of the tests, zeroed
+ *                  counters, ONE launch over the column (csrc/device_tags.h), one copy back of the counts, one wait; the
+ *                  m bitmaps share one slab at a 256 B-aligned stride, as in cph_filters_from_labels, and come out as
+ *                  ordinary cph_filter objects (all made, or none).  m == 0 is a no-op.  CPH_INVALID_ARGUMENT: no
+ *                  column in the slot, a mode above CPH_TAGS_NONE, more than CPH_MAX_TAG_TEST_VALUES distinct values
+ *                  in a test, m above 65,535 x 64.  Allowed on a borrowed replica or part handle.
+ * lifetime         exactly that of the attribute columns: cph_build, cph_load and cph_load_native drop every tag
+ *                  column (no file carries them); cph_remove, cph_set_row_map and cph_set_result_ids leave them;
+ *                  cph_compact carries them (the live rows' CSR is gathered again on the host); replicas copy them;
+ *                  cph_add on a handle that holds a tag column is CPH_INVALID_ARGUMENT.  An index that never called
+ *                  cph_set_tags allocates and launches nothing for them. */
+enum { CPH_MAX_TAG_COLUMNS = 4, CPH_MAX_TAGS_PER_ROW = 1024, CPH_MAX_TAG_TEST_VALUES = 64 };
+enum { CPH_TAGS_ANY = 0, CPH_TAGS_ALL = 1, CPH_TAGS_NONE = 2 };
+int cph_set_tags(cph_index* h, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space);
+int cph_has_tags(cph_index* h, uint32_t slot, int* flag);
+int cph_get_tags(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, uint64_t* lims_out, int32_t* tags_out);
+int cph_filters_from_tags(cph_index* h, uint32_t slot, const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes,
+                          uint32_t m, cph_filter** out);
+/* Debug hooks of the measurement script (scripts/tag_filter_sweep.py), as cph_debug_time_label_filters: while on, every
+ * cph_filters_from_tags pass of this handle (the memset of the counts and the kernel) is bracketed by two HIP events. */
+int cph_debug_time_tag_filters(cph_index* h, int on);
+int cph_debug_last_tag_filters_us(cph_index* h, double* us);
+/* Host statement of cph_set_tags + cph_filters_from_tags (no HIP call): the column and the tests are canonicalised with
+ * the same refusals, then words_out[m][(n + 31) / 32] and counts_out[m]. */
+int cph_host_tag_filters(const uint32_t* lims, const int32_t* tags, uint64_t n, const uint32_t* test_lims, const int32_t* test_vals,
+                         const uint8_t* modes, uint32_t m, uint32_t* words_out, uint64_t* counts_out);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);
@@ -1017,6 +1065,14 @@ int cph_parts_filter_count(const cph_parts_filter* f, uint64_t* count);
 int cph_multi_set_column(cph_multi* m, uint32_t slot, const int32_t* values, uint64_t n, int space);
 int cph_parts_set_column(cph_parts* m, uint32_t slot, const int32_t* values, uint64_t n);
 int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out);
+
+/* The tag columns (cph_set_tags) of replicas and parts, as the column calls above: one slot on every replica (the
+ * canonical column is made once); lims[n + 1] / tags over GLOBAL input rows, cut at the part bounds with the limits
+ * rebased; every part evaluates its own slice.  cph_multi_compact and cph_parts_compact carry the columns. */
+int cph_multi_set_tags(cph_multi* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space);
+int cph_parts_set_tags(cph_parts* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n);
+int cph_parts_filters_from_tags(cph_parts* m, uint32_t slot, const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes,
+                                uint32_t cnt, cph_parts_filter** out);
 int cph_parts_filters_combine(int op, const cph_parts_filter* const* a, uint32_t m, const cph_parts_filter* const* b, uint32_t n_b,
                               cph_parts_filter** out);
 int cph_parts_num_parts(cph_parts* m, uint32_t* n);

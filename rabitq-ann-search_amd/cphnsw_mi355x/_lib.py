@@ -190,6 +190,17 @@ SYMBOLS = {
     "cph_multi_set_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int]),
     "cph_parts_set_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     "cph_parts_filters_from_column": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_set_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_has_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    "cph_get_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cph_filters_from_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_debug_time_tag_filters": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_tag_filters_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_host_tag_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p]),
+    "cph_multi_set_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
+    "cph_parts_set_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cph_parts_filters_from_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cph_synchronize": (C.c_int, [C.c_void_p]),
     "cph_set_batch_sets": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,

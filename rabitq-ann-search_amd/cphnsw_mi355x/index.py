@@ -343,6 +343,7 @@ class CPIndex:
         self._result_ids = "internal"
         self._exact_threshold = 0
         self._columns = {}           # attribute columns (set_column): name -> slot on the handle
+        self._tag_columns = {}       # tag columns (set_tags): name -> slot on the handle
         if metric not in self._METRICS:
             raise ValueError(f'metric must be "l2", "cosine" or "ip", not {metric!r}')
         self._metric = metric
@@ -508,6 +509,7 @@ class CPIndex:
         v._result_ids = "input" if self.is_finalized else "internal"
         v._exact_threshold = self._exact_threshold
         v._columns = {}
+        v._tag_columns = {}
         return v
 
     def _need_parts(self, what):
@@ -761,22 +763,28 @@ class CPIndex:
         hi = lo if hi is None else self._as_labels(hi, what).ravel()
         if hi.shape != lo.shape:
             raise ValueError("lo and hi must have the same length")
-        m, L, n = lo.size, _lib.lib(), self.size
+        L = _lib.lib()
+        col = () if slot is None else (slot,)
+        return self._column_pass(L.cph_filters_from_labels if slot is None else L.cph_filters_from_column,
+                                 L.cph_parts_filters_from_labels if slot is None else L.cph_parts_filters_from_column,
+                                 (*col, lo.ctypes.data, hi.ctypes.data), lo.size)
+
+    def _column_pass(self, make, make_parts, args, m):
+        """[IdFilter] of one device pass over a column: make(handle, *args, m, out) on every replica, or make_parts on a
+        partitioned index; the counts are filled in, and what was made before a failure is destroyed."""
+        L, n = _lib.lib(), self.size
         if m == 0:
             return []
-        col = () if slot is None else (slot,)
         if self._p is not None:
             out = (C.c_void_p * m)()
-            make = L.cph_parts_filters_from_labels if slot is None else L.cph_parts_filters_from_column
-            _lib.check(make(self._p, *col, lo.ctypes.data, hi.ctypes.data, m, out))
+            _lib.check(make_parts(self._p, *args, m, out))
             fs = [IdFilter._adopt(n, 0, pf=C.c_void_p(out[j]), parts=len(self._devices)) for j in range(m)]
             return self._with_counts(fs, lambda f, c: L.cph_parts_filter_count(f._pf, c))
         per_rep = []
-        make = L.cph_filters_from_labels if slot is None else L.cph_filters_from_column
         try:
             for rh in self._replicas():
                 out = (C.c_void_p * m)()
-                _lib.check(make(rh, *col, lo.ctypes.data, hi.ctypes.data, m, out))
+                _lib.check(make(rh, *args, m, out))
                 per_rep.append(out)
         except Exception:
             for out in per_rep:
@@ -872,6 +880,8 @@ class CPIndex:
             raise ValueError("a column name must be a non-empty string")
         if name == "label":
             raise ValueError('"label" names the label column: use set_labels')
+        if name in self._tag_slots():
+            raise ValueError(f"{name!r} names a tag column: columns and tag columns share one namespace")
         slots = self._column_slots()
         if values is None:
             if name in slots:
@@ -909,6 +919,170 @@ class CPIndex:
         """IdFilter of the rows whose value in column `name` is `lo`, or lies in [lo, hi] (both ends inclusive)."""
         return self.column_filters(name, [lo], None if hi is None else [hi])[0]
 
+    # -- tag columns: set-valued attributes (not in the reference) --------------------------------
+    MAX_TAG_COLUMNS = 4              # CPH_MAX_TAG_COLUMNS
+    MAX_TAGS_PER_ROW = 1024          # CPH_MAX_TAGS_PER_ROW
+    MAX_TAG_TEST_VALUES = 64         # CPH_MAX_TAG_TEST_VALUES
+    _TAG_MODES = {"any": 0, "all": 1, "none": 2}
+
+    def _tag_slots(self):
+        """name -> slot of the tag columns the handle still holds (build(), load() and load_native() drop them)."""
+        def has(h, slot):
+            f = C.c_int(0)
+            _lib.check(_lib.lib().cph_has_tags(h, slot, C.byref(f)))
+            return bool(f.value)
+        hs = self._part_handles if self._p is not None else [self._h]
+        for name, slot in list(self._tag_columns.items()):
+            if not all(has(h, slot) for h in hs):
+                del self._tag_columns[name]
+        return self._tag_columns
+
+    def _tag_slot(self, name):
+        slots = self._tag_slots()
+        if name not in slots:
+            raise ValueError(f"the index has no tag column {name!r}: call set_tags first")
+        return slots[name]
+
+    def _set_tag_slot(self, slot, lims, flat, code):
+        L = _lib.lib()
+        lp = None if lims is None else lims.ctypes.data
+        tp = None if flat is None or flat.size == 0 else flat.ctypes.data
+        n = 0 if lims is None else lims.size - 1
+        if self._p is not None:
+            _lib.check(L.cph_parts_set_tags(self._p, slot, lp, tp, n))
+        elif self._m is not None:
+            _lib.check(L.cph_multi_set_tags(self._m, slot, lp, tp, n, code))
+        else:
+            _lib.check(L.cph_set_tags(self._h, slot, lp, tp, n, code))
+
+    def set_tags(self, name, tags, lims=None, ids=None):
+        """A named tag column: a SET of integer tags per row (the groups allowed to read a document, the topics of a
+        chunk, the languages of a page), kept on the device as a CSR (4 B per row and 4 B per tag).  `tags` is a
+        sequence of `size` integer sequences (a row may be empty); or, with `lims` given, the flat integer array of a
+        CSR whose `lims` is [size + 1], starts at 0 and does not decrease.  Values must fit int32; the rows are indexed in
+        the space `ids` (default: result_ids).  Duplicates and any order inside a row are accepted: the column is stored
+        sorted and distinct (tags()).  At most MAX_TAGS_PER_ROW distinct tags per row and MAX_TAG_COLUMNS names, which
+        share one namespace with the attribute columns.  None drops the column and frees its name.  tag_filter(s) and
+        where() read it.  Lifecycle as for set_column: build(), load() and load_native() drop every tag column,
+        remove() and set_row_map() leave them, compact() carries them; add() on an index that holds one raises."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a tag column name must be a non-empty string")
+        if name == "label":
+            raise ValueError('"label" names the label column: use set_labels')
+        if name in self._column_slots():
+            raise ValueError(f"{name!r} names an attribute column: columns and tag columns share one namespace")
+        slots = self._tag_slots()
+        if tags is None:
+            if name in slots:
+                self._set_tag_slot(slots[name], None, None, _lib.IDS_INTERNAL)
+                del slots[name]
+            return
+        space = self._id_space(ids)
+        if lims is None:
+            rows = [np.asarray(r).ravel() for r in tags]
+            lims = np.zeros(len(rows) + 1, np.uint64)
+            if rows:
+                np.cumsum([r.size for r in rows], out=lims[1:])
+            filled = [r for r in rows if r.size]
+            flat = np.concatenate(filled) if filled else np.zeros(0, np.int32)
+        else:
+            la = np.asarray(lims)
+            if la.ndim != 1 or la.size == 0 or not np.issubdtype(la.dtype, np.integer) or (la.size and int(la.min()) < 0):
+                raise ValueError("lims must be a 1D array of non-negative integers")
+            lims = la.astype(np.uint64, order="C")
+            flat = np.asarray(tags).ravel()
+            if int(lims[-1]) != flat.size:
+                raise ValueError(f"lims ends at {int(lims[-1])}, tags holds {flat.size} values")
+        flat = self._as_labels(flat, "tags")
+        if lims.size != self.size + 1:
+            raise ValueError(f"a tag column has one row per index row: {lims.size - 1} rows given, the index holds {self.size}")
+        slot = slots.get(name)
+        if slot is None:
+            free = [s for s in range(self.MAX_TAG_COLUMNS) if s not in slots.values()]
+            if not free:
+                raise ValueError(f"an index holds at most {self.MAX_TAG_COLUMNS} tag columns: drop one first (set_tags(name, None))")
+            slot = free[0]
+        self._set_tag_slot(slot, lims, flat, _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL)
+        slots[name] = slot
+
+    @property
+    def tag_columns(self):
+        """Names of the tag columns the index holds (set_tags)."""
+        return list(self._tag_slots())
+
+    @staticmethod
+    def _tags_of(h, n, by_row, slot):
+        """(lims int64[n + 1], tags int32) of tag column `slot` of handle h: in internal ids, or by input row."""
+        L = _lib.lib()
+        lims = np.zeros(n + 1, np.uint64)
+        _lib.check(L.cph_get_tags(h, slot, 0, n, lims.ctypes.data, None))
+        vals = np.empty(int(lims[-1]), np.int32)
+        if vals.size:
+            _lib.check(L.cph_get_tags(h, slot, 0, n, lims.ctypes.data, vals.ctypes.data))
+        lims = lims.astype(np.int64)
+        if not by_row or n == 0:
+            return lims, vals
+        rows = np.empty(n, np.uint32)
+        _lib.check(L.cph_get_row_map(h, 0, n, rows.ctypes.data))
+        id_of_row = np.empty(n, np.int64)
+        id_of_row[rows] = np.arange(n)
+        lens = np.diff(lims)[id_of_row]
+        out = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=out[1:])
+        src = np.repeat(lims[:-1][id_of_row] - out[:-1], lens) + np.arange(int(out[-1]))
+        return out, vals[src]
+
+    def tags(self, name, ids=None):
+        """(lims int64[size + 1], tags int32[lims[-1]]): tag column `name` in its canonical form (every row ascending and
+        distinct), the rows indexed in the space `ids` (default: result_ids)."""
+        slot = self._tag_slot(name)
+        by_row = self._id_space(ids) == "input"
+        if self._p is None:
+            return self._tags_of(self._h, self.size, by_row, slot)
+        cut = [self._tags_of(h, hi - lo, by_row, slot) for h, (lo, hi) in zip(self._part_handles, self.parts)]
+        lims, at = [np.zeros(1, np.int64)], 0
+        for pl, _ in cut:
+            lims.append(pl[1:] + at)
+            at += int(pl[-1])
+        return np.concatenate(lims), np.concatenate([v for _, v in cut])
+
+    def tag_filters(self, name, tests, mode="any"):
+        """[IdFilter]: one filter per test on tag column `name`.  A test is an int (the row has this tag) or a sequence
+        of at most MAX_TAG_TEST_VALUES distinct ints V; `mode` -- one string, or one per test -- says how many of V a row
+        must hold: "any" (at least one), "all" (every one) or "none".  An empty V allows nothing under "any" and every
+        row under "all" and "none".  All filters are made in ONE pass over the column on the device, which also counts
+        them; they are ordinary filters (filter=, filter_of=, & | ~, removed rows, replicas and parts).  Per-query
+        permissions: fs = tag_filters("acl", groups_of_distinct_users); search_batch(q, k, filter=fs, filter_of=user)."""
+        slot = self._tag_slot(name)
+        tests = list(tests)
+        m = len(tests)
+        modes = [mode] * m if isinstance(mode, str) else list(mode)
+        if len(modes) != m or any(not isinstance(x, str) or x not in self._TAG_MODES for x in modes):
+            raise ValueError('mode must be "any", "all" or "none": one string, or one per test')
+        vals = [self._as_labels(t, "tag test values").ravel() for t in tests]
+        lims = np.zeros(m + 1, np.uint32)
+        if m:
+            np.cumsum([v.size for v in vals], out=lims[1:])
+        flat = np.concatenate(vals) if m else np.zeros(0, np.int32)
+        flat = np.ascontiguousarray(flat, np.int32)
+        codes = np.array([self._TAG_MODES[x] for x in modes], np.uint8)
+        L = _lib.lib()
+        return self._column_pass(L.cph_filters_from_tags, L.cph_parts_filters_from_tags,
+                                 (slot, lims.ctypes.data, flat.ctypes.data if flat.size else None, codes.ctypes.data), m)
+
+    def tag_filter(self, name, test, mode="any"):
+        """IdFilter of the rows that pass one test on tag column `name` (tag_filters)."""
+        return self.tag_filters(name, [test], mode)[0]
+
+    def time_tag_filters(self, on=True):
+        """Debug hook of the measurement script: while on, every tag pass is bracketed by HIP events (last_tag_filters_us)."""
+        self._time_pass("cph_debug_time_tag_filters", on)
+
+    def last_tag_filters_us(self):
+        """Device time (HIP events, microseconds) of the last tag_filters pass made under time_tag_filters(): the longest
+        of the replicas' / parts' passes."""
+        return max(self._last_pass_us("cph_debug_last_tag_filters_us", r) for r in range(len(self._replicas())))
+
     def combine_filters(self, op, filters, other=None):
         """[IdFilter]: filters[j] OP other, made and counted on the device in one pass (module function
         combine_filters): op "and" / "or" / "andnot" / "xor" with `other` one filter (combined with every filters[j]) or
@@ -918,13 +1092,26 @@ class CPIndex:
 
     def where(self, **tests):
         """IdFilter of the rows that pass every test: name=value (equality) or name=(lo, hi) (inclusive range) on the
-        column `name`; "label" names the label column.  Each test is one column pass, the AND runs on the device; the
-        intermediate filters are closed here."""
+        column `name`; "label" names the label column.  On a tag column (set_tags) name=7 means "has tag 7", and
+        name={"any": [...]}, {"all": [...]} or {"none": [...]} (one key) is that test; a (lo, hi) pair is a ValueError
+        there.  Each test is one column pass, the AND runs on the device; the intermediate filters are closed here."""
         if not tests:
             raise ValueError("where() needs at least one column test")
         made = []
         try:
+            tag_names = self._tag_slots()
             for name, t in tests.items():
+                if name in tag_names:
+                    if isinstance(t, dict):
+                        if len(t) != 1:
+                            raise ValueError(f'a tag test is {{"any" | "all" | "none": values}} with one key, got {t!r} for {name!r}')
+                        (mode, vals), = t.items()
+                        made.append(self.tag_filter(name, vals, mode))
+                    elif isinstance(t, (tuple, list)):
+                        raise ValueError(f'tag column {name!r} has no range test: give a tag or {{"any": [...]}}, got {t!r}')
+                    else:
+                        made.append(self.tag_filter(name, t))
+                    continue
                 lo, hi = t if isinstance(t, (tuple, list)) and len(t) == 2 else (t, None)
                 if isinstance(t, (tuple, list)) and len(t) != 2:
                     raise ValueError(f"a test is a value or a (lo, hi) pair, got {t!r} for {name!r}")

@@ -33,6 +33,7 @@
 #include "device_rows.h"
 #include "device_tombstone.h"
 #include "device_labels.h"
+#include "device_tags.h"
 #include "device_filter_ops.h"
 #include "device_exact.h"
 #include "device_range.h"
@@ -233,7 +234,7 @@ constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the 
 // inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
 // rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
 // same way.
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassUntimed, kPassKinds };
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassUntimed, kPassKinds };
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -321,6 +322,14 @@ struct cph_index {
     // the parts cut -- walks these slots too (column_of)
     DevBuf<int32_t> d_columns[kMaxColumns];
     bool has_column[kMaxColumns] = {};
+    // the tag columns (cph_set_tags): up to kMaxTagColumns set-valued columns, each a canonical CSR in internal-id order
+    // (host copies: host.tag_lims / host.tag_vals; d_tag_vals stays unallocated while a column holds no tag at all), with
+    // the lifecycle of the attribute columns, and the call buffers of cph_filters_from_tags (the tests and the counts),
+    // which only grow.  A handle that never saw cph_set_tags allocates none of this.
+    DevBuf<uint32_t> d_tag_lims[kMaxTagColumns], d_tag_tests;
+    DevBuf<int32_t> d_tag_vals[kMaxTagColumns];
+    DevBuf<unsigned long long> d_tag_counts;
+    bool has_tags[kMaxTagColumns] = {};
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
@@ -465,11 +474,33 @@ ColumnRef column_of(cph_index* h, int slot) {
 bool has_extra_columns(const cph_index* h) {
     return std::any_of(h->has_column, h->has_column + kMaxColumns, [](bool b) { return b; });
 }
+bool has_tag_columns(const cph_index* h) {
+    return std::any_of(h->has_tags, h->has_tags + kMaxTagColumns, [](bool b) { return b; });
+}
 
-// After the host index changed: the device copy of its label column and of every attribute column, or none (a load or
-// a build leaves none).
+// The device copy of tag column `slot`: lims[n + 1] and tags in internal-id order, or (lims null) none.  The caller has
+// made sure nothing reads the old one.
+void upload_tags(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_t* tags, uint64_t n) {
+    h->has_tags[slot] = lims != nullptr;
+    h->d_tag_lims[slot].release();
+    h->d_tag_vals[slot].release();
+    if (!lims) return;
+    h->d_tag_lims[slot].alloc(n + 1);
+    HIP_CHECK(hipMemcpy(h->d_tag_lims[slot].p, lims, (n + 1) * 4, hipMemcpyHostToDevice));
+    if (lims[n] == 0) return;                    // (no tag at all: the kernel gets a null base and never reads it)
+    h->d_tag_vals[slot].alloc(lims[n]);
+    HIP_CHECK(hipMemcpy(h->d_tag_vals[slot].p, tags, (size_t)lims[n] * 4, hipMemcpyHostToDevice));
+}
+
+// After the host index changed: the device copy of its label column, of every attribute column and of every tag column,
+// or none (a load or a build leaves none).
 void sync_labels(cph_index* h) {
     h->label_rows.reset();
+    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {
+        const std::vector<uint32_t>& lims = h->host.tag_lims[slot];
+        if (lims.empty() && !h->has_tags[slot]) continue;        // (an index without tags: nothing to do)
+        upload_tags(h, slot, lims.empty() ? nullptr : lims.data(), h->host.tag_vals[slot].data(), lims.empty() ? 0 : lims.size() - 1);
+    }
     for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
         const ColumnRef c = column_of(h, slot);
         c.has = !c.host.empty();
@@ -576,6 +607,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed rescored maxsim search has run on this handle (cph_debug_time_maxsim_rescore)",
     "no timed rescored search has run on this handle (cph_debug_time_rescored)",
     "no timed fused search has run on this handle (cph_debug_time_fused)",
+    "no timed tag pass has run on this handle (cph_debug_time_tag_filters)",
     "this pass is not timed",
 };
 
@@ -1859,7 +1891,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 115; }
+int cph_version(void) { return 116; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -3368,6 +3400,183 @@ int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo,
     });
 }
 
+}  // extern "C"
+
+// ---- tag columns and tag filters (device_tags.h) -----------------------------------------------
+// A set of int32 tags per row on the handle (a canonical CSR in internal-id order, resident); cph_filters_from_tags turns
+// any / all / none tests into ordinary cph_filter objects, many per device pass, so no search path learns anything new.
+namespace {
+
+void require_tag_slot(uint32_t slot) {
+    if (slot >= kMaxTagColumns) throw InvalidArg("tag column slot must be below " + std::to_string(kMaxTagColumns) + " (CPH_MAX_TAG_COLUMNS)");
+}
+
+void require_tags_target(const cph_index* h, bool set, uint64_t n) {
+    if (!h->finalized) throw InvalidArg("tags belong to a finalized index: finalize or load it first");
+    if (set && n != h->size())
+        throw InvalidArg("tag column has " + std::to_string(n) + " rows, the index holds " + std::to_string(h->size()));
+}
+
+// The caller holds the handle mutex.  lims / tags: the canonical column of n == size rows in internal-id order, or
+// (lims null) the column goes.  keep_host: also as host.tag_lims / tag_vals (what compact gathers from); a replica
+// without host arrays keeps the device copy only.
+void install_tags_locked(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_t* tags, uint64_t n, bool keep_host) {
+    h->use_device();
+    quiesce(h);
+    upload_tags(h, slot, lims, tags, n);
+    std::vector<uint32_t>().swap(h->host.tag_lims[slot]);
+    std::vector<int32_t>().swap(h->host.tag_vals[slot]);
+    if (lims && keep_host) {
+        h->host.tag_lims[slot].assign(lims, lims + n + 1);
+        h->host.tag_vals[slot].assign(tags, tags + lims[n]);
+    }
+}
+
+// cph_set_tags on a handle that keeps its host arrays: rows in internal ids, or in input rows (gathered to internal
+// order on the host, through host.rows); the rows are sorted and deduplicated on the way (tags_canonical_host).
+void set_tags(cph_index* h, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_tags_target(h, lims != nullptr, n);
+    if (!lims) {
+        if (h->has_tags[slot]) install_tags_locked(h, slot, nullptr, nullptr, 0, true);
+        return;
+    }
+    const uint64_t nb = h->host.n;
+    const bool by_row = space == CPH_IDS_INPUT;
+    if (by_row && (!h->has_rows || h->host.rows.size() != nb))
+        throw InvalidArg("the index has no row map (it was loaded from a v2 file): tags in input rows need cph_set_row_map");
+    std::vector<uint32_t> cl;
+    std::vector<int32_t> cv;
+    tags_canonical_host(lims, tags, n, by_row ? h->host.rows.data() : nullptr, nb, cl, cv);      // (a tail row is its own input row)
+    install_tags_locked(h, slot, cl.data(), cv.data(), n, true);
+}
+
+// cph_filters_from_tags: out[m] all made, or none.  The tests are canonical already.
+void filters_from_tags(cph_index* h, uint32_t slot, const std::vector<uint32_t>& table, size_t vals_at, uint32_t m, cph_filter** out) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (!h->has_tags[slot]) throw InvalidArg("the index has no tag column in slot " + std::to_string(slot) + ": call cph_set_tags first");
+    const uint64_t n = h->size(), nw = (n + 31) / 32;
+    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
+    h->use_device();
+    std::vector<std::unique_ptr<cph_filter>> made(m);
+    for (auto& f : made) f.reset(new cph_filter());
+    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
+    h->d_tag_tests.alloc(table.size());
+    h->d_tag_counts.alloc(m);
+    hipStream_t st = own_stream(h);
+    HIP_CHECK(hipMemcpyAsync(h->d_tag_tests.p, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+    timed_pass(h->pass_timer[kPassTags], st, [&] {
+        tag_filters(h->d_tag_lims[slot].p, h->d_tag_vals[slot].p, n, h->d_tag_tests.p, (uint32_t)vals_at, m, slab->p, stride,
+                    h->d_tag_counts.p, st);
+    });
+    std::vector<unsigned long long> counts(m);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_tag_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
+    for (uint32_t j = 0; j < m; ++j) {
+        cph_filter* f = made[j].get();
+        f->device = h->device;
+        f->n_bits = n;
+        f->popcount = counts[j];
+        f->slab = slab;
+        f->words.p = slab->p + (size_t)j * stride;
+        f->words.n = std::max<uint64_t>(nw, 1);
+    }
+    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
+}
+
+// The caller's tests, canonical and packed for the kernel (before any handle is locked).
+void pack_tag_tests(const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, uint32_t m, std::vector<uint32_t>& table,
+                    size_t& vals_at) {
+    if (m > kTagMaxFilters) throw InvalidArg("at most " + std::to_string(kTagMaxFilters) + " tag filters per call");
+    std::vector<uint32_t> tl;
+    std::vector<int32_t> tv;
+    tag_tests_canonical_host(test_lims, test_vals, modes, m, tl, tv);
+    tag_tests_pack_host(tl.data(), tv.data(), modes, m, table, vals_at);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_set_tags(cph_index* h, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        refuse_borrowed(h, "cph_set_tags");
+        require_tag_slot(slot);
+        set_tags(h, slot, lims, tags, n, space);
+    });
+}
+
+int cph_has_tags(cph_index* h, uint32_t slot, int* flag) {
+    return guarded([&] {
+        if (!h || !flag) throw InvalidArg("null argument");
+        require_tag_slot(slot);
+        std::lock_guard<std::mutex> lk(h->mu);
+        *flag = h->finalized && h->has_tags[slot] ? 1 : 0;
+    });
+}
+
+int cph_get_tags(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, uint64_t* lims_out, int32_t* tags_out) {
+    return guarded([&] {
+        if (!h || !lims_out) throw InvalidArg("null argument");
+        require_tag_slot(slot);
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        if (!h->has_tags[slot]) throw InvalidArg("the index has no tag column in slot " + std::to_string(slot));
+        if (first > h->size() || count > h->size() - first) throw InvalidArg("tag row range out of bounds");
+        h->use_device();
+        std::vector<uint32_t> lims(count + 1);
+        HIP_CHECK(hipMemcpy(lims.data(), h->d_tag_lims[slot].p + first, (count + 1) * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i <= count; ++i) lims_out[i] = (uint64_t)(lims[i] - lims[0]);
+        if (tags_out && lims[count] != lims[0])
+            HIP_CHECK(hipMemcpy(tags_out, h->d_tag_vals[slot].p + lims[0], (size_t)(lims[count] - lims[0]) * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int cph_filters_from_tags(cph_index* h, uint32_t slot, const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, uint32_t m,
+                          cph_filter** out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + m, nullptr);
+        if (!h || !test_lims || !modes) throw InvalidArg("null argument");
+        require_tag_slot(slot);
+        std::vector<uint32_t> table;
+        size_t vals_at = 0;
+        pack_tag_tests(test_lims, test_vals, modes, m, table, vals_at);
+        filters_from_tags(h, slot, table, vals_at, m, out);
+    });
+}
+
+int cph_debug_time_tag_filters(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassTags, on != 0); });
+}
+
+int cph_debug_last_tag_filters_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassTags, us); });
+}
+
+int cph_host_tag_filters(const uint32_t* lims, const int32_t* tags, uint64_t n, const uint32_t* test_lims, const int32_t* test_vals,
+                         const uint8_t* modes, uint32_t m, uint32_t* words_out, uint64_t* counts_out) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!lims || (n != 0 && !words_out) || !test_lims || !modes || !counts_out) throw InvalidArg("null argument");
+        if (n > 0xFFFFFFFFull) throw InvalidArg("filter too large");
+        std::vector<uint64_t> wide(lims, lims + n + 1);
+        std::vector<uint32_t> cl, tl;
+        std::vector<int32_t> cv, tv;
+        tags_canonical_host(wide.data(), tags, n, nullptr, 0, cl, cv);
+        tag_tests_canonical_host(test_lims, test_vals, modes, m, tl, tv);
+        tag_filters_host(cl.data(), cv.data(), n, tl.data(), tv.data(), modes, m, words_out, counts_out);
+    });
+}
+
+}  // extern "C"
+
+extern "C" {
+
 // ---- filter algebra (cph_filters_combine; device_filter_ops.h) ----
 // What a combine call needs on its device and keeps for the next one: a stream of its own (no handle is involved), the
 // operand tables and the counts, which only grow.  One call per device at a time (mu).  Never freed: the HIP runtime
@@ -4127,6 +4336,14 @@ void replicate(cph_index* src, cph_index* dst) {
         if (from.has) copy(to.dev, from.dev);
         else to.dev.release();
         to.has = from.has;
+    }
+    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {            // ... and the tag columns
+        dst->d_tag_lims[slot].release();
+        dst->d_tag_vals[slot].release();
+        dst->has_tags[slot] = src->has_tags[slot];
+        if (!src->has_tags[slot]) continue;
+        copy(dst->d_tag_lims[slot], src->d_tag_lims[slot]);
+        if (src->d_tag_vals[slot].p) copy(dst->d_tag_vals[slot], src->d_tag_vals[slot]);
     }
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
@@ -5187,8 +5404,15 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
 // values, appended in the same order -- (*labs)[1 + slot] for every column the handle has, the label column at
 // kLabelSlot.  Returns the number of live rows.
 using LiveColumns = std::vector<int32_t>[1 + kMaxColumns];
+// The live rows' tags, appended like LiveColumns: a CSR per slot the handle has (lims without the leading 0; has: the
+// slot holds a column, which a column of empty rows over zero live rows could not show otherwise).
+struct LiveTags {
+    std::vector<uint64_t> lims[kMaxTagColumns];
+    std::vector<int32_t> vals[kMaxTagColumns];
+    bool has[kMaxTagColumns] = {};
+};
 uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new,
-                     LiveColumns* labs = nullptr) {
+                     LiveColumns* labs = nullptr, LiveTags* tags = nullptr) {
     const HostIndex& hi = h->host;
     const uint64_t n = hi.n, size = h->size();
     const bool rows = h->has_rows && hi.rows.size() == n;
@@ -5207,6 +5431,14 @@ uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool 
                 const std::vector<int32_t>& col = column_of(h, slot).host;
                 if (col.size() == size) (*labs)[1 + slot].push_back(col[id]);
             }
+        if (tags)
+            for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {
+                const std::vector<uint32_t>& tl = hi.tag_lims[slot];
+                if (tl.size() != size + 1) continue;
+                tags->has[slot] = true;
+                tags->vals[slot].insert(tags->vals[slot].end(), hi.tag_vals[slot].begin() + tl[id], hi.tag_vals[slot].begin() + tl[id + 1]);
+                tags->lims[slot].push_back(tags->vals[slot].size());
+            }
         ++live;
     }
     return live;
@@ -5218,6 +5450,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     refuse_host_less(h, "cph_compact");
     std::vector<float> vecs;
     LiveColumns labs;                            // the live rows' labels and column values, in the order of the new input rows
+    LiveTags tags;                               // ... and their tags
     uint64_t live = 0;
     bool was_input = false;
     {
@@ -5230,7 +5463,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
         was_input = h->ids_input;
         vecs.reserve(live * h->dim);
         std::vector<int64_t> map(h->size());
-        gather_live(h, vecs, map.data(), was_input, 0, &labs);
+        gather_live(h, vecs, map.data(), was_input, 0, &labs, &tags);
         std::copy(map.begin(), map.end(), old_to_new);
     }
     build_pending(h, vecs.data(), live, true);   // (cosine: the live rows are unit-half rows already)
@@ -5239,6 +5472,11 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     if (was_input) set_result_ids(h, CPH_IDS_INPUT);
     for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot)      // new input row j: the values of the live row it came from
         if (labs[1 + slot].size() == live) set_labels(h, labs[1 + slot].data(), live, CPH_IDS_INPUT, slot);
+    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot)
+        if (tags.has[slot]) {
+            tags.lims[slot].insert(tags.lims[slot].begin(), 0);
+            set_tags(h, slot, tags.lims[slot].data(), tags.vals[slot].data(), live, CPH_IDS_INPUT);
+        }
 }
 
 }  // namespace
@@ -5311,6 +5549,9 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     if (has_extra_columns(h))
         throw InvalidArg("the index holds attribute columns and the added rows would have no values in them: drop the columns "
                          "(cph_set_column with NULL), add, then set them again at the new size");
+    if (has_tag_columns(h))
+        throw InvalidArg("the index holds tag columns and the added rows would have no tags in them: drop the columns "
+                         "(cph_set_tags with NULL), add, then set them again at the new size");
     if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
     std::vector<float> unit;                     // cosine: the rows as the index stores them (a bad row refuses the call here)
     if (h->metric == CPH_METRIC_IP) {            // (inner product: against the M2 of the index)
@@ -5551,6 +5792,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
         if (!m || !old_to_new) throw InvalidArg("null argument");
         std::vector<float> vecs;
         LiveColumns labs;                         // the live rows' labels and column values in global row order (every part has a column, or none)
+        LiveTags tags;                            // ... and their tags
         uint64_t live = 0;
         {
             std::unique_lock<std::shared_mutex> lk(m->life);
@@ -5560,7 +5802,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
             for (uint32_t p = 0; p < P; ++p) {
                 cph_index* h = m->parts[p];
                 std::lock_guard<std::mutex> g(h->mu);
-                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live, &labs);
+                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live, &labs, &tags);
             }
             if (live < kMinPartRows * P)      // cph_parts_build's own refusal, before any part gives up its index
                 throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
@@ -5573,6 +5815,11 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
         if (labs[0].size() == live) check_rc(cph_parts_set_labels(m, labs[0].data(), live));     // cut again at the new bounds
         for (uint32_t slot = 0; slot < kMaxColumns; ++slot)
             if (labs[1 + slot].size() == live) check_rc(cph_parts_set_column(m, slot, labs[1 + slot].data(), live));
+        for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot)
+            if (tags.has[slot]) {
+                tags.lims[slot].insert(tags.lims[slot].begin(), 0);
+                check_rc(cph_parts_set_tags(m, slot, tags.lims[slot].data(), tags.vals[slot].data(), live));
+            }
     });
 }
 
@@ -5683,6 +5930,104 @@ int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo
     return guarded([&] {
         require_slot(slot);
         parts_filters_from_column(m, lo, hi, cnt, out, (int)slot);
+    });
+}
+
+// ---- tag columns of replicas and parts (cph_set_tags) ----
+int cph_multi_set_tags(cph_multi* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        require_tag_slot(slot);
+        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
+        cph_index* r0 = m->reps[0];
+        for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
+            std::lock_guard<std::mutex> g(h->mu);
+            require_tags_target(h, lims != nullptr, n);
+        }
+        set_tags(r0, slot, lims, tags, n, space);            // validates the rest, and makes the canonical column once
+        try {
+            for (size_t i = 1; i < m->reps.size(); ++i) {
+                cph_index* h = m->reps[i];
+                std::lock_guard<std::mutex> g(h->mu);
+                install_tags_locked(h, slot, lims ? r0->host.tag_lims[slot].data() : nullptr, r0->host.tag_vals[slot].data(), n, false);
+            }
+        } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
+            for (cph_index* h : m->reps) {
+                std::lock_guard<std::mutex> g(h->mu);
+                try { install_tags_locked(h, slot, nullptr, nullptr, 0, false); } catch (...) {}
+            }
+            throw;
+        }
+    });
+}
+
+// lims[n + 1] / tags over GLOBAL input rows, cut at the part bounds with the limits rebased.
+int cph_parts_set_tags(cph_parts* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        require_tag_slot(slot);
+        std::unique_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw InvalidArg("tags belong to a finalized index: finalize or load it first");
+        if (lims) {
+            if (n != m->bounds.back())
+                throw InvalidArg("tag column has " + std::to_string(n) + " rows, the index holds " + std::to_string(m->bounds.back()));
+            if (lims[0] != 0) throw InvalidArg("tag limits must start at 0");      // (before the cut rebases them)
+            for (uint64_t i = 0; i < n; ++i)
+                if (lims[i + 1] < lims[i]) throw InvalidArg("tag limits must not decrease (row " + std::to_string(i) + ")");
+            if (lims[n] != 0 && !tags) throw InvalidArg("null tags");
+        }
+        for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
+            std::lock_guard<std::mutex> g(h->mu);
+            if (lims && (!h->has_rows || h->host.rows.size() != h->host.n))
+                throw InvalidArg("a part has no row map: tags of a partitioned index are given in input rows");
+        }
+        try {
+            std::vector<uint64_t> cut;
+            for (size_t p = 0; p < m->parts.size(); ++p) {
+                const uint64_t b0 = m->bounds[p], b1 = m->bounds[p + 1];
+                if (!lims) {
+                    set_tags(m->parts[p], slot, nullptr, nullptr, 0, CPH_IDS_INPUT);
+                    continue;
+                }
+                cut.assign(lims + b0, lims + b1 + 1);
+                for (uint64_t& x : cut) x -= lims[b0];
+                set_tags(m->parts[p], slot, cut.data(), tags ? tags + lims[b0] : nullptr, b1 - b0, CPH_IDS_INPUT);
+            }
+        } catch (...) {                                      // (a refused row or a device failure: no part keeps a column the others lack)
+            for (cph_index* h : m->parts) {
+                std::lock_guard<std::mutex> g(h->mu);
+                try { install_tags_locked(h, slot, nullptr, nullptr, 0, true); } catch (...) {}
+            }
+            throw;
+        }
+    });
+}
+
+int cph_parts_filters_from_tags(cph_parts* m, uint32_t slot, const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes,
+                                uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] {
+        if (cnt == 0) return;
+        if (!out) throw InvalidArg("null argument");
+        std::fill(out, out + cnt, nullptr);
+        if (!m || !test_lims || !modes) throw InvalidArg("null argument");
+        require_tag_slot(slot);
+        std::vector<uint32_t> table;
+        size_t vals_at = 0;
+        pack_tag_tests(test_lims, test_vals, modes, cnt, table, vals_at);
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+        std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
+        for (auto& f : made) {
+            f.reset(new cph_parts_filter());
+            f->n_bits = m->bounds.back();
+            f->f.reserve(m->parts.size());
+        }
+        std::vector<cph_filter*> slice(cnt);
+        for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
+            filters_from_tags(m->parts[p], slot, table, vals_at, cnt, slice.data());
+            for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
+        }
+        for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
     });
 }
 

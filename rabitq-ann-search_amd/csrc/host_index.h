@@ -218,6 +218,126 @@ inline void labels_to_internal_host(const int32_t* by_row, const uint32_t* rows,
     for (size_t i = 0; i < n; ++i) out[i] = by_row[rows[i]];
 }
 
+// ---- tag columns (cph_set_tags; device_tags.h) ----
+// A tag column gives every row a SET of int32 tags, as a CSR in internal-id order: lims[n + 1] (uint32, lims[0] = 0) and
+// tags[lims[n]], ascending and distinct inside a row.  A tag test is a set V of at most kMaxTagTestValues values
+// (ascending, distinct) and a mode; with c(row) = |tags(row) & V| it allows the row when c > 0 (any), c == |V| (all: exact,
+// because both sides are distinct) or c == 0 (none).
+constexpr uint32_t kMaxTagColumns = 4;        // CPH_MAX_TAG_COLUMNS
+constexpr uint32_t kMaxTagsPerRow = 1024;     // CPH_MAX_TAGS_PER_ROW, after dedup
+constexpr uint32_t kMaxTagTestValues = 64;    // CPH_MAX_TAG_TEST_VALUES, after dedup
+enum TagMode : uint8_t { kTagsAny = 0, kTagsAll = 1, kTagsNone = 2 };
+
+// The caller's CSR (lims[n + 1], 64-bit, any order and duplicates inside a row) -> the canonical column.  rows (may be
+// null): canonical row i is the caller's row rows[i] for i < n_rows (cph_set_tags with CPH_IDS_INPUT; the rows behind
+// n_rows stay where they are), else row i.  Refuses (std::invalid_argument) a lims that does not start at 0 or decreases,
+// null tags with lims[n] != 0, a row of more than kMaxTagsPerRow distinct tags and 2^32 tags or more after dedup.
+inline void tags_canonical_host(const uint64_t* lims, const int32_t* tags, size_t n, const uint32_t* rows, size_t n_rows,
+                                std::vector<uint32_t>& out_lims, std::vector<int32_t>& out_tags) {
+    if (!lims) throw std::invalid_argument("null tag limits");
+    if (lims[0] != 0) throw std::invalid_argument("tag limits must start at 0");
+    for (size_t i = 0; i < n; ++i)
+        if (lims[i + 1] < lims[i]) throw std::invalid_argument("tag limits must not decrease (row " + std::to_string(i) + ")");
+    if (lims[n] != 0 && !tags) throw std::invalid_argument("null tags");
+    std::vector<uint32_t> ol(n + 1, 0u);
+    std::vector<int32_t> ot, row;
+    ot.reserve(lims[n]);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t r = rows && i < n_rows ? rows[i] : i;
+        row.clear();                                        // (an empty row touches no pointer: tags may be null)
+        if (lims[r + 1] != lims[r]) row.assign(tags + lims[r], tags + lims[r + 1]);
+        std::sort(row.begin(), row.end());
+        row.erase(std::unique(row.begin(), row.end()), row.end());
+        if (row.size() > kMaxTagsPerRow)
+            throw std::invalid_argument("row " + std::to_string(r) + " has " + std::to_string(row.size()) + " distinct tags, at most " +
+                                        std::to_string(kMaxTagsPerRow) + " (CPH_MAX_TAGS_PER_ROW)");
+        ot.insert(ot.end(), row.begin(), row.end());
+        if (ot.size() > 0xFFFFFFFFull) throw std::invalid_argument("a tag column holds fewer than 2^32 tags");
+        ol[i + 1] = (uint32_t)ot.size();
+    }
+    out_lims.swap(ol);
+    out_tags.swap(ot);
+}
+
+// The caller's m tests (test_lims[m + 1] from 0, non-decreasing; values in any order, duplicates allowed) -> canonical
+// ones.  Refuses a mode above kTagsNone and a test of more than kMaxTagTestValues distinct values.
+inline void tag_tests_canonical_host(const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, size_t m,
+                                     std::vector<uint32_t>& out_lims, std::vector<int32_t>& out_vals) {
+    if (!test_lims || !modes) throw std::invalid_argument("null tag tests");
+    if (test_lims[0] != 0) throw std::invalid_argument("tag test limits must start at 0");
+    std::vector<uint32_t> ol(m + 1, 0u);
+    std::vector<int32_t> ov, v;
+    for (size_t j = 0; j < m; ++j) {
+        if (test_lims[j + 1] < test_lims[j]) throw std::invalid_argument("tag test limits must not decrease (test " + std::to_string(j) + ")");
+        if (modes[j] > kTagsNone) throw std::invalid_argument("tag test mode must be CPH_TAGS_ANY, CPH_TAGS_ALL or CPH_TAGS_NONE");
+        if (test_lims[j + 1] != test_lims[j] && !test_vals) throw std::invalid_argument("null tag test values");
+        v.clear();
+        if (test_lims[j + 1] != test_lims[j]) v.assign(test_vals + test_lims[j], test_vals + test_lims[j + 1]);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        if (v.size() > kMaxTagTestValues)
+            throw std::invalid_argument("tag test " + std::to_string(j) + " has " + std::to_string(v.size()) + " distinct values, at most " +
+                                        std::to_string(kMaxTagTestValues) + " (CPH_MAX_TAG_TEST_VALUES)");
+        ov.insert(ov.end(), v.begin(), v.end());
+        ol[j + 1] = (uint32_t)ov.size();
+    }
+    out_lims.swap(ol);
+    out_vals.swap(ov);
+}
+
+inline bool tag_mode_allows(uint8_t mode, uint32_t c, uint32_t nv) {
+    return mode == kTagsAny ? c > 0 : mode == kTagsAll ? c == nv : c == 0;
+}
+
+// The host statement of the tag filters (cph_filters_from_tags; device_tags.h) on a canonical column and canonical tests:
+// bit i of filter j = tag_mode_allows(modes[j], |tags(i) & V_j|, |V_j|).  out: m bitmaps of (n + 31) / 32 words each, one
+// behind the other, every word written and the bits of the last word behind n clear; counts[j] = ids allowed by filter j.
+inline void tag_filters_host(const uint32_t* lims, const int32_t* tags, size_t n, const uint32_t* test_lims, const int32_t* test_vals,
+                             const uint8_t* modes, size_t m, uint32_t* out, uint64_t* counts) {
+    const size_t nw = (n + 31) / 32;
+    for (size_t j = 0; j < m; ++j) {
+        uint32_t* w = out + j * nw;
+        const uint32_t nv = test_lims[j + 1] - test_lims[j];
+        const int32_t* v0 = nv ? test_vals + test_lims[j] : nullptr;
+        uint64_t total = 0;
+        for (size_t k = 0; k < nw; ++k) w[k] = 0u;
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t c = 0;
+            for (uint32_t t = lims[i]; t < lims[i + 1]; ++t) c += std::binary_search(v0, v0 + nv, tags[t]) ? 1u : 0u;
+            if (tag_mode_allows(modes[j], c, nv)) {
+                w[i >> 5] |= 1u << (i & 31);
+                ++total;
+            }
+        }
+        counts[j] = total;
+    }
+}
+
+// Canonical rows [first, first + count) of a canonical column as a CSR of their own, the limits rebased to 0 (what
+// cph_get_tags returns; the cut of a partitioned index).
+inline void tags_slice_host(const uint32_t* lims, const int32_t* tags, size_t first, size_t count, uint64_t* lims_out, int32_t* tags_out) {
+    for (size_t i = 0; i <= count; ++i) lims_out[i] = (uint64_t)(lims[first + i] - lims[first]);
+    if (tags_out && lims[first + count] != lims[first]) std::copy(tags + lims[first], tags + lims[first + count], tags_out);
+}
+
+// The tests as the kernel reads them, one uint32 table: offs[m + 1] | info[m] | (pad to 4) | values.  Every test's values
+// are padded to a multiple of kTagTestPad with copies of its last value (the kernel ORs the compares of a group, so a
+// repeated value changes nothing) and start on a 16 B boundary; offs counts in values from the start of the value area;
+// info[j] = mode | |V_j| << 8 (the real size: what `all` compares with).  An empty test has no values at all.
+constexpr uint32_t kTagTestPad = 4;
+inline void tag_tests_pack_host(const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, size_t m,
+                                std::vector<uint32_t>& table, size_t& vals_at) {
+    vals_at = (2 * m + 1 + 3) / 4 * 4;
+    table.assign(vals_at, 0u);
+    for (size_t j = 0; j < m; ++j) {
+        const uint32_t nv = test_lims[j + 1] - test_lims[j];
+        table[m + 1 + j] = (uint32_t)modes[j] | nv << 8;
+        for (uint32_t i = 0; i < (nv + kTagTestPad - 1) / kTagTestPad * kTagTestPad; ++i)
+            table.push_back((uint32_t)test_vals[test_lims[j] + std::min(i, nv - 1)]);
+        table[j + 1] = (uint32_t)(table.size() - vals_at);
+    }
+}
+
 // The host statement of the filter algebra (cph_filters_combine; device_filter_ops.h): out[j] = a[j] OP b[j] word by
 // word for m bitmaps of (n_bits + 31) / 32 words each, one behind the other; b holds m bitmaps, or ONE that every j
 // reads (b_broadcast), and is not read for kFilterNot.  Every word of `out` is written; the bits of the last word at
@@ -283,6 +403,10 @@ struct HostIndex {
     // The attribute columns (cph_set_column): columns[s][i] = value of internal id i in slot s; empty = none.  They
     // live and die with the label column: no file carries them.
     std::vector<int32_t> columns[kMaxColumns];
+    // The tag columns (cph_set_tags): the canonical CSR of slot s in internal-id order, tag_lims[s] = [n + 1] offsets into
+    // tag_vals[s]; an empty tag_lims[s] = none.  They live and die with the attribute columns.
+    std::vector<uint32_t> tag_lims[kMaxTagColumns];
+    std::vector<int32_t> tag_vals[kMaxTagColumns];
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

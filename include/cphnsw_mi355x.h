@@ -94,6 +94,24 @@ int cph_finalize(cph_index* h);
  * with fewer than 32 candidates are padded with 0xFFFFFFFF / FLT_MAX. */
 int cph_knn_bruteforce(int device, const float* vectors, uint64_t n, uint64_t dim, const float* queries,
                        uint64_t nq, uint32_t* ids, float* dist);
+/* Test entries of the exact-kNN kernels (tests only, like grid_cap above).  cph_debug_knn runs the kernels behind
+ * cph_knn_bruteforce with the choices the production path makes from the size laid open; cph_host_knn is their host
+ * statement (csrc/host_knn.h, no HIP call, callable without a GPU), whose ids and distances the kernels equal byte for byte.
+ *   queries == NULL: the self-join of vectors[n][dim] (a row never lists itself; nq = 0, q_ids = NULL, exclude_self ignored);
+ *   queries != NULL: queries[nq][dim] against vectors; exclude_self = 0: nothing is excluded and q_ids is NULL;
+ *   exclude_self = 1: row i never lists column q_ids[i] (q_ids[nq], every entry < n) -- the form the join's fallback uses.
+ *   path: 0 = the two-pass kernel (knn_mfma_kernel); 1 = the symmetric join (device_knn_sym.h), refused unless this is a
+ *   self-join with 1024 <= n <= 4096 and a padded D >= 64.  dim <= 2048.
+ *   blocks_per_launch: 0 = the production slicing, else the number of 128-row blocks per launch of the two-pass kernel and
+ *   the number of workgroups per launch of the join.
+ * ids/dist [rows][32] as cph_knn_bruteforce writes them; *fallback_rows = rows the join answered through its fallback
+ * (0 on path 0); *launches = launches made of the kernel that path names; cand_count[n] (cph_host_knn on path 1, may be NULL) = the
+ * join's candidates per row.  The pointers to single values may be NULL. */
+int cph_debug_knn(int device, const float* vectors, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                  const uint32_t* q_ids, int exclude_self, int path, uint32_t blocks_per_launch, uint32_t* ids, float* dist,
+                  uint32_t* fallback_rows, uint32_t* launches);
+int cph_host_knn(const float* vectors, uint64_t n, uint64_t dim, const float* queries, uint64_t nq, const uint32_t* q_ids,
+                 int exclude_self, int path, uint32_t* ids, float* dist, uint32_t* fallback_rows, uint32_t* cand_count);
 
 /* Construction hook: the data-side encoder of one vertex' edges on the GPU (the kernel finalize() runs
  * for every vertex; encoder/rabitq_encoder.hpp:138-181, 287-323, 371-467): parent and cnt <= 32

@@ -3,7 +3,7 @@
     from cphnsw_mi355x import CPIndex      # drop-in for `from cphnsw import CPIndex`
 """
 from .index import (CPIndex, FastScanStream, GroupKeys, IdFilter, RescoreVectors, combine_filters, encode_edges, heap_ops_debug,  # noqa: F401
-                    knn_bruteforce, pack_allowed_bits, select_layer_debug, select_neighbors_debug)
+                    knn_bruteforce, knn_debug, pack_allowed_bits, select_layer_debug, select_neighbors_debug)
 
-__all__ = ["CPIndex", "FastScanStream", "GroupKeys", "IdFilter", "RescoreVectors", "combine_filters", "encode_edges", "heap_ops_debug", "knn_bruteforce",
+__all__ = ["CPIndex", "FastScanStream", "GroupKeys", "IdFilter", "RescoreVectors", "combine_filters", "encode_edges", "heap_ops_debug", "knn_bruteforce", "knn_debug",
            "pack_allowed_bits", "select_layer_debug", "select_neighbors_debug"]

@@ -28,6 +28,10 @@ SYMBOLS = {
     "cph_finalize": (C.c_int, [C.c_void_p]),
     "cph_knn_bruteforce": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.c_void_p]),
+    "cph_debug_knn": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int,
+                                C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "cph_host_knn": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int,
+                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
     "cph_debug_heap_ops": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
     "cph_select_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,

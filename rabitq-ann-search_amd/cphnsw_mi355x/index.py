@@ -2559,6 +2559,31 @@ def knn_bruteforce(vectors, queries=None, device=None):
     return ids, dist
 
 
+def knn_debug(vectors, queries=None, q_ids=None, path=0, blocks_per_launch=0, device=None):
+    """Test hook of the exact-kNN kernels: knn_bruteforce with the choices the production path makes from the size laid open.
+    queries=None: the self-join; q_ids (with queries): row i never lists column q_ids[i]; path 0 = the two-pass kernel,
+    1 = the symmetric join (self-join, 1024 <= n <= 4096, padded D >= 64); blocks_per_launch 0 = the production slicing, else
+    128-row blocks per launch (two-pass) and workgroups per launch (join).  Returns (ids u32[rows, 32], dist f32[rows, 32],
+    fallback rows of the join, launches made of the kernel `path` names)."""
+    v = _as_f32(vectors)
+    n, dim = v.shape
+    q = None if queries is None else _as_f32(queries)
+    if q is not None and (q.ndim != 2 or q.shape[1] != dim):
+        raise ValueError("queries must be a (nq, dim) array")
+    qi = None if q_ids is None else np.ascontiguousarray(q_ids, np.uint32)
+    if qi is not None and (q is None or qi.shape != (q.shape[0],)):
+        raise ValueError("q_ids must be a (nq,) array and goes with queries")
+    rows = n if q is None else q.shape[0]
+    ids = np.zeros((rows, 32), np.uint32)
+    dist = np.zeros((rows, 32), np.float32)
+    redo, made = C.c_uint32(0), C.c_uint32(0)
+    dev = _default_device() if device is None else int(device)
+    _lib.check(_lib.lib().cph_debug_knn(dev, v.ctypes.data, n, dim, None if q is None else q.ctypes.data, 0 if q is None else q.shape[0],
+                                        None if qi is None else qi.ctypes.data, 0 if qi is None else 1, int(path), int(blocks_per_launch),
+                                        ids.ctypes.data, dist.ctypes.data, C.byref(redo), C.byref(made)))
+    return ids, dist, int(redo.value), int(made.value)
+
+
 def encode_edges(parent, nbrs, bits, device=None):
     """GPU data-side encoder of one vertex' edges (construction hook): (values u8[cnt, D], aux f32[cnt, 3] =
     nop, ip_qo, ip_cp, pops u32[cnt, 2] = msb popcount, weighted popcount)."""

@@ -74,12 +74,15 @@ inline uint32_t grid_for(uint64_t items, uint32_t block) { return (uint32_t)((it
 
 // ---- exact kNN on the matrix cores (device pointers; D a multiple of 32) ----------------------------
 // exclude_self: query row i never lists column i -- or column q_ids[i] when the query rows are a gathered subset of the base
+// blocks_per_launch (tests only, cph_debug_knn): 0 = the production slicing, else row blocks of 128 per launch; *launches
+// receives the number of launches made.
 inline void knn_device(const float* d_q, const float* d_qnorm, size_t nq, const float* d_b, const float* d_bnorm,
                        size_t nb, size_t D, bool exclude_self, int num_cus, uint32_t* d_ids, float* d_dist,
-                       const uint32_t* d_q_ids = nullptr) {
+                       const uint32_t* d_q_ids = nullptr, uint32_t blocks_per_launch = 0, uint32_t* launches = nullptr) {
     if (D % kKnnKC != 0 || nq == 0 || nb == 0) throw std::invalid_argument("knn_device: D must be a multiple of 32");
     // slices of row blocks, so that no single launch runs for minutes
-    const uint32_t rows_per_launch = (uint32_t)num_cus * 8u * kKnnTile;
+    const uint32_t rows_per_launch = (blocks_per_launch ? blocks_per_launch : (uint32_t)num_cus * 8u) * kKnnTile;
+    if (launches) *launches = (uint32_t)((nq + rows_per_launch - 1) / rows_per_launch);
     for (size_t rb = 0; rb < nq; rb += rows_per_launch) {
         KnnArgs a{d_q, d_b, d_bnorm, d_qnorm, (uint32_t)nq, (uint32_t)nb, (uint32_t)D, (uint32_t)rb,
                   (uint32_t)std::min<size_t>(nq, rb + rows_per_launch), exclude_self ? 1u : 0u, d_ids, d_dist, d_q_ids};
@@ -99,12 +102,26 @@ inline bool knn_sym_wanted(size_t n, size_t D) {
     const size_t min_n = env > 1 ? (size_t)env : 32768;      // CPH_KNN_SYM=<n>: lower the size limit (tests)
     return n >= min_n && n / kKnnSymSample >= 64 && D >= 2 * kKnnKC && n < (1ull << 31);
 }
+// The knobs of cph_debug_knn (tests only; the defaults are the production path): path -1 = as knn_sym_wanted says, 0 = the
+// two-pass kernel, 1 = the join; blocks_per_launch 0 = the production slicing, else row blocks per knn_device launch and
+// workgroups per launch of the join.  *launches = launches of the kernel that `path` names, *fallback_rows = rows the join
+// handed to the fallback.
+struct KnnKnobs {
+    int path = -1;
+    uint32_t blocks_per_launch = 0;
+    uint32_t* fallback_rows = nullptr;
+    uint32_t* launches = nullptr;
+};
 inline void knn_self_device(const float* d_x, const float* d_norm, size_t n, size_t D, int num_cus, uint32_t* d_ids, float* d_dist,
-                            bool verbose = false) {
-    if (!knn_sym_wanted(n, D)) {
-        knn_device(d_x, d_norm, n, d_x, d_norm, n, D, true, num_cus, d_ids, d_dist);
+                            bool verbose = false, const KnnKnobs& knobs = KnnKnobs()) {
+    const uint32_t bpl = knobs.blocks_per_launch;
+    if (knobs.fallback_rows) *knobs.fallback_rows = 0;
+    if (knobs.path == 0 || (knobs.path < 0 && !knn_sym_wanted(n, D))) {
+        knn_device(d_x, d_norm, n, d_x, d_norm, n, D, true, num_cus, d_ids, d_dist, nullptr, bpl, knobs.launches);
         return;
     }
+    // (what the kernels below need whatever the size limit says: two K chunks per tile, eight sample rows and one more)
+    if (n / kKnnSymSample < 64 || D < 2 * kKnnKC || n >= (1ull << 31)) throw std::invalid_argument("knn_self_device: not a shape of the join");
     StageTimer tm{verbose};
     // 1. thresholds from a sample of the rows
     const uint32_t ns = (uint32_t)((n + kKnnSymSample - 1) / kKnnSymSample);
@@ -117,7 +134,7 @@ inline void knn_self_device(const float* d_x, const float* d_norm, size_t n, siz
                            d_sid.p, (uint64_t)ns, (uint32_t)D, d_sx.p);
         hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_for(ns, 256)), dim3(256), 0, nullptr, d_norm, d_sid.p, (uint64_t)ns, d_sn.p);
         HIP_CHECK(hipGetLastError());
-        knn_device(d_x, d_norm, n, d_sx.p, d_sn.p, ns, D, false, num_cus, d_soi.p, d_sod.p);
+        knn_device(d_x, d_norm, n, d_sx.p, d_sn.p, ns, D, false, num_cus, d_soi.p, d_sod.p, nullptr, bpl);
         hipLaunchKernelGGL(knn_sym_tau_kernel, dim3(grid_for(n, 256)), dim3(256), 0, nullptr, d_sod.p, (uint32_t)n, d_tau.p);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
@@ -130,7 +147,8 @@ inline void knn_self_device(const float* d_x, const float* d_norm, size_t n, siz
     HIP_CHECK(hipMemset(d_nredo.p, 0, 4));
     const uint32_t nblk = (uint32_t)((n + kKnnTile - 1) / kKnnTile);
     const uint32_t nwg = (nblk + 1) / 2;
-    const uint32_t wg_per_launch = (uint32_t)num_cus * 4u;     // slices, so that no single launch runs for minutes
+    const uint32_t wg_per_launch = bpl ? bpl : (uint32_t)num_cus * 4u;     // slices, so that no single launch runs for minutes
+    if (knobs.launches) *knobs.launches = (nwg + wg_per_launch - 1) / wg_per_launch;
     for (uint32_t w0 = 0; w0 < nwg; w0 += wg_per_launch) {
         KnnSymArgs a{d_x, d_norm, d_tau.p, (uint32_t)n, (uint32_t)D, nblk, w0, d_cnt.p, d_cid.p, d_cd.p};
         hipLaunchKernelGGL(knn_sym_kernel, dim3(std::min(wg_per_launch, nwg - w0)), dim3(256), 0, nullptr, a);
@@ -144,6 +162,7 @@ inline void knn_self_device(const float* d_x, const float* d_norm, size_t n, siz
     HIP_CHECK(hipGetLastError());
     uint32_t nredo = 0;
     HIP_CHECK(hipMemcpy(&nredo, d_nredo.p, 4, hipMemcpyDeviceToHost));
+    if (knobs.fallback_rows) *knobs.fallback_rows = nredo;
     tm.lap("kNN: selection");
     // 4. ... and are answered exactly against every row
     if (nredo) {
@@ -153,7 +172,7 @@ inline void knn_self_device(const float* d_x, const float* d_norm, size_t n, siz
                            d_redo.p, (uint64_t)nredo, (uint32_t)D, d_rx.p);
         hipLaunchKernelGGL(gather_u32_kernel, dim3(grid_for(nredo, 256)), dim3(256), 0, nullptr, d_norm, d_redo.p, (uint64_t)nredo, d_rn.p);
         HIP_CHECK(hipGetLastError());
-        knn_device(d_rx.p, d_rn.p, nredo, d_x, d_norm, n, D, true, num_cus, d_ri.p, d_rd.p, d_redo.p);
+        knn_device(d_rx.p, d_rn.p, nredo, d_x, d_norm, n, D, true, num_cus, d_ri.p, d_rd.p, d_redo.p, bpl);
         hipLaunchKernelGGL(knn_sym_scatter_kernel, dim3(grid_for((size_t)nredo * kKnnK, 256)), dim3(256), 0, nullptr, d_redo.p, nredo,
                            d_ri.p, d_rd.p, d_ids, d_dist);
         HIP_CHECK(hipGetLastError());

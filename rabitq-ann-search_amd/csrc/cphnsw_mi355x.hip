@@ -48,6 +48,7 @@
 #include "device_ip.h"
 #include "host_index.h"
 #include "host_parallel.h"
+#include "host_knn.h"
 #include "search_coalescer.h"
 #include "multi_device.h"
 #include "partitioned.h"
@@ -1891,7 +1892,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 116; }
+int cph_version(void) { return 117; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -2289,6 +2290,65 @@ int cph_knn_bruteforce(int device, const float* vectors, uint64_t n, uint64_t di
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
         build::gpu_knn(queries ? q.data() : nullptr, queries ? qn.data() : nullptr, nq, x.data(), nrm.data(), n, D,
                        cus, ids, dist);
+    });
+}
+
+// ---- the exact-kNN kernels against their host statement (host_knn.h) ----------------------------------------------------
+static_assert(kHostKnnK == (uint32_t)kKnnK && kHostKnnChunk == (uint32_t)kKnnKC && kHostKnnSymSample == kKnnSymSample &&
+              kHostKnnSymRank == kKnnSymRank && kHostKnnSymCap == kKnnSymCap, "host_knn.h restates the constants of the kernels");
+
+int cph_host_knn(const float* vectors, uint64_t n, uint64_t dim, const float* queries, uint64_t nq, const uint32_t* q_ids,
+                 int exclude_self, int path, uint32_t* ids, float* dist, uint32_t* fallback_rows, uint32_t* cand_count) {
+    return guarded([&] {
+        knn_debug_check(vectors, n, dim, queries, nq, q_ids, exclude_self, path, ids, dist);
+        const uint32_t redo = knn_host(vectors, n, dim, queries, nq, q_ids, path, ids, dist, path == 1 ? cand_count : nullptr);
+        if (fallback_rows) *fallback_rows = redo;
+    });
+}
+
+int cph_debug_knn(int device, const float* vectors, uint64_t n, uint64_t dim, const float* queries, uint64_t nq, const uint32_t* q_ids,
+                  int exclude_self, int path, uint32_t blocks_per_launch, uint32_t* ids, float* dist, uint32_t* fallback_rows,
+                  uint32_t* launches) {
+    return guarded([&] {
+        knn_debug_check(vectors, n, dim, queries, nq, q_ids, exclude_self, path, ids, dist);
+        if (blocks_per_launch > 65536) throw InvalidArg("knn debug: blocks_per_launch <= 65536");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t D = knn_padded_dim(dim);
+        std::vector<float> x, nrm, q, qn;
+        knn_pad_rows(vectors, n, dim, D, x, nrm);
+        if (queries) knn_pad_rows(queries, nq, dim, D, q, qn);
+        int cus = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
+        const size_t rows = queries ? nq : n;
+        uint32_t redo = 0, made = 0;
+        DevBuf<float> d_x(n * D), d_norm(n), d_od(rows * kKnnK);
+        DevBuf<uint32_t> d_oi(rows * kKnnK);
+        HIP_CHECK(hipMemcpy(d_x.p, x.data(), n * D * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_norm.p, nrm.data(), n * 4, hipMemcpyHostToDevice));
+        // (a row the kernels do not write would show: the model writes every slot)
+        HIP_CHECK(hipMemset(d_oi.p, 0xA5, rows * kKnnK * 4));
+        HIP_CHECK(hipMemset(d_od.p, 0xA5, rows * kKnnK * 4));
+        if (!queries) {
+            build::KnnKnobs knobs;
+            knobs.path = path;
+            knobs.blocks_per_launch = blocks_per_launch;
+            knobs.fallback_rows = &redo;
+            knobs.launches = &made;
+            build::knn_self_device(d_x.p, d_norm.p, n, D, cus, d_oi.p, d_od.p, false, knobs);
+        } else {
+            DevBuf<float> d_q(nq * D), d_qn(nq);
+            DevBuf<uint32_t> d_qi(q_ids ? nq : 1);
+            HIP_CHECK(hipMemcpy(d_q.p, q.data(), nq * D * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_qn.p, qn.data(), nq * 4, hipMemcpyHostToDevice));
+            if (q_ids) HIP_CHECK(hipMemcpy(d_qi.p, q_ids, nq * 4, hipMemcpyHostToDevice));
+            build::knn_device(d_q.p, d_qn.p, nq, d_x.p, d_norm.p, n, D, q_ids != nullptr, cus, d_oi.p, d_od.p, q_ids ? d_qi.p : nullptr,
+                              blocks_per_launch, &made);
+        }
+        HIP_CHECK(hipMemcpy(ids, d_oi.p, rows * kKnnK * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(dist, d_od.p, rows * kKnnK * 4, hipMemcpyDeviceToHost));
+        if (fallback_rows) *fallback_rows = redo;
+        if (launches) *launches = made;
     });
 }
 

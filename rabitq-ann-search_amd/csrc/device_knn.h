@@ -29,7 +29,10 @@
 // LDS operand image: row-major [128][32 + 4] floats.  Lane (h = lane >> 5, c = lane & 31) reads
 // its row's k = 8j + 4h .. 8j + 4h + 3 with one ds_read_b128 and feeds the four values to four
 // consecutive MFMAs; A and B use the same k for the same (lane half, step), which is all the
-// instruction needs -- the order in which k is summed is irrelevant to an exact-kNN list.  The 36-float
+// instruction needs -- the order in which k is summed is irrelevant to an exact-kNN list.  (It is fixed all the same:
+// inside every group of eight coordinates 0, 4, 1, 5, 2, 6, 3, 7 -- .x of lane half 0, .x of lane half 1, .y, ... --
+// and host_knn.h restates the kernels in that order, so that tests/test_gpu_knn.py can compare their outputs byte for
+// byte.  Whoever changes the operand layout changes knn_k_order with it.)  The 36-float
 // stride makes the 16 rows of each ds_read_b128 lane group land on 16 distinct 4-bank spans.
 //
 // Where the time goes (s_memtime stamps per phase, 262,144 x 128, after the half-chunk pipeline below): the chunk loop

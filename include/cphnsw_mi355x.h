@@ -153,6 +153,16 @@ int cph_calib_hook(cph_index* h, const float* queries, const uint32_t* start, ui
 int cph_debug_heap_ops(int device, const uint8_t* ops, uint64_t n_ops, const float* keys, const uint32_t* ids, uint64_t n_push,
                        float* out_keys, uint32_t* out_ids, uint32_t* out_size);
 
+/* Self-test hook for the N-bit estimator of the search kernels' expansion (csrc/device_estimator_test.h): for the
+ * neighbour blocks of vertices [first, first + count) of a finalized 2- or 4-bit index, every set s of forced aux values
+ * (force[n_sets][3] = nop, ip_qo, ip_cp, put into every lane of the block where bit 0 / 1 / 2 of fmask[s] is set; the
+ * block's own value otherwise) and every squared distance dqp[j], out[block][s][j][6][32] holds the bits of the stage-1
+ * bound, the stage-2 bound and the estimate as the expansion evaluates them (lower_bounds_split + stage2_est_only inside
+ * 1e-12 <= dqp < +inf), then the same three from stage1_lower + stage2_est, which cph_fastscan_block runs.  lut and
+ * qparams as for cph_fastscan_block.  count <= 1024, n_dqp <= 64, n_sets <= 64. */
+int cph_debug_estimator(cph_index* h, const uint8_t* lut, const float* qparams, uint32_t first, uint32_t count, const float* dqp,
+                        uint32_t n_dqp, const float* force, const uint32_t* fmask, uint32_t n_sets, uint32_t* out);
+
 /* ---- search ---------------------------------------------------------------------- */
 /* queries: host, row-major [n][dim] float32.  ids/dist: host, [n][k], rows shorter than k
  * padded with -1 / FLT_MAX (src/bindings.cpp:202-210). */

@@ -29,6 +29,7 @@
 #include "device_search.h"
 #include "device_stream.h"
 #include "device_heap_test.h"
+#include "device_estimator_test.h"
 #include "device_relayout.h"
 #include "device_rows.h"
 #include "device_tombstone.h"
@@ -3982,6 +3983,43 @@ int cph_fastscan_block(cph_index* h, const uint8_t* lut, const float* qparams, u
         std::memcpy(sums, hu, 128); std::memcpy(msb, hu + 32, 128);
         std::memcpy(est, hf, 128); std::memcpy(lower, hf + 32, 128);
         std::memcpy(lower_stage1, hf + 64, 128);
+    });
+}
+
+int cph_debug_estimator(cph_index* h, const uint8_t* lut, const float* qparams, uint32_t first, uint32_t count, const float* dqp,
+                        uint32_t n_dqp, const float* force, const uint32_t* fmask, uint32_t n_sets, uint32_t* out) {
+    return guarded([&] {
+        if (!lut || !qparams || !dqp || !force || !fmask || !out) throw InvalidArg("bad arguments");
+        if (count == 0 || count > 1024 || n_dqp == 0 || n_dqp > 64 || n_sets == 0 || n_sets > 64) throw InvalidArg("bad arguments");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        if (h->bits < 2) throw InvalidArg("the N-bit estimator: bits must be 2 or 4");
+        if ((uint64_t)first + count > h->host.n) throw InvalidArg("vertex out of range");     // (vertices of the graph, like cph_fastscan_block)
+        h->use_device();
+        const uint32_t D = h->D, PW = h->L.PW;
+        std::vector<uint8_t> qu(D);
+        lut_to_qu(lut, D, qu.data());
+        std::vector<uint32_t> masks(PW * 4);
+        qu_to_masks(qu.data(), D, masks.data());
+        const size_t words = (size_t)count * n_sets * n_dqp * 6 * 32;
+        DevBuf<uint4> d_mask(PW);
+        DevBuf<float> d_dqp(n_dqp), d_force((size_t)n_sets * 3);
+        DevBuf<uint32_t> d_fmask(n_sets), d_out(words);
+        HIP_CHECK(hipMemcpy(d_mask.p, masks.data(), PW * 16, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_dqp.p, dqp, n_dqp * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_force.p, force, (size_t)n_sets * 12, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_fmask.p, fmask, n_sets * 4, hipMemcpyHostToDevice));
+        EstimatorTestArgs a{};
+        a.blocks = h->d_blocks.p + (size_t)first * h->L.stride;
+        a.L = h->L;
+        a.qmask = d_mask.p;
+        a.qp = QP{qparams[0], qparams[1], qparams[2], qparams[3], qparams[4], qparams[5], qparams[6]};
+        a.dqp = d_dqp.p; a.force = d_force.p; a.fmask = d_fmask.p;
+        a.n_dqp = n_dqp; a.n_sets = n_sets;
+        a.out = d_out.p;
+        CPH_LAUNCH(estimator_selftest_kernel, h->bits, D, dim3(count), dim3(64), (size_t)PW * 16, nullptr, a);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_out.p, words * 4, hipMemcpyDeviceToHost));
     });
 }
 

@@ -45,6 +45,51 @@ struct LaneEst {      // per-lane (neighbour i = lane & 31) results, valid on al
 __device__ __forceinline__ float vmaxf(float a, float b) { return a > b ? a : b; }  // _mm256_max_ps
 __device__ __forceinline__ float vminf(float a, float b) { return a < b ? a : b; }  // _mm256_min_ps
 
+// max(a, b) / max(a, 0) as ONE v_max_f32.  vmaxf compiles to a compare and a select (and a hazard s_nop between them)
+// wherever the compiler cannot prove an operand canonical -- anything loaded from memory -- and __builtin_fmaxf puts a
+// canonicalising v_max_f32 x, x in front of such an operand.  The instruction returns the other operand for a quiet NaN
+// (vmaxf returns b for a NaN a, and a NaN for a NaN b) and +0 for (+0, -0): every caller says why it cannot tell.
+// (b wave-uniform: read from its scalar register, no copy into a vector register first)
+__device__ __forceinline__ float max1_su(float a, float b_uniform) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b_uniform));
+    return r;
+}
+__device__ __forceinline__ float max0(float a) {
+    float r;
+    asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+
+// Whether a wave-uniform squared distance lies in [kEpsSmall, +inf): one unsigned comparison of its bits (the bits of
+// non-negative floats are ordered like their values; a set sign bit, -0 included, +inf and every NaN land outside).
+__device__ __forceinline__ bool dqp_in_range(uint32_t dqp_bits) {
+    constexpr uint32_t lo = __builtin_bit_cast(uint32_t, kEpsSmall);
+    return dqp_bits - lo < 0x7F800000u - lo;
+}
+
+// sqrt(x) for kEpsSmall <= x < +inf: the compiler's own correctly rounded expansion of __builtin_sqrtf (v_sqrt_f32 is
+// good to 1 ulp; the two neighbouring floats' residuals x - n * s pick the rounded root) WITHOUT the two arms that are
+// identities in this range, seven of its sixteen instructions:
+//   * inputs below 2^-96 are multiplied by 2^32 first and the root by 2^-16 afterwards (a compare, two products, two
+//     selects): never taken, 1e-12 > 2^-96 -- the selects return x and the root unchanged;
+//   * zero and +inf are passed through by a v_cmp_class and a select: zero cannot arrive, and for +inf the sequence
+//     below gives +inf by itself (v_sqrt_f32(+inf) = +inf; both residuals are NaN -- inf * FLT_MAX - inf and a NaN
+//     neighbour -- so neither compare holds and the root stays).
+// A NaN x gives v_sqrt_f32's quiet NaN in both (the residuals are NaN, no select fires; the class test does not match a
+// NaN).  So the bits are __builtin_sqrtf's for every normal x >= 1e-12, +inf and NaN; zero, denormals and everything
+// else below 1e-12 must not be passed (the callers' wave-uniform range test keeps them out, with +inf and NaN).
+__device__ __forceinline__ float sqrt_in_range(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float dn = __uint_as_float(__float_as_uint(s) - 1u);
+    const float up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rdn = __fmaf_rn(-dn, s, x);
+    const float rup = __fmaf_rn(-up, s, x);
+    float r = (rdn <= 0.0f) ? dn : s;
+    r = (rup > 0.0f) ? up : r;
+    return r;
+}
+
 // popcount(x) + acc in ONE instruction: v_bcnt_u32_b32 has an accumulate operand.  Written as inline assembly
 // because the compiler, given `acc += __popc(x)`, emits the popcounts with a zero addend and then re-associates
 // the sums into a tree of v_add3 (shorter chains, a quarter more instructions -- and this kernel is bound by
@@ -498,6 +543,76 @@ __device__ __forceinline__ float stage2_est_only(const QP& q, const LaneEst& v, 
     e = __fmaf_rn(q.affine_a, e, q.affine_b);
     float dist = __fmaf_rn(v.nop, v.nop, dqp);
     dist = __fmaf_rn(-(2.0f * v.nop), e, dist);
+    return vmaxf(dist, 0.0f);
+}
+
+// ---- the same two functions for the static-D search kernels, with fewer vector instructions ------------------------
+// (profiles/estimator_valu.md).  The runtime-D kernels and `<2,128,true>` keep the forms above: their register allocation
+// does not survive this one (device_search_expansion.inc: kLeanEstimator).  lower_bounds_split as above, with the clamp
+// and the two maxima in one instruction each and the square root taken by sqrt_in_range.  Requires
+// kEpsSmall <= dqp < +inf (dqp_in_range: the caller tests that wave-uniform fact).
+//
+// NaN and signed zero at the three one-instruction sites (v_max_f32 / v_med3_f32 return the non-NaN operand where the
+// compare-and-select forms of stage1_lower kept a NaN):
+//   ipq = max(ip_qo, floor): differs from `ip_qo < floor ? floor : ip_qo` only for a NaN ip_qo (floor instead of NaN),
+//     which no builder writes; it is then est_and_lower's _mm256_max_ps.  ipq = -0 against +0 ends in `ipq > 1e-10` false.
+//   clamp = med3(c, -1, 1): c is NaN only for a NaN among the aux values or inf / inf, and sqrt_dqp is finite here
+//     while (num - ip_cp) / ipq with ipq > 1e-10 overflows for no finite aux value a builder can write (|num - ip_cp|
+//     would have to exceed 3.4e28); with ipq <= 1e-10 the bound is 0 whatever c was.  c = -0 or +0 multiplies a
+//     finite product: the sum differs at most in the sign of a zero.
+//   max(lo, 0): with dqp, sqrt_dqp finite and c in [-1, 1], lo is NaN only if nop is NaN or nop * nop + dqp overflows
+//     (a row that far from its parent has no finite distance to a query either); a zero result may differ in sign.  The readers of the bounds are `lo1 < worst0` and `!(lower >= worst0)` (votes, cand,
+//     the replay masks): neither sees the sign of a zero.
+//   (A +inf or NaN dqp -- an overflowed norm -- would make lo NaN for every finite nop, where stage 1 keeps the NaN and
+//   stage 2's max drops it: the caller sends those to the separate functions, with the tiny distances.)
+// `sh` hands ipq and nop^2 + dqp to stage2_est_only.
+struct EstShared {
+    float ipq;      // max(ip_qo, floor)
+    float nn_dqp;   // fma(nop, nop, dqp)
+};
+template <int BW>
+__device__ __forceinline__ void lower_bounds_split(const QP& q, const LaneEst& v, float dqp, float sqrt_dqp,
+                                                   int lane, float& lo_stage1, float& lo_stage2, const TailLanes& tl,
+                                                   EstShared& sh) {
+    static_assert(BW >= 2, "N-bit path");
+    const float invk = 1.0f / 3.0f;
+    const float n1 = __fmaf_rn(q.B * invk, (float)v.pop, (q.A * invk) * (float)v.msb2) + q.C;   // (a scalar loop: no tail of its own)
+    const float n2 = ip_approx_msb(q.A, (float)v.msb, q.B, (float)v.pop, q.C, tl);
+    const float num = lane >= 32 ? n2 : n1;
+    const float ipq = max1_su(v.ip_qo, q.floor);
+    const float nn = __fmaf_rn(v.nop, v.nop, dqp);
+    sh.ipq = ipq;
+    sh.nn_dqp = nn;
+    float e = (num - v.ip_cp) / ipq;
+    e = __fmaf_rn(e, q.affine_a, q.affine_b);
+    float c = (e + q.slack) / sqrt_dqp;
+    c = __builtin_amdgcn_fmed3f(c, -1.0f, 1.0f);
+    float lo = __fmaf_rn(-c, (v.nop + v.nop) * sqrt_dqp, nn);
+    lo = max0(lo);
+    lo = (ipq > kEpsMedium) ? lo : 0.0f;
+    uint32_t a, b;
+    half_pair(__float_as_uint(lo), a, b);
+    lo_stage1 = __uint_as_float(a);
+    lo_stage2 = __uint_as_float(b);
+}
+
+// stage2_est_only as above, without the tiny arm (out of range, see the caller) and with the two values shared.
+// `sh` = what lower_bounds_split computed for the same lane: max(ip_qo, floor), which is est_and_lower's _mm256_max_ps
+// for every ip_qo but a NaN (-> floor in both), and fma(nop, nop, dqp).  The last maximum stays vmaxf: its operand is an
+// fma's result, which the compiler knows to be canonical, so it is one v_max_f32 already -- the same bits as
+// est_and_lower's for every input, NaN (-> 0) and -0 (-> +0) included; est is a beam key and the numerator of the gamma
+// ratio e / ex, and both read what they read before.
+template <int BW>
+__device__ __forceinline__ float stage2_est_only(const QP& q, const LaneEst& v, const TailLanes& tl, const EstShared& sh) {
+    static_assert(BW >= 2, "N-bit path");
+    constexpr float K = (float)((1u << BW) - 1);
+    constexpr float invK = 1.0f / K;
+    const float ipn = ip_approx_est(q.A * invK, (float)v.nbit, q.B * invK, (float)v.wpop, q.C, tl);
+    float e = (ipn - v.ip_cp) / sh.ipq;
+    asm volatile("" : "+v"(e));
+    e = (sh.ipq > kEpsMedium) ? e : 0.0f;
+    e = __fmaf_rn(q.affine_a, e, q.affine_b);
+    const float dist = __fmaf_rn(-(2.0f * v.nop), e, sh.nn_dqp);
     return vmaxf(dist, 0.0f);
 }
 

@@ -220,48 +220,74 @@
             auto estimate = [&](bool fetched) -> bool {
                 LaneEst v;
                 const float dqp = exact_dist;
-                const float sq = __builtin_sqrtf(dqp);
                 bl.reduce(blk, a.L, qm, lane, v);
                 if constexpr (BW == 1) {
-                    stage2_est<1>(qp, v, dqp, sq, est, lower, tl);
+                    stage2_est<1>(qp, v, dqp, __builtin_sqrtf(dqp), est, lower, tl);
                 } else {
                     // both lower bounds at once, one per lane half (see lower_bounds_split); dqp is the popped vertex's
-                    // distance, the same in every lane
-                    float lo1 = 0.0f, lo2 = 0.0f;
-                    const bool tiny = bcast_f32(dqp) < kEpsSmall;
-                    if (!tiny) lower_bounds_split<BW>(qp, v, dqp, sq, lane, lo1, lo2, tl);
-                    // any_survivor (:178-187) ranges over ALL the list's neighbours, estimated before or not
-                    if (__builtin_expect((!ST && nn_sz < k) || any64(fetched && valid && lo1 < worst0), 1)) {
-                        est = stage2_est_only<BW>(qp, v, dqp, tl, tiny);
-                        lower = lo2;
-                    } else if constexpr (!kProbeFirst) {            // the reference's skipped batch (:201-205)
-                        est = FMAX;
-                        lower = lo1;
-                        skipped2 = true;
+                    // distance, the same in every lane.  Its usual range, 1e-12 <= dqp < +inf, is one scalar test; the
+                    // square root and the one-instruction maxima of the split bounds are only right inside it.  Outside
+                    // (the query is a base row, or a norm overflowed) the reference's own two functions run, which
+                    // test for the tiny distance themselves -- cold, and the estimate is made in front of the vote.
+                    // Both ranges end in the same three arms; `est_of` makes the estimate behind the vote.
+                    auto arms = [&](float lo1, float lo2, auto&& est_of) -> bool {
+                        // any_survivor (:178-187) ranges over ALL the list's neighbours, estimated before or not
+                        if (__builtin_expect((!ST && nn_sz < k) || any64(fetched && valid && lo1 < worst0), 1)) {
+                            est = est_of(v);
+                            lower = lo2;
+                        } else if constexpr (!kProbeFirst) {            // the reference's skipped batch (:201-205)
+                            est = FMAX;
+                            lower = lo1;
+                            skipped2 = true;
+                        } else {
+                            // Probe first: only the NEW neighbours' codes are here, and none of them survives stage 1.
+                            // Whether the reference runs stage 2 then depends on the bounds of neighbours it will skip
+                            // anyway (:227) -- which matters only if a new neighbour would ACT on its stage-2 values where
+                            // the skipped batch (est = FLT_MAX, lower = stage-1 bound >= worst) makes it do nothing: the two
+                            // bounds have different numerators (2 S0 + S1 over 3 against S0) and are not ordered.  No
+                            // rerank can happen before such a neighbour's turn without being such an action itself, so the
+                            // thresholds of the loop's entry decide: if no new neighbour passes them, both branches leave
+                            // the heaps alone and the block's other codes are never needed.  Else the query is handed to
+                            // the re-run launch, whose instantiation fetches whole blocks and takes the reference's
+                            // decision on the real bounds.  (The stage-1 bounds are loose -- the reference itself never
+                            // skips a batch on its own graphs, SURVEY F4 -- so neither happens outside the fixtures that
+                            // force it: 0 of 2.65 M expansions on the C2 benchmark.)
+                            // (The estimate is computed from a laundered copy of the sum: left recognisable, the compiler
+                            // merges this call with the one of the usual branch and hoists both above the ballot, which
+                            // measured 15 % slower on the C2 benchmark -- the estimate's division chain then sits in front
+                            // of the branch every expansion waits on.)
+                            LaneEst w = v;
+                            asm volatile("" : "+v"(w.nbit));
+                            est = est_of(w);
+                            lower = lo2;
+                            const bool acts = fetched && !(lo2 >= worst0) && (est < worst0 || est < gamma_q * worst0);
+                            if (any64(acts)) return false;
+                            undecided2 = true;
+                        }
+                        return true;
+                    };
+                    // The static-D forms of the two functions are for the static-D kernels; the runtime-D kernels and
+                    // `<2,128,true>` keep the generic square root and the bounds as they were: their register allocation
+                    // does not survive the other form (`<2,0,true>` spills a vector register more; `<2,128,true>` takes
+                    // 80 registers instead of 78, the ceiling tests/test_steady_loop_resources.py holds it to).
+                    constexpr bool kLeanEstimator = SD >= 128 && !(BW == 2 && SD == 128 && kProbeFirst);
+                    if constexpr (!kLeanEstimator) {
+                        float lo1 = 0.0f, lo2 = 0.0f;
+                        const bool tiny = bcast_f32(dqp) < kEpsSmall;
+                        if (!tiny) lower_bounds_split<BW>(qp, v, dqp, __builtin_sqrtf(dqp), lane, lo1, lo2, tl);
+                        return arms(lo1, lo2, [&](const LaneEst& x) { return stage2_est_only<BW>(qp, x, dqp, tl, tiny); });
+                    } else if (__builtin_expect(dqp_in_range(__builtin_amdgcn_readfirstlane(__float_as_uint(dqp))), 1)) {
+                        float lo1, lo2;
+                        EstShared sh;
+                        lower_bounds_split<BW>(qp, v, dqp, sqrt_in_range(dqp), lane, lo1, lo2, tl, sh);
+                        return arms(lo1, lo2, [&](const LaneEst& x) { return stage2_est_only<BW>(qp, x, tl, sh); });
                     } else {
-                        // Probe first: only the NEW neighbours' codes are here, and none of them survives stage 1.
-                        // Whether the reference runs stage 2 then depends on the bounds of neighbours it will skip
-                        // anyway (:227) -- which matters only if a new neighbour would ACT on its stage-2 values where
-                        // the skipped batch (est = FLT_MAX, lower = stage-1 bound >= worst) makes it do nothing: the two
-                        // bounds have different numerators (2 S0 + S1 over 3 against S0) and are not ordered.  No
-                        // rerank can happen before such a neighbour's turn without being such an action itself, so the
-                        // thresholds of the loop's entry decide: if no new neighbour passes them, both branches leave
-                        // the heaps alone and the block's other codes are never needed.  Else the query is handed to
-                        // the re-run launch, whose instantiation fetches whole blocks and takes the reference's
-                        // decision on the real bounds.  (The stage-1 bounds are loose -- the reference itself never
-                        // skips a batch on its own graphs, SURVEY F4 -- so neither happens outside the fixtures that
-                        // force it: 0 of 2.65 M expansions on the C2 benchmark.)
-                        // (The estimate is computed from a laundered copy of the sum: left recognisable, the compiler
-                        // merges this call with the one of the usual branch and hoists both above the ballot, which
-                        // measured 15 % slower on the C2 benchmark -- the estimate's division chain then sits in front
-                        // of the branch every expansion waits on.)
-                        LaneEst w = v;
-                        asm volatile("" : "+v"(w.nbit));
-                        est = stage2_est_only<BW>(qp, w, dqp, tl, tiny);
-                        lower = lo2;
-                        const bool acts = fetched && !(lo2 >= worst0) && (est < worst0 || est < gamma_q * worst0);
-                        if (any64(acts)) return false;
-                        undecided2 = true;
+                        // (+inf and NaN are in sqrt_in_range's domain; below 1e-12 neither function reads the root)
+                        const float sq = sqrt_in_range(dqp);
+                        float est_cold, lo2;
+                        const float lo1 = stage1_lower<BW>(qp, v, dqp, sq);
+                        stage2_est<BW>(qp, v, dqp, sq, est_cold, lo2, tl);
+                        return arms(lo1, lo2, [&](const LaneEst&) { return est_cold; });
                     }
                 }
                 return true;

@@ -838,6 +838,75 @@ int cph_debug_last_tag_filters_us(cph_index* h, double* us);
 int cph_host_tag_filters(const uint32_t* lims, const int32_t* tags, uint64_t n, const uint32_t* test_lims, const int32_t* test_vals,
                          const uint8_t* modes, uint32_t m, uint32_t* words_out, uint64_t* counts_out);
 
+/* ---- facet counts --------------------------------------------------------------------------- */
+/* Rows per distinct value of one column, under m filters at once (a terms aggregation: rows per tenant, per year, per
+ * ACL group among the rows a filter allows).  The column is named by (kind, slot): CPH_FACET_LABEL (slot ignored), an
+ * int32 column slot (CPH_FACET_COLUMN) or a tag column slot (CPH_FACET_TAGS).  Every column gets a DICTIONARY on first
+ * use: its distinct values ascending as int32 (INT32_MIN and INT32_MAX are ordinary; removed rows are included, so the
+ * list does not change under cph_remove; a tag column: the distinct tags of all rows), and one 32-bit code per row -- per
+ * CSR entry for a tag column -- resident on the device (4 B each).  U, the number of values, may be 0 (an index of size
+ * 0, a tag column whose rows are all empty).  The dictionary is dropped wherever the column changes (cph_set_labels,
+ * cph_set_column, cph_set_tags, cph_add for the label column, cph_compact, cph_build, cph_load, cph_load_native) and
+ * survives cph_remove, cph_set_row_map and cph_set_result_ids; a replica makes its own when asked.  A handle that never
+ * calls cph_facet_* allocates and launches nothing for facets.
+ *
+ * counts[j][u] = the rows i < size that filter j allows, that are not removed, and whose value is values[u] -- for a tag
+ * column: whose set holds values[u], so a row counts once per tag it holds and a row without tags adds nothing.
+ * Filters are internal-id bitmaps (any cph_filter of this size and device); every one goes through F & ~R on a handle
+ * with removed rows; a NULL entry, or filters == NULL with m == 1, means all live rows -- on a handle without removed
+ * rows that reads no bitmap at all.
+ *
+ * cph_facet_prepare   makes the dictionary now instead of on the first call.
+ * cph_facet_values    *U, and with values != NULL the U values.
+ * cph_facet_counts    counts_out[m][U] (uint64).  One launch per group of filters (csrc/device_facets.h): up to 8,192
+ *                     values (cph_facet_onchip_limit) a workgroup counts into LDS histograms and flushes its non-zero
+ *                     bins with one 64-bit atomic each; above that, 64-bit global atomics.  Counters are 64-bit: no size
+ *                     the handle accepts overflows them.  The device slab of one launch holds at most 2^22 counters (32
+ *                     MiB; cph_facet_slab_counters): when m * U exceeds that the filters are walked in groups (a single
+ *                     filter always gets its U counters).  One wait, for the outputs -- plus, on a handle with removed rows,
+ *                     one pass and one wait per filter whose F & ~R is not cached yet (the first use after a
+ *                     cph_remove, as in the search entries).  The caller sizes counts_out from cph_facet_values and must
+ *                     not change the column in between.  m == 0 is a no-op.
+ * cph_facet_top       per filter the K values (1 <= K <= 1024) with the largest non-zero counts, count descending and
+ *                     ties by value ascending: values_out[m][K], counts_out[m][K], found_out[j] = min(K, values with a
+ *                     non-zero count); slots at and behind found_out[j] hold value 0 and count 0.  A second launch, one
+ *                     workgroup per filter, selects on the device: only m * K pairs travel.
+ * CPH_INVALID_ARGUMENT, every output untouched: an unknown kind, a slot out of range or without a column, a handle that is
+ *                     not finalized, a filter of another size or device, filters == NULL with m > 1, K outside [1, 1024].
+ *                     Allowed on a borrowed replica or part handle. */
+enum { CPH_FACET_LABEL = 0, CPH_FACET_COLUMN = 1, CPH_FACET_TAGS = 2 };
+enum { CPH_FACET_PATH_AUTO = 0, CPH_FACET_PATH_ONCHIP = 1, CPH_FACET_PATH_GLOBAL = 2 };
+enum { CPH_FACET_HOOK_GUARD = 64 };
+int cph_facet_onchip_limit(void);
+uint64_t cph_facet_slab_counters(void);
+int cph_facet_prepare(cph_index* h, int kind, uint32_t slot);
+int cph_facet_values(cph_index* h, int kind, uint32_t slot, uint64_t* U, int32_t* values);
+int cph_facet_counts(cph_index* h, int kind, uint32_t slot, const cph_filter* const* filters, uint32_t m, uint64_t* counts_out);
+int cph_facet_top(cph_index* h, int kind, uint32_t slot, const cph_filter* const* filters, uint32_t m, uint32_t K, int32_t* values_out,
+                  uint64_t* counts_out, uint32_t* found_out);
+/* Debug hooks, as cph_debug_time_tag_filters: while on, the launches of every cph_facet_counts / cph_facet_top of this
+ * handle are bracketed by two HIP events (off by default; no event is recorded while off).  cph_debug_facet_slab lowers
+ * the slab bound of this handle to `counters` (0: the default again), so that the group walk shows at small shapes. */
+int cph_debug_time_facets(cph_index* h, int on);
+int cph_debug_last_facets_us(cph_index* h, double* us);
+int cph_debug_facet_slab(cph_index* h, uint64_t counters);
+/* Host statements (no HIP call).  column: one int32 per row (lims == NULL, n_entries == n), or the tags of a CSR
+ * lims[n + 1] (64-bit, canonicalised like cph_set_tags, with its refusals).  words: m bitmaps of (n + 31) / 32 words one
+ * behind the other, or NULL (every filter allows every row); removed: a bitmap of removed rows, or NULL.  The outputs
+ * are those of cph_facet_values / cph_facet_counts / cph_facet_top. */
+int cph_host_facet_values(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, uint64_t* U, int32_t* values);
+int cph_host_facet_counts(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, const uint32_t* words,
+                          const uint32_t* removed, uint32_t m, uint64_t* counts_out);
+int cph_host_facet_top(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, const uint32_t* words,
+                       const uint32_t* removed, uint32_t m, uint32_t K, int32_t* values_out, uint64_t* counts_out, uint32_t* found_out);
+/* The production counting launcher on host arrays: codes[n_entries] (each < U), lims[n + 1] (uint32) for a tag column or
+ * NULL for a dense one, words as above (uploaded at the 256 B-aligned slab stride; NULL: no bitmap is read).  `path`
+ * forces the on-chip or the global counting path, or leaves the choice to the launcher (CPH_FACET_PATH_*; on-chip above
+ * cph_facet_onchip_limit() is refused).  counts_out[m * U + CPH_FACET_HOOK_GUARD]: the device output is pre-filled with
+ * 0xA5 bytes; the m * U counters come back, then the guard words behind them as the device left them. */
+int cph_facet_hook(int device, const uint32_t* codes, uint64_t n_entries, const uint32_t* lims, uint64_t n, uint32_t U,
+                   const uint32_t* words, uint32_t m, int path, uint64_t* counts_out, double* kernel_us);
+
 /* Single query; writes m <= max(k,1) results (unpadded, src/bindings.cpp:146-175). */
 int cph_search(cph_index* h, const float* query, uint64_t k, int64_t* ids, float* dist,
                uint64_t* m);

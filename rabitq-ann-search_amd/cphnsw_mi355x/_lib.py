@@ -204,6 +204,21 @@ SYMBOLS = {
     "cph_debug_last_tag_filters_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "cph_host_tag_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p]),
+    "cph_facet_onchip_limit": (C.c_int, []),
+    "cph_facet_slab_counters": (C.c_uint64, []),
+    "cph_facet_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "cph_facet_values": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p]),
+    "cph_facet_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_facet_top": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_debug_time_facets": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_debug_last_facets_us": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "cph_debug_facet_slab": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_host_facet_values": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]),
+    "cph_host_facet_counts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cph_host_facet_top": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cph_facet_hook": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
+                                 C.c_void_p, C.POINTER(C.c_double)]),
     "cph_multi_set_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
     "cph_parts_set_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
     "cph_parts_filters_from_tags": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

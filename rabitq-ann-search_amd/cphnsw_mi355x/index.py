@@ -491,7 +491,9 @@ class CPIndex:
     def part(self, i):
         """Part i of a partitioned index as a single-device CPIndex over its slice: a borrowed view (the partitioned
         index owns it and must outlive it) that returns slice-local input rows; add parts[i][0] for global rows.  Its
-        hooks, row_map() and get_vectors work as on any index; load, build and finalize on it are refused."""
+        hooks, row_map() and get_vectors work as on any index; load, build and finalize on it are refused.  The view knows
+        the names of the index' columns and tag columns (set before or after it was made): column(), column_filters,
+        tag_filters, where and facet on it read the part's slice of them."""
         self._need_parts("part()")
         i = int(i)
         if not 0 <= i < len(self._devices):
@@ -508,8 +510,8 @@ class CPIndex:
         v._devices = [self._devices[i]]
         v._result_ids = "input" if self.is_finalized else "internal"
         v._exact_threshold = self._exact_threshold
-        v._columns = {}
-        v._tag_columns = {}
+        v._columns = self._column_slots()                # shared with the index: a part holds its slice of every column in
+        v._tag_columns = self._tag_slots()               # the same slot, so the view sees the names set before and after it was made
         return v
 
     def _need_parts(self, what):
@@ -1082,6 +1084,96 @@ class CPIndex:
         """Device time (HIP events, microseconds) of the last tag_filters pass made under time_tag_filters(): the longest
         of the replicas' / parts' passes."""
         return max(self._last_pass_us("cph_debug_last_tag_filters_us", r) for r in range(len(self._replicas())))
+
+    # -- facet counts: rows per column value under filters (not in the reference) --------------------
+    MAX_FACET_TOP = 1024             # K of facet(top=K), at most
+    _FACET_LABEL, _FACET_COLUMN, _FACET_TAGS = 0, 1, 2      # CPH_FACET_*
+
+    def _facet_column(self, name):
+        """(kind, slot) of the column `name` for the cph_facet_* calls: "label", an attribute column or a tag column."""
+        if self._p is not None:
+            raise ValueError("facet is not defined on a partitioned index (every part has its own dictionary and merging "
+                             "them is not done here): use part(i).facet")
+        if not isinstance(name, str):
+            raise ValueError("a column name must be a string")
+        if name == "label":
+            self._slot(name)
+            return self._FACET_LABEL, 0
+        if name in self._tag_slots():
+            return self._FACET_TAGS, self._tag_slot(name)
+        if name not in self._column_slots():
+            raise ValueError(f"the index has no column {name!r}: call set_column or set_tags first")
+        return self._FACET_COLUMN, self._slot(name)
+
+    def prepare_facets(self, name):
+        """Builds the facet dictionary of column `name` now (its distinct values, and one code per row on the device:
+        4 B per row, per tag for a tag column) instead of on the first facet() call."""
+        kind, slot = self._facet_column(name)
+        _lib.check(_lib.lib().cph_facet_prepare(self._h, kind, slot))
+
+    def facet(self, name, filter=None, top=None):
+        """Rows per distinct value of column `name` ("label": the label column; an attribute column; a tag column)
+        among the rows a filter allows, counted on the device: (values int32 [U] ascending, counts int64 [U]).
+        `values` are the distinct values of the whole column, removed rows included (the list does not change under
+        remove(); their count goes to 0); for a tag column the distinct tags, and a row counts once per tag it holds.
+        counts[u] = rows that the filter allows, that are not removed, and whose value is (whose set holds) values[u].
+        filter: None (all live rows), one filter (an IdFilter or anything make_filter accepts), or a list of m of them:
+        counts is then int64 [m, U], made in one device pass per 2^22 counters; an empty list gives [0, U].
+        top=K (1 <= K <= MAX_FACET_TOP): (values int32 [m, K], counts int64 [m, K], found int32 [m]) instead -- per filter
+        the K values with the largest non-zero counts, count descending and ties by value ascending, selected on the
+        device; found[j] = min(K, values with a non-zero count), the slots behind it hold 0 (a single filter: [K], [K]
+        and an int).  Not changed by result_ids or set_row_map: filters are internal-id bitmaps once made.  The call
+        waits for its outputs.  A replicated index answers from its first replica; a partitioned one raises (use
+        part(i).facet).  The dictionary is built on the first call for a column (prepare_facets) and kept until the
+        column changes.  Like every call that reads a column, facet() must not run while another thread changes that
+        column (set_labels, set_column, set_tags, add, compact, build, load): the outputs are sized from the dictionary
+        the call saw first.  On an index with removed rows every filter is first narrowed to its live rows (one more
+        device pass and wait per filter the first time it is used after a remove(); cached with the filter after that).
+        ValueError: an unknown column, an index that is not finalized, a closed filter or one of another
+        size, device or replica count, top outside [1, MAX_FACET_TOP]."""
+        if top is not None and (isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= int(top) <= self.MAX_FACET_TOP):
+            raise ValueError(f"top must be an integer in [1, {self.MAX_FACET_TOP}]")
+        kind, slot = self._facet_column(name)
+        L = _lib.lib()
+        single = not isinstance(filter, list)
+        given = [filter] if single else list(filter)
+        fs = []
+        try:
+            for f in given:
+                fs.append(None if f is None else self._filter(f))
+            U = C.c_uint64(0)
+            _lib.check(L.cph_facet_values(self._h, kind, slot, C.byref(U), None))
+            values = np.empty(U.value, np.int32)
+            _lib.check(L.cph_facet_values(self._h, kind, slot, C.byref(U), values.ctypes.data if values.size else None))
+            m = len(fs)
+            table = (C.c_void_p * m)(*[None if f is None else f._hs[0].value for f in fs]) if m else None
+            if top is None:
+                counts = np.zeros((m, U.value), np.uint64)
+                if m:
+                    _lib.check(L.cph_facet_counts(self._h, kind, slot, table, m, counts.ctypes.data if counts.size else None))
+                counts = counts.view(np.int64)              # (counts stay below 2^32: the same bits)
+                return (values, counts[0]) if single else (values, counts)
+            K = int(top)
+            tv, tc, found = np.zeros((m, K), np.int32), np.zeros((m, K), np.uint64), np.zeros(m, np.uint32)
+            if m:
+                _lib.check(L.cph_facet_top(self._h, kind, slot, table, m, K, tv.ctypes.data, tc.ctypes.data, found.ctypes.data))
+            tc, found = tc.view(np.int64), found.view(np.int32)
+            return (tv[0], tc[0], int(found[0])) if single else (tv, tc, found)
+        finally:
+            for made, g in zip(fs, given):          # the filters this call made are freed now, not by the collector
+                if made is not None and made is not g:
+                    made.close()
+
+    def time_facets(self, on=True):
+        """Debug hook of the measurement script: while on, the launches of every facet() call are bracketed by HIP events
+        (last_facets_us).  Off by default."""
+        _lib.check(_lib.lib().cph_debug_time_facets(self._h, int(bool(on))))
+
+    def last_facets_us(self):
+        """Device time (HIP events, microseconds) of the launches of the last facet() call made under time_facets()."""
+        us = C.c_double(0)
+        _lib.check(_lib.lib().cph_debug_last_facets_us(self._h, C.byref(us)))
+        return us.value
 
     def combine_filters(self, op, filters, other=None):
         """[IdFilter]: filters[j] OP other, made and counted on the device in one pass (module function

@@ -35,6 +35,7 @@
 #include "device_tombstone.h"
 #include "device_labels.h"
 #include "device_tags.h"
+#include "device_facets.h"
 #include "device_filter_ops.h"
 #include "device_exact.h"
 #include "device_range.h"
@@ -236,7 +237,16 @@ constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the 
 // inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
 // rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
 // same way.
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassUntimed, kPassKinds };
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassUntimed, kPassKinds };
+
+// The facet dictionary of one column (cph_facet_*; device_facets.h): its distinct values ascending, on both sides, and one
+// 32-bit code per row -- per CSR entry for a tag column -- on the device.  Made on first use, dropped when the column changes.
+struct FacetDict {
+    std::vector<int32_t> values;
+    DevBuf<int32_t> d_values;
+    DevBuf<uint32_t> codes;
+};
+constexpr uint32_t kFacetColumns = 1 + kMaxColumns + kMaxTagColumns;      // the label column, the int32 columns, the tag columns
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -332,6 +342,17 @@ struct cph_index {
     DevBuf<int32_t> d_tag_vals[kMaxTagColumns];
     DevBuf<unsigned long long> d_tag_counts;
     bool has_tags[kMaxTagColumns] = {};
+    // facet counts (cph_facet_*): the dictionary of every column that was asked for one (label | columns | tag columns), and
+    // the call buffers -- the counter slab of at most facet_slab counters (cph_debug_facet_slab; a single filter's U may
+    // exceed it), the filter table, the outputs of the top kernel -- which only grow.  A handle that never called
+    // cph_facet_* allocates none of this.
+    std::unique_ptr<FacetDict> facets[kFacetColumns];
+    DevBuf<unsigned long long> d_facet_counts, d_facet_top_counts;
+    DevBuf<const uint32_t*> d_facet_tab;
+    DevBuf<int32_t> d_facet_top_values;
+    DevBuf<uint32_t> d_facet_found;
+    uint64_t facet_slab = kFacetSlabCounters;
+    void drop_facets() { for (auto& d : facets) d.reset(); }
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
@@ -484,6 +505,7 @@ bool has_tag_columns(const cph_index* h) {
 // made sure nothing reads the old one.
 void upload_tags(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_t* tags, uint64_t n) {
     h->has_tags[slot] = lims != nullptr;
+    h->facets[1 + kMaxColumns + slot].reset();
     h->d_tag_lims[slot].release();
     h->d_tag_vals[slot].release();
     if (!lims) return;
@@ -498,6 +520,7 @@ void upload_tags(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_
 // or none (a load or a build leaves none).
 void sync_labels(cph_index* h) {
     h->label_rows.reset();
+    h->drop_facets();
     for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {
         const std::vector<uint32_t>& lims = h->host.tag_lims[slot];
         if (lims.empty() && !h->has_tags[slot]) continue;        // (an index without tags: nothing to do)
@@ -610,6 +633,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed rescored search has run on this handle (cph_debug_time_rescored)",
     "no timed fused search has run on this handle (cph_debug_time_fused)",
     "no timed tag pass has run on this handle (cph_debug_time_tag_filters)",
+    "no timed facet pass has run on this handle (cph_debug_time_facets)",
     "this pass is not timed",
 };
 
@@ -1893,7 +1917,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 117; }
+int cph_version(void) { return 118; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -1991,6 +2015,7 @@ static void begin_device_swap(cph_index* h) {
     h->last_range = false;
     h->range_scratch.clear();
     h->label_rows.reset();
+    h->drop_facets();
     ++h->index_epoch;
 }
 
@@ -3264,6 +3289,7 @@ void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool
     quiesce(h);                                  // a grouped batch in flight may be reading the old column
     const ColumnRef c = column_of(h, slot);
     if (slot == kLabelSlot) h->label_rows.reset();      // (idle: quiesce above)
+    h->facets[1 + slot].reset();                         // (kLabelSlot is -1: the label column's dictionary is entry 0)
     if (!labels) {
         std::vector<int32_t>().swap(c.host);
         c.has = false;
@@ -3631,6 +3657,335 @@ int cph_host_tag_filters(const uint32_t* lims, const int32_t* tags, uint64_t n, 
         tags_canonical_host(wide.data(), tags, n, nullptr, 0, cl, cv);
         tag_tests_canonical_host(test_lims, test_vals, modes, m, tl, tv);
         tag_filters_host(cl.data(), cv.data(), n, tl.data(), tv.data(), modes, m, words_out, counts_out);
+    });
+}
+
+}  // extern "C"
+
+// ---- facet counts (device_facets.h) -------------------------------------------------------------
+// Rows per distinct value of one column under m filters at once: a dictionary per column (made on first use, dropped
+// with the column), one counting launch per group of filters, and for `top` one selection launch behind it.
+namespace {
+
+// The dictionary slot of (kind, slot) in cph_index::facets; refuses an unknown kind and a slot out of range.
+uint32_t facet_column(int kind, uint32_t slot) {
+    if (kind == CPH_FACET_LABEL) return 0;
+    if (kind == CPH_FACET_COLUMN) {
+        require_slot(slot);
+        return 1 + slot;
+    }
+    if (kind == CPH_FACET_TAGS) {
+        require_tag_slot(slot);
+        return 1 + kMaxColumns + slot;
+    }
+    throw InvalidArg("facet column kind must be CPH_FACET_LABEL, CPH_FACET_COLUMN or CPH_FACET_TAGS");
+}
+
+// The caller holds the handle mutex.  The dictionary of the column, made now if it is not there: from the host copy of
+// the column, or (a replica without host arrays) from a copy of the resident one.
+FacetDict& facet_dict_locked(cph_index* h, int kind, uint32_t slot) {
+    const uint32_t at = facet_column(kind, slot);
+    if (!h->finalized) throw InvalidArg("facets belong to a finalized index: finalize or load it first");
+    const bool tags = kind == CPH_FACET_TAGS;
+    if (tags ? !h->has_tags[slot] : !column_of(h, kind == CPH_FACET_LABEL ? kLabelSlot : (int)slot).has)
+        throw InvalidArg(kind == CPH_FACET_LABEL ? "the index has no label column: call cph_set_labels first"
+                         : tags ? "the index has no tag column in slot " + std::to_string(slot) + ": call cph_set_tags first"
+                                : "the index has no column in slot " + std::to_string(slot) + ": call cph_set_column first");
+    if (h->facets[at]) return *h->facets[at];
+    h->use_device();
+    const uint64_t n = h->size();
+    std::vector<int32_t> fetched;
+    const int32_t* src = nullptr;
+    uint64_t entries = 0;
+    if (tags) {
+        const std::vector<uint32_t>& hl = h->host.tag_lims[slot];
+        if (hl.size() == n + 1) {
+            entries = hl[n];
+            src = h->host.tag_vals[slot].data();
+        } else {
+            uint32_t last = 0;
+            HIP_CHECK(hipMemcpy(&last, h->d_tag_lims[slot].p + n, 4, hipMemcpyDeviceToHost));
+            entries = last;
+            fetched.resize(entries);
+            if (entries) HIP_CHECK(hipMemcpy(fetched.data(), h->d_tag_vals[slot].p, entries * 4, hipMemcpyDeviceToHost));
+            src = fetched.data();
+        }
+    } else {
+        const ColumnRef c = column_of(h, kind == CPH_FACET_LABEL ? kLabelSlot : (int)slot);
+        entries = n;
+        if (c.host.size() == n) {
+            src = c.host.data();
+        } else {
+            fetched.resize(n);
+            if (n) HIP_CHECK(hipMemcpy(fetched.data(), c.dev.p, n * 4, hipMemcpyDeviceToHost));
+            src = fetched.data();
+        }
+    }
+    std::unique_ptr<FacetDict> d(new FacetDict());
+    std::vector<uint32_t> codes;
+    facet_dictionary_host(src, entries, d->values, codes);
+    d->codes.alloc(codes.size());
+    d->d_values.alloc(d->values.size());
+    if (!codes.empty()) HIP_CHECK(hipMemcpy(d->codes.p, codes.data(), codes.size() * 4, hipMemcpyHostToDevice));
+    if (!d->values.empty()) HIP_CHECK(hipMemcpy(d->d_values.p, d->values.data(), d->values.size() * 4, hipMemcpyHostToDevice));
+    h->facets[at] = std::move(d);
+    return *h->facets[at];
+}
+
+// cph_facet_counts (K == 0: counts_out [m][U]) and cph_facet_top (K >= 1: values_out / counts_out [m][K], found_out [m]).
+// Every refusal comes before the first write.  filters: m entries, or null with m == 1; a null entry is "all live rows".
+void facet_query(cph_index* h, int kind, uint32_t slot, const cph_filter* const* filters, uint32_t m, uint32_t K, bool top,
+                 int32_t* values_out, uint64_t* counts_out, uint32_t* found_out) {
+    if (!h) throw InvalidArg("null handle");
+    if (top && (K < 1 || K > kFacetTopMax)) throw InvalidArg("facet top must lie in [1, " + std::to_string(kFacetTopMax) + "]");
+    if (!filters && m > 1) throw InvalidArg("a null filter list stands for one filter (all live rows): m must be 1");
+    std::lock_guard<std::mutex> lk(h->mu);
+    facet_column(kind, slot);
+    if (!h->finalized) throw InvalidArg("facets belong to a finalized index: finalize or load it first");
+    for (uint32_t j = 0; filters && j < m; ++j)
+        if (filters[j]) check_filter(h, filters[j]);
+    FacetDict& d = facet_dict_locked(h, kind, slot);
+    if (m == 0) return;
+    if (top ? !values_out || !counts_out || !found_out : (!counts_out && !d.values.empty())) throw InvalidArg("null argument");
+    const uint64_t n = h->size();
+    const uint32_t U = (uint32_t)d.values.size();
+    if (U == 0) {                                   // (an empty index, a tag column without a tag: nothing to launch)
+        if (top) {
+            std::fill(values_out, values_out + (size_t)m * K, 0);
+            std::fill(counts_out, counts_out + (size_t)m * K, 0ull);
+            std::fill(found_out, found_out + m, 0u);
+        }
+        return;
+    }
+    h->use_device();
+    std::vector<std::shared_ptr<const cph_filter>> hold(m);      // F & ~R of a handle with removed rows; null: no bitmap is read
+    std::vector<const uint32_t*> tab(m);
+    bool any = false;
+    for (uint32_t j = 0; j < m; ++j) {
+        hold[j] = effective_filter(h, filters ? filters[j] : nullptr);
+        tab[j] = hold[j] ? hold[j]->words.p : nullptr;
+        any = any || tab[j];
+    }
+    const uint32_t group = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(h->facet_slab / U, 1), (uint64_t)kFacetMaxFilters, (uint64_t)m});
+    const uint32_t* d_lims = kind == CPH_FACET_TAGS ? h->d_tag_lims[slot].p : nullptr;
+    h->d_facet_counts.alloc((size_t)group * U);
+    hipStream_t st = own_stream(h);
+    if (any) {
+        h->d_facet_tab.alloc(m);
+        HIP_CHECK(hipMemcpyAsync(h->d_facet_tab.p, tab.data(), (size_t)m * sizeof(tab[0]), hipMemcpyHostToDevice, st));
+    }
+    if (top) {
+        h->d_facet_top_values.alloc((size_t)m * K);
+        h->d_facet_top_counts.alloc((size_t)m * K);
+        h->d_facet_found.alloc(m);
+    }
+    std::vector<unsigned long long> staged(top ? (size_t)m * K : 0);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counters go out as they are");
+    // (with more than one group the copies back of all but the last sit inside the timed bracket: the slab is reused)
+    timed_pass(h->pass_timer[kPassFacets], st, [&] {
+        for (uint32_t g0 = 0; g0 < m; g0 += group) {
+            const uint32_t mg = std::min(group, m - g0);
+            facet_counts(d.codes.p, d_lims, n, U, any ? h->d_facet_tab.p + g0 : nullptr, mg, h->d_facet_counts.p, kFacetAuto, st);
+            if (top)
+                facet_top(h->d_facet_counts.p, U, d.d_values.p, mg, K, h->d_facet_top_values.p + (size_t)g0 * K,
+                          h->d_facet_top_counts.p + (size_t)g0 * K, h->d_facet_found.p + g0, st);
+            else if (g0 + mg < m)
+                HIP_CHECK(hipMemcpyAsync(counts_out + (size_t)g0 * U, h->d_facet_counts.p, (size_t)mg * U * 8, hipMemcpyDeviceToHost, st));
+        }
+    });
+    if (top) {
+        HIP_CHECK(hipMemcpyAsync(values_out, h->d_facet_top_values.p, (size_t)m * K * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(staged.data(), h->d_facet_top_counts.p, (size_t)m * K * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(found_out, h->d_facet_found.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    } else {
+        const uint32_t g0 = (m - 1) / group * group;
+        HIP_CHECK(hipMemcpyAsync(counts_out + (size_t)g0 * U, h->d_facet_counts.p, (size_t)(m - g0) * U * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));            // the one wait of the call
+    if (top) std::copy(staged.begin(), staged.end(), counts_out);
+}
+
+// The host-only statements' column: dense (lims null: n_entries == n) or a caller's CSR, canonicalised like cph_set_tags.
+struct HostFacetColumn {
+    std::vector<uint32_t> lims;                    // tag column: canonical; empty for a dense one
+    std::vector<int32_t> values;
+    std::vector<uint32_t> codes;
+    bool tags = false;
+};
+void host_facet_column(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, HostFacetColumn& c) {
+    if (n >= 0xFFFFFFFFull) throw InvalidArg("facet counts cover fewer than 2^32 - 1 rows");
+    c.tags = lims != nullptr;
+    if (!lims) {
+        if (n_entries != n) throw InvalidArg("a dense facet column has one entry per row");
+        facet_dictionary_host(column, n, c.values, c.codes);
+        return;
+    }
+    if (lims[n] != n_entries) throw InvalidArg("facet limits end at " + std::to_string(lims[n]) + ", the column holds " + std::to_string(n_entries));
+    std::vector<int32_t> cv;
+    tags_canonical_host(lims, column, n, nullptr, 0, c.lims, cv);
+    facet_dictionary_host(cv.data(), cv.size(), c.values, c.codes);
+}
+
+// words: m bitmaps of (n + 31) / 32 words one behind the other, or null: every filter is "every row".
+std::vector<uint64_t> host_facet_counts(const HostFacetColumn& c, uint64_t n, const uint32_t* words, const uint32_t* removed, uint32_t m) {
+    const uint64_t nw = (n + 31) / 32, U = c.values.size();
+    std::vector<const uint32_t*> fs(m, nullptr);
+    for (uint32_t j = 0; words && j < m; ++j) fs[j] = words + (size_t)j * nw;
+    std::vector<uint64_t> counts((size_t)m * U);
+    facet_counts_host(c.codes.data(), c.tags ? c.lims.data() : nullptr, n, U, words ? fs.data() : nullptr, removed, m, counts.data());
+    return counts;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_facet_onchip_limit(void) { return (int)kFacetLdsBins; }
+uint64_t cph_facet_slab_counters(void) { return kFacetSlabCounters; }
+
+int cph_facet_prepare(cph_index* h, int kind, uint32_t slot) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        facet_dict_locked(h, kind, slot);
+    });
+}
+
+int cph_facet_values(cph_index* h, int kind, uint32_t slot, uint64_t* U, int32_t* values) {
+    return guarded([&] {
+        if (!h || !U) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        const FacetDict& d = facet_dict_locked(h, kind, slot);
+        *U = d.values.size();
+        if (values) std::copy(d.values.begin(), d.values.end(), values);
+    });
+}
+
+int cph_facet_counts(cph_index* h, int kind, uint32_t slot, const cph_filter* const* filters, uint32_t m, uint64_t* counts_out) {
+    return guarded([&] { facet_query(h, kind, slot, filters, m, 0, false, nullptr, counts_out, nullptr); });
+}
+
+int cph_facet_top(cph_index* h, int kind, uint32_t slot, const cph_filter* const* filters, uint32_t m, uint32_t K, int32_t* values_out,
+                  uint64_t* counts_out, uint32_t* found_out) {
+    return guarded([&] { facet_query(h, kind, slot, filters, m, K, true, values_out, counts_out, found_out); });
+}
+
+int cph_debug_time_facets(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassFacets, on != 0); });
+}
+
+int cph_debug_last_facets_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassFacets, us); });
+}
+
+int cph_debug_facet_slab(cph_index* h, uint64_t counters) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->facet_slab = counters ? counters : kFacetSlabCounters;
+    });
+}
+
+int cph_host_facet_values(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, uint64_t* U, int32_t* values) {
+    return guarded([&] {
+        if (!U || (n_entries != 0 && !column)) throw InvalidArg("null argument");
+        HostFacetColumn c;
+        host_facet_column(column, n_entries, lims, n, c);
+        *U = c.values.size();
+        if (values) std::copy(c.values.begin(), c.values.end(), values);
+    });
+}
+
+int cph_host_facet_counts(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, const uint32_t* words,
+                          const uint32_t* removed, uint32_t m, uint64_t* counts_out) {
+    return guarded([&] {
+        if (n_entries != 0 && !column) throw InvalidArg("null argument");
+        HostFacetColumn c;
+        host_facet_column(column, n_entries, lims, n, c);
+        if (m == 0 || c.values.empty()) return;
+        if (!counts_out) throw InvalidArg("null argument");
+        const std::vector<uint64_t> counts = host_facet_counts(c, n, words, removed, m);
+        std::copy(counts.begin(), counts.end(), counts_out);
+    });
+}
+
+int cph_host_facet_top(const int32_t* column, uint64_t n_entries, const uint64_t* lims, uint64_t n, const uint32_t* words,
+                       const uint32_t* removed, uint32_t m, uint32_t K, int32_t* values_out, uint64_t* counts_out, uint32_t* found_out) {
+    return guarded([&] {
+        if (K < 1 || K > kFacetTopMax) throw InvalidArg("facet top must lie in [1, " + std::to_string(kFacetTopMax) + "]");
+        if (n_entries != 0 && !column) throw InvalidArg("null argument");
+        HostFacetColumn c;
+        host_facet_column(column, n_entries, lims, n, c);
+        if (m == 0) return;
+        if (!values_out || !counts_out || !found_out) throw InvalidArg("null argument");
+        const std::vector<uint64_t> counts = host_facet_counts(c, n, words, removed, m);
+        const uint64_t U = c.values.size();
+        for (uint32_t j = 0; j < m; ++j)
+            facet_top_host(counts.data() + (size_t)j * U, c.values.data(), U, K, values_out + (size_t)j * K, counts_out + (size_t)j * K,
+                           found_out + j);
+    });
+}
+
+// The production launcher on host arrays: codes[n_entries] (< U), lims[n + 1] for a tag column (null: dense, n_entries ==
+// n), words: m bitmaps of (n + 31) / 32 words (null: no bitmap at all, every filter is "every row"), uploaded at the slab
+// stride.  counts_out: [m * U + CPH_FACET_HOOK_GUARD]: the counters, then the guard words behind them as the device left
+// them; everything starts as 0xA5 bytes.
+int cph_facet_hook(int device, const uint32_t* codes, uint64_t n_entries, const uint32_t* lims, uint64_t n, uint32_t U,
+                   const uint32_t* words, uint32_t m, int path, uint64_t* counts_out, double* kernel_us) {
+    return guarded([&] {
+        if (m == 0) return;
+        if (!counts_out || (n_entries != 0 && !codes)) throw InvalidArg("null argument");
+        if (n >= 0xFFFFFFFFull || n_entries > 0xFFFFFFFFull) throw InvalidArg("facet counts cover fewer than 2^32 - 1 rows");
+        if (U == 0 || m > kFacetMaxFilters) throw InvalidArg("the hook takes U >= 1 and at most " + std::to_string(kFacetMaxFilters) + " filters");
+        if ((uint64_t)m * U > (1ull << 28)) throw InvalidArg("the hook takes at most 2^28 counters");
+        if (lims) {                                  // every index the kernel forms is checked here, on the host
+            if (lims[0] != 0) throw InvalidArg("facet limits must start at 0");
+            for (uint64_t i = 0; i < n; ++i)
+                if (lims[i + 1] < lims[i]) throw InvalidArg("facet limits must not decrease (row " + std::to_string(i) + ")");
+            if (lims[n] != n_entries) throw InvalidArg("facet limits end at " + std::to_string(lims[n]) + ", the column holds " + std::to_string(n_entries));
+        } else if (n_entries != n) {
+            throw InvalidArg("a dense facet column has one entry per row");
+        }
+        for (uint64_t e = 0; e < n_entries; ++e)
+            if (codes[e] >= U) throw InvalidArg("facet code out of range (entry " + std::to_string(e) + ")");
+        facet_plan(n, U, m, path);                   // (refuses an unknown path, and the on-chip one above its limit)
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t nw = (n + 31) / 32, stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;
+        const size_t total = (size_t)m * U + CPH_FACET_HOOK_GUARD;
+        DevBuf<uint32_t> d_codes(std::max<uint64_t>(n_entries, 1)), d_lims(lims ? n + 1 : 1), d_words(words ? (size_t)m * stride : 1);
+        DevBuf<unsigned long long> d_counts(total);
+        DevBuf<const uint32_t*> d_tab(m);
+        HIP_CHECK(hipMemset(d_counts.p, 0xA5, total * 8));
+        if (n_entries) HIP_CHECK(hipMemcpy(d_codes.p, codes, n_entries * 4, hipMemcpyHostToDevice));
+        if (lims) HIP_CHECK(hipMemcpy(d_lims.p, lims, (n + 1) * 4, hipMemcpyHostToDevice));
+        if (words) {
+            HIP_CHECK(hipMemset(d_words.p, 0xA5, (size_t)m * stride * 4));      // (what lies between the bitmaps must not count)
+            std::vector<const uint32_t*> tab(m);
+            for (uint32_t j = 0; j < m; ++j) {
+                tab[j] = d_words.p + (size_t)j * stride;
+                if (nw) HIP_CHECK(hipMemcpy(d_words.p + (size_t)j * stride, words + (size_t)j * nw, nw * 4, hipMemcpyHostToDevice));
+            }
+            HIP_CHECK(hipMemcpy(d_tab.p, tab.data(), (size_t)m * sizeof(tab[0]), hipMemcpyHostToDevice));
+        }
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_CHECK(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw std::runtime_error("hipEventCreate failed"); }
+        try {
+            HIP_CHECK(hipEventRecord(e0, nullptr));
+            facet_counts(d_codes.p, lims ? d_lims.p : nullptr, n, U, words ? d_tab.p : nullptr, m, d_counts.p, path, nullptr);
+            HIP_CHECK(hipEventRecord(e1, nullptr));
+            HIP_CHECK(hipDeviceSynchronize());
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            if (kernel_us) *kernel_us = (double)ms * 1e3;
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            throw;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        HIP_CHECK(hipMemcpy(counts_out, d_counts.p, total * 8, hipMemcpyDeviceToHost));
     });
 }
 
@@ -5662,6 +6017,7 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     h->use_device();
     quiesce(h);                                  // a batch in flight reads the arrays that may move
     h->label_rows.reset();                       // the inverted label column covers `size` ids: the next rescored call rebuilds it
+    h->facets[0].reset();                        // ... and so does the label column's facet dictionary
     HostIndex& hi = h->host;
     const uint64_t D = h->L.D, dim = h->dim, nw = (need + 31) / 32;
     const bool removed = hi.n_removed != 0;

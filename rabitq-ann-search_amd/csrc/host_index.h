@@ -338,6 +338,69 @@ inline void tag_tests_pack_host(const uint32_t* test_lims, const int32_t* test_v
     }
 }
 
+// ---- facet counts (cph_facet_counts, cph_facet_top; device_facets.h) ----
+// The dictionary of a column: `values` = its distinct values ascending (as int32: INT32_MIN and INT32_MAX are ordinary),
+// codes[i] = the position of vals[i] in `values`, so codes ascend with values.  vals: one per row, or one per CSR entry of
+// a tag column.  Fewer than 2^32 entries (a code is 32-bit).
+constexpr uint32_t kFacetTopMaxHost = 1024;   // (= device_facets.h: kFacetTopMax) K of facet_top_host, at most
+inline void facet_dictionary_host(const int32_t* vals, size_t n_entries, std::vector<int32_t>& values, std::vector<uint32_t>& codes) {
+    if (n_entries > 0xFFFFFFFFull) throw std::invalid_argument("a facet column holds fewer than 2^32 entries");
+    if (n_entries != 0 && !vals) throw std::invalid_argument("null facet column");
+    std::vector<int32_t> v(vals, vals + n_entries);
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    std::vector<uint32_t> c(n_entries);
+    for (size_t i = 0; i < n_entries; ++i) c[i] = (uint32_t)(std::lower_bound(v.begin(), v.end(), vals[i]) - v.begin());
+    values.swap(v);
+    codes.swap(c);
+}
+
+// The host statement of the counting pass: counts[j][u] = rows i < n whose bit is set in filters[j] (a null entry, or
+// filters == null: every row), clear in `removed` (null: nothing removed), and whose code is u -- for a tag column (lims
+// != null: [n + 1], codes parallel to the tags) whose entries codes[lims[i] .. lims[i + 1]) hold u.  Bits at ids >= n and
+// words behind (n + 31) / 32 are not read.  counts: [m][U], every one written.  Refuses (std::invalid_argument, before the
+// first write) n >= 2^32 - 1, limits that do not start at 0 or decrease, and a code >= U.
+inline void facet_counts_host(const uint32_t* codes, const uint32_t* lims, size_t n, size_t U, const uint32_t* const* filters,
+                              const uint32_t* removed, size_t m, uint64_t* counts) {
+    if (n >= 0xFFFFFFFFull) throw std::invalid_argument("facet counts cover fewer than 2^32 - 1 rows");
+    const size_t entries = lims ? lims[n] : n;
+    if (lims && lims[0] != 0) throw std::invalid_argument("facet limits must start at 0");
+    for (size_t i = 0; lims && i < n; ++i)
+        if (lims[i + 1] < lims[i]) throw std::invalid_argument("facet limits must not decrease (row " + std::to_string(i) + ")");
+    for (size_t e = 0; e < entries; ++e)
+        if (codes[e] >= U) throw std::invalid_argument("facet code out of range (entry " + std::to_string(e) + ")");
+    for (size_t j = 0; j < m; ++j) {
+        uint64_t* c = counts + j * U;
+        const uint32_t* f = filters ? filters[j] : nullptr;
+        for (size_t u = 0; u < U; ++u) c[u] = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (f && !((f[i >> 5] >> (i & 31)) & 1u)) continue;
+            if (removed && ((removed[i >> 5] >> (i & 31)) & 1u)) continue;
+            if (!lims) ++c[codes[i]];
+            else
+                for (uint32_t e = lims[i]; e < lims[i + 1]; ++e) ++c[codes[e]];
+        }
+    }
+}
+
+// The host statement of the selection: of one filter's counts[U], the K values with the largest non-zero counts, count
+// descending and ties by value ascending (values ascend with codes); *found = min(K, non-zero counts); the slots at and
+// behind *found hold value 0 and count 0.  Refuses K outside [1, kFacetTopMaxHost].
+inline void facet_top_host(const uint64_t* counts, const int32_t* values, size_t U, size_t K, int32_t* values_out, uint64_t* counts_out,
+                           uint32_t* found) {
+    if (K < 1 || K > kFacetTopMaxHost) throw std::invalid_argument("facet top must lie in [1, " + std::to_string(kFacetTopMaxHost) + "]");
+    std::vector<uint32_t> order;
+    for (size_t u = 0; u < U; ++u)
+        if (counts[u]) order.push_back((uint32_t)u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return counts[a] > counts[b]; });
+    const size_t got = std::min(K, order.size());
+    for (size_t i = 0; i < K; ++i) {
+        values_out[i] = i < got ? values[order[i]] : 0;
+        counts_out[i] = i < got ? counts[order[i]] : 0;
+    }
+    *found = (uint32_t)got;
+}
+
 // The host statement of the filter algebra (cph_filters_combine; device_filter_ops.h): out[j] = a[j] OP b[j] word by
 // word for m bitmaps of (n_bits + 31) / 32 words each, one behind the other; b holds m bitmaps, or ONE that every j
 // reads (b_broadcast), and is not read for kFilterNot.  Every word of `out` is written; the bits of the last word at

@@ -693,26 +693,32 @@ class CPIndex:
         result_ids, as for make_filter).  None removes the column.  label_filter / label_filters and the `label=`
         argument of the searches read it.  build(), load() and load_native() drop it (no file carries it: keep the array
         and call set_labels again after loading); remove() and set_row_map() leave it; compact() carries it over."""
-        L = _lib.lib()
         if labels is None:
-            if self._p is not None:
-                _lib.check(L.cph_parts_set_labels(self._p, None, 0))
-            elif self._m is not None:
-                _lib.check(L.cph_multi_set_labels(self._m, None, 0, _lib.IDS_INTERNAL))
-            else:
-                _lib.check(L.cph_set_labels(self._h, None, 0, _lib.IDS_INTERNAL))
+            self._set_attribute("labels", None, 0)
             return
         space = self._id_space(ids)
         a = self._as_labels(labels, "labels")
         if a.ndim != 1 or a.shape[0] != self.size:
             raise ValueError(f"labels must be a 1D integer array of length {self.size} (the index size)")
-        code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
+        self._set_attribute("labels", a.ctypes.data, a.size, space=space)
+
+    def _dispatch(self, single, multi, parts):
+        """What the one handle this index has gives: parts(handle) of a partitioned index, multi(handle) of replicas,
+        else single(handle)."""
         if self._p is not None:
-            _lib.check(L.cph_parts_set_labels(self._p, a.ctypes.data, a.size))
-        elif self._m is not None:
-            _lib.check(L.cph_multi_set_labels(self._m, a.ctypes.data, a.size, code))
-        else:
-            _lib.check(L.cph_set_labels(self._h, a.ctypes.data, a.size, code))
+            return parts(self._p)
+        if self._m is not None:
+            return multi(self._m)
+        return single(self._h)
+
+    def _set_attribute(self, what, *args, space="internal"):
+        """cph_set_<what>(handle, *args, id space), or its cph_multi_ form; cph_parts_set_<what> takes the same without
+        the id space (a partitioned index is always given input rows).  None in place of the values drops the column."""
+        L = _lib.lib()
+        code = _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL
+        _lib.check(self._dispatch(lambda h: getattr(L, f"cph_set_{what}")(h, *args, code),
+                                  lambda m: getattr(L, f"cph_multi_set_{what}")(m, *args, code),
+                                  lambda p: getattr(L, f"cph_parts_set_{what}")(p, *args)))
 
     @property
     def has_labels(self):
@@ -838,18 +844,32 @@ class CPIndex:
     # -- attribute columns and filter algebra (not in the reference) ----------------------------
     MAX_COLUMNS = 8                  # CPH_MAX_COLUMNS
 
-    def _column_slots(self):
-        """name -> slot of the columns the handle still holds: build(), load() and load_native() drop every column with
-        the label column, and their names go with them here."""
+    def _held_slots(self, slots, has_entry):
+        """`slots` (name -> slot) without the names whose column a handle no longer holds (has_entry: cph_has_column or
+        cph_has_tags): build(), load() and load_native() drop every column, and their names go with them here."""
         def has(h, slot):
             f = C.c_int(0)
-            _lib.check(_lib.lib().cph_has_column(h, slot, C.byref(f)))
+            _lib.check(getattr(_lib.lib(), has_entry)(h, slot, C.byref(f)))
             return bool(f.value)
         hs = self._part_handles if self._p is not None else [self._h]
-        for name, slot in list(self._columns.items()):
+        for name, slot in list(slots.items()):
             if not all(has(h, slot) for h in hs):
-                del self._columns[name]
-        return self._columns
+                del slots[name]
+        return slots
+
+    @staticmethod
+    def _slot_for(slots, name, maximum, full):
+        """The slot `name` has in `slots`, or the first of the `maximum` that no name holds; none free: ValueError(full)."""
+        if name in slots:
+            return slots[name]
+        free = [s for s in range(maximum) if s not in slots.values()]
+        if not free:
+            raise ValueError(full)
+        return free[0]
+
+    def _column_slots(self):
+        """name -> slot of the attribute columns the handle still holds."""
+        return self._held_slots(self._columns, "cph_has_column")
 
     def _slot(self, name):
         if name == "label":
@@ -860,16 +880,6 @@ class CPIndex:
         if name not in slots:
             raise ValueError(f"the index has no column {name!r}: call set_column first")
         return slots[name]
-
-    def _set_slot(self, slot, a, code):
-        L, n = _lib.lib(), 0 if a is None else a.size
-        p = None if a is None else a.ctypes.data
-        if self._p is not None:
-            _lib.check(L.cph_parts_set_column(self._p, slot, p, n))
-        elif self._m is not None:
-            _lib.check(L.cph_multi_set_column(self._m, slot, p, n, code))
-        else:
-            _lib.check(L.cph_set_column(self._h, slot, p, n, code))
 
     def set_column(self, name, values, ids=None):
         """A named int32 attribute column next to the label column (a year, a price band, a stock flag): an integer array
@@ -887,20 +897,16 @@ class CPIndex:
         slots = self._column_slots()
         if values is None:
             if name in slots:
-                self._set_slot(slots[name], None, _lib.IDS_INTERNAL)
+                self._set_attribute("column", slots[name], None, 0)
                 del slots[name]
             return
         space = self._id_space(ids)
         a = self._as_labels(values, "column values")
         if a.ndim != 1 or a.shape[0] != self.size:
             raise ValueError(f"column values must be a 1D integer array of length {self.size} (the index size)")
-        slot = slots.get(name)
-        if slot is None:
-            free = [s for s in range(self.MAX_COLUMNS) if s not in slots.values()]
-            if not free:
-                raise ValueError(f"an index holds at most {self.MAX_COLUMNS} columns: drop one first (set_column(name, None))")
-            slot = free[0]
-        self._set_slot(slot, a, _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL)
+        slot = self._slot_for(slots, name, self.MAX_COLUMNS,
+                              f"an index holds at most {self.MAX_COLUMNS} columns: drop one first (set_column(name, None))")
+        self._set_attribute("column", slot, a.ctypes.data, a.size, space=space)
         slots[name] = slot
 
     @property
@@ -928,34 +934,14 @@ class CPIndex:
     _TAG_MODES = {"any": 0, "all": 1, "none": 2}
 
     def _tag_slots(self):
-        """name -> slot of the tag columns the handle still holds (build(), load() and load_native() drop them)."""
-        def has(h, slot):
-            f = C.c_int(0)
-            _lib.check(_lib.lib().cph_has_tags(h, slot, C.byref(f)))
-            return bool(f.value)
-        hs = self._part_handles if self._p is not None else [self._h]
-        for name, slot in list(self._tag_columns.items()):
-            if not all(has(h, slot) for h in hs):
-                del self._tag_columns[name]
-        return self._tag_columns
+        """name -> slot of the tag columns the handle still holds."""
+        return self._held_slots(self._tag_columns, "cph_has_tags")
 
     def _tag_slot(self, name):
         slots = self._tag_slots()
         if name not in slots:
             raise ValueError(f"the index has no tag column {name!r}: call set_tags first")
         return slots[name]
-
-    def _set_tag_slot(self, slot, lims, flat, code):
-        L = _lib.lib()
-        lp = None if lims is None else lims.ctypes.data
-        tp = None if flat is None or flat.size == 0 else flat.ctypes.data
-        n = 0 if lims is None else lims.size - 1
-        if self._p is not None:
-            _lib.check(L.cph_parts_set_tags(self._p, slot, lp, tp, n))
-        elif self._m is not None:
-            _lib.check(L.cph_multi_set_tags(self._m, slot, lp, tp, n, code))
-        else:
-            _lib.check(L.cph_set_tags(self._h, slot, lp, tp, n, code))
 
     def set_tags(self, name, tags, lims=None, ids=None):
         """A named tag column: a SET of integer tags per row (the groups allowed to read a document, the topics of a
@@ -976,7 +962,7 @@ class CPIndex:
         slots = self._tag_slots()
         if tags is None:
             if name in slots:
-                self._set_tag_slot(slots[name], None, None, _lib.IDS_INTERNAL)
+                self._set_attribute("tags", slots[name], None, None, 0)
                 del slots[name]
             return
         space = self._id_space(ids)
@@ -998,13 +984,9 @@ class CPIndex:
         flat = self._as_labels(flat, "tags")
         if lims.size != self.size + 1:
             raise ValueError(f"a tag column has one row per index row: {lims.size - 1} rows given, the index holds {self.size}")
-        slot = slots.get(name)
-        if slot is None:
-            free = [s for s in range(self.MAX_TAG_COLUMNS) if s not in slots.values()]
-            if not free:
-                raise ValueError(f"an index holds at most {self.MAX_TAG_COLUMNS} tag columns: drop one first (set_tags(name, None))")
-            slot = free[0]
-        self._set_tag_slot(slot, lims, flat, _lib.IDS_INPUT if space == "input" else _lib.IDS_INTERNAL)
+        slot = self._slot_for(slots, name, self.MAX_TAG_COLUMNS,
+                              f"an index holds at most {self.MAX_TAG_COLUMNS} tag columns: drop one first (set_tags(name, None))")
+        self._set_attribute("tags", slot, lims.ctypes.data, flat.ctypes.data if flat.size else None, lims.size - 1, space=space)
         slots[name] = slot
 
     @property

@@ -246,7 +246,17 @@ struct FacetDict {
     DevBuf<int32_t> d_values;
     DevBuf<uint32_t> codes;
 };
-constexpr uint32_t kFacetColumns = 1 + kMaxColumns + kMaxTagColumns;      // the label column, the int32 columns, the tag columns
+
+// One row attribute of a handle, resident (host copy: host.cols, under the same id; a replica without host arrays holds
+// the device copy only).  A dense column is vals[size] and no lims; a tag column is the canonical CSR lims[size + 1]
+// (uint32) into vals, and vals stays unallocated while the column holds no tag at all.
+struct RowColumn {
+    DevBuf<int32_t> vals;
+    DevBuf<uint32_t> lims;
+    bool has = false;
+    std::unique_ptr<FacetDict> facet;           // its facet dictionary, once asked for
+};
+constexpr uint32_t kLabelColumn = 0;
 
 // An allowed-id bitmap on one device (cph_filter_create): bit id & 31 of word id >> 5, bits >= n_bits clear.
 struct cph_filter {
@@ -322,37 +332,26 @@ struct cph_index {
     DevBuf<uint32_t> d_rows;
     bool has_rows = false;
     bool ids_input = false;            // cph_set_result_ids: searches return input rows (needs has_rows)
-    // the label column (cph_set_labels): one int32 per internal id, resident next to the row map (host copy:
-    // host.labels; a replica without host arrays holds the device copy only), and the call buffers of
-    // cph_filters_from_labels ([lo | hi] and the counts), which only grow
-    DevBuf<int32_t> d_labels, d_label_bounds;
-    DevBuf<unsigned long long> d_label_counts;
-    bool has_labels = false;
+    // the row attributes, by column id (facet_column): the label column (cph_set_labels; kLabelColumn), the attribute
+    // columns (cph_set_column), the tag columns (cph_set_tags).  One lifecycle for all of them: install_column_locked,
+    // sync_columns, replicate, the compact gather and the parts cut walk this array.  A handle that never saw a column
+    // allocates nothing here.
+    RowColumn cols[kFacetColumns];
     std::unique_ptr<KeyRows> label_rows;      // the label column inverted (rescored maxsim search), or none: made on first use
-    // the attribute columns (cph_set_column): up to kMaxColumns more int32 columns, each held like the label column
-    // (host copies: host.columns); every walk over "the label column" -- sync_labels, replicate, the compact gather,
-    // the parts cut -- walks these slots too (column_of)
-    DevBuf<int32_t> d_columns[kMaxColumns];
-    bool has_column[kMaxColumns] = {};
-    // the tag columns (cph_set_tags): up to kMaxTagColumns set-valued columns, each a canonical CSR in internal-id order
-    // (host copies: host.tag_lims / host.tag_vals; d_tag_vals stays unallocated while a column holds no tag at all), with
-    // the lifecycle of the attribute columns, and the call buffers of cph_filters_from_tags (the tests and the counts),
-    // which only grow.  A handle that never saw cph_set_tags allocates none of this.
-    DevBuf<uint32_t> d_tag_lims[kMaxTagColumns], d_tag_tests;
-    DevBuf<int32_t> d_tag_vals[kMaxTagColumns];
-    DevBuf<unsigned long long> d_tag_counts;
-    bool has_tags[kMaxTagColumns] = {};
-    // facet counts (cph_facet_*): the dictionary of every column that was asked for one (label | columns | tag columns), and
-    // the call buffers -- the counter slab of at most facet_slab counters (cph_debug_facet_slab; a single filter's U may
-    // exceed it), the filter table, the outputs of the top kernel -- which only grow.  A handle that never called
-    // cph_facet_* allocates none of this.
-    std::unique_ptr<FacetDict> facets[kFacetColumns];
+    // the call buffers of cph_filters_from_labels ([lo | hi] and the counts) and of cph_filters_from_tags (the tests and
+    // the counts), which only grow
+    DevBuf<int32_t> d_label_bounds;
+    DevBuf<uint32_t> d_tag_tests;
+    DevBuf<unsigned long long> d_label_counts, d_tag_counts;
+    // facet counts (cph_facet_*): the call buffers -- the counter slab of at most facet_slab counters
+    // (cph_debug_facet_slab; a single filter's U may exceed it), the filter table, the outputs of the top kernel -- which
+    // only grow.  A handle that never called cph_facet_* allocates none of this.
     DevBuf<unsigned long long> d_facet_counts, d_facet_top_counts;
     DevBuf<const uint32_t*> d_facet_tab;
     DevBuf<int32_t> d_facet_top_values;
     DevBuf<uint32_t> d_facet_found;
     uint64_t facet_slab = kFacetSlabCounters;
-    void drop_facets() { for (auto& d : facets) d.reset(); }
+    void drop_facets() { for (auto& c : cols) c.facet.reset(); }
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
@@ -364,8 +363,8 @@ struct cph_index {
     std::shared_ptr<cph_filter> live;
     std::atomic<bool> tombstones{false};
     // the tail (cph_add; device_tail.h): host.n / L stay the rows of the graph, `tail` rows live behind them at index
-    // host.n + j of d_raw, d_norm, d_rows, d_labels and d_removed, which then hold room for more rows than they carry
-    // (tail_capacity).  tail_vecs: their host copy ([tail][dim], what cph_get_vectors and cph_compact read); host.labels
+    // host.n + j of d_raw, d_norm, d_rows, the label column and d_removed, which then hold room for more rows than they carry
+    // (tail_capacity).  tail_vecs: their host copy ([tail][dim], what cph_get_vectors and cph_compact read); the host label column
     // and host.removed cover the tail too, host.rows does not (a tail row is its own input row).  has_tail: tail != 0,
     // readable without the mutex.
     uint64_t tail = 0;
@@ -483,59 +482,95 @@ void sync_row_map(cph_index* h) {
     }
 }
 
-// One int32 column of a handle: the label column (slot kLabelSlot) or attribute column `slot` < kMaxColumns.
-constexpr int kLabelSlot = -1;
-struct ColumnRef {
-    DevBuf<int32_t>& dev;
-    bool& has;
-    std::vector<int32_t>& host;
+// ---- the column store: every row attribute of a handle under one id ----
+void require_slot(uint32_t slot) {
+    if (slot >= kMaxColumns) throw InvalidArg("column slot must be below " + std::to_string(kMaxColumns) + " (CPH_MAX_COLUMNS)");
+}
+void require_tag_slot(uint32_t slot) {
+    if (slot >= kMaxTagColumns) throw InvalidArg("tag column slot must be below " + std::to_string(kMaxTagColumns) + " (CPH_MAX_TAG_COLUMNS)");
+}
+
+// The column id of (kind, slot) -- cph_index::cols, HostIndex::cols; refuses an unknown kind and a slot out of range.
+uint32_t facet_column(int kind, uint32_t slot) {
+    if (kind == CPH_FACET_LABEL) return kLabelColumn;
+    if (kind == CPH_FACET_COLUMN) {
+        require_slot(slot);
+        return 1 + slot;
+    }
+    if (kind == CPH_FACET_TAGS) {
+        require_tag_slot(slot);
+        return 1 + kMaxColumns + slot;
+    }
+    throw InvalidArg("facet column kind must be CPH_FACET_LABEL, CPH_FACET_COLUMN or CPH_FACET_TAGS");
+}
+int column_kind(uint32_t col) { return col == kLabelColumn ? CPH_FACET_LABEL : col <= kMaxColumns ? CPH_FACET_COLUMN : CPH_FACET_TAGS; }
+bool is_tags(uint32_t col) { return col > kMaxColumns; }
+
+// The words of the three kinds in the messages of the calls they share.
+struct ColumnWords {
+    const char* plural;                          // "labels belong to ...", "labels of a partitioned index ..."
+    const char* column;                          // "label column has ..."
+    const char* by_row;                          // "... labels in input rows need cph_set_row_map"
+    const char* setter;
 };
-ColumnRef column_of(cph_index* h, int slot) {
-    if (slot == kLabelSlot) return ColumnRef{h->d_labels, h->has_labels, h->host.labels};
-    return ColumnRef{h->d_columns[slot], h->has_column[slot], h->host.columns[slot]};
+const ColumnWords& words_of(uint32_t col) {
+    static const ColumnWords kWords[3] = {{"labels", "label column", "labels in input rows need", "cph_set_labels"},
+                                          {"columns", "column", "a column in input rows needs", "cph_set_column"},
+                                          {"tags", "tag column", "tags in input rows need", "cph_set_tags"}};
+    static_assert(CPH_FACET_LABEL == 0 && CPH_FACET_COLUMN == 1 && CPH_FACET_TAGS == 2, "kWords is indexed by kind");
+    return kWords[column_kind(col)];
 }
-bool has_extra_columns(const cph_index* h) {
-    return std::any_of(h->has_column, h->has_column + kMaxColumns, [](bool b) { return b; });
+// "the index has no label column" / "... no column in slot 3" / "... no tag column in slot 1"; hint: what to call first.
+std::string no_column(uint32_t col, bool hint) {
+    const ColumnWords& w = words_of(col);
+    std::string s = std::string("the index has no ") + w.column;
+    if (col != kLabelColumn) s += " in slot " + std::to_string(col - (is_tags(col) ? 1 + kMaxColumns : 1));
+    return hint ? s + ": call " + w.setter + " first" : s;
 }
-bool has_tag_columns(const cph_index* h) {
-    return std::any_of(h->has_tags, h->has_tags + kMaxTagColumns, [](bool b) { return b; });
-}
-
-// The device copy of tag column `slot`: lims[n + 1] and tags in internal-id order, or (lims null) none.  The caller has
-// made sure nothing reads the old one.
-void upload_tags(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_t* tags, uint64_t n) {
-    h->has_tags[slot] = lims != nullptr;
-    h->facets[1 + kMaxColumns + slot].reset();
-    h->d_tag_lims[slot].release();
-    h->d_tag_vals[slot].release();
-    if (!lims) return;
-    h->d_tag_lims[slot].alloc(n + 1);
-    HIP_CHECK(hipMemcpy(h->d_tag_lims[slot].p, lims, (n + 1) * 4, hipMemcpyHostToDevice));
-    if (lims[n] == 0) return;                    // (no tag at all: the kernel gets a null base and never reads it)
-    h->d_tag_vals[slot].alloc(lims[n]);
-    HIP_CHECK(hipMemcpy(h->d_tag_vals[slot].p, tags, (size_t)lims[n] * 4, hipMemcpyHostToDevice));
+// The handle holds a column of this kind (CPH_FACET_COLUMN, CPH_FACET_TAGS).
+bool has_columns(const cph_index* h, int kind) {
+    for (uint32_t col = 0; col < kFacetColumns; ++col)
+        if (column_kind(col) == kind && h->cols[col].has) return true;
+    return false;
 }
 
-// After the host index changed: the device copy of its label column, of every attribute column and of every tag column,
-// or none (a load or a build leaves none).
-void sync_labels(cph_index* h) {
-    h->label_rows.reset();
-    h->drop_facets();
-    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {
-        const std::vector<uint32_t>& lims = h->host.tag_lims[slot];
-        if (lims.empty() && !h->has_tags[slot]) continue;        // (an index without tags: nothing to do)
-        upload_tags(h, slot, lims.empty() ? nullptr : lims.data(), h->host.tag_vals[slot].data(), lims.empty() ? 0 : lims.size() - 1);
+// The device copy of column `col`: *src in internal-id order, or (null) none.  The caller has made sure nothing reads the
+// old one.  What was made from the old one goes with it.
+void upload_column(cph_index* h, uint32_t col, const HostColumn* src) {
+    RowColumn& c = h->cols[col];
+    c.has = false;
+    c.facet.reset();
+    if (col == kLabelColumn) h->label_rows.reset();
+    c.vals.release();
+    c.lims.release();
+    if (!src) return;
+    auto up = [](auto& dev, const auto& host) {  // (no tag at all: the kernel gets a null base and never reads it)
+        if (host.empty()) return;
+        dev.alloc(host.size());
+        HIP_CHECK(hipMemcpy(dev.p, host.data(), host.size() * sizeof(*dev.p), hipMemcpyHostToDevice));
+    };
+    up(c.lims, src->lims);
+    up(c.vals, src->vals);
+    c.has = true;
+}
+
+// After the host index changed: the device copy of every column it holds, or none (a load or a build leaves none).
+void sync_columns(cph_index* h) {
+    for (uint32_t col = 0; col < kFacetColumns; ++col) {
+        const HostColumn& hc = h->host.cols[col];
+        upload_column(h, col, hc.empty() ? nullptr : &hc);
     }
-    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
-        const ColumnRef c = column_of(h, slot);
-        c.has = !c.host.empty();
-        if (c.has) {
-            c.dev.alloc(c.host.size());
-            HIP_CHECK(hipMemcpy(c.dev.p, c.host.data(), c.host.size() * 4, hipMemcpyHostToDevice));
-        } else {
-            c.dev.release();
-        }
-    }
+}
+
+void quiesce(cph_index* h);
+
+// The caller holds the handle mutex.  *src: the column over `size` rows in internal-id order, or null: the column goes.
+// keep_host: *src moves into host.cols (what compact gathers from); a replica without host arrays keeps the device copy only.
+void install_column_locked(cph_index* h, uint32_t col, HostColumn* src, bool keep_host) {
+    h->use_device();
+    quiesce(h);                                  // a batch in flight may be reading the old column
+    upload_column(h, col, src);
+    h->host.cols[col] = src && keep_host ? std::move(*src) : HostColumn();
 }
 
 hipStream_t own_stream(cph_index* h);
@@ -2063,7 +2098,7 @@ static void load_v2(cph_index* h, const char* path) {
     drop_host_state(h);
     upload_arrays(h);
     sync_row_map(h);                            // (a v2 file carries no row map)
-    sync_labels(h);                             // (no file carries labels)
+    sync_columns(h);                             // (no file carries labels)
     sync_removed(h);                            // (... and no removed rows)
     upload_feeders(h);
     h->finalized = true;
@@ -2160,7 +2195,7 @@ static void install_native(cph_index* h, NativeLoaded& in) {
     HIP_CHECK(hipMemcpy(h->d_raw.p, h->host.raw_view, n * h->host.D * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(h->d_norm.p, h->host.norm_sq.data(), n * 4, hipMemcpyHostToDevice));
     sync_row_map(h);
-    sync_labels(h);
+    sync_columns(h);
     sync_removed(h);                            // the file's removed rows, or none
     upload_feeders(h);
     h->finalized = true;
@@ -2228,7 +2263,7 @@ static void build_pending(cph_index* h, const float* vectors, uint64_t n, bool a
     ++h->index_epoch;
     h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
     sync_row_map(h);
-    sync_labels(h);
+    sync_columns(h);
     sync_removed(h);
     for (auto& s : h->sets) release_scratch(s);
     if (!unit.empty()) h->pending = std::move(unit);
@@ -3276,103 +3311,171 @@ int cph_host_rows_filter(const uint32_t* words_in, const uint32_t* rows, uint64_
 
 }  // extern "C"
 
-// ---- label column and label filters ----------------------------------------------------------
-// One int32 per row on the handle (internal-id order, resident); cph_filters_from_labels turns it into ordinary
-// cph_filter objects, many per device pass (device_labels.h), so no search path learns anything new.
+// ---- row attributes and the filters made from them -----------------------------------------------------------------
+// The label column and the attribute columns: one int32 per row (device_labels.h).  The tag columns: a set of int32 tags per
+// row, a canonical CSR (device_tags.h).  All in internal-id order, resident; cph_filters_from_labels / _column / _tags turn
+// them into ordinary cph_filter objects, many per device pass, so no search path learns anything new.
 namespace {
 
-// The caller holds the handle mutex.  labels: n == size entries in internal-id order, or null: the column goes.
-// keep_host: also as host.labels (what compact gathers from); a replica without host arrays keeps the device copy only.
-// slot: kLabelSlot, or an attribute column (cph_set_column): the same lifecycle, one code path.
-void install_labels_locked(cph_index* h, const int32_t* labels, uint64_t n, bool keep_host, int slot = kLabelSlot) {
-    h->use_device();
-    quiesce(h);                                  // a grouped batch in flight may be reading the old column
-    const ColumnRef c = column_of(h, slot);
-    if (slot == kLabelSlot) h->label_rows.reset();      // (idle: quiesce above)
-    h->facets[1 + slot].reset();                         // (kLabelSlot is -1: the label column's dictionary is entry 0)
-    if (!labels) {
-        std::vector<int32_t>().swap(c.host);
-        c.has = false;
-        c.dev.release();
-        return;
-    }
-    c.dev.alloc(n);
-    HIP_CHECK(hipMemcpy(c.dev.p, labels, n * 4, hipMemcpyHostToDevice));
-    if (keep_host) c.host.assign(labels, labels + n);
-    c.has = true;
+// A column is given by its values (dense) or by its limits (tags: a column without a tag has no values); else it goes.
+bool column_given(uint32_t col, const int32_t* vals, const uint64_t* lims) { return is_tags(col) ? lims != nullptr : vals != nullptr; }
+
+std::string wrong_column_size(uint32_t col, uint64_t n, uint64_t size) {
+    return std::string(words_of(col).column) + " has " + std::to_string(n) + (is_tags(col) ? " rows" : " entries") + ", the index holds " +
+           std::to_string(size);
 }
 
-void require_slot(uint32_t slot) {
-    if (slot >= kMaxColumns) throw InvalidArg("column slot must be below " + std::to_string(kMaxColumns) + " (CPH_MAX_COLUMNS)");
+void require_column_target(const cph_index* h, uint32_t col, bool set, uint64_t n) {
+    if (!h->finalized) throw InvalidArg(std::string(words_of(col).plural) + " belong to a finalized index: finalize or load it first");
+    if (set && n != h->size()) throw InvalidArg(wrong_column_size(col, n, h->size()));
 }
 
-void require_labels_target(const cph_index* h, const int32_t* labels, uint64_t n, int slot = kLabelSlot) {
-    const bool lab = slot == kLabelSlot;
-    if (!h->finalized)
-        throw InvalidArg(lab ? "labels belong to a finalized index: finalize or load it first"
-                             : "columns belong to a finalized index: finalize or load it first");
-    if (labels && n != h->size())
-        throw InvalidArg(std::string(lab ? "label column has " : "column has ") + std::to_string(n) + " entries, the index holds " +
-                         std::to_string(h->size()));
-}
-
-// cph_set_labels / cph_set_column on a handle that keeps its host arrays: values in internal ids, or in input rows
-// (moved to internal order on the host, through host.rows: labels_to_internal_host).
-void set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space, int slot = kLabelSlot) {
-    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
-    std::lock_guard<std::mutex> lk(h->mu);
-    require_labels_target(h, labels, n, slot);
-    if (!labels || space == CPH_IDS_INTERNAL) {
-        install_labels_locked(h, labels, n, true, slot);
-        return;
-    }
+// The caller holds the handle mutex; the handle does not change.  A caller's column of n rows -- dense: vals[n]; tags:
+// lims[n + 1] into vals, tags in any order -- as the handle stores it: in internal-id order (input rows go through
+// host.rows; a tail row is its own input row), the tags of a row sorted and distinct (tags_canonical_host).
+HostColumn column_to_store_locked(const cph_index* h, uint32_t col, const int32_t* vals, const uint64_t* lims, uint64_t n, int space) {
+    require_column_target(h, col, true, n);
     const uint64_t nb = h->host.n;
-    if (!h->has_rows || h->host.rows.size() != nb)
-        throw InvalidArg(slot == kLabelSlot
-                             ? "the index has no row map (it was loaded from a v2 file): labels in input rows need cph_set_row_map"
-                             : "the index has no row map (it was loaded from a v2 file): a column in input rows needs cph_set_row_map");
-    std::vector<int32_t> internal(n);
-    labels_to_internal_host(labels, h->host.rows.data(), nb, internal.data());
-    std::copy(labels + nb, labels + n, internal.begin() + nb);      // (a tail row is its own input row)
-    install_labels_locked(h, internal.data(), n, true, slot);
+    const bool by_row = space == CPH_IDS_INPUT;
+    if (by_row && (!h->has_rows || h->host.rows.size() != nb))
+        throw InvalidArg(std::string("the index has no row map (it was loaded from a v2 file): ") + words_of(col).by_row + " cph_set_row_map");
+    HostColumn c;
+    if (is_tags(col)) {
+        tags_canonical_host(lims, vals, n, by_row ? h->host.rows.data() : nullptr, nb, c.lims, c.vals);
+    } else if (by_row) {
+        c.vals.resize(n);
+        labels_to_internal_host(vals, h->host.rows.data(), nb, c.vals.data());
+        std::copy(vals + nb, vals + n, c.vals.begin() + nb);
+    } else {
+        c.vals.assign(vals, vals + n);
+    }
+    return c;
 }
+
+void require_id_space(int space) {
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+}
+
+// cph_set_labels / cph_set_column / cph_set_tags on a handle that keeps its host arrays: rows in internal ids or in input rows.
+void set_column(cph_index* h, uint32_t col, const int32_t* vals, const uint64_t* lims, uint64_t n, int space) {
+    require_id_space(space);
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!column_given(col, vals, lims)) {
+        require_column_target(h, col, false, 0);
+        install_column_locked(h, col, nullptr, true);
+        return;
+    }
+    HostColumn c = column_to_store_locked(h, col, vals, lims, n, space);
+    install_column_locked(h, col, &c, true);
+}
+
+// The m filters of one device pass over n ids, all made or none: their bitmaps one behind the other in one allocation
+// (`slab`, bitmap j at j * stride words), their counts as the pass left them (`counts`, copied back by the caller, who
+// also makes the call's one wait).  The device is current.
+struct FilterSlab {
+    const uint64_t n, nw, stride;
+    std::vector<std::unique_ptr<cph_filter>> made;
+    std::shared_ptr<DevBuf<uint32_t>> slab;
+    std::vector<unsigned long long> counts;
+    FilterSlab(uint64_t n_bits, uint32_t m)
+        : n(n_bits), nw((n_bits + 31) / 32), stride((std::max<uint64_t>(nw, 1) + 63) / 64 * 64),      // every bitmap starts on a 256 B line
+          made(m), counts(m, 0) {
+        for (auto& f : made) f.reset(new cph_filter());
+        slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
+    }
+    void finish(int device, cph_filter** out) {
+        for (size_t j = 0; j < made.size(); ++j) {
+            cph_filter* f = made[j].get();
+            f->device = device;
+            f->n_bits = n;
+            f->popcount = counts[j];
+            f->slab = slab;
+            f->words.p = slab->p + j * stride;
+            f->words.n = std::max<uint64_t>(nw, 1);
+        }
+        for (size_t j = 0; j < made.size(); ++j) out[j] = made[j].release();
+    }
+};
 
 // cph_filters_from_labels / cph_filters_from_column: out[m] all made, or none.
-void filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out, int slot = kLabelSlot) {
+void filters_from_labels(cph_index* h, uint32_t col, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
     std::lock_guard<std::mutex> lk(h->mu);
     require_finalized(h);
-    const ColumnRef col = column_of(h, slot);
-    if (!col.has)
-        throw InvalidArg(slot == kLabelSlot ? "the index has no label column: call cph_set_labels first"
-                                            : "the index has no column in slot " + std::to_string(slot) + ": call cph_set_column first");
+    const RowColumn& c = h->cols[col];
+    if (!c.has) throw InvalidArg(no_column(col, true));
     if (m > kLabelMaxFilters) throw InvalidArg("at most " + std::to_string(kLabelMaxFilters) + " label filters per call");
-    const uint64_t n = h->size(), nw = (n + 31) / 32;
-    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
     h->use_device();
-    std::vector<std::unique_ptr<cph_filter>> made(m);
-    for (auto& f : made) f.reset(new cph_filter());
-    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
+    FilterSlab fs(h->size(), m);
     h->d_label_bounds.alloc((size_t)2 * m);
     h->d_label_counts.alloc(m);
     hipStream_t st = own_stream(h);
     HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p, lo, (size_t)m * 4, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(h->d_label_bounds.p + m, hi, (size_t)m * 4, hipMemcpyHostToDevice, st));
     timed_pass(h->pass_timer[kPassLabels], st, [&] {
-        label_filters(col.dev.p, n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, slab->p, stride, h->d_label_counts.p, st);
+        label_filters(c.vals.p, fs.n, h->d_label_bounds.p, h->d_label_bounds.p + m, m, fs.slab->p, fs.stride, h->d_label_counts.p, st);
     });
-    std::vector<unsigned long long> counts(m);
-    HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_label_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(fs.counts.data(), h->d_label_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
-    for (uint32_t j = 0; j < m; ++j) {
-        cph_filter* f = made[j].get();
-        f->device = h->device;
-        f->n_bits = n;
-        f->popcount = counts[j];
-        f->slab = slab;
-        f->words.p = slab->p + (size_t)j * stride;
-        f->words.n = std::max<uint64_t>(nw, 1);
-    }
-    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
+    fs.finish(h->device, out);
+}
+
+// cph_filters_from_tags: out[m] all made, or none.  The tests are canonical already.
+void filters_from_tags(cph_index* h, uint32_t col, const std::vector<uint32_t>& table, size_t vals_at, uint32_t m, cph_filter** out) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    const RowColumn& c = h->cols[col];
+    if (!c.has) throw InvalidArg(no_column(col, true));
+    h->use_device();
+    FilterSlab fs(h->size(), m);
+    h->d_tag_tests.alloc(table.size());
+    h->d_tag_counts.alloc(m);
+    hipStream_t st = own_stream(h);
+    HIP_CHECK(hipMemcpyAsync(h->d_tag_tests.p, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+    timed_pass(h->pass_timer[kPassTags], st, [&] {
+        tag_filters(c.lims.p, c.vals.p, fs.n, h->d_tag_tests.p, (uint32_t)vals_at, m, fs.slab->p, fs.stride, h->d_tag_counts.p, st);
+    });
+    HIP_CHECK(hipMemcpyAsync(fs.counts.data(), h->d_tag_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
+    fs.finish(h->device, out);
+}
+
+// The caller's tests, canonical and packed for the kernel (before any handle is locked).
+void pack_tag_tests(const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, uint32_t m, std::vector<uint32_t>& table,
+                    size_t& vals_at) {
+    if (m > kTagMaxFilters) throw InvalidArg("at most " + std::to_string(kTagMaxFilters) + " tag filters per call");
+    std::vector<uint32_t> tl;
+    std::vector<int32_t> tv;
+    tag_tests_canonical_host(test_lims, test_vals, modes, m, tl, tv);
+    tag_tests_pack_host(tl.data(), tv.data(), modes, m, table, vals_at);
+}
+
+// cph_has_labels / cph_has_column / cph_has_tags.
+void column_flag(cph_index* h, int kind, uint32_t slot, int* flag) {
+    if (!h || !flag) throw InvalidArg("null argument");
+    const uint32_t col = facet_column(kind, slot);
+    std::lock_guard<std::mutex> lk(h->mu);
+    *flag = h->finalized && h->cols[col].has ? 1 : 0;
+}
+
+// cph_get_labels / cph_get_column.
+void get_column(cph_index* h, uint32_t col, uint64_t first, uint64_t count, int32_t* out) {
+    if (!h || (!out && count != 0)) throw InvalidArg("null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    require_finalized(h);
+    if (!h->cols[col].has) throw InvalidArg(no_column(col, false));
+    if (first > h->size() || count > h->size() - first) throw InvalidArg(col == kLabelColumn ? "label range out of bounds" : "column range out of bounds");
+    if (count == 0) return;
+    h->use_device();
+    HIP_CHECK(hipMemcpy(out, h->cols[col].vals.p + first, count * 4, hipMemcpyDeviceToHost));
+}
+
+// cph_filters_from_labels / cph_filters_from_column: the checks of the entry.
+void filters_from_labels_entry(cph_index* h, int kind, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
+    if (m == 0) return;
+    if (!out) throw InvalidArg("null argument");
+    std::fill(out, out + m, nullptr);
+    if (!h || !lo || !hi) throw InvalidArg("null argument");
+    filters_from_labels(h, facet_column(kind, slot), lo, hi, m, out);
 }
 
 }  // namespace
@@ -3383,79 +3486,40 @@ int cph_set_labels(cph_index* h, const int32_t* labels, uint64_t n, int space) {
     return guarded([&] {
         if (!h) throw InvalidArg("null handle");
         refuse_borrowed(h, "cph_set_labels");
-        set_labels(h, labels, n, space);
+        set_column(h, kLabelColumn, labels, nullptr, n, space);
     });
 }
 
 int cph_has_labels(cph_index* h, int* flag) {
-    return guarded([&] {
-        if (!h || !flag) throw InvalidArg("null argument");
-        std::lock_guard<std::mutex> lk(h->mu);
-        *flag = h->finalized && h->has_labels ? 1 : 0;
-    });
-}
-
-// cph_get_labels / cph_get_column.
-static void get_column(cph_index* h, int slot, uint64_t first, uint64_t count, int32_t* out) {
-    if (!h || (!out && count != 0)) throw InvalidArg("null argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    require_finalized(h);
-    const ColumnRef c = column_of(h, slot);
-    if (!c.has) throw InvalidArg(slot == kLabelSlot ? "the index has no label column" : "the index has no column in slot " + std::to_string(slot));
-    if (first > h->size() || count > h->size() - first) throw InvalidArg(slot == kLabelSlot ? "label range out of bounds" : "column range out of bounds");
-    if (count == 0) return;
-    h->use_device();
-    HIP_CHECK(hipMemcpy(out, c.dev.p + first, count * 4, hipMemcpyDeviceToHost));
+    return guarded([&] { column_flag(h, CPH_FACET_LABEL, 0, flag); });
 }
 
 int cph_get_labels(cph_index* h, uint64_t first, uint64_t count, int32_t* out) {
-    return guarded([&] { get_column(h, kLabelSlot, first, count, out); });
+    return guarded([&] { get_column(h, kLabelColumn, first, count, out); });
 }
 
 int cph_set_column(cph_index* h, uint32_t slot, const int32_t* values, uint64_t n, int space) {
     return guarded([&] {
         if (!h) throw InvalidArg("null handle");
         refuse_borrowed(h, "cph_set_column");
-        require_slot(slot);
-        set_labels(h, values, n, space, (int)slot);
+        set_column(h, facet_column(CPH_FACET_COLUMN, slot), values, nullptr, n, space);
     });
 }
 
 int cph_has_column(cph_index* h, uint32_t slot, int* flag) {
-    return guarded([&] {
-        if (!h || !flag) throw InvalidArg("null argument");
-        require_slot(slot);
-        std::lock_guard<std::mutex> lk(h->mu);
-        *flag = h->finalized && h->has_column[slot] ? 1 : 0;
-    });
+    return guarded([&] { column_flag(h, CPH_FACET_COLUMN, slot, flag); });
 }
 
 int cph_get_column(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, int32_t* out) {
-    return guarded([&] {
-        require_slot(slot);
-        get_column(h, (int)slot, first, count, out);
-    });
+    return guarded([&] { get_column(h, facet_column(CPH_FACET_COLUMN, slot), first, count, out); });
 }
 
 int cph_filters_from_column(cph_index* h, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
-    return guarded([&] {
-        if (m == 0) return;
-        if (!out) throw InvalidArg("null argument");
-        std::fill(out, out + m, nullptr);
-        if (!h || !lo || !hi) throw InvalidArg("null argument");
-        require_slot(slot);
-        filters_from_labels(h, lo, hi, m, out, (int)slot);
-    });
+    return guarded([&] { filters_from_labels_entry(h, CPH_FACET_COLUMN, slot, lo, hi, m, out); });
 }
 
 int cph_filters_from_labels(cph_index* h, const int32_t* lo, const int32_t* hi, uint32_t m, cph_filter** out) {
-    return guarded([&] {
-        if (m == 0) return;
-        if (!out) throw InvalidArg("null argument");
-        std::fill(out, out + m, nullptr);
-        if (!h || !lo || !hi) throw InvalidArg("null argument");
-        filters_from_labels(h, lo, hi, m, out);
-    });
+    return guarded([&] { filters_from_labels_entry(h, CPH_FACET_LABEL, 0, lo, hi, m, out); });
 }
 
 int cph_debug_time_label_filters(cph_index* h, int on) {
@@ -3487,138 +3551,33 @@ int cph_host_label_filters(const int32_t* labels, uint64_t n, const int32_t* lo,
     });
 }
 
-}  // extern "C"
-
-// ---- tag columns and tag filters (device_tags.h) -----------------------------------------------
-// A set of int32 tags per row on the handle (a canonical CSR in internal-id order, resident); cph_filters_from_tags turns
-// any / all / none tests into ordinary cph_filter objects, many per device pass, so no search path learns anything new.
-namespace {
-
-void require_tag_slot(uint32_t slot) {
-    if (slot >= kMaxTagColumns) throw InvalidArg("tag column slot must be below " + std::to_string(kMaxTagColumns) + " (CPH_MAX_TAG_COLUMNS)");
-}
-
-void require_tags_target(const cph_index* h, bool set, uint64_t n) {
-    if (!h->finalized) throw InvalidArg("tags belong to a finalized index: finalize or load it first");
-    if (set && n != h->size())
-        throw InvalidArg("tag column has " + std::to_string(n) + " rows, the index holds " + std::to_string(h->size()));
-}
-
-// The caller holds the handle mutex.  lims / tags: the canonical column of n == size rows in internal-id order, or
-// (lims null) the column goes.  keep_host: also as host.tag_lims / tag_vals (what compact gathers from); a replica
-// without host arrays keeps the device copy only.
-void install_tags_locked(cph_index* h, uint32_t slot, const uint32_t* lims, const int32_t* tags, uint64_t n, bool keep_host) {
-    h->use_device();
-    quiesce(h);
-    upload_tags(h, slot, lims, tags, n);
-    std::vector<uint32_t>().swap(h->host.tag_lims[slot]);
-    std::vector<int32_t>().swap(h->host.tag_vals[slot]);
-    if (lims && keep_host) {
-        h->host.tag_lims[slot].assign(lims, lims + n + 1);
-        h->host.tag_vals[slot].assign(tags, tags + lims[n]);
-    }
-}
-
-// cph_set_tags on a handle that keeps its host arrays: rows in internal ids, or in input rows (gathered to internal
-// order on the host, through host.rows); the rows are sorted and deduplicated on the way (tags_canonical_host).
-void set_tags(cph_index* h, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
-    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
-    std::lock_guard<std::mutex> lk(h->mu);
-    require_tags_target(h, lims != nullptr, n);
-    if (!lims) {
-        if (h->has_tags[slot]) install_tags_locked(h, slot, nullptr, nullptr, 0, true);
-        return;
-    }
-    const uint64_t nb = h->host.n;
-    const bool by_row = space == CPH_IDS_INPUT;
-    if (by_row && (!h->has_rows || h->host.rows.size() != nb))
-        throw InvalidArg("the index has no row map (it was loaded from a v2 file): tags in input rows need cph_set_row_map");
-    std::vector<uint32_t> cl;
-    std::vector<int32_t> cv;
-    tags_canonical_host(lims, tags, n, by_row ? h->host.rows.data() : nullptr, nb, cl, cv);      // (a tail row is its own input row)
-    install_tags_locked(h, slot, cl.data(), cv.data(), n, true);
-}
-
-// cph_filters_from_tags: out[m] all made, or none.  The tests are canonical already.
-void filters_from_tags(cph_index* h, uint32_t slot, const std::vector<uint32_t>& table, size_t vals_at, uint32_t m, cph_filter** out) {
-    std::lock_guard<std::mutex> lk(h->mu);
-    require_finalized(h);
-    if (!h->has_tags[slot]) throw InvalidArg("the index has no tag column in slot " + std::to_string(slot) + ": call cph_set_tags first");
-    const uint64_t n = h->size(), nw = (n + 31) / 32;
-    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
-    h->use_device();
-    std::vector<std::unique_ptr<cph_filter>> made(m);
-    for (auto& f : made) f.reset(new cph_filter());
-    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
-    h->d_tag_tests.alloc(table.size());
-    h->d_tag_counts.alloc(m);
-    hipStream_t st = own_stream(h);
-    HIP_CHECK(hipMemcpyAsync(h->d_tag_tests.p, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-    timed_pass(h->pass_timer[kPassTags], st, [&] {
-        tag_filters(h->d_tag_lims[slot].p, h->d_tag_vals[slot].p, n, h->d_tag_tests.p, (uint32_t)vals_at, m, slab->p, stride,
-                    h->d_tag_counts.p, st);
-    });
-    std::vector<unsigned long long> counts(m);
-    HIP_CHECK(hipMemcpyAsync(counts.data(), h->d_tag_counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));         // the one wait of the call: the routing needs every count on the host
-    for (uint32_t j = 0; j < m; ++j) {
-        cph_filter* f = made[j].get();
-        f->device = h->device;
-        f->n_bits = n;
-        f->popcount = counts[j];
-        f->slab = slab;
-        f->words.p = slab->p + (size_t)j * stride;
-        f->words.n = std::max<uint64_t>(nw, 1);
-    }
-    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
-}
-
-// The caller's tests, canonical and packed for the kernel (before any handle is locked).
-void pack_tag_tests(const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes, uint32_t m, std::vector<uint32_t>& table,
-                    size_t& vals_at) {
-    if (m > kTagMaxFilters) throw InvalidArg("at most " + std::to_string(kTagMaxFilters) + " tag filters per call");
-    std::vector<uint32_t> tl;
-    std::vector<int32_t> tv;
-    tag_tests_canonical_host(test_lims, test_vals, modes, m, tl, tv);
-    tag_tests_pack_host(tl.data(), tv.data(), modes, m, table, vals_at);
-}
-
-}  // namespace
-
-extern "C" {
-
 int cph_set_tags(cph_index* h, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
     return guarded([&] {
         if (!h) throw InvalidArg("null handle");
         refuse_borrowed(h, "cph_set_tags");
-        require_tag_slot(slot);
-        set_tags(h, slot, lims, tags, n, space);
+        set_column(h, facet_column(CPH_FACET_TAGS, slot), tags, lims, n, space);
     });
 }
 
 int cph_has_tags(cph_index* h, uint32_t slot, int* flag) {
-    return guarded([&] {
-        if (!h || !flag) throw InvalidArg("null argument");
-        require_tag_slot(slot);
-        std::lock_guard<std::mutex> lk(h->mu);
-        *flag = h->finalized && h->has_tags[slot] ? 1 : 0;
-    });
+    return guarded([&] { column_flag(h, CPH_FACET_TAGS, slot, flag); });
 }
 
 int cph_get_tags(cph_index* h, uint32_t slot, uint64_t first, uint64_t count, uint64_t* lims_out, int32_t* tags_out) {
     return guarded([&] {
         if (!h || !lims_out) throw InvalidArg("null argument");
-        require_tag_slot(slot);
+        const uint32_t col = facet_column(CPH_FACET_TAGS, slot);
         std::lock_guard<std::mutex> lk(h->mu);
         require_finalized(h);
-        if (!h->has_tags[slot]) throw InvalidArg("the index has no tag column in slot " + std::to_string(slot));
+        const RowColumn& c = h->cols[col];
+        if (!c.has) throw InvalidArg(no_column(col, false));
         if (first > h->size() || count > h->size() - first) throw InvalidArg("tag row range out of bounds");
         h->use_device();
         std::vector<uint32_t> lims(count + 1);
-        HIP_CHECK(hipMemcpy(lims.data(), h->d_tag_lims[slot].p + first, (count + 1) * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(lims.data(), c.lims.p + first, (count + 1) * 4, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i <= count; ++i) lims_out[i] = (uint64_t)(lims[i] - lims[0]);
         if (tags_out && lims[count] != lims[0])
-            HIP_CHECK(hipMemcpy(tags_out, h->d_tag_vals[slot].p + lims[0], (size_t)(lims[count] - lims[0]) * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(tags_out, c.vals.p + lims[0], (size_t)(lims[count] - lims[0]) * 4, hipMemcpyDeviceToHost));
     });
 }
 
@@ -3629,11 +3588,11 @@ int cph_filters_from_tags(cph_index* h, uint32_t slot, const uint32_t* test_lims
         if (!out) throw InvalidArg("null argument");
         std::fill(out, out + m, nullptr);
         if (!h || !test_lims || !modes) throw InvalidArg("null argument");
-        require_tag_slot(slot);
+        const uint32_t col = facet_column(CPH_FACET_TAGS, slot);
         std::vector<uint32_t> table;
         size_t vals_at = 0;
         pack_tag_tests(test_lims, test_vals, modes, m, table, vals_at);
-        filters_from_tags(h, slot, table, vals_at, m, out);
+        filters_from_tags(h, col, table, vals_at, m, out);
     });
 }
 
@@ -3667,69 +3626,34 @@ int cph_host_tag_filters(const uint32_t* lims, const int32_t* tags, uint64_t n, 
 // with the column), one counting launch per group of filters, and for `top` one selection launch behind it.
 namespace {
 
-// The dictionary slot of (kind, slot) in cph_index::facets; refuses an unknown kind and a slot out of range.
-uint32_t facet_column(int kind, uint32_t slot) {
-    if (kind == CPH_FACET_LABEL) return 0;
-    if (kind == CPH_FACET_COLUMN) {
-        require_slot(slot);
-        return 1 + slot;
-    }
-    if (kind == CPH_FACET_TAGS) {
-        require_tag_slot(slot);
-        return 1 + kMaxColumns + slot;
-    }
-    throw InvalidArg("facet column kind must be CPH_FACET_LABEL, CPH_FACET_COLUMN or CPH_FACET_TAGS");
-}
-
 // The caller holds the handle mutex.  The dictionary of the column, made now if it is not there: from the host copy of
-// the column, or (a replica without host arrays) from a copy of the resident one.
+// the column if that is complete, or (a replica without host arrays) from a copy of the resident one.
 FacetDict& facet_dict_locked(cph_index* h, int kind, uint32_t slot) {
-    const uint32_t at = facet_column(kind, slot);
+    const uint32_t col = facet_column(kind, slot);
     if (!h->finalized) throw InvalidArg("facets belong to a finalized index: finalize or load it first");
-    const bool tags = kind == CPH_FACET_TAGS;
-    if (tags ? !h->has_tags[slot] : !column_of(h, kind == CPH_FACET_LABEL ? kLabelSlot : (int)slot).has)
-        throw InvalidArg(kind == CPH_FACET_LABEL ? "the index has no label column: call cph_set_labels first"
-                         : tags ? "the index has no tag column in slot " + std::to_string(slot) + ": call cph_set_tags first"
-                                : "the index has no column in slot " + std::to_string(slot) + ": call cph_set_column first");
-    if (h->facets[at]) return *h->facets[at];
+    RowColumn& c = h->cols[col];
+    if (!c.has) throw InvalidArg(no_column(col, true));
+    if (c.facet) return *c.facet;
     h->use_device();
     const uint64_t n = h->size();
+    const HostColumn& hc = h->host.cols[col];
     std::vector<int32_t> fetched;
-    const int32_t* src = nullptr;
-    uint64_t entries = 0;
-    if (tags) {
-        const std::vector<uint32_t>& hl = h->host.tag_lims[slot];
-        if (hl.size() == n + 1) {
-            entries = hl[n];
-            src = h->host.tag_vals[slot].data();
-        } else {
-            uint32_t last = 0;
-            HIP_CHECK(hipMemcpy(&last, h->d_tag_lims[slot].p + n, 4, hipMemcpyDeviceToHost));
-            entries = last;
-            fetched.resize(entries);
-            if (entries) HIP_CHECK(hipMemcpy(fetched.data(), h->d_tag_vals[slot].p, entries * 4, hipMemcpyDeviceToHost));
-            src = fetched.data();
-        }
-    } else {
-        const ColumnRef c = column_of(h, kind == CPH_FACET_LABEL ? kLabelSlot : (int)slot);
-        entries = n;
-        if (c.host.size() == n) {
-            src = c.host.data();
-        } else {
-            fetched.resize(n);
-            if (n) HIP_CHECK(hipMemcpy(fetched.data(), c.dev.p, n * 4, hipMemcpyDeviceToHost));
-            src = fetched.data();
-        }
+    if (!hc.covers(n)) {
+        uint32_t entries = (uint32_t)n;          // dense: one per row; tags: where the last row ends
+        if (c.lims.p) HIP_CHECK(hipMemcpy(&entries, c.lims.p + n, 4, hipMemcpyDeviceToHost));
+        fetched.resize(entries);
+        if (entries) HIP_CHECK(hipMemcpy(fetched.data(), c.vals.p, (size_t)entries * 4, hipMemcpyDeviceToHost));
     }
+    const std::vector<int32_t>& src = hc.covers(n) ? hc.vals : fetched;
     std::unique_ptr<FacetDict> d(new FacetDict());
     std::vector<uint32_t> codes;
-    facet_dictionary_host(src, entries, d->values, codes);
+    facet_dictionary_host(src.data(), src.size(), d->values, codes);
     d->codes.alloc(codes.size());
     d->d_values.alloc(d->values.size());
     if (!codes.empty()) HIP_CHECK(hipMemcpy(d->codes.p, codes.data(), codes.size() * 4, hipMemcpyHostToDevice));
     if (!d->values.empty()) HIP_CHECK(hipMemcpy(d->d_values.p, d->values.data(), d->values.size() * 4, hipMemcpyHostToDevice));
-    h->facets[at] = std::move(d);
-    return *h->facets[at];
+    c.facet = std::move(d);
+    return *c.facet;
 }
 
 // cph_facet_counts (K == 0: counts_out [m][U]) and cph_facet_top (K >= 1: values_out / counts_out [m][K], found_out [m]).
@@ -3767,7 +3691,7 @@ void facet_query(cph_index* h, int kind, uint32_t slot, const cph_filter* const*
         any = any || tab[j];
     }
     const uint32_t group = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(h->facet_slab / U, 1), (uint64_t)kFacetMaxFilters, (uint64_t)m});
-    const uint32_t* d_lims = kind == CPH_FACET_TAGS ? h->d_tag_lims[slot].p : nullptr;
+    const uint32_t* d_lims = h->cols[facet_column(kind, slot)].lims.p;      // (a dense column has none)
     h->d_facet_counts.alloc((size_t)group * U);
     hipStream_t st = own_stream(h);
     if (any) {
@@ -4033,7 +3957,7 @@ static void filters_combine(int op, const cph_filter* const* a, uint32_t m, cons
     for (uint32_t j = 0; j < n_b; ++j)
         if (!b[j]) throw InvalidArg("null filter");
     const int device = a[0]->device;
-    const uint64_t n = a[0]->n_bits, nw = (n + 31) / 32;
+    const uint64_t n = a[0]->n_bits;
     auto same = [&](const cph_filter* f) {
         if (f->n_bits != n)
             throw InvalidArg("filters of different sizes cannot be combined (" + std::to_string(f->n_bits) + " and " + std::to_string(n) + " ids)");
@@ -4041,12 +3965,8 @@ static void filters_combine(int op, const cph_filter* const* a, uint32_t m, cons
     };
     for (uint32_t j = 0; j < m; ++j) same(a[j]);
     for (uint32_t j = 0; j < n_b; ++j) same(b[j]);
-    const uint64_t stride = (std::max<uint64_t>(nw, 1) + 63) / 64 * 64;      // every bitmap starts on a 256 B line
     HIP_CHECK(hipSetDevice(device));
-    std::vector<std::unique_ptr<cph_filter>> made(m);
-    for (auto& f : made) f.reset(new cph_filter());
-    auto slab = std::make_shared<DevBuf<uint32_t>>((size_t)m * stride);
-    std::vector<unsigned long long> counts(m, 0);
+    FilterSlab fs(n, m);
     if (n != 0) {
         CombineCtx* cx = combine_ctx(device);
         std::lock_guard<std::mutex> lk(cx->mu);
@@ -4056,20 +3976,11 @@ static void filters_combine(int op, const cph_filter* const* a, uint32_t m, cons
         for (uint32_t j = 0; j < n_b; ++j) pb[j] = b[j]->words.p;
         combine_tables(pa.data(), m, pb.data(), n_b, cx->tab, cx->stream);
         cx->counts.alloc(m);
-        filter_combine(op, cx->tab.p, n_b ? cx->tab.p + m : nullptr, n_b == 1, n, m, slab->p, stride, cx->counts.p, cx->stream);
-        HIP_CHECK(hipMemcpyAsync(counts.data(), cx->counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, cx->stream));
+        filter_combine(op, cx->tab.p, n_b ? cx->tab.p + m : nullptr, n_b == 1, n, m, fs.slab->p, fs.stride, cx->counts.p, cx->stream);
+        HIP_CHECK(hipMemcpyAsync(fs.counts.data(), cx->counts.p, (size_t)m * 8, hipMemcpyDeviceToHost, cx->stream));
         HIP_CHECK(hipStreamSynchronize(cx->stream));     // the one wait of the call: the routing needs every count on the host
     }
-    for (uint32_t j = 0; j < m; ++j) {
-        cph_filter* f = made[j].get();
-        f->device = device;
-        f->n_bits = n;
-        f->popcount = counts[j];
-        f->slab = slab;
-        f->words.p = slab->p + (size_t)j * stride;
-        f->words.n = std::max<uint64_t>(nw, 1);
-    }
-    for (uint32_t j = 0; j < m; ++j) out[j] = made[j].release();
+    fs.finish(device, out);
 }
 
 int cph_filters_combine(int op, const cph_filter* const* a, uint32_t m, const cph_filter* const* b, uint32_t n_b, cph_filter** out) {
@@ -4784,19 +4695,14 @@ void replicate(cph_index* src, cph_index* dst) {
     else dst->d_rows.release();
     dst->has_rows = src->has_rows;
     dst->ids_input = dst->ids_input && dst->has_rows;
-    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {      // (compact carries the columns; a load or finalize has none)
-        const ColumnRef from = column_of(src, slot), to = column_of(dst, slot);
-        if (from.has) copy(to.dev, from.dev);
-        else to.dev.release();
+    for (uint32_t col = 0; col < kFacetColumns; ++col) {                // (compact carries the columns; a load or finalize has none)
+        const RowColumn& from = src->cols[col];
+        RowColumn& to = dst->cols[col];                                 // (its dictionary went in begin_device_swap)
+        to.vals.release();
+        to.lims.release();
+        if (from.vals.p) copy(to.vals, from.vals);                      // (a column that is not there holds neither buffer,
+        if (from.lims.p) copy(to.lims, from.lims);                      //  a dense one no limits, one without a tag no values)
         to.has = from.has;
-    }
-    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {            // ... and the tag columns
-        dst->d_tag_lims[slot].release();
-        dst->d_tag_vals[slot].release();
-        dst->has_tags[slot] = src->has_tags[slot];
-        if (!src->has_tags[slot]) continue;
-        copy(dst->d_tag_lims[slot], src->d_tag_lims[slot]);
-        if (src->d_tag_vals[slot].p) copy(dst->d_tag_vals[slot], src->d_tag_vals[slot]);
     }
     copy(dst->d_signs, src->d_signs);
     copy(dst->d_upper, src->d_upper);
@@ -4993,7 +4899,7 @@ int cph_multi_build(cph_multi* m, const float* vectors, uint64_t n) {
             h->d_blocks.release(); h->d_raw.release(); h->d_norm.release();
             h->host = HostIndex();
             sync_row_map(h);
-            sync_labels(h);
+            sync_columns(h);
             sync_removed(h);
         }
     });
@@ -5851,21 +5757,21 @@ uint64_t remove_ids(cph_index* h, const int64_t* ids, uint64_t m, int space) {
     return newly;
 }
 
+// One column of the live rows as compact gathers it, in the form the setters take: vals, and for a tag column lims (without
+// the leading 0 until set_live_columns adds it).  has: the handle holds the column, which a tag column over zero live rows
+// could not show otherwise.
+struct LiveColumn {
+    std::vector<int32_t> vals;
+    std::vector<uint64_t> lims;
+    bool has = false;
+};
+using LiveColumns = LiveColumn[kFacetColumns];
+
 // The live vectors of a finalized handle in input-row order (internal-id order without a row map), appended to `vecs`
 // (dim floats each); map[i] (the caller's, `n` entries from map_first on) = first_new + rank of the live row, -1 for a
-// removed one, indexed by input row (by_row) or by internal id.  labs (may be null): the live rows' labels and column
-// values, appended in the same order -- (*labs)[1 + slot] for every column the handle has, the label column at
-// kLabelSlot.  Returns the number of live rows.
-using LiveColumns = std::vector<int32_t>[1 + kMaxColumns];
-// The live rows' tags, appended like LiveColumns: a CSR per slot the handle has (lims without the leading 0; has: the
-// slot holds a column, which a column of empty rows over zero live rows could not show otherwise).
-struct LiveTags {
-    std::vector<uint64_t> lims[kMaxTagColumns];
-    std::vector<int32_t> vals[kMaxTagColumns];
-    bool has[kMaxTagColumns] = {};
-};
-uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new,
-                     LiveColumns* labs = nullptr, LiveTags* tags = nullptr) {
+// removed one, indexed by input row (by_row) or by internal id.  cols (may be null): the live rows' values in every column
+// the handle holds, appended in the same order.  Returns the number of live rows.
+uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool by_row, int64_t first_new, LiveColumns* cols = nullptr) {
     const HostIndex& hi = h->host;
     const uint64_t n = hi.n, size = h->size();
     const bool rows = h->has_rows && hi.rows.size() == n;
@@ -5879,22 +5785,29 @@ uint64_t gather_live(cph_index* h, std::vector<float>& vecs, int64_t* map, bool 
         map[by_row ? r : id] = gone ? -1 : first_new + (int64_t)live;
         if (gone) continue;
         vecs.insert(vecs.end(), row_vec(h, id), row_vec(h, id) + hi.dim);
-        if (labs)
-            for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot) {
-                const std::vector<int32_t>& col = column_of(h, slot).host;
-                if (col.size() == size) (*labs)[1 + slot].push_back(col[id]);
-            }
-        if (tags)
-            for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot) {
-                const std::vector<uint32_t>& tl = hi.tag_lims[slot];
-                if (tl.size() != size + 1) continue;
-                tags->has[slot] = true;
-                tags->vals[slot].insert(tags->vals[slot].end(), hi.tag_vals[slot].begin() + tl[id], hi.tag_vals[slot].begin() + tl[id + 1]);
-                tags->lims[slot].push_back(tags->vals[slot].size());
-            }
+        for (uint32_t col = 0; cols && col < kFacetColumns; ++col) {
+            const HostColumn& hc = hi.cols[col];
+            if (!hc.covers(size)) continue;
+            LiveColumn& to = (*cols)[col];
+            to.has = true;
+            to.vals.insert(to.vals.end(), hc.vals.begin() + hc.row_begin(id), hc.vals.begin() + hc.row_end(id));
+            if (is_tags(col)) to.lims.push_back(to.vals.size());
+        }
         ++live;
     }
     return live;
+}
+
+// After a compact: the gathered columns go back in.  New input row j holds the values of the live row it came from; set(col,
+// vals, lims) is the caller's setter over input rows.
+template <class Set>
+void set_live_columns(LiveColumns& cols, Set&& set) {
+    for (uint32_t col = 0; col < kFacetColumns; ++col) {
+        LiveColumn& c = cols[col];
+        if (!c.has) continue;
+        if (is_tags(col)) c.lims.insert(c.lims.begin(), 0);
+        set(col, c.vals.data(), is_tags(col) ? c.lims.data() : nullptr);
+    }
 }
 
 // cph_compact on one handle (a lifecycle call, like build + finalize).
@@ -5902,8 +5815,7 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
     if (!old_to_new) throw InvalidArg("null argument");
     refuse_host_less(h, "cph_compact");
     std::vector<float> vecs;
-    LiveColumns labs;                            // the live rows' labels and column values, in the order of the new input rows
-    LiveTags tags;                               // ... and their tags
+    LiveColumns cols;                            // the live rows' values in every column, in the order of the new input rows
     uint64_t live = 0;
     bool was_input = false;
     {
@@ -5916,20 +5828,14 @@ void compact_index(cph_index* h, int64_t* old_to_new) {
         was_input = h->ids_input;
         vecs.reserve(live * h->dim);
         std::vector<int64_t> map(h->size());
-        gather_live(h, vecs, map.data(), was_input, 0, &labs, &tags);
+        gather_live(h, vecs, map.data(), was_input, 0, &cols);
         std::copy(map.begin(), map.end(), old_to_new);
     }
     build_pending(h, vecs.data(), live, true);   // (cosine: the live rows are unit-half rows already)
     std::vector<float>().swap(vecs);
     finalize_build(h);
     if (was_input) set_result_ids(h, CPH_IDS_INPUT);
-    for (int slot = kLabelSlot; slot < (int)kMaxColumns; ++slot)      // new input row j: the values of the live row it came from
-        if (labs[1 + slot].size() == live) set_labels(h, labs[1 + slot].data(), live, CPH_IDS_INPUT, slot);
-    for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot)
-        if (tags.has[slot]) {
-            tags.lims[slot].insert(tags.lims[slot].begin(), 0);
-            set_tags(h, slot, tags.lims[slot].data(), tags.vals[slot].data(), live, CPH_IDS_INPUT);
-        }
+    set_live_columns(cols, [&](uint32_t col, const int32_t* vals, const uint64_t* lims) { set_column(h, col, vals, lims, live, CPH_IDS_INPUT); });
 }
 
 }  // namespace
@@ -5996,13 +5902,15 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     const uint64_t size = h->size(), need = size + m;
     if (m == 0) return size;
     if (!vectors) throw InvalidArg("null vectors");
-    if ((labels != nullptr) != h->has_labels)
-        throw InvalidArg(h->has_labels ? "the index has a label column: the added rows need labels"
+    RowColumn& lab = h->cols[kLabelColumn];
+    std::vector<int32_t>& host_labels = h->host.cols[kLabelColumn].vals;
+    if ((labels != nullptr) != lab.has)
+        throw InvalidArg(lab.has ? "the index has a label column: the added rows need labels"
                                        : "the index has no label column: labels for the added rows have nowhere to go");
-    if (has_extra_columns(h))
+    if (has_columns(h, CPH_FACET_COLUMN))
         throw InvalidArg("the index holds attribute columns and the added rows would have no values in them: drop the columns "
                          "(cph_set_column with NULL), add, then set them again at the new size");
-    if (has_tag_columns(h))
+    if (has_columns(h, CPH_FACET_TAGS))
         throw InvalidArg("the index holds tag columns and the added rows would have no tags in them: drop the columns "
                          "(cph_set_tags with NULL), add, then set them again at the new size");
     if (need >= 0xFFFFFFFFull) throw InvalidArg("too many vectors");
@@ -6017,20 +5925,20 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     h->use_device();
     quiesce(h);                                  // a batch in flight reads the arrays that may move
     h->label_rows.reset();                       // the inverted label column covers `size` ids: the next rescored call rebuilds it
-    h->facets[0].reset();                        // ... and so does the label column's facet dictionary
+    lab.facet.reset();                           // ... and so does the label column's facet dictionary
     HostIndex& hi = h->host;
     const uint64_t D = h->L.D, dim = h->dim, nw = (need + 31) / 32;
     const bool removed = hi.n_removed != 0;
     // everything that can fail comes first: host room, device room, the device pass; the handle changes after that
     h->tail_vecs.reserve((h->tail + m) * dim);
-    if (h->has_labels) hi.labels.reserve(need);
+    if (lab.has) host_labels.reserve(need);
     if (removed) hi.removed.reserve(nw);
     hipStream_t st = own_stream(h);
     const uint64_t cap = tail_capacity(std::min<uint64_t>(h->d_raw.n / D, h->d_norm.n), need);
     grow_keep(h->d_raw, size * D, cap * D, st);
     grow_keep(h->d_norm, size, cap, st);
     if (h->has_rows) grow_keep(h->d_rows, size, cap, st);
-    if (h->has_labels) grow_keep(h->d_labels, size, cap, st);
+    if (lab.has) grow_keep(lab.vals, size, cap, st);
     if (removed) grow_keep(h->d_removed, (size + 31) / 32, (cap + 31) / 32, st);
     DevBuf<float> d_src(m * dim);
     DevBuf<int32_t> d_lab(labels ? m : 0);
@@ -6050,13 +5958,13 @@ uint64_t add_rows(cph_index* h, const float* vectors, uint64_t m, const int32_t*
     a.raw = h->d_raw.p;
     a.norm_sq = h->d_norm.p;
     a.rows = h->has_rows ? h->d_rows.p : nullptr;
-    a.labels = labels ? h->d_labels.p : nullptr;
+    a.labels = labels ? lab.vals.p : nullptr;
     a.removed = removed ? h->d_removed.p : nullptr;
     tail_append(a, st);
     HIP_CHECK(hipStreamSynchronize(st));
     // (nothing below throws before the handle is consistent again: the room was reserved above)
     h->tail_vecs.insert(h->tail_vecs.end(), vectors, vectors + m * dim);
-    if (h->has_labels && hi.labels.size() == size) hi.labels.insert(hi.labels.end(), labels, labels + m);
+    if (lab.has && host_labels.size() == size) host_labels.insert(host_labels.end(), labels, labels + m);
     if (removed) {
         if (size & 31) hi.removed[(size - 1) >> 5] &= (1u << (size & 31)) - 1u;
         hi.removed.resize(nw, 0u);
@@ -6241,12 +6149,130 @@ int cph_parts_get_removed(cph_parts* m, uint32_t* words) {
     });
 }
 
+}  // extern "C"
+
+// ---- the columns of replicas and parts ----
+namespace {
+
+// A setter over several handles, all or none: ask(h) on every handle under its mutex before any of them changes, then
+// change(i, h) on each, under its mutex too; when one throws, the column goes from every handle.
+template <class Ask, class Change>
+void set_column_on_all(const std::vector<cph_index*>& hs, uint32_t col, Ask&& ask, Change&& change) {
+    for (cph_index* h : hs) {
+        std::lock_guard<std::mutex> g(h->mu);
+        ask(h);
+    }
+    try {
+        for (size_t i = 0; i < hs.size(); ++i) {
+            std::lock_guard<std::mutex> g(hs[i]->mu);
+            change(i, hs[i]);
+        }
+    } catch (...) {                                      // (a refused row or a device failure: no handle keeps a column the others lack)
+        for (cph_index* h : hs) {
+            std::lock_guard<std::mutex> g(h->mu);
+            try { install_column_locked(h, col, nullptr, false); } catch (...) {}
+        }
+        throw;
+    }
+}
+
+// cph_multi_set_labels / _set_column / _set_tags: replica 0 validates the rest and makes the stored form once (input rows
+// moved to internal order, tag rows canonical) before anything changes; the others receive its host copy.
+void multi_set_column(cph_multi* m, uint32_t col, const int32_t* vals, const uint64_t* lims, uint64_t n, int space) {
+    std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
+    cph_index* r0 = m->reps[0];
+    const bool set = column_given(col, vals, lims);
+    HostColumn c;
+    set_column_on_all(
+        m->reps, col,
+        [&](cph_index* h) {
+            require_column_target(h, col, set, n);
+            if (h != r0) return;
+            require_id_space(space);
+            if (set) c = column_to_store_locked(r0, col, vals, lims, n, space);
+        },
+        [&](size_t i, cph_index* h) { install_column_locked(h, col, !set ? nullptr : i == 0 ? &c : &r0->host.cols[col], i == 0); });
+}
+
+// cph_parts_set_labels / _set_column / _set_tags: a column over GLOBAL input rows, cut at the part bounds (tag limits rebased).
+void parts_set_column(cph_parts* m, uint32_t col, const int32_t* vals, const uint64_t* lims, uint64_t n) {
+    if (!m) throw InvalidArg("null handle");
+    const ColumnWords& w = words_of(col);
+    std::unique_lock<std::shared_mutex> lk(m->life);
+    if (!parts_finalized(m)) throw InvalidArg(std::string(w.plural) + " belong to a finalized index: finalize or load it first");
+    const bool set = column_given(col, vals, lims);
+    if (set && n != m->bounds.back()) throw InvalidArg(wrong_column_size(col, n, m->bounds.back()));
+    if (set && lims) {
+        if (lims[0] != 0) throw InvalidArg("tag limits must start at 0");      // (before the cut rebases them)
+        for (uint64_t i = 0; i < n; ++i)
+            if (lims[i + 1] < lims[i]) throw InvalidArg("tag limits must not decrease (row " + std::to_string(i) + ")");
+        if (lims[n] != 0 && !vals) throw InvalidArg("null tags");
+    }
+    std::vector<uint64_t> cut;
+    set_column_on_all(
+        m->parts, col,
+        [&](cph_index* h) {
+            if (set && (!h->has_rows || h->host.rows.size() != h->host.n))
+                throw InvalidArg(std::string("a part has no row map: ") + w.plural + " of a partitioned index are given in input rows");
+        },
+        [&](size_t p, cph_index* h) {
+            if (!set) {
+                require_column_target(h, col, false, 0);
+                install_column_locked(h, col, nullptr, true);
+                return;
+            }
+            const uint64_t b0 = m->bounds[p], b1 = m->bounds[p + 1];
+            if (lims) {
+                cut.assign(lims + b0, lims + b1 + 1);
+                for (uint64_t& x : cut) x -= lims[b0];
+            }
+            HostColumn c = column_to_store_locked(h, col, vals ? vals + (lims ? lims[b0] : b0) : nullptr, lims ? cut.data() : nullptr, b1 - b0, CPH_IDS_INPUT);
+            install_column_locked(h, col, &c, true);
+        });
+}
+
+// ---- the filters of a partitioned index, made part by part ----
+// cnt parts filters from their per-part slices: make(p, slice) makes part p's cnt filters on that part's device, all or
+// none.  All made, or none: what earlier parts made goes with `made` (a cph_parts_filter destroys its slices).
+template <class Make>
+void parts_filters_from_slices(size_t P, uint64_t n_bits, uint32_t cnt, cph_parts_filter** out, Make&& make) {
+    std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
+    for (auto& f : made) {
+        f.reset(new cph_parts_filter());
+        f->n_bits = n_bits;
+        f->f.reserve(P);
+    }
+    std::vector<cph_filter*> slice(cnt);
+    for (size_t p = 0; p < P; ++p) {
+        make(p, slice.data());
+        for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
+    }
+    for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
+}
+
+// cph_parts_filters_from_labels / cph_parts_filters_from_column: every part evaluates its own slice of the column.
+void parts_filters_from_column(cph_parts* m, int kind, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt,
+                               cph_parts_filter** out) {
+    const uint32_t col = facet_column(kind, slot);
+    if (cnt == 0) return;
+    if (!out) throw InvalidArg("null argument");
+    std::fill(out, out + cnt, nullptr);
+    if (!m || !lo || !hi) throw InvalidArg("null argument");
+    std::shared_lock<std::shared_mutex> lk(m->life);
+    if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
+    parts_filters_from_slices(m->parts.size(), m->bounds.back(), cnt, out,
+                              [&](size_t p, cph_filter** slice) { filters_from_labels(m->parts[p], col, lo, hi, cnt, slice); });
+}
+
+}  // namespace
+
+extern "C" {
+
 int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
     return guarded([&] {
         if (!m || !old_to_new) throw InvalidArg("null argument");
         std::vector<float> vecs;
-        LiveColumns labs;                         // the live rows' labels and column values in global row order (every part has a column, or none)
-        LiveTags tags;                            // ... and their tags
+        LiveColumns cols;                         // the live rows' values in every column, in global row order (every part has a column, or none)
         uint64_t live = 0;
         {
             std::unique_lock<std::shared_mutex> lk(m->life);
@@ -6256,7 +6282,7 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
             for (uint32_t p = 0; p < P; ++p) {
                 cph_index* h = m->parts[p];
                 std::lock_guard<std::mutex> g(h->mu);
-                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live, &labs, &tags);
+                live += gather_live(h, vecs, map.data() + m->bounds[p], true, (int64_t)live, &cols);
             }
             if (live < kMinPartRows * P)      // cph_parts_build's own refusal, before any part gives up its index
                 throw InvalidArg("a partitioned index needs at least " + std::to_string(kMinPartRows) + " rows per part: " +
@@ -6266,195 +6292,53 @@ int cph_parts_compact(cph_parts* m, int64_t* old_to_new) {
         parts_build(m, vecs.data(), live, true);              // the live rows, cut again by cph_host_part_bounds
         std::vector<float>().swap(vecs);
         check_rc(cph_parts_finalize(m));
-        if (labs[0].size() == live) check_rc(cph_parts_set_labels(m, labs[0].data(), live));     // cut again at the new bounds
-        for (uint32_t slot = 0; slot < kMaxColumns; ++slot)
-            if (labs[1 + slot].size() == live) check_rc(cph_parts_set_column(m, slot, labs[1 + slot].data(), live));
-        for (uint32_t slot = 0; slot < kMaxTagColumns; ++slot)
-            if (tags.has[slot]) {
-                tags.lims[slot].insert(tags.lims[slot].begin(), 0);
-                check_rc(cph_parts_set_tags(m, slot, tags.lims[slot].data(), tags.vals[slot].data(), live));
-            }
+        set_live_columns(cols, [&](uint32_t col, const int32_t* vals, const uint64_t* lims) { parts_set_column(m, col, vals, lims, live); });      // cut again at the new bounds
     });
 }
 
-// ---- label column of replicas and parts ----
-// cph_multi_set_labels / cph_multi_set_column.
-static void multi_set_column(cph_multi* m, const int32_t* labels, uint64_t n, int space, int slot) {
-    if (!m) throw InvalidArg("null handle");
-    std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
-    cph_index* r0 = m->reps[0];
-    for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
-        std::lock_guard<std::mutex> g(h->mu);
-        require_labels_target(h, labels, n, slot);
-    }
-    set_labels(r0, labels, n, space, slot);              // validates the rest, and moves input rows to internal order once
-    try {
-        for (size_t i = 1; i < m->reps.size(); ++i) {
-            cph_index* h = m->reps[i];
-            std::lock_guard<std::mutex> g(h->mu);
-            install_labels_locked(h, labels ? column_of(r0, slot).host.data() : nullptr, n, false, slot);
-        }
-    } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
-        for (cph_index* h : m->reps) {
-            std::lock_guard<std::mutex> g(h->mu);
-            try { install_labels_locked(h, nullptr, 0, false, slot); } catch (...) {}
-        }
-        throw;
-    }
-}
-
 int cph_multi_set_labels(cph_multi* m, const int32_t* labels, uint64_t n, int space) {
-    return guarded([&] { multi_set_column(m, labels, n, space, kLabelSlot); });
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        multi_set_column(m, kLabelColumn, labels, nullptr, n, space);
+    });
 }
 
 int cph_multi_set_column(cph_multi* m, uint32_t slot, const int32_t* values, uint64_t n, int space) {
     return guarded([&] {
-        require_slot(slot);
-        multi_set_column(m, values, n, space, (int)slot);
+        const uint32_t col = facet_column(CPH_FACET_COLUMN, slot);
+        if (!m) throw InvalidArg("null handle");
+        multi_set_column(m, col, values, nullptr, n, space);
     });
 }
 
-// cph_parts_set_labels / cph_parts_set_column.
-static void parts_set_column(cph_parts* m, const int32_t* labels, uint64_t n, int slot) {
-    const bool lab = slot == kLabelSlot;
-    if (!m) throw InvalidArg("null handle");
-    std::unique_lock<std::shared_mutex> lk(m->life);
-    if (!parts_finalized(m))
-        throw InvalidArg(lab ? "labels belong to a finalized index: finalize or load it first"
-                             : "columns belong to a finalized index: finalize or load it first");
-    if (labels && n != m->bounds.back())
-        throw InvalidArg(std::string(lab ? "label column has " : "column has ") + std::to_string(n) + " entries, the index holds " +
-                         std::to_string(m->bounds.back()));
-    for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
-        std::lock_guard<std::mutex> g(h->mu);
-        if (labels && (!h->has_rows || h->host.rows.size() != h->host.n))
-            throw InvalidArg(lab ? "a part has no row map: labels of a partitioned index are given in input rows"
-                                 : "a part has no row map: columns of a partitioned index are given in input rows");
-    }
-    try {
-        for (size_t p = 0; p < m->parts.size(); ++p)     // global input rows, cut at the part bounds
-            set_labels(m->parts[p], labels ? labels + m->bounds[p] : nullptr, m->bounds[p + 1] - m->bounds[p], CPH_IDS_INPUT, slot);
-    } catch (...) {                                      // (a device failure: no part keeps a column the others lack)
-        for (cph_index* h : m->parts) {
-            std::lock_guard<std::mutex> g(h->mu);
-            try { install_labels_locked(h, nullptr, 0, true, slot); } catch (...) {}
-        }
-        throw;
-    }
-}
-
-int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n) {
-    return guarded([&] { parts_set_column(m, labels, n, kLabelSlot); });
-}
-
-int cph_parts_set_column(cph_parts* m, uint32_t slot, const int32_t* values, uint64_t n) {
-    return guarded([&] {
-        require_slot(slot);
-        parts_set_column(m, values, n, (int)slot);
-    });
-}
-
-// cph_parts_filters_from_labels / cph_parts_filters_from_column.
-static void parts_filters_from_column(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out, int slot) {
-    if (cnt == 0) return;
-    if (!out) throw InvalidArg("null argument");
-    std::fill(out, out + cnt, nullptr);
-    if (!m || !lo || !hi) throw InvalidArg("null argument");
-    std::shared_lock<std::shared_mutex> lk(m->life);
-    if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
-    std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
-    for (auto& f : made) {
-        f.reset(new cph_parts_filter());
-        f->n_bits = m->bounds.back();
-        f->f.reserve(m->parts.size());
-    }
-    std::vector<cph_filter*> slice(cnt);
-    for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
-        filters_from_labels(m->parts[p], lo, hi, cnt, slice.data(), slot);
-        for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
-    }
-    for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
-}
-
-int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
-    return guarded([&] { parts_filters_from_column(m, lo, hi, cnt, out, kLabelSlot); });
-}
-
-int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
-    return guarded([&] {
-        require_slot(slot);
-        parts_filters_from_column(m, lo, hi, cnt, out, (int)slot);
-    });
-}
-
-// ---- tag columns of replicas and parts (cph_set_tags) ----
 int cph_multi_set_tags(cph_multi* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n, int space) {
     return guarded([&] {
         if (!m) throw InvalidArg("null handle");
-        require_tag_slot(slot);
-        std::unique_lock<std::shared_mutex> lk(m->life);     // searches in flight finish first
-        cph_index* r0 = m->reps[0];
-        for (cph_index* h : m->reps) {                       // every replica is asked before any of them changes
-            std::lock_guard<std::mutex> g(h->mu);
-            require_tags_target(h, lims != nullptr, n);
-        }
-        set_tags(r0, slot, lims, tags, n, space);            // validates the rest, and makes the canonical column once
-        try {
-            for (size_t i = 1; i < m->reps.size(); ++i) {
-                cph_index* h = m->reps[i];
-                std::lock_guard<std::mutex> g(h->mu);
-                install_tags_locked(h, slot, lims ? r0->host.tag_lims[slot].data() : nullptr, r0->host.tag_vals[slot].data(), n, false);
-            }
-        } catch (...) {                                      // (a device failure: no replica keeps a column the others lack)
-            for (cph_index* h : m->reps) {
-                std::lock_guard<std::mutex> g(h->mu);
-                try { install_tags_locked(h, slot, nullptr, nullptr, 0, false); } catch (...) {}
-            }
-            throw;
-        }
+        multi_set_column(m, facet_column(CPH_FACET_TAGS, slot), tags, lims, n, space);
     });
 }
 
-// lims[n + 1] / tags over GLOBAL input rows, cut at the part bounds with the limits rebased.
+int cph_parts_set_labels(cph_parts* m, const int32_t* labels, uint64_t n) {
+    return guarded([&] { parts_set_column(m, kLabelColumn, labels, nullptr, n); });
+}
+
+int cph_parts_set_column(cph_parts* m, uint32_t slot, const int32_t* values, uint64_t n) {
+    return guarded([&] { parts_set_column(m, facet_column(CPH_FACET_COLUMN, slot), values, nullptr, n); });
+}
+
 int cph_parts_set_tags(cph_parts* m, uint32_t slot, const uint64_t* lims, const int32_t* tags, uint64_t n) {
     return guarded([&] {
         if (!m) throw InvalidArg("null handle");
-        require_tag_slot(slot);
-        std::unique_lock<std::shared_mutex> lk(m->life);
-        if (!parts_finalized(m)) throw InvalidArg("tags belong to a finalized index: finalize or load it first");
-        if (lims) {
-            if (n != m->bounds.back())
-                throw InvalidArg("tag column has " + std::to_string(n) + " rows, the index holds " + std::to_string(m->bounds.back()));
-            if (lims[0] != 0) throw InvalidArg("tag limits must start at 0");      // (before the cut rebases them)
-            for (uint64_t i = 0; i < n; ++i)
-                if (lims[i + 1] < lims[i]) throw InvalidArg("tag limits must not decrease (row " + std::to_string(i) + ")");
-            if (lims[n] != 0 && !tags) throw InvalidArg("null tags");
-        }
-        for (cph_index* h : m->parts) {                      // every part is asked before any of them changes
-            std::lock_guard<std::mutex> g(h->mu);
-            if (lims && (!h->has_rows || h->host.rows.size() != h->host.n))
-                throw InvalidArg("a part has no row map: tags of a partitioned index are given in input rows");
-        }
-        try {
-            std::vector<uint64_t> cut;
-            for (size_t p = 0; p < m->parts.size(); ++p) {
-                const uint64_t b0 = m->bounds[p], b1 = m->bounds[p + 1];
-                if (!lims) {
-                    set_tags(m->parts[p], slot, nullptr, nullptr, 0, CPH_IDS_INPUT);
-                    continue;
-                }
-                cut.assign(lims + b0, lims + b1 + 1);
-                for (uint64_t& x : cut) x -= lims[b0];
-                set_tags(m->parts[p], slot, cut.data(), tags ? tags + lims[b0] : nullptr, b1 - b0, CPH_IDS_INPUT);
-            }
-        } catch (...) {                                      // (a refused row or a device failure: no part keeps a column the others lack)
-            for (cph_index* h : m->parts) {
-                std::lock_guard<std::mutex> g(h->mu);
-                try { install_tags_locked(h, slot, nullptr, nullptr, 0, true); } catch (...) {}
-            }
-            throw;
-        }
+        parts_set_column(m, facet_column(CPH_FACET_TAGS, slot), tags, lims, n);
     });
+}
+
+int cph_parts_filters_from_labels(cph_parts* m, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] { parts_filters_from_column(m, CPH_FACET_LABEL, 0, lo, hi, cnt, out); });
+}
+
+int cph_parts_filters_from_column(cph_parts* m, uint32_t slot, const int32_t* lo, const int32_t* hi, uint32_t cnt, cph_parts_filter** out) {
+    return guarded([&] { parts_filters_from_column(m, CPH_FACET_COLUMN, slot, lo, hi, cnt, out); });
 }
 
 int cph_parts_filters_from_tags(cph_parts* m, uint32_t slot, const uint32_t* test_lims, const int32_t* test_vals, const uint8_t* modes,
@@ -6464,24 +6348,14 @@ int cph_parts_filters_from_tags(cph_parts* m, uint32_t slot, const uint32_t* tes
         if (!out) throw InvalidArg("null argument");
         std::fill(out, out + cnt, nullptr);
         if (!m || !test_lims || !modes) throw InvalidArg("null argument");
-        require_tag_slot(slot);
+        const uint32_t col = facet_column(CPH_FACET_TAGS, slot);
         std::vector<uint32_t> table;
         size_t vals_at = 0;
         pack_tag_tests(test_lims, test_vals, modes, cnt, table, vals_at);
         std::shared_lock<std::shared_mutex> lk(m->life);
         if (!parts_finalized(m)) throw std::runtime_error("Search failed: invalid entry point after finalize.");
-        std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
-        for (auto& f : made) {
-            f.reset(new cph_parts_filter());
-            f->n_bits = m->bounds.back();
-            f->f.reserve(m->parts.size());
-        }
-        std::vector<cph_filter*> slice(cnt);
-        for (size_t p = 0; p < m->parts.size(); ++p) {       // every part evaluates its own slice of the column
-            filters_from_tags(m->parts[p], slot, table, vals_at, cnt, slice.data());
-            for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
-        }
-        for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
+        parts_filters_from_slices(m->parts.size(), m->bounds.back(), cnt, out,
+                                  [&](size_t p, cph_filter** slice) { filters_from_tags(m->parts[p], col, table, vals_at, cnt, slice); });
     });
 }
 
@@ -6506,21 +6380,12 @@ int cph_parts_filters_combine(int op, const cph_parts_filter* const* a, uint32_t
         };
         for (uint32_t j = 0; j < cnt; ++j) same(a[j]);
         for (uint32_t j = 0; j < n_b; ++j) same(b[j]);
-        std::vector<std::unique_ptr<cph_parts_filter>> made(cnt);
-        for (auto& f : made) {
-            f.reset(new cph_parts_filter());
-            f->n_bits = n_bits;
-            f->f.reserve(P);
-        }
         std::vector<const cph_filter*> ap(cnt), bp(n_b);
-        std::vector<cph_filter*> slice(cnt);
-        for (size_t p = 0; p < P; ++p) {
+        parts_filters_from_slices(P, n_bits, cnt, out, [&](size_t p, cph_filter** slice) {
             for (uint32_t j = 0; j < cnt; ++j) ap[j] = a[j]->f[p];
             for (uint32_t j = 0; j < n_b; ++j) bp[j] = b[j]->f[p];
-            filters_combine(op, ap.data(), cnt, n_b ? bp.data() : nullptr, n_b, slice.data());
-            for (uint32_t j = 0; j < cnt; ++j) made[j]->f.push_back(slice[j]);
-        }
-        for (uint32_t j = 0; j < cnt; ++j) out[j] = made[j].release();
+            filters_combine(op, ap.data(), cnt, n_b ? bp.data() : nullptr, n_b, slice);
+        });
     });
 }
 
@@ -6600,8 +6465,8 @@ void check_batch_size(uint64_t n) {
 // The key column of a grouped or maxsim call: the keys object (checked against the handle), else the label column.
 const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) {
     if (!keys) {
-        if (!h->has_labels) throw InvalidArg("grouped search needs keys: the index has no label column (cph_set_labels) and no keys object was given");
-        return h->d_labels.p;
+        if (!h->cols[kLabelColumn].has) throw InvalidArg("grouped search needs keys: the index has no label column (cph_set_labels) and no keys object was given");
+        return h->cols[kLabelColumn].vals.p;
     }
     if (keys->device != h->device) throw InvalidArg("group keys belong to another device");
     if (keys->size != h->size())

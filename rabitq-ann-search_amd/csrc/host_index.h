@@ -437,6 +437,22 @@ inline void filter_combine_host(int op, const uint32_t* a, const uint32_t* b, bo
 }
 
 constexpr uint32_t kMaxColumns = 8;   // extra attribute columns of a handle (cph_set_column), next to the label column
+// The row attributes of a handle, each under one id: 0 the label column, 1..kMaxColumns the int32 columns, then the tag columns.
+constexpr uint32_t kFacetColumns = 1 + kMaxColumns + kMaxTagColumns;
+
+// The host copy of one row attribute in internal-id order.  A dense column (the label column, an int32 column) is vals[n]
+// and no lims; a tag column is the canonical CSR lims[n + 1] into vals.  Both empty = the index holds no such column.
+struct HostColumn {
+    std::vector<int32_t> vals;
+    std::vector<uint32_t> lims;
+    bool empty() const { return vals.empty() && lims.empty(); }
+    bool dense() const { return lims.empty(); }
+    // complete over n rows (what a replica without host arrays never is)
+    bool covers(size_t n) const { return dense() ? !vals.empty() && vals.size() == n : lims.size() == n + 1; }
+    // the values of row i: vals[row_begin(i)] .. vals[row_end(i) - 1]
+    size_t row_begin(size_t i) const { return dense() ? i : lims[i]; }
+    size_t row_end(size_t i) const { return dense() ? i + 1 : lims[i + 1]; }
+};
 
 struct HostIndex {
     size_t D = 0, bw = 0, dim = 0, n = 0;
@@ -461,15 +477,9 @@ struct HostIndex {
     // empty = none (n_removed = 0).  Only a native file carries them; save() refuses an index that has some.
     std::vector<uint32_t> removed;
     uint64_t n_removed = 0;
-    // The label column (cph_set_labels): labels[i] = label of internal id i; empty = none.  No file carries it.
-    std::vector<int32_t> labels;
-    // The attribute columns (cph_set_column): columns[s][i] = value of internal id i in slot s; empty = none.  They
-    // live and die with the label column: no file carries them.
-    std::vector<int32_t> columns[kMaxColumns];
-    // The tag columns (cph_set_tags): the canonical CSR of slot s in internal-id order, tag_lims[s] = [n + 1] offsets into
-    // tag_vals[s]; an empty tag_lims[s] = none.  They live and die with the attribute columns.
-    std::vector<uint32_t> tag_lims[kMaxTagColumns];
-    std::vector<int32_t> tag_vals[kMaxTagColumns];
+    // The row attributes (cph_set_labels, cph_set_column, cph_set_tags), by column id; an empty one = none.  No file
+    // carries them: a load or a build leaves none, compact carries them over.
+    HostColumn cols[kFacetColumns];
     RefLayout RL;
     Rotation rot;
     bool has_dup_neighbors = false;

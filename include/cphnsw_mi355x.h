@@ -225,6 +225,20 @@ int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t
  * the multi form): a filter that allows at most max_allowed ids (and a k <= 1024) takes the exact path.  Default 0: never,
  * every call does what it did before. */
 int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
+/* Engine of every exact scan that serves one filter or none (cph_search_batch_exact*, the cut-over above, and the grouped,
+ * diverse, MaxSim, fused and rescored searches that ride on them).  0 (default): the fp32 VALU scan, launch for launch what
+ * it was.  1: the matrix cores (v_mfma_f32_32x32x2_f32) discard every candidate that provably cannot be in a query's top-k
+ * -- approximate distance beyond the k-th smallest seen plus twice the slack below -- and the VALU arithmetic re-scores the
+ * survivors; a query that cannot be certified (its survivors overflow a pool, or a number is not finite) is answered by the
+ * VALU scan behind it on the same stream.  Every output byte equals engine 0's.  Any other value: CPH_INVALID_ARGUMENT.
+ * The scan of a batch with per-query filters, the range search and the tail scan do not change.
+ * cph_last_matrix_stats: out[0] = parts of the candidate list, out[1] = ids re-scored (summed over the queries), out[2] =
+ * queries the VALU scan answered, of the last batch if engine 1 ran it; zeros otherwise.
+ * cph_host_exact_matrix_slack: the slack, a bound on |approximate - exact distance| for a query of squared norm qnorm
+ * against rows of squared norm <= bn_max at padded dimension D (the statement the device uses). */
+int cph_set_exact_engine(cph_index* h, int engine);
+int cph_last_matrix_stats(cph_index* h, uint64_t out[3]);
+int cph_host_exact_matrix_slack(float qnorm, float bn_max, uint32_t D, float* out);
 
 /* ---- range search ----------------------------------------------------------------------- */
 /* Every allowed id closer than a radius, in CSR form: lims[n + 1] (lims[0] = 0), query i owns ids / dist
@@ -1042,6 +1056,7 @@ int cph_multi_search_fused(cph_multi* m, const float* queries, uint64_t n, uint6
                            uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
                            int exact, int64_t* ids, float* score, int32_t* hits);
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed);
+int cph_multi_set_exact_engine(cph_multi* m, int engine);        /* every replica */
 int cph_multi_search(cph_multi* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_multi_has_row_map(cph_multi* m, int* flag);
 int cph_multi_set_row_map(cph_multi* m, const uint32_t* rows, uint64_t n);
@@ -1131,6 +1146,7 @@ int cph_parts_search_batch_filters_device(cph_parts* m, const float* d_queries, 
                                           int exact, int64_t* d_ids, float* d_dist, void* stream);
 int cph_parts_search(cph_parts* m, const float* query, uint64_t k, int64_t* ids, float* dist, uint64_t* count);
 int cph_parts_set_exact_threshold(cph_parts* m, uint64_t max_allowed);
+int cph_parts_set_exact_engine(cph_parts* m, int engine);        /* every part */
 int cph_parts_filter_create_rows(cph_parts* m, const uint32_t* words, uint64_t n_bits, cph_parts_filter** out);
 int cph_parts_filter_destroy(cph_parts_filter* f);
 int cph_parts_last_search_stats(cph_parts* m, uint64_t out[13]);

@@ -57,6 +57,11 @@ SYMBOLS = {
     "cph_search_batch_exact_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "cph_set_exact_threshold": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "cph_set_exact_engine": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_multi_set_exact_engine": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_parts_set_exact_engine": (C.c_int, [C.c_void_p, C.c_int]),
+    "cph_last_matrix_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cph_host_exact_matrix_slack": (C.c_int, [C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_float)]),
     "cph_search_batch_filters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cph_search_batch_filters_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,

@@ -342,6 +342,7 @@ class CPIndex:
         self._bits = int(bits)
         self._result_ids = "internal"
         self._exact_threshold = 0
+        self._exact_engine = "vector"
         self._columns = {}           # attribute columns (set_column): name -> slot on the handle
         self._tag_columns = {}       # tag columns (set_tags): name -> slot on the handle
         if metric not in self._METRICS:
@@ -510,6 +511,7 @@ class CPIndex:
         v._devices = [self._devices[i]]
         v._result_ids = "input" if self.is_finalized else "internal"
         v._exact_threshold = self._exact_threshold
+        v._exact_engine = self._exact_engine
         v._columns = self._column_slots()                # shared with the index: a part holds its slice of every column in
         v._tag_columns = self._tag_slots()               # the same slot, so the view sees the names set before and after it was made
         return v
@@ -2466,6 +2468,30 @@ class CPIndex:
             _lib.check(_lib.lib().cph_set_exact_threshold(self._h, v))
         self._exact_threshold = v
 
+    _EXACT_ENGINES = ("vector", "matrix")
+
+    @property
+    def exact_engine(self):
+        """Engine of every exact scan that serves one filter or none (exact=True, the exact_threshold route, and the
+        grouped, diverse, MaxSim, fused and rescored searches on top of them).  "vector" (default): the fp32 VALU scan.
+        "matrix": the matrix cores discard every candidate that provably cannot be in the top-k and the vector
+        arithmetic re-scores the survivors -- the same bytes, ids and order.  After a matrix batch last_search_stats()
+        also reports matrix_parts, matrix_survivors and matrix_redo."""
+        return self._exact_engine
+
+    @exact_engine.setter
+    def exact_engine(self, name):
+        if name not in self._EXACT_ENGINES:
+            raise ValueError(f'exact_engine must be "vector" or "matrix", not {name!r}')
+        code = self._EXACT_ENGINES.index(name)
+        if self._p is not None:
+            _lib.check(_lib.lib().cph_parts_set_exact_engine(self._p, code))
+        elif self._m is not None:
+            _lib.check(_lib.lib().cph_multi_set_exact_engine(self._m, code))
+        else:
+            _lib.check(_lib.lib().cph_set_exact_engine(self._h, code))
+        self._exact_engine = name
+
     # -- properties -------------------------------------------------------------------------
     @property
     def size(self):
@@ -2518,7 +2544,16 @@ class CPIndex:
         keys = ("expansions", "exact_l2", "new_neighbours", "beam_pushes", "stage2_skipped",
                 "rerun_queries", "kernel_us", "expansions_nothing_new", "slots", "capacity",
                 "stage2_reruns", "stage2_undecided") + (("merge_us",) if self._p is not None else ())
-        return dict(zip(keys, [int(x) for x in out]))
+        stats = dict(zip(keys, [int(x) for x in out]))
+        # a batch the matrix engine ran: parts (the most of any handle), re-scored ids and fallback queries (summed)
+        mx = [0, 0, 0]
+        for h in self._replicas():
+            w = (C.c_uint64 * 3)()
+            _lib.check(_lib.lib().cph_last_matrix_stats(h, w))
+            mx = [max(mx[0], int(w[0])), mx[1] + int(w[1]), mx[2] + int(w[2])]
+        if mx[0]:
+            stats.update(matrix_parts=mx[0], matrix_survivors=mx[1], matrix_redo=mx[2])
+        return stats
 
     def synchronize(self):
         """Waits for every batch enqueued with search_batch_device."""

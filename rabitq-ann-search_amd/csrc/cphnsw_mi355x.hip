@@ -38,6 +38,7 @@
 #include "device_facets.h"
 #include "device_filter_ops.h"
 #include "device_exact.h"
+#include "device_exact_mfma.h"
 #include "device_range.h"
 #include "device_tail.h"
 #include "device_diverse.h"
@@ -159,6 +160,12 @@ struct BatchSet {
     DevBuf<float> x_qpad, x_qnorm;
     DevBuf<unsigned long long> x_pools;
     DevBuf<uint32_t> x_counts;
+    // the matrix engine (device_exact_mfma.h): the queries' slacks and flags, the re-score's one pool per query; mx_parts:
+    // the parts of the set's last batch if the matrix engine ran it, else 0
+    DevBuf<float> mx_eps;
+    DevBuf<uint32_t> mx_flags, mx_rcounts;
+    DevBuf<unsigned long long> mx_rpools;
+    uint32_t mx_parts = 0;
     bool stats_in_hbm = false; // the last batch's statistics were not copied to pin_stats yet
     // batches with per-query filters (enqueue_filters): the call's tables -- scan descriptors, permutation, work lists,
     // filter_of, bitmap pointers -- travel as one staged table on the batch's stream.  d_redo2: the re-run list of the
@@ -353,6 +360,12 @@ struct cph_index {
     uint64_t facet_slab = kFacetSlabCounters;
     void drop_facets() { for (auto& c : cols) c.facet.reset(); }
     size_t exact_scratch_bytes = (size_t)1 << 30;   // pool scratch of one exact batch, at most (CPH_EXACT_SCRATCH_MB at creation): plan_exact
+    // cph_set_exact_engine: 0 the vector scan, 1 the matrix prefilter.  d_bn_max: the largest norm_sq of the rows (as bits),
+    // made on first use for the index state (index_epoch, size()) it is valid for; bn_ev follows the kernel that made it
+    int exact_engine = 0;
+    DevBuf<uint32_t> d_bn_max;
+    uint64_t bn_epoch = ~0ull, bn_rows = 0;
+    hipEvent_t bn_ev = nullptr;
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
     // host.n_removed (what save_native writes).  rm_epoch names this state of R (g_removed_epoch); live = ~R as a filter,
@@ -646,6 +659,7 @@ void release_scratch(BatchSet& s) {
     s.d_bitmaps.release(); s.d_logids.release(); s.d_beam.release(); s.d_beam_tail.release();
     s.r_bitmaps.release(); s.r_logids.release(); s.r_beam.release(); s.r_beam_tail.release();
     s.x_qpad.release(); s.x_qnorm.release(); s.x_pools.release(); s.x_counts.release();
+    s.mx_eps.release(); s.mx_flags.release(); s.mx_rcounts.release(); s.mx_rpools.release();
     s.m_queries.release(); s.m_c.release();
     s.slots = 0; s.cap = 0; s.r_slots = 0;
 }
@@ -1232,8 +1246,9 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
     launch_search_kernel(h->bits, h->L.D, pf, d_allow != nullptr, tab, grid, lds, st, a);
 }
 
-// Statistics block to pinned memory, completion event, bookkeeping: the tail of every enqueued batch.
-void finish_batch(cph_index* h, BatchSet& s, hipStream_t st) {
+// Statistics block to pinned memory, completion event, bookkeeping: the tail of every enqueued batch.  matrix_parts: the
+// parts of a batch the matrix engine ran (enqueue_exact_matrix), 0 from every other path.
+void finish_batch(cph_index* h, BatchSet& s, hipStream_t st, uint32_t matrix_parts = 0) {
     HIP_CHECK(hipEventRecord(s.ev1, st));
     // the statistics block lands in pinned host memory; it is only read when somebody asks.  (The private sets of the
     // cph_search leader slots leave it in HBM until then: their callers wait for the stream, and the copy command would
@@ -1242,6 +1257,7 @@ void finish_batch(cph_index* h, BatchSet& s, hipStream_t st) {
     if (!s.stats_in_hbm) HIP_CHECK(hipMemcpyAsync(s.pin_stats, s.d_stats.p, kStatWords * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipEventRecord(s.ev_done, st));
     s.used = true;
+    s.mx_parts = matrix_parts;
     h->last_search = (int)(&s - h->sets);
     h->last_range = false;
 }
@@ -1526,8 +1542,12 @@ const uint32_t* filter_id_list(const cph_filter* f, hipStream_t st) {
 
 // An exact batch (device_exact.h) in the place of enqueue_search: d_raw_q = [nq][dim] raw queries in HBM, results into
 // device buffers, everything enqueued on `st`.  The candidates are the filter's ids (not empty), or every id.
+void enqueue_exact_matrix(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
+                          int64_t* d_ids, float* d_dist, hipStream_t st);
+
 void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
                    int64_t* d_ids, float* d_dist, hipStream_t st) {
+    if (h->exact_engine == 1) return enqueue_exact_matrix(h, s, d_raw_q, nq, k, filter, d_ids, d_dist, st);
     const uint64_t n = h->size(), m = filter ? filter->popcount : n;     // (the tail rows: more candidates)
     const uint32_t D = h->L.D;
     const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT;
@@ -1570,6 +1590,132 @@ void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq,
     s.run_cap = 0;
     s.nq = nq;
     finish_batch(h, s, st);
+}
+
+// bn_max of the index state the handle holds (rows of the graph and of the tail), on the device; `st` is ordered behind the
+// kernel that made it.
+const uint32_t* matrix_bn_max(cph_index* h, hipStream_t st) {
+    if (h->bn_epoch != h->index_epoch || h->bn_rows != h->size() || !h->d_bn_max.p) {
+        if (!h->d_bn_max.p) h->d_bn_max.alloc(1);
+        if (!h->bn_ev) HIP_CHECK(hipEventCreateWithFlags(&h->bn_ev, hipEventDisableTiming));
+        hipLaunchKernelGGL(exact_mfma_bnmax_kernel, dim3(1), dim3(1024), 0, st, (const float*)h->d_norm.p, (uint64_t)h->size(), h->d_bn_max.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(h->bn_ev, st));
+        h->bn_epoch = h->index_epoch;
+        h->bn_rows = h->size();
+    } else {
+        HIP_CHECK(hipStreamWaitEvent(st, h->bn_ev, 0));
+    }
+    return h->d_bn_max.p;
+}
+
+// enqueue_exact under the matrix engine (device_exact_mfma.h): per launch of tile_q queries the prefilter and the certify
+// kernel; behind all of them the vector engine's plan over the whole batch, in the wrapper kernels that serve flagged
+// queries only.  Nothing here waits for the device.
+void enqueue_exact_matrix(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
+                          int64_t* d_ids, float* d_dist, hipStream_t st) {
+    const uint64_t n = h->size(), m = filter ? filter->popcount : n;
+    const uint32_t D = h->L.D;
+    // the certify kernel runs the candidate loop with ONE live query: its tile reads the kExactQT - 1 rows behind it
+    const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT + kExactQT;
+    const ExactPlan pl = plan_exact(m, nq, k, h->num_cus, h->exact_scratch_bytes);                 // the fallback's
+    const MatrixPlan mp = plan_exact_matrix(m, nq, k, h->num_cus, h->exact_scratch_bytes);
+    const size_t pool_keys = std::max(pl.pool_keys, mp.pool_keys);
+    const size_t counts = std::max((size_t)pl.P * pl.tile_q, (size_t)mp.P * mp.tile_q);
+    // EVERY buffer has its own term: the sizes do not move together (tile_q x C can shrink while tile_q grows, and the
+    // other enqueue paths size the shared buffers by their own plans), and DevBuf::alloc gives no slack
+    if (s.x_qpad.n < (size_t)nq_pad * D || s.x_qnorm.n < nq_pad || s.x_pools.n < pool_keys || s.x_counts.n < counts ||
+        s.d_count.n < nq || s.d_status.n < nq || s.d_redo.n < nq || s.mx_eps.n < nq || s.mx_flags.n < nq ||
+        s.mx_rpools.n < (size_t)mp.tile_q * mp.C || s.mx_rcounts.n < mp.tile_q) {
+        if (s.used) HIP_CHECK(hipEventSynchronize(s.ev_done));   // growing: the old buffers must be idle
+        s.x_qpad.alloc((size_t)nq_pad * D);
+        s.x_qnorm.alloc(nq_pad);
+        s.x_pools.alloc(pool_keys);
+        s.x_counts.alloc(counts);
+        s.d_count.alloc(nq);
+        s.d_status.alloc(nq);
+        s.d_redo.alloc(nq);
+        s.mx_eps.alloc(nq);
+        s.mx_flags.alloc(nq);
+        s.mx_rpools.alloc((size_t)mp.tile_q * mp.C);
+        s.mx_rcounts.alloc(mp.tile_q);
+    }
+    const uint32_t* d_list = filter ? filter_id_list(filter, st) : nullptr;
+    const uint32_t* d_bn = matrix_bn_max(h, st);
+    s.d_stats.alloc(kStatWords);
+    HIP_CHECK(hipMemsetAsync(s.d_stats.p, 0, kStatWords * 8, st));
+    HIP_CHECK(hipMemsetAsync(s.d_status.p, 0, (size_t)nq * 4, st));
+    HIP_CHECK(hipEventRecord(s.ev0, st));
+    pad_queries(h, d_raw_q, nullptr, nq, nq_pad, s.x_qpad.p, s.x_qnorm.p, s.d_stats.p, (unsigned long long)nq * m, st);
+    hipLaunchKernelGGL(exact_mfma_query_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, (const float*)s.x_qnorm.p, d_bn, D, nq,
+                       s.mx_eps.p, s.mx_flags.p);
+    HIP_CHECK(hipGetLastError());
+    const uint32_t* rows = h->ids_input ? h->d_rows.p : nullptr;
+    MatrixArgs a{};
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.qpad = s.x_qpad.p;
+    a.qnorm = s.x_qnorm.p;
+    a.eps = s.mx_eps.p;
+    a.ids = d_list;
+    a.m = (uint32_t)m;
+    a.D = D;
+    a.part = mp.part;
+    a.nq = nq;
+    a.k = k;
+    a.C = mp.C;
+    a.pools = s.x_pools.p;
+    a.counts = s.x_counts.p;
+    a.flags = s.mx_flags.p;
+    MatrixCertifyArgs c{};
+    c.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, kExactQT, 0);
+    c.eps = s.mx_eps.p;
+    c.P = mp.P;
+    c.k = k;
+    c.C = mp.C;
+    c.pools = s.x_pools.p;
+    c.counts = s.x_counts.p;
+    c.rpools = s.mx_rpools.p;
+    c.rcounts = s.mx_rcounts.p;
+    c.flags = s.mx_flags.p;
+    c.stats = s.d_stats.p;
+    c.rows = rows;
+    c.out_ids = d_ids;
+    c.out_dist = d_dist;
+    for (uint32_t q0 = 0; q0 < nq; q0 += mp.tile_q) {
+        const uint32_t q_count = std::min(mp.tile_q, nq - q0);
+        a.q_first = c.s.q_first = q0;
+        a.q_count = c.s.q_count = q_count;
+        const dim3 grid(mp.P, (q_count + kMxTile - 1) / kMxTile);
+        if (d_list) hipLaunchKernelGGL(exact_mfma_prefilter_kernel<true>, grid, dim3(256), (size_t)mp.C * 8 * 4, st, a);
+        else hipLaunchKernelGGL(exact_mfma_prefilter_kernel<false>, grid, dim3(256), (size_t)mp.C * 8 * 4, st, a);
+        HIP_CHECK(hipGetLastError());
+        CPH_LAUNCH_SCAN(exact_mfma_certify_kernel, D, dim3(q_count), (size_t)mp.C * 12 + 2 * kExactQT * 4, st, c);
+    }
+    // the fallback: today's scan and merge plan, for the flagged queries
+    ExactFlaggedArgs f{};
+    f.a.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, pl.gq, pl.part);
+    f.a.ids = d_list;
+    f.a.m = (uint32_t)m;
+    f.a.k = k;
+    f.a.C = pl.C;
+    f.a.pools = s.x_pools.p;
+    f.a.counts = s.x_counts.p;
+    f.flags = s.mx_flags.p;
+    for (uint32_t q0 = 0; q0 < nq; q0 += pl.tile_q) {
+        const uint32_t q_count = std::min(pl.tile_q, nq - q0);
+        f.a.s.q_first = q0;
+        f.a.s.q_count = q_count;
+        CPH_LAUNCH_SCAN(exact_scan_flagged_kernel, D, dim3(pl.P, (q_count + pl.gq - 1) / pl.gq), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, f);
+        hipLaunchKernelGGL(exact_merge_flagged_kernel, dim3(q_count), dim3(64), (size_t)pl.C * 8, st, (const unsigned long long*)s.x_pools.p,
+                           (const uint32_t*)s.x_counts.p, pl.P, q0, q_count, k, pl.C, rows, (const uint32_t*)s.mx_flags.p, s.d_stats.p,
+                           d_ids, d_dist);
+        HIP_CHECK(hipGetLastError());
+    }
+    s.run_slots = 0;
+    s.run_cap = 0;
+    s.nq = nq;
+    finish_batch(h, s, st, mp.P);
 }
 
 // Which path a batch takes.  Exact: asked for (cph_search_batch_exact*), or a filtered batch whose filter allows at most
@@ -1952,7 +2098,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 118; }
+int cph_version(void) { return 119; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -2011,6 +2157,7 @@ static void destroy_index(cph_index* h) {
         if (s.pin_stats) (void)hipHostFree(s.pin_stats);
         if (s.pin_io) (void)hipHostFree(s.pin_io);
     }
+    if (h->bn_ev) (void)hipEventDestroy(h->bn_ev);
 #ifdef CPH_SEARCH_TRACE
     if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
                          (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
@@ -2821,6 +2968,41 @@ int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed) {
         if (!h) throw InvalidArg("null handle");
         std::lock_guard<std::mutex> lk(h->mu);
         h->exact_threshold = max_allowed;
+    });
+}
+
+int cph_set_exact_engine(cph_index* h, int engine) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        if (engine != 0 && engine != 1) throw InvalidArg("exact engine must be 0 (vector) or 1 (matrix)");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->exact_engine = engine;
+    });
+}
+
+int cph_last_matrix_stats(cph_index* h, uint64_t out[3]) {
+    return guarded([&] {
+        if (!h || !out) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        out[0] = out[1] = out[2] = 0;
+        if (h->last_range || h->last_search < 0 || h->sets[h->last_search].mx_parts == 0) return;
+        BatchSet& s = h->sets[h->last_search];
+        h->use_device();
+        HIP_CHECK(hipEventSynchronize(s.ev_done));
+        if (s.stats_in_hbm) {
+            HIP_CHECK(hipMemcpy(s.pin_stats, s.d_stats.p, kStatWords * 8, hipMemcpyDeviceToHost));
+            s.stats_in_hbm = false;
+        }
+        out[0] = s.mx_parts;
+        out[1] = s.pin_stats[kStatMatrixSurvivors];
+        out[2] = s.pin_stats[kStatMatrixRedo];
+    });
+}
+
+int cph_host_exact_matrix_slack(float qnorm, float bn_max, uint32_t D, float* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = exact_matrix_slack(qnorm, bn_max, D);
     });
 }
 
@@ -4940,6 +5122,14 @@ int cph_multi_search_batch_filters(cph_multi* m, const float* queries, uint64_t 
     return guarded([&] { multi_search_batch(m, batch_call(queries, n, k, filters, n_filters, filter_of, exact != 0, ids, dist)); });
 }
 
+int cph_multi_set_exact_engine(cph_multi* m, int engine) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->reps) check_rc(cph_set_exact_engine(h, engine));
+    });
+}
+
 int cph_multi_set_exact_threshold(cph_multi* m, uint64_t max_allowed) {
     return guarded([&] {
         if (!m) throw InvalidArg("null handle");
@@ -5538,6 +5728,14 @@ int cph_parts_load_native(cph_parts* m, const char* path) {
             }
             throw;
         }
+    });
+}
+
+int cph_parts_set_exact_engine(cph_parts* m, int engine) {
+    return guarded([&] {
+        if (!m) throw InvalidArg("null handle");
+        std::shared_lock<std::shared_mutex> lk(m->life);
+        for (cph_index* h : m->parts) check_rc(cph_set_exact_engine(h, engine));
     });
 }
 

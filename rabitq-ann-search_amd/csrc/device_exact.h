@@ -7,7 +7,7 @@
 // chains over q*q; exact_from_dot on top.  The graph search spreads the eight chains over eight lanes and reduces them
 // with lane exchanges; here ONE lane owns a candidate and all eight chains of every (candidate, query) pair it works on,
 // so the reduction is three in-lane additions and the inner loop has no cross-lane traffic at all.  MFMA is out: its
-// accumulation order is another one.
+// accumulation order is another one.  (Out as the producer of a distance: device_exact_mfma.h prunes with it.)
 //
 // Work split.  The candidates (the filter's ascending id list, or 0..n-1) are cut into P contiguous PARTS, the queries of
 // one launch into G GROUPS of `gq`; workgroup (p, g) is one wave.  It takes 64 candidates of its part at a time -- a lane

@@ -70,6 +70,9 @@ enum StatWord : int {
 #else
     kStatFlushed = 10,
 #endif
+    // a matrix-engine exact batch (device_exact_mfma.h; no search kernel runs in it, so the diagnostic words are free there)
+    kStatMatrixSurvivors = 14,  // ids re-scored, summed over the queries
+    kStatMatrixRedo = 15,       // queries the fallback answered
     kStatQueues = 16,           // from here on u32 words, indexed by StatQueueWord
     kStatWords = 20,
 };

@@ -1216,6 +1216,9 @@ void launch_search(cph_index* h, BatchSet& s, uint32_t nq, uint32_t k, int64_t* 
         a.beam_tail = s.r_beam_tail.p;
         a.log_ids = s.r_logids.p;
     }
+    // the expansion loop compares the beam's and the id log's lengths with the capacity in 32 bits (ids are 32-bit with
+    // kInvalidNode reserved, so n + 1 fits; this is the place that holds every launch to it)
+    if (a.cap > 0xFFFFFFFFull) throw InvalidArg("search capacity does not fit 32 bits");
     uint32_t* queue = reinterpret_cast<uint32_t*>(s.d_stats.p + kStatQueues) + (sub ? sub->queue : 0);   // StatQueueWord
     uint32_t* const d_redo = sub ? sub->redo : s.d_redo.p;
     uint32_t grid = 0;

@@ -253,6 +253,16 @@ __device__ __forceinline__ int opaque_lane(int lane) {
 __device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ bool any64(bool p) { return ballot64(p) != 0ull; }
 __device__ __forceinline__ bool all64(bool p) { return ballot64(!p) == 0ull; }
+// Votes on a conjunction, as mask algebra.  ballot64 reads the lane mask where it is only when its argument is ONE
+// compare; handed `a && b` the compiler joins the two masks on the scalar unit, turns the result into 0 / 1 in a VGPR
+// and compares again (v_cndmask 0, 1 / v_cmp_ne, and a hazard s_nop where a select follows).  So every argument here
+// must be a bare compare (or its negation), never an && / || of compares and never a bool that crossed a branch, and
+// wave-uniform factors do not belong in them at all: they select or mask the 64-bit result at the call site.
+// v_cmp writes zero for lanes outside exec, so the & of ballots taken under one exec is the ballot of the conjunction;
+// these are only called where all their arguments are evaluated under the same exec.
+__device__ __forceinline__ unsigned long long ballot_and(bool a, bool b) { return ballot64(a) & ballot64(b); }
+// the lanes below n (n <= 64) as a scalar mask, in place of a vote on `lane < n`
+__device__ __forceinline__ unsigned long long lanes_below(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }
 
 // The LDS part is addressed through address-space-3 pointers so that every access is a ds_*
 // instruction (a generic pointer would make them flat_* accesses, which also wait on vmcnt).
@@ -364,7 +374,9 @@ __device__ __forceinline__ uint4 beam_pack(const BeamEntry& e) {
 // wave-uniform bit masks with no memory access, and the moves along the path are one parallel
 // LDS read plus one parallel write.  Two LDS round trips instead of one dependent round trip
 // per heap level.
-template <class H>
+// MV: the votes as mask algebra (ballot_and, lanes_below).  The instantiations whose register allocation does not survive
+// that form pass false and keep the votes on the joined bools (search_kernel: kMaskVotes).
+template <class H, bool MV = true>
 __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lane_in) {
 #ifdef CPH_LAUNDER_HOT      // (A/B switch: the routines of the usual path recompute their lane arithmetic as well -- fewer VGPRs, more instructions)
     const int lane = opaque_lane(lane_in);
@@ -377,13 +389,21 @@ __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lan
     // true: the left child moves up.  (Read by every lane -- entries up to index 128 / 256 exist in LDS whatever the heap
     // holds -- and masked afterwards: a predicated read costs an exec-mask save / restore, and the scalar unit is what
     // this kernel runs out of.)
-    const bool b0 = H::before(h.lds_key(2 * lane + 2), h.lds_key(2 * lane + 1)) && (uint32_t)lane < nint;
-    bool b1 = false;
-    const unsigned long long m0 = ballot64(b0);
-    unsigned long long m1 = 0;
+    unsigned long long m0, m1 = 0;
+    if constexpr (MV) m0 = ballot_and(H::before(h.lds_key(2 * lane + 2), h.lds_key(2 * lane + 1)), (uint32_t)lane < nint);
+    else m0 = ballot64(H::before(h.lds_key(2 * lane + 2), h.lds_key(2 * lane + 1)) && (uint32_t)lane < nint);
     if (nint > 64) {
-        if ((uint32_t)lane + 64 < nint) b1 = H::before(h.lds_key(2 * lane + 130), h.lds_key(2 * lane + 129));
-        m1 = ballot64(b1);
+        // (the keys cross the divergent read as floats -- equal keys compare false under either comparator -- so the
+        // vote itself is one compare, taken behind the join under the full exec)
+        if constexpr (MV) {
+            float kr = 0.0f, kl = 0.0f;
+            if ((uint32_t)lane + 64 < nint) { kr = h.lds_key(2 * lane + 130); kl = h.lds_key(2 * lane + 129); }
+            m1 = ballot64(H::before(kr, kl));
+        } else {
+            bool b1 = false;
+            if ((uint32_t)lane + 64 < nint) b1 = H::before(h.lds_key(2 * lane + 130), h.lds_key(2 * lane + 129));
+            m1 = ballot64(b1);
+        }
     }
     // Walk on hp = hole + 1: taking the left child doubles it, the right child doubles it and adds 1,
     // so after d steps hp is the binary string "1 r0 r1 .. r(d-1)" of the choices and every node on
@@ -459,7 +479,7 @@ __device__ __forceinline__ void heap_pop_wave(const H& h, uint32_t size, int lan
 // t - 1 reads ancestor p_t, all comparisons are made at once, the number of leading "parent moves down" answers m is
 // a ballot and a count, and the moves are one parallel write: ancestors 1..m each drop one step along the path, the
 // value lands on p_m.  One LDS read round trip and one write instead of one dependent round trip per heap level.
-template <class H>
+template <class H, bool MV = true>
 __device__ __forceinline__ void heap_push_wave(const H& h, uint32_t hole, typename H::E v, int lane_in) {
 #ifdef CPH_LAUNDER_HOT
     const int lane = opaque_lane(lane_in);
@@ -472,8 +492,10 @@ __device__ __forceinline__ void heap_push_wave(const H& h, uint32_t hole, typena
     const bool on = t <= depth;
     const uint32_t pt = on ? (hp >> t) - 1 : 0u;
     const typename H::E e = h.lds(pt);                                 // (lanes past the root read it again and are masked)
-    const bool down = on && H::before(H::key_of(e), H::key_of(v));
-    const unsigned long long stop = ~ballot64(down);                   // first ancestor that stays (bits >= depth are set)
+    // (`on` is lane < depth: a scalar mask on the vote, not a factor of the per-lane bool)
+    unsigned long long stop;                                           // first ancestor that stays (bits >= depth are set)
+    if constexpr (MV) stop = ~(ballot64(H::before(H::key_of(e), H::key_of(v))) & lanes_below(depth));
+    else stop = ~ballot64(on && H::before(H::key_of(e), H::key_of(v)));
     const uint32_t m = (uint32_t)__builtin_ctzll(stop);                 // ancestors p_1..p_m move down
     if (t <= m) h.lds_put((hp >> (t - 1)) - 1, e);                      // p_t's entry to p_(t-1), p_0 = the leaf
     if ((uint32_t)lane == m) h.lds_put((hp >> m) - 1, v);              // (m <= depth <= 8 < 64: that lane exists)
@@ -647,7 +669,7 @@ __device__ __forceinline__ void beam_push_hybrid(const Beam& h, uint32_t hole, u
 // heap's current root key.  Same element movement as nn_push (which stays as the path for heaps too large for
 // the two ballot masks of the wave-parallel pop).
 // FULL: the caller knows that the heap is full (the steady expansion loop): the fill arm and its test are not compiled.
-template <bool FULL = false>
+template <bool FULL = false, bool MV = true>
 __device__ __forceinline__ void nn_push_wave(const NnLds& w, Result* h, uint32_t& size, uint32_t k, uint32_t id, float dist,
                                              float top, int lane_in) {
 #ifndef CPH_NO_LAUNDER_NN
@@ -664,7 +686,7 @@ __device__ __forceinline__ void nn_push_wave(const NnLds& w, Result* h, uint32_t
     if constexpr (FULL) asm volatile("" : "+s"(sz));
     if (!FULL && sz < k) {
         if (sz < kWaveHeapMax) {
-            heap_push_wave(w, sz, r, lane);
+            heap_push_wave<NnLds, MV>(w, sz, r, lane);
         } else {
             if (lane == 0) nn_sift_up(h, sz, 0, Result{id, dist});
             __builtin_amdgcn_wave_barrier();
@@ -672,8 +694,8 @@ __device__ __forceinline__ void nn_push_wave(const NnLds& w, Result* h, uint32_t
         ++size;
     } else if (dist < top) {
         if (sz <= kWaveHeapMax) {
-            if (sz > 1) heap_pop_wave(w, sz, lane);            // std::pop_heap: the old last value sinks in from the root
-            heap_push_wave(w, sz - 1, r, lane);                // back() = r; std::push_heap
+            if (sz > 1) heap_pop_wave<NnLds, MV>(w, sz, lane); // std::pop_heap: the old last value sinks in from the root
+            heap_push_wave<NnLds, MV>(w, sz - 1, r, lane);     // back() = r; std::push_heap
         } else {
             if (lane == 0) {
                 nn_adjust(h, 0, sz - 1, h[sz - 1]);
@@ -881,9 +903,15 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         // and goes on counting once the log is full).  Every value the loop carries is copied on its latch and on the
         // exits that leave it unchanged; these two were among them (profiles/steady_tail.md).
         constexpr bool kRareOffLoop = kTwoLoops;
+        // Votes as mask algebra, the capacity tests in 32 bits and the rare stage-2 counters in LDS: the two-loop
+        // instantiations.  Every other one keeps the votes on joined bools, the 64-bit compares and the two flags: six of
+        // them spill one or two VGPRs more with the new forms and <2,128,true> takes 79 registers, one more than
+        // tests/test_steady_loop_resources.py holds it to (profiles/vote_masks.md, section 3).
+        constexpr bool kMaskVotes = kTwoLoops;
         uint32_t st_exp = 0, st_exact = 0, st_new = 0, st_push = 0, st_skip = 0, st_allseen = 0;
         // probe first only: expansions where the reference's stage-2 decision is unobservable and was left open (the reference
-        // may have skipped stage 2 there or not -- st_skip counts the skips that were decided)
+        // may have skipped stage 2 there or not -- st_skip counts the skips that were decided).  kMaskVotes: both are
+        // counted in s_tot by the arm that takes them, and these two stay zero.
         uint32_t st_undecided = 0;
 #ifdef CPH_TRAFFIC_STATS
         // diagnostic build only: what the spilled beam and the estimated-set probe touch (stats[8..15])
@@ -971,7 +999,7 @@ __global__ __launch_bounds__(64, search_waves_per_simd(SD, BW)) void search_kern
         }
 
         // (an attempt that ends between the test and the addition has overflowed: it wipes in any case)
-        if constexpr (kRareOffLoop) wipe = log_count > a.cap;
+        if constexpr (kRareOffLoop) wipe = log_count > (uint32_t)a.cap;
         // ---- results (:276; src/bindings.cpp:202-210) ----------------------------------
         if (lane == 0 && !overflow) nn_sort(nn, nn_size);
         const uint32_t nn_final = bcast_u32(nn_size);

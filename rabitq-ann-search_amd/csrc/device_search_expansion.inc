@@ -21,7 +21,7 @@
                 if (size > 8191) trf[7]++;
 #endif
                 if (size > 1) {
-                    if (size <= kBeamLds) heap_pop_wave(heap, size, lane);
+                    if (size <= kBeamLds) heap_pop_wave<Beam, kMaskVotes>(heap, size, lane);
                     else beam_pop_hybrid(heap, size, lane);
                 }
             };
@@ -183,16 +183,32 @@
             float worst0 = worst_pop;
             // (filtered: a vertex outside the allowed set never enters the result heap -- cur_id is uniform, so is this)
             const bool cur_allowed = !FILT || ((allow_cur >> (cur_id & 31u)) & 1u) != 0u;
-            const bool nn_changes = any64(cur_allowed && ((!ST && nn_size < k) || exact_dist < worst_pop));   // every lane agrees: provably uniform
+            // every lane agrees: provably uniform.  (kMaskVotes -- never with a filter --: the vote is the one compare, the
+            // uniform factor stays scalar)
+            bool nn_changes;
+            if constexpr (kMaskVotes) nn_changes = (!ST && nn_size < k) || any64(exact_dist < worst_pop);
+            else nn_changes = any64(cur_allowed && ((!ST && nn_size < k) || exact_dist < worst_pop));
             if (nn_changes) {
-                nn_push_wave<ST>(nnw, nn, nn_size, k, cur_id, exact_dist, worst_pop, lane);
+                nn_push_wave<ST, kMaskVotes>(nnw, nn, nn_size, k, cur_id, exact_dist, worst_pop, lane);
                 __builtin_amdgcn_wave_barrier();
                 worst0 = bcast_f32(nnw.lds_key(0));   // (the heap holds at least the entry just pushed)
             }
             const uint32_t nn_sz = nn_size;
             CPH_TICK(1);
             CPH_TICKF(3);
-            if (!any64(active)) {  // n_neighbors == 0 (:137)
+            // The valid lanes as a mask.  (From a compare of its own on a laundered copy of the id: a vote in this block on
+            // the bool that `valid`'s compare left in a scalar pair blocks ago goes through 0 / 1 in a VGPR again.)
+            unsigned long long valid_lanes = 0;      // (kMaskVotes only)
+            bool none_valid;
+            if constexpr (kMaskVotes) {
+                uint32_t nid_here = nid;
+                asm("" : "+v"(nid_here));
+                valid_lanes = ballot64(nid_here != kInvalidNode);
+                none_valid = (uint32_t)valid_lanes == 0u;
+            } else {
+                none_valid = !any64(active);
+            }
+            if (none_valid) {  // n_neighbors == 0 (:137); the mask's low half: lanes < 32
                 // (retire the probe's destination register on this path too: a load left pending
                 // across the back edge costs every expansion a wait where that register is reused)
                 asm volatile("" ::"v"(old_bits));
@@ -209,15 +225,17 @@
             }
             // ---- FastScan estimates (:159-206) ----------------------------------------
             float est = 0.0f, lower = 0.0f;
-            bool skipped2 = false, undecided2 = false;
+            bool skipped2 = false, undecided2 = false;     // (undecided2: without kMaskVotes only)
             // a list shorter than 32 whose length is not a multiple of 8 ends in the reference's scalar tail
             // (device_fastscan.h: TailLanes); wave-uniform, never taken on graphs the builders write.  The probe-first
             // instantiation sits on its register limit and is only launched on indexes without such lists (the loader
             // knows: SearchArgs::flags bit 1 sends the others to the instantiation without it).
             const TailLanes tl = kProbeFirst ? no_tail() : tail_lanes(valid, lane);
-            // `fetched`: the lanes whose codes and aux values bl holds -- all of them, or (probe first) the new ones.
+            // `fetched`: the valid lanes whose codes and aux values bl holds, as a scalar mask -- all the valid ones, or
+            // (probe first) the new ones, both lane halves.  It masks the votes below and is no factor of a per-lane bool.
             // Returns false when the reference's stage-2 decision cannot be taken from the fetched lanes (probe first only).
-            auto estimate = [&](bool fetched) -> bool {
+            // Without kMaskVotes: `fetched_b`, the same lanes as a per-lane bool, and votes on the joined bools.
+            auto estimate = [&](unsigned long long fetched, bool fetched_b) -> bool {
                 LaneEst v;
                 const float dqp = exact_dist;
                 bl.reduce(blk, a.L, qm, lane, v);
@@ -232,7 +250,8 @@
                     // Both ranges end in the same three arms; `est_of` makes the estimate behind the vote.
                     auto arms = [&](float lo1, float lo2, auto&& est_of) -> bool {
                         // any_survivor (:178-187) ranges over ALL the list's neighbours, estimated before or not
-                        if (__builtin_expect((!ST && nn_sz < k) || any64(fetched && valid && lo1 < worst0), 1)) {
+                        if (__builtin_expect((!ST && nn_sz < k) || (kMaskVotes ? (ballot64(lo1 < worst0) & fetched) != 0ull
+                                                                                   : any64(fetched_b && valid && lo1 < worst0)), 1)) {
                             est = est_of(v);
                             lower = lo2;
                         } else if constexpr (!kProbeFirst) {            // the reference's skipped batch (:201-205)
@@ -260,9 +279,19 @@
                             asm volatile("" : "+v"(w.nbit));
                             est = est_of(w);
                             lower = lo2;
-                            const bool acts = fetched && !(lo2 >= worst0) && (est < worst0 || est < gamma_q * worst0);
-                            if (any64(acts)) return false;
-                            undecided2 = true;
+                            if constexpr (kMaskVotes) {
+                                const unsigned long long acts = fetched & ballot64(!(lo2 >= worst0)) &
+                                                                (ballot64(est < worst0) | ballot64(est < gamma_q * worst0));
+                                if (acts != 0ull) return false;
+                                // Counted where it happens, in the wave's LDS totals: as a flag it crossed the join, a
+                                // select and an add on every expansion for an arm the builders' graphs never take.
+                                // (Every lane reads the word and writes the same sum: one instruction each, no lane branch.)
+                                s_tot[kStatStage2Undecided] = s_tot[kStatStage2Undecided] + 1ull;
+                            } else {
+                                const bool acts = fetched_b && !(lo2 >= worst0) && (est < worst0 || est < gamma_q * worst0);
+                                if (any64(acts)) return false;
+                                undecided2 = true;
+                            }
                         }
                         return true;
                     };
@@ -297,7 +326,7 @@
             // not by bandwidth: there the estimator runs BEFORE the probe's result is looked at, under its round trip.
             // The 4-bit kernel keeps the order that skips the arithmetic of all-seen expansions.
             constexpr bool kSpeculate = BW <= 2 && !kProbeFirst;
-            if constexpr (kSpeculate) estimate(true);
+            if constexpr (kSpeculate) estimate(valid_lanes, true);
             CPH_TICKF(4);
 #if CPH_PHASE_TIMERS + 0 == 2
             asm volatile("" : "+v"(old_bits));
@@ -305,9 +334,13 @@
 #endif
 
             // ---- estimated set: result of the probe issued above --------------------------------
-            bool is_new = active && (old_bits & my_bit) == 0;
+            // (the per-lane bool and the mask are written from the same compares; lanes < 32 are the mask's low half)
+            const bool unseen = (old_bits & my_bit) == 0;
+            bool is_new = active && unseen;
+            uint32_t new_mask = 0;
+            if constexpr (kMaskVotes) new_mask = (uint32_t)(valid_lanes & ballot64(unseen));
             // a vertex whose neighbour list repeats an id: only the first copy is new
-            if (!ST && (a.flags & 1u) && any64(is_new)) {    // (steady: the flag was clear where the query changed loops)
+            if (!ST && (a.flags & 1u) && (kMaskVotes ? new_mask != 0u : any64(is_new))) {    // (steady: the flag was clear where the query changed loops)
                 // (graphs written by the reference never repeat an id; the loader sets the
                 // flag when one does, and only then is this screen paid for)
 #pragma unroll 1   // cold path: rolled, or its 31 lane masks are hoisted and spilled for everyone
@@ -316,8 +349,9 @@
                     bool nj = __shfl((int)is_new, j) != 0;
                     if (nj && lane > j && lane < 32 && oj == nid) is_new = false;
                 }
+                if constexpr (kMaskVotes) new_mask = (uint32_t)ballot64(is_new);       // (cold: the screened bool, under the full exec)
             }
-            const uint32_t new_mask = (uint32_t)(ballot64(is_new) & 0xFFFFFFFFull);
+            if constexpr (!kMaskVotes) new_mask = (uint32_t)(ballot64(is_new) & 0xFFFFFFFFull);
             // mark the new ids (two may share a word) and log them for the un-marking at query end (discovery order =
             // neighbour order) under ONE predicate; a log that would overflow ends the attempt before anything is marked
             const uint32_t n_new = __popc(new_mask);
@@ -326,14 +360,18 @@
             // slot is answered by the full-capacity re-run.  The id log only exists to clear the bitmap cheaply: once it
             // is full the query simply stops logging and wipes its whole bitmap at the end (n / 8 bytes -- less than the
             // log it would have needed: a query that discovers more than `cap` ids has touched a good part of the graph).
-            if (beam_size + n_new > a.cap) { overflow = true; break; }
+            // (32 bits: launch_search refuses a capacity of 2^32 or more, and neither sum wraps -- ids are marked once, so the
+            // log's length, which goes on counting after the log is full, and the beam's size stay at or below n < 2^32 - 1)
+            // (without kMaskVotes: the 64-bit compares, as ever)
+            const std::conditional_t<kMaskVotes, uint32_t, uint64_t> cap = a.cap;
+            if (beam_size + n_new > cap) { overflow = true; break; }
             // (two loops: no `wipe` flag is carried from expansion to expansion.  The log's length only grows, and it goes on
             // counting after the log is full, so "full" is a comparison of the length -- here and at query end.)
             bool nolog;
             if constexpr (kRareOffLoop) {
-                nolog = log_count + n_new > a.cap;
+                nolog = log_count + n_new > cap;
             } else {
-                if (!wipe && log_count + n_new > a.cap) wipe = true;
+                if (!wipe && log_count + n_new > cap) wipe = true;
                 nolog = wipe;
             }
             if (is_new) {
@@ -356,10 +394,10 @@
                 // est / lower from garbage (there are no floating-point traps on this path, and no address is formed
                 // from these values), and none of it is observable: every reader is masked by a set of lanes that
                 // `fetch` contains -- fetch = new_mask's bit of (lane & 31), is_new = that bit in the lower lane half:
-                //   estimate(): any64(fetched && valid && lo1 < worst0)              -> fetched (= fetch)
-                //   estimate(): acts = fetched && ...                                -> fetched
-                //   cand = is_new && ...  (cand_mask, s_list, the speculative exact L2) -> is_new
-                //   lane-parallel pushes: p = is_new && ...  (pm, the parent check under chk = p && .., the append) -> p
+                //   estimate(): ballot64(lo1 < worst0) & fetched                     -> fetched (= fetch's lanes)
+                //   estimate(): acts = fetched & ...                                 -> fetched
+                //   cand_mask = new_mask & ...  (s_list, the speculative exact L2)   -> new_mask
+                //   lane-parallel pushes: pm = new_mask & ..., p = is_new && ...  (the parent check under pm, the append) -> p
                 //   serial replay: m = new_mask [& ballot(!(lower >= worst0))], v_readlane of est / lower at the set
                 //   bits of m only                                                   -> new_mask
                 //   replay of the lane-parallel pushes: v_readlane at the set bits of pm -> p
@@ -367,17 +405,27 @@
                 // its own lane-parallel arm builds the entry in every lane and reads it, like the general one, under p)
                 bl.leave_undefined();
                 if (fetch) bl.issue_static(blk, lane);
-                if (__builtin_expect(!estimate(fetch), 0)) { overflow = true; stage2_redo = true; break; }
+                // (new implies valid, and both lane halves hold the same id: fetch && valid is new_mask's bit of lane & 31)
+                if (__builtin_expect(!estimate((unsigned long long)new_mask << 32 | new_mask, fetch), 0)) { overflow = true; stage2_redo = true; break; }
             } else if constexpr (!kSpeculate) {
-                estimate(true);
+                estimate(valid_lanes, true);
             }
             if (skipped2) st_skip++;
-            if (undecided2) st_undecided++;
+            if constexpr (!kMaskVotes) { if (undecided2) st_undecided++; }
 
             CPH_TICK(2);
             const bool warmup = !ST && nn_sz < k;  // (:210; read at the head: an expansion whose replay fills the heap ends as a warm-up one)
-            bool cand = is_new && (warmup || (!(lower >= worst0) && est < worst0));
-            const uint32_t cand_mask = (uint32_t)(ballot64(cand) & 0xFFFFFFFFull);
+            // cand = is_new && (warmup || (!(lower >= worst0) && est < worst0)): new_mask carries is_new, `warmup` is
+            // wave-uniform and selects the mask, the two compares are one vote each (`below` also serves the pushes)
+            uint32_t below = 0, cand_mask;
+            bool cand = false;
+            if constexpr (kMaskVotes) {
+                below = (uint32_t)ballot64(!(lower >= worst0));
+                cand_mask = warmup ? new_mask : new_mask & below & (uint32_t)ballot64(est < worst0);
+            } else {
+                cand = is_new && (warmup || (!(lower >= worst0) && est < worst0));
+                cand_mask = (uint32_t)(ballot64(cand) & 0xFFFFFFFFull);
+            }
 
             if constexpr (!kDerivedCounters) st_new += n_new;
             CPH_TICK(3);
@@ -392,6 +440,8 @@
                 uint32_t allow_w = 0;
                 if constexpr (FTAB) allow_w = allow_q[is_new ? nid >> 5 : 0u];
                 else if constexpr (FILT) allow_w = CPH_COLD(allow)[is_new ? nid >> 5 : 0u];
+                // (kMaskVotes: the bool from the mask, in this rare arm only)
+                if constexpr (kMaskVotes) cand = lane < 32 && ((cand_mask >> (lane & 31)) & 1u) != 0u;
                 if (cand) s_list[__builtin_amdgcn_mbcnt_lo(cand_mask, 0u)] = (uint8_t)lane;
                 __syncthreads();
                 const uint32_t n_cand = __popc(cand_mask);
@@ -426,7 +476,12 @@
                 // only the beam pushes themselves keep neighbour order.
                 const float dabs0 = gamma_q * worst0;
                 const bool p = is_new && !(lower >= worst0) && est < dabs0;
-                uint32_t pm = (uint32_t)(ballot64(p) & 0xFFFFFFFFull);
+                uint32_t pm;                                                          // p's lanes (kMaskVotes: from the same compares)
+                if constexpr (kMaskVotes) pm = new_mask & below & (uint32_t)ballot64(est < dabs0);
+                else pm = (uint32_t)(ballot64(p) & 0xFFFFFFFFull);
+                // The parent checks below ask whether any lane has a push (pm), a parent (pos > 0) and a parent that
+                // beats it.  pos == 0 only for the first push onto an empty beam, so the first two are a scalar mask.
+                const uint32_t chk_mask = beam_size != 0u ? pm : pm & (pm - 1u);
                 // std::push_heap of each in neighbour order.  Usual case: every new entry is no
                 // better than the parent of the leaf it lands on, so nothing moves and the pushes
                 // are independent appends -- each lane checks its own parent and writes its own leaf.
@@ -449,8 +504,8 @@
                             const uint32_t pos = beam_size + __builtin_amdgcn_mbcnt_lo(pm, 0u);
                             // every lane reads a parent (lanes without a push: the root) and is masked afterwards
                             const bool chk = p && pos > 0;
-                            const bool stay = !(heap.lds_key(chk ? (pos - 1) >> 1 : 0u) > est) || !chk;
-                            if (all64(stay)) {
+                            const float parent = heap.lds_key(chk ? (pos - 1) >> 1 : 0u);
+                            if (((uint32_t)ballot64(parent > est) & chk_mask) == 0u) {
                                 CPH_CENSUS(0);
                                 if (p) heap.lds_put(pos, ent);
                                 beam_size += np;
@@ -467,9 +522,11 @@
                         } else if (np != 1) {
 #endif
                             const uint32_t pos = beam_size + __builtin_amdgcn_mbcnt_lo(pm, 0u);
-                            bool stay = true;
-                            if (p && pos > 0) stay = !(heap.raw_key((pos - 1) >> 1) > est);
-                            if (all64(stay)) {
+                            // (the key crosses the divergent read as a float, -inf beats nothing; the vote is taken
+                            // behind the join, under the full exec)
+                            float parent = -__builtin_inff();
+                            if (p && pos > 0) parent = heap.raw_key((pos - 1) >> 1);
+                            if (ballot64(parent > est) == 0ull) {
                                 CPH_CENSUS(1);
 #ifdef CPH_TRAFFIC_STATS
                                 trf[3]++;
@@ -502,15 +559,29 @@
 #endif
                     const uint32_t pos = beam_size + __builtin_amdgcn_mbcnt_lo(pm, 0u);
                     const bool in_lds = beam_size + np <= kBeamLds;   // wave-uniform: the usual case keeps its ds_* accesses
-                    bool stay = true;
-                    if (in_lds) {
-                        // every lane reads a parent (lanes without a push: the root) and is masked afterwards
-                        const bool chk = p && pos > 0;
-                        stay = !(heap.lds_key(chk ? (pos - 1) >> 1 : 0u) > est) || !chk;
-                    } else if (p && pos > 0) {
-                        stay = !(heap.raw_key((pos - 1) >> 1) > est);
+                    bool all_stay;
+                    if constexpr (kMaskVotes) {
+                        float parent = -__builtin_inff();      // (beats nothing)
+                        if (in_lds) {
+                            // every lane reads a parent (lanes without a push: the root) and is masked afterwards
+                            const bool chk = p && pos > 0;
+                            parent = heap.lds_key(chk ? (pos - 1) >> 1 : 0u);
+                        } else if (p && pos > 0) {
+                            parent = heap.raw_key((pos - 1) >> 1);
+                        }
+                        // (one vote behind the join, under the full exec; chk_mask is exact for both arms)
+                        all_stay = ((uint32_t)ballot64(parent > est) & chk_mask) == 0u;
+                    } else {
+                        bool stay = true;
+                        if (in_lds) {
+                            const bool chk = p && pos > 0;
+                            stay = !(heap.lds_key(chk ? (pos - 1) >> 1 : 0u) > est) || !chk;
+                        } else if (p && pos > 0) {
+                            stay = !(heap.raw_key((pos - 1) >> 1) > est);
+                        }
+                        all_stay = all64(stay);
                     }
-                    if (all64(stay)) {
+                    if (all_stay) {
 #ifdef CPH_TRAFFIC_STATS
                         if (!in_lds) trf[3]++;
 #endif
@@ -531,7 +602,7 @@
 #ifdef CPH_TRAFFIC_STATS
                         if (beam_size >= kBeamLds) trf[2]++;
 #endif
-                        if (beam_size < kBeamLds) heap_push_wave(heap, beam_size, make_uint4(e_i, lo_i, id_i, 0u), lane);
+                        if (beam_size < kBeamLds) heap_push_wave<Beam, kMaskVotes>(heap, beam_size, make_uint4(e_i, lo_i, id_i, 0u), lane);
                         else beam_push_hybrid(heap, beam_size, make_uint4(e_i, lo_i, id_i, 0u), lane);
                         ++beam_size;
                         ++st_push;
@@ -541,8 +612,9 @@
                 CPH_CENSUS(6);
                 // past the warm-up the threshold only falls: a lower bound that fails it at loop
                 // entry fails it at its turn too (:241), so those neighbours are dropped here
-                uint32_t m = warmup ? new_mask
-                                    : new_mask & (uint32_t)(ballot64(!(lower >= worst0)) & 0xFFFFFFFFull);
+                uint32_t m;
+                if constexpr (kMaskVotes) m = warmup ? new_mask : new_mask & below;
+                else m = warmup ? new_mask : new_mask & (uint32_t)(ballot64(!(lower >= worst0)) & 0xFFFFFFFFull);
                 // Every quantity of the reference's loop body is wave-uniform here (neighbour i's values come out
                 // of lane i with v_readlane, the heaps live in LDS), so the whole wave walks the loop together and
                 // the heap operations are the wave-parallel ones: a rerank costs two LDS round trips per heap
@@ -564,7 +636,7 @@
                     bool push = (act & 2u) != 0;
                     if (act & 1u) {
                         const float ex = bcast_f32(s_exact[i]);
-                        if (!FILT || ((allow_mask >> i) & 1u) != 0u) nn_push_wave<ST>(nnw, nn, nn_size, k, id_i, ex, worst, lane);
+                        if (!FILT || ((allow_mask >> i) & 1u) != 0u) nn_push_wave<ST, kMaskVotes>(nnw, nn, nn_size, k, id_i, ex, worst, lane);
                         if (ex < dabs) { push = true; key = ex; if (warmup) lo = ex; }
                         if ((act & 4u) && ex > kEpsSmall) {
                             // gamma adaptation (:255-267), fused as the reference compiles it; fp64 on one lane
@@ -593,7 +665,7 @@
 #ifdef CPH_TRAFFIC_STATS
                         if (beam_size >= kBeamLds) trf[2]++;
 #endif
-                        if (beam_size < kBeamLds) heap_push_wave(heap, beam_size, ent, lane);
+                        if (beam_size < kBeamLds) heap_push_wave<Beam, kMaskVotes>(heap, beam_size, ent, lane);
                         else beam_push_hybrid(heap, beam_size, ent, lane);
                         ++beam_size;
                         ++st_push;

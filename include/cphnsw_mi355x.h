@@ -235,10 +235,17 @@ int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
  * cph_last_matrix_stats: out[0] = parts of the candidate list, out[1] = ids re-scored (summed over the queries), out[2] =
  * queries the VALU scan answered, of the last batch if engine 1 ran it; zeros otherwise.
  * cph_host_exact_matrix_slack: the slack, a bound on |approximate - exact distance| for a query of squared norm qnorm
- * against rows of squared norm <= bn_max at padded dimension D (the statement the device uses). */
+ * against rows of squared norm <= bn_max at padded dimension D (the statement the device uses).
+ * cph_host_exact_matrix_plan: how engine 1 cuts a batch (host only; the argument checks of cph_host_exact_plan): out[0] = Kp,
+ * the power of two >= max(k, 64), out[1] = C = 2 Kp keys per pool, out[2] = queries per launch, out[3] = P parts of the
+ * candidate list, out[4] = candidates per part (a multiple of 128), out[5] = pool keys = P x queries per launch x C.
+ * cph_debug_matrix_bn_max: the bn_max engine 1 holds for the handle's index state (rows and added rows), after waiting for
+ * the handle's work; read-only, launches nothing.  CPH_INVALID_ARGUMENT while no engine-1 batch has run on that state. */
 int cph_set_exact_engine(cph_index* h, int engine);
 int cph_last_matrix_stats(cph_index* h, uint64_t out[3]);
 int cph_host_exact_matrix_slack(float qnorm, float bn_max, uint32_t D, float* out);
+int cph_host_exact_matrix_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t out[6]);
+int cph_debug_matrix_bn_max(cph_index* h, float* out);
 
 /* ---- range search ----------------------------------------------------------------------- */
 /* Every allowed id closer than a radius, in CSR form: lims[n + 1] (lims[0] = 0), query i owns ids / dist

@@ -1550,8 +1550,8 @@ void enqueue_exact_matrix(cph_index* h, BatchSet& s, const float* d_raw_q, uint3
 
 void enqueue_exact(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t nq, uint32_t k, const cph_filter* filter,
                    int64_t* d_ids, float* d_dist, hipStream_t st) {
-    if (h->exact_engine == 1) return enqueue_exact_matrix(h, s, d_raw_q, nq, k, filter, d_ids, d_dist, st);
     const uint64_t n = h->size(), m = filter ? filter->popcount : n;     // (the tail rows: more candidates)
+    if (h->exact_engine == 1 && m <= kMxMaxCandidates) return enqueue_exact_matrix(h, s, d_raw_q, nq, k, filter, d_ids, d_dist, st);
     const uint32_t D = h->L.D;
     const uint32_t nq_pad = (nq + kExactQT - 1) / kExactQT * kExactQT;
     const ExactPlan pl = plan_exact(m, nq, k, h->num_cus, h->exact_scratch_bytes);
@@ -3006,6 +3006,29 @@ int cph_host_exact_matrix_slack(float qnorm, float bn_max, uint32_t D, float* ou
     return guarded([&] {
         if (!out) throw InvalidArg("null argument");
         *out = exact_matrix_slack(qnorm, bn_max, D);
+    });
+}
+
+int cph_host_exact_matrix_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t out[6]) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        if (k == 0 || k > kExactMaxK || candidates == 0 || candidates > 0xFFFFFFFFull || n_queries == 0 || n_queries > 0xFFFFFFFFull)
+            throw InvalidArg("exact plan: sizes out of range");
+        const MatrixPlan mp = plan_exact_matrix(candidates, (uint32_t)n_queries, (uint32_t)k, num_cus, (size_t)scratch_bytes);
+        out[0] = mp.Kp; out[1] = mp.C; out[2] = mp.tile_q; out[3] = mp.P; out[4] = mp.part; out[5] = (uint64_t)mp.pool_keys;
+    });
+}
+
+int cph_debug_matrix_bn_max(cph_index* h, float* out) {
+    return guarded([&] {
+        if (!h || !out) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->finalized || !h->d_bn_max.p || !h->bn_ev || h->bn_epoch != h->index_epoch || h->bn_rows != h->size())
+            throw InvalidArg("no matrix batch has run on the index state this handle holds");
+        h->use_device();
+        quiesce(h);
+        HIP_CHECK(hipEventSynchronize(h->bn_ev));
+        HIP_CHECK(hipMemcpy(out, h->d_bn_max.p, 4, hipMemcpyDeviceToHost));
     });
 }
 

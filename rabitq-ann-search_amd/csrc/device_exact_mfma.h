@@ -65,6 +65,9 @@ constexpr uint32_t kMxTile = 128;          // query rows per workgroup, candidat
 constexpr uint32_t kMxKC = 32;             // floats of K per LDS stage
 constexpr uint32_t kMxLd = kMxKC + 4;
 constexpr uint32_t kMxInfBits = 0x7F800000u;
+// The prefilter counts candidates in 32 bits, a whole tile past the last one included: a longer list (which no index of
+// fewer than 2^32 - 1 rows of 64 bytes or more can hold in HBM today) is the vector engine's.
+constexpr uint64_t kMxMaxCandidates = 0xFFFFFFFFull - kMxTile + 1;
 
 // ---- per index state: bn_max; per batch: eps and the flags ----------------------------------------------------------------
 // *out = the largest norm_sq[0 .. n) as bits.  norm_sq >= +0, so unsigned order is numeric order and a NaN (or +inf) beats
@@ -138,7 +141,8 @@ struct MatrixArgs {
     const float* qnorm;           // [nq]
     const float* eps;             // [nq]
     const uint32_t* ids;          // [m] ascending internal ids (LIST), or null: candidate c is id c
-    uint32_t m, D, part;          // candidates; padded dimension; candidates per part (a multiple of 128)
+    uint32_t m, D;                // candidates; padded dimension
+    uint64_t part;                // candidates per part (a multiple of 128; 2^32 where one part holds 2^32 - 1 candidates)
     uint32_t nq, q_first, q_count;// the batch; the queries of this launch
     uint32_t k, C;
     unsigned long long* pools;    // [P][q_count][C]
@@ -151,7 +155,8 @@ template <bool LIST>
 __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs a) {
     __shared__ __align__(16) float Qs[2][kMxTile * kMxLd];       // double-buffered operand images
     __shared__ __align__(16) float Bs[2][kMxTile * kMxLd];
-    __shared__ float bn_s[2][256];                               // |b|^2 of the tile's columns, by tile parity (first 128 of each)
+    __shared__ float bn_s[2][256];                               // |b|^2 of the tile's columns, by tile parity (first 128 of each;
+                                                                 //   the second 128: where fetches past the end are staged)
     __shared__ uint32_t cnt[kMxTile];                            // per query row: keys in its pool,
     __shared__ float lim_s[kMxTile];                             //   its limit tau + 2 eps (-1: takes nothing),
     __shared__ float eps2_s[kMxTile];                            //   2 eps
@@ -160,7 +165,8 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int h = lane >> 5, c = lane & 31;
-    const uint32_t c_lo = blockIdx.x * a.part, c_hi = min(a.m, c_lo + a.part);
+    const uint64_t p_lo = (uint64_t)blockIdx.x * a.part;          // (64 bits: the last part's end may pass 2^32)
+    const uint32_t c_lo = (uint32_t)min(p_lo, (uint64_t)a.m), c_hi = (uint32_t)min(p_lo + a.part, (uint64_t)a.m);
     const uint32_t ql0 = blockIdx.y * kMxTile;                   // first query of the tile, relative to q_first
     if (c_lo >= c_hi || ql0 >= a.q_count) return;
     unsigned long long* sm = reinterpret_cast<unsigned long long*>(mx_smem) + (size_t)wave * a.C;
@@ -190,7 +196,8 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
     for (int i = 0; i < 4; ++i) qsrc[i] = a.qpad + (size_t)min(a.q_first + ql0 + srow + 32 * i, q_last) * D + skl;
     // candidate (tile, r) of this part -> internal id
     auto cand_id = [&](uint32_t tile, uint32_t r) -> uint32_t {
-        const uint32_t cc = min(c_lo + tile * kMxTile + r, c_hi - 1);
+        // (64 bits: the ids fetched ahead for the tile after the last one may pass 2^32 before the clamp)
+        const uint32_t cc = (uint32_t)min((uint64_t)c_lo + tile * kMxTile + r, (uint64_t)c_hi - 1);
         if constexpr (LIST) return a.ids[cc];
         else return cc;
     };
@@ -198,6 +205,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
     float pbn = 0.0f;                   // |b|^2 of column (tid & 127) of the tile being fetched
     uint32_t f_tile = 0, f_ch = 0;      // the chunk the next fetch() brings in (past the end: the last tile again, unused)
     uint32_t f_tile_staged = 0;
+    bool f_past = false, f_past_staged = false;   // the fetch runs past the part's last chunk: its norms go to the spare half of bn_s
     uint32_t rid[4], nid[4], bid, nbid; // ids of the rows this thread stages, and of its norm column: the tile being fetched, the one after
 #pragma unroll
     for (int i = 0; i < 4; ++i) { rid[i] = cand_id(0, srow + 32 * i); nid[i] = cand_id(1, srow + 32 * i); }
@@ -206,6 +214,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
     auto fetch = [&]() {
         const uint32_t k0 = f_ch * kMxKC;
         f_tile_staged = f_tile;
+        f_past_staged = f_past;
         pbn = a.norm_sq[bid];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -214,6 +223,7 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
             pb[i] = *reinterpret_cast<const knn_f32x4*>(a.raw + (size_t)rid[i] * D + skl + k0);
         }
         const bool wrap = f_ch + 1 == nchunk;
+        f_past = f_past || (wrap && f_tile + 1 == ntile);
         f_ch = wrap ? 0 : f_ch + 1;
         f_tile = (wrap && f_tile + 1 < ntile) ? f_tile + 1 : f_tile;
         // (every chunk, no branch: a half is one basic block)  nid was loaded a fetch ago for the tile that is now f_tile
@@ -226,7 +236,11 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
         nbid = cand_id(f_tile + 1, tid & (kMxTile - 1));
     };
     auto stage = [&](int buf) {         // what fetch() brought in -> image `buf` (and its tile's column norms)
-        bn_s[f_tile_staged & 1][tid] = pbn;
+        // A fetch past the end repeats the last tile's number with the ids of a tile that does not exist.  With one chunk per
+        // tile (D <= 32) it is staged in the iteration that reads bn_s of the same parity, with no barrier in between: a wave
+        // still in the epilogue of the tile before would start the last tile from another row's norm.  Such a fetch writes the
+        // half of bn_s nobody reads (no branch: a half is one basic block).
+        bn_s[f_tile_staged & 1][f_past_staged ? (tid | 128) : tid] = pbn;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             *reinterpret_cast<knn_f32x4*>(&Qs[buf][(srow + 32 * i) * kMxLd + skq]) = pq[i];
@@ -522,7 +536,8 @@ __global__ __launch_bounds__(64) void exact_merge_flagged_kernel(const unsigned 
 struct MatrixPlan {
     uint32_t Kp, C;
     uint32_t tile_q;
-    uint32_t P, part;
+    uint32_t P;
+    uint64_t part;        // (2^32 where one part holds more than 2^32 - 128 candidates)
     size_t pool_keys;     // P * tile_q * C
 };
 
@@ -534,7 +549,7 @@ inline MatrixPlan plan_exact_matrix(uint64_t m, uint32_t nq, uint32_t k, int num
     const uint64_t wgs = (uint64_t)std::max(1, num_cus) * 2, blocks = (m + kMxTile - 1) / kMxTile;
     auto parts = [&](uint64_t want) {
         want = std::max<uint64_t>(1, std::min<uint64_t>({want, blocks, (uint64_t)kExactMaxParts}));
-        pl.part = (uint32_t)((blocks + want - 1) / want * kMxTile);
+        pl.part = (blocks + want - 1) / want * kMxTile;
         pl.P = (uint32_t)((m + pl.part - 1) / pl.part);
         pl.pool_keys = (size_t)pl.P * pl.tile_q * pl.C;
     };

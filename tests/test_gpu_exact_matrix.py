@@ -6,8 +6,9 @@ import zlib
 import numpy as np
 import pytest
 
-from golden_util import fixture_path
+from golden_util import DATASETS, fixture_path
 from test_gpu_exact import CASES, _all_distances, _allowed, _beq, _load, _model
+from exact_matrix_model import DEFAULT_BUDGET_MB, may_flag, plan, slack_of
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +33,7 @@ def test_every_dimension_ragged_tiles(cph, oracle, gold, name, bits):
     rng = np.random.default_rng(zlib.crc32(f"m{name}{bits}".encode()))
     one = np.zeros(n, bool)
     one[7] = True
+    eps = slack_of(Q, ix.get_vectors(), DATASETS[name]["D"])
     for fname, mask in (("none", None), ("p0.5", rng.random(n) < 0.5), ("p0.1", rng.random(n) < 0.1), ("single", one)):
         allowed = _allowed(mask, n)
         dist = _all_distances(oi, Q, allowed)
@@ -44,6 +46,12 @@ def test_every_dimension_ragged_tiles(cph, oracle, gold, name, bits):
             assert np.array_equal(ids, want_ids) and _beq(d, want_d), (name, fname, k)
             if name == "g128" and mask is None:
                 assert st["matrix_parts"] > 1
+            if DATASETS[name]["kind"] == "gauss":
+                # certified by the prefilter, not answered by the fallback behind it -- on inputs of which the reference
+                # distances say that no pool can overflow (tests/exact_matrix_model.py)
+                pl = plan(len(allowed), len(Q), k, DEFAULT_BUDGET_MB)
+                assert not may_flag(dist, k, eps, pl).any(), ("bad input", name, fname, k)
+                assert st["matrix_redo"] == 0 and st["matrix_parts"] == pl["P"], (name, fname, k, st, pl)
 
 
 @pytest.mark.parametrize("k", (1, 32))

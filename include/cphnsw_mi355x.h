@@ -1422,6 +1422,18 @@ int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k
  *     The object is resident on the handle's device and follows the rules of cph_group_keys: it serves the handle and
  *     the index it was made for (a load, build or compact invalidates it: "made for another index"; after cph_add it is
  *     refused with the size message), another device refuses it, cph_save_native does not carry it.
+ *     dtype CPH_RESCORE_INT8 stores a row as signed bytes with one float32 scale and one float32 norm per row (half the
+ *     bytes of float16; device bytes: size x (row bytes + 8)) and scores it with exact integer dot products
+ *     (csrc/device_rescore_i8.h, which states it; DESIGN.md section 4, "int8 rows").  From float rows: m = max |x_i|,
+ *     scale = m / 127, code_i = clamp(rint(x_i / scale), -127, 127) (all zeros where m == 0), norm = (scale * scale) *
+ *     sum code_i^2.  The query is quantised once per call to two int8 planes (t_i in [-16256, 16256] against its own
+ *     max), the dot of a pair is one 64-bit integer times scale * query scale, and L2 / IP follow from it as above.
+ *     A row that holds a NaN or an Inf or whose norm overflows refuses the call in the same way.
+ * cph_rescore_vectors_create_i8  the same object from rows the caller holds as int8 already: rows [size][dim_full] int8
+ *     are stored as given (-128 included), scales [size] float32 are the rows' scales (NULL: 1.0 each).  A row whose
+ *     scale is not finite and >= 0, or whose norm overflows, refuses the call with the lowest such row.
+ * cph_rescore_vectors_scales  the scales of rows [first, first + count) of a CPH_RESCORE_INT8 object (another dtype is
+ *     refused); waits for the device.
  * cph_rescore_vectors_destroy waits for the device, then frees; NULL is a no-op.
  * cph_rescore_vectors_info    size, dim_full, dtype, metric, the stored bytes of a row and the device bytes of the object.
  * cph_rescore_vectors_get     the stored bytes of rows [first, first + count): rows_out [count][row bytes], norms_out
@@ -1450,11 +1462,14 @@ int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k
  *     statement of the conversion, the scatter and the norms (row_map [n_map]: rows arrive in input order and row
  *     row_map[i] goes to position i, rows at or above n_map stay where they are; NULL: internal order); *bad = the
  *     number of refused rows, *first_bad the lowest (UINT64_MAX: none).  Neither makes a HIP call. */
-enum { CPH_RESCORE_FLOAT16 = 0, CPH_RESCORE_FLOAT32 = 1 };
+enum { CPH_RESCORE_FLOAT16 = 0, CPH_RESCORE_FLOAT32 = 1, CPH_RESCORE_INT8 = 2 };
 enum { CPH_RESCORE_L2 = 0, CPH_RESCORE_IP = 1 };
 typedef struct cph_rescore_vectors cph_rescore_vectors;
 int cph_rescore_vectors_create(cph_index* h, const float* rows, uint64_t size, uint64_t dim_full, int space, int dtype, int metric,
                                cph_rescore_vectors** out);
+int cph_rescore_vectors_create_i8(cph_index* h, const int8_t* rows, const float* scales, uint64_t size, uint64_t dim_full, int space,
+                                  int metric, cph_rescore_vectors** out);
+int cph_rescore_vectors_scales(const cph_rescore_vectors* rv, uint64_t first, uint64_t count, float* out);
 int cph_rescore_vectors_destroy(cph_rescore_vectors* rv);
 int cph_rescore_vectors_info(const cph_rescore_vectors* rv, uint64_t* size, uint64_t* dim_full, int* dtype, int* metric, uint64_t* row_bytes,
                              uint64_t* nbytes);

@@ -231,24 +231,29 @@ class GroupKeys:
 
 class RescoreVectors:
     """Full-size rows for two-stage search on the index' device (CPIndex.make_rescore_vectors): one row of `dim`
-    coordinates per id of the index, stored as `dtype` ("float16" or "float32") with one float32 squared norm per row, and
-    the `metric` ("l2" or "ip") search_rescored scores them by.  It follows the rules of GroupKeys: it serves the index
+    coordinates per id of the index, stored as `dtype` ("float16", "float32" or "int8") with one float32 squared norm per
+    row (and, for "int8", one float32 scale per row: scales()), and the `metric` ("l2" or "ip") search_rescored scores
+    them by.  It follows the rules of GroupKeys: it serves the index
     it was made for and covers `size` ids -- after an add() it is refused with the size error; load(), build() and
     compact() invalidate it; save_native does not carry it.  A multi-device index' object holds one copy per replica.
     close() waits for the batches that may still read it."""
 
-    def __init__(self, index, rows, input_rows, dtype, metric):
+    def __init__(self, index, rows, input_rows, dtype, metric, scales=None):
         self._hs = []                # one cph_rescore_vectors per replica (a single-device index: one)
         self.size, self.dim = int(rows.shape[0]), int(rows.shape[1])
         self.dtype, self.metric = dtype, metric
         code = _lib.IDS_INPUT if input_rows else _lib.IDS_INTERNAL
-        dt = _lib.RESCORE_FLOAT32 if dtype == "float32" else _lib.RESCORE_FLOAT16
+        dt = {"float16": _lib.RESCORE_FLOAT16, "float32": _lib.RESCORE_FLOAT32, "int8": _lib.RESCORE_INT8}[dtype]
         mt = _lib.RESCORE_IP if metric == "ip" else _lib.RESCORE_L2
+        p_rows = rows.ctypes.data if rows.size else None
         try:
             for rh in index._replicas():
                 h = C.c_void_p()
-                _lib.check(_lib.lib().cph_rescore_vectors_create(rh, rows.ctypes.data if rows.size else None, self.size, self.dim, code,
-                                                                 dt, mt, C.byref(h)))
+                if rows.dtype == np.int8:        # codes the caller holds already: stored as given
+                    _lib.check(_lib.lib().cph_rescore_vectors_create_i8(rh, p_rows, None if scales is None else scales.ctypes.data,
+                                                                        self.size, self.dim, code, mt, C.byref(h)))
+                else:
+                    _lib.check(_lib.lib().cph_rescore_vectors_create(rh, p_rows, self.size, self.dim, code, dt, mt, C.byref(h)))
                 self._hs.append(h)
         except Exception:
             self.close()
@@ -270,7 +275,7 @@ class RescoreVectors:
 
     @property
     def nbytes(self):
-        """Device bytes of the rows and norms, summed over the replicas."""
+        """Device bytes of the rows, norms and (int8) scales, summed over the replicas."""
         return self._info()[5] * len(self._hs)
 
     def stored(self, first=0, count=None, replica=0):
@@ -282,6 +287,15 @@ class RescoreVectors:
         _lib.check(_lib.lib().cph_rescore_vectors_get(self._hs[replica], int(first), count, rows.ctypes.data if count else None,
                                                       norms.ctypes.data if count else None))
         return rows, norms
+
+    def scales(self, first=0, count=None, replica=0):
+        """float32 [count]: the scales of an "int8" object's rows in internal id order (stored code x scale = the value
+        a row stands for); another dtype is refused.  Waits for the device."""
+        size = self._info()[0]
+        count = size - first if count is None else int(count)
+        out = np.empty(count, np.float32)
+        _lib.check(_lib.lib().cph_rescore_vectors_scales(self._hs[replica], int(first), count, out.ctypes.data if count else None))
+        return out
 
     def close(self):
         hs = getattr(self, "_hs", [])
@@ -2062,26 +2076,43 @@ class CPIndex:
     RESCORE_MAX_CANDIDATES = 1024
     RESCORE_MAX_DIM = 8192
 
-    def make_rescore_vectors(self, rows, ids=None, dtype="float16", metric="l2"):
+    def make_rescore_vectors(self, rows, ids=None, dtype="float16", metric="l2", scales=None):
         """RescoreVectors from a float32 or float16 array [size, dim_full] (1 <= dim_full <= 8192), one row per id of the
         index, indexed in the space `ids` ("internal" or "input"; default: result_ids, as for make_group_keys; the input
         form needs the row map): the `vectors` argument of search_rescored.  `dtype`: how the rows are stored on the
-        device, "float16" (default; float32 input is rounded to nearest even) or "float32".  `metric`: "l2" or "ip"; it
-        belongs to the object, not to the index -- for cosine, normalise the rows and the full queries yourself and use
-        "ip".  ValueError names the lowest row that holds a NaN or an Inf, a value that overflows float16, or whose
-        squared norm overflows, and how many there are; no object exists then."""
+        device, "float16" (default; float32 input is rounded to nearest even), "float32" or "int8".  `metric`: "l2" or
+        "ip"; it belongs to the object, not to the index -- for cosine, normalise the rows and the full queries yourself
+        and use "ip".  ValueError names the lowest row that holds a NaN or an Inf, a value that overflows float16, or whose
+        squared norm overflows, and how many there are; no object exists then.
+
+        dtype="int8" stores a row as signed bytes with one scale per row -- half the device memory of "float16", and
+        half the bytes every candidate costs -- and scores it with exact integer dot products against the query
+        quantised to 15 bits: scale = max |x_i| / 127, code_i = round(x_i / scale).  With dtype="int8" `rows` may also be
+        an np.int8 array of codes you hold already (stored as given, -128 included) with `scales` float32 [size], one per
+        row (None: 1.0 each; a scale that is not finite and >= 0 is refused like a bad row); int8 rows with another dtype
+        and `scales` with float rows are refused."""
         self._no_parts("make_rescore_vectors")
         space = self._id_space(ids)
-        if dtype not in ("float16", "float32"):
-            raise ValueError('dtype must be "float16" or "float32"')
+        if dtype not in ("float16", "float32", "int8"):
+            raise ValueError('dtype must be "float16", "float32" or "int8"')
         if metric not in ("l2", "ip"):
             raise ValueError('metric must be "l2" or "ip" (cosine: normalise rows and full queries and use "ip")')
         a = np.asarray(rows)
-        if a.dtype not in (np.float32, np.float16):
-            raise ValueError("rows must be a float32 or float16 array")
+        codes = a.dtype == np.int8
+        if codes and dtype != "int8":
+            raise ValueError('int8 rows are stored as they are: pass dtype="int8"')
+        if not codes and a.dtype not in (np.float32, np.float16):
+            raise ValueError('rows must be a float32 or float16 array (or, with dtype="int8", an int8 array)')
         if a.ndim != 2 or a.shape[0] != self.size or not 1 <= a.shape[1] <= self.RESCORE_MAX_DIM:
             raise ValueError(f"rows must be a ({self.size}, dim_full) array (the index size), 1 <= dim_full <= {self.RESCORE_MAX_DIM}")
-        return RescoreVectors(self, _as_f32(a), space == "input", dtype, metric)       # (float16 -> float32 is exact)
+        if scales is not None:
+            if not codes:
+                raise ValueError("scales belong to int8 rows (float rows get their scales from their own maxima)")
+            scales = np.ascontiguousarray(scales, np.float32)
+            if scales.shape != (self.size,):
+                raise ValueError(f"scales must be a ({self.size},) array, one per row")
+        a = np.ascontiguousarray(a) if codes else _as_f32(a)                               # (float16 -> float32 is exact)
+        return RescoreVectors(self, a, space == "input", dtype, metric, scales)
 
     def _rescored_args(self, n, k, vectors, candidates, filter, filter_of):
         """Validation shared by both rescored entry points -> (k, C, the filters as of _filters_arg)."""

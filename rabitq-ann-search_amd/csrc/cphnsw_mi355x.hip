@@ -47,6 +47,7 @@
 #include "device_maxsim_rescore.h"
 #include "device_fused.h"
 #include "device_rescore.h"
+#include "device_rescore_i8.h"
 #include "device_normalize.h"
 #include "device_ip.h"
 #include "host_index.h"
@@ -7850,9 +7851,12 @@ struct cph_rescore_vectors {
     uint64_t size = 0;                         // ids it covers
     uint32_t dim = 0;                          // dim_full
     bool f32 = false, ip = false;
+    bool i8 = false;                           // CPH_RESCORE_INT8: rows of signed bytes, one scale per row
     RescoreLayout L{};
     DevBuf<uint8_t> rows;                      // [size][L.stride], internal-id order
     DevBuf<float> norms;                       // [size]
+    DevBuf<float> scales;                      // [size] (int8 only)
+    int dtype() const { return i8 ? CPH_RESCORE_INT8 : f32 ? CPH_RESCORE_FLOAT32 : CPH_RESCORE_FLOAT16; }
 };
 
 namespace {
@@ -7861,17 +7865,21 @@ RescoreStore rescore_store(const cph_rescore_vectors* rv) {
     return RescoreStore{rv->rows.p, rv->norms.p, (uint32_t)rv->size, rv->dim, rv->L.stride, rv->L.pieces, rv->L.padded, rv->L.G, rv->L.log2G};
 }
 
-void check_rescore_layout_args(uint64_t dim_full, int dtype, int metric) {
+// with_i8: the entry takes CPH_RESCORE_INT8 too (the host twins state the float dtypes only).
+void check_rescore_layout_args(uint64_t dim_full, int dtype, int metric, bool with_i8 = false) {
     if (dim_full < 1 || dim_full > kRescoreMaxDim)
         throw InvalidArg("rescore vectors support 1 <= dim_full <= " + std::to_string(kRescoreMaxDim) + ", got " + std::to_string(dim_full));
-    if (dtype != CPH_RESCORE_FLOAT16 && dtype != CPH_RESCORE_FLOAT32)
-        throw InvalidArg("rescore vectors are stored as CPH_RESCORE_FLOAT16 = 0 or CPH_RESCORE_FLOAT32 = 1");
+    if (dtype != CPH_RESCORE_FLOAT16 && dtype != CPH_RESCORE_FLOAT32 && !(with_i8 && dtype == CPH_RESCORE_INT8))
+        throw InvalidArg(with_i8 ? "rescore vectors are stored as CPH_RESCORE_FLOAT16 = 0, CPH_RESCORE_FLOAT32 = 1 or CPH_RESCORE_INT8 = 2"
+                                 : "rescore vectors are stored as CPH_RESCORE_FLOAT16 = 0 or CPH_RESCORE_FLOAT32 = 1");
     if (metric != CPH_RESCORE_L2 && metric != CPH_RESCORE_IP) throw InvalidArg("the metric of rescore vectors is CPH_RESCORE_L2 = 0 or CPH_RESCORE_IP = 1");
 }
 
-void refuse_bad_rescore_rows(uint64_t bad, unsigned long long first) {
+void refuse_bad_rescore_rows(uint64_t bad, unsigned long long first, bool i8 = false) {
     if (!bad) return;
-    throw InvalidArg("rescore vectors: row " + std::to_string(first) + " holds a NaN or an Inf, a value that overflows float16, or its squared "
+    throw InvalidArg("rescore vectors: row " + std::to_string(first) +
+                     (i8 ? " holds a NaN or an Inf, its scale is not finite and >= 0, or its squared "
+                         : " holds a NaN or an Inf, a value that overflows float16, or its squared ") +
                      "norm overflows (" + std::to_string(bad) + " such row" + (bad == 1 ? "" : "s") + " in this call): no object was made");
 }
 
@@ -7909,6 +7917,14 @@ RescoreArgs rescore_args(const RescoreStore& s, bool ip, const int64_t* r_ids, c
     return a;
 }
 
+// The one place that launches the rescoring pass: the kernel of the object's dtype.
+void rescore_pass(const cph_rescore_vectors* rv, const int64_t* r_ids, const float* r_dist, const float* d_fq, uint64_t C, uint64_t k,
+                  const uint32_t* d_rows, const RerankOuts& o, uint32_t n, hipStream_t st) {
+    const RescoreArgs a = rescore_args(rescore_store(rv), rv->ip, r_ids, r_dist, d_fq, C, k, d_rows, o);
+    if (rv->i8) rescore_i8_rows(RescoreI8Args{a, rv->scales.p}, n, st);
+    else rescore_rows(a, rv->f32, n, st);
+}
+
 // vectors[r]: the object of replica r (one handle: r = 0).  full_q: [n][dim_full], on the host (host form: staged into
 // the scratch set before the search is enqueued, so that the timed pass is the kernel alone) or on the device.
 struct RescoredSearch {
@@ -7938,10 +7954,8 @@ struct RescoredSearch {
     }
     RerankOuts outs(int64_t* ids, float* score, float* first) const { return {{{ids, 8 * k}, {score, 4 * k}, {first, 4 * k}}, 3}; }
     void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
-        const cph_rescore_vectors* rv = vectors[0];
-        rescore_rows(rescore_args(rescore_store(rv), rv->ip, gs.rows.ids.p, gs.rows.dist.p, host_form ? gs.host.fq.p : full_q, C, k,
-                                  h->ids_input ? h->d_rows.p : nullptr, o),
-                     rv->f32, (uint32_t)n, st);
+        rescore_pass(vectors[0], gs.rows.ids.p, gs.rows.dist.p, host_form ? gs.host.fq.p : full_q, C, k, h->ids_input ? h->d_rows.p : nullptr, o,
+                     (uint32_t)n, st);
     }
 };
 
@@ -7951,66 +7965,96 @@ void check_rescore_rows_args(const int64_t* ids, const float* dist, uint64_t n, 
     if (n < 1 || n > 0x7FFFFFFFull) throw InvalidArg("rescore rows: sizes out of range");
 }
 
+// The body of both create entries.  rows: float32 [size][dim_full], or (in_i8) int8 [size][dim_full] with scales [size] or null.
+void rescore_vectors_create(cph_index* h, const void* rows, bool in_i8, const float* scales, uint64_t size, uint64_t dim_full, int space,
+                            int dtype, int metric, cph_rescore_vectors** out) {
+    if (!out) throw InvalidArg("null argument");
+    *out = nullptr;
+    if (!h || (!rows && size != 0)) throw InvalidArg("null argument");
+    if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
+    check_rescore_layout_args(dim_full, dtype, metric, true);
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->finalized) throw InvalidArg("rescore vectors belong to a finalized index: finalize or load it first");
+    if (size != h->size())
+        throw InvalidArg("rescore vectors have " + std::to_string(size) + " rows, the index holds " + std::to_string(h->size()));
+    if (size > 0xFFFFFFFEull) throw InvalidArg("rescore vectors: too many rows");
+    h->use_device();
+    DevBuf<uint32_t> d_inv;
+    if (space == CPH_IDS_INPUT) {
+        const uint64_t nb = h->host.n;
+        if (!h->has_rows) throw InvalidArg("the index has no row map (it was loaded from a v2 file): rows in input order need cph_set_row_map");
+        std::vector<uint32_t> map(h->host.rows);
+        if (map.size() != nb) {                       // a replica without host arrays: its device copy
+            map.resize(nb);
+            if (nb) HIP_CHECK(hipMemcpy(map.data(), h->d_rows.p, nb * 4, hipMemcpyDeviceToHost));
+        }
+        const std::vector<uint32_t> inv = rescore_inverse_rows(map.data(), nb, size);
+        d_inv.alloc(std::max<uint64_t>(size, 1));
+        if (size) HIP_CHECK(hipMemcpy(d_inv.p, inv.data(), size * 4, hipMemcpyHostToDevice));
+    }
+    std::unique_ptr<cph_rescore_vectors> rv(new cph_rescore_vectors());
+    rv->h = h;
+    rv->epoch = h->index_epoch;
+    rv->device = h->device;
+    rv->size = size;
+    rv->dim = (uint32_t)dim_full;
+    rv->f32 = dtype == CPH_RESCORE_FLOAT32;
+    rv->i8 = dtype == CPH_RESCORE_INT8;
+    rv->ip = metric == CPH_RESCORE_IP;
+    rv->L = rv->i8 ? rescore_layout_i8(rv->dim) : rescore_layout(rv->dim, rv->f32);
+    rv->rows.alloc(std::max<uint64_t>(size, 1) * rv->L.stride);
+    rv->norms.alloc(std::max<uint64_t>(size, 1));
+    if (rv->i8) rv->scales.alloc(std::max<uint64_t>(size, 1));
+    const uint64_t elem = in_i8 ? 1 : 4;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(size, ((uint64_t)256 << 20) / (dim_full * elem)));
+    DevBuf<uint8_t> d_x(chunk * dim_full * elem);
+    DevBuf<float> d_sc(in_i8 && scales ? chunk : 1);
+    DevBuf<unsigned long long> d_cnt(2);
+    const unsigned long long init[2] = {0ull, kRescoreNoRow};
+    unsigned long long cnt[2] = {0ull, kRescoreNoRow};
+    hipStream_t st = own_stream(h);
+    HIP_CHECK(hipMemcpyAsync(d_cnt.p, init, sizeof(init), hipMemcpyHostToDevice, st));
+    const RescoreStore s = rescore_store(rv.get());
+    for (uint64_t base = 0; base < size; base += chunk) {
+        const uint64_t c = std::min(chunk, size - base);
+        const uint32_t* inv = space == CPH_IDS_INPUT ? d_inv.p : nullptr;
+        HIP_CHECK(hipMemcpyAsync(d_x.p, static_cast<const uint8_t*>(rows) + base * dim_full * elem, c * dim_full * elem, hipMemcpyHostToDevice, st));
+        if (in_i8 && scales) HIP_CHECK(hipMemcpyAsync(d_sc.p, scales + base, c * 4, hipMemcpyHostToDevice, st));
+        if (rv->i8)
+            rescore_i8_rows_in(d_x.p, in_i8, scales ? d_sc.p : nullptr, c, base, inv, s, rv->rows.p, rv->scales.p, rv->norms.p, d_cnt.p, st);
+        else
+            rescore_rows_in(reinterpret_cast<const float*>(d_x.p), c, base, inv, s, rv->f32, rv->rows.p, rv->norms.p, d_cnt.p, st);
+        HIP_CHECK(hipStreamSynchronize(st));          // (the next chunk's upload overwrites d_x from pageable memory)
+    }
+    HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    refuse_bad_rescore_rows(cnt[0], cnt[1], rv->i8);
+    *out = rv.release();
+}
+
 }  // namespace
 
 extern "C" {
 
 int cph_rescore_vectors_create(cph_index* h, const float* rows, uint64_t size, uint64_t dim_full, int space, int dtype, int metric,
                                cph_rescore_vectors** out) {
+    return guarded([&] { rescore_vectors_create(h, rows, false, nullptr, size, dim_full, space, dtype, metric, out); });
+}
+
+int cph_rescore_vectors_create_i8(cph_index* h, const int8_t* rows, const float* scales, uint64_t size, uint64_t dim_full, int space,
+                                  int metric, cph_rescore_vectors** out) {
+    return guarded([&] { rescore_vectors_create(h, rows, true, scales, size, dim_full, space, CPH_RESCORE_INT8, metric, out); });
+}
+
+int cph_rescore_vectors_scales(const cph_rescore_vectors* rv, uint64_t first, uint64_t count, float* out) {
     return guarded([&] {
-        if (!out) throw InvalidArg("null argument");
-        *out = nullptr;
-        if (!h || (!rows && size != 0)) throw InvalidArg("null argument");
-        if (space != CPH_IDS_INTERNAL && space != CPH_IDS_INPUT) throw InvalidArg("id space must be CPH_IDS_INTERNAL or CPH_IDS_INPUT");
-        check_rescore_layout_args(dim_full, dtype, metric);
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->finalized) throw InvalidArg("rescore vectors belong to a finalized index: finalize or load it first");
-        if (size != h->size())
-            throw InvalidArg("rescore vectors have " + std::to_string(size) + " rows, the index holds " + std::to_string(h->size()));
-        if (size > 0xFFFFFFFEull) throw InvalidArg("rescore vectors: too many rows");
-        h->use_device();
-        DevBuf<uint32_t> d_inv;
-        if (space == CPH_IDS_INPUT) {
-            const uint64_t nb = h->host.n;
-            if (!h->has_rows) throw InvalidArg("the index has no row map (it was loaded from a v2 file): rows in input order need cph_set_row_map");
-            std::vector<uint32_t> map(h->host.rows);
-            if (map.size() != nb) {                       // a replica without host arrays: its device copy
-                map.resize(nb);
-                if (nb) HIP_CHECK(hipMemcpy(map.data(), h->d_rows.p, nb * 4, hipMemcpyDeviceToHost));
-            }
-            const std::vector<uint32_t> inv = rescore_inverse_rows(map.data(), nb, size);
-            d_inv.alloc(std::max<uint64_t>(size, 1));
-            if (size) HIP_CHECK(hipMemcpy(d_inv.p, inv.data(), size * 4, hipMemcpyHostToDevice));
-        }
-        std::unique_ptr<cph_rescore_vectors> rv(new cph_rescore_vectors());
-        rv->h = h;
-        rv->epoch = h->index_epoch;
-        rv->device = h->device;
-        rv->size = size;
-        rv->dim = (uint32_t)dim_full;
-        rv->f32 = dtype == CPH_RESCORE_FLOAT32;
-        rv->ip = metric == CPH_RESCORE_IP;
-        rv->L = rescore_layout(rv->dim, rv->f32);
-        rv->rows.alloc(std::max<uint64_t>(size, 1) * rv->L.stride);
-        rv->norms.alloc(std::max<uint64_t>(size, 1));
-        const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(size, ((uint64_t)256 << 20) / (dim_full * 4)));
-        DevBuf<float> d_x(chunk * dim_full);
-        DevBuf<unsigned long long> d_cnt(2);
-        const unsigned long long init[2] = {0ull, kRescoreNoRow};
-        unsigned long long cnt[2] = {0ull, kRescoreNoRow};
-        hipStream_t st = own_stream(h);
-        HIP_CHECK(hipMemcpyAsync(d_cnt.p, init, sizeof(init), hipMemcpyHostToDevice, st));
-        const RescoreStore s = rescore_store(rv.get());
-        for (uint64_t base = 0; base < size; base += chunk) {
-            const uint64_t c = std::min(chunk, size - base);
-            HIP_CHECK(hipMemcpyAsync(d_x.p, rows + base * dim_full, c * dim_full * 4, hipMemcpyHostToDevice, st));
-            rescore_rows_in(d_x.p, c, base, space == CPH_IDS_INPUT ? d_inv.p : nullptr, s, rv->f32, rv->rows.p, rv->norms.p, d_cnt.p, st);
-            HIP_CHECK(hipStreamSynchronize(st));          // (the next chunk's upload overwrites d_x from pageable memory)
-        }
-        HIP_CHECK(hipMemcpyAsync(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        refuse_bad_rescore_rows(cnt[0], cnt[1]);
-        *out = rv.release();
+        if (!rv || (count != 0 && !out)) throw InvalidArg("null argument");
+        if (!rv->i8) throw InvalidArg("rescore vectors: only CPH_RESCORE_INT8 objects have scales");
+        if (first > rv->size || count > rv->size - first) throw InvalidArg("rescore vectors: rows out of range");
+        if (count == 0) return;
+        HIP_CHECK(hipSetDevice(rv->device));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, rv->scales.p + first, count * 4, hipMemcpyDeviceToHost));
     });
 }
 
@@ -8028,10 +8072,10 @@ int cph_rescore_vectors_info(const cph_rescore_vectors* rv, uint64_t* size, uint
         if (!rv || !size || !dim_full || !dtype || !metric || !row_bytes || !nbytes) throw InvalidArg("null argument");
         *size = rv->size;
         *dim_full = rv->dim;
-        *dtype = rv->f32 ? CPH_RESCORE_FLOAT32 : CPH_RESCORE_FLOAT16;
+        *dtype = rv->dtype();
         *metric = rv->ip ? CPH_RESCORE_IP : CPH_RESCORE_L2;
         *row_bytes = rv->L.stride;
-        *nbytes = rv->size * ((uint64_t)rv->L.stride + 4);
+        *nbytes = rv->size * ((uint64_t)rv->L.stride + (rv->i8 ? 8 : 4));
     });
 }
 
@@ -8105,9 +8149,7 @@ int cph_rescore_rows_hook(cph_index* h, const int64_t* ids, const float* dist, u
         const DevBuf<float> d_dist = uploaded(dist, n * candidates);
         const DevBuf<float> d_fq = uploaded(full_queries, n * vectors->dim);
         PoisonedOuts po(o, n);
-        rescore_rows(rescore_args(rescore_store(vectors), vectors->ip, d_ids.p, d_dist.p, d_fq.p, candidates, k,
-                                  h->ids_input ? h->d_rows.p : nullptr, po.dev),
-                     vectors->f32, (uint32_t)n, nullptr);
+        rescore_pass(vectors, d_ids.p, d_dist.p, d_fq.p, candidates, k, h->ids_input ? h->d_rows.p : nullptr, po.dev, (uint32_t)n, nullptr);
         po.download();
     });
 }

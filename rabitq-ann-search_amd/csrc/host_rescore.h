@@ -41,7 +41,7 @@ constexpr uint32_t kRescoreMaxDim = 8192;           // dim_full <= this (the que
 constexpr unsigned long long kRescoreNoRow = ~0ull;
 
 struct RescoreLayout {
-    uint32_t elem_bytes;     // 2 or 4
+    uint32_t elem_bytes;     // 2 or 4 (rescore_layout), 1 (rescore_layout_i8)
     uint32_t E;              // coordinates per 16-byte piece
     uint32_t stride;         // stored bytes per row, a multiple of 16
     uint32_t pieces;         // stride / 16
@@ -56,6 +56,24 @@ inline RescoreLayout rescore_layout(uint32_t dim_full, bool f32) {
     L.pieces = (dim_full + L.E - 1) / L.E;
     L.stride = L.pieces * 16u;
     L.padded = L.pieces * L.E;
+    L.G = 1;
+    L.log2G = 0;
+    while (L.G < L.pieces && L.G < 64u) {
+        L.G *= 2;
+        ++L.log2G;
+    }
+    return L;
+}
+
+// The layout of an int8 row (CPH_RESCORE_INT8; device_rescore_i8.h): 16 signed bytes per piece, the same P, stride and G
+// rules.  Its sums are integers, exact in any order, so the layout fixes where bytes lie and nothing about a sum.
+inline RescoreLayout rescore_layout_i8(uint32_t dim_full) {
+    RescoreLayout L{};
+    L.elem_bytes = 1u;
+    L.E = 16u;
+    L.pieces = (dim_full + 15u) / 16u;
+    L.stride = L.pieces * 16u;
+    L.padded = L.stride;
     L.G = 1;
     L.log2G = 0;
     while (L.G < L.pieces && L.G < 64u) {

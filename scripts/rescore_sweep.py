@@ -7,7 +7,7 @@ Data: synthetic prefix-trained rows -- 1,024 coordinates whose standard deviatio
   (b) the rescoring kernel alone (CPIndex.time_rescored / last_rescored_us), median over the same runs, against its byte
       floor: queries x C x stored row bytes / 6.29 TB/s (the measured copy rate of the part).
   (c) recall@10 against a float64 brute force at full width over --recall-queries queries: the plain search on the prefix,
-      and the rescored search at each C (float16 rows of 1,024).
+      and the rescored search at each C (float16 and int8 rows of 1,024).
 No target is fixed in advance.
     python scripts/rescore_sweep.py [--reps 5] [--nq 10000] [--out profiles/rescored_search.md]
     python scripts/rescore_sweep.py --n 100000 --no-write        # a rehearsal
@@ -24,7 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rabitq-ann-search_amd"))
 
 CS = (64, 128, 256)
-OBJECTS = ((256, "float16", CS), (1024, "float16", CS), (1024, "float32", (128,)))       # (dim_full, dtype, the C it runs at)
+# (dim_full, dtype, the C it runs at): float16 and int8 alternate at each width
+OBJECTS = ((256, "float16", CS), (256, "int8", CS), (1024, "float16", CS), (1024, "int8", CS), (1024, "float32", (128,)))
 COPY_TB_S = 6.29
 KEEP = "<!-- below this line: written by hand, kept by scripts/rescore_sweep.py -->"
 DIM, DIM_FULL, BITS, K = 128, 1024, 4, 10
@@ -133,8 +134,8 @@ def main():
             row["kernel_over_plain_call"] = round(kern / 1e3 / row["plain_ms_median"], 3)
             print(json.dumps(row), flush=True)
             rows.append(row)
-            if dim_full == DIM_FULL and dtype == "float16":
-                rec[f"rescored at C = {C_}, float16 rows of {DIM_FULL}"] = round(recall(res[0][:nr].cpu().numpy(), truth), 4)
+            if dim_full == DIM_FULL and dtype != "float32":
+                rec[f"rescored at C = {C_}, {dtype} rows of {DIM_FULL}"] = round(recall(res[0][:nr].cpu().numpy(), truth), 4)
         rv.close()
     ix.time_rescored(False)
     print(json.dumps(rec), flush=True)
@@ -156,7 +157,7 @@ def write_report(rows, rec, n, nq, nr, reps, out):
             f"1,000 clusters) indexed on their first {DIM}; batches of {nq:,} queries on the device, one process, the two calls "
             f"alternating, warm, both into preallocated outputs; median / min / max of {reps} runs each (host clock around calls that "
             "end in a device synchronise).  `plain` is the search at the same C, which the rescored call contains; `kernel us` is "
-            "rescore_rows_kernel alone between two HIP events; `floor us` = queries x C x stored row bytes / 6.29 TB/s; `kernel "
+            "the rescoring kernel alone (rescore_rows_kernel, or rescore_i8_kernel for int8 rows) between two HIP events; `floor us` = queries x C x stored row bytes / 6.29 TB/s; `kernel "
             f"over plain call` = the kernel's time over the plain call's.  Recall over the first {nr:,} queries.  "
             "scripts/rescore_sweep.py.\n\n")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)

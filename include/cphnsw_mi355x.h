@@ -231,9 +231,10 @@ int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
  * -- approximate distance beyond the k-th smallest seen plus twice the slack below -- and the VALU arithmetic re-scores the
  * survivors; a query that cannot be certified (its survivors overflow a pool, or a number is not finite) is answered by the
  * VALU scan behind it on the same stream.  Every output byte equals engine 0's.  Any other value: CPH_INVALID_ARGUMENT.
- * The scan of a batch with per-query filters, the range search and the tail scan do not change.
+ * The scan of a batch with per-query filters and the tail scan do not change.  The exact range search under engine 1: see
+ * "range search" below.
  * cph_last_matrix_stats: out[0] = parts of the candidate list, out[1] = ids re-scored (summed over the queries), out[2] =
- * queries the VALU scan answered, of the last batch if engine 1 ran it; zeros otherwise.
+ * queries the VALU scan answered, of the last batch (or exact range search) if engine 1 ran it; zeros otherwise.
  * cph_host_exact_matrix_slack: the slack, a bound on |approximate - exact distance| for a query of squared norm qnorm
  * against rows of squared norm <= bn_max at padded dimension D (the statement the device uses).
  * cph_host_exact_matrix_plan: how engine 1 cuts a batch (host only; the argument checks of cph_host_exact_plan): out[0] = Kp,
@@ -277,7 +278,16 @@ int cph_debug_matrix_bn_max(cph_index* h, float* out);
  *     Both steps hold the handle mutex, host waits included: other calls on the same handle queue behind them.
  *
  * cph_last_search_stats after an exact range search: [1] = 2 x n x candidates (two passes), every other word 0; after
- * the graph route: those of the underlying search. */
+ * the graph route: those of the underlying search.
+ *
+ * Engine 1 (cph_set_exact_engine) and exact != 0: the same lims, ids, distance bytes and order.  The matrix cores discard
+ * every pair whose approximate distance is finite and >= cph_host_range_matrix_limit(radius, slack) >= radius + slack, which
+ * proves dist >= radius; the VALU arithmetic re-scores the survivors and decides every hit.  begin then counts the
+ * survivors, waits, fills, re-scores, sorts and counts the hits, and returns the exact total; finish only emits.  Scratch:
+ * 12 bytes per survivor, 20 where a segment of survivors is longer than one LDS sort (cph_host_range_matrix_fits); a call
+ * whose survivors exceed the exact scratch budget continues as under engine 0, with engine 0's statistics.  Otherwise
+ * cph_last_search_stats [1] = pairs re-scored and cph_last_matrix_stats = {parts, the same number, 0}.
+ * cph_host_range_matrix_plan: out[0] = P parts of the candidate list, out[1] = candidates per part (a multiple of 128). */
 typedef struct cph_range cph_range;
 int cph_range_search_begin(cph_index* h, const void* queries, int queries_on_device, uint64_t n, const float* radius_host,
                            const cph_filter* filter, int exact, uint64_t max_results, void* stream, cph_range** out,
@@ -293,6 +303,9 @@ int cph_range_destroy(cph_range* r);
 int cph_host_range_plan(uint64_t candidates, uint64_t n_queries, int num_cus, uint64_t* out);
 int cph_host_range_tiles(const int64_t* lims, uint64_t n, uint64_t budget_bytes, uint64_t* starts_out, uint64_t* n_tiles_out);
 int cph_host_range_merge_pass(const uint64_t* in, uint64_t* out, uint64_t len, uint64_t width);
+int cph_host_range_matrix_limit(float radius, float eps, float* out);
+int cph_host_range_matrix_plan(uint64_t candidates, uint64_t n_queries, int num_cus, uint64_t out[2]);
+int cph_host_range_matrix_fits(uint64_t survivors, int any_long, uint64_t budget_bytes, int* out);
 
 /* ---- grouped search --------------------------------------------------------------------- */
 /* The k best key groups of every query, up to group_size rows of each (group-by / collapse): rows that share a key -- the

@@ -1421,6 +1421,10 @@ class CPIndex:
         A multi-device index shards the queries like search_batch(exact=True); the bytes are those of one device.
         Per-query filters (filter_of) and a partitioned index are refused (use part(i).range_search).
         `label`: one label value, instead of filter=label_filter(label).
+        exact_engine = "matrix" and exact=True: the matrix cores discard every pair that provably is no hit, the vector
+        arithmetic re-scores the survivors and decides -- the same lims, ids, bytes and order; last_search_stats() then
+        reports exact_l2 = matrix_survivors = pairs re-scored, matrix_parts and matrix_redo = 0.  A call whose survivors
+        exceed the exact scratch budget runs on the vector engine, with its statistics.
         metric="cosine": `radius` and the distances are in 1 - cos (0 = same direction, 1 = orthogonal, 2 = opposite)."""
         q = _as_f32(queries)
         if q.ndim != 2 or q.shape[1] != self._dim:
@@ -2507,7 +2511,8 @@ class CPIndex:
         grouped, diverse, MaxSim, fused and rescored searches on top of them).  "vector" (default): the fp32 VALU scan.
         "matrix": the matrix cores discard every candidate that provably cannot be in the top-k and the vector
         arithmetic re-scores the survivors -- the same bytes, ids and order.  After a matrix batch last_search_stats()
-        also reports matrix_parts, matrix_survivors and matrix_redo."""
+        also reports matrix_parts, matrix_survivors and matrix_redo.  range_search(exact=True) with one filter or none
+        takes it too: there the matrix cores discard every pair that provably is not within the radius."""
         return self._exact_engine
 
     @exact_engine.setter

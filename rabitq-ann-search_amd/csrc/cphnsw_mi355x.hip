@@ -40,6 +40,7 @@
 #include "device_exact.h"
 #include "device_exact_mfma.h"
 #include "device_range.h"
+#include "device_range_mfma.h"
 #include "device_tail.h"
 #include "device_diverse.h"
 #include "device_group.h"
@@ -186,6 +187,11 @@ struct RangeScratch {
     DevBuf<uint32_t> counts;
     DevBuf<unsigned long long> offs, sums, d_lims, d_stats, arena, arena2;
     DevBuf<uint8_t> d_tab;
+    // the matrix engine (device_range_mfma.h): the queries' slacks (and the flags exact_mfma_query_kernel writes beside them),
+    // the survivors' offsets per (query, part) and per query, their ids, the hits per query
+    DevBuf<float> mx_eps;
+    DevBuf<uint32_t> mx_flags, sids, hits;
+    DevBuf<unsigned long long> soffs, d_slims;
 };
 constexpr size_t kRangeScratchKept = 2;
 
@@ -403,6 +409,7 @@ struct cph_index {
     int last_search = -1;              // the set the most recent search went to
     bool last_range = false;           // ... unless an exact range search came later: it uses no set, its one counter is
     uint64_t range_exact = 0;          //     kept here (cph_last_search_stats)
+    uint32_t range_mx_parts = 0;       //     and, where the matrix engine ran it, its parts (cph_last_matrix_stats); else 0
     std::vector<std::unique_ptr<RangeScratch>> range_scratch;   // idle buffers of finished range searches (under mu)
     RerankScratch rerank_scratch[kMaxBatchSets];                // buffers of the re-rankers, in rotation (under mu)
     int last_rerank = kMaxBatchSets - 1;
@@ -2784,7 +2791,8 @@ int cph_last_search_stats(cph_index* h, uint64_t out[12]) {
         if (!h || !out) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
         for (int i = 0; i < 12; ++i) out[i] = 0;
-        if (h->last_range) {                     // an exact range search: two passes over the candidates, nothing else
+        if (h->last_range) {                     // an exact range search: two passes over the candidates (the matrix engine:
+                                                 // the survivors it re-scored), nothing else
             out[kStatExact] = h->range_exact;
             return;
         }
@@ -2989,7 +2997,11 @@ int cph_last_matrix_stats(cph_index* h, uint64_t out[3]) {
         if (!h || !out) throw InvalidArg("null argument");
         std::lock_guard<std::mutex> lk(h->mu);
         out[0] = out[1] = out[2] = 0;
-        if (h->last_range || h->last_search < 0 || h->sets[h->last_search].mx_parts == 0) return;
+        if (h->last_range) {                     // a matrix range search re-scores its survivors and nothing else
+            if (h->range_mx_parts) { out[0] = h->range_mx_parts; out[1] = h->range_exact; }
+            return;
+        }
+        if (h->last_search < 0 || h->sets[h->last_search].mx_parts == 0) return;
         BatchSet& s = h->sets[h->last_search];
         h->use_device();
         HIP_CHECK(hipEventSynchronize(s.ev_done));
@@ -3084,6 +3096,10 @@ struct cph_range {
     std::vector<int64_t> lims;                 // [n + 1]
     uint64_t total = 0;
     std::unique_ptr<RangeScratch> s;           // its device buffers: taken from the handle at begin, handed back by destroy
+    // the matrix engine: begin has re-scored and sorted the survivors, finish only emits
+    bool matrix = false;
+    std::vector<int64_t> slims;                // [n + 1] the survivors' segments
+    const unsigned long long* keys_long = nullptr;   // where the last merge pass left the segments longer than a run
 };
 
 namespace {
@@ -3116,6 +3132,128 @@ RangeArgs range_args(const cph_range* r) {
     a.offs = r->s->offs.p;
     a.arena = r->s->arena.p;
     return a;
+}
+
+// One pass of range_mfma_kernel over all the queries: grid.y holds at most 65,535 tiles.
+template <bool kFill>
+void range_matrix_pass(cph_range* r, RangeMatrixArgs a) {
+    const uint64_t per = 65535ull * kMxTile;
+    for (uint64_t q0 = 0; q0 < r->n; q0 += per) {
+        a.q_first = (uint32_t)q0;
+        a.q_count = (uint32_t)std::min<uint64_t>(per, r->n - q0);
+        const dim3 grid(a.P, (a.q_count + kMxTile - 1) / kMxTile);
+        if (a.t.ids) hipLaunchKernelGGL((range_mfma_kernel<true, kFill>), grid, dim3(256), 0, r->st, a);
+        else hipLaunchKernelGGL((range_mfma_kernel<false, kFill>), grid, dim3(256), 0, r->st, a);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+// range_begin under the matrix engine (device_range_mfma.h), behind pad_queries: count, survivor offsets, a wait (the
+// scratch size is data), fill, re-score, merge, hit offsets, a wait.  Leaves r->lims exact and the sorted segments in the
+// arena.  False: the survivors exceed the scratch budget (range_matrix_fits) and nothing but the count has happened.
+bool range_begin_matrix(cph_index* h, cph_range* r) {
+    RangeScratch& s = *r->s;
+    hipStream_t st = r->st;
+    const uint64_t n = r->n;
+    const uint32_t D = h->L.D;
+    const RangeMatrixPlan mp = plan_range_matrix(r->m, n, h->num_cus);
+    const uint64_t n_cnt = n * mp.P;
+    const uint32_t* d_bn = matrix_bn_max(h, st);
+    s.mx_eps.alloc(n);
+    s.mx_flags.alloc(n);
+    s.counts.alloc(n_cnt);
+    s.soffs.alloc(n_cnt + 1);
+    s.sums.alloc(n_cnt / kRangeScanSpan + 2);
+    s.d_slims.alloc(n + 1);
+    s.hits.alloc(n);
+    s.offs.alloc(n + 1);
+    s.d_lims.alloc(n + 1);
+    hipLaunchKernelGGL(exact_mfma_query_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const float*)s.qnorm.p, d_bn, D, (uint32_t)n,
+                       s.mx_eps.p, s.mx_flags.p);
+    HIP_CHECK(hipGetLastError());
+    RangeMatrixArgs a{};
+    a.t.raw = h->d_raw.p;
+    a.t.norm_sq = h->d_norm.p;
+    a.t.qpad = s.qpad.p;
+    a.t.qnorm = s.qnorm.p;
+    a.t.ids = r->d_list;
+    a.t.D = D;
+    a.eps = s.mx_eps.p;
+    a.radius = s.d_rad.p;
+    a.m = (uint32_t)r->m;
+    a.part = mp.part;
+    a.P = mp.P;
+    a.nq = (uint32_t)n;
+    a.counts = s.counts.p;
+    a.soffs = s.soffs.p;
+    range_matrix_pass<false>(r, a);
+    range_offsets(s.counts.p, n_cnt, mp.P, s.sums.p, s.soffs.p, s.d_slims.p, st);
+    r->slims.assign(n + 1, 0);
+    HIP_CHECK(hipMemcpyAsync(r->slims.data(), s.d_slims.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    range_sync(r);
+    const uint64_t surv = (uint64_t)r->slims[n];
+    std::vector<RangeRun> runs;
+    std::vector<RangeLong> longs;
+    uint32_t max_run = 0;
+    uint64_t max_long = 0;
+    for (uint64_t q = 0; q < n; ++q) {
+        const uint64_t start = (uint64_t)r->slims[q], len = (uint64_t)(r->slims[q + 1] - r->slims[q]);
+        if (len > kRangeRun) {
+            longs.push_back(RangeLong{start, len});
+            max_long = std::max(max_long, len);
+        }
+        for (uint64_t o = 0; o < len; o += kRangeRun) {
+            const uint32_t rl = (uint32_t)std::min<uint64_t>(kRangeRun, len - o);
+            runs.push_back(RangeRun{start + o, rl, (uint32_t)q});
+            max_run = std::max(max_run, rl);
+        }
+    }
+    if (!range_matrix_fits(surv, !longs.empty(), h->exact_scratch_bytes)) return false;
+    r->matrix = true;
+    r->pl.P = mp.P;
+    r->in_flight = true;
+    HIP_CHECK(hipMemsetAsync(s.hits.p, 0, n * 4, st));
+    std::vector<uint8_t> tab;                              // (lives until the wait at the end: the copy may read it late)
+    if (surv) {
+        s.sids.alloc(surv);
+        s.arena.alloc(surv);
+        if (!longs.empty()) s.arena2.alloc(surv);
+        a.sids = s.sids.p;
+        range_matrix_pass<true>(r, a);
+        const size_t o_long = runs.size() * sizeof(RangeRun);
+        tab.resize(o_long + longs.size() * sizeof(RangeLong));
+        std::memcpy(tab.data(), runs.data(), o_long);
+        if (!longs.empty()) std::memcpy(tab.data() + o_long, longs.data(), longs.size() * sizeof(RangeLong));
+        s.d_tab.alloc(tab.size());
+        HIP_CHECK(hipMemcpyAsync(s.d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+        RangeRescoreArgs ra{};
+        ra.s = scan_common(h, s.qpad.p, s.qnorm.p, kExactQT, 0);
+        ra.radius = s.d_rad.p;
+        ra.runs = reinterpret_cast<const RangeRun*>(s.d_tab.p);
+        ra.sids = s.sids.p;
+        ra.arena = s.arena.p;
+        ra.hits = s.hits.p;
+        uint32_t N = 64;
+        while (N < max_run) N <<= 1;
+        CPH_LAUNCH_SCAN(range_rescore_runs_kernel, D, dim3((uint32_t)runs.size()), (size_t)N * 8 + 8, st, ra);
+        unsigned long long* src = s.arena.p;
+        unsigned long long* dst = s.arena2.p;
+        const uint32_t n_long = (uint32_t)longs.size();
+        for (unsigned long long w = kRangeRun; n_long && w < max_long; w <<= 1) {
+            for (uint32_t s0 = 0; s0 < n_long; s0 += 65535u) {
+                const dim3 grid((uint32_t)((max_long + 255) / 256), std::min<uint32_t>(65535u, n_long - s0));
+                hipLaunchKernelGGL(range_merge_pass_kernel, grid, dim3(256), 0, st, reinterpret_cast<const RangeLong*>(s.d_tab.p + o_long) + s0,
+                                   (const unsigned long long*)src, dst, w);
+                HIP_CHECK(hipGetLastError());
+            }
+            std::swap(src, dst);
+        }
+        r->keys_long = src;
+    }
+    range_offsets(s.hits.p, n, 1, s.sums.p, s.offs.p, s.d_lims.p, st);
+    HIP_CHECK(hipMemcpyAsync(r->lims.data(), s.d_lims.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    range_sync(r);
+    return true;
 }
 
 void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, const float* radius, const cph_filter* f, bool exact,
@@ -3153,7 +3291,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
         r->m = r->filt ? r->filt->popcount : h->size();
     }
     if (n == 0 || (exact && r->m == 0)) {                  // nothing to scan: every segment is empty
-        if (exact) { h->last_range = true; h->range_exact = 0; }
+        if (exact) { h->last_range = true; h->range_exact = 0; h->range_mx_parts = 0; }
         *out = r.release();
         return;
     }
@@ -3188,9 +3326,6 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
             HIP_CHECK(hipGetLastError());
         } else {
             const cph_filter* ef = r->filt.get();
-            r->pl = plan_range(r->m, n, h->num_cus);
-            P = r->pl.P;
-            n_cnt = n * P;
             const uint32_t D = h->L.D;
             // Padded query rows.  exact_fma_chunk loads all kExactQT rows of a query tile, whatever the group holds, and a
             // fill launch starts its groups at a scratch tile's first query (range_tiles), which need not be a multiple of
@@ -3199,10 +3334,24 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
             const uint32_t nq_pad = (uint32_t)range_query_rows(n);
             r->s->qpad.alloc((size_t)nq_pad * D);
             r->s->qnorm.alloc(nq_pad);
-            r->s->counts.alloc(n_cnt);
             r->s->d_stats.alloc(kStatWords);
             r->d_list = ef ? filter_id_list(ef, st) : nullptr;
             pad_queries(h, d_q, nullptr, (uint32_t)n, nq_pad, r->s->qpad.p, r->s->qnorm.p, r->s->d_stats.p, (unsigned long long)(2 * n * r->m), st);
+            if (h->exact_engine == 1 && r->m <= kMxMaxCandidates && range_begin_matrix(h, r.get())) {
+                r->total = (uint64_t)r->lims[n];
+                h->last_range = true;
+                h->range_exact = (uint64_t)r->slims[n];
+                h->range_mx_parts = r->pl.P;
+                *total = r->total;
+                *out = r.release();
+                return;
+            }
+            // the vector route (a matrix call whose survivors exceed the scratch budget continues here)
+            r->in_flight = true;
+            r->pl = plan_range(r->m, n, h->num_cus);
+            P = r->pl.P;
+            n_cnt = n * P;
+            r->s->counts.alloc(n_cnt);
             range_scan_pass<false>(r.get(), range_args(r.get()), 0, (uint32_t)n);
         }
         r->s->offs.alloc(n_cnt + 1);
@@ -3216,7 +3365,7 @@ void range_begin(cph_index* h, const float* queries, bool q_dev, uint64_t n, con
         throw;
     }
     r->total = (uint64_t)r->lims[n];
-    if (exact) { h->last_range = true; h->range_exact = 2 * n * r->m; }
+    if (exact) { h->last_range = true; h->range_exact = 2 * n * r->m; h->range_mx_parts = 0; }
     *total = r->total;
     *out = r.release();
 }
@@ -3285,6 +3434,11 @@ void range_finish(cph_range* r, int64_t* lims_host, int64_t* ids, float* dist, b
         if (!r->exact) {
             hipLaunchKernelGGL(range_cut_emit_kernel, dim3((uint32_t)n), dim3(64), 0, st, (const int64_t*)r->s->g_ids.p, (const float*)r->s->g_dist.p,
                                r->K, (const float*)r->s->d_rad.p, (const unsigned long long*)r->s->d_lims.p, d_ids, d_dist);
+            HIP_CHECK(hipGetLastError());
+        } else if (r->matrix) {
+            hipLaunchKernelGGL(range_emit_hits_kernel, dim3((uint32_t)n), dim3(256), 0, st, (const unsigned long long*)r->s->arena.p, r->keys_long,
+                               (const unsigned long long*)r->s->d_slims.p, (const unsigned long long*)r->s->d_lims.p,
+                               (const uint32_t*)(h->ids_input ? h->d_rows.p : nullptr), d_ids, d_dist);
             HIP_CHECK(hipGetLastError());
         } else {
             const std::vector<uint64_t> starts = range_tiles(r->lims.data(), n, h->exact_scratch_bytes);
@@ -3382,6 +3536,30 @@ int cph_host_range_plan(uint64_t candidates, uint64_t n_queries, int num_cus, ui
             throw InvalidArg("range plan: sizes out of range");
         const RangePlan pl = plan_range(candidates, n_queries, num_cus);
         out[0] = pl.P; out[1] = pl.part; out[2] = pl.gq; out[3] = pl.run; out[4] = range_query_rows(n_queries);
+    });
+}
+
+int cph_host_range_matrix_limit(float radius, float eps, float* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = range_matrix_limit(radius, eps);
+    });
+}
+
+int cph_host_range_matrix_plan(uint64_t candidates, uint64_t n_queries, int num_cus, uint64_t out[2]) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        if (candidates == 0 || candidates > 0xFFFFFFFFull || n_queries == 0 || n_queries > 0xFFFFFFFFull)
+            throw InvalidArg("range plan: sizes out of range");
+        const RangeMatrixPlan mp = plan_range_matrix(candidates, n_queries, num_cus);
+        out[0] = mp.P; out[1] = mp.part;
+    });
+}
+
+int cph_host_range_matrix_fits(uint64_t survivors, int any_long, uint64_t budget_bytes, int* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = range_matrix_fits(survivors, any_long != 0, budget_bytes) ? 1 : 0;
     });
 }
 

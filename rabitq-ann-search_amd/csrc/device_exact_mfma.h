@@ -133,6 +133,180 @@ __device__ __forceinline__ uint32_t mx_sort_keep(unsigned long long* sm, uint32_
     return kept;
 }
 
+// ---- the operand pipeline of a (part, query tile) workgroup -----------------------------------------------------------------
+// What "Prefilter geometry" above describes, up to the tile epilogue: the loop over the part's candidate tiles and K chunks,
+// for the kernels that differ only in what they do with a finished tile (range_mfma_kernel, device_range_mfma.h).
+struct MxTileArgs {
+    const float* raw;             // [n][D]
+    const float* norm_sq;         // [n]
+    const float* qpad;            // padded query rows
+    const float* qnorm;
+    const uint32_t* ids;          // LIST: the ascending id list
+    uint32_t D;
+    uint32_t c_lo, c_hi;          // the part's candidates, c_lo < c_hi
+    uint32_t q_row0, q_last;      // the tile's first padded query row; the last row a clamped fetch may read
+};
+
+struct MxOperandLds {
+    float Qs[2][kMxTile * kMxLd]; // double-buffered operand images
+    float Bs[2][kMxTile * kMxLd];
+    float bn_s[2][256];           // |b|^2 of the tile's columns, by tile parity (first 128 of each; the second 128: where
+                                  //   fetches past the end are staged)
+};
+
+// Whole workgroup of 256, converged.  epi.begin(qn) once, behind the barrier that publishes image(0) (and whatever LDS the
+// caller wrote before the call); epi.tile(tile, acc, qn) per finished tile: acc[t][i] = q.b - |b|^2 / 2 of (row wrow +
+// (i & 3) + 8 (i >> 2) + 4 h, column 128 tile + 32 t + c), qn[i] the rows' stored norms.  Columns behind c_hi repeat the
+// part's last candidate, rows behind q_last the last query: the epilogue masks both.
+template <bool LIST, class Epilogue>
+__device__ __forceinline__ void mx_scan_tiles(const MxTileArgs& a, MxOperandLds& L, Epilogue& epi) {
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int h = lane >> 5, c = lane & 31;
+    const uint32_t D = a.D, c_lo = a.c_lo, c_hi = a.c_hi;
+    const uint32_t nchunk = D < kMxKC ? 1u : D / kMxKC;
+    const uint32_t ntile = (c_hi - c_lo + kMxTile - 1) / kMxTile;
+    const uint32_t srow = tid >> 3, skq = (tid & 7) * 4;
+    const bool kzero = skq >= D;
+    const uint32_t skl = kzero ? 0u : skq;
+    const float* qsrc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qsrc[i] = a.qpad + (size_t)min(a.q_row0 + srow + 32 * i, a.q_last) * D + skl;
+    auto cand_id = [&](uint32_t tile, uint32_t r) -> uint32_t {
+        const uint32_t cc = (uint32_t)min((uint64_t)c_lo + tile * kMxTile + r, (uint64_t)c_hi - 1);
+        if constexpr (LIST) return a.ids[cc];
+        else return cc;
+    };
+    knn_f32x4 pq[4], pb[4];
+    float pbn = 0.0f;
+    uint32_t f_tile = 0, f_ch = 0;
+    uint32_t f_tile_staged = 0;
+    bool f_past = false, f_past_staged = false;
+    uint32_t rid[4], nid[4], bid, nbid;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { rid[i] = cand_id(0, srow + 32 * i); nid[i] = cand_id(1, srow + 32 * i); }
+    bid = cand_id(0, tid & (kMxTile - 1));
+    nbid = cand_id(1, tid & (kMxTile - 1));
+    auto fetch = [&]() {
+        const uint32_t k0 = f_ch * kMxKC;
+        f_tile_staged = f_tile;
+        f_past_staged = f_past;
+        pbn = a.norm_sq[bid];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const knn_f32x4 x = *reinterpret_cast<const knn_f32x4*>(qsrc[i] + k0);
+            pq[i] = kzero ? knn_f32x4{0.0f, 0.0f, 0.0f, 0.0f} : x;
+            pb[i] = *reinterpret_cast<const knn_f32x4*>(a.raw + (size_t)rid[i] * D + skl + k0);
+        }
+        const bool wrap = f_ch + 1 == nchunk;
+        f_past = f_past || (wrap && f_tile + 1 == ntile);
+        f_ch = wrap ? 0 : f_ch + 1;
+        f_tile = (wrap && f_tile + 1 < ntile) ? f_tile + 1 : f_tile;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            rid[i] = wrap ? nid[i] : rid[i];
+            nid[i] = cand_id(f_tile + 1, srow + 32 * i);
+        }
+        bid = wrap ? nbid : bid;
+        nbid = cand_id(f_tile + 1, tid & (kMxTile - 1));
+    };
+    auto stage = [&](int buf) {
+        L.bn_s[f_tile_staged & 1][f_past_staged ? (tid | 128) : tid] = pbn;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            *reinterpret_cast<knn_f32x4*>(&L.Qs[buf][(srow + 32 * i) * kMxLd + skq]) = pq[i];
+            *reinterpret_cast<knn_f32x4*>(&L.Bs[buf][(srow + 32 * i) * kMxLd + skq]) = pb[i];
+        }
+    };
+    const int wrow = wave * 32;
+    struct Ops { knn_f32x4 av[2], bv[2][4]; };
+    auto read_ops = [&](int buf, int half, Ops& o) {
+        const float* Qb = L.Qs[buf];
+        const float* Bb = L.Bs[buf];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            const int j = 2 * half + jj;
+            o.av[jj] = *reinterpret_cast<const knn_f32x4*>(&Qb[(wrow + c) * kMxLd + 8 * j + 4 * h]);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                o.bv[jj][t] = *reinterpret_cast<const knn_f32x4*>(&Bb[(t * 32 + c) * kMxLd + 8 * j + 4 * h]);
+        }
+    };
+    knn_f32x16 acc[4];
+    auto mfma_half = [&](const Ops& o) {
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.av[jj].x, o.bv[jj][t].x, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.av[jj].y, o.bv[jj][t].y, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.av[jj].z, o.bv[jj][t].z, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.av[jj].w, o.bv[jj][t].w, acc[t], 0, 0, 0);
+            }
+        }
+    };
+    float qn[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) qn[i] = a.qnorm[min(a.q_row0 + (uint32_t)(wrow + (i & 3) + 8 * (i >> 2) + 4 * h), a.q_last)];
+
+    Ops op0, op1;
+    fetch();
+    stage(0);
+    fetch();
+    __syncthreads();
+    epi.begin(qn);
+    read_ops(0, 0, op0);
+    int buf = 0;
+    constexpr int kVmemGroups = LIST ? 13 : 9;
+    for (uint32_t tile = 0; tile < ntile; ++tile)
+    for (uint32_t ch = 0; ch < nchunk; ++ch) {
+        if (ch == 0) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float init = -0.5f * L.bn_s[tile & 1][t * 32 + c];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[t][i] = init;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        read_ops(buf, 1, op1);
+        stage(buf ^ 1);
+        fetch();
+        mfma_half(op0);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+        }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // DS write
+        }
+#pragma unroll
+        for (int i = 0; i < kVmemGroups; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);   // VALU (addresses of the fetch)
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+        }
+        if constexpr (kVmemGroups < 13) __builtin_amdgcn_sched_group_barrier(0x008, 13 - kVmemGroups, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        buf ^= 1;
+        read_ops(buf, 0, op0);
+        mfma_half(op1);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 22, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ch + 1 != nchunk) continue;
+        epi.tile(tile, acc, qn);
+    }
+}
+
 // ---- 1. the prefilter -------------------------------------------------------------------------------------------------------
 struct MatrixArgs {
     const float* raw;             // [n][D]

@@ -33,4 +33,18 @@ CPH_EXACT_MFMA_HD inline float exact_matrix_slack(float qnorm, float bn_max, uin
     return c * __builtin_fmaf(0x1.0002p-24f, N, FLT_MIN);
 }
 
+// The limit of the range search's prefilter (device_range_mfma.h) for a query of radius `radius` and slack `eps`: a pair
+// is DISCARDED iff its approximate distance d^ is finite and d^ >= lim; everything else survives and is re-scored.
+//   d^ >= lim >= radius + eps  =>  d >= d^ - eps >= radius: the pair is not a hit (a hit is d < radius, strict).
+//   NaN radius or radius <= 0: -1.  No distance (>= +0, or NaN) is < radius, so nothing need survive.
+//   eps not finite (and with it a qnorm that is not): NaN.  No comparison discards anything; the vector arithmetic answers.
+//   Otherwise (radius + eps) * (1 + 2^-22): the sum rounds to nearest, within one ulp below the real sum, and the factor
+//   gives two (the rounding-up of mx_limit).  +inf stays +inf, and a finite d^ is never >= it.
+// cph_host_range_matrix_limit exports it; tests/test_range_matrix_host.py checks lim >= radius + eps in exact rationals.
+CPH_EXACT_MFMA_HD inline float range_matrix_limit(float radius, float eps) {
+    if (!(radius > 0.0f)) return -1.0f;
+    if (!(__builtin_fabsf(eps) <= FLT_MAX)) return __builtin_nanf("");
+    return (radius + eps) * 0x1.000004p+0f;
+}
+
 }  // namespace cph

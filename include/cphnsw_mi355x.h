@@ -552,6 +552,50 @@ int cph_host_maxsim_rescore(const int32_t* cand_keys, const float* cand_lb, cons
                             int32_t* out_found, int32_t* out_certified);
 int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_t* out_keys, uint32_t* out_offsets, uint64_t* out_n_keys);
 
+/* ---- exhaustive multi-vector search: certified lower bounds over EVERY key (ABI 120) ------- */
+/* The rescored search above with another first stage: no candidate rows, no `candidates`.  A matrix-core pass over every
+ * row of every key (maxsim_all_mfma_kernel, csrc/device_maxsim_all.h: v_mfma_f32_32x32x2_f32 through the operand pipeline
+ * of the exact matrix engine, columns = the inverted key column) leaves one lower bound per (query, key) with an allowed
+ * row; the `rescore` = R keys (k <= R <= 1024) with the smallest (lb, key) are the candidates, in that order; from there on
+ * the pad, scan and select kernels and every output are those of cph_search_maxsim_rescored.  csrc/host_maxsim_all.h states
+ * the bound and proves it:
+ *   d^, eps_t   the prefilter distance and slack of the exact matrix engine (cph_host_exact_matrix_slack over the token's
+ *               norm, the largest row norm and D);
+ *   l_t(key)    cph_host_maxsim_all_term(min over the key's allowed rows of d^(t, row), eps_t) <= min over those rows of the
+ *               cph_exact_l2 distance; lb = ((+0.0f + l_0) + l_1) + ... in float32, token order; lb <= score(key) because
+ *               round-to-nearest addition is monotone;
+ *   certified   every key outside the candidates has lb >= lb_{R-1} over the WHOLE index, so the certified slots are the
+ *               true MaxSim top slots in the true order.  `exact` is ignored: the pass is exhaustive.
+ * A key without an allowed row for a query is no candidate of it.  A query whose token norm, eps or the largest row norm is
+ * not finite (or that meets a d^ that is not) gets lb = +0.0f for every key with an allowed row: certified comes out 0.
+ * The bound table [queries of a chunk][keys] lives in scratch; the call is cut into chunks of queries so that it stays
+ * within the scratch budget of the exact engine (CPH_EXACT_SCRATCH_MB; cph_debug_maxsim_all_budget sets its own, 0: that
+ * one).  Filters, filter_of, removed rows, tail rows, both id spaces, cosine, keys objects and replicas work as in the
+ * rescored call; the inner-product metric and partitioned indexes are refused as there.  The _device form only enqueues,
+ * except for building the inverted key column the first time (cph_prepare_maxsim_rescore). */
+int cph_search_maxsim_all(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                          uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                          const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                          int32_t* out_found, int32_t* out_certified);
+int cph_search_maxsim_all_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                 uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                                 const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score, int32_t* d_hits, int64_t* d_rows,
+                                 int32_t* d_found, int32_t* d_certified, void* stream);
+/* Debug hooks: the bounds kernel (of the call's last chunk) between two HIP events while switched on; the table budget. */
+int cph_debug_time_maxsim_all(cph_index* h, int on);
+int cph_debug_last_maxsim_all_us(cph_index* h, double* us);
+int cph_debug_maxsim_all_budget(cph_index* h, uint64_t bytes);
+/* The term of the bound, on the host (no HIP call): <= max(m_hat - eps, 0), never negative, never NaN. */
+int cph_host_maxsim_all_term(float m_hat, float eps, float* out);
+/* Test hook: the eps, pack, bounds and select kernels against the vectors of h.  tokens [n][n_tok][dim]; n_tokens [n] or
+ * NULL; keys: a keys object of h or NULL (the label column); allow: [n][(cph_size + 31) / 32] bitmap words, one bitmap per
+ * query, or NULL (every id).  out_lb_table [n][distinct keys] (key ranks ascend with the keys; the bits 0xFFFFFFFF: the
+ * key has no allowed row), out_cand_keys / out_cand_lb [n][rescore] (the first out_cand_found[i] are written),
+ * out_cand_found [n].  The device outputs start as 0xA5 bytes. */
+int cph_maxsim_all_hook(cph_index* h, const float* tokens, uint64_t n, uint64_t n_tok, const int32_t* n_tokens, const cph_group_keys* keys,
+                        const uint32_t* allow, uint64_t rescore, float* out_lb_table, int32_t* out_cand_keys, float* out_cand_lb,
+                        int32_t* out_cand_found);
+
 /* ---- fused search: several query vectors per query, exact weighted-sum top-k (ABI 115) ----- */
 /* queries is [n][vectors][dim]: T = vectors query vectors per query (rewrites of one question, liked and disliked examples, an
  * image and a text vector) of which the first L = n_vectors[i] are live (1 <= L <= T; NULL: all T), with weights [n][T],
@@ -1070,6 +1114,11 @@ int cph_multi_search_maxsim_rescored(cph_multi* m, const float* queries, uint64_
                                      const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of, int exact,
                                      int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows, int32_t* out_found,
                                      int32_t* out_certified);
+/* cph_search_maxsim_all over the same shards. */
+int cph_multi_search_maxsim_all(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                uint64_t rescore, const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                                const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits,
+                                int64_t* out_rows, int32_t* out_found, int32_t* out_certified);
 /* cph_search_fused, sharded by query (never inside one query's vectors): n_vectors, weights, filter_of and the outputs are
  * sliced by shard; filters[f * R + r] as in cph_multi_search_grouped.  The bytes are those of one device. */
 int cph_multi_search_fused(cph_multi* m, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,

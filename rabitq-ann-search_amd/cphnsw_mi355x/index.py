@@ -1791,13 +1791,16 @@ class CPIndex:
             raise ValueError("search_maxsim is not defined on a partitioned index (every part has its own internal ids and "
                              "its own slice of the labels): use part(i).search_maxsim")
         k = int(k)
+        every = isinstance(candidates, str)
+        if every and candidates != "all":
+            raise ValueError('candidates must be an integer, None or "all"')
         if not 1 <= T <= self.MAXSIM_MAX_TOKENS:
             raise ValueError(f"search_maxsim needs 1 <= tokens <= {self.MAXSIM_MAX_TOKENS} (queries is [n, tokens, dim]), got {T}")
         if not 1 <= k <= self.MAXSIM_MAX_K:
             raise ValueError(f"search_maxsim needs 1 <= k <= {self.MAXSIM_MAX_K}")
         if candidates is None:                       # a policy, not a measured optimum
             candidates = min(self.MAXSIM_MAX_CANDIDATES, self.MAXSIM_MAX_ENTRIES // T, max(32, 4 * k))
-        candidates = int(candidates)
+        candidates = 1 if every else int(candidates)     # ("all": there are no candidate rows)
         if not 1 <= candidates <= self.MAXSIM_MAX_CANDIDATES:
             raise ValueError(f"candidates must lie in [1, {self.MAXSIM_MAX_CANDIDATES}]")
         if T * candidates > self.MAXSIM_MAX_ENTRIES:
@@ -1835,6 +1838,13 @@ class CPIndex:
         """-> (the scalars between n and the keys, the output table) of the rescored entries."""
         lead, table = CPIndex._maxsim_call(n, T, k, C_, nt)
         return lead + (R,), table + (((n,), "int32"),)
+
+    def _maxsim_all_call(self, n, T, k, nt, rescore):
+        """candidates="all" -> (the scalars between n and the keys, the output table) of the exhaustive entries.
+        rescore=None: R = min(1024, max(64, 4 * k)), a policy, not a measured optimum."""
+        R = min(self.MAXSIM_MAX_RESCORE, max(64, 4 * k)) if rescore is None else self._maxsim_rescore_arg(rescore, k)
+        lead, table = self._maxsim_rescored_call(n, T, k, 1, nt, R)
+        return lead[:3] + (R,), table
 
     def prepare_maxsim_rescore(self, keys=None):
         """Builds the inverted key column search_maxsim(..., rescore=R) walks -- of `keys` (a GroupKeys), or of the label
@@ -1887,7 +1897,16 @@ class CPIndex:
         bound of at least lb_{R-1}, so with exact=True those leading slots are the true MaxSim top slots over the allowed
         rows, in the true order; with a graph-routed search the bound is relative to the candidate rows the search returned,
         not to the index.  The first rescored call on a key column builds its inverted form on the host and waits for the
-        device (prepare_maxsim_rescore does it ahead of time)."""
+        device (prepare_maxsim_rescore does it ahead of time).
+        `candidates="all"` replaces the first stage by an EXHAUSTIVE one and returns the six outputs: a matrix-core pass over
+        every row of every key leaves one float32 lower bound per (query, key with an allowed row) -- per live token the
+        smallest prefilter distance of the key's allowed rows less the token's slack (exact_matrix_slack), rounded outward,
+        summed in token order; never above the key's exact score -- and the R keys with the smallest (lb, key) are rescored
+        as above.  Every key outside them has lb >= lb_{R-1} over the WHOLE index, so the leading certified[i] slots are the
+        true MaxSim top slots in the true order.  rescore=None takes R = min(1024, max(64, 4 * k)): a policy, not a measured
+        optimum.  `exact` is ignored: the pass is exhaustive.  A query with a token whose norm is not finite gets lb = 0
+        for every key: certified[i] = 0.  Filters, filter_of, label, removed and added rows, result_ids, cosine, keys and
+        replicas work as in the rescored call."""
         q = _as_f32(queries)
         if q.ndim != 3 or q.shape[2] != self._dim:
             raise ValueError("queries must be a (n, tokens, dim) array")
@@ -1896,6 +1915,9 @@ class CPIndex:
                 q, k, n_tokens=n_tokens, candidates=candidates, keys=keys, filter=f, exact=exact, filter_of=fo, rescore=rescore))
         n, T = q.shape[0], q.shape[1]
         k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
+        if isinstance(candidates, str):
+            lead, table = self._maxsim_all_call(n, T, k, nt, rescore)
+            return self._rerank_host("maxsim_all", q, lead, keys, filters, exact, table)
         if rescore is not None:
             lead, table = self._maxsim_rescored_call(n, T, k, C_, nt, self._maxsim_rescore_arg(rescore, k))
             return self._rerank_host("maxsim_rescored", q, lead, keys, filters, exact, table)
@@ -1914,7 +1936,9 @@ class CPIndex:
         cosine: MaxSim similarity = n_tokens - score.
         `rescore=R`: the six outputs of search_maxsim(..., rescore=R) (`out`: six tensors, the last (n,) int32).  The first
         rescored call on a key column builds its inverted form and waits for the device -- the one exception to "only
-        enqueues"; prepare_maxsim_rescore builds it ahead of time."""
+        enqueues"; prepare_maxsim_rescore builds it ahead of time.
+        `candidates="all"`: the exhaustive first stage of search_maxsim (six outputs; rescore=None: its policy R; `exact` is
+        ignored); the bound table is scratch of the index, cut into chunks of queries that run back to back on `stream`."""
         import torch
         if queries.dim() != 3 or queries.shape[2] != self._dim or queries.dtype != torch.float32:
             raise ValueError("queries must be a (n, tokens, dim) array")
@@ -1924,9 +1948,14 @@ class CPIndex:
                 filter_of=fo, rescore=rescore))
         n, T = queries.shape[0], queries.shape[1]
         k, C_, nt, keys, filters = self._maxsim_args(n, T, k, n_tokens, candidates, keys, filter, filter_of)
-        if rescore is not None:
-            lead, table = self._maxsim_rescored_call(n, T, k, C_, nt, self._maxsim_rescore_arg(rescore, k))
-            return tuple(self._rerank_device("maxsim_rescored", queries, lead, keys, filters, exact, table, out, stream,
+        if isinstance(candidates, str) or rescore is not None:
+            if isinstance(candidates, str):
+                name = "maxsim_all"
+                lead, table = self._maxsim_all_call(n, T, k, nt, rescore)
+            else:
+                name = "maxsim_rescored"
+                lead, table = self._maxsim_rescored_call(n, T, k, C_, nt, self._maxsim_rescore_arg(rescore, k))
+            return tuple(self._rerank_device(name, queries, lead, keys, filters, exact, table, out, stream,
                                              ("out must be the six tensors (keys, score, hits, rows, found, certified)",
                                               "out must be contiguous (n, k) int32 / float32 / int32, (n, k, tokens) int64, (n,) int32 "
                                               "and (n,) int32 tensors on the queries' device")))
@@ -1945,6 +1974,16 @@ class CPIndex:
         """Device time (HIP events, microseconds) of the maxsim kernel of the last maxsim search made under time_maxsim()
         on the given replica; waits for that launch."""
         return self._last_pass_us("cph_debug_last_maxsim_rows_us", replica)
+
+    def time_maxsim_all(self, on=True):
+        """Debug hook of the measurement script: while on, the bounds kernel (maxsim_all_mfma_kernel) of every
+        search_maxsim(..., candidates="all") -- of its last chunk of queries -- is bracketed by HIP events."""
+        self._time_pass("cph_debug_time_maxsim_all", on)
+
+    def last_maxsim_all_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the bounds kernel of the last exhaustive maxsim search made
+        under time_maxsim_all() on the given replica; waits for it."""
+        return self._last_pass_us("cph_debug_last_maxsim_all_us", replica)
 
     def time_maxsim_rescore(self, on=True):
         """Debug hook of the measurement script: while on, the scan kernel of every rescored maxsim search (the exact terms;

@@ -45,6 +45,7 @@
 #include "device_diverse.h"
 #include "device_group.h"
 #include "device_maxsim.h"
+#include "device_maxsim_all.h"
 #include "device_maxsim_rescore.h"
 #include "device_fused.h"
 #include "device_rescore.h"
@@ -233,6 +234,12 @@ struct RerankScratch {
         DevBuf<float> score;
         void reserve(Reserve& r, size_t n, size_t slots) { r(ids, slots), r(hits, slots), r(score, slots), r(count, n); }
     } un;
+    // exhaustive maxsim (device_maxsim_all.h): eps and flags of the token rows, the rows in the tile layout, the queries that
+    // cannot be bounded, the bound table of one chunk of queries
+    struct All {
+        DevBuf<float> eps_raw, qp, qn, eps;
+        DevBuf<uint32_t> flags, unbounded, table;
+    } all;
     Reserve reserve() const { return Reserve{rows.ev, rows.used}; }      // growing: the set's previous batch must be done
 };
 
@@ -250,8 +257,8 @@ constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the 
 // The passes a handle can time (PassTimer).  kPassMaxsimRescore is the scan kernel of the rescored maxsim search alone, bracketed
 // inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
 // rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
-// same way.
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassUntimed, kPassKinds };
+// same way.  kPassMaxsimAll: the bounds kernel of the last chunk of an exhaustive maxsim search (device_maxsim_all.h).
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassMaxsimAll, kPassUntimed, kPassKinds };
 
 // The facet dictionary of one column (cph_facet_*; device_facets.h): its distinct values ascending, on both sides, and one
 // 32-bit code per row -- per CSR entry for a tag column -- on the device.  Made on first use, dropped when the column changes.
@@ -370,6 +377,7 @@ struct cph_index {
     // cph_set_exact_engine: 0 the vector scan, 1 the matrix prefilter.  d_bn_max: the largest norm_sq of the rows (as bits),
     // made on first use for the index state (index_epoch, size()) it is valid for; bn_ev follows the kernel that made it
     int exact_engine = 0;
+    size_t maxsim_all_table_bytes = 0; // cph_debug_maxsim_all_budget: the bound table of an exhaustive maxsim chunk, at most (0: exact_scratch_bytes)
     DevBuf<uint32_t> d_bn_max;
     uint64_t bn_epoch = ~0ull, bn_rows = 0;
     hipEvent_t bn_ev = nullptr;
@@ -691,6 +699,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed fused search has run on this handle (cph_debug_time_fused)",
     "no timed tag pass has run on this handle (cph_debug_time_tag_filters)",
     "no timed facet pass has run on this handle (cph_debug_time_facets)",
+    "no timed exhaustive maxsim search has run on this handle (cph_debug_time_maxsim_all)",
     "this pass is not timed",
 };
 
@@ -2109,7 +2118,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 119; }
+int cph_version(void) { return 120; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -6882,28 +6891,36 @@ const int32_t* group_key_column(const cph_index* h, const cph_group_keys* keys) 
 // The ordinary search at k = C into the rows of `gs`, in internal ids, then pass(), which enqueues one kernel over those
 // rows, bracketed by the timer's events while it is on; everything on `st`.  The caller holds the handle mutex and has set
 // the device.
-template <class Pass>
-void search_rows_then_pass(cph_index* h, RerankScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
-                           uint32_t F, const int32_t* filter_of, bool exact, cph_index::PassTimer& timer, hipStream_t st, Pass pass) {
+// work(), which enqueues on `st`, behind the set's previous batch and in front of its event.
+template <class Work>
+void behind_set_event(RerankScratch& gs, hipStream_t st, Work work) {
     RerankScratch::Rows& rows = gs.rows;
     if (!rows.ev) HIP_CHECK(hipEventCreateWithFlags(&rows.ev, hipEventDisableTiming));
-    Reserve r = gs.reserve();
-    r(rows.ids, n * C);
-    r(rows.dist, n * C);
-    if (rows.used) HIP_CHECK(hipStreamWaitEvent(st, rows.ev, 0));    // the rows' previous batch, maybe on another stream
+    if (rows.used) HIP_CHECK(hipStreamWaitEvent(st, rows.ev, 0));    // the set's previous batch, maybe on another stream
     try {
-        {
-            InternalIdsScope internal(h);
-            search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, rows.ids.p, rows.dist.p, true, st));
-        }
-        timed_pass(timer, st, pass);
+        work();
     } catch (...) {
-        (void)hipEventRecord(rows.ev, st);                        // whatever was enqueued may still write the rows
+        (void)hipEventRecord(rows.ev, st);                        // whatever was enqueued may still write the set
         rows.used = true;
         throw;
     }
     HIP_CHECK(hipEventRecord(rows.ev, st));
     rows.used = true;
+}
+
+template <class Pass>
+void search_rows_then_pass(cph_index* h, RerankScratch& gs, const float* d_queries, uint64_t n, uint64_t C, const cph_filter* const* filters,
+                           uint32_t F, const int32_t* filter_of, bool exact, cph_index::PassTimer& timer, hipStream_t st, Pass pass) {
+    Reserve r = gs.reserve();
+    r(gs.rows.ids, n * C);
+    r(gs.rows.dist, n * C);
+    behind_set_event(gs, st, [&] {
+        {
+            InternalIdsScope internal(h);
+            search_batch_locked(h, batch_call(d_queries, n, C, filters, F, filter_of, exact, gs.rows.ids.p, gs.rows.dist.p, true, st));
+        }
+        timed_pass(timer, st, pass);
+    });
 }
 
 RerankScratch& next_rerank_scratch(cph_index* h) {
@@ -6964,6 +6981,7 @@ struct GroupedSearch {
     uint64_t k, g, C;
     static constexpr PassKind kind = kPassGrouped;
     static constexpr bool keyed = true;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "grouped";
     uint64_t tokens() const { return 1; }
     void check_shape() const {
@@ -7024,6 +7042,7 @@ struct DiverseSearch {
     uint64_t C;
     static constexpr PassKind kind = kPassDiverse;
     static constexpr bool keyed = false;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "diverse";
     uint64_t tokens() const { return 1; }
     void check_shape() const { check_diverse_shape(k, C, lam); }
@@ -7098,6 +7117,7 @@ struct MaxsimSearch {
     uint64_t k, C;
     static constexpr PassKind kind = kPassMaxsim;
     static constexpr bool keyed = true;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "maxsim";
     uint64_t tokens() const { return T; }
     void check_shape() const { check_maxsim_shape(T, C, k); }
@@ -7259,6 +7279,7 @@ struct MaxsimRescoredSearch {
     const int32_t* filter_of;
     static constexpr PassKind kind = kPassUntimed;       // (the scan kernel alone is timed, inside the pass)
     static constexpr bool keyed = true;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "maxsim";
     uint64_t tokens() const { return T; }
     void check_shape() const { check_maxsim_rescore_shape(T, C, k, R); }
@@ -7282,6 +7303,98 @@ struct MaxsimRescoredSearch {
         send_rescore_tables(h, gs, r, n_tokens, filters, F, filter_of, n, st, rt);
         maxsim_rows(maxsim_args(gs.rows.ids.p, gs.rows.dist.p, rt.d_tokens, T, C, R, d_key_of, h->size(), nullptr, cand), (uint32_t)n, h->device, st);
         pad_rescore_tokens(h, r, gs.pad, d_queries, n * T, st);
+        const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, gs.pad, c, rt, T, R, k, o);
+        timed_pass(h->pass_timer[kPassMaxsimRescore], st, [&] { maxsim_rescore_scan(a, (uint32_t)n, st); });
+        maxsim_rescore_select(a, (uint32_t)n, st);
+    }
+};
+
+// ---- exhaustive maxsim: matrix-core lower bounds over every key, then the rescoring stage (device_maxsim_all.h) ----
+// The eps, pack, bounds and select kernels over n queries whose padded token rows are in `p`, chunk after chunk on `st`; the
+// candidates go to `c` in the layout the rescoring stage reads.  full_table (the hook): [n][n_keys], every chunk's table is
+// copied there.  The caller holds the handle mutex and has set the device.
+void enqueue_maxsim_all(cph_index* h, Reserve& r, RerankScratch::All& w, const KeyRows& kr, const RerankScratch::Padded& p,
+                        int32_t* cand_keys, float* cand_lb, int32_t* cand_found, const RescoreTables& t, const int32_t* d_tokens,
+                        uint64_t n, uint64_t T, uint64_t R, uint32_t* full_table, hipStream_t st) {
+    if (h->size() > kMxMaxCandidates) throw InvalidArg("exhaustive maxsim search: the index holds too many rows");
+    const uint32_t D = h->L.D;
+    const MaxsimAllPlan pl = plan_maxsim_all(kr.size, kr.n_keys, n, (uint32_t)T, h->num_cus,
+                                             h->maxsim_all_table_bytes ? h->maxsim_all_table_bytes : h->exact_scratch_bytes);
+    const uint64_t rows = n * T, prow = n * pl.Tp;
+    MaxsimAllArgs a{};
+    a.t.raw = h->d_raw.p;
+    a.t.norm_sq = h->d_norm.p;
+    a.t.qpad = r(w.qp, prow * D);
+    a.t.qnorm = r(w.qn, prow);
+    a.t.ids = kr.ids.p;
+    a.t.D = D;
+    a.eps = r(w.eps, prow);
+    a.csr = KeyRowsDev{kr.ids.p, kr.keys.p, kr.offsets.p, kr.n_keys};
+    a.part = pl.part;
+    a.n_tokens = d_tokens;
+    a.filter_of = t.d_filter_of;
+    a.bitmaps = t.d_bitmaps;
+    a.unfiltered = t.unfiltered;
+    a.T = (uint32_t)T;
+    a.Tp = pl.Tp;
+    a.n = (uint32_t)n;
+    a.unbounded = r(w.unbounded, n);
+    a.table = r(w.table, (size_t)pl.chunk * kr.n_keys);
+    a.R = (uint32_t)R;
+    a.cand_keys = cand_keys;
+    a.cand_lb = cand_lb;
+    a.cand_found = cand_found;
+    r(w.eps_raw, rows);
+    r(w.flags, rows);
+    const uint32_t* d_bn = matrix_bn_max(h, st);
+    hipLaunchKernelGGL(exact_mfma_query_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, (const float*)p.qnorm.p, d_bn, D,
+                       (uint32_t)rows, w.eps_raw.p, w.flags.p);
+    HIP_CHECK(hipGetLastError());
+    maxsim_all_pack(p.qpad.p, p.qnorm.p, w.eps_raw.p, w.flags.p, a, w.qp.p, w.qn.p, w.eps.p, st);
+    for (uint64_t q0 = 0; q0 < n; q0 += pl.chunk) {
+        a.q_first = (uint32_t)q0;
+        a.q_count = (uint32_t)std::min<uint64_t>(pl.chunk, n - q0);
+        timed_pass(h->pass_timer[kPassMaxsimAll], st, [&] { maxsim_all_bounds(a, pl.P, st); });      // (the last chunk's stays)
+        maxsim_all_select(a, st);
+        if (full_table)
+            HIP_CHECK(hipMemcpyAsync(full_table + q0 * kr.n_keys, a.table, (size_t)a.q_count * kr.n_keys * 4, hipMemcpyDeviceToDevice, st));
+    }
+}
+
+// No underlying search: the candidates are the R smallest bounds over ALL keys.  `exact` has nothing to select.
+struct MaxsimAllSearch {
+    uint64_t T;
+    const int32_t* n_tokens;
+    uint64_t k, R;
+    const cph_group_keys* keys_obj;
+    const cph_filter* const* filters;
+    uint32_t F;
+    const int32_t* filter_of;
+    static constexpr uint64_t C = 1;
+    static constexpr PassKind kind = kPassUntimed;
+    static constexpr bool keyed = true;
+    static constexpr bool searches_rows = false;            // (no underlying search: the pass makes its own candidates)
+    static constexpr const char* name = "maxsim";
+    uint64_t tokens() const { return T; }
+    void check_shape() const { check_maxsim_rescore_shape(T, C, k, R); }
+    void check_batch(uint64_t n) const { check_maxsim_rescore_batch(n, T, R); }
+    void check_inputs(uint64_t n) const { check_maxsim_tokens(n_tokens, n, T); }
+    void check_on(const cph_index*, uint32_t) const {}
+    void stage(RerankScratch&, uint64_t, hipStream_t) const {}
+    RerankOuts outs(int32_t* keys, float* score, int32_t* hits, int64_t* rows, int32_t* found, int32_t* certified) const {
+        return {{{keys, 4 * k}, {score, 4 * k}, {hits, 4 * k}, {rows, 8 * k * T}, {found, 4}, {certified, 4}}, 6};
+    }
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t* d_key_of, const float* d_queries, const RerankOuts& o,
+              hipStream_t st) const {
+        const KeyRows& kr = key_rows(h, keys_obj, d_key_of);
+        Reserve r = gs.reserve();
+        RerankScratch::Cand& c = gs.cand;
+        const size_t nr = n * R;
+        r(c.keys, nr), r(c.lb, nr), r(c.found, n), r(c.score, nr), r(c.rows, nr * T);
+        RescoreTables rt;
+        send_rescore_tables(h, gs, r, n_tokens, filters, F, filter_of, n, st, rt);
+        pad_rescore_tokens(h, r, gs.pad, d_queries, n * T, st);
+        enqueue_maxsim_all(h, r, gs.all, kr, gs.pad, c.keys.p, c.lb.p, c.found.p, rt, rt.d_tokens, n, T, R, nullptr, st);
         const MaxsimRescoreArgs a = maxsim_rescore_args(h, kr, gs.pad, c, rt, T, R, k, o);
         timed_pass(h->pass_timer[kPassMaxsimRescore], st, [&] { maxsim_rescore_scan(a, (uint32_t)n, st); });
         maxsim_rescore_select(a, (uint32_t)n, st);
@@ -7374,6 +7487,7 @@ struct FusedSearch {
     uint64_t k, C;
     static constexpr PassKind kind = kPassUntimed;       // (the scan kernel alone is timed, inside the pass)
     static constexpr bool keyed = false;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "fused";
     uint64_t tokens() const { return T; }
     void check_shape() const { check_fused_shape(T, C, k); }
@@ -7414,6 +7528,15 @@ template <class Rerank>
 void rerank_locked(cph_index* h, RerankScratch& gs, const Rerank& f, const RerankCall& c, const float* d_queries, const int32_t* d_key_of,
                    const RerankOuts& o, hipStream_t st) {
     const uint64_t T = f.tokens();
+    if constexpr (!Rerank::searches_rows) {
+        // no candidate rows: the checks the underlying search would make, then the pass alone
+        for (uint32_t j = 0; j < c.F; ++j) {
+            if (!c.filters[j]) throw InvalidArg("null filter in the filter list");
+            check_filter(h, c.filters[j]);
+        }
+        if (c.filter_of) check_filter_of(c.filter_of, c.n, c.F);
+        return behind_set_event(gs, st, [&] { f.pass(h, gs, c.n, d_key_of, d_queries, o, st); });
+    }
     std::vector<int32_t> token_filter;
     if (c.filter_of && T > 1) {
         token_filter.resize(c.n * T);
@@ -7922,6 +8045,112 @@ int cph_host_key_rows(const int32_t* keys, uint64_t n, uint32_t* out_ids, int32_
     });
 }
 
+// ---- exhaustive multi-vector search: bounds over every key, then the rescoring stage (host_maxsim_all.h) ----
+int cph_search_maxsim_all(cph_index* h, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                          uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                          const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits, int64_t* out_rows,
+                          int32_t* out_found, int32_t* out_certified) {
+    return guarded([&] {
+        const MaxsimAllSearch f{tokens, n_tokens, k, rescore, keys, filters, n_filters, filter_of};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0,
+                             f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified)}, keys);
+    });
+}
+
+int cph_search_maxsim_all_device(cph_index* h, const float* d_queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                 uint64_t rescore, const cph_group_keys* keys, const cph_filter* const* filters, uint32_t n_filters,
+                                 const int32_t* filter_of, int exact, int32_t* d_keys, float* d_score, int32_t* d_hits, int64_t* d_rows,
+                                 int32_t* d_found, int32_t* d_certified, void* stream) {
+    return guarded([&] {
+        const MaxsimAllSearch f{tokens, n_tokens, k, rescore, keys, filters, n_filters, filter_of};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_keys, d_score, d_hits, d_rows, d_found, d_certified)},
+                      keys, &stream);
+    });
+}
+
+int cph_multi_search_maxsim_all(cph_multi* m, const float* queries, uint64_t n, uint64_t tokens, const int32_t* n_tokens, uint64_t k,
+                                uint64_t rescore, const cph_group_keys* const* keys, const cph_filter* const* filters, uint32_t n_filters,
+                                const int32_t* filter_of, int exact, int32_t* out_keys, float* out_score, int32_t* out_hits,
+                                int64_t* out_rows, int32_t* out_found, int32_t* out_certified) {
+    return guarded([&] {
+        const MaxsimAllSearch f{tokens, n_tokens, k, rescore, nullptr, filters, n_filters, filter_of};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0,
+                            f.outs(out_keys, out_score, out_hits, out_rows, out_found, out_certified)},
+                     keys, [&](cph_index* h, const RerankCall& s, const cph_group_keys* key, uint64_t lo) {
+            return cph_search_maxsim_all(h, s.q, s.n, tokens, n_tokens ? n_tokens + lo : nullptr, k, rescore, key, s.filters, s.F, s.filter_of,
+                                         s.exact ? 1 : 0, s.out.at<int32_t>(0), s.out.at<float>(1), s.out.at<int32_t>(2), s.out.at<int64_t>(3),
+                                         s.out.at<int32_t>(4), s.out.at<int32_t>(5));
+        });
+    });
+}
+
+int cph_debug_time_maxsim_all(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassMaxsimAll, on != 0); });
+}
+
+int cph_debug_last_maxsim_all_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassMaxsimAll, us); });
+}
+
+int cph_debug_maxsim_all_budget(cph_index* h, uint64_t bytes) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->maxsim_all_table_bytes = (size_t)bytes;
+    });
+}
+
+int cph_host_maxsim_all_term(float m_hat, float eps, float* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        *out = maxsim_all_term(m_hat, eps);
+    });
+}
+
+int cph_maxsim_all_hook(cph_index* h, const float* tokens, uint64_t n, uint64_t n_tok, const int32_t* n_tokens, const cph_group_keys* keys,
+                        const uint32_t* allow, uint64_t rescore, float* out_lb_table, int32_t* out_cand_keys, float* out_cand_lb,
+                        int32_t* out_cand_found) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        refuse_ip(h, "maxsim search");
+        require_finalized(h);
+        const uint64_t T = n_tok, R = rescore;
+        if (!tokens || n < 1) throw InvalidArg("null argument");
+        check_maxsim_rescore_shape(T, 1, 1, R);
+        check_maxsim_rescore_batch(n, T, R);
+        check_maxsim_tokens(n_tokens, n, T);
+        const int32_t* d_key_of = group_key_column(h, keys);
+        h->use_device();
+        const KeyRows& kr = key_rows(h, keys, d_key_of);
+        const RerankOuts o = {{{out_lb_table, 4 * (size_t)kr.n_keys}, {out_cand_keys, 4 * R}, {out_cand_lb, 4 * R}, {out_cand_found, 4}}, 4};
+        if (!o.all()) throw InvalidArg("null argument");
+        const uint64_t rows = n * T, nw = (h->size() + 31) / 32;
+        RerankScratch::Padded pad;
+        RerankScratch::All all;
+        const DevBuf<int32_t> d_tok = uploaded(n_tokens, n);
+        const DevBuf<float> d_q = uploaded(tokens, rows * h->dim);
+        const DevBuf<uint32_t> d_allow = uploaded(allow, n * nw);
+        std::vector<uint64_t> ptrs(n);
+        std::vector<int32_t> of(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            ptrs[i] = reinterpret_cast<uint64_t>(d_allow.p + i * nw);
+            of[i] = (int32_t)i;
+        }
+        const DevBuf<uint64_t> d_ptrs = uploaded(allow ? ptrs.data() : nullptr, n);
+        const DevBuf<int32_t> d_of = uploaded(allow ? of.data() : nullptr, n);
+        RescoreTables rt;
+        if (allow) rt.d_filter_of = d_of.p;
+        if (allow) rt.d_bitmaps = reinterpret_cast<const uint32_t* const*>(d_ptrs.p);
+        PoisonedOuts po(o, n);
+        Reserve fresh{nullptr, false};
+        pad_rescore_tokens(h, fresh, pad, d_q.p, rows, nullptr);
+        enqueue_maxsim_all(h, fresh, all, kr, pad, po.dev.at<int32_t>(1), po.dev.at<float>(2), po.dev.at<int32_t>(3), rt,
+                           n_tokens ? d_tok.p : nullptr, n, T, R, po.dev.at<uint32_t>(0), nullptr);
+        po.download();
+    });
+}
+
 // ---- fused search: several query vectors per query, exact weighted-sum top-k (host_fused.h) ----
 int cph_search_fused(cph_index* h, const float* queries, uint64_t n, uint64_t vectors, const int32_t* n_vectors, const float* weights,
                      uint64_t k, uint64_t candidates, const cph_filter* const* filters, uint32_t n_filters, const int32_t* filter_of,
@@ -8113,6 +8342,7 @@ struct RescoredSearch {
     bool host_form;
     static constexpr PassKind kind = kPassRescored;
     static constexpr bool keyed = false;
+    static constexpr bool searches_rows = true;
     static constexpr const char* name = "rescored";
     uint64_t tokens() const { return 1; }
     void check_shape() const { check_rescore_shape(k, C); }

@@ -1555,6 +1555,42 @@ int cph_host_rescore_rows(const int64_t* ids, const float* dist, uint64_t n, uin
 int cph_host_rescore_rows_in(const float* rows_in, uint64_t n, uint64_t dim_full, int dtype, const uint32_t* row_map, uint64_t n_map,
                              void* stored, float* norms, uint64_t* bad, uint64_t* first_bad);
 
+/* ---- Exhaustive rescored search: the true full-width top-k over every row of an int8 object -------------------------------
+ * cph_search_rescored without a first stage and without `candidates`: for every query the k best rows (1 <= k <= 1024) by
+ * (score, internal id) ascending over EVERY allowed row of `vectors` -- the query's filter AND not removed -- the score
+ * having, byte for byte, the value the two-stage call writes for that (query, row) pair (csrc/device_rescore_i8.h states it).
+ * `vectors` must be a CPH_RESCORE_INT8 object: its score is made of two integer dot products, exact in any order, which
+ * v_mfma_i32_32x32x32_i8 computes (csrc/device_rescore_i8_all.h: a pack kernel, the matrix-core scan over (query tiles of
+ * 128) x (row parts) with per-(part, query) top-k pools in scratch, a select kernel that folds the parts); a float16 or
+ * float32 object is refused.  `first` is FLT_MAX in every slot; fewer than k allowed rows: -1 / FLT_MAX / FLT_MAX; a query
+ * whose largest |q_i| is NaN or Inf gets a row of padding; ids are input rows under cph_set_result_ids.  `queries`
+ * [n][cph_dim] is checked like any batch and otherwise unused; `exact` is ignored.  Scratch stays within the budget of the
+ * exact engine (CPH_EXACT_SCRATCH_MB): a batch is cut into launches of whole query tiles.  A stale object, the inner-product
+ * metric and partitioned indexes are refused as for cph_search_rescored.  The _device form only enqueues.
+ * cph_multi_search_rescored_all shards the queries over the replicas; vectors[r] is replica r's object.
+ * cph_debug_time_rescored_all / cph_debug_last_rescored_all_us: the scan kernel of a call's last launch between two events.
+ * cph_rescore_all_hook runs the three kernels on full queries [n][dim_full of the object] under per-query allow bitmaps
+ * [n][ceil(size / 32)] (NULL: every id; removed rows are NOT masked here) with `parts` row parts (0: the plan's); the device
+ * outputs start as 0xA5 bytes.  cph_host_plan_rescore_all (no HIP call) is the plan: out[5] = {parts, rows per part, queries
+ * per launch, pool words per (part, query), scratch bytes of a launch}. */
+int cph_search_rescored_all(cph_index* h, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                            const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first);
+int cph_search_rescored_all_device(cph_index* h, const float* d_queries, uint64_t n, const float* d_full_queries, uint64_t dim_full,
+                                   uint64_t k, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                                   const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, float* d_first, void* stream);
+int cph_multi_search_rescored_all(cph_multi* m, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                                  const cph_rescore_vectors* const* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                                  const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first);
+int cph_debug_time_rescored_all(cph_index* h, int on);
+int cph_debug_last_rescored_all_us(cph_index* h, double* us);
+int cph_rescore_all_hook(cph_index* h, const float* full_queries, uint64_t n, const cph_rescore_vectors* vectors, const uint32_t* allow,
+                         uint64_t k, uint64_t parts, int64_t* out_ids, float* out_score, float* out_first);
+int cph_host_plan_rescore_all(uint64_t size, uint64_t n, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t* out);
+/* The measurement script's yardstick for the scan's compute floor: a bare loop of `iters` x 8 independent
+ * v_mfma_i32_32x32x32_i8 per wave, two workgroups of four waves per CU, timed warm between two HIP events -> int8 MACs/s. */
+int cph_debug_mfma_i8_rate(cph_index* h, uint64_t iters, double* macs_per_s);
+
 #ifdef __cplusplus
 }
 #endif

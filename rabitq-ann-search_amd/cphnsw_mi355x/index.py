@@ -2172,6 +2172,15 @@ class CPIndex:
         cap = self.RESCORE_MAX_CANDIDATES
         if k < 1:
             raise ValueError("search_rescored needs k >= 1")
+        if isinstance(candidates, str):                  # "all": no first stage, no candidate rows -> C is None
+            if candidates != "all":
+                raise ValueError('candidates must be an integer, None or "all"')
+            if vectors.dtype != "int8":
+                raise ValueError('candidates="all" needs dtype="int8" rescore vectors: the sum shape the float dtypes '
+                                 "prescribe is not the matrix pipe's")
+            if k > cap:
+                raise ValueError(f'search_rescored needs k <= {cap} with candidates="all"')
+            return k, None, self._filters_arg(filter, filter_of, n)
         if candidates is None:
             if k > cap:
                 raise ValueError(f"search_rescored needs k <= {cap} (the longest candidate row)")
@@ -2201,7 +2210,14 @@ class CPIndex:
         `candidates=C` (k <= C <= 1024); None takes C = min(1024, max(64, 4 * k)): a policy, not a measured optimum, in
         ONE pass.  A multi-device index shards the queries like search_batch; the bytes are those of one device.  A
         partitioned index is refused (use part(i).search_rescored), an inner-product index too: search a cosine or L2
-        index and give the object metric="ip"."""
+        index and give the object metric="ip".
+        `candidates="all"` (dtype="int8" objects only; 1 <= k <= 1024) drops the first stage: the answer is the true
+        full-width top-k, the k best by (score, internal id) over EVERY allowed row of the object (the query's filter AND
+        not removed), each score byte for byte what the two-stage call writes for that pair -- the two integer dot
+        products of the int8 statement come from the matrix cores (v_mfma_i32_32x32x32_i8), which changes no bit.
+        `first` is FLT_MAX in every slot; `exact` is ignored; `queries` [n, dim] is validated and otherwise unused.  Use it
+        as the answer, as ground truth for tuning C, or where a filter is so selective that the narrow graph runs dry.  A
+        float16 or float32 object is refused with "all": the sum shape they prescribe is not the matrix pipe's."""
         q = _as_f32(queries)
         if full_queries is None:
             fq = q
@@ -2219,6 +2235,9 @@ class CPIndex:
                 q, k, vectors, full_queries=fq, candidates=candidates, filter=f, exact=exact, filter_of=fo))
         n = q.shape[0]
         k, C_, filters = self._rescored_args(n, k, vectors, candidates, filter, filter_of)
+        if C_ is None:
+            return self._rerank_host("rescored_all", q, (fq.ctypes.data if n else None, fq.shape[1], k), vectors, filters, exact,
+                                     self._rescored_table(n, k))
         return self._rerank_host("rescored", q, (fq.ctypes.data if n else None, fq.shape[1], k, C_), vectors, filters, exact,
                                  self._rescored_table(n, k))
 
@@ -2256,7 +2275,8 @@ class CPIndex:
                 filter_of=fo))
         n = queries.shape[0]
         k, C_, filters = self._rescored_args(n, k, vectors, candidates, filter, filter_of)
-        return tuple(self._rerank_device("rescored", queries, (fq.data_ptr() if n else None, fq.shape[1], k, C_), vectors, filters, exact,
+        name, lead = ("rescored", (k, C_)) if C_ is not None else ("rescored_all", (k,))
+        return tuple(self._rerank_device(name, queries, (fq.data_ptr() if n else None, fq.shape[1]) + lead, vectors, filters, exact,
                                          self._rescored_table(n, k), out, stream,
                                          ("out must be the three tensors (ids, score, first)",
                                           "out must be contiguous (n, k) int64 / float32 / float32 tensors on the queries' device")))
@@ -2270,6 +2290,16 @@ class CPIndex:
         """Device time (HIP events, microseconds) of the rescoring kernel of the last rescored search made under
         time_rescored() on the given replica; waits for that launch."""
         return self._last_pass_us("cph_debug_last_rescored_us", replica)
+
+    def time_rescored_all(self, on=True):
+        """Debug hook of the measurement script: while on, the scan kernel (rescore_i8_all_scan_kernel) of every
+        search_rescored(..., candidates="all") -- of its last launch -- is bracketed by HIP events."""
+        self._time_pass("cph_debug_time_rescored_all", on)
+
+    def last_rescored_all_us(self, replica=0):
+        """Device time (HIP events, microseconds) of the scan kernel of the last exhaustive rescored search made under
+        time_rescored_all() on the given replica; waits for it."""
+        return self._last_pass_us("cph_debug_last_rescored_all_us", replica)
 
     # -- removed rows (not in the reference) ---------------------------------------------------
     def _id_space(self, ids):

@@ -50,6 +50,7 @@
 #include "device_fused.h"
 #include "device_rescore.h"
 #include "device_rescore_i8.h"
+#include "device_rescore_i8_all.h"
 #include "device_normalize.h"
 #include "device_ip.h"
 #include "host_index.h"
@@ -240,6 +241,13 @@ struct RerankScratch {
         DevBuf<float> eps_raw, qp, qn, eps;
         DevBuf<uint32_t> flags, unbounded, table;
     } all;
+    // exhaustive rescored search (device_rescore_i8_all.h): the query planes, sq, qn and ok flags of the padded batch, the
+    // (part, query) pools of one launch and their counts
+    struct RescoreAll {
+        DevBuf<uint32_t> hq, lq, ok, counts;
+        DevBuf<float> sq, qn;
+        DevBuf<unsigned long long> pools;
+    } rall;
     Reserve reserve() const { return Reserve{rows.ev, rows.used}; }      // growing: the set's previous batch must be done
 };
 
@@ -258,7 +266,8 @@ constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the 
 // inside that search's pass; the pass as a whole goes by kPassUntimed, a timer nothing switches on.  kPassRescored: the
 // rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
 // same way.  kPassMaxsimAll: the bounds kernel of the last chunk of an exhaustive maxsim search (device_maxsim_all.h).
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassMaxsimAll, kPassUntimed, kPassKinds };
+// kPassRescoredAll: the scan kernel of the last launch of an exhaustive rescored search (device_rescore_i8_all.h).
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassMaxsimAll, kPassRescoredAll, kPassUntimed, kPassKinds };
 
 // The facet dictionary of one column (cph_facet_*; device_facets.h): its distinct values ascending, on both sides, and one
 // 32-bit code per row -- per CSR entry for a tag column -- on the device.  Made on first use, dropped when the column changes.
@@ -700,6 +709,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed tag pass has run on this handle (cph_debug_time_tag_filters)",
     "no timed facet pass has run on this handle (cph_debug_time_facets)",
     "no timed exhaustive maxsim search has run on this handle (cph_debug_time_maxsim_all)",
+    "no timed exhaustive rescored search has run on this handle (cph_debug_time_rescored_all)",
     "this pass is not timed",
 };
 
@@ -2118,7 +2128,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 120; }
+int cph_version(void) { return 121; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -8367,6 +8377,100 @@ struct RescoredSearch {
     }
 };
 
+// ---- exhaustive rescored search: every row of an int8 object on the matrix cores (device_rescore_i8_all.h) ----
+void check_rescore_all_object(const cph_rescore_vectors* rv) {
+    if (!rv->i8)
+        throw InvalidArg("an exhaustive rescored search (candidates = all) needs CPH_RESCORE_INT8 rescore vectors: the sum shape the "
+                         "float dtypes prescribe is not the matrix pipe's");
+}
+
+void check_rescore_all_shape(uint64_t k) {
+    if (k < 1 || k > kRescoreAllMaxK)
+        throw InvalidArg("an exhaustive rescored search supports 1 <= k <= " + std::to_string(kRescoreAllMaxK) + ", got " + std::to_string(k));
+}
+
+// The pack, scan and select kernels over n full queries at d_fq against every row of `rv`, launch after launch on `st`.
+// t: the queries' bitmaps (filter AND not removed).  parts: a forced part count, 0: the plan's.  The caller holds the handle
+// mutex and has set the device.
+void enqueue_rescore_all(cph_index* h, Reserve& r, RerankScratch::RescoreAll& w, const cph_rescore_vectors* rv, const float* d_fq,
+                         const RescoreTables& t, uint64_t n, uint64_t k, uint32_t parts, const RerankOuts& o, hipStream_t st) {
+    const RescoreAllPlan pl = plan_rescore_all(rv->size, n, (uint32_t)k, h->num_cus, h->exact_scratch_bytes, parts);
+    const uint64_t n_pad = (n + kRescoreAllTile - 1) / kRescoreAllTile * kRescoreAllTile;
+    RescoreAllArgs a{};
+    a.s = rescore_store(rv);
+    a.scales = rv->scales.p;
+    a.fq = d_fq;
+    a.n = (uint32_t)n;
+    a.n_pad = (uint32_t)n_pad;
+    a.Kq = rescore_all_kpad(rv->L.stride);
+    a.hq = r(w.hq, n_pad * a.Kq / 4);
+    a.lq = r(w.lq, n_pad * a.Kq / 4);
+    a.sq = r(w.sq, n_pad);
+    a.qn = r(w.qn, n_pad);
+    a.ok = r(w.ok, n_pad);
+    a.filter_of = t.d_filter_of;
+    a.bitmaps = t.d_bitmaps;
+    a.unfiltered = t.unfiltered;
+    a.ip = rv->ip ? 1 : 0;
+    a.k = (uint32_t)k;
+    a.C = pl.C;
+    a.P = pl.P;
+    a.part = pl.part;
+    a.pools = r(w.pools, pl.pool_keys);
+    a.counts = r(w.counts, (size_t)pl.P * pl.tile_q);
+    a.rows = h->ids_input ? h->d_rows.p : nullptr;
+    a.out_ids = o.at<int64_t>(0);
+    a.out_score = o.at<float>(1);
+    a.out_first = o.at<float>(2);
+    rescore_i8_all_pack(a, st);
+    for (uint64_t q0 = 0; q0 < n; q0 += pl.tile_q) {
+        a.q_first = (uint32_t)q0;
+        a.q_count = (uint32_t)std::min<uint64_t>(pl.tile_q, n - q0);
+        if (rv->size == 0) a.P = 0;                       // (nothing to scan: the select writes padding)
+        else timed_pass(h->pass_timer[kPassRescoredAll], st, [&] { rescore_i8_all_scan(a, h->device, st); });     // (the last launch's stays)
+        rescore_i8_all_select(a, st);
+    }
+}
+
+// No underlying search: the narrow queries are checked like any batch and otherwise unused.  `exact` has nothing to select.
+struct RescoredAllSearch {
+    uint64_t k;
+    const cph_rescore_vectors* const* vectors;
+    const float* full_q;
+    uint64_t dim_full;
+    bool host_form;
+    const cph_filter* const* filters;
+    uint32_t F;
+    const int32_t* filter_of;
+    static constexpr uint64_t C = 1;
+    static constexpr PassKind kind = kPassUntimed;       // (the scan kernel alone is timed, inside the pass)
+    static constexpr bool keyed = false;
+    static constexpr bool searches_rows = false;
+    static constexpr const char* name = "rescored";
+    uint64_t tokens() const { return 1; }
+    void check_shape() const { check_rescore_all_shape(k); }
+    void check_batch(uint64_t n) const { check_batch_size(n); }
+    void check_inputs(uint64_t) const {
+        if (!full_q) throw InvalidArg("null argument");
+    }
+    void check_on(const cph_index* h, uint32_t r) const {
+        const RescoredSearch two_stage{k, k, vectors, full_q, dim_full, host_form};
+        two_stage.check_on(h, r);
+        check_rescore_all_object(vectors[r]);
+    }
+    void stage(RerankScratch& gs, uint64_t n, hipStream_t st) const {
+        const size_t floats = (size_t)n * dim_full;
+        HIP_CHECK(hipMemcpyAsync(gs.reserve()(gs.host.fq, floats), full_q, floats * 4, hipMemcpyHostToDevice, st));
+    }
+    RerankOuts outs(int64_t* ids, float* score, float* first) const { return {{{ids, 8 * k}, {score, 4 * k}, {first, 4 * k}}, 3}; }
+    void pass(cph_index* h, RerankScratch& gs, uint64_t n, const int32_t*, const float*, const RerankOuts& o, hipStream_t st) const {
+        Reserve r = gs.reserve();
+        RescoreTables rt;
+        send_rescore_tables(h, gs, r, nullptr, filters, F, filter_of, n, st, rt);
+        enqueue_rescore_all(h, r, gs.rall, vectors[0], host_form ? gs.host.fq.p : full_q, rt, n, k, 0, o, st);
+    }
+};
+
 void check_rescore_rows_args(const int64_t* ids, const float* dist, uint64_t n, uint64_t C, const float* fq, uint64_t k, const RerankOuts& o) {
     if (!ids || !dist || !fq || !o.all()) throw InvalidArg("null argument");
     check_rescore_shape(k, C);
@@ -8541,6 +8645,125 @@ int cph_debug_time_rescored(cph_index* h, int on) {
 
 int cph_debug_last_rescored_us(cph_index* h, double* us) {
     return guarded([&] { pass_timer_us(h, kPassRescored, us); });
+}
+
+// ---- exhaustive rescored search: no first stage, every row of an int8 object (device_rescore_i8_all.h) ----
+int cph_search_rescored_all(cph_index* h, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                            const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                            const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first) {
+    return guarded([&] {
+        const RescoredAllSearch f{k, vectors ? &vectors : nullptr, full_queries, dim_full, true, filters, n_filters, filter_of};
+        rerank_search(h, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, first)}, nullptr);
+    });
+}
+
+int cph_search_rescored_all_device(cph_index* h, const float* d_queries, uint64_t n, const float* d_full_queries, uint64_t dim_full,
+                                   uint64_t k, const cph_rescore_vectors* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                                   const int32_t* filter_of, int exact, int64_t* d_ids, float* d_score, float* d_first, void* stream) {
+    return guarded([&] {
+        const RescoredAllSearch f{k, vectors ? &vectors : nullptr, d_full_queries, dim_full, false, filters, n_filters, filter_of};
+        rerank_search(h, f, {d_queries, n, filters, n_filters, filter_of, exact != 0, f.outs(d_ids, d_score, d_first)}, nullptr, &stream);
+    });
+}
+
+int cph_multi_search_rescored_all(cph_multi* m, const float* queries, uint64_t n, const float* full_queries, uint64_t dim_full, uint64_t k,
+                                  const cph_rescore_vectors* const* vectors, const cph_filter* const* filters, uint32_t n_filters,
+                                  const int32_t* filter_of, int exact, int64_t* ids, float* score, float* first) {
+    return guarded([&] {
+        if (m && vectors)
+            for (size_t r = 0; r < m->reps.size(); ++r)
+                if (!vectors[r]) throw InvalidArg("a rescored multi-device search needs one rescore vectors object per replica");
+        const RescoredAllSearch f{k, vectors, full_queries, dim_full, true, filters, n_filters, filter_of};
+        rerank_multi(m, f, {queries, n, filters, n_filters, filter_of, exact != 0, f.outs(ids, score, first)}, nullptr,
+                     [&](cph_index* h, const RerankCall& s, const cph_group_keys*, uint64_t lo) {
+            uint32_t r = 0;
+            while (m->reps[r] != h) ++r;
+            return cph_search_rescored_all(h, s.q, s.n, full_queries + lo * dim_full, dim_full, k, vectors[r], s.filters, s.F, s.filter_of,
+                                           s.exact ? 1 : 0, s.out.at<int64_t>(0), s.out.at<float>(1), s.out.at<float>(2));
+        });
+    });
+}
+
+int cph_debug_time_rescored_all(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassRescoredAll, on != 0); });
+}
+
+int cph_debug_last_rescored_all_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassRescoredAll, us); });
+}
+
+int cph_rescore_all_hook(cph_index* h, const float* full_queries, uint64_t n, const cph_rescore_vectors* vectors, const uint32_t* allow,
+                         uint64_t k, uint64_t parts, int64_t* out_ids, float* out_score, float* out_first) {
+    return guarded([&] {
+        if (!h) throw InvalidArg("null handle");
+        std::lock_guard<std::mutex> lk(h->mu);
+        require_finalized(h);
+        check_rescore_vectors(h, vectors);
+        check_rescore_all_object(vectors);
+        check_rescore_all_shape(k);
+        const RerankOuts o = RescoredAllSearch{k, &vectors, full_queries, vectors->dim, true, nullptr, 0, nullptr}.outs(out_ids, out_score, out_first);
+        if (!full_queries || !o.all()) throw InvalidArg("null argument");
+        if (n < 1 || n > 0x7FFFFFFFull || parts > kRescoreAllMaxParts) throw InvalidArg("rescore all: sizes out of range");
+        h->use_device();
+        const uint64_t nw = (h->size() + 31) / 32;
+        const DevBuf<float> d_fq = uploaded(full_queries, n * vectors->dim);
+        const DevBuf<uint32_t> d_allow = uploaded(allow, n * nw);
+        std::vector<uint64_t> ptrs(n);
+        std::vector<int32_t> of(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            ptrs[i] = reinterpret_cast<uint64_t>(d_allow.p + i * nw);
+            of[i] = (int32_t)i;
+        }
+        const DevBuf<uint64_t> d_ptrs = uploaded(allow ? ptrs.data() : nullptr, n);
+        const DevBuf<int32_t> d_of = uploaded(allow ? of.data() : nullptr, n);
+        RescoreTables rt;
+        if (allow) rt.d_filter_of = d_of.p;
+        if (allow) rt.d_bitmaps = reinterpret_cast<const uint32_t* const*>(d_ptrs.p);
+        RerankScratch::RescoreAll w;
+        PoisonedOuts po(o, n);
+        Reserve fresh{nullptr, false};
+        enqueue_rescore_all(h, fresh, w, vectors, d_fq.p, rt, n, k, (uint32_t)parts, po.dev, nullptr);
+        po.download();
+    });
+}
+
+int cph_debug_mfma_i8_rate(cph_index* h, uint64_t iters, double* macs_per_s) {
+    return guarded([&] {
+        if (!h || !macs_per_s) throw InvalidArg("null argument");
+        if (iters < 1 || iters > 0xFFFFFFull) throw InvalidArg("mfma rate: iters out of range");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->use_device();
+        const uint32_t grid = (uint32_t)std::max(1, h->num_cus) * 2;
+        DevBuf<int> d_out((size_t)grid * kRescoreThreads);
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        float ms = 0.0f;
+        for (int rep = 0; rep < 2; ++rep) {               // (the second launch is the warm one)
+            HIP_CHECK(hipEventRecord(e0, nullptr));
+            hipLaunchKernelGGL(rescore_all_mfma_rate_kernel, dim3(grid), dim3(kRescoreThreads), 0, nullptr, (uint32_t)iters, d_out.p);
+            HIP_CHECK(hipEventRecord(e1, nullptr));
+            HIP_CHECK(hipEventSynchronize(e1));
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        *macs_per_s = (double)grid * 4.0 * (double)iters * 8.0 * 32768.0 / ((double)ms * 1e-3);      // 32 x 32 x 32 MACs an instruction
+    });
+}
+
+int cph_host_plan_rescore_all(uint64_t size, uint64_t n, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t* out) {
+    return guarded([&] {
+        if (!out) throw InvalidArg("null argument");
+        check_rescore_all_shape(k);
+        if (size > 0xFFFFFFFEull || n > 0x7FFFFFFFull) throw InvalidArg("rescore all: sizes out of range");
+        const RescoreAllPlan pl = plan_rescore_all(size, n, (uint32_t)k, num_cus, scratch_bytes);
+        out[0] = pl.P;
+        out[1] = pl.part;
+        out[2] = pl.tile_q;
+        out[3] = pl.C;
+        out[4] = pl.pool_keys * 8;
+    });
 }
 
 int cph_rescore_rows_hook(cph_index* h, const int64_t* ids, const float* dist, uint64_t n, uint64_t candidates, const float* full_queries,

@@ -82,6 +82,43 @@ __device__ __forceinline__ int rescore_i8_dot16(const uint4& x, const uint4& y, 
 // An integer below 2^53 in magnitude as the nearest float: exact in double, then one rounding.
 __device__ __forceinline__ float rescore_i8_to_float(long long v) { return __double2float_rn(__ll2double_rn(v)); }
 
+// ---- the query side of the statement, shared with the exhaustive scan's pack kernel (device_rescore_i8_all.h) ----
+// The largest |q_i| by bit pattern over this wave's share of the query: thread tid of T takes i = tid, tid + T, ...
+__device__ __forceinline__ uint32_t rescore_i8_query_max(const float* __restrict__ fq, uint32_t dim, uint32_t tid) {
+    uint32_t qbits = 0;
+    for (uint32_t i = tid; i < dim; i += kRescoreThreads) qbits = max(qbits, rescore_i8_abs_bits(fq[i]));
+    return rescore_i8_fold_max(qbits, 64);
+}
+
+// The codes t of coordinates 4 i .. 4 i + 3 (0 behind dim, or where the query is not live: qmax zero, NaN or Inf) as one
+// dword per plane; t2 += their squares.
+__device__ __forceinline__ void rescore_i8_plane_words(const float* __restrict__ fq, uint32_t i, uint32_t dim, bool live, float sq,
+                                                       uint32_t& hw, uint32_t& lw, unsigned long long& t2) {
+    hw = 0;
+    lw = 0;
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+        const uint32_t c = 4 * i + e;
+        const int t = (live && c < dim) ? rescore_i8_code(fq[c], sq, kRescoreI8QueryMax) : 0;
+        const int h = (t + 64) >> 7, l = t - 128 * h;
+        hw |= ((uint32_t)h & 0xFFu) << (8 * e);
+        lw |= ((uint32_t)l & 0xFFu) << (8 * e);
+        t2 += (unsigned long long)(uint32_t)(t * t);
+    }
+}
+
+__device__ __forceinline__ float rescore_i8_query_norm(float sq, unsigned long long T2) {
+    return __fmul_rn(__fmul_rn(sq, sq), rescore_i8_to_float((long long)T2));
+}
+
+// The score of one pair from its integer dot I = 128 H + L: every float operation rounded on its own.
+__device__ __forceinline__ float rescore_i8_score(long long I, float scale, float sq, float qn, float xn, bool ip) {
+    const float dot = __fmul_rn(__fmul_rn(scale, sq), rescore_i8_to_float(I));
+    if (ip) return __fsub_rn(0.0f, dot);
+    const float v = __fsub_rn(__fadd_rn(qn, xn), __fmul_rn(2.0f, dot));
+    return (v < 0.0f) ? 0.0f : v;
+}
+
 // Grid n, kRescoreThreads threads; LDS: rescore_i8_lds_bytes(C, s.padded).
 __global__ __launch_bounds__(kRescoreThreads) void rescore_i8_kernel(RescoreI8Args args) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -103,9 +140,7 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_i8_kernel(RescoreI8Ar
     const float* __restrict__ fq = a.fq + q * dim;
 
     // qmax: the largest |q_i| by bit pattern
-    uint32_t qbits = 0;
-    for (uint32_t i = tid; i < dim; i += kRescoreThreads) qbits = max(qbits, rescore_i8_abs_bits(fq[i]));
-    qbits = rescore_i8_fold_max(qbits, 64);
+    uint32_t qbits = rescore_i8_query_max(fq, dim, tid);
     if (lane == 0) red[wave] = qbits;
     for (uint32_t s = tid; s < H; s += kRescoreThreads) id_table_clear(tab_id, tab_pos, s);
     for (uint32_t j = tid; j < P2; j += kRescoreThreads) w[j] = kSortNone;
@@ -118,16 +153,8 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_i8_kernel(RescoreI8Ar
     // the two planes and T2; the candidates: an id's first position in the row
     unsigned long long t2 = 0;
     for (uint32_t i = tid; i < padded / 4; i += kRescoreThreads) {
-        uint32_t hw = 0, lw = 0;
-#pragma unroll
-        for (uint32_t e = 0; e < 4; ++e) {
-            const uint32_t c = 4 * i + e;
-            const int t = (q_ok && qbits != 0 && c < dim) ? rescore_i8_code(fq[c], sq, kRescoreI8QueryMax) : 0;
-            const int h = (t + 64) >> 7, l = t - 128 * h;
-            hw |= ((uint32_t)h & 0xFFu) << (8 * e);
-            lw |= ((uint32_t)l & 0xFFu) << (8 * e);
-            t2 += (unsigned long long)(uint32_t)(t * t);
-        }
+        uint32_t hw, lw;
+        rescore_i8_plane_words(fq, i, dim, q_ok && qbits != 0, sq, hw, lw, t2);
         hq[i] = hw;
         lq[i] = lw;
     }
@@ -147,7 +174,7 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_i8_kernel(RescoreI8Ar
         if (tab_pos[id_table_find(tab_id, H, id)] != j) c_id[j] = kNoId;      // a repeat
     }
     const unsigned long long T2 = red[4] + red[5] + red[6] + red[7];
-    const float qn = __fmul_rn(__fmul_rn(sq, sq), rescore_i8_to_float((long long)T2));
+    const float qn = rescore_i8_query_norm(sq, T2);
     __syncthreads();
 
     const uint4* __restrict__ hq4 = reinterpret_cast<const uint4*>(hq);
@@ -194,14 +221,7 @@ __global__ __launch_bounds__(kRescoreThreads) void rescore_i8_kernel(RescoreI8Ar
         for (uint32_t u = 0; u < kRescoreI8Unroll; ++u) {
             if (sub != 0 || id[u] == kNoId) continue;
             const long long I = 128ll * (long long)ph[u] + (long long)pl[u];
-            const float dot = __fmul_rn(__fmul_rn(args.scales[id[u]], sq), rescore_i8_to_float(I));
-            float score;
-            if (a.ip) {
-                score = __fsub_rn(0.0f, dot);
-            } else {
-                const float v = __fsub_rn(__fadd_rn(qn, a.s.norms[id[u]]), __fmul_rn(2.0f, dot));
-                score = (v < 0.0f) ? 0.0f : v;
-            }
+            const float score = rescore_i8_score(I, args.scales[id[u]], sq, qn, a.ip ? 0.0f : a.s.norms[id[u]], a.ip != 0);
             if (score == score) w[base + u * groups + grp] = ((unsigned long long)orderable(score) << 32) | id[u];
         }
     }

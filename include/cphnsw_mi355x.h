@@ -225,27 +225,36 @@ int cph_search_batch_exact_device(cph_index* h, const float* d_queries, uint64_t
  * the multi form): a filter that allows at most max_allowed ids (and a k <= 1024) takes the exact path.  Default 0: never,
  * every call does what it did before. */
 int cph_set_exact_threshold(cph_index* h, uint64_t max_allowed);
-/* Engine of every exact scan that serves one filter or none (cph_search_batch_exact*, the cut-over above, and the grouped,
+/* Engine of every exact scan (cph_search_batch_exact*, the cut-over above, batches with per-query filters, and the grouped,
  * diverse, MaxSim, fused and rescored searches that ride on them).  0 (default): the fp32 VALU scan, launch for launch what
  * it was.  1: the matrix cores (v_mfma_f32_32x32x2_f32) discard every candidate that provably cannot be in a query's top-k
  * -- approximate distance beyond the k-th smallest seen plus twice the slack below -- and the VALU arithmetic re-scores the
  * survivors; a query that cannot be certified (its survivors overflow a pool, or a number is not finite) is answered by the
  * VALU scan behind it on the same stream.  Every output byte equals engine 0's.  Any other value: CPH_INVALID_ARGUMENT.
- * The scan of a batch with per-query filters and the tail scan do not change.  The exact range search under engine 1: see
- * "range search" below.
- * cph_last_matrix_stats: out[0] = parts of the candidate list, out[1] = ids re-scored (summed over the queries), out[2] =
+ * A batch with per-query filters: every scanned segment (one filter's ids, or every id, with its queries) of at least 64
+ * queries and at most 2^32 - 128 candidates takes the grouped matrix kernels, the others stay in the grouped VALU scan of the
+ * same call.  The tail scan does not change.  The exact range search under engine 1: see "range search" below.
+ * cph_last_matrix_stats: out[0] = parts of the candidate list (per-query filters: the most of any segment), out[1] = ids re-scored (summed over the queries), out[2] =
  * queries the VALU scan answered, of the last batch (or exact range search) if engine 1 ran it; zeros otherwise.
  * cph_host_exact_matrix_slack: the slack, a bound on |approximate - exact distance| for a query of squared norm qnorm
  * against rows of squared norm <= bn_max at padded dimension D (the statement the device uses).
  * cph_host_exact_matrix_plan: how engine 1 cuts a batch (host only; the argument checks of cph_host_exact_plan): out[0] = Kp,
  * the power of two >= max(k, 64), out[1] = C = 2 Kp keys per pool, out[2] = queries per launch, out[3] = P parts of the
  * candidate list, out[4] = candidates per part (a multiple of 128), out[5] = pool keys = P x queries per launch x C.
+ * cph_host_exact_matrix_groups_plan: how engine 1 cuts the segments of a batch with per-query filters that take the matrix
+ * kernels (host only; arguments, item rows and checks of cph_host_exact_group_plan, a segment of at most 2^32 - 128 candidates):
+ * items[i] = {segment, part, c_lo, c_hi, q_lo, q_cnt, pool, launch}, one (segment, tile of <= 128 queries, part of whole
+ * 128-candidate tiles) each, the pool of (item, query q_lo + j) being pool + j inside its launch; out[0] = items, out[1] =
+ * launches, out[2] = 128, out[3] = C, out[4] = scratch bytes of the largest launch (pools, counts and the certify kernel's
+ * pool and count per query, C x 8 + 4 bytes each), out[5] = the most parts of any segment.
  * cph_debug_matrix_bn_max: the bn_max engine 1 holds for the handle's index state (rows and added rows), after waiting for
  * the handle's work; read-only, launches nothing.  CPH_INVALID_ARGUMENT while no engine-1 batch has run on that state. */
 int cph_set_exact_engine(cph_index* h, int engine);
 int cph_last_matrix_stats(cph_index* h, uint64_t out[3]);
 int cph_host_exact_matrix_slack(float qnorm, float bn_max, uint32_t D, float* out);
 int cph_host_exact_matrix_plan(uint64_t candidates, uint64_t n_queries, uint64_t k, int num_cus, uint64_t scratch_bytes, uint64_t out[6]);
+int cph_host_exact_matrix_groups_plan(const uint64_t* seg_candidates, const uint64_t* seg_queries, uint32_t n_segments, uint64_t k,
+                                      int num_cus, uint64_t scratch_bytes, uint32_t* items, uint64_t cap_items, uint64_t* out);
 int cph_debug_matrix_bn_max(cph_index* h, float* out);
 
 /* ---- range search ----------------------------------------------------------------------- */

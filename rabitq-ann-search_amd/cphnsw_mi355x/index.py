@@ -2576,8 +2576,9 @@ class CPIndex:
 
     @property
     def exact_engine(self):
-        """Engine of every exact scan that serves one filter or none (exact=True, the exact_threshold route, and the
-        grouped, diverse, MaxSim, fused and rescored searches on top of them).  "vector" (default): the fp32 VALU scan.
+        """Engine of every exact scan (exact=True, the exact_threshold route, and the grouped, diverse, MaxSim, fused and
+        rescored searches on top of them; with one filter, none, or per-query filters -- filter_of= / label= -- where every
+        scanned segment of at least 64 queries takes it).  "vector" (default): the fp32 VALU scan.
         "matrix": the matrix cores discard every candidate that provably cannot be in the top-k and the vector
         arithmetic re-scores the survivors -- the same bytes, ids and order.  After a matrix batch last_search_stats()
         also reports matrix_parts, matrix_survivors and matrix_redo.  range_search(exact=True) with one filter or none

@@ -39,6 +39,7 @@
 #include "device_filter_ops.h"
 #include "device_exact.h"
 #include "device_exact_mfma.h"
+#include "device_exact_mfma_groups.h"
 #include "device_range.h"
 #include "device_range_mfma.h"
 #include "device_tail.h"
@@ -386,6 +387,7 @@ struct cph_index {
     // cph_set_exact_engine: 0 the vector scan, 1 the matrix prefilter.  d_bn_max: the largest norm_sq of the rows (as bits),
     // made on first use for the index state (index_epoch, size()) it is valid for; bn_ev follows the kernel that made it
     int exact_engine = 0;
+    uint32_t mx_group_min = kMxGroupMinQueries;   // queries from which a segment of a per-query call takes the matrix kernels (CPH_MATRIX_GROUP_MIN at creation: the sweep's knob)
     size_t maxsim_all_table_bytes = 0; // cph_debug_maxsim_all_budget: the bound table of an exhaustive maxsim chunk, at most (0: exact_scratch_bytes)
     DevBuf<uint32_t> d_bn_max;
     uint64_t bn_epoch = ~0ull, bn_rows = 0;
@@ -1639,6 +1641,26 @@ const uint32_t* matrix_bn_max(cph_index* h, hipStream_t st) {
     return h->d_bn_max.p;
 }
 
+// What the certify kernels of a set's matrix batch share (device_exact_mfma.h: mx_certify_query).
+MatrixCertifyCommon matrix_certify_common(const cph_index* h, BatchSet& s, uint32_t k, uint32_t C, const uint32_t* rows, int64_t* d_ids,
+                                          float* d_dist) {
+    MatrixCertifyCommon c{};
+    c.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, kExactQT, 0);
+    c.eps = s.mx_eps.p;
+    c.k = k;
+    c.C = C;
+    c.pools = s.x_pools.p;
+    c.counts = s.x_counts.p;
+    c.rpools = s.mx_rpools.p;
+    c.rcounts = s.mx_rcounts.p;
+    c.flags = s.mx_flags.p;
+    c.stats = s.d_stats.p;
+    c.rows = rows;
+    c.out_ids = d_ids;
+    c.out_dist = d_dist;
+    return c;
+}
+
 // enqueue_exact under the matrix engine (device_exact_mfma.h): per launch of tile_q queries the prefilter and the certify
 // kernel; behind all of them the vector engine's plan over the whole batch, in the wrapper kernels that serve flagged
 // queries only.  Nothing here waits for the device.
@@ -1698,24 +1720,12 @@ void enqueue_exact_matrix(cph_index* h, BatchSet& s, const float* d_raw_q, uint3
     a.counts = s.x_counts.p;
     a.flags = s.mx_flags.p;
     MatrixCertifyArgs c{};
-    c.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, kExactQT, 0);
-    c.eps = s.mx_eps.p;
+    c.c = matrix_certify_common(h, s, k, mp.C, rows, d_ids, d_dist);
     c.P = mp.P;
-    c.k = k;
-    c.C = mp.C;
-    c.pools = s.x_pools.p;
-    c.counts = s.x_counts.p;
-    c.rpools = s.mx_rpools.p;
-    c.rcounts = s.mx_rcounts.p;
-    c.flags = s.mx_flags.p;
-    c.stats = s.d_stats.p;
-    c.rows = rows;
-    c.out_ids = d_ids;
-    c.out_dist = d_dist;
     for (uint32_t q0 = 0; q0 < nq; q0 += mp.tile_q) {
         const uint32_t q_count = std::min(mp.tile_q, nq - q0);
-        a.q_first = c.s.q_first = q0;
-        a.q_count = c.s.q_count = q_count;
+        a.q_first = c.c.s.q_first = q0;
+        a.q_count = c.c.s.q_count = q_count;
         const dim3 grid(mp.P, (q_count + kMxTile - 1) / kMxTile);
         if (d_list) hipLaunchKernelGGL(exact_mfma_prefilter_kernel<true>, grid, dim3(256), (size_t)mp.C * 8 * 4, st, a);
         else hipLaunchKernelGGL(exact_mfma_prefilter_kernel<false>, grid, dim3(256), (size_t)mp.C * 8 * 4, st, a);
@@ -1860,6 +1870,62 @@ bool filters_batch_has_work(cph_index* h, const cph_filter* const* filters, uint
     return true;
 }
 
+// The matrix segments of a batch with per-query filters (device_exact_mfma_groups.h), behind pad_queries: scan rows
+// [0, nqm).  eps and flags of those rows; per launch of the matrix plan the grouped prefilter over its items and the grouped
+// certify kernel over its rows; behind all of them the grouped vector plan `fp` over the same segments in the wrappers that
+// serve flagged queries only (fl_q: the rows of its launches).  The tables are device addresses inside the call's blob.
+struct MatrixGroupTables { const uint8_t *items, *desc, *fitems, *fdesc; };
+
+void enqueue_matrix_groups(cph_index* h, BatchSet& s, const MatrixGroupPlan& mp, const ExactGroupPlan& fp, const std::vector<uint32_t>& fl_q,
+                           uint32_t nqm, uint32_t k, const uint32_t* d_bn, const MatrixGroupTables& t, const uint32_t* d_rows, int64_t* d_ids,
+                           float* d_dist, hipStream_t st) {
+    const uint32_t D = h->L.D, C = mp.g.C;
+    hipLaunchKernelGGL(exact_mfma_query_kernel, dim3((nqm + 255) / 256), dim3(256), 0, st, (const float*)s.x_qnorm.p, d_bn, D, nqm,
+                       s.mx_eps.p, s.mx_flags.p);
+    HIP_CHECK(hipGetLastError());
+    MatrixGroupArgs a{};
+    a.raw = h->d_raw.p;
+    a.norm_sq = h->d_norm.p;
+    a.qpad = s.x_qpad.p;
+    a.qnorm = s.x_qnorm.p;
+    a.eps = s.mx_eps.p;
+    a.D = D;
+    a.k = k;
+    a.C = C;
+    a.pools = s.x_pools.p;
+    a.counts = s.x_counts.p;
+    a.flags = s.mx_flags.p;
+    MatrixCertifyGroupArgs c{};
+    c.c = matrix_certify_common(h, s, k, C, d_rows, d_ids, d_dist);
+    uint32_t row0 = 0;
+    for (size_t l = 0; l < mp.launch_rows.size(); ++l) {
+        a.items = reinterpret_cast<const MatrixItem*>(t.items) + mp.g.launch_items[l];
+        hipLaunchKernelGGL(exact_mfma_prefilter_groups_kernel, dim3(mp.g.launch_items[l + 1] - mp.g.launch_items[l]), dim3(256),
+                           (size_t)C * 8 * 4, st, a);
+        HIP_CHECK(hipGetLastError());
+        c.c.s.q_first = row0;
+        c.desc = reinterpret_cast<const uint4*>(t.desc) + row0;
+        CPH_LAUNCH_SCAN(exact_mfma_certify_groups_kernel, D, dim3(mp.launch_rows[l]), (size_t)C * 12 + 2 * kExactQT * 4, st, c);
+        row0 += mp.launch_rows[l];
+    }
+    ExactGroupFlaggedArgs f{};
+    f.a.s = scan_common(h, s.x_qpad.p, s.x_qnorm.p, fp.gq, 0);
+    f.a.k = k;
+    f.a.C = C;
+    f.a.pools = s.x_pools.p;
+    f.a.counts = s.x_counts.p;
+    f.flags = s.mx_flags.p;
+    for (size_t l = 0; l < fp.launch_pools.size(); ++l) {
+        f.a.items = reinterpret_cast<const ExactItem*>(t.fitems) + fp.launch_items[l];
+        CPH_LAUNCH_SCAN(exact_scan_groups_flagged_kernel, D, dim3(fp.launch_items[l + 1] - fp.launch_items[l]), (size_t)C * 8 + (size_t)fp.gq * 8, st, f);
+        hipLaunchKernelGGL(exact_merge_groups_flagged_kernel, dim3(fl_q[2 * l + 1] - fl_q[2 * l]), dim3(64), (size_t)C * 8, st,
+                           (const unsigned long long*)s.x_pools.p, (const uint32_t*)s.x_counts.p,
+                           reinterpret_cast<const uint4*>(t.fdesc) + fl_q[2 * l], k, C, d_rows, (const uint32_t*)s.mx_flags.p + fl_q[2 * l],
+                           s.d_stats.p, d_ids, d_dist);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
 // A batch with per-query filters in the place of enqueue_search / enqueue_exact: d_raw_q = [nq][dim] raw queries in HBM,
 // results into device buffers, everything enqueued on `st`.  Per route (FilterGroups): padded rows are filled, scanned
 // queries of ALL filters share one pad launch and one scan + merge launch pair per scratch budget (device_exact.h: the
@@ -1878,21 +1944,40 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
     std::vector<uint32_t> seg_group, seg_first;
     uint32_t nqs = 0, n_pad = 0, n_gf = 0, n_gp = 0;
     unsigned long long n_exact = 0;
-    for (uint32_t f = 0; f <= F; ++f) {
-        const uint32_t cnt = g.seg[f + 1] - g.seg[f];
-        if (!cnt) continue;
-        if (g.route[f] == kRoutePad) n_pad += cnt;
-        else if (g.route[f] == kRouteGraph) (f < F ? n_gf : n_gp) += cnt;
-        else {
+    // Under the matrix engine the segments that take the matrix kernels (device_exact_mfma_groups.h) come first -- scan rows
+    // [0, nqm), segments [0, n_mseg) -- so that the rows of either plan are consecutive; the vector engine makes one pass.
+    const bool matrix = h->exact_engine == 1;
+    uint32_t n_mseg = 0, nqm = 0;
+    for (int pass = matrix ? 0 : 1; pass < 2; ++pass) {
+        for (uint32_t f = 0; f <= F; ++f) {
+            const uint32_t cnt = g.seg[f + 1] - g.seg[f];
+            if (!cnt) continue;
+            if (g.route[f] != kRouteScan) {
+                if (pass == 0) continue;
+                if (g.route[f] == kRoutePad) n_pad += cnt;
+                else (f < F ? n_gf : n_gp) += cnt;
+                continue;
+            }
+            const uint64_t m = f < F ? g.pop[f] : h->size();
+            if (matrix && (cnt >= h->mx_group_min && m <= kMxMaxCandidates) != (pass == 0)) continue;
             seg_group.push_back(f);
-            seg_m.push_back(f < F ? g.pop[f] : h->size());
+            seg_m.push_back(m);
             seg_q.push_back(cnt);
             seg_first.push_back(nqs);
             nqs += cnt;
-            n_exact += (unsigned long long)cnt * seg_m.back();
+            n_exact += (unsigned long long)cnt * m;
         }
+        if (pass == 0) { n_mseg = (uint32_t)seg_m.size(); nqm = nqs; }
     }
-    const ExactGroupPlan pl = plan_exact_groups(seg_m.data(), seg_q.data(), (uint32_t)seg_m.size(), k, h->num_cus, h->exact_scratch_bytes);
+    const uint32_t n_seg = (uint32_t)seg_m.size();
+    const ExactGroupPlan pl = plan_exact_groups(seg_m.data() + n_mseg, seg_q.data() + n_mseg, n_seg - n_mseg, k, h->num_cus, h->exact_scratch_bytes);
+    // the matrix segments: their plan, and the grouped vector plan over them that serves the flagged queries
+    MatrixGroupPlan mp;
+    ExactGroupPlan fp;
+    if (n_mseg) {
+        mp = plan_exact_matrix_groups(seg_m.data(), seg_q.data(), n_mseg, k, h->num_cus, h->exact_scratch_bytes);
+        fp = plan_exact_groups(seg_m.data(), seg_q.data(), n_mseg, k, h->num_cus, h->exact_scratch_bytes);
+    }
     const uint32_t nq_pad = nqs ? (nqs + kExactQT - 1) / kExactQT * kExactQT + kExactQT : 0;   // (a group's last tile reads up to 7 rows behind it)
     // the call's tables, one blob
     size_t need = 0;
@@ -1900,10 +1985,16 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
                  o_scanq = table_take(need, (size_t)nqs * 4), o_pad = table_take(need, (size_t)n_pad * 4),
                  o_gf = table_take(need, (size_t)n_gf * 4), o_gp = table_take(need, (size_t)n_gp * 4),
                  o_fof = table_take(need, n_gf ? (size_t)nq * 4 : 0), o_tab = table_take(need, n_gf ? (size_t)F * 8 : 0);
+    size_t o_mitems = 0, o_fitems = 0, o_fdesc = 0;
+    if (n_mseg) {
+        o_mitems = table_take(need, mp.g.items.size() * sizeof(MatrixItem));
+        o_fitems = table_take(need, fp.items.size() * sizeof(ExactItem));
+        o_fdesc = table_take(need, (size_t)nqm * 16);
+    }
     need = std::max<size_t>(need, 16);
     Reserve r{s.ev_done, s.used};                                 // growing: the old buffers must be idle (one wait)
     uint8_t* const tb = s.tab.begin(need, r);
-    const size_t pools = (size_t)pl.max_pools;
+    const size_t pools = std::max<size_t>({pl.max_pools, mp.g.max_pools, fp.max_pools});
     r(s.x_qpad, (size_t)nq_pad * D);
     r(s.x_qnorm, nq_pad);
     r(s.x_pools, pools * pl.C);
@@ -1912,10 +2003,17 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
     r(s.d_status, nq);
     r(s.d_redo, nq);
     r(s.d_redo2, nq);
+    if (n_mseg) {
+        r(s.mx_eps, nqm);
+        r(s.mx_flags, nqm);
+        r(s.mx_rpools, (size_t)mp.max_rows * pl.C);
+        r(s.mx_rcounts, mp.max_rows);
+    }
     // every scanned filter's id list: made once (filter_id_list), the stream waits for it
     std::vector<const uint32_t*> seg_ids(seg_m.size(), nullptr);
     for (size_t i = 0; i < seg_m.size(); ++i)
         if (seg_group[i] < F) seg_ids[i] = filter_id_list(filters[seg_group[i]], st);
+    const uint32_t* d_bn = n_mseg ? matrix_bn_max(h, st) : nullptr;
     ExactItem* items = reinterpret_cast<ExactItem*>(tb + o_items);
     uint4* desc = reinterpret_cast<uint4*>(tb + o_desc);
     uint32_t* scanq = reinterpret_cast<uint32_t*>(tb + o_scanq);
@@ -1923,16 +2021,28 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
              *gp = reinterpret_cast<uint32_t*>(tb + o_gp);
     for (size_t i = 0; i < seg_m.size(); ++i)
         std::memcpy(scanq + seg_first[i], g.perm.data() + g.seg[seg_group[i]], (size_t)seg_q[i] * 4);
+    // A plan over segments [seg0, ..) -> its device items, the descriptors of its rows, the scan positions every launch merges
+    // (l_q[2 l], l_q[2 l + 1]).  MatrixItem and ExactItem state the same seven words.
+    auto write_plan = [&](const ExactGroupPlan& p, uint32_t seg0, auto* out, uint4* dsc) {
+        std::vector<uint32_t> l_q(2 * p.launch_pools.size());
+        for (size_t l = 0; l < p.launch_pools.size(); ++l) { l_q[2 * l] = 0xFFFFFFFFu; l_q[2 * l + 1] = 0; }
+        for (size_t i = 0; i < p.items.size(); ++i) {
+            const ExactGroupItem& it = p.items[i];
+            const uint32_t row0 = seg_first[seg0 + it.seg] + it.q_lo;
+            out[i] = {seg_ids[seg0 + it.seg], it.c_lo, it.c_hi, row0, it.q_cnt, it.pool, 0u};
+            if (it.part != 0) continue;
+            for (uint32_t j = 0; j < it.q_cnt; ++j) dsc[row0 + j] = make_uint4(it.pool + j, it.q_cnt, p.seg_parts[it.seg], scanq[row0 + j]);
+            l_q[2 * it.launch] = std::min(l_q[2 * it.launch], row0);
+            l_q[2 * it.launch + 1] = std::max(l_q[2 * it.launch + 1], row0 + it.q_cnt);
+        }
+        return l_q;
+    };
     const size_t n_launch = pl.launch_pools.size();
-    std::vector<uint32_t> l_qlo(n_launch, 0xFFFFFFFFu), l_qhi(n_launch, 0);       // scan positions every launch merges
-    for (size_t i = 0; i < pl.items.size(); ++i) {
-        const ExactGroupItem& it = pl.items[i];
-        const uint32_t row0 = seg_first[it.seg] + it.q_lo;
-        items[i] = ExactItem{seg_ids[it.seg], it.c_lo, it.c_hi, row0, it.q_cnt, it.pool, 0u};
-        if (it.part != 0) continue;
-        for (uint32_t j = 0; j < it.q_cnt; ++j) desc[row0 + j] = make_uint4(it.pool + j, it.q_cnt, pl.seg_parts[it.seg], scanq[row0 + j]);
-        l_qlo[it.launch] = std::min(l_qlo[it.launch], row0);
-        l_qhi[it.launch] = std::max(l_qhi[it.launch], row0 + it.q_cnt);
+    const std::vector<uint32_t> l_q = write_plan(pl, n_mseg, items, desc);
+    std::vector<uint32_t> fl_q;                 // (the matrix plan's descriptors are rows [0, nqm) of desc, the vector plan's the rest)
+    if (n_mseg) {
+        (void)write_plan(mp.g, 0, reinterpret_cast<MatrixItem*>(tb + o_mitems), desc);   // (its launches' rows follow each other)
+        fl_q = write_plan(fp, 0, reinterpret_cast<ExactItem*>(tb + o_fitems), reinterpret_cast<uint4*>(tb + o_fdesc));
     }
     {
         uint32_t a_pad = 0, a_gf = 0, a_gp = 0;
@@ -1963,12 +2073,15 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
         a.C = pl.C;
         a.pools = s.x_pools.p;
         a.counts = s.x_counts.p;
+        if (n_mseg)
+            enqueue_matrix_groups(h, s, mp, fp, fl_q, nqm, k, d_bn, MatrixGroupTables{dt + o_mitems, dt + o_desc, dt + o_fitems, dt + o_fdesc},
+                                  d_rows, d_ids, d_dist, st);
         for (size_t l = 0; l < n_launch; ++l) {
             a.items = reinterpret_cast<const ExactItem*>(dt + o_items) + pl.launch_items[l];
             CPH_LAUNCH_SCAN(exact_scan_groups_kernel, D, dim3(pl.launch_items[l + 1] - pl.launch_items[l]), (size_t)pl.C * 8 + (size_t)pl.gq * 8, st, a);
-            hipLaunchKernelGGL(exact_merge_groups_kernel, dim3(l_qhi[l] - l_qlo[l]), dim3(64), (size_t)pl.C * 8, st,
+            hipLaunchKernelGGL(exact_merge_groups_kernel, dim3(l_q[2 * l + 1] - l_q[2 * l]), dim3(64), (size_t)pl.C * 8, st,
                                (const unsigned long long*)s.x_pools.p, (const uint32_t*)s.x_counts.p,
-                               reinterpret_cast<const uint4*>(dt + o_desc) + l_qlo[l], k, pl.C, d_rows, d_ids, d_dist);
+                               reinterpret_cast<const uint4*>(dt + o_desc) + l_q[2 * l], k, pl.C, d_rows, d_ids, d_dist);
             HIP_CHECK(hipGetLastError());
         }
     }
@@ -2019,7 +2132,7 @@ void enqueue_filters(cph_index* h, BatchSet& s, const float* d_raw_q, uint32_t n
         }
     }
     s.nq = nq;
-    finish_batch(h, s, st);
+    finish_batch(h, s, st, mp.max_parts);
 }
 
 // The host form's I/O around `enqueue(d_q, d_ids, d_dist)`: the queries up (unless nothing will read them), result rows in
@@ -2158,6 +2271,7 @@ int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
         if (const char* e = getenv("CPH_QUERY_ORDER")) h->order_queries = atoi(e) != 0;
         if (const char* e = getenv("CPH_LEADER_SLOTS")) h->coal.n_slots = std::max(1, std::min(kLeaderSlots, atoi(e)));
         if (const char* e = getenv("CPH_EXACT_SCRATCH_MB")) h->exact_scratch_bytes = (size_t)std::max(1, atoi(e)) << 20;
+        if (const char* e = getenv("CPH_MATRIX_GROUP_MIN")) h->mx_group_min = (uint32_t)std::max(1, atoi(e));
         if (const char* e = getenv("CPH_GATHER_US")) h->coal.gather_us = std::max(0, atoi(e));
         if (const char* e = getenv("CPH_WAVES_PER_CU")) { h->waves_per_cu = (uint32_t)std::max(1, atoi(e)); h->waves_from_env = true; }
         *out = h;
@@ -3048,6 +3162,24 @@ int cph_host_exact_matrix_plan(uint64_t candidates, uint64_t n_queries, uint64_t
             throw InvalidArg("exact plan: sizes out of range");
         const MatrixPlan mp = plan_exact_matrix(candidates, (uint32_t)n_queries, (uint32_t)k, num_cus, (size_t)scratch_bytes);
         out[0] = mp.Kp; out[1] = mp.C; out[2] = mp.tile_q; out[3] = mp.P; out[4] = mp.part; out[5] = (uint64_t)mp.pool_keys;
+    });
+}
+
+int cph_host_exact_matrix_groups_plan(const uint64_t* seg_candidates, const uint64_t* seg_queries, uint32_t n_segments, uint64_t k,
+                                      int num_cus, uint64_t scratch_bytes, uint32_t* items, uint64_t cap_items, uint64_t* out) {
+    return guarded([&] {
+        if (!out || (n_segments && (!seg_candidates || !seg_queries)) || (cap_items && !items)) throw InvalidArg("null argument");
+        if (k == 0 || k > kExactMaxK) throw InvalidArg("exact plan: sizes out of range");
+        for (uint32_t s = 0; s < n_segments; ++s)
+            if (seg_candidates[s] > kMxMaxCandidates || seg_queries[s] > 0xFFFFFFFFull) throw InvalidArg("exact plan: sizes out of range");
+        const MatrixGroupPlan mp = plan_exact_matrix_groups(seg_candidates, seg_queries, n_segments, (uint32_t)k, num_cus, (size_t)scratch_bytes);
+        out[0] = mp.g.items.size(); out[1] = mp.launch_rows.size(); out[2] = mp.g.gq; out[3] = mp.g.C;
+        out[4] = mp.max_bytes; out[5] = mp.max_parts;
+        for (size_t i = 0; i < mp.g.items.size() && i < cap_items; ++i) {
+            const ExactGroupItem& it = mp.g.items[i];
+            const uint32_t row[8] = {it.seg, it.part, it.c_lo, it.c_hi, it.q_lo, it.q_cnt, it.pool, it.launch};
+            std::memcpy(items + i * 8, row, sizeof(row));
+        }
     });
 }
 

@@ -605,14 +605,18 @@ __global__ __launch_bounds__(256, 1) void exact_mfma_prefilter_kernel(MatrixArgs
 }
 
 // ---- 2. certify and re-score --------------------------------------------------------------------------------------------------
-struct MatrixCertifyArgs {
-    ScanCommon s;                 // (gq, part: unused)
+// One query certified by one wave: the pools of its P parts (part p's is pool index first + p * stride) folded under the keep
+// rule, the survivors through THE candidate loop into the query's one re-score pool (index ql of rpools / rcounts), the row
+// to out row `out_row`.  q: the query's padded row (and its index in eps and flags).  LDS: C keys + 2 x kExactQT words (the
+// ExactPoolSink of a group of kExactQT), C ids.  Shared by the certify kernels of the plain and the grouped scan.
+struct MatrixCertifyCommon {
+    ScanCommon s;                 // (gq, part, q_first, q_count: unused here)
     const float* eps;             // [nq]
-    uint32_t P, k, C;
-    const unsigned long long* pools;   // [P][q_count][C]   the prefilter's
-    const uint32_t* counts;            // [P][q_count]
-    unsigned long long* rpools;   // [q_count][C]      the re-score's: one list per query
-    uint32_t* rcounts;            // [q_count]
+    uint32_t k, C;
+    const unsigned long long* pools;   // the prefilter's
+    const uint32_t* counts;
+    unsigned long long* rpools;   // [queries of the launch][C]      the re-score's: one list per query
+    uint32_t* rcounts;            // [queries of the launch]
     uint32_t* flags;              // [nq]
     unsigned long long* stats;
     const uint32_t* rows;         // the row map, or null
@@ -620,12 +624,10 @@ struct MatrixCertifyArgs {
     float* out_dist;
 };
 
-// One wave per query of the launch.  LDS: C keys + 2 x kExactQT words (the ExactPoolSink of a group of kExactQT), C ids.
 template <int SD, int CH>
-__global__ __launch_bounds__(64) void exact_mfma_certify_kernel(MatrixCertifyArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
+__device__ __forceinline__ void mx_certify_query(const MatrixCertifyCommon& a, size_t first, uint32_t stride, uint32_t P, uint32_t ql,
+                                                 uint32_t q, size_t out_row, unsigned char* smem) {
     const int lane = threadIdx.x;
-    const uint32_t ql = blockIdx.x, q = a.s.q_first + ql;
     const uint32_t D = SD ? (uint32_t)SD : a.s.D;
     if (a.flags[q]) return;                                       // (only this wave ever flags q from here on)
     unsigned long long* sm = reinterpret_cast<unsigned long long*>(smem);
@@ -633,8 +635,8 @@ __global__ __launch_bounds__(64) void exact_mfma_certify_kernel(MatrixCertifyArg
     const float eps2 = 2.0f * a.eps[q];
     // the fold: every part's keys past the running limit into one pool of C keys, cut by the keep rule when it is full
     uint32_t cnt = 0, lim = kMxInfBits;
-    for (uint32_t p = 0; p < a.P; ++p) {
-        const size_t pi = (size_t)p * a.s.q_count + ql;
+    for (uint32_t p = 0; p < P; ++p) {
+        const size_t pi = first + (size_t)p * stride;
         const uint32_t np = a.counts[pi];
         const unsigned long long* pool = a.pools + pi * a.C;
         for (uint32_t base = 0; base < np; base += 64) {
@@ -667,7 +669,20 @@ __global__ __launch_bounds__(64) void exact_mfma_certify_kernel(MatrixCertifyArg
                                   ExactPoolSink(smem, kExactQT, a.rpools + (size_t)ql * a.C, a.rcounts + ql, a.k, a.C));
     __threadfence();
     __syncthreads();
-    exact_merge_query(a.rpools, a.rcounts, ql, 1u, 1u, a.k, a.C, a.rows, a.out_ids, a.out_dist, q, smem);
+    exact_merge_query(a.rpools, a.rcounts, ql, 1u, 1u, a.k, a.C, a.rows, a.out_ids, a.out_dist, out_row, smem);
+}
+
+struct MatrixCertifyArgs {
+    MatrixCertifyCommon c;        // (c.s.q_first, c.s.q_count: the queries of this launch; pools [P][q_count][C], counts [P][q_count])
+    uint32_t P;
+};
+
+// One wave per query of the launch.
+template <int SD, int CH>
+__global__ __launch_bounds__(64) void exact_mfma_certify_kernel(MatrixCertifyArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t ql = blockIdx.x, q = a.c.s.q_first + ql;
+    mx_certify_query<SD, CH>(a.c, ql, a.c.s.q_count, a.P, ql, q, q, smem);
 }
 
 // ---- 3. the fallback: the vector engine's scan and merge, for flagged queries only ---------------------------------------------

@@ -1600,6 +1600,42 @@ int cph_host_plan_rescore_all(uint64_t size, uint64_t n, uint64_t k, int num_cus
  * v_mfma_i32_32x32x32_i8 per wave, two workgroups of four waves per CU, timed warm between two HIP events -> int8 MACs/s. */
 int cph_debug_mfma_i8_rate(cph_index* h, uint64_t iters, double* macs_per_s);
 
+/* ---- K-means over the resident rows ----------------------------------------------------------------------------------------
+ * Lloyd's iteration over the LIVE stored rows of a finalized handle (graph rows and the tail of cph_add, minus the removed
+ * rows), squared L2 over the stored coordinates (cosine: the normalised rows; the centroids are plain means in that space
+ * and are not renormalised).  n_clusters = k in [1, min(live rows, 16384)], iters in [0, 65536].
+ * Start: init [k][cph_dim] (finite rows; the host form checks, the device form takes them as they are) or init_ids [k]
+ * (host memory in both forms: live internal ids, whose stored rows the device gathers); exactly one of the two.
+ * Every iteration assigns, then updates; a last assignment follows the last update, so assign and dist refer to the
+ * returned centroids (iters == 0 only assigns).
+ *   assignment  row x -> the centroid c with the smallest (d bits, c), d = the bits cph_exact_l2 returns for query =
+ *               centroid c and id = x; ties go to the lowest c.  The matrix cores find it for every row they can certify
+ *               (csrc/device_kmeans.h: the bound of the matrix engine at k = 1), the vector arithmetic answers the rest:
+ *               the result never depends on which of the two served a row.
+ *   update      centroid c -> the mean of its members: a stable counting sort of the live ids by cluster, then per
+ *               coordinate four sequential partial sums over the members ascending by id, combined in fixed order, and one
+ *               division (csrc/host_kmeans.h: kmeans_mean_host).  No floating-point atomics: two calls return the same
+ *               bytes.  A cluster without members keeps its centroid and has count 0.
+ * Outputs: centroids [k][cph_dim]; assign [size] int32 in internal ids, -1 for a removed row; dist [size], FLT_MAX for a
+ * removed row; counts [k], the members under the returned assignment; moved [iters] (may be NULL when iters == 0),
+ * moved[i] = rows whose assignment in iteration i differs from the one before (iteration 0: every live row).  There is no
+ * early stop and no host round trip per iteration: the call is enqueued on one stream, cph_kmeans waits once for its
+ * outputs, cph_kmeans_device (everything but init_ids in device memory) only enqueues on `stream`.
+ * CPH_INVALID_ARGUMENT, nothing launched: a handle that is not finalized, the inner-product metric (its rows carry a
+ * coordinate that is not the caller's), k or iters out of range, init and init_ids both or neither, an init row that is
+ * not finite (host form), an init id out of range or removed, a NULL output.  Allowed on a borrowed replica or part handle.
+ * A handle that never calls cph_kmeans allocates and launches nothing for it.
+ * cph_kmeans_stats: out[2] = {assignment passes of the last call, rows its matrix kernels left to the vector kernel,
+ * summed over the passes}; waits for that call.  cph_debug_time_kmeans / cph_debug_last_kmeans_us: while on, the matrix
+ * kernel of a call's last assignment pass runs between two HIP events. */
+int cph_kmeans(cph_index* h, uint64_t n_clusters, int64_t iters, const float* init, const uint32_t* init_ids, float* centroids,
+               int32_t* assign, float* dist, uint64_t* counts, int64_t* moved);
+int cph_kmeans_device(cph_index* h, uint64_t n_clusters, int64_t iters, const float* d_init, const uint32_t* init_ids, float* d_centroids,
+                      int32_t* d_assign, float* d_dist, uint64_t* d_counts, int64_t* d_moved, void* stream);
+int cph_kmeans_stats(cph_index* h, uint64_t out[2]);
+int cph_debug_time_kmeans(cph_index* h, int on);
+int cph_debug_last_kmeans_us(cph_index* h, double* us);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2418,6 +2418,104 @@ class CPIndex:
         _lib.check(_lib.lib().cph_tail_count(self._h, C.byref(t)))
         return t.value
 
+    # -- k-means over the stored rows (not in the reference) -------------------------------------
+    MAX_KMEANS_CLUSTERS = 16384
+
+    def _kmeans_args(self, n_clusters, iters, init, seed):
+        """The checks of kmeans / kmeans_device, before anything is launched -> (k, iters, init float32 [k, dim] or
+        None, ids uint32 [k] or None)."""
+        self._no_parts("kmeans")
+        if self._metric == "ip":
+            raise ValueError('kmeans is not available under metric="ip": the stored rows carry one coordinate more than the caller\'s')
+        if not self.is_finalized:
+            raise ValueError("kmeans clusters the rows of a finalized index: finalize or load it first")
+        for v, what in ((n_clusters, "n_clusters"), (iters, "iters")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{what} must be an integer")
+        k, iters, live = int(n_clusters), int(iters), self.live_count
+        if not 1 <= k <= min(live, self.MAX_KMEANS_CLUSTERS):
+            raise ValueError(f"n_clusters must lie in [1, min(live rows, {self.MAX_KMEANS_CLUSTERS})]: the index holds {live} live rows")
+        if not 0 <= iters <= 65536:
+            raise ValueError("iters must lie in [0, 65536]")
+        if init is not None:
+            c0 = _as_f32(init.detach().cpu().numpy() if hasattr(init, "detach") else init)
+            if c0.shape != (k, self._dim):
+                raise ValueError(f"init must be a float array of shape ({k}, {self._dim})")
+            if not np.isfinite(c0).all():
+                raise ValueError("init rows must be finite")
+            return k, iters, c0, None
+        n = self.size
+        ids = np.arange(n) if live == n else np.flatnonzero(~self.removed_mask(ids="internal"))
+        picked = np.random.default_rng(seed).choice(ids, size=k, replace=False)
+        return k, iters, None, np.ascontiguousarray(picked, np.uint32)
+
+    def kmeans(self, n_clusters, iters=10, init=None, seed=0):
+        """Lloyd's k-means over the LIVE stored rows (graph rows and the tail of add(), minus the removed rows), on the
+        device: (centroids float32 [k, dim], assign int32 [size], dist float32 [size], counts int64 [k], moved int64
+        [iters]).  The metric is squared L2 over the stored coordinates; metric="cosine": the stored rows are
+        x / (sqrt(2) |x|), the centroids are plain means in that space and are NOT renormalised.
+        Every iteration assigns each row to its nearest centroid, then moves every centroid to the mean of its members;
+        a last assignment follows the last update, so `assign` (internal id order, -1 for a removed row), `dist` (the
+        bytes of exact_l2(centroid, id) for the row's centroid; FLT_MAX for a removed row) and `counts` refer to the
+        RETURNED centroids.  iters=0 only assigns.  moved[i]: rows whose assignment in iteration i differs from the one
+        before (moved[0]: every live row); there is no early stop and the call waits once, for its outputs.
+        The assignment is the argmin of exact_l2 over the centroids, ties to the lowest centroid: the matrix cores serve
+        every row they can certify, the vector arithmetic the rest.  The update sums a cluster's members in id order in a
+        fixed shape and uses no floating-point atomics, so two calls return the same bytes.  A cluster without members
+        keeps its centroid and has count 0.
+        init: a float array [k, dim] of finite rows (in the stored space), or None: k distinct live internal ids drawn
+        with np.random.default_rng(seed).choice over the sorted live ids, whose stored rows the device gathers.
+        1 <= n_clusters <= min(live_count, MAX_KMEANS_CLUSTERS), 0 <= iters <= 65536; metric="ip" and a partitioned index
+        (use part(i).kmeans) raise ValueError, like every bad argument, before anything is launched.  A replicated
+        index runs on its first replica."""
+        k, iters, c0, ids = self._kmeans_args(n_clusters, iters, init, seed)
+        n = self.size
+        cent, assign, dist = np.empty((k, self._dim), np.float32), np.empty(n, np.int32), np.empty(n, np.float32)
+        counts, moved = np.empty(k, np.uint64), np.empty(iters, np.int64)
+        _lib.check(_lib.lib().cph_kmeans(self._h, k, iters, None if c0 is None else c0.ctypes.data,
+                                         None if ids is None else ids.ctypes.data, cent.ctypes.data, assign.ctypes.data,
+                                         dist.ctypes.data, counts.ctypes.data, moved.ctypes.data if iters else None))
+        return cent, assign, dist, counts.view(np.int64), moved
+
+    def kmeans_device(self, n_clusters, iters=10, init=None, seed=0, stream=None):
+        """kmeans with its five outputs as torch tensors on this index' device (a replicated index: its first device),
+        enqueued on `stream` (default: torch's current stream) without waiting: the tensors are valid in stream order.
+        init: as in kmeans, or a float32 tensor; it is checked on the host (a device tensor is copied back for that)."""
+        import torch
+        k, iters, c0, ids = self._kmeans_args(n_clusters, iters, init, seed)
+        n, dev = self.size, torch.device("cuda", self._device)
+        with torch.cuda.device(dev):
+            d_init = None if c0 is None else torch.from_numpy(c0).to(dev)
+            cent = torch.empty((k, self._dim), dtype=torch.float32, device=dev)
+            assign = torch.empty(n, dtype=torch.int32, device=dev)
+            dist = torch.empty(n, dtype=torch.float32, device=dev)
+            counts = torch.empty(k, dtype=torch.int64, device=dev)
+            moved = torch.empty(iters, dtype=torch.int64, device=dev)
+            fresh = [cent, assign, dist, counts, moved] + ([] if d_init is None else [d_init])
+            st, _ = self._search_stream(stream, cent, fresh)
+        _lib.check(_lib.lib().cph_kmeans_device(self._h, k, iters, None if d_init is None else d_init.data_ptr(),
+                                                None if ids is None else ids.ctypes.data, cent.data_ptr(), assign.data_ptr(),
+                                                dist.data_ptr(), counts.data_ptr(), moved.data_ptr() if iters else None, st))
+        return cent, assign, dist, counts, moved
+
+    def kmeans_stats(self):
+        """(assignment passes, rows the matrix kernels left to the vector kernel, summed over the passes) of the last
+        kmeans call on the first replica; waits for it."""
+        out = (C.c_uint64 * 2)()
+        _lib.check(_lib.lib().cph_kmeans_stats(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def time_kmeans(self, on=True):
+        """Debug hook of the measurement script: while on, the matrix kernel of the last assignment pass of every kmeans
+        call is bracketed by HIP events (last_kmeans_us).  Off by default."""
+        _lib.check(_lib.lib().cph_debug_time_kmeans(self._h, int(bool(on))))
+
+    def last_kmeans_us(self):
+        """Device time (HIP events, microseconds) of that kernel in the last kmeans call made under time_kmeans()."""
+        us = C.c_double(0)
+        _lib.check(_lib.lib().cph_debug_last_kmeans_us(self._h, C.byref(us)))
+        return us.value
+
     # -- persistence ------------------------------------------------------------------------
     def save(self, path):
         """Reference-format (v2) file.  metric="cosine": refused (ValueError) -- the format cannot carry the metric and a

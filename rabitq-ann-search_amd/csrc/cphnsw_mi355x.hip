@@ -54,6 +54,7 @@
 #include "device_rescore_i8_all.h"
 #include "device_normalize.h"
 #include "device_ip.h"
+#include "device_kmeans.h"
 #include "host_index.h"
 #include "host_parallel.h"
 #include "host_knn.h"
@@ -268,7 +269,8 @@ constexpr uint64_t kSmallBatch = 32;        // batches up to this size take the 
 // rescoring kernel of cph_search_rescored* (device_rescore.h).  kPassFused: the scan kernel of fused search alone, bracketed the
 // same way.  kPassMaxsimAll: the bounds kernel of the last chunk of an exhaustive maxsim search (device_maxsim_all.h).
 // kPassRescoredAll: the scan kernel of the last launch of an exhaustive rescored search (device_rescore_i8_all.h).
-enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassMaxsimAll, kPassRescoredAll, kPassUntimed, kPassKinds };
+// kPassKmeans: the matrix kernel of the last assignment pass of a cph_kmeans call (device_kmeans.h).
+enum PassKind { kPassGrouped, kPassDiverse, kPassMaxsim, kPassLabels, kPassMaxsimRescore, kPassRescored, kPassFused, kPassTags, kPassFacets, kPassMaxsimAll, kPassRescoredAll, kPassKmeans, kPassUntimed, kPassKinds };
 
 // The facet dictionary of one column (cph_facet_*; device_facets.h): its distinct values ascending, on both sides, and one
 // 32-bit code per row -- per CSR entry for a tag column -- on the device.  Made on first use, dropped when the column changes.
@@ -322,6 +324,21 @@ struct EffDeleter {
     }
 };
 static std::atomic<uint64_t> g_removed_epoch{0};
+
+// The device buffers of cph_kmeans (device_kmeans.h), made on the first call and only ever grown; `ev` follows the last
+// kernel of the last call, the next call's stream waits for it.  passes / uncertain: what the last call enqueued, and (once
+// it has been waited for) how many rows its matrix kernels left to the vector kernel (cph_kmeans_stats).
+struct KmeansScratch {
+    DevBuf<float> cent, cnorm, init, o_cent, o_dist;
+    DevBuf<uint32_t> cn_max, unc_ids, unc_counts, hist, sizes, starts, order;
+    DevBuf<int32_t> assign, o_assign;
+    DevBuf<unsigned long long> o_counts, o_moved;
+    StagedTable ids;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+    uint32_t passes = 0;
+    ~KmeansScratch() { if (ev) (void)hipEventDestroy(ev); }
+};
 
 struct cph_index {
     // dim: the width of the rows the index stores and every kernel reads; dim_in: the width of the caller's rows and
@@ -392,6 +409,7 @@ struct cph_index {
     DevBuf<uint32_t> d_bn_max;
     uint64_t bn_epoch = ~0ull, bn_rows = 0;
     hipEvent_t bn_ev = nullptr;
+    std::unique_ptr<KmeansScratch> km; // cph_kmeans: nothing before the first call
     uint64_t exact_threshold = 0;      // cph_set_exact_threshold: filtered batches with at most this many allowed ids are scanned exactly (0: never)
     // removed rows (cph_remove): R as a bitmap over internal ids, resident; its host copy and count are host.removed /
     // host.n_removed (what save_native writes).  rm_epoch names this state of R (g_removed_epoch); live = ~R as a filter,
@@ -697,6 +715,7 @@ void quiesce(cph_index* h) {
         if (s.used && s.ev_done) HIP_CHECK(hipEventSynchronize(s.ev_done));
     for (auto& gs : h->rerank_scratch)           // (the re-rank pass runs behind its batch's ev_done)
         if (gs.rows.used) HIP_CHECK(hipEventSynchronize(gs.rows.ev));
+    if (h->km && h->km->used) HIP_CHECK(hipEventSynchronize(h->km->ev));
 }
 
 // ---- pass timers (cph_debug_time_*, cph_debug_last_*_us) --------------------------------------------------------------------
@@ -712,6 +731,7 @@ constexpr const char* kNoTimedPass[kPassKinds] = {
     "no timed facet pass has run on this handle (cph_debug_time_facets)",
     "no timed exhaustive maxsim search has run on this handle (cph_debug_time_maxsim_all)",
     "no timed exhaustive rescored search has run on this handle (cph_debug_time_rescored_all)",
+    "no timed k-means call has run on this handle (cph_debug_time_kmeans)",
     "this pass is not timed",
 };
 
@@ -2241,7 +2261,7 @@ static inline uint64_t now_ns() { return 0; }
 extern "C" {
 
 const char* cph_last_error(void) { return g_err.c_str(); }
-int cph_version(void) { return 121; }
+int cph_version(void) { return 122; }
 
 int cph_create(uint64_t dim, uint64_t bits, int device, cph_index** out) {
     return guarded([&] {
@@ -2302,6 +2322,7 @@ static void destroy_index(cph_index* h) {
         if (s.pin_io) (void)hipHostFree(s.pin_io);
     }
     if (h->bn_ev) (void)hipEventDestroy(h->bn_ev);
+    if (h->km && h->km->used) (void)hipEventSynchronize(h->km->ev);
 #ifdef CPH_SEARCH_TRACE
     if (g_tr[0]) fprintf(stderr, "[search trace] groups=%llu callers=%llu per group: mutex wait %.1f us, enqueue %.1f us; per caller: own-query wait %.1f us\n",
                          (unsigned long long)g_tr[0], (unsigned long long)g_tr[1], g_tr[2] / 1e3 / g_tr[0], g_tr[3] / 1e3 / g_tr[0], g_tr[4] / 1e3 / g_tr[1]);
@@ -9228,6 +9249,170 @@ int cph_host_ip_epilogue(const int64_t* ids, float* dist, uint64_t n, uint64_t k
         check_ip_epilogue_args(ids, dist, n, k, c);
         ip_epilogue_host(ids, dist, n, k, c);
     });
+}
+
+}  // extern "C"
+
+// ---- k-means over the resident rows (cph_kmeans; device_kmeans.h) ----------------------------------------------------------------
+namespace {
+
+constexpr int64_t kKmeansMaxIters = 65536;
+
+struct KmeansOuts {
+    float* cent;                 // [k][dim]
+    int32_t* assign;             // [size]
+    float* dist;                 // [size]
+    uint64_t* counts;            // [k]
+    int64_t* moved;              // [iters]
+    bool all(int64_t iters) const { return cent && assign && dist && counts && (moved || iters == 0); }
+};
+
+// Every refusal of both forms, before anything is allocated or launched.  The handle is locked.
+void kmeans_check(const cph_index* h, uint64_t k, int64_t iters, const float* init, const uint32_t* init_ids, const KmeansOuts& o) {
+    if (!h->finalized) throw InvalidArg("kmeans clusters the rows of a finalized index: finalize or load it first");
+    if (h->metric == CPH_METRIC_IP)
+        throw InvalidArg("kmeans is not available under the inner-product (ip) metric: the stored rows carry a coordinate that is not the caller's");
+    const uint64_t n = h->size(), live = n - h->host.n_removed;
+    if (n > kMxMaxCandidates) throw InvalidArg("kmeans takes fewer than 2^32 - 128 rows");
+    if (k < 1 || k > std::min<uint64_t>(live, kKmeansMaxClusters))
+        throw InvalidArg("n_clusters must lie in [1, min(live rows, " + std::to_string(kKmeansMaxClusters) + ")]: the index holds " +
+                         std::to_string(live) + " live rows");
+    if (iters < 0 || iters > kKmeansMaxIters) throw InvalidArg("iters must lie in [0, " + std::to_string(kKmeansMaxIters) + "]");
+    if ((init != nullptr) == (init_ids != nullptr)) throw InvalidArg("kmeans takes either init rows or init ids");
+    if (!o.all(iters)) throw InvalidArg("null argument");
+    const std::vector<uint32_t>& rm = h->host.removed;
+    for (uint64_t c = 0; init_ids && c < k; ++c) {
+        const uint32_t id = init_ids[c];
+        if (id >= n) throw InvalidArg("init id out of range");
+        if (h->host.n_removed && (id >> 5) < rm.size() && ((rm[id >> 5] >> (id & 31)) & 1u)) throw InvalidArg("init id names a removed row");
+    }
+}
+
+// Enqueues the whole call on `st`: d_init [k][dim] in device memory or init_ids [k] on the host; the outputs in device
+// memory.  Nothing here waits for a kernel (a growing scratch waits for the call before).
+void kmeans_enqueue(cph_index* h, uint32_t k, uint32_t iters, const float* d_init, const uint32_t* init_ids, const KmeansOuts& o, hipStream_t st) {
+    if (!h->km) h->km.reset(new KmeansScratch());
+    KmeansScratch& km = *h->km;
+    const uint32_t n = (uint32_t)h->size(), D = h->L.D, dim = (uint32_t)h->dim, passes = iters + 1;
+    const KmeansSegments sg = kmeans_segments(n);
+    Reserve r{km.ev, km.used};
+    KmeansBuffers b{};
+    b.cent = r(km.cent, (size_t)(k + kExactQT) * D);
+    b.cnorm = r(km.cnorm, k + kExactQT);
+    b.cn_max = r(km.cn_max, 1);
+    b.assign[0] = r(km.assign, (size_t)2 * n);
+    b.assign[1] = b.assign[0] + n;
+    b.unc_ids = r(km.unc_ids, n);
+    b.unc_counts = r(km.unc_counts, passes);
+    if (iters) {
+        b.hist = r(km.hist, (size_t)sg.count * k);
+        b.sizes = r(km.sizes, k);
+        b.starts = r(km.starts, k + 1);
+        b.order = r(km.order, n);
+    }
+    if (!km.ev) HIP_CHECK(hipEventCreateWithFlags(&km.ev, hipEventDisableTiming));
+    if (km.used) HIP_CHECK(hipStreamWaitEvent(st, km.ev, 0));         // (the call before may run on another stream)
+    const uint32_t* d_ids = nullptr;
+    if (init_ids) {
+        std::memcpy(km.ids.begin((size_t)k * 4, r), init_ids, (size_t)k * 4);
+        d_ids = reinterpret_cast<const uint32_t*>(km.ids.send((size_t)k * 4, st));
+    }
+    const uint32_t* removed = h->host.n_removed ? h->d_removed.p : nullptr;
+    unsigned long long* moved = reinterpret_cast<unsigned long long*>(o.moved);
+    unsigned long long* counts = reinterpret_cast<unsigned long long*>(o.counts);
+    const uint32_t cells = std::max({n, passes, k});
+    hipLaunchKernelGGL(kmeans_reset_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, b.assign[1], n, b.unc_counts, passes, moved, iters, counts, k);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(kmeans_seed_kernel, dim3(k + kExactQT), dim3(64), 0, st, d_init, d_ids, (const float*)h->d_raw.p, k, dim, D, b.cent);
+    HIP_CHECK(hipGetLastError());
+    cph_index::PassTimer& t = h->pass_timer[kPassKmeans];
+    t.timed = false;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        int32_t* cur = b.assign[pass & 1];
+        const bool timed = t.on && pass + 1 == passes;                // (the last pass' stays)
+        kmeans_assign(h->d_raw.p, h->d_norm.p, removed, n, k, D, b, cur, pass, timed ? t.ev0 : nullptr, timed ? t.ev1 : nullptr, st);
+        if (pass < iters) kmeans_update(h->d_raw.p, n, k, D, b, cur, b.assign[(pass & 1) ^ 1], moved + pass, st);
+    }
+    t.timed = t.on;
+    // (the last update is followed by a pass of its own: the norms in b.cnorm are those of the returned centroids)
+    hipLaunchKernelGGL(kmeans_final_kernel, dim3((n + 31) / 32), dim3(256), 0, st, (const float*)h->d_raw.p, (const float*)h->d_norm.p,
+                       (const float*)b.cent, (const float*)b.cnorm, n, D, (const int32_t*)b.assign[iters & 1], o.assign, o.dist, counts);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(kmeans_export_kernel, dim3((uint32_t)(((uint64_t)k * dim + 255) / 256)), dim3(256), 0, st, (const float*)b.cent, k, dim, D, o.cent);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(km.ev, st));
+    km.used = true;
+    km.passes = passes;
+}
+
+// cph_kmeans (stream == null: init and the outputs on the host, the call waits once) and cph_kmeans_device.
+void kmeans_call(cph_index* h, uint64_t k, int64_t iters, const float* init, const uint32_t* init_ids, const KmeansOuts& o, void* const* stream) {
+    if (!h) throw InvalidArg("null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    kmeans_check(h, k, iters, init, init_ids, o);
+    const uint64_t n = h->size(), dim = h->dim;
+    if (!stream && init)
+        for (uint64_t e = 0; e < k * dim; ++e)
+            if (!(std::fabs(init[e]) <= FLT_MAX)) throw InvalidArg("init row " + std::to_string(e / dim) + " is not finite");
+    h->use_device();
+    if (stream) return kmeans_enqueue(h, (uint32_t)k, (uint32_t)iters, init, init_ids, o, reinterpret_cast<hipStream_t>(*stream));
+    if (!h->km) h->km.reset(new KmeansScratch());
+    KmeansScratch& km = *h->km;
+    Reserve r{km.ev, km.used};
+    const KmeansOuts dev{r(km.o_cent, k * dim), r(km.o_assign, n), r(km.o_dist, n), reinterpret_cast<uint64_t*>(r(km.o_counts, k)),
+                         reinterpret_cast<int64_t*>(r(km.o_moved, std::max<int64_t>(iters, 1)))};
+    hipStream_t st = own_stream(h);
+    const float* d_init = nullptr;
+    if (init) {
+        d_init = r(km.init, k * dim);
+        if (km.used) HIP_CHECK(hipStreamWaitEvent(st, km.ev, 0));     // (a call in flight on another stream may still read it)
+        HIP_CHECK(hipMemcpyAsync(km.init.p, init, k * dim * 4, hipMemcpyHostToDevice, st));
+    }
+    kmeans_enqueue(h, (uint32_t)k, (uint32_t)iters, d_init, init_ids, dev, st);
+    HIP_CHECK(hipMemcpyAsync(o.cent, dev.cent, k * dim * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.assign, dev.assign, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.dist, dev.dist, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(o.counts, dev.counts, k * 8, hipMemcpyDeviceToHost, st));
+    if (iters) HIP_CHECK(hipMemcpyAsync(o.moved, dev.moved, (size_t)iters * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(km.ev, st));                             // (the copies read the scratch too)
+    HIP_CHECK(hipStreamSynchronize(st));                              // the one wait of the call
+}
+
+}  // namespace
+
+extern "C" {
+
+int cph_kmeans(cph_index* h, uint64_t n_clusters, int64_t iters, const float* init, const uint32_t* init_ids, float* centroids,
+               int32_t* assign, float* dist, uint64_t* counts, int64_t* moved) {
+    return guarded([&] { kmeans_call(h, n_clusters, iters, init, init_ids, {centroids, assign, dist, counts, moved}, nullptr); });
+}
+
+int cph_kmeans_device(cph_index* h, uint64_t n_clusters, int64_t iters, const float* d_init, const uint32_t* init_ids, float* d_centroids,
+                      int32_t* d_assign, float* d_dist, uint64_t* d_counts, int64_t* d_moved, void* stream) {
+    return guarded([&] { kmeans_call(h, n_clusters, iters, d_init, init_ids, {d_centroids, d_assign, d_dist, d_counts, d_moved}, &stream); });
+}
+
+int cph_kmeans_stats(cph_index* h, uint64_t out[2]) {
+    return guarded([&] {
+        if (!h || !out) throw InvalidArg("null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->km || !h->km->used) throw InvalidArg("no k-means call has run on this handle (cph_kmeans)");
+        h->use_device();
+        HIP_CHECK(hipEventSynchronize(h->km->ev));
+        std::vector<uint32_t> unc(h->km->passes);
+        HIP_CHECK(hipMemcpy(unc.data(), h->km->unc_counts.p, unc.size() * 4, hipMemcpyDeviceToHost));
+        out[0] = unc.size();
+        out[1] = 0;
+        for (uint32_t u : unc) out[1] += u;
+    });
+}
+
+int cph_debug_time_kmeans(cph_index* h, int on) {
+    return guarded([&] { pass_timer_switch(h, kPassKmeans, on != 0); });
+}
+
+int cph_debug_last_kmeans_us(cph_index* h, double* us) {
+    return guarded([&] { pass_timer_us(h, kPassKmeans, us); });
 }
 
 }  // extern "C"
